@@ -133,6 +133,37 @@ def replica_digest(sess):
     return int.from_bytes(h.digest(), "little")
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, sess):
+    """--dump-outputs DIR: what the timed path (GibbsSession.step) leaves its caller after the last timed step -- the model
+    sample (w0, w, V, cutpoints), the hyper-parameters and the residual -- as DIR/<name>.npy in float64, so that two builds can
+    be compared output for output. At most DUMP_BYTES in all: when the arrays are larger, each array over 1 MB keeps the same
+    fraction of its rows, a fixed seeded sample, and the kept row indices are written beside it as <name>_rows.npy."""
+    fm, hy = sess.fm, sess.hyper
+    arrays = {"w0": fm.w0, "w": fm.w, "V": fm.V, "alpha": hy.alpha, "mu_w": hy.mu_w, "lambda_w": hy.lambda_w, "mu_V": hy.mu_V,
+              "lambda_V": hy.lambda_V, "residual": sess.residual()}
+    for i, c in enumerate(fm.cutpoints):
+        arrays["cutpoints_%d" % i] = c
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES:
+        big = [k for k, v in arrays.items() if v.nbytes > (1 << 20)]
+        small = total - sum(arrays[k].nbytes for k in big)
+        per_row = sum(arrays[k].nbytes + 8 * arrays[k].shape[0] for k in big)  # (8 bytes of row index per kept row)
+        frac = (DUMP_BYTES - small - 4096 * (len(arrays) + len(big))) / per_row  # (4096: room for the .npy headers)
+        rng = np.random.default_rng(0)
+        for k in big:
+            a = arrays[k]
+            rows = np.sort(rng.choice(a.shape[0], size=int(a.shape[0] * frac), replace=False))
+            arrays[k] = a[rows]
+            arrays[k + "_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def self_launch(n_gpus):
     """`python bench.py --gpus N` without a launcher: run the N ranks under torch.distributed.run (one process per GPU,
     rendezvous on 127.0.0.1) and pass rank 0's single JSON line through. Returns the exit code."""
@@ -232,6 +263,8 @@ def main():
     ap.add_argument("--task", default=None, help="regression | classification | ordered: the config's design with another task's target")
     ap.add_argument("--latent", default=None, help="latent draws of classification / ordered probit: exact (the reference's own stream, "
                     "draw for draw, evaluated on the device) | host (the same on the host) | philox (per-row streams)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last timed step to "
+                    "DIR/<name>.npy (float64, at most 64 MB: a fixed seeded sample of larger arrays); N > 1: rank 0's")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a.gpus))
@@ -433,6 +466,8 @@ def main():
     if live_timing:
         sess.timing_enable(False)
         sess.timing_select("")
+    if a.dump_outputs and rank == 0:  # (before the value_long loop below steps the chain further)
+        dump_outputs(a.dump_outputs, sess)
     calls = (sess.comm_stats()[0] - calls0) if sharded else 0
     doubles = (sess.comm_stats()[1] - doubles0) if sharded else 0
     per_rank = None
