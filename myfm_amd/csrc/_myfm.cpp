@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "mfm_env.hpp"
 #include "mfm_hostnormals.hpp"
 #include "mfm_mtjump.hpp"
 #include "myfm_hip.h"
@@ -166,14 +167,14 @@ struct FMLearningConfig {
   // trainer's std::mt19937 stays on the host for every variate of the fit; 2 "exact" = the generator lives on the device as for
   // regression and the latent draws consume ITS stream in the reference's order, evaluated in parallel on the device
   // (csrc/mfm_latent.hpp: coalescing flows) -- the same chain as mode 1 draw for draw. set_exact_latent_draws(true) selects
-  // mode 2 (MYFM_AMD_EXACT_ON_HOST=1: mode 1).
+  // mode 2.
   int latent_mode = 2;
   // latent_order (ConfigBuilder.set_latent_row_order; classification, modes "exact" / "host"): the rows in the order in which the
   // reference draws their latent z -- entry i = the row of THIS table that is the caller's row i. Empty: the table's own order.
   // (MyFM*.fit sorts the rows for the device paths and passes the inverse permutation here; ordered probit carries the same
   // information in its cutpoint groups' row lists.)
   vector<int64_t> latent_order;
-  bool host_rng() const { return latent_mode == 1 || std::getenv("MYFM_AMD_HOST_RNG") != nullptr; }
+  bool host_rng() const { return latent_mode == 1 || mfm::env_flag("MYFM_AMD_HOST_RNG"); }
   bool exact_dev() const { return latent_mode == 2 && !host_rng() && task_type != TaskType::REGRESSION; }
 
   // FMLearningConfig.hpp:17-57
@@ -243,7 +244,7 @@ struct ConfigBuilder {
     FMLearningConfig c(alpha_0, beta_0, gamma_0, mu_0, reg_0, task_type, nu_oprobit, fit_w0, fit_linear, group_index, n_iter,
                        n_kept_samples, cutpoint_scale, cutpoint_groups);
     c.exact_latent_draws = exact_latent_draws;
-    c.latent_mode = latent_mode >= 0 ? latent_mode : (exact_latent_draws ? (std::getenv("MYFM_AMD_EXACT_ON_HOST") ? 1 : 2) : 0);
+    c.latent_mode = latent_mode >= 0 ? latent_mode : (exact_latent_draws ? 2 : 0);
     c.latent_order = latent_order;
     return c;
   }
@@ -325,7 +326,7 @@ size_t check_row_consistency_return_column(const M &X, const Relations &relation
 // The GPU this process works on: MYFM_AMD_DEVICE (one process per GPU sets it to its local rank), default 0.
 // Training contexts and prediction designs are created on the same device.
 int selected_device() {
-  if (const char *e = std::getenv("MYFM_AMD_DEVICE")) return std::atoi(e);
+  if (mfm::env_flag("MYFM_AMD_DEVICE")) return mfm::env_int("MYFM_AMD_DEVICE", 0);
   return 0;
 }
 
@@ -460,7 +461,7 @@ struct FM {
       }
       return true;
     }();
-    if (std::getenv("MYFM_AMD_STD_INIT") || !filler_ok) {  // the plain loop (tests hold the bulk filler against it)
+    if (!filler_ok) {  // the plain loop
       std::normal_distribution<Real> nd;
       V.resize(nV);
       for (auto &v : V) v = nd(gen) * init_std;
@@ -1036,7 +1037,7 @@ struct SetupLap {
   const char *who;
   bool on;
   std::chrono::steady_clock::time_point t;
-  explicit SetupLap(const char *w) : who(w), on(std::getenv("MFM_SETUP_TIMING") != nullptr), t(std::chrono::steady_clock::now()) {}
+  explicit SetupLap(const char *w) : who(w), on(mfm::env_flag("MFM_SETUP_TIMING")), t(std::chrono::steady_clock::now()) {}
   void operator()(const char *what) {
     if (!on) return;
     const auto n = std::chrono::steady_clock::now();
@@ -1228,7 +1229,7 @@ struct FMTrainer {
     if (!cfg.latent_order.empty() && cfg.task_type == TaskType::CLASSIFICATION)
       ck(ctx, mfm_set_latent_order(ctx, cfg.latent_order.data(), (int64_t)cfg.latent_order.size()));
     // regression: update_e recomputes the residual after every update_V (:494), nothing reads it in between
-    if (cfg.task_type == TaskType::REGRESSION && !std::getenv("MYFM_AMD_KEEP_RESIDUAL")) ck(ctx, mfm_set_residual_policy(ctx, 1));
+    if (cfg.task_type == TaskType::REGRESSION && !mfm::env_flag("MYFM_AMD_KEEP_RESIDUAL")) ck(ctx, mfm_set_residual_policy(ctx, 1));
   }
   void upload(const FM &fm) { ck(ctx, mfm_set_state(ctx, fm.w0, fm.w.data(), fm.V.data())); }
   void download(FM &fm) {
@@ -1366,7 +1367,7 @@ struct FMTrainer {
   // ---- one Gibbs iteration, BaseFMTrainer.hpp:135-152 ----
   // MYFM_AMD_HOST_TIMELINE=1: where the host thread spends an iteration (mean microseconds per stage, every 100 iterations)
   struct HostTimeline {
-    bool on = std::getenv("MYFM_AMD_HOST_TIMELINE") != nullptr;
+    bool on = mfm::env_flag("MYFM_AMD_HOST_TIMELINE");
     std::chrono::steady_clock::time_point t;
     double acc[8] = {0};
     int n = 0;
@@ -1399,10 +1400,8 @@ struct FMTrainer {
     // shorten the iteration (config 3: 335-338 against 338 it/s). What fills the 0.29 ms between two launches is the random
     // stream, not the host: the evaluation of a set's 2.6 M sweep normals runs starved beside the launch on the CUs it leaves free,
     // and the set's single-workgroup draw kernels (0.26 ms in a row) then take the whole gap.
-    static const bool host_hypers = [] {  // (default since round 6: the device form; MYFM_AMD_DEVICE_HYPERS=0 keeps the host in the loop)
-      const char *e = std::getenv("MYFM_AMD_DEVICE_HYPERS");
-      return e != nullptr && std::atoi(e) == 0;
-    }();
+    // (default since round 6: the device form; MYFM_AMD_DEVICE_HYPERS=0 keeps the host in the loop)
+    static const bool host_hypers = mfm::env_flag("MYFM_AMD_DEVICE_HYPERS") && mfm::env_int("MYFM_AMD_DEVICE_HYPERS", 0) == 0;
     if (!host_hypers && device_rng && cfg.task_type == TaskType::REGRESSION && cfg.fit_linear && dim_all && Kf > 0 && !comm_active() &&
         mfm_regression_iteration_ready(ctx) == 1) {
       mfm_hyper_prior pr;
@@ -1605,7 +1604,7 @@ struct FMTrainer {
     // MYFM_AMD_HOST_SAMPLES=1 or a store that does not fit: plain host copies as before
     std::shared_ptr<DeviceStore> store;
     // (row-sharded fits too: the model is replicated, every rank keeps its own copy of the samples on its device)
-    if (cfg.n_kept_samples > 0 && !std::getenv("MYFM_AMD_HOST_SAMPLES"))
+    if (cfg.n_kept_samples > 0 && !mfm::env_flag("MYFM_AMD_HOST_SAMPLES"))
     {
       store = std::make_shared<DeviceStore>((int64_t)dim_all, fm.n_factors);
       if (mfm_store_reserve(store->st, cfg.n_kept_samples) != MFM_OK) store.reset();  // (does not fit: host copies)

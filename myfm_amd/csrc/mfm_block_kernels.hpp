@@ -565,7 +565,7 @@ struct DevBlock {
     B = hX.rows;
     Db = hX.cols;
     nnz = hX.nnz();
-    const bool tlog = std::getenv("MFM_SETUP_TIMING") != nullptr;
+    const bool tlog = env_flag("MFM_SETUP_TIMING");
     double t_prev = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     auto lap = [&](const char *what) {
       if (!tlog) return;
@@ -575,7 +575,7 @@ struct DevBlock {
     };
     // X_B^T: on the device (a stable sort of the entries by column, one bulk copy back for the planner) unless the block is tiny
     HostCsr Xt;
-    if (nnz >= ((int64_t)1 << 16) && !std::getenv("MFM_HOST_TRANSPOSE")) {
+    if (nnz >= ((int64_t)1 << 16)) {
       X.upload(hX, nullptr);
       Xt = transpose_device(X, s);
     } else {
@@ -590,12 +590,12 @@ struct DevBlock {
     dev_view.n_rows = B;
     dev_view.n_cols = Db;
     dev_view.ell = (int)X.ell_width;
-    plan_V.dev_csc = plan_W.dev_csc = (B > 0 && nnz > 0 && !std::getenv("MFM_HOST_LEVELS")) ? &dev_view : nullptr;
+    plan_V.dev_csc = plan_W.dev_csc = (B > 0 && nnz > 0) ? &dev_view : nullptr;
     plan_V.block_plan = plan_W.block_plan = true;
     plan_V.build(Xt, PBlockV::R_W16, PBlockV::R_WG, coop_capacity<PBlockV>());
     lap("plan_V");
     plan_W.build(Xt, PBlockW::R_W16, PBlockW::R_WG, coop_capacity<PBlockW>(), false, false,
-                 std::getenv("MFM_NO_PLAN_TWIN") ? nullptr : &plan_V);  // (the level schedule of the same matrix: computed once)
+                 &plan_V);  // (the level schedule of the same matrix: computed once)
     lap("plan_W");
     plan_V.dev_csc = plan_W.dev_csc = nullptr;  // (the view lives on this frame)
     // rows of a block row far apart in the table (lists longer than a workgroup handles at once) and a table that fits
@@ -630,12 +630,11 @@ struct DevBlock {
     } else {
       MFM_HIP_CHECK(hipStreamSynchronize(s));
     }
-    stream_unsync = !sorted && B >= 1 && B <= UNSYNC_STREAM_MAX_B && N >= 64 * B && N >= ((int64_t)1 << 20) &&
-                    !std::getenv("MFM_NO_UNSYNC_STREAM");  // (short tables: too few workgroups to stream with)
-    if (const char *e = std::getenv("MFM_UNSYNC_STREAM_FORCE")) stream_unsync = std::atoi(e) != 0 && B >= 1 && B <= UNSYNC_STREAM_MAX_B;
+    stream_unsync = !sorted && B >= 1 && B <= UNSYNC_STREAM_MAX_B && N >= 64 * B && N >= ((int64_t)1 << 20);  // (short tables: too few workgroups to stream with)
+    if (env_flag("MFM_UNSYNC_STREAM_FORCE")) stream_unsync = env_int("MFM_UNSYNC_STREAM_FORCE", 0) != 0 && B >= 1 && B <= UNSYNC_STREAM_MAX_B;
     // too many block rows for the LDS table, lists scattered over a long table: split form
-    split_unsync = !sorted && !stream_unsync && N >= ((int64_t)1 << 20) && !std::getenv("MFM_NO_UNSYNC_SPLIT");
-    if (const char *e = std::getenv("MFM_UNSYNC_SPLIT_FORCE")) split_unsync = std::atoi(e) != 0 && !stream_unsync;
+    split_unsync = !sorted && !stream_unsync && N >= ((int64_t)1 << 20);
+    if (env_flag("MFM_UNSYNC_SPLIT_FORCE")) split_unsync = env_int("MFM_UNSYNC_SPLIT_FORCE", 0) != 0 && !stream_unsync;
     if (lean) stream_unsync = split_unsync = false;
     if (!stream_unsync && !lean && N > 0) {
       // inverse map: the training rows ordered by block row, ascending inside a block row (a stable sort of (block row, t))
@@ -652,7 +651,7 @@ struct DevBlock {
       tmp.alloc(tmp_bytes);
       MFM_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, map.p, keys_out.p, iota.p, inv_rows.p, (int)N, 0, end_bit, s));
       MFM_HIP_CHECK(hipStreamSynchronize(s));
-      if (std::getenv("MFM_PLAN_CHECK") && hmap) {  // tests: the host's counting sort
+      if (env_flag("MFM_PLAN_CHECK") && hmap) {  // tests: the host's counting sort
         std::vector<int32_t> want((size_t)N), got((size_t)N);
         std::vector<int64_t> cur(iptr.begin(), iptr.end() - 1);
         for (int64_t t = 0; t < N; t++) want[cur[hmap[t]]++] = (int32_t)t;
@@ -694,7 +693,7 @@ struct DevBlock {
     bl.alloc_zero((size_t)B, s);
     bs.alloc_zero((size_t)B, s);
     comm_buf.alloc((size_t)std::max<int64_t>(B, 1) * 4);
-    if (!std::getenv("MFM_NO_COMPACT_QB")) qc.alloc_zero((size_t)std::max<int64_t>(B, 1), s);
+    qc.alloc_zero((size_t)std::max<int64_t>(B, 1), s);
     if (stream_unsync) {
       const int64_t step = (int64_t)WG * UNSYNC_R;
       const int64_t steps = (N + step - 1) / step;

@@ -21,16 +21,10 @@ struct CsStream {
   mutable const int32_t *col_group_of = nullptr;  // ... from this group array
 };
 
-static int env_int(const char *name, int dflt) {
-  const char *e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
-
 std::shared_ptr<CsStream> cs_stream_build(const HostCsr &csc, const std::vector<int32_t> &run, CsStreamInfo *info) {
   const auto t0 = std::chrono::steady_clock::now();
   CsParams prm;
   prm.NB = std::max(1, std::min(CS_MAX_NB, env_int("MFM_CS_NB", 32)));
-  prm.RD = std::max(1, std::min(CS_ER, env_int("MFM_CS_RD", 2)));  // (the walker keeps the hot entry lists of CS_ER steps)
   prm.cap = std::max(16, env_int("MFM_CS_CAP", 1 << 20));
   const int cg_forced = env_int("MFM_CS_CG", 0);
   const int lw_max = std::max(2, std::min(CS_MAX_LW, env_int("MFM_CS_LW", CS_MAX_LW)));
@@ -158,7 +152,6 @@ void cs_stream_launch(hipStream_t s, const SweepArgs &a, const CsStream &st, boo
   g.max_exit = I.max_exit;
   g.n_slots = I.n_slots;
   g.ecap = cs_ecap(I.max_hot_col);
-  g.dbg = env_int("MFM_CS_DBG", 0);
   g.cols = st.cols.p;
   g.col_group = st.col_group.p;
   g.cold_ptr = st.cold_ptr.p;
@@ -192,7 +185,7 @@ void cs_stream_launch(hipStream_t s, const SweepArgs &a, const CsStream &st, boo
     g.prof = prof_buf.p;
   }
   // MFM_CS_TRACE=file (with MFM_CB_PROF): raw stamps of every actor and step of the MFM_CS_TRACE_LAUNCH-th launch (default 40)
-  static const char *trace_file = std::getenv("MFM_CS_TRACE");
+  static const char *trace_file = env_str("MFM_CS_TRACE");
   static const long trace_launch = env_int("MFM_CS_TRACE_LAUNCH", 40);
   static long n_launch = 0;
   DevBuf<unsigned long long> trace_buf;

@@ -51,7 +51,6 @@ struct CsSync {  // zeroed before every launch
 struct CsArgs {
   int n_cols, n_steps, Cg, Lw, NB, RD, max_enter, max_exit, n_slots;
   int ecap;  // hot entries of a column at most, rounded up to whole wavefronts
-  int dbg;   // MFM_CS_DBG (experiments): 8 / 16 the walker sees no / at most 64 hot entries per column (wrong results: timing only)
   const int32_t *cols, *col_group;
   const int32_t *cold_ptr, *cold_rc;
   const double *cold_x;
@@ -304,9 +303,7 @@ __global__ __launch_bounds__(CS_NT) void k_cs_stream(SweepArgs a, CsArgs g) {
         if (!have) load_col(C, s, c);
         have = c + 1 < Cg && k + 1 < n;  // the next column of the SAME step: its entries and scalars are requested now
         if (have) load_col(N, s, c + 1);
-        int cnt = __builtin_amdgcn_readfirstlane(C.cnt);
-        if (g.dbg & 8) cnt = 0;              // (timing experiments only, wrong results: no hot entries at all ...
-        if (g.dbg & 16) cnt = min(cnt, 64);  //  ... one round at most)
+        const int cnt = __builtin_amdgcn_readfirstlane(C.cnt);
         double fresh;
         switch ((cnt + WAVE - 1) / WAVE) {
           case 0: fresh = P::template draw<true>(C.S1c, C.S2c, C.old, a.alpha, C.lam, C.mu, C.z); break;

@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "mfm_env.hpp"
 #include "myfm_hip.h"
 
 namespace mfm {
@@ -247,11 +248,11 @@ static __global__ __launch_bounds__(1024) void k_poison_lds(uint32_t word) {
   if (poison_words[(threadIdx.x * 37) % (160 * 256)] == 1u) __builtin_trap();  // (keeps the stores)
 }
 inline bool poison_lds(hipStream_t s, int cls, int line, bool clean = false) {  // MFM_DEBUG_POISON_LDS = a kernel class, or -1 for all;
-  static const bool on = std::getenv("MFM_DEBUG_POISON_LDS") != nullptr;  // MFM_DEBUG_POISON_LINE = one launch site
+  static const bool on = env_flag("MFM_DEBUG_POISON_LDS");  // MFM_DEBUG_POISON_LINE = one launch site
   if (!on) return false;
-  static const int only = std::atoi(std::getenv("MFM_DEBUG_POISON_LDS"));
-  static const int only_line = std::getenv("MFM_DEBUG_POISON_LINE") ? std::atoi(std::getenv("MFM_DEBUG_POISON_LINE")) : -1;
-  if (std::getenv("MFM_DEBUG_POISON_LIST")) {
+  static const int only = env_int("MFM_DEBUG_POISON_LDS", 0);
+  static const int only_line = env_int("MFM_DEBUG_POISON_LINE", -1);
+  if (env_flag("MFM_DEBUG_POISON_LIST")) {
     static std::vector<int> seen;
     if (std::find(seen.begin(), seen.end(), cls * 100000 + line) == seen.end()) {
       seen.push_back(cls * 100000 + line);
@@ -266,7 +267,7 @@ inline bool poison_lds(hipStream_t s, int cls, int line, bool clean = false) {  
     raised.mark();
   }
   static const uint32_t word =
-      std::getenv("MFM_DEBUG_POISON_WORD") ? (uint32_t)std::strtoul(std::getenv("MFM_DEBUG_POISON_WORD"), nullptr, 16) : 0x7ff4deadu;
+      env_flag("MFM_DEBUG_POISON_WORD") ? (uint32_t)std::strtoul(env_str("MFM_DEBUG_POISON_WORD"), nullptr, 16) : 0x7ff4deadu;
   hipLaunchKernelGGL(k_poison_lds, dim3(1024), dim3(1024), 160 * 1024, s, clean ? 0u : word);  // (clean: after the scope)
   return true;
 }

@@ -77,8 +77,8 @@ struct ResidentBudget {
       why = "another context of this process holds the CUs for its persistent sweep";
       return false;
     }
-    if (d.lock_fd < 0 && !std::getenv("MFM_RES_NO_PROCESS_LOCK")) {
-      const char *dir = std::getenv("MFM_LOCK_DIR");
+    if (d.lock_fd < 0 && !env_flag("MFM_RES_NO_PROCESS_LOCK")) {
+      const char *dir = env_str("MFM_LOCK_DIR");
       const std::string path = std::string(dir && *dir ? dir : "/tmp") + "/myfm_amd_resident_" + k + ".lock";
       // The file is shared by every user of the machine: never follow a planted link (O_NOFOLLOW), make it 0666 whatever the
       // creator's umask was, and if it belongs to somebody else and cannot be opened for writing, open it read-only -- flock
@@ -599,8 +599,7 @@ static void score_train(mfm_ctx *c, bool subtract_y) {
   c->e_in_cell = false;
   c->slot_sums_valid = false;
   if (c->main_lazy) {
-    static const bool no_res_score0 = std::getenv("MFM_NO_RES_SCORE") != nullptr || std::getenv("MFM_NO_MF_SCORE") != nullptr;
-    if (subtract_y && c->res.ready && !no_res_score0 && res_score_supported(c->res, c->K)) {
+    if (subtract_y && c->res.ready && res_score_supported(c->res, c->K)) {
       hipStream_t s = c->stream;
       {
         TimedLaunch t(c->timing, s, KC_BUILD_VT, 16.0 * c->D * c->K);
@@ -613,7 +612,7 @@ static void score_train(mfm_ctx *c, bool subtract_y) {
     }
     c->ensure_main_plans();
   }
-  if (c->mf && !std::getenv("MFM_NO_MF_SCORE")) {
+  if (c->mf) {
     // two-field table: scorer on the row tiles of the latent sweep (item rows gathered once per run, not once per row)
     hipStream_t s = c->stream;
     {
@@ -621,8 +620,7 @@ static void score_train(mfm_ctx *c, bool subtract_y) {
       build_vt(s, c->V.p, c->Vt.p, c->D, c->K, c->KS);
     }
     // regression on a table that takes the persistent sweep: e = score - y straight in the sweep's slot order, with its sums
-    static const bool no_res_score = std::getenv("MFM_NO_RES_SCORE") != nullptr;
-    if (subtract_y && c->res.ready && !no_res_score && res_score_supported(c->res, c->K)) {
+    if (subtract_y && c->res.ready && res_score_supported(c->res, c->K)) {
       run_res_score(s, c->timing, c->res, KC_UPDATE_E, c->Vt.p, c->w.p, c->w0, c->K, c->y.p, c->X.nnz, c->w0_dev);
       c->e_in_slots = true;
       c->slot_sums_valid = true;
@@ -636,8 +634,7 @@ static void score_train(mfm_ctx *c, bool subtract_y) {
                                                          subtract_y ? c->y.p : nullptr, c->eq_raw());
     if (done) return;
   }
-  static const bool no_cell_score = std::getenv("MFM_NO_CELL_SCORE") != nullptr;
-  if (c->cell.ready && !no_cell_score) {
+  if (c->cell.ready) {
     // index-tuple design: K / FB passes over (accumulator, index record) with the factor tables in LDS (mfm_cell.hpp)
     hipStream_t s = c->stream;
     {
@@ -839,7 +836,6 @@ struct CodeWarmup {
   std::thread th;
   void start(int device) {
     std::call_once(once, [&]() {
-      if (std::getenv("MFM_NO_WARMUP")) return;
       th = std::thread([device]() {
         hipStream_t st = nullptr;
         if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return;
@@ -1056,7 +1052,7 @@ int mfm_set_groups(mfm_ctx *ctx, const int32_t *group_index, int64_t D, int32_t 
 }
 
 static int64_t res_min_rows(const mfm_ctx *) {
-  return std::getenv("MFM_RES_MIN_ROWS") ? std::atoll(std::getenv("MFM_RES_MIN_ROWS")) : ((int64_t)1 << 20);
+  return env_i64("MFM_RES_MIN_ROWS", (int64_t)1 << 20);
 }
 
 // The persistent sweep's layout (build(plan, workgroups): the device builder of mfm_res_plan.hpp or the host builder) and the
@@ -1065,8 +1061,8 @@ static void plan_resident(mfm_ctx *c, const std::function<void(ResPlan &, int)> 
   int n_cu = 0;
   MFM_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
   const int n_cu_dev = n_cu;
-  if (const char *e = std::getenv("MFM_RES_CUS")) {
-    n_cu = std::max(1, std::min(n_cu, std::atoi(e)));
+  if (env_flag("MFM_RES_CUS")) {
+    n_cu = std::max(1, std::min(n_cu, env_int("MFM_RES_CUS", 0)));
     build(c->res, n_cu);
   } else {
     // one CU per XCD stays free when the rows still fit the others (config 3: 40 323 of 40 959 slots per workgroup): the small
@@ -1104,36 +1100,31 @@ static void plan_resident(mfm_ctx *c, const std::function<void(ResPlan &, int)> 
 
 // Before anything else is planned: does the table take the persistent sweep? (the layout from the device CSR, mfm_res_plan.hpp)
 static void try_resident_first(mfm_ctx *c, const std::function<void(const char *)> &lap) {
-  static const char *const off[] = {"MFM_NO_RESIDENT", "MFM_RES_HOST_PLAN", "MFM_RES_PROF", "MFM_HOST_TRANSPOSE", "MFM_NO_SOA",
-                                    "MFM_NO_FUSED_QBUILD", "MFM_NO_FUSED_NEXT", "MFM_NO_MF", "MFM_NO_FUSED_TWO", "MFM_NO_FUSED_STATS",
-                                    "MFM_HOST_LEVELS", "MFM_NO_SCATTER", "MFM_TILE_BITS"};
-  for (const char *e : off)
-    if (std::getenv(e)) return;
-  if (std::getenv("MFM_QFREE") && std::atoi(std::getenv("MFM_QFREE"))) return;
+  for (const char *e : {"MFM_NO_RESIDENT", "MFM_RES_PROF", "MFM_NO_FUSED_NEXT", "MFM_NO_MF", "MFM_NO_SCATTER", "MFM_TILE_BITS"})
+    if (env_flag(e)) return;
+  if (env_int("MFM_QFREE", 0)) return;
   if (c->comm.active() || !c->hblocks.empty() || !c->hlevels.empty() || !c->X.unit || c->X.ell_width != 2 || c->K < 1 ||
       c->N < res_min_rows(c))
     return;
-  const bool tlog = std::getenv("MFM_SETUP_TIMING") != nullptr;
+  const bool tlog = env_flag("MFM_SETUP_TIMING");
   plan_resident(c, [&](ResPlan &rp, int n_cu) { res_plan_build_device(rp, c->X, &c->hgroup, n_cu, c->stream); }, tlog);
   lap("resident plan (device)");
   // (tests: with MFM_PLAN_CHECK everything else is built too and the host builder's layout compared)
-  c->main_lazy = c->res.ready && !std::getenv("MFM_PLAN_CHECK") && !std::getenv("MFM_EAGER_PLANS");
+  c->main_lazy = c->res.ready && !env_flag("MFM_PLAN_CHECK");
 }
 
 // The main table's generic structures: X_t (device transpose, copied back for the planner), the level plans of both sweeps, the
-// row tiles. Xt: filled here unless the caller already has it (MFM_HOST_TRANSPOSE).
+// row tiles. Xt: filled here.
 static void plan_main_table(mfm_ctx *c, HostCsr &Xt, const std::function<void(const char *)> &lap) {
-    if (!std::getenv("MFM_HOST_TRANSPOSE") || (int64_t)Xt.ptr.size() != c->D0 + 1) {
-      Xt = transpose_device(c->X, c->stream);
-      lap("transpose (device) + copy back");
-    }
+    Xt = transpose_device(c->X, c->stream);
+    lap("transpose (device) + copy back");
     c->plan_V.sharded = c->plan_W.sharded = c->comm.active();
     c->plan_V.given_levels = c->plan_W.given_levels = c->hlevels;
     // scattered levels: LDS row tiles of 2^tile_bits {e, q} records (64 KiB by default: two workgroups per CU)
     // (short tables: 1024-row tiles -- a 4096-row tile leaves most of the 256 CUs without a workgroup and the pass is bound by
     // the life time of one workgroup: ML-100k shape 3270 -> 4040 it/s)
     int tile_bits = (c->N < ((int64_t)1 << 20) && !c->comm.active()) ? 10 : 12;
-    if (const char *e = std::getenv("MFM_TILE_BITS")) tile_bits = std::atoi(e);
+    tile_bits = env_int("MFM_TILE_BITS", tile_bits);
     if (tile_bits < 9 || tile_bits > 13) tile_bits = 0;  // 0: L2-window path (k_scat_*)
     c->plan_V.tile_bits = c->plan_W.tile_bits = tile_bits;
     // one plan serves the three latent policies of the main table: size the co-resident launch for all of them
@@ -1142,8 +1133,7 @@ static void plan_main_table(mfm_ctx *c, HostCsr &Xt, const std::function<void(co
     // Row-sharded fused tile path: which first-level columns need an all-reduce of their statistics? Those
     // with rows on more than one rank -- the same ("special") set on every rank, from two all-reduces of
     // per-column indicators (columns empty on every rank are drawn from the prior by every rank itself).
-    bool try_fused = c->comm.active() && c->hblocks.empty() && !c->hlevels.empty() && tile_bits > 0 && c->N > 0 &&
-                     !std::getenv("MFM_NO_SHARDED_FUSED") && !std::getenv("MFM_NO_SOA");
+    bool try_fused = c->comm.active() && c->hblocks.empty() && !c->hlevels.empty() && tile_bits > 0 && c->N > 0;
     if (c->comm.active()) {
       // the predicate has rank-local inputs (an empty shard, the environment): every rank must enter the collectives
       // below or none -- agree first
@@ -1224,7 +1214,7 @@ static void plan_main_table(mfm_ctx *c, HostCsr &Xt, const std::function<void(co
       }
     }
     c->plan_W.build(Xt, PMainW::R_W16, PMainW::R_WG, coop_capacity<PMainW>(), true, c->X.unit,
-                    std::getenv("MFM_NO_PLAN_TWIN") ? nullptr : &c->plan_V);
+                    &c->plan_V);
     lap("plan_W");
     c->plan_V.dev_csc = c->plan_W.dev_csc = nullptr;  // (the view lives on this frame: build() is its only reader)
     c->ls.reserve_cols(std::max(c->plan_V.max_cols_scat, c->plan_W.max_cols_scat));
@@ -1239,17 +1229,15 @@ static void decide_main_paths(mfm_ctx *c) {
   // q-free latent sweep (PMainVe), opt-in (MFM_QFREE=1): pays off when the levels' rows are contiguous; needs
   // short rows, no relation blocks, no sharding, single-pass PAR levels, no row-tile levels
   c->qfree = !c->comm.active() && c->blocks.empty() && c->X.rows > 0 && c->X.avg_row_nnz <= 4.0 &&
-             plan_is_single_pass_par(c->plan_V) && std::getenv("MFM_QFREE") && std::atoi(std::getenv("MFM_QFREE"));
+             plan_is_single_pass_par(c->plan_V) && env_int("MFM_QFREE", 0);
   if (c->qfree) c->ec.alloc((size_t)c->N);
   // split e / q layout for update_V (run_plan_soa)
-  c->soa = !c->qfree && !c->comm.active() && c->blocks.empty() && c->N > 0 && plan_supports_soa(c->plan_V) &&
-           !std::getenv("MFM_NO_SOA") && !std::getenv("MFM_NO_FUSED_QBUILD");
+  c->soa = !c->qfree && !c->comm.active() && c->blocks.empty() && c->N > 0 && plan_supports_soa(c->plan_V);
   if (c->sharded_fused) {
     c->ec.alloc((size_t)c->N);
     c->qc.alloc((size_t)c->N);
     // no first-level column straddles a rank boundary (and none is longer than ... any length is fine): the two-field pass
-    c->mf = plan_supports_mf(c->plan_V) && c->plan_V.n_special == 0 && !std::getenv("MFM_NO_MF") &&
-            !std::getenv("MFM_NO_FUSED_TWO") && !std::getenv("MFM_NO_FUSED_STATS");
+    c->mf = plan_supports_mf(c->plan_V) && c->plan_V.n_special == 0 && !env_flag("MFM_NO_MF");
     {  // every rank must take the same path
       double no = c->mf ? 0.0 : 1.0;
       DevBuf<double> d;
@@ -1263,9 +1251,8 @@ static void decide_main_paths(mfm_ctx *c) {
   if (c->soa) {
     c->ec.alloc((size_t)c->N);
     c->qc.alloc((size_t)c->N);
-    c->fuse_next = plan_supports_fused_next(c->plan_V) && !std::getenv("MFM_NO_FUSED_NEXT");
-    c->mf = c->fuse_next && plan_supports_mf(c->plan_V) && !std::getenv("MFM_NO_MF") && !std::getenv("MFM_NO_FUSED_TWO") &&
-            !std::getenv("MFM_NO_FUSED_STATS");
+    c->fuse_next = plan_supports_fused_next(c->plan_V) && !env_flag("MFM_NO_FUSED_NEXT");
+    c->mf = c->fuse_next && plan_supports_mf(c->plan_V) && !env_flag("MFM_NO_MF");
   }
 }
 
@@ -1273,7 +1260,6 @@ static void decide_main_paths(mfm_ctx *c) {
 // draws (an upper estimate of the generating workgroups): computed on a helper thread, cached per process. Returns the
 // generator's workgroup count (par_blocks; `keep` when the serial generator serves the problem).
 static int rng_prefetch_jumps(int64_t D, int K, int G, int keep) {
-  if (std::getenv("MFM_RNG_SERIAL")) return keep;
   const double normals = (double)D * (K + 1) + 4.0 * G * (K + 1) + 16;
   const double need = normals * (16.0 / 3.14159265358979) * 1.02 + 6.0 * 2.4 * std::sqrt(normals + 1.0) + 4096.0 * (2 + 2.0 * G * (K + 1)) + 2e6;
   const int64_t blocks = (int64_t)(need / MT_N) + 2;
@@ -1326,7 +1312,7 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
   // the parallel generator's jump polynomials (mfm_rng_set_program needs them right after this call): start computing
   // them now on a helper thread (a caller that knows the problem's size earlier has already asked: mfm_rng_prepare)
   c->rng.par_blocks = rng_prefetch_jumps(c->D, c->K, c->G, c->rng.par_blocks);
-  const bool tlog = std::getenv("MFM_SETUP_TIMING") != nullptr;
+  const bool tlog = env_flag("MFM_SETUP_TIMING");
   auto tnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_prev = tnow();
   CodeWarmup::get().join();
@@ -1341,17 +1327,11 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
   HostCsr Xt_keep;  // (X_t outlives the planner's scope: the resident layout is built from it once the path is known)
   {
     HostCsr &Xt = Xt_keep;
-    if (std::getenv("MFM_HOST_TRANSPOSE")) {
-      Xt = transpose_host(c->host_main());
-      lap("transpose (host)");
-      c->X.upload_csc(Xt);
-      lap("upload CSC");
-    }
     // a row of unit-valued one-hot fields + relation blocks on one GPU: update_w / update_V / update_e on index tuples, no
     // q-cache (mfm_cell.hpp). Decided first: when it takes the design, X_t, the main table's level plans and row tiles and
     // the blocks' inverse maps are never used and are not built (config 5: 1.3 s of mfm_finalize and 3 GB of HBM).
     {
-      const int64_t cell_min_rows = std::getenv("MFM_CELL_MIN_ROWS") ? std::atoll(std::getenv("MFM_CELL_MIN_ROWS")) : ((int64_t)1 << 20);
+      const int64_t cell_min_rows = env_i64("MFM_CELL_MIN_ROWS", (int64_t)1 << 20);
       // row-sharded: every rank plans its own rows; what must be the same everywhere (fields, streams, the verdict) is summed
       // over the ranks inside the planner
       const bool sh = c->comm.active();
@@ -1364,8 +1344,8 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
       };
       // (also tables of three or more one-hot fields WITHOUT relation blocks on one GPU: one pass per field instead of the
       //  row-tile passes of run_sweep_soa_multi; two-field tables keep the persistent sweep / the two-field pass)
-      const bool flat = c->hblocks.empty() && !sh && c->X.ell_width >= 3 && !std::getenv("MFM_NO_CELL_FLAT");
-      bool try_cell = (!c->hblocks.empty() || flat) && c->K > 0 && !std::getenv("MFM_NO_CELL") && (!sh || !std::getenv("MFM_NO_CELL_SHARDED"));
+      const bool flat = c->hblocks.empty() && !sh && c->X.ell_width >= 3;
+      bool try_cell = (!c->hblocks.empty() || flat) && c->K > 0 && !env_flag("MFM_NO_CELL");
       if (!sh) {
         try_cell = try_cell && c->X.unit && c->X.ell_width >= 1 && c->N >= cell_min_rows;
       } else if (try_cell) {  // (the same decision on every rank: the rows of all of them count, an empty shard has no say)
@@ -1376,65 +1356,58 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
       if (try_cell) {
         int n_cu = 0;
         MFM_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-        if (const char *e = std::getenv("MFM_CELL_GROUPS")) n_cu = std::max(1, std::atoi(e));
+        if (env_flag("MFM_CELL_GROUPS")) n_cu = std::max(1, env_int("MFM_CELL_GROUPS", 0));
         std::vector<CellBlockIn> bin;
         for (auto &hb : c->hblocks) bin.push_back(CellBlockIn{hb.map.get(), hb.X.rows});
         const int sh_rank = c->comm.shard_set ? c->comm.rank : -1;
-        if (std::getenv("MFM_CELL_HOST_PLAN")) {
-          if (sh)
-            cell_plan_build(c->cell, c->host_main(), bin, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
-          else
-            cell_plan_build(c->cell, c->host_main(), bin, n_cu, c->stream);
-        } else {
-          // one GPU: the plan is built on the device from the CSR and the blocks' maps (uploaded here, kept for the blocks)
-          const size_t nb = c->hblocks.size();
-          c->pre_maps.clear();
-          c->pre_maps.resize(nb);
-          {
-            std::vector<std::thread> pool;
-            std::vector<std::exception_ptr> errs(nb);
-            auto up = [&](size_t b) {
-              try {
-                MFM_HIP_CHECK(hipSetDevice(c->device));
-                c->pre_maps[b].upload(c->hblocks[b].map.get(), (size_t)c->N);
-              } catch (...) {
-                errs[b] = std::current_exception();
-              }
-            };
-            for (size_t b = 0; b + 1 < nb; b++) pool.emplace_back(up, b);
-            if (nb) up(nb - 1);
-            for (auto &t : pool) t.join();
-            for (auto &e : errs)
-              if (e) std::rethrow_exception(e);
-          }
-          lap("block maps to the device");
-          std::vector<CellBlockDev> bdev;
-          for (size_t b = 0; b < nb; b++) bdev.push_back(CellBlockDev{c->pre_maps[b].p, c->hblocks[b].X.rows});
-          // (row-sharded: every rank plans its own rows on its own device, the agreements are summed over the ranks inside)
-          auto host_plan = [&](CellPlan &cp) {
-            if (sh)
-              cell_plan_build(cp, c->host_main(), bin, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
-            else
-              cell_plan_build(cp, c->host_main(), bin, n_cu, c->stream);
-          };
-          if (sh)
-            cell_plan_build_device(c->cell, c->X, bdev, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
-          else
-            cell_plan_build_device(c->cell, c->X, bdev, n_cu, c->stream);
-          if (!c->cell.ready && c->cell.why.rfind("device planner:", 0) == 0) {
-            host_plan(c->cell);  // (a shape only the host planner handles: the same verdict on every rank)
-          } else if (std::getenv("MFM_PLAN_CHECK")) {  // tests: the host planner must give the same plan, array for array
-            lap("cell plan (device)");
-            CellPlan chk;
-            host_plan(chk);
-            if (chk.ready != c->cell.ready) throw Error(MFM_ERR_RUNTIME, "plan check: device and host cell planners disagree: device '" + c->cell.why + "' host '" + chk.why + "'");
-            if (chk.ready) {
-              const std::string diff = cell_plan_compare(c->cell, chk, c->stream);
-              if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host cell plans differ (" + diff + ")");
+        // one GPU: the plan is built on the device from the CSR and the blocks' maps (uploaded here, kept for the blocks)
+        const size_t nb = c->hblocks.size();
+        c->pre_maps.clear();
+        c->pre_maps.resize(nb);
+        {
+          std::vector<std::thread> pool;
+          std::vector<std::exception_ptr> errs(nb);
+          auto up = [&](size_t b) {
+            try {
+              MFM_HIP_CHECK(hipSetDevice(c->device));
+              c->pre_maps[b].upload(c->hblocks[b].map.get(), (size_t)c->N);
+            } catch (...) {
+              errs[b] = std::current_exception();
             }
+          };
+          for (size_t b = 0; b + 1 < nb; b++) pool.emplace_back(up, b);
+          if (nb) up(nb - 1);
+          for (auto &t : pool) t.join();
+          for (auto &e : errs)
+            if (e) std::rethrow_exception(e);
+        }
+        lap("block maps to the device");
+        std::vector<CellBlockDev> bdev;
+        for (size_t b = 0; b < nb; b++) bdev.push_back(CellBlockDev{c->pre_maps[b].p, c->hblocks[b].X.rows});
+        // (row-sharded: every rank plans its own rows on its own device, the agreements are summed over the ranks inside)
+        auto host_plan = [&](CellPlan &cp) {
+          if (sh)
+            cell_plan_build(cp, c->host_main(), bin, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
+          else
+            cell_plan_build(cp, c->host_main(), bin, n_cu, c->stream);
+        };
+        if (sh)
+          cell_plan_build_device(c->cell, c->X, bdev, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
+        else
+          cell_plan_build_device(c->cell, c->X, bdev, n_cu, c->stream);
+        if (!c->cell.ready && c->cell.why.rfind("device planner:", 0) == 0) {
+          host_plan(c->cell);  // (a shape only the host planner handles: the same verdict on every rank)
+        } else if (env_flag("MFM_PLAN_CHECK")) {  // tests: the host planner must give the same plan, array for array
+          lap("cell plan (device)");
+          CellPlan chk;
+          host_plan(chk);
+          if (chk.ready != c->cell.ready) throw Error(MFM_ERR_RUNTIME, "plan check: device and host cell planners disagree: device '" + c->cell.why + "' host '" + chk.why + "'");
+          if (chk.ready) {
+            const std::string diff = cell_plan_compare(c->cell, chk, c->stream);
+            if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host cell plans differ (" + diff + ")");
           }
         }
-        c->cell_w = c->cell.ready && !std::getenv("MFM_NO_CELL_W");
+        c->cell_w = c->cell.ready && !env_flag("MFM_NO_CELL_W");
         if (tlog)
           std::fprintf(stderr, "[mfm_finalize] cell plan: %s (G=%d umax=%lld streams=%zu fields=%zu item32=%d)\n",
                        c->cell.ready ? "ready" : c->cell.why.c_str(), c->cell.G, (long long)c->cell.umax, c->cell.streams.size(),
@@ -1494,7 +1467,7 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
       (void)coop_capacity<PBlockV>();  // (function-local caches: filled before the threads start)
       (void)coop_capacity<PBlockW>();
       std::vector<std::thread> pool;
-      const bool par = c->hblocks.size() > 1 && !std::getenv("MFM_SERIAL_BLOCK_BUILD");
+      const bool par = c->hblocks.size() > 1;
       for (size_t b = 0; b < c->hblocks.size(); b++) {
         if (par && b + 1 < c->hblocks.size())
           pool.emplace_back(build_one, b);
@@ -1529,14 +1502,14 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
   //  residual -- outweigh the bytes it saves; ML-100k shape: fit() 3060 it/s resident, 3950 per-factor. MFM_RES_MIN_ROWS)
   if (c->res.ready) {
     // (built first, on the device) tests: the host builder on X_t must give the same layout, array for array
-    if (!c->main_lazy && std::getenv("MFM_PLAN_CHECK")) {
+    if (!c->main_lazy && env_flag("MFM_PLAN_CHECK")) {
       ResPlan chk;
       chk.build(Xt_keep, c->plan_V.h_level, &c->hgroup, c->res_plan_cus);
       const std::string diff = chk.ready ? res_plan_compare(c->res, chk, c->stream) : ("host builder: " + chk.why);
       if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host resident layouts differ (" + diff + ")");
       lap("resident plan (host, check)");
     }
-  } else if (!c->res_refused && c->soa && c->mf && c->X.unit && !c->comm.active() && c->N >= res_min_rows(c) && !std::getenv("MFM_NO_RESIDENT")) {
+  } else if (!c->res_refused && c->soa && c->mf && c->X.unit && !c->comm.active() && c->N >= res_min_rows(c) && !env_flag("MFM_NO_RESIDENT")) {
     plan_resident(c, [&](ResPlan &rp, int n_cu) { rp.build(Xt_keep, c->plan_V.h_level, &c->hgroup, n_cu); }, tlog);
     lap("resident plan (host)");
   }
@@ -1545,7 +1518,7 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
   // level-1 columns of the GLOBAL design, so every rank numbers them alike -- and goes live when the caller has handed over the
   // peers' exchange buffers (mfm_peer_set); until then, and if any rank cannot take part, the per-factor passes run.
   if (c->comm.active() && c->sharded_fused && c->mf && c->comm.shard_set && c->comm.world <= RES_MAX_PEERS && c->comm.world > 1 &&
-      !std::getenv("MFM_NO_RESIDENT") && !std::getenv("MFM_NO_SHARDED_RESIDENT")) {
+      !env_flag("MFM_NO_RESIDENT") && !env_flag("MFM_NO_SHARDED_RESIDENT")) {
     const int64_t min_rows = res_min_rows(c);
     const bool want = c->X.unit && c->X.ell_width == 2 && c->N >= std::max<int64_t>(1, min_rows / c->comm.world) && c->K > 0;
     bool mine = false;
@@ -1556,7 +1529,7 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
         rp.allow_overflow = false;
         res_plan_build_device(rp, c->X, &c->hgroup, n_cu, c->stream, &c->hlevels, &draw_empty);
       }, tlog);
-      if (c->res.ready && std::getenv("MFM_PLAN_CHECK")) {
+      if (c->res.ready && env_flag("MFM_PLAN_CHECK")) {
         ResPlan chk;
         chk.allow_overflow = false;
         chk.build(Xt_keep, c->hlevels, &c->hgroup, c->res_plan_cus, &draw_empty);
@@ -1652,7 +1625,7 @@ int mfm_peer_set_model(mfm_ctx *ctx, int32_t world, int32_t rank, void *const *w
   if (c->res.peer_w[rank] != c->w.p || c->res.peer_V[rank] != c->V.p)
     throw Error(MFM_ERR_INVALID, "mfm_peer_set_model: this rank's own entry must be its own w / V (mfm_peer_model_info)");
   MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-  c->res.peers_model = !std::getenv("MFM_NO_PEER_MODEL");
+  c->res.peers_model = true;
   MFM_CATCH(ctx)
 }
 
@@ -1719,8 +1692,7 @@ int mfm_peer_import(mfm_ctx *ctx, int32_t world, int32_t rank, const void *all_h
   // it has run on two GPUs the default keeps the model all-reduce after the launch (sync_model_sharded): the only memory another
   // GPU writes is then the exchange buffers, which are uncached (MYFM_PEER_MODEL=0 / 1 also separates "exchange wrong" from "model
   // write wrong" on a first real run).
-  const char *pm = std::getenv("MYFM_PEER_MODEL");
-  if (pm && std::atoi(pm) != 0) {
+  if (env_int("MYFM_PEER_MODEL", 0) != 0) {
     rc = mfm_peer_set_model(ctx, world, rank, ws, Vs);
     if (rc != MFM_OK) return rc;
   }
@@ -2054,7 +2026,7 @@ int mfm_sweep_wV(mfm_ctx *ctx, double alpha, double e_shift, const double *lambd
                  int32_t f_begin, int32_t f_end, const double *lambda_V, const double *mu_V, const double *zv) {
   {
     mfm_ctx *c = ctx;
-    const bool fused = c && c->finalized && c->res.ready && f_begin < f_end && !std::getenv("MFM_RES_NO_LINEAR");
+    const bool fused = c && c->finalized && c->res.ready && f_begin < f_end;
     if (!fused) {
       int rc = e_shift != 0.0 ? mfm_shift_e(ctx, e_shift) : MFM_OK;
       if (rc == MFM_OK) rc = mfm_sweep_w(ctx, alpha, lambda_w, mu_w, zw);
@@ -2096,13 +2068,11 @@ int mfm_sweep_wV(mfm_ctx *ctx, double alpha, double e_shift, const double *lambd
     zwdev = c->rng.slot[c->rng.current].zw.p;
     zbase = c->rng.slot[c->rng.current].zv.p + (size_t)f_begin * c->D;
   }
-  const bool lazy_store = !std::getenv("MFM_RES_EAGER_STORE");
   // (regression, all factors swept: update_e follows and recomputes the residual -- the launch's copy would be a dead store, 64 us)
-  const bool no_store =
-      c->e_recomputable && c->e_is_residual && lazy_store && f_begin == 0 && f_end == c->K && !std::getenv("MFM_RES_ALWAYS_STORE");
+  const bool no_store = c->e_recomputable && c->e_is_residual && f_begin == 0 && f_end == c->K;
   run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, d_lam, d_mu,
-                     c->group.p, c->G, alpha, c->ls.error.p, lazy_store, c->w.p, zwdev, d_lam_w, d_mu_w, e_shift, load_slots, no_store);
-  c->e_in_slots = lazy_store && !no_store;
+                     c->group.p, c->G, alpha, c->ls.error.p, c->w.p, zwdev, d_lam_w, d_mu_w, e_shift, load_slots, no_store);
+  c->e_in_slots = !no_store;
   c->e_lost = no_store;
   c->q_stale_factor = f_end - 1;
   if (c->comm.active() && !c->res.peers_model) sync_model_sharded(c, true, f_begin, f_end);
@@ -2112,9 +2082,7 @@ int mfm_sweep_wV(mfm_ctx *ctx, double alpha, double e_shift, const double *lambd
 // ---- a whole regression iteration without the host in its loop (include/myfm_hip.h) -------------------------------------------
 static bool regression_iteration_ready(mfm_ctx *c) {
   if (!c || !c->finalized || !c->res.ready || c->comm.active() || c->K <= 0 || c->D <= 0) return false;
-  if (std::getenv("MFM_RES_NO_LINEAR") || std::getenv("MFM_RES_EAGER_STORE")) return false;
-  static const bool no_res_score = std::getenv("MFM_NO_RES_SCORE") != nullptr || std::getenv("MFM_NO_MF_SCORE") != nullptr;
-  if (no_res_score || !res_score_supported(c->res, c->K)) return false;
+  if (!res_score_supported(c->res, c->K)) return false;
   if (!(c->e_in_slots && c->slot_sums_valid && c->e_is_residual && !c->e_lost)) return false;  // (update_e's slot-order sums)
   const auto &r = c->rng;
   if (!r.programmed || r.produced <= r.acquired || r.n_zw != c->D || r.n_zv != c->D * (int64_t)c->K) return false;
@@ -2205,9 +2173,9 @@ int mfm_regression_iteration(mfm_ctx *ctx, const mfm_hyper_prior *prior, const d
     const bool load_slots = c->e_in_slots;
     c->slot_sums_valid = false;
     const double *d_lam_w = c->hyp.p + 4, *d_mu_w = d_lam_w + nG, *d_lam = d_mu_w + nG, *d_mu = d_lam + nGK;
-    const bool no_store = c->e_recomputable && c->e_is_residual && !std::getenv("MFM_RES_ALWAYS_STORE");
+    const bool no_store = c->e_recomputable && c->e_is_residual;
     run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, 0, K, sl.zv.p, d_lam, d_mu, c->group.p,
-                       c->G, 0.0, c->ls.error.p, true, c->w.p, sl.zw.p, d_lam_w, d_mu_w, 0.0, load_slots, no_store, c->hyp.p);
+                       c->G, 0.0, c->ls.error.p, c->w.p, sl.zw.p, d_lam_w, d_mu_w, 0.0, load_slots, no_store, c->hyp.p);
     c->e_in_slots = !no_store;
     c->e_lost = no_store;
     c->q_stale_factor = K - 1;
@@ -2264,18 +2232,16 @@ int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, cons
   }
   if (c->main_lazy) {
     if (c->res.ready) {
-      const bool lazy_store = !std::getenv("MFM_RES_EAGER_STORE");
       run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, c->lam.p, c->mu.p,
-                         c->group.p, c->G, alpha, c->ls.error.p, lazy_store);
-      c->e_in_slots = lazy_store;
+                         c->group.p, c->G, alpha, c->ls.error.p);
+      c->e_in_slots = true;
       c->q_stale_factor = f_end - 1;
       return MFM_OK;
     }
     c->ensure_main_plans();
   }
   // the first level rebuilds q from the CSR rows itself when it touches every row exactly once
-  const bool first_q = !c->comm.active() && c->blocks.empty() && plan_first_level_builds_q(c->plan_V) &&
-                       !std::getenv("MFM_NO_FUSED_QBUILD");
+  const bool first_q = !c->comm.active() && c->blocks.empty() && plan_first_level_builds_q(c->plan_V);
   if (c->qfree) {
     // compact e for the duration of the factor loop; q is never materialised inside it
     hipLaunchKernelGGL(k_e_pack, dim3(cdiv(c->N, 256)), dim3(256), 0, s, c->eq_rows(), c->ec.p, c->N);
@@ -2298,10 +2264,9 @@ int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, cons
     return MFM_OK;
   }
   if (c->sharded_fused && c->res.ready) {  // (row-sharded persistent sweep: the peers' buffers are set)
-    const bool lazy_store = !std::getenv("MFM_RES_EAGER_STORE");
     run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, c->lam.p, c->mu.p,
-                       c->group.p, c->G, alpha, c->ls.error.p, lazy_store);
-    c->e_in_slots = lazy_store;
+                       c->group.p, c->G, alpha, c->ls.error.p);
+    c->e_in_slots = true;
     c->q_stale_factor = f_end - 1;
     if (!c->res.peers_model) sync_model_sharded(c, false, f_begin, f_end);
     return MFM_OK;
@@ -2367,10 +2332,9 @@ int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, cons
     };
     const bool fuse = c->fuse_next;
     if (c->res.ready) {
-      const bool lazy_store = !std::getenv("MFM_RES_EAGER_STORE");
       run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, c->lam.p, c->mu.p,
-                         c->group.p, c->G, alpha, c->ls.error.p, lazy_store);
-      c->e_in_slots = lazy_store;
+                         c->group.p, c->G, alpha, c->ls.error.p);
+      c->e_in_slots = true;
       c->q_stale_factor = f_end - 1;
       return MFM_OK;
     }
@@ -2420,13 +2384,12 @@ int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, cons
     else
       run_plan<PMainV>(s, c->timing, c->plan_V, a, c->ls, kcv, c->X.unit, first_q);  // :343-376
     // a block whose successor streams its statistics pass leaves its re-sync to that pass (one read + write of eq less)
-    static const bool fuse_resync = !std::getenv("MFM_NO_RESYNC_FUSE");
     DevBlock *pending = nullptr;
     for (size_t bi = 0; bi < c->blocks.size(); bi++) {
       DevBlock &B = *c->blocks[bi];
       const bool last = bi + 1 == c->blocks.size();
       // ... and the last block leaves it to the next factor's q-cache build (thread-per-row form)
-      const bool defer = fuse_resync && c->N > 0 &&
+      const bool defer = c->N > 0 &&
                          (last ? (f + 1 < f_end && !first_q && qbuild_by_rows(c))
                                : (c->blocks[bi + 1]->stream_unsync || c->blocks[bi + 1]->split_unsync));
       block_sweep_V(s, c->timing, c->ls, B, c->N, c->eq_rows(), Vf, zf, c->group.p, lamf, muf, alpha, c->comm, pending, defer);  // :378-482
@@ -2462,7 +2425,7 @@ int mfm_rng_seed_mt19937(mfm_ctx *ctx, const uint32_t *state624, int32_t positio
     // every CU at once: a generator workgroup still running then delays all of its workgroups) is launched
     int lo = 0, hi = 0;
     MFM_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    MFM_HIP_CHECK(hipStreamCreateWithPriority(&r.stream, hipStreamNonBlocking, std::getenv("MFM_RNG_NO_PRIORITY") ? lo : hi));
+    MFM_HIP_CHECK(hipStreamCreateWithPriority(&r.stream, hipStreamNonBlocking, hi));
   }
   MFM_HIP_CHECK(hipStreamSynchronize(r.stream));
   RngState h;
@@ -2547,7 +2510,7 @@ int mfm_rng_set_program(mfm_ctx *ctx, const mfm_rng_op *ops, int32_t n_ops) {
   r.need_gen = r.need;
   {
     const int64_t blocks1 = (int64_t)(r.need / MT_N) + 2;
-    if (blocks1 > MT_PAR_BLOCKS && !std::getenv("MFM_RNG_SERIAL")) {
+    if (blocks1 > MT_PAR_BLOCKS) {
       r.need_gen = r.need * (uint64_t)(latent_rows > (1 << 22) ? 2 : mt_gen_batch((double)r.need));
       const int64_t blocks = (int64_t)(r.need_gen / MT_N) + 2;
       if (r.par_blocks <= 0) r.par_blocks = mt_par_blocks_for(blocks);
@@ -2657,25 +2620,14 @@ int mfm_rng_prefetch(mfm_ctx *ctx) {
   // narrow chain, of which only the last single-workgroup kernel overlaps the next sweep's start.
   if (r.produced - r.acquired >= (r.current >= 0 ? mfm_ctx::RngEngine::N_SLOTS - 1 : mfm_ctx::RngEngine::N_SLOTS))
     throw Error(MFM_ERR_RUNTIME, "every random set is in use (one acquired, the others in flight): acquire the next one first");
-  static const bool no_gate = std::getenv("MFM_RES_NO_GATE") != nullptr;  // (experiments with CUs left free by MFM_RES_CUS)
-  static const bool one_part = std::getenv("MFM_RNG_ONE_PART") != nullptr;  // (the whole set behind one gate, as before round 6)
   // (the gate only where the persistent sweep fills the device: a small table's launch leaves most CUs free, and there the
   //  generator should run beside it -- ML-100k shape: 2700 it/s gated, 3000 not)
-  const bool gated = ctx->res.ready && ctx->res_fills_device && !no_gate;
+  const bool gated = ctx->res.ready && ctx->res_fills_device;
   rng_finish_pending(ctx, gated);
   auto &sl = r.slot[r.produced % mfm_ctx::RngEngine::N_SLOTS];
   hipStream_t s = r.stream;
-  {  // (timing experiment, wrong results: after the first sets nothing is generated any more -- what the iteration costs without the
-     //  random stream's work)
-    static const bool reuse = std::getenv("MFM_RNG_DBG_REUSE") != nullptr;
-    if (reuse && r.produced >= 2 * mfm_ctx::RngEngine::N_SLOTS) {
-      MFM_HIP_CHECK(hipEventRecord(sl.ready, s));
-      r.produced++;
-      return MFM_OK;
-    }
-  }
   // two parts only with another finished set ahead of this one (the set is then not needed before the request after this one)
-  const bool two_parts = gated && !one_part && r.produced - r.acquired >= 1;
+  const bool two_parts = gated && r.produced - r.acquired >= 1;
   if (gated && !two_parts) {
     if (!r.gate) MFM_HIP_CHECK(hipEventCreateWithFlags(&r.gate, hipEventDisableTiming));
     MFM_HIP_CHECK(hipEventRecord(r.gate, ctx->stream));
@@ -2689,17 +2641,11 @@ int mfm_rng_prefetch(mfm_ctx *ctx) {
     r.latent_pending = false;
   }
   if (r.par_wgs > 1) {
-    if (std::getenv("MFM_RNG_FUSED_JUMP")) {
-      hipLaunchKernelGGL(k_mt_generate_par<0>, dim3(r.par_wgs), dim3(MT_GEN_THREADS),
-                         (MT_JUMP_SPAN * MT_N + 2 * (MT_N + 1)) * sizeof(uint32_t), s, r.state.p, r.state_next.p, r.raw.p, r.mask,
-                         r.need_gen, r.jump.p, r.par_blocks, (uint32_t *)nullptr, r.need);
-    } else {
-      hipLaunchKernelGGL(k_mt_generate_par<1>, dim3(r.par_wgs), dim3(MT_GEN_THREADS),
-                         (MT_JUMP_SPAN * MT_N + 2 * (MT_N + 1)) * sizeof(uint32_t), s, r.state.p, r.state_next.p, r.raw.p, r.mask,
-                         r.need_gen, r.jump.p, r.par_blocks, r.starts.p, r.need);
-      hipLaunchKernelGGL(k_mt_generate_par<2>, dim3(r.par_wgs), dim3(MT_GEN_THREADS), 2 * (MT_N + 1) * sizeof(uint32_t), s,
-                         r.state.p, r.state_next.p, r.raw.p, r.mask, r.need_gen, r.jump.p, r.par_blocks, r.starts.p, r.need);
-    }
+    hipLaunchKernelGGL(k_mt_generate_par<1>, dim3(r.par_wgs), dim3(MT_GEN_THREADS),
+                       (MT_JUMP_SPAN * MT_N + 2 * (MT_N + 1)) * sizeof(uint32_t), s, r.state.p, r.state_next.p, r.raw.p, r.mask,
+                       r.need_gen, r.jump.p, r.par_blocks, r.starts.p, r.need);
+    hipLaunchKernelGGL(k_mt_generate_par<2>, dim3(r.par_wgs), dim3(MT_GEN_THREADS), 2 * (MT_N + 1) * sizeof(uint32_t), s,
+                       r.state.p, r.state_next.p, r.raw.p, r.mask, r.need_gen, r.jump.p, r.par_blocks, r.starts.p, r.need);
     hipLaunchKernelGGL(k_mt_commit, dim3(1), dim3(MT_GEN_THREADS), 0, s, r.state.p, r.state_next.p);
   } else {
     hipLaunchKernelGGL(k_mt_generate, dim3(1), dim3(MT_GEN_THREADS), 0, s, r.state.p, r.raw.p, r.mask, r.need);

@@ -86,34 +86,34 @@ __device__ __forceinline__ void column_update(const SweepArgs &a, int j, int tid
 // XCD-aware block index: workgroup b is observed to run on XCD b % 8 (MI355X_MICROARCH.md); map the
 // blocks of one XCD to a CONTIGUOUS range of the work list so that columns with neighbouring rows
 // share that XCD's L2. Bijective for any nb; a wrong placement guess only costs speed.
-__device__ __forceinline__ int xcd_swizzle(int b, int nb, int on) {
-  if (!on || nb < 16) return b;
+__device__ __forceinline__ int xcd_swizzle(int b, int nb) {
+  if (nb < 16) return b;
   const int q = nb >> 3, r = nb & 7, x = b & 7;
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
 }
 
 template <class P, bool UNIT>
 __global__ __launch_bounds__(WG) void k_level_light(SweepArgs a, const int32_t *__restrict__ cols_w4, int n_w4,
-                                                    const int32_t *__restrict__ cols_w1, int n_w1, int swz) {
+                                                    const int32_t *__restrict__ cols_w1, int n_w1) {
   const int nb4 = (n_w4 + 3) >> 2;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if ((int)blockIdx.x < nb4) {
-    const int w = xcd_swizzle(blockIdx.x, nb4, swz) * 4 + wv;
+    const int w = xcd_swizzle(blockIdx.x, nb4) * 4 + wv;
     if (w < n_w4) column_update<P, 4, WAVE, UNIT>(a, cols_w4[w], lane, nullptr);
   } else {
-    const int w = xcd_swizzle(blockIdx.x - nb4, gridDim.x - nb4, swz) * 4 + wv;
+    const int w = xcd_swizzle(blockIdx.x - nb4, gridDim.x - nb4) * 4 + wv;
     if (w < n_w1) column_update<P, 1, WAVE, UNIT>(a, cols_w1[w], lane, nullptr);
   }
 }
 
 template <class P, bool UNIT>
 __global__ __launch_bounds__(WG) void k_level_heavy(SweepArgs a, const int32_t *__restrict__ cols_wg, int n_wg,
-                                                    const int32_t *__restrict__ cols_w16, int n_w16, int swz) {
+                                                    const int32_t *__restrict__ cols_w16, int n_w16) {
   __shared__ double lds[2 * WG / WAVE];
   if ((int)blockIdx.x < n_wg) {
-    column_update<P, P::R_WG, WG, UNIT>(a, cols_wg[xcd_swizzle(blockIdx.x, n_wg, swz)], threadIdx.x, lds);
+    column_update<P, P::R_WG, WG, UNIT>(a, cols_wg[xcd_swizzle(blockIdx.x, n_wg)], threadIdx.x, lds);
   } else if (P::R_W16 > 0) {
-    const int w = xcd_swizzle(blockIdx.x - n_wg, gridDim.x - n_wg, swz) * 4 + (threadIdx.x >> 6);
+    const int w = xcd_swizzle(blockIdx.x - n_wg, gridDim.x - n_wg) * 4 + (threadIdx.x >> 6);
     if (w < n_w16) column_update<P, (P::R_W16 > 0 ? P::R_W16 : 1), WAVE, UNIT>(a, cols_w16[w], threadIdx.x & 63, nullptr);
   }
 }
@@ -266,8 +266,8 @@ constexpr int SCAT_RB = 65536;
 template <class P, bool UNIT>
 __global__ __launch_bounds__(WG) void k_scat_stats(SweepArgs a, const int2 *__restrict__ ent, const double *__restrict__ eval,
                                                    int64_t n_ent, const int32_t *__restrict__ run_base,
-                                                   double2 *__restrict__ slots, int n_wg, int swz) {
-  const int wgi = xcd_swizzle(blockIdx.x, n_wg, swz);
+                                                   double2 *__restrict__ slots, int n_wg) {
+  const int wgi = xcd_swizzle(blockIdx.x, n_wg);
   const int lane = threadIdx.x & 63;
   const int64_t tile = (int64_t)wgi * (WG / WAVE) + (threadIdx.x >> 6);
   const int64_t e = tile * WAVE + lane;
@@ -329,8 +329,8 @@ __global__ __launch_bounds__(WG) void k_scat_draw(SweepArgs a, const int32_t *__
 
 template <class P, bool UNIT>
 __global__ __launch_bounds__(WG) void k_scat_apply(SweepArgs a, const int2 *__restrict__ ent, const double *__restrict__ eval,
-                                                   int64_t n_ent, const double2 *__restrict__ oldnew, int n_wg, int swz) {
-  const int64_t e = (int64_t)xcd_swizzle(blockIdx.x, n_wg, swz) * WG + threadIdx.x;
+                                                   int64_t n_ent, const double2 *__restrict__ oldnew, int n_wg) {
+  const int64_t e = (int64_t)xcd_swizzle(blockIdx.x, n_wg) * WG + threadIdx.x;
   if (e >= n_ent) return;
   const int2 rc = ent[e];
   const double2 on = oldnew[rc.y];
@@ -407,10 +407,10 @@ template <class P, bool UNIT, bool SOA = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_tile_stats(
     SweepArgs a, const uint32_t *__restrict__ tent, const double *__restrict__ tval, const int32_t *__restrict__ tile_ptr,
     const int32_t *__restrict__ tile_row0, const double *__restrict__ told, const int32_t *__restrict__ run_base,
-    const int32_t *__restrict__ slot_pos, double2 *__restrict__ slots, int tile_bits, int n_tiles, int swz,
+    const int32_t *__restrict__ slot_pos, double2 *__restrict__ slots, int tile_bits, int n_tiles,
     const int32_t *__restrict__ tile_list) {
   extern __shared__ double2 lds_rec[];
-  const int b = tile_list ? tile_list[blockIdx.x] : xcd_swizzle(blockIdx.x, n_tiles, swz);
+  const int b = tile_list ? tile_list[blockIdx.x] : xcd_swizzle(blockIdx.x, n_tiles);
   const int64_t row0 = tile_row0[b];
   const int nr = tile_row0[b + 1] - (int)row0;
   const int nt = blockDim.x, tid = threadIdx.x, lane = tid & 63, nw = nt >> 6;
@@ -492,9 +492,9 @@ template <class P, bool UNIT, bool SOA = false, bool WRITE_Q = true>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_tile_apply(SweepArgs a, const uint32_t *__restrict__ tent,
                                                      const double *__restrict__ tval, const int32_t *__restrict__ tile_ptr,
                                                      const int32_t *__restrict__ tile_row0,
-                                                     const double2 *__restrict__ oldnew, int tile_bits, int n_tiles, int swz) {
+                                                     const double2 *__restrict__ oldnew, int tile_bits, int n_tiles) {
   extern __shared__ double2 lds_rec[];
-  const int b = xcd_swizzle(blockIdx.x, n_tiles, swz);
+  const int b = xcd_swizzle(blockIdx.x, n_tiles);
   const int64_t row0 = tile_row0[b];
   const int nr = tile_row0[b + 1] - (int)row0;
   const int nt = blockDim.x, tid = threadIdx.x;
@@ -661,10 +661,10 @@ struct FuseArgs {
 template <bool UNIT, bool TWO, bool SPLIT = false, bool MULTIQ = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_tile_apply_next(
     SweepArgs a, const uint32_t *__restrict__ tent, const double *__restrict__ tval, const int32_t *__restrict__ tile_ptr,
-    const int32_t *__restrict__ tile_row0, const double2 *__restrict__ oldnew, int tile_bits, int n_tiles, int swz,
+    const int32_t *__restrict__ tile_row0, const double2 *__restrict__ oldnew, int tile_bits, int n_tiles,
     FuseArgs fa) {
   extern __shared__ double2 lds_rec[];
-  const int b = xcd_swizzle(blockIdx.x, n_tiles, swz);
+  const int b = xcd_swizzle(blockIdx.x, n_tiles);
   const int64_t row0 = tile_row0[b];
   const int nr = tile_row0[b + 1] - (int)row0;
   const int nt = blockDim.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = nt >> 6;
@@ -915,9 +915,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) vo
     const double2 *__restrict__ oldnewA, const uint32_t *__restrict__ tentS, const double *__restrict__ tvalS,
     const int32_t *__restrict__ tile_ptrS, const double *__restrict__ told, const int32_t *__restrict__ run_base,
     const int32_t *__restrict__ slot_pos, double2 *__restrict__ slots, const int32_t *__restrict__ tile_row0, int tile_bits,
-    int n_tiles, int swz) {
+    int n_tiles) {
   extern __shared__ double2 lds_rec[];
-  const int b = xcd_swizzle(blockIdx.x, n_tiles, swz);
+  const int b = xcd_swizzle(blockIdx.x, n_tiles);
   const int64_t row0 = tile_row0[b];
   const int nr = tile_row0[b + 1] - (int)row0;
   const int nt = blockDim.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = nt >> 6;
@@ -2086,8 +2086,6 @@ struct CbPersistArgs {
   int *error;
   unsigned long long *prof;  // MFM_CB_PROF: [16] sums of s_memrealtime ticks (100 MHz) of thread 0 of the hot walker (0..4: wait,
                              // stage in, walk, stage out, batches) and of range 0 (8..11: wait, near part, far part, batches)
-  int dbg;            // timing experiments only (MFM_CB_DBG; results are wrong when set): 1 no hot walk, 2 no hot-record staging,
-                      // 4 no cold statistics, 8 no cold update
 };
 
 template <class P>
@@ -2134,7 +2132,7 @@ __global__ __launch_bounds__(CHAINB_NT) void k_cb_persist(SweepArgs a, CbPersist
         c_lam[tid] = cb_ld(colpack + 2 * MC + tid);
         c_mu[tid] = cb_ld(colpack + 3 * MC + tid);
       }
-      for (int i = tid; i < ((g.dbg & 2) ? 0 : B.n_hot * rec2_g); i += NT) {
+      for (int i = tid; i < B.n_hot * rec2_g; i += NT) {
         const int slot = i / rec2_g, w = i - slot * rec2_g;
         lds_hot[(size_t)slot * rec2_l + w] = cb_ld2(hot_pack + i);
       }
@@ -2154,7 +2152,7 @@ __global__ __launch_bounds__(CHAINB_NT) void k_cb_persist(SweepArgs a, CbPersist
       }
       __syncthreads();
       if (pf) t2 = __builtin_amdgcn_s_memrealtime();
-      if (wv == 0 && !(g.dbg & 1)) {
+      if (wv == 0) {
         for (int c = 0; c < B.ncols; c++) {
           const double S1 = csum[c].x, S2 = csum[c].y;
           const double old = c_old[c];
@@ -2164,10 +2162,9 @@ __global__ __launch_bounds__(CHAINB_NT) void k_cb_persist(SweepArgs a, CbPersist
           __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
         }
       }
-      if ((g.dbg & 1) && tid < B.ncols) c_new[tid] = c_old[tid];
       __syncthreads();
       if (pf) t3 = __builtin_amdgcn_s_memrealtime();
-      for (int i = tid; i < ((g.dbg & 2) ? 0 : B.n_hot * rec2_g); i += NT) {
+      for (int i = tid; i < B.n_hot * rec2_g; i += NT) {
         const int slot = i / rec2_g, w = i - slot * rec2_g;
         cb_st2(hot_pack + i, lds_hot[(size_t)slot * rec2_l + w]);
       }
@@ -2297,7 +2294,6 @@ __global__ __launch_bounds__(CHAINB_NT) void k_cb_persist(SweepArgs a, CbPersist
       n2 = g.bk_cls[(in_ * NB + w) * 3 + 1];
       n3 = g.bk_cls[(in_ * NB + w) * 3 + 2];
     }
-    if (g.dbg & 4) n2 = n3 = n1;
     int lc0[U], row0[U];
     double xv0[U];
 #pragma unroll
@@ -2321,7 +2317,6 @@ __global__ __launch_bounds__(CHAINB_NT) void k_cb_persist(SweepArgs a, CbPersist
       p0 = g.bk_ptr[ip * (NB + 1) + w];
       p4 = g.bk_ptr[ip * (NB + 1) + w + 1];
       p2 = g.bk_cls[(ip * NB + w) * 3 + 1];
-      if (g.dbg & 8) p0 = p2 = p4 = 0;
       if (pfr) r0 = __builtin_amdgcn_s_memrealtime();
       if (tid == 0) cb_wait(&g.sync->hot_done, (unsigned long long)bi, g.error, dead);
       if (pfr) r1 = __builtin_amdgcn_s_memrealtime();
@@ -2335,7 +2330,6 @@ __global__ __launch_bounds__(CHAINB_NT) void k_cb_persist(SweepArgs a, CbPersist
         ((double2 *)a.state)[(int64_t)g.hot_rows[Bp.hot_row0 + slot] * rec2_global + q] = cb_ld2(hot_pack_p + i);
       }
       update_range(p0, p2);
-      if (g.dbg & 16) update_range(p2, p4);
     }
     __threadfence_block();
     __syncthreads();  // this range's records are up to date for everything below (the only reader of them is this workgroup)
@@ -2364,7 +2358,7 @@ __global__ __launch_bounds__(CHAINB_NT) void k_cb_persist(SweepArgs a, CbPersist
     }
     if (pfr) r2 = __builtin_amdgcn_s_memrealtime();
     // ---- while the hot walker is busy with batch bi ----
-    if (Bp.ncols > 0 && !(g.dbg & 16)) update_range(p2, p4);  // update far: rows batch bi does not touch
+    if (Bp.ncols > 0) update_range(p2, p4);  // update far: rows batch bi does not touch
     __threadfence_block();
     __syncthreads();
     if (Bq.ncols > 0) {  // statistics far of batch bi + 1: rows batch bi does not touch
@@ -2373,10 +2367,8 @@ __global__ __launch_bounds__(CHAINB_NT) void k_cb_persist(SweepArgs a, CbPersist
       const int q0 = g.bk_ptr[iq * (NB + 1) + w], q4 = g.bk_ptr[iq * (NB + 1) + w + 1];
       const int q1 = g.bk_cls[(iq * NB + w) * 3 + 0], q3 = g.bk_cls[(iq * NB + w) * 3 + 2];
       __syncthreads();
-      if (!(g.dbg & 4)) {
-        stats_range(q3, q4, c_oldq, false, nullptr, nullptr, nullptr);
-        stats_range(q0, q1, c_oldq, false, nullptr, nullptr, nullptr);
-      }
+      stats_range(q3, q4, c_oldq, false, nullptr, nullptr, nullptr);
+      stats_range(q0, q1, c_oldq, false, nullptr, nullptr, nullptr);
     }
     __syncthreads();
     if (pfr && Bp.ncols > 0 && Bn.ncols > 0) {

@@ -1130,15 +1130,6 @@ __global__ void k_lat_commit(RngState *__restrict__ rs, LatStatus *__restrict__ 
   }
 }
 
-static double env_double(const char *name, double dflt) {
-  const char *e = std::getenv(name);
-  return e ? std::atof(e) : dflt;
-}
-static int env_int(const char *name, int dflt) {
-  const char *e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
-
 }  // namespace
 
 struct LatentEngine::Impl {
@@ -1260,7 +1251,7 @@ int LatentEngine::run(const LatentJob &job, const LatentPrep &prep, LatentStats 
     if (stats) *stats = S;
     return 5;
   }
-  const bool timing = std::getenv("MFM_LATENT_TIMING") != nullptr;
+  const bool timing = env_flag("MFM_LATENT_TIMING");
   hipEvent_t ev[4];
   if (timing)
     for (auto &e : ev) MFM_HIP_CHECK(hipEventCreate(&e));
@@ -1284,7 +1275,7 @@ int LatentEngine::run(const LatentJob &job, const LatentPrep &prep, LatentStats 
   // (probit classification only: there the quads decide two thirds of the variance; for ordered probit -- two-sided rows, whose
   //  decisions depend on their own interval -- a third, which pays for the table and no more: 56.7 -> 56.2 ... 57.8 it/s at config 3's
   //  shape, 2.437 -> 2.432 ... 2.439 at config 5, against 62.5 -> 68.3 ... 69.4 for classification)
-  const bool use_cv = job.n_class == 0 && n >= env_int("MFM_LAT_CV_MIN_ROWS", 1 << 20) && std::getenv("MFM_LAT_NO_CV") == nullptr;
+  const bool use_cv = job.n_class == 0 && n >= (1 << 20);
   const int64_t n_waves = (nq + 63) / 64;
   if (use_cv) {
     constexpr int NC = LAT_CV_G * LAT_CV_G;
@@ -1299,7 +1290,7 @@ int LatentEngine::run(const LatentJob &job, const LatentPrep &prep, LatentStats 
     hipLaunchKernelGGL(k_lat_cv_table, dim3(NC / 256), dim3(256), 0, s, m.wrec.p, n, m.cvtab.p, m.cvq.p);
     hipLaunchKernelGGL(k_lat_cv_stats, dim3((unsigned)S), dim3(256), 0, s, m.wrec.p, n, m.cvtab.p, m.cvq.p, m.cvrow.p,
                        m.cvrow.p + LAT_CV_S, m.cv.p);
-    hipLaunchKernelGGL(k_lat_cv_rho, dim3(1), dim3(256), 0, s, m.cvrow.p, m.cvrow.p + LAT_CV_S, n, env_double("MFM_LAT_CV_SAFETY", 1.15),
+    hipLaunchKernelGGL(k_lat_cv_rho, dim3(1), dim3(256), 0, s, m.cvrow.p, m.cvrow.p + LAT_CV_S, n, 1.15,
                        m.cv.p);
   }
   hipLaunchKernelGGL(k_lat_quads, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, job.state, job.raw, job.mask, nq, m.qt.p, m.qx.p,
@@ -1333,7 +1324,7 @@ int LatentEngine::run(const LatentJob &job, const LatentPrep &prep, LatentStats 
     int32_t *sc = m.cur0.p, *sf = m.fin0.p, *dc = m.cur1.p, *df = m.fin1.p;
     max_live = Wmax;
     int Rr = R;
-    const bool no_resident = std::getenv("MFM_LAT_NO_RESIDENT") != nullptr;
+    const bool no_resident = env_flag("MFM_LAT_NO_RESIDENT");
     constexpr int res_nt = LAT_RES_NT;
     while (done < Lq) {
       if (!first && max_live <= res_nt && !no_resident) break;
@@ -1393,43 +1384,7 @@ int LatentEngine::run(const LatentJob &job, const LatentPrep &prep, LatentStats 
     MFM_HIP_CHECK(hipGetLastError());
     MFM_HIP_CHECK(hipMemcpyAsync(m.h_status, m.status.p, sizeof(LatStatus), hipMemcpyDeviceToHost, s));
     MFM_HIP_CHECK(hipStreamSynchronize(s));
-    if (m.h_status->fail == 1 && use_cv && std::getenv("MFM_LAT_CV_DEBUG")) {
-      const int fc = m.h_status->fail_chunk;
-      int32_t t = 0, l = 0, h = 0;
-      double cum = 0;
-      MFM_HIP_CHECK(hipMemcpy(&t, m.Tc.p + fc, sizeof(int32_t), hipMemcpyDeviceToHost));
-      MFM_HIP_CHECK(hipMemcpy(&l, m.win_lo.p + fc, sizeof(int32_t), hipMemcpyDeviceToHost));
-      MFM_HIP_CHECK(hipMemcpy(&h, m.win_hi.p + fc, sizeof(int32_t), hipMemcpyDeviceToHost));
-      MFM_HIP_CHECK(hipMemcpy(&cum, m.cvcum.p + fc, sizeof(double), hipMemcpyDeviceToHost));
-      std::fprintf(stderr, "[latent cv] attempt %d missed at chunk %d of %d: entering row %d, window [%d, %d] (shift %.1f)\n", attempts, fc, C, t, l, h, cum);
-    }
     if (m.h_status->fail != 1 || ksig >= m.ksig_retry) break;  // (only a missed window is worth a second look)
-  }
-  if (use_cv && std::getenv("MFM_LAT_CV_DEBUG")) {  // how well the control variate tracks the path (chunk by chunk)
-    std::vector<int32_t> tc((size_t)C + 1), lo((size_t)C), hi((size_t)C);
-    std::vector<double> cum((size_t)C + 1);
-    MFM_HIP_CHECK(hipMemcpy(tc.data(), m.Tc.p, sizeof(int32_t) * ((size_t)C + 1), hipMemcpyDeviceToHost));
-    MFM_HIP_CHECK(hipMemcpy(lo.data(), m.win_lo.p, sizeof(int32_t) * (size_t)C, hipMemcpyDeviceToHost));
-    MFM_HIP_CHECK(hipMemcpy(hi.data(), m.win_hi.p, sizeof(int32_t) * (size_t)C, hipMemcpyDeviceToHost));
-    MFM_HIP_CHECK(hipMemcpy(cum.data(), m.cvcum.p, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost));
-    const bool shifted = attempts == 1;
-    double sxx = 0, syy = 0, sxy = 0, sx = 0, sy = 0;
-    int cnt = 0;
-    for (int c = 1; c < C; c++) {
-      if (tc[c] >= n) break;
-      const double mid = 0.5 * ((double)lo[c] + hi[c]) - (shifted ? std::llrint(cum[c]) : 0);  // a-priori centre
-      const double d = (double)tc[c] - mid, v = cum[c];
-      sx += d; sy += v; sxx += d * d; syy += v * v; sxy += d * v;
-      cnt++;
-    }
-    if (cnt > 2) {
-      const double mx = sx / cnt, my = sy / cnt;
-      const double vx = sxx / cnt - mx * mx, vy = syy / cnt - my * my, cxy = sxy / cnt - mx * my;
-      std::fprintf(stderr, "[latent cv] chunks %d attempts %d: rms deviation from the a-priori centre %.1f, rms control variate %.1f, correlation %.3f, "
-                   "rms of (deviation - cv) %.1f; last chunk: deviation %.1f cv %.1f\n", cnt, attempts, std::sqrt(sxx / cnt), std::sqrt(syy / cnt),
-                   cxy / std::sqrt(vx * vy + 1e-300), std::sqrt((sxx - 2 * sxy + syy) / cnt),
-                   (double)tc[cnt] - (0.5 * ((double)lo[cnt] + hi[cnt]) - (shifted ? std::llrint(cum[cnt]) : 0)), cum[cnt]);
-    }
   }
   S.status = m.h_status->fail;
   S.chunks = C;

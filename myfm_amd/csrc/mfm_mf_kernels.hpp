@@ -57,7 +57,7 @@ struct MfArgs {
   const int32_t *tile_row0, *tile_ptr;
   const uint32_t *tent;
   const double *tval;  // !UNIT
-  int tile_bits, n_tiles, swz, ucap;
+  int tile_bits, n_tiles, ucap;
   const double2 *dv;   // per second-level column: (delta of factor f, coefficient of factor f + 1)
   // first-level columns per tile (row order, then the tile's share of never-occurring columns)
   const int4 *udesc;   // {column, length, first row - tile start, group}
@@ -70,7 +70,6 @@ struct MfArgs {
   const double *z_next, *lam_next, *mu_next;
   double alpha;
   int do_apply, do_next;
-  int dbg;  // timing experiments only (results are wrong when set): 1 skip the row-order scan, 2 skip P5, 4 skip P3-P4, 8 no slot stores, 16 no P5 scan, 32 slots tile-major
   // !UNIT: stored values of the first level (CSC, contiguous rows per column)
   const int64_t *colptr;
   const double *cval;
@@ -115,7 +114,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) vo
   d2_t *part = rowbuf + R;                                   // [R / 64 + ucap + 2]
   d2_t *uval = part + (R >> 6) + a.ucap + 2;                 // [ucap]
   long long *uvb = (long long *)(uval + a.ucap);             // [ucap]  (!UNIT)
-  const int b = xcd_swizzle(blockIdx.x, a.n_tiles, a.swz);
+  const int b = xcd_swizzle(blockIdx.x, a.n_tiles);
   const int row0 = a.tile_row0[b];
   const int nr = a.tile_row0[b + 1] - row0;
   const int nt = blockDim.x, tid = threadIdx.x, lane = tid & 63, nw = nt >> 6;
@@ -187,22 +186,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) vo
       if (!UNIT) uvb[tid] = (long long)a.colptr[uj] - d.z;
     }
   }
-  if (a.dbg & 64) {  // (timing experiment: the loads only)
-#pragma unroll
-    for (int k = 0; k < K; k++) asm volatile("" ::"v"(e[k]), "v"(dv[k][0]), "v"(dv[k][1]), "v"(rb[k]));
-    asm volatile("" ::"v"(uold), "v"(uz), "v"(ulam), "v"(umu));
-    return;
-  }
   // ---- P1: (b delta_i, b v_i^{f+1}) to the entry's row
 #pragma unroll
   for (int k = 0; k < K; k++)
     if (u[k] != TILE_PAD) rowbuf[u[k] & rmask] = UNIT ? dv[k] : d2_t{xb[k] * dv[k][0], xb[k] * dv[k][1]};
   __syncthreads();
-  if (a.dbg & 128) {
-#pragma unroll
-    for (int k = 0; k < K; k++) asm volatile("" ::"v"(e[k]));
-    return;
-  }
 
   if (solo_j >= 0) {
     // A tile inside a first-level column longer than a tile: apply the second level's update, leave the tile's partial
@@ -266,7 +254,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) vo
     if (do_next) {
       double s1 = valid ? (-e1) * h[k] : 0.0, s2 = valid ? h[k] * h[k] : 0.0;
       int f = (lane == 0) | (int)((C.heads >> lane) & 1ull);
-      if (!(a.dbg & 1)) wave_segscan2(s1, s2, f);
+      wave_segscan2(s1, s2, f);
       const bool tail = lane == 63 || (((C.heads >> 1) >> lane) & 1ull);
       if (tail) part[C.pbase + cnt] = d2_t{s1, s2};
     } else if (valid) {
@@ -276,7 +264,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) vo
   if (!do_next) return;
   lds_barrier();
 
-  if (a.dbg & 4) return;
   // ---- P3: one thread per first-level column: partials in row order, draw
   for (int uu = tid; uu < nu; uu += nt) {
     if (uu != tid) {  // (more columns than threads: a tile that hosts many never-occurring columns)
@@ -317,7 +304,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) vo
   }
   lds_barrier();
 
-  if (a.dbg & 2) return;
   // ---- P5: item order
 #pragma unroll
   for (int k = 0; k < K; k++) {
@@ -330,15 +316,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(1, 4))) vo
       s1 = (-rr[0]) * hh;
     }
     int f = (int)(flags[k] & 1u);
-    if (!(a.dbg & 16)) wave_segscan2(s1, s2, f);
-    if (a.dbg & 8) {
-      asm volatile("" ::"v"(s1), "v"(s2), "v"(pos[k]));
-    } else if (a.dbg & 32) {  // the same stores, tile-major (contiguous per tile) instead of column-major
-      if (flags[k] & 2u) a.slots[rb[k] + __popcll(__ballot(flags[k] & 1u) & ((2ull << lane) - 1ull)) - 1] = make_double2(s1, s2);
-    } else if (flags[k] & 2u) {
-      // (dbg 256: timing experiment -- all slot stores folded into a 4 MiB window, i.e. cache-resident targets)
-      a.slots[(a.dbg & 256) ? (pos[k] & 0x3ffff) : pos[k]] = make_double2(s1, s2);
-    }
+    wave_segscan2(s1, s2, f);
+    if (flags[k] & 2u) a.slots[pos[k]] = make_double2(s1, s2);
   }
 }
 
@@ -482,7 +461,7 @@ struct MfScoreArgs {
   const int32_t *tile_row0, *tile_ptr;
   const uint32_t *tent;
   const double *tval;
-  int tile_bits, n_tiles, swz;
+  int tile_bits, n_tiles;
   const int32_t *scols;      // second-level column (position in the level) -> feature
   const int4 *udesc;
   const int32_t *ucol_ptr;
@@ -498,7 +477,6 @@ struct MfScoreArgs {
   const double *y;  // may be null
   double2 *eq;
   int ucache;  // > 0: the Vt rows of the tile's first-level columns (at most this many) are staged in LDS
-  int dbg;     // timing experiments (wrong results): 1 no item-row gather, 2 no user-row gather, 4 no final store
 };
 
 // sum over the GS lanes of a lane group (GS a power of two <= 64, groups aligned to GS), valid in the group's LAST lane:
@@ -522,7 +500,7 @@ __global__ __launch_bounds__(512) void k_mf_score(MfScoreArgs a) {
   double *sc = (double *)mf_lds;                  // [R]
   int *ucol = (int *)(sc + R);                    // [ucap] feature of the tile's u-th first-level column
   long long *uvb = (long long *)(ucol + mf_user_cap(a.tile_bits));  // [ucap] (!UNIT) value offset
-  const int b = xcd_swizzle(blockIdx.x, a.n_tiles, a.swz);
+  const int b = xcd_swizzle(blockIdx.x, a.n_tiles);
   const int row0 = a.tile_row0[b];
   const int nr = a.tile_row0[b + 1] - row0;
   const int nt = blockDim.x, tid = threadIdx.x;
@@ -604,7 +582,7 @@ __global__ __launch_bounds__(512) void k_mf_score(MfScoreArgs a) {
 #pragma unroll
       for (int sp = 0; sp < SPL; sp++) {
         vi[q][sp] = make_double2(0.0, 0.0);
-        if (u[q] != TILE_PAD && lig + sp * GS < KP && !(a.dbg & 1))
+        if (u[q] != TILE_PAD && lig + sp * GS < KP)
           vi[q][sp] = ((const double2 *)(a.Vt + (int64_t)ji[q] * a.KS))[lig + sp * GS];
       }
     }
@@ -613,7 +591,7 @@ __global__ __launch_bounds__(512) void k_mf_score(MfScoreArgs a) {
       dot[q] = 0.0;
 #pragma unroll
       for (int sp = 0; sp < SPL; sp++) {
-        if (u[q] != TILE_PAD && lig + sp * GS < KP && !(a.dbg & 2)) {
+        if (u[q] != TILE_PAD && lig + sp * GS < KP) {
           const double2 vu = cached ? uV[lu[q] * KP + lig + sp * GS] : ((const double2 *)(a.Vt + (int64_t)ju[q] * a.KS))[lig + sp * GS];
           dot[q] += vu.x * vi[q][sp].x + vu.y * vi[q][sp].y;
         }
@@ -643,7 +621,6 @@ __global__ __launch_bounds__(512) void k_mf_score(MfScoreArgs a) {
     }
   }
   __syncthreads();
-  if (a.dbg & 4) return;
   for (int i = tid; i < nr; i += nt) {
     const double yv = a.y ? __builtin_nontemporal_load(&a.y[row0 + i]) : 0.0;
     a.eq[row0 + i].x = sc[i] - yv;

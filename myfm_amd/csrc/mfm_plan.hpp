@@ -284,7 +284,7 @@ __global__ __launch_bounds__(1024) void k_cbb_batches(const int64_t *__restrict_
 // hot slots' row ranges. ONE workgroup, batch by batch (the neighbours' rows are stamped as the host form stamps them).
 __global__ __launch_bounds__(1024) void k_cbb_buckets(const ChainBatch *__restrict__ bt, int nb, const int32_t *__restrict__ crow,
                                                        const int32_t *__restrict__ clcol, const double *__restrict__ cx,
-                                                       const int32_t *__restrict__ hrows, int64_t n_rows, int split, int32_t *seen_prev,
+                                                       const int32_t *__restrict__ hrows, int64_t n_rows, int32_t *seen_prev,
                                                        int32_t *seen_next, int32_t *__restrict__ bptr, int32_t *__restrict__ hbptr,
                                                        int32_t *__restrict__ bcls, int32_t *__restrict__ brow, int32_t *__restrict__ blcol,
                                                        double *__restrict__ bx) {
@@ -306,8 +306,8 @@ __global__ __launch_bounds__(1024) void k_cbb_buckets(const ChainBatch *__restri
     for (int i = tid; i <= NB; i += 1024) hc[i] = 0;
     __syncthreads();
     auto key_of = [&](int32_t r) {
-      const bool sn = b == 0 || cbb_ld(&seen_prev[r]) == b - 1 || !(split & 1);
-      const bool un = b + 1 == nb || cbb_ld(&seen_next[r]) == b + 1 || !(split & 2);
+      const bool sn = b == 0 || cbb_ld(&seen_prev[r]) == b - 1;
+      const bool un = b + 1 == nb || cbb_ld(&seen_next[r]) == b + 1;
       const int ord = sn ? (un ? 1 : 2) : (un ? 0 : 3);
       return (int)(((int64_t)r * NB) / nr) * 4 + ord;
     };
@@ -514,10 +514,9 @@ struct ChainRun {
     batched = true;
     bucketed = false;
     // 3. the grid form's row-bucketed copies
-    const int64_t grid_min = std::getenv("MFM_CHAIN_GRID_MIN") ? std::atoll(std::getenv("MFM_CHAIN_GRID_MIN")) : 4096;
-    if (n_batches > 0 && n_cold / n_batches >= grid_min && !std::getenv("MFM_NO_CHAIN_GRID") && !std::getenv("MFM_NO_CB_MERGE")) {
+    const int64_t grid_min = env_i64("MFM_CHAIN_GRID_MIN", 4096);
+    if (n_batches > 0 && n_cold / n_batches >= grid_min && !env_flag("MFM_NO_CHAIN_GRID")) {
       constexpr int NB = CB_BUCKETS;
-      const int split = std::getenv("MFM_NO_CB_PERSIST") ? 0 : std::getenv("MFM_CB_SPLIT") ? std::atoi(std::getenv("MFM_CB_SPLIT")) : 3;
       DevBuf<int32_t> seen_prev, seen_next;
       seen_prev.alloc((size_t)n_rows);
       seen_next.alloc((size_t)n_rows);
@@ -530,7 +529,7 @@ struct ChainRun {
       bk_lcol.alloc((size_t)n_cold);
       bk_x.alloc((size_t)n_cold);
       hipLaunchKernelGGL(k_cbb_buckets, dim3(1), dim3(1024), 0, s, batches.p, n_batches, cold_row.p, cold_lcol.p, cold_x.p, hot_rows.p, n_rows,
-                         split, seen_prev.p, seen_next.p, bk_ptr.p, hbk_ptr.p, bk_cls.p, bk_row.p, bk_lcol.p, bk_x.p);
+                         seen_prev.p, seen_next.p, bk_ptr.p, hbk_ptr.p, bk_cls.p, bk_row.p, bk_lcol.p, bk_x.p);
       MFM_HIP_CHECK(hipGetLastError());
       MFM_HIP_CHECK(hipStreamSynchronize(s));
       bucketed = true;
@@ -663,8 +662,8 @@ struct ChainRun {
     hot_rows.upload(hrows);
     batched = true;
     // the grid form (k_cb_*) also gets the row-bucketed copies
-    const int64_t grid_min = std::getenv("MFM_CHAIN_GRID_MIN") ? std::atoll(std::getenv("MFM_CHAIN_GRID_MIN")) : 4096;
-    if (n_batches > 0 && n_cold / n_batches >= grid_min && !std::getenv("MFM_NO_CHAIN_GRID") && !std::getenv("MFM_NO_CB_MERGE")) {
+    const int64_t grid_min = env_i64("MFM_CHAIN_GRID_MIN", 4096);
+    if (n_batches > 0 && n_cold / n_batches >= grid_min && !env_flag("MFM_NO_CHAIN_GRID")) {
       constexpr int NB = CB_BUCKETS;
       auto bucket = [&](int32_t r) { return (int)(((int64_t)r * NB) / std::max<int64_t>(n_rows, 1)); };
       std::vector<int32_t> bptr((size_t)n_batches * (NB + 1), 0), hbptr((size_t)n_batches * (NB + 1), 0);
@@ -677,8 +676,6 @@ struct ChainRun {
       // and by column inside a class, so that "update near", "statistics near" and "update far" are contiguous and "statistics
       // far" is the two ends.
       std::vector<int32_t> seen_prev((size_t)n_rows, -1), seen_next((size_t)n_rows, -1);
-      // (the two-launch form, MFM_NO_CB_PERSIST, walks a range as ONE column-ordered run: a single class)
-      const int split = std::getenv("MFM_NO_CB_PERSIST") ? 0 : std::getenv("MFM_CB_SPLIT") ? std::atoi(std::getenv("MFM_CB_SPLIT")) : 3;  // (bit 0: statistics, bit 1: update)
       auto stamp = [&](std::vector<int32_t> &seen, int b) {
         const ChainBatch &B = bt[b];
         for (int p = B.cold_b; p < B.cold_e; p++) seen[crow[p]] = b;
@@ -689,7 +686,7 @@ struct ChainRun {
         const int cb = B.cold_b, ce = B.cold_e;
         if (b + 1 < n_batches) stamp(seen_next, b + 1);
         auto order_of = [&](int32_t r) {
-          const bool sn = b == 0 || seen_prev[r] == b - 1 || !(split & 1), un = b + 1 == n_batches || seen_next[r] == b + 1 || !(split & 2);
+          const bool sn = b == 0 || seen_prev[r] == b - 1, un = b + 1 == n_batches || seen_next[r] == b + 1;
           return sn ? (un ? 1 : 2) : (un ? 0 : 3);
         };
         int cntb[NB * 4 + 1] = {0};
@@ -1000,11 +997,9 @@ struct StepPlan {
   static bool build_scattered(const HostCsr &csc, const std::vector<int32_t> &cols, int64_t lnnz, bool unit, ParLevel &L,
                               int tile_bits = 0, const std::vector<int32_t> *bounds = nullptr, const DevCscView *dev = nullptr,
                               const LevelScan *scan = nullptr) {
-    int64_t min_nnz = 1 << 16;  // (measured: the tile path and the fusions it enables win from ~10^5 entries per level on)
-    if (const char *e = std::getenv("MFM_SCATTER_MIN_NNZ")) min_nnz = std::atoll(e);
-    if (lnnz < min_nnz) return false;
-    if (const char *e = std::getenv("MFM_NO_SCATTER"))
-      if (std::atoi(e)) return false;
+    // (measured: the tile path and the fusions it enables win from ~10^5 entries per level on)
+    const int64_t min_nnz = env_i64("MFM_SCATTER_MIN_NNZ", 1 << 16);
+    if (lnnz < min_nnz || env_int("MFM_NO_SCATTER", 0)) return false;
     int64_t far = 0;
     if (scan && scan->valid) {
       far = scan->far;  // (counted on the device: level_scan_device)
@@ -1020,9 +1015,9 @@ struct StepPlan {
       if (2 * lnnz < N || (int64_t)cols.size() >= ((int64_t)1 << (32 - tile_bits)) - 1) tile_bits = 0;
     }
     if (tile_bits > 0) {
-      if (dev && dev->colptr && !std::getenv("MFM_HOST_TILE_PACK") &&
+      if (dev && dev->colptr &&
           build_tiled_device(*dev, csc, cols, lnnz, unit, L, tile_bits, bounds)) {
-        if (std::getenv("MFM_PLAN_CHECK")) {  // tests: the device layout must be the host layout, array by array
+        if (env_flag("MFM_PLAN_CHECK")) {  // tests: the device layout must be the host layout, array by array
           ParLevel H;
           if (!build_tiled(csc, cols, lnnz, unit, H, tile_bits, bounds)) throw Error(MFM_ERR_RUNTIME, "plan check: host layout failed");
           auto same = [](const auto &a, const auto &b, size_t n, const char *what) {
@@ -1049,8 +1044,7 @@ struct StepPlan {
       }
       return build_tiled(csc, cols, lnnz, unit, L, tile_bits, bounds);
     }
-    int64_t RB = SCAT_RB;
-    if (const char *e = std::getenv("MFM_SCAT_RB")) RB = std::max<int64_t>(1024, std::atoll(e));
+    const int64_t RB = SCAT_RB;
     const int64_t nb = (N + RB - 1) / RB;
     std::vector<int64_t> bptr((size_t)nb + 1, 0);
     for (int32_t j : cols)
@@ -1632,8 +1626,8 @@ struct StepPlan {
     } else if (twin && !twin->h_level.empty() && (int64_t)twin->h_level.size() == csc.rows) {
       level = twin->h_level;
       n_levels = twin->n_levels;
-    } else if (dev_csc && !std::getenv("MFM_HOST_LEVELS") && column_levels_device(*dev_csc, level, n_levels)) {
-      if (std::getenv("MFM_PLAN_CHECK")) {  // tests: the device schedule must be the host schedule
+    } else if (dev_csc && column_levels_device(*dev_csc, level, n_levels)) {
+      if (env_flag("MFM_PLAN_CHECK")) {  // tests: the device schedule must be the host schedule
         std::vector<int32_t> hl;
         const int32_t hn = column_levels(csc, hl);
         if (hn != n_levels || hl != level) throw Error(MFM_ERR_RUNTIME, "plan check: device and host level schedules differ");
@@ -1656,7 +1650,7 @@ struct StepPlan {
       {  // the twin has the same run at the same place: its arrays serve both sweeps
         const size_t si = steps.size() - 1;
         const Step *tw = twin && si < twin->steps.size() && twin->steps[si].is_chain ? &twin->steps[si] : nullptr;
-        if (tw && !sharded && !twin->sharded && tw->chain.h_cols == run && !std::getenv("MFM_NO_CHAIN_TWIN")) {
+        if (tw && !sharded && !twin->sharded && tw->chain.h_cols == run) {
           s.chain.borrow(tw->chain);
           launches += 1;
           run.clear();
@@ -1676,12 +1670,11 @@ struct StepPlan {
       // state too large for the LDS chain of any policy: also keep the conflict-batched form
       // (a main-table plan never launches the stream: building it, and skipping the conflict batches for it, would leave a long main
       //  chain to the single-workgroup kernel)
-      const bool stream_allowed =
-          block_plan && !std::getenv("MFM_NO_CB_STREAM") && !std::getenv("MFM_NO_CB_PERSIST") && !std::getenv("MFM_NO_CHAIN_GRID");
+      const bool stream_allowed = block_plan && !env_flag("MFM_NO_CB_STREAM") && !env_flag("MFM_NO_CHAIN_GRID");
       auto try_stream = [&]() {
         CsStreamInfo ci;
         s.chain.stream = cs_stream_build(csc, run, &ci);
-        if (std::getenv("MFM_SETUP_TIMING")) {
+        if (env_flag("MFM_SETUP_TIMING")) {
           if (s.chain.stream)
             std::fprintf(stderr, "[plan] streamed chain of %zu columns: steps of %d columns, window %d steps, %d ranges, %d LDS slots, %lld cold + %lld "
                                  "hot entries (<= %d hot per column), <= %d entering / %d leaving rows per step, planned in %.3f s\n",
@@ -1691,27 +1684,27 @@ struct StepPlan {
         }
       };
       const bool chain_batched_wanted =
-          (csc.cols > 1900 || std::getenv("MFM_CHAIN_FORCE_BATCHED")) && run.size() >= 2 && !std::getenv("MFM_NO_CHAIN_BATCHED");
+          (csc.cols > 1900 || env_flag("MFM_CHAIN_FORCE_BATCHED")) && run.size() >= 2;
       // Long columns (the cold parts of a batch would run on the whole GPU: relation blocks with 10^5..10^6 rows): the streamed form is
       // tried FIRST, and when it can be built the conflict batches -- then never launched -- are not built at all (0.06 s of device
       // work and ~100 MB per big block at config 5). The checker mode builds both: the batches' device / host comparison stays tested.
       bool stream_tried = false;
-      if (chain_batched_wanted && stream_allowed && !std::getenv("MFM_PLAN_CHECK") && !std::getenv("MFM_CHAIN_FORCE_BATCHED") &&
+      if (chain_batched_wanted && stream_allowed && !env_flag("MFM_PLAN_CHECK") && !env_flag("MFM_CHAIN_FORCE_BATCHED") &&
           run_nnz >= (int64_t)256 * (int64_t)run.size()) {
         try_stream();
         stream_tried = true;
       }
       if (chain_batched_wanted && !s.chain.stream) {
-        const int hot_cap = std::getenv("MFM_CHAIN_HOT_CAP") ? std::max(64, std::atoi(std::getenv("MFM_CHAIN_HOT_CAP"))) : 1200;
+        const int hot_cap = env_flag("MFM_CHAIN_HOT_CAP") ? std::max(64, env_int("MFM_CHAIN_HOT_CAP", 0)) : 1200;
         // on the device when the matrix's CSC is there (relation blocks, the main table): the host form is the fall-back and,
         // under MFM_PLAN_CHECK, the checker
-        const bool on_dev = dev_csc && !std::getenv("MFM_HOST_CHAIN_BATCHES") && s.chain.build_batched_device(*dev_csc, run, hot_cap);
-        if (std::getenv("MFM_SETUP_TIMING"))
+        const bool on_dev = dev_csc && s.chain.build_batched_device(*dev_csc, run, hot_cap);
+        if (env_flag("MFM_SETUP_TIMING"))
           std::fprintf(stderr, "[plan] conflict batches of a %zu-column chain run: %s (%d batches, %lld cold entries)\n", run.size(),
                        on_dev ? "device" : "host", on_dev ? s.chain.n_batches : -1, on_dev ? (long long)s.chain.n_cold : -1ll);
         if (!on_dev) {
           s.chain.build_batched(csc, run, hot_cap);
-        } else if (std::getenv("MFM_PLAN_CHECK")) {
+        } else if (env_flag("MFM_PLAN_CHECK")) {
           ChainRun chk;
           chk.build_batched(csc, run, hot_cap);
           const std::string diff = s.chain.compare_batched(chk, dev_csc->stream);
@@ -1755,9 +1748,9 @@ struct StepPlan {
       // first look at the level -- contiguous columns? far-apart rows? every row exactly once? -- on the device when the CSC is there
       const bool want_once = steps.size() == 1 && lnnz == csc.cols;
       LevelScan scan;
-      if (dev_csc && !std::getenv("MFM_HOST_LEVEL_SCAN")) {
+      if (dev_csc) {
         scan = level_scan_device(*dev_csc, L.cols_all.p, L.n_all, want_once);
-        if (scan.valid && std::getenv("MFM_PLAN_CHECK")) {  // tests: the host's counts
+        if (scan.valid && env_flag("MFM_PLAN_CHECK")) {  // tests: the host's counts
           int64_t gaps = 0, far = 0, twice = 0;
           std::vector<char> seen(want_once ? (size_t)csc.cols : 0, 0);
           for (int32_t j : by_level[l])
@@ -1795,16 +1788,14 @@ struct StepPlan {
       }
       bin_columns(csc, by_level[l], L, cap_w1, cap_w4, cap_w16, cap_wg, coop_max);
       {
-        bool contig = !std::getenv("MFM_NO_CONTIG");
-        if (scan.valid) contig = contig && scan.gaps == 0;
+        bool contig = !scan.valid || scan.gaps == 0;
         for (size_t c = 0; !scan.valid && contig && c < by_level[l].size(); c++) {
           const int32_t j = by_level[l][c];
           for (int64_t p = csc.ptr[j] + 1; contig && p < csc.ptr[j + 1]; p++) contig = csc.idx[p] == csc.idx[p - 1] + 1;
         }
         L.contig = contig;
       }
-      if (steps.size() == 1 && L.contig && L.first_and_once && allow_scatter && (!sharded || sharded_tiles) && tile_bits > 0 &&
-          !std::getenv("MFM_NO_ALIGNED_TILES"))
+      if (steps.size() == 1 && L.contig && L.first_and_once && allow_scatter && (!sharded || sharded_tiles) && tile_bits > 0)
         build_aligned_tiles(csc, by_level[l], (int64_t)1 << tile_bits);
       if (steps.size() == 1 && sharded_tiles && aligned_tiles) {
         std::vector<int32_t> sp, loc;
@@ -1877,15 +1868,6 @@ struct LongScratch {
   }
 };
 
-static inline int xcd_swizzle_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = std::getenv("MFM_XCD_SWIZZLE");
-    v = e ? std::atoi(e) : 1;
-  }
-  return v;
-}
-
 struct SweepClasses {
   int light, heavy, coop, hstats, hdraw, happly, chain, scat;
 };
@@ -1923,12 +1905,12 @@ static void launch_binned_level(hipStream_t s, Timing &tm, const ParLevel &L, co
   if (L.n_wg + L.n_w16) {
     TimedLaunch t(tm, s, kc.heavy, P::BYTES * L.nnz_heavy);
     hipLaunchKernelGGL((k_level_heavy<P, UNIT>), dim3(L.n_wg + (L.n_w16 + 3) / 4), dim3(WG), 0, s, a, L.cols_wg.p, L.n_wg,
-                       L.cols_w16.p, L.n_w16, xcd_swizzle_enabled());
+                       L.cols_w16.p, L.n_w16);
   }
   if (L.n_w4 + L.n_w1) {
     TimedLaunch t(tm, s, kc.light, P::BYTES * L.nnz_light);
     hipLaunchKernelGGL((k_level_light<P, UNIT>), dim3((L.n_w4 + 3) / 4 + (L.n_w1 + 3) / 4), dim3(WG), 0, s, a, L.cols_w4.p,
-                       L.n_w4, L.cols_w1.p, L.n_w1, xcd_swizzle_enabled());
+                       L.n_w4, L.cols_w1.p, L.n_w1);
   }
 }
 
@@ -1950,7 +1932,7 @@ static void run_plan_t(hipStream_t s, Timing &tm, const StepPlan &plan, const Sw
     if (st.is_chain) {
       TimedLaunch t(tm, s, kc.chain, P::BYTES * st.chain.nnz);
       const size_t lds_bytes = (size_t)plan.n_state_rows * (P::REC_DOUBLES > 2 ? P::REC_DOUBLES + 2 : P::REC_DOUBLES) * sizeof(double);
-      const bool force_batched = st.chain.batched && std::getenv("MFM_CHAIN_FORCE_BATCHED");
+      const bool force_batched = st.chain.batched && env_flag("MFM_CHAIN_FORCE_BATCHED");
       if (plan.n_state_rows > 0 && lds_bytes <= CHAIN_LDS_MAX && !force_batched) {
         hipLaunchKernelGGL((k_chain_lds<P>), dim3(1), dim3(WAVE), lds_bytes, s, a, st.chain.desc.p, st.chain.n_cols,
                            plan.n_state_rows, (int)P::REC_DOUBLES);
@@ -1976,8 +1958,8 @@ static void run_plan_t(hipStream_t s, Timing &tm, const StepPlan &plan, const Sw
           raised.mark();
         }
         // batches with many cold entries: cold statistics / updates as grid launches (one CU cannot stream them)
-        const int64_t grid_min = std::getenv("MFM_CHAIN_GRID_MIN") ? std::atoll(std::getenv("MFM_CHAIN_GRID_MIN")) : 4096;
-        if (C.n_batches > 0 && C.n_cold / C.n_batches >= grid_min && !std::getenv("MFM_NO_CHAIN_GRID")) {
+        const int64_t grid_min = env_i64("MFM_CHAIN_GRID_MIN", 4096);
+        if (C.n_batches > 0 && C.n_cold / C.n_batches >= grid_min && !env_flag("MFM_NO_CHAIN_GRID")) {
           constexpr int GMAX = 64;  // workgroups of a cold launch
           if (ls.cb_part.n < (size_t)GMAX * CHAINB_MAXCOLS) ls.cb_part.alloc((size_t)GMAX * CHAINB_MAXCOLS);
           if (ls.cb_oldnew.n < (size_t)CHAINB_MAXCOLS) ls.cb_oldnew.alloc((size_t)CHAINB_MAXCOLS);
@@ -1995,8 +1977,7 @@ static void run_plan_t(hipStream_t s, Timing &tm, const StepPlan &plan, const Sw
             if (ls.cb_hot2.n < hot16) ls.cb_hot2.alloc(hot16);
             if (ls.cb_colpack.n < (size_t)8 * CHAINB_MAXCOLS) ls.cb_colpack.alloc((size_t)8 * CHAINB_MAXCOLS);
             if (ls.cb_part.n < (size_t)CB_BUCKETS * CHAINB_MAXCOLS) ls.cb_part.alloc((size_t)CB_BUCKETS * CHAINB_MAXCOLS);
-            static const bool persist = !std::getenv("MFM_NO_CB_PERSIST");
-            if (persist && ls.error.p) {
+            if (ls.error.p) {
               // the whole batch sequence as one launch: the hot walker + CB_BUCKETS row-range workgroups, counters instead of
               // kernel boundaries
               if (!ls.cb_sync.p) ls.cb_sync.alloc(1);
@@ -2025,10 +2006,8 @@ static void run_plan_t(hipStream_t s, Timing &tm, const StepPlan &plan, const Sw
               g.colpack = ls.cb_colpack.p;
               g.sync = ls.cb_sync.p;
               g.error = ls.error.p;
-              static const int cb_dbg = std::getenv("MFM_CB_DBG") ? std::atoi(std::getenv("MFM_CB_DBG")) : 0;
-              g.dbg = cb_dbg;
               // MFM_CB_PROF=n: phase sums of the hot walker and of range 0 (s_memrealtime, thread 0), printed every n launches
-              static const int cb_prof = std::getenv("MFM_CB_PROF") ? std::atoi(std::getenv("MFM_CB_PROF")) : 0;
+              static const int cb_prof = env_int("MFM_CB_PROF", 0);
               static DevBuf<unsigned long long> prof_buf;
               static long prof_launches = 0;
               g.prof = nullptr;
@@ -2097,7 +2076,6 @@ static void run_plan_t(hipStream_t s, Timing &tm, const StepPlan &plan, const Sw
     if (L.scattered && L.tiled) {
       if constexpr (P::REC_DOUBLES == 2 && !P::QFREE) {
         TimedLaunch t(tm, s, kc.scat, P::BYTES * L.n_ent);
-        const int swz = xcd_swizzle_enabled();
         const size_t lds = sizeof(double2) << L.tile_bits;
         const int nt = tile_threads(L.tile_bits);
         if (lds > 64 * 1024) {  // beyond the default dynamic-LDS limit: opt in once per kernel
@@ -2113,25 +2091,24 @@ static void run_plan_t(hipStream_t s, Timing &tm, const StepPlan &plan, const Sw
         hipLaunchKernelGGL(k_tile_old, dim3((L.n_cols + 255) / 256), dim3(256), 0, s, a.theta, L.scols.p, L.n_cols,
                            ls.vnext_col.p);
         hipLaunchKernelGGL((k_tile_stats<P, UNIT>), dim3(L.n_tiles), dim3(nt), lds, s, a, L.tent.p, L.ent_val.p, L.tile_ptr.p,
-                           L.tile_row0.p, ls.vnext_col.p, L.run_base.p, L.slot_pos.p, L.slots.p, L.tile_bits, L.n_tiles, swz,
+                           L.tile_row0.p, ls.vnext_col.p, L.run_base.p, L.slot_pos.p, L.slots.p, L.tile_bits, L.n_tiles,
                            (const int32_t *)nullptr);
         hipLaunchKernelGGL((k_tile_draw<P>), dim3((L.n_cols + 3) / 4), dim3(WG), 0, s, a, L.scols.p, L.n_cols, L.slot_ptr.p,
                            L.slots.p, ls.oldnew_col.p);
         hipLaunchKernelGGL((k_tile_apply<P, UNIT>), dim3(L.n_tiles), dim3(nt), lds, s, a, L.tent.p, L.ent_val.p,
-                           L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, swz);
+                           L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles);
       }
       continue;
     }
     if (L.scattered) {
       TimedLaunch t(tm, s, kc.scat, P::BYTES * L.n_ent);
-      const int swz = xcd_swizzle_enabled();
       const int n_wg_s = (int)((L.n_ent + WG - 1) / WG);
       hipLaunchKernelGGL((k_scat_stats<P, UNIT>), dim3(n_wg_s), dim3(WG), 0, s, a, L.ent.p, L.ent_val.p, L.n_ent, L.run_base.p,
-                         L.slots.p, n_wg_s, swz);
+                         L.slots.p, n_wg_s);
       hipLaunchKernelGGL((k_scat_draw<P>), dim3((L.n_cols + 3) / 4), dim3(WG), 0, s, a, L.scols.p, L.n_cols, L.slot_ptr.p,
                          L.slot_idx.p, L.slots.p, ls.oldnew_col.p);
       hipLaunchKernelGGL((k_scat_apply<PA, UNIT>), dim3(n_wg_s), dim3(WG), 0, s, a, L.ent.p, L.ent_val.p, L.n_ent,
-                           ls.oldnew_col.p, n_wg_s, swz);
+                           ls.oldnew_col.p, n_wg_s);
       continue;
     }
     if (first_builds_q && &st == &plan.steps.front())
@@ -2273,7 +2250,7 @@ static void run_plan_sharded_t(hipStream_t s, Timing &tm, const StepPlan &plan, 
       TimedLaunch t(tm, s, kc.scat, P::STAT_BYTES * L.n_ent);
       const int n_wg_s = (int)((L.n_ent + WG - 1) / WG);
       hipLaunchKernelGGL((k_scat_stats<P, UNIT>), dim3(n_wg_s), dim3(WG), 0, s, a, L.ent.p, L.ent_val.p, L.n_ent, L.run_base.p,
-                         L.slots.p, n_wg_s, xcd_swizzle_enabled());
+                         L.slots.p, n_wg_s);
       hipLaunchKernelGGL(k_scat_sum, dim3((L.n_cols + 3) / 4), dim3(WG), 0, s, L.scols.p, L.n_cols, L.slot_ptr.p, L.slot_idx.p,
                          L.slots.p, S);
     } else {
@@ -2298,7 +2275,7 @@ static void run_plan_sharded_t(hipStream_t s, Timing &tm, const StepPlan &plan, 
       TimedLaunch t(tm, s, kc.scat, P::BYTES * L.n_ent);
       const int n_wg_s = (int)((L.n_ent + WG - 1) / WG);
       hipLaunchKernelGGL((k_scat_apply<P, UNIT>), dim3(n_wg_s), dim3(WG), 0, s, a, L.ent.p, L.ent_val.p, L.n_ent,
-                         ls.oldnew_col.p, n_wg_s, xcd_swizzle_enabled());
+                         ls.oldnew_col.p, n_wg_s);
     } else {
       const int grid = L.n_wg + (L.n_w16 + 3) / 4 + (L.n_w4 + 3) / 4 + (L.n_w1 + 3) / 4;
       if (grid) {
@@ -2378,7 +2355,7 @@ static inline bool plan_supports_fused_next(const StepPlan &plan) {
 
 // statistics (unless already produced by the previous factor's fused pass) and draw of a row-tile level
 template <class P, bool UNIT>
-static void launch_tile_head(hipStream_t s, const ParLevel &L, const SweepArgs &a, LongScratch &ls, int swz,
+static void launch_tile_head(hipStream_t s, const ParLevel &L, const SweepArgs &a, LongScratch &ls,
                              const double *theta_next = nullptr, bool have_stats = false) {
   const size_t lds = sizeof(double2) << L.tile_bits;
   const int nt = tile_threads(L.tile_bits);
@@ -2386,7 +2363,7 @@ static void launch_tile_head(hipStream_t s, const ParLevel &L, const SweepArgs &
     hipLaunchKernelGGL(k_tile_old, dim3((L.n_cols + 255) / 256), dim3(256), 0, s, a.theta, L.scols.p, L.n_cols, ls.vnext_col.p);
     hipLaunchKernelGGL((k_tile_stats<P, UNIT, true>), dim3(L.n_tiles), dim3(nt), lds, s, a, L.tent.p, L.ent_val.p,
                        L.tile_ptr.p, L.tile_row0.p, ls.vnext_col.p, L.run_base.p, L.slot_pos.p, L.slots.p, L.tile_bits,
-                       L.n_tiles, swz, (const int32_t *)nullptr);
+                       L.n_tiles, (const int32_t *)nullptr);
   }
   hipLaunchKernelGGL((k_tile_draw<P>), dim3((L.n_cols + 3) / 4), dim3(WG), 0, s, a, L.scols.p, L.n_cols, L.slot_ptr.p,
                      L.slots.p, ls.oldnew_col.p, theta_next, ls.vnext_col.p);
@@ -2440,7 +2417,6 @@ static void run_sweep_soa_multi(hipStream_t s, Timing &tm, const StepPlan &plan,
   // comm != null: row-sharded (plan.sharded_tiles): every tile level's slot sums are all-reduced before its draw, the
   // special first-level columns go through run_level_sharded, the locally complete ones stay local (see
   // run_sweep_soa_sharded)
-  const int swz = xcd_swizzle_enabled();
   raise_fused_lds_limit<UNIT>();
   {
     static DeviceOnce raised;
@@ -2455,7 +2431,7 @@ static void run_sweep_soa_multi(hipStream_t s, Timing &tm, const StepPlan &plan,
   const size_t lds = sizeof(double2) << T1.tile_bits;
   const int nt = tile_threads(T1.tile_bits);
   // every tile level a one-hot field (one entry per row): the next q comes from the entry streams (MULTIQ)
-  bool multiq = nl - 1 <= 7 && !std::getenv("MFM_NO_FUSED_MULTIQ");
+  bool multiq = nl - 1 <= 7 && !env_flag("MFM_NO_FUSED_MULTIQ");
   for (int l = 1; l < nl; l++) multiq = multiq && plan.steps[l].par.covers_rows_once;
   if (ls.vnext_lvl.size() < (size_t)nl) ls.vnext_lvl.resize((size_t)nl);
   for (int l = 1; l < nl; l++)
@@ -2503,7 +2479,7 @@ static void run_sweep_soa_multi(hipStream_t s, Timing &tm, const StepPlan &plan,
                          ls.told_col.p);
       hipLaunchKernelGGL((k_tile_stats<PMainV, UNIT, true>), dim3(T1.n_tiles), dim3(nt), lds, s, a, T1.tent.p, T1.ent_val.p,
                          T1.tile_ptr.p, T1.tile_row0.p, ls.told_col.p, T1.run_base.p, T1.slot_pos.p, T1.slots.p, T1.tile_bits,
-                         T1.n_tiles, swz, (const int32_t *)nullptr);
+                         T1.n_tiles, (const int32_t *)nullptr);
     }
     const double *tn = next ? (const double *)an.theta : (const double *)nullptr;
     {
@@ -2516,13 +2492,13 @@ static void run_sweep_soa_multi(hipStream_t s, Timing &tm, const StepPlan &plan,
       hipLaunchKernelGGL(k_tile_old, dim3((S.n_cols + 255) / 256), dim3(256), 0, s, a.theta, S.scols.p, S.n_cols, ls.told_col.p);
       hipLaunchKernelGGL((k_tile_apply_stats<UNIT>), dim3(A.n_tiles), dim3(nt), lds, s, a, A.tent.p, A.ent_val.p, A.tile_ptr.p,
                          ls.oldnew_col.p, S.tent.p, S.ent_val.p, S.tile_ptr.p, ls.told_col.p, S.run_base.p, S.slot_pos.p,
-                         S.slots.p, A.tile_row0.p, A.tile_bits, A.n_tiles, swz);
+                         S.slots.p, A.tile_row0.p, A.tile_bits, A.n_tiles);
       draw(l + 1, a, tn);
     }
     if (!next) {
       TimedLaunch t(tm, s, kc.scat, 28.0 * TL.n_ent);
       hipLaunchKernelGGL((k_tile_apply<PMainV, UNIT, true, false>), dim3(TL.n_tiles), dim3(nt), lds, s, soa_final_args(a, true),
-                         TL.tent.p, TL.ent_val.p, TL.tile_ptr.p, TL.tile_row0.p, ls.oldnew_col.p, TL.tile_bits, TL.n_tiles, swz);
+                         TL.tent.p, TL.ent_val.p, TL.tile_ptr.p, TL.tile_row0.p, ls.oldnew_col.p, TL.tile_bits, TL.n_tiles);
       continue;
     }
     {
@@ -2545,10 +2521,10 @@ static void run_sweep_soa_multi(hipStream_t s, Timing &tm, const StepPlan &plan,
       }
       if (multiq)
         hipLaunchKernelGGL((k_tile_apply_next<UNIT, false, true, true>), dim3(TL.n_tiles), dim3(nt), lds + 256, s, af, TL.tent.p,
-                           TL.ent_val.p, TL.tile_ptr.p, TL.tile_row0.p, ls.oldnew_col.p, TL.tile_bits, TL.n_tiles, swz, fa);
+                           TL.ent_val.p, TL.tile_ptr.p, TL.tile_row0.p, ls.oldnew_col.p, TL.tile_bits, TL.n_tiles, fa);
       else
         hipLaunchKernelGGL((k_tile_apply_next<UNIT, false, true>), dim3(TL.n_tiles), dim3(nt), lds + 256, s, af, TL.tent.p,
-                           TL.ent_val.p, TL.tile_ptr.p, TL.tile_row0.p, ls.oldnew_col.p, TL.tile_bits, TL.n_tiles, swz, fa);
+                           TL.ent_val.p, TL.tile_ptr.p, TL.tile_row0.p, ls.oldnew_col.p, TL.tile_bits, TL.n_tiles, fa);
     }
     launch_long_finish<UNIT>(s, tm, plan, T1, an, ls, kc, 1, lds, nt, ls.vnext_lvl[1].p);
     first_level_rest(an);
@@ -2556,7 +2532,7 @@ static void run_sweep_soa_multi(hipStream_t s, Timing &tm, const StepPlan &plan,
       TimedLaunch t(tm, s, kc.scat, 20.0 * plan.n_solo_tiles * (1 << T1.tile_bits));
       hipLaunchKernelGGL((k_tile_stats<PMainV, UNIT, true>), dim3(plan.n_solo_tiles), dim3(nt), lds, s, an, T1.tent.p,
                          T1.ent_val.p, T1.tile_ptr.p, T1.tile_row0.p, ls.vnext_lvl[1].p, T1.run_base.p, T1.slot_pos.p,
-                         T1.slots.p, T1.tile_bits, T1.n_tiles, swz, plan.solo_tiles.p);
+                         T1.slots.p, T1.tile_bits, T1.n_tiles, plan.solo_tiles.p);
     }
   }
   MFM_HIP_CHECK(hipGetLastError());
@@ -2567,14 +2543,13 @@ static void run_sweep_soa_multi(hipStream_t s, Timing &tm, const StepPlan &plan,
 template <bool UNIT, class ArgsOf>
 static void run_sweep_soa(hipStream_t s, Timing &tm, const StepPlan &plan, ArgsOf args, int f_begin, int f_end,
                           LongScratch &ls, const SweepClasses &kc, bool fuse) {
-  if (fuse && plan_supports_fused_multi(plan) && !std::getenv("MFM_NO_FUSED_MULTI")) {
+  if (fuse && plan_supports_fused_multi(plan) && !env_flag("MFM_NO_FUSED_MULTI")) {
     run_sweep_soa_multi<UNIT>(s, tm, plan, args, f_begin, f_end, ls, kc);
     return;
   }
-  const int swz = xcd_swizzle_enabled();
   if (fuse) raise_fused_lds_limit<UNIT>();
   // two-level plan: the fused pass also produces the next factor's last-level statistics
-  const int fuse_stats = fuse && plan.steps.size() == 2 && !std::getenv("MFM_NO_FUSED_STATS") ? 1 : 0;
+  const int fuse_stats = fuse && plan.steps.size() == 2 ? 1 : 0;
   {
     static DeviceOnce raised;  // tiles beyond the default dynamic-LDS limit: opt in once
     if (raised.need() && plan.tile_bits > 12) {
@@ -2599,10 +2574,10 @@ static void run_sweep_soa(hipStream_t s, Timing &tm, const StepPlan &plan, ArgsO
         if (last && fuse && f + 1 < f_end) {
           SweepArgs an = args(f + 1);
           an.row0 = plan.col_row0.p;
-          const bool two = plan.steps.size() == 2 && L.covers_rows_once && !std::getenv("MFM_NO_FUSED_TWO");
+          const bool two = plan.steps.size() == 2 && L.covers_rows_once;
           {
             TimedLaunch t(tm, s, kc.scat, 20.0 * L.n_ent);
-            launch_tile_head<PMainV, UNIT>(s, L, a, ls, swz, an.theta, fuse_stats && f > f_begin);
+            launch_tile_head<PMainV, UNIT>(s, L, a, ls, an.theta, fuse_stats && f > f_begin);
           }
           {
             // algorithmic bytes of the FUSED pass: e, q read + written once (32 B / row), the 4-byte entry stream
@@ -2616,10 +2591,10 @@ static void run_sweep_soa(hipStream_t s, Timing &tm, const StepPlan &plan, ArgsO
                         nullptr,    nullptr,      nullptr};
             if (two)
               hipLaunchKernelGGL((k_tile_apply_next<UNIT, true>), dim3(L.n_tiles), dim3(nt), lds + 256, s, af, L.tent.p,
-                                 L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, swz, fa);
+                                 L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, fa);
             else
               hipLaunchKernelGGL((k_tile_apply_next<UNIT, false>), dim3(L.n_tiles), dim3(nt), lds + 256, s, af, L.tent.p,
-                                 L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, swz, fa);
+                                 L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, fa);
           }
           // first-level columns longer than a tile: draw from their tiles' partial statistics, second pass
           launch_long_finish<UNIT>(s, tm, plan, L, an, ls, kc, fuse_stats, lds, nt);
@@ -2627,19 +2602,19 @@ static void run_sweep_soa(hipStream_t s, Timing &tm, const StepPlan &plan, ArgsO
             TimedLaunch t(tm, s, kc.scat, 20.0 * plan.n_solo_tiles * (1 << L.tile_bits));
             hipLaunchKernelGGL((k_tile_stats<PMainV, UNIT, true>), dim3(plan.n_solo_tiles), dim3(nt), lds, s, an, L.tent.p,
                                L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.vnext_col.p, L.run_base.p, L.slot_pos.p,
-                               L.slots.p, L.tile_bits, L.n_tiles, swz, plan.solo_tiles.p);
+                               L.slots.p, L.tile_bits, L.n_tiles, plan.solo_tiles.p);
           }
           continue;
         }
         TimedLaunch t(tm, s, kc.scat, (last ? 48.0 : 56.0) * L.n_ent);
-        launch_tile_head<PMainV, UNIT>(s, L, a, ls, swz, nullptr, last && fuse && fuse_stats && f > f_begin);
+        launch_tile_head<PMainV, UNIT>(s, L, a, ls, nullptr, last && fuse && fuse_stats && f > f_begin);
         if (last)
           hipLaunchKernelGGL((k_tile_apply<PMainV, UNIT, true, false>), dim3(L.n_tiles), dim3(nt), lds, s,
                              soa_final_args(a, f + 1 == f_end), L.tent.p, L.ent_val.p, L.tile_ptr.p, L.tile_row0.p,
-                             ls.oldnew_col.p, L.tile_bits, L.n_tiles, swz);
+                             ls.oldnew_col.p, L.tile_bits, L.n_tiles);
         else
           hipLaunchKernelGGL((k_tile_apply<PMainV, UNIT, true, true>), dim3(L.n_tiles), dim3(nt), lds, s, a, L.tent.p,
-                             L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, swz);
+                             L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles);
         continue;
       }
       if (first) {
@@ -2669,8 +2644,7 @@ static inline bool plan_supports_mf(const StepPlan &plan) {
 }
 
 static inline int mf_rows_per_thread(int64_t n_rows) {
-  const char *e = std::getenv("MFM_MF_K");  // (read per sweep: the tests switch it inside one process)
-  if (e) return std::atoi(e) == 4 ? 4 : 8;
+  if (env_flag("MFM_MF_K")) return env_int("MFM_MF_K", 0) == 4 ? 4 : 8;  // (read per sweep: the tests switch it inside one process)
   return n_rows < ((int64_t)1 << 20) ? 4 : 8;  // short tables: more, shorter-lived threads per tile
 }
 
@@ -2682,7 +2656,6 @@ static void run_sweep_mf(hipStream_t s, Timing &tm, const StepPlan &plan, ArgsOf
   // comm != null: row-sharded, every first-level column complete on one rank (shards cut between two of them): the user
   // level runs locally inside the tiles, per factor ONE all-reduce carries the item level's statistics (2 n_cols doubles)
   const ParLevel &L = plan.steps.back().par;
-  const int swz = xcd_swizzle_enabled();
   const int KR = mf_rows_per_thread(plan.n_state_rows);
   const int nt = (1 << L.tile_bits) / KR;
   const size_t lds = mf_lds_bytes(L.tile_bits, UNIT);
@@ -2708,7 +2681,6 @@ static void run_sweep_mf(hipStream_t s, Timing &tm, const StepPlan &plan, ArgsOf
   m.tval = L.ent_val.p;
   m.tile_bits = L.tile_bits;
   m.n_tiles = L.n_tiles;
-  m.swz = swz;
   m.ucap = mf_user_cap(L.tile_bits);
   m.dv = ls.dv_col.p;
   m.udesc = plan.fuse_desc.p;
@@ -2717,7 +2689,6 @@ static void run_sweep_mf(hipStream_t s, Timing &tm, const StepPlan &plan, ArgsOf
   m.chunk = plan.mf_chunk.p;
   m.chunk_ptr = plan.mf_chunk_ptr.p;
   m.alpha = a0.alpha;
-  m.dbg = std::getenv("MFM_MF_DBG") ? std::atoi(std::getenv("MFM_MF_DBG")) : 0;
   m.colptr = a0.colptr;
   m.cval = a0.val;
   m.col_row0 = plan.col_row0.p;
@@ -2806,7 +2777,6 @@ static bool launch_mf_score(hipStream_t s, const StepPlan &plan, const SweepArgs
   m.tval = L.ent_val.p;
   m.tile_bits = L.tile_bits;
   m.n_tiles = L.n_tiles;
-  m.swz = xcd_swizzle_enabled();
   m.scols = L.scols.p;
   m.udesc = plan.fuse_desc.p;
   m.ucol_ptr = plan.fuse_col_ptr.p;
@@ -2823,15 +2793,14 @@ static bool launch_mf_score(hipStream_t s, const StepPlan &plan, const SweepArgs
   m.KS = KS;
   m.y = y;
   m.eq = eq;
-  m.dbg = std::getenv("MFM_SCORE_DBG") ? std::atoi(std::getenv("MFM_SCORE_DBG")) : 0;
   size_t lds = ((size_t)8 << L.tile_bits) + (size_t)mf_user_cap(L.tile_bits) * 12 + 16;
   {
     // stage the tile's first-level Vt rows in LDS when they fit next to the score array (three workgroups per CU)
     const size_t rows = (size_t)std::max(plan.mf_max_users, 1);
     const size_t need = rows * (size_t)KS * 8;
-    const size_t cap = std::getenv("MFM_SCORE_UCACHE_KB") ? (size_t)std::atoi(std::getenv("MFM_SCORE_UCACHE_KB")) * 1024 : 52 * 1024;
-    if (std::getenv("MFM_SETUP_TIMING")) std::fprintf(stderr, "[k_mf_score] max users per tile %d, LDS %zu + %zu\n", plan.mf_max_users, lds, need);
-    if (lds + need <= cap && !std::getenv("MFM_NO_SCORE_UCACHE")) {
+    const size_t cap = 52 * 1024;
+    if (env_flag("MFM_SETUP_TIMING")) std::fprintf(stderr, "[k_mf_score] max users per tile %d, LDS %zu + %zu\n", plan.mf_max_users, lds, need);
+    if (lds + need <= cap) {
       m.ucache = (int)rows;
       lds += need;
     }
@@ -2933,10 +2902,9 @@ template <bool UNIT, class ArgsOf>
 static void run_sweep_soa_sharded(hipStream_t s, Timing &tm, const StepPlan &plan, ArgsOf args, int f_begin, int f_end,
                                   LongScratch &ls, const SweepClasses &kc, const Comm &comm) {
   const ParLevel &L1 = plan.steps.front().par, &L = plan.steps.back().par;
-  const int swz = xcd_swizzle_enabled();
   const size_t lds = sizeof(double2) << L.tile_bits;
   const int nt = tile_threads(L.tile_bits);
-  const bool two = L.covers_rows_once && !std::getenv("MFM_NO_FUSED_TWO");
+  const bool two = L.covers_rows_once;
   raise_fused_lds_limit<UNIT>();
   {
     // first factor's first level: the locally complete columns in one pass, the special ones all-reduced
@@ -2957,7 +2925,7 @@ static void run_sweep_soa_sharded(hipStream_t s, Timing &tm, const StepPlan &pla
                            ls.vnext_col.p);
         hipLaunchKernelGGL((k_tile_stats<PMainV, UNIT, true>), dim3(L.n_tiles), dim3(nt), lds, s, a, L.tent.p, L.ent_val.p,
                            L.tile_ptr.p, L.tile_row0.p, ls.vnext_col.p, L.run_base.p, L.slot_pos.p, L.slots.p, L.tile_bits,
-                           L.n_tiles, swz, (const int32_t *)nullptr);
+                           L.n_tiles, (const int32_t *)nullptr);
       }
       hipLaunchKernelGGL(k_tile_sum, dim3((L.n_cols + 3) / 4), dim3(WG), 0, s, L.n_cols, L.slot_ptr.p, L.slots.p, ls.S_col.p);
     }
@@ -2969,7 +2937,7 @@ static void run_sweep_soa_sharded(hipStream_t s, Timing &tm, const StepPlan &pla
     if (!next) {
       TimedLaunch t(tm, s, kc.scat, 28.0 * L.n_ent);
       hipLaunchKernelGGL((k_tile_apply<PMainV, UNIT, true, false>), dim3(L.n_tiles), dim3(nt), lds, s, soa_final_args(a, true),
-                         L.tent.p, L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, swz);
+                         L.tent.p, L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles);
       continue;
     }
     an.row0 = plan.col_row0.p;
@@ -2982,10 +2950,10 @@ static void run_sweep_soa_sharded(hipStream_t s, Timing &tm, const StepPlan &pla
                   nullptr,  nullptr,      nullptr};
       if (two)
         hipLaunchKernelGGL((k_tile_apply_next<UNIT, true>), dim3(L.n_tiles), dim3(nt), lds + 256, s, af, L.tent.p, L.ent_val.p,
-                           L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, swz, fa);
+                           L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, fa);
       else
         hipLaunchKernelGGL((k_tile_apply_next<UNIT, false>), dim3(L.n_tiles), dim3(nt), lds + 256, s, af, L.tent.p,
-                           L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, swz, fa);
+                           L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.oldnew_col.p, L.tile_bits, L.n_tiles, fa);
     }
     MFM_HIP_CHECK(hipGetLastError());
     // first-level columns of factor f + 1 longer than a tile (complete here: second pass over their tiles), then
@@ -2998,7 +2966,7 @@ static void run_sweep_soa_sharded(hipStream_t s, Timing &tm, const StepPlan &pla
       TimedLaunch t(tm, s, kc.scat, 20.0 * plan.n_solo_tiles * (1 << L.tile_bits));
       hipLaunchKernelGGL((k_tile_stats<PMainV, UNIT, true>), dim3(plan.n_solo_tiles), dim3(nt), lds, s, an, L.tent.p,
                          L.ent_val.p, L.tile_ptr.p, L.tile_row0.p, ls.vnext_col.p, L.run_base.p, L.slot_pos.p, L.slots.p,
-                         L.tile_bits, L.n_tiles, swz, plan.solo_tiles.p);
+                         L.tile_bits, L.n_tiles, plan.solo_tiles.p);
     }
   }
   MFM_HIP_CHECK(hipGetLastError());
@@ -3027,7 +2995,6 @@ static int coop_capacity() {
   // delay residency but never wait on anything, and the spin is bounded.
   if (per_cu >= 7) per_cu -= 1;
   per_cu = std::max(1, std::min(per_cu, 4));
-  if (const char *e = std::getenv("MFM_COOP_PER_CU")) per_cu = std::max(1, std::atoi(e));
   return std::max(8, cus * per_cu);
 }
 

@@ -352,8 +352,7 @@ int mfm_store_reserve(mfm_store *st, int32_t n_samples) {
     const int64_t have = (int64_t)(st->wv.size() + st->spare.size());
     const double need = (double)std::max<int64_t>(n_samples - have, 0) * (double)std::max<int64_t>(st->D * (st->K + 1), 1) * sizeof(double);
     size_t free_b = 0, total_b = 0;
-    const char *fe = std::getenv("MFM_STORE_MAX_FRACTION");
-    const double frac = fe ? std::atof(fe) : 0.5;
+    const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
     if (need > 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > frac * (double)free_b)
       throw Error(MFM_ERR_RUNTIME, "sample store: the reservation exceeds MFM_STORE_MAX_FRACTION of the free device memory");
   }
@@ -557,7 +556,7 @@ int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_
   }
   // designs without relation blocks: every sample in ONE pass over the test rows (k_score_store); chunks of samples whose
   // row-major V copies fit 512 MB (the buffer is allocated per design: a larger one costs more than it saves)
-  if (d->blocks.empty() && N > 0 && rank <= 512 && (mode != 2 || n_cut + 1 <= PRED_MAX_CLASS) && !std::getenv("MFM_PREDICT_PER_SAMPLE")) {
+  if (d->blocks.empty() && N > 0 && rank <= 512 && (mode != 2 || n_cut + 1 <= PRED_MAX_CLASS) && !env_flag("MFM_PREDICT_PER_SAMPLE")) {
     const size_t per = (size_t)std::max<int64_t>(D * d->KS, 1) * sizeof(double);
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, ((size_t)512 << 20) / per));
     if (d->vt_all.n < (size_t)chunk * (per / sizeof(double))) d->vt_all.alloc((size_t)chunk * (per / sizeof(double)));

@@ -108,9 +108,7 @@ struct ResArgs {
   double *xw[RES_MAX_PEERS], *xV[RES_MAX_PEERS];
   int ngx;                   // OVF: overflow groups of 16 slots per thread (their residual lives in e_slots, which must be set)
   int no_store;              // the residual is not written back at the end (the caller recomputes it: update_e follows, FMTrainer.hpp:494)
-  int rot;                   // workgroup g runs as block (g - rot) mod G (MFM_RES_ROT: placement experiments)
-  int dbg;                   // timing experiments only (MFM_RES_DBG; results are wrong when set): 4 no grid barriers, 32 no item
-                             // draw, 64 no sweep A, 128 no sweep B, 4096 no partial stores inside sweep B
+  int xch_break;             // tests (MFM_RES_XCH_BREAK): this rank never raises its exchange flags (the time-out path)
 };
 
 __device__ __forceinline__ void res_store2(double *p, double a, double b) {
@@ -176,7 +174,6 @@ __device__ __forceinline__ void res_bar_init(const ResArgs &a, ResBar &rb, bool 
   __hip_atomic_fetch_add(a.bar + RES_BAR_START, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   rb.n_x = 1;
   rb.nx = 1;
-  if (a.dbg & 4) return;
   if (!res_spin(a, a.bar + RES_BAR_START, (unsigned long long)a.n_wg, dead)) return;
   rb.nx = 0;
   for (int i = 0; i < 8; i++) {
@@ -190,7 +187,7 @@ __device__ __forceinline__ void res_bar_init(const ResArgs &a, ResBar &rb, bool 
 __device__ __forceinline__ void res_grid_barrier(const ResArgs &a, const ResBar &rb, unsigned long long k, int tid, bool &dead) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its stores have reached the XCD's L2
   __syncthreads();
-  if (tid == 0 && !dead && !(a.dbg & 4)) {
+  if (tid == 0 && !dead) {
     const unsigned long long old =
         __hip_atomic_fetch_add(a.bar + RES_BAR_XCNT + 16 * rb.xcc, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (old + 1 == k * rb.n_x) {
@@ -232,7 +229,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   extern __shared__ __attribute__((aligned(16))) char res_smem[];
   constexpr int NW = NT / WAVE, NG = NGV + NGL, R = 16 * NG, RL = 16 * NGL;
   constexpr int B = 4;  // slots per batch
-  const int g = (int)((blockIdx.x + (unsigned)a.rot) % gridDim.x), tid = threadIdx.x, lane = tid & 63;
+  const int g = (int)blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int U = a.umax;
   const double alpha_k = a.scal ? a.scal[0] : a.alpha, e_shift_k = a.scal ? a.scal[2] : a.e_shift;
@@ -258,20 +255,16 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   RES_STAMP0(0);
   if (tid == 0) res_bar_init(a, rbar, dead);
   RES_STAMP0(1);
-  const bool nost = (a.dbg & 4096) != 0;  // (4096: no partial stores inside sweep B)
   // The two wavefronts of a SIMD (w and w + 4) take turns at the higher issue priority, group by group: the arbiter otherwise
   // prefers the older one throughout, which then finishes a sweep 5 us ahead and leaves the younger to run alone (MFM_RES_PROF:
   // waves 0-3 at 20 us, waves 4-7 at 25 us of sweep B; with the turns 19.0 and 19.7, config 3 333.4 -> 338-341 it/s in one box;
-  // changing turns every half group gains nothing more). a.dbg & 262144 switches it off (A/B).
-  const bool prio_swap = !(a.dbg & 262144);
+  // changing turns every half group gains nothing more).
   const int wv_hi = wv >> 2;
-#define RES_PRIO(j)                              \
-  if (prio_swap) {                               \
-    if ((((j) & 1) ^ wv_hi) != 0)                \
-      __builtin_amdgcn_s_setprio(1);             \
-    else                                         \
-      __builtin_amdgcn_s_setprio(0);             \
-  }
+#define RES_PRIO(j)                  \
+  if ((((j) & 1) ^ wv_hi) != 0)      \
+    __builtin_amdgcn_s_setprio(1);   \
+  else                               \
+    __builtin_amdgcn_s_setprio(0)
   const int trash_run = a.wg_run_ptr[g] + a.wg_nruns[g];
 #define RES_STAMP(k)                                                                                      \
   if (a.prof && tid == 0) a.prof[((int64_t)g * a.n_sw + (f - f_first)) * 64 + (k)] = __builtin_amdgcn_s_memrealtime()
@@ -375,7 +368,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     RES_STAMP(0);
     // ---- sweep A: the item update of the previous factor (:371-375; dv.x = 0 before the first), the user level's
     //      statistics (:351-356)
-    if (!(a.dbg & 64)) {
+    {
       int rc = run0 - 1;  // run counter of the run_item stage
       int itA[B];         // items of the next batch (in flight)
       d2_t ddA[B];        // dv pairs of this batch (in flight)
@@ -518,7 +511,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       bool have_head = false;
       double f1 = 0.0, f2 = 0.0, s1 = 0.0, s2 = 0.0;
       d2_t *part2 = (d2_t *)a.partials;
-      if (!(a.dbg & 128)) {
+      {
         int rc = run0 - 1, rcC = run0 - 1;  // run counters of the run_item stage and of the compute stage
         int itA[B];
         double ccA[B];
@@ -545,7 +538,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
 #define RES_PARTIAL_STORE() part2[head && have_head ? rcC - 1 : trash_run] = d2_t{s1, s2}
 #else
 #define RES_PARTIAL_STORE() \
-  if (head && have_head && !nost) part2[rcC - 1] = d2_t{s1, s2}
+  if (head && have_head) part2[rcC - 1] = d2_t{s1, s2}
 #endif
 #define RES_STEP_B(j, bb, iti, ito, cci, cco)                                                                              \
   {                                                                                                                        \
@@ -728,7 +721,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     //      whole lines); a wave takes a contiguous stretch of the list and adds into its own accumulator array (ds_add_f64:
     //      the lanes of one instruction that hit the same item are serialised in lane order, a wave's instructions run in
     //      program order); then a thread per item adds the wave arrays in wave order (fixed association) and draws.
-    if (!(a.dbg & 32)) {
+    {
       const d2_t *part2 = (const d2_t *)a.partials;
       for (int cb = wb; cb < we; cb += CH) {
         d2_t sv[CH];
@@ -783,7 +776,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
             // arrivals. The flag itself is a system-scope RELEASE store (one per rank and sweep: buffer_wbl2 sc0 sc1 + the store),
             // so that the hand-over is a release / acquire pair in the memory model as well; the readers poll relaxed and read
             // the sums with system-scope loads, which bypass the non-coherent caches (no acquire fence: it would drop the XCD's L2).
-            for (int r = 0; r < a.xworld && !(a.dbg & 8192); r++)  // (8192: a test of the time-out path -- the flags stay down)
+            for (int r = 0; r < a.xworld && !a.xch_break; r++)
               __hip_atomic_store(a.xflag[r] + 16 * a.xrank, E, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
           }
           for (int r = 0; r < a.xworld && !dead; r++) res_spin_sys(a, a.xflag[a.xrank] + 16 * r, E, dead);
@@ -917,7 +910,6 @@ struct ResScoreArgs {
   const double *y_slots;
   double *e_slots;
   double2 *sums;  // [G] {sum e, sum e^2}
-  int dbg;        // timing experiments (wrong results): 1 no item-row fetch, 2 no user-row reads, 4 one user row for all
   unsigned long long *prof;  // (MFM_RES_SCORE_PROF) [G][4] s_memrealtime at start / users staged / slots done / end
 };
 
@@ -1024,7 +1016,7 @@ __global__ __launch_bounds__(NT) void k_res_score(ResScoreArgs a) {
         if (head) {
           const int ji = jc[k];  // (-1: the pad run)
           wi = 0.0;
-          if (ji >= 0 && !(a.dbg & 1)) {
+          if (ji >= 0) {
             const double2 *src = (const double2 *)(a.Vt + (int64_t)ji * a.KS);
 #pragma unroll
             for (int p = 0; p < KPT; p++) vi[p] = p < KP ? src[p] : make_double2(0.0, 0.0);
@@ -1034,11 +1026,10 @@ __global__ __launch_bounds__(NT) void k_res_score(ResScoreArgs a) {
             for (int p = 0; p < KPT; p++) vi[p] = make_double2(0.0, 0.0);
           }
         }
-        const double2 *vu = (const double2 *)(uV + (size_t)((a.dbg & 4) ? 0 : uid[k]) * US);
+        const double2 *vu = (const double2 *)(uV + (size_t)uid[k] * US);
         double d0 = 0.0, d1 = 0.0;  // two chains: even / odd pairs
 #pragma unroll
         for (int p = 0; p < KPT; p += 2) {
-          if (a.dbg & 2) break;
           const double2 x0 = vu[p], x1 = vu[p + 1];
           d0 += x0.x * vi[p].x + x0.y * vi[p].y;
           d1 += x1.x * vi[p + 1].x + x1.y * vi[p + 1].y;
@@ -1197,7 +1188,7 @@ struct ResPlan {
       int64_t Gw = (N + (cap - slack) - 1) / (cap - slack);
       if (Gw > n_cu && N <= (int64_t)n_cu * cap) Gw = n_cu;  // (tight: the cuts below decide whether it fits)
       if (Gw > n_cu) continue;
-      if (const char *e = std::getenv("MFM_RES_WGS")) Gw = std::min<int64_t>(n_cu, std::max<int64_t>(Gw, std::atoll(e)));
+      if (env_flag("MFM_RES_WGS")) Gw = std::min<int64_t>(n_cu, std::max<int64_t>(Gw, env_i64("MFM_RES_WGS", 0)));
       Gw = std::min<int64_t>(Gw, n_users);
       // cut g at the user boundary nearest to g N / G, never beyond cap rows
       ucut.assign(1, 0);
@@ -1227,9 +1218,9 @@ struct ResPlan {
     }
     // Tables beyond the on-chip capacity (512 x 80 slots per CU): the largest variant plus RX slots per thread whose residual is
     // streamed from / to the slot-ordered buffer every sweep (k_mf_resident<.., OVF>), up to twice the capacity -- beyond that the
-    // per-factor passes. Not row-sharded (the exchange variant has no overflow form), not with MFM_RES_EAGER_STORE.
+    // per-factor passes. Not row-sharded (the exchange variant has no overflow form).
     RX = 0;
-    if (!found && allow_overflow && !std::getenv("MFM_RES_EAGER_STORE") && !std::getenv("MFM_RES_NO_OVERFLOW")) {
+    if (!found && allow_overflow) {
       const Variant big = vs[nv - 1];
       for (int rx = 16; rx <= 80 && !found; rx += 16) {
         const int64_t cap = (int64_t)NT * (big.rv + big.rl + rx) - 1;
@@ -1292,13 +1283,7 @@ struct ResPlan {
   static std::vector<int32_t> run_bases(const std::vector<int32_t> &nruns) {
     const int G = (int)nruns.size();
     std::vector<int32_t> run_base((size_t)G + 1, 0);
-    const int run_align = std::getenv("MFM_RES_RUN_ALIGN") ? std::max(1, std::atoi(std::getenv("MFM_RES_RUN_ALIGN"))) : 1;
-    const int run_skew = std::getenv("MFM_RES_RUN_SKEW") ? std::atoi(std::getenv("MFM_RES_RUN_SKEW")) : 0;
-    for (int g = 0; g < G; g++) {
-      int64_t nb = run_base[g] + nruns[g] + 1;
-      nb = (nb + run_align - 1) / run_align * run_align + (run_align > 1 ? (int64_t)run_skew * ((g + 1) % 8) : 0);
-      run_base[g + 1] = (int32_t)nb;
-    }
+    for (int g = 0; g < G; g++) run_base[g + 1] = run_base[g] + nruns[g] + 1;
     return run_base;
   }
 
@@ -1535,7 +1520,7 @@ struct ResPlan {
       y_slots = DevBuf<double>();
     }
     h_nruns = nruns;
-    if (std::getenv("MFM_RES_PROF")) {
+    if (env_flag("MFM_RES_PROF")) {
       h_diag.assign((size_t)G, "");
       for (int g = 0; g < G; g++) {
         int64_t maxlen = 0;
@@ -1614,7 +1599,7 @@ static inline hipError_t res_occupancy(const ResPlan &rp, int *per_cu) {
 // update_V of factors [f_begin, f_end) in one launch. zbase: variates of factor f_begin (factor f at + (f - f_begin) D).
 static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, int kernel_class, double2 *eq, double *V, int64_t D,
                                       int f_begin, int f_end, const double *zbase, const double *lam, const double *mu,
-                                      const int32_t *group, int n_groups, double alpha, int *error, bool lazy_store,
+                                      const int32_t *group, int n_groups, double alpha, int *error,
                                       double *w = nullptr, const double *zw = nullptr, const double *lam_w = nullptr,
                                       const double *mu_w = nullptr, double e_shift = 0.0, bool load_slots = false,
                                       bool no_store = false, const double *scal = nullptr) {
@@ -1622,7 +1607,7 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
   std::memset(&a, 0, sizeof(a));
   a.scal = scal;
   a.eq = eq;
-  a.e_slots = (lazy_store || rp.RX) ? rp.e_slots.p : nullptr;  // (overflow slots live there)
+  a.e_slots = rp.e_slots.p;
   a.ngx = rp.RX / 16;
   a.no_store = no_store ? 1 : 0;
   a.e_in = load_slots ? rp.e_slots.p : nullptr;
@@ -1664,10 +1649,8 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
   a.bar = rp.bar.p;
   a.n_wg = rp.G;
   a.error = error;
-  a.dbg = std::getenv("MFM_RES_DBG") ? std::atoi(std::getenv("MFM_RES_DBG")) : 0;
-  a.rot = std::getenv("MFM_RES_ROT") ? std::atoi(std::getenv("MFM_RES_ROT")) : 0;
   const bool xch = rp.xworld > 1;
-  if (xch && rp.xrank == 1 && std::getenv("MFM_RES_XCH_BREAK")) a.dbg |= 8192;  // tests: rank 1 never raises its flags
+  a.xch_break = xch && rp.xrank == 1 && env_flag("MFM_RES_XCH_BREAK");  // tests: rank 1 never raises its flags
   a.xworld = rp.xworld;
   a.xrank = rp.xrank;
   a.xepoch0 = rp.xepoch;
@@ -1682,7 +1665,7 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
   if (xch && !rp.peers_set) throw Error(MFM_ERR_RUNTIME, "row-sharded persistent sweep: the peers' exchange buffers are not set (mfm_peer_set)");
   // MFM_RES_PROF=n: the n-th launch of the process records the phase stamps of every workgroup and prints a summary
   static int prof_launch = 0;
-  const bool prof = std::getenv("MFM_RES_PROF") && ++prof_launch == std::atoi(std::getenv("MFM_RES_PROF"));
+  const bool prof = env_flag("MFM_RES_PROF") && ++prof_launch == env_int("MFM_RES_PROF", 0);
   DevBuf<unsigned long long> prof_buf;
   if (prof) {
     prof_buf.alloc((size_t)rp.G * a.n_sw * 64);
@@ -1695,7 +1678,6 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
   // its 8-byte list entry, its item read by both sweeps (2 x 4 B)
   double bytes = (8.0 + (load_slots ? 0.0 : 4.0) + 1.4 + (no_store ? 0.0 : 8.0)) * rp.n_rows + K * 48.0 * rp.n_runs;  // (slot order: no map; no_store: not written back)
   if (rp.RX) bytes += (double)K * (16.0 + 1.75) * (double)rp.G * rp.NT * rp.RX;  // overflow slots: residual read + written, static words, per sweep
-  (void)lazy_store;
   hipLaunchKernelGGL(k_res_init_dv, dim3((rp.n_items + 256) / 256), dim3(256), 0, s,
                      w ? (const double *)nullptr : V + (int64_t)f_begin * D, rp.scols.p, rp.n_items,
                      rp.dv.p, rp.bar.p);
@@ -1795,7 +1777,7 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
           std::fprintf(stderr, "\n");
         }
     }
-    if (const char *dump = std::getenv("MFM_RES_PROF_DUMP")) {  // one line per workgroup: phase means, then the diagnostics
+    if (const char *dump = env_str("MFM_RES_PROF_DUMP")) {  // one line per workgroup: phase means, then the diagnostics
       if (FILE *fp = std::fopen(dump, "w")) {
         for (int g = 0; g < rp.G; g++) {
           std::fprintf(fp, "%d", g);
@@ -1867,9 +1849,8 @@ static inline void run_res_score(hipStream_t s, Timing &tm, ResPlan &rp, int ker
   a.y_slots = rp.y_slots.p;
   a.e_slots = rp.e_slots.p;
   a.sums = rp.sums.p;
-  a.dbg = std::getenv("MFM_RES_SCORE_DBG") ? std::atoi(std::getenv("MFM_RES_SCORE_DBG")) : 0;
   static int prof_calls = 0;
-  const bool prof = std::getenv("MFM_RES_SCORE_PROF") && ++prof_calls == std::atoi(std::getenv("MFM_RES_SCORE_PROF"));
+  const bool prof = env_flag("MFM_RES_SCORE_PROF") && ++prof_calls == env_int("MFM_RES_SCORE_PROF", 0);
   DevBuf<unsigned long long> prof_buf;
   a.prof = nullptr;
   if (prof) {

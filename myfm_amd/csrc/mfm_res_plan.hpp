@@ -308,7 +308,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
   if (N < 1 || n_cu < 1 || D0 < 2 || !X.unit || X.ell_width != 2) return rpn.fail("shape");
   if (N >= ((int64_t)1 << 31) - 1) return rpn.fail("too many rows");
   auto grid = [](int64_t n) { return dim3((unsigned)((n + TB - 1) / TB)); };
-  const bool tlog = std::getenv("MFM_SETUP_TIMING") != nullptr;
+  const bool tlog = env_flag("MFM_SETUP_TIMING");
   double t_prev = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
   auto lap = [&](const char *what) {
     if (!tlog) return;

@@ -138,18 +138,16 @@ constexpr int MT_PAR_BLOCKS = 512;  // blocks per workgroup at most (and the req
 // profiles/r04_q_res_cus.txt); larger problems keep four (the ring holds the batch: 4 GB of raw words at config 5).
 constexpr int MT_GEN_BATCH = 4, MT_GEN_BATCH_SMALL = 6;
 static inline int mt_gen_batch(double outputs_per_iteration) {
-  if (const char *e = std::getenv("MFM_RNG_GEN_BATCH")) return std::max(1, std::min(16, std::atoi(e)));
   return outputs_per_iteration <= 33554432.0 ? MT_GEN_BATCH_SMALL : MT_GEN_BATCH;
 }
 static inline int mt_par_blocks_for(int64_t blocks) {
-  if (const char *e = std::getenv("MFM_RNG_PAR_BLOCKS")) return std::max(32, std::min(MT_PAR_BLOCKS, std::atoi(e)));
   const int64_t b = ((blocks + 169) / 170 + 15) / 16 * 16;
   return (int)std::max<int64_t>(64, std::min<int64_t>(MT_PAR_BLOCKS, b));
 }
 constexpr int MT_JUMP_SPAN = 33;  // blocks covering 19937 + 624 words
 
-// PHASE 0: jump + generation in one launch. PHASE 1: the jump only -- workgroup p leaves the block before its first one in
-// starts[p] -- and PHASE 2: the generation from those blocks. The jump needs 87 KB of LDS, the generation 5 KB: as two
+// PHASE 1: the jump only -- workgroup p leaves the block before its first one in starts[p] -- and PHASE 2: the generation from
+// those blocks. The jump needs 87 KB of LDS, the generation 5 KB: as two
 // launches the ~0.15 ms of generation do not take the LDS of 169 CUs away from the scorer running beside them (update_e
 // ran 0.5 instead of 0.3 ms next to the fused launch).
 template <int PHASE>
@@ -157,7 +155,7 @@ __global__ __launch_bounds__(MT_GEN_THREADS) void k_mt_generate_par(const RngSta
                                                                     uint32_t *__restrict__ raw, uint64_t mask, uint64_t need,
                                                                     const uint32_t *__restrict__ jump_tab, int par_blocks,
                                                                     uint32_t *__restrict__ starts, uint64_t need_min) {
-  extern __shared__ uint32_t lds_seq[];  // [MT_JUMP_SPAN * 624] sequence (PHASE 0, 1), then 2 x 625 generation buffers
+  extern __shared__ uint32_t lds_seq[];  // [MT_JUMP_SPAN * 624] sequence (PHASE 1), then 2 x 625 generation buffers
   uint32_t *seq = lds_seq;
   uint32_t(*buf)[MT_N + 1] = (uint32_t(*)[MT_N + 1])(lds_seq + (PHASE == 2 ? 0 : MT_JUMP_SPAN * MT_N));
   const int t = threadIdx.x, p = blockIdx.x;
