@@ -174,7 +174,9 @@ struct FMLearningConfig {
   // (MyFM*.fit sorts the rows for the device paths and passes the inverse permutation here; ordered probit carries the same
   // information in its cutpoint groups' row lists.)
   vector<int64_t> latent_order;
-  bool host_rng() const { return latent_mode == 1 || mfm::env_flag("MYFM_AMD_HOST_RNG"); }
+  // set by FMTrainer::resolve_latent_mode for a row-sharded fit of a latent task: neither mode 1 nor MYFM_AMD_HOST_RNG applies
+  bool row_sharded = false;
+  bool host_rng() const { return !row_sharded && (latent_mode == 1 || mfm::env_flag("MYFM_AMD_HOST_RNG")); }
   bool exact_dev() const { return latent_mode == 2 && !host_rng() && task_type != TaskType::REGRESSION; }
 
   // FMLearningConfig.hpp:17-57
@@ -794,6 +796,18 @@ static void warn_sequential_latent(int32_t status) {
                (int)status, status >= 1 && status <= 5 ? why[status] : "?");
 }
 
+// a row-sharded fit of a latent task asked for exact or host latent draws: it makes them from the per-row Philox streams instead, said
+// once per process -- the same seed gives another chain than on one GPU
+static void warn_sharded_latent(const char *requested) {
+  static bool said = false;
+  if (said) return;
+  said = true;
+  std::fprintf(stderr,
+               "myfm_amd: row-sharded fit: the latent draws come from the per-row Philox streams (latent mode \"%s\" walks one "
+               "stream over all rows, which no shard holds); the chain differs from an unsharded fit with the same seed.\n",
+               requested);
+}
+
 struct OprobitSampler {
   mfm_ctx *ctx;
   int group;  // device-side cutpoint group
@@ -1172,10 +1186,19 @@ struct FMTrainer {
   }
   FMTrainer(const FMTrainer &) = delete;
   bool comm_active() const { return !comm_id.empty() || (allreduce.ptr() != nullptr && !allreduce.is_none()); }
-  // before the device is built: the exact latent draws walk ONE stream over ALL rows in order -- a row-sharded fit keeps the
-  // per-row Philox streams (which do not depend on the sharding)
+  // before the device is built: the exact latent draws ("exact", "host") walk ONE stream over ALL rows in order -- a row-sharded fit
+  // keeps the per-row Philox streams (which do not depend on the sharding). In "host" mode each rank would walk its own copy of the
+  // generator over its own rows, a data-dependent number of variates per row, and the ranks' copies of the model would drift apart.
   void resolve_latent_mode() {
-    if (cfg.latent_mode == 2 && comm_active()) cfg.latent_mode = 0;
+    if (comm_active()) {
+      if (cfg.task_type != TaskType::REGRESSION) {
+        const bool env_host = mfm::env_flag("MYFM_AMD_HOST_RNG");
+        if (cfg.latent_mode != 0 || env_host) warn_sharded_latent(env_host || cfg.latent_mode == 1 ? "host" : "exact");
+        cfg.row_sharded = true;
+      }
+      if (cfg.latent_mode == 2 || cfg.row_sharded) cfg.latent_mode = 0;
+      cfg.latent_order.clear();  // (the caller's order of ALL rows: nothing the per-row streams use)
+    }
     if (!cfg.latent_order.empty()) {
       if ((int64_t)cfg.latent_order.size() != N) throw std::invalid_argument("latent row order must list every row once");
       vector<bool> seen((size_t)N, false);
@@ -1337,9 +1360,13 @@ struct FMTrainer {
               all_rows = false;
               break;
             }
+        // (a group without rows of this table -- a shard's share of a group can be empty -- must not pass the null pointer of an
+        //  empty vector: mfm_oprobit_add_group reads a null row list as the whole table)
         vector<int64_t> rows;
         if (!all_rows) rows.assign(c.second.begin(), c.second.end());
-        ck(ctx, mfm_oprobit_add_group(ctx, (int32_t)c.first, all_rows ? nullptr : rows.data(), (int64_t)c.second.size(), &g));
+        const int64_t no_rows = 0;
+        const int64_t *rp = all_rows ? nullptr : (rows.empty() ? &no_rows : rows.data());
+        ck(ctx, mfm_oprobit_add_group(ctx, (int32_t)c.first, rp, (int64_t)c.second.size(), &g));
         StreamEngine eng;
         if (cfg.exact_dev()) {  // the cutpoint sampler's own draws come from the device stream too (between two sets)
           if (!dwin) dwin.reset(new DeviceStreamWindow(ctx));

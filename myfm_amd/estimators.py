@@ -260,9 +260,12 @@ class MyFMGibbsBase:
                 else:
                     cuts = [(n * r) // world for r in range(world + 1)]
                 lo, hi = cuts[rank], cuts[rank + 1]
-                if self._task_type == TaskType.ORDERED:  # the cutpoint group lists LOCAL rows
+                # the latent draws of a shard come from per-row Philox streams, which need no caller's row order; the
+                # cutpoint group lists LOCAL rows
+                config_builder.set_latent_row_order(np.zeros(0, dtype=np.int64))
+                if self._task_type == TaskType.ORDERED:
                     config_builder.set_cutpoint_groups([(int(np.asarray(y).max()) + 1, np.arange(hi - lo, dtype=np.int64))])
-                    config = config_builder.build()
+                config = config_builder.build()
                 rel_l = [RelationBlock(r.original_to_block_array[lo:hi], r.data) for r in X_rel]
                 y_l = np.ascontiguousarray(np.asarray(y, dtype=REAL)[lo:hi])
                 self.predictor_, self.history_ = _myfm.create_train_fm_sharded(

@@ -316,6 +316,22 @@ def test_two_processes_one_gpu_sharded_fit():
     assert r.returncode == 0 and "mp_fit_worker ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
 
 
+def test_two_processes_one_gpu_sharded_latent_fit():
+    # MyFMClassifier / MyFMOrderedProbit fitted row-sharded by two ranks on device 0 (gloo, the torch.distributed callback) on rows
+    # that fit() re-sorts: the unsharded chain with exact_latent_draws=False on every rank, the copies bit for bit
+    # (tests/mp_latent_worker.py)
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", "29643", os.path.join(root, "tests", "mp_latent_worker.py")]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "mp_latent_worker ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+
+
 @pytest.mark.parametrize("peer_model", ["0", "1"])
 def test_two_processes_one_gpu_persistent_sweep(peer_model):
     # the row-sharded persistent sweep with its ranks in two PROCESSES (one GPU: both on device 0, each with a share of the CUs):
@@ -729,3 +745,188 @@ def test_cell_path_empty_shard(oracle, monkeypatch):
         np.testing.assert_allclose(gw, w, rtol=1e-7, atol=1e-8)
         np.testing.assert_allclose(gV, V, rtol=1e-7, atol=1e-8)
         np.testing.assert_allclose(ge, t.e(n)[lo:lo + ge.shape[0]], rtol=1e-7, atol=1e-7)
+
+
+# ---- the latent tasks row-sharded: probit classification and ordered probit. A shard's latent draws come from the per-row Philox
+# streams keyed by the GLOBAL row (mfm_tasks.hpp), so any sharding must give the unsharded chain of latent mode "philox"; the
+# modes "exact" and "host" walk one stream over all rows, which no shard holds: a sharded fit makes the Philox draws instead.
+
+def _latent_design(task):
+    n = 24001
+    X, yr, shapes = ds.onehot_mf(n, 300, 60, seed=17)
+    gi = ds.group_index_from_shapes(shapes)
+    if task == "classification":
+        return X, np.where(yr > np.median(yr), 1.0, -1.0), gi, None
+    # two cutpoint groups: every third row with 3 classes, the others with 6
+    y = np.empty(n)
+    rows_a = np.arange(0, n, 3, dtype=np.int64)
+    rows_b = np.setdiff1d(np.arange(n, dtype=np.int64), rows_a)
+    for rows, c in ((rows_a, 3), (rows_b, 6)):
+        y[rows] = np.searchsorted(np.quantile(yr[rows], np.linspace(0, 1, c + 1)[1:-1]), yr[rows])
+    return X, y, gi, [(3, rows_a), (6, rows_b)]
+
+
+def _latent_config(gi, task, groups, mode, n_iter=6):
+    from myfm_amd import _myfm
+
+    b = _myfm.ConfigBuilder()
+    b.set_alpha_0(1.0).set_beta_0(1.0).set_gamma_0(1.0).set_mu_0(0.0).set_reg_0(1.0)
+    b.set_group_index([int(g) for g in gi]).set_n_iter(n_iter).set_n_kept_samples(0)
+    if task == "classification":
+        b.set_task_type(_myfm.TaskType.CLASSIFICATION)
+    else:
+        b.set_task_type(_myfm.TaskType.ORDERED).set_cutpoint_groups([(c, np.asarray(r, dtype=np.int64)) for c, r in groups])
+    b.set_latent_mode(mode)
+    return b.build()
+
+
+def _local_groups(groups, lo, hi):
+    if groups is None:
+        return None
+    return [(c, r[(r >= lo) & (r < hi)] - lo) for c, r in groups]
+
+
+def _record(s):
+    h = s.hyper
+    return dict(w0=s.fm.w0, w=np.array(s.fm.w), V=np.array(s.fm.V), alpha=float(h.alpha), lambda_w=np.array(h.lambda_w),
+                mu_w=np.array(h.mu_w), lambda_V=np.array(h.lambda_V), mu_V=np.array(h.mu_V),
+                cutpoints=[np.array(c) for c in s.fm.cutpoints])
+
+
+def _unsharded_latent_chain(X, y, gi, task, groups, K, n_iter):
+    from myfm_amd import _myfm
+
+    s = _myfm.GibbsSession(K, 0.1, X, [], y, 42, _latent_config(gi, task, groups, "philox", n_iter))
+    recs = []
+    for _ in range(n_iter):
+        s.step()
+        recs.append(_record(s))
+    return recs, s.residual()
+
+
+def _assert_latent_chain(got, want, tol=1e-7):
+    for g, w in zip(got, want):
+        assert abs(g["w0"] - w["w0"]) <= tol * max(1.0, abs(w["w0"]))
+        np.testing.assert_allclose(g["w"], w["w"], rtol=tol, atol=tol)
+        np.testing.assert_allclose(g["V"], w["V"], rtol=tol, atol=tol)
+        assert abs(g["alpha"] - w["alpha"]) <= tol * w["alpha"]
+        for k in ("lambda_w", "lambda_V"):
+            np.testing.assert_allclose(g[k], w[k], rtol=tol)
+        for k in ("mu_w", "mu_V"):
+            np.testing.assert_allclose(g[k], w[k], rtol=tol, atol=tol)
+        # the cutpoints of every iteration: the same Metropolis decisions
+        assert len(g["cutpoints"]) == len(w["cutpoints"])
+        for a, b in zip(g["cutpoints"], w["cutpoints"]):
+            np.testing.assert_allclose(a, b, rtol=tol, atol=tol)
+
+
+@pytest.mark.parametrize("mode", ["philox", "exact", "host"])
+@pytest.mark.parametrize("world,cut", [(2, "even"), (3, "awkward")])
+@pytest.mark.parametrize("task", ["classification", "ordered"])
+def test_sharded_latent_chain(task, world, cut, mode):
+    from myfm_amd import _capi, _myfm
+
+    X, y, gi, groups = _latent_design(task)
+    n, K, n_iter = X.shape[0], 3, 6
+    # awkward: rank 0 holds a single row (one of group a: group b has no row there), the other two cut inside users
+    cuts = [(n * r) // world for r in range(world + 1)] if cut == "even" else [0, 1, 9000, n]
+    ls = Lockstep(world)
+    levels = _capi.column_levels(X)[0]
+    out, errs = {}, []
+
+    def run(rank):
+        try:
+            lo, hi = cuts[rank], cuts[rank + 1]
+            cfg = _latent_config(gi, task, _local_groups(groups, lo, hi), mode, n_iter)
+            s = _myfm.GibbsSession(K, 0.1, X[lo:hi], [], y[lo:hi], 42, cfg, allreduce=ls.callback(rank), n_total_rows=n,
+                                   row_offset=lo, main_levels=levels, shard_rank=rank, shard_world=world)
+            recs = []
+            for _ in range(n_iter):
+                s.step()
+                recs.append(_record(s))
+            out[rank] = (recs, s.residual(), lo, s.latent_info()["mode"])
+        except BaseException as ex:  # noqa
+            errs.append(ex)
+            ls.bar.abort()
+
+    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    for t_ in th:
+        t_.start()
+    for t_ in th:
+        t_.join(timeout=300)
+    assert not errs, errs
+    # the copies of the model on the ranks: bit for bit, every iteration
+    for rank in range(1, world):
+        for it, (a, b) in enumerate(zip(out[rank][0], out[0][0])):
+            assert a["w0"] == b["w0"] and np.array_equal(a["w"], b["w"]) and np.array_equal(a["V"], b["V"]), (rank, it)
+            assert all(np.array_equal(p, q) for p, q in zip(a["cutpoints"], b["cutpoints"])), (rank, it)
+    assert len(set(ls.counts)) == 1 and ls.counts[0] > 0
+    want, e = _unsharded_latent_chain(X, y, gi, task, groups, K, n_iter)
+    for rank in range(world):
+        recs, ge, lo, info_mode = out[rank]
+        assert info_mode == "philox"
+        _assert_latent_chain(recs, want)
+        np.testing.assert_allclose(ge, e[lo:lo + ge.shape[0]], rtol=1e-7, atol=1e-7)
+
+
+@pytest.mark.parametrize("task", ["classification", "ordered"])
+def test_world1_latent_identity_allreduce(task):
+    from myfm_amd import _capi, _myfm
+
+    X, y, gi, groups = _latent_design(task)
+    K, n_iter = 3, 4
+    calls = []
+    s = _myfm.GibbsSession(K, 0.1, X, [], y, 42, _latent_config(gi, task, groups, "philox", n_iter),
+                           allreduce=lambda p, c: calls.append(c), n_total_rows=X.shape[0], main_levels=_capi.column_levels(X)[0])
+    recs = []
+    for _ in range(n_iter):
+        s.step()
+        recs.append(_record(s))
+    want, e = _unsharded_latent_chain(X, y, gi, task, groups, K, n_iter)
+    _assert_latent_chain(recs, want)
+    np.testing.assert_allclose(s.residual(), e, rtol=1e-7, atol=1e-7)
+    assert len(calls) > n_iter * (K + 1)
+
+
+_NOTICE_SCRIPT = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from myfm_amd import _capi, _myfm
+from tests import datasets as ds
+X, yr, shapes = ds.onehot_mf(3000, 40, 20, seed=2)
+y = np.where(yr > np.median(yr), 1.0, -1.0)
+for mode in sys.argv[2:]:
+    b = _myfm.ConfigBuilder()
+    b.set_group_index([int(g) for g in ds.group_index_from_shapes(shapes)]).set_n_iter(2).set_n_kept_samples(0)
+    b.set_task_type(_myfm.TaskType.CLASSIFICATION).set_latent_mode(mode)
+    s = _myfm.GibbsSession(2, 0.1, X, [], y, 42, b.build(), allreduce=lambda p, c: None, n_total_rows=X.shape[0],
+                           main_levels=_capi.column_levels(X)[0])
+    s.step()
+    assert s.latent_info()["mode"] == "philox", s.latent_info()
+print("notice script ok")
+"""
+
+
+@pytest.mark.parametrize("modes,env_host,said", [(["exact", "host", "exact"], False, "exact"), (["philox"], True, "host"),
+                                                 (["philox"], False, None)])
+def test_sharded_latent_mode_notice(modes, env_host, said):
+    # a row-sharded fit that was asked for exact or host latent draws (set_latent_mode, MYFM_AMD_HOST_RNG) makes the Philox draws and
+    # says so on stderr, once per process (a child process: the notice is once per process)
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("MYFM_AMD_HOST_RNG", None)
+    if env_host:
+        env["MYFM_AMD_HOST_RNG"] = "1"
+    r = subprocess.run([sys.executable, "-c", _NOTICE_SCRIPT, root] + modes, cwd=root, env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "notice script ok" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stderr.splitlines() if "row-sharded fit" in ln]
+    if said is None:
+        assert not lines, lines
+    else:
+        assert len(lines) == 1 and ('"%s"' % said) in lines[0], lines
