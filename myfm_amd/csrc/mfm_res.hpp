@@ -234,17 +234,20 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   const int U = a.umax;
   const double alpha_k = a.scal ? a.scal[0] : a.alpha, e_shift_k = a.scal ? a.scal[2] : a.e_shift;
   const int ngx = OVF ? a.ngx : 0, NGt = NG + ngx, Rt = 16 * NGt;  // groups / slots of a thread in all (the layout arrays' strides)
-  double *elds = (double *)res_smem;      // [RL][NT] residual of the LDS-resident slots
+  d2_t *utab = (d2_t *)res_smem;          // [U] {new coefficient, new - old} (first: its address is uid << 4, no base register)
+  double *elds = (double *)(utab + U);    // [RL][NT] residual of the LDS-resident slots
   double *acc1 = elds + (size_t)RL * NT;  // [NW][U]  sum of -e h per (wave, user) / (wave, item of the slice)
   double *acc2 = acc1 + NW * U;           // [NW][U]  sum of h^2
-  d2_t *utab = (d2_t *)(acc2 + NW * U);   // [U] {new coefficient, new - old}
-  d2_t *wcarry = utab + U;                // [NW]
+  d2_t *wcarry = (d2_t *)(acc2 + NW * U); // [NW]
   int *wflag = (int *)(wcarry + NW);      // [NW]
   const int32_t *perm_g = a.perm + (int64_t)g * Rt * NT;
-  const d2_t *dv2 = (const d2_t *)a.dv;
   const int u0 = a.wg_user_ptr[g], nu = a.wg_user_ptr[g + 1] - u0;
   const int rb0 = a.wg_run_ptr[g];
   const int pad_item = a.n_items;
+  // the sweeps' gathers take 32-bit byte offsets from the arrays' (wave-uniform) bases: global_load v_off, s[base]
+  const unsigned rb0b = 4u * (unsigned)rb0, padb = 16u * (unsigned)pad_item;
+  const char *run_item_b = (const char *)a.run_item, *dv_b = (const char *)a.dv;
+  double *acc1w = acc1 + wv * U, *acc2w = acc2 + wv * U;  // this wave's accumulator arrays
   bool dead = false;
   unsigned long long nbar = 0;
   ResBar rbar;
@@ -313,6 +316,15 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     uid[3] = (int)((lo_ >> 30) | (((uxx >> (8 * (bb))) & 0xffu) << 2));          \
   }
 
+  // Sweep A's on-chip batch loops are unrolled: every residual has a static register name (no s_set_gpr_idx windows). Sweep B's
+  // stay rolled: unrolled as well, the code of the two sweeps outgrew the instruction cache (HISTORY.md). At the top of each
+  // sweep the static words pass through an empty asm statement, so that what the sweep decodes from them (users, gather bits)
+  // is recomputed inside the sweep instead of being hoisted out of the factor loop and kept live across it. The ";; res sweep"
+  // comments mark the sweeps in the listing for scripts/res_isa.py.
+#define RES_OPAQUE()                                                                            \
+  _Pragma("unroll") for (int j_ = 0; j_ < NG; j_++) {                                           \
+    asm volatile("" : "+v"(uw[j_]), "+v"(ux[j_]), "+v"(hbv[j_]), "+v"(nbv[j_]));                \
+  }
   // Pad slots carry (pad item, pad user): an item whose dv entry stays (0, 0) and a user slot nobody draws, so that every slot
   // runs the same straight-line code: a pad's statistics add 0 whatever its residual holds.
   res_d16_t ev[NGV > 0 ? NGV : 1];
@@ -369,7 +381,9 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     // ---- sweep A: the item update of the previous factor (:371-375; dv.x = 0 before the first), the user level's
     //      statistics (:351-356)
     {
-      int rc = run0 - 1;  // run counter of the run_item stage
+      RES_OPAQUE();
+      asm volatile(";; res sweep A");
+      unsigned rcb = 4u * (unsigned)(run0 - 1);  // run counter of the run_item stage, in bytes
       int itA[B];         // items of the next batch (in flight)
       d2_t ddA[B];        // dv pairs of this batch (in flight)
       {
@@ -377,16 +391,16 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
         const unsigned n0 = RES_NIB(0, 0), n1 = RES_NIB(0, 1);
 #pragma unroll
         for (int k = 0; k < B; k++) {
-          rc += (int)((n0 >> k) & 1u);
-          it0[k] = a.run_item[(n0 >> k) & 1u ? rc : rb0];
+          rcb += ((n0 >> k) & 1u) << 2;
+          it0[k] = *(const int *)(run_item_b + ((n0 >> k) & 1u ? rcb : rb0b));
         }
 #pragma unroll
         for (int k = 0; k < B; k++) {
-          rc += (int)((n1 >> k) & 1u);
-          itA[k] = a.run_item[(n1 >> k) & 1u ? rc : rb0];
+          rcb += ((n1 >> k) & 1u) << 2;
+          itA[k] = *(const int *)(run_item_b + ((n1 >> k) & 1u ? rcb : rb0b));
         }
 #pragma unroll
-        for (int k = 0; k < B; k++) ddA[k] = dv2[(n0 >> k) & 1u ? it0[k] : pad_item];
+        for (int k = 0; k < B; k++) ddA[k] = *(const d2_t *)(dv_b + ((n0 >> k) & 1u ? (unsigned)it0[k] << 4 : padb));
       }
       d2_t ddc = d2_t{0.0, 0.0};
       int itB[B];
@@ -398,10 +412,11 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   {                                                                                                                        \
     const unsigned n4 = RES_NIB(j, bb), n4a = RES_NIB(j, (bb) + 1), n4b = RES_NIB(j, (bb) + 2);                            \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      rc += (int)((n4b >> k) & 1u);                                                                                        \
-      ito[k] = a.run_item[(n4b >> k) & 1u ? rc : rb0];                                                                     \
+      rcb += ((n4b >> k) & 1u) << 2;                                                                                       \
+      ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
     }                                                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < B; k++) ddo[k] = dv2[(n4a >> k) & 1u ? iti[k] : pad_item];                       \
+    _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
+      ddo[k] = *(const d2_t *)(dv_b + ((n4a >> k) & 1u ? (unsigned)iti[k] << 4 : padb));                                   \
     int uid[B];                                                                                                            \
     RES_UIDS(j, bb, uid);                                                                                                  \
     double up[B], ex[B];                                                                                                   \
@@ -419,18 +434,19 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       else                                                                                                                 \
         elds[(16 * (j - NGV) + 4 * (bb) + k) * NT + tid] = er;                                                             \
       const double c = ddc[1];                                                                                             \
-      __hip_atomic_fetch_add(&acc1[wv * U + uid[k]], (-er) * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);           \
-      __hip_atomic_fetch_add(&acc2[wv * U + uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);               \
+      __hip_atomic_fetch_add(&acc1w[uid[k]], (-er) * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                   \
+      __hip_atomic_fetch_add(&acc2w[uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                       \
     }                                                                                                                      \
   }
 #define RES_STEP_AX(bb, iti, ito, ddi, ddo)                                                                                 \
   {                                                                                                                        \
     const unsigned n4 = ((nbw >> (4 * (bb))) & 15u), n4a = ((nbw >> (4 * ((bb) + 1))) & 15u), n4b = ((nbw >> (4 * ((bb) + 2))) & 15u);                            \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      rc += (int)((n4b >> k) & 1u);                                                                                        \
-      ito[k] = a.run_item[(n4b >> k) & 1u ? rc : rb0];                                                                     \
+      rcb += ((n4b >> k) & 1u) << 2;                                                                                       \
+      ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
     }                                                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < B; k++) ddo[k] = dv2[(n4a >> k) & 1u ? iti[k] : pad_item];                       \
+    _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
+      ddo[k] = *(const d2_t *)(dv_b + ((n4a >> k) & 1u ? (unsigned)iti[k] << 4 : padb));                                   \
     int uid[B];                                                                                                            \
     RES_UIDSX(bb, uid);                                                                                                      \
     double up[B], ex[B];                                                                                                   \
@@ -445,19 +461,20 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       const double er = ex[k] + up[k] * ddc[0];                                                                            \
       eo[4 * (bb) + k] = er;                                                             \
       const double c = ddc[1];                                                                                             \
-      __hip_atomic_fetch_add(&acc1[wv * U + uid[k]], (-er) * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);           \
-      __hip_atomic_fetch_add(&acc2[wv * U + uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);               \
+      __hip_atomic_fetch_add(&acc1w[uid[k]], (-er) * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                   \
+      __hip_atomic_fetch_add(&acc2w[uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                       \
     }                                                                                                                      \
   }
 #pragma unroll
       for (int j = 0; j < NG; j++) {
         RES_PRIO(j);
-#pragma unroll 1
+#pragma unroll
         for (int bp = 0; bp < 2; bp++) {
           RES_STEP_A(j, 2 * bp, itA, itB, ddA, ddB);
           RES_STEP_A(j, 2 * bp + 1, itB, itA, ddB, ddA);
         }
       }
+      asm volatile(";; res sweep end");
       if (OVF) {  // the overflow groups: static words and residuals from global memory, group by group
         unsigned hb_c = nbx0;
         for (int jx = 0; jx < ngx; jx++) {
@@ -511,8 +528,13 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       bool have_head = false;
       double f1 = 0.0, f2 = 0.0, s1 = 0.0, s2 = 0.0;
       d2_t *part2 = (d2_t *)a.partials;
+      char *part_b = (char *)a.partials - 16;  // (RES_PARTIAL_STORE's offsets are one run ahead)
+      const unsigned trashb = 16u * (unsigned)(trash_run + 1);
       {
-        int rc = run0 - 1, rcC = run0 - 1;  // run counters of the run_item stage and of the compute stage
+        RES_OPAQUE();
+        asm volatile(";; res sweep B");
+        unsigned rcb = 4u * (unsigned)(run0 - 1);  // run counter of the run_item stage, in bytes
+        unsigned rcCb = 16u * (unsigned)(run0 - 1);  // ... and of the compute stage, in bytes
         int itA[B];
         double ccA[B];
         {
@@ -520,35 +542,34 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
           const unsigned n0 = RES_NIB(0, 0), n1 = RES_NIB(0, 1);
 #pragma unroll
           for (int k = 0; k < B; k++) {
-            rc += (int)((n0 >> k) & 1u);
-            it0[k] = a.run_item[(n0 >> k) & 1u ? rc : rb0];
+            rcb += ((n0 >> k) & 1u) << 2;
+            it0[k] = *(const int *)(run_item_b + ((n0 >> k) & 1u ? rcb : rb0b));
           }
 #pragma unroll
           for (int k = 0; k < B; k++) {
-            rc += (int)((n1 >> k) & 1u);
-            itA[k] = a.run_item[(n1 >> k) & 1u ? rc : rb0];
+            rcb += ((n1 >> k) & 1u) << 2;
+            itA[k] = *(const int *)(run_item_b + ((n1 >> k) & 1u ? rcb : rb0b));
           }
 #pragma unroll
-          for (int k = 0; k < B; k++) ccA[k] = a.dv[2 * (int64_t)((n0 >> k) & 1u ? it0[k] : pad_item) + 1];
+          for (int k = 0; k < B; k++) ccA[k] = *(const double *)(dv_b + 8 + ((n0 >> k) & 1u ? (unsigned)it0[k] << 4 : padb));
         }
         double ccc = 0.0;
         int itB[B];
         double ccB[B];
-#ifdef MFM_RES_UCST  // (experiment: a fixed number of stores per batch, the slots that close nothing store to the pad run)
-#define RES_PARTIAL_STORE() part2[head && have_head ? rcC - 1 : trash_run] = d2_t{s1, s2}
-#else
-#define RES_PARTIAL_STORE() \
-  if (head && have_head) part2[rcC - 1] = d2_t{s1, s2}
-#endif
+// One store per slot, no branch: a slot that closes no run stores into the workgroup's pad run, which nobody reads. (Some
+// lane of a wave closes a run at almost every slot -- a run start every 4.9th slot, 64 lanes -- so the masked store was
+// issued anyway; its exec-mask save / restore split every step into basic blocks.)
+#define RES_PARTIAL_STORE() *(d2_t *)(part_b + (head && have_head ? rcCb : trashb)) = d2_t{s1, s2}
 #define RES_STEP_B(j, bb, iti, ito, cci, cco)                                                                              \
   {                                                                                                                        \
     const unsigned n4 = RES_NIB(j, bb), n4a = RES_NIB(j, (bb) + 1), n4b = RES_NIB(j, (bb) + 2);                            \
     const unsigned h4 = (hbv[j] >> (4 * (bb))) & 15u;                                                                      \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      rc += (int)((n4b >> k) & 1u);                                                                                        \
-      ito[k] = a.run_item[(n4b >> k) & 1u ? rc : rb0];                                                                     \
+      rcb += ((n4b >> k) & 1u) << 2;                                                                                       \
+      ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
     }                                                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < B; k++) cco[k] = a.dv[2 * (int64_t)((n4a >> k) & 1u ? iti[k] : pad_item) + 1];   \
+    _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
+      cco[k] = *(const double *)(dv_b + 8 + ((n4a >> k) & 1u ? (unsigned)iti[k] << 4 : padb));                             \
     int uid[B];                                                                                                            \
     RES_UIDS(j, bb, uid);                                                                                                  \
     d2_t ut[B];                                                                                                            \
@@ -561,8 +582,8 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       const bool need = ((n4 >> k) & 1u) != 0u;                                                                            \
       const bool head = ((h4 >> k) & 1u) != 0u;                                                                            \
       ccc = need ? cci[k] : ccc;                                                                                           \
-      rcC += need ? 1 : 0; /* the run of this slot */                                                                      \
-      /* a run that began and ended in this thread: the slot before this head closed run rcC - 1 */                        \
+      rcCb += need ? 16u : 0u; /* the run of this slot, in bytes */                                                        \
+      /* a run that began and ended in this thread: the slot before this head closed the run before it */                        \
       RES_PARTIAL_STORE();                                                                                                 \
       f1 = head && !have_head ? s1 : f1;                                                                                   \
       f2 = head && !have_head ? s2 : f2;                                                                                   \
@@ -581,10 +602,11 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     const unsigned n4 = ((nbw >> (4 * (bb))) & 15u), n4a = ((nbw >> (4 * ((bb) + 1))) & 15u), n4b = ((nbw >> (4 * ((bb) + 2))) & 15u);                            \
     const unsigned h4 = (hb_c >> (4 * (bb))) & 15u;                                                                       \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      rc += (int)((n4b >> k) & 1u);                                                                                        \
-      ito[k] = a.run_item[(n4b >> k) & 1u ? rc : rb0];                                                                     \
+      rcb += ((n4b >> k) & 1u) << 2;                                                                                       \
+      ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
     }                                                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < B; k++) cco[k] = a.dv[2 * (int64_t)((n4a >> k) & 1u ? iti[k] : pad_item) + 1];   \
+    _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
+      cco[k] = *(const double *)(dv_b + 8 + ((n4a >> k) & 1u ? (unsigned)iti[k] << 4 : padb));                             \
     int uid[B];                                                                                                            \
     RES_UIDSX(bb, uid);                                                                                                      \
     d2_t ut[B];                                                                                                            \
@@ -597,8 +619,8 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       const bool need = ((n4 >> k) & 1u) != 0u;                                                                            \
       const bool head = ((h4 >> k) & 1u) != 0u;                                                                            \
       ccc = need ? cci[k] : ccc;                                                                                           \
-      rcC += need ? 1 : 0; /* the run of this slot */                                                                      \
-      /* a run that began and ended in this thread: the slot before this head closed run rcC - 1 */                        \
+      rcCb += need ? 16u : 0u; /* the run of this slot, in bytes */                                                        \
+      /* a run that began and ended in this thread: the slot before this head closed the run before it */                        \
       RES_PARTIAL_STORE();                                                                                                 \
       f1 = head && !have_head ? s1 : f1;                                                                                   \
       f2 = head && !have_head ? s2 : f2;                                                                                   \
@@ -614,16 +636,13 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
           RES_PRIO(j);
 #pragma unroll 1
           for (int bp = 0; bp < 2; bp++) {
-              RES_STEP_B(j, 2 * bp, itA, itB, ccA, ccB);
-            if (a.prof && lane == 0 && (wv == 4 || wv == 7))  // (waves 4 and 7: every batch)
-              a.prof[((int64_t)g * a.n_sw + (f - f_first)) * 64 + 16 + (wv == 4 ? 0 : 20) + 4 * j + 2 * bp] =
-                  __builtin_amdgcn_s_memrealtime();
+            RES_STEP_B(j, 2 * bp, itA, itB, ccA, ccB);
             RES_STEP_B(j, 2 * bp + 1, itB, itA, ccB, ccA);
-            if (a.prof && lane == 0 && (wv == 4 || wv == 7))
-              a.prof[((int64_t)g * a.n_sw + (f - f_first)) * 64 + 16 + (wv == 4 ? 0 : 20) + 4 * j + 2 * bp + 1] =
-                  __builtin_amdgcn_s_memrealtime();
           }
+          if (a.prof && lane == 0 && (wv == 4 || wv == 7))  // (waves 4 and 7: every group)
+            a.prof[((int64_t)g * a.n_sw + (f - f_first)) * 64 + 16 + (wv == 4 ? 0 : 20) + j] = __builtin_amdgcn_s_memrealtime();
         }
+        asm volatile(";; res sweep end");
         if (OVF) {
           unsigned hb_c = nbx0;
           for (int jx = 0; jx < ngx; jx++) {
@@ -863,6 +882,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
 #undef RES_NIB
 #undef RES_UIDS
 #undef RES_UIDSX
+#undef RES_OPAQUE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   RES_STAMP0(4);
 #undef RES_STAMP0
@@ -1768,10 +1788,10 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
             for (int f = 0; f < K2; f++) d += (double)(h[((size_t)g * K2 + f) * 64 + 8 + w] - h[((size_t)g * K2 + f) * 64 + 2]) * 0.01;
             std::fprintf(stderr, " %.1f", d / K2);
           }
-          std::fprintf(stderr, "\n      batches of waves 4 and 7 (factor 3 alone):");
+          std::fprintf(stderr, "\n      groups of 16 slots of waves 4 and 7 (factor 3 alone):");
           for (int w : {0, 20}) {
             std::fprintf(stderr, " |");
-            for (int b = 0; b < (rp.RV + rp.RL) / 4; b++)
+            for (int b = 0; b < (rp.RV + rp.RL) / 16; b++)
               std::fprintf(stderr, " %.1f", (double)(h[((size_t)g * K2 + 3) * 64 + 16 + w + b] - h[((size_t)g * K2 + 3) * 64 + 2]) * 0.01);
           }
           std::fprintf(stderr, "\n");
