@@ -14,12 +14,19 @@ libmyfm_hip.so through RCCL (strong scaling: `value` = iterations/s of that chai
 
 Other BASELINE workloads (not the judged line; same code path): --config 2 | 4 | 5 [--scale S].
 
-Besides the contract's fields the line carries
-  "roofline":     HBM roofline of the dominant kernel class (its own algorithmic bytes / HIP-event time in the timed region)
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line. Besides the contract's fields
+that line carries
+  "roofline":     HBM roofline of the dominant kernel class (its own algorithmic bytes / HIP-event time in the timed region;
+                  the per-class breakdown from the diagnostic steps before the warm-up, which every run takes)
+--full also runs the legs the headline figure does not need, each of which can be given a budget of its own (and is then
+run without --full too):
   "cpu_baseline": the CPU oracle (Eigen-free restatement of the reference, built here with -O3 -march=native), ONE thread
-                  pinned to core 0, >= 30 s of full iterations of the same design
+                  pinned to core 0, >= 30 s of full iterations of the same design (--cpu-seconds)
   "fit":          the rate of the path users call: MyFMRegressor(rank).fit(X, y, n_iter) with the default number of kept
-                  samples and the default callback (create_train_fm: retention + callback inside the loop)
+                  samples and the default callback (create_train_fm: retention + callback inside the loop) (--fit-iters)
+  "value_long":   a timed region shorter than 1 s timed again for about 2 s (--long-seconds)
+  "weak_scaling": N > 1, config 3: one chain over N x the rows (--weak-steps)
+  "other_configs": config 3 on one GPU: BASELINE's other workloads and task types, each in a bench.py run of its own
 """
 import argparse
 import json
@@ -190,7 +197,7 @@ def self_launch(n_gpus):
 
 def other_configs(budget_s):
     """BASELINE's other workloads through the same code path, each as `bench.py --config C` in a subprocess (a fresh context,
-    bounded samples): iterations/s on the GPU next to the pinned CPU oracle. Reported inside the default line."""
+    bounded samples): iterations/s on the GPU next to the pinned CPU oracle. Reported inside the --full line."""
     out = {}
     runs = [("configs[1]", ["--config", "2", "--steps", "300", "--warmup", "20", "--cpu-seconds", "3"]),
             ("configs[3]", ["--config", "4", "--steps", "40", "--warmup", "5", "--cpu-seconds", "3"]),
@@ -219,7 +226,8 @@ def other_configs(budget_s):
         t0 = time.time()
         timing_args = [] if "--kernel-timing" in args else ["--no-kernel-timing"]
         args = [x for x in args if x != "--kernel-timing"]
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--fit-iters", "0", "--no-other-configs"] + timing_args + args,
+        # (each leg is a plain run: no fit leg, no value_long, no other_configs; the CPU oracle where the leg gives it a budget)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1"] + timing_args + args,
                            capture_output=True, text=True, cwd=ROOT)
         line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
         if r.returncode != 0 or not line:
@@ -238,7 +246,11 @@ def other_configs(budget_s):
     return out
 
 
-def main():
+# the budgets of the legs --full adds (None: not given on the command line -> this value with --full, 0 = off without it)
+FULL_LEGS = {"cpu_seconds": 30.0, "fit_iters": 100, "long_seconds": 2.0, "weak_steps": 20}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=0, help="timed iterations (0: enough for >= 10 s of GPU work at config 3, so that "
@@ -250,28 +262,40 @@ def main():
     ap.add_argument("--users", type=int, default=69878)
     ap.add_argument("--items", type=int, default=10677)
     ap.add_argument("--rank", type=int, default=0, help="0: the config's own rank")
-    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="CPU-oracle time budget (0 disables)")
+    ap.add_argument("--full", action="store_true", help="also run the legs the headline figure does not need: the CPU oracle, the "
+                    "MyFM*.fit() leg, value_long, the weak-scaling leg (N > 1) and, at config 3 on one GPU, other_configs")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="CPU-oracle time budget (default 30 with --full, else 0; 0 disables)")
     ap.add_argument("--cpu-iters", type=int, default=-1, help="(compat) 0 disables the CPU baseline")
-    ap.add_argument("--fit-iters", type=int, default=100, help="iterations of the MyFM*.fit() leg (0 disables)")
+    ap.add_argument("--fit-iters", type=int, default=None, help="iterations of the MyFM*.fit() leg (default 100 with --full, else 0; "
+                    "0 disables)")
     ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--weak-steps", type=int, default=20, help="N > 1: timed iterations of the weak-scaling leg (0 disables)")
-    ap.add_argument("--long-seconds", type=float, default=2.0, help="when the timed region is shorter than 1 s: also time the same loop "
-                    "for about this long and report it as value_long (0 disables)")
+    ap.add_argument("--weak-steps", type=int, default=None, help="N > 1: timed iterations of the weak-scaling leg (default 20 with "
+                    "--full, else 0; 0 disables)")
+    ap.add_argument("--long-seconds", type=float, default=None, help="when the timed region is shorter than 1 s: also time the same loop "
+                    "for about this long and report it as value_long (default 2 with --full, else 0; 0 disables)")
     ap.add_argument("--peer-exchange", action="store_true", help="N > 1, config 3: the persistent sweep row-sharded with the ranks' item sums "
                     "exchanged inside the launch (never run on two physical GPUs yet: opt-in; a trial of three iterations decides)")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run (config 3, 1 GPU): skip the other_configs legs")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full (config 3, 1 GPU): skip the other_configs legs")
     ap.add_argument("--task", default=None, help="regression | classification | ordered: the config's design with another task's target")
     ap.add_argument("--latent", default=None, help="latent draws of classification / ordered probit: exact (the reference's own stream, "
                     "draw for draw, evaluated on the device) | host (the same on the host) | philox (per-row streams)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last timed step to "
                     "DIR/<name>.npy (float64, at most 64 MB: a fixed seeded sample of larger arrays); N > 1: rank 0's")
-    a = ap.parse_args()
-    if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        raise SystemExit(self_launch(a.gpus))
+    a = ap.parse_args(argv)
+    for k, v in FULL_LEGS.items():
+        if getattr(a, k) is None:
+            setattr(a, k, v if a.full else type(v)(0))
     if a.cpu_iters == 0:
         a.cpu_seconds = 0.0
     if a.steps <= 0:
         a.steps = 2000 if a.config == 3 else (100 if a.config != 5 else 10)
+    return a
+
+
+def main():
+    a = parse_args()
+    if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        raise SystemExit(self_launch(a.gpus))
 
     # stdout carries exactly ONE line (the JSON): whatever native libraries print there (RCCL's version banner is flushed
     # at exit) goes to stderr instead
@@ -720,7 +744,7 @@ def main():
         #  10 M rows; the weak-scaling leg is one chain over N x 10 M rows)
         out["weak_scaling_it_per_s"] = weak["it_per_s"]
         out["weak_scaling_row_iterations_per_s"] = weak["row_iterations_per_s"]
-    if a.config == 3 and world == 1 and not a.no_other_configs and not force_sharded:
+    if a.full and a.config == 3 and world == 1 and not a.no_other_configs and not force_sharded:
         out["other_configs"] = other_configs(budget_s=300.0)
     if sharded:
         out["config"]["allreduce_calls_per_step"] = round(calls / a.steps, 1)

@@ -38,6 +38,23 @@ def test_bench_line_small_config3():
     assert d["fit"]["fit_it_per_s"] > 0
 
 
+def test_bench_plain_line_is_lean():
+    """A plain run prints the contract's fields and the roofline of its own timed region, and runs no other leg."""
+    d = _run("--rows", "300000", "--steps", "4", "--warmup", "2")
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert d["roofline"]["bound"] == "hbm" and d["roofline"]["by_kernel_ms_per_step"]
+    assert d["cpu_baseline"] is None and d["fit"] is None
+    for k in ("value_long", "other_configs", "weak_scaling", "speedup_vs_cpu_baseline"):
+        assert k not in d, k
+
+
+def test_bench_full_runs_the_other_legs():
+    """--full turns on the legs of its own with their default budgets (value_long here: the timed region is far below 1 s)."""
+    d = _run("--full", "--no-other-configs", "--rows", "300000", "--steps", "4", "--warmup", "2", "--cpu-seconds", "1", "--fit-iters", "3")
+    assert d["steps"] == 4 and d["value"] > 0 and d["value_long"] > 0 and d["value_long_steps"] > 4
+    assert d["cpu_baseline"]["value"] > 0 and d["fit"]["fit_it_per_s"] > 0 and "other_configs" not in d
+
+
 def test_bench_line_relation_blocks():
     d = _run("--config", "4", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--fit-iters", "0")
     assert d["config"]["relation_blocks"] and d["value"] > 0 and d["cpu_baseline"] is None
