@@ -382,6 +382,58 @@ int mfm_host_column_levels(int64_t n_rows, int64_t n_cols, const int64_t *indptr
 int mfm_cs_plan_selftest(int64_t n_rows, int32_t n_cols, const int64_t *colptr, const int32_t *rowidx, const double *val, int32_t cg,
                          int32_t lw, int32_t nb, int32_t rd, int32_t cap, double *max_rel_diff, int64_t *info);
 
+/* ---- variational inference (csrc/mfm_vb.hip): the device steps of VariationalFMTrainer::update_all
+ * (include/myfm/variational.hpp:192-217, BaseFMTrainer.hpp:135-152). An mfm_vb holds the table -- the main table with the
+ * rows of its relation blocks appended (CSR, and CSC in a conflict-free level order of its columns) --, y, the group of
+ * every feature, the model
+ * (w0, w0_var, w, w_var, V, V_var; V / V_var column-major (D, K)) and the per-row residual e. It takes none of the Gibbs
+ * context's fast paths and draws no random numbers: after the initial weights (drawn by the host) the iteration is
+ * deterministic, and every sum has a fixed association, so a rerun is bit-identical. Per-group arrays are packed by "slot":
+ * slot 0 is w, slot 1 + f is factor f, entry (slot s, group g) at [s * G + g].                                               */
+typedef struct mfm_vb mfm_vb;
+/* VariationalFMTrainer(X, relations, y, ...) (variational.hpp:180-185, BaseFMTrainer.hpp:58-105) in three calls: the (N, D0)
+ * main table and y; each relation block (B rows, Db columns, original_to_block (N)), in order; then finalize with
+ * group_index (D = D0 + the blocks' columns, values in [0, G)) and the rank. The blocks' rows are appended to the train
+ * rows that map to them: the block caches of the reference (:388-447, :557-710, :728-827) are sums over those rows, so the
+ * iteration is the same in exact arithmetic. A row that holds a column twice is refused (MFM_ERR_INVALID).              */
+int mfm_vb_create(int device, int64_t N, int64_t D0, const int64_t *indptr, const int32_t *indices, const double *data,
+                  const double *y, mfm_vb **out);
+int mfm_vb_add_block(mfm_vb *v, int64_t B, int64_t Db, const int64_t *indptr, const int32_t *indices, const double *data,
+                     const int64_t *original_to_block);
+int mfm_vb_finalize(mfm_vb *v, const int32_t *group_index, int32_t G, int32_t rank);
+void mfm_vb_destroy(mfm_vb *v);
+const char *mfm_vb_last_error(const mfm_vb *v); /* (NULL: the error of the last failed mfm_vb_create of this thread) */
+/* levels of the column schedule, kernel launches of one iteration */
+int mfm_vb_plan_info(const mfm_vb *v, int64_t *n_levels, int64_t *n_launches_per_iteration);
+/* the model (VariationalFM, variational.hpp:64-103); NULL array pointers are skipped */
+int mfm_vb_set_state(mfm_vb *v, double w0, double w0_var, const double *w, const double *w_var, const double *V,
+                     const double *V_var);
+int mfm_vb_get_state(mfm_vb *v, double *w0, double *w0_var, double *w, double *w_var, double *V, double *V_var);
+/* update_w0 (variational.hpp:348-361): the scalars only; the host shifts e with mfm_vb_shift_e */
+int mfm_vb_set_w0(mfm_vb *v, double w0, double w0_var);
+/* update_e_and_var (variational.hpp:715-833) and the residual: mode 0 e -= y (initialize_e :234-241, update_e for regression
+ * :839-840), mode 1 e -= E[z] of the truncated normal (classification, :841-856). out4: sum e, sum e^2, e_var_sum (with
+ * N * w0_var), sum over rows of lnZ + (E[z] - score)^2 / 2 (0 in mode 0).                                                  */
+int mfm_vb_update_e(mfm_vb *v, int32_t mode, double *out4);
+int mfm_vb_shift_e(mfm_vb *v, double delta); /* e += delta (update_w0 :358) */
+int mfm_vb_get_e(mfm_vb *v, double *e);
+/* the per-row cache of the factor last swept by mfm_vb_sweep_V: q, x2s, x3sv (NULL skips) */
+int mfm_vb_get_cache(mfm_vb *v, double *q, double *x2s, double *x3sv);
+/* fit_linear == false: w = w_var = 0 without touching e (variational.hpp:364-367); the caller then sweeps anyway */
+int mfm_vb_zero_w(mfm_vb *v);
+/* update_w, main table (variational.hpp:368-386): lambda_w, mu_w (G) */
+int mfm_vb_sweep_w(mfm_vb *v, double alpha, const double *lambda_w, const double *mu_w);
+/* update_V, main table (variational.hpp:450-554) for factors [f_begin, f_end): lambda_V, mu_V column-major (G, K) */
+int mfm_vb_sweep_V(mfm_vb *v, int32_t f_begin, int32_t f_end, double alpha, const double *lambda_V, const double *mu_V);
+/* per slot s in [s_begin, s_end) and group g, with mu / mu_var packed by slot ((K + 1) * G each): out[((s - s_begin) * G + g)
+ * * 3 + k] = sum theta, sum ((theta - mu)^2 + mu_var + var), sum log var over the group's features (update_lambda_generic
+ * :269-295, update_mu_generic :298-318, the weight terms of the ELBO :872-917).                                            */
+int mfm_vb_group_stats(mfm_vb *v, int32_t s_begin, int32_t s_end, const double *mu, const double *mu_var, double *out);
+int mfm_vb_synchronize(mfm_vb *v);
+/* mean_var_truncated_normal_left (right = 0) / _right (right = 1) (util.hpp:80-115) on the host, by the same code the
+ * classification residual of mfm_vb_update_e runs on the device: out3 = mean, variance, log Z                              */
+int mfm_vb_truncated_normal(int32_t right, double mu, double *out3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ from .estimators import (  # noqa: E402
     MyFMGibbsRegressor,
     MyFMOrderedProbit,
     MyFMRegressor,
+    VariationalFMClassifier,
+    VariationalFMRegressor,
 )
 
 __all__ = [
@@ -35,4 +37,6 @@ __all__ = [
     "MyFMClassifier",
     "MyFMGibbsRegressor",
     "MyFMGibbsClassifier",
+    "VariationalFMRegressor",
+    "VariationalFMClassifier",
 ]

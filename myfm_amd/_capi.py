@@ -33,6 +33,9 @@ SYMBOLS = [
     "mfm_store_push_host", "mfm_store_get", "mfm_design_predict_store", "mfm_store_reserve", "mfm_cs_plan_selftest",
     "mfm_regression_iteration_ready", "mfm_regression_iteration",
     "mfm_update_e_classification_exact", "mfm_oprobit_sample_z_exact", "mfm_latent_stats", "mfm_rng_host_read", "mfm_rng_host_advance", "mfm_set_latent_order",
+    "mfm_vb_create", "mfm_vb_add_block", "mfm_vb_finalize", "mfm_vb_destroy", "mfm_vb_last_error", "mfm_vb_plan_info", "mfm_vb_set_state", "mfm_vb_get_state",
+    "mfm_vb_set_w0", "mfm_vb_update_e", "mfm_vb_shift_e", "mfm_vb_get_e", "mfm_vb_get_cache", "mfm_vb_zero_w", "mfm_vb_sweep_w",
+    "mfm_vb_sweep_V", "mfm_vb_group_stats", "mfm_vb_synchronize", "mfm_vb_truncated_normal",
 ]
 
 _lib = None

@@ -1819,6 +1819,280 @@ struct GibbsSession {
   }
 };
 
+// ---- variational FM (include/myfm/variational.hpp): VariationalFM, VariationalFMHyperParameters, VariationalPredictor,
+// VariationalLearningHistory, VariationalFMTrainer. The device steps run behind the mfm_vb_* entry points (csrc/mfm_vb.hip);
+// the O(G K) hyper-parameter arithmetic runs here, in the reference's order.
+void vck(mfm_vb *v, int code) {
+  if (code != MFM_OK) throw_code(code, mfm_vb_last_error(v));
+}
+
+// variational.hpp:64-103
+struct VFM {
+  int n_factors = 0;
+  Real w0 = 0, w0_var = 0;
+  vector<Real> w, w_var;   // (D)
+  vector<Real> V, V_var;   // column-major (D, K)
+  vector<vector<Real>> cutpoints;
+  // live model handed to callbacks: w, w_var, V, V_var stay on the GPU until somebody looks at them
+  mfm_vb *live = nullptr;
+  bool stale = false;
+  VFM() {}
+  explicit VFM(int n_factors) : n_factors(n_factors) {}
+  VFM(Real w0, Real w0_var, vector<Real> w, vector<Real> w_var, vector<Real> V, vector<Real> V_var, int K,
+      vector<vector<Real>> cutpoints = {})
+      : n_factors(K), w0(w0), w0_var(w0_var), w(std::move(w)), w_var(std::move(w_var)), V(std::move(V)),
+        V_var(std::move(V_var)), cutpoints(std::move(cutpoints)) {}
+  void ensure() {
+    if (stale && live) {
+      stale = false;
+      vck(live, mfm_vb_get_state(live, nullptr, nullptr, w.data(), w_var.data(), V.data(), V_var.data()));
+    }
+  }
+  int64_t D() const { return (int64_t)w.size(); }
+  // the mean model as a one-sample Gibbs FM: prediction runs the Gibbs scorer
+  FM mean_fm() {
+    ensure();
+    return FM(w0, w, V, n_factors, cutpoints);
+  }
+  py::array_t<double> predict_score(const py::object &Xo, const py::object &relso) { return mean_fm().predict_score(Xo, relso); }
+};
+
+// variational.hpp:25-62
+struct VHyper {
+  Real alpha = 1, alpha_rate = 1;
+  vector<Real> mu_w, mu_w_var, lambda_w, lambda_w_rate;  // (G)
+  vector<Real> mu_V, mu_V_var, lambda_V, lambda_V_rate;  // column-major (G, K)
+  size_t G = 0, K = 0;
+  VHyper() {}
+  VHyper(size_t n_factors, size_t n_groups)
+      : mu_w(n_groups), mu_w_var(n_groups), lambda_w(n_groups), lambda_w_rate(n_groups), mu_V(n_groups * n_factors),
+        mu_V_var(n_groups * n_factors), lambda_V(n_groups * n_factors), lambda_V_rate(n_groups * n_factors), G(n_groups),
+        K(n_factors) {}
+  // the FMHyperParameters part (the history keeps the model's hyper-parameters sliced to it, variational.hpp:139-145)
+  Hyper sliced() const {
+    Hyper h(K, G);
+    h.alpha = alpha;
+    h.mu_w = mu_w;
+    h.lambda_w = lambda_w;
+    h.mu_V = mu_V;
+    h.lambda_V = lambda_V;
+    return h;
+  }
+};
+
+struct VHistory {
+  Hyper hyper;
+  vector<Real> elbos;
+};
+
+// Predictor<Real, VariationalFM<Real>> (variational.hpp:105-106): one sample, the final model, scored by the Gibbs predictor
+struct VPredictor {
+  size_t rank, feature_size;
+  TaskType type;
+  vector<VFM> samples;
+  VPredictor(size_t rank, size_t feature_size, TaskType type) : rank(rank), feature_size(feature_size), type(type) {}
+  py::array_t<double> predict(const py::object &X, const py::object &rels) const {
+    Predictor p(rank, feature_size, type);
+    for (auto &s : samples) p.samples.push_back(const_cast<VFM &>(s).mean_fm());
+    return p.predict(X, rels);
+  }
+};
+
+struct VFMTrainer {
+  CsrView X;
+  Relations rels;
+  vector<Real> y;
+  size_t dim_all = 0;
+  FMLearningConfig cfg;
+  std::mt19937 gen_;
+  // BaseFMTrainer.hpp:58-105
+  VFMTrainer(const py::object &Xo, const py::object &relso, const py::object &yo, int random_seed, FMLearningConfig config)
+      : cfg(std::move(config)), gen_(random_seed) {
+    X = csr_view_from_py(Xo);
+    rels = relations_from_py(relso);
+    dim_all = check_row_consistency_return_column(X, rels);
+    y = np_to_vec(yo);
+    if ((int64_t)y.size() != X.rows) throw std::invalid_argument("X and y have different numbers of rows");
+    if (cfg.group_index.size() != dim_all) throw std::out_of_range("group_index does not cover all features");
+  }
+  // variational.hpp:70-89: w0, then w, then V from one normal_distribution -- the same 1 + D + D K outputs as the Gibbs
+  // initialisation (FM.hpp:34-45, which assigns them to V, w, w0), so the Gibbs filler draws them and they are reassigned
+  VFM create_FM(int rank, Real init_std) {
+    FM g(rank);
+    g.initialize_weight((int64_t)dim_all, init_std, gen_);
+    vector<Real> s(g.V);
+    s.insert(s.end(), g.w.begin(), g.w.end());
+    s.push_back(g.w0);
+    const size_t D = dim_all;
+    VFM fm(rank);
+    fm.w0 = s[0];
+    fm.w0_var = 1;
+    fm.w.assign(s.begin() + 1, s.begin() + 1 + (std::ptrdiff_t)D);
+    fm.w_var.assign(D, init_std * init_std);
+    fm.V.assign(s.begin() + 1 + (std::ptrdiff_t)D, s.end());
+    fm.V_var.assign(D * (size_t)rank, init_std * init_std);
+    return fm;
+  }
+  VHyper create_Hyper(size_t rank) { return VHyper(rank, cfg.n_groups); }
+
+  std::pair<VPredictor, VHistory> learn_with_callback(VFM &fm, VHyper &hyper,
+                                                      const std::function<bool(int, VFM *, VHyper *, VHistory *)> &cb) {
+    const int64_t N = X.rows, D = (int64_t)dim_all;
+    const int K = fm.n_factors;
+    const size_t G = cfg.n_groups;
+    // initialize_hyper (variational.hpp:219-232)
+    hyper.alpha = 1;
+    hyper.alpha_rate = N * .5;
+    std::fill(hyper.mu_w.begin(), hyper.mu_w.end(), 0.0);
+    std::fill(hyper.mu_w_var.begin(), hyper.mu_w_var.end(), 1.0);
+    std::fill(hyper.lambda_w.begin(), hyper.lambda_w.end(), 1e-5);
+    std::fill(hyper.lambda_w_rate.begin(), hyper.lambda_w_rate.end(), 1.0);
+    std::fill(hyper.mu_V.begin(), hyper.mu_V.end(), 0.0);
+    std::fill(hyper.mu_V_var.begin(), hyper.mu_V_var.end(), 1.0);
+    std::fill(hyper.lambda_V.begin(), hyper.lambda_V.end(), 1e-5);
+    std::fill(hyper.lambda_V_rate.begin(), hyper.lambda_V_rate.end(), 1.0);
+    // initialize_e (:234-241)
+    if (cfg.task_type == TaskType::ORDERED)
+      throw std::runtime_error("Ordered Probit Regression  for Variational FM not implemented");
+    vector<int32_t> gidx(cfg.group_index.begin(), cfg.group_index.end());
+    mfm_vb *raw = nullptr;
+    int code = mfm_vb_create(selected_device(), N, X.cols, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), &raw);
+    if (code != MFM_OK) throw_code(code, mfm_vb_last_error(nullptr));
+    std::unique_ptr<mfm_vb, void (*)(mfm_vb *)> v(raw, mfm_vb_destroy);
+    for (auto &r : rels)
+      vck(v.get(), mfm_vb_add_block(v.get(), r->X.rows, r->X.cols, r->X.indptr.data(), r->X.indices.data(), r->X.data.data(),
+                                    r->map64()));
+    vck(v.get(), mfm_vb_finalize(v.get(), gidx.data(), (int32_t)G, K));
+    (void)D;
+    vck(v.get(), mfm_vb_set_state(v.get(), fm.w0, fm.w0_var, fm.w.data(), fm.w_var.data(), fm.V.data(), fm.V_var.data()));
+    double sums[4];
+    vck(v.get(), mfm_vb_update_e(v.get(), 0, sums));
+
+    std::pair<VPredictor, VHistory> result{VPredictor((size_t)K, dim_all, cfg.task_type), VHistory{hyper.sliced(), {}}};
+    vector<Real> n_g(G, 0.0);
+    for (size_t g = 0; g < G; g++) n_g[g] = (Real)cfg.group_vs_feature_index[g].size();
+    const size_t S = (size_t)K + 1;
+    vector<Real> st(S * G * 3), mu(S * G), mu_var(S * G);
+    auto pack_mu = [&]() {
+      std::copy(hyper.mu_w.begin(), hyper.mu_w.end(), mu.begin());
+      std::copy(hyper.mu_V.begin(), hyper.mu_V.end(), mu.begin() + (std::ptrdiff_t)G);
+      std::copy(hyper.mu_w_var.begin(), hyper.mu_w_var.end(), mu_var.begin());
+      std::copy(hyper.mu_V_var.begin(), hyper.mu_V_var.end(), mu_var.begin() + (std::ptrdiff_t)G);
+    };
+    // update_lambda_generic (:269-295) then update_mu_generic (:298-318) of one slot, from its group statistics
+    auto lambda_mu = [&](const Real *s3, Real &mu_g, Real &mu_var_g, Real &lambda_g, Real &lambda_rate_g, Real n) {
+      const Real beta = cfg.beta_0 + s3[1];
+      lambda_g = (cfg.alpha_0 + n) / beta;
+      lambda_rate_g = beta / 2;
+      const Real square = lambda_g * (cfg.gamma_0 + n);
+      const Real linear = (cfg.gamma_0 * cfg.mu_0 + s3[0]) * lambda_g;
+      mu_g = linear / square;
+      mu_var_g = 1 / square;
+    };
+    Real elbo = 0;
+    for (int iteration = 0; iteration < cfg.n_iter; iteration++) {
+      // update_alpha (:248-266)
+      if (cfg.task_type == TaskType::CLASSIFICATION) {
+        hyper.alpha = 1;
+        hyper.alpha_rate = 1;
+      } else {
+        const Real e_all = sums[1] + sums[2];
+        const Real exponent = (cfg.alpha_0 + N) / 2;
+        const Real rate = (cfg.beta_0 + e_all) / 2;
+        hyper.alpha = exponent / rate;
+        hyper.alpha_rate = rate;
+      }
+      // update_w0 (:348-361)
+      if (!cfg.fit_w0) {
+        fm.w0 = 0;
+        fm.w0_var = 0;
+      } else {
+        const Real lin = hyper.alpha * (fm.w0 * N - sums[0]);
+        const Real quad = hyper.alpha * N + cfg.reg_0;
+        const Real w0_new = lin / quad;
+        vck(v.get(), mfm_vb_shift_e(v.get(), w0_new - fm.w0));
+        fm.w0 = w0_new;
+        fm.w0_var = 1 / quad;
+      }
+      vck(v.get(), mfm_vb_set_w0(v.get(), fm.w0, fm.w0_var));
+      // update_lambda_w, update_mu_w
+      pack_mu();
+      vck(v.get(), mfm_vb_group_stats(v.get(), 0, 1, mu.data(), mu_var.data(), st.data()));
+      for (size_t g = 0; g < G; g++)
+        lambda_mu(&st[g * 3], hyper.mu_w[g], hyper.mu_w_var[g], hyper.lambda_w[g], hyper.lambda_w_rate[g], n_g[g]);
+      // update_w (:363-386): with fit_linear == false w and w_var are zeroed, e is left alone, and the sweep runs anyway
+      if (!cfg.fit_linear) vck(v.get(), mfm_vb_zero_w(v.get()));
+      vck(v.get(), mfm_vb_sweep_w(v.get(), hyper.alpha, hyper.lambda_w.data(), hyper.mu_w.data()));
+      // update_lambda_V, update_mu_V: every factor's lambda from the old mu, then every factor's mu
+      if (K > 0) {
+        pack_mu();
+        vck(v.get(), mfm_vb_group_stats(v.get(), 1, K + 1, mu.data(), mu_var.data(), st.data()));
+        for (int r = 0; r < K; r++)
+          for (size_t g = 0; g < G; g++) {
+            const size_t i = (size_t)r * G + g;
+            lambda_mu(&st[i * 3], hyper.mu_V[i], hyper.mu_V_var[i], hyper.lambda_V[i], hyper.lambda_V_rate[i], n_g[g]);
+          }
+        // update_V (:450-554)
+        vck(v.get(), mfm_vb_sweep_V(v.get(), 0, K, hyper.alpha, hyper.lambda_V.data(), hyper.mu_V.data()));
+      }
+      // update_e (:835-918)
+      const bool clf = cfg.task_type == TaskType::CLASSIFICATION;
+      vck(v.get(), mfm_vb_update_e(v.get(), clf ? 1 : 0, sums));
+      elbo = clf ? sums[3] : 0;
+      elbo += -hyper.alpha * (cfg.beta_0 + sums[1] + sums[2]) / 2;
+      elbo += hyper.alpha * hyper.alpha_rate * (1 - std::log(hyper.alpha_rate));
+      elbo += -cfg.gamma_0 * (fm.w0 * fm.w0 + fm.w0_var) + 0.5 * std::log(fm.w0_var);
+      pack_mu();
+      vck(v.get(), mfm_vb_group_stats(v.get(), 0, K + 1, mu.data(), mu_var.data(), st.data()));
+      for (size_t g = 0; g < G; g++) {
+        elbo += 0.5 * std::log(hyper.mu_w_var[g]);
+        Real rate = cfg.beta_0 + st[g * 3 + 1];
+        elbo += 0.5 * st[g * 3 + 2];
+        elbo += hyper.lambda_w[g] * (-rate / 2 + hyper.lambda_w_rate[g]);
+        elbo -= hyper.lambda_w[g] * hyper.lambda_w_rate[g] * std::log(hyper.lambda_w_rate[g]);
+        const Real dev = hyper.mu_w[g] - cfg.mu_0;
+        elbo += -(dev * dev) / 2;
+        for (int r = 0; r < K; r++) {
+          const size_t i = (size_t)r * G + g, s = (size_t)(r + 1) * G + g;
+          elbo += 0.5 * std::log(hyper.mu_V_var[i]);
+          rate = cfg.beta_0 + st[s * 3 + 1];
+          elbo += 0.5 * st[s * 3 + 2];
+          elbo += hyper.lambda_V[i] * (-rate / 2 + hyper.lambda_V_rate[i]);
+          elbo -= hyper.lambda_V[i] * hyper.lambda_V_rate[i] * std::log(hyper.lambda_V_rate[i]);
+        }
+      }
+      result.second.elbos.push_back(elbo);
+      fm.live = v.get();
+      fm.stale = true;
+      const bool stop = cb(iteration, &fm, &hyper, &result.second);
+      if (stop) break;
+    }
+    fm.live = v.get();
+    fm.stale = true;
+    fm.ensure();
+    fm.live = nullptr;
+    result.second.hyper = hyper.sliced();
+    result.first.samples.push_back(fm);
+    return result;
+  }
+};
+
+// cpp_source/declare_module.hpp:47-67
+std::pair<VPredictor, VHistory> create_train_vfm(size_t rank, Real init_std, const py::object &X, const py::object &relations,
+                                                 const py::object &y, int random_seed, FMLearningConfig &config,
+                                                 std::function<bool(int, VFM *, VHyper *, VHistory *)> cb) {
+  VFMTrainer trainer(X, relations, y, random_seed, config);
+  VFM fm = trainer.create_FM((int)rank, init_std);
+  VHyper hyper = trainer.create_Hyper(rank);
+  return trainer.learn_with_callback(fm, hyper, cb);
+}
+
+py::tuple truncated_normal_tuple(int right, Real mu) {
+  double r[3];
+  mfm_vb_truncated_normal(right, mu, r);
+  return py::make_tuple(r[0], r[1], r[2]);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_myfm, m) {
@@ -2072,6 +2346,177 @@ PYBIND11_MODULE(_myfm, m) {
                                });
       },
       "create and train fm.", py::return_value_policy::move);
+
+  // ---- variational FM (cpp_source/declare_module.hpp:194-404) ----
+  py::class_<VFM>(m, "VariationalFM")
+      .def_property(
+          "w0", [](VFM &f) { return f.w0; }, [](VFM &f, Real v) { f.w0 = v; })
+      .def_property(
+          "w0_var", [](VFM &f) { return f.w0_var; }, [](VFM &f, Real v) { f.w0_var = v; })
+      .def_property(
+          "w",
+          [](VFM &f) {
+            f.ensure();
+            return vec_to_np(f.w);
+          },
+          [](VFM &f, const py::object &v) {
+            f.ensure();
+            f.w = np_to_vec(v);
+          })
+      .def_property(
+          "w_var",
+          [](VFM &f) {
+            f.ensure();
+            return vec_to_np(f.w_var);
+          },
+          [](VFM &f, const py::object &v) {
+            f.ensure();
+            f.w_var = np_to_vec(v);
+          })
+      .def_property(
+          "V",
+          [](VFM &f) {
+            f.ensure();
+            return colmajor_to_np(f.V, f.D(), f.n_factors);
+          },
+          [](VFM &f, const py::object &v) {
+            f.ensure();
+            int64_t r, c;
+            f.V = np_to_colmajor(v, &r, &c);
+            f.n_factors = (int)c;
+          })
+      .def_property(
+          "V_var",
+          [](VFM &f) {
+            f.ensure();
+            return colmajor_to_np(f.V_var, f.D(), f.n_factors);
+          },
+          [](VFM &f, const py::object &v) {
+            f.ensure();
+            int64_t r, c;
+            f.V_var = np_to_colmajor(v, &r, &c);
+          })
+      .def_property(
+          "cutpoints",
+          [](VFM &f) {
+            py::list out;
+            for (auto &c : f.cutpoints) out.append(vec_to_np(c));
+            return out;
+          },
+          [](VFM &f, const py::object &v) {
+            f.cutpoints.clear();
+            for (auto item : py::reinterpret_borrow<py::sequence>(v)) f.cutpoints.push_back(np_to_vec(item));
+          })
+      .def("predict_score", &VFM::predict_score)
+      .def("__repr__",
+           [](VFM &f) {
+             f.ensure();
+             std::ostringstream ss;
+             ss << "<Factorization Machine sample with feature size = " << f.w.size() << ", rank = " << f.n_factors << ">";
+             return ss.str();
+           })
+      .def(py::pickle(
+          [](VFM &f) {
+            f.ensure();
+            py::list cps;
+            for (auto &c : f.cutpoints) cps.append(vec_to_np(c));
+            return py::make_tuple(f.w0, f.w0_var, vec_to_np(f.w), vec_to_np(f.w_var), colmajor_to_np(f.V, f.D(), f.n_factors),
+                                  colmajor_to_np(f.V_var, f.D(), f.n_factors), cps);
+          },
+          [](py::tuple t) {
+            if (t.size() != 6 && t.size() != 7) throw std::runtime_error("invalid state for FM.");
+            int64_t r, c, r2, c2;
+            vector<Real> V = np_to_colmajor(t[4], &r, &c), V_var = np_to_colmajor(t[5], &r2, &c2);
+            vector<vector<Real>> cps;
+            if (t.size() == 7)  // (the 6-tuple is the state of earlier versions)
+              for (auto item : py::reinterpret_borrow<py::sequence>(t[6])) cps.push_back(np_to_vec(item));
+            return VFM(t[0].cast<Real>(), t[1].cast<Real>(), np_to_vec(t[2]), np_to_vec(t[3]), std::move(V), std::move(V_var),
+                       (int)c, std::move(cps));
+          }));
+
+  py::class_<VHyper>(m, "VariationalFMHyperParameters")
+      .def_readonly("alpha", &VHyper::alpha)
+      .def_readonly("alpha_rate", &VHyper::alpha_rate)
+      .def_property_readonly("mu_w", [](const VHyper &h) { return vec_to_np(h.mu_w); })
+      .def_property_readonly("mu_w_var", [](const VHyper &h) { return vec_to_np(h.mu_w_var); })
+      .def_property_readonly("lambda_w", [](const VHyper &h) { return vec_to_np(h.lambda_w); })
+      .def_property_readonly("lambda_w_rate", [](const VHyper &h) { return vec_to_np(h.lambda_w_rate); })
+      .def_property_readonly("mu_V", [](const VHyper &h) { return colmajor_to_np(h.mu_V, h.G, h.K); })
+      .def_property_readonly("mu_V_var", [](const VHyper &h) { return colmajor_to_np(h.mu_V_var, h.G, h.K); })
+      .def_property_readonly("lambda_V", [](const VHyper &h) { return colmajor_to_np(h.lambda_V, h.G, h.K); })
+      .def_property_readonly("lambda_V_rate", [](const VHyper &h) { return colmajor_to_np(h.lambda_V_rate, h.G, h.K); })
+      .def(py::pickle(
+          [](const VHyper &h) {
+            return py::make_tuple(h.alpha, h.alpha_rate, vec_to_np(h.mu_w), vec_to_np(h.mu_w_var), vec_to_np(h.lambda_w),
+                                  vec_to_np(h.lambda_w_rate), colmajor_to_np(h.mu_V, h.G, h.K),
+                                  colmajor_to_np(h.mu_V_var, h.G, h.K), colmajor_to_np(h.lambda_V, h.G, h.K),
+                                  colmajor_to_np(h.lambda_V_rate, h.G, h.K));
+          },
+          [](py::tuple t) {
+            if (t.size() != 10) throw std::runtime_error("invalid state for FMHyperParameters.");
+            VHyper h;
+            h.alpha = t[0].cast<Real>();
+            h.alpha_rate = t[1].cast<Real>();
+            h.mu_w = np_to_vec(t[2]);
+            h.mu_w_var = np_to_vec(t[3]);
+            h.lambda_w = np_to_vec(t[4]);
+            h.lambda_w_rate = np_to_vec(t[5]);
+            int64_t r, c;
+            h.mu_V = np_to_colmajor(t[6], &r, &c);
+            h.mu_V_var = np_to_colmajor(t[7], &r, &c);
+            h.lambda_V = np_to_colmajor(t[8], &r, &c);
+            h.lambda_V_rate = np_to_colmajor(t[9], &r, &c);
+            h.G = (size_t)r;
+            h.K = (size_t)c;
+            return h;
+          }));
+
+  py::class_<VPredictor>(m, "VariationalPredictor")
+      .def("predict", &VPredictor::predict)
+      .def(py::pickle(
+          [](const VPredictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
+          [](py::tuple t) {
+            if (t.size() != 4) throw std::runtime_error("invalid state for FMHyperParameters.");
+            VPredictor p(t[0].cast<size_t>(), t[1].cast<size_t>(), static_cast<TaskType>(t[2].cast<int>()));
+            p.samples = t[3].cast<vector<VFM>>();
+            return p;
+          }))
+      .def("weights", [](VPredictor &p) { return p.samples.at(0); });
+
+  py::class_<VFMTrainer>(m, "VariationalFMTrainer")
+      .def(py::init<const py::object &, const py::object &, const py::object &, int, FMLearningConfig>())
+      .def("create_FM", &VFMTrainer::create_FM)
+      .def("create_Hyper", &VFMTrainer::create_Hyper);
+
+  py::class_<VHistory>(m, "VariationalLearningHistory")
+      .def_readonly("hypers", &VHistory::hyper)
+      .def_readonly("elbos", &VHistory::elbos)
+      .def(py::pickle([](const VHistory &h) { return py::make_tuple(h.hyper, h.elbos); },
+                      [](py::tuple t) {
+                        if (t.size() != 2) throw std::runtime_error("invalid state for VariationalLearningHistory.");
+                        return VHistory{t[0].cast<Hyper>(), t[1].cast<vector<Real>>()};
+                      }));
+
+  // (the callback protocol of create_train_fm, `myfm_every` included)
+  m.def(
+      "create_train_vfm",
+      [](size_t rank, Real init_std, const py::object &X, const py::object &relations, const py::object &y, int random_seed,
+         FMLearningConfig &learning_config, py::object callback) {
+        int every = 1;
+        if (py::hasattr(callback, "myfm_every")) every = std::max(1, callback.attr("myfm_every").cast<int>());
+        auto f = callback.cast<std::function<bool(int, VFM *, VHyper *, VHistory *)>>();
+        if (every == 1) return create_train_vfm(rank, init_std, X, relations, y, random_seed, learning_config, f);
+        const int n_iter = learning_config.n_iter;
+        return create_train_vfm(rank, init_std, X, relations, y, random_seed, learning_config,
+                                [f, every, n_iter](int it, VFM *fm, VHyper *hy, VHistory *h) {
+                                  if (it % every != 0 && it != n_iter - 1) return false;
+                                  return f(it, fm, hy, h);
+                                });
+      },
+      "create and train fm.", py::return_value_policy::move, py::arg("rank"), py::arg("init_std"), py::arg("X"),
+      py::arg("relations"), py::arg("y"), py::arg("random_seed"), py::arg("learning_config"), py::arg("callback"));
+  m.def("mean_var_truncated_normal_left", [](Real mu) { return truncated_normal_tuple(0, mu); });
+  m.def("mean_var_truncated_normal_right", [](Real mu) { return truncated_normal_tuple(1, mu); });
 
   // extensions beyond the reference's surface (bench / tests)
   py::class_<GibbsSession>(m, "GibbsSession")

@@ -75,10 +75,11 @@ class _ProgressBar:
             self.bar.update(n)
 
 
-class MyFMGibbsBase:
-    """Common part of the Gibbs estimators (base.py:70-323 + gibbs.py:32-142)."""
+class _FMEstimatorBase:
+    """What the Gibbs and the variational estimators share (base.py:70-323): arguments, fit's argument handling, prediction."""
 
     _task_type = TaskType.REGRESSION
+    _variational = False  # MyFMVariationalBase: create_train_vfm, rows in the caller's order
 
     def __init__(
         self,
@@ -209,7 +210,7 @@ class MyFMGibbsBase:
         # The sampler does not depend on the order of the training rows (every conditional is a sum over rows), the
         # device path does: a table sorted by its first one-hot field runs the fused passes. Rows that
         # arrive in another order are sorted by the first stored column here, together with y and the relation maps.
-        perm = _device_row_order(X)
+        perm = None if self._variational else _device_row_order(X)
         if perm is not None:
             ptr, idx, val = _myfm.permute_csr_rows(X.indptr, X.indices, X.data, perm)
             X = sps.csr_matrix((val, idx, ptr), shape=X.shape)
@@ -225,7 +226,8 @@ class MyFMGibbsBase:
                 else:
                     config_builder.set_latent_row_order(inv)
         config_builder.set_task_type(self._task_type)
-        config_builder.set_exact_latent_draws(self.exact_latent_draws and not os.environ.get("MYFM_AMD_PHILOX_LATENT"))
+        if not self._variational:
+            config_builder.set_exact_latent_draws(self.exact_latent_draws and not os.environ.get("MYFM_AMD_PHILOX_LATENT"))
         config = config_builder.build()
 
         default_callback = callback is None
@@ -248,7 +250,13 @@ class MyFMGibbsBase:
 
             from . import distributed as _dist
 
-            if _dist.active():
+            if self._variational:
+                if _dist.active():
+                    raise NotImplementedError("row-sharded variational inference is not supported")
+                self.predictor_, self.history_ = _myfm.create_train_vfm(
+                    self.rank, self.init_stdev, X, list(X_rel), np.ascontiguousarray(y, dtype=REAL), self.random_seed, config,
+                    wrapped)
+            elif _dist.active():
                 # row-sharded over the process group: same data on every rank, each trains on its slice
                 from . import _capi
 
@@ -282,6 +290,18 @@ class MyFMGibbsBase:
             raise RuntimeError("Predictor called before fit.")
         return self.predictor_
 
+    def _predict_core(self, X, X_rel=[], n_workers: Optional[int] = None):
+        predictor = self._fetch_predictor()
+        n = check_data_consistency(X, X_rel)
+        X = _as_csr(X, n)
+        if n_workers is None:
+            return predictor.predict(X, list(X_rel))
+        return predictor.predict_parallel(X, list(X_rel), n_workers)
+
+
+class MyFMGibbsBase(_FMEstimatorBase):
+    """Common part of the Gibbs estimators (base.py:70-323 + gibbs.py:32-142)."""
+
     @property
     def w0_samples(self):
         if self.predictor_ is None:
@@ -299,14 +319,6 @@ class MyFMGibbsBase:
         if self.predictor_ is None:
             return None
         return np.asarray([fm.V for fm in self.predictor_.samples], dtype=REAL)
-
-    def _predict_core(self, X, X_rel=[], n_workers: Optional[int] = None):
-        predictor = self._fetch_predictor()
-        n = check_data_consistency(X, X_rel)
-        X = _as_csr(X, n)
-        if n_workers is None:
-            return predictor.predict(X, list(X_rel))
-        return predictor.predict_parallel(X, list(X_rel), n_workers)
 
     def get_hyper_trace(self):
         """alpha, mu_w[g], lambda_w[g], mu_V[g,r], lambda_V[g,r] per iteration (gibbs.py:109-142)."""
@@ -472,6 +484,92 @@ class MyFMOrderedProbit(MyFMGibbsBase):
         if self.predictor_ is None:
             return None
         return np.asarray([fm.cutpoints[0] for fm in self.predictor_.samples], dtype=REAL)
+
+
+class MyFMVariationalBase(_FMEstimatorBase):
+    """Common part of the variational estimators (src/myfm/variational.py:40-167): the same arguments as the Gibbs
+    estimators (exact_latent_draws does not apply), and the posterior means and variances of the final model."""
+
+    _variational = True
+
+    def __init__(self, rank: int, init_stdev: float = 0.1, random_seed: int = 42, alpha_0: float = 1.0, beta_0: float = 1.0,
+                 gamma_0: float = 1.0, mu_0: float = 0.0, reg_0: float = 1.0, fit_w0: bool = True, fit_linear: bool = True):
+        super().__init__(rank, init_stdev=init_stdev, random_seed=random_seed, alpha_0=alpha_0, beta_0=beta_0, gamma_0=gamma_0,
+                         mu_0=mu_0, reg_0=reg_0, fit_w0=fit_w0, fit_linear=fit_linear)
+        del self.exact_latent_draws  # (a Gibbs option)
+
+    def _weight(self, name):
+        if self.predictor_ is None:
+            return None
+        return getattr(self.predictor_.weights(), name)
+
+    @property
+    def w0_mean(self):
+        return self._weight("w0")
+
+    @property
+    def w0_var(self):
+        return self._weight("w0_var")
+
+    @property
+    def w_mean(self):
+        return self._weight("w")
+
+    @property
+    def w_var(self):
+        return self._weight("w_var")
+
+    @property
+    def V_mean(self):
+        return self._weight("V")
+
+    @property
+    def V_var(self):
+        return self._weight("V_var")
+
+    def _fit_vb(self, X, y, X_rel, X_test, y_test, X_rel_test, n_iter, grouping, group_shapes, callback, config_builder):
+        self._fit(X, y, X_rel=X_rel, X_test=X_test, y_test=y_test, X_rel_test=X_rel_test, n_iter=n_iter, grouping=grouping,
+                  group_shapes=group_shapes, callback=callback, config_builder=config_builder)
+        return self
+
+
+class VariationalFMRegressor(MyFMVariationalBase):
+    """Bayesian FM regression by mean-field variational inference (variational.py:170-265)."""
+
+    # the task hooks of the regression estimators (the two families are siblings, as in the reference)
+    _task_type = TaskType.REGRESSION
+    _prepare_prediction_for_test = MyFMGibbsRegressor._prepare_prediction_for_test
+    _status_report = MyFMGibbsRegressor._status_report
+    _measure_score = MyFMGibbsRegressor._measure_score
+
+    def fit(self, X, y, X_rel=[], X_test=None, y_test=None, X_rel_test=[], n_iter=100, grouping=None, group_shapes=None,
+            callback=None, config_builder=None):
+        return self._fit_vb(X, y, X_rel, X_test, y_test, X_rel_test, n_iter, grouping, group_shapes, callback, config_builder)
+
+    def predict(self, X, X_rel=[]):
+        """The score of the mean model (variational.py:248-265)."""
+        return self._predict_core(X, X_rel)
+
+
+class VariationalFMClassifier(MyFMVariationalBase):
+    """Bayesian FM probit classification by mean-field variational inference (variational.py:268-383)."""
+
+    _task_type = TaskType.CLASSIFICATION
+    _process_y = MyFMGibbsClassifier._process_y
+    _prepare_prediction_for_test = MyFMGibbsClassifier._prepare_prediction_for_test
+    _status_report = MyFMGibbsClassifier._status_report
+    _measure_score = MyFMGibbsClassifier._measure_score
+
+    def fit(self, X, y, X_rel=[], X_test=None, y_test=None, X_rel_test=[], n_iter=100, grouping=None, group_shapes=None,
+            callback=None, config_builder=None):
+        return self._fit_vb(X, y, X_rel, X_test, y_test, X_rel_test, n_iter, grouping, group_shapes, callback, config_builder)
+
+    def predict_proba(self, X, X_rel=[]):
+        """Phi of the mean model's score (variational.py:366-383)."""
+        return self._predict_core(X, X_rel)
+
+    def predict(self, X, X_rel=[]):
+        return self.predict_proba(X, X_rel) > 0.5
 
 
 MyFMRegressor = MyFMGibbsRegressor
