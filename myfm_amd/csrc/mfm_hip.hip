@@ -127,6 +127,13 @@ struct ResidentBudget {
 struct mfm_ctx;
 namespace mfm {
 static void materialize_e(::mfm_ctx *c);  // (brings the residual back to row order: mfm_ctx::eq_rows)
+// Where the residual e is between two calls: in eq_ (row order); in res.e_slots, the persistent sweep's slot order -- WithSums:
+// res.sums holds sum e / sum e^2 of exactly these numbers; in cell.e (cell order); or nowhere: it is score - y and is recomputed
+// when somebody asks (mfm_set_residual_policy).
+enum class EWhere : uint8_t { Rows, Slots, SlotsWithSums, Cell, Dropped };
+// The form update_V takes on the main table, decided by decide_main_paths. Deferred: the persistent sweep took the
+// table first and the generic plans are not built; ensure_main_plans resolves it when a call needs them.
+enum class VPath : uint8_t { Deferred, Generic, QFree, Split, SplitFused, TwoField, ShardedSplit, ShardedTwoField, Cell };
 }
 using namespace mfm;
 
@@ -167,8 +174,7 @@ struct mfm_ctx {
   int64_t row_offset = 0;  // global index of local row 0 (keys the per-row Philox streams)
   std::vector<std::unique_ptr<DevBlock>> blocks;
   DevBuf<double> y;
-  // {e_t, q_t} in ROW order. Between the sweeps the residual may live elsewhere -- in the persistent sweep's slot order
-  // (e_in_slots), in the cell path's order (e_in_cell), or nowhere at all (e_lost: recomputed on demand) -- so nobody touches the
+  // {e_t, q_t} in ROW order. Between the sweeps the residual may live elsewhere (e_where) -- so nobody touches the
   // buffer directly: eq_rows() first brings the residual home (materialize_e) and is what every reader and read-modify-writer
   // in row order uses; eq_raw() is for the code that manages those states itself (the scorers that overwrite every residual, the
   // sweeps that take it from / leave it in another order, materialize_e).
@@ -178,6 +184,18 @@ struct mfm_ctx {
     mfm::materialize_e(this);
     return eq_.p;
   }
+  EWhere e_where = EWhere::Rows;
+  bool e_slot_order() const { return e_where == EWhere::Slots || e_where == EWhere::SlotsWithSums; }
+  // What the persistent launch over factors [f_begin, f_end) does with the residual: it reads it in slot order when it is there
+  // already, and does not write it back when update_e follows and recomputes it anyway (regression, every factor swept, the
+  // launch with the linear half that the Gibbs loop issues: the copy would be a dead store, 64 us). A sub-range never drops.
+  struct ResidentE {
+    bool load_slots, no_store;
+  };
+  ResidentE e_for_resident(bool with_w, int f_begin, int f_end) const {
+    return {e_slot_order(), with_w && e_recomputable && e_is_residual && f_begin == 0 && f_end == K};
+  }
+  void e_left_by_resident(const ResidentE &r) { e_where = r.no_store ? EWhere::Dropped : EWhere::Slots; }
   DevBuf<int32_t> group;
   DevBuf<int32_t> feat_sorted;
   DevBuf<int64_t> group_ptr;
@@ -196,29 +214,27 @@ struct mfm_ctx {
   DevBuf<double2> hs_out;       // mfm_hyper_stats: [sum e | w groups | V groups]
   DevBuf<double> hs_mu;         // mfm_hyper_stats: [mu_w | mu_V]
   int gs_chunks = 1;            // chunks of the largest group
-  DevBuf<double> ec, qc;        // split e / q arrays of the latent sweep (soa), compact residual (qfree)
-  bool qfree = false, soa = false, fuse_next = false;
-  bool mf = false;              // two-field pass (run_sweep_mf): no q-cache in HBM during update_V
+  DevBuf<double> ec, qc;        // split e / q arrays of the latent sweep (Split..., Sharded...), compact residual (QFree)
+  VPath v_path = VPath::Generic;
+  bool two_field() const { return v_path == VPath::TwoField || v_path == VPath::ShardedTwoField; }  // run_sweep_mf: no q-cache in HBM
   ResPlan res;                  // ... as one persistent launch with the residual resident on chip (mfm_res.hpp)
-  // the persistent sweep's layout was built first, on the device, and took the table: X_t, the level plans and the row tiles of
-  // the per-factor passes (their fall-back) are built when a call needs them (ensure_main_plans)
+  // The persistent sweep is an overlay on the forms whose tables it can take: it is switched on at mfm_finalize or by mfm_peer_set
+  // and off by drop_resident, and update_V asks here whether it runs.
+  bool resident_V() const { return res.ready && v_path != VPath::QFree && v_path != VPath::Generic && v_path != VPath::Cell; }
   std::vector<DevBuf<int32_t>> pre_maps;  // the blocks' maps uploaded ahead of the blocks (mfm_finalize only)
   // regression: outside the sweeps the residual IS score - y (update_e recomputes it after every update_V, FMTrainer.hpp:494), so
   // the persistent launch need not write its copy back (mfm_set_residual_policy); whoever asks for it in between gets it recomputed
-  bool e_recomputable = false, e_lost = false;
+  bool e_recomputable = false;
   // the residual is (score of the current model) - y, maintained by the sweeps: true after score_train(subtract_y), false once the
   // caller has installed his own residual (mfm_set_e, mfm_shift_e, the latent draws of classification / ordered probit). Only
   // such a residual may be dropped by the sweep and recomputed on demand.
   bool e_is_residual = false;
   bool res_sharded_pending = false;  // row-sharded: the persistent sweep's layout is built on every rank, waiting for mfm_peer_set
-  bool main_lazy = false;
   bool res_refused = false;  // the CUs of the persistent sweep were not ours to take
   int res_plan_cus = 0;      // workgroups the layout was asked for
   void ensure_main_plans();
-  bool e_in_cell = false;       // the residual lives in cell.e (cell order): every reader of eq calls materialize_e first
-  bool cell_w = false;          // ... and update_w runs on the cell layout too (the generic plans of the main table were not built)
   CellPlan cell;                // update_V of a design of index tuples (one-hot fields + relation blocks): no q-cache (mfm_cell.hpp)
-  bool sharded_fused = false;   // row-sharded + fused tile path (run_sweep_soa_sharded)
+  bool cell_w = false;          // ... and update_w runs on the cell layout too (the generic plans of the main table were not built)
   int q_stale_factor = -1;      // >= 0: the stored q column is stale, mfm_get_q rebuilds it for this factor first
   BlockOverflow gather_overflow;       // q-cache build: pointers of the relation blocks beyond MAX_BLOCKS
   DevBuf<double> wv_pack, zw_host;  // mfm_sweep_wV: [lambda_w | mu_w | lambda_V | mu_V] of the launch / host-given variates
@@ -229,11 +245,8 @@ struct mfm_ctx {
   hipEvent_t hyp_ev = nullptr;
   const double *w0_dev = nullptr;  // non-null while score_train should read the intercept from device memory
   std::vector<double> hs_stage;     // host staging of the packed hyper-parameter copies
-  bool slot_sums_valid = false;     // res.sums holds sum e / sum e^2 of the residual that is in slot order right now
   bool res_fills_device = false;  // the persistent sweep takes (nearly) every CU: nothing runs beside it
   int res_claim = 0;              // CUs this context holds in ResidentBudget for its persistent launch
-  bool e_in_slots = false;      // the residual after the resident latent sweep lives in res.e_slots (slot order): every
-                                // reader of eq calls materialize_e first; update_e overwrites it and just drops the flag
   DevBuf<double> sync_mask;     // [D] 1: this rank contributes the column to the model synchronisation
   PinnedRing ring;
   double2 *h_red = nullptr;  // pinned readback
@@ -569,63 +582,56 @@ static SweepArgs main_args(mfm_ctx *c, double *theta, const double *z, const dou
   return a;
 }
 
-// the residual the resident latent sweep left in slot order -> eq (only when somebody reads it: in the Gibbs loop update_e
-// follows and recomputes it)
 static void score_train(mfm_ctx *c, bool subtract_y);
 // the persistent launch did not write the residual back (e_recomputable): here it is again, e = score - y
 static void ensure_e(mfm_ctx *c) {
-  if (!c->e_lost) return;
-  c->e_lost = false;
-  score_train(c, true);
+  if (c->e_where == EWhere::Dropped) score_train(c, true);
 }
+// the residual, wherever a sweep left it -> eq in row order (only when somebody reads it: in the Gibbs loop update_e follows and
+// overwrites it). Whoever asks for it in row order may change it: the slot-order sums go with it.
 static void materialize_e(mfm_ctx *c) {
-  ensure_e(c);
-  c->slot_sums_valid = false;  // (whoever asks for the residual in row order may change it)
-  if (c->e_in_cell) {  // (the cell path's sweeps leave it in cell order; update_e, which follows in the Gibbs loop, just drops it)
-    cell_unpack_e(c->stream, c->cell, c->eq_raw());
-    c->e_in_cell = false;
+  ensure_e(c);  // (leaves it in row or in slot order)
+  switch (c->e_where) {
+    case EWhere::Cell:
+      cell_unpack_e(c->stream, c->cell, c->eq_raw());
+      break;
+    case EWhere::Slots:
+    case EWhere::SlotsWithSums: {
+      const int64_t n_slots = (int64_t)c->res.G * c->res.NT * c->res.R();
+      hipLaunchKernelGGL(k_res_unpermute, dim3((unsigned)cdiv(n_slots, 256)), dim3(256), 0, c->stream, c->res.e_slots.p, c->res.perm.p,
+                         n_slots, c->eq_raw());
+      break;
+    }
+    case EWhere::Rows:
+    case EWhere::Dropped:
+      break;
   }
-  if (!c->e_in_slots) return;
-  const int64_t n_slots = (int64_t)c->res.G * c->res.NT * c->res.R();
-  hipLaunchKernelGGL(k_res_unpermute, dim3((unsigned)cdiv(n_slots, 256)), dim3(256), 0, c->stream, c->res.e_slots.p, c->res.perm.p,
-                     n_slots, c->eq_raw());
-  c->e_in_slots = false;
+  c->e_where = EWhere::Rows;
+}
+// the cell passes take the residual in cell order and leave it there
+static void e_to_cell(mfm_ctx *c) {
+  if (c->e_where != EWhere::Cell) cell_pack_e(c->stream, c->cell, c->eq_rows());
+  c->e_where = EWhere::Cell;
 }
 
 static void score_train(mfm_ctx *c, bool subtract_y) {
-  c->e_lost = false;
   c->e_is_residual = subtract_y;
-  c->e_in_slots = false;  // (every residual is overwritten)
-  c->e_in_cell = false;
-  c->slot_sums_valid = false;
-  if (c->main_lazy) {
-    if (subtract_y && c->res.ready && res_score_supported(c->res, c->K)) {
-      hipStream_t s = c->stream;
-      {
-        TimedLaunch t(c->timing, s, KC_BUILD_VT, 16.0 * c->D * c->K);
-        build_vt(s, c->V.p, c->Vt.p, c->D, c->K, c->KS);
-      }
-      run_res_score(s, c->timing, c->res, KC_UPDATE_E, c->Vt.p, c->w.p, c->w0, c->K, c->y.p, c->X.nnz, c->w0_dev);
-      c->e_in_slots = true;
-      c->slot_sums_valid = true;
-      return;
-    }
-    c->ensure_main_plans();
+  c->e_where = EWhere::Rows;  // (every residual is overwritten)
+  hipStream_t s = c->stream;
+  // regression on a table that takes the persistent sweep: e = score - y straight in the sweep's slot order, with its sums
+  const bool in_slots = subtract_y && c->res.ready && (c->v_path == VPath::Deferred || c->two_field()) && res_score_supported(c->res, c->K);
+  if (!in_slots) c->ensure_main_plans();
+  if (in_slots || c->two_field() || c->cell.ready) {
+    TimedLaunch t(c->timing, s, KC_BUILD_VT, 16.0 * c->D * c->K);
+    build_vt(s, c->V.p, c->Vt.p, c->D, c->K, c->KS);
   }
-  if (c->mf) {
+  if (in_slots) {
+    run_res_score(s, c->timing, c->res, KC_UPDATE_E, c->Vt.p, c->w.p, c->w0, c->K, c->y.p, c->X.nnz, c->w0_dev);
+    c->e_where = EWhere::SlotsWithSums;
+    return;
+  }
+  if (c->two_field()) {
     // two-field table: scorer on the row tiles of the latent sweep (item rows gathered once per run, not once per row)
-    hipStream_t s = c->stream;
-    {
-      TimedLaunch t(c->timing, s, KC_BUILD_VT, 16.0 * c->D * c->K);
-      build_vt(s, c->V.p, c->Vt.p, c->D, c->K, c->KS);
-    }
-    // regression on a table that takes the persistent sweep: e = score - y straight in the sweep's slot order, with its sums
-    if (subtract_y && c->res.ready && res_score_supported(c->res, c->K)) {
-      run_res_score(s, c->timing, c->res, KC_UPDATE_E, c->Vt.p, c->w.p, c->w0, c->K, c->y.p, c->X.nnz, c->w0_dev);
-      c->e_in_slots = true;
-      c->slot_sums_valid = true;
-      return;
-    }
     TimedLaunch t(c->timing, s, KC_UPDATE_E, 12.0 * c->X.nnz + 16.0 * c->X.rows + 8.0 * c->D * (c->K + 1));
     SweepArgs a = main_args(c, c->w.p, nullptr, nullptr, nullptr, 0.0);
     const bool done = c->X.unit ? launch_mf_score<true>(s, c->plan_V, a, c->Vt.p, c->w.p, c->w0, c->K, c->KS,
@@ -636,11 +642,6 @@ static void score_train(mfm_ctx *c, bool subtract_y) {
   }
   if (c->cell.ready) {
     // index-tuple design: K / FB passes over (accumulator, index record) with the factor tables in LDS (mfm_cell.hpp)
-    hipStream_t s = c->stream;
-    {
-      TimedLaunch t(c->timing, s, KC_BUILD_VT, 16.0 * c->D * c->K);
-      build_vt(s, c->V.p, c->Vt.p, c->D, c->K, c->KS);
-    }
     std::vector<CellScoreSrc> src(c->cell.fields.size());
     for (size_t k = 0; k < c->cell.fields.size(); k++) {
       const CellField &fd = c->cell.fields[k];
@@ -669,8 +670,7 @@ static void run_sweep_cell(mfm_ctx *c, int f_begin, int f_end, const double *zba
   CellPlan &cp = c->cell;
   Timing &tm = c->timing;
   const int m = (int)cp.fields.size();
-  if (!c->e_in_cell) cell_pack_e(s, cp, c->eq_raw());
-  c->e_in_cell = true;  // (stays in cell order: materialize_e brings it back when somebody reads eq)
+  e_to_cell(c);  // (stays in cell order: materialize_e brings it back when somebody reads eq)
   std::vector<CellSrc> cur((size_t)m);
   cp.touch_all();  // (whatever cell_prep built in an earlier call is stale)
   auto set_cur = [&](int f) {
@@ -760,14 +760,13 @@ static void run_sweep_w_cell(mfm_ctx *c, const double *zdev, double alpha) {
   const int m = (int)cp.fields.size();
   const bool sh = c->comm.active();
   if (!cp.cnt_ready) {
-    if (c->e_in_cell) materialize_e(c);  // (cell.e is the scratch of the one-off row count)
+    materialize_e(c);  // (cell.e is the scratch of the one-off row count)
     cell_counts(s, tm, cp);
     if (sh)  // (a column's rows on all ranks)
       for (int k = 0; k < m; k++)
         if (cp.fields[k].kind == 0) c->comm.allreduce(cp.cnt[k].p, cp.fields[k].n);
   }
-  if (!c->e_in_cell) cell_pack_e(s, cp, c->eq_raw());
-  c->e_in_cell = true;
+  e_to_cell(c);
   const SweepClasses kc{KC_BLOCK_SWEEP, KC_BLOCK_SWEEP, KC_BLOCK_SWEEP, KC_BLOCK_SWEEP, KC_BLOCK_SWEEP, KC_BLOCK_SWEEP,
                         KC_BLOCK_SWEEP, KC_BLOCK_SWEEP};
   for (int k = 0; k < m; k++) {
@@ -1110,7 +1109,7 @@ static void try_resident_first(mfm_ctx *c, const std::function<void(const char *
   plan_resident(c, [&](ResPlan &rp, int n_cu) { res_plan_build_device(rp, c->X, &c->hgroup, n_cu, c->stream); }, tlog);
   lap("resident plan (device)");
   // (tests: with MFM_PLAN_CHECK everything else is built too and the host builder's layout compared)
-  c->main_lazy = c->res.ready && !env_flag("MFM_PLAN_CHECK");
+  if (c->res.ready && !env_flag("MFM_PLAN_CHECK")) c->v_path = VPath::Deferred;
 }
 
 // The main table's generic structures: X_t (device transpose, copied back for the planner), the level plans of both sweeps, the
@@ -1200,8 +1199,7 @@ static void plan_main_table(mfm_ctx *c, HostCsr &Xt, const std::function<void(co
         c->plan_V.group_of = &c->hgroup;
         c->plan_V.dev_csc = c->plan_W.dev_csc;
         c->plan_V.build(Xt, PMainV::R_W16, PMainV::R_WG, coop_v, true, c->X.unit);
-      } else {
-        c->sharded_fused = true;
+      } else {  // (plan_V.sharded_tiles stays set: decide_main_paths takes one of the Sharded forms)
         // model synchronisation after the sweep: a non-special first-level column is contributed by the rank
         // that holds its rows, every other column (identical on all ranks) by rank 0 of the communicator
         // (a caller of the older sequence mfm_set_allreduce + mfm_set_row_offset never said which rank it is: the shard
@@ -1224,36 +1222,34 @@ static void plan_main_table(mfm_ctx *c, HostCsr &Xt, const std::function<void(co
     }
 }
 
-// which of the main table's sweep forms the plans support (flags of mfm_plan_flags) and their buffers
-static void decide_main_paths(mfm_ctx *c) {
+// which of update_V's forms the main table's plans support, and its buffers
+static VPath decide_main_paths(mfm_ctx *c) {
+  const bool one_gpu_no_blocks = !c->comm.active() && c->blocks.empty();
   // q-free latent sweep (PMainVe), opt-in (MFM_QFREE=1): pays off when the levels' rows are contiguous; needs
   // short rows, no relation blocks, no sharding, single-pass PAR levels, no row-tile levels
-  c->qfree = !c->comm.active() && c->blocks.empty() && c->X.rows > 0 && c->X.avg_row_nnz <= 4.0 &&
-             plan_is_single_pass_par(c->plan_V) && env_int("MFM_QFREE", 0);
-  if (c->qfree) c->ec.alloc((size_t)c->N);
+  if (one_gpu_no_blocks && c->X.rows > 0 && c->X.avg_row_nnz <= 4.0 && plan_is_single_pass_par(c->plan_V) && env_int("MFM_QFREE", 0)) {
+    c->ec.alloc((size_t)c->N);
+    return VPath::QFree;
+  }
+  const bool sharded = c->plan_V.sharded_tiles;  // row-sharded + fused tile path: the ranks agreed on it in plan_main_table
   // split e / q layout for update_V (run_plan_soa)
-  c->soa = !c->qfree && !c->comm.active() && c->blocks.empty() && c->N > 0 && plan_supports_soa(c->plan_V);
-  if (c->sharded_fused) {
-    c->ec.alloc((size_t)c->N);
-    c->qc.alloc((size_t)c->N);
+  const bool split = one_gpu_no_blocks && c->N > 0 && plan_supports_soa(c->plan_V);
+  if (!sharded && !split) return c->cell.ready ? VPath::Cell : VPath::Generic;
+  c->ec.alloc((size_t)c->N);
+  c->qc.alloc((size_t)c->N);
+  if (sharded) {
     // no first-level column straddles a rank boundary (and none is longer than ... any length is fine): the two-field pass
-    c->mf = plan_supports_mf(c->plan_V) && c->plan_V.n_special == 0 && !env_flag("MFM_NO_MF");
-    {  // every rank must take the same path
-      double no = c->mf ? 0.0 : 1.0;
-      DevBuf<double> d;
-      d.upload(&no, 1);
-      c->comm.allreduce(d.p, 1);
-      MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-      MFM_HIP_CHECK(hipMemcpy(&no, d.p, sizeof(double), hipMemcpyDeviceToHost));
-      c->mf = no == 0.0;
-    }
+    double no = plan_supports_mf(c->plan_V) && c->plan_V.n_special == 0 && !env_flag("MFM_NO_MF") ? 0.0 : 1.0;
+    // every rank must take the same path
+    DevBuf<double> d;
+    d.upload(&no, 1);
+    c->comm.allreduce(d.p, 1);
+    MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    MFM_HIP_CHECK(hipMemcpy(&no, d.p, sizeof(double), hipMemcpyDeviceToHost));
+    return no == 0.0 ? VPath::ShardedTwoField : VPath::ShardedSplit;
   }
-  if (c->soa) {
-    c->ec.alloc((size_t)c->N);
-    c->qc.alloc((size_t)c->N);
-    c->fuse_next = plan_supports_fused_next(c->plan_V) && !env_flag("MFM_NO_FUSED_NEXT");
-    c->mf = c->fuse_next && plan_supports_mf(c->plan_V) && !env_flag("MFM_NO_MF");
-  }
+  if (!plan_supports_fused_next(c->plan_V) || env_flag("MFM_NO_FUSED_NEXT")) return VPath::Split;
+  return plan_supports_mf(c->plan_V) && !env_flag("MFM_NO_MF") ? VPath::TwoField : VPath::SplitFused;
 }
 
 // The jump polynomials of the parallel MT19937 generator for a problem of D features, rank K, G groups, sized for one iteration's
@@ -1281,13 +1277,12 @@ int mfm_rng_prepare(int64_t n_features, int32_t rank, int32_t n_groups) {
 }
 
 void mfm_ctx::ensure_main_plans() {
-  if (!main_lazy) return;
-  main_lazy = false;
+  if (v_path != VPath::Deferred) return;
   use_device();
   HostCsr Xt;
   plan_main_table(this, Xt, [](const char *) {});
   ls.reserve(std::max({plan_V.max_hchunks, plan_W.max_hchunks, 1}), std::max({plan_V.max_huge, plan_W.max_huge, 1}));
-  decide_main_paths(this);
+  v_path = decide_main_paths(this);
 }
 
 int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
@@ -1420,7 +1415,7 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
     // fall-back, and what a stand-alone mfm_sweep_w runs) are built only if a call ever needs them (ensure_main_plans):
     // config 3 0.26 s of mfm_finalize -> 0.1 s.
     if (!c->cell.ready) try_resident_first(c, lap);
-    const bool lean = c->cell_w || c->main_lazy;
+    const bool lean = c->cell_w || c->v_path == VPath::Deferred;
     if (!lean) plan_main_table(c, Xt, lap);
   }
   c->eq_.alloc_zero((size_t)c->N, c->stream);
@@ -1496,28 +1491,28 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
   c->red_partial.alloc(REDUCE_BLOCKS);
   c->red_out.alloc((size_t)1 + (size_t)c->G * std::max(c->K, 1));
   c->scratch_n.alloc((size_t)std::max<int64_t>(c->N, 1));
-  decide_main_paths(c);
+  if (c->v_path != VPath::Deferred) c->v_path = decide_main_paths(c);
   // two-field unit-valued table on one GPU: the whole update_V as one persistent launch, residual resident on chip
   // (small tables stay with the per-factor passes: the launch's fixed costs -- two grid barriers per sweep, census, slot-ordered
   //  residual -- outweigh the bytes it saves; ML-100k shape: fit() 3060 it/s resident, 3950 per-factor. MFM_RES_MIN_ROWS)
   if (c->res.ready) {
     // (built first, on the device) tests: the host builder on X_t must give the same layout, array for array
-    if (!c->main_lazy && env_flag("MFM_PLAN_CHECK")) {
+    if (c->v_path != VPath::Deferred && env_flag("MFM_PLAN_CHECK")) {
       ResPlan chk;
       chk.build(Xt_keep, c->plan_V.h_level, &c->hgroup, c->res_plan_cus);
       const std::string diff = chk.ready ? res_plan_compare(c->res, chk, c->stream) : ("host builder: " + chk.why);
       if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host resident layouts differ (" + diff + ")");
       lap("resident plan (host, check)");
     }
-  } else if (!c->res_refused && c->soa && c->mf && c->X.unit && !c->comm.active() && c->N >= res_min_rows(c) && !env_flag("MFM_NO_RESIDENT")) {
+  } else if (!c->res_refused && c->v_path == VPath::TwoField && c->X.unit && c->N >= res_min_rows(c) && !env_flag("MFM_NO_RESIDENT")) {
     plan_resident(c, [&](ResPlan &rp, int n_cu) { rp.build(Xt_keep, c->plan_V.h_level, &c->hgroup, n_cu); }, tlog);
     lap("resident plan (host)");
   }
-  // Row-sharded with the shards cut between users (the two-field pass runs sharded, c->mf): the persistent sweep runs on every rank
+  // Row-sharded with the shards cut between users (VPath::ShardedTwoField): the persistent sweep runs on every rank
   // over its own rows, the ranks' item sums meet inside the launch (mfm_res.hpp, XCH). The layout is built here -- items = the
   // level-1 columns of the GLOBAL design, so every rank numbers them alike -- and goes live when the caller has handed over the
   // peers' exchange buffers (mfm_peer_set); until then, and if any rank cannot take part, the per-factor passes run.
-  if (c->comm.active() && c->sharded_fused && c->mf && c->comm.shard_set && c->comm.world <= RES_MAX_PEERS && c->comm.world > 1 &&
+  if (c->v_path == VPath::ShardedTwoField && c->comm.shard_set && c->comm.world <= RES_MAX_PEERS && c->comm.world > 1 &&
       !env_flag("MFM_NO_RESIDENT") && !env_flag("MFM_NO_SHARDED_RESIDENT")) {
     const int64_t min_rows = res_min_rows(c);
     const bool want = c->X.unit && c->X.ell_width == 2 && c->N >= std::max<int64_t>(1, min_rows / c->comm.world) && c->K > 0;
@@ -1718,7 +1713,7 @@ int mfm_set_residual_policy(mfm_ctx *ctx, int32_t recomputable) {
 int64_t mfm_dim_all(const mfm_ctx *ctx) { return ctx->D; }
 
 int mfm_plan_info(const mfm_ctx *ctx, int64_t *n_levels_main, int64_t *n_launches_per_sweep) {
-  if (ctx->main_lazy) {  // (a two-field table on the persistent sweep: what its per-factor fall-back would be)
+  if (ctx->v_path == VPath::Deferred) {  // (a two-field table on the persistent sweep: what its per-factor fall-back would be)
     if (n_levels_main) *n_levels_main = 2;
     if (n_launches_per_sweep) *n_launches_per_sweep = 1;
     return MFM_OK;
@@ -1736,9 +1731,21 @@ int mfm_plan_flags(const mfm_ctx *ctx) {
   bool streamed = false;  // a relation block's feature chain runs as the streamed one-launch form (mfm_chain_stream.hpp)
   for (auto &B : ctx->blocks)
     for (const Step &st : B->plan_V.steps) streamed = streamed || (st.is_chain && st.chain.stream);
-  return (streamed ? 1024 : 0) | (ctx->res.ready && ctx->res.RX > 0 ? 2048 : 0) | (ctx->qfree ? 1 : 0) | (ctx->X.unit ? 2 : 0) | (ctx->X.ell_width >= 0 ? 4 : 0) | (ctx->comm.active() ? 8 : 0) |
-         (ctx->soa ? 16 : 0) | (ctx->fuse_next ? 32 : 0) | (ctx->sharded_fused ? 64 : 0) | (ctx->mf ? 128 : 0) |
-         (ctx->res.ready ? 256 : 0) | (ctx->cell.ready ? 512 : 0);
+  int form = 0;  // bits 0 and 4-7 (include/myfm_hip.h): what each form of update_V has always reported
+  switch (ctx->v_path) {
+    case VPath::QFree: form = 1; break;
+    case VPath::Split: form = 16; break;
+    case VPath::SplitFused: form = 16 | 32; break;
+    case VPath::TwoField: form = 16 | 32 | 128; break;
+    case VPath::ShardedSplit: form = 64; break;
+    case VPath::ShardedTwoField: form = 64 | 128; break;
+    case VPath::Deferred:
+    case VPath::Generic:
+    case VPath::Cell:
+      break;
+  }
+  return (streamed ? 1024 : 0) | (ctx->res.ready && ctx->res.RX > 0 ? 2048 : 0) | form | (ctx->X.unit ? 2 : 0) | (ctx->X.ell_width >= 0 ? 4 : 0) |
+         (ctx->comm.active() ? 8 : 0) | (ctx->res.ready ? 256 : 0) | (ctx->cell.ready ? 512 : 0);
 }
 
 // ---- state ------------------------------------------------------------------------------------
@@ -1768,7 +1775,7 @@ int mfm_set_w0(mfm_ctx *ctx, double w0) {
   MFM_TRY(ctx)
   // a residual the sweep dropped is recomputed from the model AND this intercept: materialise it first with the intercept it
   // belongs to (a following mfm_shift_e would otherwise count the change twice)
-  if (ctx->e_lost && w0 != ctx->w0) ensure_e(ctx);
+  if (w0 != ctx->w0) ensure_e(ctx);
   ctx->w0 = w0;
   MFM_CATCH(ctx)
 }
@@ -1815,7 +1822,7 @@ int mfm_get_q(mfm_ctx *ctx, double *q) {
 int mfm_set_e(mfm_ctx *ctx, const double *e) {
   MFM_TRY(ctx)
   ctx->need_final();
-  ctx->e_lost = false;  // (every residual is overwritten)
+  if (ctx->e_where == EWhere::Dropped) ctx->e_where = EWhere::Rows;  // (every residual is overwritten: nothing to recompute)
   ctx->e_is_residual = false;  // (the caller's own numbers: never dropped and recomputed)
   materialize_e(ctx);
   if (ctx->N) {
@@ -1910,7 +1917,7 @@ int mfm_hyper_stats(mfm_ctx *ctx, int32_t need_e, const double *mu_w, const doub
   mfm_ctx *c = ctx;
   // the slot-order scorer has left sum e / sum e^2 as one partial per workgroup: no pass over the residual, which stays in
   // slot order for the next persistent launch
-  const bool slot_sums = need_e && c->e_in_slots && c->slot_sums_valid;
+  const bool slot_sums = need_e && c->e_where == EWhere::SlotsWithSums;
   if (need_e && !slot_sums) materialize_e(ctx);
   hipStream_t s = c->stream;
   const int G = c->G, K = c->K, n_ch = std::max(1, c->gs_chunks);
@@ -1985,6 +1992,26 @@ static void sync_model_sharded(mfm_ctx *c, bool with_w, int f_begin, int f_end) 
   }
 }
 
+// The persistent launch: update_V of factors [f_begin, f_end) (zbase: the variates of factor f_begin), with lin.w set also
+// update_w0's residual shift and update_w in front of it (mfm_res.hpp). hyp: alpha and e_shift are read from the device instead.
+struct ResidentLinear {
+  double *w = nullptr;
+  const double *zw = nullptr, *lam_w = nullptr, *mu_w = nullptr;
+  double e_shift = 0.0;
+};
+static void launch_resident(mfm_ctx *c, int f_begin, int f_end, const double *zbase, const double *lam, const double *mu, double alpha,
+                            const ResidentLinear &lin = ResidentLinear(), const double *hyp = nullptr) {
+  ensure_e(c);
+  const mfm_ctx::ResidentE e = c->e_for_resident(lin.w != nullptr, f_begin, f_end);
+  run_sweep_resident(c->stream, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, lam, mu,
+                     c->group.p, c->G, alpha, c->ls.error.p, lin.w, lin.zw, lin.lam_w, lin.mu_w, lin.e_shift, e.load_slots, e.no_store,
+                     hyp);
+  c->e_left_by_resident(e);
+  c->q_stale_factor = f_end - 1;  // q_train as the reference leaves it (FMTrainer.hpp:373): rebuilt when asked for
+  // row-sharded: a first-level coefficient was drawn where its rows live
+  if (c->comm.active() && !c->res.peers_model) sync_model_sharded(c, lin.w != nullptr, f_begin, f_end);
+}
+
 // ---- sweeps -----------------------------------------------------------------------------------
 int mfm_sweep_w(mfm_ctx *ctx, double alpha, const double *lambda_w, const double *mu_w, const double *z) {
   MFM_TRY(ctx)
@@ -2042,9 +2069,6 @@ int mfm_sweep_wV(mfm_ctx *ctx, double alpha, double e_shift, const double *lambd
   if ((zw == nullptr) != (zv == nullptr)) throw Error(MFM_ERR_INVALID, "mfm_sweep_wV: give both variate arrays or none");
   if (!zw && (c->rng.current < 0 || c->rng.n_zw != c->D || c->rng.n_zv != c->D * (int64_t)c->K))
     throw Error(MFM_ERR_RUNTIME, "mfm_sweep_wV(z = NULL) needs an acquired device random set with D + K*D variates");
-  ensure_e(c);
-  const bool load_slots = c->e_in_slots;  // the residual is already in the launch's slot order: read it there
-  c->slot_sums_valid = false;
   hipStream_t s = c->stream;
   // the four hyper-parameter vectors in ONE copy: [lambda_w | mu_w | lambda_V | mu_V]
   const size_t nG = (size_t)c->G, nGK = (size_t)c->G * c->K;
@@ -2068,14 +2092,7 @@ int mfm_sweep_wV(mfm_ctx *ctx, double alpha, double e_shift, const double *lambd
     zwdev = c->rng.slot[c->rng.current].zw.p;
     zbase = c->rng.slot[c->rng.current].zv.p + (size_t)f_begin * c->D;
   }
-  // (regression, all factors swept: update_e follows and recomputes the residual -- the launch's copy would be a dead store, 64 us)
-  const bool no_store = c->e_recomputable && c->e_is_residual && f_begin == 0 && f_end == c->K;
-  run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, d_lam, d_mu,
-                     c->group.p, c->G, alpha, c->ls.error.p, c->w.p, zwdev, d_lam_w, d_mu_w, e_shift, load_slots, no_store);
-  c->e_in_slots = !no_store;
-  c->e_lost = no_store;
-  c->q_stale_factor = f_end - 1;
-  if (c->comm.active() && !c->res.peers_model) sync_model_sharded(c, true, f_begin, f_end);
+  launch_resident(c, f_begin, f_end, zbase, d_lam, d_mu, alpha, {c->w.p, zwdev, d_lam_w, d_mu_w, e_shift});
   MFM_CATCH(ctx)
 }
 
@@ -2083,7 +2100,7 @@ int mfm_sweep_wV(mfm_ctx *ctx, double alpha, double e_shift, const double *lambd
 static bool regression_iteration_ready(mfm_ctx *c) {
   if (!c || !c->finalized || !c->res.ready || c->comm.active() || c->K <= 0 || c->D <= 0) return false;
   if (!res_score_supported(c->res, c->K)) return false;
-  if (!(c->e_in_slots && c->slot_sums_valid && c->e_is_residual && !c->e_lost)) return false;  // (update_e's slot-order sums)
+  if (!(c->e_where == EWhere::SlotsWithSums && c->e_is_residual)) return false;  // (update_e's slot-order sums)
   const auto &r = c->rng;
   if (!r.programmed || r.produced <= r.acquired || r.n_zw != c->D || r.n_zv != c->D * (int64_t)c->K) return false;
   return true;
@@ -2170,15 +2187,8 @@ int mfm_regression_iteration(mfm_ctx *ctx, const mfm_hyper_prior *prior, const d
   MFM_HIP_CHECK(hipEventRecord(c->hyp_ev, s));
   // 6. update_w0's shift + update_w + update_V: the persistent launch with alpha / e_shift read from c->hyp
   {
-    const bool load_slots = c->e_in_slots;
-    c->slot_sums_valid = false;
     const double *d_lam_w = c->hyp.p + 4, *d_mu_w = d_lam_w + nG, *d_lam = d_mu_w + nG, *d_mu = d_lam + nGK;
-    const bool no_store = c->e_recomputable && c->e_is_residual;
-    run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, 0, K, sl.zv.p, d_lam, d_mu, c->group.p,
-                       c->G, 0.0, c->ls.error.p, c->w.p, sl.zw.p, d_lam_w, d_mu_w, 0.0, load_slots, no_store, c->hyp.p);
-    c->e_in_slots = !no_store;
-    c->e_lost = no_store;
-    c->q_stale_factor = K - 1;
+    launch_resident(c, 0, K, sl.zv.p, d_lam, d_mu, 0.0, {c->w.p, sl.zw.p, d_lam_w, d_mu_w, 0.0}, c->hyp.p);
   }
   // 7. the set after the next (gated behind the launch), 8. update_e with the intercept the device has drawn
   {
@@ -2211,152 +2221,11 @@ int mfm_regression_iteration(mfm_ctx *ctx, const mfm_hyper_prior *prior, const d
   MFM_CATCH(ctx)
 }
 
-int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, const double *lambda_V, const double *mu_V,
-                const double *z) {
-  MFM_TRY(ctx)
-  ctx->need_final();
-  if (!ctx->cell.ready) materialize_e(ctx);
-  mfm_ctx *c = ctx;
-  if (f_begin < 0 || f_end > c->K || f_begin > f_end) throw Error(MFM_ERR_INVALID, "factor range out of bounds");
-  if (f_begin == f_end) return MFM_OK;
+// update_V (FMTrainer.hpp:315-482) with the q-cache in HBM: per factor the q-cache build, the main table's level plan, the blocks
+static void sweep_V_generic(mfm_ctx *c, int f_begin, int f_end, const double *zbase, double alpha, const SweepClasses &kcv) {
   hipStream_t s = c->stream;
-  c->ring.upload(c->lam.p, lambda_V, (size_t)c->G * c->K * sizeof(double), s);
-  c->ring.upload(c->mu.p, mu_V, (size_t)c->G * c->K * sizeof(double), s);
-  const double *zbase = c->z.p;
-  if (z) {
-    c->ring.upload(c->z.p, z, (size_t)c->D * (f_end - f_begin) * sizeof(double), s);
-  } else {
-    if (c->rng.current < 0 || c->rng.n_zv != c->D * (int64_t)c->K)
-      throw Error(MFM_ERR_RUNTIME, "mfm_sweep_V(z = NULL) needs an acquired device random set with K*D z_V variates");
-    zbase = c->rng.slot[c->rng.current].zv.p + (size_t)f_begin * c->D;
-  }
-  if (c->main_lazy) {
-    if (c->res.ready) {
-      run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, c->lam.p, c->mu.p,
-                         c->group.p, c->G, alpha, c->ls.error.p);
-      c->e_in_slots = true;
-      c->q_stale_factor = f_end - 1;
-      return MFM_OK;
-    }
-    c->ensure_main_plans();
-  }
   // the first level rebuilds q from the CSR rows itself when it touches every row exactly once
   const bool first_q = !c->comm.active() && c->blocks.empty() && plan_first_level_builds_q(c->plan_V);
-  if (c->qfree) {
-    // compact e for the duration of the factor loop; q is never materialised inside it
-    hipLaunchKernelGGL(k_e_pack, dim3(cdiv(c->N, 256)), dim3(256), 0, s, c->eq_rows(), c->ec.p, c->N);
-    const SweepClasses kcv{KC_SWEEP_V_LIGHT, KC_SWEEP_V_HEAVY, KC_SWEEP_V_COOP, KC_SWEEP_V_LSTATS, KC_SWEEP_V_LDRAW,
-                           KC_SWEEP_V_LAPPLY, KC_SWEEP_V_CHAIN, KC_SWEEP_V_SCAT};
-    for (int f = f_begin; f < f_end; f++) {
-      double *Vf = c->V.p + (size_t)f * c->D;
-      SweepArgs a = main_args(c, Vf, zbase + (size_t)(f - f_begin) * c->D, c->lam.p + (size_t)f * c->G,
-                              c->mu.p + (size_t)f * c->G, alpha);
-      a.state = c->ec.p;
-      a.r_rowptr = c->X.rowptr.p;
-      a.r_colidx = c->X.colidx.p;
-      a.r_val = c->X.rval.p;
-      a.r_ell = (int)c->X.ell_width;
-      run_plan_qfree(s, c->timing, c->plan_V, a, c->ls, kcv, c->X.unit);
-    }
-    hipLaunchKernelGGL(k_e_unpack, dim3(cdiv(c->N, 256)), dim3(256), 0, s, c->eq_rows(), c->ec.p, c->N);
-    c->q_stale_factor = f_end - 1;  // q_train as the reference leaves it (FMTrainer.hpp:373): rebuilt when asked for
-    MFM_HIP_CHECK(hipGetLastError());
-    return MFM_OK;
-  }
-  if (c->sharded_fused && c->res.ready) {  // (row-sharded persistent sweep: the peers' buffers are set)
-    run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, c->lam.p, c->mu.p,
-                       c->group.p, c->G, alpha, c->ls.error.p);
-    c->e_in_slots = true;
-    c->q_stale_factor = f_end - 1;
-    if (!c->res.peers_model) sync_model_sharded(c, false, f_begin, f_end);
-    return MFM_OK;
-  }
-  if (c->sharded_fused) {
-    // (no pack / unpack passes: the first level reads e from the interleaved array, the final apply pass writes it back)
-    const SweepClasses kcv{KC_SWEEP_V_LIGHT, KC_SWEEP_V_HEAVY, KC_SWEEP_V_COOP, KC_SWEEP_V_LSTATS, KC_SWEEP_V_LDRAW,
-                           KC_SWEEP_V_LAPPLY, KC_SWEEP_V_CHAIN, KC_SWEEP_V_SCAT};
-    auto args = [&](int f) {
-      SweepArgs a = main_args(c, c->V.p + (size_t)f * c->D, zbase + (size_t)(f - f_begin) * c->D,
-                              c->lam.p + (size_t)f * c->G, c->mu.p + (size_t)f * c->G, alpha);
-      a.state = c->ec.p;
-      a.state2 = c->qc.p;
-      a.aos = c->eq_rows();
-      a.r_rowptr = c->X.rowptr.p;
-      a.r_colidx = c->X.colidx.p;
-      a.r_val = c->X.rval.p;
-      a.r_ell = (int)c->X.ell_width;
-      return a;
-    };
-    if (c->mf) {
-      if (c->X.unit)
-        run_sweep_mf<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, &c->comm);
-      else
-        run_sweep_mf<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, &c->comm);
-    } else if (c->plan_V.steps.size() > 2) {
-      if (c->X.unit)
-        run_sweep_soa_multi<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, &c->comm);
-      else
-        run_sweep_soa_multi<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, &c->comm);
-    } else if (c->X.unit) {
-      run_sweep_soa_sharded<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, c->comm);
-    } else {
-      run_sweep_soa_sharded<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, c->comm);
-    }
-    // make the first-level coefficients identical on every rank again (each was drawn where its rows live)
-    {
-      const int64_t n = (int64_t)(f_end - f_begin) * c->D;
-      double *Vb = c->V.p + (size_t)f_begin * c->D;
-      hipLaunchKernelGGL(k_mask_rows, dim3(cdiv(n, 256)), dim3(256), 0, s, Vb, c->sync_mask.p, c->D, n);
-      c->comm.allreduce(Vb, n);
-    }
-    c->q_stale_factor = f_end - 1;  // q_train as the reference leaves it (FMTrainer.hpp:373): rebuilt when asked for
-    MFM_HIP_CHECK(hipGetLastError());
-    return MFM_OK;
-  }
-  if (c->soa) {
-    // (no pack pass: the first level reads e from the interleaved array; no unpack pass when the last level runs on
-    // row tiles: its final apply pass writes e back there)
-    const SweepClasses kcv{KC_SWEEP_V_LIGHT, KC_SWEEP_V_HEAVY, KC_SWEEP_V_COOP, KC_SWEEP_V_LSTATS, KC_SWEEP_V_LDRAW,
-                           KC_SWEEP_V_LAPPLY, KC_SWEEP_V_CHAIN, KC_SWEEP_V_SCAT};
-    auto args = [&](int f) {
-      SweepArgs a = main_args(c, c->V.p + (size_t)f * c->D, zbase + (size_t)(f - f_begin) * c->D,
-                              c->lam.p + (size_t)f * c->G, c->mu.p + (size_t)f * c->G, alpha);
-      a.state = c->ec.p;
-      a.state2 = c->qc.p;
-      a.aos = c->eq_rows();
-      a.r_rowptr = c->X.rowptr.p;
-      a.r_colidx = c->X.colidx.p;
-      a.r_val = c->X.rval.p;
-      a.r_ell = (int)c->X.ell_width;
-      return a;
-    };
-    const bool fuse = c->fuse_next;
-    if (c->res.ready) {
-      run_sweep_resident(s, c->timing, c->res, KC_SWEEP_V_RESIDENT, c->eq_raw(), c->V.p, c->D, f_begin, f_end, zbase, c->lam.p, c->mu.p,
-                         c->group.p, c->G, alpha, c->ls.error.p);
-      c->e_in_slots = true;
-      c->q_stale_factor = f_end - 1;
-      return MFM_OK;
-    }
-    if (c->mf) {
-      if (c->X.unit)
-        run_sweep_mf<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv);
-      else
-        run_sweep_mf<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv);
-    } else if (c->X.unit)
-      run_sweep_soa<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, fuse);
-    else
-      run_sweep_soa<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, fuse);
-    if (!c->plan_V.steps.back().par.tiled)
-      hipLaunchKernelGGL(k_e_unpack, dim3(cdiv(c->N, 256)), dim3(256), 0, s, c->eq_rows(), c->ec.p, c->N);
-    c->q_stale_factor = f_end - 1;  // q_train as the reference leaves it (FMTrainer.hpp:373): rebuilt when asked for
-    MFM_HIP_CHECK(hipGetLastError());
-    return MFM_OK;
-  }
-  if (c->cell.ready) {
-    run_sweep_cell(c, f_begin, f_end, zbase, alpha);
-    return MFM_OK;
-  }
   DevBlock *carry = nullptr;  // last block of the previous factor, re-sync still owed
   for (int f = f_begin; f < f_end; f++) {
     double *Vf = c->V.p + (size_t)f * c->D;
@@ -2377,8 +2246,6 @@ int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, cons
       a.r_val = c->X.rval.p;
       a.r_ell = (int)c->X.ell_width;
     }
-    const SweepClasses kcv{KC_SWEEP_V_LIGHT, KC_SWEEP_V_HEAVY, KC_SWEEP_V_COOP, KC_SWEEP_V_LSTATS, KC_SWEEP_V_LDRAW,
-                           KC_SWEEP_V_LAPPLY, KC_SWEEP_V_CHAIN, KC_SWEEP_V_SCAT};
     if (c->comm.active())
       run_plan_sharded<PMainV>(s, c->timing, c->plan_V, a, c->ls, kcv, c->X.unit, c->comm);
     else
@@ -2397,6 +2264,106 @@ int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, cons
     }
     carry = pending;
   }
+}
+
+int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, const double *lambda_V, const double *mu_V,
+                const double *z) {
+  MFM_TRY(ctx)
+  ctx->need_final();
+  if (!ctx->cell.ready) materialize_e(ctx);
+  mfm_ctx *c = ctx;
+  if (f_begin < 0 || f_end > c->K || f_begin > f_end) throw Error(MFM_ERR_INVALID, "factor range out of bounds");
+  if (f_begin == f_end) return MFM_OK;
+  hipStream_t s = c->stream;
+  c->ring.upload(c->lam.p, lambda_V, (size_t)c->G * c->K * sizeof(double), s);
+  c->ring.upload(c->mu.p, mu_V, (size_t)c->G * c->K * sizeof(double), s);
+  const double *zbase = c->z.p;
+  if (z) {
+    c->ring.upload(c->z.p, z, (size_t)c->D * (f_end - f_begin) * sizeof(double), s);
+  } else {
+    if (c->rng.current < 0 || c->rng.n_zv != c->D * (int64_t)c->K)
+      throw Error(MFM_ERR_RUNTIME, "mfm_sweep_V(z = NULL) needs an acquired device random set with K*D z_V variates");
+    zbase = c->rng.slot[c->rng.current].zv.p + (size_t)f_begin * c->D;
+  }
+  if (c->v_path == VPath::Deferred && !c->res.ready) c->ensure_main_plans();
+  if (c->resident_V()) {  // (row-sharded: the peers' buffers are set)
+    launch_resident(c, f_begin, f_end, zbase, c->lam.p, c->mu.p, alpha);
+    return MFM_OK;
+  }
+  const SweepClasses kcv{KC_SWEEP_V_LIGHT, KC_SWEEP_V_HEAVY, KC_SWEEP_V_COOP, KC_SWEEP_V_LSTATS, KC_SWEEP_V_LDRAW,
+                         KC_SWEEP_V_LAPPLY, KC_SWEEP_V_CHAIN, KC_SWEEP_V_SCAT};
+  // the forms without a q-cache read the CSR rows; state = compact e, and in the split layout state2 = q, aos = the interleaved array
+  auto args = [&](int f) {
+    SweepArgs a = main_args(c, c->V.p + (size_t)f * c->D, zbase + (size_t)(f - f_begin) * c->D, c->lam.p + (size_t)f * c->G,
+                            c->mu.p + (size_t)f * c->G, alpha);
+    a.r_rowptr = c->X.rowptr.p;
+    a.r_colidx = c->X.colidx.p;
+    a.r_val = c->X.rval.p;
+    a.r_ell = (int)c->X.ell_width;
+    a.state = c->ec.p;
+    if (c->v_path != VPath::QFree) {
+      a.state2 = c->qc.p;
+      a.aos = c->eq_rows();
+    }
+    return a;
+  };
+  const bool unit = c->X.unit;
+  switch (c->v_path) {
+    case VPath::QFree:
+      // compact e for the duration of the factor loop; q is never materialised inside it
+      hipLaunchKernelGGL(k_e_pack, dim3(cdiv(c->N, 256)), dim3(256), 0, s, c->eq_rows(), c->ec.p, c->N);
+      for (int f = f_begin; f < f_end; f++) run_plan_qfree(s, c->timing, c->plan_V, args(f), c->ls, kcv, unit);
+      hipLaunchKernelGGL(k_e_unpack, dim3(cdiv(c->N, 256)), dim3(256), 0, s, c->eq_rows(), c->ec.p, c->N);
+      break;
+    case VPath::ShardedTwoField:
+    case VPath::ShardedSplit: {
+      // (no pack / unpack passes: the first level reads e from the interleaved array, the final apply pass writes it back)
+      if (c->v_path == VPath::ShardedTwoField) {
+        if (unit)
+          run_sweep_mf<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, &c->comm);
+        else
+          run_sweep_mf<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, &c->comm);
+      } else if (c->plan_V.steps.size() > 2) {
+        if (unit)
+          run_sweep_soa_multi<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, &c->comm);
+        else
+          run_sweep_soa_multi<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, &c->comm);
+      } else if (unit) {
+        run_sweep_soa_sharded<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, c->comm);
+      } else {
+        run_sweep_soa_sharded<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, c->comm);
+      }
+      // make the first-level coefficients identical on every rank again (each was drawn where its rows live)
+      sync_model_sharded(c, false, f_begin, f_end);
+      break;
+    }
+    case VPath::TwoField:
+    case VPath::SplitFused:
+    case VPath::Split:
+      // (no pack pass: the first level reads e from the interleaved array; no unpack pass when the last level runs on
+      // row tiles: its final apply pass writes e back there)
+      if (c->v_path == VPath::TwoField) {
+        if (unit)
+          run_sweep_mf<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv);
+        else
+          run_sweep_mf<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv);
+      } else if (unit)
+        run_sweep_soa<true>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, c->v_path == VPath::SplitFused);
+      else
+        run_sweep_soa<false>(s, c->timing, c->plan_V, args, f_begin, f_end, c->ls, kcv, c->v_path == VPath::SplitFused);
+      if (!c->plan_V.steps.back().par.tiled)
+        hipLaunchKernelGGL(k_e_unpack, dim3(cdiv(c->N, 256)), dim3(256), 0, s, c->eq_rows(), c->ec.p, c->N);
+      break;
+    case VPath::Cell:
+      run_sweep_cell(c, f_begin, f_end, zbase, alpha);
+      return MFM_OK;
+    case VPath::Generic:
+    case VPath::Deferred:  // (resolved above)
+      sweep_V_generic(c, f_begin, f_end, zbase, alpha, kcv);
+      return MFM_OK;
+  }
+  c->q_stale_factor = f_end - 1;  // q_train as the reference leaves it (FMTrainer.hpp:373): rebuilt when asked for
+  MFM_HIP_CHECK(hipGetLastError());
   MFM_CATCH(ctx)
 }
 
