@@ -401,9 +401,35 @@ int mfm_vb_create(int device, int64_t N, int64_t D0, const int64_t *indptr, cons
 int mfm_vb_add_block(mfm_vb *v, int64_t B, int64_t Db, const int64_t *indptr, const int32_t *indices, const double *data,
                      const int64_t *original_to_block);
 int mfm_vb_finalize(mfm_vb *v, const int32_t *group_index, int32_t G, int32_t rank);
+/* Row-sharded mode, all before mfm_vb_finalize (the counterparts of mfm_set_stream, mfm_set_allreduce, mfm_set_shard,
+ * mfm_comm_init, mfm_comm_stats, mfm_set_main_levels). The context holds rows [row_offset, row_offset + N) of n_total_rows
+ * and a replica of the model; a context with a communicator runs every level of a sweep as statistics -> ONE all-reduce of
+ * the level's sums -> apply, and all-reduces the four sums of mfm_vb_update_e as one buffer: (K + 1) * (non-empty levels) + 1
+ * collectives per iteration. A world of 1 with a communicator takes the same path. With a shard declared mfm_vb_create's N may
+ * be 0 (an empty shard takes part in every collective with zeros); otherwise mfm_vb_finalize refuses N < 1.
+ * mfm_vb_set_stream: run on the caller's stream (a callback provider enqueues its all-reduce on it) instead of the context's
+ * own; before mfm_vb_comm_init. mfm_vb_comm_init: RCCL called from this library on the context's stream, id128 from
+ * mfm_comm_unique_id.
+ * mfm_vb_set_levels: the level of every column of the GLOBAL expanded design (mfm_vb_design_levels on all rows). The ranks'
+ * own schedules could differ and their collectives would not match, so a world of more than one rank must pass it;
+ * mfm_vb_finalize uses it instead of computing its own and returns MFM_ERR_INVALID, having launched nothing, unless along every
+ * local row the levels grow with the column index (so no two columns of one level share a row).
+ * mfm_vb_design_levels: host only, no device: the expansion mfm_vb_finalize does (block k: block_rows[k] x block_cols[k] CSR and
+ * its original_to_block (N)) and the levels of its D0 + sum block_cols columns into level_out.                              */
+int mfm_vb_set_stream(mfm_vb *v, void *hip_stream);
+int mfm_vb_set_allreduce(mfm_vb *v, int (*fn)(void *user, void *dev_buf, int64_t count), void *user);
+int mfm_vb_set_shard(mfm_vb *v, int32_t rank, int32_t world, int64_t n_total_rows, int64_t row_offset);
+int mfm_vb_comm_init(mfm_vb *v, const void *id128, int32_t rank, int32_t world);
+int mfm_vb_comm_stats(const mfm_vb *v, int64_t *calls, int64_t *doubles);
+int mfm_vb_set_levels(mfm_vb *v, const int32_t *level, int64_t D);
+int mfm_vb_design_levels(int64_t N, int64_t D0, const int64_t *indptr, const int32_t *indices, const double *data,
+                         int32_t n_blocks, const int64_t *block_rows, const int64_t *block_cols,
+                         const int64_t *const *block_indptr, const int32_t *const *block_indices,
+                         const double *const *block_data, const int64_t *const *block_maps, int32_t *level_out,
+                         int32_t *n_levels);
 void mfm_vb_destroy(mfm_vb *v);
 const char *mfm_vb_last_error(const mfm_vb *v); /* (NULL: the error of the last failed mfm_vb_create of this thread) */
-/* levels of the column schedule, kernel launches of one iteration */
+/* levels of the column schedule, kernel launches of one iteration (row-sharded: two per level) */
 int mfm_vb_plan_info(const mfm_vb *v, int64_t *n_levels, int64_t *n_launches_per_iteration);
 /* the model (VariationalFM, variational.hpp:64-103); NULL array pointers are skipped */
 int mfm_vb_set_state(mfm_vb *v, double w0, double w0_var, const double *w, const double *w_var, const double *V,
@@ -413,7 +439,8 @@ int mfm_vb_get_state(mfm_vb *v, double *w0, double *w0_var, double *w, double *w
 int mfm_vb_set_w0(mfm_vb *v, double w0, double w0_var);
 /* update_e_and_var (variational.hpp:715-833) and the residual: mode 0 e -= y (initialize_e :234-241, update_e for regression
  * :839-840), mode 1 e -= E[z] of the truncated normal (classification, :841-856). out4: sum e, sum e^2, e_var_sum (with
- * N * w0_var), sum over rows of lnZ + (E[z] - score)^2 / 2 (0 in mode 0).                                                  */
+ * N * w0_var), sum over rows of lnZ + (E[z] - score)^2 / 2 (0 in mode 0). Row-sharded: the sums over all ranks' rows, with
+ * n_total_rows * w0_var added once after the all-reduce; e is the local rows'.                                              */
 int mfm_vb_update_e(mfm_vb *v, int32_t mode, double *out4);
 int mfm_vb_shift_e(mfm_vb *v, double delta); /* e += delta (update_w0 :358) */
 int mfm_vb_get_e(mfm_vb *v, double *e);

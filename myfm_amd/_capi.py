@@ -36,6 +36,8 @@ SYMBOLS = [
     "mfm_vb_create", "mfm_vb_add_block", "mfm_vb_finalize", "mfm_vb_destroy", "mfm_vb_last_error", "mfm_vb_plan_info", "mfm_vb_set_state", "mfm_vb_get_state",
     "mfm_vb_set_w0", "mfm_vb_update_e", "mfm_vb_shift_e", "mfm_vb_get_e", "mfm_vb_get_cache", "mfm_vb_zero_w", "mfm_vb_sweep_w",
     "mfm_vb_sweep_V", "mfm_vb_group_stats", "mfm_vb_synchronize", "mfm_vb_truncated_normal",
+    "mfm_vb_set_stream", "mfm_vb_set_allreduce", "mfm_vb_set_shard", "mfm_vb_comm_init", "mfm_vb_comm_stats", "mfm_vb_set_levels",
+    "mfm_vb_design_levels",
 ]
 
 _lib = None

@@ -1849,6 +1849,12 @@ struct VFM {
     }
   }
   int64_t D() const { return (int64_t)w.size(); }
+  // (calls, doubles) of the all-reduces of the row-sharded fit this model is live in; (0, 0) otherwise
+  py::tuple comm_stats() const {
+    int64_t c = 0, d = 0;
+    if (live) mfm_vb_comm_stats(live, &c, &d);
+    return py::make_tuple(c, d);
+  }
   // the mean model as a one-sample Gibbs FM: prediction runs the Gibbs scorer
   FM mean_fm() {
     ensure();
@@ -1905,6 +1911,15 @@ struct VFMTrainer {
   size_t dim_all = 0;
   FMLearningConfig cfg;
   std::mt19937 gen_;
+  // row-sharded mode (create_train_vfm_sharded): X, rels, y are rows [row_offset, row_offset + X.rows) of N_total; the providers
+  // of the all-reduce are those of FMTrainer
+  bool sharded = false;
+  int shard_rank = 0, shard_world = 1;
+  int64_t N_total = 0, row_offset = 0;
+  vector<int32_t> levels;  // level schedule of the GLOBAL expanded design (vb_column_levels)
+  std::string comm_id;
+  py::object allreduce;
+  uint64_t stream_ptr = 0;
   // BaseFMTrainer.hpp:58-105
   VFMTrainer(const py::object &Xo, const py::object &relso, const py::object &yo, int random_seed, FMLearningConfig config)
       : cfg(std::move(config)), gen_(random_seed) {
@@ -1937,7 +1952,8 @@ struct VFMTrainer {
 
   std::pair<VPredictor, VHistory> learn_with_callback(VFM &fm, VHyper &hyper,
                                                       const std::function<bool(int, VFM *, VHyper *, VHistory *)> &cb) {
-    const int64_t N = X.rows, D = (int64_t)dim_all;
+    // N: the rows of the data set (row-sharded: of all ranks), what alpha_rate, update_alpha and update_w0 count
+    const int64_t N = sharded ? N_total : X.rows, D = (int64_t)dim_all;
     const int K = fm.n_factors;
     const size_t G = cfg.n_groups;
     // initialize_hyper (variational.hpp:219-232)
@@ -1956,9 +1972,20 @@ struct VFMTrainer {
       throw std::runtime_error("Ordered Probit Regression  for Variational FM not implemented");
     vector<int32_t> gidx(cfg.group_index.begin(), cfg.group_index.end());
     mfm_vb *raw = nullptr;
-    int code = mfm_vb_create(selected_device(), N, X.cols, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), &raw);
+    int code = mfm_vb_create(selected_device(), X.rows, X.cols, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), &raw);
     if (code != MFM_OK) throw_code(code, mfm_vb_last_error(nullptr));
     std::unique_ptr<mfm_vb, void (*)(mfm_vb *)> v(raw, mfm_vb_destroy);
+    if (sharded) {
+      if (stream_ptr) vck(v.get(), mfm_vb_set_stream(v.get(), (void *)stream_ptr));
+      if (!comm_id.empty()) {
+        if (comm_id.size() != 128) throw std::invalid_argument("comm_id must be the 128 bytes of comm_unique_id()");
+        vck(v.get(), mfm_vb_comm_init(v.get(), comm_id.data(), shard_rank, shard_world));
+      } else if (allreduce.ptr() != nullptr && !allreduce.is_none()) {
+        vck(v.get(), mfm_vb_set_allreduce(v.get(), &FMTrainer::allreduce_trampoline, &allreduce));
+      }
+      vck(v.get(), mfm_vb_set_shard(v.get(), shard_rank, shard_world, N_total, row_offset));
+      vck(v.get(), mfm_vb_set_levels(v.get(), levels.data(), (int64_t)levels.size()));
+    }
     for (auto &r : rels)
       vck(v.get(), mfm_vb_add_block(v.get(), r->X.rows, r->X.cols, r->X.indptr.data(), r->X.indices.data(), r->X.data.data(),
                                     r->map64()));
@@ -2085,6 +2112,73 @@ std::pair<VPredictor, VHistory> create_train_vfm(size_t rank, Real init_std, con
   VFM fm = trainer.create_FM((int)rank, init_std);
   VHyper hyper = trainer.create_Hyper(rank);
   return trainer.learn_with_callback(fm, hyper, cb);
+}
+
+// create_train_vfm over row shards (not part of the reference's surface): every rank passes its contiguous slice of the rows
+// (X, y, every original_to_block), the level schedule of the GLOBAL expanded design (vb_column_levels) and a provider of the
+// all-reduce, as for create_train_fm_sharded. The initial weights come from the seed and the global number of features, so
+// they are the same on every rank; every rank returns the same predictor and history. The training loop runs without the GIL
+// (the all-reduce trampoline and the callback take it): ranks living in threads of one process meet in their collectives.
+std::pair<VPredictor, VHistory> create_train_vfm_sharded(size_t rank, Real init_std, const py::object &X, const py::object &relations,
+                                                         const py::object &y, int random_seed, FMLearningConfig &config,
+                                                         std::function<bool(int, VFM *, VHyper *, VHistory *)> cb, int shard_rank,
+                                                         int shard_world, int64_t n_total_rows, int64_t row_offset,
+                                                         const py::object &levels, py::object allreduce, uint64_t stream,
+                                                         const std::string &comm_id) {
+  VFMTrainer trainer(X, relations, y, random_seed, config);
+  trainer.sharded = true;
+  trainer.shard_rank = shard_rank;
+  trainer.shard_world = shard_world;
+  trainer.N_total = n_total_rows;
+  trainer.row_offset = row_offset;
+  trainer.allreduce = allreduce;
+  trainer.stream_ptr = stream;
+  trainer.comm_id = comm_id;
+  auto lv = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(levels);
+  if (!lv) throw std::invalid_argument("levels must be an int32 array");
+  trainer.levels.assign(lv.data(), lv.data() + lv.size());
+  VFM fm = trainer.create_FM((int)rank, init_std);
+  VHyper hyper = trainer.create_Hyper(rank);
+  py::gil_scoped_release release;
+  return trainer.learn_with_callback(fm, hyper, cb);
+}
+
+// the callback protocol of create_train_fm: a callback with `myfm_every` is called on those iterations and the last only
+std::function<bool(int, VFM *, VHyper *, VHistory *)> vfm_callback(py::object callback, int n_iter) {
+  int every = 1;
+  if (py::hasattr(callback, "myfm_every")) every = std::max(1, callback.attr("myfm_every").cast<int>());
+  auto f = callback.cast<std::function<bool(int, VFM *, VHyper *, VHistory *)>>();
+  if (every == 1) return f;
+  return [f, every, n_iter](int it, VFM *fm, VHyper *hy, VHistory *h) {
+    if (it % every != 0 && it != n_iter - 1) return false;
+    return f(it, fm, hy, h);
+  };
+}
+
+// levels of the columns of the design the variational trainer walks: X with the relation blocks' rows appended (host only)
+py::array_t<int32_t> vb_column_levels(const py::object &Xo, const py::object &relso) {
+  CsrView X = csr_view_from_py(Xo);
+  Relations rels = relations_from_py(relso);
+  const size_t D = check_row_consistency_return_column(X, rels);
+  vector<int64_t> rows, cols;
+  vector<const int64_t *> ptrs, maps;
+  vector<const int32_t *> idxs;
+  vector<const double *> vals;
+  for (auto &r : rels) {
+    rows.push_back(r->X.rows);
+    cols.push_back(r->X.cols);
+    ptrs.push_back(r->X.indptr.data());
+    idxs.push_back(r->X.indices.data());
+    vals.push_back(r->X.data.data());
+    maps.push_back(r->map64());
+  }
+  py::array_t<int32_t> level(D);
+  int32_t n_levels = 0;
+  int code = mfm_vb_design_levels(X.rows, X.cols, X.indptr.data(), X.indices.data(), X.data.data(), (int32_t)rels.size(),
+                                  rows.data(), cols.data(), ptrs.data(), idxs.data(), vals.data(), maps.data(),
+                                  level.mutable_data(), &n_levels);
+  if (code != MFM_OK) throw_code(code, mfm_vb_last_error(nullptr));
+  return level;
 }
 
 py::tuple truncated_normal_tuple(int right, Real mu) {
@@ -2408,6 +2502,7 @@ PYBIND11_MODULE(_myfm, m) {
             for (auto item : py::reinterpret_borrow<py::sequence>(v)) f.cutpoints.push_back(np_to_vec(item));
           })
       .def("predict_score", &VFM::predict_score)
+      .def("comm_stats", &VFM::comm_stats)
       .def("__repr__",
            [](VFM &f) {
              f.ensure();
@@ -2502,19 +2597,25 @@ PYBIND11_MODULE(_myfm, m) {
       "create_train_vfm",
       [](size_t rank, Real init_std, const py::object &X, const py::object &relations, const py::object &y, int random_seed,
          FMLearningConfig &learning_config, py::object callback) {
-        int every = 1;
-        if (py::hasattr(callback, "myfm_every")) every = std::max(1, callback.attr("myfm_every").cast<int>());
-        auto f = callback.cast<std::function<bool(int, VFM *, VHyper *, VHistory *)>>();
-        if (every == 1) return create_train_vfm(rank, init_std, X, relations, y, random_seed, learning_config, f);
-        const int n_iter = learning_config.n_iter;
         return create_train_vfm(rank, init_std, X, relations, y, random_seed, learning_config,
-                                [f, every, n_iter](int it, VFM *fm, VHyper *hy, VHistory *h) {
-                                  if (it % every != 0 && it != n_iter - 1) return false;
-                                  return f(it, fm, hy, h);
-                                });
+                                vfm_callback(callback, learning_config.n_iter));
       },
       "create and train fm.", py::return_value_policy::move, py::arg("rank"), py::arg("init_std"), py::arg("X"),
       py::arg("relations"), py::arg("y"), py::arg("random_seed"), py::arg("learning_config"), py::arg("callback"));
+  m.def(
+      "create_train_vfm_sharded",
+      [](size_t rank, Real init_std, const py::object &X, const py::object &relations, const py::object &y, int random_seed,
+         FMLearningConfig &config, py::object callback, int shard_rank, int shard_world, int64_t n_total_rows, int64_t row_offset,
+         const py::object &levels, py::object allreduce, uint64_t stream, const std::string &comm_id) {
+        return create_train_vfm_sharded(rank, init_std, X, relations, y, random_seed, config, vfm_callback(callback, config.n_iter),
+                                        shard_rank, shard_world, n_total_rows, row_offset, levels, allreduce, stream, comm_id);
+      },
+      "create_train_vfm over row shards (one process per GPU).", py::return_value_policy::move, py::arg("rank"),
+      py::arg("init_std"), py::arg("X"), py::arg("relations"), py::arg("y"), py::arg("random_seed"), py::arg("config"),
+      py::arg("callback"), py::arg("shard_rank"), py::arg("shard_world"), py::arg("n_total_rows"), py::arg("row_offset"),
+      py::arg("levels"), py::arg("allreduce") = py::none(), py::arg("stream") = 0, py::arg("comm_id") = py::bytes(""));
+  m.def("vb_column_levels", &vb_column_levels, py::arg("X"), py::arg("relations"),
+        "Level of every column of X with the relation blocks expanded: the schedule create_train_vfm_sharded takes (host only).");
   m.def("mean_var_truncated_normal_left", [](Real mu) { return truncated_normal_tuple(0, mu); });
   m.def("mean_var_truncated_normal_right", [](Real mu) { return truncated_normal_tuple(1, mu); });
 

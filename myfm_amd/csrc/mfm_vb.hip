@@ -8,13 +8,24 @@
 // Per row: e, and for the factor being swept q, x2s, x3sv. Every sum has a fixed association (lane-strided, then a butterfly
 // over the wavefront or a tree over the workgroup, then one workgroup over the partials), so a rerun is bit-identical; no
 // floating-point atomics.
+//
+// Row-sharded (a communicator set: mfm_vb_set_allreduce / mfm_vb_comm_init): this context holds a contiguous slice of the rows
+// and a replica of the model. A column's sums must cross the ranks before its update, so every level runs as
+//   k_vb_stats_w / k_vb_stats_v -> S (2 | 4 doubles per column of the level) -> ONE all-reduce of S -> k_vb_apply_w / k_vb_apply_v
+// with S holding only terms that are additive over rows; everything that multiplies by v_old, alpha or lambda happens in the
+// apply kernel, from the reduced sums, which are the same on every rank: every rank writes the model entry itself and the
+// replicas stay bit-identical without a broadcast. The four score sums are all-reduced as one buffer per mfm_vb_update_e.
+// Per iteration: (K + 1) * (non-empty levels) + 1 collectives.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
+#include "mfm_comm.hpp"
 #include "mfm_common.hpp"
 #include "mfm_vb.hpp"
 
@@ -157,6 +168,60 @@ __global__ __launch_bounds__(WG) void k_vb_sweep_w(const int32_t *__restrict__ c
   }
 }
 
+// row-sharded update_w, first half: per column of the level (sum x^2, sum x (e - x w_old)) over the LOCAL rows -> S[2 c ..]
+__global__ __launch_bounds__(WG) void k_vb_stats_w(const int32_t *__restrict__ cols, int n, const int64_t *__restrict__ cptr,
+                                                   const int32_t *__restrict__ ridx, const double *__restrict__ cval,
+                                                   const double *__restrict__ w, const double *__restrict__ e,
+                                                   double *__restrict__ S) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = blockIdx.x * COLS_PER_WG + (threadIdx.x / WAVE);
+  if (c >= n) return;  // (whole wavefronts)
+  const int32_t j = cols[c];
+  const int64_t b = cptr[j], en = cptr[j + 1];
+  const double w_old = w[j];
+  double s2 = 0, s1 = 0;
+  for (int64_t p = b + lane; p < en; p += WAVE) {
+    const double x = cval[p];
+    s2 += x * x;
+    s1 += x * (e[ridx[p]] - x * w_old);
+  }
+  s2 = wave_sum(s2);
+  s1 = wave_sum(s1);
+  if (lane == 0) {
+    S[(int64_t)c * 2] = s2;
+    S[(int64_t)c * 2 + 1] = s1;
+  }
+}
+
+// second half: w_new and 1 / square from the sums over ALL ranks' rows (k_vb_sweep_w's expressions), e of the local rows
+__global__ __launch_bounds__(WG) void k_vb_apply_w(const int32_t *__restrict__ cols, int n, const int64_t *__restrict__ cptr,
+                                                   const int32_t *__restrict__ ridx, const double *__restrict__ cval,
+                                                   const int32_t *__restrict__ gidx, double alpha,
+                                                   const double *__restrict__ lam, const double *__restrict__ mu,
+                                                   const double *__restrict__ S, double *__restrict__ w,
+                                                   double *__restrict__ wv, double *__restrict__ e) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = blockIdx.x * COLS_PER_WG + (threadIdx.x / WAVE);
+  if (c >= n) return;
+  const int32_t j = cols[c];
+  const int32_t g = gidx[j];
+  const int64_t b = cptr[j], en = cptr[j + 1];
+  const double w_old = w[j];
+  const double s2 = S[(int64_t)c * 2], s1 = S[(int64_t)c * 2 + 1];
+  const double square = lam[g] + alpha * s2;
+  const double linear = -alpha * s1 + lam[g] * mu[g];
+  const double w_new = linear / square;
+  for (int64_t p = b + lane; p < en; p += WAVE) {
+    const double x = cval[p];
+    const int32_t r = ridx[p];
+    e[r] = (e[r] - x * w_old) + x * w_new;
+  }
+  if (lane == 0) {
+    w[j] = w_new;
+    wv[j] = 1 / square;
+  }
+}
+
 // the per-row cache of one factor (variational.hpp:452-465): q, x2s, x3sv
 __global__ void k_vb_cache(int64_t N, const int64_t *__restrict__ ptr, const int32_t *__restrict__ idx,
                            const double *__restrict__ val, const double *__restrict__ Vf, const double *__restrict__ Vvf,
@@ -230,6 +295,87 @@ __global__ __launch_bounds__(WG) void k_vb_sweep_v(const int32_t *__restrict__ c
   }
 }
 
+// row-sharded update_V, first half: (sq, lin, sq_var, lin_var) of k_vb_sweep_v over the LOCAL rows, as they stand before
+// `lin += sq * v_old` -> S[4 c ..]
+__global__ __launch_bounds__(WG) void k_vb_stats_v(const int32_t *__restrict__ cols, int n, const int64_t *__restrict__ cptr,
+                                                   const int32_t *__restrict__ ridx, const double *__restrict__ cval,
+                                                   const double *__restrict__ Vf, const double *__restrict__ Vvf,
+                                                   const double *__restrict__ e, const double *__restrict__ q,
+                                                   const double *__restrict__ x2s, const double *__restrict__ x3sv,
+                                                   double *__restrict__ S) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = blockIdx.x * COLS_PER_WG + (threadIdx.x / WAVE);
+  if (c >= n) return;
+  const int32_t j = cols[c];
+  const int64_t b = cptr[j], en = cptr[j + 1];
+  const double v_old = Vf[j], s_old = Vvf[j];
+  double sq = 0, lin = 0, sq_var = 0, lin_var = 0;
+  for (int64_t p = b + lane; p < en; p += WAVE) {
+    const double x = cval[p];
+    const int32_t r = ridx[p];
+    const double h = x * (q[r] - x * v_old);
+    double a2 = x2s[r], a3 = x3sv[r];
+    a2 -= x * x * s_old;
+    a3 -= x * x * x * s_old * v_old;
+    sq += h * h;
+    lin += (-e[r]) * h;
+    sq_var += a2 * x * x;
+    lin_var += h * a2 - x * a3;
+  }
+  sq = wave_sum(sq);
+  lin = wave_sum(lin);
+  sq_var = wave_sum(sq_var);
+  lin_var = wave_sum(lin_var);
+  if (lane == 0) {
+    double *o = S + (int64_t)c * 4;
+    o[0] = sq;
+    o[1] = lin;
+    o[2] = sq_var;
+    o[3] = lin_var;
+  }
+}
+
+// second half: v_new and s_new from the sums over ALL ranks' rows (k_vb_sweep_v's expressions), the state of the local rows
+__global__ __launch_bounds__(WG) void k_vb_apply_v(const int32_t *__restrict__ cols, int n, const int64_t *__restrict__ cptr,
+                                                   const int32_t *__restrict__ ridx, const double *__restrict__ cval,
+                                                   const int32_t *__restrict__ gidx, double alpha,
+                                                   const double *__restrict__ lam, const double *__restrict__ mu,
+                                                   const double *__restrict__ S, double *__restrict__ Vf,
+                                                   double *__restrict__ Vvf, double *__restrict__ e, double *__restrict__ q,
+                                                   double *__restrict__ x2s, double *__restrict__ x3sv) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int c = blockIdx.x * COLS_PER_WG + (threadIdx.x / WAVE);
+  if (c >= n) return;
+  const int32_t j = cols[c];
+  const int32_t g = gidx[j];
+  const int64_t b = cptr[j], en = cptr[j + 1];
+  const double v_old = Vf[j], s_old = Vvf[j];
+  const double *in = S + (int64_t)c * 4;
+  double sq = in[0], lin = in[1];
+  const double sq_var = in[2], lin_var = in[3];
+  lin += sq * v_old;
+  lin -= lin_var;
+  sq += sq_var;
+  sq *= alpha;
+  lin *= alpha;
+  sq += lam[g];
+  lin += lam[g] * mu[g];
+  const double v_new = lin / sq, s_new = 1 / sq;
+  for (int64_t p = b + lane; p < en; p += WAVE) {
+    const double x = cval[p];
+    const int32_t r = ridx[p];
+    const double h = x * (q[r] - x * v_old);
+    q[r] += x * (v_new - v_old);
+    e[r] += h * (v_new - v_old);
+    x2s[r] += x * x * (s_new - s_old);
+    x3sv[r] += x * x * x * (s_new * v_new - s_old * v_old);
+  }
+  if (lane == 0) {
+    Vf[j] = v_new;
+    Vvf[j] = s_new;
+  }
+}
+
 // per (slot, group): slot 0 = (w, w_var), slot 1 + f = (V[:, f], V_var[:, f]); one workgroup each over the group's features:
 // sum theta, sum ((theta - mu)^2 + mu_var + var), sum log var (update_lambda_generic :269-295, update_mu_generic :298-318, the
 // weight terms of the ELBO :880-917)
@@ -264,7 +410,11 @@ using namespace mfm;
 struct mfm_vb {
   int device = 0;
   hipStream_t stream = nullptr;
+  bool own_stream = true;
   std::string err;
+  Comm comm;  // row-sharded mode: set before mfm_vb_finalize
+  int64_t N_total = 0, row_offset = 0;  // (mfm_vb_set_shard; unsharded: N_total == N)
+  std::vector<int32_t> given_levels;    // mfm_vb_set_levels: the schedule of the GLOBAL expanded design
   int64_t N = 0, D = 0;
   int K = 0, G = 0;
   double w0 = 0, w0_var = 0;
@@ -274,6 +424,7 @@ struct mfm_vb {
   DevBuf<int64_t> ptr, cptr, gptr;
   DevBuf<int32_t> idx, ridx, order, gidx, gfeat;
   DevBuf<double> val, cval, y, w, wv, V, Vv, e, q, x2s, x3sv, part, red, hyp, stats;
+  DevBuf<double> S;  // row-sharded: the sums of one level's columns (4 doubles per column of the largest level)
   int n_parts = 0;
   // staged by mfm_vb_create / mfm_vb_add_block until mfm_vb_finalize
   struct Block {
@@ -286,8 +437,13 @@ struct mfm_vb {
   bool finalized = false;
 
   ~mfm_vb() {
-    if (stream) (void)hipStreamDestroy(stream);
+    if (comm.nccl) {  // (before the stream it is enqueued on goes)
+      (void)Rccl::get().CommDestroy(comm.nccl);
+      comm.nccl = nullptr;
+    }
+    if (stream && own_stream) (void)hipStreamDestroy(stream);
   }
+  bool sharded() const { return comm.active(); }
   void use() { MFM_HIP_CHECK(hipSetDevice(device)); }
   void put_hyp(const double *a, size_t na, const double *b, size_t nb) {  // small per-call uploads: [a | b]
     std::vector<double> h(a, a + na);
@@ -325,6 +481,83 @@ int vb_guard(mfm_vb *v, F f, bool need_finalized = true) {
   }
 }
 thread_local std::string g_vb_error;
+
+// The design the sweeps walk: the main table with every relation block's row appended to the train rows that map to
+// it, block columns after the main table's (the feature order of BaseFMTrainer.hpp:58-105). The reference's block
+// caches (variational.hpp:388-447, :557-710, :728-827) are sums over the train rows of a block row, so this is the same
+// iteration in exact arithmetic; tests/vb_ref.py restates the block algebra and holds the two to rounding.
+// X: the expanded table, Xt: its CSC. Shared by mfm_vb_finalize and mfm_vb_design_levels.
+void vb_expand_design(const HostCsr &main, const std::vector<mfm_vb::Block> &blocks, HostCsr &X, HostCsr &Xt) {
+  const int64_t N = main.rows;
+  int64_t D = main.cols;
+  std::vector<int64_t> offset;
+  for (auto &b : blocks) {
+    offset.push_back(D);
+    D += b.X.cols;
+  }
+  X.rows = N;
+  X.cols = D;
+  X.ptr.assign((size_t)N + 1, 0);
+  for (int64_t t = 0; t < N; t++) {
+    int64_t n = main.ptr[t + 1] - main.ptr[t];
+    for (auto &b : blocks) n += b.X.ptr[b.map[t] + 1] - b.X.ptr[b.map[t]];
+    X.ptr[t + 1] = X.ptr[t] + n;
+  }
+  if (X.ptr[N] >= (int64_t)2147483647) throw Error(MFM_ERR_INVALID, "nnz must be < 2^31 (relation blocks expanded)");
+  X.idx.resize((size_t)X.ptr[N]);
+  X.val.resize((size_t)X.ptr[N]);
+  // a column twice in one row would put the row twice into one CSC column, and two lanes of a sweep would update that
+  // row's state at the same time
+  std::vector<int64_t> seen((size_t)D, -1);
+  for (int64_t t = 0; t < N; t++) {
+    int64_t o = X.ptr[t];
+    auto put = [&](int64_t col, double x) {
+      if (seen[(size_t)col] == t)
+        throw Error(MFM_ERR_INVALID, "a row holds the same column twice: sum duplicate entries first (scipy: sum_duplicates)");
+      seen[(size_t)col] = t;
+      X.idx[(size_t)o] = (int32_t)col;
+      X.val[(size_t)o++] = x;
+    };
+    for (int64_t p = main.ptr[t]; p < main.ptr[t + 1]; p++) put(main.idx[p], main.val[p]);
+    for (size_t k = 0; k < blocks.size(); k++) {
+      const auto &b = blocks[k];
+      const int64_t i = b.map[t];
+      for (int64_t p = b.X.ptr[i]; p < b.X.ptr[i + 1]; p++) put(offset[k] + b.X.idx[p], b.X.val[p]);
+    }
+  }
+  Xt = transpose_host(X);
+}
+
+mfm_vb::Block vb_make_block(int64_t N, int64_t B, int64_t Db, const int64_t *indptr, const int32_t *indices, const double *data,
+                            const int64_t *original_to_block) {
+  mfm_vb::Block b;
+  b.X = make_host_csr(B, Db, indptr, indices, data);
+  b.map.assign(original_to_block, original_to_block + N);
+  for (int64_t t = 0; t < N; t++)
+    if (b.map[t] < 0 || b.map[t] >= B) throw Error(MFM_ERR_INVALID, "original_to_block out of range");
+  return b;
+}
+
+// a schedule handed in (mfm_vb_set_levels) must be one the sweeps may run on the LOCAL rows: along every row the levels grow
+// with the column index, so no two columns of one level share a row and every column sees the columns before it
+int32_t vb_check_levels(const HostCsr &X, const std::vector<int32_t> &level) {
+  if ((int64_t)level.size() != X.cols) throw Error(MFM_ERR_INVALID, "mfm_vb_set_levels: one level per column of the expanded design");
+  int32_t n_levels = 0;
+  for (int32_t l : level) {
+    if (l < 0 || l >= X.cols) throw Error(MFM_ERR_INVALID, "mfm_vb_set_levels: a level lies outside [0, D)");
+    n_levels = std::max(n_levels, l + 1);
+  }
+  std::vector<std::pair<int32_t, int32_t>> row;
+  for (int64_t t = 0; t < X.rows; t++) {
+    row.clear();
+    for (int64_t p = X.ptr[t]; p < X.ptr[t + 1]; p++) row.emplace_back(X.idx[p], level[(size_t)X.idx[p]]);
+    std::sort(row.begin(), row.end());
+    for (size_t k = 1; k < row.size(); k++)
+      if (row[k].second <= row[k - 1].second)
+        throw Error(MFM_ERR_INVALID, "mfm_vb_set_levels: two columns that share a row must lie in levels that grow with the column index");
+  }
+  return n_levels;
+}
 }  // namespace
 
 extern "C" {
@@ -334,7 +567,8 @@ int mfm_vb_create(int device, int64_t N, int64_t D0, const int64_t *indptr, cons
   *out = nullptr;
   auto *v = new mfm_vb();
   try {
-    if (N < 1) throw Error(MFM_ERR_INVALID, "the variational trainer needs at least one row");
+    // (N == 0 is an empty shard once mfm_vb_set_shard has said so; mfm_vb_finalize refuses it otherwise)
+    if (N < 0) throw Error(MFM_ERR_INVALID, "the variational trainer needs at least one row");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
       throw Error(MFM_ERR_DEVICE, "no usable HIP device");
@@ -363,14 +597,120 @@ int mfm_vb_add_block(mfm_vb *v, int64_t B, int64_t Db, const int64_t *indptr, co
       v,
       [&]() {
         if (v->finalized) throw Error(MFM_ERR_INVALID, "mfm_vb_add_block after mfm_vb_finalize");
-        mfm_vb::Block b;
-        b.X = make_host_csr(B, Db, indptr, indices, data);
-        b.map.assign(original_to_block, original_to_block + v->N);
-        for (int64_t t = 0; t < v->N; t++)
-          if (b.map[t] < 0 || b.map[t] >= B) throw Error(MFM_ERR_INVALID, "original_to_block out of range");
-        v->blocks.push_back(std::move(b));
+        v->blocks.push_back(vb_make_block(v->N, B, Db, indptr, indices, data, original_to_block));
       },
       false);
+}
+
+int mfm_vb_set_stream(mfm_vb *v, void *hip_stream) {
+  return vb_guard(
+      v,
+      [&]() {
+        if (v->finalized) throw Error(MFM_ERR_RUNTIME, "mfm_vb_set_stream must be called before mfm_vb_finalize");
+        if (v->comm.nccl) throw Error(MFM_ERR_RUNTIME, "mfm_vb_set_stream must be called before mfm_vb_comm_init");
+        if (v->own_stream && v->stream) {
+          MFM_HIP_CHECK(hipStreamSynchronize(v->stream));
+          MFM_HIP_CHECK(hipStreamDestroy(v->stream));
+        }
+        v->stream = (hipStream_t)hip_stream;
+        v->own_stream = false;
+        v->comm.stream = v->stream;
+      },
+      false);
+}
+
+int mfm_vb_set_allreduce(mfm_vb *v, int (*fn)(void *user, void *dev_buf, int64_t count), void *user) {
+  return vb_guard(
+      v,
+      [&]() {
+        if (v->finalized) throw Error(MFM_ERR_RUNTIME, "mfm_vb_set_allreduce must be called before mfm_vb_finalize");
+        v->comm.fn = fn;
+        v->comm.user = user;
+      },
+      false);
+}
+
+int mfm_vb_set_shard(mfm_vb *v, int32_t rank, int32_t world, int64_t n_total_rows, int64_t row_offset) {
+  return vb_guard(
+      v,
+      [&]() {
+        if (v->finalized) throw Error(MFM_ERR_RUNTIME, "mfm_vb_set_shard must be called before mfm_vb_finalize");
+        if (world < 1 || rank < 0 || rank >= world) throw Error(MFM_ERR_INVALID, "bad rank / world size");
+        if (n_total_rows < 1 || row_offset < 0 || row_offset + v->N > n_total_rows)
+          throw Error(MFM_ERR_INVALID, "the shard's rows [row_offset, row_offset + N) must lie inside n_total_rows >= 1 rows");
+        v->comm.rank = rank;
+        v->comm.world = world;
+        v->comm.shard_set = true;
+        v->N_total = n_total_rows;
+        v->row_offset = row_offset;
+      },
+      false);
+}
+
+int mfm_vb_comm_init(mfm_vb *v, const void *id128, int32_t rank, int32_t world) {
+  return vb_guard(
+      v,
+      [&]() {
+        if (v->finalized) throw Error(MFM_ERR_RUNTIME, "mfm_vb_comm_init must be called before mfm_vb_finalize");
+        if (world < 1 || rank < 0 || rank >= world) throw Error(MFM_ERR_INVALID, "bad rank / world size");
+        if (v->comm.nccl) throw Error(MFM_ERR_RUNTIME, "communicator already initialised");
+        Rccl &r = Rccl::get();
+        mfm_nccl_id id;
+        std::memcpy(&id, id128, sizeof(id));
+        void *comm = nullptr;
+        r.check(r.CommInitRank(&comm, world, id, rank), "ncclCommInitRank");
+        v->comm.nccl = comm;
+        v->comm.stream = v->stream;
+        v->comm.rank = rank;
+        v->comm.world = world;
+      },
+      false);
+}
+
+int mfm_vb_comm_stats(const mfm_vb *v, int64_t *calls, int64_t *doubles) {
+  if (!v) return MFM_ERR_INVALID;
+  if (calls) *calls = v->comm.calls;
+  if (doubles) *doubles = v->comm.doubles;
+  return MFM_OK;
+}
+
+int mfm_vb_set_levels(mfm_vb *v, const int32_t *level, int64_t D) {
+  return vb_guard(
+      v,
+      [&]() {
+        if (v->finalized) throw Error(MFM_ERR_RUNTIME, "mfm_vb_set_levels must be called before mfm_vb_finalize");
+        if (D < 0) throw Error(MFM_ERR_INVALID, "negative number of columns");
+        v->given_levels.assign(level, level + D);
+      },
+      false);
+}
+
+int mfm_vb_design_levels(int64_t N, int64_t D0, const int64_t *indptr, const int32_t *indices, const double *data,
+                         int32_t n_blocks, const int64_t *block_rows, const int64_t *block_cols,
+                         const int64_t *const *block_indptr, const int32_t *const *block_indices,
+                         const double *const *block_data, const int64_t *const *block_maps, int32_t *level_out,
+                         int32_t *n_levels) {
+  try {
+    if (N < 0 || n_blocks < 0) throw Error(MFM_ERR_INVALID, "negative shape");
+    HostCsr main = make_host_csr(N, D0, indptr, indices, data);
+    std::vector<mfm_vb::Block> blocks;
+    for (int32_t k = 0; k < n_blocks; k++)
+      blocks.push_back(vb_make_block(N, block_rows[k], block_cols[k], block_indptr[k], block_indices[k], block_data[k],
+                                     block_maps[k]));
+    HostCsr X, Xt;
+    vb_expand_design(main, blocks, X, Xt);
+    std::vector<int32_t> level;
+    const int32_t n = column_levels(Xt, level);
+    std::copy(level.begin(), level.end(), level_out);
+    if (n_levels) *n_levels = n;
+    return MFM_OK;
+  } catch (const Error &ex) {
+    g_vb_error = ex.what();
+    return ex.code;
+  } catch (const std::exception &ex) {
+    g_vb_error = ex.what();
+    return MFM_ERR_RUNTIME;
+  }
 }
 
 int mfm_vb_finalize(mfm_vb *v, const int32_t *group_index, int32_t G, int32_t rank) {
@@ -380,54 +720,31 @@ int mfm_vb_finalize(mfm_vb *v, const int32_t *group_index, int32_t G, int32_t ra
     if (v->finalized) throw Error(MFM_ERR_INVALID, "mfm_vb_finalize called twice");
     if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
     const int64_t N = v->N;
-    // The design the sweeps walk: the main table with every relation block's row appended to the train rows that map to
-    // it, block columns after the main table's (the feature order of BaseFMTrainer.hpp:58-105). The reference's block
-    // caches (variational.hpp:388-447, :557-710, :728-827) are sums over the train rows of a block row, so this is the same
-    // iteration in exact arithmetic; tests/vb_ref.py restates the block algebra and holds the two to rounding.
+    const bool declared = v->comm.shard_set;
+    if (N < 1 && !declared) throw Error(MFM_ERR_INVALID, "the variational trainer needs at least one row");
+    if (declared && v->comm.world > 1 && !v->comm.active())
+      throw Error(MFM_ERR_INVALID, "a shard of more than one rank needs an all-reduce (mfm_vb_set_allreduce / mfm_vb_comm_init)");
+    if (!declared && v->comm.world > 1)
+      throw Error(MFM_ERR_INVALID, "a communicator of more than one rank needs mfm_vb_set_shard (n_total_rows, row_offset)");
+    if (!declared) v->N_total = N;
     int64_t D = v->main.cols;
-    std::vector<int64_t> offset;
-    for (auto &b : v->blocks) {
-      offset.push_back(D);
-      D += b.X.cols;
-    }
+    for (auto &b : v->blocks) D += b.X.cols;
     if (G < 0 || (G == 0 && D > 0)) throw Error(MFM_ERR_INVALID, "every feature needs a group");
-    HostCsr X;
-    X.rows = N;
-    X.cols = D;
-    X.ptr.assign((size_t)N + 1, 0);
-    for (int64_t t = 0; t < N; t++) {
-      int64_t n = v->main.ptr[t + 1] - v->main.ptr[t];
-      for (auto &b : v->blocks) n += b.X.ptr[b.map[t] + 1] - b.X.ptr[b.map[t]];
-      X.ptr[t + 1] = X.ptr[t] + n;
-    }
-    if (X.ptr[N] >= (int64_t)2147483647) throw Error(MFM_ERR_INVALID, "nnz must be < 2^31 (relation blocks expanded)");
-    X.idx.resize((size_t)X.ptr[N]);
-    X.val.resize((size_t)X.ptr[N]);
-    // a column twice in one row would put the row twice into one CSC column, and two lanes of a sweep would update that
-    // row's state at the same time
-    std::vector<int64_t> seen((size_t)D, -1);
-    for (int64_t t = 0; t < N; t++) {
-      int64_t o = X.ptr[t];
-      auto put = [&](int64_t col, double x) {
-        if (seen[(size_t)col] == t)
-          throw Error(MFM_ERR_INVALID, "a row holds the same column twice: sum duplicate entries first (scipy: sum_duplicates)");
-        seen[(size_t)col] = t;
-        X.idx[(size_t)o] = (int32_t)col;
-        X.val[(size_t)o++] = x;
-      };
-      for (int64_t p = v->main.ptr[t]; p < v->main.ptr[t + 1]; p++) put(v->main.idx[p], v->main.val[p]);
-      for (size_t k = 0; k < v->blocks.size(); k++) {
-        const auto &b = v->blocks[k];
-        const int64_t i = b.map[t];
-        for (int64_t p = b.X.ptr[i]; p < b.X.ptr[i + 1]; p++) put(offset[k] + b.X.idx[p], b.X.val[p]);
-      }
-    }
+    HostCsr X, Xt;
+    vb_expand_design(v->main, v->blocks, X, Xt);
     v->D = D;
     v->K = rank;
     v->G = G;
-    HostCsr Xt = transpose_host(X);
+    // a shard sees only its own rows: its own schedule could differ from another rank's and the ranks' collectives would not
+    // match, so a sharded fit is handed the schedule of the global design
     std::vector<int32_t> level;
-    v->n_levels = column_levels(Xt, level);
+    if (!v->given_levels.empty() || (v->sharded() && D > 0 && v->comm.world > 1)) {
+      if (v->given_levels.empty()) throw Error(MFM_ERR_INVALID, "a row-sharded fit needs the global level schedule (mfm_vb_set_levels)");
+      level = v->given_levels;
+      v->n_levels = vb_check_levels(X, level);
+    } else {
+      v->n_levels = column_levels(Xt, level);
+    }
     // columns by (level, index)
     v->level_ptr.assign((size_t)v->n_levels + 1, 0);
     for (int64_t j = 0; j < D; j++) v->level_ptr[(size_t)level[j] + 1]++;
@@ -469,7 +786,13 @@ int mfm_vb_finalize(mfm_vb *v, const int32_t *group_index, int32_t G, int32_t ra
     v->q.alloc((size_t)N);
     v->x2s.alloc((size_t)N);
     v->x3sv.alloc((size_t)N);
-    v->n_parts = (int)std::min<int64_t>(vb::MAX_PARTS, mfm_vb::cdiv_(N, vb::WG));
+    v->given_levels.clear();
+    v->n_parts = (int)std::max<int64_t>(1, std::min<int64_t>(vb::MAX_PARTS, mfm_vb::cdiv_(N, vb::WG)));
+    if (v->sharded()) {
+      int64_t widest = 1;
+      for (int32_t l = 0; l < v->n_levels; l++) widest = std::max(widest, v->level_ptr[l + 1] - v->level_ptr[l]);
+      v->S.alloc((size_t)widest * 4);
+    }
     v->part.alloc((size_t)v->n_parts * 4);
     v->red.alloc(4);
     v->stats.alloc((size_t)(rank + 1) * G * 3);
@@ -495,8 +818,10 @@ int mfm_vb_plan_info(const mfm_vb *v, int64_t *n_levels, int64_t *n_launches_per
   int64_t lv = 0;
   for (int32_t l = 0; l < v->n_levels; l++) lv += v->level_ptr[l + 1] > v->level_ptr[l];
   if (n_levels) *n_levels = v->n_levels;
-  // score + reduce, w sweep, per factor the cache and its levels, two group-statistics launches
-  if (n_launches_per_iteration) *n_launches_per_iteration = 2 + lv + (int64_t)v->K * (1 + lv) + 2;
+  // score + reduce, w sweep, per factor the cache and its levels, two group-statistics launches; row-sharded every level is
+  // two launches (statistics, apply)
+  const int64_t per_level = v->sharded() ? 2 : 1;
+  if (n_launches_per_iteration) *n_launches_per_iteration = 2 + per_level * lv + (int64_t)v->K * (1 + per_level * lv) + 2;
   return MFM_OK;
 }
 
@@ -546,18 +871,20 @@ int mfm_vb_update_e(mfm_vb *v, int32_t mode, double *out4) {
                        v->val.p, v->w0, v->w.p, v->wv.p, v->V.p, v->Vv.p, v->y.p, (int)mode, v->e.p, v->part.p);
     hipLaunchKernelGGL(vb::k_vb_reduce, dim3(1), dim3(vb::WG), 0, v->stream, v->part.p, v->n_parts, v->red.p);
     MFM_HIP_CHECK(hipGetLastError());
+    v->comm.allreduce(v->red.p, 4);  // (row-sharded: the four sums over all ranks' rows as one buffer)
     double h[4];
     MFM_HIP_CHECK(hipMemcpyAsync(h, v->red.p, sizeof(h), hipMemcpyDeviceToHost, v->stream));
     MFM_HIP_CHECK(hipStreamSynchronize(v->stream));
     out4[0] = h[0];
     out4[1] = h[1];
-    out4[2] = v->w0_var * (double)v->N + h[2];
+    out4[2] = v->w0_var * (double)v->N_total + h[2];  // (once, after the all-reduce)
     out4[3] = h[3];
   });
 }
 
 int mfm_vb_shift_e(mfm_vb *v, double delta) {
   return vb_guard(v, [&]() {
+    if (!v->N) return;  // (an empty shard)
     hipLaunchKernelGGL(vb::k_vb_shift, dim3(mfm_vb::cdiv_(v->N, vb::WG)), dim3(vb::WG), 0, v->stream, v->N, v->e.p, delta);
     MFM_HIP_CHECK(hipGetLastError());
   });
@@ -566,7 +893,7 @@ int mfm_vb_shift_e(mfm_vb *v, double delta) {
 int mfm_vb_get_e(mfm_vb *v, double *e) {
   return vb_guard(v, [&]() {
     MFM_HIP_CHECK(hipStreamSynchronize(v->stream));
-    MFM_HIP_CHECK(hipMemcpy(e, v->e.p, (size_t)v->N * sizeof(double), hipMemcpyDeviceToHost));
+    if (v->N) MFM_HIP_CHECK(hipMemcpy(e, v->e.p, (size_t)v->N * sizeof(double), hipMemcpyDeviceToHost));
   });
 }
 
@@ -574,6 +901,7 @@ int mfm_vb_get_cache(mfm_vb *v, double *q, double *x2s, double *x3sv) {
   return vb_guard(v, [&]() {
     MFM_HIP_CHECK(hipStreamSynchronize(v->stream));
     const size_t n = (size_t)v->N * sizeof(double);
+    if (!n) return;
     if (q) MFM_HIP_CHECK(hipMemcpy(q, v->q.p, n, hipMemcpyDeviceToHost));
     if (x2s) MFM_HIP_CHECK(hipMemcpy(x2s, v->x2s.p, n, hipMemcpyDeviceToHost));
     if (x3sv) MFM_HIP_CHECK(hipMemcpy(x3sv, v->x3sv.p, n, hipMemcpyDeviceToHost));
@@ -594,6 +922,14 @@ int mfm_vb_sweep_w(mfm_vb *v, double alpha, const double *lambda_w, const double
     v->put_hyp(lambda_w, (size_t)v->G, mu_w, (size_t)v->G);
     const double *lam = v->hyp.p, *mu = v->hyp.p + v->G;
     v->each_level([&](const int32_t *cols, int n, int grid) {
+      if (v->sharded()) {
+        hipLaunchKernelGGL(vb::k_vb_stats_w, dim3(grid), dim3(vb::WG), 0, v->stream, cols, n, v->cptr.p, v->ridx.p, v->cval.p,
+                           v->w.p, v->e.p, v->S.p);
+        v->comm.allreduce(v->S.p, 2 * (int64_t)n);
+        hipLaunchKernelGGL(vb::k_vb_apply_w, dim3(grid), dim3(vb::WG), 0, v->stream, cols, n, v->cptr.p, v->ridx.p, v->cval.p,
+                           v->gidx.p, alpha, lam, mu, v->S.p, v->w.p, v->wv.p, v->e.p);
+        return;
+      }
       hipLaunchKernelGGL(vb::k_vb_sweep_w, dim3(grid), dim3(vb::WG), 0, v->stream, cols, n, v->cptr.p, v->ridx.p, v->cval.p,
                          v->gidx.p, alpha, lam, mu, v->w.p, v->wv.p, v->e.p);
     });
@@ -610,9 +946,18 @@ int mfm_vb_sweep_V(mfm_vb *v, int32_t f_begin, int32_t f_end, double alpha, cons
     for (int32_t f = f_begin; f < f_end; f++) {
       double *Vf = v->V.p + (int64_t)f * v->D, *Vvf = v->Vv.p + (int64_t)f * v->D;
       const double *lam = v->hyp.p + (size_t)f * v->G, *mu = v->hyp.p + GK + (size_t)f * v->G;
-      hipLaunchKernelGGL(vb::k_vb_cache, dim3(grid_rows), dim3(vb::WG), 0, v->stream, v->N, v->ptr.p, v->idx.p, v->val.p, Vf,
-                         Vvf, v->q.p, v->x2s.p, v->x3sv.p);
+      if (grid_rows)  // (0: an empty shard)
+        hipLaunchKernelGGL(vb::k_vb_cache, dim3(grid_rows), dim3(vb::WG), 0, v->stream, v->N, v->ptr.p, v->idx.p, v->val.p, Vf,
+                           Vvf, v->q.p, v->x2s.p, v->x3sv.p);
       v->each_level([&](const int32_t *cols, int n, int grid) {
+        if (v->sharded()) {
+          hipLaunchKernelGGL(vb::k_vb_stats_v, dim3(grid), dim3(vb::WG), 0, v->stream, cols, n, v->cptr.p, v->ridx.p, v->cval.p,
+                             Vf, Vvf, v->e.p, v->q.p, v->x2s.p, v->x3sv.p, v->S.p);
+          v->comm.allreduce(v->S.p, 4 * (int64_t)n);
+          hipLaunchKernelGGL(vb::k_vb_apply_v, dim3(grid), dim3(vb::WG), 0, v->stream, cols, n, v->cptr.p, v->ridx.p, v->cval.p,
+                             v->gidx.p, alpha, lam, mu, v->S.p, Vf, Vvf, v->e.p, v->q.p, v->x2s.p, v->x3sv.p);
+          return;
+        }
         hipLaunchKernelGGL(vb::k_vb_sweep_v, dim3(grid), dim3(vb::WG), 0, v->stream, cols, n, v->cptr.p, v->ridx.p, v->cval.p,
                            v->gidx.p, alpha, lam, mu, Vf, Vvf, v->e.p, v->q.p, v->x2s.p, v->x3sv.p);
       });

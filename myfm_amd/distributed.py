@@ -83,7 +83,7 @@ _STATE = {"on": False, "group": None, "native": True, "peer_exchange": False}
 
 
 def enable(group=None, set_device=True, native=True, peer_exchange=False):
-    """Make `MyFM*.fit()` row-sharded over the ranks of `group` (default: the world group of an initialised
+    """Make `MyFM*.fit()` and `VariationalFM*.fit()` row-sharded over the ranks of `group` (default: the world group of an initialised
     torch.distributed): every rank calls fit() with the SAME full data, trains on its contiguous slice of the rows on its
     own GPU (LOCAL_RANK) with the all-reduces issued by libmyfm_hip.so through RCCL, and ends with the same samples.
 
@@ -92,7 +92,7 @@ def enable(group=None, set_device=True, native=True, peer_exchange=False):
 
     peer_exchange=True: two-field one-hot tables train with the persistent sweep on every rank, the ranks' item sums exchanged
     inside the launch through IPC-mapped buffers (`connect_peers`) instead of one all-reduce per factor. Opt-in:
-    the path has been tested with the ranks side by side on one GPU only."""
+    the path has been tested with the ranks side by side on one GPU only. (Gibbs only: the variational estimators ignore it.)"""
     import os
 
     import torch.distributed as dist

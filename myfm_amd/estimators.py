@@ -250,9 +250,20 @@ class _FMEstimatorBase:
 
             from . import distributed as _dist
 
-            if self._variational:
-                if _dist.active():
-                    raise NotImplementedError("row-sharded variational inference is not supported")
+            if self._variational and _dist.active():
+                # row-sharded: the same data on every rank, each trains on its contiguous slice of the rows as they come
+                # (VB does not re-sort them), with the level schedule of the whole expanded design
+                rank, world = _dist.rank_world()
+                n = X.shape[0]
+                lo, hi = _dist.row_range(n, rank, world)
+                levels = _myfm.vb_column_levels(X, list(X_rel))
+                rel_l = [RelationBlock(r.original_to_block_array[lo:hi], r.data) for r in X_rel]
+                y_l = np.ascontiguousarray(np.asarray(y, dtype=REAL)[lo:hi])
+                kw = {k: v for k, v in _dist.comm_kwargs().items() if k != "peer_connect"}  # (a Gibbs path)
+                self.predictor_, self.history_ = _myfm.create_train_vfm_sharded(
+                    self.rank, self.init_stdev, X[lo:hi], rel_l, y_l, self.random_seed, config, wrapped, rank, world, n, lo,
+                    levels, **kw)
+            elif self._variational:
                 self.predictor_, self.history_ = _myfm.create_train_vfm(
                     self.rank, self.init_stdev, X, list(X_rel), np.ascontiguousarray(y, dtype=REAL), self.random_seed, config,
                     wrapped)
