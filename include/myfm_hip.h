@@ -146,6 +146,17 @@ int mfm_plan_info(const mfm_ctx *ctx, int64_t *n_levels_main, int64_t *n_launche
  * bit 10 = a relation block's feature chain (FMTrainer.hpp:276-302, :419-470) runs as the streamed one-launch form,
  * bit 11 = the persistent sweep holds more rows per CU than fit on chip (the rest of the residual is streamed every sweep). */
 int mfm_plan_flags(const mfm_ctx *ctx);
+/* The persistent sweep's slot layout (csrc/mfm_res.hpp, ResPlan) as mfm_finalize left it, for diagnostics and for tests that must
+ * prove which layout edge they reached. Reads host-side fields only: no launch, no synchronisation. out[i], i < n_out:
+ *   0 ready (the layout was taken), 1 G (workgroups), 2 RV / 3 RL / 4 RX (slots per thread in registers / in LDS / streamed from
+ *   global memory), 5 umax (stride of the per-wave accumulator arrays), 6 n_items, 7 item_bits, 8 n_runs ((workgroup, item) pairs),
+ *   9 the most first-level columns any workgroup draws, 10 the most items any slice draws, 11 where the residual is now
+ *   (0 row order, 1 slot order, 2 slot order with its sums from mfm_update_e_regression, 3 cell order, 4 not stored: recomputed on
+ *   demand), 12 the rows the layout was planned for; entries beyond MFM_RES_INFO_FIELDS are 0. Fields 1-10 are those of the last
+ *   layout the planner tried: after a refusal the ones it had not reached keep their earlier values (0 in a fresh context).
+ * why (why_len bytes, NUL-terminated, may be NULL with why_len 0): the planner's refusal text when not ready, else empty. */
+#define MFM_RES_INFO_FIELDS 13
+int mfm_res_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why_len);
 
 /* ---- model state (FM.hpp:164-168) ------------------------------------------------------ */
 int mfm_set_state(mfm_ctx *ctx, double w0, const double *w, const double *V);

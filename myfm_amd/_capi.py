@@ -20,7 +20,7 @@ TASK_REGRESSION, TASK_CLASSIFICATION, TASK_ORDERED = 0, 1, 2
 SYMBOLS = [
     "mfm_version", "mfm_device_count", "mfm_global_error", "mfm_create", "mfm_destroy", "mfm_last_error",
     "mfm_set_stream", "mfm_synchronize", "mfm_set_main", "mfm_add_block", "mfm_set_groups", "mfm_finalize",
-    "mfm_peer_info", "mfm_peer_set", "mfm_peer_model_info", "mfm_peer_set_model", "mfm_peer_export", "mfm_peer_import", "mfm_peer_drop", "mfm_set_residual_policy", "mfm_dim_all", "mfm_plan_info", "mfm_plan_flags", "mfm_set_state", "mfm_get_state", "mfm_set_w0", "mfm_zero_w", "mfm_get_e",
+    "mfm_peer_info", "mfm_peer_set", "mfm_peer_model_info", "mfm_peer_set_model", "mfm_peer_export", "mfm_peer_import", "mfm_peer_drop", "mfm_set_residual_policy", "mfm_dim_all", "mfm_plan_info", "mfm_plan_flags", "mfm_res_info", "mfm_set_state", "mfm_get_state", "mfm_set_w0", "mfm_zero_w", "mfm_get_e",
     "mfm_get_q", "mfm_set_e", "mfm_reduce_e", "mfm_shift_e", "mfm_group_stats_w", "mfm_group_stats_V",
     "mfm_sweep_w", "mfm_sweep_V", "mfm_sweep_wV", "mfm_update_e_regression", "mfm_update_e_classification", "mfm_score_train",
     "mfm_oprobit_add_group", "mfm_oprobit_eval", "mfm_oprobit_sample_z", "mfm_hyper_stats", "mfm_timing_enable", "mfm_timing_select", "mfm_timing_reset",
@@ -85,6 +85,7 @@ def lib():
     L.mfm_dim_all.argtypes = [vp]
     L.mfm_plan_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.mfm_plan_flags.argtypes = [vp]
+    L.mfm_res_info.argtypes = [vp, P, C.c_int, C.c_char_p, C.c_int]
     L.mfm_set_state.argtypes = [vp, dbl, P, P]
     L.mfm_get_state.argtypes = [vp, C.POINTER(dbl), P, P]
     L.mfm_set_w0.argtypes = [vp, dbl]
@@ -435,6 +436,22 @@ class Context:
         f = lib().mfm_plan_flags(self.h)
         return {"qfree": bool(f & 1), "unit": bool(f & 2), "ell": bool(f & 4), "sharded": bool(f & 8), "soa": bool(f & 16),
                 "fused_next": bool(f & 32), "sharded_fused": bool(f & 64), "mf": bool(f & 128), "resident": bool(f & 256), "cell": bool(f & 512), "streamed_chain": bool(f & 1024), "resident_overflow": bool(f & 2048)}
+
+    RES_INFO = ("ready", "G", "RV", "RL", "RX", "umax", "n_items", "item_bits", "n_runs", "max_wg_users", "max_slice_items",
+                "e_where", "n_rows")
+    E_WHERE = ("rows", "slots", "slots_with_sums", "cell", "dropped")
+
+    def res_info(self):
+        """the persistent sweep's layout (mfm_res_info): the RES_INFO fields as ints, `ready` as a bool, `e_where` as one of
+        E_WHERE, and `why`, the planner's refusal text ('' when the layout was taken)"""
+        out = np.zeros(len(self.RES_INFO), dtype=np.int64)
+        why = C.create_string_buffer(256)
+        self._ck(lib().mfm_res_info(self.h, _p(out), out.shape[0], why, len(why)))
+        d = dict(zip(self.RES_INFO, (int(v) for v in out)))
+        d["ready"] = bool(d["ready"])
+        d["e_where"] = self.E_WHERE[d["e_where"]]
+        d["why"] = why.value.decode()
+        return d
 
     def plan_info(self):
         a, b = C.c_int64(), C.c_int64()

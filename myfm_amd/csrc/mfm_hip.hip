@@ -219,8 +219,10 @@ struct mfm_ctx {
   bool two_field() const { return v_path == VPath::TwoField || v_path == VPath::ShardedTwoField; }  // run_sweep_mf: no q-cache in HBM
   ResPlan res;                  // ... as one persistent launch with the residual resident on chip (mfm_res.hpp)
   // The persistent sweep is an overlay on the forms whose tables it can take: it is switched on at mfm_finalize or by mfm_peer_set
-  // and off by drop_resident, and update_V asks here whether it runs.
-  bool resident_V() const { return res.ready && v_path != VPath::QFree && v_path != VPath::Generic && v_path != VPath::Cell; }
+  // and off by drop_resident, and update_V asks here whether it runs. A layout that is ready runs whatever form the generic plans of
+  // the same table took (a one-row table's are VPath::Generic): mfm_sweep_V and mfm_sweep_wV take the same launch, with the plans
+  // built (MFM_PLAN_CHECK, or after ensure_main_plans) and without. (No layout is ever built beside QFree or Cell.)
+  bool resident_V() const { return res.ready; }
   std::vector<DevBuf<int32_t>> pre_maps;  // the blocks' maps uploaded ahead of the blocks (mfm_finalize only)
   // regression: outside the sweeps the residual IS score - y (update_e recomputes it after every update_V, FMTrainer.hpp:494), so
   // the persistent launch need not write its copy back (mfm_set_residual_policy); whoever asks for it in between gets it recomputed
@@ -1746,6 +1748,21 @@ int mfm_plan_flags(const mfm_ctx *ctx) {
   }
   return (streamed ? 1024 : 0) | (ctx->res.ready && ctx->res.RX > 0 ? 2048 : 0) | form | (ctx->X.unit ? 2 : 0) | (ctx->X.ell_width >= 0 ? 4 : 0) |
          (ctx->comm.active() ? 8 : 0) | (ctx->res.ready ? 256 : 0) | (ctx->cell.ready ? 512 : 0);
+}
+
+// The persistent sweep's layout as the planner left it (host-side fields only: no launch, no synchronisation)
+int mfm_res_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why_len) {
+  if (!ctx || n_out < 0 || (n_out > 0 && !out) || why_len < 0 || (why_len > 0 && !why)) return MFM_ERR_INVALID;
+  const ResPlan &rp = ctx->res;
+  const int64_t v[MFM_RES_INFO_FIELDS] = {rp.ready ? 1 : 0, rp.G,       rp.RV,     rp.RL,           rp.RX,
+                                          rp.umax,          rp.n_items, rp.item_bits, rp.n_runs,    rp.max_wg_users,
+                                          rp.max_slice_items, (int64_t)ctx->e_where, rp.n_rows};
+  for (int i = 0; i < n_out; i++) out[i] = i < MFM_RES_INFO_FIELDS ? v[i] : 0;
+  if (why_len > 0) {
+    std::strncpy(why, rp.ready ? "" : rp.why.c_str(), (size_t)why_len - 1);
+    why[why_len - 1] = 0;
+  }
+  return MFM_OK;
 }
 
 // ---- state ------------------------------------------------------------------------------------

@@ -1135,7 +1135,8 @@ struct ResPlan {
   DevBuf<int32_t> run_feat, wg_fill;  // feature of every run (-1: pad run); rows of every workgroup
   DevBuf<double> y_slots;             // y in slot order, built at the first scoring
   DevBuf<double2> sums;               // [G] {sum e, sum e^2} of the last scoring
-  int maxu_rows = 0;                  // users of the largest workgroup (+ the pad user)
+  int max_wg_users = 0, max_slice_items = 0;  // first-level columns drawn by the largest workgroup (the never-occurring ones it is
+                                              // dealt included), items of the largest slice (diagnostics: mfm_res_info)
   // row-sharded: this rank's exchange array and flags (allocated with the layout), every rank's (mfm_peer_set), sweeps so far
   int xworld = 1, xrank = 0;
   bool peers_set = false;
@@ -1225,6 +1226,7 @@ struct ResPlan {
           hi_u = std::max(hi_u, lo_u + 1);
           // leave at least one user for each of the remaining workgroups
           hi_u = std::min<int64_t>(hi_u, n_users - (Gw - g));
+          hi_u = std::max<int64_t>(hi_u, n_users - (Gw - g) * NT);  // ... and at most NT for each of them (a thread draws a user)
           while (hi_u > lo_u + 1 && ustart[hi_u] - ustart[lo_u] > cap) hi_u--;
         }
         if (hi_u <= lo_u || ustart[hi_u] - ustart[lo_u] > cap) ok = false;
@@ -1259,6 +1261,7 @@ struct ResPlan {
             if (hi_u + 1 <= n_users && ustart[hi_u + 1] - want < want - ustart[hi_u]) hi_u++;
             hi_u = std::max(hi_u, lo_u + 1);
             hi_u = std::min<int64_t>(hi_u, n_users - (Gw - g));
+            hi_u = std::max<int64_t>(hi_u, n_users - (Gw - g) * NT);
             while (hi_u > lo_u + 1 && ustart[hi_u] - ustart[lo_u] > cap) hi_u--;
           }
           if (hi_u <= lo_u || ustart[hi_u] - ustart[lo_u] > cap) ok = false;
@@ -1375,6 +1378,7 @@ struct ResPlan {
     for (size_t k = 0; k < empties.size(); k++) wg_users[k % G].push_back(empties[k]);
     int maxu = 0;
     for (int g = 0; g < G; g++) maxu = std::max(maxu, (int)wg_users[g].size());
+    max_wg_users = maxu;
     if (maxu > NT) return fail("more first-level columns in a workgroup than threads");
     item_bits = bits_for((int64_t)n_items + 1);
     // slots: per workgroup the rows in (item, row) order
@@ -1467,6 +1471,7 @@ struct ResPlan {
     if (!choose_item_slices(h_slot_ptr, counter, h_iptr)) return false;
     int imax = 0;
     for (int g = 0; g < G; g++) imax = std::max(imax, h_iptr[g + 1] - h_iptr[g]);
+    max_slice_items = imax;
     umax = std::max(maxu, imax) + 1;  // stride of the per-wave accumulator arrays; the pad user is umax - 1
     if (umax > 1024) return fail("internal: user field");
     std::vector<uint32_t> h_uidw((size_t)G * UW * NT, 0);

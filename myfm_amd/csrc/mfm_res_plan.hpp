@@ -396,6 +396,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
     maxu = std::max(maxu, nu);
     h_uptr[g + 1] = h_uptr[g] + nu;
   }
+  rpn.max_wg_users = maxu;
   if (maxu > NT) return rpn.fail("more first-level columns in a workgroup than threads");
   rpn.item_bits = ResPlan::bits_for((int64_t)n_items + 1);
   const int gbits = ResPlan::bits_for(G);
@@ -455,6 +456,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
   if (!rpn.choose_item_slices(h_slot_ptr, counter, h_iptr)) return false;
   int imax = 0;
   for (int g = 0; g < G; g++) imax = std::max(imax, h_iptr[g + 1] - h_iptr[g]);
+  rpn.max_slice_items = imax;
   rpn.umax = std::max(maxu, imax) + 1;
   if (rpn.umax > 1024) return rpn.fail("internal: user field");
   const int UW = 5 * (R / 16), HW = R / 16;
@@ -528,7 +530,8 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
 // tests (MFM_PLAN_CHECK): every array of the device-built layout against the host-built one
 static inline std::string res_plan_compare(const ResPlan &a, const ResPlan &b, hipStream_t s) {
   if (a.G != b.G || a.RV != b.RV || a.RL != b.RL || a.RX != b.RX || a.umax != b.umax || a.item_bits != b.item_bits || a.n_items != b.n_items ||
-      a.n_rows != b.n_rows || a.n_runs != b.n_runs || a.lds_bytes != b.lds_bytes)
+      a.n_rows != b.n_rows || a.n_runs != b.n_runs || a.lds_bytes != b.lds_bytes || a.max_wg_users != b.max_wg_users ||
+      a.max_slice_items != b.max_slice_items)
     return "scalars";
   auto same = [&](const void *p, size_t np, const void *q, size_t nq, size_t elem) {
     if (np != nq) return false;

@@ -258,7 +258,7 @@ def test_split_layout_latent_sweep(oracle, capi, monkeypatch, n_fields, fused):
 def test_resident_latent_sweep(oracle, capi, monkeypatch, cus):
     # update_V of a two-field one-hot table as ONE persistent launch (mfm_res.hpp): a workgroup per CU keeps the residual of
     # its users' rows in registers / LDS for all factors, item statistics leave the CU once per (workgroup, item), grid
-    # barriers around the item draw. cus = CUs the planner may use: all (8 slots per thread, ~37 workgroups), 12 (32 slots per
+    # barriers around the item draw. cus = CUs the planner may use: all (16 slots per thread, ~21 workgroups), 12 (32 slots per
     # thread), 4 (64 register + 16 LDS slots per thread), 1 (a single workgroup: no second arrival at the barriers).
     # Against the oracle draw for draw; a second context reproduces the chain bit for bit.
     monkeypatch.setenv("MFM_SCATTER_MIN_NNZ", "1000")
