@@ -361,6 +361,37 @@ int mfm_store_get(mfm_store *st, int32_t idx, double *w0, double *w, double *V);
 int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t n_cut,
                              const double *cutpoints, double *out);
 
+/* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
+ * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), no relation blocks; pair (u, i) is the
+ * design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column
+ * ..."): the score then splits into per-side terms and one dense contraction, which runs on the fp64 MFMA. The arguments are
+ * checked before the device is looked for, so a machine without a GPU gets MFM_ERR_INVALID for bad ones and MFM_ERR_DEVICE
+ * otherwise. The handle's last error: the one of the pairs entry points (NULL: of the last failed create of this thread).
+ *   mode 0: value(u, i) = mean_s score_s(u, i);  mode 1: mean_s Phi(score_s(u, i))   (as the prediction entry points above)
+ *   scores: out[U * I] row-major = value(u, i).
+ *   topk:   per query row the k (1 <= k <= 256) candidates of largest value, ordered by (value descending, candidate index
+ *           ascending); idx[U * k], score[U * k] row-major, a tail of idx -1 / score -inf where fewer than k candidates remain.
+ *           The pairs stored in the exclusion pattern (CSR pattern (U, I), NULL indptr: none) are left out.
+ *   *_store: over samples [first, first + count) of a device store read in place; the others take host samples laid out as
+ *           for the host-sample prediction entry point (w0s[S], ws[S * D], Vs[S * D * K], each V column-major (D, K)).
+ * Memory: the candidate side's embedding (I x S x K doubles, padded) is resident for the call and refused when it exceeds
+ * MFM_STORE_MAX_FRACTION of the free device memory; the queries are walked in chunks whose scratch stays under the scratch
+ * bound (256 MB by default, never less than one 64-row tile).                                                            */
+typedef struct mfm_pairs mfm_pairs;
+int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, const int32_t *q_indices, const double *q_data,
+                     int64_t I, const int64_t *c_indptr, const int32_t *c_indices, const double *c_data, mfm_pairs **out);
+void mfm_pairs_destroy(mfm_pairs *p);
+const char *mfm_pairs_last_error(const mfm_pairs *p);
+int mfm_pairs_set_exclude(mfm_pairs *p, const int64_t *indptr, const int32_t *indices);
+int mfm_pairs_set_scratch_bound(mfm_pairs *p, int64_t bytes);
+int mfm_pairs_scores_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, double *out);
+int mfm_pairs_topk_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int64_t *idx,
+                         double *score);
+int mfm_pairs_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                     int32_t mode, double *out);
+int mfm_pairs_topk(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                   int32_t mode, int32_t k, int64_t *idx, double *score);
+
 /* FM::predict_score of the LIVE sample (the FM* handed to the per-iteration callback,
  * FMTrainer.hpp:78; utils/callbacks/libfm.py:85): scores design `d` with the (w0, w, V) currently
  * resident in training context `ctx` -- no download / upload of the model state. Same device only.  */

@@ -23,6 +23,7 @@ HIP_UNITS = {
     "mfm_cell.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_cell.hpp"],
     "mfm_chain.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_policies.hpp", "mfm_chain_api.hpp", "mfm_chain_plan.hpp", "mfm_chain_stream.hpp"],
     "mfm_vb.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_erfcx.hpp", "mfm_vb.hpp", "mfm_comm.hpp"],
+    "mfm_pairs.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_pairs.hpp"],
 }
 OBJ_DIR = os.path.join(CSRC, "_obj")
 PYMOD_HEADERS = ["mfm_env.hpp", "mfm_hostnormals.hpp", "mfm_mtjump.hpp"]

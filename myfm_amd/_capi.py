@@ -38,6 +38,8 @@ SYMBOLS = [
     "mfm_vb_sweep_V", "mfm_vb_group_stats", "mfm_vb_synchronize", "mfm_vb_truncated_normal",
     "mfm_vb_set_stream", "mfm_vb_set_allreduce", "mfm_vb_set_shard", "mfm_vb_comm_init", "mfm_vb_comm_stats", "mfm_vb_set_levels",
     "mfm_vb_design_levels",
+    "mfm_pairs_create", "mfm_pairs_destroy", "mfm_pairs_last_error", "mfm_pairs_set_exclude", "mfm_pairs_set_scratch_bound",
+    "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk",
 ]
 
 _lib = None
@@ -158,6 +160,17 @@ def lib():
     L.mfm_store_push_host.argtypes = [vp, dbl, P, P]
     L.mfm_store_get.argtypes = [vp, i32, C.POINTER(dbl), P, P]
     L.mfm_design_predict_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P]
+    L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
+    L.mfm_pairs_destroy.argtypes = [vp]
+    L.mfm_pairs_destroy.restype = None
+    L.mfm_pairs_last_error.restype = C.c_char_p
+    L.mfm_pairs_last_error.argtypes = [vp]
+    L.mfm_pairs_set_exclude.argtypes = [vp, P, P]
+    L.mfm_pairs_set_scratch_bound.argtypes = [vp, i64]
+    L.mfm_pairs_scores_store.argtypes = [vp, vp, i32, i32, i32, P]
+    L.mfm_pairs_topk_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P]
+    L.mfm_pairs_scores.argtypes = [vp, i32, i32, P, P, P, i32, P]
+    L.mfm_pairs_topk.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P]
     L.mfm_test_erfcx.argtypes = [C.c_int, P, i64, P]
     L.mfm_test_truncated_normal.argtypes = [C.c_int, i32, dbl, dbl, u64, u64, i64, P]
     _lib = L
@@ -591,3 +604,85 @@ class Store:
         if rc:
             _raise(rc, lib().mfm_design_last_error(design.h))
         return out
+
+
+def _pack_samples(samples):
+    """list of (w0, w[D], V[D, K]) -> K, S, w0s, ws, Vs in the layout of the host-sample entry points"""
+    S = len(samples)
+    K = np.asarray(samples[0][2]).shape[1] if S else 0
+    w0s = _f64([s[0] for s in samples])
+    ws = _f64(np.stack([np.asarray(s[1], dtype=np.float64) for s in samples])) if S else np.empty(0)
+    Vs = _f64(np.stack([np.asarray(s[2], dtype=np.float64).T for s in samples])) if S else np.empty(0)
+    return K, S, w0s, ws, Vs
+
+
+class Pairs:
+    """Query x candidate scoring (mfm_pairs_*): both sides (U, D) / (I, D) sparse in the model's feature space, no column in
+    both. `exclude`: optional (U, I) sparse pattern of pairs the top-k leaves out. `scratch_bound`: bytes of query-side
+    scratch per chunk of queries (default 256 MB; a small value makes a small table cross the chunking)."""
+
+    def __init__(self, X_query, X_cand, exclude=None, scratch_bound=None, device=0):
+        L = lib()
+        h = C.c_void_p()
+        Xq, qp, qx, qv = csr_parts(X_query)
+        Xc, cp, cx, cv = csr_parts(X_cand)
+        if Xq.shape[1] != Xc.shape[1]:
+            raise ValueError("X_query and X_cand differ in width")
+        rc = L.mfm_pairs_create(device, Xq.shape[1], Xq.shape[0], _p(qp), _p(qx), _p(qv), Xc.shape[0], _p(cp), _p(cx), _p(cv),
+                                C.byref(h))
+        if rc:
+            _raise(rc, L.mfm_pairs_last_error(None))
+        self.h, self.U, self.I, self.D = h, Xq.shape[0], Xc.shape[0], Xq.shape[1]
+        if exclude is not None:
+            E = sps.csr_matrix(exclude)
+            if E.shape != (self.U, self.I):
+                self.close()
+                raise ValueError("exclude must have shape (n_queries, n_candidates)")
+            ep = np.ascontiguousarray(E.indptr, dtype=np.int64)
+            ex = np.ascontiguousarray(E.indices, dtype=np.int32)
+            self._ck(L.mfm_pairs_set_exclude(h, _p(ep), _p(ex)))
+        if scratch_bound is not None:
+            self._ck(L.mfm_pairs_set_scratch_bound(h, int(scratch_bound)))
+
+    def _ck(self, rc):
+        if rc:
+            _raise(rc, lib().mfm_pairs_last_error(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mfm_pairs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scores(self, samples, mode=0):
+        """(U, I) mean score (mode 0) or mean Phi(score) (mode 1); samples: list of (w0, w[D], V[D, K])"""
+        K, S, w0s, ws, Vs = _pack_samples(samples)
+        out = np.empty((self.U, self.I))
+        self._ck(lib().mfm_pairs_scores(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, _p(out)))
+        return out
+
+    def topk(self, samples, k, mode=0):
+        """(indices int64 (U, k), values (U, k)) ordered by (value descending, index ascending); tail -1 / -inf"""
+        K, S, w0s, ws, Vs = _pack_samples(samples)
+        kk = max(int(k), 1)
+        idx, val = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk))
+        self._ck(lib().mfm_pairs_topk(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, int(k), _p(idx), _p(val)))
+        return idx, val
+
+    def scores_store(self, store, mode=0, first=0, count=None):
+        count = len(store) - first if count is None else count
+        out = np.empty((self.U, self.I))
+        self._ck(lib().mfm_pairs_scores_store(self.h, store.h, first, count, mode, _p(out)))
+        return out
+
+    def topk_store(self, store, k, mode=0, first=0, count=None):
+        count = len(store) - first if count is None else count
+        kk = max(int(k), 1)
+        idx, val = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk))
+        self._ck(lib().mfm_pairs_topk_store(self.h, store.h, first, count, mode, int(k), _p(idx), _p(val)))
+        return idx, val

@@ -374,6 +374,23 @@ struct DeviceStore {
   int size() const { return mfm_store_size(st); }
 };
 
+// Two sparse sides resident on the GPU for the duration of one pair-scoring call (include/myfm_hip.h "query x candidate scoring").
+struct DevicePairs {
+  mfm_pairs *p = nullptr;
+  DevicePairs(int64_t D, const Csr &Xq, const Csr &Xc) {
+    int code = mfm_pairs_create(selected_device(), D, Xq.rows, Xq.indptr.data(), Xq.indices.data(), Xq.data.data(), Xc.rows,
+                                Xc.indptr.data(), Xc.indices.data(), Xc.data.data(), &p);
+    if (code != MFM_OK) throw_code(code, mfm_pairs_last_error(nullptr));
+  }
+  ~DevicePairs() {
+    if (p) mfm_pairs_destroy(p);
+  }
+  DevicePairs(const DevicePairs &) = delete;
+  void ck(int code) const {
+    if (code != MFM_OK) throw_code(code, mfm_pairs_last_error(p));
+  }
+};
+
 // ---- FM (FM.hpp:10-172) -----------------------------------------------------------------------------
 struct FM {
   int n_factors = 0;
@@ -627,6 +644,67 @@ struct Predictor {
     py::array_t<double> out((py::ssize_t)X.rows);
     run_predict(X, rels, 0, 0, {}, out.mutable_data());
     return out;
+  }
+  // ---- query x candidate scoring (not in the reference): pair (u, i) is the design row X_query[u] + X_cand[i] ----------------
+  // everything that can be wrong with the arguments is found here, on the host, before the device is looked for
+  void check_pairs(const Csr &Xq, const Csr &Xc) const {
+    if (type == TaskType::ORDERED) throw std::runtime_error("pair scoring is not available for the ordered probit model.");
+    for (const Csr *X : {&Xq, &Xc})
+      if ((size_t)X->cols != feature_size) {
+        std::ostringstream ss;
+        ss << "Told to predict for " << X->cols << " but this->feature_size is " << feature_size;
+        throw std::invalid_argument(ss.str());
+      }
+    for (const Csr *X : {&Xq, &Xc})
+      for (int32_t j : X->indices)
+        if (j < 0 || (size_t)j >= feature_size) throw std::invalid_argument("column index out of range");
+    vector<uint8_t> seen(feature_size, 0);
+    for (int32_t j : Xq.indices) seen[(size_t)j] = 1;
+    for (int32_t j : Xc.indices)
+      if (seen[(size_t)j]) throw std::invalid_argument("X_query and X_cand share column " + std::to_string(j));
+  }
+  // idx / score: the top k; dense: all pairs (exactly one of the two forms)
+  void run_pairs(const Csr &Xq, const Csr &Xc, const Csr *exclude, int k, int64_t *idx, double *score, double *dense) const {
+    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
+    DevicePairs dp((int64_t)feature_size, Xq, Xc);
+    if (exclude) dp.ck(mfm_pairs_set_exclude(dp.p, exclude->indptr.data(), exclude->indices.data()));
+    const int mode = type == TaskType::CLASSIFICATION ? 1 : 0;
+    int first = 0;
+    if (auto st = resident(&first)) {  // the unmodified entries of the device store: in place, as run_predict
+      dp.ck(dense ? mfm_pairs_scores_store(dp.p, st->st, first, (int)samples.size(), mode, dense)
+                  : mfm_pairs_topk_store(dp.p, st->st, first, (int)samples.size(), mode, k, idx, score));
+      return;
+    }
+    vector<double> w0s, ws, Vs;
+    pack(w0s, ws, Vs);
+    dp.ck(dense ? mfm_pairs_scores(dp.p, (int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, dense)
+                : mfm_pairs_topk(dp.p, (int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, k, idx, score));
+  }
+  py::array_t<double> predict_pairs(const py::object &Xqo, const py::object &Xco) const {
+    Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
+    check_pairs(Xq, Xc);
+    if ((double)Xq.rows * (double)Xc.rows > 16777216.0)
+      throw std::invalid_argument("predict_pairs returns every pair: more than 2^24 pairs are refused, use predict_topk");
+    py::array_t<double> out({(py::ssize_t)Xq.rows, (py::ssize_t)Xc.rows});
+    run_pairs(Xq, Xc, nullptr, 0, nullptr, nullptr, out.mutable_data());
+    return out;
+  }
+  py::tuple predict_topk(const py::object &Xqo, const py::object &Xco, int64_t k, const py::object &excludeo) const {
+    Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
+    check_pairs(Xq, Xc);
+    if (k < 1 || k > 256) throw std::invalid_argument("k must be in [1, 256]");
+    Csr ex;
+    if (!excludeo.is_none()) {
+      ex = csr_from_py(excludeo);
+      if (ex.rows != Xq.rows || ex.cols != Xc.rows)
+        throw std::invalid_argument("exclude must have shape (n_queries, n_candidates)");
+      for (int32_t j : ex.indices)
+        if (j < 0 || j >= ex.cols) throw std::invalid_argument("exclude: column index out of range");
+    }
+    py::array_t<int64_t> idx({(py::ssize_t)Xq.rows, (py::ssize_t)k});
+    py::array_t<double> score({(py::ssize_t)Xq.rows, (py::ssize_t)k});
+    run_pairs(Xq, Xc, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), score.mutable_data(), nullptr);
+    return py::make_tuple(idx, score);
   }
   // predictor.hpp:78-124
   py::array_t<double> predict_parallel_oprobit(const py::object &Xo, const py::object &relso, size_t n_workers,
@@ -1902,6 +1980,15 @@ struct VPredictor {
     for (auto &s : samples) p.samples.push_back(const_cast<VFM &>(s).mean_fm());
     return p.predict(X, rels);
   }
+  Predictor mean_predictor() const {
+    Predictor p(rank, feature_size, type);
+    for (auto &s : samples) p.samples.push_back(const_cast<VFM &>(s).mean_fm());
+    return p;
+  }
+  py::array_t<double> predict_pairs(const py::object &Xq, const py::object &Xc) const { return mean_predictor().predict_pairs(Xq, Xc); }
+  py::tuple predict_topk(const py::object &Xq, const py::object &Xc, int64_t k, const py::object &exclude) const {
+    return mean_predictor().predict_topk(Xq, Xc, k, exclude);
+  }
 };
 
 struct VFMTrainer {
@@ -2392,6 +2479,8 @@ PYBIND11_MODULE(_myfm, m) {
       .def("predict", &Predictor::predict)
       .def("predict_parallel", &Predictor::predict_parallel)
       .def("predict_parallel_oprobit", &Predictor::predict_parallel_oprobit)
+      .def("predict_pairs", &Predictor::predict_pairs)
+      .def("predict_topk", &Predictor::predict_topk)
       .def(py::pickle(
           [](const Predictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {
@@ -2568,6 +2657,8 @@ PYBIND11_MODULE(_myfm, m) {
 
   py::class_<VPredictor>(m, "VariationalPredictor")
       .def("predict", &VPredictor::predict)
+      .def("predict_pairs", &VPredictor::predict_pairs)
+      .def("predict_topk", &VPredictor::predict_topk)
       .def(py::pickle(
           [](const VPredictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {

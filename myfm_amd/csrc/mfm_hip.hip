@@ -2735,3 +2735,22 @@ int mfm_host_column_levels(int64_t n_rows, int64_t n_cols, const int64_t *indptr
 #include "mfm_tasks.hpp"    // classification / ordered-probit entry points
 #include "mfm_latent_host.hpp"  // ... their exact latent draws on the device stream
 #include "mfm_predict.hpp"  // mfm_design_* entry points
+
+// the samples [first, first + count) as another translation unit reads them in place (declared in mfm_pairs.hpp; defined here, in the one unit that knows mfm_store)
+namespace mfm {
+void store_view(mfm_store *st, int first, int count, int *device, int64_t *D, int *K, std::vector<const double *> &wv,
+                std::vector<double> &w0, hipEvent_t *pushed) {
+  if (first < 0 || count < 0 || first + count > (int)st->wv.size()) throw Error(MFM_ERR_INVALID, "sample range out of bounds");
+  *device = st->device;
+  *D = st->D;
+  *K = st->K;
+  wv.resize((size_t)count);
+  w0.resize((size_t)count);
+  for (int k = 0; k < count; k++) {
+    wv[(size_t)k] = st->wv[(size_t)(first + k)]->p;
+    w0[(size_t)k] = st->w0[(size_t)(first + k)];
+  }
+  *pushed = st->pushed_valid ? st->pushed : nullptr;
+}
+}  // namespace mfm
+

@@ -1,0 +1,377 @@
+// mfm_pairs.hip -- mfm_pairs_*: scores of every (query row, candidate row) pair of two sparse sides under the posterior samples, dense
+// or as the per-query top-k, on the fp64 MFMA (kernels and the decomposition: mfm_pairs.hpp).
+//
+// Memory rule. The candidate side's embedding Q (padded candidates x samples x padded factors doubles) and its biases stay resident
+// for the whole call; they are refused, before anything is allocated, when they exceed MFM_STORE_MAX_FRACTION (default 0.5) of the
+// free device memory. The queries are walked in chunks of rows whose scratch -- P and the biases, the exclusion bitmask, the
+// per-stripe lists at the most stripes a launch can have, the outputs -- stays under `scratch_bound` bytes (256 MB unless
+// mfm_pairs_set_scratch_bound says otherwise; never less than one 64-row tile).
+#include "mfm_pairs.hpp"
+
+#include <cmath>
+#include <memory>
+
+using namespace mfm;
+
+struct mfm_pairs {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  int64_t D = 0, U = 0, I = 0;
+  DevBuf<int64_t> q_ptr, c_ptr, e_ptr;
+  DevBuf<int32_t> q_idx, c_idx, e_idx;
+  DevBuf<double> q_val, c_val;
+  std::vector<int64_t> e_ptr_host;  // (the exclusions of a chunk are counted on the host)
+  bool has_exclude = false;
+  int64_t scratch_bound = (int64_t)256 << 20;
+  ~mfm_pairs() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+  void use_device() { MFM_HIP_CHECK(hipSetDevice(device)); }
+};
+
+static thread_local std::string g_pairs_error;
+
+#define PAIRS_TRY(p) \
+  try {              \
+    (p)->use_device();
+#define PAIRS_CATCH(p)               \
+  return MFM_OK;                     \
+  }                                  \
+  catch (const mfm::Error &ex) {     \
+    (p)->err = ex.what();            \
+    return ex.code;                  \
+  }                                  \
+  catch (const std::exception &ex) { \
+    (p)->err = ex.what();            \
+    return MFM_ERR_RUNTIME;          \
+  }
+
+namespace {
+
+void check_csr(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices, const char *what) {
+  if (rows < 0 || cols < 0) throw Error(MFM_ERR_INVALID, std::string(what) + ": negative matrix shape");
+  if (indptr[0] != 0) throw Error(MFM_ERR_INVALID, std::string(what) + ": indptr[0] must be 0");
+  for (int64_t i = 0; i < rows; i++)
+    if (indptr[i + 1] < indptr[i]) throw Error(MFM_ERR_INVALID, std::string(what) + ": indptr must be non-decreasing");
+  for (int64_t p = 0; p < indptr[rows]; p++)
+    if (indices[p] < 0 || indices[p] >= cols) throw Error(MFM_ERR_INVALID, std::string(what) + ": column index out of range");
+}
+
+int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+template <class T>
+void ensure(DevBuf<T> &b, size_t n) {
+  if (b.n < std::max<size_t>(n, 1)) b.alloc(std::max<size_t>(n, 1));
+}
+
+template <int MT, int NT, int MODE, bool DENSE>
+void launch_tile_t(hipStream_t s, dim3 grid, const PairsArgs &a) {
+  const size_t lds = DENSE ? 0 : PairsSel<MT>::BYTES;
+  static DeviceOnce raised;
+  if (lds > 48 * 1024 && raised.need()) {
+    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_pairs_tile<MT, NT, MODE, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised.mark();
+  }
+  hipLaunchKernelGGL((k_pairs_tile<MT, NT, MODE, DENSE>), grid, dim3(PAIRS_WG), lds, s, a);
+}
+
+// the tile shape that serves k: the per-row buffers of MT * 16 rows x (256 / MT + 64) candidates must fit the LDS
+int tile_rows(bool dense, int k) { return dense || k <= 64 ? 64 : k <= 128 ? 32 : 16; }
+int tile_step(bool dense, int k) { return dense || k <= 64 ? 128 : k <= 128 ? 256 : 512; }
+
+void launch_tile(hipStream_t s, dim3 grid, const PairsArgs &a, int mode, bool dense) {
+#define PAIRS_LAUNCH(MT, NT, DENSE)           \
+  do {                                        \
+    if (mode == 0)                            \
+      launch_tile_t<MT, NT, 0, DENSE>(s, grid, a); \
+    else                                      \
+      launch_tile_t<MT, NT, 1, DENSE>(s, grid, a); \
+  } while (0)
+  if (dense)
+    PAIRS_LAUNCH(4, 2, true);
+  else if (a.k <= 64)
+    PAIRS_LAUNCH(4, 2, false);
+  else if (a.k <= 128)
+    PAIRS_LAUNCH(2, 4, false);
+  else
+    PAIRS_LAUNCH(1, 8, false);
+#undef PAIRS_LAUNCH
+}
+
+// The whole call. wv: the samples' device buffers (w[D] then V[K][D]); w0: theirs. dense != nullptr: (U, I) scores; else the top k.
+void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, const std::vector<double> &w0, int mode, int k,
+               int64_t *idx, double *score, double *dense) {
+  const int S = (int)wv.size();
+  if (S <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
+  if (S > 65535) throw Error(MFM_ERR_INVALID, "at most 65535 samples per call");
+  if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
+  if (mode != 0 && mode != 1) throw Error(MFM_ERR_INVALID, "bad prediction mode (0: mean score, 1: mean Phi(score))");
+  const bool is_dense = dense != nullptr;
+  if (!is_dense && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  const int64_t U = p->U, I = p->I, D = p->D;
+  if (U == 0 || (is_dense && I == 0)) return;
+  hipStream_t s = p->stream;
+  const int K = rank, KS = (K + 3) & ~3, KS4 = KS / 4;
+  const int64_t NK = (int64_t)S * KS4;
+  const int64_t Ipad = round_up(std::max<int64_t>(I, 1), PAIRS_COL_ALIGN);
+
+  // ---- the memory rule: Q resident, the query scratch bounded
+  const double q_bytes = ((double)Ipad * S * KS + (double)Ipad * (S + 1)) * sizeof(double);
+  {
+    size_t free_b = 0, total_b = 0;
+    const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && q_bytes > frac * (double)free_b)
+      throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + std::to_string((int64_t)(q_bytes / 1048576.0)) +
+                                       " MB for all samples) exceeds MFM_STORE_MAX_FRACTION of the free device memory; "
+                                       "score fewer samples or fewer candidates per call");
+  }
+  const int64_t W = (I + 31) / 32;
+  const int rows_t = tile_rows(is_dense, k), step = tile_step(is_dense, k);
+  const int64_t steps_total = (std::max<int64_t>(I, 1) + step - 1) / step;
+  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && !is_dense ? (double)W * 4 : 0.0) +
+                         (is_dense ? (double)I * 8 : (double)(PAIRS_MAX_STRIPES + 1) * k * 12);
+  int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
+  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
+  chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
+
+  // ---- the samples' pointers and w0
+  DevBuf<const double *> d_wv;
+  DevBuf<double> d_w0;
+  d_wv.upload(wv);
+  d_w0.upload(w0);
+  double w0sum = 0.0;
+  for (int i = 0; i < S; i++) w0sum += w0[i];
+
+  // ---- candidate side, once
+  DevBuf<double> Qf, Bb, Bsum;
+  Qf.alloc((size_t)std::max<int64_t>(Ipad * NK * 4, 1));
+  Bb.alloc((size_t)Ipad * S);
+  Bsum.alloc((size_t)Ipad);
+  hipLaunchKernelGGL(k_pairs_embed, dim3((unsigned)(Ipad / PAIRS_WG), (unsigned)S), dim3(PAIRS_WG), 0, s, p->c_ptr.p, p->c_idx.p,
+                     p->c_val.p, (int64_t)0, I, Ipad, (const double *const *)d_wv.p, D, K, KS, S, Qf.p, Bb.p);
+  hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)(Ipad / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Bb.p, S, Ipad, Bsum.p);
+  MFM_HIP_CHECK(hipGetLastError());
+
+  // ---- queries, chunk by chunk
+  DevBuf<double> Pf, Ab, Asum, list_v, out_v, d_dense;
+  DevBuf<int32_t> list_i, out_i;
+  DevBuf<uint32_t> mask;
+  std::vector<int32_t> h_idx;
+  for (int64_t u0 = 0; u0 < U; u0 += chunk) {
+    const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
+    ensure(Pf, (size_t)(Upad * NK * 4));
+    ensure(Ab, (size_t)(Upad * S));
+    ensure(Asum, (size_t)Upad);
+    hipLaunchKernelGGL(k_pairs_embed, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S), dim3(PAIRS_WG), 0, s,
+                       p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, (const double *const *)d_wv.p, D, K, KS, S, Pf.p, Ab.p);
+    hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Ab.p, S, Upad,
+                       Asum.p);
+    const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
+    if (use_mask) {
+      ensure(mask, (size_t)(Uc * W));
+      MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), s));
+      hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
+    }
+    // stripes: enough workgroups to fill the device twice, at most PAIRS_MAX_STRIPES lists to merge
+    const int64_t n_qt = Upad / rows_t;
+    int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_qt - 1) / n_qt, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
+    const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
+    n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
+    PairsArgs a;
+    a.Pf = Pf.p;
+    a.Qf = Qf.p;
+    a.Ab = Ab.p;
+    a.Asum = Asum.p;
+    a.Bb = Bb.p;
+    a.Bsum = Bsum.p;
+    a.w0s = d_w0.p;
+    a.w0sum = w0sum;
+    a.NK = NK;
+    a.KS4 = KS4;
+    a.S = S;
+    a.Upad = Upad;
+    a.Ipad = Ipad;
+    a.Uc = Uc;
+    a.I = I;
+    a.stripe_len = stripe_steps * step;
+    a.mask = use_mask ? mask.p : nullptr;
+    a.W = W;
+    a.k = k;
+    a.list_v = nullptr;
+    a.list_i = nullptr;
+    a.dense = nullptr;
+    if (is_dense) {
+      ensure(d_dense, (size_t)(Uc * I));
+      a.dense = d_dense.p;
+      launch_tile(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, true);
+      MFM_HIP_CHECK(hipGetLastError());
+      MFM_HIP_CHECK(hipMemcpyAsync(dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipStreamSynchronize(s));
+      continue;
+    }
+    ensure(list_v, (size_t)(n_stripes * Upad * k));
+    ensure(list_i, (size_t)(n_stripes * Upad * k));
+    ensure(out_v, (size_t)(Uc * k));
+    ensure(out_i, (size_t)(Uc * k));
+    a.list_v = list_v.p;
+    a.list_i = list_i.p;
+    if (I > 0) {
+      launch_tile(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, false);
+      MFM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, k,
+                       out_v.p, out_i.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    h_idx.resize((size_t)(Uc * k));
+    MFM_HIP_CHECK(hipMemcpyAsync(score + (size_t)u0 * k, out_v.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), out_i.p, (size_t)(Uc * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipStreamSynchronize(s));
+    for (int64_t e = 0; e < Uc * k; e++) idx[u0 * k + e] = h_idx[(size_t)e];
+  }
+  MFM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense) {
+  if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
+  if (count <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
+  int device = 0, K = 0;
+  int64_t D = 0;
+  std::vector<const double *> wv;
+  std::vector<double> w0;
+  hipEvent_t pushed = nullptr;
+  store_view(st, first, count, &device, &D, &K, wv, w0, &pushed);
+  if (device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
+  if (D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+  // the samples' device-to-device copies (training stream) must be complete: this stream waits for the latest one's event
+  if (pushed) MFM_HIP_CHECK(hipStreamWaitEvent(p->stream, pushed, 0));
+  run_pairs(p, K, wv, w0, mode, k, idx, score, dense);
+}
+
+void run_pairs_host(mfm_pairs *p, int rank, int n_samples, const double *w0s, const double *ws, const double *Vs, int mode, int k,
+                    int64_t *idx, double *score, double *dense) {
+  if (n_samples <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
+  if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
+  const size_t D = (size_t)p->D, per = std::max<size_t>(D * ((size_t)rank + 1), 1);
+  DevBuf<double> buf;  // per sample: w[D] then V[K][D], the store's layout
+  buf.alloc(per * (size_t)n_samples);
+  std::vector<const double *> wv((size_t)n_samples);
+  std::vector<double> w0(w0s, w0s + n_samples);
+  for (int i = 0; i < n_samples; i++) {
+    double *b = buf.p + per * (size_t)i;
+    if (D) MFM_HIP_CHECK(hipMemcpy(b, ws + D * (size_t)i, D * sizeof(double), hipMemcpyHostToDevice));
+    if (D && rank) MFM_HIP_CHECK(hipMemcpy(b + D, Vs + D * rank * (size_t)i, D * rank * sizeof(double), hipMemcpyHostToDevice));
+    wv[(size_t)i] = b;
+  }
+  run_pairs(p, rank, wv, w0, mode, k, idx, score, dense);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, const int32_t *q_indices, const double *q_data,
+                     int64_t I, const int64_t *c_indptr, const int32_t *c_indices, const double *c_data, mfm_pairs **out) {
+  *out = nullptr;
+  try {
+    // (the arguments first: a machine without a GPU still learns that they are wrong)
+    check_csr(U, D, q_indptr, q_indices, "X_query");
+    check_csr(I, D, c_indptr, c_indices, "X_cand");
+    if (I >= (int64_t)2147483647 - PAIRS_COL_ALIGN) throw Error(MFM_ERR_INVALID, "too many candidates");
+    {
+      std::vector<uint8_t> seen((size_t)D, 0);
+      for (int64_t q = 0; q < q_indptr[U]; q++) seen[(size_t)q_indices[q]] = 1;
+      for (int64_t q = 0; q < c_indptr[I]; q++)
+        if (seen[(size_t)c_indices[q]])
+          throw Error(MFM_ERR_INVALID, "X_query and X_cand share column " + std::to_string(c_indices[q]));
+    }
+    const int n = mfm_device_count();
+    if (n <= 0)
+      throw Error(MFM_ERR_DEVICE, "no HIP device is visible: libmyfm_hip.so has no CPU fallback (pair scoring runs on MI355X only)");
+    if (device < 0 || device >= n) throw Error(MFM_ERR_INVALID, "device index out of range");
+    std::unique_ptr<mfm_pairs> p(new mfm_pairs());
+    p->device = device;
+    p->use_device();
+    MFM_HIP_CHECK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+    p->D = D;
+    p->U = U;
+    p->I = I;
+    p->q_ptr.upload(q_indptr, (size_t)U + 1);
+    p->q_idx.upload(q_indices, (size_t)q_indptr[U]);
+    p->q_val.upload(q_data, (size_t)q_indptr[U]);
+    p->c_ptr.upload(c_indptr, (size_t)I + 1);
+    p->c_idx.upload(c_indices, (size_t)c_indptr[I]);
+    p->c_val.upload(c_data, (size_t)c_indptr[I]);
+    *out = p.release();
+    return MFM_OK;
+  } catch (const mfm::Error &ex) {
+    g_pairs_error = ex.what();
+    return ex.code;
+  } catch (const std::exception &ex) {
+    g_pairs_error = ex.what();
+    return MFM_ERR_RUNTIME;
+  }
+}
+
+void mfm_pairs_destroy(mfm_pairs *p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  if (p->stream) (void)hipStreamSynchronize(p->stream);
+  delete p;
+}
+
+const char *mfm_pairs_last_error(const mfm_pairs *p) { return p ? p->err.c_str() : g_pairs_error.c_str(); }
+
+int mfm_pairs_set_exclude(mfm_pairs *p, const int64_t *indptr, const int32_t *indices) {
+  PAIRS_TRY(p)
+  if (!indptr) {
+    p->has_exclude = false;
+    return MFM_OK;
+  }
+  check_csr(p->U, p->I, indptr, indices, "exclude");
+  p->e_ptr_host.assign(indptr, indptr + p->U + 1);
+  p->e_ptr.upload(indptr, (size_t)p->U + 1);
+  p->e_idx.upload(indices, (size_t)indptr[p->U]);
+  p->has_exclude = indptr[p->U] > 0;
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_set_scratch_bound(mfm_pairs *p, int64_t bytes) {
+  PAIRS_TRY(p)
+  if (bytes < 1) throw Error(MFM_ERR_INVALID, "the scratch bound must be positive");
+  p->scratch_bound = bytes;
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_scores_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, double *out) {
+  PAIRS_TRY(p)
+  if (!out) throw Error(MFM_ERR_INVALID, "no output array");
+  run_pairs_store(p, st, first, count, mode, 0, nullptr, nullptr, out);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int64_t *idx,
+                         double *score) {
+  PAIRS_TRY(p)
+  if (!idx || !score) throw Error(MFM_ERR_INVALID, "no output array");
+  run_pairs_store(p, st, first, count, mode, k, idx, score, nullptr);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                     int32_t mode, double *out) {
+  PAIRS_TRY(p)
+  if (!out) throw Error(MFM_ERR_INVALID, "no output array");
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, 0, nullptr, nullptr, out);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                   int32_t mode, int32_t k, int64_t *idx, double *score) {
+  PAIRS_TRY(p)
+  if (!idx || !score) throw Error(MFM_ERR_INVALID, "no output array");
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, idx, score, nullptr);
+  PAIRS_CATCH(p)
+}
+
+}  // extern "C"

@@ -310,6 +310,43 @@ class _FMEstimatorBase:
         return predictor.predict_parallel(X, list(X_rel), n_workers)
 
 
+class _PairScoringMixin:
+    """Ranking with a fitted model: scores of every (query row, candidate row) pair and the per-query top-k, computed on the
+    device without materialising the pair rows. Regressors score the posterior-mean prediction, classifiers the
+    mean over the samples of Phi(score) -- what predict / predict_proba return for the design row X_query[u] + X_cand[i]. The
+    variational estimators have one sample, the mean model.
+
+    Both arguments are sparse matrices in the model's full feature space, (U, D) and (I, D) with D the fitted feature size;
+    either side may hold empty rows, multi-hot rows and non-unit values, but no column may be stored in both (ValueError).
+    Not covered: MyFMOrderedProbit; relation-block inputs for the two sides; row-sharded operation (the model is replicated,
+    so each rank can call this on its own queries). The arguments are validated on the host before the device is touched."""
+
+    def _pair_sides(self, X_query, X_cand):
+        predictor = self._fetch_predictor()
+        if X_query is None or X_cand is None:
+            raise ValueError("X_query and X_cand must be given.")
+        return predictor, _as_csr(X_query, 0), _as_csr(X_cand, 0)
+
+    def predict_pairs(self, X_query, X_cand):
+        """(U, I) array of the value of every pair. U * I > 2^24 is refused (ValueError): use predict_topk."""
+        predictor, Xq, Xc = self._pair_sides(X_query, X_cand)
+        return predictor.predict_pairs(Xq, Xc)
+
+    def predict_topk(self, X_query, X_cand, k: int, exclude=None):
+        """Per query row the k candidates of largest value: (indices int64 (U, k), scores float64 (U, k)), each row ordered by
+        (value descending, candidate index ascending). `exclude`: optional (U, I) scipy sparse matrix whose stored positions
+        are pairs to leave out (the stored values are ignored). Where fewer than k candidates remain the tail is index -1,
+        score -inf. 1 <= k <= 256, else ValueError."""
+        predictor, Xq, Xc = self._pair_sides(X_query, X_cand)
+        if isinstance(k, bool) or int(k) != k:
+            raise ValueError("k must be an integer in [1, 256]")
+        if exclude is not None:
+            exclude = sps.csr_matrix(exclude)
+            if exclude.shape != (Xq.shape[0], Xc.shape[0]):
+                raise ValueError("exclude must have shape (n_queries, n_candidates)")
+        return predictor.predict_topk(Xq, Xc, int(k), exclude)
+
+
 class MyFMGibbsBase(_FMEstimatorBase):
     """Common part of the Gibbs estimators (base.py:70-323 + gibbs.py:32-142)."""
 
@@ -356,7 +393,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -386,7 +423,7 @@ class MyFMGibbsRegressor(MyFMGibbsBase):
         return self._predict_core(X, X_rel, n_workers=n_workers)
 
 
-class MyFMGibbsClassifier(MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -544,7 +581,7 @@ class MyFMVariationalBase(_FMEstimatorBase):
         return self
 
 
-class VariationalFMRegressor(MyFMVariationalBase):
+class VariationalFMRegressor(_PairScoringMixin, MyFMVariationalBase):
     """Bayesian FM regression by mean-field variational inference (variational.py:170-265)."""
 
     # the task hooks of the regression estimators (the two families are siblings, as in the reference)
@@ -562,7 +599,7 @@ class VariationalFMRegressor(MyFMVariationalBase):
         return self._predict_core(X, X_rel)
 
 
-class VariationalFMClassifier(MyFMVariationalBase):
+class VariationalFMClassifier(_PairScoringMixin, MyFMVariationalBase):
     """Bayesian FM probit classification by mean-field variational inference (variational.py:268-383)."""
 
     _task_type = TaskType.CLASSIFICATION
