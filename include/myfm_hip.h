@@ -157,6 +157,23 @@ int mfm_plan_flags(const mfm_ctx *ctx);
  * why (why_len bytes, NUL-terminated, may be NULL with why_len 0): the planner's refusal text when not ready, else empty. */
 #define MFM_RES_INFO_FIELDS 13
 int mfm_res_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why_len);
+/* The cell path's plan (csrc/mfm_cell.hpp, CellPlan: index-tuple designs) as mfm_finalize left it, for diagnostics and for tests
+ * that must prove which layout edge they reached. Reads host-side fields only: no launch, no synchronisation. out[i], i < n_out:
+ *   0 ready (the plan was taken), 1 G (groups = workgroups of a pass), 2 umax (most first-field values of one group), 3 item32 (the
+ *   scattered index is a separate int32 array), 4 n_streams, 5 n_fields, 6 N, 7 Npad (positions of the padded step layout),
+ *   8 the most steps any group takes, 9 / 10 rows of the longest / the shortest wave chunk (an empty chunk counts as 0), 11 wave
+ *   chunks without a row, 12 bit k set: update_V's pass into field k (apply the field before it, statistics of k) runs as an
+ *   apply-only launch plus a statistics-only launch because both roles do not fit the LDS together, 13 factors per pass of the
+ *   scorer (4, 2 or 1; 0 when not ready);
+ *   14 + 3 s ..: stream s < 4: type (0 U: sorted first field, 1 I: the scattered stream, 2 C: whole table in LDS), its 16-bit slot of
+ *   the row record (-1: the int32 array), its cardinality;   26 + 3 k ..: field k < 16 in Gibbs order: its stream, its kind (0 one-hot
+ *   main field, 1 relation block), its columns / block rows. Entries of streams and fields that do not exist, and entries beyond
+ *   MFM_CELL_INFO_FIELDS, are 0. The fields are those of the last plan the planner tried: after a refusal the ones it had not
+ *   reached keep their earlier values (0 in a fresh context, and in one whose design the cell path was never tried on).
+ * why (why_len bytes, NUL-terminated, may be NULL with why_len 0): the planner's refusal text when not ready (empty when the cell
+ * path was not tried), else empty. */
+#define MFM_CELL_INFO_FIELDS 74
+int mfm_cell_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why_len);
 
 /* ---- model state (FM.hpp:164-168) ------------------------------------------------------ */
 int mfm_set_state(mfm_ctx *ctx, double w0, const double *w, const double *V);

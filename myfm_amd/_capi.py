@@ -20,7 +20,7 @@ TASK_REGRESSION, TASK_CLASSIFICATION, TASK_ORDERED = 0, 1, 2
 SYMBOLS = [
     "mfm_version", "mfm_device_count", "mfm_global_error", "mfm_create", "mfm_destroy", "mfm_last_error",
     "mfm_set_stream", "mfm_synchronize", "mfm_set_main", "mfm_add_block", "mfm_set_groups", "mfm_finalize",
-    "mfm_peer_info", "mfm_peer_set", "mfm_peer_model_info", "mfm_peer_set_model", "mfm_peer_export", "mfm_peer_import", "mfm_peer_drop", "mfm_set_residual_policy", "mfm_dim_all", "mfm_plan_info", "mfm_plan_flags", "mfm_res_info", "mfm_set_state", "mfm_get_state", "mfm_set_w0", "mfm_zero_w", "mfm_get_e",
+    "mfm_peer_info", "mfm_peer_set", "mfm_peer_model_info", "mfm_peer_set_model", "mfm_peer_export", "mfm_peer_import", "mfm_peer_drop", "mfm_set_residual_policy", "mfm_dim_all", "mfm_plan_info", "mfm_plan_flags", "mfm_res_info", "mfm_cell_info", "mfm_set_state", "mfm_get_state", "mfm_set_w0", "mfm_zero_w", "mfm_get_e",
     "mfm_get_q", "mfm_set_e", "mfm_reduce_e", "mfm_shift_e", "mfm_group_stats_w", "mfm_group_stats_V",
     "mfm_sweep_w", "mfm_sweep_V", "mfm_sweep_wV", "mfm_update_e_regression", "mfm_update_e_classification", "mfm_score_train",
     "mfm_oprobit_add_group", "mfm_oprobit_eval", "mfm_oprobit_sample_z", "mfm_hyper_stats", "mfm_timing_enable", "mfm_timing_select", "mfm_timing_reset",
@@ -88,6 +88,7 @@ def lib():
     L.mfm_plan_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.mfm_plan_flags.argtypes = [vp]
     L.mfm_res_info.argtypes = [vp, P, C.c_int, C.c_char_p, C.c_int]
+    L.mfm_cell_info.argtypes = [vp, P, C.c_int, C.c_char_p, C.c_int]
     L.mfm_set_state.argtypes = [vp, dbl, P, P]
     L.mfm_get_state.argtypes = [vp, C.POINTER(dbl), P, P]
     L.mfm_set_w0.argtypes = [vp, dbl]
@@ -463,6 +464,29 @@ class Context:
         d = dict(zip(self.RES_INFO, (int(v) for v in out)))
         d["ready"] = bool(d["ready"])
         d["e_where"] = self.E_WHERE[d["e_where"]]
+        d["why"] = why.value.decode()
+        return d
+
+    CELL_INFO = ("ready", "G", "umax", "item32", "n_streams", "n_fields", "N", "Npad", "max_steps", "chunk_max", "chunk_min",
+                 "chunks_empty", "split_mask", "score_fb")
+    CELL_STREAM_TYPE = ("U", "I", "C")
+    CELL_MAX_STREAMS, CELL_MAX_FIELDS = 4, 16  # (csrc/mfm_cell.hpp; three entries each in mfm_cell_info's output)
+    CELL_INFO_FIELDS = len(CELL_INFO) + 3 * CELL_MAX_STREAMS + 3 * CELL_MAX_FIELDS  # MFM_CELL_INFO_FIELDS of include/myfm_hip.h
+
+    def cell_info(self):
+        """the cell path's plan (mfm_cell_info): the CELL_INFO fields as ints (`ready`, `item32` as bools), `streams`: a list of
+        (type 'U' | 'I' | 'C', record slot, cardinality), `fields`: a list of (stream, kind 0 main field | 1 block, n) in Gibbs
+        order, and `why`, the planner's refusal text ('' when the plan was taken or the cell path was not tried)"""
+        out = np.zeros(self.CELL_INFO_FIELDS, dtype=np.int64)
+        why = C.create_string_buffer(256)
+        self._ck(lib().mfm_cell_info(self.h, _p(out), out.shape[0], why, len(why)))
+        n = len(self.CELL_INFO)
+        nf = n + 3 * self.CELL_MAX_STREAMS  # where the fields' entries begin
+        d = dict(zip(self.CELL_INFO, (int(v) for v in out[:n])))
+        d["ready"], d["item32"] = bool(d["ready"]), bool(d["item32"])
+        d["streams"] = [(self.CELL_STREAM_TYPE[int(out[n + 3 * s])], int(out[n + 3 * s + 1]), int(out[n + 3 * s + 2]))
+                        for s in range(d["n_streams"])]
+        d["fields"] = [tuple(int(x) for x in out[nf + 3 * k:nf + 3 * k + 3]) for k in range(d["n_fields"])]
         d["why"] = why.value.decode()
         return d
 

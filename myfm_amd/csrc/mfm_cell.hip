@@ -54,6 +54,33 @@ size_t CellPlan::lds_bytes(int P, int F, bool sw, int *off, bool linear) const {
   return o * sizeof(double);
 }
 
+// LDS of a scorer pass (offsets in doubles): per LDS stream its table of tw doubles per index value
+size_t CellPlan::score_lds_bytes(int tw, int *off) const {
+  size_t o = 0;
+  for (size_t si = 0; si < streams.size(); si++) {
+    if (streams[si].type == CELL_I) continue;
+    if (off) off[si] = (int)o;
+    o += (size_t)tw * (streams[si].type == CELL_U ? (size_t)umax : (size_t)streams[si].card);
+    o = (o + 1) & ~(size_t)1;
+  }
+  return (o + 2) * sizeof(double);
+}
+int CellPlan::score_fb() const {
+  int FB = 4;  // (8 factors' q of 6 rows per lane do not fit 128 VGPRs)
+  while (FB > 1 && score_lds_bytes(FB) > CELL_LDS_BYTES) FB /= 2;
+  return score_lds_bytes(FB) > CELL_LDS_BYTES ? 0 : FB;
+}
+void CellPlan::set_chunk_stats(const std::vector<int32_t> &clen, const std::vector<int32_t> &steps) {
+  max_steps = 0;
+  chunk_max = chunk_min = chunks_empty = 0;
+  for (int32_t v : steps) max_steps = std::max(max_steps, (int)v);
+  for (size_t i = 0; i < clen.size(); i++) {
+    chunk_max = std::max<int64_t>(chunk_max, clen[i]);
+    chunk_min = i == 0 ? (int64_t)clen[i] : std::min<int64_t>(chunk_min, clen[i]);
+    if (clen[i] == 0) chunks_empty++;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // planner
 template <class F>
@@ -117,6 +144,8 @@ static bool cell_plan_streams(CellPlan &cp, int64_t W, const std::vector<int64_t
     cp.streams[found].fields.push_back((int)cp.fields.size());
     cp.fields.push_back(f);
   }
+  for (auto &st : cp.streams)  // (a table of a pass is the sum of its stream's fields: cell_prep adds up to four)
+    if (st.fields.size() > 4) return cp.fail("more than four fields on one index stream");
   // stream types and record slots
   cp.sU = 0;
   cp.sI = -1;
@@ -210,6 +239,7 @@ bool cell_plan_build(CellPlan &cp, const HostCsr &X, const std::vector<CellBlock
   cp.ready = false;
   cp.streams.clear();
   cp.fields.clear();
+  cp.sU = cp.sI = -1;  // (no stream has a type yet: a refusal before they are set must not show an earlier plan's)
   const int64_t N = X.rows;
   cp.N = N;
   const bool shared = (bool)sum_ranks;
@@ -452,6 +482,7 @@ bool cell_plan_build(CellPlan &cp, const HostCsr &X, const std::vector<CellBlock
   cp.grp_base.upload(gbase);
   cp.grp_u0.upload(gu0);
   cp.grp_steps.upload(steps);
+  cp.set_chunk_stats(clen, steps);
   cell_plan_buffers(cp, s);
   cp.ready = true;
   return true;
@@ -656,6 +687,7 @@ bool cell_plan_build_device(CellPlan &cp, const DevSparse &X, const std::vector<
   cp.ready = false;
   cp.streams.clear();
   cp.fields.clear();
+  cp.sU = cp.sI = -1;  // (no stream has a type yet: a refusal before they are set must not show an earlier plan's)
   const int64_t N = X.rows;
   cp.N = N;
   const bool shared = (bool)sum_ranks;
@@ -843,6 +875,8 @@ bool cell_plan_build_device(CellPlan &cp, const DevSparse &X, const std::vector<
     hipLaunchKernelGGL(k_chunk_fin, grid(G), dim3(TB), 0, s, c0.p, G, WROWS, cp.chunk_len.p, steps.p);
   }
   const std::vector<int32_t> h_steps = download(steps.p, (size_t)G, s);
+  // (diagnostics, mfm_cell_info: one more synchronous copy of G * 16 int32 at mfm_finalize, never in a sweep)
+  cp.set_chunk_stats(download(cp.chunk_len.p, (size_t)G * CELL_NW, s), h_steps);
   std::vector<int32_t> gbase((size_t)G + 1, 0);
   int64_t npad = 0;
   for (int g = 0; g < G; g++) {
@@ -1791,6 +1825,14 @@ void cell_score(hipStream_t s, Timing &tm, CellPlan &cp, const std::vector<CellS
     CellPrepArgs a;
     a.n_jobs = 0;
     int64_t maxn = 0;
+    // a job sums four terms; a stream with more than two fields has more terms of LS than that: the rest is added in
+    // continuation rounds, each (the table so far) + three more terms, in field order
+    std::vector<CellPrepArgs> more;
+    struct Term {
+      const double *p;
+      int sn;
+      double coef;
+    };
     for (size_t si = 0; si < cp.streams.size(); si++) {
       const CellStream &st = cp.streams[si];
       CellPrepJob &jq = a.job[a.n_jobs++];
@@ -1804,36 +1846,50 @@ void cell_score(hipStream_t s, Timing &tm, CellPlan &cp, const std::vector<CellS
       jl.n = (int)st.card;
       jl.nsrc = 0;
       if (st.card * KS >= (int64_t)2147483647) throw Error(MFM_ERR_RUNTIME, "cell scorer: table too large");
-      if (st.fields.size() > 2) throw Error(MFM_ERR_RUNTIME, "internal: more than two fields on one index stream");
+      if (st.fields.size() > 4) throw Error(MFM_ERR_RUNTIME, "internal: more than four fields on one index stream");
+      std::vector<Term> terms;
       for (int f : st.fields) {
         const CellField &fd = cp.fields[f];
         const CellScoreSrc &sc = src[f];
         const double *q = fd.kind == 0 ? Vt + fd.base * KS : sc.q;
-        const double *lin = sc.lin;
         const double *ss = fd.kind == 0 ? cp.vss.p + fd.base : sc.ss;
+        const int sn = (int)std::min<int64_t>(fd.n, st.card);
         if (K > 0) {
           jq.src[jq.nsrc] = q;
           jq.sstride[jq.nsrc] = 1;
-          jq.sn[jq.nsrc] = (int)(std::min<int64_t>(fd.n, st.card) * KS);
+          jq.sn[jq.nsrc] = sn * KS;
           jq.coef[jq.nsrc] = 1.0;
           jq.nsrc++;
         }
-        jl.src[jl.nsrc] = lin;
-        jl.sstride[jl.nsrc] = 1;
-        jl.sn[jl.nsrc] = (int)std::min<int64_t>(fd.n, st.card);
-        jl.coef[jl.nsrc] = 1.0;
-        jl.nsrc++;
-        if (K > 0) {
-          jl.src[jl.nsrc] = ss;
-          jl.sstride[jl.nsrc] = 1;
-          jl.sn[jl.nsrc] = (int)std::min<int64_t>(fd.n, st.card);
-          jl.coef[jl.nsrc] = -0.5;
-          jl.nsrc++;
+        terms.push_back(Term{sc.lin, sn, 1.0});
+        if (K > 0) terms.push_back(Term{ss, sn, -0.5});
+      }
+      auto put = [](CellPrepJob &j, const Term &t) {
+        j.src[j.nsrc] = t.p;
+        j.sstride[j.nsrc] = 1;
+        j.sn[j.nsrc] = t.sn;
+        j.coef[j.nsrc] = t.coef;
+        j.nsrc++;
+      };
+      size_t done = 0;
+      for (; done < terms.size() && jl.nsrc < 4; done++) put(jl, terms[done]);
+      for (size_t round = 0; done < terms.size(); round++) {
+        if (more.size() <= round) {
+          more.emplace_back();
+          more.back().n_jobs = 0;
         }
+        CellPrepJob &jc = more[round].job[more[round].n_jobs++];
+        jc.dst = jl.dst;
+        jc.dst_stride = 1;
+        jc.n = jl.n;
+        jc.nsrc = 0;
+        put(jc, Term{jl.dst, jl.n, 1.0});
+        for (; done < terms.size() && jc.nsrc < 4; done++) put(jc, terms[done]);
       }
       maxn = std::max<int64_t>(maxn, std::max<int64_t>(jq.n, jl.n));
     }
     hipLaunchKernelGGL(k_cell_prep, dim3(cdiv_c(maxn, 256), a.n_jobs), dim3(256), 0, s, a);
+    for (const CellPrepArgs &m : more) hipLaunchKernelGGL(k_cell_prep, dim3(cdiv_c(maxn, 256), m.n_jobs), dim3(256), 0, s, m);
   }
   CellScoreArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1848,28 +1904,16 @@ void cell_score(hipStream_t s, Timing &tm, CellPlan &cp, const std::vector<CellS
   a.KS = KS;
   a.w0 = w0;
   a.cardI = cp.sI >= 0 ? (int)cp.streams[cp.sI].card : 0;
-  size_t per_factor = 0;  // LDS doubles per factor of a pass
   for (int si = 0; si < a.n_streams; si++) {
     a.Q[si] = cp.scoreQ[si].p;
     a.LS[si] = cp.scoreLS[si].p;
     a.type[si] = cp.streams[si].type;
     a.slot[si] = cp.streams[si].slot;
     a.card[si] = (int)cp.streams[si].card;
-    if (a.type[si] != CELL_I) per_factor += a.type[si] == CELL_U ? (size_t)cp.umax : (size_t)cp.streams[si].card;
   }
-  auto layout = [&](int tw) {
-    size_t o = 0;
-    for (int si = 0; si < a.n_streams; si++) {
-      if (a.type[si] == CELL_I) continue;
-      a.lds_off[si] = (int)o;
-      o += (size_t)tw * (a.type[si] == CELL_U ? (size_t)cp.umax : (size_t)cp.streams[si].card);
-      o = (o + 1) & ~(size_t)1;
-    }
-    return (o + 2) * sizeof(double);
-  };
-  int FB = 4;  // (8 factors' q of 6 rows per lane do not fit 128 VGPRs)
-  while (FB > 1 && layout(FB) > CELL_LDS_BYTES) FB /= 2;
-  if (layout(1) > CELL_LDS_BYTES) throw Error(MFM_ERR_RUNTIME, "internal: cell scorer tables do not fit the LDS");
+  auto layout = [&](int tw) { return cp.score_lds_bytes(tw, a.lds_off); };
+  const int FB = cp.score_fb();
+  if (FB == 0) throw Error(MFM_ERR_RUNTIME, "internal: cell scorer tables do not fit the LDS");
   const double row_bytes = (double)cp.N * (8.0 + 8.0 + 8.0 + (cp.item32 ? 4.0 : 0.0));
   if (cp.G == 0) return;  // (an empty shard: no rows to score)
   {

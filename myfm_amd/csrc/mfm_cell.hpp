@@ -85,6 +85,10 @@ struct CellPlan {
   int sU = -1, sI = -1;
   bool item32 = false;
   int64_t umax = 0;  // most U values in one group
+  // the chunk layout as the planner left it (host copies, set by both planners at mfm_finalize; diagnostics: mfm_cell_info)
+  int max_steps = 0;                       // steps of the group with the longest chunk
+  int64_t chunk_max = 0, chunk_min = 0;    // rows of the longest / the shortest wave chunk (an empty chunk counts: 0)
+  int64_t chunks_empty = 0;                // wave chunks without a row
   std::vector<CellStream> streams;
   std::vector<CellField> fields;  // in Gibbs order: main fields, then blocks
   // rows in cell order
@@ -125,6 +129,11 @@ struct CellPlan {
   }
   bool fail(const std::string &w) { return fail(w.c_str()); }
   size_t lds_bytes(int P, int F, bool sw, int *off = nullptr, bool linear = false) const;  // LDS of the pass (P, F: field numbers or -1)
+  // update_V's pass (apply P, statistics of F) runs as two launches: both roles together do not fit the LDS
+  bool split_pass(int P, int F, bool sw) const { return P >= 0 && F >= 0 && lds_bytes(P, F, sw) > CELL_LDS_BYTES; }
+  size_t score_lds_bytes(int tw, int *off = nullptr) const;  // LDS of a scorer pass with tw doubles per table entry
+  int score_fb() const;                                      // factors per scorer pass: 4, 2 or 1 (0: the tables do not fit at 1)
+  void set_chunk_stats(const std::vector<int32_t> &chunk_len, const std::vector<int32_t> &steps);
 };
 
 // planner (host): X = the main table in CSR (rows sorted by the first field), blocks in Gibbs order

@@ -708,7 +708,7 @@ static void run_sweep_cell(mfm_ctx *c, int f_begin, int f_end, const double *zba
       DevBlock *B = fd.kind == 1 ? c->blocks[(size_t)fd.base].get() : nullptr;
       double *out_u = B ? B->rec.p + 2 : cp.stat.p;  // a U field's sums: (c, c_S, e, e_q) of the record / (S2, S_eh)
       int out_stride = B ? BLOCK_REC : 2;
-      const bool split = P >= 0 && cp.lds_bytes(P, k, sw) > CELL_LDS_BYTES;
+      const bool split = cp.split_pass(P, k, sw);
       if (sw)
         cell_prep(s, tm, cp, cur, false, -1, true, k, false);
       else
@@ -1760,6 +1760,37 @@ int mfm_res_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why
   for (int i = 0; i < n_out; i++) out[i] = i < MFM_RES_INFO_FIELDS ? v[i] : 0;
   if (why_len > 0) {
     std::strncpy(why, rp.ready ? "" : rp.why.c_str(), (size_t)why_len - 1);
+    why[why_len - 1] = 0;
+  }
+  return MFM_OK;
+}
+
+// The cell path's plan as the planner left it (host-side fields only: no launch, no synchronisation)
+int mfm_cell_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why_len) {
+  if (!ctx || n_out < 0 || (n_out > 0 && !out) || why_len < 0 || (why_len > 0 && !why)) return MFM_ERR_INVALID;
+  const CellPlan &cp = ctx->cell;
+  int64_t v[MFM_CELL_INFO_FIELDS] = {0};
+  const int m = (int)cp.fields.size(), ns = (int)cp.streams.size();
+  int64_t split = 0;  // the passes of a factor after the first, as run_sweep_cell runs them: (last field, 0) across two factors, (k - 1, k)
+  const bool typed = ns > 0 && cp.sU == 0;  // (a refusal before the stream types were set: lds_bytes has nothing to go by)
+  for (int k = 0; k < m && typed; k++)
+    if (cp.split_pass(k == 0 ? m - 1 : k - 1, k, k == 0)) split |= (int64_t)1 << k;
+  const int64_t head[14] = {cp.ready ? 1 : 0, cp.G,         cp.umax,      cp.item32 ? 1 : 0, ns,    m, cp.N, cp.Npad, cp.max_steps,
+                            cp.chunk_max,     cp.chunk_min, cp.chunks_empty, split,          cp.ready ? cp.score_fb() : 0};
+  for (int i = 0; i < 14; i++) v[i] = head[i];
+  for (int i = 0; i < ns && i < CELL_MAX_STREAMS; i++) {
+    v[14 + 3 * i] = cp.streams[i].type;
+    v[15 + 3 * i] = cp.streams[i].slot;
+    v[16 + 3 * i] = cp.streams[i].card;
+  }
+  for (int k = 0; k < m && k < CELL_MAX_FIELDS; k++) {
+    v[14 + 3 * CELL_MAX_STREAMS + 3 * k] = cp.fields[k].stream;
+    v[15 + 3 * CELL_MAX_STREAMS + 3 * k] = cp.fields[k].kind;
+    v[16 + 3 * CELL_MAX_STREAMS + 3 * k] = cp.fields[k].n;
+  }
+  for (int i = 0; i < n_out; i++) out[i] = i < MFM_CELL_INFO_FIELDS ? v[i] : 0;
+  if (why_len > 0) {
+    std::strncpy(why, cp.ready ? "" : cp.why.c_str(), (size_t)why_len - 1);
     why[why_len - 1] = 0;
   }
   return MFM_OK;

@@ -9,6 +9,10 @@ from .gibbs_driver import CapiGibbs
 
 pytestmark = pytest.mark.gpu
 
+# single-call bounds of the cell path (shared with tests/cell_ref.py): w after one update_w, the scorer's e
+TOL_W = dict(rtol=1e-10, atol=1e-12)
+TOL_SCORE = dict(rtol=1e-10, atol=1e-10)
+
 
 @pytest.fixture(scope="module")
 def capi():
@@ -123,7 +127,7 @@ def test_cell_scorer(oracle, capi, monkeypatch, shape, rank):
     t.substep(8)
     c.update_e_regression()
     e = c.get_e()
-    np.testing.assert_allclose(e, t.e(n), rtol=1e-10, atol=1e-10)
+    np.testing.assert_allclose(e, t.e(n), **TOL_SCORE)
     monkeypatch.setenv("MFM_NO_CELL", "1")
     _, cg = _pair(oracle, capi, main, y, gi, rank, blocks)
     cg.update_e_regression()
@@ -149,7 +153,7 @@ def test_cell_linear_sweep(oracle, capi, monkeypatch, shape):
     z = t.clone().rng_sample_normals(D)
     t.substep(4)
     c.sweep_w(1.3, lam, mu, z)
-    np.testing.assert_allclose(c.get_state()[1], t.fm()[1], rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(c.get_state()[1], t.fm()[1], **TOL_W)
     np.testing.assert_allclose(c.get_e(), t.e(n), rtol=1e-9, atol=1e-10)
     monkeypatch.setenv("MFM_NO_CELL_W", "1")
     t2, cg = _pair(oracle, capi, main, y, gi, 2, blocks)
