@@ -379,12 +379,20 @@ int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_
                              const double *cutpoints, double *out);
 
 /* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
- * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), no relation blocks; pair (u, i) is the
- * design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column
+ * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), each optionally with relation blocks
+ * (below); pair (u, i) is the design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column
  * ..."): the score then splits into per-side terms and one dense contraction, which runs on the fp64 MFMA. The arguments are
  * checked before the device is looked for, so a machine without a GPU gets MFM_ERR_INVALID for bad ones and MFM_ERR_DEVICE
  * otherwise. The handle's last error: the one of the pairs entry points (NULL: of the last failed create of this thread).
  *   mode 0: value(u, i) = mean_s score_s(u, i);  mode 1: mean_s Phi(score_s(u, i))   (as the prediction entry points above)
+ *   mode 2: ordered probit, mean_s sum_j Phi(score_s(u, i) - cut_s[j]) = the posterior mean of the expected class index
+ *           sum_c c p_c; needs mfm_pairs_set_cutpoints with the call's sample count and n_cut >= 1, else MFM_ERR_INVALID.
+ *   add_block: side (0 query, 1 candidates) row r additionally holds row o2b[r] of a CSR block (block_rows, width) with
+ *           block-local column indices, placed at columns [col_offset, col_offset + width) of the feature space. Blocks of a side
+ *           are applied in the order they were added. MFM_ERR_INVALID, with a message naming the offender, for a bad side, an
+ *           o2b entry outside [0, block_rows), a malformed CSR, col_offset + width > D, and a stored column (referenced by a
+ *           side row or not) that the other side stores in its main matrix or in an earlier block ("X_query and X_cand share
+ *           column j", j in model coordinates) or that this side already stores.
  *   scores: out[U * I] row-major = value(u, i).
  *   topk:   per query row the k (1 <= k <= 256) candidates of largest value, ordered by (value descending, candidate index
  *           ascending); idx[U * k], score[U * k] row-major, a tail of idx -1 / score -inf where fewer than k candidates remain.
@@ -393,7 +401,8 @@ int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_
  *           for the host-sample prediction entry point (w0s[S], ws[S * D], Vs[S * D * K], each V column-major (D, K)).
  * Memory: the candidate side's embedding (I x S x K doubles, padded) is resident for the call and refused when it exceeds
  * MFM_STORE_MAX_FRACTION of the free device memory; the queries are walked in chunks whose scratch stays under the scratch
- * bound (256 MB by default, never less than one 64-row tile).                                                            */
+ * bound (256 MB by default, never less than one 64-row tile). Every block's table (block_rows x S x (K + 2) doubles, padded,
+ * both sides) is built once per call and counts as resident next to the candidate embedding.                              */
 typedef struct mfm_pairs mfm_pairs;
 int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, const int32_t *q_indices, const double *q_data,
                      int64_t I, const int64_t *c_indptr, const int32_t *c_indices, const double *c_data, mfm_pairs **out);
@@ -401,6 +410,9 @@ void mfm_pairs_destroy(mfm_pairs *p);
 const char *mfm_pairs_last_error(const mfm_pairs *p);
 int mfm_pairs_set_exclude(mfm_pairs *p, const int64_t *indptr, const int32_t *indices);
 int mfm_pairs_set_scratch_bound(mfm_pairs *p, int64_t bytes);
+int mfm_pairs_add_block(mfm_pairs *p, int32_t side /*0 query, 1 cand*/, int64_t col_offset, int64_t width, int64_t block_rows,
+                        const int64_t *o2b /*[U] or [I]*/, const int64_t *indptr, const int32_t *indices, const double *data);
+int mfm_pairs_set_cutpoints(mfm_pairs *p, int32_t n_samples, int32_t n_cut, const double *cutpoints /*[n_samples][n_cut]*/);
 int mfm_pairs_scores_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, double *out);
 int mfm_pairs_topk_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int64_t *idx,
                          double *score);

@@ -39,7 +39,8 @@ SYMBOLS = [
     "mfm_vb_set_stream", "mfm_vb_set_allreduce", "mfm_vb_set_shard", "mfm_vb_comm_init", "mfm_vb_comm_stats", "mfm_vb_set_levels",
     "mfm_vb_design_levels",
     "mfm_pairs_create", "mfm_pairs_destroy", "mfm_pairs_last_error", "mfm_pairs_set_exclude", "mfm_pairs_set_scratch_bound",
-    "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk",
+    "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
+    "mfm_pairs_set_cutpoints",
 ]
 
 _lib = None
@@ -168,6 +169,8 @@ def lib():
     L.mfm_pairs_last_error.argtypes = [vp]
     L.mfm_pairs_set_exclude.argtypes = [vp, P, P]
     L.mfm_pairs_set_scratch_bound.argtypes = [vp, i64]
+    L.mfm_pairs_add_block.argtypes = [vp, i32, i64, i64, i64, P, P, P, P]
+    L.mfm_pairs_set_cutpoints.argtypes = [vp, i32, i32, P]
     L.mfm_pairs_scores_store.argtypes = [vp, vp, i32, i32, i32, P]
     L.mfm_pairs_topk_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P]
     L.mfm_pairs_scores.argtypes = [vp, i32, i32, P, P, P, i32, P]
@@ -643,9 +646,13 @@ def _pack_samples(samples):
 class Pairs:
     """Query x candidate scoring (mfm_pairs_*): both sides (U, D) / (I, D) sparse in the model's feature space, no column in
     both. `exclude`: optional (U, I) sparse pattern of pairs the top-k leaves out. `scratch_bound`: bytes of query-side
-    scratch per chunk of queries (default 256 MB; a small value makes a small table cross the chunking)."""
+    scratch per chunk of queries (default 256 MB; a small value makes a small table cross the chunking). `rel_query` /
+    `rel_cand`: relation blocks of the sides, each entry (col_offset, o2b, csr): side row r additionally holds row o2b[r] of
+    `csr` at columns [col_offset, col_offset + csr.shape[1]) of the same D columns (the main matrices keep the model's width
+    and leave the blocks' columns empty); applied in list order. `cutpoints`: (S, n_cut) array, the samples' cutpoints for
+    mode 2 (the mean over the samples of the expected class index of the ordered probit)."""
 
-    def __init__(self, X_query, X_cand, exclude=None, scratch_bound=None, device=0):
+    def __init__(self, X_query, X_cand, exclude=None, scratch_bound=None, device=0, rel_query=(), rel_cand=(), cutpoints=None):
         L = lib()
         h = C.c_void_p()
         Xq, qp, qx, qv = csr_parts(X_query)
@@ -667,6 +674,20 @@ class Pairs:
             self._ck(L.mfm_pairs_set_exclude(h, _p(ep), _p(ex)))
         if scratch_bound is not None:
             self._ck(L.mfm_pairs_set_scratch_bound(h, int(scratch_bound)))
+        try:
+            for side, rels in ((0, rel_query), (1, rel_cand)):
+                for off, o2b, B in rels:
+                    B, bp, bx, bv = csr_parts(B)
+                    o2b = np.ascontiguousarray(o2b, dtype=np.int64)
+                    if o2b.shape != ((self.U, self.I)[side],):
+                        raise ValueError("a block's o2b must have one entry per row of its side")
+                    self._ck(L.mfm_pairs_add_block(h, side, int(off), B.shape[1], B.shape[0], _p(o2b), _p(bp), _p(bx), _p(bv)))
+            if cutpoints is not None:
+                cp = _f64(np.atleast_2d(np.asarray(cutpoints, dtype=np.float64)))
+                self._ck(L.mfm_pairs_set_cutpoints(h, cp.shape[0], cp.shape[1], _p(cp)))
+        except Exception:
+            self.close()
+            raise
 
     def _ck(self, rc):
         if rc:
@@ -684,7 +705,8 @@ class Pairs:
             pass
 
     def scores(self, samples, mode=0):
-        """(U, I) mean score (mode 0) or mean Phi(score) (mode 1); samples: list of (w0, w[D], V[D, K])"""
+        """(U, I) mean score (mode 0), mean Phi(score) (mode 1) or mean expected class index (mode 2, with `cutpoints`);
+        samples: list of (w0, w[D], V[D, K])"""
         K, S, w0s, ws, Vs = _pack_samples(samples)
         out = np.empty((self.U, self.I))
         self._ck(lib().mfm_pairs_scores(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, _p(out)))

@@ -308,6 +308,15 @@ Relations relations_from_py(const py::handle &h) {
   return out;
 }
 
+// the block list of one side of a pair call: an entry may be None (null here: this side holds nothing at that block position)
+Relations pair_relations_from_py(const py::handle &h) {
+  Relations out;
+  if (h.is_none()) return out;
+  for (auto item : py::reinterpret_borrow<py::sequence>(h))
+    out.push_back(item.is_none() ? std::shared_ptr<RelationBlock>() : item.cast<std::shared_ptr<RelationBlock>>());
+  return out;
+}
+
 // util.hpp:147-165
 template <class M>
 size_t check_row_consistency_return_column(const M &X, const Relations &relations) {
@@ -386,6 +395,15 @@ struct DevicePairs {
     if (p) mfm_pairs_destroy(p);
   }
   DevicePairs(const DevicePairs &) = delete;
+  // the blocks of one side (0 query, 1 candidates) at the column offsets of their positions; null entries hold nothing
+  void add_blocks(int side, const Relations &rels, const vector<size_t> &offsets) {
+    for (size_t i = 0; i < rels.size(); i++) {
+      if (!rels[i]) continue;
+      const RelationBlock &r = *rels[i];
+      ck(mfm_pairs_add_block(p, side, (int64_t)offsets[i], r.X.cols, r.X.rows, r.map64(), r.X.indptr.data(), r.X.indices.data(),
+                             r.X.data.data()));
+    }
+  }
   void ck(int code) const {
     if (code != MFM_OK) throw_code(code, mfm_pairs_last_error(p));
   }
@@ -647,28 +665,102 @@ struct Predictor {
   }
   // ---- query x candidate scoring (not in the reference): pair (u, i) is the design row X_query[u] + X_cand[i] ----------------
   // everything that can be wrong with the arguments is found here, on the host, before the device is looked for
-  void check_pairs(const Csr &Xq, const Csr &Xc) const {
-    if (type == TaskType::ORDERED) throw std::runtime_error("pair scoring is not available for the ordered probit model.");
-    for (const Csr *X : {&Xq, &Xc})
-      if ((size_t)X->cols != feature_size) {
+  void check_width(size_t given) const {
+    if (given != feature_size) {
+      std::ostringstream ss;
+      ss << "Told to predict for " << given << " but this->feature_size is " << feature_size;
+      throw std::invalid_argument(ss.str());
+    }
+  }
+  // The two sides of a pair call. Without blocks both matrices are in the full feature space. With blocks the model's row is
+  // [X | B_0[idx_0] | B_1[idx_1] ...]: each list is empty (no blocks on that side; made a list of nulls here) or has one entry per
+  // block position, a null entry meaning that the side holds nothing there; the matrices then have the main width. Returns the
+  // column offset of every block position in the model's feature space.
+  vector<size_t> check_pairs(const Csr &Xq, const Csr &Xc, Relations &rq, Relations &rc) const {
+    vector<size_t> offsets;
+    if (rq.empty() && rc.empty()) {
+      check_width((size_t)Xq.cols);
+      check_width((size_t)Xc.cols);
+    } else {
+      if (rq.empty()) rq.resize(rc.size());
+      if (rc.empty()) rc.resize(rq.size());
+      if (rq.size() != rc.size())
+        throw std::invalid_argument("X_rel_query and X_rel_cand must each be empty or hold one entry per block position of the model");
+      size_t blocks_width = 0;
+      for (size_t i = 0; i < rq.size(); i++) {
         std::ostringstream ss;
-        ss << "Told to predict for " << X->cols << " but this->feature_size is " << feature_size;
-        throw std::invalid_argument(ss.str());
+        if (!rq[i] && !rc[i]) {
+          ss << "block position " << i << " is None in both X_rel_query and X_rel_cand";
+          throw std::invalid_argument(ss.str());
+        }
+        if (rq[i] && rc[i] && rq[i]->feature_size != rc[i]->feature_size) {
+          ss << "block position " << i << ": X_rel_query has width " << rq[i]->feature_size << " but X_rel_cand has width "
+             << rc[i]->feature_size;
+          throw std::invalid_argument(ss.str());
+        }
+        if (rq[i] && rq[i]->mapper_size != (size_t)Xq.rows) {
+          ss << "X_query has size " << Xq.rows << " but X_rel_query[" << i << "] has size " << rq[i]->mapper_size;
+          throw std::invalid_argument(ss.str());
+        }
+        if (rc[i] && rc[i]->mapper_size != (size_t)Xc.rows) {
+          ss << "X_cand has size " << Xc.rows << " but X_rel_cand[" << i << "] has size " << rc[i]->mapper_size;
+          throw std::invalid_argument(ss.str());
+        }
+        blocks_width += (rq[i] ? rq[i] : rc[i])->feature_size;
       }
+      check_width((size_t)Xq.cols + blocks_width);
+      check_width((size_t)Xc.cols + blocks_width);
+      size_t off = (size_t)Xq.cols;
+      for (size_t i = 0; i < rq.size(); i++) {
+        offsets.push_back(off);
+        off += (rq[i] ? rq[i] : rc[i])->feature_size;
+      }
+    }
     for (const Csr *X : {&Xq, &Xc})
       for (int32_t j : X->indices)
-        if (j < 0 || (size_t)j >= feature_size) throw std::invalid_argument("column index out of range");
+        if (j < 0 || j >= X->cols) throw std::invalid_argument("column index out of range");
+    for (const Relations *rels : {&rq, &rc})
+      for (auto &r : *rels)
+        if (r)
+          for (int32_t j : r->X.indices)
+            if (j < 0 || j >= r->X.cols) throw std::invalid_argument("relation block: column index out of range");
+    // disjointness over the whole feature space; a block counts every column it stores, referenced or not
     vector<uint8_t> seen(feature_size, 0);
     for (int32_t j : Xq.indices) seen[(size_t)j] = 1;
+    for (size_t i = 0; i < rq.size(); i++)
+      if (rq[i])
+        for (int32_t j : rq[i]->X.indices) seen[offsets[i] + (size_t)j] = 1;
     for (int32_t j : Xc.indices)
       if (seen[(size_t)j]) throw std::invalid_argument("X_query and X_cand share column " + std::to_string(j));
+    for (size_t i = 0; i < rc.size(); i++)
+      if (rc[i])
+        for (int32_t j : rc[i]->X.indices)
+          if (seen[offsets[i] + (size_t)j])
+            throw std::invalid_argument("X_query and X_cand share column " + std::to_string(offsets[i] + (size_t)j));
+    // ordered probit ranks by the expected class index: every sample needs its cutpoints (group 0, as predict_proba)
+    if (type == TaskType::ORDERED && !samples.empty()) {
+      const size_t n_cpt = samples.at(0).cutpoints.empty() ? 0 : samples[0].cutpoints[0].size();
+      if (n_cpt < 1) throw std::runtime_error("No cutpoint available for this FM.");
+      for (auto &sm : samples)
+        if (sm.cutpoints.empty() || sm.cutpoints[0].size() != n_cpt)
+          throw std::runtime_error("inconsistent cutpoint sizes among samples.");
+    }
+    return offsets;
   }
   // idx / score: the top k; dense: all pairs (exactly one of the two forms)
-  void run_pairs(const Csr &Xq, const Csr &Xc, const Csr *exclude, int k, int64_t *idx, double *score, double *dense) const {
+  void run_pairs(const Csr &Xq, const Csr &Xc, const Relations &rq, const Relations &rc, const vector<size_t> &offsets,
+                 const Csr *exclude, int k, int64_t *idx, double *score, double *dense) const {
     if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
     DevicePairs dp((int64_t)feature_size, Xq, Xc);
+    dp.add_blocks(0, rq, offsets);
+    dp.add_blocks(1, rc, offsets);
     if (exclude) dp.ck(mfm_pairs_set_exclude(dp.p, exclude->indptr.data(), exclude->indices.data()));
-    const int mode = type == TaskType::CLASSIFICATION ? 1 : 0;
+    const int mode = type == TaskType::CLASSIFICATION ? 1 : type == TaskType::ORDERED ? 2 : 0;
+    if (mode == 2) {
+      vector<double> cuts;
+      for (auto &sm : samples) cuts.insert(cuts.end(), sm.cutpoints[0].begin(), sm.cutpoints[0].end());
+      dp.ck(mfm_pairs_set_cutpoints(dp.p, (int)samples.size(), (int)samples[0].cutpoints[0].size(), cuts.data()));
+    }
     int first = 0;
     if (auto st = resident(&first)) {  // the unmodified entries of the device store: in place, as run_predict
       dp.ck(dense ? mfm_pairs_scores_store(dp.p, st->st, first, (int)samples.size(), mode, dense)
@@ -680,18 +772,21 @@ struct Predictor {
     dp.ck(dense ? mfm_pairs_scores(dp.p, (int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, dense)
                 : mfm_pairs_topk(dp.p, (int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, k, idx, score));
   }
-  py::array_t<double> predict_pairs(const py::object &Xqo, const py::object &Xco) const {
+  py::array_t<double> predict_pairs(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
     Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
-    check_pairs(Xq, Xc);
+    Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
+    const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
     if ((double)Xq.rows * (double)Xc.rows > 16777216.0)
       throw std::invalid_argument("predict_pairs returns every pair: more than 2^24 pairs are refused, use predict_topk");
     py::array_t<double> out({(py::ssize_t)Xq.rows, (py::ssize_t)Xc.rows});
-    run_pairs(Xq, Xc, nullptr, 0, nullptr, nullptr, out.mutable_data());
+    run_pairs(Xq, Xc, rq, rc, offsets, nullptr, 0, nullptr, nullptr, out.mutable_data());
     return out;
   }
-  py::tuple predict_topk(const py::object &Xqo, const py::object &Xco, int64_t k, const py::object &excludeo) const {
+  py::tuple predict_topk(const py::object &Xqo, const py::object &Xco, int64_t k, const py::object &excludeo, const py::object &rqo,
+                         const py::object &rco) const {
     Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
-    check_pairs(Xq, Xc);
+    Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
+    const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
     if (k < 1 || k > 256) throw std::invalid_argument("k must be in [1, 256]");
     Csr ex;
     if (!excludeo.is_none()) {
@@ -703,7 +798,7 @@ struct Predictor {
     }
     py::array_t<int64_t> idx({(py::ssize_t)Xq.rows, (py::ssize_t)k});
     py::array_t<double> score({(py::ssize_t)Xq.rows, (py::ssize_t)k});
-    run_pairs(Xq, Xc, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), score.mutable_data(), nullptr);
+    run_pairs(Xq, Xc, rq, rc, offsets, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), score.mutable_data(), nullptr);
     return py::make_tuple(idx, score);
   }
   // predictor.hpp:78-124
@@ -1985,9 +2080,12 @@ struct VPredictor {
     for (auto &s : samples) p.samples.push_back(const_cast<VFM &>(s).mean_fm());
     return p;
   }
-  py::array_t<double> predict_pairs(const py::object &Xq, const py::object &Xc) const { return mean_predictor().predict_pairs(Xq, Xc); }
-  py::tuple predict_topk(const py::object &Xq, const py::object &Xc, int64_t k, const py::object &exclude) const {
-    return mean_predictor().predict_topk(Xq, Xc, k, exclude);
+  py::array_t<double> predict_pairs(const py::object &Xq, const py::object &Xc, const py::object &rq, const py::object &rc) const {
+    return mean_predictor().predict_pairs(Xq, Xc, rq, rc);
+  }
+  py::tuple predict_topk(const py::object &Xq, const py::object &Xc, int64_t k, const py::object &exclude, const py::object &rq,
+                         const py::object &rc) const {
+    return mean_predictor().predict_topk(Xq, Xc, k, exclude, rq, rc);
   }
 };
 
@@ -2479,8 +2577,10 @@ PYBIND11_MODULE(_myfm, m) {
       .def("predict", &Predictor::predict)
       .def("predict_parallel", &Predictor::predict_parallel)
       .def("predict_parallel_oprobit", &Predictor::predict_parallel_oprobit)
-      .def("predict_pairs", &Predictor::predict_pairs)
-      .def("predict_topk", &Predictor::predict_topk)
+      .def("predict_pairs", &Predictor::predict_pairs, py::arg("X_query"), py::arg("X_cand"), py::arg("X_rel_query") = py::tuple(),
+           py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk", &Predictor::predict_topk, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("exclude") = py::none(),
+           py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def(py::pickle(
           [](const Predictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {
@@ -2657,8 +2757,10 @@ PYBIND11_MODULE(_myfm, m) {
 
   py::class_<VPredictor>(m, "VariationalPredictor")
       .def("predict", &VPredictor::predict)
-      .def("predict_pairs", &VPredictor::predict_pairs)
-      .def("predict_topk", &VPredictor::predict_topk)
+      .def("predict_pairs", &VPredictor::predict_pairs, py::arg("X_query"), py::arg("X_cand"), py::arg("X_rel_query") = py::tuple(),
+           py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk", &VPredictor::predict_topk, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("exclude") = py::none(),
+           py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def(py::pickle(
           [](const VPredictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {

@@ -6,6 +6,12 @@
 // free device memory. The queries are walked in chunks of rows whose scratch -- P and the biases, the exclusion bitmask, the
 // per-stripe lists at the most stripes a launch can have, the outputs -- stays under `scratch_bound` bytes (256 MB unless
 // mfm_pairs_set_scratch_bound says otherwise; never less than one 64-row tile).
+//
+// Relation blocks (mfm_pairs_add_block). A side's row is [main | B_0[o2b_0[r]] | ...]; every block of either side gets a table
+// (block rows x samples x (padded factors + 2) doubles, mfm_pairs.hpp) built once per call -- the query side's too, not once per
+// chunk -- and resident for it. The tables count against MFM_STORE_MAX_FRACTION together with Q; the per-row scratch formula is
+// unchanged. A side with blocks is embedded by k_pairs_embed_rel, one without by k_pairs_embed, so a call without blocks computes
+// what it computed before there were any.
 #include "mfm_pairs.hpp"
 
 #include <cmath>
@@ -21,6 +27,17 @@ struct mfm_pairs {
   DevBuf<int64_t> q_ptr, c_ptr, e_ptr;
   DevBuf<int32_t> q_idx, c_idx, e_idx;
   DevBuf<double> q_val, c_val;
+  // relation blocks of the two sides (0 query, 1 candidates), in the order they were added
+  struct Block {
+    int64_t off = 0, width = 0, M = 0;
+    DevBuf<int64_t> o2b, ptr;
+    DevBuf<int32_t> idx;
+    DevBuf<double> val;
+  };
+  std::vector<std::unique_ptr<Block>> blocks[2];
+  std::vector<uint8_t> stored[2];  // per side: column j of the model's feature space is stored in its main matrix or in a block
+  std::vector<double> cut;         // [cut_S][n_cut], the samples' cutpoints (mode 2)
+  int cut_S = 0, n_cut = 0;
   std::vector<int64_t> e_ptr_host;  // (the exclusions of a chunk are counted on the host)
   bool has_exclude = false;
   int64_t scratch_bound = (int64_t)256 << 20;
@@ -85,8 +102,10 @@ void launch_tile(hipStream_t s, dim3 grid, const PairsArgs &a, int mode, bool de
   do {                                        \
     if (mode == 0)                            \
       launch_tile_t<MT, NT, 0, DENSE>(s, grid, a); \
-    else                                      \
+    else if (mode == 1)                       \
       launch_tile_t<MT, NT, 1, DENSE>(s, grid, a); \
+    else                                      \
+      launch_tile_t<MT, NT, 2, DENSE>(s, grid, a); \
   } while (0)
   if (dense)
     PAIRS_LAUNCH(4, 2, true);
@@ -106,7 +125,13 @@ void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, co
   if (S <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
   if (S > 65535) throw Error(MFM_ERR_INVALID, "at most 65535 samples per call");
   if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
-  if (mode != 0 && mode != 1) throw Error(MFM_ERR_INVALID, "bad prediction mode (0: mean score, 1: mean Phi(score))");
+  if (mode != 0 && mode != 1 && mode != 2)
+    throw Error(MFM_ERR_INVALID, "bad prediction mode (0: mean score, 1: mean Phi(score), 2: mean expected class index of the ordered probit)");
+  if (mode == 2) {
+    if (p->n_cut < 1) throw Error(MFM_ERR_INVALID, "mode 2 needs the samples' cutpoints (mfm_pairs_set_cutpoints), at least one per sample");
+    if (p->cut_S != S)
+      throw Error(MFM_ERR_INVALID, "mode 2: cutpoints were set for " + std::to_string(p->cut_S) + " samples, the call has " + std::to_string(S));
+  }
   const bool is_dense = dense != nullptr;
   if (!is_dense && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
   const int64_t U = p->U, I = p->I, D = p->D;
@@ -116,15 +141,29 @@ void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, co
   const int64_t NK = (int64_t)S * KS4;
   const int64_t Ipad = round_up(std::max<int64_t>(I, 1), PAIRS_COL_ALIGN);
 
-  // ---- the memory rule: Q resident, the query scratch bounded
+  // ---- the memory rule: Q and every block table resident, the query scratch bounded
   const double q_bytes = ((double)Ipad * S * KS + (double)Ipad * (S + 1)) * sizeof(double);
+  double t_bytes[2] = {0.0, 0.0};
+  for (int side = 0; side < 2; side++)
+    for (auto &b : p->blocks[side]) t_bytes[side] += (double)b->M * S * (KS + 2) * sizeof(double);
   {
     size_t free_b = 0, total_b = 0;
     const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && q_bytes > frac * (double)free_b)
-      throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + std::to_string((int64_t)(q_bytes / 1048576.0)) +
-                                       " MB for all samples) exceeds MFM_STORE_MAX_FRACTION of the free device memory; "
-                                       "score fewer samples or fewer candidates per call");
+    const double all_bytes = q_bytes + t_bytes[0] + t_bytes[1];
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && all_bytes > frac * (double)free_b) {
+      if (t_bytes[0] + t_bytes[1] == 0.0)
+        throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + std::to_string((int64_t)(q_bytes / 1048576.0)) +
+                                         " MB for all samples) exceeds MFM_STORE_MAX_FRACTION of the free device memory; "
+                                         "score fewer samples or fewer candidates per call");
+      const auto mb = [](double b) { return std::to_string((int64_t)(b / 1048576.0)) + " MB"; };
+      const char *large = q_bytes >= t_bytes[0] && q_bytes >= t_bytes[1] ? "the candidate side's embedding"
+                          : t_bytes[0] >= t_bytes[1]                     ? "the query side's block tables"
+                                                                         : "the candidate side's block tables";
+      throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + mb(q_bytes) + "), the query side's block tables (" +
+                                       mb(t_bytes[0]) + ") and the candidate side's block tables (" + mb(t_bytes[1]) +
+                                       ") for all samples together exceed MFM_STORE_MAX_FRACTION of the free device memory; the largest part is " +
+                                       large + ": score fewer samples, fewer candidates or smaller blocks per call");
+    }
   }
   const int64_t W = (I + 31) / 32;
   const int rows_t = tile_rows(is_dense, k), step = tile_step(is_dense, k);
@@ -143,13 +182,53 @@ void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, co
   double w0sum = 0.0;
   for (int i = 0; i < S; i++) w0sum += w0[i];
 
+  DevBuf<double> d_cut;
+  if (mode == 2) d_cut.upload(p->cut);
+
+  // ---- the block tables of both sides, once per call
+  std::vector<DevBuf<double>> tables[2];
+  DevBuf<PairsBlockRef> d_blk[2];
+  for (int side = 0; side < 2; side++) {
+    std::vector<PairsBlockRef> refs;
+    for (auto &b : p->blocks[side]) {
+      const size_t SM = (size_t)S * (size_t)b->M;
+      tables[side].emplace_back();
+      DevBuf<double> &t = tables[side].back();
+      t.alloc(std::max<size_t>(SM * (size_t)(KS + 2), 1));
+      PairsBlockRef ref;
+      ref.o2b = b->o2b.p;
+      ref.T = t.p;
+      ref.lin = t.p + SM * (size_t)KS;
+      ref.vv = t.p + SM * (size_t)(KS + 1);
+      ref.M = b->M;
+      refs.push_back(ref);
+      if (b->M > 0) {
+        hipLaunchKernelGGL(k_pairs_embed_block, dim3((unsigned)((b->M + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S), dim3(PAIRS_WG), 0, s,
+                           b->ptr.p, b->idx.p, b->val.p, b->M, b->off, (const double *const *)d_wv.p, D, K, KS, t.p,
+                           t.p + SM * (size_t)KS, t.p + SM * (size_t)(KS + 1));
+        MFM_HIP_CHECK(hipGetLastError());
+      }
+    }
+    if (!refs.empty()) d_blk[side].upload(refs);
+  }
+  // a side with blocks gathers from its tables, one without takes the plain kernel
+  const auto embed = [&](int side, const int64_t *ptr, const int32_t *idx, const double *val, int64_t r0, int64_t R, int64_t Rpad, double *Pf,
+                         double *bias) {
+    const dim3 grid((unsigned)((Rpad + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S);
+    if (p->blocks[side].empty())
+      hipLaunchKernelGGL(k_pairs_embed, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K, KS, S,
+                         Pf, bias);
+    else
+      hipLaunchKernelGGL(k_pairs_embed_rel, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K, KS,
+                         S, (const PairsBlockRef *)d_blk[side].p, (int)p->blocks[side].size(), Pf, bias);
+  };
+
   // ---- candidate side, once
   DevBuf<double> Qf, Bb, Bsum;
   Qf.alloc((size_t)std::max<int64_t>(Ipad * NK * 4, 1));
   Bb.alloc((size_t)Ipad * S);
   Bsum.alloc((size_t)Ipad);
-  hipLaunchKernelGGL(k_pairs_embed, dim3((unsigned)(Ipad / PAIRS_WG), (unsigned)S), dim3(PAIRS_WG), 0, s, p->c_ptr.p, p->c_idx.p,
-                     p->c_val.p, (int64_t)0, I, Ipad, (const double *const *)d_wv.p, D, K, KS, S, Qf.p, Bb.p);
+  embed(1, p->c_ptr.p, p->c_idx.p, p->c_val.p, (int64_t)0, I, Ipad, Qf.p, Bb.p);
   hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)(Ipad / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Bb.p, S, Ipad, Bsum.p);
   MFM_HIP_CHECK(hipGetLastError());
 
@@ -163,8 +242,7 @@ void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, co
     ensure(Pf, (size_t)(Upad * NK * 4));
     ensure(Ab, (size_t)(Upad * S));
     ensure(Asum, (size_t)Upad);
-    hipLaunchKernelGGL(k_pairs_embed, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S), dim3(PAIRS_WG), 0, s,
-                       p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, (const double *const *)d_wv.p, D, K, KS, S, Pf.p, Ab.p);
+    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p);
     hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Ab.p, S, Upad,
                        Asum.p);
     const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
@@ -186,6 +264,8 @@ void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, co
     a.Bb = Bb.p;
     a.Bsum = Bsum.p;
     a.w0s = d_w0.p;
+    a.cut = mode == 2 ? d_cut.p : nullptr;
+    a.n_cut = mode == 2 ? p->n_cut : 0;
     a.w0sum = w0sum;
     a.NK = NK;
     a.KS4 = KS4;
@@ -278,12 +358,11 @@ int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, 
     check_csr(U, D, q_indptr, q_indices, "X_query");
     check_csr(I, D, c_indptr, c_indices, "X_cand");
     if (I >= (int64_t)2147483647 - PAIRS_COL_ALIGN) throw Error(MFM_ERR_INVALID, "too many candidates");
-    {
-      std::vector<uint8_t> seen((size_t)D, 0);
-      for (int64_t q = 0; q < q_indptr[U]; q++) seen[(size_t)q_indices[q]] = 1;
-      for (int64_t q = 0; q < c_indptr[I]; q++)
-        if (seen[(size_t)c_indices[q]])
-          throw Error(MFM_ERR_INVALID, "X_query and X_cand share column " + std::to_string(c_indices[q]));
+    std::vector<uint8_t> seen((size_t)D, 0), seen_c((size_t)D, 0);
+    for (int64_t q = 0; q < q_indptr[U]; q++) seen[(size_t)q_indices[q]] = 1;
+    for (int64_t q = 0; q < c_indptr[I]; q++) {
+      if (seen[(size_t)c_indices[q]]) throw Error(MFM_ERR_INVALID, "X_query and X_cand share column " + std::to_string(c_indices[q]));
+      seen_c[(size_t)c_indices[q]] = 1;
     }
     const int n = mfm_device_count();
     if (n <= 0)
@@ -302,6 +381,8 @@ int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, 
     p->c_ptr.upload(c_indptr, (size_t)I + 1);
     p->c_idx.upload(c_indices, (size_t)c_indptr[I]);
     p->c_val.upload(c_data, (size_t)c_indptr[I]);
+    p->stored[0] = std::move(seen);
+    p->stored[1] = std::move(seen_c);
     *out = p.release();
     return MFM_OK;
   } catch (const mfm::Error &ex) {
@@ -333,6 +414,58 @@ int mfm_pairs_set_exclude(mfm_pairs *p, const int64_t *indptr, const int32_t *in
   p->e_ptr.upload(indptr, (size_t)p->U + 1);
   p->e_idx.upload(indices, (size_t)indptr[p->U]);
   p->has_exclude = indptr[p->U] > 0;
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_add_block(mfm_pairs *p, int32_t side, int64_t col_offset, int64_t width, int64_t block_rows, const int64_t *o2b,
+                        const int64_t *indptr, const int32_t *indices, const double *data) {
+  PAIRS_TRY(p)
+  if (side != 0 && side != 1) throw Error(MFM_ERR_INVALID, "side must be 0 (query) or 1 (candidates), got " + std::to_string(side));
+  const char *name = side == 0 ? "X_rel_query" : "X_rel_cand";
+  const std::string what = std::string(name) + "[" + std::to_string(p->blocks[side].size()) + "]";
+  if (col_offset < 0 || width < 0 || block_rows < 0) throw Error(MFM_ERR_INVALID, what + ": negative column offset or shape");
+  if (col_offset > p->D || width > p->D - col_offset)
+    throw Error(MFM_ERR_INVALID, what + ": columns [" + std::to_string(col_offset) + ", " + std::to_string(col_offset) + " + " +
+                                     std::to_string(width) + ") exceed the feature size " + std::to_string(p->D));
+  if (!o2b || !indptr) throw Error(MFM_ERR_INVALID, what + ": no index arrays");
+  const int64_t R = side == 0 ? p->U : p->I;
+  for (int64_t r = 0; r < R; r++)
+    if (o2b[r] < 0 || o2b[r] >= block_rows)
+      throw Error(MFM_ERR_INVALID, what + ": row " + std::to_string(r) + " maps to block row " + std::to_string(o2b[r]) + ", the block has " +
+                                       std::to_string(block_rows));
+  check_csr(block_rows, width, indptr, indices, what.c_str());
+  const int64_t nnz = indptr[block_rows];
+  // every stored column counts, referenced or not; nothing is marked before the whole block has passed
+  for (int64_t q = 0; q < nnz; q++) {
+    const size_t j = (size_t)(col_offset + indices[q]);
+    if (p->stored[1 - side][j]) throw Error(MFM_ERR_INVALID, "X_query and X_cand share column " + std::to_string(j));
+  }
+  {
+    std::vector<uint8_t> own((size_t)width, 0);
+    for (int64_t q = 0; q < nnz; q++) own[(size_t)indices[q]] = 1;
+    for (int64_t j = 0; j < width; j++)
+      if (own[(size_t)j] && p->stored[side][(size_t)(col_offset + j)])
+        throw Error(MFM_ERR_INVALID, what + ": column " + std::to_string(col_offset + j) + " is already stored in this side");
+  }
+  std::unique_ptr<mfm_pairs::Block> b(new mfm_pairs::Block());
+  b->off = col_offset;
+  b->width = width;
+  b->M = block_rows;
+  b->o2b.upload(o2b, (size_t)R);
+  b->ptr.upload(indptr, (size_t)block_rows + 1);
+  b->idx.upload(indices, (size_t)nnz);
+  b->val.upload(data, (size_t)nnz);
+  for (int64_t q = 0; q < nnz; q++) p->stored[side][(size_t)(col_offset + indices[q])] = 1;
+  p->blocks[side].push_back(std::move(b));
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_set_cutpoints(mfm_pairs *p, int32_t n_samples, int32_t n_cut, const double *cutpoints) {
+  PAIRS_TRY(p)
+  if (n_samples < 1 || n_cut < 1 || !cutpoints) throw Error(MFM_ERR_INVALID, "cutpoints: at least one sample and one cutpoint per sample");
+  p->cut.assign(cutpoints, cutpoints + (size_t)n_samples * (size_t)n_cut);
+  p->cut_S = n_samples;
+  p->n_cut = n_cut;
   PAIRS_CATCH(p)
 }
 

@@ -3,7 +3,10 @@
 //   score_s(u, i) = w0_s + A_s[u] + B_s[i] + sum_k P_s[u, k] Q_s[i, k],   P_s[u, k] = sum_j V_s[k, j] a_uj  (Q_s from b_i),
 //   A_s[u] = w_s . a_u + 1/2 sum_k (P_s[u, k]^2 - sum_j V_s[k, j]^2 a_uj^2)                                  (B_s likewise),
 // a dense (U, S KS) x (S KS, I) contraction on v_mfma_f64_16x16x4_f64 plus rank-one terms, with the per-row top-k selection
-// in the contraction kernel's epilogue so that the (U, I) matrix is never written.
+// in the contraction kernel's epilogue so that the (U, I) matrix is never written. A side may carry relation blocks (row r
+// additionally holds row o2b[r] of a block): their share of P_s, of the linear term and of sum V^2 x^2 is tabulated once per block row
+// and gathered (k_pairs_embed_block / k_pairs_embed_rel). Values: the mean over the samples of the score, of Phi(score), or -- ordered
+// probit -- of sum_j Phi(score - cut_s[j]), the expected class index.
 #pragma once
 #include "mfm_common.hpp"
 
@@ -69,6 +72,105 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed(const int64_t *__restr
   bias[(int64_t)s * Rpad + r] = lin + 0.5 * (sq - vv);
 }
 
+// ---- side embedding with relation blocks ---------------------------------------------------------------------------------
+// A side row is [main | B_0[o2b_0[r]] | B_1[o2b_1[r]] ...]: what a block row adds to P, to the linear term and to sum V^2 x^2 does not
+// depend on the side row that points at it, so it is computed once per block row (k_pairs_embed_block) and gathered per side row
+// (k_pairs_embed_rel): O(K * blocks) per side row instead of O(K * nnz of the expanded row).
+//
+// Table layout of one block of M rows, one allocation of S * M * (KS + 2) doubles:
+//   T[(s * M + m) * KS + k] = sum_j V_s[k, off + j] x_mj  (zero for k in [K, KS)),   then lin[s * M + m] = sum_j w_s[off + j] x_mj,
+//   then vv[s * M + m] = sum_k sum_j V_s[k, off + j]^2 x_mj^2.
+// Row-major in m with the KS factors innermost: the gathering thread owns one (side row, sample) and walks the factors, so its KS
+// reads of a block row are one contiguous run (whole cache lines: KS * 8 is a multiple of 32 bytes), and side rows that share a block
+// row -- the common case, many ratings per user -- read the same lines. A fragment-ordered table would scatter them 128 bytes apart.
+// lin and vv are read once per (side row, sample) and stay out of the T rows so that those keep their alignment.
+struct PairsBlockRef {
+  const int64_t *o2b;  // [side rows], absolute side row -> block row
+  const double *T, *lin, *vv;
+  int64_t M;
+};
+
+// One thread per (block row m, sample s). CSR with block-local columns; `off`: the block's first column in the model's feature space.
+// V is read factor-major where it lies, as k_pairs_embed does.
+__global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed_block(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
+                                                                const double *__restrict__ val, int64_t M, int64_t off,
+                                                                const double *const *__restrict__ wv, int64_t D, int K, int KS,
+                                                                double *__restrict__ T, double *__restrict__ lin_out,
+                                                                double *__restrict__ vv_out) {
+  const int64_t m = (int64_t)blockIdx.x * PAIRS_WG + threadIdx.x;
+  if (m >= M) return;
+  const int s = blockIdx.y;
+  const double *__restrict__ w = wv[s] + off;
+  const double *__restrict__ V = wv[s] + D + off;
+  const int64_t pb = rowptr[m], pe = rowptr[m + 1];
+  double *__restrict__ Trow = T + ((int64_t)s * M + m) * KS;
+  double lin = 0.0, vv = 0.0;
+  for (int64_t p = pb; p < pe; p++) lin += val[p] * w[colidx[p]];
+  for (int f = 0; f < KS; f++) {
+    double a = 0.0;
+    if (f < K) {
+      const double *__restrict__ Vf = V + (int64_t)f * D;
+      for (int64_t p = pb; p < pe; p++) {
+        const double x = val[p], v = Vf[colidx[p]];
+        a += x * v;
+        vv += (x * x) * (v * v);
+      }
+    }
+    Trow[f] = a;
+  }
+  lin_out[(int64_t)s * M + m] = lin;
+  vv_out[(int64_t)s * M + m] = vv;
+}
+
+// One thread per (side row, sample), grid and row padding of k_pairs_embed. Summation order, fixed: the main CSR part exactly as
+// k_pairs_embed forms it, then the blocks in list order (block b adds T_b[s][o2b_b[r0 + r]][.] to P, lin_b to lin, vv_b to vv), then
+// bias = lin + 1/2 (sum_k P_k^2 - vv). o2b is indexed with the ABSOLUTE side row r0 + r: a query chunk does not re-base it. P in
+// fragment order; rows [R, Rpad) and factors [K, KS) are zeros (the tables hold zeros for k >= K).
+__global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed_rel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
+                                                              const double *__restrict__ val, int64_t r0, int64_t R, int64_t Rpad,
+                                                              const double *const *__restrict__ wv, int64_t D, int K, int KS, int S,
+                                                              const PairsBlockRef *__restrict__ blk, int n_blk,
+                                                              double *__restrict__ Pf, double *__restrict__ bias) {
+  const int64_t r = (int64_t)blockIdx.x * PAIRS_WG + threadIdx.x;
+  if (r >= Rpad) return;
+  const int s = blockIdx.y;
+  const double *__restrict__ w = wv[s];
+  const double *__restrict__ V = w + D;
+  const int KS4 = KS >> 2;
+  const int64_t NK = (int64_t)S * KS4;
+  double *__restrict__ Prow = Pf + ((r >> 4) * NK + (int64_t)s * KS4) * 64 + (r & 15);
+  const bool live = r < R;
+  int64_t pb = 0, pe = 0;
+  if (live) {
+    pb = rowptr[r0 + r];
+    pe = rowptr[r0 + r + 1];
+  }
+  double lin = 0.0, sq = 0.0, vv = 0.0;
+  for (int64_t p = pb; p < pe; p++) lin += val[p] * w[colidx[p]];
+  for (int f = 0; f < KS; f++) {
+    double a = 0.0;
+    if (f < K) {
+      const double *__restrict__ Vf = V + (int64_t)f * D;
+      for (int64_t p = pb; p < pe; p++) {
+        const double x = val[p], v = Vf[colidx[p]];
+        a += x * v;
+        vv += (x * x) * (v * v);
+      }
+    }
+    if (live)
+      for (int b = 0; b < n_blk; b++) a += blk[b].T[((int64_t)s * blk[b].M + blk[b].o2b[r0 + r]) * KS + f];
+    Prow[(int64_t)(f >> 2) * 64 + (f & 3) * 16] = a;
+    sq += a * a;
+  }
+  if (live)
+    for (int b = 0; b < n_blk; b++) {
+      const int64_t e = (int64_t)s * blk[b].M + blk[b].o2b[r0 + r];
+      lin += blk[b].lin[e];
+      vv += blk[b].vv[e];
+    }
+  bias[(int64_t)s * Rpad + r] = lin + 0.5 * (sq - vv);
+}
+
 // sum over the samples, in sample order, of a side's biases (regression mode adds it once)
 __global__ __launch_bounds__(PAIRS_WG) void k_pairs_bias_sum(const double *__restrict__ bias, int S, int64_t Rpad,
                                                              double *__restrict__ out) {
@@ -107,6 +209,8 @@ struct PairsArgs {
   double *list_v;                           // [stripes][Upad][k]: each stripe's best k per row, in order, padded (-inf, -1)
   int32_t *list_i;
   double *dense;                            // [Uc][I] (the scores entry points)
+  const double *cut;                        // [S][n_cut]: the samples' cutpoints (MODE 2; last, so that the other modes' argument
+  int n_cut;                                //  offsets are what they were)
 };
 
 // LDS of the selecting kernel: per query row a buffer of CAP candidates that survived the row's threshold, its fill count and
@@ -169,7 +273,8 @@ __device__ __forceinline__ void pairs_compact(double *buf_v, int *buf_i, double 
 // accumulates the MT x NT tiles of 16 x 16 pairs at candidate tiles [w NT, (w + 1) NT) of the step. f64 C/D map: lane l, register
 // g hold (row (l >> 4) + 4 g, column l & 15). MODE 0: all samples are one inner dimension of NK k-steps, the mean biases and the
 // mean w0 are added once. MODE 1: a tile is finished per sample (KS4 k-steps), Phi applied, and summed in sample order in
-// registers. DENSE writes the tile; otherwise the values go through the per-row selection (rounds of one tile column per wave).
+// registers. MODE 2 (ordered probit): as MODE 1, but a sample adds sum_{j < n_cut} Phi(score - cut[s][j]) = sum_c c p_c, the expected
+// class index under that sample's class probabilities (P(y > j) = Phi(score - cut_j)). DENSE writes the tile; otherwise the values go through the per-row selection (rounds of one tile column per wave).
 template <int MT, int NT, int MODE, bool DENSE>
 __global__ __launch_bounds__(PAIRS_WG) void k_pairs_tile(PairsArgs a) {
   typedef PairsSel<MT> L;
@@ -218,8 +323,8 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_tile(PairsArgs a) {
     for (int m = 0; m < MT; m++) an[m] = a.NK > 0 ? pa[m][0] : 0.0;
 #pragma unroll
     for (int n = 0; n < NT; n++) bn[n] = a.NK > 0 ? pq[n][0] : 0.0;
-    const int n_pass = MODE == 1 ? a.S : 1;
-    const int64_t per_pass = MODE == 1 ? (int64_t)a.KS4 : a.NK;
+    const int n_pass = MODE != 0 ? a.S : 1;
+    const int64_t per_pass = MODE != 0 ? (int64_t)a.KS4 : a.NK;
     int64_t ks = 0;
     for (int s = 0; s < n_pass; s++) {
       pairs_d4 acc[MT][NT];
@@ -244,7 +349,7 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_tile(PairsArgs a) {
 #pragma unroll
           for (int n = 0; n < NT; n++) acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[m], bc[n], acc[m][n], 0, 0, 0);
       }
-      if (MODE == 1) {
+      if (MODE != 0) {
         const double w0 = a.w0s[s];
         double bb[NT];
 #pragma unroll
@@ -257,7 +362,12 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_tile(PairsArgs a) {
 #pragma unroll
             for (int n = 0; n < NT; n++) {
               const double t = ((w0 + ab) + bb[n]) + acc[m][n][g];
-              tot[m][n][g] += (erf(t * 0.70710678118654752440) + 1.0) / 2.0;
+              if constexpr (MODE == 2) {
+                const double *__restrict__ cs = a.cut + (size_t)s * a.n_cut;
+                for (int j = 0; j < a.n_cut; j++) tot[m][n][g] += (erf((t - cs[j]) * 0.70710678118654752440) + 1.0) / 2.0;
+              } else {
+                tot[m][n][g] += (erf(t * 0.70710678118654752440) + 1.0) / 2.0;
+              }
             }
           }
       } else {

@@ -314,37 +314,54 @@ class _PairScoringMixin:
     """Ranking with a fitted model: scores of every (query row, candidate row) pair and the per-query top-k, computed on the
     device without materialising the pair rows. Regressors score the posterior-mean prediction, classifiers the
     mean over the samples of Phi(score) -- what predict / predict_proba return for the design row X_query[u] + X_cand[i]. The
-    variational estimators have one sample, the mean model.
+    variational estimators have one sample, the mean model. MyFMOrderedProbit scores the posterior mean of the expected class
+    index, sum_c c p_c per sample with that sample's cutpoints (group 0): predict_proba(pair rows) @ arange(n_class), from the
+    device store and from host samples after unpickling alike.
 
-    Both arguments are sparse matrices in the model's full feature space, (U, D) and (I, D) with D the fitted feature size;
-    either side may hold empty rows, multi-hot rows and non-unit values, but no column may be stored in both (ValueError).
-    Not covered: MyFMOrderedProbit; relation-block inputs for the two sides; row-sharded operation (the model is replicated,
-    so each rank can call this on its own queries). The arguments are validated on the host before the device is touched."""
+    Without block arguments both sides are sparse matrices in the model's full feature space, (U, D) and (I, D) with D the fitted
+    feature size. A model fitted with relation blocks has rows [X | B_0[idx_0] | B_1[idx_1] ...]; its sides are given as main
+    matrices of the main width plus X_rel_query / X_rel_cand, each either empty (no blocks on that side) or a list with one entry
+    per block position of the model: a RelationBlock whose mapper has one entry per row of that side, or None where the side
+    holds nothing at that position (a user block is [ub, None] on the query side and [None, ib] on the candidate side). Main
+    width + the blocks' widths must equal the feature size; a position that is None on both sides, two blocks of different
+    width at one position and a mapper of the wrong size are ValueErrors. A block row's share of the embedding is computed once
+    and gathered by the side rows that point at it.
 
-    def _pair_sides(self, X_query, X_cand):
+    Either side may hold empty rows, multi-hot rows and non-unit values, but no column of the feature space may be stored in
+    both, block columns included and referenced by a side row or not (ValueError naming the column in model coordinates).
+    Not covered: row-sharded operation (the model is replicated, so each rank can call this on its own queries). The arguments
+    are validated on the host before the device is touched."""
+
+    def _pair_sides(self, X_query, X_cand, X_rel_query, X_rel_cand):
         predictor = self._fetch_predictor()
         if X_query is None or X_cand is None:
             raise ValueError("X_query and X_cand must be given.")
-        return predictor, _as_csr(X_query, 0), _as_csr(X_cand, 0)
+        rels = []
+        for name, rel in (("X_rel_query", X_rel_query), ("X_rel_cand", X_rel_cand)):
+            rel = [] if rel is None else list(rel)
+            if any(r is not None and not isinstance(r, RelationBlock) for r in rel):
+                raise ValueError("%s must hold RelationBlock or None entries" % name)
+            rels.append(rel)
+        return predictor, _as_csr(X_query, 0), _as_csr(X_cand, 0), rels[0], rels[1]
 
-    def predict_pairs(self, X_query, X_cand):
+    def predict_pairs(self, X_query, X_cand, X_rel_query=[], X_rel_cand=[]):
         """(U, I) array of the value of every pair. U * I > 2^24 is refused (ValueError): use predict_topk."""
-        predictor, Xq, Xc = self._pair_sides(X_query, X_cand)
-        return predictor.predict_pairs(Xq, Xc)
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        return predictor.predict_pairs(Xq, Xc, rq, rc)
 
-    def predict_topk(self, X_query, X_cand, k: int, exclude=None):
+    def predict_topk(self, X_query, X_cand, k: int, exclude=None, X_rel_query=[], X_rel_cand=[]):
         """Per query row the k candidates of largest value: (indices int64 (U, k), scores float64 (U, k)), each row ordered by
         (value descending, candidate index ascending). `exclude`: optional (U, I) scipy sparse matrix whose stored positions
         are pairs to leave out (the stored values are ignored). Where fewer than k candidates remain the tail is index -1,
         score -inf. 1 <= k <= 256, else ValueError."""
-        predictor, Xq, Xc = self._pair_sides(X_query, X_cand)
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
         if isinstance(k, bool) or int(k) != k:
             raise ValueError("k must be an integer in [1, 256]")
         if exclude is not None:
             exclude = sps.csr_matrix(exclude)
             if exclude.shape != (Xq.shape[0], Xc.shape[0]):
                 raise ValueError("exclude must have shape (n_queries, n_candidates)")
-        return predictor.predict_topk(Xq, Xc, int(k), exclude)
+        return predictor.predict_topk(Xq, Xc, int(k), exclude, rq, rc)
 
 
 class MyFMGibbsBase(_FMEstimatorBase):
@@ -478,8 +495,9 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(MyFMGibbsBase):
-    """Bayesian FM ordinal regression (gibbs.py:374-543)."""
+class MyFMOrderedProbit(_PairScoringMixin, MyFMGibbsBase):
+    """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
+    class index (see _PairScoringMixin)."""
 
     _task_type = TaskType.ORDERED
 

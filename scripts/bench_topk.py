@@ -3,10 +3,21 @@
   (b) predict_topk's device path (mfm_pairs_topk_store) on the same samples;
 for U = 4096 queries, then (b) alone for all users. The samples are random draws pushed into a device store (what a fit keeps);
 the model's quality plays no role in the timing. Every timing: one warm-up, `reps` repetitions, median and min .. max.
-Writes the report to stdout and, with --out FILE, to that file."""
+Writes the report to stdout and, with --out FILE, to that file.
+
+--rel-blocks: both sides carry multi-hot relation blocks (config 5's block shapes, scaled by --rel-scale: the query side a
+user-side block of 10 entries per row and a context block of 5, the candidate side an item-side block of 10), and the script
+times (a) the sides expanded on the host into flat matrices, run through the path without blocks, against (b) the block
+arguments of mfm_pairs_add_block. The embedding kernels' share of the call is taken from a kernel trace: each variant is run once
+more in a child process under `rocprofv3 --kernel-trace --stats` (skipped, and said so, where rocprofv3 is not installed)."""
 import argparse
+import csv
+import glob
 import os
+import shutil
+import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -28,6 +39,9 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--reps-materialised", type=int, default=3)
 ap.add_argument("--skip-materialised", action="store_true")
 ap.add_argument("--out", default=None)
+ap.add_argument("--rel-blocks", action="store_true", help="relation-block sides: expanded flat matrices against block arguments")
+ap.add_argument("--rel-scale", type=float, default=0.02, help="scale of config 5's block shapes (1.0: 500 000 users, 50 000 items)")
+ap.add_argument("--rel-variant", choices=["flat", "blocks"], default=None, help=argparse.SUPPRESS)  # (the traced child runs one variant once)
 args = ap.parse_args()
 NU, NI, K, S, U, k = args.users, args.items, args.rank, args.samples, args.queries, args.k
 D = NU + NI
@@ -48,6 +62,111 @@ def timed(fn, reps):
         ts.append(time.perf_counter() - t0)
     return r, float(np.median(ts)), min(ts), max(ts)
 
+
+def write_out():
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def rel_blocks():
+    """config 5's blocks, scaled: feature space [user one-hot | item one-hot | user-side block | context block | item-side block]"""
+    rng = np.random.default_rng(0)
+    nu, ni = max(1000, int(500_000 * args.rel_scale)), max(200, int(50_000 * args.rel_scale))
+    U = args.queries
+
+    def block(n_rows, n_cols, per_row):
+        cols = np.sort(rng.integers(0, n_cols, size=(n_rows, per_row)), axis=1)
+        keep = np.ones_like(cols, dtype=bool)
+        keep[:, 1:] = cols[:, 1:] != cols[:, :-1]
+        rows = np.repeat(np.arange(n_rows), per_row).reshape(n_rows, per_row)
+        return sps.csr_matrix((np.full(keep.sum(), 1.0 / np.sqrt(per_row)), (rows[keep], cols[keep])), shape=(n_rows, n_cols))
+
+    ub, cb, ib = block(nu, 2000, 10), block(1000, 200, 5), block(ni, 1000, 10)
+    D0 = nu + ni
+    offs = [D0, D0 + 2000, D0 + 2200]
+    Dr = D0 + 3200
+    users = rng.integers(0, nu, size=U)  # (a user may be asked for more than once, in several contexts)
+    ctx = rng.integers(0, 1000, size=U)
+    Xq = sps.csr_matrix((np.ones(U), (np.arange(U), users)), shape=(U, Dr))
+    Xc = sps.csr_matrix((np.ones(ni), (np.arange(ni), nu + np.arange(ni))), shape=(ni, Dr))
+    rel_q = [(offs[0], users, ub), (offs[1], ctx, cb)]
+    rel_c = [(offs[2], np.arange(ni), ib)]
+
+    def widen(B, off):
+        B = sps.coo_matrix(B)
+        return sps.csr_matrix((B.data, (B.row, B.col + off)), shape=(B.shape[0], Dr))
+
+    store = _capi.Store(Dr, K)
+    for _ in range(S):
+        store.push(float(rng.normal()), rng.normal(size=Dr) * 0.3, rng.normal(size=(Dr, K)) * 0.2)
+
+    def flat():
+        Fq = Xq + widen(ub[users], offs[0]) + widen(cb[ctx], offs[1])
+        Fc = Xc + widen(ib, offs[2])
+        P = _capi.Pairs(Fq, Fc)
+        r = P.topk_store(store, k)
+        P.close()
+        return r
+
+    def blocks():
+        P = _capi.Pairs(Xq, Xc, rel_query=rel_q, rel_cand=rel_c)
+        r = P.topk_store(store, k)
+        P.close()
+        return r
+
+    if args.rel_variant:  # the traced child: one call, nothing reported
+        (flat if args.rel_variant == "flat" else blocks)()
+        return
+    say("ranking with relation-block sides (config 5's blocks at scale %g): %d queries of %d users x %d items, rank %d, %d samples, "
+        "k = %d; side rows hold 1 + 10 + 5 (query) and 1 + 10 (candidate) entries" % (args.rel_scale, U, nu, ni, K, S, k))
+    (idx_a, val_a), med_a, lo_a, hi_a = timed(flat, args.reps)
+    (idx_b, val_b), med_b, lo_b, hi_b = timed(blocks, args.reps)
+    say("(a) sides expanded on the host, path without blocks (expansion, upload and call): median %.4f s (min %.4f, max %.4f, %d reps)"
+        % (med_a, lo_a, hi_a, args.reps))
+    say("(b) block arguments (upload and call):                                            median %.4f s (min %.4f, max %.4f, %d reps)"
+        % (med_b, lo_b, hi_b, args.reps))
+    say("    max |top-k value difference| = %.2e, rows whose index lists agree: %d of %d"
+        % (np.abs(val_a - val_b).max(), int(np.all(idx_a == idx_b, axis=1).sum()), U))
+    scale = 1.0 + 2 * 0.3 * 6 * 4 + K * (2 * 0.2 * 6 * 4) ** 2
+    if not np.all(np.abs(val_a - val_b) <= 1e-10 * scale):
+        raise SystemExit("the block path's values differ from the expanded path's")
+    prof = shutil.which("rocprofv3")
+    if not prof:
+        say("    embedding kernels' share of the call: not measured (rocprofv3 not found)")
+        return
+    for name, variant in (("(a)", "flat"), ("(b)", "blocks")):
+        tmp = tempfile.mkdtemp(prefix="topk_rel_")
+        try:
+            cmd = [prof, "--kernel-trace", "--stats", "-d", tmp, "-o", "t", "--output-format", "csv", "--", sys.executable,
+                   os.path.abspath(__file__), "--rel-blocks", "--rel-variant", variant, "--rel-scale", str(args.rel_scale), "--rank", str(K),
+                   "--samples", str(S), "--queries", str(args.queries), "--k", str(k)]
+            subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            tot, emb, parts = 0.0, 0.0, {}
+            for fn in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
+                with open(fn) as f:
+                    for row in csv.DictReader(f):
+                        ns = float(row["TotalDurationNs"])
+                        tot += ns
+                        if "k_pairs_embed" in row["Name"]:
+                            emb += ns
+                            short = row["Name"].split("(")[0].split("::")[-1]
+                            parts[short] = parts.get(short, 0.0) + ns
+            if tot > 0:
+                say("    %s kernel time %.3f ms, of it embedding %.3f ms = %.1f %% (%s)"
+                    % (name, tot / 1e6, emb / 1e6, 100 * emb / tot, ", ".join("%s %.3f ms" % (n, v / 1e6) for n, v in sorted(parts.items()))))
+            else:
+                say("    %s embedding kernels' share: not measured (the trace held no kernel statistics)" % name)
+        except (subprocess.CalledProcessError, OSError, KeyError, ValueError) as e:
+            say("    %s embedding kernels' share: not measured (%s)" % (name, type(e).__name__))
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+
+
+if args.rel_blocks:
+    rel_blocks()
+    write_out()
+    sys.exit(0)
 
 rng = np.random.default_rng(0)
 store = _capi.Store(D, K)
@@ -104,6 +223,4 @@ if NU > U:
     say("(b) predict_topk, all %d users x %d items: median %.3f s (min %.3f, max %.3f) -- %.1f TFLOP/s fp64 over the whole call, "
         "%.0f %% of the MFMA peak" % (NU, NI, med, lo, hi, flop / med / 1e12, 100 * flop / med / FP64_MFMA_PEAK))
     pairs.close()
-if args.out:
-    with open(args.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+write_out()
