@@ -378,6 +378,25 @@ int mfm_store_get(mfm_store *st, int32_t idx, double *w0, double *w, double *V);
 int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t n_cut,
                              const double *cutpoints, double *out);
 
+/* ---- posterior predictive summaries over the kept samples (csrc/mfm_dist.hpp) ------------------------------
+ * Per design row, over samples [first, first + count) of a store (or n_samples host samples in the layout of
+ * mfm_design_predict), with v_s = score_s (mode 0) or Phi(score_s) (mode 1):
+ *   out_mean[N]       (v_0 + v_1 + ...) * (1 / S): bit for bit what mfm_design_predict* returns
+ *   out_std[N]        population standard deviation of the v_s; with precisions sqrt(var_s + mean_s 1 / precisions[s])
+ *   out_q[n_q * N]    row-major (n_q, N): the empirical quantile of the v_s at probs[q] under numpy's "linear" rule (exact
+ *                     order statistics, sorted on the device); with precisions[S] (mode 0 only; z[q] = Phi^-1(probs[q]), probs
+ *                     strictly inside (0, 1)) the quantile of the mixture mean_s N(score_s, 1 / precisions[s])
+ * n_q <= 32; n_q > 0 needs count <= 4096 (MFM_ERR_INVALID otherwise); n_q = 0 computes the moments alone, for any count.
+ * precisions / z may be NULL (no noise). tile_rows / chunk_samples force the row tile and the sample chunk of the device passes
+ * (0: automatic); the results do not depend on them. mfm_design_summary uploads all its samples at once, S * D * (K + 1) * 8 bytes,
+ * under the limit of mfm_store_reserve (MFM_ERR_RUNTIME beyond it).                                                         */
+int mfm_design_summary_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t n_q,
+                             const double *probs, const double *precisions, const double *z, int64_t tile_rows,
+                             int32_t chunk_samples, double *out_mean, double *out_std, double *out_q);
+int mfm_design_summary(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t mode, int32_t n_q, const double *probs, const double *precisions, const double *z,
+                       int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q);
+
 /* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
  * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), each optionally with relation blocks
  * (below); pair (u, i) is the design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column

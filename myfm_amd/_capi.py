@@ -41,6 +41,7 @@ SYMBOLS = [
     "mfm_pairs_create", "mfm_pairs_destroy", "mfm_pairs_last_error", "mfm_pairs_set_exclude", "mfm_pairs_set_scratch_bound",
     "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
     "mfm_pairs_set_cutpoints",
+    "mfm_design_summary_store", "mfm_design_summary",
 ]
 
 _lib = None
@@ -162,6 +163,8 @@ def lib():
     L.mfm_store_push_host.argtypes = [vp, dbl, P, P]
     L.mfm_store_get.argtypes = [vp, i32, C.POINTER(dbl), P, P]
     L.mfm_design_predict_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P]
+    L.mfm_design_summary_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, P, i64, i32, P, P, P]
+    L.mfm_design_summary.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, P, i64, i32, P, P, P]
     L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
@@ -579,6 +582,29 @@ class Design:
             _raise(rc, lib().mfm_design_last_error(self.h))
         return out
 
+    def summary(self, samples, mode=0, quantiles=(), precisions=None, tile_rows=0, chunk_samples=0):
+        """samples as predict; mode 0 score, 1 Phi(score). Returns (mean[N], std[N], quantiles[Q, N]) over the samples;
+        precisions[S]: of the mixture mean_s N(score_s, 1 / precisions[s]) (mfm_design_summary)."""
+        K, S, w0s, ws, Vs = _pack_samples(samples)
+        probs, prec, z, mean, std, q = _summary_args(self.N, quantiles, precisions)
+        rc = lib().mfm_design_summary(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, len(probs), _p(probs), _p(prec), _p(z),
+                                      int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
+        if rc:
+            _raise(rc, lib().mfm_design_last_error(self.h))
+        return mean, std, q
+
+
+def _summary_args(N, quantiles, precisions):
+    """probabilities, precisions, Phi^-1 of the probabilities (noise only) and the three output arrays of a summary call"""
+    from statistics import NormalDist
+
+    probs = _f64(quantiles).reshape(-1)
+    prec = None if precisions is None else _f64(precisions).reshape(-1)
+    z = None
+    if prec is not None:
+        z = _f64([NormalDist().inv_cdf(float(p)) if 0.0 < p < 1.0 else np.nan for p in probs])
+    return probs, prec, z, np.empty(N), np.empty(N), np.empty((len(probs), N))
+
 
 class Store:
     """posterior samples resident on the GPU (mfm_store_*)"""
@@ -631,6 +657,16 @@ class Store:
         if rc:
             _raise(rc, lib().mfm_design_last_error(design.h))
         return out
+
+    def summary(self, design, mode=0, quantiles=(), precisions=None, first=0, count=None, tile_rows=0, chunk_samples=0):
+        """Design.summary over the resident samples [first, first + count) (mfm_design_summary_store)"""
+        count = len(self) - first if count is None else count
+        probs, prec, z, mean, std, q = _summary_args(design.N, quantiles, precisions)
+        rc = lib().mfm_design_summary_store(design.h, self.h, first, count, mode, len(probs), _p(probs), _p(prec), _p(z),
+                                            int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
+        if rc:
+            _raise(rc, lib().mfm_design_last_error(design.h))
+        return mean, std, q
 
 
 def _pack_samples(samples):

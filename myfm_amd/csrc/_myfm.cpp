@@ -801,6 +801,72 @@ struct Predictor {
     run_pairs(Xq, Xc, rq, rc, offsets, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), score.mutable_data(), nullptr);
     return py::make_tuple(idx, score);
   }
+  // ---- posterior predictive summaries (not in the reference): mean, standard deviation and quantiles over the samples -------
+  // Phi^-1(p), 0 < p < 1, by bisection of 0.5 erfc(-z / sqrt 2) down to neighbouring doubles (it only places the root bracket
+  // of the device's mixture solve)
+  static double std_normal_quantile(double p) {
+    double lo = -40.0, hi = 40.0;
+    for (int it = 0; it < 200; it++) {
+      const double mid = 0.5 * (lo + hi);
+      if (!(mid > lo && mid < hi)) break;
+      if (0.5 * std::erfc(-mid * 0.70710678118654752440) < p)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    return 0.5 * (lo + hi);
+  }
+  // (mean[N], std[N], quantiles[Q, N]); precisions: the noise precision alpha_s of every sample (regression), or None.
+  // tile_rows / chunk_samples force the device passes' row tile and sample chunk (0: automatic). Every argument is checked here,
+  // before the device is looked for.
+  py::tuple predict_dist(const py::object &Xo, const py::object &relso, const py::object &quantileso, const py::object &precisionso,
+                         int64_t tile_rows, int chunk_samples) const {
+    Csr X = csr_from_py(Xo);
+    Relations rels = relations_from_py(relso);
+    check_input(X, rels);
+    if (type == TaskType::ORDERED) throw std::invalid_argument("predict_dist covers regression and classification, not ordered probit");
+    auto qa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(quantileso);
+    if (!qa || qa.ndim() != 1) throw std::invalid_argument("quantiles must be a 1-D sequence of probabilities");
+    const int n_q = (int)qa.shape(0);
+    if (n_q > 32) throw std::invalid_argument("at most 32 quantiles per call");
+    vector<double> probs(qa.data(), qa.data() + n_q), prec, z;
+    const bool noise = !precisionso.is_none();
+    for (double p : probs) {
+      if (!(p >= 0.0 && p <= 1.0)) throw std::invalid_argument("quantiles must lie in [0, 1]");
+      if (noise && !(p > 0.0 && p < 1.0)) throw std::invalid_argument("with noise the quantiles must lie strictly inside (0, 1)");
+    }
+    if (noise) {
+      if (type != TaskType::REGRESSION) throw std::invalid_argument("noise precisions apply to regression only");
+      auto pa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(precisionso);
+      if (!pa || pa.ndim() != 1 || (size_t)pa.shape(0) != samples.size())
+        throw std::invalid_argument("precisions must hold one value per kept sample");
+      prec.assign(pa.data(), pa.data() + pa.shape(0));
+      for (double a : prec)
+        if (!(a > 0.0) || !std::isfinite(a)) throw std::invalid_argument("precisions must be positive and finite");
+      for (double p : probs) z.push_back(std_normal_quantile(p));
+    }
+    if (tile_rows < 0 || chunk_samples < 0) throw std::invalid_argument("tile_rows and chunk_samples must be non-negative");
+    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
+    if (n_q > 0 && samples.size() > 4096)
+      throw std::invalid_argument("quantiles are computed over at most 4096 kept samples, this predictor holds " + std::to_string(samples.size()));
+    py::array_t<double> mean((py::ssize_t)X.rows), sd((py::ssize_t)X.rows), q({(py::ssize_t)n_q, (py::ssize_t)X.rows});
+    const int mode = type == TaskType::CLASSIFICATION ? 1 : 0;
+    DeviceDesign dd(X, rels);
+    int first = 0, code;
+    if (auto st = resident(&first)) {  // the unmodified entries of the device store: in place, as run_predict
+      code = mfm_design_summary_store(dd.d, st->st, first, (int)samples.size(), mode, n_q, probs.data(), noise ? prec.data() : nullptr,
+                                      noise ? z.data() : nullptr, tile_rows, chunk_samples, mean.mutable_data(), sd.mutable_data(),
+                                      q.mutable_data());
+    } else {
+      vector<double> w0s, ws, Vs;
+      pack(w0s, ws, Vs);
+      code = mfm_design_summary(dd.d, (int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, n_q, probs.data(),
+                                noise ? prec.data() : nullptr, noise ? z.data() : nullptr, tile_rows, chunk_samples, mean.mutable_data(),
+                                sd.mutable_data(), q.mutable_data());
+    }
+    if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
+    return py::make_tuple(mean, sd, q);
+  }
   // predictor.hpp:78-124
   py::array_t<double> predict_parallel_oprobit(const py::object &Xo, const py::object &relso, size_t n_workers,
                                                size_t cutpoint_index) const {
@@ -2581,6 +2647,13 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk", &Predictor::predict_topk, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def_property_readonly("resident",
+                             [](const Predictor &p) {
+                               int first = 0;
+                               return (bool)p.resident(&first);
+                             })  // the samples are read in place from the device store (else: uploaded from the host)
+      .def("predict_dist", &Predictor::predict_dist, py::arg("X"), py::arg("rels"), py::arg("quantiles"), py::arg("precisions") = py::none(),
+           py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def(py::pickle(
           [](const Predictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {

@@ -1,0 +1,370 @@
+// mfm_dist.hpp -- posterior predictive summaries (not in the reference): per test row the mean, the population
+// standard deviation and empirical quantiles of the S kept samples' values (score, or Phi(score)), and with per-sample noise
+// precisions the moments and quantiles of the mixture mean_s N(score_s, 1 / alpha_s). Included by mfm_hip.hip after
+// mfm_predict.hpp.
+//
+// Rows are processed in tiles of T rows. Stage 1 writes the values of a tile, all samples, into a sample-major scratch
+// [S][T] (k_score_store MODE 3 / 4, or the per-sample pass and k_dist_copy for designs with relation blocks); stage 2,
+// k_row_summary, reduces every row of the tile. Everything is fp64, there are no atomics, every sum runs in sample order.
+#pragma once
+
+namespace mfm {
+
+constexpr int DIST_MAX_Q = 32;             // quantiles per call
+constexpr int DIST_MAX_S = 4096;           // samples per call when quantiles are asked for (a row's values are sorted in LDS)
+constexpr size_t DIST_SCRATCH_BYTES = (size_t)256 << 20;
+constexpr int DIST_LDS_BYTES = 48 * 1024;  // per workgroup, where more than one row fits
+constexpr int DIST_LDS_MAX_BYTES = (2 * DIST_MAX_S + 1) * 8;  // one row of DIST_MAX_S samples and their sqrt(alpha)
+constexpr int DIST_MAX_ROWS = 32;          // rows per workgroup of the LDS form
+
+// scratch[t] = score[t] | Phi(score[t]) (the expression of k_accumulate_pred): one sample's slot of a row tile
+__global__ __launch_bounds__(WG) void k_dist_copy(const double *__restrict__ score, double *__restrict__ scratch, int64_t n, int mode) {
+  const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x;
+  if (t >= n) return;
+  double v = score[t];
+  if (mode == 1) v = (erf(v * 0.70710678118654752440) + 1.0) / 2.0;
+  scratch[t] = v;
+}
+
+struct RowSummaryArgs {
+  const double *scratch;  // [S][Tn]
+  const double *sqa;      // [S] sqrt(alpha_s) (noise)
+  double *mean, *sd, *q;  // of the tile's first row; q[n_q][ldq]
+  int64_t Tn, ldq;
+  int S, P, stride, R;    // P: S padded to a power of two (sorted form), stride: doubles per row in LDS, R: rows per workgroup
+  int n_q, noise;
+  double inv_S, noise_var;  // 1 / S, mean_s 1 / alpha_s
+  int lo[DIST_MAX_Q];       // empirical: the lower order statistic of quantile q ...
+  double g[DIST_MAX_Q];     // ... and the weight of the upper one; noise: Phi^-1(p_q)
+  double p[DIST_MAX_Q];
+};
+
+// mean = (v_0 + v_1 + ...) * (1 / S), the sum and the factor of the predictors; the variance two-pass about the mean of
+// the values shifted by v_0 (exactly 0 when all values are equal, and no cancellation against a large common offset)
+template <class Get>
+__device__ __forceinline__ void dist_moments(const Get &v, int S, double inv_S, double &mean, double &var) {
+  const double v0 = v(0);
+  double sum = v0, dsum = 0.0;
+  for (int s = 1; s < S; s++) {
+    const double x = v(s);
+    sum += x;
+    dsum += x - v0;
+  }
+  mean = sum * inv_S;
+  const double md = dsum * inv_S;
+  double ss = 0.0;
+  for (int s = 0; s < S; s++) {
+    const double e = (v(s) - v0) - md;
+    ss += e * e;
+  }
+  var = ss * inv_S;
+}
+
+// y with mean_s Phi((y - v_s) sqa_s) = p: Newton steps kept inside a bracket that every evaluation shrinks, a bisection step
+// wherever Newton leaves it (or the density underflows); at most DIST_SOLVE_STEPS evaluations, the last 140 of them plain
+// bisection (which ends at neighbouring doubles). Ends after a Newton step below 1e-11 of the scale: the step after it
+// (quadratic convergence) is below the evaluation's rounding.
+constexpr int DIST_SOLVE_STEPS = 200;
+__device__ __forceinline__ double dist_mixture_quantile(const double *v, const double *sqa, int S, double inv_S, double z, double p) {
+  double lo = v[0] + z / sqa[0], hi = lo;
+  for (int s = 1; s < S; s++) {
+    const double y = v[s] + z / sqa[s];
+    lo = fmin(lo, y);
+    hi = fmax(hi, y);
+  }
+  if (!(lo < hi)) return lo;
+  const double width = hi - lo;
+  double y = 0.5 * (lo + hi);
+  for (int it = 0; it < DIST_SOLVE_STEPS; it++) {
+    double F = 0.0, f = 0.0;
+    for (int s = 0; s < S; s++) {
+      const double a = sqa[s];
+      const double x = (y - v[s]) * a;
+      F += 0.5 * erfc(-x * 0.70710678118654752440);
+      f += a * exp(-0.5 * x * x);
+    }
+    F *= inv_S;
+    f *= inv_S * 0.39894228040143267794;
+    const double r = F - p;
+    if (r == 0.0) break;
+    if (r < 0.0)
+      lo = y;
+    else
+      hi = y;
+    double yn = y - r / f;
+    const bool newton = it < DIST_SOLVE_STEPS - 140 && f > 0.0 && yn > lo && yn < hi;
+    if (!newton) yn = 0.5 * (lo + hi);
+    if (!(yn > lo && yn < hi)) break;  // lo and hi are neighbours
+    const double step = fabs(yn - y);
+    y = yn;
+    if (newton && step <= 1e-11 * (fabs(y) + width)) break;
+  }
+  return y;
+}
+
+// One launch per row tile. LDS form (quantiles asked for): a workgroup brings R rows' S values into LDS (row stride odd: the
+// row-per-lane phases are conflict-free), lane r computes row r's moments, then either all R rows are sorted in place by one
+// bitonic network over P = S padded with +inf (every compare-exchange of a step spread over the workgroup) and thread (q, r)
+// interpolates quantile q of row r as numpy's "linear" rule does, or (noise) thread (q, r) solves the mixture quantile with
+// the row's scores and sqrt(alpha_s) read from LDS (the latter at one address for all lanes: a broadcast read).
+// Direct form (LDS_ROWS = false, no quantiles, any S): a thread per row reads the scratch itself.
+template <bool LDS_ROWS>
+__global__ __launch_bounds__(WG) void k_row_summary(RowSummaryArgs a) {
+  extern __shared__ double dist_lds[];
+  const int S = a.S;
+  if (!LDS_ROWS) {
+    const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x;
+    if (t >= a.Tn) return;
+    const double *__restrict__ col = a.scratch + t;
+    const int64_t Tn = a.Tn;
+    double mean, var;
+    dist_moments([&](int s) { return col[(size_t)s * Tn]; }, S, a.inv_S, mean, var);
+    a.mean[t] = mean;
+    a.sd[t] = sqrt(var + a.noise_var);
+    return;
+  }
+  const int R = a.R, st = a.stride, P = a.P;
+  const int64_t r0 = (int64_t)blockIdx.x * R;
+  const int nr = (int)(a.Tn - r0 < R ? a.Tn - r0 : R);
+  const int tid = threadIdx.x;
+  for (int i = tid; i < S * R; i += WG) {
+    const int s = i / R, r = i - s * R;
+    dist_lds[r * st + s] = r < nr ? a.scratch[(size_t)s * a.Tn + r0 + r] : 0.0;
+  }
+  double *sqa = dist_lds + R * st;  // (noise) sqrt(alpha_s) behind the rows: every lane of the solve reads the same address
+  if (!a.noise)
+    for (int i = tid; i < (P - S) * R; i += WG) {
+      const int s = i / R, r = i - s * R;
+      dist_lds[r * st + S + s] = __builtin_inf();
+    }
+  else
+    for (int s = tid; s < S; s += WG) sqa[s] = a.sqa[s];
+  __syncthreads();
+  if (tid < nr) {
+    const double *row = dist_lds + tid * st;
+    double mean, var;
+    dist_moments([&](int s) { return row[s]; }, S, a.inv_S, mean, var);
+    a.mean[r0 + tid] = mean;
+    a.sd[r0 + tid] = sqrt(var + a.noise_var);
+  }
+  if (a.noise) {
+    for (int w = tid; w < a.n_q * R; w += WG) {
+      const int q = w / R, r = w - q * R;
+      if (r < nr) a.q[(size_t)q * a.ldq + r0 + r] = dist_mixture_quantile(dist_lds + r * st, sqa, S, a.inv_S, a.g[q], a.p[q]);
+    }
+    return;
+  }
+  __syncthreads();  // (the moments read the rows in sample order)
+  const int half = P >> 1;
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int idx = tid; idx < R * half; idx += WG) {
+        const int r = idx / half, c = idx - r * half;
+        const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1));
+        double *row = dist_lds + r * st;
+        const double x = row[i], y = row[i | j];
+        if ((x > y) == ((i & k) == 0)) {
+          row[i] = y;
+          row[i | j] = x;
+        }
+      }
+      __syncthreads();
+    }
+  for (int w = tid; w < a.n_q * R; w += WG) {
+    const int q = w / R, r = w - q * R;
+    if (r >= nr) continue;
+    const double *row = dist_lds + r * st;
+    const int lo = a.lo[q], hi = lo + 1 < S ? lo + 1 : lo;
+    const double x = row[lo], y = row[hi], g = a.g[q];
+    const double d = y - x;
+    a.q[(size_t)q * a.ldq + r0 + r] = g >= 0.5 ? y - d * (1.0 - g) : x + d * g;  // (numpy's _lerp)
+  }
+}
+
+static void launch_row_summary(hipStream_t s, RowSummaryArgs &a) {
+  if (a.n_q == 0) {
+    hipLaunchKernelGGL(k_row_summary<false>, dim3((unsigned)cdiv(a.Tn, WG)), dim3(WG), 0, s, a);
+    return;
+  }
+  int P = 1;
+  while (P < a.S) P <<= 1;
+  a.P = a.noise ? a.S : P;
+  a.stride = a.P | 1;
+  // R rows of `stride` doubles, with noise S more for sqrt(alpha), within DIST_LDS_BYTES -- but never less than one row: one
+  // row of S = 4096 takes 32 776 B, with noise 65 544 B, above the default limit of dynamic LDS (opted into once per device)
+  const int aux = a.noise ? a.S : 0;
+  const int fit = (DIST_LDS_BYTES / (int)sizeof(double) - aux) / a.stride;
+  a.R = (int)std::min<int64_t>(std::max(1, std::min(DIST_MAX_ROWS, fit)), a.Tn);
+  const size_t lds = ((size_t)a.R * a.stride + aux) * sizeof(double);
+  static DeviceOnce raised;
+  if (lds > 64 * 1024 && raised.need()) {
+    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_row_summary<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DIST_LDS_MAX_BYTES));
+    raised.mark();
+  }
+  hipLaunchKernelGGL(k_row_summary<true>, dim3((unsigned)cdiv(a.Tn, a.R)), dim3(WG), lds, s, a);
+}
+
+static void design_summary_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t n_q,
+                                 const double *probs, const double *precisions, const double *z, int64_t tile_rows,
+                                 int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
+  if (count <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
+  if (first < 0 || first + count > (int)st->wv.size()) throw Error(MFM_ERR_INVALID, "sample range out of bounds");
+  if (st->device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
+  if (st->D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+  if (mode < 0 || mode > 1) throw Error(MFM_ERR_INVALID, "bad summary mode (0: score, 1: Phi(score))");
+  if (n_q < 0 || n_q > DIST_MAX_Q) throw Error(MFM_ERR_INVALID, "at most " + std::to_string(DIST_MAX_Q) + " quantiles per call");
+  if (n_q > 0 && count > DIST_MAX_S)
+    throw Error(MFM_ERR_INVALID, "quantiles are computed over at most " + std::to_string(DIST_MAX_S) + " samples, got " + std::to_string(count));
+  if (n_q > 0 && !probs) throw Error(MFM_ERR_INVALID, "quantiles asked for without their probabilities");
+  if (precisions && mode != 0) throw Error(MFM_ERR_INVALID, "noise precisions apply to scores (mode 0) only");
+  if (precisions && n_q > 0 && !z) throw Error(MFM_ERR_INVALID, "noise quantiles need Phi^-1 of their probabilities");
+  if (tile_rows < 0 || chunk_samples < 0) throw Error(MFM_ERR_INVALID, "negative tiling override");
+  for (int q = 0; q < n_q; q++) {
+    const bool inside = precisions ? probs[q] > 0.0 && probs[q] < 1.0 && std::isfinite(z[q]) : probs[q] >= 0.0 && probs[q] <= 1.0;
+    if (!inside) throw Error(MFM_ERR_INVALID, "quantile probability out of range ([0, 1]; with noise strictly inside)");
+  }
+  if (precisions)
+    for (int k = 0; k < count; k++)
+      if (!(precisions[k] > 0.0) || !std::isfinite(precisions[k])) throw Error(MFM_ERR_INVALID, "noise precisions must be positive and finite");
+  hipStream_t s = d->stream;
+  const int rank = st->K;
+  const int64_t N = d->N, D = d->D;
+  if (N == 0) return;
+  design_use_rank(d, rank, s);
+  const int64_t T = std::min<int64_t>(N, tile_rows > 0 ? tile_rows : std::max<int64_t>(1, (int64_t)(DIST_SCRATCH_BYTES / sizeof(double)) / count));
+  if (d->dist_scratch.n < (size_t)(T * count)) d->dist_scratch.alloc((size_t)(T * count));
+  const size_t out_n = (size_t)N * (2 + n_q);
+  if (d->dist_out.n < out_n) d->dist_out.alloc(out_n);
+  RowSummaryArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.scratch = d->dist_scratch.p;
+  a.ldq = N;
+  a.S = count;
+  a.n_q = n_q;
+  a.noise = precisions != nullptr;
+  a.inv_S = 1.0 / count;
+  if (precisions) {
+    std::vector<double> sq((size_t)count);
+    double nv = 0.0;
+    for (int k = 0; k < count; k++) {
+      sq[k] = std::sqrt(precisions[k]);
+      nv += 1.0 / precisions[k];
+    }
+    a.noise_var = nv * a.inv_S;
+    if (d->dist_aux.n < (size_t)count) d->dist_aux.alloc((size_t)count);
+    MFM_HIP_CHECK(hipMemcpy(d->dist_aux.p, sq.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
+    a.sqa = d->dist_aux.p;
+  }
+  for (int q = 0; q < n_q; q++) {
+    a.p[q] = probs[q];
+    if (precisions) {
+      a.g[q] = z[q];
+    } else {  // numpy's "linear" rule: position (S - 1) p between the order statistics floor and floor + 1
+      const double h = (double)(count - 1) * probs[q];
+      const double fl = std::floor(h);
+      a.lo[q] = (int)std::min<double>(fl, (double)(count - 1));
+      a.g[q] = h - fl;
+    }
+  }
+  if (st->pushed_valid) MFM_HIP_CHECK(hipStreamWaitEvent(s, st->pushed, 0));
+  const bool one_pass = d->blocks.empty() && rank <= 512;
+  int chunk = count;
+  if (one_pass) {  // (the sample chunks of mfm_design_predict_store)
+    const size_t per = (size_t)std::max<int64_t>(D * d->KS, 1) * sizeof(double);
+    chunk = chunk_samples > 0 ? std::min<int>(chunk_samples, count)
+                              : (int)std::max<size_t>(1, std::min<size_t>((size_t)count, ((size_t)512 << 20) / per));
+    if (d->vt_all.n < (size_t)chunk * (per / sizeof(double))) d->vt_all.alloc((size_t)chunk * (per / sizeof(double)));
+    std::vector<const double *> hp((size_t)count);
+    std::vector<double> hw0((size_t)count);
+    for (int k = 0; k < count; k++) {
+      hp[k] = st->wv[first + k]->p;
+      hw0[k] = st->w0[first + k];
+    }
+    if (d->wvp.n < (size_t)count) d->wvp.alloc((size_t)count);
+    if (d->w0s.n < (size_t)count) d->w0s.alloc((size_t)count);
+    MFM_HIP_CHECK(hipMemcpyAsync(d->wvp.p, hp.data(), (size_t)count * sizeof(double *), hipMemcpyHostToDevice, s));
+    MFM_HIP_CHECK(hipMemcpyAsync(d->w0s.p, hw0.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice, s));
+    MFM_HIP_CHECK(hipStreamSynchronize(s));  // (hp / hw0 are pageable host vectors of this frame)
+  }
+  int built = -1;  // the chunk whose row-major V copies vt_all holds
+  for (int64_t r0 = 0; r0 < N; r0 += T) {
+    const int64_t Tn = std::min<int64_t>(T, N - r0);
+    if (one_pass) {
+      for (int c0 = 0; c0 < count; c0 += chunk) {
+        const int C = std::min(chunk, count - c0);
+        if (built != c0 && rank > 0 && D > 0) {
+          hipLaunchKernelGGL(k_build_vt_batch, dim3((unsigned)cdiv(D, 32), (unsigned)cdiv(d->KS, 32), (unsigned)C), dim3(WG), 0, s,
+                             (const double *const *)d->wvp.p + c0, D, rank, d->KS, d->vt_all.p);
+          built = c0;
+        }
+        ScoreStoreArgs sa;
+        sa.wv = (const double *const *)d->wvp.p + c0;
+        sa.vt_all = d->vt_all.p;
+        sa.w0 = d->w0s.p + c0;
+        sa.cut = nullptr;
+        sa.S = C;
+        sa.n_cut = 0;
+        sa.first = 1;
+        sa.scale = 1.0;
+        launch_score_store_rows(s, 3 + mode, d->X, score_rows(d->X, r0, Tn), sa, D, rank, d->KS, d->dist_scratch.p + (size_t)c0 * Tn);
+      }
+    } else {
+      // relation blocks: the per-sample pass over the whole design, of which this tile's rows are kept (a design of more
+      // than one tile is scored once per tile)
+      for (int k = 0; k < count; k++) {
+        const double *w = st->wv[first + k]->p, *V = w + D;
+        score_design(s, d->timing, 1, d->X, d->blocks, D, rank, d->KS, st->w0[first + k], w, V, d->Vt.p, nullptr, nullptr, d->score.p);
+        hipLaunchKernelGGL(k_dist_copy, dim3((unsigned)cdiv(Tn, WG)), dim3(WG), 0, s, d->score.p + r0, d->dist_scratch.p + (size_t)k * Tn, Tn,
+                           mode);
+      }
+    }
+    MFM_HIP_CHECK(hipGetLastError());
+    a.Tn = Tn;
+    a.mean = d->dist_out.p + r0;
+    a.sd = d->dist_out.p + N + r0;
+    a.q = d->dist_out.p + 2 * N + r0;
+    launch_row_summary(s, a);
+    MFM_HIP_CHECK(hipGetLastError());
+  }
+  MFM_HIP_CHECK(hipMemcpyAsync(out_mean, d->dist_out.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+  MFM_HIP_CHECK(hipMemcpyAsync(out_std, d->dist_out.p + N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (n_q) MFM_HIP_CHECK(hipMemcpyAsync(out_q, d->dist_out.p + 2 * N, (size_t)N * n_q * sizeof(double), hipMemcpyDeviceToHost, s));
+  MFM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+}  // namespace mfm
+
+extern "C" {
+
+int mfm_design_summary_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t n_q,
+                             const double *probs, const double *precisions, const double *z, int64_t tile_rows,
+                             int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
+  MFM_TRY(d)
+  design_summary_store(d, st, first, count, mode, n_q, probs, precisions, z, tile_rows, chunk_samples, out_mean, out_std, out_q);
+  MFM_CATCH(d)
+}
+
+// host samples: uploaded into a store of this call's own, then as above (the same kernels over the same chunks)
+// (all S samples at once, through mfm_store_reserve: refused with its message beyond MFM_STORE_MAX_FRACTION of the free device memory,
+//  where mfm_design_predict, which streams one sample at a time, still runs)
+int mfm_design_summary(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t mode, int32_t n_q, const double *probs, const double *precisions, const double *z,
+                       int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
+  MFM_TRY(d)
+  if (n_samples <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
+  if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
+  mfm_store st;
+  st.device = d->device;
+  st.D = d->D;
+  st.K = rank;
+  const size_t D = (size_t)d->D;
+  if (mfm_store_reserve(&st, n_samples) != MFM_OK) throw Error(MFM_ERR_RUNTIME, st.err);  // (one allocation, not one per sample)
+  for (int k = 0; k < n_samples; k++) {
+    const int code = mfm_store_push_host(&st, w0s[k], ws + (size_t)k * D, Vs + (size_t)k * D * rank);
+    if (code != MFM_OK) throw Error(code, st.err);
+  }
+  design_summary_store(d, &st, 0, n_samples, mode, n_q, probs, precisions, z, tile_rows, chunk_samples, out_mean, out_std, out_q);
+  MFM_CATCH(d)
+}
+
+}  // extern "C"

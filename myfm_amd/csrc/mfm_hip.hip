@@ -2766,6 +2766,7 @@ int mfm_host_column_levels(int64_t n_rows, int64_t n_cols, const int64_t *indptr
 #include "mfm_tasks.hpp"    // classification / ordered-probit entry points
 #include "mfm_latent_host.hpp"  // ... their exact latent draws on the device stream
 #include "mfm_predict.hpp"  // mfm_design_* entry points
+#include "mfm_dist.hpp"     // ... and the posterior summaries over the kept samples
 
 // the samples [first, first + count) as another translation unit reads them in place (declared in mfm_pairs.hpp; defined here, in the one unit that knows mfm_store)
 namespace mfm {

@@ -60,6 +60,9 @@ __global__ __launch_bounds__(WG) void k_build_vt_batch(const double *const *__re
 // row's scores never leave the registers, mean score / mean Phi(score) / mean class probabilities are accumulated in sample
 // order in registers and written once. MODE 0 / 1 / 2 as k_accumulate_pred / k_accumulate_oprobit. `first` = 0: continue
 // the sums a previous chunk of samples left in `out`.
+// MODE 3 / 4 (mfm_dist.hpp) accumulate nothing: sample smp's score / Phi(score) of row t is stored to out[smp * N + t], the
+// sample-major scratch of the posterior summaries. Their caller passes the row tile as (rowptr, colidx, val, N), so there is
+// no extra argument and the instantiations of MODE 0 / 1 / 2 are what they were.
 constexpr int PRED_MAX_CLASS = 32;  // ordered-probit classes of the single-pass predictor (more: the per-sample passes)
 struct ScoreStoreArgs {
   const double *const *wv;  // [S] sample buffers (w then V)
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(WG) void k_score_store(const int32_t *__restrict__ 
 #pragma unroll
     for (int c = 0; c < CPL; c++) {
       acc[u][c] = 0.0;
-      if (!sa.first && t0 + u < N) {
+      if (MODE < 3 && !sa.first && t0 + u < N) {
         if (MODE == 2) {
           const int cls = lig + c * GS;
           if (cls < n_class) acc[u][c] = out[(t0 + u) * n_class + cls];
@@ -165,6 +168,10 @@ __global__ __launch_bounds__(WG) void k_score_store(const int32_t *__restrict__ 
       } else if (MODE == 1) {
         const double v = (erf(score * 0.70710678118654752440) + 1.0) / 2.0;
         acc[u][0] = (smp == 0 && sa.first) ? v : acc[u][0] + v;
+      } else if (MODE == 3) {
+        if (lig == 0 && t0 + u < N) out[(size_t)smp * N + (t0 + u)] = score;
+      } else if (MODE == 4) {
+        if (lig == 0 && t0 + u < N) out[(size_t)smp * N + (t0 + u)] = (erf(score * 0.70710678118654752440) + 1.0) / 2.0;
       } else {
         const double *cut = sa.cut + (size_t)smp * sa.n_cut;
 #pragma unroll
@@ -179,6 +186,7 @@ __global__ __launch_bounds__(WG) void k_score_store(const int32_t *__restrict__ 
       }
     }
   }
+  if (MODE >= 3) return;
 #pragma unroll
   for (int u = 0; u < RU; u++) {
     const int64_t t = t0 + u;
@@ -203,38 +211,53 @@ __global__ void k_scale(double *__restrict__ x, int64_t n, double s) {
 }  // namespace mfm
 
 namespace mfm {
+// rows [r0, r0 + N) of a design as k_score_store reads them (CSR: rowptr holds absolute positions; ELL: row t starts at t * width)
+struct ScoreRows {
+  const int32_t *rowptr, *colidx;
+  const double *val;
+  int64_t N;
+};
+static ScoreRows score_rows(const DevSparse &X, int64_t r0, int64_t n) {
+  const bool ell = X.ell_width >= 0;
+  const int64_t e0 = ell ? r0 * X.ell_width : 0;
+  return ScoreRows{ell ? X.rowptr.p : X.rowptr.p + r0, X.colidx.p ? X.colidx.p + e0 : nullptr, X.rval.p ? X.rval.p + e0 : nullptr, n};
+}
 template <int GS, int SPL, bool UNIT, bool ELL>
-static void launch_score_store_t(hipStream_t s, int mode, const DevSparse &X, const ScoreStoreArgs &sa, int64_t D, int K, int KS,
-                                 double *out) {
-  const int64_t N = X.rows;
-  const int64_t groups = (N + SCORE_RU - 1) / SCORE_RU;
+static void launch_score_store_t(hipStream_t s, int mode, const DevSparse &X, const ScoreRows &R, const ScoreStoreArgs &sa, int64_t D,
+                                 int K, int KS, double *out) {
+  const int64_t groups = (R.N + SCORE_RU - 1) / SCORE_RU;
   dim3 grid(cdiv(groups * GS, WG)), block(WG);
 #define MFM_SS(MODE_)                                                                                                       \
-  hipLaunchKernelGGL((k_score_store<GS, SPL, MODE_, UNIT, ELL>), grid, block, 0, s, X.rowptr.p, X.colidx.p, X.rval.p, sa, D, K, KS, \
-                     (int)X.ell_width, out, N)
+  hipLaunchKernelGGL((k_score_store<GS, SPL, MODE_, UNIT, ELL>), grid, block, 0, s, R.rowptr, R.colidx, R.val, sa, D, K, KS, \
+                     (int)X.ell_width, out, R.N)
   if (mode == 0)
     MFM_SS(0);
   else if (mode == 1)
     MFM_SS(1);
-  else
+  else if (mode == 2)
     MFM_SS(2);
+  else if (mode == 3)
+    MFM_SS(3);
+  else
+    MFM_SS(4);
 #undef MFM_SS
 }
 template <int GS, int SPL>
-static void launch_score_store_f(hipStream_t s, int mode, const DevSparse &X, const ScoreStoreArgs &sa, int64_t D, int K, int KS,
-                                 double *out) {
+static void launch_score_store_f(hipStream_t s, int mode, const DevSparse &X, const ScoreRows &R, const ScoreStoreArgs &sa, int64_t D,
+                                 int K, int KS, double *out) {
   const bool ell = X.ell_width >= 0;
   if (X.unit && ell)
-    launch_score_store_t<GS, SPL, true, true>(s, mode, X, sa, D, K, KS, out);
+    launch_score_store_t<GS, SPL, true, true>(s, mode, X, R, sa, D, K, KS, out);
   else if (X.unit)
-    launch_score_store_t<GS, SPL, true, false>(s, mode, X, sa, D, K, KS, out);
+    launch_score_store_t<GS, SPL, true, false>(s, mode, X, R, sa, D, K, KS, out);
   else
-    launch_score_store_t<GS, SPL, false, false>(s, mode, X, sa, D, K, KS, out);
+    launch_score_store_t<GS, SPL, false, false>(s, mode, X, R, sa, D, K, KS, out);
 }
-// (the lane-group shapes of launch_score: the scores must be those of the per-sample pass bit for bit)
-static void launch_score_store(hipStream_t s, int mode, const DevSparse &X, const ScoreStoreArgs &sa, int64_t D, int K, int KS,
-                               double *out) {
-#define MFM_SCORE(GS, SPL) launch_score_store_f<GS, SPL>(s, mode, X, sa, D, K, KS, out)
+// (the lane-group shapes of launch_score: the scores must be those of the per-sample pass bit for bit). `R`: the rows to score,
+// the whole design for the predictors (mode 0 / 1 / 2), a row tile for the posterior summaries (mode 3 / 4, mfm_dist.hpp)
+static void launch_score_store_rows(hipStream_t s, int mode, const DevSparse &X, const ScoreRows &R, const ScoreStoreArgs &sa,
+                                    int64_t D, int K, int KS, double *out) {
+#define MFM_SCORE(GS, SPL) launch_score_store_f<GS, SPL>(s, mode, X, R, sa, D, K, KS, out)
   if (K <= 8)
     MFM_SCORE(4, 1);
   else if (K <= 16)
@@ -251,6 +274,10 @@ static void launch_score_store(hipStream_t s, int mode, const DevSparse &X, cons
     MFM_SCORE(64, 4);
 #undef MFM_SCORE
 }
+static void launch_score_store(hipStream_t s, int mode, const DevSparse &X, const ScoreStoreArgs &sa, int64_t D, int K, int KS,
+                               double *out) {
+  launch_score_store_rows(s, mode, X, score_rows(X, 0, X.rows), sa, D, K, KS, out);
+}
 }  // namespace mfm
 
 struct mfm_design {
@@ -265,6 +292,7 @@ struct mfm_design {
   DevBuf<double> w, V, Vt, score, out, cut;
   DevBuf<double> vt_all, w0s;      // single-pass predictor: row-major V of a chunk of samples, their w0
   DevBuf<const double *> wvp;      // ... and the samples' buffers
+  DevBuf<double> dist_scratch, dist_out, dist_aux;  // posterior summaries (mfm_dist.hpp): [S][T] values of a row tile, outputs, sqrt(alpha)
   PinnedRing ring;
   Timing timing;
   ~mfm_design() {
@@ -272,6 +300,23 @@ struct mfm_design {
   }
   void use_device() { MFM_HIP_CHECK(hipSetDevice(device)); }
 };
+
+// the per-rank caches of a design (sample buffers, row-major V, scores, the blocks' row caches): (re)allocated when the rank changes
+static void design_use_rank(mfm_design *d, int rank, hipStream_t s) {
+  if (d->K == rank) return;
+  const int64_t N = d->N, D = d->D;
+  d->K = rank;
+  d->KS = (rank + 1) & ~1;
+  d->w.alloc((size_t)std::max<int64_t>(D, 1));
+  d->V.alloc((size_t)std::max<int64_t>(D * rank, 1));
+  d->Vt.alloc_zero((size_t)std::max<int64_t>(D * d->KS, 1), s);
+  d->score.alloc((size_t)std::max<int64_t>(N, 1));
+  for (auto &B : d->blocks) {
+    B->bq.alloc_zero((size_t)B->B * std::max(d->KS, 1), s);
+    B->bl.alloc_zero((size_t)B->B, s);
+    B->bs.alloc_zero((size_t)B->B, s);
+  }
+}
 
 // Posterior-sample store (FMTrainer.hpp:71-74 keeps the last n_kept_samples FM copies): the kept samples stay in HBM --
 // retention is a device-to-device copy on the training stream, prediction reads them in place, the host sees a sample
@@ -533,19 +578,7 @@ int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_
   hipStream_t s = d->stream;
   const int rank = st->K;
   const int64_t N = d->N, D = d->D;
-  if (d->K != rank) {
-    d->K = rank;
-    d->KS = (rank + 1) & ~1;
-    d->w.alloc((size_t)std::max<int64_t>(D, 1));
-    d->V.alloc((size_t)std::max<int64_t>(D * rank, 1));
-    d->Vt.alloc_zero((size_t)std::max<int64_t>(D * d->KS, 1), s);
-    d->score.alloc((size_t)std::max<int64_t>(N, 1));
-    for (auto &B : d->blocks) {
-      B->bq.alloc_zero((size_t)B->B * std::max(d->KS, 1), s);
-      B->bl.alloc_zero((size_t)B->B, s);
-      B->bs.alloc_zero((size_t)B->B, s);
-    }
-  }
+  design_use_rank(d, rank, s);
   const int64_t out_n = mode == 2 ? N * (n_cut + 1) : N;
   if (d->out.n < (size_t)std::max<int64_t>(out_n, 1)) d->out.alloc((size_t)std::max<int64_t>(out_n, 1));
   // the samples' device-to-device copies (training stream) must be complete: this stream waits for the latest one's event
@@ -622,19 +655,7 @@ int mfm_design_predict(mfm_design *d, int32_t rank, int32_t n_samples, const dou
   if (mode == 2 && n_cut < 1) throw Error(MFM_ERR_RUNTIME, "No cutpoint available for this FM.");  // FM.hpp:141-143
   hipStream_t s = d->stream;
   const int64_t N = d->N, D = d->D;
-  if (d->K != rank) {
-    d->K = rank;
-    d->KS = (rank + 1) & ~1;
-    d->w.alloc((size_t)std::max<int64_t>(D, 1));
-    d->V.alloc((size_t)std::max<int64_t>(D * rank, 1));
-    d->Vt.alloc_zero((size_t)std::max<int64_t>(D * d->KS, 1), s);
-    d->score.alloc((size_t)std::max<int64_t>(N, 1));
-    for (auto &B : d->blocks) {
-      B->bq.alloc_zero((size_t)B->B * std::max(d->KS, 1), s);
-      B->bl.alloc_zero((size_t)B->B, s);
-      B->bs.alloc_zero((size_t)B->B, s);
-    }
-  }
+  design_use_rank(d, rank, s);
   const int64_t out_n = mode == 2 ? N * (n_cut + 1) : N;
   if (d->out.n < (size_t)std::max<int64_t>(out_n, 1)) d->out.alloc((size_t)std::max<int64_t>(out_n, 1));
   if (mode == 2 && d->cut.n < (size_t)n_cut) d->cut.alloc((size_t)n_cut);

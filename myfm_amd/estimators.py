@@ -4,7 +4,7 @@ written against ``myfm_amd._myfm``. Same constructor / fit / predict arguments, 
 error behaviour; numpy-2 safe.
 """
 import os
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -310,6 +310,57 @@ class _FMEstimatorBase:
         return predictor.predict_parallel(X, list(X_rel), n_workers)
 
 
+PredictiveSummary = namedtuple("PredictiveSummary", ["mean", "std", "quantiles"])
+PREDICT_DIST_MAX_QUANTILES = 32
+PREDICT_DIST_MAX_SAMPLES = 4096  # with a non-empty `quantiles`: a row's values are sorted in the device's local memory
+
+
+class _PredictiveDistMixin:
+    """Posterior predictive summaries of a fitted Gibbs regressor / classifier. MyFMOrderedProbit and the
+    variational estimators have no predict_dist. Row-sharded operation is not covered: the model is replicated, so each rank
+    may call predict_dist on its own rows."""
+
+    def predict_dist(self, X, X_rel=[], quantiles=(0.05, 0.5, 0.95), noise=False):
+        """PredictiveSummary(mean, std, quantiles) per test row over the S kept samples, computed on the device in one pass
+        over the test rows. The per-sample value v_s is the sample's score for a regressor and Phi(score) for a classifier.
+
+        mean (N,): what predict / predict_proba return, bit for bit. std (N,): population standard deviation (ddof = 0) of
+        the v_s. quantiles (Q, N): np.quantile(v, quantiles, axis=0) under the default "linear" rule, from exactly sorted
+        values; `quantiles` may be empty (at most 32 entries in [0, 1]; S <= 4096 unless it is empty).
+
+        noise=True (regressor only) describes y itself, the equal-weight mixture of N(score_s, 1 / alpha_s) with alpha_s
+        the noise precision of the iteration that produced sample s (the last S entries of history_.hypers): the mean is
+        unchanged, std is sqrt(var_s(score) + mean_s(1 / alpha_s)) and the quantiles are those of the mixture, solved per
+        row on the device; they must then lie strictly inside (0, 1).
+
+        The arguments are checked on the host before the device is touched."""
+        predictor = self._fetch_predictor()
+        n = check_data_consistency(X, X_rel)
+        X = _as_csr(X, n)
+        probs = np.asarray(quantiles, dtype=REAL)
+        if probs.ndim != 1:
+            raise ValueError("quantiles must be a 1-D sequence of probabilities")
+        if probs.shape[0] > PREDICT_DIST_MAX_QUANTILES:
+            raise ValueError("at most %d quantiles per call" % PREDICT_DIST_MAX_QUANTILES)
+        if not np.all((probs >= 0.0) & (probs <= 1.0)):  # (NaN fails both comparisons)
+            raise ValueError("quantiles must lie in [0, 1]")
+        n_samples = len(predictor.samples)
+        precisions = None
+        if noise:
+            if self._task_type != TaskType.REGRESSION:
+                raise ValueError("noise=True describes a regression target: it is not available on a classifier")
+            if np.any((probs <= 0.0) | (probs >= 1.0)):
+                raise ValueError("with noise=True the quantiles must lie strictly inside (0, 1)")
+            hypers = None if self.history_ is None else self.history_.hypers
+            if hypers is None or len(hypers) < n_samples:
+                raise RuntimeError("noise=True needs history_ with the noise precision of every kept sample")
+            precisions = np.asarray([h.alpha for h in hypers[len(hypers) - n_samples:]], dtype=REAL)
+        if probs.shape[0] > 0 and n_samples > PREDICT_DIST_MAX_SAMPLES:
+            raise ValueError("quantiles are computed over at most %d kept samples, this model keeps %d (mean and std have no "
+                             "limit: pass quantiles=())" % (PREDICT_DIST_MAX_SAMPLES, n_samples))
+        return PredictiveSummary(*predictor.predict_dist(X, list(X_rel), probs, precisions))
+
+
 class _PairScoringMixin:
     """Ranking with a fitted model: scores of every (query row, candidate row) pair and the per-query top-k, computed on the
     device without materialising the pair rows. Regressors score the posterior-mean prediction, classifiers the
@@ -410,7 +461,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -440,7 +491,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, MyFMGibbsBase):
         return self._predict_core(X, X_rel, n_workers=n_workers)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
