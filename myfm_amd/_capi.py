@@ -566,11 +566,7 @@ class Design:
 
     def predict(self, samples, mode=0, cutpoints=None):
         """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
-        S = len(samples)
-        K = np.asarray(samples[0][2]).shape[1] if S else 0
-        w0s = _f64([s[0] for s in samples])
-        ws = _f64(np.stack([np.asarray(s[1], dtype=np.float64) for s in samples])) if S else np.empty(0)
-        Vs = _f64(np.stack([np.asarray(s[2], dtype=np.float64).T for s in samples])) if S else np.empty(0)
+        K, S, w0s, ws, Vs = _pack_samples(samples)
         n_cut = 0
         cp = None
         if mode == 2:

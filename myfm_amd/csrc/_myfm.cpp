@@ -598,18 +598,26 @@ struct Predictor {
       if (samples[k].store != st || samples[k].store_idx != *first + (int)k) return nullptr;
     return st;
   }
+  // Where a call's samples come from, decided once for every device predictor: in_store(store, first) reads them in place,
+  // packed(w0s, ws, Vs) gets them packed on the host (a restored or modified predictor). Returns the callee's code.
+  template <class InStore, class Packed>
+  int with_samples(const InStore &in_store, const Packed &packed) const {
+    int first = 0;
+    if (auto st = resident(&first)) return in_store(st->st, first);
+    vector<double> w0s, ws, Vs;
+    pack(w0s, ws, Vs);
+    return packed(w0s.data(), ws.data(), Vs.data());
+  }
   // mode / cutpoints as mfm_design_predict
   void run_predict(const Csr &X, const Relations &rels, int mode, int n_cut, const vector<double> &cuts, double *out) const {
     DeviceDesign dd(X, rels);
-    int first = 0;
-    if (auto st = resident(&first)) {
-      int code = mfm_design_predict_store(dd.d, st->st, first, (int)samples.size(), mode, n_cut, cuts.data(), out);
-      if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
-      return;
-    }
-    vector<double> w0s, ws, Vs;
-    pack(w0s, ws, Vs);
-    dd.predict((int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, n_cut, cuts.data(), out);
+    const int S = (int)samples.size();
+    const int code = with_samples(
+        [&](mfm_store *st, int first) { return mfm_design_predict_store(dd.d, st, first, S, mode, n_cut, cuts.data(), out); },
+        [&](const double *w0s, const double *ws, const double *Vs) {
+          return mfm_design_predict(dd.d, (int)rank, S, w0s, ws, Vs, mode, n_cut, cuts.data(), out);
+        });
+    if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
   }
 
   void check_input(const Csr &X, const Relations &relations) const {  // predictor.hpp:24-33
@@ -761,16 +769,15 @@ struct Predictor {
       for (auto &sm : samples) cuts.insert(cuts.end(), sm.cutpoints[0].begin(), sm.cutpoints[0].end());
       dp.ck(mfm_pairs_set_cutpoints(dp.p, (int)samples.size(), (int)samples[0].cutpoints[0].size(), cuts.data()));
     }
-    int first = 0;
-    if (auto st = resident(&first)) {  // the unmodified entries of the device store: in place, as run_predict
-      dp.ck(dense ? mfm_pairs_scores_store(dp.p, st->st, first, (int)samples.size(), mode, dense)
-                  : mfm_pairs_topk_store(dp.p, st->st, first, (int)samples.size(), mode, k, idx, score));
-      return;
-    }
-    vector<double> w0s, ws, Vs;
-    pack(w0s, ws, Vs);
-    dp.ck(dense ? mfm_pairs_scores(dp.p, (int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, dense)
-                : mfm_pairs_topk(dp.p, (int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, k, idx, score));
+    const int S = (int)samples.size();
+    dp.ck(with_samples(
+        [&](mfm_store *st, int first) {
+          return dense ? mfm_pairs_scores_store(dp.p, st, first, S, mode, dense) : mfm_pairs_topk_store(dp.p, st, first, S, mode, k, idx, score);
+        },
+        [&](const double *w0s, const double *ws, const double *Vs) {
+          return dense ? mfm_pairs_scores(dp.p, (int)rank, S, w0s, ws, Vs, mode, dense)
+                       : mfm_pairs_topk(dp.p, (int)rank, S, w0s, ws, Vs, mode, k, idx, score);
+        }));
   }
   py::array_t<double> predict_pairs(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
     Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
@@ -852,18 +859,17 @@ struct Predictor {
     py::array_t<double> mean((py::ssize_t)X.rows), sd((py::ssize_t)X.rows), q({(py::ssize_t)n_q, (py::ssize_t)X.rows});
     const int mode = type == TaskType::CLASSIFICATION ? 1 : 0;
     DeviceDesign dd(X, rels);
-    int first = 0, code;
-    if (auto st = resident(&first)) {  // the unmodified entries of the device store: in place, as run_predict
-      code = mfm_design_summary_store(dd.d, st->st, first, (int)samples.size(), mode, n_q, probs.data(), noise ? prec.data() : nullptr,
-                                      noise ? z.data() : nullptr, tile_rows, chunk_samples, mean.mutable_data(), sd.mutable_data(),
-                                      q.mutable_data());
-    } else {
-      vector<double> w0s, ws, Vs;
-      pack(w0s, ws, Vs);
-      code = mfm_design_summary(dd.d, (int)rank, (int)samples.size(), w0s.data(), ws.data(), Vs.data(), mode, n_q, probs.data(),
-                                noise ? prec.data() : nullptr, noise ? z.data() : nullptr, tile_rows, chunk_samples, mean.mutable_data(),
-                                sd.mutable_data(), q.mutable_data());
-    }
+    const int S = (int)samples.size();
+    const double *pr = noise ? prec.data() : nullptr, *zs = noise ? z.data() : nullptr;
+    const int code = with_samples(
+        [&](mfm_store *st, int first) {
+          return mfm_design_summary_store(dd.d, st, first, S, mode, n_q, probs.data(), pr, zs, tile_rows, chunk_samples, mean.mutable_data(),
+                                          sd.mutable_data(), q.mutable_data());
+        },
+        [&](const double *w0s, const double *ws, const double *Vs) {
+          return mfm_design_summary(dd.d, (int)rank, S, w0s, ws, Vs, mode, n_q, probs.data(), pr, zs, tile_rows, chunk_samples,
+                                    mean.mutable_data(), sd.mutable_data(), q.mutable_data());
+        });
     if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
     return py::make_tuple(mean, sd, q);
   }

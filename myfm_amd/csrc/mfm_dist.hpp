@@ -204,13 +204,11 @@ static void launch_row_summary(hipStream_t s, RowSummaryArgs &a) {
   hipLaunchKernelGGL(k_row_summary<true>, dim3((unsigned)cdiv(a.Tn, a.R)), dim3(WG), lds, s, a);
 }
 
-static void design_summary_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t n_q,
-                                 const double *probs, const double *precisions, const double *z, int64_t tile_rows,
-                                 int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
-  if (count <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
-  if (first < 0 || first + count > (int)st->wv.size()) throw Error(MFM_ERR_INVALID, "sample range out of bounds");
-  if (st->device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
-  if (st->D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int32_t n_q, const double *probs, const double *precisions,
+                           const double *z, int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
+  const int count = v.count();
+  if (v.device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
+  if (v.D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
   if (mode < 0 || mode > 1) throw Error(MFM_ERR_INVALID, "bad summary mode (0: score, 1: Phi(score))");
   if (n_q < 0 || n_q > DIST_MAX_Q) throw Error(MFM_ERR_INVALID, "at most " + std::to_string(DIST_MAX_Q) + " quantiles per call");
   if (n_q > 0 && count > DIST_MAX_S)
@@ -227,7 +225,7 @@ static void design_summary_store(mfm_design *d, mfm_store *st, int32_t first, in
     for (int k = 0; k < count; k++)
       if (!(precisions[k] > 0.0) || !std::isfinite(precisions[k])) throw Error(MFM_ERR_INVALID, "noise precisions must be positive and finite");
   hipStream_t s = d->stream;
-  const int rank = st->K;
+  const int rank = v.K;
   const int64_t N = d->N, D = d->D;
   if (N == 0) return;
   design_use_rank(d, rank, s);
@@ -266,54 +264,25 @@ static void design_summary_store(mfm_design *d, mfm_store *st, int32_t first, in
       a.g[q] = h - fl;
     }
   }
-  if (st->pushed_valid) MFM_HIP_CHECK(hipStreamWaitEvent(s, st->pushed, 0));
+  if (v.pushed) MFM_HIP_CHECK(hipStreamWaitEvent(s, v.pushed, 0));
   const bool one_pass = d->blocks.empty() && rank <= 512;
-  int chunk = count;
-  if (one_pass) {  // (the sample chunks of mfm_design_predict_store)
-    const size_t per = (size_t)std::max<int64_t>(D * d->KS, 1) * sizeof(double);
-    chunk = chunk_samples > 0 ? std::min<int>(chunk_samples, count)
-                              : (int)std::max<size_t>(1, std::min<size_t>((size_t)count, ((size_t)512 << 20) / per));
-    if (d->vt_all.n < (size_t)chunk * (per / sizeof(double))) d->vt_all.alloc((size_t)chunk * (per / sizeof(double)));
-    std::vector<const double *> hp((size_t)count);
-    std::vector<double> hw0((size_t)count);
-    for (int k = 0; k < count; k++) {
-      hp[k] = st->wv[first + k]->p;
-      hw0[k] = st->w0[first + k];
-    }
-    if (d->wvp.n < (size_t)count) d->wvp.alloc((size_t)count);
-    if (d->w0s.n < (size_t)count) d->w0s.alloc((size_t)count);
-    MFM_HIP_CHECK(hipMemcpyAsync(d->wvp.p, hp.data(), (size_t)count * sizeof(double *), hipMemcpyHostToDevice, s));
-    MFM_HIP_CHECK(hipMemcpyAsync(d->w0s.p, hw0.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice, s));
-    MFM_HIP_CHECK(hipStreamSynchronize(s));  // (hp / hw0 are pageable host vectors of this frame)
-  }
+  const int chunk = one_pass ? design_stage_samples(d, s, v, chunk_samples) : count;
   int built = -1;  // the chunk whose row-major V copies vt_all holds
   for (int64_t r0 = 0; r0 < N; r0 += T) {
     const int64_t Tn = std::min<int64_t>(T, N - r0);
     if (one_pass) {
       for (int c0 = 0; c0 < count; c0 += chunk) {
         const int C = std::min(chunk, count - c0);
-        if (built != c0 && rank > 0 && D > 0) {
-          hipLaunchKernelGGL(k_build_vt_batch, dim3((unsigned)cdiv(D, 32), (unsigned)cdiv(d->KS, 32), (unsigned)C), dim3(WG), 0, s,
-                             (const double *const *)d->wvp.p + c0, D, rank, d->KS, d->vt_all.p);
-          built = c0;
-        }
-        ScoreStoreArgs sa;
-        sa.wv = (const double *const *)d->wvp.p + c0;
-        sa.vt_all = d->vt_all.p;
-        sa.w0 = d->w0s.p + c0;
-        sa.cut = nullptr;
-        sa.S = C;
-        sa.n_cut = 0;
-        sa.first = 1;
-        sa.scale = 1.0;
+        const ScoreStoreArgs sa = design_sample_chunk(d, s, c0, C, built != c0);
+        built = c0;
         launch_score_store_rows(s, 3 + mode, d->X, score_rows(d->X, r0, Tn), sa, D, rank, d->KS, d->dist_scratch.p + (size_t)c0 * Tn);
       }
     } else {
       // relation blocks: the per-sample pass over the whole design, of which this tile's rows are kept (a design of more
       // than one tile is scored once per tile)
       for (int k = 0; k < count; k++) {
-        const double *w = st->wv[first + k]->p, *V = w + D;
-        score_design(s, d->timing, 1, d->X, d->blocks, D, rank, d->KS, st->w0[first + k], w, V, d->Vt.p, nullptr, nullptr, d->score.p);
+        const double *w = v.wv[(size_t)k], *V = w + D;
+        score_design(s, d->timing, 1, d->X, d->blocks, D, rank, d->KS, v.w0[(size_t)k], w, V, d->Vt.p, nullptr, nullptr, d->score.p);
         hipLaunchKernelGGL(k_dist_copy, dim3((unsigned)cdiv(Tn, WG)), dim3(WG), 0, s, d->score.p + r0, d->dist_scratch.p + (size_t)k * Tn, Tn,
                            mode);
       }
@@ -340,30 +309,20 @@ int mfm_design_summary_store(mfm_design *d, mfm_store *st, int32_t first, int32_
                              const double *probs, const double *precisions, const double *z, int64_t tile_rows,
                              int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
   MFM_TRY(d)
-  design_summary_store(d, st, first, count, mode, n_q, probs, precisions, z, tile_rows, chunk_samples, out_mean, out_std, out_q);
+  design_summary(d, samples_of_store(st, first, count), mode, n_q, probs, precisions, z, tile_rows, chunk_samples, out_mean, out_std, out_q);
   MFM_CATCH(d)
 }
 
-// host samples: uploaded into a store of this call's own, then as above (the same kernels over the same chunks)
-// (all S samples at once, through mfm_store_reserve: refused with its message beyond MFM_STORE_MAX_FRACTION of the free device memory,
-//  where mfm_design_predict, which streams one sample at a time, still runs)
+// host samples: all S uploaded for this call, then as above (the same kernels over the same chunks). Like a store's reservation
+// the upload is refused beyond MFM_STORE_MAX_FRACTION of the free device memory, where mfm_design_predict, which streams one
+// sample at a time, still runs.
 int mfm_design_summary(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                        int32_t mode, int32_t n_q, const double *probs, const double *precisions, const double *z,
                        int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
   MFM_TRY(d)
-  if (n_samples <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
-  if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
-  mfm_store st;
-  st.device = d->device;
-  st.D = d->D;
-  st.K = rank;
-  const size_t D = (size_t)d->D;
-  if (mfm_store_reserve(&st, n_samples) != MFM_OK) throw Error(MFM_ERR_RUNTIME, st.err);  // (one allocation, not one per sample)
-  for (int k = 0; k < n_samples; k++) {
-    const int code = mfm_store_push_host(&st, w0s[k], ws + (size_t)k * D, Vs + (size_t)k * D * rank);
-    if (code != MFM_OK) throw Error(code, st.err);
-  }
-  design_summary_store(d, &st, 0, n_samples, mode, n_q, probs, precisions, z, tile_rows, chunk_samples, out_mean, out_std, out_q);
+  store_check_fraction(d->D, rank, n_samples);
+  design_summary(d, samples_of_host(d->device, d->D, rank, n_samples, w0s, ws, Vs), mode, n_q, probs, precisions, z, tile_rows,
+                 chunk_samples, out_mean, out_std, out_q);
   MFM_CATCH(d)
 }
 

@@ -14,6 +14,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <fcntl.h>
@@ -466,54 +467,59 @@ static void launch_qbuild(mfm_ctx *c, const double *vf, DevBlock *pending = null
   MFM_HIP_CHECK(hipGetLastError());
 }
 
-template <int GS, int SPL, bool UNIT, bool ELL>
-static void launch_score_t(hipStream_t s, int mode, const DevSparse &X, const double *Vt, const double *w, double w0, int K,
-                           int KS, const double *y, double2 *eq, double *out, const BlockScoreArgs &blk) {
-  const int64_t N = X.rows;
-  const int64_t groups = (N + SCORE_RU - 1) / SCORE_RU;
-  dim3 grid(cdiv(groups * GS, WG)), block(WG);
-  if (mode == 0)
-    hipLaunchKernelGGL((k_score<GS, SPL, 0, UNIT, ELL>), grid, block, 0, s, X.rowptr.p, X.colidx.p, X.rval.p, Vt, w, w0, K, KS,
-                       (int)X.ell_width, y, eq, out, N, blk);
+// The scorer's shape table, the only one: rank K -> GS lanes per row (a lane owns factor pairs: GS lanes cover 2 GS factors) and SPL
+// pairs per lane, and X's layout -> UNIT / ELL. f(GS, SPL, UNIT, ELL) is called with std::integral_constants. k_score and
+// k_score_store (mfm_predict.hpp) both launch through it: the one-pass predictors are bit-identical to the per-sample pass because
+// the two kernels add in the same lane groups. False: rank > 512, nothing was called.
+template <class F>
+static bool score_shape(int K, const DevSparse &X, F &&f) {
+  const auto layout = [&](auto gs, auto spl) {
+    if (X.unit && X.ell_width >= 0)
+      f(gs, spl, std::true_type{}, std::true_type{});
+    else if (X.unit)
+      f(gs, spl, std::true_type{}, std::false_type{});
+    else
+      f(gs, spl, std::false_type{}, std::false_type{});
+  };
+#define MFM_SHAPE(GS, SPL) layout(std::integral_constant<int, GS>{}, std::integral_constant<int, SPL>{})
+  if (K <= 8)
+    MFM_SHAPE(4, 1);
+  else if (K <= 16)
+    MFM_SHAPE(8, 1);
+  else if (K <= 32)
+    MFM_SHAPE(16, 1);
+  else if (K <= 64)
+    MFM_SHAPE(32, 1);
+  else if (K <= 128)
+    MFM_SHAPE(64, 1);
+  else if (K <= 256)
+    MFM_SHAPE(64, 2);
+  else if (K <= 512)
+    MFM_SHAPE(64, 4);
   else
-    hipLaunchKernelGGL((k_score<GS, SPL, 1, UNIT, ELL>), grid, block, 0, s, X.rowptr.p, X.colidx.p, X.rval.p, Vt, w, w0, K, KS,
-                       (int)X.ell_width, y, eq, out, N, blk);
+    return false;
+#undef MFM_SHAPE
+  return true;
 }
 
-template <int GS, int SPL>
-static void launch_score_f(hipStream_t s, int mode, const DevSparse &X, const double *Vt, const double *w, double w0, int K,
-                           int KS, const double *y, double2 *eq, double *out, const BlockScoreArgs &blk) {
-  const bool ell = X.ell_width >= 0;
-  if (X.unit && ell)
-    launch_score_t<GS, SPL, true, true>(s, mode, X, Vt, w, w0, K, KS, y, eq, out, blk);
-  else if (X.unit)
-    launch_score_t<GS, SPL, true, false>(s, mode, X, Vt, w, w0, K, KS, y, eq, out, blk);
-  else
-    launch_score_t<GS, SPL, false, false>(s, mode, X, Vt, w, w0, K, KS, y, eq, out, blk);
-}
-
-// mode 0: eq.x = score (- y)   mode 1: out = score.  A lane owns factor pairs: GS lanes cover 2 GS factors.
+// mode 0: eq.x = score (- y)   mode 1: out = score
 static void launch_score(hipStream_t s, int mode, const DevSparse &X, const double *Vt, const double *w, double w0, int K,
                          int KS, const double *y, double2 *eq, double *out, const BlockScoreArgs &blk) {
-  if (X.rows == 0) return;
-#define MFM_SCORE(GS, SPL) launch_score_f<GS, SPL>(s, mode, X, Vt, w, w0, K, KS, y, eq, out, blk)
-  if (K <= 8)
-    MFM_SCORE(4, 1);
-  else if (K <= 16)
-    MFM_SCORE(8, 1);
-  else if (K <= 32)
-    MFM_SCORE(16, 1);
-  else if (K <= 64)
-    MFM_SCORE(32, 1);
-  else if (K <= 128)
-    MFM_SCORE(64, 1);
-  else if (K <= 256)
-    MFM_SCORE(64, 2);
-  else if (K <= 512)
-    MFM_SCORE(64, 4);
-  else
-    throw Error(MFM_ERR_INVALID, "rank > 512 is not supported");
-#undef MFM_SCORE
+  const int64_t N = X.rows;
+  if (N == 0) return;
+  const bool known = score_shape(K, X, [&](auto gs, auto spl, auto unit, auto ell) {
+    constexpr int GS = decltype(gs)::value, SPL = decltype(spl)::value;
+    constexpr bool UNIT = decltype(unit)::value, ELL = decltype(ell)::value;
+    const int64_t groups = (N + SCORE_RU - 1) / SCORE_RU;
+    dim3 grid(cdiv(groups * GS, WG)), block(WG);
+    if (mode == 0)
+      hipLaunchKernelGGL((k_score<GS, SPL, 0, UNIT, ELL>), grid, block, 0, s, X.rowptr.p, X.colidx.p, X.rval.p, Vt, w, w0, K, KS,
+                         (int)X.ell_width, y, eq, out, N, blk);
+    else
+      hipLaunchKernelGGL((k_score<GS, SPL, 1, UNIT, ELL>), grid, block, 0, s, X.rowptr.p, X.colidx.p, X.rval.p, Vt, w, w0, K, KS,
+                         (int)X.ell_width, y, eq, out, N, blk);
+  });
+  if (!known) throw Error(MFM_ERR_INVALID, "rank > 512 is not supported");
   MFM_HIP_CHECK(hipGetLastError());
 }
 
@@ -2767,22 +2773,3 @@ int mfm_host_column_levels(int64_t n_rows, int64_t n_cols, const int64_t *indptr
 #include "mfm_latent_host.hpp"  // ... their exact latent draws on the device stream
 #include "mfm_predict.hpp"  // mfm_design_* entry points
 #include "mfm_dist.hpp"     // ... and the posterior summaries over the kept samples
-
-// the samples [first, first + count) as another translation unit reads them in place (declared in mfm_pairs.hpp; defined here, in the one unit that knows mfm_store)
-namespace mfm {
-void store_view(mfm_store *st, int first, int count, int *device, int64_t *D, int *K, std::vector<const double *> &wv,
-                std::vector<double> &w0, hipEvent_t *pushed) {
-  if (first < 0 || count < 0 || first + count > (int)st->wv.size()) throw Error(MFM_ERR_INVALID, "sample range out of bounds");
-  *device = st->device;
-  *D = st->D;
-  *K = st->K;
-  wv.resize((size_t)count);
-  w0.resize((size_t)count);
-  for (int k = 0; k < count; k++) {
-    wv[(size_t)k] = st->wv[(size_t)(first + k)]->p;
-    w0[(size_t)k] = st->w0[(size_t)(first + k)];
-  }
-  *pushed = st->pushed_valid ? st->pushed : nullptr;
-}
-}  // namespace mfm
-

@@ -13,6 +13,7 @@
 // unchanged. A side with blocks is embedded by k_pairs_embed_rel, one without by k_pairs_embed, so a call without blocks computes
 // what it computed before there were any.
 #include "mfm_pairs.hpp"
+#include "mfm_samples.hpp"
 
 #include <cmath>
 #include <memory>
@@ -118,13 +119,14 @@ void launch_tile(hipStream_t s, dim3 grid, const PairsArgs &a, int mode, bool de
 #undef PAIRS_LAUNCH
 }
 
-// The whole call. wv: the samples' device buffers (w[D] then V[K][D]); w0: theirs. dense != nullptr: (U, I) scores; else the top k.
-void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, const std::vector<double> &w0, int mode, int k,
-               int64_t *idx, double *score, double *dense) {
-  const int S = (int)wv.size();
-  if (S <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
+// The whole call over the samples of `v` (mfm_samples.hpp). dense != nullptr: (U, I) scores; else the top k.
+void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx, double *score, double *dense) {
+  const int S = v.count(), rank = v.K;
+  if (v.device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
+  if (v.D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+  // a store's device-to-device copies (training stream) must be complete: this stream waits for the latest one's event
+  if (v.pushed) MFM_HIP_CHECK(hipStreamWaitEvent(p->stream, v.pushed, 0));
   if (S > 65535) throw Error(MFM_ERR_INVALID, "at most 65535 samples per call");
-  if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
   if (mode != 0 && mode != 1 && mode != 2)
     throw Error(MFM_ERR_INVALID, "bad prediction mode (0: mean score, 1: mean Phi(score), 2: mean expected class index of the ordered probit)");
   if (mode == 2) {
@@ -177,10 +179,10 @@ void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, co
   // ---- the samples' pointers and w0
   DevBuf<const double *> d_wv;
   DevBuf<double> d_w0;
-  d_wv.upload(wv);
-  d_w0.upload(w0);
+  d_wv.upload(v.wv);
+  d_w0.upload(v.w0);
   double w0sum = 0.0;
-  for (int i = 0; i < S; i++) w0sum += w0[i];
+  for (int i = 0; i < S; i++) w0sum += v.w0[i];
 
   DevBuf<double> d_cut;
   if (mode == 2) d_cut.upload(p->cut);
@@ -314,36 +316,12 @@ void run_pairs(mfm_pairs *p, int rank, const std::vector<const double *> &wv, co
 
 void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense) {
   if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  if (count <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
-  int device = 0, K = 0;
-  int64_t D = 0;
-  std::vector<const double *> wv;
-  std::vector<double> w0;
-  hipEvent_t pushed = nullptr;
-  store_view(st, first, count, &device, &D, &K, wv, w0, &pushed);
-  if (device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
-  if (D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
-  // the samples' device-to-device copies (training stream) must be complete: this stream waits for the latest one's event
-  if (pushed) MFM_HIP_CHECK(hipStreamWaitEvent(p->stream, pushed, 0));
-  run_pairs(p, K, wv, w0, mode, k, idx, score, dense);
+  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense);
 }
 
 void run_pairs_host(mfm_pairs *p, int rank, int n_samples, const double *w0s, const double *ws, const double *Vs, int mode, int k,
                     int64_t *idx, double *score, double *dense) {
-  if (n_samples <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
-  if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
-  const size_t D = (size_t)p->D, per = std::max<size_t>(D * ((size_t)rank + 1), 1);
-  DevBuf<double> buf;  // per sample: w[D] then V[K][D], the store's layout
-  buf.alloc(per * (size_t)n_samples);
-  std::vector<const double *> wv((size_t)n_samples);
-  std::vector<double> w0(w0s, w0s + n_samples);
-  for (int i = 0; i < n_samples; i++) {
-    double *b = buf.p + per * (size_t)i;
-    if (D) MFM_HIP_CHECK(hipMemcpy(b, ws + D * (size_t)i, D * sizeof(double), hipMemcpyHostToDevice));
-    if (D && rank) MFM_HIP_CHECK(hipMemcpy(b + D, Vs + D * rank * (size_t)i, D * rank * sizeof(double), hipMemcpyHostToDevice));
-    wv[(size_t)i] = b;
-  }
-  run_pairs(p, rank, wv, w0, mode, k, idx, score, dense);
+  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense);
 }
 
 }  // namespace

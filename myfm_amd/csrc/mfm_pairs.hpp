@@ -10,14 +10,7 @@
 #pragma once
 #include "mfm_common.hpp"
 
-struct mfm_store;
-
 namespace mfm {
-
-// the samples [first, first + count) of a device store, read in place (defined next to mfm_store, mfm_predict.hpp): their
-// buffers (w[D] then V[K][D]), their w0, the store's sizes and the event behind its latest device-to-device snapshot
-void store_view(mfm_store *st, int first, int count, int *device, int64_t *D, int *K, std::vector<const double *> &wv,
-                std::vector<double> &w0, hipEvent_t *pushed);
 
 constexpr int PAIRS_WG = 256;        // 4 waves: the same query rows, side-by-side candidate columns
 constexpr int PAIRS_ROW_ALIGN = 64;  // query chunks are padded to the largest workgroup tile (zero rows)

@@ -2,6 +2,7 @@
 // predict_parallel / predict_parallel_oprobit (predictor.hpp:35-147), FM::oprobit_predict_proba
 // (FM.hpp:137-162). Included by mfm_hip.hip.
 #pragma once
+#include "mfm_samples.hpp"
 
 namespace mfm {
 
@@ -222,57 +223,31 @@ static ScoreRows score_rows(const DevSparse &X, int64_t r0, int64_t n) {
   const int64_t e0 = ell ? r0 * X.ell_width : 0;
   return ScoreRows{ell ? X.rowptr.p : X.rowptr.p + r0, X.colidx.p ? X.colidx.p + e0 : nullptr, X.rval.p ? X.rval.p + e0 : nullptr, n};
 }
-template <int GS, int SPL, bool UNIT, bool ELL>
-static void launch_score_store_t(hipStream_t s, int mode, const DevSparse &X, const ScoreRows &R, const ScoreStoreArgs &sa, int64_t D,
-                                 int K, int KS, double *out) {
-  const int64_t groups = (R.N + SCORE_RU - 1) / SCORE_RU;
-  dim3 grid(cdiv(groups * GS, WG)), block(WG);
+// (the lane-group shapes of launch_score, from the same table -- score_shape: the scores must be those of the per-sample pass bit
+// for bit). `R`: the rows to score, the whole design for the predictors (mode 0 / 1 / 2), a row tile for the posterior summaries
+// (mode 3 / 4, mfm_dist.hpp). Callers keep to rank <= 512.
+static void launch_score_store_rows(hipStream_t s, int mode, const DevSparse &X, const ScoreRows &R, const ScoreStoreArgs &sa,
+                                    int64_t D, int K, int KS, double *out) {
+  (void)score_shape(K, X, [&](auto gs, auto spl, auto unit, auto ell) {
+    constexpr int GS = decltype(gs)::value, SPL = decltype(spl)::value;
+    constexpr bool UNIT = decltype(unit)::value, ELL = decltype(ell)::value;
+    const int64_t groups = (R.N + SCORE_RU - 1) / SCORE_RU;
+    dim3 grid(cdiv(groups * GS, WG)), block(WG);
 #define MFM_SS(MODE_)                                                                                                       \
   hipLaunchKernelGGL((k_score_store<GS, SPL, MODE_, UNIT, ELL>), grid, block, 0, s, R.rowptr, R.colidx, R.val, sa, D, K, KS, \
                      (int)X.ell_width, out, R.N)
-  if (mode == 0)
-    MFM_SS(0);
-  else if (mode == 1)
-    MFM_SS(1);
-  else if (mode == 2)
-    MFM_SS(2);
-  else if (mode == 3)
-    MFM_SS(3);
-  else
-    MFM_SS(4);
+    if (mode == 0)
+      MFM_SS(0);
+    else if (mode == 1)
+      MFM_SS(1);
+    else if (mode == 2)
+      MFM_SS(2);
+    else if (mode == 3)
+      MFM_SS(3);
+    else
+      MFM_SS(4);
 #undef MFM_SS
-}
-template <int GS, int SPL>
-static void launch_score_store_f(hipStream_t s, int mode, const DevSparse &X, const ScoreRows &R, const ScoreStoreArgs &sa, int64_t D,
-                                 int K, int KS, double *out) {
-  const bool ell = X.ell_width >= 0;
-  if (X.unit && ell)
-    launch_score_store_t<GS, SPL, true, true>(s, mode, X, R, sa, D, K, KS, out);
-  else if (X.unit)
-    launch_score_store_t<GS, SPL, true, false>(s, mode, X, R, sa, D, K, KS, out);
-  else
-    launch_score_store_t<GS, SPL, false, false>(s, mode, X, R, sa, D, K, KS, out);
-}
-// (the lane-group shapes of launch_score: the scores must be those of the per-sample pass bit for bit). `R`: the rows to score,
-// the whole design for the predictors (mode 0 / 1 / 2), a row tile for the posterior summaries (mode 3 / 4, mfm_dist.hpp)
-static void launch_score_store_rows(hipStream_t s, int mode, const DevSparse &X, const ScoreRows &R, const ScoreStoreArgs &sa,
-                                    int64_t D, int K, int KS, double *out) {
-#define MFM_SCORE(GS, SPL) launch_score_store_f<GS, SPL>(s, mode, X, R, sa, D, K, KS, out)
-  if (K <= 8)
-    MFM_SCORE(4, 1);
-  else if (K <= 16)
-    MFM_SCORE(8, 1);
-  else if (K <= 32)
-    MFM_SCORE(16, 1);
-  else if (K <= 64)
-    MFM_SCORE(32, 1);
-  else if (K <= 128)
-    MFM_SCORE(64, 1);
-  else if (K <= 256)
-    MFM_SCORE(64, 2);
-  else
-    MFM_SCORE(64, 4);
-#undef MFM_SCORE
+  });
 }
 static void launch_score_store(hipStream_t s, int mode, const DevSparse &X, const ScoreStoreArgs &sa, int64_t D, int K, int KS,
                                double *out) {
@@ -318,6 +293,39 @@ static void design_use_rank(mfm_design *d, int rank, hipStream_t s) {
   }
 }
 
+// ---- the one-pass predictors' samples (k_score_store) ----
+// The samples' buffers and w0 go to the device; vt_all is sized for a chunk of samples whose row-major V copies fit 512 MB (the
+// buffer is allocated per design: a larger one costs more than it saves), or for the caller's chunk_samples. Returns the chunk size.
+static int design_stage_samples(mfm_design *d, hipStream_t s, const SampleView &v, int chunk_samples) {
+  const size_t count = (size_t)v.count(), per = (size_t)std::max<int64_t>(d->D * d->KS, 1);  // doubles of one sample's copy
+  const size_t chunk = chunk_samples > 0 ? std::min<size_t>((size_t)chunk_samples, count)
+                                         : std::max<size_t>(1, std::min<size_t>(count, ((size_t)512 << 20) / (per * sizeof(double))));
+  if (d->vt_all.n < chunk * per) d->vt_all.alloc(chunk * per);
+  if (d->wvp.n < count) d->wvp.alloc(count);
+  if (d->w0s.n < count) d->w0s.alloc(count);
+  MFM_HIP_CHECK(hipMemcpyAsync(d->wvp.p, v.wv.data(), count * sizeof(double *), hipMemcpyHostToDevice, s));
+  MFM_HIP_CHECK(hipMemcpyAsync(d->w0s.p, v.w0.data(), count * sizeof(double), hipMemcpyHostToDevice, s));
+  MFM_HIP_CHECK(hipStreamSynchronize(s));  // (pageable host vectors)
+  return (int)chunk;
+}
+// the staged samples [c0, c0 + C) as k_score_store takes them, a first and unscaled chunk without cutpoints; build: their
+// row-major V copies into vt_all first
+static ScoreStoreArgs design_sample_chunk(mfm_design *d, hipStream_t s, int c0, int C, bool build) {
+  if (build && d->K > 0 && d->D > 0)
+    hipLaunchKernelGGL(k_build_vt_batch, dim3((unsigned)cdiv(d->D, 32), (unsigned)cdiv(d->KS, 32), (unsigned)C), dim3(WG), 0, s,
+                       (const double *const *)d->wvp.p + c0, d->D, d->K, d->KS, d->vt_all.p);
+  ScoreStoreArgs sa;
+  sa.wv = (const double *const *)d->wvp.p + c0;
+  sa.vt_all = d->vt_all.p;
+  sa.w0 = d->w0s.p + c0;
+  sa.cut = nullptr;
+  sa.S = C;
+  sa.n_cut = 0;
+  sa.first = 1;
+  sa.scale = 1.0;
+  return sa;
+}
+
 // Posterior-sample store (FMTrainer.hpp:71-74 keeps the last n_kept_samples FM copies): the kept samples stay in HBM --
 // retention is a device-to-device copy on the training stream, prediction reads them in place, the host sees a sample
 // only when somebody asks for its arrays (pickling, w_samples / V_samples).
@@ -347,6 +355,51 @@ struct mfm_store {
     if (pushed) (void)hipEventDestroy(pushed);
   }
 };
+
+namespace mfm {
+SampleView samples_of_store(mfm_store *st, int first, int count) {
+  if (count <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");  // predictor.hpp:39-41
+  if (first < 0 || first + count > (int)st->wv.size()) throw Error(MFM_ERR_INVALID, "sample range out of bounds");
+  SampleView v;
+  v.device = st->device;
+  v.D = st->D;
+  v.K = st->K;
+  v.wv.resize((size_t)count);
+  for (int k = 0; k < count; k++) v.wv[(size_t)k] = st->wv[(size_t)(first + k)]->p;
+  v.w0.assign(st->w0.begin() + first, st->w0.begin() + first + count);
+  v.pushed = st->pushed_valid ? st->pushed : nullptr;
+  return v;
+}
+SampleView samples_of_host(int device, int64_t D, int rank, int n, const double *w0s, const double *ws, const double *Vs) {
+  if (n <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");
+  if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
+  SampleView v;
+  v.device = device;
+  v.D = D;
+  v.K = rank;
+  const size_t d = (size_t)D, per = std::max<size_t>(d * ((size_t)rank + 1), 1);
+  v.own.alloc(per * (size_t)n);
+  v.wv.resize((size_t)n);
+  v.w0.assign(w0s, w0s + n);
+  for (int i = 0; i < n; i++) {
+    double *b = v.own.p + per * (size_t)i;
+    if (d) MFM_HIP_CHECK(hipMemcpy(b, ws + d * (size_t)i, d * sizeof(double), hipMemcpyHostToDevice));
+    if (d && rank) MFM_HIP_CHECK(hipMemcpy(b + d, Vs + d * rank * (size_t)i, d * rank * sizeof(double), hipMemcpyHostToDevice));
+    v.wv[(size_t)i] = b;
+  }
+  return v;
+}
+// Samples that stay in HBM for a Predictor's lifetime, or for a summary call: refuse n more of them when they would take more than
+// half of what is free now (MFM_STORE_MAX_FRACTION), so that a later fit / predict on the same GPU still finds room -- the trainer
+// then keeps host copies, as it does when an allocation fails
+static void store_check_fraction(int64_t D, int K, int64_t n) {
+  const double need = (double)std::max<int64_t>(n, 0) * (double)std::max<int64_t>(D * (K + 1), 1) * sizeof(double);
+  size_t free_b = 0, total_b = 0;
+  const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
+  if (need > 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > frac * (double)free_b)
+    throw Error(MFM_ERR_RUNTIME, "sample store: the reservation exceeds MFM_STORE_MAX_FRACTION of the free device memory");
+}
+}  // namespace mfm
 
 extern "C" {
 
@@ -390,17 +443,7 @@ static mfm_store::Sample *store_new_sample(mfm_store *st) {
 
 int mfm_store_reserve(mfm_store *st, int32_t n_samples) {
   MFM_TRY(st)
-  {
-    // the kept samples live in HBM for the Predictor's lifetime: refuse a reservation that would take more than half of what
-    // is free now (MFM_STORE_MAX_FRACTION), so that a later fit / predict on the same GPU still finds room -- the trainer
-    // then keeps host copies, as it does when an allocation fails
-    const int64_t have = (int64_t)(st->wv.size() + st->spare.size());
-    const double need = (double)std::max<int64_t>(n_samples - have, 0) * (double)std::max<int64_t>(st->D * (st->K + 1), 1) * sizeof(double);
-    size_t free_b = 0, total_b = 0;
-    const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
-    if (need > 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > frac * (double)free_b)
-      throw Error(MFM_ERR_RUNTIME, "sample store: the reservation exceeds MFM_STORE_MAX_FRACTION of the free device memory");
-  }
+  store_check_fraction(st->D, st->K, (int64_t)n_samples - (int64_t)(st->wv.size() + st->spare.size()));
   {
     const size_t per = ((size_t)std::max<int64_t>(st->D * (st->K + 1), 1) + 31) & ~(size_t)31;  // doubles per sample, 256-byte multiples
     const size_t slab_max = std::max<size_t>(((size_t)4 << 30) / (per * sizeof(double)), 1);    // samples per slab
@@ -544,19 +587,7 @@ int mfm_design_score_ctx(mfm_design *d, mfm_ctx *ctx, double *out) {
   }
   const int rank = ctx->K;
   hipStream_t s = ctx->stream;  // ordered after the sweeps that produced the state
-  if (d->K != rank) {
-    d->K = rank;
-    d->KS = (rank + 1) & ~1;
-    d->Vt.alloc_zero((size_t)std::max<int64_t>(d->D * d->KS, 1), s);
-    d->score.alloc((size_t)std::max<int64_t>(d->N, 1));
-    d->w.alloc((size_t)std::max<int64_t>(d->D, 1));
-    d->V.alloc((size_t)std::max<int64_t>(d->D * rank, 1));
-    for (auto &B : d->blocks) {
-      B->bq.alloc_zero((size_t)B->B * std::max(d->KS, 1), s);
-      B->bl.alloc_zero((size_t)B->B, s);
-      B->bs.alloc_zero((size_t)B->B, s);
-    }
-  }
+  design_use_rank(d, rank, s);
   score_design(s, ctx->timing, 1, d->X, d->blocks, d->D, rank, d->KS, ctx->w0, ctx->w.p, ctx->V.p, d->Vt.p, nullptr, nullptr,
                d->score.p);
   if (d->N) MFM_HIP_CHECK(hipMemcpyAsync(out, d->score.p, (size_t)d->N * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -564,71 +595,36 @@ int mfm_design_score_ctx(mfm_design *d, mfm_ctx *ctx, double *out) {
   MFM_CATCH(d)
 }
 
-// Predictor::predict* over samples resident in a store (no per-sample upload, no host synchronisation inside the loop):
-// samples [first, first + count).
-int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t n_cut,
-                             const double *cutpoints, double *out) {
-  MFM_TRY(d)
-  if (count <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");  // predictor.hpp:39-41
-  if (first < 0 || first + count > (int)st->wv.size()) throw Error(MFM_ERR_INVALID, "sample range out of bounds");
-  if (st->device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
-  if (st->D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+}  // extern "C"
+
+// what the two flavours of Predictor::predict* share: the checks of mode and cutpoints, the rank's caches, the output buffer and
+// the samples' cutpoints [count][n_cut] on the device (mode 2). Returns the number of outputs.
+static int64_t design_predict_setup(mfm_design *d, hipStream_t s, int rank, int count, int mode, int n_cut, const double *cutpoints) {
   if (mode < 0 || mode > 2) throw Error(MFM_ERR_INVALID, "bad prediction mode");
-  if (mode == 2 && n_cut < 1) throw Error(MFM_ERR_RUNTIME, "No cutpoint available for this FM.");
-  hipStream_t s = d->stream;
-  const int rank = st->K;
-  const int64_t N = d->N, D = d->D;
+  if (mode == 2 && n_cut < 1) throw Error(MFM_ERR_RUNTIME, "No cutpoint available for this FM.");  // FM.hpp:141-143
   design_use_rank(d, rank, s);
-  const int64_t out_n = mode == 2 ? N * (n_cut + 1) : N;
+  const int64_t out_n = mode == 2 ? d->N * (n_cut + 1) : d->N;
   if (d->out.n < (size_t)std::max<int64_t>(out_n, 1)) d->out.alloc((size_t)std::max<int64_t>(out_n, 1));
-  // the samples' device-to-device copies (training stream) must be complete: this stream waits for the latest one's event
-  if (st->pushed_valid) MFM_HIP_CHECK(hipStreamWaitEvent(s, st->pushed, 0));
   if (mode == 2) {
     if (d->cut.n < (size_t)n_cut * count) d->cut.alloc((size_t)n_cut * count);
     MFM_HIP_CHECK(hipMemcpyAsync(d->cut.p, cutpoints, (size_t)n_cut * count * sizeof(double), hipMemcpyHostToDevice, s));
   }
-  // designs without relation blocks: every sample in ONE pass over the test rows (k_score_store); chunks of samples whose
-  // row-major V copies fit 512 MB (the buffer is allocated per design: a larger one costs more than it saves)
-  if (d->blocks.empty() && N > 0 && rank <= 512 && (mode != 2 || n_cut + 1 <= PRED_MAX_CLASS) && !env_flag("MFM_PREDICT_PER_SAMPLE")) {
-    const size_t per = (size_t)std::max<int64_t>(D * d->KS, 1) * sizeof(double);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)count, ((size_t)512 << 20) / per));
-    if (d->vt_all.n < (size_t)chunk * (per / sizeof(double))) d->vt_all.alloc((size_t)chunk * (per / sizeof(double)));
-    std::vector<const double *> hp((size_t)count);
-    std::vector<double> hw0((size_t)count);
-    for (int k = 0; k < count; k++) {
-      hp[k] = st->wv[first + k]->p;
-      hw0[k] = st->w0[first + k];
-    }
-    if (d->wvp.n < (size_t)count) d->wvp.alloc((size_t)count);
-    if (d->w0s.n < (size_t)count) d->w0s.alloc((size_t)count);
-    MFM_HIP_CHECK(hipMemcpyAsync(d->wvp.p, hp.data(), (size_t)count * sizeof(double *), hipMemcpyHostToDevice, s));
-    MFM_HIP_CHECK(hipMemcpyAsync(d->w0s.p, hw0.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice, s));
-    MFM_HIP_CHECK(hipStreamSynchronize(s));  // (hp / hw0 are pageable host vectors of this frame)
-    for (int c0 = 0; c0 < count; c0 += chunk) {
-      const int C = std::min(chunk, count - c0);
-      if (rank > 0 && D > 0)
-        hipLaunchKernelGGL(k_build_vt_batch, dim3((unsigned)cdiv(D, 32), (unsigned)cdiv(d->KS, 32), (unsigned)C), dim3(WG), 0, s,
-                           (const double *const *)d->wvp.p + c0, D, rank, d->KS, d->vt_all.p);
-      ScoreStoreArgs sa;
-      sa.wv = (const double *const *)d->wvp.p + c0;
-      sa.vt_all = d->vt_all.p;
-      sa.w0 = d->w0s.p + c0;
-      sa.cut = mode == 2 ? d->cut.p + (size_t)c0 * n_cut : nullptr;
-      sa.S = C;
-      sa.n_cut = mode == 2 ? n_cut : 0;
-      sa.first = c0 == 0;
-      sa.scale = c0 + C == count ? 1.0 / count : 1.0;
-      launch_score_store(s, mode, d->X, sa, D, rank, d->KS, d->out.p);
-    }
-    MFM_HIP_CHECK(hipGetLastError());
-    if (out_n) MFM_HIP_CHECK(hipMemcpyAsync(out, d->out.p, (size_t)out_n * sizeof(double), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipStreamSynchronize(s));
-    return MFM_OK;
-  }
+  return out_n;
+}
+
+// The per-sample pass (predictor.hpp:126-147): score_design, accumulate, scale by 1 / count, copy out. sample(k) yields sample
+// k on the device; for samples in a store nothing is uploaded and the host is not synchronised inside the loop.
+struct DeviceSample {
+  double w0;
+  const double *w, *V;
+};
+template <class Sample>
+static void design_predict_per_sample(mfm_design *d, hipStream_t s, int count, int mode, int n_cut, int64_t out_n, double *out,
+                                      const Sample &sample) {
+  const int64_t N = d->N;
   for (int k = 0; k < count; k++) {
-    const double *w = st->wv[first + k]->p, *V = w + D;
-    score_design(s, d->timing, 1, d->X, d->blocks, D, rank, d->KS, st->w0[first + k], w, V, d->Vt.p, nullptr, nullptr,
-                 d->score.p);
+    const DeviceSample f = sample(k);
+    score_design(s, d->timing, 1, d->X, d->blocks, d->D, d->K, d->KS, f.w0, f.w, f.V, d->Vt.p, nullptr, nullptr, d->score.p);
     if (N) {
       if (mode == 2)
         hipLaunchKernelGGL(k_accumulate_oprobit, dim3(cdiv(N, WG)), dim3(WG), 0, s, d->score.p, d->cut.p + (size_t)k * n_cut, n_cut,
@@ -643,43 +639,63 @@ int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_
     MFM_HIP_CHECK(hipMemcpyAsync(out, d->out.p, (size_t)out_n * sizeof(double), hipMemcpyDeviceToHost, s));
   }
   MFM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// Predictor::predict* over the samples of a view, all of them on the device
+static void design_predict_view(mfm_design *d, const SampleView &v, int mode, int n_cut, const double *cutpoints, double *out) {
+  if (v.device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
+  if (v.D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+  hipStream_t s = d->stream;
+  const int count = v.count(), rank = v.K;
+  const int64_t N = d->N, D = d->D;
+  const int64_t out_n = design_predict_setup(d, s, rank, count, mode, n_cut, cutpoints);
+  // a store's device-to-device copies (training stream) must be complete: this stream waits for the latest one's event
+  if (v.pushed) MFM_HIP_CHECK(hipStreamWaitEvent(s, v.pushed, 0));
+  // designs without relation blocks: every sample in ONE pass over the test rows (k_score_store), chunk of samples by chunk
+  if (d->blocks.empty() && N > 0 && rank <= 512 && (mode != 2 || n_cut + 1 <= PRED_MAX_CLASS) && !env_flag("MFM_PREDICT_PER_SAMPLE")) {
+    const int chunk = design_stage_samples(d, s, v, 0);
+    for (int c0 = 0; c0 < count; c0 += chunk) {
+      const int C = std::min(chunk, count - c0);
+      ScoreStoreArgs sa = design_sample_chunk(d, s, c0, C, true);
+      sa.cut = mode == 2 ? d->cut.p + (size_t)c0 * n_cut : nullptr;
+      sa.n_cut = mode == 2 ? n_cut : 0;
+      sa.first = c0 == 0;
+      sa.scale = c0 + C == count ? 1.0 / count : 1.0;
+      launch_score_store(s, mode, d->X, sa, D, rank, d->KS, d->out.p);
+    }
+    MFM_HIP_CHECK(hipGetLastError());
+    if (out_n) MFM_HIP_CHECK(hipMemcpyAsync(out, d->out.p, (size_t)out_n * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipStreamSynchronize(s));
+    return;
+  }
+  design_predict_per_sample(d, s, count, mode, n_cut, out_n, out, [&](int k) { return DeviceSample{v.w0[(size_t)k], v.wv[(size_t)k], v.wv[(size_t)k] + D}; });
+}
+
+extern "C" {
+
+// samples [first, first + count) resident in a store
+int mfm_design_predict_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t n_cut,
+                             const double *cutpoints, double *out) {
+  MFM_TRY(d)
+  design_predict_view(d, samples_of_store(st, first, count), mode, n_cut, cutpoints, out);
   MFM_CATCH(d)
 }
 
-int mfm_design_predict(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws,
-                       const double *Vs, int32_t mode, int32_t n_cut, const double *cutpoints, double *out) {
+// host samples, streamed one at a time through the pinned ring into the design's own w / V: the flavour that never holds all samples
+// on the device, and so still runs when memory is tight
+int mfm_design_predict(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t mode, int32_t n_cut, const double *cutpoints, double *out) {
   MFM_TRY(d)
   if (n_samples <= 0) throw Error(MFM_ERR_RUNTIME, "Told to predict but no sample available.");  // predictor.hpp:39-41
   if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
-  if (mode < 0 || mode > 2) throw Error(MFM_ERR_INVALID, "bad prediction mode");
-  if (mode == 2 && n_cut < 1) throw Error(MFM_ERR_RUNTIME, "No cutpoint available for this FM.");  // FM.hpp:141-143
   hipStream_t s = d->stream;
-  const int64_t N = d->N, D = d->D;
-  design_use_rank(d, rank, s);
-  const int64_t out_n = mode == 2 ? N * (n_cut + 1) : N;
-  if (d->out.n < (size_t)std::max<int64_t>(out_n, 1)) d->out.alloc((size_t)std::max<int64_t>(out_n, 1));
-  if (mode == 2 && d->cut.n < (size_t)n_cut) d->cut.alloc((size_t)n_cut);
-  for (int smp = 0; smp < n_samples; smp++) {
-    if (D) d->ring.upload(d->w.p, ws + (size_t)smp * D, (size_t)D * sizeof(double), s);
-    if (D && rank) d->ring.upload(d->V.p, Vs + (size_t)smp * D * rank, (size_t)D * rank * sizeof(double), s);
-    score_design(s, d->timing, 1, d->X, d->blocks, D, rank, d->KS, w0s[smp], d->w.p, d->V.p, d->Vt.p, nullptr, nullptr,
-                 d->score.p);
-    if (N) {
-      if (mode == 2) {
-        d->ring.upload(d->cut.p, cutpoints + (size_t)smp * n_cut, (size_t)n_cut * sizeof(double), s);
-        hipLaunchKernelGGL(k_accumulate_oprobit, dim3(cdiv(N, WG)), dim3(WG), 0, s, d->score.p, d->cut.p, n_cut, d->out.p,
-                           N, smp == 0);
-      } else {
-        hipLaunchKernelGGL(k_accumulate_pred, dim3(cdiv(N, WG)), dim3(WG), 0, s, d->score.p, d->out.p, N, mode, smp == 0);
-      }
-      MFM_HIP_CHECK(hipGetLastError());
-    }
-  }
-  if (out_n) {
-    hipLaunchKernelGGL(k_scale, dim3(cdiv(out_n, WG)), dim3(WG), 0, s, d->out.p, out_n, 1.0 / n_samples);
-    MFM_HIP_CHECK(hipMemcpyAsync(out, d->out.p, (size_t)out_n * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  MFM_HIP_CHECK(hipStreamSynchronize(s));
+  const size_t D = (size_t)d->D;
+  const int64_t out_n = design_predict_setup(d, s, rank, n_samples, mode, n_cut, cutpoints);
+  design_predict_per_sample(d, s, n_samples, mode, n_cut, out_n, out, [&](int k) {
+    if (D) d->ring.upload(d->w.p, ws + (size_t)k * D, D * sizeof(double), s);
+    if (D && rank) d->ring.upload(d->V.p, Vs + (size_t)k * D * rank, D * rank * sizeof(double), s);
+    return DeviceSample{w0s[k], d->w.p, d->V.p};
+  });
   MFM_CATCH(d)
 }
 
