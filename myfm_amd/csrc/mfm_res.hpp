@@ -30,6 +30,7 @@
 #include <atomic>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "mfm_common.hpp"
@@ -68,6 +69,8 @@ struct ResArgs {
   const int2 *item_desc;     // item -> {feature, group}
   double *partials;          // [runs + 1][2], workgroup-major: a thread's runs are consecutive; the last stays (0, 0)
   double *dv;                // [items + 1][2]  (delta of this factor, coefficient of the next); the pad item stays (0, 0)
+                             // S2B: [items + 1][4]  (delta, coefficient of the next sweep, SQUARE of the coefficient of the sweep
+                             // after next, 0): 32-byte entries, sweep A gathers 16 bytes at + 0, sweep B 16 bytes at + 8
   double *V;                 // factor-major [K][D]
   int64_t D;
   int f_begin, f_end;
@@ -207,6 +210,11 @@ __device__ __forceinline__ void res_grid_barrier(const ResArgs &a, const ResBar 
 
 typedef double res_d16_t __attribute__((ext_vector_type(16)));
 typedef unsigned res_u4_t __attribute__((ext_vector_type(4)));
+typedef double res_d2u_t __attribute__((ext_vector_type(2), aligned(8)));  // a pair at an 8-byte boundary (dv + 8 of a 32-byte entry)
+__device__ __forceinline__ double res_cc0(double x) { return x; }
+__device__ __forceinline__ double res_cc1(double) { return 0.0; }
+__device__ __forceinline__ double res_cc0(res_d2u_t x) { return x[0]; }
+__device__ __forceinline__ double res_cc1(res_d2u_t x) { return x[1]; }
 
 // NT threads; a thread's slots come in groups of 16: NGV groups live in registers (one 16-double vector each), NGL groups in
 // LDS ([16 NGL][NT] doubles: lane-consecutive, conflict-free). Everything static about a group stays in registers for the whole
@@ -224,7 +232,12 @@ typedef unsigned res_u4_t __attribute__((ext_vector_type(4)));
 // the slot-ordered buffer in global memory (e_slots: 8 bytes read + 8 written per slot and sweep, coalesced) and whose static
 // words are read again every sweep; they run through the same batch steps behind the on-chip groups (the run / dv gather
 // pipelines carry straight on), so the sums, partials and draws are those of the all-on-chip form.
-template <int NT, int NGV, int NGL, bool XCH = false, bool OVF = false>
+// S2B: the user level's sum of h^2 (h = the item's coefficient, which nothing changes between the item's own draws) is taken in
+// sweep B of the sweep BEFORE, where the LDS unit has room, instead of in sweep A: one ds_add_f64 per slot moves from A to B,
+// into a third wave-private array acc3 (acc1 / acc2 serve the item draw in between). Same products, same accumulator per wave,
+// same slot order: the sums are bit for bit those of the other form. The first sweep of a launch has no sweep B before it: a
+// rolled prologue walks the slots once.
+template <int NT, int NGV, int NGL, bool XCH = false, bool OVF = false, bool S2B = false>
 __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   extern __shared__ __attribute__((aligned(16))) char res_smem[];
   constexpr int NW = NT / WAVE, NG = NGV + NGL, R = 16 * NG, RL = 16 * NGL;
@@ -238,16 +251,18 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   double *elds = (double *)(utab + U);    // [RL][NT] residual of the LDS-resident slots
   double *acc1 = elds + (size_t)RL * NT;  // [NW][U]  sum of -e h per (wave, user) / (wave, item of the slice)
   double *acc2 = acc1 + NW * U;           // [NW][U]  sum of h^2
-  d2_t *wcarry = (d2_t *)(acc2 + NW * U); // [NW]
+  double *acc3 = acc2 + NW * U;           // [NW][U]  S2B: sum of h^2 of the NEXT sweep's user level
+  d2_t *wcarry = (d2_t *)(acc2 + (S2B ? 2 : 1) * NW * U);  // [NW]
   int *wflag = (int *)(wcarry + NW);      // [NW]
   const int32_t *perm_g = a.perm + (int64_t)g * Rt * NT;
   const int u0 = a.wg_user_ptr[g], nu = a.wg_user_ptr[g + 1] - u0;
   const int rb0 = a.wg_run_ptr[g];
   const int pad_item = a.n_items;
   // the sweeps' gathers take 32-bit byte offsets from the arrays' (wave-uniform) bases: global_load v_off, s[base]
-  const unsigned rb0b = 4u * (unsigned)rb0, padb = 16u * (unsigned)pad_item;
+  constexpr int DSH = S2B ? 5 : 4;  // log2 of a dv entry's bytes
+  const unsigned rb0b = 4u * (unsigned)rb0, padb = (unsigned)pad_item << DSH;
   const char *run_item_b = (const char *)a.run_item, *dv_b = (const char *)a.dv;
-  double *acc1w = acc1 + wv * U, *acc2w = acc2 + wv * U;  // this wave's accumulator arrays
+  double *acc1w = acc1 + wv * U, *acc2w = acc2 + wv * U, *acc3w = acc3 + wv * U;  // this wave's accumulator arrays
   bool dead = false;
   unsigned long long nbar = 0;
   ResBar rbar;
@@ -272,7 +287,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
 #define RES_STAMP(k)                                                                                      \
   if (a.prof && tid == 0) a.prof[((int64_t)g * a.n_sw + (f - f_first)) * 64 + (k)] = __builtin_amdgcn_s_memrealtime()
 
-  for (int i = tid; i < 2 * NW * U; i += NT) acc1[i] = 0.0;
+  for (int i = tid; i < (S2B ? 3 : 2) * NW * U; i += NT) acc1[i] = 0.0;
   for (int i = tid; i < U; i += NT) utab[i] = d2_t{0.0, 0.0};
 
   // static per-thread words
@@ -357,6 +372,35 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     }
   }
   __syncthreads();
+  if (S2B) {
+    // the first sweep's sum of h^2: what sweep B of the sweep before would have left in acc3. One rolled walk over the slots in
+    // sweep A's order (on-chip groups, then the overflow groups), static words read again from global memory, a divergent fetch
+    // at the run starts: once per launch, small rather than fast. k_res_init_dv left the first sweep's coefficient in dv[.][1]
+    // (1 for the linear sweep).
+    const uint32_t *uidw_p = a.uidw + (int64_t)g * (5 * NGt) * NT + tid;
+    const uint32_t *headw_p = a.headw + (int64_t)g * NGt * NT + tid;
+    int run = run0 - 1;
+    double c = 0.0;
+#pragma unroll 1
+    for (int jp = 0; jp < NGt; jp++) {
+      const unsigned nb = headw_p[jp * NT] | (jp == 0 ? 1u : 0u);
+      const unsigned uxp = uidw_p[(5 * jp + 4) * NT];
+#pragma unroll 1
+      for (int bb = 0; bb < 4; bb++) {
+        const unsigned lo_ = uidw_p[(5 * jp + bb) * NT];
+#pragma unroll 1
+        for (int k = 0; k < B; k++) {
+          if ((nb >> (4 * bb + k)) & 1u) {
+            run++;
+            c = a.dv[((int64_t)a.run_item[run] << (DSH - 3)) + 1];
+          }
+          const int uid = k < 3 ? (int)((lo_ >> (10 * k)) & 0x3ffu) : (int)((lo_ >> 30) | (((uxp >> (8 * bb)) & 0xffu) << 2));
+          __hip_atomic_fetch_add(&acc3w[uid], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    }
+    __syncthreads();
+  }
 
   RES_STAMP0(2);
   const int f_first = a.f_begin - a.linear;
@@ -400,7 +444,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
           itA[k] = *(const int *)(run_item_b + ((n1 >> k) & 1u ? rcb : rb0b));
         }
 #pragma unroll
-        for (int k = 0; k < B; k++) ddA[k] = *(const d2_t *)(dv_b + ((n0 >> k) & 1u ? (unsigned)it0[k] << 4 : padb));
+        for (int k = 0; k < B; k++) ddA[k] = *(const d2_t *)(dv_b + ((n0 >> k) & 1u ? (unsigned)it0[k] << DSH : padb));
       }
       d2_t ddc = d2_t{0.0, 0.0};
       int itB[B];
@@ -416,7 +460,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
     }                                                                                                                      \
     _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
-      ddo[k] = *(const d2_t *)(dv_b + ((n4a >> k) & 1u ? (unsigned)iti[k] << 4 : padb));                                   \
+      ddo[k] = *(const d2_t *)(dv_b + ((n4a >> k) & 1u ? (unsigned)iti[k] << DSH : padb));                                 \
     int uid[B];                                                                                                            \
     RES_UIDS(j, bb, uid);                                                                                                  \
     double up[B], ex[B];                                                                                                   \
@@ -435,7 +479,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
         elds[(16 * (j - NGV) + 4 * (bb) + k) * NT + tid] = er;                                                             \
       const double c = ddc[1];                                                                                             \
       __hip_atomic_fetch_add(&acc1w[uid[k]], (-er) * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                   \
-      __hip_atomic_fetch_add(&acc2w[uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                       \
+      if (!S2B) __hip_atomic_fetch_add(&acc2w[uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);             \
     }                                                                                                                      \
   }
 #define RES_STEP_AX(bb, iti, ito, ddi, ddo)                                                                                 \
@@ -446,7 +490,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
     }                                                                                                                      \
     _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
-      ddo[k] = *(const d2_t *)(dv_b + ((n4a >> k) & 1u ? (unsigned)iti[k] << 4 : padb));                                   \
+      ddo[k] = *(const d2_t *)(dv_b + ((n4a >> k) & 1u ? (unsigned)iti[k] << DSH : padb));                                 \
     int uid[B];                                                                                                            \
     RES_UIDSX(bb, uid);                                                                                                      \
     double up[B], ex[B];                                                                                                   \
@@ -462,7 +506,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       eo[4 * (bb) + k] = er;                                                             \
       const double c = ddc[1];                                                                                             \
       __hip_atomic_fetch_add(&acc1w[uid[k]], (-er) * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                   \
-      __hip_atomic_fetch_add(&acc2w[uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                       \
+      if (!S2B) __hip_atomic_fetch_add(&acc2w[uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);             \
     }                                                                                                                      \
   }
 #pragma unroll
@@ -507,10 +551,11 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       double S1 = 0.0, S2 = 0.0;
 #pragma unroll
       for (int w = 0; w < NW; w++) {
+        double *accS = S2B ? acc3 : acc2;  // (S2B: acc2 was not touched since the item draw zeroed it)
         S1 += acc1[w * U + tid];
-        S2 += acc2[w * U + tid];
+        S2 += accS[w * U + tid];
         acc1[w * U + tid] = 0.0;
-        acc2[w * U + tid] = 0.0;
+        accS[w * U + tid] = 0.0;
       }
       const double fresh = PMainV::draw(S1, S2, uold, alpha_k, ulam, umu, uz);
       Vf[uj] = fresh;
@@ -523,8 +568,12 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     }
     __syncthreads();
     RES_STAMP(2);
-    // ---- sweep B: the user update (:371-375), the item level's statistics run by run
+    // ---- sweep B: the user update (:371-375), the item level's statistics run by run; S2B: the NEXT sweep's sum of h^2 of the
+    //      user level (the 16-byte gather at dv + 8 brings the square along with this sweep's coefficient)
     {
+      typedef typename std::conditional<S2B, res_d2u_t, double>::type cc_t;
+#define RES_CC0(x) res_cc0(x)
+#define RES_CC1(x) res_cc1(x)
       bool have_head = false;
       double f1 = 0.0, f2 = 0.0, s1 = 0.0, s2 = 0.0;
       d2_t *part2 = (d2_t *)a.partials;
@@ -536,7 +585,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
         unsigned rcb = 4u * (unsigned)(run0 - 1);  // run counter of the run_item stage, in bytes
         unsigned rcCb = 16u * (unsigned)(run0 - 1);  // ... and of the compute stage, in bytes
         int itA[B];
-        double ccA[B];
+        cc_t ccA[B];
         {
           int it0[B];
           const unsigned n0 = RES_NIB(0, 0), n1 = RES_NIB(0, 1);
@@ -551,11 +600,11 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
             itA[k] = *(const int *)(run_item_b + ((n1 >> k) & 1u ? rcb : rb0b));
           }
 #pragma unroll
-          for (int k = 0; k < B; k++) ccA[k] = *(const double *)(dv_b + 8 + ((n0 >> k) & 1u ? (unsigned)it0[k] << 4 : padb));
+          for (int k = 0; k < B; k++) ccA[k] = *(const cc_t *)(dv_b + 8 + ((n0 >> k) & 1u ? (unsigned)it0[k] << DSH : padb));
         }
-        double ccc = 0.0;
+        double ccc = 0.0, cqc = 0.0;  // the run's coefficient; S2B: the square of its next sweep's
         int itB[B];
-        double ccB[B];
+        cc_t ccB[B];
 // One store per slot, no branch: a slot that closes no run stores into the workgroup's pad run, which nobody reads. (Some
 // lane of a wave closes a run at almost every slot -- a run start every 4.9th slot, 64 lanes -- so the masked store was
 // issued anyway; its exec-mask save / restore split every step into basic blocks.)
@@ -569,7 +618,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
     }                                                                                                                      \
     _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
-      cco[k] = *(const double *)(dv_b + 8 + ((n4a >> k) & 1u ? (unsigned)iti[k] << 4 : padb));                             \
+      cco[k] = *(const cc_t *)(dv_b + 8 + ((n4a >> k) & 1u ? (unsigned)iti[k] << DSH : padb));                             \
     int uid[B];                                                                                                            \
     RES_UIDS(j, bb, uid);                                                                                                  \
     d2_t ut[B];                                                                                                            \
@@ -581,7 +630,11 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
       const bool need = ((n4 >> k) & 1u) != 0u;                                                                            \
       const bool head = ((h4 >> k) & 1u) != 0u;                                                                            \
-      ccc = need ? cci[k] : ccc;                                                                                           \
+      ccc = need ? RES_CC0(cci[k]) : ccc;                                                                                  \
+      if (S2B) {                                                                                                           \
+        cqc = need ? RES_CC1(cci[k]) : cqc;                                                                                \
+        __hip_atomic_fetch_add(&acc3w[uid[k]], cqc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                       \
+      }                                                                                                                    \
       rcCb += need ? 16u : 0u; /* the run of this slot, in bytes */                                                        \
       /* a run that began and ended in this thread: the slot before this head closed the run before it */                        \
       RES_PARTIAL_STORE();                                                                                                 \
@@ -606,7 +659,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
     }                                                                                                                      \
     _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
-      cco[k] = *(const double *)(dv_b + 8 + ((n4a >> k) & 1u ? (unsigned)iti[k] << 4 : padb));                             \
+      cco[k] = *(const cc_t *)(dv_b + 8 + ((n4a >> k) & 1u ? (unsigned)iti[k] << DSH : padb));                             \
     int uid[B];                                                                                                            \
     RES_UIDSX(bb, uid);                                                                                                      \
     d2_t ut[B];                                                                                                            \
@@ -618,7 +671,11 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
       const bool need = ((n4 >> k) & 1u) != 0u;                                                                            \
       const bool head = ((h4 >> k) & 1u) != 0u;                                                                            \
-      ccc = need ? cci[k] : ccc;                                                                                           \
+      ccc = need ? RES_CC0(cci[k]) : ccc;                                                                                  \
+      if (S2B) {                                                                                                           \
+        cqc = need ? RES_CC1(cci[k]) : cqc;                                                                                \
+        __hip_atomic_fetch_add(&acc3w[uid[k]], cqc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                       \
+      }                                                                                                                    \
       rcCb += need ? 16u : 0u; /* the run of this slot, in bytes */                                                        \
       /* a run that began and ended in this thread: the slot before this head closed the run before it */                        \
       RES_PARTIAL_STORE();                                                                                                 \
@@ -667,6 +724,8 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
         }
 #undef RES_STEP_B
 #undef RES_STEP_BX
+#undef RES_CC0
+#undef RES_CC1
 #undef RES_PARTIAL_STORE
       }
       if (a.prof && lane == 0)  // (per wave: the end of its own sweep B)
@@ -716,13 +775,14 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     const int i0 = a.wg_item_ptr[g], ni = a.wg_item_ptr[g + 1] - i0;
     const bool more = f + 1 < a.f_end;
     int ij = 0;
-    double iold = 0.0, iz = 0.0, ivn = 0.0, ilam = 0.0, imu = 0.0;
+    double iold = 0.0, iz = 0.0, ivn = 0.0, ivq = 0.0, ilam = 0.0, imu = 0.0;
     if (tid < ni) {
       const int2 d = a.item_desc[i0 + tid];
       ij = d.x;
       iold = Vf[ij];
       iz = zf[ij];
       ivn = more ? a.V[(int64_t)(f + 1) * a.D + ij] : 0.0;
+      if (S2B) ivq = f + 2 < a.f_end ? a.V[(int64_t)(f + 2) * a.D + ij] : 0.0;
       ilam = lamf[d.y];
       imu = muf[d.y];
     }
@@ -813,7 +873,8 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       if (tid < ni) {
         const double fresh = PMainV::draw(S1, S2, iold, alpha_k, ilam, imu, iz);
         Vf[ij] = fresh;
-        res_store2(a.dv + 2 * (int64_t)(i0 + tid), fresh - iold, ivn);
+        res_store2(a.dv + ((int64_t)(i0 + tid) << (DSH - 3)), fresh - iold, ivn);
+        if (S2B) __hip_atomic_store(a.dv + 4 * (int64_t)(i0 + tid) + 2, ivq * ivq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
     RES_STAMP(5);
@@ -841,7 +902,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
         RES_UIDS(j, bb, uid);
 #pragma unroll
         for (int k = 0; k < B; k++) {
-          const double dl = a.dv[2 * (int64_t)it[k]];
+          const double dl = a.dv[(int64_t)it[k] << (DSH - 3)];
           const double ex = j < NGV ? ev[j < NGV ? j : 0][4 * bb + k] : elds[(16 * (j - NGV) + 4 * bb + k) * NT + tid];
           const double ef = ex + utab[uid[k]][0] * dl;
           if (a.e_slots)
@@ -870,7 +931,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
           RES_UIDSX(bb, uid);
 #pragma unroll
           for (int k = 0; k < B; k++) {
-            const double dl = a.dv[2 * (int64_t)it[k]];
+            const double dl = a.dv[(int64_t)it[k] << (DSH - 3)];
             double *ep = eog + (16 * jx + 4 * bb + k) * NT;
             *ep = *ep + utab[uid[k]][0] * dl;
           }
@@ -889,11 +950,25 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
 }
 
 // ---- host side: the resident layout of a two-field table and the launch ---------------------------------------------
+// theta2 (32-byte entries, S2B): the coefficients of the sweep after the first (null: there is none); otherwise 16-byte entries
 __global__ void k_res_init_dv(const double *__restrict__ theta, const int32_t *__restrict__ scols, int n_items,
-                              double *__restrict__ dv, unsigned long long *__restrict__ bar) {
+                              double *__restrict__ dv, unsigned long long *__restrict__ bar, int wide = 0,
+                              const double *__restrict__ theta2 = nullptr) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.x == 0)  // the launch's barrier words start from zero (one dispatch less than a memset of their own)
     for (int k = threadIdx.x; k < RES_BAR_WORDS; k += blockDim.x) bar[k] = 0ull;
+  if (wide) {
+    if (i < n_items) {
+      const double c2 = theta2 ? theta2[scols[i]] : 0.0;
+      dv[4 * i] = 0.0;
+      dv[4 * i + 1] = theta ? theta[scols[i]] : 1.0;
+      dv[4 * i + 2] = c2 * c2;
+      dv[4 * i + 3] = 0.0;
+    } else if (i == n_items) {
+      for (int k = 0; k < 4; k++) dv[4 * i + k] = 0.0;
+    }
+    return;
+  }
   if (i < n_items) {
     dv[2 * i] = 0.0;
     dv[2 * i + 1] = theta ? theta[scols[i]] : 1.0;  // (theta == null: the linear sweep, h = 1)
@@ -1124,6 +1199,17 @@ struct ResPlan {
   bool allow_overflow = true;  // (false: row-sharded -- the exchange variant of the kernel has no overflow form)
   int64_t n_rows = 0, n_runs = 0;  // (workgroup, item) pairs
   size_t lds_bytes = 0;
+  int s2b = 0;  // 1: the kernel form that takes the user level's sum of h^2 in the sweep before (k_mf_resident<.., S2B>; 32-byte dv entries)
+  // LDS of the plan's kernel and the form it runs: S2B's third accumulator array where it fits and the variant has the form
+  // (<512, 4, 1> and its overflow form, not row-sharded), else the two-array form
+  bool plan_lds() {
+    const size_t nw = (size_t)(NT / WAVE), lim = 160 * 1024 - 512;
+    lds_bytes = (size_t)RL * NT * 8 + 2 * nw * umax * 8 + (size_t)umax * 16 + nw * 16 + nw * 4 + 64;
+    if (lds_bytes > lim) return false;
+    s2b = allow_overflow && RV == 64 && RL == 16 && lds_bytes + nw * umax * 8 <= lim ? 1 : 0;
+    if (s2b) lds_bytes += nw * umax * 8;
+    return true;
+  }
   DevBuf<int32_t> perm, first_run, wg_run_ptr, wg_nruns, wg_user_ptr, wg_item_ptr, ent_ptr, scols;
   DevBuf<int2> entries;
   DevBuf<uint32_t> uidw, headw;
@@ -1519,8 +1605,7 @@ struct ResPlan {
         }
     }
     if (h_entries.size() >= ((size_t)1 << 31)) return fail("too many entries");
-    lds_bytes = (size_t)RL * NT * 8 + (size_t)2 * (NT / WAVE) * umax * 8 + (size_t)umax * 16 + (size_t)(NT / WAVE) * 16 + (NT / WAVE) * 4 + 64;
-    if (lds_bytes > 160 * 1024 - 512) return fail("LDS");
+    if (!plan_lds()) return fail("LDS");
     uidw.upload(h_uidw);
     headw.upload(h_headw);
     run_item.upload(h_run_item);
@@ -1591,7 +1676,7 @@ struct ResPlan {
     }
     partials.alloc((size_t)2 * ((size_t)zero_run + 1));
     MFM_HIP_CHECK(hipMemset(partials.p, 0, (size_t)16 * ((size_t)zero_run + 1)));
-    dv.alloc((size_t)2 * (n_items + 1));
+    dv.alloc((size_t)(s2b ? 4 : 2) * (n_items + 1));
     bar.alloc(RES_BAR_WORDS);
     ready = true;
     why.clear();
@@ -1613,7 +1698,8 @@ static inline hipError_t res_occupancy(const ResPlan &rp, int *per_cu) {
   else if (rp.RV == 32 && rp.RL == 0)
     fn = (const void *)k_mf_resident<512, 2, 0>;
   else if (rp.RV == 64 && rp.RL == 16)
-    fn = rp.RX ? (const void *)k_mf_resident<512, 4, 1, false, true> : (const void *)k_mf_resident<512, 4, 1>;
+    fn = rp.s2b ? (rp.RX ? (const void *)k_mf_resident<512, 4, 1, false, true, true> : (const void *)k_mf_resident<512, 4, 1, false, false, true>)
+                : (rp.RX ? (const void *)k_mf_resident<512, 4, 1, false, true> : (const void *)k_mf_resident<512, 4, 1>);
   else
     return hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1703,9 +1789,12 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
   // its 8-byte list entry, its item read by both sweeps (2 x 4 B)
   double bytes = (8.0 + (load_slots ? 0.0 : 4.0) + 1.4 + (no_store ? 0.0 : 8.0)) * rp.n_rows + K * 48.0 * rp.n_runs;  // (slot order: no map; no_store: not written back)
   if (rp.RX) bytes += (double)K * (16.0 + 1.75) * (double)rp.G * rp.NT * rp.RX;  // overflow slots: residual read + written, static words, per sweep
-  hipLaunchKernelGGL(k_res_init_dv, dim3((rp.n_items + 256) / 256), dim3(256), 0, s,
-                     w ? (const double *)nullptr : V + (int64_t)f_begin * D, rp.scols.p, rp.n_items,
-                     rp.dv.p, rp.bar.p);
+  {
+    const int f_second = f_begin + (w ? 0 : 1);  // the factor of the launch's second sweep (S2B: its square goes into dv too)
+    hipLaunchKernelGGL(k_res_init_dv, dim3((rp.n_items + 256) / 256), dim3(256), 0, s,
+                       w ? (const double *)nullptr : V + (int64_t)f_begin * D, rp.scols.p, rp.n_items,
+                       rp.dv.p, rp.bar.p, rp.s2b, rp.s2b && f_second < f_end ? V + (int64_t)f_second * D : (const double *)nullptr);
+  }
   TimedLaunch t(tm, s, kernel_class, bytes);
 #define MFM_RES_LAUNCH(RV_, RL_)                                                                                              \
   do {                                                                                                                        \
@@ -1731,7 +1820,19 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
     MFM_RES_LAUNCH(16, 0);
   else if (rp.RV == 32 && rp.RL == 0)
     MFM_RES_LAUNCH(32, 0);
-  else if (rp.RV == 64 && rp.RL == 16 && rp.RX > 0) {
+  else if (rp.RV == 64 && rp.RL == 16 && rp.s2b) {
+    if (xch) throw Error(MFM_ERR_RUNTIME, "internal: no row-sharded resident kernel of the S2B form");
+    static DeviceOnce raised_s;
+    if (raised_s.need()) {
+      MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_mf_resident<512, 4, 1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_mf_resident<512, 4, 1, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      raised_s.mark();
+    }
+    if (rp.RX > 0)
+      hipLaunchKernelGGL((k_mf_resident<512, 4, 1, false, true, true>), dim3(rp.G), dim3(512), rp.lds_bytes, s, a);
+    else
+      hipLaunchKernelGGL((k_mf_resident<512, 4, 1, false, false, true>), dim3(rp.G), dim3(512), rp.lds_bytes, s, a);
+  } else if (rp.RV == 64 && rp.RL == 16 && rp.RX > 0) {
     if (xch) throw Error(MFM_ERR_RUNTIME, "internal: no row-sharded resident kernel with overflow slots");
     static DeviceOnce raised_o;
     if (raised_o.need()) {

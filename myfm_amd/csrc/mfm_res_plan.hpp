@@ -507,9 +507,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
     for (int g = 0; g < G; g++) h_fill[g] = h_rowcut[g + 1] - h_rowcut[g];
     rpn.wg_fill.upload(h_fill);
   }
-  rpn.lds_bytes = (size_t)rpn.RL * NT * 8 + (size_t)2 * (NT / WAVE) * rpn.umax * 8 + (size_t)rpn.umax * 16 + (size_t)(NT / WAVE) * 16 +
-                  (NT / WAVE) * 4 + 64;
-  if (rpn.lds_bytes > 160 * 1024 - 512) return rpn.fail("LDS");
+  if (!rpn.plan_lds()) return rpn.fail("LDS");
   rpn.e_slots.alloc((size_t)G * cap_slots);
   rpn.sums.alloc((size_t)G);
   rpn.y_slots = DevBuf<double>();
@@ -517,7 +515,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
   rpn.h_diag.clear();
   rpn.partials.alloc((size_t)2 * ((size_t)zero_run + 1));
   MFM_HIP_CHECK(hipMemsetAsync(rpn.partials.p, 0, (size_t)16 * ((size_t)zero_run + 1), s));
-  rpn.dv.alloc((size_t)2 * (n_items + 1));
+  rpn.dv.alloc((size_t)(rpn.s2b ? 4 : 2) * (n_items + 1));
   rpn.bar.alloc(RES_BAR_WORDS);
   MFM_HIP_CHECK(hipStreamSynchronize(s));
   MFM_HIP_CHECK(hipGetLastError());
@@ -530,7 +528,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
 // tests (MFM_PLAN_CHECK): every array of the device-built layout against the host-built one
 static inline std::string res_plan_compare(const ResPlan &a, const ResPlan &b, hipStream_t s) {
   if (a.G != b.G || a.RV != b.RV || a.RL != b.RL || a.RX != b.RX || a.umax != b.umax || a.item_bits != b.item_bits || a.n_items != b.n_items ||
-      a.n_rows != b.n_rows || a.n_runs != b.n_runs || a.lds_bytes != b.lds_bytes || a.max_wg_users != b.max_wg_users ||
+      a.n_rows != b.n_rows || a.n_runs != b.n_runs || a.lds_bytes != b.lds_bytes || a.s2b != b.s2b || a.max_wg_users != b.max_wg_users ||
       a.max_slice_items != b.max_slice_items)
     return "scalars";
   auto same = [&](const void *p, size_t np, const void *q, size_t nq, size_t elem) {

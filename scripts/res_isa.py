@@ -147,7 +147,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm", help="read this listing instead of compiling")
     ap.add_argument("--keep", help="write the compiled listing here")
-    ap.add_argument("--all", action="store_true", help="every instantiation (default: <512,4,1,false,false> and its OVF / XCH forms)")
+    ap.add_argument("--all", action="store_true", help="every instantiation (default: <512,4,1,...> in all its forms: OVF, XCH, S2B)")
     args = ap.parse_args()
     path = args.asm
     if not path:
@@ -158,9 +158,9 @@ def main():
     funcs, meta = functions(lines), kernel_meta(lines)
     print("%-28s" % "" + "".join("%9s" % k[:9] for k in CATS))
     for name in sorted(funcs):
-        m = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E", name)
-        tag = "<%s,%s,%s,%s,%s>" % (m.group(1), m.group(2), m.group(3), "true" if m.group(4) == "1" else "false",
-                                    "true" if m.group(5) == "1" else "false") if m else name
+        m = re.search(r"ILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELb(\d)E(?:Lb(\d)E)?", name)  # (the sixth flag, S2B: from its introduction on)
+        tag = "<%s>" % ",".join([m.group(1), m.group(2), m.group(3)] +
+                                ["true" if b == "1" else "false" for b in m.groups()[3:] if b is not None]) if m else name
         if not args.all and not (m and m.group(2) == "4" and m.group(3) == "1"):
             continue
         body = funcs[name]
