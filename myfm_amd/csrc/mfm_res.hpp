@@ -208,6 +208,8 @@ __device__ __forceinline__ void res_grid_barrier(const ResArgs &a, const ResBar 
   __syncthreads();
 }
 
+// log2 of a dv entry's bytes: {delta, coefficient}; S2B: {delta, coefficient, square of the sweep after next's, 0}
+constexpr int res_dv_shift(bool s2b) { return s2b ? 5 : 4; }
 typedef double res_d16_t __attribute__((ext_vector_type(16)));
 typedef unsigned res_u4_t __attribute__((ext_vector_type(4)));
 typedef double res_d2u_t __attribute__((ext_vector_type(2), aligned(8)));  // a pair at an 8-byte boundary (dv + 8 of a 32-byte entry)
@@ -215,6 +217,30 @@ __device__ __forceinline__ double res_cc0(double x) { return x; }
 __device__ __forceinline__ double res_cc1(double) { return 0.0; }
 __device__ __forceinline__ double res_cc0(res_d2u_t x) { return x[0]; }
 __device__ __forceinline__ double res_cc1(res_d2u_t x) { return x[1]; }
+
+// How k_mf_resident and k_res_score (both have NT, g and tid) read the slots' static words. Shared as macros, here and inside
+// k_mf_resident: the kernels are held to their listings (scripts/res_isa.py --same), and a macro hands the compiler the
+// statements it had (the decode as a loop over k, or a group's words through one pointer, changed every instantiation).
+// User k of batch bb of a group, 10 bits: users 0 .. 2 in word bb (lo); of user 3 the low 2 bits there, the high 8 in byte bb of
+// the group's fifth word (hi)
+#define RES_UID(lo, hi, bb, k) \
+  ((k) < 3 ? (int)(((lo) >> (10 * (k))) & 0x3ffu) : (int)(((lo) >> 30) | ((((hi) >> (8 * (bb))) & 0xffu) << 2)))
+#define RES_UIDS(lo, hi, bb, uid)        \
+  {                                      \
+    const unsigned lo_ = lo;             \
+    uid[0] = RES_UID(lo_, hi, bb, 0);    \
+    uid[1] = RES_UID(lo_, hi, bb, 1);    \
+    uid[2] = RES_UID(lo_, hi, bb, 2);    \
+    uid[3] = RES_UID(lo_, hi, bb, 3);    \
+  }
+// the five user words of a group (-> uw_, ux_): word w of it is p_[(row_ + w) NT + off_]
+#define RES_USER_WORDS(p_, row_, off_, uw_, ux_)                                                      \
+  _Pragma("unroll") for (int w_ = 0; w_ < 4; w_++) uw_[w_] = (p_)[((row_) + w_) * NT + (off_)];       \
+  ux_ = (p_)[((row_) + 4) * NT + (off_)]
+// ... of group j_ of workgroup g of a layout with ngt_ groups per thread, and the group's head bits (-> hb_)
+#define RES_GROUP_WORDS(a_, ngt_, j_, uw_, ux_, hb_)                                           \
+  RES_USER_WORDS((a_).uidw, (int64_t)g * (5 * (ngt_)) + 5 * (j_), tid, uw_, ux_);              \
+  hb_ = (a_).headw[((int64_t)g * (ngt_) + (j_)) * NT + tid]
 
 // NT threads; a thread's slots come in groups of 16: NGV groups live in registers (one 16-double vector each), NGL groups in
 // LDS ([16 NGL][NT] doubles: lane-consecutive, conflict-free). Everything static about a group stays in registers for the whole
@@ -259,7 +285,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   const int rb0 = a.wg_run_ptr[g];
   const int pad_item = a.n_items;
   // the sweeps' gathers take 32-bit byte offsets from the arrays' (wave-uniform) bases: global_load v_off, s[base]
-  constexpr int DSH = S2B ? 5 : 4;  // log2 of a dv entry's bytes
+  constexpr int DSH = res_dv_shift(S2B);
   const unsigned rb0b = 4u * (unsigned)rb0, padb = (unsigned)pad_item << DSH;
   const char *run_item_b = (const char *)a.run_item, *dv_b = (const char *)a.dv;
   double *acc1w = acc1 + wv * U, *acc2w = acc2 + wv * U, *acc3w = acc3 + wv * U;  // this wave's accumulator arrays
@@ -296,10 +322,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   unsigned hbv[NG], nbv[NG];  // head bits; "gather here" bits = the head bits + the thread's first slot
 #pragma unroll
   for (int j = 0; j < NG; j++) {
-#pragma unroll
-    for (int w = 0; w < 4; w++) uw[j][w] = a.uidw[((int64_t)g * (5 * NGt) + 5 * j + w) * NT + tid];
-    ux[j] = a.uidw[((int64_t)g * (5 * NGt) + 5 * j + 4) * NT + tid];
-    hbv[j] = a.headw[((int64_t)g * NGt + j) * NT + tid];
+    RES_GROUP_WORDS(a, NGt, j, uw[j], ux[j], hbv[j]);
     nbv[j] = hbv[j] | (j == 0 ? 1u : 0u);
   }
   // OVF: the head bits of the first overflow group (the last on-chip group's gathers look two batches ahead), the overflow
@@ -312,23 +335,60 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   const bool head0 = (hbv[0] & 1u) != 0u;
   // gather bits of batch q of group j; q may run past the group (0 .. 5)
 #define RES_NIB(j, q) ((((nbv[j]) | ((j) + 1 < NG ? nbv[(j) + 1 < NG ? (j) + 1 : (j)] << 16 : nbx0 << 16)) >> (4 * (q))) & 15u)
-  // the four users of batch bb of group j
-#define RES_UIDS(j, bb, uid)                                                     \
-  {                                                                              \
-    const unsigned lo_ = uw[j][bb];                                              \
-    uid[0] = (int)(lo_ & 0x3ffu);                                                \
-    uid[1] = (int)((lo_ >> 10) & 0x3ffu);                                        \
-    uid[2] = (int)((lo_ >> 20) & 0x3ffu);                                        \
-    uid[3] = (int)((lo_ >> 30) | (((ux[j] >> (8 * (bb))) & 0xffu) << 2));        \
+  // What a batch step reads of its group, in two forms: RES_ON, on-chip group j (static words and residual in registers / LDS),
+  // and RES_OV, the overflow group at hand (RES_OVERFLOW_GROUPS: words uwx / uxx / hb_c / nbw, residual eo). _NIB(q): the gather
+  // bits of batch q, _HEADS: the group's head bits, _UIDS: the four users of batch bb, _LD / _ST: residual k of batch bb.
+#define RES_ON_NIB(q) RES_NIB(j, q)
+#define RES_ON_HEADS hbv[j]
+#define RES_ON_UIDS(bb, uid) RES_UIDS(uw[j][bb], ux[j], bb, uid)
+#define RES_ON_LD(bb, k) (j < NGV ? ev[j < NGV ? j : 0][4 * (bb) + k] : elds[(16 * (j - NGV) + 4 * (bb) + k) * NT + tid])
+#define RES_ON_ST(bb, k, x)                \
+  if (j < NGV)                             \
+    ev[j < NGV ? j : 0][4 * (bb) + k] = x; \
+  else                                     \
+    elds[(16 * (j - NGV) + 4 * (bb) + k) * NT + tid] = x
+#define RES_OV_NIB(q) ((nbw >> (4 * (q))) & 15u)
+#define RES_OV_HEADS hb_c
+#define RES_OV_UIDS(bb, uid) RES_UIDS(uwx[bb], uxx, bb, uid)
+#define RES_OV_LD(bb, k) eo[4 * (bb) + k]
+#define RES_OV_ST(bb, k, x) eo[4 * (bb) + k] = x
+  // The overflow groups behind a sweep's on-chip ones: static words and residuals from global memory, group by group, through
+  // the sweep's STEP with the in-flight buffers gA / gB (the items' are itA / itB in both sweeps)
+#define RES_OVERFLOW_GROUPS(STEP, gA, gB)                                                   \
+  if (OVF) {                                                                                \
+    unsigned hb_c = nbx0;                                                                   \
+    for (int jx = 0; jx < ngx; jx++) {                                                      \
+      res_u4_t uwx;                                                                         \
+      unsigned uxx;                                                                         \
+      RES_USER_WORDS(uidw_x, 5 * jx, 0, uwx, uxx);                                          \
+      const unsigned hb_n = jx + 1 < ngx ? headw_x[(jx + 1) * NT] : 0u;                     \
+      const unsigned nbw = hb_c | (hb_n << 16);                                             \
+      res_d16_t eo;                                                                         \
+      _Pragma("unroll") for (int i = 0; i < 16; i++) eo[i] = eog[(16 * jx + i) * NT];       \
+      _Pragma("unroll 1") for (int bp = 0; bp < 2; bp++) {                                  \
+        STEP(RES_OV, 2 * bp, itA, itB, gA, gB);                                             \
+        STEP(RES_OV, 2 * bp + 1, itB, itA, gB, gA);                                         \
+      }                                                                                     \
+      _Pragma("unroll") for (int i = 0; i < 16; i++) eog[(16 * jx + i) * NT] = eo[i];       \
+      hb_c = hb_n;                                                                          \
+    }                                                                                       \
   }
-
-#define RES_UIDSX(bb, uid)                                                       \
-  {                                                                              \
-    const unsigned lo_ = uwx[bb];                                                \
-    uid[0] = (int)(lo_ & 0x3ffu);                                                \
-    uid[1] = (int)((lo_ >> 10) & 0x3ffu);                                        \
-    uid[2] = (int)((lo_ >> 20) & 0x3ffu);                                        \
-    uid[3] = (int)((lo_ >> 30) | (((uxx >> (8 * (bb))) & 0xffu) << 2));          \
+  // Primes a sweep's gather pipelines: the items of batches 0 and 1 (the latter -> itA, in flight), then batch 0's dv gathers
+  // (-> gA: a T at byte OFF of the entry). rcb: the run counter of the run_item stage, in bytes.
+#define RES_PRIME(T, OFF, gA)                                                                                         \
+  {                                                                                                                   \
+    int it0[B];                                                                                                       \
+    const unsigned n0 = RES_NIB(0, 0), n1 = RES_NIB(0, 1);                                                            \
+    _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                   \
+      rcb += ((n0 >> k) & 1u) << 2;                                                                                   \
+      it0[k] = *(const int *)(run_item_b + ((n0 >> k) & 1u ? rcb : rb0b));                                            \
+    }                                                                                                                 \
+    _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                   \
+      rcb += ((n1 >> k) & 1u) << 2;                                                                                   \
+      itA[k] = *(const int *)(run_item_b + ((n1 >> k) & 1u ? rcb : rb0b));                                            \
+    }                                                                                                                 \
+    _Pragma("unroll") for (int k = 0; k < B; k++)                                                                     \
+      gA[k] = *(const T *)(dv_b + (OFF) + ((n0 >> k) & 1u ? (unsigned)it0[k] << DSH : padb));                         \
   }
 
   // Sweep A's on-chip batch loops are unrolled: every residual has a static register name (no s_set_gpr_idx windows). Sweep B's
@@ -353,10 +413,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
 #pragma unroll
       for (int k = 0; k < B; k++) {
         const double x = (a.e_in ? a.e_in[((int64_t)g * Rt + 16 * j + 4 * bb + k) * NT + tid] : a.eq[row[k] < 0 ? 0 : row[k]].x) + e_shift_k;
-        if (j < NGV)
-          ev[j < NGV ? j : 0][4 * bb + k] = x;
-        else
-          elds[(16 * (j - NGV) + 4 * bb + k) * NT + tid] = x;
+        RES_ON_ST(bb, k, x);
       }
     }
   }
@@ -394,7 +451,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
             run++;
             c = a.dv[((int64_t)a.run_item[run] << (DSH - 3)) + 1];
           }
-          const int uid = k < 3 ? (int)((lo_ >> (10 * k)) & 0x3ffu) : (int)((lo_ >> 30) | (((uxp >> (8 * bb)) & 0xffu) << 2));
+          const int uid = RES_UID(lo_, uxp, bb, k);
           __hip_atomic_fetch_add(&acc3w[uid], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
       }
@@ -430,31 +487,16 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       unsigned rcb = 4u * (unsigned)(run0 - 1);  // run counter of the run_item stage, in bytes
       int itA[B];         // items of the next batch (in flight)
       d2_t ddA[B];        // dv pairs of this batch (in flight)
-      {
-        int it0[B];
-        const unsigned n0 = RES_NIB(0, 0), n1 = RES_NIB(0, 1);
-#pragma unroll
-        for (int k = 0; k < B; k++) {
-          rcb += ((n0 >> k) & 1u) << 2;
-          it0[k] = *(const int *)(run_item_b + ((n0 >> k) & 1u ? rcb : rb0b));
-        }
-#pragma unroll
-        for (int k = 0; k < B; k++) {
-          rcb += ((n1 >> k) & 1u) << 2;
-          itA[k] = *(const int *)(run_item_b + ((n1 >> k) & 1u ? rcb : rb0b));
-        }
-#pragma unroll
-        for (int k = 0; k < B; k++) ddA[k] = *(const d2_t *)(dv_b + ((n0 >> k) & 1u ? (unsigned)it0[k] << DSH : padb));
-      }
+      RES_PRIME(d2_t, 0, ddA);
       d2_t ddc = d2_t{0.0, 0.0};
       int itB[B];
       d2_t ddB[B];
       // one batch: the run_item gathers of batch b + 2 (-> ito), the dv gathers of batch b + 1 (items iti -> ddo), then batch
       // b from ddi. Two steps with the buffers swapped make one iteration of the rolled loop: no register is copied while
       // its load is in flight.
-#define RES_STEP_A(j, bb, iti, ito, ddi, ddo)                                                                              \
+#define RES_STEP_A(F, bb, iti, ito, ddi, ddo)                                                                              \
   {                                                                                                                        \
-    const unsigned n4 = RES_NIB(j, bb), n4a = RES_NIB(j, (bb) + 1), n4b = RES_NIB(j, (bb) + 2);                            \
+    const unsigned n4 = F##_NIB(bb), n4a = F##_NIB((bb) + 1), n4b = F##_NIB((bb) + 2);                                     \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
       rcb += ((n4b >> k) & 1u) << 2;                                                                                       \
       ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
@@ -462,48 +504,18 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
       ddo[k] = *(const d2_t *)(dv_b + ((n4a >> k) & 1u ? (unsigned)iti[k] << DSH : padb));                                 \
     int uid[B];                                                                                                            \
-    RES_UIDS(j, bb, uid);                                                                                                  \
+    F##_UIDS(bb, uid);                                                                                                     \
     double up[B], ex[B];                                                                                                   \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
       up[k] = utab[uid[k]][0];                                                                                             \
-      ex[k] = j < NGV ? ev[j < NGV ? j : 0][4 * (bb) + k] : elds[(16 * (j - NGV) + 4 * (bb) + k) * NT + tid];              \
+      ex[k] = F##_LD(bb, k);                                                                                               \
     }                                                                                                                      \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
       const bool need = ((n4 >> k) & 1u) != 0u;                                                                            \
       ddc[0] = need ? ddi[k][0] : ddc[0];                                                                                  \
       ddc[1] = need ? ddi[k][1] : ddc[1];                                                                                  \
       const double er = ex[k] + up[k] * ddc[0];                                                                            \
-      if (j < NGV)                                                                                                         \
-        ev[j < NGV ? j : 0][4 * (bb) + k] = er;                                                                            \
-      else                                                                                                                 \
-        elds[(16 * (j - NGV) + 4 * (bb) + k) * NT + tid] = er;                                                             \
-      const double c = ddc[1];                                                                                             \
-      __hip_atomic_fetch_add(&acc1w[uid[k]], (-er) * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                   \
-      if (!S2B) __hip_atomic_fetch_add(&acc2w[uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);             \
-    }                                                                                                                      \
-  }
-#define RES_STEP_AX(bb, iti, ito, ddi, ddo)                                                                                 \
-  {                                                                                                                        \
-    const unsigned n4 = ((nbw >> (4 * (bb))) & 15u), n4a = ((nbw >> (4 * ((bb) + 1))) & 15u), n4b = ((nbw >> (4 * ((bb) + 2))) & 15u);                            \
-    _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      rcb += ((n4b >> k) & 1u) << 2;                                                                                       \
-      ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
-    }                                                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
-      ddo[k] = *(const d2_t *)(dv_b + ((n4a >> k) & 1u ? (unsigned)iti[k] << DSH : padb));                                 \
-    int uid[B];                                                                                                            \
-    RES_UIDSX(bb, uid);                                                                                                      \
-    double up[B], ex[B];                                                                                                   \
-    _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      up[k] = utab[uid[k]][0];                                                                                             \
-      ex[k] = eo[4 * (bb) + k];              \
-    }                                                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      const bool need = ((n4 >> k) & 1u) != 0u;                                                                            \
-      ddc[0] = need ? ddi[k][0] : ddc[0];                                                                                  \
-      ddc[1] = need ? ddi[k][1] : ddc[1];                                                                                  \
-      const double er = ex[k] + up[k] * ddc[0];                                                                            \
-      eo[4 * (bb) + k] = er;                                                             \
+      F##_ST(bb, k, er);                                                                                                   \
       const double c = ddc[1];                                                                                             \
       __hip_atomic_fetch_add(&acc1w[uid[k]], (-er) * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                   \
       if (!S2B) __hip_atomic_fetch_add(&acc2w[uid[k]], c * c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);             \
@@ -514,35 +526,13 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
         RES_PRIO(j);
 #pragma unroll
         for (int bp = 0; bp < 2; bp++) {
-          RES_STEP_A(j, 2 * bp, itA, itB, ddA, ddB);
-          RES_STEP_A(j, 2 * bp + 1, itB, itA, ddB, ddA);
+          RES_STEP_A(RES_ON, 2 * bp, itA, itB, ddA, ddB);
+          RES_STEP_A(RES_ON, 2 * bp + 1, itB, itA, ddB, ddA);
         }
       }
       asm volatile(";; res sweep end");
-      if (OVF) {  // the overflow groups: static words and residuals from global memory, group by group
-        unsigned hb_c = nbx0;
-        for (int jx = 0; jx < ngx; jx++) {
-          res_u4_t uwx;
-#pragma unroll
-          for (int w = 0; w < 4; w++) uwx[w] = uidw_x[(5 * jx + w) * NT];
-          const unsigned uxx = uidw_x[(5 * jx + 4) * NT];
-          const unsigned hb_n = jx + 1 < ngx ? headw_x[(jx + 1) * NT] : 0u;
-          const unsigned nbw = hb_c | (hb_n << 16);
-          res_d16_t eo;
-#pragma unroll
-          for (int i = 0; i < 16; i++) eo[i] = eog[(16 * jx + i) * NT];
-#pragma unroll 1
-          for (int bp = 0; bp < 2; bp++) {
-            RES_STEP_AX(2 * bp, itA, itB, ddA, ddB);
-            RES_STEP_AX(2 * bp + 1, itB, itA, ddB, ddA);
-          }
-#pragma unroll
-          for (int i = 0; i < 16; i++) eog[(16 * jx + i) * NT] = eo[i];
-          hb_c = hb_n;
-        }
-      }
+      RES_OVERFLOW_GROUPS(RES_STEP_A, ddA, ddB);
 #undef RES_STEP_A
-#undef RES_STEP_AX
     }
     __syncthreads();
     RES_STAMP(1);
@@ -586,22 +576,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
         unsigned rcCb = 16u * (unsigned)(run0 - 1);  // ... and of the compute stage, in bytes
         int itA[B];
         cc_t ccA[B];
-        {
-          int it0[B];
-          const unsigned n0 = RES_NIB(0, 0), n1 = RES_NIB(0, 1);
-#pragma unroll
-          for (int k = 0; k < B; k++) {
-            rcb += ((n0 >> k) & 1u) << 2;
-            it0[k] = *(const int *)(run_item_b + ((n0 >> k) & 1u ? rcb : rb0b));
-          }
-#pragma unroll
-          for (int k = 0; k < B; k++) {
-            rcb += ((n1 >> k) & 1u) << 2;
-            itA[k] = *(const int *)(run_item_b + ((n1 >> k) & 1u ? rcb : rb0b));
-          }
-#pragma unroll
-          for (int k = 0; k < B; k++) ccA[k] = *(const cc_t *)(dv_b + 8 + ((n0 >> k) & 1u ? (unsigned)it0[k] << DSH : padb));
-        }
+        RES_PRIME(cc_t, 8, ccA);
         double ccc = 0.0, cqc = 0.0;  // the run's coefficient; S2B: the square of its next sweep's
         int itB[B];
         cc_t ccB[B];
@@ -609,10 +584,10 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
 // lane of a wave closes a run at almost every slot -- a run start every 4.9th slot, 64 lanes -- so the masked store was
 // issued anyway; its exec-mask save / restore split every step into basic blocks.)
 #define RES_PARTIAL_STORE() *(d2_t *)(part_b + (head && have_head ? rcCb : trashb)) = d2_t{s1, s2}
-#define RES_STEP_B(j, bb, iti, ito, cci, cco)                                                                              \
+#define RES_STEP_B(F, bb, iti, ito, cci, cco)                                                                              \
   {                                                                                                                        \
-    const unsigned n4 = RES_NIB(j, bb), n4a = RES_NIB(j, (bb) + 1), n4b = RES_NIB(j, (bb) + 2);                            \
-    const unsigned h4 = (hbv[j] >> (4 * (bb))) & 15u;                                                                      \
+    const unsigned n4 = F##_NIB(bb), n4a = F##_NIB((bb) + 1), n4b = F##_NIB((bb) + 2);                                     \
+    const unsigned h4 = (F##_HEADS >> (4 * (bb))) & 15u;                                                                   \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
       rcb += ((n4b >> k) & 1u) << 2;                                                                                       \
       ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
@@ -620,12 +595,12 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
       cco[k] = *(const cc_t *)(dv_b + 8 + ((n4a >> k) & 1u ? (unsigned)iti[k] << DSH : padb));                             \
     int uid[B];                                                                                                            \
-    RES_UIDS(j, bb, uid);                                                                                                  \
+    F##_UIDS(bb, uid);                                                                                                     \
     d2_t ut[B];                                                                                                            \
     double ex[B];                                                                                                          \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
       ut[k] = utab[uid[k]];                                                                                                \
-      ex[k] = j < NGV ? ev[j < NGV ? j : 0][4 * (bb) + k] : elds[(16 * (j - NGV) + 4 * (bb) + k) * NT + tid];              \
+      ex[k] = F##_LD(bb, k);                                                                                               \
     }                                                                                                                      \
     _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
       const bool need = ((n4 >> k) & 1u) != 0u;                                                                            \
@@ -636,54 +611,13 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
         __hip_atomic_fetch_add(&acc3w[uid[k]], cqc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                       \
       }                                                                                                                    \
       rcCb += need ? 16u : 0u; /* the run of this slot, in bytes */                                                        \
-      /* a run that began and ended in this thread: the slot before this head closed the run before it */                        \
+      /* a run that began and ended in this thread: the slot before this head closed the run before it */                  \
       RES_PARTIAL_STORE();                                                                                                 \
       f1 = head && !have_head ? s1 : f1;                                                                                   \
       f2 = head && !have_head ? s2 : f2;                                                                                   \
       have_head = have_head || head;                                                                                       \
       const double er = ex[k] + ccc * ut[k][1];                                                                            \
-      if (j < NGV)                                                                                                         \
-        ev[j < NGV ? j : 0][4 * (bb) + k] = er;                                                                            \
-      else                                                                                                                 \
-        elds[(16 * (j - NGV) + 4 * (bb) + k) * NT + tid] = er;                                                             \
-      s1 = (head ? 0.0 : s1) + (-er) * ut[k][0];                                                                           \
-      s2 = (head ? 0.0 : s2) + ut[k][0] * ut[k][0];                                                                        \
-    }                                                                                                                      \
-  }
-#define RES_STEP_BX(bb, iti, ito, cci, cco)                                                                                 \
-  {                                                                                                                        \
-    const unsigned n4 = ((nbw >> (4 * (bb))) & 15u), n4a = ((nbw >> (4 * ((bb) + 1))) & 15u), n4b = ((nbw >> (4 * ((bb) + 2))) & 15u);                            \
-    const unsigned h4 = (hb_c >> (4 * (bb))) & 15u;                                                                       \
-    _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      rcb += ((n4b >> k) & 1u) << 2;                                                                                       \
-      ito[k] = *(const int *)(run_item_b + ((n4b >> k) & 1u ? rcb : rb0b));                                                \
-    }                                                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < B; k++)                                                                          \
-      cco[k] = *(const cc_t *)(dv_b + 8 + ((n4a >> k) & 1u ? (unsigned)iti[k] << DSH : padb));                             \
-    int uid[B];                                                                                                            \
-    RES_UIDSX(bb, uid);                                                                                                      \
-    d2_t ut[B];                                                                                                            \
-    double ex[B];                                                                                                          \
-    _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      ut[k] = utab[uid[k]];                                                                                                \
-      ex[k] = eo[4 * (bb) + k];              \
-    }                                                                                                                      \
-    _Pragma("unroll") for (int k = 0; k < B; k++) {                                                                        \
-      const bool need = ((n4 >> k) & 1u) != 0u;                                                                            \
-      const bool head = ((h4 >> k) & 1u) != 0u;                                                                            \
-      ccc = need ? RES_CC0(cci[k]) : ccc;                                                                                  \
-      if (S2B) {                                                                                                           \
-        cqc = need ? RES_CC1(cci[k]) : cqc;                                                                                \
-        __hip_atomic_fetch_add(&acc3w[uid[k]], cqc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);                       \
-      }                                                                                                                    \
-      rcCb += need ? 16u : 0u; /* the run of this slot, in bytes */                                                        \
-      /* a run that began and ended in this thread: the slot before this head closed the run before it */                        \
-      RES_PARTIAL_STORE();                                                                                                 \
-      f1 = head && !have_head ? s1 : f1;                                                                                   \
-      f2 = head && !have_head ? s2 : f2;                                                                                   \
-      have_head = have_head || head;                                                                                       \
-      const double er = ex[k] + ccc * ut[k][1];                                                                            \
-      eo[4 * (bb) + k] = er;                                                             \
+      F##_ST(bb, k, er);                                                                                                   \
       s1 = (head ? 0.0 : s1) + (-er) * ut[k][0];                                                                           \
       s2 = (head ? 0.0 : s2) + ut[k][0] * ut[k][0];                                                                        \
     }                                                                                                                      \
@@ -693,37 +627,15 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
           RES_PRIO(j);
 #pragma unroll 1
           for (int bp = 0; bp < 2; bp++) {
-            RES_STEP_B(j, 2 * bp, itA, itB, ccA, ccB);
-            RES_STEP_B(j, 2 * bp + 1, itB, itA, ccB, ccA);
+            RES_STEP_B(RES_ON, 2 * bp, itA, itB, ccA, ccB);
+            RES_STEP_B(RES_ON, 2 * bp + 1, itB, itA, ccB, ccA);
           }
           if (a.prof && lane == 0 && (wv == 4 || wv == 7))  // (waves 4 and 7: every group)
             a.prof[((int64_t)g * a.n_sw + (f - f_first)) * 64 + 16 + (wv == 4 ? 0 : 20) + j] = __builtin_amdgcn_s_memrealtime();
         }
         asm volatile(";; res sweep end");
-        if (OVF) {
-          unsigned hb_c = nbx0;
-          for (int jx = 0; jx < ngx; jx++) {
-            res_u4_t uwx;
-#pragma unroll
-            for (int w = 0; w < 4; w++) uwx[w] = uidw_x[(5 * jx + w) * NT];
-            const unsigned uxx = uidw_x[(5 * jx + 4) * NT];
-            const unsigned hb_n = jx + 1 < ngx ? headw_x[(jx + 1) * NT] : 0u;
-            const unsigned nbw = hb_c | (hb_n << 16);
-            res_d16_t eo;
-#pragma unroll
-            for (int i = 0; i < 16; i++) eo[i] = eog[(16 * jx + i) * NT];
-#pragma unroll 1
-            for (int bp = 0; bp < 2; bp++) {
-              RES_STEP_BX(2 * bp, itA, itB, ccA, ccB);
-              RES_STEP_BX(2 * bp + 1, itB, itA, ccB, ccA);
-            }
-#pragma unroll
-            for (int i = 0; i < 16; i++) eog[(16 * jx + i) * NT] = eo[i];
-            hb_c = hb_n;
-          }
-        }
+        RES_OVERFLOW_GROUPS(RES_STEP_B, ccA, ccB);
 #undef RES_STEP_B
-#undef RES_STEP_BX
 #undef RES_CC0
 #undef RES_CC1
 #undef RES_PARTIAL_STORE
@@ -899,11 +811,11 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
           row[k] = perm_g[(16 * j + 4 * bb + k) * NT + tid];
         }
         int uid[B];
-        RES_UIDS(j, bb, uid);
+        RES_ON_UIDS(bb, uid);
 #pragma unroll
         for (int k = 0; k < B; k++) {
           const double dl = a.dv[(int64_t)it[k] << (DSH - 3)];
-          const double ex = j < NGV ? ev[j < NGV ? j : 0][4 * bb + k] : elds[(16 * (j - NGV) + 4 * bb + k) * NT + tid];
+          const double ex = RES_ON_LD(bb, k);
           const double ef = ex + utab[uid[k]][0] * dl;
           if (a.e_slots)
             a.e_slots[((int64_t)g * Rt + 16 * j + 4 * bb + k) * NT + tid] = ef;
@@ -915,9 +827,8 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     if (OVF) {
       for (int jx = 0; jx < ngx; jx++) {
         res_u4_t uwx;
-#pragma unroll
-        for (int w = 0; w < 4; w++) uwx[w] = uidw_x[(5 * jx + w) * NT];
-        const unsigned uxx = uidw_x[(5 * jx + 4) * NT];
+        unsigned uxx;
+        RES_USER_WORDS(uidw_x, 5 * jx, 0, uwx, uxx);
         const unsigned hbx = headw_x[jx * NT];
 #pragma unroll 1
         for (int bb = 0; bb < 4; bb++) {
@@ -928,7 +839,7 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
             run_last += (int)((h4 >> k) & 1u);
             it[k] = a.run_item[run_last];
           }
-          RES_UIDSX(bb, uid);
+          RES_OV_UIDS(bb, uid);
 #pragma unroll
           for (int k = 0; k < B; k++) {
             const double dl = a.dv[(int64_t)it[k] << (DSH - 3)];
@@ -941,8 +852,18 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
   }
 #undef RES_PRIO
 #undef RES_NIB
-#undef RES_UIDS
-#undef RES_UIDSX
+#undef RES_ON_NIB
+#undef RES_ON_HEADS
+#undef RES_ON_UIDS
+#undef RES_ON_LD
+#undef RES_ON_ST
+#undef RES_OV_NIB
+#undef RES_OV_HEADS
+#undef RES_OV_UIDS
+#undef RES_OV_LD
+#undef RES_OV_ST
+#undef RES_OVERFLOW_GROUPS
+#undef RES_PRIME
 #undef RES_OPAQUE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   RES_STAMP0(4);
@@ -950,31 +871,23 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
 }
 
 // ---- host side: the resident layout of a two-field table and the launch ---------------------------------------------
-// theta2 (32-byte entries, S2B): the coefficients of the sweep after the first (null: there is none); otherwise 16-byte entries
+// dv before the first sweep: entries of wd doubles (ResPlan::dv_doubles), {0, c} or {0, c, c2^2, 0} with c = theta's coefficient
+// (theta == null: the linear sweep, h = 1) and c2 = theta2's, the sweep after the first (null: there is none); the pad item: all
+// zero for ever
 __global__ void k_res_init_dv(const double *__restrict__ theta, const int32_t *__restrict__ scols, int n_items,
-                              double *__restrict__ dv, unsigned long long *__restrict__ bar, int wide = 0,
-                              const double *__restrict__ theta2 = nullptr) {
+                              double *__restrict__ dv, unsigned long long *__restrict__ bar, int wd,
+                              const double *__restrict__ theta2) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.x == 0)  // the launch's barrier words start from zero (one dispatch less than a memset of their own)
     for (int k = threadIdx.x; k < RES_BAR_WORDS; k += blockDim.x) bar[k] = 0ull;
-  if (wide) {
-    if (i < n_items) {
-      const double c2 = theta2 ? theta2[scols[i]] : 0.0;
-      dv[4 * i] = 0.0;
-      dv[4 * i + 1] = theta ? theta[scols[i]] : 1.0;
-      dv[4 * i + 2] = c2 * c2;
-      dv[4 * i + 3] = 0.0;
-    } else if (i == n_items) {
-      for (int k = 0; k < 4; k++) dv[4 * i + k] = 0.0;
-    }
-    return;
-  }
-  if (i < n_items) {
-    dv[2 * i] = 0.0;
-    dv[2 * i + 1] = theta ? theta[scols[i]] : 1.0;  // (theta == null: the linear sweep, h = 1)
-  } else if (i == n_items) {  // the pad item: (0, 0) for ever
-    dv[2 * i] = 0.0;
-    dv[2 * i + 1] = 0.0;
+  if (i > n_items) return;
+  const bool pad = i == n_items;
+  dv[wd * i] = 0.0;
+  dv[wd * i + 1] = pad ? 0.0 : theta ? theta[scols[i]] : 1.0;
+  if (wd == 4) {
+    const double c2 = !pad && theta2 ? theta2[scols[i]] : 0.0;
+    dv[wd * i + 2] = c2 * c2;
+    dv[wd * i + 3] = 0.0;
   }
 }
 
@@ -1036,15 +949,12 @@ __global__ __launch_bounds__(NT) void k_res_score(ResScoreArgs a) {
     if (ju >= 0 && pr < KP) v = ((const double2 *)(a.Vt + (int64_t)ju * a.KS))[pr];
     ((double2 *)(uV + (size_t)ul * US))[pr] = v;
   }
-  // static per-thread words (as in k_mf_resident)
+  // static per-thread words
   res_u4_t uw[NG];
   unsigned ux[NG], hbv[NG];
 #pragma unroll
   for (int j = 0; j < NG; j++) {
-#pragma unroll
-    for (int w = 0; w < 4; w++) uw[j][w] = a.uidw[((int64_t)g * (5 * NG) + 5 * j + w) * NT + tid];
-    ux[j] = a.uidw[((int64_t)g * (5 * NG) + 5 * j + 4) * NT + tid];
-    hbv[j] = a.headw[((int64_t)g * NG + j) * NT + tid];
+    RES_GROUP_WORDS(a, NG, j, uw[j], ux[j], hbv[j]);
   }
   int run = a.first_run[g * NT + tid];
   const int64_t fill = a.wg_fill[g];
@@ -1088,12 +998,8 @@ __global__ __launch_bounds__(NT) void k_res_score(ResScoreArgs a) {
         }
         run = r;
       }
-      const unsigned lo_ = uw[j][bb];
       int uid[4];
-      uid[0] = (int)(lo_ & 0x3ffu);
-      uid[1] = (int)((lo_ >> 10) & 0x3ffu);
-      uid[2] = (int)((lo_ >> 20) & 0x3ffu);
-      uid[3] = (int)((lo_ >> 30) | (((ux[j] >> (8 * bb)) & 0xffu) << 2));
+      RES_UIDS(uw[j][bb], ux[j], bb, uid);
       const unsigned h4 = (hbv[j] >> (4 * bb)) & 15u;
       // the residual's other operand is requested first: it does not depend on anything computed here
       double yv[4], eb[4];
@@ -1159,6 +1065,11 @@ __global__ __launch_bounds__(NT) void k_res_score(ResScoreArgs a) {
   }
 }
 
+#undef RES_UID
+#undef RES_UIDS
+#undef RES_USER_WORDS
+#undef RES_GROUP_WORDS
+
 // y in slot order (pads: 0), once per plan
 __global__ void k_res_permute_y(const double *__restrict__ y, const int32_t *__restrict__ perm, int64_t n_slots,
                                 double *__restrict__ y_slots) {
@@ -1191,6 +1102,51 @@ static inline void res_parallel_for(int n, F f) {
   for (auto &t : pool) t.join();
 }
 
+// The compiled forms of k_mf_resident and k_res_score: the ONE place that says which exist. The planners' variants, the S2B
+// eligibility (ResPlan::plan_lds), the occupancy query and the launches look here. `raised`: the 160 KB dynamic-LDS attribute.
+struct ResForm {
+  int rv, rl;  // slots per thread in registers / in LDS
+  bool xch, ovf, s2b;
+  const void *fn;
+  DeviceOnce raised;
+};
+static inline auto &res_forms() {
+#define MFM_RES_FORM(NGV, NGL, ...) {16 * NGV, 16 * NGL, __VA_ARGS__, (const void *)k_mf_resident<512, NGV, NGL, __VA_ARGS__>, {}}
+  static ResForm forms[] = {  // (plain forms: smallest first, ResPlan::variants)
+      MFM_RES_FORM(1, 0, false, false, false), MFM_RES_FORM(2, 0, false, false, false), MFM_RES_FORM(4, 1, false, false, false),
+      MFM_RES_FORM(1, 0, true, false, false),  MFM_RES_FORM(2, 0, true, false, false),  MFM_RES_FORM(4, 1, true, false, false),
+      MFM_RES_FORM(4, 1, false, true, false),  MFM_RES_FORM(4, 1, false, false, true),  MFM_RES_FORM(4, 1, false, true, true)};
+#undef MFM_RES_FORM
+  return forms;
+}
+static inline ResForm *res_form(int rv, int rl, bool xch, bool ovf, bool s2b) {  // null: not compiled
+  for (ResForm &f : res_forms())
+    if (f.rv == rv && f.rl == rl && f.xch == xch && f.ovf == ovf && f.s2b == s2b) return &f;
+  return nullptr;
+}
+struct ResScoreForm {
+  int ng;  // groups of 16 slots per thread
+  const void *fn;
+  DeviceOnce raised;
+};
+static inline auto &res_score_forms() {
+#define MFM_RES_SCORE_FORM(NG) {NG, (const void *)k_res_score<512, NG, 16>, {}}
+  static ResScoreForm forms[] = {MFM_RES_SCORE_FORM(1), MFM_RES_SCORE_FORM(2), MFM_RES_SCORE_FORM(5), MFM_RES_SCORE_FORM(6),
+                                 MFM_RES_SCORE_FORM(7), MFM_RES_SCORE_FORM(8), MFM_RES_SCORE_FORM(9), MFM_RES_SCORE_FORM(10)};
+#undef MFM_RES_SCORE_FORM
+  return forms;
+}
+// launches fn(a) with 512 threads per workgroup, the form's LDS attribute raised on this device first
+template <class Form, class Args>
+static inline void res_launch(Form &f, int G, size_t lds, hipStream_t s, Args &a) {
+  if (f.raised.need()) {
+    MFM_HIP_CHECK(hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    f.raised.mark();
+  }
+  void *args[] = {&a};
+  MFM_HIP_CHECK(hipLaunchKernel(f.fn, dim3(G), dim3(512), args, lds, s));
+}
+
 struct ResPlan {
   bool ready = false;
   int G = 0, NT = 512, RV = 0, RL = 0, umax = 0, item_bits = 0, n_items = 0;
@@ -1200,13 +1156,14 @@ struct ResPlan {
   int64_t n_rows = 0, n_runs = 0;  // (workgroup, item) pairs
   size_t lds_bytes = 0;
   int s2b = 0;  // 1: the kernel form that takes the user level's sum of h^2 in the sweep before (k_mf_resident<.., S2B>; 32-byte dv entries)
+  int dv_doubles() const { return 1 << (res_dv_shift(s2b != 0) - 3); }  // doubles of a dv entry
   // LDS of the plan's kernel and the form it runs: S2B's third accumulator array where it fits and the variant has the form
-  // (<512, 4, 1> and its overflow form, not row-sharded), else the two-array form
+  // (res_forms: <512, 4, 1> and its overflow form, not row-sharded), else the two-array form
   bool plan_lds() {
     const size_t nw = (size_t)(NT / WAVE), lim = 160 * 1024 - 512;
     lds_bytes = (size_t)RL * NT * 8 + 2 * nw * umax * 8 + (size_t)umax * 16 + nw * 16 + nw * 4 + 64;
     if (lds_bytes > lim) return false;
-    s2b = allow_overflow && RV == 64 && RL == 16 && lds_bytes + nw * umax * 8 <= lim ? 1 : 0;
+    s2b = res_form(RV, RL, !allow_overflow, RX > 0, true) && lds_bytes + nw * umax * 8 <= lim ? 1 : 0;
     if (s2b) lds_bytes += nw * umax * 8;
     return true;
   }
@@ -1271,13 +1228,14 @@ struct ResPlan {
     while (((int64_t)1 << b) < n) b++;
     return b;
   }
-  // (NT, RV, RL) variants compiled below, by rows per workgroup
+  // (RV, RL) variants compiled, by rows per workgroup: the plain forms of res_forms
   struct Variant {
     int rv, rl;
   };
-  static const Variant *variants(int &n) {
-    static const Variant v[] = {{16, 0}, {32, 0}, {64, 16}};
-    n = 3;
+  static std::vector<Variant> variants() {
+    std::vector<Variant> v;
+    for (const ResForm &f : res_forms())
+      if (!f.xch && !f.ovf && !f.s2b) v.push_back({f.rv, f.rl});
     return v;
   }
 
@@ -1285,8 +1243,8 @@ struct ResPlan {
   // the smallest variant that fits the device. Sets G, RV, RL and the user ordinal boundaries ucut[0 .. G].
   bool choose_layout(int64_t N, const std::vector<int64_t> &ustart, int64_t max_user, int n_cu, std::vector<int64_t> &ucut) {
     const int64_t n_users = (int64_t)ustart.size() - 1;
-    int nv = 0;
-    const Variant *vs = variants(nv);
+    const std::vector<Variant> vs = variants();
+    const int nv = (int)vs.size();
     bool found = false;
     for (int vi = 0; vi < nv && !found; vi++) {
       const int64_t cap = (int64_t)NT * (vs[vi].rv + vs[vi].rl) - 1;  // (at least one pad slot closes the last run)
@@ -1676,7 +1634,7 @@ struct ResPlan {
     }
     partials.alloc((size_t)2 * ((size_t)zero_run + 1));
     MFM_HIP_CHECK(hipMemset(partials.p, 0, (size_t)16 * ((size_t)zero_run + 1)));
-    dv.alloc((size_t)(s2b ? 4 : 2) * (n_items + 1));
+    dv.alloc((size_t)dv_doubles() * (n_items + 1));
     bar.alloc(RES_BAR_WORDS);
     ready = true;
     why.clear();
@@ -1689,19 +1647,20 @@ struct ResPlan {
   }
 };
 
+// the form of the plan's launches (xch: row-sharded, the ranks' sums meet inside the launch). The row-sharded kernel has neither
+// overflow slots nor the S2B form: such a plan is refused. (RX counts where the variant has an overflow form at all: the planner
+// sets it with no other, choose_layout.)
+static inline ResForm &res_kernel(const ResPlan &rp, bool xch) {
+  const bool ovf = rp.RX > 0 && res_form(rp.RV, rp.RL, false, true, false);
+  ResForm *f = res_form(rp.RV, rp.RL, xch, ovf, rp.s2b != 0);
+  if (!f) throw Error(MFM_ERR_RUNTIME, "internal: no resident kernel variant for this plan");
+  return *f;
+}
+
 // resident workgroups of the plan's kernel variant per CU (0: it does not fit): the grid barrier needs all G at once
 static inline hipError_t res_occupancy(const ResPlan &rp, int *per_cu) {
   *per_cu = 0;
-  const void *fn = nullptr;
-  if (rp.RV == 16 && rp.RL == 0)
-    fn = (const void *)k_mf_resident<512, 1, 0>;
-  else if (rp.RV == 32 && rp.RL == 0)
-    fn = (const void *)k_mf_resident<512, 2, 0>;
-  else if (rp.RV == 64 && rp.RL == 16)
-    fn = rp.s2b ? (rp.RX ? (const void *)k_mf_resident<512, 4, 1, false, true, true> : (const void *)k_mf_resident<512, 4, 1, false, false, true>)
-                : (rp.RX ? (const void *)k_mf_resident<512, 4, 1, false, true> : (const void *)k_mf_resident<512, 4, 1>);
-  else
-    return hipErrorInvalidValue;
+  const void *fn = res_kernel(rp, false).fn;  // (asked of the single-GPU form, row-sharded or not)
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return e;
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, fn, 512, rp.lds_bytes);
@@ -1793,58 +1752,10 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
     const int f_second = f_begin + (w ? 0 : 1);  // the factor of the launch's second sweep (S2B: its square goes into dv too)
     hipLaunchKernelGGL(k_res_init_dv, dim3((rp.n_items + 256) / 256), dim3(256), 0, s,
                        w ? (const double *)nullptr : V + (int64_t)f_begin * D, rp.scols.p, rp.n_items,
-                       rp.dv.p, rp.bar.p, rp.s2b, rp.s2b && f_second < f_end ? V + (int64_t)f_second * D : (const double *)nullptr);
+                       rp.dv.p, rp.bar.p, rp.dv_doubles(), rp.s2b && f_second < f_end ? V + (int64_t)f_second * D : (const double *)nullptr);
   }
   TimedLaunch t(tm, s, kernel_class, bytes);
-#define MFM_RES_LAUNCH(RV_, RL_)                                                                                              \
-  do {                                                                                                                        \
-    static DeviceOnce raised;                                                                                                 \
-    if (raised.need()) {                                                                                                      \
-      MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_mf_resident<512, RV_ / 16, RL_ / 16>,                                  \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                             \
-      raised.mark();                                                                                                          \
-    }                                                                                                                         \
-    if (xch) {                                                                                                                \
-      static DeviceOnce raised_x;                                                                                             \
-      if (raised_x.need()) {                                                                                                  \
-        MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_mf_resident<512, RV_ / 16, RL_ / 16, true>,                          \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                           \
-        raised_x.mark();                                                                                                      \
-      }                                                                                                                       \
-      hipLaunchKernelGGL((k_mf_resident<512, RV_ / 16, RL_ / 16, true>), dim3(rp.G), dim3(512), rp.lds_bytes, s, a);            \
-    } else {                                                                                                                  \
-      hipLaunchKernelGGL((k_mf_resident<512, RV_ / 16, RL_ / 16>), dim3(rp.G), dim3(512), rp.lds_bytes, s, a);                  \
-    }                                                                                                                         \
-  } while (0)
-  if (rp.RV == 16 && rp.RL == 0)
-    MFM_RES_LAUNCH(16, 0);
-  else if (rp.RV == 32 && rp.RL == 0)
-    MFM_RES_LAUNCH(32, 0);
-  else if (rp.RV == 64 && rp.RL == 16 && rp.s2b) {
-    if (xch) throw Error(MFM_ERR_RUNTIME, "internal: no row-sharded resident kernel of the S2B form");
-    static DeviceOnce raised_s;
-    if (raised_s.need()) {
-      MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_mf_resident<512, 4, 1, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_mf_resident<512, 4, 1, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      raised_s.mark();
-    }
-    if (rp.RX > 0)
-      hipLaunchKernelGGL((k_mf_resident<512, 4, 1, false, true, true>), dim3(rp.G), dim3(512), rp.lds_bytes, s, a);
-    else
-      hipLaunchKernelGGL((k_mf_resident<512, 4, 1, false, false, true>), dim3(rp.G), dim3(512), rp.lds_bytes, s, a);
-  } else if (rp.RV == 64 && rp.RL == 16 && rp.RX > 0) {
-    if (xch) throw Error(MFM_ERR_RUNTIME, "internal: no row-sharded resident kernel with overflow slots");
-    static DeviceOnce raised_o;
-    if (raised_o.need()) {
-      MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_mf_resident<512, 4, 1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      raised_o.mark();
-    }
-    hipLaunchKernelGGL((k_mf_resident<512, 4, 1, false, true>), dim3(rp.G), dim3(512), rp.lds_bytes, s, a);
-  } else if (rp.RV == 64 && rp.RL == 16)
-    MFM_RES_LAUNCH(64, 16);
-  else
-    throw Error(MFM_ERR_RUNTIME, "internal: no resident kernel variant for this plan");
-#undef MFM_RES_LAUNCH
+  res_launch(res_kernel(rp, xch), rp.G, rp.lds_bytes, s, a);
   MFM_HIP_CHECK(hipGetLastError());
   if (xch) rp.xepoch += (unsigned long long)a.n_sw;  // (every rank runs the same launches: the epochs agree)
   if (prof) {
@@ -1987,36 +1898,11 @@ static inline void run_res_score(hipStream_t s, Timing &tm, ResPlan &rp, int ker
   // algorithmic bytes: y and e in slot order (8 + 8 B / row), the static slot words (1.4 B), one Vt row per run and per user
   TimedLaunch t(tm, s, kernel_class, 17.4 * rp.n_rows + 8.0 * KS * (double)rp.n_runs);
   (void)nnz;
-#define MFM_RES_SCORE(NG_)                                                                                              \
-  do {                                                                                                                  \
-    static DeviceOnce raised;                                                                                           \
-    if (raised.need()) {                                                                                                \
-      MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_res_score<512, NG_, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                        160 * 1024));                                                                   \
-      raised.mark();                                                                                                    \
-    }                                                                                                                   \
-    hipLaunchKernelGGL((k_res_score<512, NG_, 16>), dim3(rp.G), dim3(512), lds, s, a);                                   \
-  } while (0)
-  const int NG = rp.R() / 16;
-  if (NG == 1)
-    MFM_RES_SCORE(1);
-  else if (NG == 2)
-    MFM_RES_SCORE(2);
-  else if (NG == 5)
-    MFM_RES_SCORE(5);
-  else if (NG == 6)
-    MFM_RES_SCORE(6);
-  else if (NG == 7)
-    MFM_RES_SCORE(7);
-  else if (NG == 8)
-    MFM_RES_SCORE(8);
-  else if (NG == 9)
-    MFM_RES_SCORE(9);
-  else if (NG == 10)
-    MFM_RES_SCORE(10);
-  else
-    throw Error(MFM_ERR_RUNTIME, "internal: no slot-order scorer for this plan");
-#undef MFM_RES_SCORE
+  ResScoreForm *form = nullptr;
+  for (ResScoreForm &f : res_score_forms())
+    if (f.ng == rp.R() / 16) form = &f;
+  if (!form) throw Error(MFM_ERR_RUNTIME, "internal: no slot-order scorer for this plan");
+  res_launch(*form, rp.G, lds, s, a);
   MFM_HIP_CHECK(hipGetLastError());
   if (prof) {
     MFM_HIP_CHECK(hipStreamSynchronize(s));

@@ -515,7 +515,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
   rpn.h_diag.clear();
   rpn.partials.alloc((size_t)2 * ((size_t)zero_run + 1));
   MFM_HIP_CHECK(hipMemsetAsync(rpn.partials.p, 0, (size_t)16 * ((size_t)zero_run + 1), s));
-  rpn.dv.alloc((size_t)(rpn.s2b ? 4 : 2) * (n_items + 1));
+  rpn.dv.alloc((size_t)rpn.dv_doubles() * (n_items + 1));
   rpn.bar.alloc(RES_BAR_WORDS);
   MFM_HIP_CHECK(hipStreamSynchronize(s));
   MFM_HIP_CHECK(hipGetLastError());

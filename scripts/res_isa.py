@@ -9,7 +9,13 @@ code of sweeps A and B. The sweeps are found in one of two forms:
     slots that runs for 16);
   - failing those, as the innermost loops of at least 250 instructions (the rolled batch loops: two batches of 4 slots per
     iteration); a loop with ds_add_f64 is sweep A's, one without is sweep B's.
-Usage: python scripts/res_isa.py [--asm FILE] [--keep FILE] [--all]"""
+Usage: python scripts/res_isa.py [--asm FILE] [--keep FILE] [--all]
+
+--same A.s B.s compares two listings of the same translation unit (say, before and after a change that claims to leave a
+form's code alone): per k_mf_resident / k_res_score symbol whether the instruction streams and the .amdhsa_* resource lines are
+equal; every other kernel must be in both, and a changed instruction count of one is reported. A plain comparison of the text
+(comments, the __hip_cuid_* symbol and the function ordinal in local labels aside); exit status 1 on a difference or a missing
+kernel, with the differing symbol and its first differing line."""
 import argparse
 import os
 import re
@@ -64,6 +70,57 @@ def kernel_meta(lines):
             if ".end_amdhsa_kernel" in ln:
                 cur = None
     return meta
+
+
+def kernels(path):
+    """kernel symbol -> (its instructions and labels, comments stripped; its .amdhsa_* lines)"""
+    text, meta, cur, cur_k = {}, {}, None, None
+    with open(path) as f:
+        for ln in f:
+            m = re.match(r"^(\w+):", ln)
+            if cur is None and m:  # (a function's label, or a data symbol's: those have no .amdhsa_kernel block and are dropped)
+                cur = m.group(1)
+                text[cur] = []
+            elif ln.startswith(".Lfunc_end"):
+                cur = None
+            elif cur is not None:
+                s = re.sub(r"\.L(BB|JTI)\d+_", r".L\1_", ln.split(";")[0].strip())  # (local labels carry the function's ordinal)
+                if s and "__hip_cuid_" not in s:
+                    text[cur].append(s)
+            m = re.match(r"^\s*\.amdhsa_kernel\s+(\S+)", ln)
+            if m:
+                cur_k = m.group(1)
+                meta[cur_k] = []
+            elif ".end_amdhsa_kernel" in ln:
+                cur_k = None
+            elif cur_k is not None:
+                meta[cur_k].append(ln.strip())
+    return {k: (text[k], meta[k]) for k in meta if k in text}
+
+
+def same(path_a, path_b):
+    a, b = kernels(path_a), kernels(path_b)
+    bad = 0
+    for name in sorted(set(a) | set(b)):
+        if name not in a or name not in b:
+            print("MISSING in %s: %s" % (path_a if name not in a else path_b, name))
+            bad += 1
+            continue
+        n_a, n_b = (sum(1 for x in k[name][0] if not x.endswith(":") and not x.startswith(".")) for k in (a, b))
+        if not re.search(r"k_mf_resident|k_res_score", name):
+            if n_a != n_b:  # (reported, not counted: the exit status speaks of the sweep and the scorer)
+                print("other kernel, %d -> %d instructions: %s" % (n_a, n_b, name))
+            continue
+        for what, x, y in (("instruction stream", a[name][0], b[name][0]), ("resources", a[name][1], b[name][1])):
+            if x != y:
+                i = next((i for i, (p, q) in enumerate(zip(x, y)) if p != q), min(len(x), len(y)))
+                print("DIFFERENT %s: %s\n  line %d: %r\n      vs: %r" % (what, name, i, x[i] if i < len(x) else None, y[i] if i < len(y) else None))
+                bad += 1
+                break
+        else:
+            print("equal (%d instructions, %d resource lines): %s" % (n_a, len(a[name][1]), name))
+    print("%d kernels compared, %d differ" % (len(set(a) | set(b)), bad))
+    return 1 if bad else 0
 
 
 def is_insn(ln):
@@ -148,7 +205,10 @@ def main():
     ap.add_argument("--asm", help="read this listing instead of compiling")
     ap.add_argument("--keep", help="write the compiled listing here")
     ap.add_argument("--all", action="store_true", help="every instantiation (default: <512,4,1,...> in all its forms: OVF, XCH, S2B)")
+    ap.add_argument("--same", nargs=2, metavar=("A.s", "B.s"), help="compare two listings kernel by kernel")
     args = ap.parse_args()
+    if args.same:
+        return same(*args.same)
     path = args.asm
     if not path:
         path = args.keep or os.path.join(tempfile.mkdtemp(prefix="res_isa_"), "mfm_hip.s")
