@@ -398,6 +398,20 @@ int mfm_design_summary_store(mfm_design *d, mfm_store *st, int32_t first, int32_
 int mfm_design_summary(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                        int32_t mode, int32_t n_q, const double *probs, const double *precisions, const double *z,
                        int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q);
+/* Ordered probit: the same summaries of a function of the score and of THAT sample's cutpoints, cutpoints[count * n_cut] row-major
+ * (count, n_cut), with cdf_j = (1 + erf((cut_j - score) / sqrt 2)) / 2, cdf_-1 = 0, cdf_n_cut = 1 and C = n_cut + 1 classes:
+ *   expected = 0: v_s[c] = p_c = cdf_c - cdf_c-1 per class; out_mean / out_std row-major (N, C), out_q row-major (n_q, N, C);
+ *                 out_mean is bit for bit what mfm_design_predict* returns in mode 2
+ *   expected = 1: v_s = sum_c c p_c, added in ascending class order; out_mean[N], out_std[N], out_q row-major (n_q, N)
+ * There is no noise form (y is discrete: its predictive distribution is the out_mean of expected = 0) and no limit on C. n_cut < 1,
+ * a cutpoint that is not finite and cutpoints that do not ascend within a sample are MFM_ERR_INVALID; n_q, count, tile_rows,
+ * chunk_samples and the upload rule of the host flavour are those of mfm_design_summary*.                                   */
+int mfm_design_summary_oprobit_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t expected, int32_t n_cut,
+                                     const double *cutpoints, int32_t n_q, const double *probs, int64_t tile_rows,
+                                     int32_t chunk_samples, double *out_mean, double *out_std, double *out_q);
+int mfm_design_summary_oprobit(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                               int32_t expected, int32_t n_cut, const double *cutpoints, int32_t n_q, const double *probs,
+                               int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q);
 
 /* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
  * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), each optionally with relation blocks

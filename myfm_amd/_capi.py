@@ -41,7 +41,7 @@ SYMBOLS = [
     "mfm_pairs_create", "mfm_pairs_destroy", "mfm_pairs_last_error", "mfm_pairs_set_exclude", "mfm_pairs_set_scratch_bound",
     "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
     "mfm_pairs_set_cutpoints",
-    "mfm_design_summary_store", "mfm_design_summary",
+    "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
 ]
 
 _lib = None
@@ -165,6 +165,8 @@ def lib():
     L.mfm_design_predict_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P]
     L.mfm_design_summary_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, P, i64, i32, P, P, P]
     L.mfm_design_summary.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, P, i64, i32, P, P, P]
+    L.mfm_design_summary_oprobit_store.argtypes = [vp, vp, i32, i32, i32, i32, P, i32, P, i64, i32, P, P, P]
+    L.mfm_design_summary_oprobit.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, i32, P, i64, i32, P, P, P]
     L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
@@ -589,6 +591,29 @@ class Design:
             _raise(rc, lib().mfm_design_last_error(self.h))
         return mean, std, q
 
+    def summary_oprobit(self, samples, cutpoints, expected=False, quantiles=(), tile_rows=0, chunk_samples=0):
+        """samples as predict, cutpoints[S][n_cut]. Summaries of the class probabilities, (mean[N, C], std[N, C],
+        quantiles[Q, N, C]) with C = n_cut + 1, or with `expected` of the expected class index, (mean[N], std[N],
+        quantiles[Q, N]) (mfm_design_summary_oprobit)."""
+        K, S, w0s, ws, Vs = _pack_samples(samples)
+        cp, n_cut, probs, mean, std, q = _summary_oprobit_args(self.N, cutpoints, expected, quantiles)
+        rc = lib().mfm_design_summary_oprobit(self.h, K, S, _p(w0s), _p(ws), _p(Vs), int(bool(expected)), n_cut, _p(cp), len(probs),
+                                              _p(probs), int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
+        if rc:
+            _raise(rc, lib().mfm_design_last_error(self.h))
+        return mean, std, q
+
+
+def _summary_oprobit_args(N, cutpoints, expected, quantiles):
+    """cutpoints [S][n_cut] (n_cut = 0 for none), n_cut, the probabilities and the three output arrays of an ordered-probit summary"""
+    cp = _f64(cutpoints)
+    if cp.ndim != 2:
+        raise ValueError("cutpoints must be a 2-D array, one row of n_cut cutpoints per sample")
+    n_cut = cp.shape[1]
+    probs = _f64(quantiles).reshape(-1)
+    tail = () if expected else (n_cut + 1,)
+    return cp, n_cut, probs, np.empty((N,) + tail), np.empty((N,) + tail), np.empty((len(probs), N) + tail)
+
 
 def _summary_args(N, quantiles, precisions):
     """probabilities, precisions, Phi^-1 of the probabilities (noise only) and the three output arrays of a summary call"""
@@ -660,6 +685,16 @@ class Store:
         probs, prec, z, mean, std, q = _summary_args(design.N, quantiles, precisions)
         rc = lib().mfm_design_summary_store(design.h, self.h, first, count, mode, len(probs), _p(probs), _p(prec), _p(z),
                                             int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
+        if rc:
+            _raise(rc, lib().mfm_design_last_error(design.h))
+        return mean, std, q
+
+    def summary_oprobit(self, design, cutpoints, expected=False, quantiles=(), first=0, count=None, tile_rows=0, chunk_samples=0):
+        """Design.summary_oprobit over the resident samples [first, first + count) (mfm_design_summary_oprobit_store)"""
+        count = len(self) - first if count is None else count
+        cp, n_cut, probs, mean, std, q = _summary_oprobit_args(design.N, cutpoints, expected, quantiles)
+        rc = lib().mfm_design_summary_oprobit_store(design.h, self.h, first, count, int(bool(expected)), n_cut, _p(cp), len(probs),
+                                                    _p(probs), int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
         if rc:
             _raise(rc, lib().mfm_design_last_error(design.h))
         return mean, std, q

@@ -873,6 +873,57 @@ struct Predictor {
     if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
     return py::make_tuple(mean, sd, q);
   }
+  // Ordered probit (not in the reference): the same summaries of the class probabilities p_c(score_s; cutpoints_s) -- (mean[N, C],
+  // std[N, C], quantiles[Q, N, C]) -- or, with `expected`, of the expected class index sum_c c p_c -- (mean[N], std[N],
+  // quantiles[Q, N]). Checked here like predict_dist, the cutpoints gathered like predict_parallel_oprobit.
+  py::tuple predict_dist_oprobit(const py::object &Xo, const py::object &relso, const py::object &quantileso, int64_t cutpoint_idx,
+                                 bool expected, int64_t tile_rows, int chunk_samples) const {
+    Csr X = csr_from_py(Xo);
+    Relations rels = relations_from_py(relso);
+    check_input(X, rels);
+    if (type != TaskType::ORDERED) throw std::invalid_argument("predict_dist_oprobit must be called for oprobit model.");
+    auto qa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(quantileso);
+    if (!qa || qa.ndim() != 1) throw std::invalid_argument("quantiles must be a 1-D sequence of probabilities");
+    const int n_q = (int)qa.shape(0);
+    if (n_q > 32) throw std::invalid_argument("at most 32 quantiles per call");
+    vector<double> probs(qa.data(), qa.data() + n_q);
+    for (double p : probs)
+      if (!(p >= 0.0 && p <= 1.0)) throw std::invalid_argument("quantiles must lie in [0, 1]");
+    if (tile_rows < 0 || chunk_samples < 0) throw std::invalid_argument("tile_rows and chunk_samples must be non-negative");
+    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
+    if (n_q > 0 && samples.size() > 4096)
+      throw std::invalid_argument("quantiles are computed over at most 4096 kept samples, this predictor holds " + std::to_string(samples.size()));
+    const size_t cutpoint_index = (size_t)cutpoint_idx;  // (a negative one is out of range as well)
+    if (cutpoint_idx < 0 || cutpoint_index >= samples[0].cutpoints.size() || samples[0].cutpoints[cutpoint_index].empty())
+      throw std::invalid_argument("cutpoint_index " + std::to_string(cutpoint_idx) + " out of range: the model has " +
+                                  std::to_string(samples[0].cutpoints.size()) + " cutpoint group(s)");
+    const int n_cpt = (int)samples[0].cutpoints[cutpoint_index].size();
+    vector<double> cuts;
+    for (auto &s : samples) {
+      if (cutpoint_index >= s.cutpoints.size() || (int)s.cutpoints[cutpoint_index].size() != n_cpt)
+        throw std::invalid_argument("inconsistent cutpoint sizes among samples.");
+      const auto &cp = s.cutpoints[cutpoint_index];
+      cuts.insert(cuts.end(), cp.begin(), cp.end());
+    }
+    const py::ssize_t N = (py::ssize_t)X.rows, C = n_cpt + 1;
+    const std::vector<py::ssize_t> shape = expected ? std::vector<py::ssize_t>{N} : std::vector<py::ssize_t>{N, C};
+    std::vector<py::ssize_t> qshape = shape;
+    qshape.insert(qshape.begin(), (py::ssize_t)n_q);
+    py::array_t<double> mean(shape), sd(shape), q(qshape);
+    DeviceDesign dd(X, rels);
+    const int S = (int)samples.size();
+    const int code = with_samples(
+        [&](mfm_store *st, int first) {
+          return mfm_design_summary_oprobit_store(dd.d, st, first, S, expected ? 1 : 0, n_cpt, cuts.data(), n_q, probs.data(), tile_rows,
+                                                  chunk_samples, mean.mutable_data(), sd.mutable_data(), q.mutable_data());
+        },
+        [&](const double *w0s, const double *ws, const double *Vs) {
+          return mfm_design_summary_oprobit(dd.d, (int)rank, S, w0s, ws, Vs, expected ? 1 : 0, n_cpt, cuts.data(), n_q, probs.data(),
+                                            tile_rows, chunk_samples, mean.mutable_data(), sd.mutable_data(), q.mutable_data());
+        });
+    if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
+    return py::make_tuple(mean, sd, q);
+  }
   // predictor.hpp:78-124
   py::array_t<double> predict_parallel_oprobit(const py::object &Xo, const py::object &relso, size_t n_workers,
                                                size_t cutpoint_index) const {
@@ -2660,6 +2711,8 @@ PYBIND11_MODULE(_myfm, m) {
                              })  // the samples are read in place from the device store (else: uploaded from the host)
       .def("predict_dist", &Predictor::predict_dist, py::arg("X"), py::arg("rels"), py::arg("quantiles"), py::arg("precisions") = py::none(),
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+      .def("predict_dist_oprobit", &Predictor::predict_dist_oprobit, py::arg("X"), py::arg("rels"), py::arg("quantiles"),
+           py::arg("cutpoint_index") = 0, py::arg("expected") = false, py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def(py::pickle(
           [](const Predictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {

@@ -1,6 +1,8 @@
 // mfm_dist.hpp -- posterior predictive summaries (not in the reference): per test row the mean, the population
 // standard deviation and empirical quantiles of the S kept samples' values (score, or Phi(score)), and with per-sample noise
-// precisions the moments and quantiles of the mixture mean_s N(score_s, 1 / alpha_s). Included by mfm_hip.hip after
+// precisions the moments and quantiles of the mixture mean_s N(score_s, 1 / alpha_s). Ordered probit: the values are the class
+// probabilities p_c(score_s; cutpoints_s), one summary per (row, class), or the expected class index sum_c c p_c; both are taken
+// from the stored scores where stage 2 reads them (the load transform of k_row_summary). Included by mfm_hip.hip after
 // mfm_predict.hpp.
 //
 // Rows are processed in tiles of T rows. Stage 1 writes the values of a tile, all samples, into a sample-major scratch
@@ -38,6 +40,35 @@ struct RowSummaryArgs {
   double g[DIST_MAX_Q];     // ... and the weight of the upper one; noise: Phi^-1(p_q)
   double p[DIST_MAX_Q];
 };
+
+// The load transforms of stage 2: what a stored score becomes on its way out of the scratch.
+constexpr int XF_NONE = 0;      // the stored value itself
+constexpr int XF_CLASS = 1;     // p_c(score; the sample's cutpoints), class c = c0 + blockIdx.y; outputs strided by C
+constexpr int XF_EXPECTED = 2;  // sum_c c p_c
+struct RowTransformArgs {
+  const double *cut;  // [S][n_cut], on the device
+  int n_cut, C;       // C: values per row in the outputs (XF_CLASS: n_cut + 1, XF_EXPECTED: 1)
+  int c0;             // XF_CLASS: the class of blockIdx.y = 0 (a launch covers at most 65535 classes)
+  int cut_lds;        // the cutpoints a workgroup needs are staged in LDS behind the rows (LDS form)
+};
+
+// p_c = cdf_c - cdf_{c-1} with cdf_{-1} = 0 and cdf_{n_cut} = 1, the expression of k_score_store MODE 2 and k_accumulate_oprobit;
+// lo / hi: cut[c - 1] / cut[c] (unused where has_lo / has_hi is false)
+__device__ __forceinline__ double oprobit_cdf(double cut, double score) { return (1.0 + erf((cut - score) * 0.70710678118654752440)) / 2.0; }
+__device__ __forceinline__ double oprobit_class_prob(double score, bool has_lo, double lo, bool has_hi, double hi) {
+  const double prev = has_lo ? oprobit_cdf(lo, score) : 0.0;
+  return has_hi ? oprobit_cdf(hi, score) - prev : 1.0 - prev;
+}
+// sum_{c = 1 .. n_cut} c p_c in ascending class order
+__device__ __forceinline__ double oprobit_expected(double score, const double *cut, int n_cut) {
+  double prev = 0.0, e = 0.0;
+  for (int c = 0; c < n_cut; c++) {
+    const double cdf = oprobit_cdf(cut[c], score);
+    if (c > 0) e += (double)c * (cdf - prev);
+    prev = cdf;
+  }
+  return e + (double)n_cut * (1.0 - prev);
+}
 
 // mean = (v_0 + v_1 + ...) * (1 / S), the sum and the factor of the predictors; the variance two-pass about the mean of
 // the values shifted by v_0 (exactly 0 when all values are equal, and no cancellation against a large common offset)
@@ -108,31 +139,100 @@ __device__ __forceinline__ double dist_mixture_quantile(const double *v, const d
 // interpolates quantile q of row r as numpy's "linear" rule does, or (noise) thread (q, r) solves the mixture quantile with
 // the row's scores and sqrt(alpha_s) read from LDS (the latter at one address for all lanes: a broadcast read).
 // Direct form (LDS_ROWS = false, no quantiles, any S): a thread per row reads the scratch itself.
-template <bool LDS_ROWS>
-__global__ __launch_bounds__(WG) void k_row_summary(RowSummaryArgs a) {
+// XF (ordered probit, never with noise): the value of (sample s, row t) is a function of scratch[s][t] and cut[s][.], computed
+// where the score leaves the scratch -- on the way into the sort buffer (the moments are taken from that buffer, there is no
+// second one), or at the read of the direct form. XF_CLASS: blockIdx.y is the class; every class block reads the tile's scores
+// again (from L2) and writes its outputs with stride C. The two cutpoints of every sample that a class needs (XF_EXPECTED: all
+// n_cut) are staged in LDS behind the rows, where sqrt(alpha) goes with noise, if the launcher found room for them; else they
+// are read from global memory (one address per sample for the whole workgroup).
+// The identity takes RowSummaryArgs alone and the transforms RowTransformArgs after it (the pack X is empty or that one type), so
+// that the identity's arguments, instructions and kernel descriptor are those of the kernel without transforms.
+__device__ __forceinline__ RowTransformArgs row_transform_args() { return RowTransformArgs{}; }
+__device__ __forceinline__ RowTransformArgs row_transform_args(const RowTransformArgs &x) { return x; }
+template <bool LDS_ROWS, int XF = XF_NONE, class... X>
+__global__ __launch_bounds__(WG) void k_row_summary(RowSummaryArgs a, X... xs) {
+  static_assert(sizeof...(X) == (XF == XF_NONE ? 0 : 1), "a transform takes RowTransformArgs, the identity nothing");
+  const RowTransformArgs x = row_transform_args(xs...);
   extern __shared__ double dist_lds[];
   const int S = a.S;
+  const int c = XF == XF_CLASS ? x.c0 + (int)blockIdx.y : 0;
+  const bool has_lo = c > 0, has_hi = c < x.n_cut;
+  // output i of the identity is output i * C + c of the class form
+  const auto at = [&](size_t i) { return XF == XF_CLASS ? i * (size_t)x.C + (size_t)c : i; };
   if (!LDS_ROWS) {
     const int64_t t = (int64_t)blockIdx.x * WG + threadIdx.x;
     if (t >= a.Tn) return;
     const double *__restrict__ col = a.scratch + t;
     const int64_t Tn = a.Tn;
     double mean, var;
-    dist_moments([&](int s) { return col[(size_t)s * Tn]; }, S, a.inv_S, mean, var);
-    a.mean[t] = mean;
-    a.sd[t] = sqrt(var + a.noise_var);
+    if constexpr (XF == XF_NONE) {
+      dist_moments([&](int s) { return col[(size_t)s * Tn]; }, S, a.inv_S, mean, var);
+      a.mean[t] = mean;
+      a.sd[t] = sqrt(var + a.noise_var);
+    } else {
+      const auto value = [&](int s) {
+        const double *cs = x.cut + (size_t)s * x.n_cut;
+        const double score = col[(size_t)s * Tn];
+        if constexpr (XF == XF_CLASS)
+          return oprobit_class_prob(score, has_lo, has_lo ? cs[c - 1] : 0.0, has_hi, has_hi ? cs[c] : 0.0);
+        else
+          return oprobit_expected(score, cs, x.n_cut);
+      };
+      dist_moments(value, S, a.inv_S, mean, var);
+      a.mean[at((size_t)t)] = mean;
+      a.sd[at((size_t)t)] = sqrt(var);
+    }
     return;
   }
   const int R = a.R, st = a.stride, P = a.P;
   const int64_t r0 = (int64_t)blockIdx.x * R;
   const int nr = (int)(a.Tn - r0 < R ? a.Tn - r0 : R);
   const int tid = threadIdx.x;
-  for (int i = tid; i < S * R; i += WG) {
-    const int s = i / R, r = i - s * R;
-    dist_lds[r * st + s] = r < nr ? a.scratch[(size_t)s * a.Tn + r0 + r] : 0.0;
+  if constexpr (XF == XF_NONE) {
+    for (int i = tid; i < S * R; i += WG) {
+      const int s = i / R, r = i - s * R;
+      dist_lds[r * st + s] = r < nr ? a.scratch[(size_t)s * a.Tn + r0 + r] : 0.0;
+    }
+  } else {
+    // the cutpoints of a value: XF_CLASS cut[s * cw + co - 1], cut[s * cw + co]; XF_EXPECTED cut[s * cw + 0 .. n_cut). (Called
+    // once with the LDS pointer and once with the global one, so that neither becomes a flat access.)
+    const auto fill = [&](const double *cut, int cw, int co) {
+      for (int i = tid; i < S * R; i += WG) {
+        const int s = i / R, r = i - s * R;
+        double v = 0.0;
+        if (r < nr) {
+          const double score = a.scratch[(size_t)s * a.Tn + r0 + r];
+          const double *cs = cut + (size_t)s * cw;
+          if constexpr (XF == XF_CLASS)
+            v = oprobit_class_prob(score, has_lo, has_lo ? cs[co - 1] : 0.0, has_hi, has_hi ? cs[co] : 0.0);
+          else
+            v = oprobit_expected(score, cs, x.n_cut);
+        }
+        dist_lds[r * st + s] = v;
+      }
+    };
+    if (x.cut_lds) {
+      double *staged = dist_lds + R * st;
+      if constexpr (XF == XF_CLASS) {
+        for (int s = tid; s < S; s += WG) {
+          const double *cs = x.cut + (size_t)s * x.n_cut;
+          staged[2 * s] = has_lo ? cs[c - 1] : 0.0;
+          staged[2 * s + 1] = has_hi ? cs[c] : 0.0;
+        }
+      } else {
+        for (int i = tid; i < S * x.n_cut; i += WG) staged[i] = x.cut[i];
+      }
+      __syncthreads();
+      if constexpr (XF == XF_CLASS)
+        fill(staged, 2, 1);
+      else
+        fill(staged, x.n_cut, 0);
+    } else {
+      fill(x.cut, x.n_cut, c);
+    }
   }
   double *sqa = dist_lds + R * st;  // (noise) sqrt(alpha_s) behind the rows: every lane of the solve reads the same address
-  if (!a.noise)
+  if (XF != XF_NONE || !a.noise)
     for (int i = tid; i < (P - S) * R; i += WG) {
       const int s = i / R, r = i - s * R;
       dist_lds[r * st + S + s] = __builtin_inf();
@@ -144,10 +244,10 @@ __global__ __launch_bounds__(WG) void k_row_summary(RowSummaryArgs a) {
     const double *row = dist_lds + tid * st;
     double mean, var;
     dist_moments([&](int s) { return row[s]; }, S, a.inv_S, mean, var);
-    a.mean[r0 + tid] = mean;
-    a.sd[r0 + tid] = sqrt(var + a.noise_var);
+    a.mean[at((size_t)(r0 + tid))] = mean;
+    a.sd[at((size_t)(r0 + tid))] = sqrt(XF == XF_NONE ? var + a.noise_var : var);
   }
-  if (a.noise) {
+  if (XF == XF_NONE && a.noise) {
     for (int w = tid; w < a.n_q * R; w += WG) {
       const int q = w / R, r = w - q * R;
       if (r < nr) a.q[(size_t)q * a.ldq + r0 + r] = dist_mixture_quantile(dist_lds + r * st, sqa, S, a.inv_S, a.g[q], a.p[q]);
@@ -159,13 +259,13 @@ __global__ __launch_bounds__(WG) void k_row_summary(RowSummaryArgs a) {
   for (int k = 2; k <= P; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
       for (int idx = tid; idx < R * half; idx += WG) {
-        const int r = idx / half, c = idx - r * half;
-        const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1));
+        const int r = idx / half, c2 = idx - r * half;
+        const int i = ((c2 & ~(j - 1)) << 1) | (c2 & (j - 1));
         double *row = dist_lds + r * st;
-        const double x = row[i], y = row[i | j];
-        if ((x > y) == ((i & k) == 0)) {
+        const double x0 = row[i], y = row[i | j];
+        if ((x0 > y) == ((i & k) == 0)) {
           row[i] = y;
-          row[i | j] = x;
+          row[i | j] = x0;
         }
       }
       __syncthreads();
@@ -175,15 +275,26 @@ __global__ __launch_bounds__(WG) void k_row_summary(RowSummaryArgs a) {
     if (r >= nr) continue;
     const double *row = dist_lds + r * st;
     const int lo = a.lo[q], hi = lo + 1 < S ? lo + 1 : lo;
-    const double x = row[lo], y = row[hi], g = a.g[q];
-    const double d = y - x;
-    a.q[(size_t)q * a.ldq + r0 + r] = g >= 0.5 ? y - d * (1.0 - g) : x + d * g;  // (numpy's _lerp)
+    const double x0 = row[lo], y = row[hi], g = a.g[q];
+    const double d = y - x0;
+    a.q[at((size_t)q * a.ldq + r0 + r)] = g >= 0.5 ? y - d * (1.0 - g) : x0 + d * g;  // (numpy's _lerp)
   }
 }
-
-static void launch_row_summary(hipStream_t s, RowSummaryArgs &a) {
+// x: the load transform `xf` (XF_CLASS / XF_EXPECTED) and its cutpoints, or null (the values are the stored ones)
+static void launch_row_summary(hipStream_t s, RowSummaryArgs &a, int xf = XF_NONE, RowTransformArgs *x = nullptr) {
+  // XF_CLASS: the classes are grid.y, at most 65535 of them per launch
+  const auto launch_classes = [&](auto kernel, unsigned blocks, size_t lds) {
+    const int n_class = xf == XF_CLASS ? x->C : 1;
+    for (x->c0 = 0; x->c0 < n_class; x->c0 += 65535)
+      hipLaunchKernelGGL(kernel, dim3(blocks, (unsigned)std::min(65535, n_class - x->c0)), dim3(WG), lds, s, a, *x);
+  };
   if (a.n_q == 0) {
-    hipLaunchKernelGGL(k_row_summary<false>, dim3((unsigned)cdiv(a.Tn, WG)), dim3(WG), 0, s, a);
+    if (xf == XF_CLASS)
+      launch_classes(k_row_summary<false, XF_CLASS, RowTransformArgs>, (unsigned)cdiv(a.Tn, WG), 0);
+    else if (xf == XF_EXPECTED)
+      launch_classes(k_row_summary<false, XF_EXPECTED, RowTransformArgs>, (unsigned)cdiv(a.Tn, WG), 0);
+    else
+      hipLaunchKernelGGL(k_row_summary<false>, dim3((unsigned)cdiv(a.Tn, WG)), dim3(WG), 0, s, a);
     return;
   }
   int P = 1;
@@ -195,17 +306,40 @@ static void launch_row_summary(hipStream_t s, RowSummaryArgs &a) {
   const int aux = a.noise ? a.S : 0;
   const int fit = (DIST_LDS_BYTES / (int)sizeof(double) - aux) / a.stride;
   a.R = (int)std::min<int64_t>(std::max(1, std::min(DIST_MAX_ROWS, fit)), a.Tn);
+  if (xf != XF_NONE) {
+    // The rows are sized as without a transform. The cutpoints that a workgroup needs -- two per sample for a class, all n_cut
+    // for the expected index -- are staged behind the rows where the DIST_LDS_BYTES still hold them, and read from global memory
+    // where not (S = 4096: the one row is all the LDS there is).
+    const int64_t want = (int64_t)a.S * (xf == XF_CLASS ? 2 : x->n_cut);
+    x->cut_lds = (int64_t)a.R * a.stride + want <= DIST_LDS_BYTES / (int)sizeof(double);
+    const size_t lds = ((size_t)a.R * a.stride + (x->cut_lds ? (size_t)want : 0)) * sizeof(double);  // <= 48 KB, or one row: 32 776 B
+    if (xf == XF_CLASS)
+      launch_classes(k_row_summary<true, XF_CLASS, RowTransformArgs>, (unsigned)cdiv(a.Tn, a.R), lds);
+    else
+      launch_classes(k_row_summary<true, XF_EXPECTED, RowTransformArgs>, (unsigned)cdiv(a.Tn, a.R), lds);
+    return;
+  }
   const size_t lds = ((size_t)a.R * a.stride + aux) * sizeof(double);
   static DeviceOnce raised;
   if (lds > 64 * 1024 && raised.need()) {
-    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_row_summary<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DIST_LDS_MAX_BYTES));
+    void (*const identity)(RowSummaryArgs) = k_row_summary<true>;
+    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)identity, hipFuncAttributeMaxDynamicSharedMemorySize, DIST_LDS_MAX_BYTES));
     raised.mark();
   }
   hipLaunchKernelGGL(k_row_summary<true>, dim3((unsigned)cdiv(a.Tn, a.R)), dim3(WG), lds, s, a);
 }
 
+// what an ordered-probit summary adds to the call: which value, and the samples' cutpoints [count][n_cut] on the host
+struct OprobitValues {
+  int32_t expected, n_cut;
+  const double *cutpoints;
+};
+
+// op: summarise class probabilities / the expected class index of the scores (mode 0) instead of the scores; the outputs then
+// hold C = n_cut + 1 (expected: 1) values per row, row-major (N, C) and (n_q, N, C)
 static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int32_t n_q, const double *probs, const double *precisions,
-                           const double *z, int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
+                           const double *z, int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q,
+                           const OprobitValues *op = nullptr) {
   const int count = v.count();
   if (v.device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
   if (v.D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
@@ -224,6 +358,19 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
   if (precisions)
     for (int k = 0; k < count; k++)
       if (!(precisions[k] > 0.0) || !std::isfinite(precisions[k])) throw Error(MFM_ERR_INVALID, "noise precisions must be positive and finite");
+  if (op) {
+    if (op->expected < 0 || op->expected > 1) throw Error(MFM_ERR_INVALID, "bad value selector (0: class probabilities, 1: expected class index)");
+    if (op->n_cut < 1) throw Error(MFM_ERR_INVALID, "an ordered-probit summary needs at least one cutpoint per sample");
+    if (!op->cutpoints) throw Error(MFM_ERR_INVALID, "an ordered-probit summary needs the samples' cutpoints");
+    for (int k = 0; k < count; k++)
+      for (int j = 0; j < op->n_cut; j++) {
+        const double *cs = op->cutpoints + (size_t)k * op->n_cut;
+        if (!std::isfinite(cs[j]) || (j > 0 && !(cs[j - 1] <= cs[j])))
+          throw Error(MFM_ERR_INVALID, "cutpoints must be finite and ascending within every sample");
+      }
+  }
+  const int xf = !op ? XF_NONE : op->expected ? XF_EXPECTED : XF_CLASS;
+  const int64_t C = xf == XF_CLASS ? (int64_t)op->n_cut + 1 : 1;
   hipStream_t s = d->stream;
   const int rank = v.K;
   const int64_t N = d->N, D = d->D;
@@ -231,7 +378,8 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
   design_use_rank(d, rank, s);
   const int64_t T = std::min<int64_t>(N, tile_rows > 0 ? tile_rows : std::max<int64_t>(1, (int64_t)(DIST_SCRATCH_BYTES / sizeof(double)) / count));
   if (d->dist_scratch.n < (size_t)(T * count)) d->dist_scratch.alloc((size_t)(T * count));
-  const size_t out_n = (size_t)N * (2 + n_q);
+  const size_t NC = (size_t)N * (size_t)C;
+  const size_t out_n = NC * (2 + n_q);
   if (d->dist_out.n < out_n) d->dist_out.alloc(out_n);
   RowSummaryArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -252,6 +400,15 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
     if (d->dist_aux.n < (size_t)count) d->dist_aux.alloc((size_t)count);
     MFM_HIP_CHECK(hipMemcpy(d->dist_aux.p, sq.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
     a.sqa = d->dist_aux.p;
+  }
+  RowTransformArgs x{};
+  if (op) {
+    const size_t n = (size_t)count * op->n_cut;
+    if (d->cut.n < n) d->cut.alloc(n);
+    MFM_HIP_CHECK(hipMemcpyAsync(d->cut.p, op->cutpoints, n * sizeof(double), hipMemcpyHostToDevice, s));
+    x.cut = d->cut.p;
+    x.n_cut = op->n_cut;
+    x.C = (int)C;
   }
   for (int q = 0; q < n_q; q++) {
     a.p[q] = probs[q];
@@ -289,15 +446,15 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
     }
     MFM_HIP_CHECK(hipGetLastError());
     a.Tn = Tn;
-    a.mean = d->dist_out.p + r0;
-    a.sd = d->dist_out.p + N + r0;
-    a.q = d->dist_out.p + 2 * N + r0;
-    launch_row_summary(s, a);
+    a.mean = d->dist_out.p + (size_t)r0 * C;
+    a.sd = d->dist_out.p + NC + (size_t)r0 * C;
+    a.q = d->dist_out.p + 2 * NC + (size_t)r0 * C;
+    launch_row_summary(s, a, xf, &x);
     MFM_HIP_CHECK(hipGetLastError());
   }
-  MFM_HIP_CHECK(hipMemcpyAsync(out_mean, d->dist_out.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipMemcpyAsync(out_std, d->dist_out.p + N, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (n_q) MFM_HIP_CHECK(hipMemcpyAsync(out_q, d->dist_out.p + 2 * N, (size_t)N * n_q * sizeof(double), hipMemcpyDeviceToHost, s));
+  MFM_HIP_CHECK(hipMemcpyAsync(out_mean, d->dist_out.p, NC * sizeof(double), hipMemcpyDeviceToHost, s));
+  MFM_HIP_CHECK(hipMemcpyAsync(out_std, d->dist_out.p + NC, NC * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (n_q) MFM_HIP_CHECK(hipMemcpyAsync(out_q, d->dist_out.p + 2 * NC, NC * n_q * sizeof(double), hipMemcpyDeviceToHost, s));
   MFM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -323,6 +480,28 @@ int mfm_design_summary(mfm_design *d, int32_t rank, int32_t n_samples, const dou
   store_check_fraction(d->D, rank, n_samples);
   design_summary(d, samples_of_host(d->device, d->D, rank, n_samples, w0s, ws, Vs), mode, n_q, probs, precisions, z, tile_rows,
                  chunk_samples, out_mean, out_std, out_q);
+  MFM_CATCH(d)
+}
+
+// ordered probit: the class probabilities (expected = 0; outputs (N, C), (N, C), (n_q, N, C) with C = n_cut + 1) or the expected
+// class index (expected = 1; (N), (N), (n_q, N)) of every sample's score under that sample's cutpoints [count][n_cut]
+int mfm_design_summary_oprobit_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t expected, int32_t n_cut,
+                                     const double *cutpoints, int32_t n_q, const double *probs, int64_t tile_rows,
+                                     int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
+  MFM_TRY(d)
+  const OprobitValues op{expected, n_cut, cutpoints};
+  design_summary(d, samples_of_store(st, first, count), 0, n_q, probs, nullptr, nullptr, tile_rows, chunk_samples, out_mean, out_std, out_q, &op);
+  MFM_CATCH(d)
+}
+
+int mfm_design_summary_oprobit(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                               int32_t expected, int32_t n_cut, const double *cutpoints, int32_t n_q, const double *probs,
+                               int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q) {
+  MFM_TRY(d)
+  store_check_fraction(d->D, rank, n_samples);
+  const OprobitValues op{expected, n_cut, cutpoints};
+  design_summary(d, samples_of_host(d->device, d->D, rank, n_samples, w0s, ws, Vs), 0, n_q, probs, nullptr, nullptr, tile_rows,
+                 chunk_samples, out_mean, out_std, out_q, &op);
   MFM_CATCH(d)
 }
 

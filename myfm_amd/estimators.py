@@ -315,10 +315,27 @@ PREDICT_DIST_MAX_QUANTILES = 32
 PREDICT_DIST_MAX_SAMPLES = 4096  # with a non-empty `quantiles`: a row's values are sorted in the device's local memory
 
 
+def _checked_quantiles(quantiles):
+    probs = np.asarray(quantiles, dtype=REAL)
+    if probs.ndim != 1:
+        raise ValueError("quantiles must be a 1-D sequence of probabilities")
+    if probs.shape[0] > PREDICT_DIST_MAX_QUANTILES:
+        raise ValueError("at most %d quantiles per call" % PREDICT_DIST_MAX_QUANTILES)
+    if not np.all((probs >= 0.0) & (probs <= 1.0)):  # (NaN fails both comparisons)
+        raise ValueError("quantiles must lie in [0, 1]")
+    return probs
+
+
+def _check_sample_limit(probs, n_samples):
+    if probs.shape[0] > 0 and n_samples > PREDICT_DIST_MAX_SAMPLES:
+        raise ValueError("quantiles are computed over at most %d kept samples, this model keeps %d (mean and std have no "
+                         "limit: pass quantiles=())" % (PREDICT_DIST_MAX_SAMPLES, n_samples))
+
+
 class _PredictiveDistMixin:
     """Posterior predictive summaries of a fitted Gibbs regressor / classifier. MyFMOrderedProbit and the
-    variational estimators have no predict_dist. Row-sharded operation is not covered: the model is replicated, so each rank
-    may call predict_dist on its own rows."""
+    variational estimators have no predict_dist (for ordered probit see predict_proba_dist / predict_expected_dist). Row-sharded
+    operation is not covered: the model is replicated, so each rank may call predict_dist on its own rows."""
 
     def predict_dist(self, X, X_rel=[], quantiles=(0.05, 0.5, 0.95), noise=False):
         """PredictiveSummary(mean, std, quantiles) per test row over the S kept samples, computed on the device in one pass
@@ -337,13 +354,7 @@ class _PredictiveDistMixin:
         predictor = self._fetch_predictor()
         n = check_data_consistency(X, X_rel)
         X = _as_csr(X, n)
-        probs = np.asarray(quantiles, dtype=REAL)
-        if probs.ndim != 1:
-            raise ValueError("quantiles must be a 1-D sequence of probabilities")
-        if probs.shape[0] > PREDICT_DIST_MAX_QUANTILES:
-            raise ValueError("at most %d quantiles per call" % PREDICT_DIST_MAX_QUANTILES)
-        if not np.all((probs >= 0.0) & (probs <= 1.0)):  # (NaN fails both comparisons)
-            raise ValueError("quantiles must lie in [0, 1]")
+        probs = _checked_quantiles(quantiles)
         n_samples = len(predictor.samples)
         precisions = None
         if noise:
@@ -355,9 +366,7 @@ class _PredictiveDistMixin:
             if hypers is None or len(hypers) < n_samples:
                 raise RuntimeError("noise=True needs history_ with the noise precision of every kept sample")
             precisions = np.asarray([h.alpha for h in hypers[len(hypers) - n_samples:]], dtype=REAL)
-        if probs.shape[0] > 0 and n_samples > PREDICT_DIST_MAX_SAMPLES:
-            raise ValueError("quantiles are computed over at most %d kept samples, this model keeps %d (mean and std have no "
-                             "limit: pass quantiles=())" % (PREDICT_DIST_MAX_SAMPLES, n_samples))
+        _check_sample_limit(probs, n_samples)
         return PredictiveSummary(*predictor.predict_dist(X, list(X_rel), probs, precisions))
 
 
@@ -548,7 +557,8 @@ def _device_row_order(X):
 
 class MyFMOrderedProbit(_PairScoringMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
-    class index (see _PairScoringMixin)."""
+    class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
+    quantiles of every class probability and of the expected class index over the kept samples."""
 
     _task_type = TaskType.ORDERED
 
@@ -595,6 +605,40 @@ class MyFMOrderedProbit(_PairScoringMixin, MyFMGibbsBase):
 
     def predict(self, X, X_rel=[]):
         return self.predict_proba(X, X_rel=X_rel).argmax(axis=1)
+
+    def _predict_dist_oprobit(self, X, X_rel, quantiles, cutpoint_index, expected):
+        predictor = self._fetch_predictor()
+        n = check_data_consistency(X, X_rel)
+        X = _as_csr(X, n)
+        probs = _checked_quantiles(quantiles)
+        samples = predictor.samples
+        _check_sample_limit(probs, len(samples))
+        if isinstance(cutpoint_index, bool) or not isinstance(cutpoint_index, (int, np.integer)):
+            raise ValueError("cutpoint_index must be an integer")
+        sizes = set(len(fm.cutpoints[cutpoint_index]) if 0 <= cutpoint_index < len(fm.cutpoints) else 0 for fm in samples)
+        if 0 in sizes:
+            raise ValueError("cutpoint_index %d out of range: a kept sample has no such cutpoint group" % cutpoint_index)
+        if len(sizes) > 1:
+            raise ValueError("the kept samples hold different numbers of cutpoints in group %d" % cutpoint_index)
+        return PredictiveSummary(*predictor.predict_dist_oprobit(X, list(X_rel), probs, int(cutpoint_index), expected))
+
+    def predict_proba_dist(self, X, X_rel=[], quantiles=(0.05, 0.5, 0.95), cutpoint_index=0):
+        """PredictiveSummary(mean, std, quantiles) of every class probability over the S kept samples, computed on the device:
+        the per-sample value is p_c(score_s; cutpoints_s), the probability of class c under sample s's score and sample s's
+        own cutpoints, C = n_cut + 1 classes.
+
+        mean (N, C): what predict_proba returns, bit for bit -- and, y being discrete, the predictive distribution of y itself
+        (there is no `noise` argument). std (N, C): population standard deviation (ddof = 0). quantiles (Q, N, C):
+        np.quantile(p, quantiles, axis=0) under the default "linear" rule, from exactly sorted values; `quantiles` may be empty
+        (at most 32 entries in [0, 1]; S <= 4096 unless it is empty). The number of classes has no limit.
+
+        The arguments are checked on the host before the device is touched."""
+        return self._predict_dist_oprobit(X, X_rel, quantiles, cutpoint_index, False)
+
+    def predict_expected_dist(self, X, X_rel=[], quantiles=(0.05, 0.5, 0.95), cutpoint_index=0):
+        """As predict_proba_dist, of the expected class index sum_c c p_c (added in ascending class order), the value that
+        predict_topk ranks by: mean (N,), std (N,), quantiles (Q, N)."""
+        return self._predict_dist_oprobit(X, X_rel, quantiles, cutpoint_index, True)
 
     @property
     def cutpoint_samples(self):
