@@ -456,6 +456,37 @@ int mfm_pairs_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double
 int mfm_pairs_topk(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                    int32_t mode, int32_t k, int64_t *idx, double *score);
 
+/* ---- folding new one-hot features into the kept samples (csrc/mfm_foldin.hip) ----------------------------------
+ * U new entities (users or items that were not in the training table), each a new one-hot column with value 1 in its own
+ * observations. X (n, D) holds the CONTEXT of the n observations in the model's feature space (not the new column), y their
+ * targets; the observations are grouped by entity: entity u owns rows [entity_offsets[u], entity_offsets[u + 1]), an entity may
+ * own none. Under kept sample s the new column's parameters theta = (w_u, V_u1 .. V_uK) have the Gaussian posterior
+ *   Lambda = diag(lambda_s) + alpha_s sum_i z_i z_i^T,  b = diag(lambda_s) mu_s + alpha_s sum_i z_i r_i,  theta_mean = Lambda^-1 b
+ * with z_i = (1, q_s(x_i)), q_sk(x) = sum_j V_s[k, j] x_j and r_i = y_i - score_s(x_i); fit_linear = 0 drops the w_u component (the
+ * written w_new is 0). alpha[S], mu[S][K + 1], lambda[S][K + 1]: per sample the noise precision and the prior mean / precision of
+ * (w, V_1 .. V_K) -- component 0 is read only with fit_linear. draw = 0 writes the posterior mean; draw != 0 writes
+ * theta_mean + L^-T eps (Lambda = L L^T), eps_j the Box-Muller value of counter word j >> 1 (r cos for even j, r sin for odd j) of
+ * the per-row Philox stream keyed (seed, the fold-in draw tag, row = s U + u), j counting the components of theta. An entity without
+ * observations gets the prior: mu bit for bit, or mu_j + eps_j / sqrt(lambda_j). Outputs: w_new[S][U], V_new[S][U][K].
+ * The arguments are checked before the device is looked for (MFM_ERR_INVALID: a malformed CSR or offsets, a non-finite y or value;
+ * per call: a rank above the limit returned by the max_rank entry point (64), a precision that is not positive and finite). A posterior
+ * precision matrix that is not positive definite is MFM_ERR_INVALID from the call, never a NaN in the result.
+ * A result does not depend on U, on the chunking or on the scratch bound (bytes of results per chunk of entities and samples; 256 MB
+ * by default). *_store reads samples [first, first + count) of a device store in place; the other takes host samples laid out as
+ * for the host-sample prediction entry point. The handle's last error: NULL for the last failed create of this thread.        */
+typedef struct mfm_foldin mfm_foldin;
+int mfm_foldin_create(int device, int64_t D, int64_t n, const int64_t *indptr, const int32_t *indices, const double *data,
+                      const double *y, int64_t U, const int64_t *entity_offsets /*[U + 1]*/, int32_t fit_linear, mfm_foldin **out);
+void mfm_foldin_destroy(mfm_foldin *p);
+const char *mfm_foldin_last_error(const mfm_foldin *p);
+int mfm_foldin_set_scratch_bound(mfm_foldin *p, int64_t bytes);
+int mfm_foldin_max_rank(void);
+int mfm_foldin_solve_store(mfm_foldin *p, mfm_store *st, int32_t first, int32_t count, const double *alpha, const double *mu,
+                           const double *lambda, int32_t draw, uint64_t seed, double *w_new, double *V_new);
+int mfm_foldin_solve(mfm_foldin *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                     const double *alpha, const double *mu, const double *lambda, int32_t draw, uint64_t seed, double *w_new,
+                     double *V_new);
+
 /* FM::predict_score of the LIVE sample (the FM* handed to the per-iteration callback,
  * FMTrainer.hpp:78; utils/callbacks/libfm.py:85): scores design `d` with the (w0, w, V) currently
  * resident in training context `ctx` -- no download / upload of the model state. Same device only.  */

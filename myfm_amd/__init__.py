@@ -21,6 +21,7 @@ _hip_runtime = _preload()
 
 from ._myfm import RelationBlock  # noqa: E402
 from .estimators import (  # noqa: E402
+    FOLD_IN_MAX_RANK,
     MyFMClassifier,
     MyFMGibbsClassifier,
     MyFMGibbsRegressor,
@@ -39,4 +40,5 @@ __all__ = [
     "MyFMGibbsClassifier",
     "VariationalFMRegressor",
     "VariationalFMClassifier",
+    "FOLD_IN_MAX_RANK",
 ]

@@ -41,6 +41,8 @@ SYMBOLS = [
     "mfm_pairs_create", "mfm_pairs_destroy", "mfm_pairs_last_error", "mfm_pairs_set_exclude", "mfm_pairs_set_scratch_bound",
     "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
     "mfm_pairs_set_cutpoints",
+    "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
+    "mfm_foldin_solve_store", "mfm_foldin_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
 ]
 
@@ -180,6 +182,15 @@ def lib():
     L.mfm_pairs_topk_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P]
     L.mfm_pairs_scores.argtypes = [vp, i32, i32, P, P, P, i32, P]
     L.mfm_pairs_topk.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P]
+    L.mfm_foldin_create.argtypes = [C.c_int, i64, i64, P, P, P, P, i64, P, i32, C.POINTER(vp)]
+    L.mfm_foldin_destroy.argtypes = [vp]
+    L.mfm_foldin_destroy.restype = None
+    L.mfm_foldin_last_error.restype = C.c_char_p
+    L.mfm_foldin_last_error.argtypes = [vp]
+    L.mfm_foldin_set_scratch_bound.argtypes = [vp, i64]
+    L.mfm_foldin_max_rank.argtypes = []
+    L.mfm_foldin_solve_store.argtypes = [vp, vp, i32, i32, P, P, P, i32, u64, P, P]
+    L.mfm_foldin_solve.argtypes = [vp, i32, i32, P, P, P, P, P, P, i32, u64, P, P]
     L.mfm_test_erfcx.argtypes = [C.c_int, P, i64, P]
     L.mfm_test_truncated_normal.argtypes = [C.c_int, i32, dbl, dbl, u64, u64, i64, P]
     _lib = L
@@ -799,3 +810,70 @@ class Pairs:
         idx, val = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk))
         self._ck(lib().mfm_pairs_topk_store(self.h, store.h, first, count, mode, int(k), _p(idx), _p(val)))
         return idx, val
+
+
+def group_by_entity(X, y, entity, n_entities):
+    """the observations grouped by entity with a stable sort: (X rows in that order, y, offsets int64 (U + 1,))"""
+    entity = np.ascontiguousarray(entity, dtype=np.int64)
+    order = np.argsort(entity, kind="stable")
+    offsets = np.zeros(int(n_entities) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(entity, minlength=int(n_entities)), out=offsets[1:])
+    return sps.csr_matrix(X, dtype=np.float64)[order], _f64(y)[order], offsets
+
+
+class FoldIn:
+    """The observations of U new one-hot entities resident on the GPU (mfm_foldin_*): X (n, D) the context rows in the model's
+    feature space, y (n,), entity (n,) in [0, U) in any order. `scratch_bound`: bytes of results per chunk of entities and
+    samples (default 256 MB; a small value makes a small problem cross the chunking)."""
+
+    def __init__(self, X, y, entity, n_entities, fit_linear=True, scratch_bound=None, device=0):
+        L = lib()
+        h = C.c_void_p()
+        Xg, yg, off = group_by_entity(X, y, entity, n_entities)
+        Xg, ip, ix, dv = csr_parts(Xg)
+        rc = L.mfm_foldin_create(device, Xg.shape[1], Xg.shape[0], _p(ip), _p(ix), _p(dv), _p(yg), int(n_entities), _p(off),
+                                 int(bool(fit_linear)), C.byref(h))
+        if rc:
+            _raise(rc, L.mfm_foldin_last_error(None))
+        self.h, self.U, self.D = h, int(n_entities), Xg.shape[1]
+        if scratch_bound is not None:
+            self._ck(L.mfm_foldin_set_scratch_bound(h, int(scratch_bound)))
+
+    def _ck(self, rc):
+        if rc:
+            _raise(rc, lib().mfm_foldin_last_error(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().mfm_foldin_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _hypers(S, K, alpha, mu, lam):
+        alpha, mu, lam = _f64(alpha).reshape(-1), _f64(mu), _f64(lam)
+        if alpha.shape != (S,) or mu.shape != (S, K + 1) or lam.shape != (S, K + 1):
+            raise ValueError("alpha must have shape (S,), mu and lam (S, K + 1)")
+        return alpha, mu, lam
+
+    def solve(self, samples, alpha, mu, lam, draw=False, seed=0):
+        """(w_new (S, U), V_new (S, U, K)) under host samples, a list of (w0, w[D], V[D, K]); alpha (S,), mu / lam (S, K + 1)"""
+        K, S, w0s, ws, Vs = _pack_samples(samples)
+        alpha, mu, lam = self._hypers(S, K, alpha, mu, lam)
+        w_new, V_new = np.empty((S, self.U)), np.empty((S, self.U, K))
+        self._ck(lib().mfm_foldin_solve(self.h, K, S, _p(w0s), _p(ws), _p(Vs), _p(alpha), _p(mu), _p(lam), int(bool(draw)),
+                                        int(seed), _p(w_new), _p(V_new)))
+        return w_new, V_new
+
+    def solve_store(self, store, alpha, mu, lam, draw=False, seed=0, first=0, count=None):
+        count = len(store) - first if count is None else count
+        alpha, mu, lam = self._hypers(count, store.K, alpha, mu, lam)
+        w_new, V_new = np.empty((count, self.U)), np.empty((count, self.U, store.K))
+        self._ck(lib().mfm_foldin_solve_store(self.h, store.h, first, count, _p(alpha), _p(mu), _p(lam), int(bool(draw)), int(seed),
+                                              _p(w_new), _p(V_new)))
+        return w_new, V_new

@@ -808,6 +808,72 @@ struct Predictor {
     run_pairs(Xq, Xc, rq, rc, offsets, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), score.mutable_data(), nullptr);
     return py::make_tuple(idx, score);
   }
+  // ---- folding new one-hot entities into the kept samples (not in the reference; include/myfm_hip.h "folding new one-hot features")
+  // X: the context rows GROUPED by entity (offsets (U + 1,)), alpha (S,), mu / lam (S, K + 1). Returns (w_new (S, U), V_new (S, U, K)).
+  py::tuple fold_in_solve(const py::object &Xo, const NpF64 &y, const py::array_t<int64_t, py::array::c_style | py::array::forcecast> &offsets,
+                          bool fit_linear, const NpF64 &alpha, const NpF64 &mu, const NpF64 &lam, bool draw, uint64_t seed) const {
+    Csr X = csr_from_py(Xo);
+    const size_t S = samples.size(), K = rank;
+    if ((size_t)X.cols != feature_size) {
+      std::ostringstream ss;
+      ss << "Told to fold in rows of width " << X.cols << " but this->feature_size is " << feature_size;
+      throw std::invalid_argument(ss.str());
+    }
+    if (y.size() != X.rows) throw std::invalid_argument("X and y have different sizes");
+    if (offsets.size() < 1) throw std::invalid_argument("no entity offsets");
+    if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
+    if ((size_t)alpha.size() != S || (size_t)mu.size() != S * (K + 1) || (size_t)lam.size() != S * (K + 1))
+      throw std::invalid_argument("fold-in: alpha must hold one entry per kept sample, mu and lambda (K + 1) per kept sample");
+    if ((int)K > mfm_foldin_max_rank()) {
+      std::ostringstream ss;
+      ss << "fold_in serves ranks up to " << mfm_foldin_max_rank() << ", this model has rank " << K;
+      throw std::invalid_argument(ss.str());
+    }
+    const int64_t U = (int64_t)offsets.size() - 1;
+    mfm_foldin *h = nullptr;
+    int code = mfm_foldin_create(selected_device(), X.cols, X.rows, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), U,
+                                 offsets.data(), fit_linear ? 1 : 0, &h);
+    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(nullptr));
+    std::unique_ptr<mfm_foldin, void (*)(mfm_foldin *)> guard(h, mfm_foldin_destroy);
+    py::array_t<double> w_new({(py::ssize_t)S, (py::ssize_t)U});
+    py::array_t<double> V_new({(py::ssize_t)S, (py::ssize_t)U, (py::ssize_t)K});
+    code = with_samples(
+        [&](mfm_store *st, int first) {
+          return mfm_foldin_solve_store(h, st, first, (int)S, alpha.data(), mu.data(), lam.data(), draw ? 1 : 0, seed, w_new.mutable_data(),
+                                        V_new.mutable_data());
+        },
+        [&](const double *w0s, const double *ws, const double *Vs) {
+          return mfm_foldin_solve(h, (int)K, (int)S, w0s, ws, Vs, alpha.data(), mu.data(), lam.data(), draw ? 1 : 0, seed,
+                                  w_new.mutable_data(), V_new.mutable_data());
+        });
+    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(h));
+    return py::make_tuple(w_new, V_new);
+  }
+  // the predictor of feature size D + U whose sample s is this one's sample s with w and V extended by w_new[s], V_new[s] (host
+  // samples: the restored-model path of every device predictor)
+  Predictor extended(const NpF64 &w_new, const NpF64 &V_new) const {
+    const size_t S = samples.size(), K = rank, D = feature_size;
+    if (w_new.ndim() != 2 || V_new.ndim() != 3 || (size_t)w_new.shape(0) != S || (size_t)V_new.shape(0) != S ||
+        V_new.shape(1) != w_new.shape(1) || (size_t)V_new.shape(2) != K)
+      throw std::invalid_argument("extended: expected w_new (S, U) and V_new (S, U, K)");
+    const size_t U = (size_t)w_new.shape(1), D2 = D + U;
+    Predictor out(rank, D2, type);
+    out.samples.reserve(S);
+    for (size_t s = 0; s < S; s++) {
+      const_cast<FM &>(samples[s]).ensure();
+      const FM &f = samples[s];
+      if (f.w.size() != D || f.V.size() != D * K) throw std::invalid_argument("feature size mismatch!");
+      vector<Real> w(D2), V(D2 * K);
+      std::copy(f.w.begin(), f.w.end(), w.begin());
+      std::copy(w_new.data() + s * U, w_new.data() + (s + 1) * U, w.begin() + (std::ptrdiff_t)D);
+      for (size_t k = 0; k < K; k++) {
+        std::copy(f.V.begin() + (std::ptrdiff_t)(k * D), f.V.begin() + (std::ptrdiff_t)((k + 1) * D), V.begin() + (std::ptrdiff_t)(k * D2));
+        for (size_t u = 0; u < U; u++) V[k * D2 + D + u] = V_new.data()[(s * U + u) * K + k];
+      }
+      out.samples.emplace_back(f.w0, std::move(w), std::move(V), (int)K, f.cutpoints);
+    }
+    return out;
+  }
   // ---- posterior predictive summaries (not in the reference): mean, standard deviation and quantiles over the samples -------
   // Phi^-1(p), 0 < p < 1, by bisection of 0.5 erfc(-z / sqrt 2) down to neighbouring doubles (it only places the root bracket
   // of the device's mixture solve)
@@ -2697,6 +2763,7 @@ PYBIND11_MODULE(_myfm, m) {
 
   py::class_<Predictor>(m, "Predictor")
       .def_readonly("samples", &Predictor::samples)
+      .def_readonly("feature_size", &Predictor::feature_size)
       .def("predict", &Predictor::predict)
       .def("predict_parallel", &Predictor::predict_parallel)
       .def("predict_parallel_oprobit", &Predictor::predict_parallel_oprobit)
@@ -2709,6 +2776,9 @@ PYBIND11_MODULE(_myfm, m) {
                                int first = 0;
                                return (bool)p.resident(&first);
                              })  // the samples are read in place from the device store (else: uploaded from the host)
+      .def("fold_in_solve", &Predictor::fold_in_solve, py::arg("X"), py::arg("y"), py::arg("offsets"), py::arg("fit_linear"), py::arg("alpha"),
+           py::arg("mu"), py::arg("lam"), py::arg("draw") = false, py::arg("seed") = 0)
+      .def("extended", &Predictor::extended, py::arg("w_new"), py::arg("V_new"))
       .def("predict_dist", &Predictor::predict_dist, py::arg("X"), py::arg("rels"), py::arg("quantiles"), py::arg("precisions") = py::none(),
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def("predict_dist_oprobit", &Predictor::predict_dist_oprobit, py::arg("X"), py::arg("rels"), py::arg("quantiles"),

@@ -312,6 +312,7 @@ class _FMEstimatorBase:
 
 PredictiveSummary = namedtuple("PredictiveSummary", ["mean", "std", "quantiles"])
 PREDICT_DIST_MAX_QUANTILES = 32
+FOLD_IN_MAX_RANK = 64  # fold_in factors a (rank + 1)^2 matrix per (entity, sample) in the device's local memory (csrc/mfm_foldin.hpp)
 PREDICT_DIST_MAX_SAMPLES = 4096  # with a non-empty `quantiles`: a row's values are sorted in the device's local memory
 
 
@@ -498,6 +499,100 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase)
     def predict(self, X, X_rel=[], n_workers: Optional[int] = None):
         """Posterior predictive mean (gibbs.py:219-240)."""
         return self._predict_core(X, X_rel, n_workers=n_workers)
+
+    def fold_in(self, X, y, entity, group, n_entities=None, draw=False, random_seed=0):
+        """The fitted model extended by U new one-hot features -- users or items that were not in the training table and have
+        now been observed a few times -- without refitting the chain. Returns a new MyFMGibbsRegressor of feature
+        size D + U; this one is left untouched.
+
+        X (n, D) scipy sparse, D the fitted feature size: the CONTEXT of each new observation in the model's full feature space
+        (for a new user: the item's one-hot and whatever else the row carries), without the new entity's own column; a model
+        fitted with relation blocks takes the expanded rows. y (n,): the targets. entity (n,): integers in [0, U) naming the new
+        entity of each observation, in any order; an entity may have no observation. U = n_entities, or entity.max() + 1 when
+        that is None. group: the prior group in [0, n_groups_) the new features belong to (the users' group for new users).
+
+        A new feature with value 1 enters the score linearly, so under kept sample s its parameters theta = (w_u, V_u1 .. V_uK)
+        have an exact Gaussian posterior given that sample's noise precision alpha_s and its group's mu_w, lambda_w, mu_V,
+        lambda_V (the last S entries of history_.hypers, as predict_dist(noise=True) reads them):
+            Lambda = diag(lambda) + alpha_s sum_i z_i z_i^T,   b = diag(lambda) mu + alpha_s sum_i z_i r_i,
+            z_i = (1, q_s(x_i)),  q_sk(x) = sum_j V_s[j, k] x_j,  r_i = y_i - score_s(x_i),
+        computed on the device per (entity, sample). draw=False stores the posterior mean Lambda^-1 b; draw=True stores a draw
+        from the posterior, reproducible for random_seed. An entity without observations gets the prior mean (or a prior draw).
+        A model fitted with fit_linear=False gets w_u = 0; rank 0 estimates w_u alone.
+
+        The result's sample s is this model's sample s with w and V extended by the columns D .. D + U - 1 in entity order;
+        cutpoints, history_, n_groups_ and the constructor arguments are carried over and fold_in_columns_ = (D, D + U). A query
+        row for new entity u is the one-hot of column D + u (plus its context); predict, predict_dist, predict_pairs,
+        predict_topk, w_samples, V_samples and pickling work on it as on any fitted model, and folding in twice (users, then
+        items) composes. Its samples are host copies, the path of an unpickled model.
+
+        Not covered: the classifier, ordered-probit and variational estimators (the first two need a latent-variable inner
+        loop); X_rel arguments; new features with a value other than 1; row-sharded operation (the model is replicated, so each
+        rank can fold in its own entities). Ranks up to FOLD_IN_MAX_RANK. The arguments are checked on the host before the
+        device is touched (ValueError)."""
+        predictor = self._fetch_predictor()
+        D, K = int(predictor.feature_size), int(self.rank)
+        if X is None or not sps.issparse(X):
+            raise ValueError("X must be a scipy sparse matrix of shape (n, %d)" % D)
+        X = _as_csr(X, 0)
+        n = X.shape[0]
+        if X.shape[1] != D:
+            raise ValueError("X has %d columns but the fitted feature size is %d (the rows hold the context of the new "
+                             "observations, not the new entity's column)" % (X.shape[1], D))
+        y = np.asarray(y, dtype=REAL).reshape(-1)
+        if y.shape[0] != n:
+            raise ValueError("X has %d rows but y has %d entries" % (n, y.shape[0]))
+        entity = np.asarray(entity)
+        if entity.ndim != 1 or entity.shape[0] != n:
+            raise ValueError("X has %d rows but entity has shape %s" % (n, entity.shape))
+        if n and not np.issubdtype(entity.dtype, np.integer):
+            raise ValueError("entity must hold integers")
+        entity = entity.astype(np.int64)
+        if n_entities is None:
+            if n == 0:
+                raise ValueError("an empty entity array needs n_entities")
+            U = int(entity.max()) + 1
+        else:
+            if isinstance(n_entities, bool) or int(n_entities) != n_entities or n_entities < 0:
+                raise ValueError("n_entities must be a non-negative integer")
+            U = int(n_entities)
+        if n and entity.min() < 0:
+            raise ValueError("entity holds a negative index")
+        if n and entity.max() >= U:
+            raise ValueError("entity holds index %d but n_entities is %d" % (int(entity.max()), U))
+        if not np.all(np.isfinite(y)):
+            raise ValueError("y holds a value that is not finite")
+        G = self.n_groups_ if self.n_groups_ is not None else 0
+        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or not 0 <= group < G:
+            raise ValueError("group must be an integer in [0, %d)" % G)
+        if K > FOLD_IN_MAX_RANK:
+            raise ValueError("fold_in serves ranks up to %d, this model has rank %d" % (FOLD_IN_MAX_RANK, K))
+        n_samples = len(predictor.samples)
+        hypers = None if self.history_ is None else self.history_.hypers
+        if hypers is None or len(hypers) < n_samples:
+            raise RuntimeError("fold_in needs history_ with the hyper-parameters of every kept sample")
+        kept = hypers[len(hypers) - n_samples:]
+        g = int(group)
+        alpha = np.asarray([h.alpha for h in kept], dtype=REAL)
+        mu = np.empty((n_samples, K + 1), dtype=REAL)
+        lam = np.empty((n_samples, K + 1), dtype=REAL)
+        for s, h in enumerate(kept):
+            mu[s, 0], lam[s, 0] = np.asarray(h.mu_w)[g], np.asarray(h.lambda_w)[g]
+            mu[s, 1:], lam[s, 1:] = np.asarray(h.mu_V)[g, :K], np.asarray(h.lambda_V)[g, :K]
+        # the observations grouped by entity (stable: an entity's rows keep their order)
+        order = np.argsort(entity, kind="stable")
+        offsets = np.zeros(U + 1, dtype=np.int64)
+        np.cumsum(np.bincount(entity, minlength=U), out=offsets[1:])
+        w_new, V_new = predictor.fold_in_solve(X[order], np.ascontiguousarray(y[order]), offsets, bool(self.fit_linear), alpha, mu,
+                                               lam, bool(draw), int(random_seed) & 0xFFFFFFFFFFFFFFFF)
+        out = MyFMGibbsRegressor(self.rank, init_stdev=self.init_stdev, random_seed=self.random_seed, alpha_0=self.alpha_0,
+                                 beta_0=self.beta_0, gamma_0=self.gamma_0, mu_0=self.mu_0, reg_0=self.reg_0, fit_w0=self.fit_w0,
+                                 fit_linear=self.fit_linear, exact_latent_draws=self.exact_latent_draws)
+        out.predictor_ = predictor.extended(w_new, V_new)
+        out.history_ = self.history_
+        out.n_groups_ = self.n_groups_
+        out.fold_in_columns_ = (D, D + U)
+        return out
 
 
 class MyFMGibbsClassifier(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase):
