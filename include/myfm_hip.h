@@ -487,6 +487,28 @@ int mfm_foldin_solve(mfm_foldin *p, int32_t rank, int32_t n_samples, const doubl
                      const double *alpha, const double *mu, const double *lambda, int32_t draw, uint64_t seed, double *w_new,
                      double *V_new);
 
+/* ---- the same for the probit tasks: a short Albert-Chib chain per (entity, sample) (csrc/mfm_foldin_gibbs.hip) ----
+ * The handle is mfm_foldin_create's; its y holds the labels: +-1 for the classifier (task 0), class indices in [0, n_class) for
+ * ordered probit (task 1; cutpoints[S][n_class - 1], the group's cutpoints of every sample; NULL and n_class ignored for task 0).
+ * Both tasks have noise precision 1, so Lambda = diag(lambda_s) + sum_i z_i z_i^T = U^T U is fixed. From theta^0 = mu, sweep
+ * t = 0 .. T - 1, T = n_burn + n_inner: m_i = f_i + z_i^T theta^t; d_i a truncated standard normal (classifier: above -m_i for
+ * y_i > 0, else below; ordered probit: between the cutpoints of the class, minus m_i) on the per-row Philox stream keyed (seed,
+ * the fold-in latent tag + t, row = s n + i), i the grouped row and n the handle's row count; r_i = z_i^T theta^t + d_i;
+ * b = lambda mu + sum_i z_i r_i; thetabar^{t+1} = Lambda^-1 b; theta^{t+1} = thetabar^{t+1} + U^-1 eps^t, eps^t_j as the closed
+ * form's normals but on draw word (the fold-in draw tag + 1 + t). draw != 0 writes theta^T, a posterior draw given sample s;
+ * draw = 0 writes the mean of thetabar^{t+1} over t >= n_burn. An entity without observations gets mu bit for bit, or
+ * mu_j + eps^{T-1}_j / sqrt(lambda_j). fit_linear = 0 writes w_new = 0. Outputs: w_new[S][U], V_new[S][U][K].
+ * MFM_ERR_INVALID before any launch: lambda not positive and finite, mu or a cutpoint not finite, cutpoints not non-decreasing, a
+ * label that is not an integer in [0, n_class), n_inner < 1, n_burn < 0, T > 65535, a rank above the limit. A non-finite model
+ * value is MFM_ERR_INVALID from the call and zeros in the result. A cell keeps n_u (M + 1) doubles of scratch; the call walks
+ * entities, then samples, in chunks that stay under the handle's scratch bound, and a result does not depend on that.          */
+int mfm_foldin_gibbs_solve_store(mfm_foldin *p, mfm_store *st, int32_t first, int32_t count, int32_t task, int32_t n_class,
+                                 const double *cutpoints, const double *mu, const double *lambda, int32_t n_burn, int32_t n_inner,
+                                 int32_t draw, uint64_t seed, double *w_new, double *V_new);
+int mfm_foldin_gibbs_solve(mfm_foldin *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                           int32_t task, int32_t n_class, const double *cutpoints, const double *mu, const double *lambda,
+                           int32_t n_burn, int32_t n_inner, int32_t draw, uint64_t seed, double *w_new, double *V_new);
+
 /* FM::predict_score of the LIVE sample (the FM* handed to the per-iteration callback,
  * FMTrainer.hpp:78; utils/callbacks/libfm.py:85): scores design `d` with the (w0, w, V) currently
  * resident in training context `ctx` -- no download / upload of the model state. Same device only.  */

@@ -42,7 +42,7 @@ SYMBOLS = [
     "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
     "mfm_pairs_set_cutpoints",
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
-    "mfm_foldin_solve_store", "mfm_foldin_solve",
+    "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
 ]
 
@@ -191,6 +191,8 @@ def lib():
     L.mfm_foldin_max_rank.argtypes = []
     L.mfm_foldin_solve_store.argtypes = [vp, vp, i32, i32, P, P, P, i32, u64, P, P]
     L.mfm_foldin_solve.argtypes = [vp, i32, i32, P, P, P, P, P, P, i32, u64, P, P]
+    L.mfm_foldin_gibbs_solve_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, P, i32, i32, i32, u64, P, P]
+    L.mfm_foldin_gibbs_solve.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, P, i32, i32, i32, u64, P, P]
     L.mfm_test_erfcx.argtypes = [C.c_int, P, i64, P]
     L.mfm_test_truncated_normal.argtypes = [C.c_int, i32, dbl, dbl, u64, u64, i64, P]
     _lib = L
@@ -876,4 +878,39 @@ class FoldIn:
         w_new, V_new = np.empty((count, self.U)), np.empty((count, self.U, store.K))
         self._ck(lib().mfm_foldin_solve_store(self.h, store.h, first, count, _p(alpha), _p(mu), _p(lam), int(bool(draw)), int(seed),
                                               _p(w_new), _p(V_new)))
+        return w_new, V_new
+
+    FOLDIN_TASKS = {"classifier": 0, "ordered": 1}
+
+    @classmethod
+    def _gibbs_args(cls, S, K, mu, lam, task, cutpoints):
+        """(task code, n_class, cutpoints (S, n_class - 1) or None, mu, lam) of a solve_gibbs* call"""
+        _, mu, lam = cls._hypers(S, K, np.ones(S), mu, lam)
+        if task not in cls.FOLDIN_TASKS:
+            raise ValueError("task must be 'classifier' or 'ordered'")
+        if task == "classifier":
+            return 0, 0, None, mu, lam
+        cut = _f64(cutpoints)
+        if cut.ndim != 2 or cut.shape[0] != S or cut.shape[1] < 1:
+            raise ValueError("cutpoints must have shape (S, n_class - 1)")
+        return 1, cut.shape[1] + 1, cut, mu, lam
+
+    def solve_gibbs(self, samples, mu, lam, task, cutpoints=None, n_burn=10, n_inner=40, draw=False, seed=0):
+        """(w_new (S, U), V_new (S, U, K)) of a probit model under host samples by the inner chain (mfm_foldin_gibbs_solve): task
+        'classifier' (the handle's y is +-1) or 'ordered' (class indices; cutpoints (S, n_class - 1)); mu / lam (S, K + 1)"""
+        K, S, w0s, ws, Vs = _pack_samples(samples)
+        code, n_class, cut, mu, lam = self._gibbs_args(S, K, mu, lam, task, cutpoints)
+        w_new, V_new = np.empty((S, self.U)), np.empty((S, self.U, K))
+        self._ck(lib().mfm_foldin_gibbs_solve(self.h, K, S, _p(w0s), _p(ws), _p(Vs), code, n_class, _p(cut),
+                                              _p(mu), _p(lam), int(n_burn), int(n_inner), int(bool(draw)), int(seed), _p(w_new),
+                                              _p(V_new)))
+        return w_new, V_new
+
+    def solve_gibbs_store(self, store, mu, lam, task, cutpoints=None, n_burn=10, n_inner=40, draw=False, seed=0, first=0, count=None):
+        count = len(store) - first if count is None else count
+        code, n_class, cut, mu, lam = self._gibbs_args(count, store.K, mu, lam, task, cutpoints)
+        w_new, V_new = np.empty((count, self.U)), np.empty((count, self.U, store.K))
+        self._ck(lib().mfm_foldin_gibbs_solve_store(self.h, store.h, first, count, code, n_class, _p(cut),
+                                                    _p(mu), _p(lam), int(n_burn), int(n_inner), int(bool(draw)), int(seed),
+                                                    _p(w_new), _p(V_new)))
         return w_new, V_new

@@ -849,6 +849,65 @@ struct Predictor {
     if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(h));
     return py::make_tuple(w_new, V_new);
   }
+  // the same for the probit tasks (mfm_foldin_gibbs_*): y the labels (+-1, or class indices), the task this predictor's type, the
+  // cutpoints those of group `cutpoint_index` of every kept sample; mu / lam (S, K + 1)
+  py::tuple fold_in_gibbs_solve(const py::object &Xo, const NpF64 &y, const py::array_t<int64_t, py::array::c_style | py::array::forcecast> &offsets,
+                                bool fit_linear, const NpF64 &mu, const NpF64 &lam, int64_t cutpoint_index, int n_burn, int n_inner,
+                                bool draw, uint64_t seed) const {
+    Csr X = csr_from_py(Xo);
+    const size_t S = samples.size(), K = rank;
+    if (type != TaskType::CLASSIFICATION && type != TaskType::ORDERED)
+      throw std::invalid_argument("fold_in_gibbs serves the classifier and ordered probit");
+    if ((size_t)X.cols != feature_size) {
+      std::ostringstream ss;
+      ss << "Told to fold in rows of width " << X.cols << " but this->feature_size is " << feature_size;
+      throw std::invalid_argument(ss.str());
+    }
+    if (y.size() != X.rows) throw std::invalid_argument("X and y have different sizes");
+    if (offsets.size() < 1) throw std::invalid_argument("no entity offsets");
+    if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
+    if ((size_t)mu.size() != S * (K + 1) || (size_t)lam.size() != S * (K + 1))
+      throw std::invalid_argument("fold-in: mu and lambda must hold (K + 1) entries per kept sample");
+    if ((int)K > mfm_foldin_max_rank()) {
+      std::ostringstream ss;
+      ss << "fold_in_gibbs serves ranks up to " << mfm_foldin_max_rank() << ", this model has rank " << K;
+      throw std::invalid_argument(ss.str());
+    }
+    const bool ordered = type == TaskType::ORDERED;
+    vector<double> cuts;
+    size_t n_cut = 0;
+    if (ordered) {
+      for (auto &sm : samples) {
+        if (cutpoint_index < 0 || (size_t)cutpoint_index >= sm.cutpoints.size() || sm.cutpoints[(size_t)cutpoint_index].empty())
+          throw std::invalid_argument("cutpoint_index out of range: a kept sample has no such cutpoint group");
+        const auto &c = sm.cutpoints[(size_t)cutpoint_index];
+        if (n_cut == 0) n_cut = c.size();
+        if (c.size() != n_cut) throw std::invalid_argument("the kept samples hold different numbers of cutpoints");
+        cuts.insert(cuts.end(), c.begin(), c.end());
+      }
+    }
+    const int64_t U = (int64_t)offsets.size() - 1;
+    mfm_foldin *h = nullptr;
+    int code = mfm_foldin_create(selected_device(), X.cols, X.rows, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), U,
+                                 offsets.data(), fit_linear ? 1 : 0, &h);
+    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(nullptr));
+    std::unique_ptr<mfm_foldin, void (*)(mfm_foldin *)> guard(h, mfm_foldin_destroy);
+    py::array_t<double> w_new({(py::ssize_t)S, (py::ssize_t)U});
+    py::array_t<double> V_new({(py::ssize_t)S, (py::ssize_t)U, (py::ssize_t)K});
+    const int task = ordered ? 1 : 0, n_class = ordered ? (int)n_cut + 1 : 0;
+    const double *cp = ordered ? cuts.data() : nullptr;
+    code = with_samples(
+        [&](mfm_store *st, int first) {
+          return mfm_foldin_gibbs_solve_store(h, st, first, (int)S, task, n_class, cp, mu.data(), lam.data(), n_burn, n_inner, draw ? 1 : 0,
+                                              seed, w_new.mutable_data(), V_new.mutable_data());
+        },
+        [&](const double *w0s, const double *ws, const double *Vs) {
+          return mfm_foldin_gibbs_solve(h, (int)K, (int)S, w0s, ws, Vs, task, n_class, cp, mu.data(), lam.data(), n_burn, n_inner,
+                                        draw ? 1 : 0, seed, w_new.mutable_data(), V_new.mutable_data());
+        });
+    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(h));
+    return py::make_tuple(w_new, V_new);
+  }
   // the predictor of feature size D + U whose sample s is this one's sample s with w and V extended by w_new[s], V_new[s] (host
   // samples: the restored-model path of every device predictor)
   Predictor extended(const NpF64 &w_new, const NpF64 &V_new) const {
@@ -2778,6 +2837,9 @@ PYBIND11_MODULE(_myfm, m) {
                              })  // the samples are read in place from the device store (else: uploaded from the host)
       .def("fold_in_solve", &Predictor::fold_in_solve, py::arg("X"), py::arg("y"), py::arg("offsets"), py::arg("fit_linear"), py::arg("alpha"),
            py::arg("mu"), py::arg("lam"), py::arg("draw") = false, py::arg("seed") = 0)
+      .def("fold_in_gibbs_solve", &Predictor::fold_in_gibbs_solve, py::arg("X"), py::arg("y"), py::arg("offsets"), py::arg("fit_linear"),
+           py::arg("mu"), py::arg("lam"), py::arg("cutpoint_index") = 0, py::arg("n_burn") = 10, py::arg("n_inner") = 40,
+           py::arg("draw") = false, py::arg("seed") = 0)
       .def("extended", &Predictor::extended, py::arg("w_new"), py::arg("V_new"))
       .def("predict_dist", &Predictor::predict_dist, py::arg("X"), py::arg("rels"), py::arg("quantiles"), py::arg("precisions") = py::none(),
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)

@@ -8,6 +8,7 @@
 // whose results stay under `scratch_bound` bytes (256 MB unless mfm_foldin_set_scratch_bound says otherwise; never less than one
 // (entity, sample)). A result does not depend on the chunking.
 #include "mfm_foldin.hpp"
+#include "mfm_foldin_handle.hpp"
 #include "mfm_samples.hpp"
 
 #include <cmath>
@@ -15,38 +16,7 @@
 
 using namespace mfm;
 
-struct mfm_foldin {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  int64_t D = 0, n = 0, U = 0;
-  bool lin = true;
-  DevBuf<int64_t> ptr, eoff;
-  DevBuf<int32_t> idx;
-  DevBuf<double> val, y;
-  int64_t scratch_bound = (int64_t)256 << 20;
-  ~mfm_foldin() {
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  void use_device() { MFM_HIP_CHECK(hipSetDevice(device)); }
-};
-
 static thread_local std::string g_foldin_error;
-
-#define FOLDIN_TRY(p) \
-  try {               \
-    (p)->use_device();
-#define FOLDIN_CATCH(p)              \
-  return MFM_OK;                     \
-  }                                  \
-  catch (const mfm::Error &ex) {     \
-    (p)->err = ex.what();            \
-    return ex.code;                  \
-  }                                  \
-  catch (const std::exception &ex) { \
-    (p)->err = ex.what();            \
-    return MFM_ERR_RUNTIME;          \
-  }
 
 namespace {
 
@@ -202,6 +172,8 @@ int mfm_foldin_create(int device, int64_t D, int64_t n, const int64_t *indptr, c
     p->val.upload(data, (size_t)indptr[n]);
     p->y.upload(y, (size_t)n);
     p->eoff.upload(entity_offsets, (size_t)U + 1);
+    p->h_eoff.assign(entity_offsets, entity_offsets + U + 1);
+    p->h_y.assign(y, y + n);
     *out = p.release();
     return MFM_OK;
   } catch (const mfm::Error &ex) {

@@ -62,6 +62,54 @@ struct FoldinDD {
   }
 };
 
+// z and f of rows [rb, rb + nr) of the context table under the sample (w0, w, V): lane = row, wave w the factors w, w + 4, ...
+// Z[lane][off + k] takes q_k of row `lane` (the caller sets column 0 where the model has a linear term); wave 0 returns the row's
+// f in double-double, the other waves an empty sum. One barrier inside; the caller places one more before Z is read.
+__device__ __forceinline__ FoldinDD foldin_rows_zf(const FoldinArgs &a, const double *__restrict__ w, const double *__restrict__ V,
+                                                   double w0, int64_t rb, int nr, double *Z, double *part) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int K = a.K, off = a.lin, ldz = (K + off) | 1;
+  int64_t pb = 0, pe = 0;
+  if (lane < nr) {
+    pb = a.rowptr[rb + lane];
+    pe = a.rowptr[rb + lane + 1];
+  }
+  // f in double-double. The posterior is driven by the residual r = y - f, which is of the noise's size while y and f are of
+  // the target's: an error of one rounding of f's TERMS in r moves theta by alpha z / Lambda times that, which a bound relative
+  // to |theta| does not cover for an entity with one or two rows. The pair term is taken as sum_{p' < p} t_p t_p' (t_p = x_p v_p,
+  // a running prefix sum) instead of 1/2 (q^2 - sum t^2): no cancellation, and exactly 0 for a one-hot row.
+  FoldinDD lin, pair;
+  if (wave == 0)
+    for (int64_t p = pb; p < pe; p++) {
+      const double x = a.val[p], wj = w[a.colidx[p]];
+      const double ph = x * wj;
+      lin.add(ph, fma(x, wj, -ph));
+    }
+  for (int k = wave; k < K; k += FOLDIN_WG / 64) {
+    const double *__restrict__ Vk = V + (int64_t)k * a.D;
+    FoldinDD q;
+    for (int64_t p = pb; p < pe; p++) {
+      const double x = a.val[p], v = Vk[a.colidx[p]];
+      const double th = x * v, tl = fma(x, v, -th);  // t = th + tl exactly
+      const double ph = th * q.hi;
+      pair.add(ph, fma(th, q.hi, -ph) + (th * q.lo + tl * q.hi));
+      q.add(th, tl);
+    }
+    Z[lane * ldz + off + k] = q.hi + q.lo;
+  }
+  if (wave == 0) pair.add(lin.hi, lin.lo);
+  part[wave * FOLDIN_ROWS + lane] = pair.hi;
+  part[(FOLDIN_WG / 64 + wave) * FOLDIN_ROWS + lane] = pair.lo;
+  __syncthreads();
+  FoldinDD f;
+  if (wave == 0) {
+    f.add(w0, 0.0);
+#pragma unroll
+    for (int q = 0; q < FOLDIN_WG / 64; q++) f.add(part[q * FOLDIN_ROWS + lane], part[(FOLDIN_WG / 64 + q) * FOLDIN_ROWS + lane]);
+  }
+  return f;
+}
+
 template <bool DRAW>
 __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
   extern __shared__ double foldin_smem[];
@@ -122,45 +170,10 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
 
   for (int64_t rb = e0; rb < e1; rb += FOLDIN_ROWS) {
     const int nr = (int)(e1 - rb < FOLDIN_ROWS ? e1 - rb : FOLDIN_ROWS);
-    // ---- z, f and the residual of rows [rb, rb + nr): lane = row, wave w the factors w, w + 4, ...
+    // ---- z, f and the residual of rows [rb, rb + nr)
     {
-      int64_t pb = 0, pe = 0;
-      if (lane < nr) {
-        pb = a.rowptr[rb + lane];
-        pe = a.rowptr[rb + lane + 1];
-      }
-      // f in double-double. The posterior is driven by the residual r = y - f, which is of the noise's size while y and f are of
-      // the target's: an error of one rounding of f's TERMS in r moves theta by alpha z / Lambda times that, which a bound relative
-      // to |theta| does not cover for an entity with one or two rows. The pair term is taken as sum_{p' < p} t_p t_p' (t_p = x_p v_p,
-      // a running prefix sum) instead of 1/2 (q^2 - sum t^2): no cancellation, and exactly 0 for a one-hot row.
-      FoldinDD lin, pair;
-      if (wave == 0)
-        for (int64_t p = pb; p < pe; p++) {
-          const double x = a.val[p], wj = w[a.colidx[p]];
-          const double ph = x * wj;
-          lin.add(ph, fma(x, wj, -ph));
-        }
-      for (int k = wave; k < K; k += FOLDIN_WG / 64) {
-        const double *__restrict__ Vk = V + (int64_t)k * a.D;
-        FoldinDD q;
-        for (int64_t p = pb; p < pe; p++) {
-          const double x = a.val[p], v = Vk[a.colidx[p]];
-          const double th = x * v, tl = fma(x, v, -th);  // t = th + tl exactly
-          const double ph = th * q.hi;
-          pair.add(ph, fma(th, q.hi, -ph) + (th * q.lo + tl * q.hi));
-          q.add(th, tl);
-        }
-        Z[lane * ldz + off + k] = q.hi + q.lo;
-      }
-      if (wave == 0) pair.add(lin.hi, lin.lo);
-      part[wave * FOLDIN_ROWS + lane] = pair.hi;
-      part[(FOLDIN_WG / 64 + wave) * FOLDIN_ROWS + lane] = pair.lo;
-      __syncthreads();
+      const FoldinDD f = foldin_rows_zf(a, w, V, w0, rb, nr, Z, part);
       if (wave == 0) {
-        FoldinDD f;
-        f.add(w0, 0.0);
-#pragma unroll
-        for (int q = 0; q < FOLDIN_WG / 64; q++) f.add(part[q * FOLDIN_ROWS + lane], part[(FOLDIN_WG / 64 + q) * FOLDIN_ROWS + lane]);
         double rr = 0.0;
         if (lane < nr) {
           const double yv = a.y[rb + lane];

@@ -425,6 +425,127 @@ class _PairScoringMixin:
         return predictor.predict_topk(Xq, Xc, int(k), exclude, rq, rc)
 
 
+def _fold_in_checked(est, name, X, y, entity, group, n_entities):
+    """The host-side checks that fold_in and fold_in_gibbs share, in one order and with one set of messages (`name`: the calling
+    method). Returns (predictor, D, K, X csr, y float64 (n,), entity int64 (n,), U, the hyper-parameters of the kept samples, group)."""
+    predictor = est._fetch_predictor()
+    D, K = int(predictor.feature_size), int(est.rank)
+    if X is None or not sps.issparse(X):
+        raise ValueError("X must be a scipy sparse matrix of shape (n, %d)" % D)
+    X = _as_csr(X, 0)
+    n = X.shape[0]
+    if X.shape[1] != D:
+        raise ValueError("X has %d columns but the fitted feature size is %d (the rows hold the context of the new "
+                         "observations, not the new entity's column)" % (X.shape[1], D))
+    y = np.asarray(y, dtype=REAL).reshape(-1)
+    if y.shape[0] != n:
+        raise ValueError("X has %d rows but y has %d entries" % (n, y.shape[0]))
+    entity = np.asarray(entity)
+    if entity.ndim != 1 or entity.shape[0] != n:
+        raise ValueError("X has %d rows but entity has shape %s" % (n, entity.shape))
+    if n and not np.issubdtype(entity.dtype, np.integer):
+        raise ValueError("entity must hold integers")
+    entity = entity.astype(np.int64)
+    if n_entities is None:
+        if n == 0:
+            raise ValueError("an empty entity array needs n_entities")
+        U = int(entity.max()) + 1
+    else:
+        if isinstance(n_entities, bool) or int(n_entities) != n_entities or n_entities < 0:
+            raise ValueError("n_entities must be a non-negative integer")
+        U = int(n_entities)
+    if n and entity.min() < 0:
+        raise ValueError("entity holds a negative index")
+    if n and entity.max() >= U:
+        raise ValueError("entity holds index %d but n_entities is %d" % (int(entity.max()), U))
+    if not np.all(np.isfinite(y)):
+        raise ValueError("y holds a value that is not finite")
+    G = est.n_groups_ if est.n_groups_ is not None else 0
+    if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or not 0 <= group < G:
+        raise ValueError("group must be an integer in [0, %d)" % G)
+    if K > FOLD_IN_MAX_RANK:
+        raise ValueError("%s serves ranks up to %d, this model has rank %d" % (name, FOLD_IN_MAX_RANK, K))
+    n_samples = len(predictor.samples)
+    hypers = None if est.history_ is None else est.history_.hypers
+    if hypers is None or len(hypers) < n_samples:
+        raise RuntimeError("%s needs history_ with the hyper-parameters of every kept sample" % name)
+    return predictor, D, K, X, y, entity, U, hypers[len(hypers) - n_samples:], int(group)
+
+
+def _fold_in_prior(kept, g, K):
+    """(mu, lam), each (S, K + 1): per kept sample the prior mean and precision of (w, V_1 .. V_K) in group g"""
+    mu = np.empty((len(kept), K + 1), dtype=REAL)
+    lam = np.empty((len(kept), K + 1), dtype=REAL)
+    for s, h in enumerate(kept):
+        mu[s, 0], lam[s, 0] = np.asarray(h.mu_w)[g], np.asarray(h.lambda_w)[g]
+        mu[s, 1:], lam[s, 1:] = np.asarray(h.mu_V)[g, :K], np.asarray(h.lambda_V)[g, :K]
+    return mu, lam
+
+
+def _fold_in_grouping(entity, U):
+    """the observations grouped by entity (stable: an entity's rows keep their order): (order, offsets (U + 1,))"""
+    order = np.argsort(entity, kind="stable")
+    offsets = np.zeros(U + 1, dtype=np.int64)
+    np.cumsum(np.bincount(entity, minlength=U), out=offsets[1:])
+    return order, offsets
+
+
+def _folded_in(est, predictor, D, U):
+    """a new estimator of est's class around the extended predictor: constructor arguments, history_ and n_groups_ carried over"""
+    out = type(est)(est.rank, init_stdev=est.init_stdev, random_seed=est.random_seed, alpha_0=est.alpha_0, beta_0=est.beta_0,
+                    gamma_0=est.gamma_0, mu_0=est.mu_0, reg_0=est.reg_0, fit_w0=est.fit_w0, fit_linear=est.fit_linear,
+                    exact_latent_draws=est.exact_latent_draws)
+    out.predictor_ = predictor
+    out.history_ = est.history_
+    out.n_groups_ = est.n_groups_
+    out.fold_in_columns_ = (D, D + U)
+    return out
+
+
+FOLD_IN_GIBBS_MAX_SWEEPS = 65535  # n_burn + n_inner: the sweep number is part of the random streams' draw word
+
+
+class _FoldInGibbsMixin:
+    """fold_in for the probit estimators: the new features' parameters have no closed-form posterior there, so each (entity, sample)
+    runs a short Albert-Chib chain on the device."""
+
+    def _fold_in_gibbs(self, X, y, entity, group, n_entities, draw, random_seed, n_burn, n_inner, cutpoint_index):
+        for name, v, lo in (("n_burn", n_burn, 0), ("n_inner", n_inner, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+                raise ValueError("%s must be an integer of at least %d" % (name, lo))
+        if n_burn + n_inner > FOLD_IN_GIBBS_MAX_SWEEPS:
+            raise ValueError("n_burn + n_inner must not exceed %d" % FOLD_IN_GIBBS_MAX_SWEEPS)
+        predictor, D, K, X, y, entity, U, kept, g = _fold_in_checked(self, "fold_in_gibbs", X, y, entity, group, n_entities)
+        mu, lam = _fold_in_prior(kept, g, K)
+        o = 0 if self.fit_linear else 1
+        if not (np.all(np.isfinite(lam[:, o:])) and np.all(lam[:, o:] > 0.0)):
+            raise ValueError("a kept sample has a prior precision that is not positive and finite")
+        if not np.all(np.isfinite(mu[:, o:])):
+            raise ValueError("a kept sample has a prior mean that is not finite")
+        if self._task_type == TaskType.ORDERED:
+            if isinstance(cutpoint_index, bool) or not isinstance(cutpoint_index, (int, np.integer)):
+                raise ValueError("cutpoint_index must be an integer")
+            samples = predictor.samples
+            sizes = set(len(fm.cutpoints[cutpoint_index]) if 0 <= cutpoint_index < len(fm.cutpoints) else 0 for fm in samples)
+            if 0 in sizes:
+                raise ValueError("cutpoint_index %d out of range: a kept sample has no such cutpoint group" % cutpoint_index)
+            if len(sizes) > 1:
+                raise ValueError("the kept samples hold different numbers of cutpoints in group %d" % cutpoint_index)
+            cut = np.asarray([fm.cutpoints[cutpoint_index] for fm in samples], dtype=REAL)
+            if not np.all(np.isfinite(cut)):
+                raise ValueError("a kept sample has a cutpoint that is not finite")
+            if np.any(np.diff(cut, axis=1) < 0.0):
+                raise ValueError("the cutpoints of a kept sample are not non-decreasing")
+            n_class = cut.shape[1] + 1
+            if np.any(y != np.floor(y)) or np.any(y < 0) or np.any(y >= n_class):
+                raise ValueError("y must hold integer class labels in [0, %d)" % n_class)
+        order, offsets = _fold_in_grouping(entity, U)
+        w_new, V_new = predictor.fold_in_gibbs_solve(X[order], np.ascontiguousarray(y[order]), offsets, bool(self.fit_linear), mu, lam,
+                                                     int(cutpoint_index), int(n_burn), int(n_inner), bool(draw),
+                                                     int(random_seed) & 0xFFFFFFFFFFFFFFFF)
+        return _folded_in(self, predictor.extended(w_new, V_new), D, U)
+
+
 class MyFMGibbsBase(_FMEstimatorBase):
     """Common part of the Gibbs estimators (base.py:70-323 + gibbs.py:32-142)."""
 
@@ -526,76 +647,20 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase)
         predict_topk, w_samples, V_samples and pickling work on it as on any fitted model, and folding in twice (users, then
         items) composes. Its samples are host copies, the path of an unpickled model.
 
-        Not covered: the classifier, ordered-probit and variational estimators (the first two need a latent-variable inner
-        loop); X_rel arguments; new features with a value other than 1; row-sharded operation (the model is replicated, so each
+        Not covered: the variational estimators (MyFMGibbsClassifier and MyFMOrderedProbit have fold_in_gibbs, which runs a
+        latent-variable inner chain); X_rel arguments; new features with a value other than 1; row-sharded operation (the model is replicated, so each
         rank can fold in its own entities). Ranks up to FOLD_IN_MAX_RANK. The arguments are checked on the host before the
         device is touched (ValueError)."""
-        predictor = self._fetch_predictor()
-        D, K = int(predictor.feature_size), int(self.rank)
-        if X is None or not sps.issparse(X):
-            raise ValueError("X must be a scipy sparse matrix of shape (n, %d)" % D)
-        X = _as_csr(X, 0)
-        n = X.shape[0]
-        if X.shape[1] != D:
-            raise ValueError("X has %d columns but the fitted feature size is %d (the rows hold the context of the new "
-                             "observations, not the new entity's column)" % (X.shape[1], D))
-        y = np.asarray(y, dtype=REAL).reshape(-1)
-        if y.shape[0] != n:
-            raise ValueError("X has %d rows but y has %d entries" % (n, y.shape[0]))
-        entity = np.asarray(entity)
-        if entity.ndim != 1 or entity.shape[0] != n:
-            raise ValueError("X has %d rows but entity has shape %s" % (n, entity.shape))
-        if n and not np.issubdtype(entity.dtype, np.integer):
-            raise ValueError("entity must hold integers")
-        entity = entity.astype(np.int64)
-        if n_entities is None:
-            if n == 0:
-                raise ValueError("an empty entity array needs n_entities")
-            U = int(entity.max()) + 1
-        else:
-            if isinstance(n_entities, bool) or int(n_entities) != n_entities or n_entities < 0:
-                raise ValueError("n_entities must be a non-negative integer")
-            U = int(n_entities)
-        if n and entity.min() < 0:
-            raise ValueError("entity holds a negative index")
-        if n and entity.max() >= U:
-            raise ValueError("entity holds index %d but n_entities is %d" % (int(entity.max()), U))
-        if not np.all(np.isfinite(y)):
-            raise ValueError("y holds a value that is not finite")
-        G = self.n_groups_ if self.n_groups_ is not None else 0
-        if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or not 0 <= group < G:
-            raise ValueError("group must be an integer in [0, %d)" % G)
-        if K > FOLD_IN_MAX_RANK:
-            raise ValueError("fold_in serves ranks up to %d, this model has rank %d" % (FOLD_IN_MAX_RANK, K))
-        n_samples = len(predictor.samples)
-        hypers = None if self.history_ is None else self.history_.hypers
-        if hypers is None or len(hypers) < n_samples:
-            raise RuntimeError("fold_in needs history_ with the hyper-parameters of every kept sample")
-        kept = hypers[len(hypers) - n_samples:]
-        g = int(group)
+        predictor, D, K, X, y, entity, U, kept, g = _fold_in_checked(self, "fold_in", X, y, entity, group, n_entities)
         alpha = np.asarray([h.alpha for h in kept], dtype=REAL)
-        mu = np.empty((n_samples, K + 1), dtype=REAL)
-        lam = np.empty((n_samples, K + 1), dtype=REAL)
-        for s, h in enumerate(kept):
-            mu[s, 0], lam[s, 0] = np.asarray(h.mu_w)[g], np.asarray(h.lambda_w)[g]
-            mu[s, 1:], lam[s, 1:] = np.asarray(h.mu_V)[g, :K], np.asarray(h.lambda_V)[g, :K]
-        # the observations grouped by entity (stable: an entity's rows keep their order)
-        order = np.argsort(entity, kind="stable")
-        offsets = np.zeros(U + 1, dtype=np.int64)
-        np.cumsum(np.bincount(entity, minlength=U), out=offsets[1:])
+        mu, lam = _fold_in_prior(kept, g, K)
+        order, offsets = _fold_in_grouping(entity, U)
         w_new, V_new = predictor.fold_in_solve(X[order], np.ascontiguousarray(y[order]), offsets, bool(self.fit_linear), alpha, mu,
                                                lam, bool(draw), int(random_seed) & 0xFFFFFFFFFFFFFFFF)
-        out = MyFMGibbsRegressor(self.rank, init_stdev=self.init_stdev, random_seed=self.random_seed, alpha_0=self.alpha_0,
-                                 beta_0=self.beta_0, gamma_0=self.gamma_0, mu_0=self.mu_0, reg_0=self.reg_0, fit_w0=self.fit_w0,
-                                 fit_linear=self.fit_linear, exact_latent_draws=self.exact_latent_draws)
-        out.predictor_ = predictor.extended(w_new, V_new)
-        out.history_ = self.history_
-        out.n_groups_ = self.n_groups_
-        out.fold_in_columns_ = (D, D + U)
-        return out
+        return _folded_in(self, predictor.extended(w_new, V_new), D, U)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PredictiveDistMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -632,6 +697,27 @@ class MyFMGibbsClassifier(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase
     def predict(self, X, X_rel=[], n_workers: Optional[int] = None):
         return self.predict_proba(X, X_rel, n_workers=n_workers) > 0.5
 
+    def fold_in_gibbs(self, X, y, entity, group, n_entities=None, draw=False, random_seed=0, n_burn=10, n_inner=40):
+        """The fitted classifier extended by U new one-hot features (users or items that were not in the training table) from a few
+        observations each, without refitting. Returns a new MyFMGibbsClassifier of feature size D + U; this one is
+        left untouched. X, entity, group and n_entities are MyFMGibbsRegressor.fold_in's, checked the same way; y (n,) holds 0 / 1
+        or bool labels as fit takes them.
+
+        Under kept sample s the new feature's theta = (w_u, V_u1 .. V_uK) enters the score linearly, but a probit likelihood leaves
+        no closed-form posterior: each (entity, sample) runs a chain of n_burn + n_inner Albert-Chib sweeps on the device (draw the
+        latent of every observation truncated by its label, then theta from its Gaussian conditional), started at the prior mean.
+        draw=False stores the Rao-Blackwellised posterior mean over the last n_inner sweeps; draw=True stores the chain's last
+        state, a posterior draw. Both are reproducible for random_seed. n_burn + n_inner <= 65535. An entity without observations
+        gets the prior mean (or a prior draw); fit_linear=False gives w_u = 0.
+
+        The result is as fold_in's: history_, n_groups_ and the constructor arguments carried over, fold_in_columns_ = (D, D + U);
+        predict_proba, predict_dist, predict_pairs, predict_topk and pickling work on it, and folding in twice composes. Not
+        covered: X_rel arguments, features with a value other than 1, row-sharded operation. Ranks up to FOLD_IN_MAX_RANK. The
+        arguments are checked on the host before the device is touched (ValueError)."""
+        if self.predictor_ is not None and y is not None:
+            y = self._process_y(y)
+        return self._fold_in_gibbs(X, y, entity, group, n_entities, draw, random_seed, n_burn, n_inner, 0)
+
 
 def _device_row_order(X):
     """stable order of the rows by their first stored column, or None when they already are (or it does not apply)"""
@@ -650,7 +736,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""
@@ -700,6 +786,16 @@ class MyFMOrderedProbit(_PairScoringMixin, MyFMGibbsBase):
 
     def predict(self, X, X_rel=[]):
         return self.predict_proba(X, X_rel=X_rel).argmax(axis=1)
+
+    def fold_in_gibbs(self, X, y, entity, group, n_entities=None, draw=False, random_seed=0, n_burn=10, n_inner=40, cutpoint_index=0):
+        """MyFMGibbsClassifier.fold_in_gibbs for ordered probit: y (n,) holds integer class labels in [0, n_class), n_class the
+        number of cutpoints of group `cutpoint_index` of the kept samples plus one (checked as predict_proba_dist checks it). A
+        latent is drawn between its class's cutpoints of that sample. Returns a new MyFMOrderedProbit of feature size D + U with
+        the cutpoints carried over; predict_proba, predict_proba_dist, predict_expected_dist, predict_topk and pickling work on it."""
+        out = self._fold_in_gibbs(X, y, entity, group, n_entities, draw, random_seed, n_burn, n_inner, cutpoint_index)
+        if hasattr(self, "n_cutpoint_groups"):
+            out.n_cutpoint_groups = self.n_cutpoint_groups
+        return out
 
     def _predict_dist_oprobit(self, X, X_rel, quantiles, cutpoint_index, expected):
         predictor = self._fetch_predictor()
