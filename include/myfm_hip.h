@@ -456,6 +456,25 @@ int mfm_pairs_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double
 int mfm_pairs_topk(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                    int32_t mode, int32_t k, int64_t *idx, double *score);
 
+/* ---- ranking by an upper confidence bound (csrc/mfm_pairs_ucb.hpp) ---------------------------------------------
+ * The same pairs, sides, blocks, exclusions, sample views and memory rule, but the spread over the samples is kept. With v_s(u, i)
+ * the per-sample value of the mode (0: score_s, 1: Phi(score_s), 2: sum_j Phi(score_s - cut_s[j])):
+ *   mean = (sum_s v_s) / S,   std = the population standard deviation (ddof 0) of the v_s,   value = mean + beta * std,
+ * the moments by Welford's recurrence in sample order (S = 1 and bitwise-equal v_s give std == 0.0 exactly).
+ *   moments:  mean[U * I], std[U * I] row-major, every pair.
+ *   topk_ucb: per query row the k (1 <= k <= 256) candidates of largest value under the order of topk; idx, value, mean,
+ *             std are [U * k] row-major. mean and std are recomputed for the selected pairs after the merge, with the factors
+ *             summed in another association than the selecting kernel's, so value and mean + beta * std agree within rounding,
+ *             not bit for bit. Tail: idx -1, value -inf, mean and std NaN. beta: any finite number (negative: a lower bound).
+ * A non-finite beta and k outside [1, 256] are MFM_ERR_INVALID before any launch.                                          */
+int mfm_pairs_moments_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, double *mean, double *std);
+int mfm_pairs_moments(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                      int32_t mode, double *mean, double *std);
+int mfm_pairs_topk_ucb_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, double beta,
+                             int64_t *idx, double *value, double *mean, double *std);
+int mfm_pairs_topk_ucb(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t mode, int32_t k, double beta, int64_t *idx, double *value, double *mean, double *std);
+
 /* ---- folding new one-hot features into the kept samples (csrc/mfm_foldin.hip) ----------------------------------
  * U new entities (users or items that were not in the training table), each a new one-hot column with value 1 in its own
  * observations. X (n, D) holds the CONTEXT of the n observations in the model's feature space (not the new column), y their

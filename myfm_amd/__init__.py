@@ -27,6 +27,8 @@ from .estimators import (  # noqa: E402
     MyFMGibbsRegressor,
     MyFMOrderedProbit,
     MyFMRegressor,
+    PairSummary,
+    RankedSummary,
     VariationalFMClassifier,
     VariationalFMRegressor,
 )
@@ -41,4 +43,6 @@ __all__ = [
     "VariationalFMRegressor",
     "VariationalFMClassifier",
     "FOLD_IN_MAX_RANK",
+    "PairSummary",
+    "RankedSummary",
 ]

@@ -40,7 +40,7 @@ SYMBOLS = [
     "mfm_vb_design_levels",
     "mfm_pairs_create", "mfm_pairs_destroy", "mfm_pairs_last_error", "mfm_pairs_set_exclude", "mfm_pairs_set_scratch_bound",
     "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
-    "mfm_pairs_set_cutpoints",
+    "mfm_pairs_set_cutpoints", "mfm_pairs_moments_store", "mfm_pairs_moments", "mfm_pairs_topk_ucb_store", "mfm_pairs_topk_ucb",
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
@@ -182,6 +182,10 @@ def lib():
     L.mfm_pairs_topk_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P]
     L.mfm_pairs_scores.argtypes = [vp, i32, i32, P, P, P, i32, P]
     L.mfm_pairs_topk.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P]
+    L.mfm_pairs_moments_store.argtypes = [vp, vp, i32, i32, i32, P, P]
+    L.mfm_pairs_moments.argtypes = [vp, i32, i32, P, P, P, i32, P, P]
+    L.mfm_pairs_topk_ucb_store.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, P, P, P, P]
+    L.mfm_pairs_topk_ucb.argtypes = [vp, i32, i32, P, P, P, i32, i32, C.c_double, P, P, P, P]
     L.mfm_foldin_create.argtypes = [C.c_int, i64, i64, P, P, P, P, i64, P, i32, C.POINTER(vp)]
     L.mfm_foldin_destroy.argtypes = [vp]
     L.mfm_foldin_destroy.restype = None
@@ -812,6 +816,41 @@ class Pairs:
         idx, val = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk))
         self._ck(lib().mfm_pairs_topk_store(self.h, store.h, first, count, mode, int(k), _p(idx), _p(val)))
         return idx, val
+
+    # ---- the moments form: mean and population std over the samples of the per-sample value
+    def moments(self, samples, mode=0):
+        """(mean (U, I), std (U, I)) of the per-sample value of every pair"""
+        K, S, w0s, ws, Vs = _pack_samples(samples)
+        mean, std = np.empty((self.U, self.I)), np.empty((self.U, self.I))
+        self._ck(lib().mfm_pairs_moments(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, _p(mean), _p(std)))
+        return mean, std
+
+    def moments_store(self, store, mode=0, first=0, count=None):
+        count = len(store) - first if count is None else count
+        mean, std = np.empty((self.U, self.I)), np.empty((self.U, self.I))
+        self._ck(lib().mfm_pairs_moments_store(self.h, store.h, first, count, mode, _p(mean), _p(std)))
+        return mean, std
+
+    def _ucb_out(self, k):
+        kk = max(int(k), 1)
+        return np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk)), np.empty((self.U, kk)), np.empty((self.U, kk))
+
+    def topk_ucb(self, samples, k, beta=1.0, mode=0):
+        """(indices int64 (U, k), value, mean, std (U, k)) ranked by value = mean + beta * std under (value descending, index
+        ascending). mean and std are recomputed for the selected pairs in another association than the selecting kernel's:
+        value equals mean + beta * std within rounding, not bit for bit. Tail: -1 / -inf / NaN / NaN."""
+        K, S, w0s, ws, Vs = _pack_samples(samples)
+        idx, val, mean, std = self._ucb_out(k)
+        self._ck(lib().mfm_pairs_topk_ucb(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, int(k), float(beta), _p(idx), _p(val),
+                                          _p(mean), _p(std)))
+        return idx, val, mean, std
+
+    def topk_ucb_store(self, store, k, beta=1.0, mode=0, first=0, count=None):
+        count = len(store) - first if count is None else count
+        idx, val, mean, std = self._ucb_out(k)
+        self._ck(lib().mfm_pairs_topk_ucb_store(self.h, store.h, first, count, mode, int(k), float(beta), _p(idx), _p(val),
+                                                _p(mean), _p(std)))
+        return idx, val, mean, std
 
 
 def group_by_entity(X, y, entity, n_entities):

@@ -755,9 +755,12 @@ struct Predictor {
     }
     return offsets;
   }
-  // idx / score: the top k; dense: all pairs (exactly one of the two forms)
+  // idx / score: the top k; dense: all pairs (exactly one of the two forms). std_out != nullptr: the moments form:
+  // dense holds the mean and std_out the std of all pairs, or the top k are ranked by mean + beta * std and mean_out / std_out
+  // hold the selected pairs' moments.
   void run_pairs(const Csr &Xq, const Csr &Xc, const Relations &rq, const Relations &rc, const vector<size_t> &offsets,
-                 const Csr *exclude, int k, int64_t *idx, double *score, double *dense) const {
+                 const Csr *exclude, int k, int64_t *idx, double *score, double *dense, double beta = 0.0, double *mean_out = nullptr,
+                 double *std_out = nullptr) const {
     if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
     DevicePairs dp((int64_t)feature_size, Xq, Xc);
     dp.add_blocks(0, rq, offsets);
@@ -772,12 +775,28 @@ struct Predictor {
     const int S = (int)samples.size();
     dp.ck(with_samples(
         [&](mfm_store *st, int first) {
+          if (std_out)
+            return dense ? mfm_pairs_moments_store(dp.p, st, first, S, mode, dense, std_out)
+                         : mfm_pairs_topk_ucb_store(dp.p, st, first, S, mode, k, beta, idx, score, mean_out, std_out);
           return dense ? mfm_pairs_scores_store(dp.p, st, first, S, mode, dense) : mfm_pairs_topk_store(dp.p, st, first, S, mode, k, idx, score);
         },
         [&](const double *w0s, const double *ws, const double *Vs) {
+          if (std_out)
+            return dense ? mfm_pairs_moments(dp.p, (int)rank, S, w0s, ws, Vs, mode, dense, std_out)
+                         : mfm_pairs_topk_ucb(dp.p, (int)rank, S, w0s, ws, Vs, mode, k, beta, idx, score, mean_out, std_out);
           return dense ? mfm_pairs_scores(dp.p, (int)rank, S, w0s, ws, Vs, mode, dense)
                        : mfm_pairs_topk(dp.p, (int)rank, S, w0s, ws, Vs, mode, k, idx, score);
         }));
+  }
+  // the exclusion pattern of a ranked call (None: an empty one, which the caller does not pass on)
+  static Csr checked_exclude(const py::object &excludeo, const Csr &Xq, const Csr &Xc) {
+    Csr ex;
+    if (excludeo.is_none()) return ex;
+    ex = csr_from_py(excludeo);
+    if (ex.rows != Xq.rows || ex.cols != Xc.rows) throw std::invalid_argument("exclude must have shape (n_queries, n_candidates)");
+    for (int32_t j : ex.indices)
+      if (j < 0 || j >= ex.cols) throw std::invalid_argument("exclude: column index out of range");
+    return ex;
   }
   py::array_t<double> predict_pairs(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
     Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
@@ -795,18 +814,38 @@ struct Predictor {
     Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
     const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
     if (k < 1 || k > 256) throw std::invalid_argument("k must be in [1, 256]");
-    Csr ex;
-    if (!excludeo.is_none()) {
-      ex = csr_from_py(excludeo);
-      if (ex.rows != Xq.rows || ex.cols != Xc.rows)
-        throw std::invalid_argument("exclude must have shape (n_queries, n_candidates)");
-      for (int32_t j : ex.indices)
-        if (j < 0 || j >= ex.cols) throw std::invalid_argument("exclude: column index out of range");
-    }
+    const Csr ex = checked_exclude(excludeo, Xq, Xc);
     py::array_t<int64_t> idx({(py::ssize_t)Xq.rows, (py::ssize_t)k});
     py::array_t<double> score({(py::ssize_t)Xq.rows, (py::ssize_t)k});
     run_pairs(Xq, Xc, rq, rc, offsets, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), score.mutable_data(), nullptr);
     return py::make_tuple(idx, score);
+  }
+  // (mean (U, I), std (U, I)) over the kept samples of the per-sample value of every pair
+  py::tuple predict_pairs_dist(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
+    Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
+    Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
+    const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
+    if ((double)Xq.rows * (double)Xc.rows > 16777216.0)
+      throw std::invalid_argument("predict_pairs_dist returns every pair: more than 2^24 pairs are refused, use predict_topk_ucb");
+    py::array_t<double> mean({(py::ssize_t)Xq.rows, (py::ssize_t)Xc.rows}), sd({(py::ssize_t)Xq.rows, (py::ssize_t)Xc.rows});
+    run_pairs(Xq, Xc, rq, rc, offsets, nullptr, 0, nullptr, nullptr, mean.mutable_data(), 0.0, nullptr, sd.mutable_data());
+    return py::make_tuple(mean, sd);
+  }
+  // (indices, value, mean, std), each (U, k): the top k by value = mean + beta * std
+  py::tuple predict_topk_ucb(const py::object &Xqo, const py::object &Xco, int64_t k, double beta, const py::object &excludeo,
+                             const py::object &rqo, const py::object &rco) const {
+    Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
+    Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
+    const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
+    if (k < 1 || k > 256) throw std::invalid_argument("k must be in [1, 256]");
+    if (!std::isfinite(beta)) throw std::invalid_argument("beta must be a finite number");
+    const Csr ex = checked_exclude(excludeo, Xq, Xc);
+    const py::ssize_t U = (py::ssize_t)Xq.rows;
+    py::array_t<int64_t> idx({U, (py::ssize_t)k});
+    py::array_t<double> value({U, (py::ssize_t)k}), mean({U, (py::ssize_t)k}), sd({U, (py::ssize_t)k});
+    run_pairs(Xq, Xc, rq, rc, offsets, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), value.mutable_data(), nullptr, beta,
+              mean.mutable_data(), sd.mutable_data());
+    return py::make_tuple(idx, value, mean, sd);
   }
   // ---- folding new one-hot entities into the kept samples (not in the reference; include/myfm_hip.h "folding new one-hot features")
   // X: the context rows GROUPED by entity (offsets (U + 1,)), alpha (S,), mu / lam (S, K + 1). Returns (w_new (S, U), V_new (S, U, K)).
@@ -2830,6 +2869,10 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk", &Predictor::predict_topk, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_pairs_dist", &Predictor::predict_pairs_dist, py::arg("X_query"), py::arg("X_cand"),
+           py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk_ucb", &Predictor::predict_topk_ucb, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("beta") = 1.0,
+           py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def_property_readonly("resident",
                              [](const Predictor &p) {
                                int first = 0;

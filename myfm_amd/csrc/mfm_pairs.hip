@@ -12,7 +12,12 @@
 // chunk -- and resident for it. The tables count against MFM_STORE_MAX_FRACTION together with Q; the per-row scratch formula is
 // unchanged. A side with blocks is embedded by k_pairs_embed_rel, one without by k_pairs_embed, so a call without blocks computes
 // what it computed before there were any.
+//
+// Moments (mfm_pairs_moments*, mfm_pairs_topk_ucb*; kernels: mfm_pairs_ucb.hpp). The same call with the spread over
+// the samples kept: k_pairs_tile_moments in place of k_pairs_tile, ranking by mean + beta * std, and after each chunk's merge
+// k_pairs_moments_at for mean and std of the selected pairs. A call without them launches what it launched before.
 #include "mfm_pairs.hpp"
+#include "mfm_pairs_ucb.hpp"
 #include "mfm_samples.hpp"
 
 #include <cmath>
@@ -119,8 +124,64 @@ void launch_tile(hipStream_t s, dim3 grid, const PairsArgs &a, int mode, bool de
 #undef PAIRS_LAUNCH
 }
 
-// The whole call over the samples of `v` (mfm_samples.hpp). dense != nullptr: (U, I) scores; else the top k.
-void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx, double *score, double *dense) {
+// ---- the moments form (mfm_pairs_ucb.hpp): MT * NT = 4, the selection buffers of PairsSel<MT>
+template <int MT, int NT, int MODE, bool DENSE>
+void launch_moments_t(hipStream_t s, dim3 grid, const PairsArgs &a) {
+  const size_t lds = DENSE ? 0 : PairsSel<MT>::BYTES;
+  static DeviceOnce raised;
+  if (lds > 48 * 1024 && raised.need()) {
+    MFM_HIP_CHECK(
+        hipFuncSetAttribute((const void *)k_pairs_tile_moments<MT, NT, MODE, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised.mark();
+  }
+  hipLaunchKernelGGL((k_pairs_tile_moments<MT, NT, MODE, DENSE>), grid, dim3(PAIRS_WG), lds, s, a);
+}
+
+int moments_rows(bool dense, int k) { return dense ? 32 : k <= 64 ? 64 : k <= 128 ? 32 : 16; }
+int moments_step(bool dense, int k) { return dense ? 128 : k <= 64 ? 64 : k <= 128 ? 128 : 256; }
+
+void launch_moments(hipStream_t s, dim3 grid, const PairsArgs &a, int mode, bool dense) {
+#define PAIRS_LAUNCH(MT, NT, DENSE)                   \
+  do {                                                \
+    if (mode == 0)                                    \
+      launch_moments_t<MT, NT, 0, DENSE>(s, grid, a); \
+    else if (mode == 1)                               \
+      launch_moments_t<MT, NT, 1, DENSE>(s, grid, a); \
+    else                                              \
+      launch_moments_t<MT, NT, 2, DENSE>(s, grid, a); \
+  } while (0)
+  if (dense)
+    PAIRS_LAUNCH(2, 2, true);
+  else if (a.k <= 64)
+    PAIRS_LAUNCH(4, 1, false);
+  else if (a.k <= 128)
+    PAIRS_LAUNCH(2, 2, false);
+  else
+    PAIRS_LAUNCH(1, 4, false);
+#undef PAIRS_LAUNCH
+}
+
+void launch_moments_at(hipStream_t s, const PairsArgs &a, int mode, const int32_t *out_i, int64_t n, double *mean, double *sd) {
+  const dim3 grid((unsigned)((n + PAIRS_WG / 64 - 1) / (PAIRS_WG / 64)));
+  if (mode == 0)
+    hipLaunchKernelGGL(k_pairs_moments_at<0>, grid, dim3(PAIRS_WG), 0, s, a, out_i, n, mean, sd);
+  else if (mode == 1)
+    hipLaunchKernelGGL(k_pairs_moments_at<1>, grid, dim3(PAIRS_WG), 0, s, a, out_i, n, mean, sd);
+  else
+    hipLaunchKernelGGL(k_pairs_moments_at<2>, grid, dim3(PAIRS_WG), 0, s, a, out_i, n, mean, sd);
+}
+
+// what a moments call adds to a mean call: rank by mean + beta * std, and return mean and std ((U, I) each with `dense`, which
+// then holds the mean; (U, k) each with the top k)
+struct PairsMoments {
+  double beta = 0.0;
+  double *mean = nullptr, *sd = nullptr;
+};
+
+// The whole call over the samples of `v` (mfm_samples.hpp). dense != nullptr: (U, I) scores; else the top k. mo != nullptr: the
+// moments form.
+void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx, double *score, double *dense,
+               const PairsMoments *mo = nullptr) {
   const int S = v.count(), rank = v.K;
   if (v.device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
   if (v.D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
@@ -168,10 +229,12 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     }
   }
   const int64_t W = (I + 31) / 32;
-  const int rows_t = tile_rows(is_dense, k), step = tile_step(is_dense, k);
+  const int rows_t = mo ? moments_rows(is_dense, k) : tile_rows(is_dense, k);
+  const int step = mo ? moments_step(is_dense, k) : tile_step(is_dense, k);
   const int64_t steps_total = (std::max<int64_t>(I, 1) + step - 1) / step;
   const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && !is_dense ? (double)W * 4 : 0.0) +
-                         (is_dense ? (double)I * 8 : (double)(PAIRS_MAX_STRIPES + 1) * k * 12);
+                         (is_dense ? (double)I * 8 : (double)(PAIRS_MAX_STRIPES + 1) * k * 12) +
+                         (!mo ? 0.0 : is_dense ? (double)I * 8 : (double)k * 16);  // (the second dense output / mean and std of the lists)
   int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
   chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
   chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
@@ -235,7 +298,7 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   MFM_HIP_CHECK(hipGetLastError());
 
   // ---- queries, chunk by chunk
-  DevBuf<double> Pf, Ab, Asum, list_v, out_v, d_dense;
+  DevBuf<double> Pf, Ab, Asum, list_v, out_v, d_dense, d_dense_std, out_m, out_s;
   DevBuf<int32_t> list_i, out_i;
   DevBuf<uint32_t> mask;
   std::vector<int32_t> h_idx;
@@ -283,11 +346,22 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     a.list_v = nullptr;
     a.list_i = nullptr;
     a.dense = nullptr;
+    a.dense_std = nullptr;
+    a.beta = mo ? mo->beta : 0.0;
     if (is_dense) {
       ensure(d_dense, (size_t)(Uc * I));
       a.dense = d_dense.p;
-      launch_tile(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, true);
-      MFM_HIP_CHECK(hipGetLastError());
+      if (mo) {
+        ensure(d_dense_std, (size_t)(Uc * I));
+        a.dense_std = d_dense_std.p;
+        launch_moments(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, true);
+        MFM_HIP_CHECK(hipGetLastError());
+        MFM_HIP_CHECK(
+            hipMemcpyAsync(mo->sd + (size_t)u0 * I, d_dense_std.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
+      } else {
+        launch_tile(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, true);
+        MFM_HIP_CHECK(hipGetLastError());
+      }
       MFM_HIP_CHECK(hipMemcpyAsync(dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
       MFM_HIP_CHECK(hipStreamSynchronize(s));
       continue;
@@ -299,12 +373,23 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     a.list_v = list_v.p;
     a.list_i = list_i.p;
     if (I > 0) {
-      launch_tile(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, false);
+      if (mo)
+        launch_moments(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, false);
+      else
+        launch_tile(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, false);
       MFM_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, k,
                        out_v.p, out_i.p);
     MFM_HIP_CHECK(hipGetLastError());
+    if (mo) {
+      ensure(out_m, (size_t)(Uc * k));
+      ensure(out_s, (size_t)(Uc * k));
+      launch_moments_at(s, a, mode, out_i.p, Uc * k, out_m.p, out_s.p);
+      MFM_HIP_CHECK(hipGetLastError());
+      MFM_HIP_CHECK(hipMemcpyAsync(mo->mean + (size_t)u0 * k, out_m.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(mo->sd + (size_t)u0 * k, out_s.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
     h_idx.resize((size_t)(Uc * k));
     MFM_HIP_CHECK(hipMemcpyAsync(score + (size_t)u0 * k, out_v.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
     MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), out_i.p, (size_t)(Uc * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -314,14 +399,27 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   MFM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense) {
+void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense,
+                     const PairsMoments *mo = nullptr) {
   if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense);
+  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo);
 }
 
 void run_pairs_host(mfm_pairs *p, int rank, int n_samples, const double *w0s, const double *ws, const double *Vs, int mode, int k,
-                    int64_t *idx, double *score, double *dense) {
-  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense);
+                    int64_t *idx, double *score, double *dense, const PairsMoments *mo = nullptr) {
+  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo);
+}
+
+// the checks of the ranked moments calls that need neither samples nor a device
+PairsMoments checked_ucb(int k, double beta, const int64_t *idx, const double *value, double *mean, double *sd) {
+  if (!idx || !value || !mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
+  if (k < 1 || k > PAIRS_MAX_K) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  if (!std::isfinite(beta)) throw Error(MFM_ERR_INVALID, "beta must be a finite number");
+  PairsMoments mo;
+  mo.beta = beta;
+  mo.mean = mean;
+  mo.sd = sd;
+  return mo;
 }
 
 }  // namespace
@@ -482,6 +580,41 @@ int mfm_pairs_topk(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *
   PAIRS_TRY(p)
   if (!idx || !score) throw Error(MFM_ERR_INVALID, "no output array");
   run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, idx, score, nullptr);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_moments_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, double *mean, double *sd) {
+  PAIRS_TRY(p)
+  if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
+  PairsMoments mo;
+  mo.sd = sd;
+  run_pairs_store(p, st, first, count, mode, 0, nullptr, nullptr, mean, &mo);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_moments(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                      int32_t mode, double *mean, double *sd) {
+  PAIRS_TRY(p)
+  if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
+  PairsMoments mo;
+  mo.sd = sd;
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, 0, nullptr, nullptr, mean, &mo);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_ucb_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, double beta,
+                             int64_t *idx, double *value, double *mean, double *sd) {
+  PAIRS_TRY(p)
+  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
+  run_pairs_store(p, st, first, count, mode, k, idx, value, nullptr, &mo);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_ucb(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t mode, int32_t k, double beta, int64_t *idx, double *value, double *mean, double *sd) {
+  PAIRS_TRY(p)
+  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, idx, value, nullptr, &mo);
   PAIRS_CATCH(p)
 }
 

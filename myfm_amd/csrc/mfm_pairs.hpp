@@ -204,6 +204,8 @@ struct PairsArgs {
   double *dense;                            // [Uc][I] (the scores entry points)
   const double *cut;                        // [S][n_cut]: the samples' cutpoints (MODE 2; last, so that the other modes' argument
   int n_cut;                                //  offsets are what they were)
+  double *dense_std;                        // [Uc][I]: the moments form's second dense output (mfm_pairs_ucb.hpp; dense holds the mean)
+  double beta;                              // the moments form ranks by mean + beta * std (last, for the same reason)
 };
 
 // LDS of the selecting kernel: per query row a buffer of CAP candidates that survived the row's threshold, its fill count and

@@ -425,6 +425,46 @@ class _PairScoringMixin:
         return predictor.predict_topk(Xq, Xc, int(k), exclude, rq, rc)
 
 
+PairSummary = namedtuple("PairSummary", ["mean", "std"])
+RankedSummary = namedtuple("RankedSummary", ["indices", "value", "mean", "std"])
+
+
+class _PairUncertaintyMixin:
+    """Ranking that counts what the model does not know yet, for the estimators that keep S posterior samples:
+    the Gibbs regressor and classifier and MyFMOrderedProbit. The variational estimators keep one sample, the mean model, and have
+    no spread to rank by. With v_s(u, i) the per-sample value of the pair -- the score for a regressor, Phi(score) for a
+    classifier, the expected class index for ordered probit, i.e. what predict_dist / predict_expected_dist summarise per row --
+
+        mean = sum_s v_s / S,    std = the population standard deviation (ddof = 0) of the v_s,    value = mean + beta * std.
+
+    Sides, relation-block arguments, the disjoint-columns rule, the exclusions and the memory rule are _PairScoringMixin's; the
+    arguments are validated on the host before the device is touched. S = 1 and identical samples give std == 0.0 exactly."""
+
+    def predict_pairs_dist(self, X_query, X_cand, X_rel_query=[], X_rel_cand=[]):
+        """PairSummary(mean (U, I), std (U, I)) of every pair. U * I > 2^24 is refused (ValueError): use predict_topk_ucb."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        return PairSummary(*predictor.predict_pairs_dist(Xq, Xc, rq, rc))
+
+    def predict_topk_ucb(self, X_query, X_cand, k: int, beta: float = 1.0, exclude=None, X_rel_query=[], X_rel_cand=[]):
+        """Per query row the k candidates of largest value = mean + beta * std: RankedSummary(indices int64 (U, k), value, mean,
+        std), each row ordered by (value descending, candidate index ascending). beta may be any finite float: positive explores,
+        negative gives a conservative list (a lower bound), 0 ranks by the mean through this path. `exclude` as in predict_topk.
+
+        value is what the selection compared; mean and std are recomputed for the selected pairs with the factors summed in
+        another order, so value equals mean + beta * std within rounding, not bit for bit. Where fewer than k candidates remain
+        the tail is index -1, value -inf, mean and std NaN. 1 <= k <= 256 and a finite real beta, else ValueError."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        if isinstance(k, bool) or int(k) != k:
+            raise ValueError("k must be an integer in [1, 256]")
+        if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or not np.isfinite(beta):
+            raise ValueError("beta must be a finite real number")
+        if exclude is not None:
+            exclude = sps.csr_matrix(exclude)
+            if exclude.shape != (Xq.shape[0], Xc.shape[0]):
+                raise ValueError("exclude must have shape (n_queries, n_candidates)")
+        return RankedSummary(*predictor.predict_topk_ucb(Xq, Xc, int(k), float(beta), exclude, rq, rc))
+
+
 def _fold_in_checked(est, name, X, y, entity, group, n_entities):
     """The host-side checks that fold_in and fold_in_gibbs share, in one order and with one set of messages (`name`: the calling
     method). Returns (predictor, D, K, X csr, y float64 (n,), entity int64 (n,), U, the hyper-parameters of the kept samples, group)."""
@@ -592,7 +632,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -660,7 +700,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PredictiveDistMixin, MyFMGibbsBase)
         return _folded_in(self, predictor.extended(w_new, V_new), D, U)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PredictiveDistMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -736,7 +776,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""

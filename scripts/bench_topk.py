@@ -9,7 +9,12 @@ Writes the report to stdout and, with --out FILE, to that file.
 user-side block of 10 entries per row and a context block of 5, the candidate side an item-side block of 10), and the script
 times (a) the sides expanded on the host into flat matrices, run through the path without blocks, against (b) the block
 arguments of mfm_pairs_add_block. The embedding kernels' share of the call is taken from a kernel trace: each variant is run once
-more in a child process under `rocprofv3 --kernel-trace --stats` (skipped, and said so, where rocprofv3 is not installed)."""
+more in a child process under `rocprofv3 --kernel-trace --stats` (skipped, and said so, where rocprofv3 is not installed).
+
+--ucb: the cost of keeping the spread. At the same shape and on the same store, in one process: predict_topk's
+path (mfm_pairs_topk_store, the mean) against predict_topk_ucb's (mfm_pairs_topk_ucb_store, mean + beta * std with --beta), for
+the regressor's value (mode 0) and the classifier's (mode 1); then the kernel split of each of the four calls from a child process
+under `rocprofv3 --kernel-trace --stats`."""
 import argparse
 import csv
 import glob
@@ -42,6 +47,9 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--rel-blocks", action="store_true", help="relation-block sides: expanded flat matrices against block arguments")
 ap.add_argument("--rel-scale", type=float, default=0.02, help="scale of config 5's block shapes (1.0: 500 000 users, 50 000 items)")
 ap.add_argument("--rel-variant", choices=["flat", "blocks"], default=None, help=argparse.SUPPRESS)  # (the traced child runs one variant once)
+ap.add_argument("--ucb", action="store_true", help="predict_topk_ucb's path against predict_topk's on the same store")
+ap.add_argument("--beta", type=float, default=1.0)
+ap.add_argument("--ucb-variant", choices=["mean0", "ucb0", "mean1", "ucb1"], default=None, help=argparse.SUPPRESS)  # (the traced child)
 args = ap.parse_args()
 NU, NI, K, S, U, k = args.users, args.items, args.rank, args.samples, args.queries, args.k
 D = NU + NI
@@ -163,8 +171,73 @@ def rel_blocks():
             shutil.rmtree(tmp, ignore_errors=True)
 
 
+def kernel_split(child_args):
+    """{kernel name: total ms} of one child run under rocprofv3 --kernel-trace --stats, or a string saying why there is none"""
+    prof = shutil.which("rocprofv3")
+    if not prof:
+        return "rocprofv3 not found"
+    tmp = tempfile.mkdtemp(prefix="topk_trace_")
+    try:
+        cmd = [prof, "--kernel-trace", "--stats", "-d", tmp, "-o", "t", "--output-format", "csv", "--", sys.executable,
+               os.path.abspath(__file__)] + child_args
+        subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        parts = {}
+        for fn in glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True):
+            with open(fn) as f:
+                for row in csv.DictReader(f):
+                    short = row["Name"].split("(")[0].split("::")[-1].split("<")[0]
+                    parts[short] = parts.get(short, 0.0) + float(row["TotalDurationNs"]) / 1e6
+        return parts or "the trace held no kernel statistics"
+    except (subprocess.CalledProcessError, OSError, KeyError, ValueError) as e:
+        return type(e).__name__
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def ucb():
+    rng = np.random.default_rng(0)
+    store = _capi.Store(D, K)
+    for _ in range(S):
+        store.push(float(rng.normal()), rng.normal(size=D) * 0.3, rng.normal(size=(D, K)) * 0.2)
+    users = np.sort(rng.choice(NU, size=U, replace=False))
+    Xq = sps.csr_matrix((np.ones(U), (np.arange(U), users)), shape=(U, D))
+    Xc = sps.csr_matrix((np.ones(NI), (np.arange(NI), NU + np.arange(NI))), shape=(NI, D))
+    pairs = _capi.Pairs(Xq, Xc)
+    calls = {"mean0": lambda: pairs.topk_store(store, k, mode=0), "ucb0": lambda: pairs.topk_ucb_store(store, k, args.beta, mode=0),
+             "mean1": lambda: pairs.topk_store(store, k, mode=1), "ucb1": lambda: pairs.topk_ucb_store(store, k, args.beta, mode=1)}
+    if args.ucb_variant:  # the traced child: one call, nothing reported
+        calls[args.ucb_variant]()
+        return
+    say("ranking by mean + beta * std at the config-3 shape: %d queries x %d items, rank %d, %d samples, k = %d, beta = %g"
+        % (U, NI, K, S, k, args.beta))
+    flop = 2.0 * U * NI * S * K
+    med = {}
+    for name, what in (("mean0", "predict_topk, regressor's value (mode 0)      "), ("ucb0", "predict_topk_ucb, regressor's value (mode 0)  "),
+                       ("mean1", "predict_topk, classifier's value (mode 1)     "), ("ucb1", "predict_topk_ucb, classifier's value (mode 1) ")):
+        r, med[name], lo, hi = timed(calls[name], args.reps)
+        say("%s: median %.4f s (min %.4f, max %.4f, %d reps) -- %.1f TFLOP/s fp64 over the whole call"
+            % (what, med[name], lo, hi, args.reps, flop / med[name] / 1e12))
+        if name.startswith("ucb"):
+            idx, val, mean, std = r
+            say("    max |value - (mean + beta std)| = %.2e, std in [%.3g, %.3g]" % (np.abs(val - (mean + args.beta * std)).max(), std.min(), std.max()))
+    say("keeping the spread costs %.2fx the mean path's time for the regressor's value and %.2fx for the classifier's; the regressor's "
+        "moments call takes %.2fx the classifier's mean call" % (med["ucb0"] / med["mean0"], med["ucb1"] / med["mean1"], med["ucb0"] / med["mean1"]))
+    for name in ("mean0", "ucb0", "mean1", "ucb1"):
+        parts = kernel_split(["--ucb", "--ucb-variant", name, "--users", str(NU), "--items", str(NI), "--rank", str(K), "--samples", str(S),
+                              "--queries", str(U), "--k", str(k), "--beta", str(args.beta)])
+        if isinstance(parts, str):
+            say("    %s kernel split: not measured (%s)" % (name, parts))
+        else:
+            say("    %s kernel time %.3f ms: %s" % (name, sum(parts.values()), ", ".join("%s %.3f" % (n, v) for n, v in sorted(parts.items(), key=lambda t: -t[1]))))
+    pairs.close()
+
+
 if args.rel_blocks:
     rel_blocks()
+    write_out()
+    sys.exit(0)
+if args.ucb:
+    ucb()
     write_out()
     sys.exit(0)
 
