@@ -578,47 +578,49 @@ class Design:
     def score_ctx(self, ctx):
         """FM::predict_score with the model state resident in training context `ctx`."""
         out = np.empty(self.N)
-        rc = lib().mfm_design_score_ctx(self.h, ctx.h, _p(out))
-        if rc:
-            _raise(rc, lib().mfm_design_last_error(self.h))
+        self._ck(lib().mfm_design_score_ctx(self.h, ctx.h, _p(out)))
         return out
 
-    def predict(self, samples, mode=0, cutpoints=None):
-        """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        n_cut = 0
-        cp = None
+    def _ck(self, rc):
+        if rc:
+            _raise(rc, lib().mfm_design_last_error(self.h))
+
+    # each operation once, over a sample source (_host / _resident); Store's methods of the same names pass a resident range
+    def _predict(self, src, mode, cutpoints):
+        n_cut, cp = 0, None
         if mode == 2:
             cp = _f64(np.stack([np.asarray(c, dtype=np.float64) for c in cutpoints]))
             n_cut = cp.shape[1]
         out = np.empty((self.N, n_cut + 1) if mode == 2 else self.N)
-        rc = lib().mfm_design_predict(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, n_cut, _p(cp), _p(out))
-        if rc:
-            _raise(rc, lib().mfm_design_last_error(self.h))
+        self._ck(src.call("mfm_design_predict", self.h, mode, n_cut, _p(cp), _p(out)))
         return out
+
+    def _summary(self, src, mode, quantiles, precisions, tile_rows, chunk_samples):
+        probs, prec, z, mean, std, q = _summary_args(self.N, quantiles, precisions)
+        self._ck(src.call("mfm_design_summary", self.h, mode, len(probs), _p(probs), _p(prec), _p(z), int(tile_rows),
+                          int(chunk_samples), _p(mean), _p(std), _p(q)))
+        return mean, std, q
+
+    def _summary_oprobit(self, src, cutpoints, expected, quantiles, tile_rows, chunk_samples):
+        cp, n_cut, probs, mean, std, q = _summary_oprobit_args(self.N, cutpoints, expected, quantiles)
+        self._ck(src.call("mfm_design_summary_oprobit", self.h, int(bool(expected)), n_cut, _p(cp), len(probs), _p(probs),
+                          int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q)))
+        return mean, std, q
+
+    def predict(self, samples, mode=0, cutpoints=None):
+        """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
+        return self._predict(_host(samples), mode, cutpoints)
 
     def summary(self, samples, mode=0, quantiles=(), precisions=None, tile_rows=0, chunk_samples=0):
         """samples as predict; mode 0 score, 1 Phi(score). Returns (mean[N], std[N], quantiles[Q, N]) over the samples;
         precisions[S]: of the mixture mean_s N(score_s, 1 / precisions[s]) (mfm_design_summary)."""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        probs, prec, z, mean, std, q = _summary_args(self.N, quantiles, precisions)
-        rc = lib().mfm_design_summary(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, len(probs), _p(probs), _p(prec), _p(z),
-                                      int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
-        if rc:
-            _raise(rc, lib().mfm_design_last_error(self.h))
-        return mean, std, q
+        return self._summary(_host(samples), mode, quantiles, precisions, tile_rows, chunk_samples)
 
     def summary_oprobit(self, samples, cutpoints, expected=False, quantiles=(), tile_rows=0, chunk_samples=0):
         """samples as predict, cutpoints[S][n_cut]. Summaries of the class probabilities, (mean[N, C], std[N, C],
         quantiles[Q, N, C]) with C = n_cut + 1, or with `expected` of the expected class index, (mean[N], std[N],
         quantiles[Q, N]) (mfm_design_summary_oprobit)."""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        cp, n_cut, probs, mean, std, q = _summary_oprobit_args(self.N, cutpoints, expected, quantiles)
-        rc = lib().mfm_design_summary_oprobit(self.h, K, S, _p(w0s), _p(ws), _p(Vs), int(bool(expected)), n_cut, _p(cp), len(probs),
-                                              _p(probs), int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
-        if rc:
-            _raise(rc, lib().mfm_design_last_error(self.h))
-        return mean, std, q
+        return self._summary_oprobit(_host(samples), cutpoints, expected, quantiles, tile_rows, chunk_samples)
 
 
 def _summary_oprobit_args(N, cutpoints, expected, quantiles):
@@ -685,36 +687,15 @@ class Store:
         return w0.value, w, np.ascontiguousarray(V.T)
 
     def predict(self, design, mode=0, cutpoints=None, first=0, count=None):
-        count = len(self) - first if count is None else count
-        n_cut, cp = 0, None
-        if mode == 2:
-            cp = _f64(np.stack([np.asarray(c, dtype=np.float64) for c in cutpoints]))
-            n_cut = cp.shape[1]
-        out = np.empty((design.N, n_cut + 1) if mode == 2 else design.N)
-        rc = lib().mfm_design_predict_store(design.h, self.h, first, count, mode, n_cut, _p(cp), _p(out))
-        if rc:
-            _raise(rc, lib().mfm_design_last_error(design.h))
-        return out
+        return design._predict(_resident(self, first, count), mode, cutpoints)
 
     def summary(self, design, mode=0, quantiles=(), precisions=None, first=0, count=None, tile_rows=0, chunk_samples=0):
         """Design.summary over the resident samples [first, first + count) (mfm_design_summary_store)"""
-        count = len(self) - first if count is None else count
-        probs, prec, z, mean, std, q = _summary_args(design.N, quantiles, precisions)
-        rc = lib().mfm_design_summary_store(design.h, self.h, first, count, mode, len(probs), _p(probs), _p(prec), _p(z),
-                                            int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
-        if rc:
-            _raise(rc, lib().mfm_design_last_error(design.h))
-        return mean, std, q
+        return design._summary(_resident(self, first, count), mode, quantiles, precisions, tile_rows, chunk_samples)
 
     def summary_oprobit(self, design, cutpoints, expected=False, quantiles=(), first=0, count=None, tile_rows=0, chunk_samples=0):
         """Design.summary_oprobit over the resident samples [first, first + count) (mfm_design_summary_oprobit_store)"""
-        count = len(self) - first if count is None else count
-        cp, n_cut, probs, mean, std, q = _summary_oprobit_args(design.N, cutpoints, expected, quantiles)
-        rc = lib().mfm_design_summary_oprobit_store(design.h, self.h, first, count, int(bool(expected)), n_cut, _p(cp), len(probs),
-                                                    _p(probs), int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q))
-        if rc:
-            _raise(rc, lib().mfm_design_last_error(design.h))
-        return mean, std, q
+        return design._summary_oprobit(_resident(self, first, count), cutpoints, expected, quantiles, tile_rows, chunk_samples)
 
 
 def _pack_samples(samples):
@@ -725,6 +706,30 @@ def _pack_samples(samples):
     ws = _f64(np.stack([np.asarray(s[1], dtype=np.float64) for s in samples])) if S else np.empty(0)
     Vs = _f64(np.stack([np.asarray(s[2], dtype=np.float64).T for s in samples])) if S else np.empty(0)
     return K, S, w0s, ws, Vs
+
+
+class _Samples:
+    """Where an operation reads the kept samples: S samples of rank K, the suffix of the C symbol that reads them and the head
+    of its argument list after the handle. Every mfm_X_store(h, store, first, count, TAIL...) has a twin
+    mfm_X(h, rank, n_samples, w0s, ws, Vs, TAIL...) with the same TAIL (include/myfm_hip.h)."""
+
+    def __init__(self, S, K, suffix, head, keep):
+        self.S, self.K, self.suffix, self.head, self.keep = S, K, suffix, head, keep  # (keep: what the head points into)
+
+    def call(self, symbol, handle, *tail):
+        return getattr(lib(), symbol + self.suffix)(handle, *self.head, *tail)
+
+
+def _host(samples):
+    """host samples, a list of (w0, w[D], V[D, K]), packed once"""
+    K, S, w0s, ws, Vs = _pack_samples(samples)
+    return _Samples(S, K, "", (K, S, _p(w0s), _p(ws), _p(Vs)), (w0s, ws, Vs))
+
+
+def _resident(store, first, count):
+    """the samples [first, first + count) of a Store (count None: up to its end), read in place"""
+    count = len(store) - first if count is None else count
+    return _Samples(count, store.K, "_store", (store.h, first, count), store)
 
 
 class Pairs:
@@ -788,69 +793,60 @@ class Pairs:
         except Exception:
             pass
 
+    # each operation once, over a sample source (_host / _resident)
+    def _scores(self, src, mode):
+        out = np.empty((self.U, self.I))
+        self._ck(src.call("mfm_pairs_scores", self.h, mode, _p(out)))
+        return out
+
+    def _topk(self, src, k, mode):
+        kk = max(int(k), 1)
+        idx, val = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk))
+        self._ck(src.call("mfm_pairs_topk", self.h, mode, int(k), _p(idx), _p(val)))
+        return idx, val
+
+    def _moments(self, src, mode):
+        mean, std = np.empty((self.U, self.I)), np.empty((self.U, self.I))
+        self._ck(src.call("mfm_pairs_moments", self.h, mode, _p(mean), _p(std)))
+        return mean, std
+
+    def _topk_ucb(self, src, k, beta, mode):
+        kk = max(int(k), 1)
+        idx, val, mean, std = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk)), np.empty((self.U, kk)), np.empty((self.U, kk))
+        self._ck(src.call("mfm_pairs_topk_ucb", self.h, mode, int(k), float(beta), _p(idx), _p(val), _p(mean), _p(std)))
+        return idx, val, mean, std
+
     def scores(self, samples, mode=0):
         """(U, I) mean score (mode 0), mean Phi(score) (mode 1) or mean expected class index (mode 2, with `cutpoints`);
         samples: list of (w0, w[D], V[D, K])"""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        out = np.empty((self.U, self.I))
-        self._ck(lib().mfm_pairs_scores(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, _p(out)))
-        return out
+        return self._scores(_host(samples), mode)
 
     def topk(self, samples, k, mode=0):
         """(indices int64 (U, k), values (U, k)) ordered by (value descending, index ascending); tail -1 / -inf"""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        kk = max(int(k), 1)
-        idx, val = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk))
-        self._ck(lib().mfm_pairs_topk(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, int(k), _p(idx), _p(val)))
-        return idx, val
+        return self._topk(_host(samples), k, mode)
 
     def scores_store(self, store, mode=0, first=0, count=None):
-        count = len(store) - first if count is None else count
-        out = np.empty((self.U, self.I))
-        self._ck(lib().mfm_pairs_scores_store(self.h, store.h, first, count, mode, _p(out)))
-        return out
+        return self._scores(_resident(store, first, count), mode)
 
     def topk_store(self, store, k, mode=0, first=0, count=None):
-        count = len(store) - first if count is None else count
-        kk = max(int(k), 1)
-        idx, val = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk))
-        self._ck(lib().mfm_pairs_topk_store(self.h, store.h, first, count, mode, int(k), _p(idx), _p(val)))
-        return idx, val
+        return self._topk(_resident(store, first, count), k, mode)
 
     # ---- the moments form (DESIGN 4.13.1): mean and population std over the samples of the per-sample value
     def moments(self, samples, mode=0):
         """(mean (U, I), std (U, I)) of the per-sample value of every pair"""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        mean, std = np.empty((self.U, self.I)), np.empty((self.U, self.I))
-        self._ck(lib().mfm_pairs_moments(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, _p(mean), _p(std)))
-        return mean, std
+        return self._moments(_host(samples), mode)
 
     def moments_store(self, store, mode=0, first=0, count=None):
-        count = len(store) - first if count is None else count
-        mean, std = np.empty((self.U, self.I)), np.empty((self.U, self.I))
-        self._ck(lib().mfm_pairs_moments_store(self.h, store.h, first, count, mode, _p(mean), _p(std)))
-        return mean, std
-
-    def _ucb_out(self, k):
-        kk = max(int(k), 1)
-        return np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk)), np.empty((self.U, kk)), np.empty((self.U, kk))
+        return self._moments(_resident(store, first, count), mode)
 
     def topk_ucb(self, samples, k, beta=1.0, mode=0):
         """(indices int64 (U, k), value, mean, std (U, k)) ranked by value = mean + beta * std under (value descending, index
         ascending). mean and std are recomputed for the selected pairs in another association than the selecting kernel's:
         value equals mean + beta * std within rounding, not bit for bit. Tail: -1 / -inf / NaN / NaN."""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        idx, val, mean, std = self._ucb_out(k)
-        self._ck(lib().mfm_pairs_topk_ucb(self.h, K, S, _p(w0s), _p(ws), _p(Vs), mode, int(k), float(beta), _p(idx), _p(val),
-                                          _p(mean), _p(std)))
-        return idx, val, mean, std
+        return self._topk_ucb(_host(samples), k, beta, mode)
 
     def topk_ucb_store(self, store, k, beta=1.0, mode=0, first=0, count=None):
-        count = len(store) - first if count is None else count
-        idx, val, mean, std = self._ucb_out(k)
-        self._ck(lib().mfm_pairs_topk_ucb_store(self.h, store.h, first, count, mode, int(k), float(beta), _p(idx), _p(val),
-                                                _p(mean), _p(std)))
-        return idx, val, mean, std
+        return self._topk_ucb(_resident(store, first, count), k, beta, mode)
 
 
 def group_by_entity(X, y, entity, n_entities):
@@ -902,54 +898,41 @@ class FoldIn:
             raise ValueError("alpha must have shape (S,), mu and lam (S, K + 1)")
         return alpha, mu, lam
 
-    def solve(self, samples, alpha, mu, lam, draw=False, seed=0):
-        """(w_new (S, U), V_new (S, U, K)) under host samples, a list of (w0, w[D], V[D, K]); alpha (S,), mu / lam (S, K + 1)"""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        alpha, mu, lam = self._hypers(S, K, alpha, mu, lam)
-        w_new, V_new = np.empty((S, self.U)), np.empty((S, self.U, K))
-        self._ck(lib().mfm_foldin_solve(self.h, K, S, _p(w0s), _p(ws), _p(Vs), _p(alpha), _p(mu), _p(lam), int(bool(draw)),
-                                        int(seed), _p(w_new), _p(V_new)))
+    # each operation once, over a sample source (_host / _resident)
+    def _solve(self, src, alpha, mu, lam, draw, seed):
+        alpha, mu, lam = self._hypers(src.S, src.K, alpha, mu, lam)
+        w_new, V_new = np.empty((src.S, self.U)), np.empty((src.S, self.U, src.K))
+        self._ck(src.call("mfm_foldin_solve", self.h, _p(alpha), _p(mu), _p(lam), int(bool(draw)), int(seed), _p(w_new), _p(V_new)))
         return w_new, V_new
 
+    def solve(self, samples, alpha, mu, lam, draw=False, seed=0):
+        """(w_new (S, U), V_new (S, U, K)) under host samples, a list of (w0, w[D], V[D, K]); alpha (S,), mu / lam (S, K + 1)"""
+        return self._solve(_host(samples), alpha, mu, lam, draw, seed)
+
     def solve_store(self, store, alpha, mu, lam, draw=False, seed=0, first=0, count=None):
-        count = len(store) - first if count is None else count
-        alpha, mu, lam = self._hypers(count, store.K, alpha, mu, lam)
-        w_new, V_new = np.empty((count, self.U)), np.empty((count, self.U, store.K))
-        self._ck(lib().mfm_foldin_solve_store(self.h, store.h, first, count, _p(alpha), _p(mu), _p(lam), int(bool(draw)), int(seed),
-                                              _p(w_new), _p(V_new)))
-        return w_new, V_new
+        return self._solve(_resident(store, first, count), alpha, mu, lam, draw, seed)
 
     FOLDIN_TASKS = {"classifier": 0, "ordered": 1}
 
-    @classmethod
-    def _gibbs_args(cls, S, K, mu, lam, task, cutpoints):
-        """(task code, n_class, cutpoints (S, n_class - 1) or None, mu, lam) of a solve_gibbs* call"""
-        _, mu, lam = cls._hypers(S, K, np.ones(S), mu, lam)
-        if task not in cls.FOLDIN_TASKS:
+    def _solve_gibbs(self, src, mu, lam, task, cutpoints, n_burn, n_inner, draw, seed):
+        _, mu, lam = self._hypers(src.S, src.K, np.ones(src.S), mu, lam)
+        if task not in self.FOLDIN_TASKS:
             raise ValueError("task must be 'classifier' or 'ordered'")
-        if task == "classifier":
-            return 0, 0, None, mu, lam
-        cut = _f64(cutpoints)
-        if cut.ndim != 2 or cut.shape[0] != S or cut.shape[1] < 1:
-            raise ValueError("cutpoints must have shape (S, n_class - 1)")
-        return 1, cut.shape[1] + 1, cut, mu, lam
+        n_class, cut = 0, None
+        if task == "ordered":
+            cut = _f64(cutpoints)
+            if cut.ndim != 2 or cut.shape[0] != src.S or cut.shape[1] < 1:
+                raise ValueError("cutpoints must have shape (S, n_class - 1)")
+            n_class = cut.shape[1] + 1
+        w_new, V_new = np.empty((src.S, self.U)), np.empty((src.S, self.U, src.K))
+        self._ck(src.call("mfm_foldin_gibbs_solve", self.h, self.FOLDIN_TASKS[task], n_class, _p(cut), _p(mu), _p(lam), int(n_burn),
+                          int(n_inner), int(bool(draw)), int(seed), _p(w_new), _p(V_new)))
+        return w_new, V_new
 
     def solve_gibbs(self, samples, mu, lam, task, cutpoints=None, n_burn=10, n_inner=40, draw=False, seed=0):
         """(w_new (S, U), V_new (S, U, K)) of a probit model under host samples by the inner chain (mfm_foldin_gibbs_solve): task
         'classifier' (the handle's y is +-1) or 'ordered' (class indices; cutpoints (S, n_class - 1)); mu / lam (S, K + 1)"""
-        K, S, w0s, ws, Vs = _pack_samples(samples)
-        code, n_class, cut, mu, lam = self._gibbs_args(S, K, mu, lam, task, cutpoints)
-        w_new, V_new = np.empty((S, self.U)), np.empty((S, self.U, K))
-        self._ck(lib().mfm_foldin_gibbs_solve(self.h, K, S, _p(w0s), _p(ws), _p(Vs), code, n_class, _p(cut),
-                                              _p(mu), _p(lam), int(n_burn), int(n_inner), int(bool(draw)), int(seed), _p(w_new),
-                                              _p(V_new)))
-        return w_new, V_new
+        return self._solve_gibbs(_host(samples), mu, lam, task, cutpoints, n_burn, n_inner, draw, seed)
 
     def solve_gibbs_store(self, store, mu, lam, task, cutpoints=None, n_burn=10, n_inner=40, draw=False, seed=0, first=0, count=None):
-        count = len(store) - first if count is None else count
-        code, n_class, cut, mu, lam = self._gibbs_args(count, store.K, mu, lam, task, cutpoints)
-        w_new, V_new = np.empty((count, self.U)), np.empty((count, self.U, store.K))
-        self._ck(lib().mfm_foldin_gibbs_solve_store(self.h, store.h, first, count, code, n_class, _p(cut),
-                                                    _p(mu), _p(lam), int(n_burn), int(n_inner), int(bool(draw)), int(seed),
-                                                    _p(w_new), _p(V_new)))
-        return w_new, V_new
+        return self._solve_gibbs(_resident(store, first, count), mu, lam, task, cutpoints, n_burn, n_inner, draw, seed)

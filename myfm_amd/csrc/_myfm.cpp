@@ -28,6 +28,8 @@
 #include <sstream>
 #include <stdexcept>
 #include <string>
+#include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "mfm_env.hpp"
@@ -364,7 +366,9 @@ struct DeviceDesign {
   }
   void predict(int rank, int S, const double *w0s, const double *ws, const double *Vs, int mode, int n_cut,
                const double *cuts, double *out) {
-    int code = mfm_design_predict(d, rank, S, w0s, ws, Vs, mode, n_cut, cuts, out);
+    ck(mfm_design_predict(d, rank, S, w0s, ws, Vs, mode, n_cut, cuts, out));
+  }
+  void ck(int code) const {
     if (code != MFM_OK) throw_code(code, mfm_design_last_error(d));
   }
 };
@@ -395,6 +399,7 @@ struct DevicePairs {
     if (p) mfm_pairs_destroy(p);
   }
   DevicePairs(const DevicePairs &) = delete;
+  DevicePairs(DevicePairs &&o) : p(o.p) { o.p = nullptr; }
   // the blocks of one side (0 query, 1 candidates) at the column offsets of their positions; null entries hold nothing
   void add_blocks(int side, const Relations &rels, const vector<size_t> &offsets) {
     for (size_t i = 0; i < rels.size(); i++) {
@@ -598,26 +603,44 @@ struct Predictor {
       if (samples[k].store != st || samples[k].store_idx != *first + (int)k) return nullptr;
     return st;
   }
-  // Where a call's samples come from, decided once for every device predictor: in_store(store, first) reads them in place,
-  // packed(w0s, ws, Vs) gets them packed on the host (a restored or modified predictor). Returns the callee's code.
-  template <class InStore, class Packed>
-  int with_samples(const InStore &in_store, const Packed &packed) const {
+  // Where a call's samples come from, decided once for every device predictor. The C library declares each predictor as a twin
+  // pair, X_store(h, store, first, count, TAIL...) and X(h, rank, n_samples, w0s, ws, Vs, TAIL...): the resident range is read in
+  // place, anything else (a restored or modified predictor) is packed on the host once. Returns the callee's code.
+  template <class H, class... SA, class... HA, class... T>
+  int on_samples(int (*in_store)(H *, mfm_store *, int32_t, int32_t, SA...),
+                 int (*host)(H *, int32_t, int32_t, const double *, const double *, const double *, HA...), H *h, T... tail) const {
+    static_assert(std::is_same<std::tuple<SA...>, std::tuple<HA...>>::value, "a twin pair takes the same arguments after the samples");
+    const int S = (int)samples.size();
     int first = 0;
-    if (auto st = resident(&first)) return in_store(st->st, first);
+    if (auto st = resident(&first)) return in_store(h, st->st, first, S, tail...);
     vector<double> w0s, ws, Vs;
     pack(w0s, ws, Vs);
-    return packed(w0s.data(), ws.data(), Vs.data());
+    return host(h, (int)rank, S, w0s.data(), ws.data(), Vs.data(), tail...);
   }
   // mode / cutpoints as mfm_design_predict
   void run_predict(const Csr &X, const Relations &rels, int mode, int n_cut, const vector<double> &cuts, double *out) const {
     DeviceDesign dd(X, rels);
-    const int S = (int)samples.size();
-    const int code = with_samples(
-        [&](mfm_store *st, int first) { return mfm_design_predict_store(dd.d, st, first, S, mode, n_cut, cuts.data(), out); },
-        [&](const double *w0s, const double *ws, const double *Vs) {
-          return mfm_design_predict(dd.d, (int)rank, S, w0s, ws, Vs, mode, n_cut, cuts.data(), out);
-        });
-    if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
+    dd.ck(on_samples(mfm_design_predict_store, mfm_design_predict, dd.d, mode, n_cut, cuts.data(), out));
+  }
+  // Cutpoint group g of every kept sample, gathered into cuts[S][n_cut]. The callers differ in what they throw, so what is wrong
+  // is reported: bad = 1, sample `at` has no group g (an empty one counts unless allow_empty); bad = 2, its size differs from
+  // sample 0's. The samples are checked in order and the first finding is the one reported.
+  struct Cutpoints {
+    vector<double> cuts;
+    size_t n_cut = 0, at = 0;
+    int bad = 0;
+  };
+  Cutpoints gather_cutpoints(int64_t g, bool allow_empty = false) const {
+    Cutpoints c;
+    for (; c.at < samples.size(); c.at++) {
+      const auto &groups = samples[c.at].cutpoints;
+      const vector<Real> *group = g >= 0 && (size_t)g < groups.size() ? &groups[(size_t)g] : nullptr;
+      if (c.at == 0 && group) c.n_cut = group->size();
+      c.bad = !group || (group->empty() && !allow_empty) ? 1 : group->size() != c.n_cut ? 2 : 0;
+      if (c.bad) break;
+      c.cuts.insert(c.cuts.end(), group->begin(), group->end());
+    }
+    return c;
   }
 
   void check_input(const Csr &X, const Relations &relations) const {  // predictor.hpp:24-33
@@ -745,207 +768,176 @@ struct Predictor {
         for (int32_t j : rc[i]->X.indices)
           if (seen[offsets[i] + (size_t)j])
             throw std::invalid_argument("X_query and X_cand share column " + std::to_string(offsets[i] + (size_t)j));
-    // ordered probit ranks by the expected class index: every sample needs its cutpoints (group 0, as predict_proba)
-    if (type == TaskType::ORDERED && !samples.empty()) {
-      const size_t n_cpt = samples.at(0).cutpoints.empty() ? 0 : samples[0].cutpoints[0].size();
-      if (n_cpt < 1) throw std::runtime_error("No cutpoint available for this FM.");
-      for (auto &sm : samples)
-        if (sm.cutpoints.empty() || sm.cutpoints[0].size() != n_cpt)
-          throw std::runtime_error("inconsistent cutpoint sizes among samples.");
-    }
     return offsets;
   }
-  // idx / score: the top k; dense: all pairs (exactly one of the two forms). std_out != nullptr: the moments form:
-  // dense holds the mean and std_out the std of all pairs, or the top k are ranked by mean + beta * std and mean_out / std_out
-  // hold the selected pairs' moments.
-  void run_pairs(const Csr &Xq, const Csr &Xc, const Relations &rq, const Relations &rc, const vector<size_t> &offsets,
-                 const Csr *exclude, int k, int64_t *idx, double *score, double *dense, double beta = 0.0, double *mean_out = nullptr,
-                 double *std_out = nullptr) const {
-    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
-    DevicePairs dp((int64_t)feature_size, Xq, Xc);
-    dp.add_blocks(0, rq, offsets);
-    dp.add_blocks(1, rc, offsets);
-    if (exclude) dp.ck(mfm_pairs_set_exclude(dp.p, exclude->indptr.data(), exclude->indices.data()));
-    const int mode = type == TaskType::CLASSIFICATION ? 1 : type == TaskType::ORDERED ? 2 : 0;
-    if (mode == 2) {
-      vector<double> cuts;
-      for (auto &sm : samples) cuts.insert(cuts.end(), sm.cutpoints[0].begin(), sm.cutpoints[0].end());
-      dp.ck(mfm_pairs_set_cutpoints(dp.p, (int)samples.size(), (int)samples[0].cutpoints[0].size(), cuts.data()));
+  // What the four pair methods share: the sides as checked by check_pairs, the optional exclusion of a ranked call, and, for
+  // ordered probit, the cutpoints (group 0, as predict_proba) that rank by the expected class index.
+  struct PairCall {
+    Csr Xq, Xc, ex;
+    Relations rq, rc;
+    vector<size_t> offsets;
+    Cutpoints cp;
+    int64_t D;
+    int S, mode;
+    bool excluded = false;
+    py::ssize_t U() const { return (py::ssize_t)Xq.rows; }
+    py::ssize_t I() const { return (py::ssize_t)Xc.rows; }
+    void refuse_every_pair(const char *method, const char *instead) const {
+      if ((double)Xq.rows * (double)Xc.rows > 16777216.0)
+        throw std::invalid_argument(std::string(method) + " returns every pair: more than 2^24 pairs are refused, use " + instead);
     }
-    const int S = (int)samples.size();
-    dp.ck(with_samples(
-        [&](mfm_store *st, int first) {
-          if (std_out)
-            return dense ? mfm_pairs_moments_store(dp.p, st, first, S, mode, dense, std_out)
-                         : mfm_pairs_topk_ucb_store(dp.p, st, first, S, mode, k, beta, idx, score, mean_out, std_out);
-          return dense ? mfm_pairs_scores_store(dp.p, st, first, S, mode, dense) : mfm_pairs_topk_store(dp.p, st, first, S, mode, k, idx, score);
-        },
-        [&](const double *w0s, const double *ws, const double *Vs) {
-          if (std_out)
-            return dense ? mfm_pairs_moments(dp.p, (int)rank, S, w0s, ws, Vs, mode, dense, std_out)
-                         : mfm_pairs_topk_ucb(dp.p, (int)rank, S, w0s, ws, Vs, mode, k, beta, idx, score, mean_out, std_out);
-          return dense ? mfm_pairs_scores(dp.p, (int)rank, S, w0s, ws, Vs, mode, dense)
-                       : mfm_pairs_topk(dp.p, (int)rank, S, w0s, ws, Vs, mode, k, idx, score);
-        }));
-  }
-  // the exclusion pattern of a ranked call (None: an empty one, which the caller does not pass on)
-  static Csr checked_exclude(const py::object &excludeo, const Csr &Xq, const Csr &Xc) {
-    Csr ex;
-    if (excludeo.is_none()) return ex;
-    ex = csr_from_py(excludeo);
-    if (ex.rows != Xq.rows || ex.cols != Xc.rows) throw std::invalid_argument("exclude must have shape (n_queries, n_candidates)");
-    for (int32_t j : ex.indices)
-      if (j < 0 || j >= ex.cols) throw std::invalid_argument("exclude: column index out of range");
-    return ex;
+    // the arguments of a ranked call; the exclusion pattern may be None (an empty one, which open() does not pass on)
+    void ranked(int64_t k, const py::object &excludeo, double beta = 0.0) {
+      if (k < 1 || k > 256) throw std::invalid_argument("k must be in [1, 256]");
+      if (!std::isfinite(beta)) throw std::invalid_argument("beta must be a finite number");
+      if (excludeo.is_none()) return;
+      ex = csr_from_py(excludeo);
+      excluded = true;
+      if (ex.rows != Xq.rows || ex.cols != Xc.rows) throw std::invalid_argument("exclude must have shape (n_queries, n_candidates)");
+      for (int32_t j : ex.indices)
+        if (j < 0 || j >= ex.cols) throw std::invalid_argument("exclude: column index out of range");
+    }
+    // the first device contact: both sides with their blocks, the exclusion and the mode-2 cutpoints
+    DevicePairs open() const {
+      if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
+      DevicePairs dp(D, Xq, Xc);
+      dp.add_blocks(0, rq, offsets);
+      dp.add_blocks(1, rc, offsets);
+      if (excluded) dp.ck(mfm_pairs_set_exclude(dp.p, ex.indptr.data(), ex.indices.data()));
+      if (mode == 2) dp.ck(mfm_pairs_set_cutpoints(dp.p, S, (int)cp.n_cut, cp.cuts.data()));
+      return dp;
+    }
+  };
+  PairCall pair_call(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
+    PairCall pc{csr_from_py(Xqo), csr_from_py(Xco), Csr(), pair_relations_from_py(rqo), pair_relations_from_py(rco)};
+    pc.offsets = check_pairs(pc.Xq, pc.Xc, pc.rq, pc.rc);
+    pc.D = (int64_t)feature_size;
+    pc.S = (int)samples.size();
+    pc.mode = type == TaskType::CLASSIFICATION ? 1 : type == TaskType::ORDERED ? 2 : 0;
+    if (pc.mode == 2 && pc.S > 0) {
+      pc.cp = gather_cutpoints(0);
+      if (pc.cp.bad)
+        throw std::runtime_error(pc.cp.at == 0 ? "No cutpoint available for this FM." : "inconsistent cutpoint sizes among samples.");
+    }
+    return pc;
   }
   py::array_t<double> predict_pairs(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
-    Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
-    Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
-    const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
-    if ((double)Xq.rows * (double)Xc.rows > 16777216.0)
-      throw std::invalid_argument("predict_pairs returns every pair: more than 2^24 pairs are refused, use predict_topk");
-    py::array_t<double> out({(py::ssize_t)Xq.rows, (py::ssize_t)Xc.rows});
-    run_pairs(Xq, Xc, rq, rc, offsets, nullptr, 0, nullptr, nullptr, out.mutable_data());
+    const PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.refuse_every_pair("predict_pairs", "predict_topk");
+    py::array_t<double> out({pc.U(), pc.I()});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_scores_store, mfm_pairs_scores, dp.p, pc.mode, out.mutable_data()));
     return out;
   }
   py::tuple predict_topk(const py::object &Xqo, const py::object &Xco, int64_t k, const py::object &excludeo, const py::object &rqo,
                          const py::object &rco) const {
-    Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
-    Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
-    const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
-    if (k < 1 || k > 256) throw std::invalid_argument("k must be in [1, 256]");
-    const Csr ex = checked_exclude(excludeo, Xq, Xc);
-    py::array_t<int64_t> idx({(py::ssize_t)Xq.rows, (py::ssize_t)k});
-    py::array_t<double> score({(py::ssize_t)Xq.rows, (py::ssize_t)k});
-    run_pairs(Xq, Xc, rq, rc, offsets, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), score.mutable_data(), nullptr);
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.ranked(k, excludeo);
+    py::array_t<int64_t> idx({pc.U(), (py::ssize_t)k});
+    py::array_t<double> score({pc.U(), (py::ssize_t)k});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_topk_store, mfm_pairs_topk, dp.p, pc.mode, (int)k, idx.mutable_data(), score.mutable_data()));
     return py::make_tuple(idx, score);
   }
-  // (mean (U, I), std (U, I)) over the kept samples of the per-sample value of every pair
+  // (mean (U, I), std (U, I)) over the kept samples of the per-sample value of every pair (DESIGN 4.13.1)
   py::tuple predict_pairs_dist(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
-    Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
-    Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
-    const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
-    if ((double)Xq.rows * (double)Xc.rows > 16777216.0)
-      throw std::invalid_argument("predict_pairs_dist returns every pair: more than 2^24 pairs are refused, use predict_topk_ucb");
-    py::array_t<double> mean({(py::ssize_t)Xq.rows, (py::ssize_t)Xc.rows}), sd({(py::ssize_t)Xq.rows, (py::ssize_t)Xc.rows});
-    run_pairs(Xq, Xc, rq, rc, offsets, nullptr, 0, nullptr, nullptr, mean.mutable_data(), 0.0, nullptr, sd.mutable_data());
+    const PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.refuse_every_pair("predict_pairs_dist", "predict_topk_ucb");
+    py::array_t<double> mean({pc.U(), pc.I()}), sd({pc.U(), pc.I()});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_moments_store, mfm_pairs_moments, dp.p, pc.mode, mean.mutable_data(), sd.mutable_data()));
     return py::make_tuple(mean, sd);
   }
   // (indices, value, mean, std), each (U, k): the top k by value = mean + beta * std
   py::tuple predict_topk_ucb(const py::object &Xqo, const py::object &Xco, int64_t k, double beta, const py::object &excludeo,
                              const py::object &rqo, const py::object &rco) const {
-    Csr Xq = csr_from_py(Xqo), Xc = csr_from_py(Xco);
-    Relations rq = pair_relations_from_py(rqo), rc = pair_relations_from_py(rco);
-    const vector<size_t> offsets = check_pairs(Xq, Xc, rq, rc);
-    if (k < 1 || k > 256) throw std::invalid_argument("k must be in [1, 256]");
-    if (!std::isfinite(beta)) throw std::invalid_argument("beta must be a finite number");
-    const Csr ex = checked_exclude(excludeo, Xq, Xc);
-    const py::ssize_t U = (py::ssize_t)Xq.rows;
-    py::array_t<int64_t> idx({U, (py::ssize_t)k});
-    py::array_t<double> value({U, (py::ssize_t)k}), mean({U, (py::ssize_t)k}), sd({U, (py::ssize_t)k});
-    run_pairs(Xq, Xc, rq, rc, offsets, excludeo.is_none() ? nullptr : &ex, (int)k, idx.mutable_data(), value.mutable_data(), nullptr, beta,
-              mean.mutable_data(), sd.mutable_data());
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.ranked(k, excludeo, beta);
+    py::array_t<int64_t> idx({pc.U(), (py::ssize_t)k});
+    py::array_t<double> value({pc.U(), (py::ssize_t)k}), mean({pc.U(), (py::ssize_t)k}), sd({pc.U(), (py::ssize_t)k});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_topk_ucb_store, mfm_pairs_topk_ucb, dp.p, pc.mode, (int)k, beta, idx.mutable_data(), value.mutable_data(),
+                     mean.mutable_data(), sd.mutable_data()));
     return py::make_tuple(idx, value, mean, sd);
   }
   // ---- folding new one-hot entities into the kept samples (not in the reference; include/myfm_hip.h "folding new one-hot features")
-  // X: the context rows GROUPED by entity (offsets (U + 1,)), alpha (S,), mu / lam (S, K + 1). Returns (w_new (S, U), V_new (S, U, K)).
-  py::tuple fold_in_solve(const py::object &Xo, const NpF64 &y, const py::array_t<int64_t, py::array::c_style | py::array::forcecast> &offsets,
-                          bool fit_linear, const NpF64 &alpha, const NpF64 &mu, const NpF64 &lam, bool draw, uint64_t seed) const {
-    Csr X = csr_from_py(Xo);
-    const size_t S = samples.size(), K = rank;
-    if ((size_t)X.cols != feature_size) {
-      std::ostringstream ss;
-      ss << "Told to fold in rows of width " << X.cols << " but this->feature_size is " << feature_size;
-      throw std::invalid_argument(ss.str());
-    }
-    if (y.size() != X.rows) throw std::invalid_argument("X and y have different sizes");
-    if (offsets.size() < 1) throw std::invalid_argument("no entity offsets");
-    if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
-    if ((size_t)alpha.size() != S || (size_t)mu.size() != S * (K + 1) || (size_t)lam.size() != S * (K + 1))
-      throw std::invalid_argument("fold-in: alpha must hold one entry per kept sample, mu and lambda (K + 1) per kept sample");
-    if ((int)K > mfm_foldin_max_rank()) {
-      std::ostringstream ss;
-      ss << "fold_in serves ranks up to " << mfm_foldin_max_rank() << ", this model has rank " << K;
-      throw std::invalid_argument(ss.str());
-    }
-    const int64_t U = (int64_t)offsets.size() - 1;
+  typedef py::array_t<int64_t, py::array::c_style | py::array::forcecast> NpI64;
+  // What the two fold-in methods share, in the order both keep: the checks up to the sample count (the constructor), the rank
+  // limit (check_rank), then the first device contact, the handle, and the two outputs (open). A method's own checks go between.
+  struct FoldInCall {
+    const char *method;
+    const Csr X;
+    const NpF64 &y;
+    const NpI64 &offsets;
+    const size_t S, K;
     mfm_foldin *h = nullptr;
-    int code = mfm_foldin_create(selected_device(), X.cols, X.rows, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), U,
-                                 offsets.data(), fit_linear ? 1 : 0, &h);
-    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(nullptr));
-    std::unique_ptr<mfm_foldin, void (*)(mfm_foldin *)> guard(h, mfm_foldin_destroy);
-    py::array_t<double> w_new({(py::ssize_t)S, (py::ssize_t)U});
-    py::array_t<double> V_new({(py::ssize_t)S, (py::ssize_t)U, (py::ssize_t)K});
-    code = with_samples(
-        [&](mfm_store *st, int first) {
-          return mfm_foldin_solve_store(h, st, first, (int)S, alpha.data(), mu.data(), lam.data(), draw ? 1 : 0, seed, w_new.mutable_data(),
-                                        V_new.mutable_data());
-        },
-        [&](const double *w0s, const double *ws, const double *Vs) {
-          return mfm_foldin_solve(h, (int)K, (int)S, w0s, ws, Vs, alpha.data(), mu.data(), lam.data(), draw ? 1 : 0, seed,
-                                  w_new.mutable_data(), V_new.mutable_data());
-        });
-    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(h));
-    return py::make_tuple(w_new, V_new);
+    py::array_t<double> w_new, V_new;
+    FoldInCall(const Predictor &p, const char *method, Csr X_, const NpF64 &y, const NpI64 &offsets)
+        : method(method), X(std::move(X_)), y(y), offsets(offsets), S(p.samples.size()), K(p.rank) {
+      if ((size_t)X.cols != p.feature_size) {
+        std::ostringstream ss;
+        ss << "Told to fold in rows of width " << X.cols << " but this->feature_size is " << p.feature_size;
+        throw std::invalid_argument(ss.str());
+      }
+      if (y.size() != X.rows) throw std::invalid_argument("X and y have different sizes");
+      if (offsets.size() < 1) throw std::invalid_argument("no entity offsets");
+      if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
+    }
+    FoldInCall(const FoldInCall &) = delete;
+    ~FoldInCall() {
+      if (h) mfm_foldin_destroy(h);
+    }
+    void check_rank() const {
+      if ((int)K > mfm_foldin_max_rank()) {
+        std::ostringstream ss;
+        ss << method << " serves ranks up to " << mfm_foldin_max_rank() << ", this model has rank " << K;
+        throw std::invalid_argument(ss.str());
+      }
+    }
+    void open(bool fit_linear) {
+      const int64_t U = (int64_t)offsets.size() - 1;
+      const int code = mfm_foldin_create(selected_device(), X.cols, X.rows, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), U,
+                                         offsets.data(), fit_linear ? 1 : 0, &h);
+      if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(nullptr));
+      w_new = py::array_t<double>({(py::ssize_t)S, (py::ssize_t)U});
+      V_new = py::array_t<double>({(py::ssize_t)S, (py::ssize_t)U, (py::ssize_t)K});
+    }
+    py::tuple result(int code) const {
+      if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(h));
+      return py::make_tuple(w_new, V_new);
+    }
+  };
+  // X: the context rows GROUPED by entity (offsets (U + 1,)), alpha (S,), mu / lam (S, K + 1). Returns (w_new (S, U), V_new (S, U, K)).
+  py::tuple fold_in_solve(const py::object &Xo, const NpF64 &y, const NpI64 &offsets, bool fit_linear, const NpF64 &alpha, const NpF64 &mu,
+                          const NpF64 &lam, bool draw, uint64_t seed) const {
+    FoldInCall c(*this, "fold_in", csr_from_py(Xo), y, offsets);
+    if ((size_t)alpha.size() != c.S || (size_t)mu.size() != c.S * (c.K + 1) || (size_t)lam.size() != c.S * (c.K + 1))
+      throw std::invalid_argument("fold-in: alpha must hold one entry per kept sample, mu and lambda (K + 1) per kept sample");
+    c.check_rank();
+    c.open(fit_linear);
+    return c.result(on_samples(mfm_foldin_solve_store, mfm_foldin_solve, c.h, alpha.data(), mu.data(), lam.data(), draw ? 1 : 0, seed,
+                               c.w_new.mutable_data(), c.V_new.mutable_data()));
   }
   // the same for the probit tasks (mfm_foldin_gibbs_*): y the labels (+-1, or class indices), the task this predictor's type, the
   // cutpoints those of group `cutpoint_index` of every kept sample; mu / lam (S, K + 1)
-  py::tuple fold_in_gibbs_solve(const py::object &Xo, const NpF64 &y, const py::array_t<int64_t, py::array::c_style | py::array::forcecast> &offsets,
-                                bool fit_linear, const NpF64 &mu, const NpF64 &lam, int64_t cutpoint_index, int n_burn, int n_inner,
-                                bool draw, uint64_t seed) const {
+  py::tuple fold_in_gibbs_solve(const py::object &Xo, const NpF64 &y, const NpI64 &offsets, bool fit_linear, const NpF64 &mu, const NpF64 &lam,
+                                int64_t cutpoint_index, int n_burn, int n_inner, bool draw, uint64_t seed) const {
     Csr X = csr_from_py(Xo);
-    const size_t S = samples.size(), K = rank;
-    if (type != TaskType::CLASSIFICATION && type != TaskType::ORDERED)
-      throw std::invalid_argument("fold_in_gibbs serves the classifier and ordered probit");
-    if ((size_t)X.cols != feature_size) {
-      std::ostringstream ss;
-      ss << "Told to fold in rows of width " << X.cols << " but this->feature_size is " << feature_size;
-      throw std::invalid_argument(ss.str());
-    }
-    if (y.size() != X.rows) throw std::invalid_argument("X and y have different sizes");
-    if (offsets.size() < 1) throw std::invalid_argument("no entity offsets");
-    if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
-    if ((size_t)mu.size() != S * (K + 1) || (size_t)lam.size() != S * (K + 1))
-      throw std::invalid_argument("fold-in: mu and lambda must hold (K + 1) entries per kept sample");
-    if ((int)K > mfm_foldin_max_rank()) {
-      std::ostringstream ss;
-      ss << "fold_in_gibbs serves ranks up to " << mfm_foldin_max_rank() << ", this model has rank " << K;
-      throw std::invalid_argument(ss.str());
-    }
     const bool ordered = type == TaskType::ORDERED;
-    vector<double> cuts;
-    size_t n_cut = 0;
-    if (ordered) {
-      for (auto &sm : samples) {
-        if (cutpoint_index < 0 || (size_t)cutpoint_index >= sm.cutpoints.size() || sm.cutpoints[(size_t)cutpoint_index].empty())
-          throw std::invalid_argument("cutpoint_index out of range: a kept sample has no such cutpoint group");
-        const auto &c = sm.cutpoints[(size_t)cutpoint_index];
-        if (n_cut == 0) n_cut = c.size();
-        if (c.size() != n_cut) throw std::invalid_argument("the kept samples hold different numbers of cutpoints");
-        cuts.insert(cuts.end(), c.begin(), c.end());
-      }
-    }
-    const int64_t U = (int64_t)offsets.size() - 1;
-    mfm_foldin *h = nullptr;
-    int code = mfm_foldin_create(selected_device(), X.cols, X.rows, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), U,
-                                 offsets.data(), fit_linear ? 1 : 0, &h);
-    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(nullptr));
-    std::unique_ptr<mfm_foldin, void (*)(mfm_foldin *)> guard(h, mfm_foldin_destroy);
-    py::array_t<double> w_new({(py::ssize_t)S, (py::ssize_t)U});
-    py::array_t<double> V_new({(py::ssize_t)S, (py::ssize_t)U, (py::ssize_t)K});
-    const int task = ordered ? 1 : 0, n_class = ordered ? (int)n_cut + 1 : 0;
-    const double *cp = ordered ? cuts.data() : nullptr;
-    code = with_samples(
-        [&](mfm_store *st, int first) {
-          return mfm_foldin_gibbs_solve_store(h, st, first, (int)S, task, n_class, cp, mu.data(), lam.data(), n_burn, n_inner, draw ? 1 : 0,
-                                              seed, w_new.mutable_data(), V_new.mutable_data());
-        },
-        [&](const double *w0s, const double *ws, const double *Vs) {
-          return mfm_foldin_gibbs_solve(h, (int)K, (int)S, w0s, ws, Vs, task, n_class, cp, mu.data(), lam.data(), n_burn, n_inner,
-                                        draw ? 1 : 0, seed, w_new.mutable_data(), V_new.mutable_data());
-        });
-    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(h));
-    return py::make_tuple(w_new, V_new);
+    if (type != TaskType::CLASSIFICATION && !ordered) throw std::invalid_argument("fold_in_gibbs serves the classifier and ordered probit");
+    FoldInCall c(*this, "fold_in_gibbs", std::move(X), y, offsets);
+    if ((size_t)mu.size() != c.S * (c.K + 1) || (size_t)lam.size() != c.S * (c.K + 1))
+      throw std::invalid_argument("fold-in: mu and lambda must hold (K + 1) entries per kept sample");
+    c.check_rank();
+    Cutpoints cp;
+    if (ordered) cp = gather_cutpoints(cutpoint_index);
+    if (cp.bad)
+      throw std::invalid_argument(cp.bad == 1 ? "cutpoint_index out of range: a kept sample has no such cutpoint group"
+                                              : "the kept samples hold different numbers of cutpoints");
+    c.open(fit_linear);
+    return c.result(on_samples(mfm_foldin_gibbs_solve_store, mfm_foldin_gibbs_solve, c.h, ordered ? 1 : 0, ordered ? (int)cp.n_cut + 1 : 0,
+                               ordered ? cp.cuts.data() : nullptr, mu.data(), lam.data(), n_burn, n_inner, draw ? 1 : 0, seed,
+                               c.w_new.mutable_data(), c.V_new.mutable_data()));
   }
   // the predictor of feature size D + U whose sample s is this one's sample s with w and V extended by w_new[s], V_new[s] (host
   // samples: the restored-model path of every device predictor)
@@ -987,6 +979,26 @@ struct Predictor {
     }
     return 0.5 * (lo + hi);
   }
+  // The quantile arguments of predict_dist and predict_dist_oprobit: the probabilities, 1-D, at most 32, each in [0, 1] (`open`:
+  // with noise, strictly inside, checked value by value together with the range) ...
+  static vector<double> quantile_probs(const py::object &quantileso, bool open = false) {
+    auto qa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(quantileso);
+    if (!qa || qa.ndim() != 1) throw std::invalid_argument("quantiles must be a 1-D sequence of probabilities");
+    if (qa.shape(0) > 32) throw std::invalid_argument("at most 32 quantiles per call");
+    vector<double> probs(qa.data(), qa.data() + qa.shape(0));
+    for (double p : probs) {
+      if (!(p >= 0.0 && p <= 1.0)) throw std::invalid_argument("quantiles must lie in [0, 1]");
+      if (open && !(p > 0.0 && p < 1.0)) throw std::invalid_argument("with noise the quantiles must lie strictly inside (0, 1)");
+    }
+    return probs;
+  }
+  // ... and, after a method's own checks, the limits of the device passes
+  void check_summary_limits(size_t n_q, int64_t tile_rows, int chunk_samples) const {
+    if (tile_rows < 0 || chunk_samples < 0) throw std::invalid_argument("tile_rows and chunk_samples must be non-negative");
+    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
+    if (n_q > 0 && samples.size() > 4096)
+      throw std::invalid_argument("quantiles are computed over at most 4096 kept samples, this predictor holds " + std::to_string(samples.size()));
+  }
   // (mean[N], std[N], quantiles[Q, N]); precisions: the noise precision alpha_s of every sample (regression), or None.
   // tile_rows / chunk_samples force the device passes' row tile and sample chunk (0: automatic). Every argument is checked here,
   // before the device is looked for.
@@ -996,16 +1008,9 @@ struct Predictor {
     Relations rels = relations_from_py(relso);
     check_input(X, rels);
     if (type == TaskType::ORDERED) throw std::invalid_argument("predict_dist covers regression and classification, not ordered probit");
-    auto qa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(quantileso);
-    if (!qa || qa.ndim() != 1) throw std::invalid_argument("quantiles must be a 1-D sequence of probabilities");
-    const int n_q = (int)qa.shape(0);
-    if (n_q > 32) throw std::invalid_argument("at most 32 quantiles per call");
-    vector<double> probs(qa.data(), qa.data() + n_q), prec, z;
     const bool noise = !precisionso.is_none();
-    for (double p : probs) {
-      if (!(p >= 0.0 && p <= 1.0)) throw std::invalid_argument("quantiles must lie in [0, 1]");
-      if (noise && !(p > 0.0 && p < 1.0)) throw std::invalid_argument("with noise the quantiles must lie strictly inside (0, 1)");
-    }
+    const vector<double> probs = quantile_probs(quantileso, noise);
+    vector<double> prec, z;
     if (noise) {
       if (type != TaskType::REGRESSION) throw std::invalid_argument("noise precisions apply to regression only");
       auto pa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(precisionso);
@@ -1016,25 +1021,13 @@ struct Predictor {
         if (!(a > 0.0) || !std::isfinite(a)) throw std::invalid_argument("precisions must be positive and finite");
       for (double p : probs) z.push_back(std_normal_quantile(p));
     }
-    if (tile_rows < 0 || chunk_samples < 0) throw std::invalid_argument("tile_rows and chunk_samples must be non-negative");
-    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
-    if (n_q > 0 && samples.size() > 4096)
-      throw std::invalid_argument("quantiles are computed over at most 4096 kept samples, this predictor holds " + std::to_string(samples.size()));
+    const int n_q = (int)probs.size();
+    check_summary_limits(probs.size(), tile_rows, chunk_samples);
     py::array_t<double> mean((py::ssize_t)X.rows), sd((py::ssize_t)X.rows), q({(py::ssize_t)n_q, (py::ssize_t)X.rows});
-    const int mode = type == TaskType::CLASSIFICATION ? 1 : 0;
     DeviceDesign dd(X, rels);
-    const int S = (int)samples.size();
-    const double *pr = noise ? prec.data() : nullptr, *zs = noise ? z.data() : nullptr;
-    const int code = with_samples(
-        [&](mfm_store *st, int first) {
-          return mfm_design_summary_store(dd.d, st, first, S, mode, n_q, probs.data(), pr, zs, tile_rows, chunk_samples, mean.mutable_data(),
-                                          sd.mutable_data(), q.mutable_data());
-        },
-        [&](const double *w0s, const double *ws, const double *Vs) {
-          return mfm_design_summary(dd.d, (int)rank, S, w0s, ws, Vs, mode, n_q, probs.data(), pr, zs, tile_rows, chunk_samples,
-                                    mean.mutable_data(), sd.mutable_data(), q.mutable_data());
-        });
-    if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
+    dd.ck(on_samples(mfm_design_summary_store, mfm_design_summary, dd.d, type == TaskType::CLASSIFICATION ? 1 : 0, n_q, probs.data(),
+                     noise ? prec.data() : nullptr, noise ? z.data() : nullptr, tile_rows, chunk_samples, mean.mutable_data(),
+                     sd.mutable_data(), q.mutable_data()));
     return py::make_tuple(mean, sd, q);
   }
   // Ordered probit (not in the reference): the same summaries of the class probabilities p_c(score_s; cutpoints_s) -- (mean[N, C],
@@ -1046,46 +1039,22 @@ struct Predictor {
     Relations rels = relations_from_py(relso);
     check_input(X, rels);
     if (type != TaskType::ORDERED) throw std::invalid_argument("predict_dist_oprobit must be called for oprobit model.");
-    auto qa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(quantileso);
-    if (!qa || qa.ndim() != 1) throw std::invalid_argument("quantiles must be a 1-D sequence of probabilities");
-    const int n_q = (int)qa.shape(0);
-    if (n_q > 32) throw std::invalid_argument("at most 32 quantiles per call");
-    vector<double> probs(qa.data(), qa.data() + n_q);
-    for (double p : probs)
-      if (!(p >= 0.0 && p <= 1.0)) throw std::invalid_argument("quantiles must lie in [0, 1]");
-    if (tile_rows < 0 || chunk_samples < 0) throw std::invalid_argument("tile_rows and chunk_samples must be non-negative");
-    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
-    if (n_q > 0 && samples.size() > 4096)
-      throw std::invalid_argument("quantiles are computed over at most 4096 kept samples, this predictor holds " + std::to_string(samples.size()));
-    const size_t cutpoint_index = (size_t)cutpoint_idx;  // (a negative one is out of range as well)
-    if (cutpoint_idx < 0 || cutpoint_index >= samples[0].cutpoints.size() || samples[0].cutpoints[cutpoint_index].empty())
+    const vector<double> probs = quantile_probs(quantileso);
+    const int n_q = (int)probs.size();
+    check_summary_limits(probs.size(), tile_rows, chunk_samples);
+    const Cutpoints cp = gather_cutpoints(cutpoint_idx);
+    if (cp.bad && cp.at == 0)
       throw std::invalid_argument("cutpoint_index " + std::to_string(cutpoint_idx) + " out of range: the model has " +
                                   std::to_string(samples[0].cutpoints.size()) + " cutpoint group(s)");
-    const int n_cpt = (int)samples[0].cutpoints[cutpoint_index].size();
-    vector<double> cuts;
-    for (auto &s : samples) {
-      if (cutpoint_index >= s.cutpoints.size() || (int)s.cutpoints[cutpoint_index].size() != n_cpt)
-        throw std::invalid_argument("inconsistent cutpoint sizes among samples.");
-      const auto &cp = s.cutpoints[cutpoint_index];
-      cuts.insert(cuts.end(), cp.begin(), cp.end());
-    }
-    const py::ssize_t N = (py::ssize_t)X.rows, C = n_cpt + 1;
+    if (cp.bad) throw std::invalid_argument("inconsistent cutpoint sizes among samples.");
+    const py::ssize_t N = (py::ssize_t)X.rows, C = (py::ssize_t)cp.n_cut + 1;
     const std::vector<py::ssize_t> shape = expected ? std::vector<py::ssize_t>{N} : std::vector<py::ssize_t>{N, C};
     std::vector<py::ssize_t> qshape = shape;
     qshape.insert(qshape.begin(), (py::ssize_t)n_q);
     py::array_t<double> mean(shape), sd(shape), q(qshape);
     DeviceDesign dd(X, rels);
-    const int S = (int)samples.size();
-    const int code = with_samples(
-        [&](mfm_store *st, int first) {
-          return mfm_design_summary_oprobit_store(dd.d, st, first, S, expected ? 1 : 0, n_cpt, cuts.data(), n_q, probs.data(), tile_rows,
-                                                  chunk_samples, mean.mutable_data(), sd.mutable_data(), q.mutable_data());
-        },
-        [&](const double *w0s, const double *ws, const double *Vs) {
-          return mfm_design_summary_oprobit(dd.d, (int)rank, S, w0s, ws, Vs, expected ? 1 : 0, n_cpt, cuts.data(), n_q, probs.data(),
-                                            tile_rows, chunk_samples, mean.mutable_data(), sd.mutable_data(), q.mutable_data());
-        });
-    if (code != MFM_OK) throw_code(code, mfm_design_last_error(dd.d));
+    dd.ck(on_samples(mfm_design_summary_oprobit_store, mfm_design_summary_oprobit, dd.d, expected ? 1 : 0, (int)cp.n_cut, cp.cuts.data(), n_q,
+                     probs.data(), tile_rows, chunk_samples, mean.mutable_data(), sd.mutable_data(), q.mutable_data()));
     return py::make_tuple(mean, sd, q);
   }
   // predictor.hpp:78-124
@@ -1096,15 +1065,11 @@ struct Predictor {
     check_input(X, rels);
     if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
     if (type != TaskType::ORDERED) throw std::runtime_error("predict_parallel_oprobit must be called for oprobit model.");
-    int n_cpt = (int)samples.at(0).cutpoints.at(cutpoint_index).size();
-    vector<double> cuts;
-    for (auto &s : samples) {
-      const auto &cp = s.cutpoints.at(cutpoint_index);
-      if ((int)cp.size() != n_cpt) throw std::runtime_error("inconsistent cutpoint sizes among samples.");
-      cuts.insert(cuts.end(), cp.begin(), cp.end());
-    }
-    py::array_t<double> out({(py::ssize_t)X.rows, (py::ssize_t)(n_cpt + 1)});
-    run_predict(X, rels, 2, n_cpt, cuts, out.mutable_data());
+    const Cutpoints cp = gather_cutpoints((int64_t)cutpoint_index, true);
+    if (cp.bad == 1) samples[cp.at].cutpoints.at(cutpoint_index);  // (throws what the reference's .at() throws)
+    if (cp.bad) throw std::runtime_error("inconsistent cutpoint sizes among samples.");
+    py::array_t<double> out({(py::ssize_t)X.rows, (py::ssize_t)(cp.n_cut + 1)});
+    run_predict(X, rels, 2, (int)cp.n_cut, cp.cuts, out.mutable_data());
     return out;
   }
 };

@@ -371,6 +371,19 @@ class _PredictiveDistMixin:
         return PredictiveSummary(*predictor.predict_dist(X, list(X_rel), probs, precisions))
 
 
+def _ranked_args(Xq, Xc, k, exclude, beta=0.0):
+    """The checks predict_topk and predict_topk_ucb share, in one order: (k int, beta float, exclude csr or None)."""
+    if isinstance(k, bool) or int(k) != k:
+        raise ValueError("k must be an integer in [1, 256]")
+    if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or not np.isfinite(beta):
+        raise ValueError("beta must be a finite real number")
+    if exclude is not None:
+        exclude = sps.csr_matrix(exclude)
+        if exclude.shape != (Xq.shape[0], Xc.shape[0]):
+            raise ValueError("exclude must have shape (n_queries, n_candidates)")
+    return int(k), float(beta), exclude
+
+
 class _PairScoringMixin:
     """Ranking with a fitted model: scores of every (query row, candidate row) pair and the per-query top-k, computed on the
     device without materialising the pair rows. Regressors score the posterior-mean prediction, classifiers the
@@ -416,13 +429,8 @@ class _PairScoringMixin:
         are pairs to leave out (the stored values are ignored). Where fewer than k candidates remain the tail is index -1,
         score -inf. 1 <= k <= 256, else ValueError."""
         predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
-        if isinstance(k, bool) or int(k) != k:
-            raise ValueError("k must be an integer in [1, 256]")
-        if exclude is not None:
-            exclude = sps.csr_matrix(exclude)
-            if exclude.shape != (Xq.shape[0], Xc.shape[0]):
-                raise ValueError("exclude must have shape (n_queries, n_candidates)")
-        return predictor.predict_topk(Xq, Xc, int(k), exclude, rq, rc)
+        k, _, exclude = _ranked_args(Xq, Xc, k, exclude)
+        return predictor.predict_topk(Xq, Xc, k, exclude, rq, rc)
 
 
 PairSummary = namedtuple("PairSummary", ["mean", "std"])
@@ -454,15 +462,8 @@ class _PairUncertaintyMixin:
         another order, so value equals mean + beta * std within rounding, not bit for bit. Where fewer than k candidates remain
         the tail is index -1, value -inf, mean and std NaN. 1 <= k <= 256 and a finite real beta, else ValueError."""
         predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
-        if isinstance(k, bool) or int(k) != k:
-            raise ValueError("k must be an integer in [1, 256]")
-        if isinstance(beta, bool) or not isinstance(beta, (int, float, np.integer, np.floating)) or not np.isfinite(beta):
-            raise ValueError("beta must be a finite real number")
-        if exclude is not None:
-            exclude = sps.csr_matrix(exclude)
-            if exclude.shape != (Xq.shape[0], Xc.shape[0]):
-                raise ValueError("exclude must have shape (n_queries, n_candidates)")
-        return RankedSummary(*predictor.predict_topk_ucb(Xq, Xc, int(k), float(beta), exclude, rq, rc))
+        k, beta, exclude = _ranked_args(Xq, Xc, k, exclude, beta)
+        return RankedSummary(*predictor.predict_topk_ucb(Xq, Xc, k, beta, exclude, rq, rc))
 
 
 def _fold_in_checked(est, name, X, y, entity, group, n_entities):

@@ -59,6 +59,35 @@ def test_pairs_host_samples_equal_the_store(blocks, K, mode):
     st4.close()
 
 
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("K", [0, 3])
+@pytest.mark.parametrize("blocks", [0, 1])
+def test_pair_moments_host_samples_equal_the_store(blocks, K, mode):
+    """The moments form (mean and std of every pair, the top 10 by mean + 0.7 std) on the shapes of the test above. k = 10 < I
+    and nothing is excluded, so no NaN tail enters the comparison."""
+    from myfm_amd import _capi
+
+    rng = np.random.default_rng(1000 + 100 * blocks + 10 * K + mode)
+    sd = rr.block_sides(rng, 17, 250, 9, 11, blocks, blocks, mean_nnz=2.0)
+    Xq, Xc, rq, rc = rr.capi_args(sd)
+    samples = pr.normal_samples(rng, sd["D"], K, 4)
+    cuts = rr.sorted_cuts(rng, 4, 2) if mode == 2 else None
+
+    def pairs(lo, hi):
+        return _capi.Pairs(Xq, Xc, rel_query=rq, rel_cand=rc, cutpoints=None if cuts is None else cuts[lo:hi])
+
+    P, st3 = pairs(0, 3), store_of(samples[:3])
+    assert same(P.moments(samples[:3], mode), P.moments_store(st3, mode))
+    assert same(P.topk_ucb(samples[:3], 10, beta=0.7, mode=mode), P.topk_ucb_store(st3, 10, beta=0.7, mode=mode))
+    P.close()
+    st3.close()
+    P, st4 = pairs(1, 3), store_of(samples)
+    assert same(P.moments(samples[1:3], mode), P.moments_store(st4, mode, first=1, count=2))
+    assert same(P.topk_ucb(samples[1:3], 10, beta=0.7, mode=mode), P.topk_ucb_store(st4, 10, beta=0.7, mode=mode, first=1, count=2))
+    P.close()
+    st4.close()
+
+
 # ---- summaries and predictions -------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module", params=["flat", "block"])
 def rows257(request):
