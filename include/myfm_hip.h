@@ -475,6 +475,20 @@ int mfm_pairs_topk_ucb_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t
 int mfm_pairs_topk_ucb(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                        int32_t mode, int32_t k, double beta, int64_t *idx, double *value, double *mean, double *std);
 
+/* ---- ranks of given pairs among all candidates (csrc/mfm_pairs_rank.hpp) -----------------------------------------
+ * The same sides, blocks, exclusions, sample views and memory rule. set_targets: a CSR pattern (U, I) of the pairs to rank, the
+ * columns of a row sorted and unique, at most 64 per row, none of them excluded (checked against the exclusions whichever of the
+ * two is set last); a violation is MFM_ERR_INVALID and the message names the query row and the candidate. A null indptr clears.
+ *   rank: for the p-th stored target (u, i), rank_out[p] = the number of candidates j != i of query u that are not excluded and
+ *         beat it under the order of topk (value descending, candidate index ascending) -- other targets of the row count --
+ *         and value_out[p] = the pair's value, bit for bit what scores / topk give for it. Exact and independent of the
+ *         chunking. Without targets or candidates nothing is written and nothing is launched.                              */
+int mfm_pairs_set_targets(mfm_pairs *p, const int64_t *indptr, const int32_t *indices);
+int mfm_pairs_rank_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int64_t *rank_out,
+                         double *value_out);
+int mfm_pairs_rank(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                   int32_t mode, int64_t *rank_out, double *value_out);
+
 /* ---- folding new one-hot features into the kept samples (csrc/mfm_foldin.hip) ----------------------------------
  * U new entities (users or items that were not in the training table), each a new one-hot column with value 1 in its own
  * observations. X (n, D) holds the CONTEXT of the n observations in the model's feature space (not the new column), y their

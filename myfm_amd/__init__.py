@@ -29,6 +29,7 @@ from .estimators import (  # noqa: E402
     MyFMRegressor,
     PairSummary,
     RankedSummary,
+    TargetRanks,
     VariationalFMClassifier,
     VariationalFMRegressor,
 )
@@ -45,4 +46,5 @@ __all__ = [
     "FOLD_IN_MAX_RANK",
     "PairSummary",
     "RankedSummary",
+    "TargetRanks",
 ]

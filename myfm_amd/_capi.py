@@ -41,6 +41,7 @@ SYMBOLS = [
     "mfm_pairs_create", "mfm_pairs_destroy", "mfm_pairs_last_error", "mfm_pairs_set_exclude", "mfm_pairs_set_scratch_bound",
     "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
     "mfm_pairs_set_cutpoints", "mfm_pairs_moments_store", "mfm_pairs_moments", "mfm_pairs_topk_ucb_store", "mfm_pairs_topk_ucb",
+    "mfm_pairs_set_targets", "mfm_pairs_rank_store", "mfm_pairs_rank",
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
@@ -186,6 +187,9 @@ def lib():
     L.mfm_pairs_moments.argtypes = [vp, i32, i32, P, P, P, i32, P, P]
     L.mfm_pairs_topk_ucb_store.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, P, P, P, P]
     L.mfm_pairs_topk_ucb.argtypes = [vp, i32, i32, P, P, P, i32, i32, C.c_double, P, P, P, P]
+    L.mfm_pairs_set_targets.argtypes = [vp, P, P]
+    L.mfm_pairs_rank_store.argtypes = [vp, vp, i32, i32, i32, P, P]
+    L.mfm_pairs_rank.argtypes = [vp, i32, i32, P, P, P, i32, P, P]
     L.mfm_foldin_create.argtypes = [C.c_int, i64, i64, P, P, P, P, i64, P, i32, C.POINTER(vp)]
     L.mfm_foldin_destroy.argtypes = [vp]
     L.mfm_foldin_destroy.restype = None
@@ -739,9 +743,11 @@ class Pairs:
     `rel_cand`: relation blocks of the sides, each entry (col_offset, o2b, csr): side row r additionally holds row o2b[r] of
     `csr` at columns [col_offset, col_offset + csr.shape[1]) of the same D columns (the main matrices keep the model's width
     and leave the blocks' columns empty); applied in list order. `cutpoints`: (S, n_cut) array, the samples' cutpoints for
-    mode 2 (the mean over the samples of the expected class index of the ordered probit)."""
+    mode 2 (the mean over the samples of the expected class index of the ordered probit). `targets`: optional (U, I) sparse
+    pattern of the pairs `rank` ranks, at most 64 per row and none of them excluded."""
 
-    def __init__(self, X_query, X_cand, exclude=None, scratch_bound=None, device=0, rel_query=(), rel_cand=(), cutpoints=None):
+    def __init__(self, X_query, X_cand, exclude=None, scratch_bound=None, device=0, rel_query=(), rel_cand=(), cutpoints=None,
+                 targets=None):
         L = lib()
         h = C.c_void_p()
         Xq, qp, qx, qv = csr_parts(X_query)
@@ -753,6 +759,7 @@ class Pairs:
         if rc:
             _raise(rc, L.mfm_pairs_last_error(None))
         self.h, self.U, self.I, self.D = h, Xq.shape[0], Xc.shape[0], Xq.shape[1]
+        self.n_targets = 0
         if exclude is not None:
             E = sps.csr_matrix(exclude)
             if E.shape != (self.U, self.I):
@@ -774,6 +781,16 @@ class Pairs:
             if cutpoints is not None:
                 cp = _f64(np.atleast_2d(np.asarray(cutpoints, dtype=np.float64)))
                 self._ck(L.mfm_pairs_set_cutpoints(h, cp.shape[0], cp.shape[1], _p(cp)))
+            if targets is not None:
+                T = sps.csr_matrix(targets)
+                if T.shape != (self.U, self.I):
+                    raise ValueError("targets must have shape (n_queries, n_candidates)")
+                if not T.has_sorted_indices:
+                    T = T.sorted_indices()
+                tp = np.ascontiguousarray(T.indptr, dtype=np.int64)
+                tx = np.ascontiguousarray(T.indices, dtype=np.int32)
+                self._ck(L.mfm_pairs_set_targets(h, _p(tp), _p(tx)))
+                self.n_targets = int(tp[-1])
         except Exception:
             self.close()
             raise
@@ -816,6 +833,11 @@ class Pairs:
         self._ck(src.call("mfm_pairs_topk_ucb", self.h, mode, int(k), float(beta), _p(idx), _p(val), _p(mean), _p(std)))
         return idx, val, mean, std
 
+    def _rank(self, src, mode):
+        rank, val = np.empty(self.n_targets, dtype=np.int64), np.empty(self.n_targets)
+        self._ck(src.call("mfm_pairs_rank", self.h, mode, _p(rank), _p(val)))
+        return rank, val
+
     def scores(self, samples, mode=0):
         """(U, I) mean score (mode 0), mean Phi(score) (mode 1) or mean expected class index (mode 2, with `cutpoints`);
         samples: list of (w0, w[D], V[D, K])"""
@@ -847,6 +869,16 @@ class Pairs:
 
     def topk_ucb_store(self, store, k, beta=1.0, mode=0, first=0, count=None):
         return self._topk_ucb(_resident(store, first, count), k, beta, mode)
+
+    # ---- the rank form
+    def rank(self, samples, mode=0):
+        """(rank int64 (nnz,), value (nnz,)) of the handle's `targets`, in the order of targets.indices after sort_indices():
+        rank = the number of non-excluded candidates of the target's query that beat it under (value descending, index
+        ascending), the target itself apart; value = the pair's value, bit for bit that of scores / topk"""
+        return self._rank(_host(samples), mode)
+
+    def rank_store(self, store, mode=0, first=0, count=None):
+        return self._rank(_resident(store, first, count), mode)
 
 
 def group_by_entity(X, y, entity, n_entities):

@@ -780,6 +780,8 @@ struct Predictor {
     int64_t D;
     int S, mode;
     bool excluded = false;
+    Csr tg;  // the targets of a rank call
+    bool targeted = false;
     py::ssize_t U() const { return (py::ssize_t)Xq.rows; }
     py::ssize_t I() const { return (py::ssize_t)Xc.rows; }
     void refuse_every_pair(const char *method, const char *instead) const {
@@ -797,6 +799,31 @@ struct Predictor {
       for (int32_t j : ex.indices)
         if (j < 0 || j >= ex.cols) throw std::invalid_argument("exclude: column index out of range");
     }
+    // the arguments of a rank call: the target pattern (columns sorted and unique within a row, at most 64 per row, none of them
+    // excluded) and the optional exclusion pattern
+    void ranks(const py::object &targetso, const py::object &excludeo) {
+      ranked(1, excludeo);
+      tg = csr_from_py(targetso);
+      targeted = true;
+      if (tg.rows != Xq.rows || tg.cols != Xc.rows) throw std::invalid_argument("targets must have shape (n_queries, n_candidates)");
+      vector<int32_t> row;
+      for (int64_t u = 0; u < tg.rows; u++) {
+        const int64_t b = tg.indptr[u], e = tg.indptr[u + 1];
+        if (e - b > 64)
+          throw std::invalid_argument("targets: query row " + std::to_string(u) + " has " + std::to_string(e - b) +
+                                      " targets, a call takes at most 64 per row");
+        for (int64_t q = b; q < e; q++) {
+          if (tg.indices[q] < 0 || tg.indices[q] >= tg.cols) throw std::invalid_argument("targets: column index out of range");
+          if (q > b && tg.indices[q] <= tg.indices[q - 1])
+            throw std::invalid_argument("targets: the candidates of query row " + std::to_string(u) + " must be sorted and unique");
+        }
+        if (!excluded || b == e) continue;
+        for (int64_t q = ex.indptr[u]; q < ex.indptr[u + 1]; q++)
+          if (std::binary_search(tg.indices.begin() + b, tg.indices.begin() + e, ex.indices[q]))
+            throw std::invalid_argument("targets: the pair (query row " + std::to_string(u) + ", candidate " + std::to_string(ex.indices[q]) +
+                                        ") is also excluded");
+      }
+    }
     // the first device contact: both sides with their blocks, the exclusion and the mode-2 cutpoints
     DevicePairs open() const {
       if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
@@ -805,6 +832,7 @@ struct Predictor {
       dp.add_blocks(1, rc, offsets);
       if (excluded) dp.ck(mfm_pairs_set_exclude(dp.p, ex.indptr.data(), ex.indices.data()));
       if (mode == 2) dp.ck(mfm_pairs_set_cutpoints(dp.p, S, (int)cp.n_cut, cp.cuts.data()));
+      if (targeted) dp.ck(mfm_pairs_set_targets(dp.p, tg.indptr.data(), tg.indices.data()));
       return dp;
     }
   };
@@ -859,6 +887,17 @@ struct Predictor {
     dp.ck(on_samples(mfm_pairs_topk_ucb_store, mfm_pairs_topk_ucb, dp.p, pc.mode, (int)k, beta, idx.mutable_data(), value.mutable_data(),
                      mean.mutable_data(), sd.mutable_data()));
     return py::make_tuple(idx, value, mean, sd);
+  }
+  // (rank int64 (nnz,), value (nnz,)) of the stored positions of `targets`, in CSR order
+  py::tuple predict_rank(const py::object &Xqo, const py::object &Xco, const py::object &targetso, const py::object &excludeo,
+                         const py::object &rqo, const py::object &rco) const {
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.ranks(targetso, excludeo);
+    py::array_t<int64_t> rank_out((py::ssize_t)pc.tg.nnz());
+    py::array_t<double> value((py::ssize_t)pc.tg.nnz());
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_rank_store, mfm_pairs_rank, dp.p, pc.mode, rank_out.mutable_data(), value.mutable_data()));
+    return py::make_tuple(rank_out, value);
   }
   // ---- folding new one-hot entities into the kept samples (not in the reference; include/myfm_hip.h "folding new one-hot features")
   typedef py::array_t<int64_t, py::array::c_style | py::array::forcecast> NpI64;
@@ -2339,6 +2378,10 @@ struct VPredictor {
                          const py::object &rc) const {
     return mean_predictor().predict_topk(Xq, Xc, k, exclude, rq, rc);
   }
+  py::tuple predict_rank(const py::object &Xq, const py::object &Xc, const py::object &targets, const py::object &exclude,
+                         const py::object &rq, const py::object &rc) const {
+    return mean_predictor().predict_rank(Xq, Xc, targets, exclude, rq, rc);
+  }
 };
 
 struct VFMTrainer {
@@ -2834,6 +2877,8 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk", &Predictor::predict_topk, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_rank", &Predictor::predict_rank, py::arg("X_query"), py::arg("X_cand"), py::arg("targets"), py::arg("exclude") = py::none(),
+           py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_pairs_dist", &Predictor::predict_pairs_dist, py::arg("X_query"), py::arg("X_cand"),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk_ucb", &Predictor::predict_topk_ucb, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("beta") = 1.0,
@@ -3032,6 +3077,8 @@ PYBIND11_MODULE(_myfm, m) {
       .def("predict_pairs", &VPredictor::predict_pairs, py::arg("X_query"), py::arg("X_cand"), py::arg("X_rel_query") = py::tuple(),
            py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk", &VPredictor::predict_topk, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("exclude") = py::none(),
+           py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_rank", &VPredictor::predict_rank, py::arg("X_query"), py::arg("X_cand"), py::arg("targets"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def(py::pickle(
           [](const VPredictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },

@@ -16,10 +16,16 @@
 // Moments (mfm_pairs_moments*, mfm_pairs_topk_ucb*; kernels: mfm_pairs_ucb.hpp). The same call with the spread over
 // the samples kept: k_pairs_tile_moments in place of k_pairs_tile, ranking by mean + beta * std, and after each chunk's merge
 // k_pairs_moments_at for mean and std of the selected pairs. A call without them launches what it launched before.
+//
+// Ranks (mfm_pairs_set_targets, mfm_pairs_rank*; kernels: mfm_pairs_rank.hpp). Per query chunk two launches of
+// k_pairs_tile_rank: the values at the chunk's targets, then the count of the admissible candidates that beat each of them. A chunk
+// without targets launches nothing; a call without targets or candidates touches no device memory.
 #include "mfm_pairs.hpp"
+#include "mfm_pairs_rank.hpp"
 #include "mfm_pairs_ucb.hpp"
 #include "mfm_samples.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <memory>
 
@@ -45,7 +51,14 @@ struct mfm_pairs {
   std::vector<double> cut;         // [cut_S][n_cut], the samples' cutpoints (mode 2)
   int cut_S = 0, n_cut = 0;
   std::vector<int64_t> e_ptr_host;  // (the exclusions of a chunk are counted on the host)
+  std::vector<int32_t> e_idx_host;  // (and compared with the targets there)
   bool has_exclude = false;
+  // the targets of the rank form: CSR pattern (U, I), columns sorted and unique within a row
+  DevBuf<int64_t> t_ptr;
+  DevBuf<int32_t> t_idx;
+  std::vector<int64_t> t_ptr_host;
+  std::vector<int32_t> t_idx_host;
+  bool has_targets = false;
   int64_t scratch_bound = (int64_t)256 << 20;
   ~mfm_pairs() {
     if (stream) (void)hipStreamDestroy(stream);
@@ -178,10 +191,51 @@ struct PairsMoments {
   double *mean = nullptr, *sd = nullptr;
 };
 
+// ---- the rank form (mfm_pairs_rank.hpp): one tile shape, 64 rows x 128 candidates per step
+template <int MODE, bool COUNT>
+void launch_rank_t(hipStream_t s, dim3 grid, const PairsArgs &a) {
+  const size_t lds = PairsRankLds<COUNT>::BYTES;
+  static DeviceOnce raised;
+  if (lds > 48 * 1024 && raised.need()) {
+    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_pairs_tile_rank<4, 2, MODE, COUNT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised.mark();
+  }
+  hipLaunchKernelGGL((k_pairs_tile_rank<4, 2, MODE, COUNT>), grid, dim3(PAIRS_WG), lds, s, a);
+}
+
+template <bool COUNT>
+void launch_rank(hipStream_t s, dim3 grid, const PairsArgs &a, int mode) {
+  if (mode == 0)
+    launch_rank_t<0, COUNT>(s, grid, a);
+  else if (mode == 1)
+    launch_rank_t<1, COUNT>(s, grid, a);
+  else
+    launch_rank_t<2, COUNT>(s, grid, a);
+}
+
+// the outputs of a rank call, one entry per stored target in CSR order
+struct PairsRank {
+  int64_t *rank = nullptr;
+  double *value = nullptr;
+};
+
+// a target that is also excluded has no rank: refused when the second of the two patterns arrives
+void check_targets_not_excluded(const mfm_pairs *p) {
+  if (!p->has_targets || !p->has_exclude) return;
+  for (int64_t u = 0; u < p->U; u++) {
+    const int32_t *tb = p->t_idx_host.data() + p->t_ptr_host[u], *te = p->t_idx_host.data() + p->t_ptr_host[u + 1];
+    if (tb == te) continue;
+    for (int64_t q = p->e_ptr_host[u]; q < p->e_ptr_host[u + 1]; q++)
+      if (std::binary_search(tb, te, p->e_idx_host[(size_t)q]))
+        throw Error(MFM_ERR_INVALID, "targets: the pair (query row " + std::to_string(u) + ", candidate " +
+                                         std::to_string(p->e_idx_host[(size_t)q]) + ") is also excluded");
+  }
+}
+
 // The whole call over the samples of `v` (mfm_samples.hpp). dense != nullptr: (U, I) scores; else the top k. mo != nullptr: the
-// moments form.
+// moments form. rk != nullptr: the rank form (neither dense nor k).
 void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx, double *score, double *dense,
-               const PairsMoments *mo = nullptr) {
+               const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr) {
   const int S = v.count(), rank = v.K;
   if (v.device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
   if (v.D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
@@ -196,9 +250,10 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
       throw Error(MFM_ERR_INVALID, "mode 2: cutpoints were set for " + std::to_string(p->cut_S) + " samples, the call has " + std::to_string(S));
   }
   const bool is_dense = dense != nullptr;
-  if (!is_dense && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  if (!is_dense && !rk && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
   const int64_t U = p->U, I = p->I, D = p->D;
   if (U == 0 || (is_dense && I == 0)) return;
+  if (rk && (I == 0 || !p->has_targets)) return;
   hipStream_t s = p->stream;
   const int K = rank, KS = (K + 3) & ~3, KS4 = KS / 4;
   const int64_t NK = (int64_t)S * KS4;
@@ -229,11 +284,13 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     }
   }
   const int64_t W = (I + 31) / 32;
-  const int rows_t = mo ? moments_rows(is_dense, k) : tile_rows(is_dense, k);
-  const int step = mo ? moments_step(is_dense, k) : tile_step(is_dense, k);
+  const int rows_t = rk ? PAIRS_RANK_ROWS : mo ? moments_rows(is_dense, k) : tile_rows(is_dense, k);
+  const int step = rk ? 128 : mo ? moments_step(is_dense, k) : tile_step(is_dense, k);
   const int64_t steps_total = (std::max<int64_t>(I, 1) + step - 1) / step;
   const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && !is_dense ? (double)W * 4 : 0.0) +
-                         (is_dense ? (double)I * 8 : (double)(PAIRS_MAX_STRIPES + 1) * k * 12) +
+                         (is_dense ? (double)I * 8
+                          : rk     ? (double)PAIRS_RANK_MAX_T * 12  // (the targets' values and ranks)
+                                   : (double)(PAIRS_MAX_STRIPES + 1) * k * 12) +
                          (!mo ? 0.0 : is_dense ? (double)I * 8 : (double)k * 16);  // (the second dense output / mean and std of the lists)
   int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
   chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
@@ -301,9 +358,13 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   DevBuf<double> Pf, Ab, Asum, list_v, out_v, d_dense, d_dense_std, out_m, out_s;
   DevBuf<int32_t> list_i, out_i;
   DevBuf<uint32_t> mask;
+  DevBuf<int32_t> t_rank;
+  DevBuf<double> t_val;
   std::vector<int32_t> h_idx;
   for (int64_t u0 = 0; u0 < U; u0 += chunk) {
     const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
+    const int64_t tbase = rk ? p->t_ptr_host[u0] : 0, n_t = rk ? p->t_ptr_host[u0 + Uc] - tbase : 0;
+    if (rk && n_t == 0) continue;
     ensure(Pf, (size_t)(Upad * NK * 4));
     ensure(Ab, (size_t)(Upad * S));
     ensure(Asum, (size_t)Upad);
@@ -348,6 +409,32 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     a.dense = nullptr;
     a.dense_std = nullptr;
     a.beta = mo ? mo->beta : 0.0;
+    a.tptr = nullptr;
+    a.tidx = nullptr;
+    a.tval = nullptr;
+    a.trank = nullptr;
+    a.u0 = u0;
+    a.tbase = tbase;
+    if (rk) {
+      ensure(t_val, (size_t)n_t);
+      ensure(t_rank, (size_t)n_t);
+      a.tptr = p->t_ptr.p;
+      a.tidx = p->t_idx.p;
+      a.tval = t_val.p;
+      a.trank = t_rank.p;
+      MFM_HIP_CHECK(hipMemsetAsync(t_rank.p, 0, (size_t)n_t * sizeof(int32_t), s));
+      const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
+      launch_rank<false>(s, grid, a, mode);
+      MFM_HIP_CHECK(hipGetLastError());
+      launch_rank<true>(s, grid, a, mode);
+      MFM_HIP_CHECK(hipGetLastError());
+      h_idx.resize((size_t)n_t);
+      MFM_HIP_CHECK(hipMemcpyAsync(rk->value + tbase, t_val.p, (size_t)n_t * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), t_rank.p, (size_t)n_t * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipStreamSynchronize(s));
+      for (int64_t e = 0; e < n_t; e++) rk->rank[tbase + e] = h_idx[(size_t)e];
+      continue;
+    }
     if (is_dense) {
       ensure(d_dense, (size_t)(Uc * I));
       a.dense = d_dense.p;
@@ -400,14 +487,23 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
 }
 
 void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense,
-                     const PairsMoments *mo = nullptr) {
+                     const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr) {
   if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo);
+  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo, rk);
 }
 
 void run_pairs_host(mfm_pairs *p, int rank, int n_samples, const double *w0s, const double *ws, const double *Vs, int mode, int k,
-                    int64_t *idx, double *score, double *dense, const PairsMoments *mo = nullptr) {
-  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo);
+                    int64_t *idx, double *score, double *dense, const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr) {
+  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo, rk);
+}
+
+// the outputs of a rank call: none is needed while no target is stored
+PairsRank checked_rank(const mfm_pairs *p, int64_t *rank_out, double *value_out) {
+  if (p->has_targets && (!rank_out || !value_out)) throw Error(MFM_ERR_INVALID, "no output array");
+  PairsRank rk;
+  rk.rank = rank_out;
+  rk.value = value_out;
+  return rk;
 }
 
 // the checks of the ranked moments calls that need neither samples nor a device
@@ -487,9 +583,46 @@ int mfm_pairs_set_exclude(mfm_pairs *p, const int64_t *indptr, const int32_t *in
   }
   check_csr(p->U, p->I, indptr, indices, "exclude");
   p->e_ptr_host.assign(indptr, indptr + p->U + 1);
+  p->e_idx_host.assign(indices, indices + indptr[p->U]);
+  p->has_exclude = indptr[p->U] > 0;
+  try {
+    check_targets_not_excluded(p);
+  } catch (...) {
+    p->has_exclude = false;
+    throw;
+  }
   p->e_ptr.upload(indptr, (size_t)p->U + 1);
   p->e_idx.upload(indices, (size_t)indptr[p->U]);
-  p->has_exclude = indptr[p->U] > 0;
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_set_targets(mfm_pairs *p, const int64_t *indptr, const int32_t *indices) {
+  PAIRS_TRY(p)
+  if (!indptr) {
+    p->has_targets = false;
+    return MFM_OK;
+  }
+  check_csr(p->U, p->I, indptr, indices, "targets");
+  for (int64_t u = 0; u < p->U; u++) {
+    if (indptr[u + 1] - indptr[u] > PAIRS_RANK_MAX_T)
+      throw Error(MFM_ERR_INVALID, "targets: query row " + std::to_string(u) + " has " + std::to_string(indptr[u + 1] - indptr[u]) +
+                                       " targets, a call takes at most " + std::to_string(PAIRS_RANK_MAX_T) + " per row");
+    for (int64_t q = indptr[u] + 1; q < indptr[u + 1]; q++)
+      if (indices[q] <= indices[q - 1])
+        throw Error(MFM_ERR_INVALID, "targets: the candidates of query row " + std::to_string(u) + " must be sorted and unique (candidate " +
+                                         std::to_string(indices[q]) + " follows " + std::to_string(indices[q - 1]) + ")");
+  }
+  p->t_ptr_host.assign(indptr, indptr + p->U + 1);
+  p->t_idx_host.assign(indices, indices + indptr[p->U]);
+  p->has_targets = indptr[p->U] > 0;
+  try {
+    check_targets_not_excluded(p);
+  } catch (...) {
+    p->has_targets = false;
+    throw;
+  }
+  p->t_ptr.upload(indptr, (size_t)p->U + 1);
+  p->t_idx.upload(indices, (size_t)indptr[p->U]);
   PAIRS_CATCH(p)
 }
 
@@ -615,6 +748,21 @@ int mfm_pairs_topk_ucb(mfm_pairs *p, int32_t rank, int32_t n_samples, const doub
   PAIRS_TRY(p)
   const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
   run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, idx, value, nullptr, &mo);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_rank_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int64_t *rank_out, double *value_out) {
+  PAIRS_TRY(p)
+  const PairsRank rk = checked_rank(p, rank_out, value_out);
+  run_pairs_store(p, st, first, count, mode, 0, nullptr, nullptr, nullptr, nullptr, &rk);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_rank(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t mode,
+                   int64_t *rank_out, double *value_out) {
+  PAIRS_TRY(p)
+  const PairsRank rk = checked_rank(p, rank_out, value_out);
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, 0, nullptr, nullptr, nullptr, nullptr, &rk);
   PAIRS_CATCH(p)
 }
 

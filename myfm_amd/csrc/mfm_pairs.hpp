@@ -206,6 +206,11 @@ struct PairsArgs {
   int n_cut;                                //  offsets are what they were)
   double *dense_std;                        // [Uc][I]: the moments form's second dense output (mfm_pairs_ucb.hpp; dense holds the mean)
   double beta;                              // the moments form ranks by mean + beta * std (last, for the same reason)
+  const int64_t *tptr;                      // the rank form's targets (mfm_pairs_rank.hpp): CSR over ALL query rows, indexed u0 + row
+  const int32_t *tidx;
+  double *tval;                             // [the chunk's targets]: entry tptr[u0 + row] - tbase + t, the target's value
+  int32_t *trank;                           // [the chunk's targets]: its rank, zeroed per chunk
+  int64_t u0, tbase;                        // the chunk's first query row and tptr[u0]
 };
 
 // LDS of the selecting kernel: per query row a buffer of CAP candidates that survived the row's threshold, its fill count and

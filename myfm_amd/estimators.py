@@ -432,7 +432,60 @@ class _PairScoringMixin:
         k, _, exclude = _ranked_args(Xq, Xc, k, exclude)
         return predictor.predict_topk(Xq, Xc, k, exclude, rq, rc)
 
+    def predict_rank(self, X_query, X_cand, targets, exclude=None, X_rel_query=[], X_rel_cand=[]):
+        """Where given pairs land in the ranking of all candidates of their query, computed on the device without the (U, I)
+        matrix: the held-out evaluation of a recommender, with `targets` the held-out pairs and `exclude` the
+        training pairs. `targets`: (U, I) scipy sparse pattern (stored values are ignored, stored zeros count); `exclude` as in
+        predict_topk. Returns TargetRanks(rank int64 (nnz,), value float64 (nnz,), n_candidates int64 (U,)), rank and value in
+        the order of the stored positions of `targets` as CSR with sorted indices:
 
+        rank[p]: the number of non-excluded candidates of the pair's query that beat it under predict_topk's order (value
+        descending, candidate index ascending). Other targets of the same row count, the target itself does not: rank 0 is the
+        head of the predict_topk list. value[p]: the pair's value, bit for bit that of predict_pairs / predict_topk.
+        n_candidates[u] = I - the number of excluded candidates of row u. myfm_amd.utils.ranking.ranking_metrics turns the
+        result into MRR, AUC, NDCG@k and recall@k.
+
+        The device takes at most 64 targets per row and call: rows with more are served by further calls over the rows that
+        still have targets, and the ranks do not depend on that split. A target that is also excluded, a wrong shape and sides
+        that share a column are ValueErrors, raised on the host before the device is touched."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        _, _, exclude = _ranked_args(Xq, Xc, 1, exclude)
+        U, I = Xq.shape[0], Xc.shape[0]
+        if targets is None or not sps.issparse(targets) or targets.shape != (U, I):
+            raise ValueError("targets must be a scipy sparse matrix of shape (n_queries, n_candidates)")
+        T = sps.csr_matrix(targets, copy=True)
+        T.sum_duplicates()  # (sorts the indices too)
+        n_candidates = np.full(U, I, dtype=np.int64)
+        if exclude is not None:
+            exclude = sps.csr_matrix(exclude, copy=True)
+            exclude.sum_duplicates()
+            n_candidates -= np.diff(exclude.indptr)
+            pattern = lambda M: sps.csr_matrix((np.ones(M.nnz), M.indices, M.indptr), shape=M.shape)
+            both = pattern(T).multiply(pattern(exclude)).tocoo()
+            if both.nnz:
+                raise ValueError("targets: the pair (query row %d, candidate %d) is also excluded" % (both.row[0], both.col[0]))
+        rank, value = np.empty(T.nnz, dtype=np.int64), np.empty(T.nnz)
+        per_row = np.diff(T.indptr)
+        for lo in range(0, int(per_row.max()) if U else 0, _RANK_TARGETS_PER_CALL):
+            rows = np.flatnonzero(per_row > lo)
+            n = np.minimum(per_row[rows] - lo, _RANK_TARGETS_PER_CALL)
+            # entry p of this call's pattern is stored target `at[p]` of T
+            ptr = np.concatenate(([0], np.cumsum(n)))
+            at = np.repeat(T.indptr[rows] + lo - ptr[:-1], n) + np.arange(ptr[-1])
+            part = sps.csr_matrix((np.ones(at.size), T.indices[at], ptr), shape=(rows.size, I))
+            whole = rows.size == U
+            sub = lambda r: None if r is None else RelationBlock(np.asarray(r.original_to_block_array)[rows], r.data)
+            rank[at], value[at] = predictor.predict_rank(
+                Xq if whole else Xq[rows], Xc, part, exclude if whole or exclude is None else exclude[rows],
+                rq if whole else [sub(r) for r in rq], rc)
+        if per_row.size == 0 or per_row.max() == 0:
+            # nothing to rank: the arguments are still checked by the binding, which launches nothing
+            predictor.predict_rank(Xq, Xc, T, exclude, rq, rc)
+        return TargetRanks(rank, value, n_candidates)
+
+
+_RANK_TARGETS_PER_CALL = 64  # (PAIRS_RANK_MAX_T of the device code)
+TargetRanks = namedtuple("TargetRanks", ["rank", "value", "n_candidates"])
 PairSummary = namedtuple("PairSummary", ["mean", "std"])
 RankedSummary = namedtuple("RankedSummary", ["indices", "value", "mean", "std"])
 
