@@ -10,16 +10,15 @@
 // Relation blocks (mfm_pairs_add_block). A side's row is [main | B_0[o2b_0[r]] | ...]; every block of either side gets a table
 // (block rows x samples x (padded factors + 2) doubles, mfm_pairs.hpp) built once per call -- the query side's too, not once per
 // chunk -- and resident for it. The tables count against MFM_STORE_MAX_FRACTION together with Q; the per-row scratch formula is
-// unchanged. A side with blocks is embedded by k_pairs_embed_rel, one without by k_pairs_embed, so a call without blocks computes
-// what it computed before there were any.
+// unchanged. A side with blocks is embedded by k_pairs_embed<true>, one without by k_pairs_embed<false>, which reads no block
+// argument, so a call without blocks computes what it computed before there were any.
 //
-// Moments (mfm_pairs_moments*, mfm_pairs_topk_ucb*; kernels: mfm_pairs_ucb.hpp). The same call with the spread over
-// the samples kept: k_pairs_tile_moments in place of k_pairs_tile, ranking by mean + beta * std, and after each chunk's merge
-// k_pairs_moments_at for mean and std of the selected pairs. A call without them launches what it launched before.
-//
-// Ranks (mfm_pairs_set_targets, mfm_pairs_rank*; kernels: mfm_pairs_rank.hpp). Per query chunk two launches of
-// k_pairs_tile_rank: the values at the chunk's targets, then the count of the admissible candidates that beat each of them. A chunk
-// without targets launches nothing; a call without targets or candidates touches no device memory.
+// Forms. What a call launches for its tiles is decided once, by pairs_form(): the mean forms (k_pairs_tile), the moments forms
+// (mfm_pairs_moments*, mfm_pairs_topk_ucb*; k_pairs_tile_moments of mfm_pairs_ucb.hpp, DESIGN 4.13.1: the spread over the samples
+// kept, ranking by mean + beta * std, and after each chunk's merge k_pairs_moments_at for mean and std of the selected pairs), or
+// the rank form (mfm_pairs_set_targets, mfm_pairs_rank*; k_pairs_tile_rank of mfm_pairs_rank.hpp, DESIGN 4.13.2: per query chunk
+// the values at the chunk's targets, then the count of the admissible candidates that beat each of them; a chunk without targets
+// launches nothing, a call without targets or candidates touches no device memory).
 #include "mfm_pairs.hpp"
 #include "mfm_pairs_rank.hpp"
 #include "mfm_pairs_ucb.hpp"
@@ -101,77 +100,78 @@ void ensure(DevBuf<T> &b, size_t n) {
   if (b.n < std::max<size_t>(n, 1)) b.alloc(std::max<size_t>(n, 1));
 }
 
-template <int MT, int NT, int MODE, bool DENSE>
-void launch_tile_t(hipStream_t s, dim3 grid, const PairsArgs &a) {
-  const size_t lds = DENSE ? 0 : PairsSel<MT>::BYTES;
+// ---- the forms of the tile kernel ---------------------------------------------------------------------------------------------
+// launches a tile kernel with its dynamic LDS, the limit raised once per device where the form needs more than the default
+template <auto KERNEL>
+void launch_pairs(hipStream_t s, dim3 grid, size_t lds, const PairsArgs &a) {
   static DeviceOnce raised;
   if (lds > 48 * 1024 && raised.need()) {
-    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_pairs_tile<MT, NT, MODE, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     raised.mark();
   }
-  hipLaunchKernelGGL((k_pairs_tile<MT, NT, MODE, DENSE>), grid, dim3(PAIRS_WG), lds, s, a);
+  hipLaunchKernelGGL(KERNEL, grid, dim3(PAIRS_WG), lds, s, a);
 }
 
-// the tile shape that serves k: the per-row buffers of MT * 16 rows x (256 / MT + 64) candidates must fit the LDS
-int tile_rows(bool dense, int k) { return dense || k <= 64 ? 64 : k <= 128 ? 32 : 16; }
-int tile_step(bool dense, int k) { return dense || k <= 64 ? 128 : k <= 128 ? 256 : 512; }
+// what becomes of a finished value: written (the scores entry points), selected (the top k), or looked up and counted at the
+// targets (the rank form's two launches)
+enum PairsOut { PAIRS_DENSE, PAIRS_SELECT, PAIRS_TARGETS };
 
-void launch_tile(hipStream_t s, dim3 grid, const PairsArgs &a, int mode, bool dense) {
-#define PAIRS_LAUNCH(MT, NT, DENSE)           \
-  do {                                        \
-    if (mode == 0)                            \
-      launch_tile_t<MT, NT, 0, DENSE>(s, grid, a); \
-    else if (mode == 1)                       \
-      launch_tile_t<MT, NT, 1, DENSE>(s, grid, a); \
-    else                                      \
-      launch_tile_t<MT, NT, 2, DENSE>(s, grid, a); \
-  } while (0)
-  if (dense)
-    PAIRS_LAUNCH(4, 2, true);
-  else if (a.k <= 64)
-    PAIRS_LAUNCH(4, 2, false);
-  else if (a.k <= 128)
-    PAIRS_LAUNCH(2, 4, false);
-  else
-    PAIRS_LAUNCH(1, 8, false);
-#undef PAIRS_LAUNCH
-}
-
-// ---- the moments form (mfm_pairs_ucb.hpp): MT * NT = 4, the selection buffers of PairsSel<MT>
-template <int MT, int NT, int MODE, bool DENSE>
-void launch_moments_t(hipStream_t s, dim3 grid, const PairsArgs &a) {
-  const size_t lds = DENSE ? 0 : PairsSel<MT>::BYTES;
-  static DeviceOnce raised;
-  if (lds > 48 * 1024 && raised.need()) {
-    MFM_HIP_CHECK(
-        hipFuncSetAttribute((const void *)k_pairs_tile_moments<MT, NT, MODE, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    raised.mark();
+template <int MT, int NT, int MODE, bool SPREAD, PairsOut OUT>
+void launch_form_mode(hipStream_t s, dim3 grid, const PairsArgs &a) {
+  if constexpr (OUT == PAIRS_TARGETS) {
+    launch_pairs<k_pairs_tile_rank<MT, NT, MODE, false>>(s, grid, PairsRankLds<false>::BYTES, a);
+    MFM_HIP_CHECK(hipGetLastError());
+    launch_pairs<k_pairs_tile_rank<MT, NT, MODE, true>>(s, grid, PairsRankLds<true>::BYTES, a);
+  } else {
+    constexpr bool DENSE = OUT == PAIRS_DENSE;
+    const size_t lds = DENSE ? 0 : PairsSel<MT>::BYTES;
+    if constexpr (SPREAD)
+      launch_pairs<k_pairs_tile_moments<MT, NT, MODE, DENSE>>(s, grid, lds, a);
+    else
+      launch_pairs<k_pairs_tile<MT, NT, MODE, DENSE>>(s, grid, lds, a);
   }
-  hipLaunchKernelGGL((k_pairs_tile_moments<MT, NT, MODE, DENSE>), grid, dim3(PAIRS_WG), lds, s, a);
 }
 
-int moments_rows(bool dense, int k) { return dense ? 32 : k <= 64 ? 64 : k <= 128 ? 32 : 16; }
-int moments_step(bool dense, int k) { return dense ? 128 : k <= 64 ? 64 : k <= 128 ? 128 : 256; }
-
-void launch_moments(hipStream_t s, dim3 grid, const PairsArgs &a, int mode, bool dense) {
-#define PAIRS_LAUNCH(MT, NT, DENSE)                   \
-  do {                                                \
-    if (mode == 0)                                    \
-      launch_moments_t<MT, NT, 0, DENSE>(s, grid, a); \
-    else if (mode == 1)                               \
-      launch_moments_t<MT, NT, 1, DENSE>(s, grid, a); \
-    else                                              \
-      launch_moments_t<MT, NT, 2, DENSE>(s, grid, a); \
-  } while (0)
-  if (dense)
-    PAIRS_LAUNCH(2, 2, true);
-  else if (a.k <= 64)
-    PAIRS_LAUNCH(4, 1, false);
-  else if (a.k <= 128)
-    PAIRS_LAUNCH(2, 2, false);
+template <int MT, int NT, bool SPREAD, PairsOut OUT>
+void launch_form(hipStream_t s, dim3 grid, const PairsArgs &a, int mode) {
+  if (mode == 0)
+    launch_form_mode<MT, NT, 0, SPREAD, OUT>(s, grid, a);
+  else if (mode == 1)
+    launch_form_mode<MT, NT, 1, SPREAD, OUT>(s, grid, a);
   else
-    PAIRS_LAUNCH(1, 4, false);
-#undef PAIRS_LAUNCH
+    launch_form_mode<MT, NT, 2, SPREAD, OUT>(s, grid, a);
+}
+
+// The form of a call: a workgroup takes 16 MT query rows and walks its stripe in steps of 64 NT candidates.
+struct PairsForm {
+  int MT, NT;
+  bool spread;  // the moments over the samples (mfm_pairs_ucb.hpp) instead of the mean
+  PairsOut out;
+  void (*launch)(hipStream_t, dim3, const PairsArgs &, int mode);
+  int rows() const { return 16 * MT; }
+  int step() const { return 64 * NT; }
+};
+
+template <int MT, int NT, bool SPREAD, PairsOut OUT>
+PairsForm pairs_form_of() {
+  return {MT, NT, SPREAD, OUT, &launch_form<MT, NT, SPREAD, OUT>};
+}
+
+// The one table of forms. A selecting form's tile shape follows from k: the per-row buffers of 16 MT rows x (256 / MT + 64)
+// candidates must fit the LDS. The moments forms hold MT NT = 4 tiles (their accumulators take twice the registers), the rank
+// form has the one shape its target lists are laid out for.
+PairsForm pairs_form(bool targets, bool spread, bool dense, int k) {
+  if (targets) return pairs_form_of<4, 2, false, PAIRS_TARGETS>();
+  if (!spread) {
+    if (dense) return pairs_form_of<4, 2, false, PAIRS_DENSE>();
+    if (k <= 64) return pairs_form_of<4, 2, false, PAIRS_SELECT>();
+    if (k <= 128) return pairs_form_of<2, 4, false, PAIRS_SELECT>();
+    return pairs_form_of<1, 8, false, PAIRS_SELECT>();
+  }
+  if (dense) return pairs_form_of<2, 2, true, PAIRS_DENSE>();
+  if (k <= 64) return pairs_form_of<4, 1, true, PAIRS_SELECT>();
+  if (k <= 128) return pairs_form_of<2, 2, true, PAIRS_SELECT>();
+  return pairs_form_of<1, 4, true, PAIRS_SELECT>();
 }
 
 void launch_moments_at(hipStream_t s, const PairsArgs &a, int mode, const int32_t *out_i, int64_t n, double *mean, double *sd) {
@@ -190,28 +190,6 @@ struct PairsMoments {
   double beta = 0.0;
   double *mean = nullptr, *sd = nullptr;
 };
-
-// ---- the rank form (mfm_pairs_rank.hpp): one tile shape, 64 rows x 128 candidates per step
-template <int MODE, bool COUNT>
-void launch_rank_t(hipStream_t s, dim3 grid, const PairsArgs &a) {
-  const size_t lds = PairsRankLds<COUNT>::BYTES;
-  static DeviceOnce raised;
-  if (lds > 48 * 1024 && raised.need()) {
-    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_pairs_tile_rank<4, 2, MODE, COUNT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    raised.mark();
-  }
-  hipLaunchKernelGGL((k_pairs_tile_rank<4, 2, MODE, COUNT>), grid, dim3(PAIRS_WG), lds, s, a);
-}
-
-template <bool COUNT>
-void launch_rank(hipStream_t s, dim3 grid, const PairsArgs &a, int mode) {
-  if (mode == 0)
-    launch_rank_t<0, COUNT>(s, grid, a);
-  else if (mode == 1)
-    launch_rank_t<1, COUNT>(s, grid, a);
-  else
-    launch_rank_t<2, COUNT>(s, grid, a);
-}
 
 // the outputs of a rank call, one entry per stored target in CSR order
 struct PairsRank {
@@ -251,6 +229,8 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   }
   const bool is_dense = dense != nullptr;
   if (!is_dense && !rk && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  // the form of the call, decided here once: the scratch per query row, the stripes, the grid and the launch all read it
+  const PairsForm form = pairs_form(rk != nullptr, mo != nullptr, is_dense, k);
   const int64_t U = p->U, I = p->I, D = p->D;
   if (U == 0 || (is_dense && I == 0)) return;
   if (rk && (I == 0 || !p->has_targets)) return;
@@ -284,14 +264,13 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     }
   }
   const int64_t W = (I + 31) / 32;
-  const int rows_t = rk ? PAIRS_RANK_ROWS : mo ? moments_rows(is_dense, k) : tile_rows(is_dense, k);
-  const int step = rk ? 128 : mo ? moments_step(is_dense, k) : tile_step(is_dense, k);
-  const int64_t steps_total = (std::max<int64_t>(I, 1) + step - 1) / step;
-  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && !is_dense ? (double)W * 4 : 0.0) +
-                         (is_dense ? (double)I * 8
-                          : rk     ? (double)PAIRS_RANK_MAX_T * 12  // (the targets' values and ranks)
-                                   : (double)(PAIRS_MAX_STRIPES + 1) * k * 12) +
-                         (!mo ? 0.0 : is_dense ? (double)I * 8 : (double)k * 16);  // (the second dense output / mean and std of the lists)
+  const int64_t steps_total = (std::max<int64_t>(I, 1) + form.step() - 1) / form.step();
+  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && form.out != PAIRS_DENSE ? (double)W * 4 : 0.0) +
+                         (form.out == PAIRS_DENSE     ? (double)I * 8
+                          : form.out == PAIRS_TARGETS ? (double)PAIRS_RANK_MAX_T * 12  // (the targets' values and ranks)
+                                                      : (double)(PAIRS_MAX_STRIPES + 1) * k * 12) +
+                         // (the second dense output / mean and std of the lists)
+                         (!form.spread ? 0.0 : form.out == PAIRS_DENSE ? (double)I * 8 : (double)k * 16);
   int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
   chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
   chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
@@ -333,16 +312,16 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     }
     if (!refs.empty()) d_blk[side].upload(refs);
   }
-  // a side with blocks gathers from its tables, one without takes the plain kernel
+  // a side with blocks gathers from its tables, one without takes the instantiation that reads no block argument
   const auto embed = [&](int side, const int64_t *ptr, const int32_t *idx, const double *val, int64_t r0, int64_t R, int64_t Rpad, double *Pf,
                          double *bias) {
     const dim3 grid((unsigned)((Rpad + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S);
     if (p->blocks[side].empty())
-      hipLaunchKernelGGL(k_pairs_embed, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K, KS, S,
-                         Pf, bias);
+      hipLaunchKernelGGL(k_pairs_embed<false>, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K,
+                         KS, S, (const PairsBlockRef *)nullptr, 0, Pf, bias);
     else
-      hipLaunchKernelGGL(k_pairs_embed_rel, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K, KS,
-                         S, (const PairsBlockRef *)d_blk[side].p, (int)p->blocks[side].size(), Pf, bias);
+      hipLaunchKernelGGL(k_pairs_embed<true>, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K,
+                         KS, S, (const PairsBlockRef *)d_blk[side].p, (int)p->blocks[side].size(), Pf, bias);
   };
 
   // ---- candidate side, once
@@ -378,37 +357,38 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
       hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
     }
     // stripes: enough workgroups to fill the device twice, at most PAIRS_MAX_STRIPES lists to merge
-    const int64_t n_qt = Upad / rows_t;
+    const int64_t n_qt = Upad / form.rows();
     int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_qt - 1) / n_qt, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
     const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
     n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
+    const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
     PairsArgs a;
     a.Pf = Pf.p;
     a.Qf = Qf.p;
+    a.NK = NK;
+    a.KS4 = KS4;
+    a.S = S;
     a.Ab = Ab.p;
     a.Asum = Asum.p;
     a.Bb = Bb.p;
     a.Bsum = Bsum.p;
     a.w0s = d_w0.p;
+    a.w0sum = w0sum;
     a.cut = mode == 2 ? d_cut.p : nullptr;
     a.n_cut = mode == 2 ? p->n_cut : 0;
-    a.w0sum = w0sum;
-    a.NK = NK;
-    a.KS4 = KS4;
-    a.S = S;
+    a.beta = mo ? mo->beta : 0.0;
     a.Upad = Upad;
     a.Ipad = Ipad;
     a.Uc = Uc;
     a.I = I;
-    a.stripe_len = stripe_steps * step;
+    a.stripe_len = stripe_steps * form.step();
+    a.dense = nullptr;
+    a.dense_std = nullptr;
     a.mask = use_mask ? mask.p : nullptr;
     a.W = W;
     a.k = k;
     a.list_v = nullptr;
     a.list_i = nullptr;
-    a.dense = nullptr;
-    a.dense_std = nullptr;
-    a.beta = mo ? mo->beta : 0.0;
     a.tptr = nullptr;
     a.tidx = nullptr;
     a.tval = nullptr;
@@ -423,10 +403,7 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
       a.tval = t_val.p;
       a.trank = t_rank.p;
       MFM_HIP_CHECK(hipMemsetAsync(t_rank.p, 0, (size_t)n_t * sizeof(int32_t), s));
-      const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
-      launch_rank<false>(s, grid, a, mode);
-      MFM_HIP_CHECK(hipGetLastError());
-      launch_rank<true>(s, grid, a, mode);
+      form.launch(s, grid, a, mode);
       MFM_HIP_CHECK(hipGetLastError());
       h_idx.resize((size_t)n_t);
       MFM_HIP_CHECK(hipMemcpyAsync(rk->value + tbase, t_val.p, (size_t)n_t * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -441,14 +418,12 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
       if (mo) {
         ensure(d_dense_std, (size_t)(Uc * I));
         a.dense_std = d_dense_std.p;
-        launch_moments(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, true);
-        MFM_HIP_CHECK(hipGetLastError());
+      }
+      form.launch(s, grid, a, mode);
+      MFM_HIP_CHECK(hipGetLastError());
+      if (mo)
         MFM_HIP_CHECK(
             hipMemcpyAsync(mo->sd + (size_t)u0 * I, d_dense_std.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
-      } else {
-        launch_tile(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, true);
-        MFM_HIP_CHECK(hipGetLastError());
-      }
       MFM_HIP_CHECK(hipMemcpyAsync(dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
       MFM_HIP_CHECK(hipStreamSynchronize(s));
       continue;
@@ -460,10 +435,7 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     a.list_v = list_v.p;
     a.list_i = list_i.p;
     if (I > 0) {
-      if (mo)
-        launch_moments(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, false);
-      else
-        launch_tile(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, mode, false);
+      form.launch(s, grid, a, mode);
       MFM_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, k,

@@ -119,6 +119,40 @@ def test_ranks_of_a_topk_list_are_its_positions(mode):
     assert np.array_equal(value[place], val)
 
 
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_the_forms_finish_the_same_value(mode):
+    """the dense form, the three selecting tile shapes (k = 10, 100, 256) and the rank form's two passes finish one pair's value
+    with the same code, so they agree bit for bit: 65 queries x 600 candidates (two 64-row tiles, two steps of the 512-wide
+    shape), rank 33 (KS = 36), 3 samples, real-valued sides, 5 exclusions per row, mode 2 with 4 cutpoints per sample"""
+    from myfm_amd import _capi
+
+    rng = np.random.default_rng(123 + mode)
+    U, I, K, S, n_cut = 65, 600, 33, 3, 4
+    Xq, Xc, D = pr.disjoint_sides(rng, U, I, 30, 50, list(rng.normal(size=7)), mean_nnz=3.0)
+    samples = pr.normal_samples(rng, D, K, S)
+    cuts = rr.sorted_cuts(rng, S, n_cut) if mode == 2 else None
+    ex_cols = np.stack([rng.choice(I - 1, size=5, replace=False) for _ in range(U)])  # (never the last candidate: it is a target)
+    exclude = sps.csr_matrix((np.ones(U * 5), (np.repeat(np.arange(U), 5), ex_cols.ravel())), shape=(U, I))
+    top = _capi.Pairs(Xq, Xc, exclude=exclude, cutpoints=cuts)
+    scores = top.scores(samples, mode=mode)
+    lists = {k: top.topk(samples, k, mode=mode) for k in (10, 100, 256)}
+    top.close()
+    for k, (idx, val) in lists.items():
+        assert idx.shape == (U, k) and np.all(idx >= 0)
+        assert np.array_equal(val, np.take_along_axis(scores, idx, axis=1)), k
+    idx10 = lists[10][0]
+    cols = [np.union1d(idx10[u], [I - 1]) for u in range(U)]  # sorted and unique
+    indptr = np.concatenate([[0], np.cumsum([c.size for c in cols])])
+    t_cols = np.concatenate(cols)
+    targets = sps.csr_matrix((np.ones(t_cols.size), t_cols, indptr), shape=(U, I))
+    P = _capi.Pairs(Xq, Xc, exclude=exclude, targets=targets, cutpoints=cuts)
+    rank, value = P.rank(samples, mode=mode)
+    P.close()
+    assert np.array_equal(value, scores[np.repeat(np.arange(U), np.diff(indptr)), t_cols])
+    place = np.stack([indptr[u] + np.searchsorted(cols[u], idx10[u]) for u in range(U)])
+    assert np.array_equal(rank[place], np.tile(np.arange(10), (U, 1)))
+
+
 # ---- 4. independence of chunking and stripes ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", [0, 1])
 def test_query_chunks_give_identical_output(mode):
