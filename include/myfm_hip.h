@@ -153,11 +153,12 @@ int mfm_plan_flags(const mfm_ctx *ctx);
  *   9 the most first-level columns any workgroup draws, 10 the most items any slice draws, 11 where the residual is now
  *   (0 row order, 1 slot order, 2 slot order with its sums from mfm_update_e_regression, 3 cell order, 4 not stored: recomputed on
  *   demand), 12 the rows the layout was planned for, 13 the kernel form (0: the user level's sum of h^2 is taken in sweep A, 1: in
- *   sweep B of the sweep before, with a third accumulator array in LDS), 14 the kernel's dynamic LDS in bytes; entries beyond
- *   MFM_RES_INFO_FIELDS are 0. Fields 1-10, 13 and 14 are those of the last
+ *   sweep B of the sweep before, with a third accumulator array in LDS), 14 the kernel's dynamic LDS in bytes, 15 the bytes of an entry of the item draw's
+ *   lists (4: run and item packed into one word, 8: two words; csrc/mfm_res_entry.hpp); entries beyond
+ *   MFM_RES_INFO_FIELDS are 0. Fields 1-10 and 13-15 are those of the last
  *   layout the planner tried: after a refusal the ones it had not reached keep their earlier values (0 in a fresh context).
  * why (why_len bytes, NUL-terminated, may be NULL with why_len 0): the planner's refusal text when not ready, else empty. */
-#define MFM_RES_INFO_FIELDS 15
+#define MFM_RES_INFO_FIELDS 16
 int mfm_res_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why_len);
 /* The cell path's plan (csrc/mfm_cell.hpp, CellPlan: index-tuple designs) as mfm_finalize left it, for diagnostics and for tests
  * that must prove which layout edge they reached. Reads host-side fields only: no launch, no synchronisation. out[i], i < n_out:

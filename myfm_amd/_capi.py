@@ -481,7 +481,7 @@ class Context:
                 "fused_next": bool(f & 32), "sharded_fused": bool(f & 64), "mf": bool(f & 128), "resident": bool(f & 256), "cell": bool(f & 512), "streamed_chain": bool(f & 1024), "resident_overflow": bool(f & 2048)}
 
     RES_INFO = ("ready", "G", "RV", "RL", "RX", "umax", "n_items", "item_bits", "n_runs", "max_wg_users", "max_slice_items",
-                "e_where", "n_rows", "s2_in_sweep_b", "lds_bytes")
+                "e_where", "n_rows", "s2_in_sweep_b", "lds_bytes", "entry_bytes")
     E_WHERE = ("rows", "slots", "slots_with_sums", "cell", "dropped")
 
     def res_info(self):

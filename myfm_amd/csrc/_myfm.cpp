@@ -3163,6 +3163,13 @@ PYBIND11_MODULE(_myfm, m) {
       .def("plan_info", &GibbsSession::plan_info)
       .def("latent_info", &GibbsSession::latent_info)
       .def("plan_flags", [](GibbsSession &s) { return mfm_plan_flags(s.trainer->ctx); })
+      .def("res_info",
+           [](GibbsSession &s) {
+             std::vector<int64_t> v(MFM_RES_INFO_FIELDS, 0);
+             ck(s.trainer->ctx, mfm_res_info(s.trainer->ctx, v.data(), (int)v.size(), nullptr, 0));
+             return v;
+           },
+           "the persistent sweep's layout: the MFM_RES_INFO_FIELDS values of mfm_res_info (myfm_hip.h)")
       // row-sharded persistent sweep (myfm_hip.h: mfm_peer_*): this rank's exchange buffers, every rank's buffers
       .def("peer_info",
            [](GibbsSession &s) {

@@ -1762,7 +1762,8 @@ int mfm_res_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why
   const ResPlan &rp = ctx->res;
   const int64_t v[MFM_RES_INFO_FIELDS] = {rp.ready ? 1 : 0, rp.G,       rp.RV,     rp.RL,           rp.RX,
                                           rp.umax,          rp.n_items, rp.item_bits, rp.n_runs,    rp.max_wg_users,
-                                          rp.max_slice_items, (int64_t)ctx->e_where, rp.n_rows, rp.s2b, (int64_t)rp.lds_bytes};
+                                          rp.max_slice_items, (int64_t)ctx->e_where, rp.n_rows, rp.s2b, (int64_t)rp.lds_bytes,
+                                          rp.ent_bytes};
   for (int i = 0; i < n_out; i++) out[i] = i < MFM_RES_INFO_FIELDS ? v[i] : 0;
   if (why_len > 0) {
     std::strncpy(why, rp.ready ? "" : rp.why.c_str(), (size_t)why_len - 1);

@@ -35,6 +35,7 @@
 
 #include "mfm_common.hpp"
 #include "mfm_mf_kernels.hpp"
+#include "mfm_res_entry.hpp"
 
 namespace mfm {
 
@@ -63,8 +64,8 @@ struct ResArgs {
   const int2 *user_desc;     // {feature, group}
   const int32_t *wg_item_ptr;  // [G + 1] items (positions in the level) drawn by the workgroup: at most umax - 1
   const int32_t *ent_ptr;    // [G + 1] the workgroup's slice of `entries`, in entries (a multiple of 64)
-  const int2 *entries;       // per slice, source-workgroup-major: {run whose partial belongs to the item, item - first item
-                             // of the slice}; pads: {the zero run, 0}
+  const uint32_t *entries;   // per slice, source-workgroup-major: {run whose partial belongs to the item, item - first item
+                             // of the slice}; pads: {the zero run, 0}. ent4 (below): one packed word each (mfm_res_entry.hpp), else two
   const int32_t *scols;      // item -> feature
   const int2 *item_desc;     // item -> {feature, group}
   double *partials;          // [runs + 1][2], workgroup-major: a thread's runs are consecutive; the last stays (0, 0)
@@ -112,6 +113,9 @@ struct ResArgs {
   int ngx;                   // OVF: overflow groups of 16 slots per thread (their residual lives in e_slots, which must be set)
   int no_store;              // the residual is not written back at the end (the caller recomputes it: update_e follows, FMTrainer.hpp:494)
   int xch_break;             // tests (MFM_RES_XCH_BREAK): this rank never raises its exchange flags (the time-out path)
+  int ent4;                  // the entries of `entries` are packed words
+  const double *s2_lin;      // S2B, set when the launch starts with the linear sweep: [G][NW][umax] the first sweep's sum of h^2 per
+                             // (wave, user), a constant of the plan (ResPlan::s2_lin); null: the prologue walks the slots
 };
 
 __device__ __forceinline__ void res_store2(double *p, double a, double b) {
@@ -313,7 +317,12 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
 #define RES_STAMP(k)                                                                                      \
   if (a.prof && tid == 0) a.prof[((int64_t)g * a.n_sw + (f - f_first)) * 64 + (k)] = __builtin_amdgcn_s_memrealtime()
 
-  for (int i = tid; i < (S2B ? 3 : 2) * NW * U; i += NT) acc1[i] = 0.0;
+  // S2B: the first sweep's sum of h^2 comes from the plan's table where the launch has one (requested here, needed at the first
+  // user draw), else from the prologue's walk into a zeroed acc3
+  const bool s2_tab = S2B && a.s2_lin != nullptr;
+  for (int i = tid; i < (S2B && !s2_tab ? 3 : 2) * NW * U; i += NT) acc1[i] = 0.0;
+  if (s2_tab)
+    for (int i = tid; i < NW * U; i += NT) acc3[i] = a.s2_lin[(int64_t)g * (NW * U) + i];
   for (int i = tid; i < U; i += NT) utab[i] = d2_t{0.0, 0.0};
 
   // static per-thread words
@@ -429,11 +438,11 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     }
   }
   __syncthreads();
-  if (S2B) {
+  if (S2B && !s2_tab) {
     // the first sweep's sum of h^2: what sweep B of the sweep before would have left in acc3. One rolled walk over the slots in
     // sweep A's order (on-chip groups, then the overflow groups), static words read again from global memory, a divergent fetch
     // at the run starts: once per launch, small rather than fast. k_res_init_dv left the first sweep's coefficient in dv[.][1]
-    // (1 for the linear sweep).
+    // (1 for the linear sweep: then the sums are counts of slots, and a Gibbs launch loads them from ResPlan::s2_lin instead).
     const uint32_t *uidw_p = a.uidw + (int64_t)g * (5 * NGt) * NT + tid;
     const uint32_t *headw_p = a.headw + (int64_t)g * NGt * NT + tid;
     int run = run0 - 1;
@@ -698,12 +707,24 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       ilam = lamf[d.y];
       imu = muf[d.y];
     }
+    // the list's entries are read through RES_ENTRIES (chunks c_ .. c_ + CH - 1 of the wave's stretch -> en, as stored) and
+    // RES_ENT_RUN / RES_ENT_ITEM (what an entry says); the width is the plan's, the same for every wave of the launch
+    const bool ent4 = a.ent4 != 0;
+#define RES_ENTRIES(c_)                                                                                                    \
+  if (ent4) {                                                                                                              \
+    _Pragma("unroll") for (int k = 0; k < CH; k++)                                                                         \
+      en[k] = make_int2((int)a.entries[(int64_t)((c_) + k < we ? (c_) + k : (c_)) * WAVE + lane], 0);                      \
+  } else {                                                                                                                 \
+    _Pragma("unroll") for (int k = 0; k < CH; k++)                                                                         \
+      en[k] = ((const int2 *)a.entries)[(int64_t)((c_) + k < we ? (c_) + k : (c_)) * WAVE + lane];                         \
+  }
+#define RES_ENT_RUN(e_) (ent4 ? res_entry_run((uint32_t)(e_).x) : (e_).x)
+#define RES_ENT_ITEM(e_) (ent4 ? res_entry_item((uint32_t)(e_).x) : (e_).y)
     int2 en[CH];
 #pragma unroll
     for (int k = 0; k < CH; k++) en[k] = make_int2(0, 0);
     if (wb < we) {  // (wave-uniform)
-#pragma unroll
-      for (int k = 0; k < CH; k++) en[k] = a.entries[(int64_t)(wb + k < we ? wb + k : wb) * WAVE + lane];
+      RES_ENTRIES(wb);
     }
     res_grid_barrier(a, rbar, ++nbar, tid, dead);
     RES_STAMP(4);
@@ -717,13 +738,12 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
       for (int cb = wb; cb < we; cb += CH) {
         d2_t sv[CH];
 #pragma unroll
-        for (int k = 0; k < CH; k++) sv[k] = part2[en[k].x];
+        for (int k = 0; k < CH; k++) sv[k] = part2[RES_ENT_RUN(en[k])];
         int il[CH];
 #pragma unroll
-        for (int k = 0; k < CH; k++) il[k] = en[k].y;
+        for (int k = 0; k < CH; k++) il[k] = RES_ENT_ITEM(en[k]);
         if (cb + CH < we) {  // the next entries while the partials are in flight (wave-uniform)
-#pragma unroll
-          for (int k = 0; k < CH; k++) en[k] = a.entries[(int64_t)(cb + CH + k < we ? cb + CH + k : cb + CH) * WAVE + lane];
+          RES_ENTRIES(cb + CH);
         }
 #pragma unroll
         for (int k = 0; k < CH; k++) {
@@ -794,6 +814,9 @@ __global__ __launch_bounds__(NT) void k_mf_resident(ResArgs a) {
     RES_STAMP(6);
   }
 #undef RES_STAMP
+#undef RES_ENTRIES
+#undef RES_ENT_RUN
+#undef RES_ENT_ITEM
   RES_STAMP0(3);
   // the last factor's item update, then the residual goes back -- unless nobody will read it (no_store)
   if (!a.no_store) {
@@ -889,6 +912,40 @@ __global__ void k_res_init_dv(const double *__restrict__ theta, const int32_t *_
     dv[wd * i + 2] = c2 * c2;
     dv[wd * i + 3] = 0.0;
   }
+}
+
+// ResPlan::s2_lin, once per plan: what k_mf_resident<.., S2B>'s prologue leaves in acc3 when the launch starts with the linear
+// sweep. There every real slot's coefficient is 1 and a pad's is 0, so the sum of h^2 of (wave, user) is the number of real slots
+// of the user that the wave holds: the prologue's walk (on-chip groups, then the overflow groups) with counters in place of the
+// sums. A workgroup per workgroup of the plan, 512 threads, [8][umax] counters in LDS.
+__global__ __launch_bounds__(512) void k_res_s2_lin(const uint32_t *__restrict__ uidw, const uint32_t *__restrict__ headw,
+                                                    const int32_t *__restrict__ run_item, const int32_t *__restrict__ first_run,
+                                                    int NGt, int umax, int n_items, double *__restrict__ s2_lin) {
+  extern __shared__ unsigned res_s2_cnt[];
+  constexpr int NT = 512, NW = NT / WAVE;
+  const int g = (int)blockIdx.x, tid = threadIdx.x, wv = tid >> 6;
+  for (int i = tid; i < NW * umax; i += NT) res_s2_cnt[i] = 0u;
+  __syncthreads();
+  const uint32_t *uidw_p = uidw + (int64_t)g * (5 * NGt) * NT + tid;
+  const uint32_t *headw_p = headw + (int64_t)g * NGt * NT + tid;
+  int run = first_run[g * NT + tid] - 1;
+  bool real = false;
+  for (int jp = 0; jp < NGt; jp++) {
+    const unsigned nb = headw_p[jp * NT] | (jp == 0 ? 1u : 0u);
+    const unsigned uxp = uidw_p[(5 * jp + 4) * NT];
+    for (int bb = 0; bb < 4; bb++) {
+      const unsigned lo_ = uidw_p[(5 * jp + bb) * NT];
+      for (int k = 0; k < 4; k++) {
+        if ((nb >> (4 * bb + k)) & 1u) {
+          run++;
+          real = run_item[run] < n_items;  // (the pad runs carry the pad item, whose coefficient stays 0)
+        }
+        if (real) atomicAdd(&res_s2_cnt[wv * umax + RES_UID(lo_, uxp, bb, k)], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < NW * umax; i += NT) s2_lin[(int64_t)g * (NW * umax) + i] = (double)res_s2_cnt[i];
 }
 
 // eq[row].x of every slot's row from the slot-ordered copy the resident sweep left
@@ -1168,7 +1225,22 @@ struct ResPlan {
     return true;
   }
   DevBuf<int32_t> perm, first_run, wg_run_ptr, wg_nruns, wg_user_ptr, wg_item_ptr, ent_ptr, scols;
-  DevBuf<int2> entries;
+  DevBuf<uint32_t> entries;  // the item draw's lists: ent_bytes / 4 words per entry (mfm_res_entry.hpp)
+  int ent_bytes = 8;
+  // the width of the plan's list entries, from its largest run index (the zero run); row-sharded plans keep 8 bytes
+  void choose_entry_width(int64_t zero_run) { ent_bytes = res_entry_bytes(zero_run, !allow_overflow); }
+  DevBuf<double> s2_lin;  // s2b: [G][NT / 64][umax] the first sweep's sum of h^2 of a launch that starts with the linear sweep (k_res_s2_lin)
+  // (both planners, once the layout's arrays are on the device)
+  void fill_s2_lin(hipStream_t s) {
+    s2_lin = DevBuf<double>();
+    if (!s2b) return;
+    const size_t nw = (size_t)(NT / WAVE);
+    s2_lin.alloc((size_t)G * nw * umax);
+    hipLaunchKernelGGL(k_res_s2_lin, dim3(G), dim3(NT), nw * umax * sizeof(unsigned), s, uidw.p, headw.p, run_item.p, first_run.p,
+                       R() / 16, umax, n_items, s2_lin.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    MFM_HIP_CHECK(hipStreamSynchronize(s));
+  }
   DevBuf<uint32_t> uidw, headw;
   DevBuf<int32_t> run_item;
   DevBuf<int2> user_desc, item_desc;
@@ -1551,7 +1623,18 @@ struct ResPlan {
         h_eptr[g + 1] = (int32_t)e;
       }
     }
-    std::vector<int2> h_entries((size_t)h_eptr[G], make_int2(zero_run, 0));
+    choose_entry_width(zero_run);
+    const size_t ew = (size_t)ent_bytes / 4;  // words per entry
+    std::vector<uint32_t> h_entries(ew * (size_t)h_eptr[G]);
+    auto put_entry = [&](size_t i, int32_t run, int32_t item) {
+      if (ew == 1) {
+        h_entries[i] = res_entry_pack(run, item);
+      } else {
+        h_entries[2 * i] = (uint32_t)run;
+        h_entries[2 * i + 1] = (uint32_t)item;
+      }
+    };
+    for (size_t i = 0; i < (size_t)h_eptr[G]; i++) put_entry(i, zero_run, 0);
     {
       std::vector<int64_t> pos((size_t)G);
       for (int g = 0; g < G; g++) pos[g] = h_eptr[g];
@@ -1559,10 +1642,10 @@ struct ResPlan {
         for (size_t l = 0; l < wg_run_item[g].size(); l++) {
           const int32_t c = wg_run_item[g][l];
           const int sgl = slice_of[c];
-          h_entries[(size_t)pos[sgl]++] = make_int2(run_base[g] + (int32_t)l, c - h_iptr[sgl]);
+          put_entry((size_t)pos[sgl]++, run_base[g] + (int32_t)l, c - h_iptr[sgl]);
         }
     }
-    if (h_entries.size() >= ((size_t)1 << 31)) return fail("too many entries");
+    if ((size_t)h_eptr[G] >= ((size_t)1 << 31)) return fail("too many entries");
     if (!plan_lds()) return fail("LDS");
     uidw.upload(h_uidw);
     headw.upload(h_headw);
@@ -1573,9 +1656,10 @@ struct ResPlan {
     user_desc.upload(h_udesc.data(), h_udesc.size());
     wg_item_ptr.upload(h_iptr);
     ent_ptr.upload(h_eptr);
-    entries.upload(h_entries.data(), h_entries.size());
+    entries.upload(h_entries);
     wg_run_ptr.upload(run_base);
     wg_nruns.upload(nruns);
+    fill_s2_lin(nullptr);
     e_slots.alloc((size_t)G * cap_slots);
     {
       std::vector<int32_t> h_run_feat(h_run_item.size() + 8, -1);  // (the scorer's look-ahead reads a few runs past the last)
@@ -1698,6 +1782,8 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
   a.wg_item_ptr = rp.wg_item_ptr.p;
   a.ent_ptr = rp.ent_ptr.p;
   a.entries = rp.entries.p;
+  a.ent4 = rp.ent_bytes == 4 ? 1 : 0;
+  a.s2_lin = rp.s2b && w ? rp.s2_lin.p : nullptr;  // (w: the launch starts with the linear sweep, k_res_init_dv's theta == null below)
   a.wg_run_ptr = rp.wg_run_ptr.p;
   a.wg_nruns = rp.wg_nruns.p;
   a.scols = rp.scols.p;
@@ -1745,8 +1831,8 @@ static inline void run_sweep_resident(hipStream_t s, Timing &tm, ResPlan &rp, in
   const int K = a.n_sw;
   // algorithmic bytes of the launch: e read once (8 B) with its slot map (4 B) and the static slot words (11 bits), written
   // once (8 B: slot order, or scattered to eq); per sweep one 16-byte partial per (workgroup, item) run written and read,
-  // its 8-byte list entry, its item read by both sweeps (2 x 4 B)
-  double bytes = (8.0 + (load_slots ? 0.0 : 4.0) + 1.4 + (no_store ? 0.0 : 8.0)) * rp.n_rows + K * 48.0 * rp.n_runs;  // (slot order: no map; no_store: not written back)
+  // its list entry (4 or 8 B), its item read by both sweeps (2 x 4 B)
+  double bytes = (8.0 + (load_slots ? 0.0 : 4.0) + 1.4 + (no_store ? 0.0 : 8.0)) * rp.n_rows + K * (40.0 + rp.ent_bytes) * rp.n_runs;  // (slot order: no map; no_store: not written back)
   if (rp.RX) bytes += (double)K * (16.0 + 1.75) * (double)rp.G * rp.NT * rp.RX;  // overflow slots: residual read + written, static words, per sweep
   {
     const int f_second = f_begin + (w ? 0 : 1);  // the factor of the launch's second sweep (S2B: its square goes into dv too)

@@ -142,9 +142,14 @@ __global__ void k_fill32(int32_t *p, int64_t n, int32_t v) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
 }
-__global__ void k_fill_int2(int2 *p, int64_t n, int2 v) {
+// an item-draw list of n entries, every one {run, item}: one packed word each (ent4) or two
+__global__ void k_fill_entries(uint32_t *p, int64_t n, int32_t run, int32_t item, bool ent4) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
+  if (i >= n) return;
+  if (ent4)
+    p[i] = res_entry_pack(run, item);
+  else
+    ((int2 *)p)[i] = make_int2(run, item);
 }
 
 // run heads: the run's item (compact list and the workgroup-major padded list), runs per item
@@ -255,7 +260,8 @@ __global__ void k_slice_keys(const int32_t *__restrict__ run_item_c, const int32
 // the item draw's lists: slice by slice its (run, item within the slice) pairs, source workgroup by source workgroup
 __global__ void k_entries(const uint32_t *__restrict__ key, const int32_t *__restrict__ val, const int32_t *__restrict__ run_item_c,
                           const int32_t *__restrict__ hrun0, const int32_t *__restrict__ run_base, const int32_t *__restrict__ iptr,
-                          const int32_t *__restrict__ eptr, const int32_t *__restrict__ sstart, int G, int64_t n, int2 *__restrict__ entries) {
+                          const int32_t *__restrict__ eptr, const int32_t *__restrict__ sstart, int G, int64_t n, uint32_t *__restrict__ entries,
+                          bool ent4) {
   __shared__ int32_t cut[1026];
   for (int i = threadIdx.x; i <= G; i += blockDim.x) cut[i] = hrun0[i];
   __syncthreads();
@@ -264,7 +270,12 @@ __global__ void k_entries(const uint32_t *__restrict__ key, const int32_t *__res
   const int sl = (int)key[q];
   const int32_t kc = val[q];
   const int g = upper_group(cut, G, kc);
-  entries[eptr[sl] + (q - sstart[sl])] = make_int2(run_base[g] + (kc - cut[g]), run_item_c[kc] - iptr[sl]);
+  const int64_t at = eptr[sl] + (q - sstart[sl]);
+  const int32_t run = run_base[g] + (kc - cut[g]), item = run_item_c[kc] - iptr[sl];
+  if (ent4)
+    entries[at] = res_entry_pack(run, item);
+  else
+    ((int2 *)entries)[at] = make_int2(run, item);
 }
 
 template <class T>
@@ -473,8 +484,10 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
   }
   rpn.wg_item_ptr.upload(h_iptr);
   rpn.ent_ptr.upload(h_eptr);
-  rpn.entries.alloc((size_t)h_eptr[G]);
-  if (h_eptr[G]) hipLaunchKernelGGL(k_fill_int2, grid(h_eptr[G]), dim3(TB), 0, s, rpn.entries.p, (int64_t)h_eptr[G], make_int2(zero_run, 0));
+  rpn.choose_entry_width(zero_run);
+  const bool ent4 = rpn.ent_bytes == 4;
+  rpn.entries.alloc((size_t)(rpn.ent_bytes / 4) * (size_t)h_eptr[G]);
+  if (h_eptr[G]) hipLaunchKernelGGL(k_fill_entries, grid(h_eptr[G]), dim3(TB), 0, s, rpn.entries.p, (int64_t)h_eptr[G], zero_run, 0, ent4);
   if (counter > 0) {
     DevBuf<int32_t> sstart;
     sstart.upload(h_sstart);
@@ -487,7 +500,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
     hipLaunchKernelGGL(k_slice_keys, grid(counter), dim3(TB), 0, s, run_item_c.p, rpn.wg_item_ptr.p, G, counter, sk.p, sv.p);
     sort_pairs(sk, sk2, sv, sv2, counter, gbits, tmp, s);
     hipLaunchKernelGGL(k_entries, grid(counter), dim3(TB), 0, s, sk2.p, sv2.p, run_item_c.p, hrun0.p, rpn.wg_run_ptr.p, rpn.wg_item_ptr.p,
-                       rpn.ent_ptr.p, sstart.p, G, counter, rpn.entries.p);
+                       rpn.ent_ptr.p, sstart.p, G, counter, rpn.entries.p, ent4);
     MFM_HIP_CHECK(hipStreamSynchronize(s));  // (the sort buffers go out of scope)
   }
   lap("slices, pack, entries");
@@ -508,6 +521,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
     rpn.wg_fill.upload(h_fill);
   }
   if (!rpn.plan_lds()) return rpn.fail("LDS");
+  rpn.fill_s2_lin(s);
   rpn.e_slots.alloc((size_t)G * cap_slots);
   rpn.sums.alloc((size_t)G);
   rpn.y_slots = DevBuf<double>();
@@ -529,7 +543,7 @@ static inline bool res_plan_build_device(ResPlan &rpn, const DevSparse &X, const
 static inline std::string res_plan_compare(const ResPlan &a, const ResPlan &b, hipStream_t s) {
   if (a.G != b.G || a.RV != b.RV || a.RL != b.RL || a.RX != b.RX || a.umax != b.umax || a.item_bits != b.item_bits || a.n_items != b.n_items ||
       a.n_rows != b.n_rows || a.n_runs != b.n_runs || a.lds_bytes != b.lds_bytes || a.s2b != b.s2b || a.max_wg_users != b.max_wg_users ||
-      a.max_slice_items != b.max_slice_items)
+      a.max_slice_items != b.max_slice_items || a.ent_bytes != b.ent_bytes)
     return "scalars";
   auto same = [&](const void *p, size_t np, const void *q, size_t nq, size_t elem) {
     if (np != nq) return false;
@@ -559,6 +573,7 @@ static inline std::string res_plan_compare(const ResPlan &a, const ResPlan &b, h
   MFM_RP_CMP(item_desc)
   MFM_RP_CMP(run_feat)
   MFM_RP_CMP(wg_fill)
+  MFM_RP_CMP(s2_lin)
 #undef MFM_RP_CMP
   return "";
 }
