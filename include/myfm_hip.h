@@ -414,6 +414,35 @@ int mfm_design_summary_oprobit(mfm_design *d, int32_t rank, int32_t n_samples, c
                                int32_t expected, int32_t n_cut, const double *cutpoints, int32_t n_q, const double *probs,
                                int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q);
 
+/* ---- pointwise log predictive density over the kept samples (csrc/mfm_logdens.hpp) --------------------------
+ * Per design row t with observed target y[t], over the samples of mfm_design_summary*, l_s = log p(y[t] | sample s):
+ *   task 0 (regression)      log N(y; score_s, 1 / precisions[s])
+ *   task 1 (probit)          log Phi(score_s) for y = 1, log Phi(-score_s) for y = 0
+ *   task 2 (ordered probit)  log(Phi(cut_s[y] - score_s) - Phi(cut_s[y - 1] - score_s)), cut_s[-1] = -inf, cut_s[n_cut] = +inf,
+ *                            cutpoints[count * n_cut] row-major (count, n_cut)
+ * evaluated without forming Phi (finite and relatively accurate to |score| ~ 38 and beyond).
+ *   out_lpd[N]   logsumexp_s l_s - log S, the log pointwise predictive density
+ *   out_mean[N]  mean_s l_s;   out_var[N]  the sample variance (ddof = 1) of the l_s, exactly 0 for S = 1 or equal values
+ *   out_pit[N]   task 0 only, may be NULL: mean_s Phi((y - score_s) sqrt(precisions[s]))
+ *   out_ll[S * N]  may be NULL: row-major (S, N), the l_s themselves
+ * Everything is fp64 and summed in sample order: tile_rows / chunk_samples (0: automatic) do not change a bit of the results.
+ * MFM_ERR_INVALID, before the device is used: a bad task; y not finite, not 0 / 1 (task 1), not an integer in [0, n_cut]
+ * (task 2); precisions missing, non-positive or non-finite for task 0 or given otherwise; cutpoints missing (or n_cut < 1),
+ * non-finite or not ascending for task 2 or given otherwise; out_pit for a task other than 0; negative tiling overrides. N = 0
+ * returns at once. The upload rule of the host flavour is that of mfm_design_summary.                                        */
+int mfm_design_logdens_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t task, const double *y,
+                             const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
+                             int32_t chunk_samples, double *out_lpd, double *out_mean, double *out_var, double *out_pit,
+                             double *out_ll);
+int mfm_design_logdens(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t task, const double *y, const double *precisions, int32_t n_cut, const double *cutpoints,
+                       int64_t tile_rows, int32_t chunk_samples, double *out_lpd, double *out_mean, double *out_var,
+                       double *out_pit, double *out_ll);
+/* l of one (y, score) on the host, by the code the kernel runs (no device): log_norm = log(precision) / 2 - log(2 pi) / 2 and
+ * sqrt_alpha for task 0, cutpoints_row[n_cut] for task 2, ignored otherwise                                                 */
+int mfm_logdens_value(int32_t task, double y, double score, double log_norm, double sqrt_alpha, int32_t n_cut,
+                      const double *cutpoints_row, double *out);
+
 /* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
  * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), each optionally with relation blocks
  * (below); pair (u, i) is the design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column

@@ -28,6 +28,7 @@ from .estimators import (  # noqa: E402
     MyFMOrderedProbit,
     MyFMRegressor,
     PairSummary,
+    PointwiseDensity,
     RankedSummary,
     TargetRanks,
     VariationalFMClassifier,
@@ -47,4 +48,5 @@ __all__ = [
     "PairSummary",
     "RankedSummary",
     "TargetRanks",
+    "PointwiseDensity",
 ]

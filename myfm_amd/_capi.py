@@ -45,6 +45,7 @@ SYMBOLS = [
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
+    "mfm_design_logdens_store", "mfm_design_logdens", "mfm_logdens_value",
 ]
 
 _lib = None
@@ -170,6 +171,9 @@ def lib():
     L.mfm_design_summary.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, P, i64, i32, P, P, P]
     L.mfm_design_summary_oprobit_store.argtypes = [vp, vp, i32, i32, i32, i32, P, i32, P, i64, i32, P, P, P]
     L.mfm_design_summary_oprobit.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, i32, P, i64, i32, P, P, P]
+    L.mfm_design_logdens_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P, P, P]
+    L.mfm_design_logdens.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, P, P, P, P, P]
+    L.mfm_logdens_value.argtypes = [i32, dbl, dbl, dbl, dbl, i32, P, P]
     L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
@@ -611,6 +615,30 @@ class Design:
                           int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q)))
         return mean, std, q
 
+    def _log_density(self, src, task, y, precisions, cutpoints, pointwise, tile_rows, chunk_samples):
+        y = _f64(y).reshape(-1)
+        if y.shape[0] != self.N:
+            raise ValueError("y must hold one value per design row")
+        prec = None if precisions is None else _f64(precisions).reshape(-1)
+        cp, n_cut = None, 0
+        if cutpoints is not None:
+            cp = _f64(cutpoints)
+            if cp.ndim != 2:
+                raise ValueError("cutpoints must be a 2-D array, one row of n_cut cutpoints per sample")
+            n_cut = cp.shape[1]
+        lpd, mean, var = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        pit = np.empty(self.N) if task == TASK_REGRESSION else None
+        ll = np.empty((src.S, self.N)) if pointwise else None
+        self._ck(src.call("mfm_design_logdens", self.h, int(task), _p(y), _p(prec), n_cut, _p(cp), int(tile_rows), int(chunk_samples),
+                          _p(lpd), _p(mean), _p(var), _p(pit), _p(ll)))
+        return lpd, mean, var, pit, ll
+
+    def log_density(self, samples, task, y, precisions=None, cutpoints=None, pointwise=False, tile_rows=0, chunk_samples=0):
+        """samples as predict; task 0 regression (precisions[S]), 1 probit classification (y in {0, 1}), 2 ordered probit
+        (cutpoints[S][n_cut], y the class labels). Returns (lpd[N], log_lik_mean[N], log_lik_var[N], pit[N] or None,
+        log_lik[S, N] or None) of the observed y over the samples (mfm_design_logdens)."""
+        return self._log_density(_host(samples), task, y, precisions, cutpoints, pointwise, tile_rows, chunk_samples)
+
     def predict(self, samples, mode=0, cutpoints=None):
         """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
         return self._predict(_host(samples), mode, cutpoints)
@@ -700,6 +728,11 @@ class Store:
     def summary_oprobit(self, design, cutpoints, expected=False, quantiles=(), first=0, count=None, tile_rows=0, chunk_samples=0):
         """Design.summary_oprobit over the resident samples [first, first + count) (mfm_design_summary_oprobit_store)"""
         return design._summary_oprobit(_resident(self, first, count), cutpoints, expected, quantiles, tile_rows, chunk_samples)
+
+    def log_density(self, design, task, y, precisions=None, cutpoints=None, pointwise=False, first=0, count=None, tile_rows=0,
+                    chunk_samples=0):
+        """Design.log_density over the resident samples [first, first + count) (mfm_design_logdens_store)"""
+        return design._log_density(_resident(self, first, count), task, y, precisions, cutpoints, pointwise, tile_rows, chunk_samples)
 
 
 def _pack_samples(samples):

@@ -1096,6 +1096,86 @@ struct Predictor {
                      probs.data(), tile_rows, chunk_samples, mean.mutable_data(), sd.mutable_data(), q.mutable_data()));
     return py::make_tuple(mean, sd, q);
   }
+  // Pointwise log predictive density (not in the reference): (lpd[N], log_lik_mean[N], log_lik_var[N], pit[N] or None,
+  // log_lik[S, N] or None) of the observed y under the kept samples. task: this predictor's TaskType as an integer. y as the C entry
+  // point takes it: real (0), 0 / 1 (1), integer class labels (2). precisions[S]: regression; cutpoints: ordered probit, a cutpoint
+  // group index or an (S, n_cut) array. Every argument is checked here, before the device is looked for.
+  py::tuple predict_log_density(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
+                                const py::object &cutpointso, bool pointwise, int64_t tile_rows, int chunk_samples) const {
+    Csr X = csr_from_py(Xo);
+    Relations rels = relations_from_py(relso);
+    check_input(X, rels);
+    if (task < 0 || task > 2) throw std::invalid_argument("bad task (0: regression, 1: probit classification, 2: ordered probit)");
+    if (task != static_cast<int>(type)) throw std::invalid_argument("task does not match the task this predictor was fitted for");
+    if (tile_rows < 0 || chunk_samples < 0) throw std::invalid_argument("tile_rows and chunk_samples must be non-negative");
+    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
+    const size_t S = samples.size();
+    auto ya = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(yo);
+    if (!ya || ya.ndim() != 1 || (size_t)ya.shape(0) != (size_t)X.rows) throw std::invalid_argument("y must hold one value per row of X");
+    vector<double> prec;
+    if (!precisionso.is_none()) {
+      if (type != TaskType::REGRESSION) throw std::invalid_argument("noise precisions apply to regression only");
+      auto pa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(precisionso);
+      if (!pa || pa.ndim() != 1 || (size_t)pa.shape(0) != S) throw std::invalid_argument("precisions must hold one value per kept sample");
+      prec.assign(pa.data(), pa.data() + pa.shape(0));
+      for (double a : prec)
+        if (!(a > 0.0) || !std::isfinite(a)) throw std::invalid_argument("precisions must be positive and finite");
+    } else if (type == TaskType::REGRESSION) {
+      throw std::invalid_argument("a regression log density needs the noise precision of every kept sample");
+    }
+    Cutpoints cp;
+    if (!cutpointso.is_none()) {
+      if (type != TaskType::ORDERED) throw std::invalid_argument("cutpoints apply to ordered probit only");
+      if (py::isinstance<py::int_>(cutpointso) && !py::isinstance<py::bool_>(cutpointso)) {
+        const int64_t g = cutpointso.cast<int64_t>();
+        cp = gather_cutpoints(g);
+        if (cp.bad && cp.at == 0)
+          throw std::invalid_argument("cutpoint_index " + std::to_string(g) + " out of range: the model has " +
+                                      std::to_string(samples[0].cutpoints.size()) + " cutpoint group(s)");
+        if (cp.bad) throw std::invalid_argument("inconsistent cutpoint sizes among samples.");
+      } else {
+        auto ca = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(cutpointso);
+        if (!ca || ca.ndim() != 2 || (size_t)ca.shape(0) != S || ca.shape(1) < 1)
+          throw std::invalid_argument("cutpoints must be a cutpoint group index or an array of shape (kept samples, n_cut)");
+        cp.n_cut = (size_t)ca.shape(1);
+        cp.cuts.assign(ca.data(), ca.data() + ca.size());
+      }
+      for (size_t k = 0; k < S; k++)
+        for (size_t j = 0; j < cp.n_cut; j++) {
+          const double *cs = cp.cuts.data() + k * cp.n_cut;
+          if (!std::isfinite(cs[j]) || (j > 0 && !(cs[j - 1] <= cs[j])))
+            throw std::invalid_argument("cutpoints must be finite and ascending within every sample");
+        }
+    } else if (type == TaskType::ORDERED) {
+      throw std::invalid_argument("an ordered-probit log density needs the samples' cutpoints");
+    }
+    for (py::ssize_t t = 0; t < ya.shape(0); t++) {
+      const double y = ya.data()[t];
+      if (!std::isfinite(y)) throw std::invalid_argument("y must be finite");
+      if (type == TaskType::CLASSIFICATION && y != 0.0 && y != 1.0) throw std::invalid_argument("classification labels must be 0 or 1");
+      if (type == TaskType::ORDERED && (y != std::floor(y) || y < 0.0 || y > (double)cp.n_cut))
+        throw std::invalid_argument("ordered-probit labels must be integers in [0, " + std::to_string(cp.n_cut) + "]");
+    }
+    const py::ssize_t N = (py::ssize_t)X.rows;
+    py::array_t<double> lpd(N), mean(N), var(N);
+    py::object pit = py::none(), ll = py::none();
+    double *pit_p = nullptr, *ll_p = nullptr;
+    if (type == TaskType::REGRESSION) {
+      py::array_t<double> a(N);
+      pit_p = a.mutable_data();
+      pit = a;
+    }
+    if (pointwise) {
+      py::array_t<double> a({(py::ssize_t)S, N});
+      ll_p = a.mutable_data();
+      ll = a;
+    }
+    DeviceDesign dd(X, rels);
+    dd.ck(on_samples(mfm_design_logdens_store, mfm_design_logdens, dd.d, (int32_t)task, ya.data(), prec.empty() ? (const double *)nullptr : prec.data(),
+                     (int32_t)cp.n_cut, cp.n_cut ? cp.cuts.data() : (const double *)nullptr, tile_rows, (int32_t)chunk_samples, lpd.mutable_data(),
+                     mean.mutable_data(), var.mutable_data(), pit_p, ll_p));
+    return py::make_tuple(lpd, mean, var, pit, ll);
+  }
   // predictor.hpp:78-124
   py::array_t<double> predict_parallel_oprobit(const py::object &Xo, const py::object &relso, size_t n_workers,
                                                size_t cutpoint_index) const {
@@ -2898,6 +2978,9 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def("predict_dist_oprobit", &Predictor::predict_dist_oprobit, py::arg("X"), py::arg("rels"), py::arg("quantiles"),
            py::arg("cutpoint_index") = 0, py::arg("expected") = false, py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+      .def("predict_log_density", &Predictor::predict_log_density, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
+           py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("pointwise") = false, py::arg("tile_rows") = 0,
+           py::arg("chunk_samples") = 0)
       .def(py::pickle(
           [](const Predictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {
@@ -3130,6 +3213,19 @@ PYBIND11_MODULE(_myfm, m) {
         "Level of every column of X with the relation blocks expanded: the schedule create_train_vfm_sharded takes (host only).");
   m.def("mean_var_truncated_normal_left", [](Real mu) { return truncated_normal_tuple(0, mu); });
   m.def("mean_var_truncated_normal_right", [](Real mu) { return truncated_normal_tuple(1, mu); });
+  // log p(y | score, one sample's constants) on the host, by the code k_row_logdens runs on the device (csrc/mfm_logdens.hpp)
+  m.def(
+      "log_density_value",
+      [](int task, double y, double score, double log_norm, double sqrt_alpha, const py::object &cutpoints_row) {
+        vector<double> cut;
+        if (!cutpoints_row.is_none()) cut = cutpoints_row.cast<vector<double>>();
+        double out = 0.0;
+        const int code = mfm_logdens_value(task, y, score, log_norm, sqrt_alpha, (int32_t)cut.size(), cut.empty() ? nullptr : cut.data(), &out);
+        if (code != MFM_OK) throw_code(code, mfm_global_error());
+        return out;
+      },
+      py::arg("task"), py::arg("y"), py::arg("score"), py::arg("log_norm") = 0.0, py::arg("sqrt_alpha") = 0.0,
+      py::arg("cutpoints_row") = py::none());
 
   // extensions beyond the reference's surface (bench / tests)
   py::class_<GibbsSession>(m, "GibbsSession")

@@ -329,6 +329,42 @@ static void launch_row_summary(hipStream_t s, RowSummaryArgs &a, int xf = XF_NON
   hipLaunchKernelGGL(k_row_summary<true>, dim3((unsigned)cdiv(a.Tn, a.R)), dim3(WG), lds, s, a);
 }
 
+// Stage 1 of a tiled pass over the design (design_summary here, design_logdens in mfm_logdens.hpp): the values of the rows
+// [r0, r0 + Tn), all samples, into d->dist_scratch [S][Tn]. begin: once per call, behind the store's latest snapshot; designs
+// without relation blocks (rank <= 512) stage their samples for the one-pass scorer, in chunks of `chunk` samples.
+struct DistStage1 {
+  bool one_pass;
+  int chunk;
+  int built;  // the chunk whose row-major V copies vt_all holds
+};
+static DistStage1 dist_stage1_begin(mfm_design *d, hipStream_t s, const SampleView &v, int32_t chunk_samples) {
+  if (v.pushed) MFM_HIP_CHECK(hipStreamWaitEvent(s, v.pushed, 0));
+  const bool one_pass = d->blocks.empty() && v.K <= 512;
+  return DistStage1{one_pass, one_pass ? design_stage_samples(d, s, v, chunk_samples) : v.count(), -1};
+}
+// mode 0: scores, 1: Phi(score)
+static void dist_stage1_tile(mfm_design *d, hipStream_t s, const SampleView &v, DistStage1 &st, int mode, int64_t r0, int64_t Tn) {
+  const int count = v.count(), rank = v.K;
+  const int64_t D = d->D;
+  if (st.one_pass) {
+    for (int c0 = 0; c0 < count; c0 += st.chunk) {
+      const int C = std::min(st.chunk, count - c0);
+      const ScoreStoreArgs sa = design_sample_chunk(d, s, c0, C, st.built != c0);
+      st.built = c0;
+      launch_score_store_rows(s, 3 + mode, d->X, score_rows(d->X, r0, Tn), sa, D, rank, d->KS, d->dist_scratch.p + (size_t)c0 * Tn);
+    }
+  } else {
+    // relation blocks: the per-sample pass over the whole design, of which this tile's rows are kept (a design of more
+    // than one tile is scored once per tile)
+    for (int k = 0; k < count; k++) {
+      const double *w = v.wv[(size_t)k], *V = w + D;
+      score_design(s, d->timing, 1, d->X, d->blocks, D, rank, d->KS, v.w0[(size_t)k], w, V, d->Vt.p, nullptr, nullptr, d->score.p);
+      hipLaunchKernelGGL(k_dist_copy, dim3((unsigned)cdiv(Tn, WG)), dim3(WG), 0, s, d->score.p + r0, d->dist_scratch.p + (size_t)k * Tn, Tn,
+                         mode);
+    }
+  }
+}
+
 // what an ordered-probit summary adds to the call: which value, and the samples' cutpoints [count][n_cut] on the host
 struct OprobitValues {
   int32_t expected, n_cut;
@@ -373,7 +409,7 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
   const int64_t C = xf == XF_CLASS ? (int64_t)op->n_cut + 1 : 1;
   hipStream_t s = d->stream;
   const int rank = v.K;
-  const int64_t N = d->N, D = d->D;
+  const int64_t N = d->N;
   if (N == 0) return;
   design_use_rank(d, rank, s);
   const int64_t T = std::min<int64_t>(N, tile_rows > 0 ? tile_rows : std::max<int64_t>(1, (int64_t)(DIST_SCRATCH_BYTES / sizeof(double)) / count));
@@ -421,29 +457,10 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
       a.g[q] = h - fl;
     }
   }
-  if (v.pushed) MFM_HIP_CHECK(hipStreamWaitEvent(s, v.pushed, 0));
-  const bool one_pass = d->blocks.empty() && rank <= 512;
-  const int chunk = one_pass ? design_stage_samples(d, s, v, chunk_samples) : count;
-  int built = -1;  // the chunk whose row-major V copies vt_all holds
+  DistStage1 st = dist_stage1_begin(d, s, v, chunk_samples);
   for (int64_t r0 = 0; r0 < N; r0 += T) {
     const int64_t Tn = std::min<int64_t>(T, N - r0);
-    if (one_pass) {
-      for (int c0 = 0; c0 < count; c0 += chunk) {
-        const int C = std::min(chunk, count - c0);
-        const ScoreStoreArgs sa = design_sample_chunk(d, s, c0, C, built != c0);
-        built = c0;
-        launch_score_store_rows(s, 3 + mode, d->X, score_rows(d->X, r0, Tn), sa, D, rank, d->KS, d->dist_scratch.p + (size_t)c0 * Tn);
-      }
-    } else {
-      // relation blocks: the per-sample pass over the whole design, of which this tile's rows are kept (a design of more
-      // than one tile is scored once per tile)
-      for (int k = 0; k < count; k++) {
-        const double *w = v.wv[(size_t)k], *V = w + D;
-        score_design(s, d->timing, 1, d->X, d->blocks, D, rank, d->KS, v.w0[(size_t)k], w, V, d->Vt.p, nullptr, nullptr, d->score.p);
-        hipLaunchKernelGGL(k_dist_copy, dim3((unsigned)cdiv(Tn, WG)), dim3(WG), 0, s, d->score.p + r0, d->dist_scratch.p + (size_t)k * Tn, Tn,
-                           mode);
-      }
-    }
+    dist_stage1_tile(d, s, v, st, mode, r0, Tn);
     MFM_HIP_CHECK(hipGetLastError());
     a.Tn = Tn;
     a.mean = d->dist_out.p + (size_t)r0 * C;

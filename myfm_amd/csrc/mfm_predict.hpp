@@ -268,6 +268,7 @@ struct mfm_design {
   DevBuf<double> vt_all, w0s;      // single-pass predictor: row-major V of a chunk of samples, their w0
   DevBuf<const double *> wvp;      // ... and the samples' buffers
   DevBuf<double> dist_scratch, dist_out, dist_aux;  // posterior summaries (mfm_dist.hpp): [S][T] values of a row tile, outputs, sqrt(alpha)
+  DevBuf<double> dist_y;                            // log densities (mfm_logdens.hpp): the observed targets
   PinnedRing ring;
   Timing timing;
   ~mfm_design() {

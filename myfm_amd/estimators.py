@@ -333,6 +333,14 @@ def _check_sample_limit(probs, n_samples):
                          "limit: pass quantiles=())" % (PREDICT_DIST_MAX_SAMPLES, n_samples))
 
 
+def _kept_precisions(est, n_samples, what):
+    """the noise precision alpha_s of every kept sample: the last n_samples entries of history_.hypers"""
+    hypers = None if est.history_ is None else est.history_.hypers
+    if hypers is None or len(hypers) < n_samples:
+        raise RuntimeError("%s needs history_ with the noise precision of every kept sample" % what)
+    return np.asarray([h.alpha for h in hypers[len(hypers) - n_samples:]], dtype=REAL)
+
+
 class _PredictiveDistMixin:
     """Posterior predictive summaries of a fitted Gibbs regressor / classifier. MyFMOrderedProbit and the
     variational estimators have no predict_dist (for ordered probit see predict_proba_dist / predict_expected_dist). Row-sharded
@@ -363,12 +371,60 @@ class _PredictiveDistMixin:
                 raise ValueError("noise=True describes a regression target: it is not available on a classifier")
             if np.any((probs <= 0.0) | (probs >= 1.0)):
                 raise ValueError("with noise=True the quantiles must lie strictly inside (0, 1)")
-            hypers = None if self.history_ is None else self.history_.hypers
-            if hypers is None or len(hypers) < n_samples:
-                raise RuntimeError("noise=True needs history_ with the noise precision of every kept sample")
-            precisions = np.asarray([h.alpha for h in hypers[len(hypers) - n_samples:]], dtype=REAL)
+            precisions = _kept_precisions(self, n_samples, "noise=True")
         _check_sample_limit(probs, n_samples)
         return PredictiveSummary(*predictor.predict_dist(X, list(X_rel), probs, precisions))
+
+
+PointwiseDensity = namedtuple("PointwiseDensity", ["lpd", "log_lik_mean", "log_lik_var", "pit", "log_lik"])
+
+
+class _LogDensityMixin:
+    """How probable were the observed targets under the posterior: the pointwise log predictive density of a fitted Gibbs
+    regressor, classifier or ordered probit. The variational estimators keep one point estimate and have no such
+    method. Row-sharded operation is not covered: the model is replicated, so each rank may call it on its own rows."""
+
+    def predict_log_density(self, X, y, X_rel=[], pointwise=False):
+        """PointwiseDensity(lpd, log_lik_mean, log_lik_var, pit, log_lik) per test row over the S kept samples, computed on the
+        device in one pass over the rows. With l_s = log p(y | sample s) -- the normal density with that sample's noise precision
+        (the last S entries of history_.hypers, as predict_dist(noise=True) takes them), log Phi(+-score) for a classifier, the log
+        of the class interval's probability under that sample's cutpoints for ordered probit --
+
+        lpd (N,): logsumexp_s l_s - log S, the log pointwise predictive density. log_lik_mean (N,): mean_s l_s. log_lik_var (N,):
+        the sample variance (ddof = 1) of the l_s, WAIC's penalty (exactly 0 for one kept sample). pit (N,), regressor only (else
+        None): the predictive CDF at y, mean_s Phi((y - score_s) sqrt(alpha_s)), uniform on [0, 1] for a calibrated model.
+        log_lik (S, N), only with pointwise=True (else None and nothing of that size exists on the host): the l_s themselves,
+        for PSIS-LOO or arviz. The tails are evaluated without forming Phi: finite wherever the scores are.
+
+        y (N,) as fit takes it: real targets, 0 / 1 or bool labels, integer classes in [0, n_class) (MyFMOrderedProbit also takes
+        cutpoint_index, the cutpoint group). See myfm_amd.utils.evaluation for waic, log_score and pit_histogram.
+
+        The arguments are checked on the host before the device is touched."""
+        return self._predict_log_density(X, y, X_rel, pointwise, None)
+
+    def _predict_log_density(self, X, y, X_rel, pointwise, cutpoint_index):
+        predictor = self._fetch_predictor()
+        n = check_data_consistency(X, X_rel)
+        X = _as_csr(X, n)
+        y = np.asarray(y)
+        if y.ndim != 1 or y.shape[0] != n:
+            raise ValueError("y must hold one value per row: expected shape (%d,), got %s" % (n, y.shape))
+        if y.dtype.kind not in "buif" or not np.all(np.isfinite(y)):
+            raise ValueError("y must be finite")
+        if self._task_type == TaskType.ORDERED and y.shape[0] and y.min() < 0:
+            raise ValueError("ordered-probit labels must be integers in [0, n_class)")
+        y = self._process_y(y) if y.shape[0] else y.astype(REAL)
+        precisions = cutpoints = None
+        if self._task_type == TaskType.REGRESSION:
+            precisions = _kept_precisions(self, len(predictor.samples), "predict_log_density")
+        elif self._task_type == TaskType.CLASSIFICATION:
+            y = (y + 1) / 2  # (fit's -1 / +1 back to the 0 / 1 the device call takes)
+        else:
+            if isinstance(cutpoint_index, bool) or not isinstance(cutpoint_index, (int, np.integer)):
+                raise ValueError("cutpoint_index must be an integer")
+            cutpoints = int(cutpoint_index)
+        return PointwiseDensity(*predictor.predict_log_density(X, list(X_rel), np.ascontiguousarray(y, dtype=REAL), int(self._task_type),
+                                                               precisions, cutpoints, bool(pointwise)))
 
 
 def _ranked_args(Xq, Xc, k, exclude, beta=0.0):
@@ -686,7 +742,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LogDensityMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -754,7 +810,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDi
         return _folded_in(self, predictor.extended(w_new, V_new), D, U)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LogDensityMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -830,7 +886,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LogDensityMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""
@@ -924,6 +980,11 @@ class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _FoldInGibbsMi
         """As predict_proba_dist, of the expected class index sum_c c p_c (added in ascending class order), the value that
         predict_topk ranks by: mean (N,), std (N,), quantiles (Q, N)."""
         return self._predict_dist_oprobit(X, X_rel, quantiles, cutpoint_index, True)
+
+    def predict_log_density(self, X, y, X_rel=[], pointwise=False, cutpoint_index=0):
+        """_LogDensityMixin.predict_log_density with the cutpoint group to use: y (N,) holds integer class labels in [0, n_class),
+        n_class the number of cutpoints of group `cutpoint_index` of the kept samples plus one."""
+        return self._predict_log_density(X, y, X_rel, pointwise, cutpoint_index)
 
     @property
     def cutpoint_samples(self):
