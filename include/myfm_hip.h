@@ -443,6 +443,32 @@ int mfm_design_logdens(mfm_design *d, int32_t rank, int32_t n_samples, const dou
 int mfm_logdens_value(int32_t task, double y, double score, double log_norm, double sqrt_alpha, int32_t n_cut,
                       const double *cutpoints_row, double *out);
 
+/* ---- Pareto-smoothed importance-sampling leave-one-out over the kept samples (csrc/mfm_psis.hpp) -------------
+ * Per design row t, with l_s of mfm_design_logdens* and the importance ratios r_s = -l_s - max_s(-l_s): the largest tail_len
+ * ratios (ordered by (r_s, s)) are replaced by the quantiles of a generalized Pareto distribution fitted to them (Zhang and
+ * Stephens 2009 on a grid of 30 + floor(sqrt(tail_len)) points, the loo package's priors), lw_s = r_s - logsumexp_s r_s.
+ *   out_elpd[N]  logsumexp_s(lw_s + l_s), the leave-one-out log predictive density when y[t] is a row the model was fitted on
+ *   out_k[N]     the fit's shape k^; +inf where no fit was made: tail_len < 5, a tail whose lower quarter equals the cutoff,
+ *                or an l_s of -inf (then out_elpd = -inf and the row's log weights are NaN)
+ *   out_lpd[N]   as mfm_design_logdens* writes it, bit for bit
+ *   out_pit[N]   task 0 only, may be NULL: sum_s exp(lw_s) Phi((y - score_s) sqrt(precisions[s]))
+ *   out_lw[S * N]  may be NULL: row-major (S, N), the normalised log weights lw_s
+ * tail_len: ceil(min(0.2 S, 3 sqrt(S / r_eff))) for a relative efficiency r_eff of the draws (1 for independent ones).
+ * Everything is fp64; the sums over samples run in sample order, those over the grid in grid order: tile_rows / chunk_samples
+ * (0: automatic) do not change a bit of the results. MFM_ERR_INVALID, before the device is used: what mfm_design_logdens*
+ * refuses; more than 4096 samples; tail_len outside [0, S). N = 0 returns at once.                                            */
+int mfm_design_loo_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t task, const double *y,
+                         const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
+                         int32_t chunk_samples, int32_t tail_len, double *out_elpd, double *out_k, double *out_lpd,
+                         double *out_pit, double *out_lw);
+int mfm_design_loo(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                   int32_t task, const double *y, const double *precisions, int32_t n_cut, const double *cutpoints,
+                   int64_t tile_rows, int32_t chunk_samples, int32_t tail_len, double *out_elpd, double *out_k,
+                   double *out_lpd, double *out_pit, double *out_lw);
+/* one row on the host, by the scalar pieces the kernel runs and in its summation orders (no device): log_lik[S], 1 <= S <= 4096,
+ * tail_len in [0, S); out_lw[S] may be NULL                                                                                  */
+int mfm_psis_row(int32_t S, int32_t tail_len, const double *log_lik, double *out_elpd, double *out_k, double *out_lw);
+
 /* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
  * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), each optionally with relation blocks
  * (below); pair (u, i) is the design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column

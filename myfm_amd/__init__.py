@@ -22,6 +22,7 @@ _hip_runtime = _preload()
 from ._myfm import RelationBlock  # noqa: E402
 from .estimators import (  # noqa: E402
     FOLD_IN_MAX_RANK,
+    LooDensity,
     MyFMClassifier,
     MyFMGibbsClassifier,
     MyFMGibbsRegressor,
@@ -49,4 +50,5 @@ __all__ = [
     "RankedSummary",
     "TargetRanks",
     "PointwiseDensity",
+    "LooDensity",
 ]

@@ -46,6 +46,7 @@ SYMBOLS = [
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
     "mfm_design_logdens_store", "mfm_design_logdens", "mfm_logdens_value",
+    "mfm_design_loo_store", "mfm_design_loo", "mfm_psis_row",
 ]
 
 _lib = None
@@ -174,6 +175,9 @@ def lib():
     L.mfm_design_logdens_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P, P, P]
     L.mfm_design_logdens.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, P, P, P, P, P]
     L.mfm_logdens_value.argtypes = [i32, dbl, dbl, dbl, dbl, i32, P, P]
+    L.mfm_design_loo_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, i32, P, P, P, P, P]
+    L.mfm_design_loo.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, i32, P, P, P, P, P]
+    L.mfm_psis_row.argtypes = [i32, i32, P, P, P, P]
     L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
@@ -615,7 +619,8 @@ class Design:
                           int(tile_rows), int(chunk_samples), _p(mean), _p(std), _p(q)))
         return mean, std, q
 
-    def _log_density(self, src, task, y, precisions, cutpoints, pointwise, tile_rows, chunk_samples):
+    def _log_density_args(self, y, precisions, cutpoints):
+        """(y[N], precisions[S] or None, n_cut, cutpoints[S, n_cut] or None) as mfm_design_logdens* and mfm_design_loo* take them"""
         y = _f64(y).reshape(-1)
         if y.shape[0] != self.N:
             raise ValueError("y must hold one value per design row")
@@ -626,6 +631,10 @@ class Design:
             if cp.ndim != 2:
                 raise ValueError("cutpoints must be a 2-D array, one row of n_cut cutpoints per sample")
             n_cut = cp.shape[1]
+        return y, prec, n_cut, cp
+
+    def _log_density(self, src, task, y, precisions, cutpoints, pointwise, tile_rows, chunk_samples):
+        y, prec, n_cut, cp = self._log_density_args(y, precisions, cutpoints)
         lpd, mean, var = np.empty(self.N), np.empty(self.N), np.empty(self.N)
         pit = np.empty(self.N) if task == TASK_REGRESSION else None
         ll = np.empty((src.S, self.N)) if pointwise else None
@@ -638,6 +647,21 @@ class Design:
         (cutpoints[S][n_cut], y the class labels). Returns (lpd[N], log_lik_mean[N], log_lik_var[N], pit[N] or None,
         log_lik[S, N] or None) of the observed y over the samples (mfm_design_logdens)."""
         return self._log_density(_host(samples), task, y, precisions, cutpoints, pointwise, tile_rows, chunk_samples)
+
+    def _loo(self, src, task, y, precisions, cutpoints, log_weights, r_eff, tile_rows, chunk_samples):
+        y, prec, n_cut, cp = self._log_density_args(y, precisions, cutpoints)
+        elpd, k, lpd = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        pit = np.empty(self.N) if task == TASK_REGRESSION else None
+        lw = np.empty((src.S, self.N)) if log_weights else None
+        self._ck(src.call("mfm_design_loo", self.h, int(task), _p(y), _p(prec), n_cut, _p(cp), int(tile_rows), int(chunk_samples),
+                          psis_tail_len(src.S, r_eff), _p(elpd), _p(k), _p(lpd), _p(pit), _p(lw)))
+        return elpd, k, lpd, pit, lw
+
+    def loo(self, samples, task, y, precisions=None, cutpoints=None, log_weights=False, r_eff=1.0, tile_rows=0, chunk_samples=0):
+        """samples, task, y, precisions and cutpoints as log_density. Returns (elpd_loo[N], pareto_k[N], lpd[N], loo_pit[N] or
+        None, log_weights[S, N] or None): Pareto-smoothed importance-sampling leave-one-out of the observed y over the samples,
+        the tail of ceil(min(0.2 S, 3 sqrt(S / r_eff))) ratios smoothed (mfm_design_loo)."""
+        return self._loo(_host(samples), task, y, precisions, cutpoints, log_weights, r_eff, tile_rows, chunk_samples)
 
     def predict(self, samples, mode=0, cutpoints=None):
         """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
@@ -733,6 +757,19 @@ class Store:
                     chunk_samples=0):
         """Design.log_density over the resident samples [first, first + count) (mfm_design_logdens_store)"""
         return design._log_density(_resident(self, first, count), task, y, precisions, cutpoints, pointwise, tile_rows, chunk_samples)
+
+    def loo(self, design, task, y, precisions=None, cutpoints=None, log_weights=False, r_eff=1.0, first=0, count=None, tile_rows=0,
+            chunk_samples=0):
+        """Design.loo over the resident samples [first, first + count) (mfm_design_loo_store)"""
+        return design._loo(_resident(self, first, count), task, y, precisions, cutpoints, log_weights, r_eff, tile_rows, chunk_samples)
+
+
+def psis_tail_len(S, r_eff=1.0):
+    """the number of importance ratios PSIS smooths: ceil(min(0.2 S, 3 sqrt(S / r_eff)))"""
+    r_eff = float(r_eff)
+    if not (r_eff > 0.0) or not np.isfinite(r_eff):
+        raise ValueError("r_eff must be one finite positive number")
+    return 0 if S <= 1 else int(np.ceil(min(0.2 * S, 3.0 * np.sqrt(S / r_eff))))  # (below 5 nothing is smoothed; the library wants M < S)
 
 
 def _pack_samples(samples):

@@ -588,6 +588,14 @@ struct LearningHistory {
 };
 
 // ---- Predictor (predictor.hpp:14-167) ---------------------------------------------------------------
+// the number of importance ratios PSIS smooths: ceil(min(0.2 S, 3 sqrt(S / r_eff))), r_eff one finite positive number
+constexpr int PSIS_MAX_SAMPLES = 4096;  // (DIST_MAX_S of the library: a row's ratios are sorted in the device's local memory)
+static int32_t psis_tail_len(size_t S, double r_eff) {
+  if (!(r_eff > 0.0) || !std::isfinite(r_eff)) throw std::invalid_argument("r_eff must be one finite positive number");
+  const int32_t M = (int32_t)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / r_eff)));
+  return S == 1 ? 0 : M;  // (one sample: ceil(0.2) = 1 is no tail below the S the library asks for; under 5 nothing is smoothed anyway)
+}
+
 struct Predictor {
   size_t rank, feature_size;
   TaskType type;
@@ -1096,14 +1104,25 @@ struct Predictor {
                      probs.data(), tile_rows, chunk_samples, mean.mutable_data(), sd.mutable_data(), q.mutable_data()));
     return py::make_tuple(mean, sd, q);
   }
-  // Pointwise log predictive density (not in the reference; DESIGN 4.9.2): (lpd[N], log_lik_mean[N], log_lik_var[N], pit[N] or None,
-  // log_lik[S, N] or None) of the observed y under the kept samples. task: this predictor's TaskType as an integer. y as the C entry
-  // point takes it: real (0), 0 / 1 (1), integer class labels (2). precisions[S]: regression; cutpoints: ordered probit, a cutpoint
-  // group index or an (S, n_cut) array. Every argument is checked here, before the device is looked for.
-  py::tuple predict_log_density(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
-                                const py::object &cutpointso, bool pointwise, int64_t tile_rows, int chunk_samples) const {
-    Csr X = csr_from_py(Xo);
-    Relations rels = relations_from_py(relso);
+  // What predict_log_density and predict_loo take besides their switches, converted and checked before the device is looked for.
+  // task: this predictor's TaskType as an integer. y as the C entry points take it: real (0), 0 / 1 (1), integer class labels (2).
+  // precisions[S]: regression; cutpoints: ordered probit, a cutpoint group index or an (S, n_cut) array.
+  struct DensityArgs {
+    Csr X;
+    Relations rels;
+    py::array_t<double, py::array::c_style | py::array::forcecast> y;
+    vector<double> prec;
+    Cutpoints cp;
+    const double *precisions() const { return prec.empty() ? nullptr : prec.data(); }
+    const double *cutpoints() const { return cp.n_cut ? cp.cuts.data() : nullptr; }
+  };
+  DensityArgs density_args(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
+                           const py::object &cutpointso, int64_t tile_rows, int chunk_samples) const {
+    DensityArgs a;
+    Csr &X = a.X = csr_from_py(Xo);
+    Relations &rels = a.rels = relations_from_py(relso);
+    vector<double> &prec = a.prec;
+    Cutpoints &cp = a.cp;
     check_input(X, rels);
     if (task < 0 || task > 2) throw std::invalid_argument("bad task (0: regression, 1: probit classification, 2: ordered probit)");
     if (task != static_cast<int>(type)) throw std::invalid_argument("task does not match the task this predictor was fitted for");
@@ -1112,7 +1131,6 @@ struct Predictor {
     const size_t S = samples.size();
     auto ya = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(yo);
     if (!ya || ya.ndim() != 1 || (size_t)ya.shape(0) != (size_t)X.rows) throw std::invalid_argument("y must hold one value per row of X");
-    vector<double> prec;
     if (!precisionso.is_none()) {
       if (type != TaskType::REGRESSION) throw std::invalid_argument("noise precisions apply to regression only");
       auto pa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(precisionso);
@@ -1123,7 +1141,6 @@ struct Predictor {
     } else if (type == TaskType::REGRESSION) {
       throw std::invalid_argument("a regression log density needs the noise precision of every kept sample");
     }
-    Cutpoints cp;
     if (!cutpointso.is_none()) {
       if (type != TaskType::ORDERED) throw std::invalid_argument("cutpoints apply to ordered probit only");
       if (py::isinstance<py::int_>(cutpointso) && !py::isinstance<py::bool_>(cutpointso)) {
@@ -1156,25 +1173,61 @@ struct Predictor {
       if (type == TaskType::ORDERED && (y != std::floor(y) || y < 0.0 || y > (double)cp.n_cut))
         throw std::invalid_argument("ordered-probit labels must be integers in [0, " + std::to_string(cp.n_cut) + "]");
     }
-    const py::ssize_t N = (py::ssize_t)X.rows;
+    a.y = ya;
+    return a;
+  }
+  // Pointwise log predictive density (not in the reference; DESIGN 4.9.2): (lpd[N], log_lik_mean[N], log_lik_var[N], pit[N] or None,
+  // log_lik[S, N] or None) of the observed y under the kept samples; the arguments of density_args.
+  py::tuple predict_log_density(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
+                                const py::object &cutpointso, bool pointwise, int64_t tile_rows, int chunk_samples) const {
+    const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
+    const py::ssize_t N = (py::ssize_t)a.X.rows, S = (py::ssize_t)samples.size();
     py::array_t<double> lpd(N), mean(N), var(N);
     py::object pit = py::none(), ll = py::none();
     double *pit_p = nullptr, *ll_p = nullptr;
     if (type == TaskType::REGRESSION) {
-      py::array_t<double> a(N);
-      pit_p = a.mutable_data();
-      pit = a;
+      py::array_t<double> out(N);
+      pit_p = out.mutable_data();
+      pit = out;
     }
     if (pointwise) {
-      py::array_t<double> a({(py::ssize_t)S, N});
-      ll_p = a.mutable_data();
-      ll = a;
+      py::array_t<double> out({S, N});
+      ll_p = out.mutable_data();
+      ll = out;
     }
-    DeviceDesign dd(X, rels);
-    dd.ck(on_samples(mfm_design_logdens_store, mfm_design_logdens, dd.d, (int32_t)task, ya.data(), prec.empty() ? (const double *)nullptr : prec.data(),
-                     (int32_t)cp.n_cut, cp.n_cut ? cp.cuts.data() : (const double *)nullptr, tile_rows, (int32_t)chunk_samples, lpd.mutable_data(),
-                     mean.mutable_data(), var.mutable_data(), pit_p, ll_p));
+    DeviceDesign dd(a.X, a.rels);
+    dd.ck(on_samples(mfm_design_logdens_store, mfm_design_logdens, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
+                     a.cutpoints(), tile_rows, (int32_t)chunk_samples, lpd.mutable_data(), mean.mutable_data(), var.mutable_data(), pit_p, ll_p));
     return py::make_tuple(lpd, mean, var, pit, ll);
+  }
+  // Pareto-smoothed leave-one-out (not in the reference): (elpd_loo[N], pareto_k[N], lpd[N], loo_pit[N] or None,
+  // log_weights[S, N] or None) of the observed y under the kept samples; the arguments of density_args, and the relative efficiency
+  // of the draws that sets the length of the smoothed tail.
+  py::tuple predict_loo(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
+                        const py::object &cutpointso, bool log_weights, double r_eff, int64_t tile_rows, int chunk_samples) const {
+    const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
+    const py::ssize_t N = (py::ssize_t)a.X.rows, S = (py::ssize_t)samples.size();
+    const int32_t tail_len = psis_tail_len((size_t)S, r_eff);
+    if (S > PSIS_MAX_SAMPLES)
+      throw std::invalid_argument("leave-one-out weights are computed over at most " + std::to_string(PSIS_MAX_SAMPLES) +
+                                  " kept samples, this model keeps " + std::to_string(S));
+    py::array_t<double> elpd(N), khat(N), lpd(N);
+    py::object pit = py::none(), lw = py::none();
+    double *pit_p = nullptr, *lw_p = nullptr;
+    if (type == TaskType::REGRESSION) {
+      py::array_t<double> out(N);
+      pit_p = out.mutable_data();
+      pit = out;
+    }
+    if (log_weights) {
+      py::array_t<double> out({S, N});
+      lw_p = out.mutable_data();
+      lw = out;
+    }
+    DeviceDesign dd(a.X, a.rels);
+    dd.ck(on_samples(mfm_design_loo_store, mfm_design_loo, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut, a.cutpoints(),
+                     tile_rows, (int32_t)chunk_samples, tail_len, elpd.mutable_data(), khat.mutable_data(), lpd.mutable_data(), pit_p, lw_p));
+    return py::make_tuple(elpd, khat, lpd, pit, lw);
   }
   // predictor.hpp:78-124
   py::array_t<double> predict_parallel_oprobit(const py::object &Xo, const py::object &relso, size_t n_workers,
@@ -2981,6 +3034,9 @@ PYBIND11_MODULE(_myfm, m) {
       .def("predict_log_density", &Predictor::predict_log_density, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
            py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("pointwise") = false, py::arg("tile_rows") = 0,
            py::arg("chunk_samples") = 0)
+      .def("predict_loo", &Predictor::predict_loo, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
+           py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("log_weights") = false, py::arg("r_eff") = 1.0,
+           py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def(py::pickle(
           [](const Predictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {
@@ -3226,6 +3282,22 @@ PYBIND11_MODULE(_myfm, m) {
       },
       py::arg("task"), py::arg("y"), py::arg("score"), py::arg("log_norm") = 0.0, py::arg("sqrt_alpha") = 0.0,
       py::arg("cutpoints_row") = py::none());
+
+  // PSIS of one row of log likelihoods on the host, by the scalar pieces k_row_psis runs on the device (csrc/mfm_psis.hpp):
+  // (elpd_loo, pareto_k, log_weights[S])
+  m.def(
+      "psis_row",
+      [](const py::array_t<double, py::array::c_style | py::array::forcecast> &log_lik, double r_eff) {
+        if (log_lik.ndim() != 1 || log_lik.shape(0) < 1) throw std::invalid_argument("log_lik must be a non-empty 1-D array");
+        const py::ssize_t S = log_lik.shape(0);
+        const int32_t tail_len = psis_tail_len((size_t)S, r_eff);
+        py::array_t<double> lw(S);
+        double elpd = 0.0, k = 0.0;
+        const int code = mfm_psis_row((int32_t)S, tail_len, log_lik.data(), &elpd, &k, lw.mutable_data());
+        if (code != MFM_OK) throw_code(code, mfm_global_error());
+        return py::make_tuple(elpd, k, lw);
+      },
+      py::arg("log_lik"), py::arg("r_eff") = 1.0);
 
   // extensions beyond the reference's surface (bench / tests)
   py::class_<GibbsSession>(m, "GibbsSession")

@@ -69,6 +69,21 @@ __host__ __device__ __forceinline__ double logdens_value(double y, double score,
   }
 }
 
+// One step of the streaming log-sum-exp in sample order, for sample s with value l: the running maximum m and acc = sum exp(l - m),
+// rescaled when m moves, one exp per sample; lpd = m + log(acc) - log S. The one text of k_row_logdens and of k_row_psis
+// (mfm_psis.hpp), which must give lpd the same bits. A macro and not a function: as an inlined function the same statements left
+// k_row_logdens with other registers and another instruction order than the parent commit's, as a macro its listing is the
+// parent's instruction for instruction.
+#define MFM_LOGDENS_LSE_STEP(s, l, m, acc)                                                                                  \
+  if (s == 0) {                                                                                                             \
+    m = l;                                                                                                                  \
+    acc = 1.0;                                                                                                              \
+  } else {                                                                                                                  \
+    const double e = l == m ? 1.0 : exp(-fabs(l - m)); /* (l = m = -inf: a density of 0 under every sample so far) */      \
+    acc = l > m ? acc * e + 1.0 : acc + e;                                                                                  \
+    m = fmax(m, l);                                                                                                         \
+  }
+
 struct RowLogdensArgs {
   double *scratch;    // [S][Tn] the tile's scores; KEEP: l in their place on exit
   const double *y;    // of the tile's first row
@@ -118,14 +133,7 @@ __global__ __launch_bounds__(WG) void k_row_logdens(RowLogdensArgs a) {
         l = logdens_value<TASK>(yt, score, 0.0, 0.0, aux + (size_t)s * n_cut, n_cut);
       }
       if (KEEP) col[(size_t)s * Tn] = l;
-      if (s == 0) {
-        m = l;
-        acc = 1.0;
-      } else {
-        const double e = l == m ? 1.0 : exp(-fabs(l - m));  // (l = m = -inf: a density of 0 under every sample so far)
-        acc = l > m ? acc * e + 1.0 : acc + e;
-        m = fmax(m, l);
-      }
+      MFM_LOGDENS_LSE_STEP(s, l, m, acc)
       sum += l;
       const double delta = l - wmean;
       wmean += delta / (double)(s + 1);
@@ -208,6 +216,35 @@ static void logdens_check(const LogdensCall &c, int64_t N, int count) {
   }
 }
 
+// The targets of the N rows into d->dist_y and the task's per-sample constants onto the device (design_logdens, and design_loo of
+// mfm_psis.hpp): where they are, and how many doubles.
+struct LogdensConstants {
+  const double *aux;
+  size_t n_aux;
+};
+static LogdensConstants logdens_upload(mfm_design *d, hipStream_t s, const LogdensCall &c, int64_t N, int count) {
+  if (d->dist_y.n < (size_t)N) d->dist_y.alloc((size_t)N);
+  MFM_HIP_CHECK(hipMemcpyAsync(d->dist_y.p, c.y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s));
+  if (c.task == LOGDENS_REGRESSION) {
+    const size_t n_aux = 2 * (size_t)count;
+    std::vector<double> aux(n_aux);
+    for (int k = 0; k < count; k++) {
+      aux[(size_t)k] = 0.5 * std::log(c.precisions[k]) - 0.91893853320467274178;  // log(2 pi) / 2
+      aux[(size_t)count + k] = std::sqrt(c.precisions[k]);
+    }
+    if (d->dist_aux.n < n_aux) d->dist_aux.alloc(n_aux);
+    MFM_HIP_CHECK(hipMemcpy(d->dist_aux.p, aux.data(), n_aux * sizeof(double), hipMemcpyHostToDevice));
+    return {d->dist_aux.p, n_aux};
+  }
+  if (c.task == LOGDENS_ORDERED) {
+    const size_t n_aux = (size_t)count * c.n_cut;
+    if (d->cut.n < n_aux) d->cut.alloc(n_aux);
+    MFM_HIP_CHECK(hipMemcpyAsync(d->cut.p, c.cutpoints, n_aux * sizeof(double), hipMemcpyHostToDevice, s));
+    return {d->cut.p, n_aux};
+  }
+  return {nullptr, 0};
+}
+
 static void design_logdens(mfm_design *d, const SampleView &v, const LogdensCall &c) {
   const int count = v.count();
   if (v.device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
@@ -220,8 +257,7 @@ static void design_logdens(mfm_design *d, const SampleView &v, const LogdensCall
   if (d->dist_scratch.n < (size_t)(T * count)) d->dist_scratch.alloc((size_t)(T * count));
   const size_t n_out = c.task == LOGDENS_REGRESSION ? 4 : 3;  // lpd, mean, var, pit
   if (d->dist_out.n < (size_t)N * n_out) d->dist_out.alloc((size_t)N * n_out);
-  if (d->dist_y.n < (size_t)N) d->dist_y.alloc((size_t)N);
-  MFM_HIP_CHECK(hipMemcpyAsync(d->dist_y.p, c.y, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s));
+  const LogdensConstants k = logdens_upload(d, s, c, N, count);
   RowLogdensArgs a;
   std::memset(&a, 0, sizeof(a));
   a.scratch = d->dist_scratch.p;
@@ -229,25 +265,9 @@ static void design_logdens(mfm_design *d, const SampleView &v, const LogdensCall
   a.inv_S = 1.0 / count;
   a.inv_Sm1 = count > 1 ? 1.0 / (count - 1) : 0.0;
   a.log_S = std::log((double)count);
-  size_t n_aux = 0;
-  if (c.task == LOGDENS_REGRESSION) {
-    n_aux = 2 * (size_t)count;
-    std::vector<double> aux(n_aux);
-    for (int k = 0; k < count; k++) {
-      aux[(size_t)k] = 0.5 * std::log(c.precisions[k]) - 0.91893853320467274178;  // log(2 pi) / 2
-      aux[(size_t)count + k] = std::sqrt(c.precisions[k]);
-    }
-    if (d->dist_aux.n < n_aux) d->dist_aux.alloc(n_aux);
-    MFM_HIP_CHECK(hipMemcpy(d->dist_aux.p, aux.data(), n_aux * sizeof(double), hipMemcpyHostToDevice));
-    a.aux = d->dist_aux.p;
-  } else if (c.task == LOGDENS_ORDERED) {
-    n_aux = (size_t)count * c.n_cut;
-    if (d->cut.n < n_aux) d->cut.alloc(n_aux);
-    MFM_HIP_CHECK(hipMemcpyAsync(d->cut.p, c.cutpoints, n_aux * sizeof(double), hipMemcpyHostToDevice, s));
-    a.aux = d->cut.p;
-    a.n_cut = c.n_cut;
-  }
-  a.aux_lds = n_aux > 0 && n_aux * sizeof(double) <= (size_t)LOGDENS_LDS_BYTES;
+  a.aux = k.aux;
+  a.n_cut = c.task == LOGDENS_ORDERED ? c.n_cut : 0;
+  a.aux_lds = k.n_aux > 0 && k.n_aux * sizeof(double) <= (size_t)LOGDENS_LDS_BYTES;
   DistStage1 st = dist_stage1_begin(d, s, v, c.chunk_samples);
   for (int64_t r0 = 0; r0 < N; r0 += T) {
     const int64_t Tn = std::min<int64_t>(T, N - r0);

@@ -394,7 +394,7 @@ class _LogDensityMixin:
         the sample variance (ddof = 1) of the l_s, WAIC's penalty (exactly 0 for one kept sample). pit (N,), regressor only (else
         None): the predictive CDF at y, mean_s Phi((y - score_s) sqrt(alpha_s)), uniform on [0, 1] for a calibrated model.
         log_lik (S, N), only with pointwise=True (else None and nothing of that size exists on the host): the l_s themselves,
-        for PSIS-LOO or arviz. The tails are evaluated without forming Phi: finite wherever the scores are.
+        for arviz or one's own estimators (PSIS-LOO itself runs on the device: predict_loo). The tails are evaluated without forming Phi: finite wherever the scores are.
 
         y (N,) as fit takes it: real targets, 0 / 1 or bool labels, integer classes in [0, n_class) (MyFMOrderedProbit also takes
         cutpoint_index, the cutpoint group). See myfm_amd.utils.evaluation for waic, log_score and pit_histogram.
@@ -403,6 +403,11 @@ class _LogDensityMixin:
         return self._predict_log_density(X, y, X_rel, pointwise, None)
 
     def _predict_log_density(self, X, y, X_rel, pointwise, cutpoint_index):
+        predictor, args = self._log_density_args(X, y, X_rel, cutpoint_index, "predict_log_density")
+        return PointwiseDensity(*predictor.predict_log_density(*args, bool(pointwise)))
+
+    def _log_density_args(self, X, y, X_rel, cutpoint_index, what):
+        """(predictor, (X, X_rel, y, task, precisions, cutpoints)): what predict_log_density and predict_loo hand to the predictor"""
         predictor = self._fetch_predictor()
         n = check_data_consistency(X, X_rel)
         X = _as_csr(X, n)
@@ -416,15 +421,58 @@ class _LogDensityMixin:
         y = self._process_y(y) if y.shape[0] else y.astype(REAL)
         precisions = cutpoints = None
         if self._task_type == TaskType.REGRESSION:
-            precisions = _kept_precisions(self, len(predictor.samples), "predict_log_density")
+            precisions = _kept_precisions(self, len(predictor.samples), what)
         elif self._task_type == TaskType.CLASSIFICATION:
             y = (y + 1) / 2  # (fit's -1 / +1 back to the 0 / 1 the device call takes)
         else:
             if isinstance(cutpoint_index, bool) or not isinstance(cutpoint_index, (int, np.integer)):
                 raise ValueError("cutpoint_index must be an integer")
             cutpoints = int(cutpoint_index)
-        return PointwiseDensity(*predictor.predict_log_density(X, list(X_rel), np.ascontiguousarray(y, dtype=REAL), int(self._task_type),
-                                                               precisions, cutpoints, bool(pointwise)))
+        return predictor, (X, list(X_rel), np.ascontiguousarray(y, dtype=REAL), int(self._task_type), precisions, cutpoints)
+
+
+LooDensity = namedtuple("LooDensity", ["elpd_loo", "pareto_k", "lpd", "loo_pit", "log_weights"])
+PREDICT_LOO_MAX_SAMPLES = PREDICT_DIST_MAX_SAMPLES  # a row's importance ratios are sorted in the device's local memory
+
+
+class _LooMixin(_LogDensityMixin):
+    """Pareto-smoothed importance-sampling leave-one-out of a fitted Gibbs regressor, classifier or ordered probit (DESIGN
+    4.9.3), after Vehtari, Gelman and Gabry (2017) and Vehtari et al. (2024). Limits: one relative efficiency r_eff for all rows
+    (none per row, none estimated from the chain); no moment matching or refit for rows with a large k; at most 4096 kept samples;
+    no variational estimator; not row-sharded (the model is replicated: each rank may call it on its own rows)."""
+
+    def predict_loo(self, X, y, X_rel=[], log_weights=False, r_eff=1.0):
+        """LooDensity(elpd_loo, pareto_k, lpd, loo_pit, log_weights) per row over the S kept samples, computed on the device in one
+        pass over the rows. The leave-one-out reading holds when X, y are rows the model was fitted on: the importance ratios
+        1 / p(y | sample s) then turn the posterior into the posterior without that row. For other rows the numbers are still
+        computed, but they estimate nothing.
+
+        With l_s = log p(y | sample s) as predict_log_density takes it, the largest M = ceil(min(0.2 S, 3 sqrt(S / r_eff))) ratios
+        are replaced by the quantiles of a generalized Pareto distribution fitted to them and the weights w_s are normalised.
+        elpd_loo (N,): log sum_s w_s p(y | sample s). pareto_k (N,): the shape k of the fit, the diagnostic (see
+        myfm_amd.utils.evaluation.loo for the threshold); +inf where no fit was made: M < 5 (S < 25 at r_eff = 1), a tail whose lower
+        quarter equals the cutoff, or a sample under which y has density 0 (then elpd_loo = -inf). lpd (N,): bit for bit
+        predict_log_density(X, y).lpd, so that p_loo = lpd - elpd_loo needs no second call. loo_pit (N,), regressor only (else
+        None): sum_s w_s Phi((y - score_s) sqrt(alpha_s)); pit_histogram(result.loo_pit) takes it. log_weights (S, N), only with
+        log_weights=True (else None and nothing of that size exists on the host): log w_s.
+
+        r_eff: the relative efficiency of the draws, one finite positive number (1: independent draws), used for M alone. At most
+        4096 kept samples. X, y, X_rel (MyFMOrderedProbit: cutpoint_index) as predict_log_density takes and checks them; all
+        arguments are checked on the host before the device is touched."""
+        return self._predict_loo(X, y, X_rel, log_weights, r_eff, None)
+
+    def _predict_loo(self, X, y, X_rel, log_weights, r_eff, cutpoint_index):
+        if not isinstance(log_weights, (bool, np.bool_)):
+            raise ValueError("log_weights must be a bool")
+        if isinstance(r_eff, (bool, np.bool_)) or not isinstance(r_eff, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(r_eff) or not r_eff > 0:
+            raise ValueError("r_eff must be one finite positive number")
+        predictor, args = self._log_density_args(X, y, X_rel, cutpoint_index, "predict_loo")
+        n_samples = len(predictor.samples)
+        if n_samples > PREDICT_LOO_MAX_SAMPLES:
+            raise ValueError("leave-one-out weights are computed over at most %d kept samples, this model keeps %d"
+                             % (PREDICT_LOO_MAX_SAMPLES, n_samples))
+        return LooDensity(*predictor.predict_loo(*args, bool(log_weights), float(r_eff)))
 
 
 def _ranked_args(Xq, Xc, k, exclude, beta=0.0):
@@ -742,7 +790,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LogDensityMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -810,7 +858,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDi
         return _folded_in(self, predictor.extended(w_new, V_new), D, U)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LogDensityMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -886,7 +934,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LogDensityMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""
@@ -985,6 +1033,10 @@ class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LogDensityMix
         """_LogDensityMixin.predict_log_density with the cutpoint group to use: y (N,) holds integer class labels in [0, n_class),
         n_class the number of cutpoints of group `cutpoint_index` of the kept samples plus one."""
         return self._predict_log_density(X, y, X_rel, pointwise, cutpoint_index)
+
+    def predict_loo(self, X, y, X_rel=[], log_weights=False, r_eff=1.0, cutpoint_index=0):
+        """_LooMixin.predict_loo with the cutpoint group to use, as predict_log_density takes it."""
+        return self._predict_loo(X, y, X_rel, log_weights, r_eff, cutpoint_index)
 
     @property
     def cutpoint_samples(self):

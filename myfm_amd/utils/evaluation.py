@@ -1,4 +1,5 @@
-"""Model evaluation from the pointwise log predictive density (predict_log_density). Pure NumPy."""
+"""Model evaluation from the pointwise log predictive density (predict_log_density) and from Pareto-smoothed
+leave-one-out (predict_loo). Pure NumPy."""
 import numpy as np
 
 WAIC_HIGH_VARIANCE = 0.4  # a row whose log-likelihood variance exceeds this makes WAIC unreliable (Vehtari, Gelman, Gabry 2017)
@@ -35,7 +36,8 @@ def log_score(result):
 def pit_histogram(result, bins=10):
     """Calibration of a regression model from the probability integral transform: (counts, chi2), the counts of pit in `bins`
     equal cells of [0, 1] and the chi-square statistic sum (count - N / bins)^2 / (N / bins) against the uniform distribution
-    (bins - 1 degrees of freedom). `result`: a PointwiseDensity of a regressor, or the pit values themselves."""
+    (bins - 1 degrees of freedom). `result`: a PointwiseDensity of a regressor, or the pit values themselves -- for the
+    leave-one-out transform of predict_loo pass result.loo_pit."""
     pit = getattr(result, "pit", result)
     if pit is None:
         raise ValueError("the probability integral transform exists for regression only")
@@ -47,3 +49,48 @@ def pit_histogram(result, bins=10):
     counts, _ = np.histogram(pit, bins=int(bins), range=(0.0, 1.0))
     expected = pit.shape[0] / int(bins)
     return counts, float(((counts - expected) ** 2).sum() / expected)
+
+
+def pareto_k_threshold(n_samples):
+    """Above this k the PSIS estimate of a row is unreliable at S draws: min(1 - 1 / log10(S), 0.7) (Vehtari et al. 2024)"""
+    return min(1.0 - 1.0 / np.log10(n_samples), 0.7)
+
+
+def loo(result, n_samples):
+    """Leave-one-out cross-validation from a LooDensity `result` of predict_loo (or any tuple that starts with elpd_loo, pareto_k,
+    lpd) over `n_samples` kept samples, after Vehtari, Gelman and Gabry (2017). Returns a dict:
+
+        elpd_loo            sum_t elpd_loo_t, the expected log pointwise predictive density
+        p_loo               sum_t (lpd_t - elpd_loo_t), the effective number of parameters
+        looic               -2 elpd_loo
+        se                  sqrt(N var_t elpd_loo_t), the standard error of elpd_loo (population variance over the rows)
+        pareto_k_threshold  min(1 - 1 / log10(S), 0.7)
+        n_bad_k             the number of rows whose k exceeds the threshold (+inf, where no fit was made, counts)
+
+    For a regressor, pit_histogram(result.loo_pit) gives the calibration of the leave-one-out predictive distributions."""
+    elpd = np.asarray(result[0], dtype=np.float64)
+    k = np.asarray(result[1], dtype=np.float64)
+    lpd = np.asarray(result[2], dtype=np.float64)
+    if elpd.ndim != 1 or elpd.shape != k.shape or elpd.shape != lpd.shape:
+        raise ValueError("elpd_loo, pareto_k and lpd must be 1-D arrays of one length")
+    if isinstance(n_samples, bool) or int(n_samples) != n_samples or n_samples < 2:
+        raise ValueError("n_samples must be an integer of at least 2")
+    total = float(elpd.sum())
+    n = elpd.shape[0]
+    threshold = pareto_k_threshold(int(n_samples))
+    return {"elpd_loo": total, "p_loo": float((lpd - elpd).sum()), "looic": -2.0 * total,
+            "se": float(np.sqrt(n * np.var(elpd))) if n else float("nan"), "pareto_k_threshold": threshold,
+            "n_bad_k": int(np.count_nonzero(k > threshold))}
+
+
+def compare(a, b):
+    """The difference of two models' expected log predictive densities over the same rows: `a` and `b` are LooDensity results (or
+    the pointwise elpd arrays themselves). Returns a dict: elpd_diff = sum_t (a_t - b_t), positive where `a` predicts better, and
+    se_diff = sqrt(N var_t(a_t - b_t)) (population variance over the rows)."""
+    ea = np.asarray(getattr(a, "elpd_loo", a), dtype=np.float64)
+    eb = np.asarray(getattr(b, "elpd_loo", b), dtype=np.float64)
+    if ea.ndim != 1 or eb.ndim != 1 or ea.shape != eb.shape:
+        raise ValueError("the two results must hold one value per row of the same rows")
+    d = ea - eb
+    n = d.shape[0]
+    return {"elpd_diff": float(d.sum()), "se_diff": float(np.sqrt(n * np.var(d))) if n else float("nan")}
