@@ -1039,13 +1039,46 @@ struct Predictor {
     }
     return probs;
   }
-  // ... and, after a method's own checks, the limits of the device passes
-  void check_summary_limits(size_t n_q, int64_t tile_rows, int chunk_samples) const {
+  // ... and, after a method's own checks, the limits of the device passes: those of every tiled pass, and the summaries' own
+  void check_tiled_pass(int64_t tile_rows, int chunk_samples) const {
     if (tile_rows < 0 || chunk_samples < 0) throw std::invalid_argument("tile_rows and chunk_samples must be non-negative");
     if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
+  }
+  void check_summary_limits(size_t n_q, int64_t tile_rows, int chunk_samples) const {
+    check_tiled_pass(tile_rows, chunk_samples);
     if (n_q > 0 && samples.size() > 4096)
       throw std::invalid_argument("quantiles are computed over at most 4096 kept samples, this predictor holds " + std::to_string(samples.size()));
   }
+  // The noise precisions of a call that gives them: regression only, 1-D, one per kept sample, positive and finite
+  vector<double> noise_precisions(const py::object &precisionso) const {
+    if (type != TaskType::REGRESSION) throw std::invalid_argument("noise precisions apply to regression only");
+    auto pa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(precisionso);
+    if (!pa || pa.ndim() != 1 || (size_t)pa.shape(0) != samples.size())
+      throw std::invalid_argument("precisions must hold one value per kept sample");
+    for (py::ssize_t k = 0; k < pa.shape(0); k++)
+      if (!(pa.data()[k] > 0.0) || !std::isfinite(pa.data()[k])) throw std::invalid_argument("precisions must be positive and finite");
+    return vector<double>(pa.data(), pa.data() + pa.shape(0));
+  }
+  // Cutpoint group g of every kept sample (there is one), as the summaries and the log densities refuse a bad g
+  Cutpoints cutpoint_group(int64_t g) const {
+    Cutpoints cp = gather_cutpoints(g);
+    if (cp.bad && cp.at == 0)
+      throw std::invalid_argument("cutpoint_index " + std::to_string(g) + " out of range: the model has " +
+                                  std::to_string(samples[0].cutpoints.size()) + " cutpoint group(s)");
+    if (cp.bad) throw std::invalid_argument("inconsistent cutpoint sizes among samples.");
+    return cp;
+  }
+  // An output that a call may leave out: the array and its data, or None and null
+  struct OptionalOut {
+    py::object array = py::none();
+    double *p = nullptr;
+    OptionalOut(bool wanted, const std::vector<py::ssize_t> &shape) {
+      if (!wanted) return;
+      py::array_t<double> out(shape);
+      p = out.mutable_data();
+      array = out;
+    }
+  };
   // (mean[N], std[N], quantiles[Q, N]); precisions: the noise precision alpha_s of every sample (regression), or None.
   // tile_rows / chunk_samples force the device passes' row tile and sample chunk (0: automatic). Every argument is checked here,
   // before the device is looked for.
@@ -1059,13 +1092,7 @@ struct Predictor {
     const vector<double> probs = quantile_probs(quantileso, noise);
     vector<double> prec, z;
     if (noise) {
-      if (type != TaskType::REGRESSION) throw std::invalid_argument("noise precisions apply to regression only");
-      auto pa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(precisionso);
-      if (!pa || pa.ndim() != 1 || (size_t)pa.shape(0) != samples.size())
-        throw std::invalid_argument("precisions must hold one value per kept sample");
-      prec.assign(pa.data(), pa.data() + pa.shape(0));
-      for (double a : prec)
-        if (!(a > 0.0) || !std::isfinite(a)) throw std::invalid_argument("precisions must be positive and finite");
+      prec = noise_precisions(precisionso);
       for (double p : probs) z.push_back(std_normal_quantile(p));
     }
     const int n_q = (int)probs.size();
@@ -1089,11 +1116,7 @@ struct Predictor {
     const vector<double> probs = quantile_probs(quantileso);
     const int n_q = (int)probs.size();
     check_summary_limits(probs.size(), tile_rows, chunk_samples);
-    const Cutpoints cp = gather_cutpoints(cutpoint_idx);
-    if (cp.bad && cp.at == 0)
-      throw std::invalid_argument("cutpoint_index " + std::to_string(cutpoint_idx) + " out of range: the model has " +
-                                  std::to_string(samples[0].cutpoints.size()) + " cutpoint group(s)");
-    if (cp.bad) throw std::invalid_argument("inconsistent cutpoint sizes among samples.");
+    const Cutpoints cp = cutpoint_group(cutpoint_idx);
     const py::ssize_t N = (py::ssize_t)X.rows, C = (py::ssize_t)cp.n_cut + 1;
     const std::vector<py::ssize_t> shape = expected ? std::vector<py::ssize_t>{N} : std::vector<py::ssize_t>{N, C};
     std::vector<py::ssize_t> qshape = shape;
@@ -1126,30 +1149,19 @@ struct Predictor {
     check_input(X, rels);
     if (task < 0 || task > 2) throw std::invalid_argument("bad task (0: regression, 1: probit classification, 2: ordered probit)");
     if (task != static_cast<int>(type)) throw std::invalid_argument("task does not match the task this predictor was fitted for");
-    if (tile_rows < 0 || chunk_samples < 0) throw std::invalid_argument("tile_rows and chunk_samples must be non-negative");
-    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
+    check_tiled_pass(tile_rows, chunk_samples);
     const size_t S = samples.size();
     auto ya = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(yo);
     if (!ya || ya.ndim() != 1 || (size_t)ya.shape(0) != (size_t)X.rows) throw std::invalid_argument("y must hold one value per row of X");
     if (!precisionso.is_none()) {
-      if (type != TaskType::REGRESSION) throw std::invalid_argument("noise precisions apply to regression only");
-      auto pa = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(precisionso);
-      if (!pa || pa.ndim() != 1 || (size_t)pa.shape(0) != S) throw std::invalid_argument("precisions must hold one value per kept sample");
-      prec.assign(pa.data(), pa.data() + pa.shape(0));
-      for (double a : prec)
-        if (!(a > 0.0) || !std::isfinite(a)) throw std::invalid_argument("precisions must be positive and finite");
+      prec = noise_precisions(precisionso);
     } else if (type == TaskType::REGRESSION) {
       throw std::invalid_argument("a regression log density needs the noise precision of every kept sample");
     }
     if (!cutpointso.is_none()) {
       if (type != TaskType::ORDERED) throw std::invalid_argument("cutpoints apply to ordered probit only");
       if (py::isinstance<py::int_>(cutpointso) && !py::isinstance<py::bool_>(cutpointso)) {
-        const int64_t g = cutpointso.cast<int64_t>();
-        cp = gather_cutpoints(g);
-        if (cp.bad && cp.at == 0)
-          throw std::invalid_argument("cutpoint_index " + std::to_string(g) + " out of range: the model has " +
-                                      std::to_string(samples[0].cutpoints.size()) + " cutpoint group(s)");
-        if (cp.bad) throw std::invalid_argument("inconsistent cutpoint sizes among samples.");
+        cp = cutpoint_group(cutpointso.cast<int64_t>());
       } else {
         auto ca = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(cutpointso);
         if (!ca || ca.ndim() != 2 || (size_t)ca.shape(0) != S || ca.shape(1) < 1)
@@ -1183,22 +1195,11 @@ struct Predictor {
     const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
     const py::ssize_t N = (py::ssize_t)a.X.rows, S = (py::ssize_t)samples.size();
     py::array_t<double> lpd(N), mean(N), var(N);
-    py::object pit = py::none(), ll = py::none();
-    double *pit_p = nullptr, *ll_p = nullptr;
-    if (type == TaskType::REGRESSION) {
-      py::array_t<double> out(N);
-      pit_p = out.mutable_data();
-      pit = out;
-    }
-    if (pointwise) {
-      py::array_t<double> out({S, N});
-      ll_p = out.mutable_data();
-      ll = out;
-    }
+    const OptionalOut pit(type == TaskType::REGRESSION, {N}), ll(pointwise, {S, N});
     DeviceDesign dd(a.X, a.rels);
     dd.ck(on_samples(mfm_design_logdens_store, mfm_design_logdens, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
-                     a.cutpoints(), tile_rows, (int32_t)chunk_samples, lpd.mutable_data(), mean.mutable_data(), var.mutable_data(), pit_p, ll_p));
-    return py::make_tuple(lpd, mean, var, pit, ll);
+                     a.cutpoints(), tile_rows, (int32_t)chunk_samples, lpd.mutable_data(), mean.mutable_data(), var.mutable_data(), pit.p, ll.p));
+    return py::make_tuple(lpd, mean, var, pit.array, ll.array);
   }
   // Pareto-smoothed leave-one-out (not in the reference): (elpd_loo[N], pareto_k[N], lpd[N], loo_pit[N] or None,
   // log_weights[S, N] or None) of the observed y under the kept samples; the arguments of density_args, and the relative efficiency
@@ -1212,22 +1213,11 @@ struct Predictor {
       throw std::invalid_argument("leave-one-out weights are computed over at most " + std::to_string(PSIS_MAX_SAMPLES) +
                                   " kept samples, this model keeps " + std::to_string(S));
     py::array_t<double> elpd(N), khat(N), lpd(N);
-    py::object pit = py::none(), lw = py::none();
-    double *pit_p = nullptr, *lw_p = nullptr;
-    if (type == TaskType::REGRESSION) {
-      py::array_t<double> out(N);
-      pit_p = out.mutable_data();
-      pit = out;
-    }
-    if (log_weights) {
-      py::array_t<double> out({S, N});
-      lw_p = out.mutable_data();
-      lw = out;
-    }
+    const OptionalOut pit(type == TaskType::REGRESSION, {N}), lw(log_weights, {S, N});
     DeviceDesign dd(a.X, a.rels);
     dd.ck(on_samples(mfm_design_loo_store, mfm_design_loo, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut, a.cutpoints(),
-                     tile_rows, (int32_t)chunk_samples, tail_len, elpd.mutable_data(), khat.mutable_data(), lpd.mutable_data(), pit_p, lw_p));
-    return py::make_tuple(elpd, khat, lpd, pit, lw);
+                     tile_rows, (int32_t)chunk_samples, tail_len, elpd.mutable_data(), khat.mutable_data(), lpd.mutable_data(), pit.p, lw.p));
+    return py::make_tuple(elpd, khat, lpd, pit.array, lw.array);
   }
   // predictor.hpp:78-124
   py::array_t<double> predict_parallel_oprobit(const py::object &Xo, const py::object &relso, size_t n_workers,

@@ -5,9 +5,10 @@
 // from the stored scores where stage 2 reads them (the load transform of k_row_summary). Included by mfm_hip.hip after
 // mfm_predict.hpp.
 //
-// Rows are processed in tiles of T rows. Stage 1 writes the values of a tile, all samples, into a sample-major scratch
-// [S][T] (k_score_store MODE 3 / 4, or the per-sample pass and k_dist_copy for designs with relation blocks); stage 2,
-// k_row_summary, reduces every row of the tile. Everything is fp64, there are no atomics, every sum runs in sample order.
+// Rows are processed in tiles of T rows (dist_tiles_run, the one tiled pass of this file, mfm_logdens.hpp and mfm_psis.hpp).
+// Stage 1 writes the values of a tile, all samples, into a sample-major scratch [S][T] (k_score_store MODE 3 / 4, or the
+// per-sample pass and k_dist_copy for designs with relation blocks); stage 2, here k_row_summary, reduces every row of the tile.
+// Everything is fp64, there are no atomics, every sum runs in sample order.
 #pragma once
 
 namespace mfm {
@@ -329,9 +330,10 @@ static void launch_row_summary(hipStream_t s, RowSummaryArgs &a, int xf = XF_NON
   hipLaunchKernelGGL(k_row_summary<true>, dim3((unsigned)cdiv(a.Tn, a.R)), dim3(WG), lds, s, a);
 }
 
-// Stage 1 of a tiled pass over the design (design_summary here, design_logdens in mfm_logdens.hpp): the values of the rows
-// [r0, r0 + Tn), all samples, into d->dist_scratch [S][Tn]. begin: once per call, behind the store's latest snapshot; designs
-// without relation blocks (rank <= 512) stage their samples for the one-pass scorer, in chunks of `chunk` samples.
+// The tiled pass over the design that design_summary here, design_logdens (mfm_logdens.hpp) and design_loo (mfm_psis.hpp) share
+// (DESIGN 4.9.1). Stage 1: the values of the rows [r0, r0 + Tn), all samples, into d->dist_scratch [S][Tn]. begin: once per call,
+// behind the store's latest snapshot; designs without relation blocks (rank <= 512) stage their samples for the one-pass scorer,
+// in chunks of `chunk` samples.
 struct DistStage1 {
   bool one_pass;
   int chunk;
@@ -365,6 +367,61 @@ static void dist_stage1_tile(mfm_design *d, hipStream_t s, const SampleView &v, 
   }
 }
 
+// The pass in its two steps, between which a caller uploads what its stage 2 reads (their order on the stream). reserve (N > 0): the
+// rank's caches, the tile of T rows (tile_rows, or what DIST_SCRATCH_BYTES hold of all samples), room for it and for out_n outputs.
+static int64_t dist_tiles_reserve(mfm_design *d, const SampleView &v, int64_t tile_rows, size_t out_n) {
+  const int count = v.count();
+  design_use_rank(d, v.K, d->stream);
+  const int64_t T = std::min<int64_t>(d->N, tile_rows > 0 ? tile_rows : std::max<int64_t>(1, (int64_t)(DIST_SCRATCH_BYTES / sizeof(double)) / count));
+  if (d->dist_scratch.n < (size_t)(T * count)) d->dist_scratch.alloc((size_t)(T * count));
+  if (d->dist_out.n < out_n) d->dist_out.alloc(out_n);
+  return T;
+}
+// `len` doubles of d->dist_out from `off` on, which leave for `host` when the last tile is done (len 0: nothing to copy)
+struct DistColumn {
+  double *host;
+  size_t off, len;
+};
+// run: per tile stage 1 in `mode`, then stage2(r0, Tn), the caller's launch over the scratch; out_sn, where not null: the host's
+// (S, N) matrix, whose columns r0 .. r0 + Tn are what stage 2 left in the scratch [S][Tn]. Then the columns go back, and one wait.
+template <class Stage2>
+static void dist_tiles_run(mfm_design *d, const SampleView &v, int64_t T, int mode, int32_t chunk_samples, double *out_sn,
+                           std::initializer_list<DistColumn> columns, const Stage2 &stage2) {
+  hipStream_t s = d->stream;
+  const int64_t N = d->N;
+  DistStage1 st = dist_stage1_begin(d, s, v, chunk_samples);
+  for (int64_t r0 = 0; r0 < N; r0 += T) {
+    const int64_t Tn = std::min<int64_t>(T, N - r0);
+    dist_stage1_tile(d, s, v, st, mode, r0, Tn);
+    MFM_HIP_CHECK(hipGetLastError());
+    stage2(r0, Tn);
+    MFM_HIP_CHECK(hipGetLastError());
+    if (out_sn)
+      MFM_HIP_CHECK(hipMemcpy2DAsync(out_sn + r0, (size_t)N * sizeof(double), d->dist_scratch.p, (size_t)Tn * sizeof(double),
+                                     (size_t)Tn * sizeof(double), (size_t)v.count(), hipMemcpyDeviceToHost, s));
+  }
+  for (const DistColumn &c : columns)
+    if (c.len) MFM_HIP_CHECK(hipMemcpyAsync(c.host, d->dist_out.p + c.off, c.len * sizeof(double), hipMemcpyDeviceToHost, s));
+  MFM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// The argument checks that the summaries and the log densities (logdens_check, mfm_logdens.hpp) share; nothing here touches the device.
+static void check_tiling(int64_t tile_rows, int32_t chunk_samples) {
+  if (tile_rows < 0 || chunk_samples < 0) throw Error(MFM_ERR_INVALID, "negative tiling override");
+}
+static void check_precisions(const double *p, int count) {
+  for (int k = 0; k < count; k++)
+    if (!(p[k] > 0.0) || !std::isfinite(p[k])) throw Error(MFM_ERR_INVALID, "noise precisions must be positive and finite");
+}
+static void check_cutpoints(const double *c, int count, int n_cut) {
+  for (int k = 0; k < count; k++)
+    for (int j = 0; j < n_cut; j++) {
+      const double *cs = c + (size_t)k * n_cut;
+      if (!std::isfinite(cs[j]) || (j > 0 && !(cs[j - 1] <= cs[j])))
+        throw Error(MFM_ERR_INVALID, "cutpoints must be finite and ascending within every sample");
+    }
+}
+
 // what an ordered-probit summary adds to the call: which value, and the samples' cutpoints [count][n_cut] on the host
 struct OprobitValues {
   int32_t expected, n_cut;
@@ -377,8 +434,7 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
                            const double *z, int64_t tile_rows, int32_t chunk_samples, double *out_mean, double *out_std, double *out_q,
                            const OprobitValues *op = nullptr) {
   const int count = v.count();
-  if (v.device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
-  if (v.D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+  check_sample_source(d, v);
   if (mode < 0 || mode > 1) throw Error(MFM_ERR_INVALID, "bad summary mode (0: score, 1: Phi(score))");
   if (n_q < 0 || n_q > DIST_MAX_Q) throw Error(MFM_ERR_INVALID, "at most " + std::to_string(DIST_MAX_Q) + " quantiles per call");
   if (n_q > 0 && count > DIST_MAX_S)
@@ -386,37 +442,25 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
   if (n_q > 0 && !probs) throw Error(MFM_ERR_INVALID, "quantiles asked for without their probabilities");
   if (precisions && mode != 0) throw Error(MFM_ERR_INVALID, "noise precisions apply to scores (mode 0) only");
   if (precisions && n_q > 0 && !z) throw Error(MFM_ERR_INVALID, "noise quantiles need Phi^-1 of their probabilities");
-  if (tile_rows < 0 || chunk_samples < 0) throw Error(MFM_ERR_INVALID, "negative tiling override");
+  check_tiling(tile_rows, chunk_samples);
   for (int q = 0; q < n_q; q++) {
     const bool inside = precisions ? probs[q] > 0.0 && probs[q] < 1.0 && std::isfinite(z[q]) : probs[q] >= 0.0 && probs[q] <= 1.0;
     if (!inside) throw Error(MFM_ERR_INVALID, "quantile probability out of range ([0, 1]; with noise strictly inside)");
   }
-  if (precisions)
-    for (int k = 0; k < count; k++)
-      if (!(precisions[k] > 0.0) || !std::isfinite(precisions[k])) throw Error(MFM_ERR_INVALID, "noise precisions must be positive and finite");
+  if (precisions) check_precisions(precisions, count);
   if (op) {
     if (op->expected < 0 || op->expected > 1) throw Error(MFM_ERR_INVALID, "bad value selector (0: class probabilities, 1: expected class index)");
     if (op->n_cut < 1) throw Error(MFM_ERR_INVALID, "an ordered-probit summary needs at least one cutpoint per sample");
     if (!op->cutpoints) throw Error(MFM_ERR_INVALID, "an ordered-probit summary needs the samples' cutpoints");
-    for (int k = 0; k < count; k++)
-      for (int j = 0; j < op->n_cut; j++) {
-        const double *cs = op->cutpoints + (size_t)k * op->n_cut;
-        if (!std::isfinite(cs[j]) || (j > 0 && !(cs[j - 1] <= cs[j])))
-          throw Error(MFM_ERR_INVALID, "cutpoints must be finite and ascending within every sample");
-      }
+    check_cutpoints(op->cutpoints, count, op->n_cut);
   }
   const int xf = !op ? XF_NONE : op->expected ? XF_EXPECTED : XF_CLASS;
   const int64_t C = xf == XF_CLASS ? (int64_t)op->n_cut + 1 : 1;
   hipStream_t s = d->stream;
-  const int rank = v.K;
   const int64_t N = d->N;
   if (N == 0) return;
-  design_use_rank(d, rank, s);
-  const int64_t T = std::min<int64_t>(N, tile_rows > 0 ? tile_rows : std::max<int64_t>(1, (int64_t)(DIST_SCRATCH_BYTES / sizeof(double)) / count));
-  if (d->dist_scratch.n < (size_t)(T * count)) d->dist_scratch.alloc((size_t)(T * count));
   const size_t NC = (size_t)N * (size_t)C;
-  const size_t out_n = NC * (2 + n_q);
-  if (d->dist_out.n < out_n) d->dist_out.alloc(out_n);
+  const int64_t T = dist_tiles_reserve(d, v, tile_rows, NC * (2 + n_q));
   RowSummaryArgs a;
   std::memset(&a, 0, sizeof(a));
   a.scratch = d->dist_scratch.p;
@@ -457,22 +501,14 @@ static void design_summary(mfm_design *d, const SampleView &v, int32_t mode, int
       a.g[q] = h - fl;
     }
   }
-  DistStage1 st = dist_stage1_begin(d, s, v, chunk_samples);
-  for (int64_t r0 = 0; r0 < N; r0 += T) {
-    const int64_t Tn = std::min<int64_t>(T, N - r0);
-    dist_stage1_tile(d, s, v, st, mode, r0, Tn);
-    MFM_HIP_CHECK(hipGetLastError());
+  const auto stage2 = [&](int64_t r0, int64_t Tn) {
     a.Tn = Tn;
     a.mean = d->dist_out.p + (size_t)r0 * C;
     a.sd = d->dist_out.p + NC + (size_t)r0 * C;
     a.q = d->dist_out.p + 2 * NC + (size_t)r0 * C;
     launch_row_summary(s, a, xf, &x);
-    MFM_HIP_CHECK(hipGetLastError());
-  }
-  MFM_HIP_CHECK(hipMemcpyAsync(out_mean, d->dist_out.p, NC * sizeof(double), hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipMemcpyAsync(out_std, d->dist_out.p + NC, NC * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (n_q) MFM_HIP_CHECK(hipMemcpyAsync(out_q, d->dist_out.p + 2 * NC, NC * n_q * sizeof(double), hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipStreamSynchronize(s));
+  };
+  dist_tiles_run(d, v, T, mode, chunk_samples, nullptr, {{out_mean, 0, NC}, {out_std, NC, NC}, {out_q, 2 * NC, NC * n_q}}, stage2);
 }
 
 }  // namespace mfm

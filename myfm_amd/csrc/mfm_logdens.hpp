@@ -3,8 +3,8 @@
 // the sample variance (ddof = 1, WAIC's penalty) of the l_s, for regression the probability integral transform
 // mean_s Phi((y - score_s) sqrt(alpha_s)), and on request the l_s themselves. Included by mfm_hip.hip after mfm_dist.hpp.
 //
-// Rows are processed in the tiles of mfm_dist.hpp: stage 1 (dist_stage1_tile, shared with design_summary) leaves the scores of a tile
-// sample-major in the scratch [S][T], stage 2, k_row_logdens, walks every row's samples in sample order. Everything is fp64, there
+// Rows are processed by the tiled pass of mfm_dist.hpp (dist_tiles_run): its stage 1 leaves the scores of a tile sample-major in
+// the scratch [S][T], the stage 2 given to it here, k_row_logdens, walks every row's samples in sample order. Everything is fp64, there
 // are no atomics: a rerun, another row tile or another sample chunk give the same bits.
 #pragma once
 #include "mfm_erfcx.hpp"
@@ -150,23 +150,26 @@ __global__ __launch_bounds__(WG) void k_row_logdens(RowLogdensArgs a) {
     run(a.aux);
 }
 
-template <int TASK>
-static void launch_row_logdens_task(hipStream_t s, const RowLogdensArgs &a, bool keep, size_t lds) {
-  const dim3 grid((unsigned)cdiv(a.Tn, WG));
-  if (keep)
-    hipLaunchKernelGGL((k_row_logdens<TASK, true>), grid, dim3(WG), lds, s, a);
-  else
-    hipLaunchKernelGGL((k_row_logdens<TASK, false>), grid, dim3(WG), lds, s, a);
+// The runtime task (checked: one of the three) as a compile-time constant: f(std::integral_constant<int, TASK>{}). The one dispatch
+// of launch_row_logdens, of launch_row_psis (mfm_psis.hpp) and of mfm_logdens_value.
+template <class F>
+static auto logdens_with_task(int task, const F &f) {
+  if (task == LOGDENS_REGRESSION) return f(std::integral_constant<int, LOGDENS_REGRESSION>{});
+  if (task == LOGDENS_CLASSIFICATION) return f(std::integral_constant<int, LOGDENS_CLASSIFICATION>{});
+  return f(std::integral_constant<int, LOGDENS_ORDERED>{});
 }
+
 static void launch_row_logdens(hipStream_t s, int task, const RowLogdensArgs &a, bool keep) {
   const size_t n_aux = task == LOGDENS_REGRESSION ? 2 * (size_t)a.S : task == LOGDENS_ORDERED ? (size_t)a.S * a.n_cut : 0;
   const size_t lds = a.aux_lds ? n_aux * sizeof(double) : 0;
-  if (task == LOGDENS_REGRESSION)
-    launch_row_logdens_task<LOGDENS_REGRESSION>(s, a, keep, lds);
-  else if (task == LOGDENS_CLASSIFICATION)
-    launch_row_logdens_task<LOGDENS_CLASSIFICATION>(s, a, keep, lds);
-  else
-    launch_row_logdens_task<LOGDENS_ORDERED>(s, a, keep, lds);
+  const dim3 grid((unsigned)cdiv(a.Tn, WG));
+  logdens_with_task(task, [&](auto task_c) {
+    constexpr int TASK = decltype(task_c)::value;
+    if (keep)
+      hipLaunchKernelGGL((k_row_logdens<TASK, true>), grid, dim3(WG), lds, s, a);
+    else
+      hipLaunchKernelGGL((k_row_logdens<TASK, false>), grid, dim3(WG), lds, s, a);
+  });
 }
 
 // what a call computes besides the samples: the task, the targets y[N] and that task's per-sample constants, all on the host
@@ -183,23 +186,17 @@ struct LogdensCall {
 // Every argument check of a call over `count` samples and N rows; nothing here touches the device.
 static void logdens_check(const LogdensCall &c, int64_t N, int count) {
   if (c.task < 0 || c.task > 2) throw Error(MFM_ERR_INVALID, "bad task (0: regression, 1: probit classification, 2: ordered probit)");
-  if (c.tile_rows < 0 || c.chunk_samples < 0) throw Error(MFM_ERR_INVALID, "negative tiling override");
+  check_tiling(c.tile_rows, c.chunk_samples);
   if (c.task == LOGDENS_REGRESSION) {
     if (!c.precisions) throw Error(MFM_ERR_INVALID, "a regression log density needs the noise precision of every sample");
-    for (int k = 0; k < count; k++)
-      if (!(c.precisions[k] > 0.0) || !std::isfinite(c.precisions[k])) throw Error(MFM_ERR_INVALID, "noise precisions must be positive and finite");
+    check_precisions(c.precisions, count);
   } else if (c.precisions) {
     throw Error(MFM_ERR_INVALID, "noise precisions apply to regression (task 0) only");
   }
   if (c.task == LOGDENS_ORDERED) {
     if (c.n_cut < 1) throw Error(MFM_ERR_INVALID, "an ordered-probit log density needs at least one cutpoint per sample");
     if (!c.cutpoints) throw Error(MFM_ERR_INVALID, "an ordered-probit log density needs the samples' cutpoints");
-    for (int k = 0; k < count; k++)
-      for (int j = 0; j < c.n_cut; j++) {
-        const double *cs = c.cutpoints + (size_t)k * c.n_cut;
-        if (!std::isfinite(cs[j]) || (j > 0 && !(cs[j - 1] <= cs[j])))
-          throw Error(MFM_ERR_INVALID, "cutpoints must be finite and ascending within every sample");
-      }
+    check_cutpoints(c.cutpoints, count, c.n_cut);
   } else if (c.cutpoints || c.n_cut != 0) {
     throw Error(MFM_ERR_INVALID, "cutpoints apply to ordered probit (task 2) only");
   }
@@ -211,7 +208,8 @@ static void logdens_check(const LogdensCall &c, int64_t N, int count) {
     const double y = c.y[t];
     if (!std::isfinite(y)) throw Error(MFM_ERR_INVALID, "y must be finite");
     if (c.task == LOGDENS_CLASSIFICATION && y != 0.0 && y != 1.0) throw Error(MFM_ERR_INVALID, "classification labels must be 0 or 1");
-    if (c.task == LOGDENS_ORDERED && (y != std::floor(y) || y < 0.0 || y > (double)c.n_cut))
+    // (the range first: inside it the cast is exact, and the loop calls nothing -- with a floor per row its time followed its address)
+    if (c.task == LOGDENS_ORDERED && (y < 0.0 || y > (double)c.n_cut || y != (double)(int)y))
       throw Error(MFM_ERR_INVALID, "ordered-probit labels must be integers in [0, n_cut]");
   }
 }
@@ -247,17 +245,13 @@ static LogdensConstants logdens_upload(mfm_design *d, hipStream_t s, const Logde
 
 static void design_logdens(mfm_design *d, const SampleView &v, const LogdensCall &c) {
   const int count = v.count();
-  if (v.device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
-  if (v.D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+  check_sample_source(d, v);
   hipStream_t s = d->stream;
-  const int64_t N = d->N;
+  const size_t N = (size_t)d->N;
   if (N == 0) return;
-  design_use_rank(d, v.K, s);
-  const int64_t T = std::min<int64_t>(N, c.tile_rows > 0 ? c.tile_rows : std::max<int64_t>(1, (int64_t)(DIST_SCRATCH_BYTES / sizeof(double)) / count));
-  if (d->dist_scratch.n < (size_t)(T * count)) d->dist_scratch.alloc((size_t)(T * count));
-  const size_t n_out = c.task == LOGDENS_REGRESSION ? 4 : 3;  // lpd, mean, var, pit
-  if (d->dist_out.n < (size_t)N * n_out) d->dist_out.alloc((size_t)N * n_out);
-  const LogdensConstants k = logdens_upload(d, s, c, N, count);
+  const bool pit = c.task == LOGDENS_REGRESSION;
+  const int64_t T = dist_tiles_reserve(d, v, c.tile_rows, N * (pit ? 4 : 3));  // lpd, mean, var, pit
+  const LogdensConstants k = logdens_upload(d, s, c, d->N, count);
   RowLogdensArgs a;
   std::memset(&a, 0, sizeof(a));
   a.scratch = d->dist_scratch.p;
@@ -268,30 +262,18 @@ static void design_logdens(mfm_design *d, const SampleView &v, const LogdensCall
   a.aux = k.aux;
   a.n_cut = c.task == LOGDENS_ORDERED ? c.n_cut : 0;
   a.aux_lds = k.n_aux > 0 && k.n_aux * sizeof(double) <= (size_t)LOGDENS_LDS_BYTES;
-  DistStage1 st = dist_stage1_begin(d, s, v, c.chunk_samples);
-  for (int64_t r0 = 0; r0 < N; r0 += T) {
-    const int64_t Tn = std::min<int64_t>(T, N - r0);
-    dist_stage1_tile(d, s, v, st, 0, r0, Tn);
-    MFM_HIP_CHECK(hipGetLastError());
+  const auto stage2 = [&](int64_t r0, int64_t Tn) {
     a.Tn = Tn;
     a.y = d->dist_y.p + r0;
     a.lpd = d->dist_out.p + r0;
-    a.mean = d->dist_out.p + (size_t)N + r0;
-    a.var = d->dist_out.p + 2 * (size_t)N + r0;
-    a.pit = c.task == LOGDENS_REGRESSION ? d->dist_out.p + 3 * (size_t)N + r0 : nullptr;
+    a.mean = d->dist_out.p + N + r0;
+    a.var = d->dist_out.p + 2 * N + r0;
+    a.pit = pit ? d->dist_out.p + 3 * N + r0 : nullptr;
     launch_row_logdens(s, c.task, a, c.out_ll != nullptr);
-    MFM_HIP_CHECK(hipGetLastError());
-    // the tile's l, [S][Tn] in the scratch, are columns r0 .. r0 + Tn of the (S, N) result; the next tile's stage 1 follows on the stream
-    if (c.out_ll)
-      MFM_HIP_CHECK(hipMemcpy2DAsync(c.out_ll + r0, (size_t)N * sizeof(double), d->dist_scratch.p, (size_t)Tn * sizeof(double),
-                                     (size_t)Tn * sizeof(double), (size_t)count, hipMemcpyDeviceToHost, s));
-  }
-  const size_t bytes = (size_t)N * sizeof(double);
-  MFM_HIP_CHECK(hipMemcpyAsync(c.out_lpd, d->dist_out.p, bytes, hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipMemcpyAsync(c.out_mean, d->dist_out.p + (size_t)N, bytes, hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipMemcpyAsync(c.out_var, d->dist_out.p + 2 * (size_t)N, bytes, hipMemcpyDeviceToHost, s));
-  if (c.task == LOGDENS_REGRESSION && c.out_pit) MFM_HIP_CHECK(hipMemcpyAsync(c.out_pit, d->dist_out.p + 3 * (size_t)N, bytes, hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipStreamSynchronize(s));
+  };
+  // out_ll: the tile's l, which KEEP leaves in the scratch
+  dist_tiles_run(d, v, T, 0, c.chunk_samples, c.out_ll,
+                 {{c.out_lpd, 0, N}, {c.out_mean, N, N}, {c.out_var, 2 * N, N}, {c.out_pit, 3 * N, pit && c.out_pit ? N : 0}}, stage2);
 }
 
 }  // namespace mfm
@@ -323,16 +305,15 @@ int mfm_design_logdens(mfm_design *d, int32_t rank, int32_t n_samples, const dou
 // logdens_value on the host, by the code the kernel runs: l of one (y, score) under one sample's constants; cutpoints_row[n_cut]
 int mfm_logdens_value(int32_t task, double y, double score, double log_norm, double sqrt_alpha, int32_t n_cut, const double *cutpoints_row,
                       double *out) {
-  if (task == mfm::LOGDENS_REGRESSION)
-    *out = mfm::logdens_value<mfm::LOGDENS_REGRESSION>(y, score, log_norm, sqrt_alpha, nullptr, 0);
-  else if (task == mfm::LOGDENS_CLASSIFICATION)
-    *out = mfm::logdens_value<mfm::LOGDENS_CLASSIFICATION>(y, score, 0.0, 0.0, nullptr, 0);
-  else if (task == mfm::LOGDENS_ORDERED && n_cut >= 1 && cutpoints_row && y >= 0.0 && y <= (double)n_cut)
-    *out = mfm::logdens_value<mfm::LOGDENS_ORDERED>(y, score, 0.0, 0.0, cutpoints_row, n_cut);
-  else {
+  const bool label_ok = n_cut >= 1 && cutpoints_row && y >= 0.0 && y <= (double)n_cut;
+  if (task < 0 || task > 2 || (task == mfm::LOGDENS_ORDERED && !label_ok)) {
     g_global_error = "bad task, or an ordered-probit label outside its cutpoints";
     return MFM_ERR_INVALID;
   }
+  // every task is handed all the constants: the if constexpr branches of logdens_value read their own task's alone
+  *out = mfm::logdens_with_task(task, [&](auto task_c) {
+    return mfm::logdens_value<decltype(task_c)::value>(y, score, log_norm, sqrt_alpha, cutpoints_row, n_cut);
+  });
   return MFM_OK;
 }
 

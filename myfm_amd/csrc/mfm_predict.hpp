@@ -642,10 +642,15 @@ static void design_predict_per_sample(mfm_design *d, hipStream_t s, int count, i
   MFM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// Predictor::predict* over the samples of a view, all of them on the device
-static void design_predict_view(mfm_design *d, const SampleView &v, int mode, int n_cut, const double *cutpoints, double *out) {
+// the samples of a view can be read by this design: the first check of every predictor over a view (here, mfm_dist.hpp and after)
+static void check_sample_source(const mfm_design *d, const SampleView &v) {
   if (v.device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
   if (v.D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+}
+
+// Predictor::predict* over the samples of a view, all of them on the device
+static void design_predict_view(mfm_design *d, const SampleView &v, int mode, int n_cut, const double *cutpoints, double *out) {
+  check_sample_source(d, v);
   hipStream_t s = d->stream;
   const int count = v.count(), rank = v.K;
   const int64_t N = d->N, D = d->D;

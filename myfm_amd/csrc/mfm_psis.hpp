@@ -5,10 +5,11 @@
 // elpd_loo = logsumexp_s(lw_s + l_s), the fit's shape k^ as the diagnostic, lpd as k_row_logdens computes it and for regression
 // loo_pit = sum_s exp(lw_s) Phi(z_s) are written. Included by mfm_hip.hip after mfm_logdens.hpp.
 //
-// Stage 1 is that of mfm_dist.hpp (the scores of a row tile, sample-major, in the scratch); stage 2, k_row_psis, follows the LDS form
-// of k_row_summary. Everything is fp64, there are no atomics; every sum over samples runs in sample order and the sums over the
-// grid in grid order, so a row's result depends on its own samples alone: another row tile, sample chunk, number of rows per
-// workgroup or a rerun give the same bits. mfm_psis_row runs one row on the host through the same scalar pieces in the same orders.
+// The tiled pass is that of mfm_dist.hpp (dist_tiles_run: the scores of a row tile, sample-major, in the scratch); its stage 2
+// here, k_row_psis, follows the LDS form of k_row_summary. Everything is fp64, there are no atomics; every sum over samples runs
+// in sample order and the sums over the grid in grid order, so a row's result depends on its own samples alone: another row tile,
+// sample chunk, number of rows per workgroup or a rerun give the same bits. mfm_psis_row runs one row on the host through the
+// same scalar pieces in the same orders.
 #pragma once
 #include <algorithm>
 #include <numeric>
@@ -294,19 +295,13 @@ static void launch_row_psis(hipStream_t s, int task, RowPsisArgs &a, size_t n_au
   const size_t rows = psis_lds_doubles(a.R, a.st, a.stv, P, 0);
   a.aux_lds = n_aux > 0 && rows + n_aux <= budget;
   const size_t lds = (rows + (a.aux_lds ? n_aux : 0)) * sizeof(double);
-  const auto forms = [&](auto task_c) {
+  logdens_with_task(task, [&](auto task_c) {
     constexpr int T = decltype(task_c)::value;
     if (keep_w)
       launch_row_psis_form<T, true>(s, a, lds);
     else
       launch_row_psis_form<T, false>(s, a, lds);
-  };
-  if (task == LOGDENS_REGRESSION)
-    forms(std::integral_constant<int, LOGDENS_REGRESSION>{});
-  else if (task == LOGDENS_CLASSIFICATION)
-    forms(std::integral_constant<int, LOGDENS_CLASSIFICATION>{});
-  else
-    forms(std::integral_constant<int, LOGDENS_ORDERED>{});
+  });
 }
 
 // One row on the host, sequentially, through the scalar pieces and in the summation orders of k_row_psis. out_lw[S] may be null.
@@ -379,16 +374,13 @@ static void loo_check(const LogdensCall &c, int64_t N, int count, int32_t tail_l
 
 static void design_loo(mfm_design *d, const SampleView &v, const LogdensCall &c, int32_t tail_len) {
   const int count = v.count();
-  if (v.device != d->device) throw Error(MFM_ERR_INVALID, "design and sample store live on different devices");
-  if (v.D != d->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
+  check_sample_source(d, v);
   hipStream_t s = d->stream;
-  const int64_t N = d->N;
+  const size_t N = (size_t)d->N;
   if (N == 0) return;
-  design_use_rank(d, v.K, s);
-  const int64_t T = std::min<int64_t>(N, c.tile_rows > 0 ? c.tile_rows : std::max<int64_t>(1, (int64_t)(DIST_SCRATCH_BYTES / sizeof(double)) / count));
-  if (d->dist_scratch.n < (size_t)(T * count)) d->dist_scratch.alloc((size_t)(T * count));
-  if (d->dist_out.n < (size_t)N * 4) d->dist_out.alloc((size_t)N * 4);  // lpd, elpd, k, pit
-  const LogdensConstants k = logdens_upload(d, s, c, N, count);
+  const bool pit = c.task == LOGDENS_REGRESSION;
+  const int64_t T = dist_tiles_reserve(d, v, c.tile_rows, N * 4);  // lpd, elpd, k, pit
+  const LogdensConstants k = logdens_upload(d, s, c, d->N, count);
   RowPsisArgs a;
   std::memset(&a, 0, sizeof(a));
   a.scratch = d->dist_scratch.p;
@@ -397,29 +389,18 @@ static void design_loo(mfm_design *d, const SampleView &v, const LogdensCall &c,
   a.n_cut = c.task == LOGDENS_ORDERED ? c.n_cut : 0;
   a.M = tail_len;
   a.log_S = std::log((double)count);
-  DistStage1 st = dist_stage1_begin(d, s, v, c.chunk_samples);
-  for (int64_t r0 = 0; r0 < N; r0 += T) {
-    const int64_t Tn = std::min<int64_t>(T, N - r0);
-    dist_stage1_tile(d, s, v, st, 0, r0, Tn);
-    MFM_HIP_CHECK(hipGetLastError());
+  const auto stage2 = [&](int64_t r0, int64_t Tn) {
     a.Tn = Tn;
     a.y = d->dist_y.p + r0;
     a.lpd = d->dist_out.p + r0;
-    a.elpd = d->dist_out.p + (size_t)N + r0;
-    a.khat = d->dist_out.p + 2 * (size_t)N + r0;
-    a.pit = c.task == LOGDENS_REGRESSION ? d->dist_out.p + 3 * (size_t)N + r0 : nullptr;
+    a.elpd = d->dist_out.p + N + r0;
+    a.khat = d->dist_out.p + 2 * N + r0;
+    a.pit = pit ? d->dist_out.p + 3 * N + r0 : nullptr;
     launch_row_psis(s, c.task, a, k.n_aux, c.out_ll != nullptr);
-    MFM_HIP_CHECK(hipGetLastError());
-    if (c.out_ll)  // the tile's log weights leave the scratch as design_logdens' l do
-      MFM_HIP_CHECK(hipMemcpy2DAsync(c.out_ll + r0, (size_t)N * sizeof(double), d->dist_scratch.p, (size_t)Tn * sizeof(double),
-                                     (size_t)Tn * sizeof(double), (size_t)count, hipMemcpyDeviceToHost, s));
-  }
-  const size_t bytes = (size_t)N * sizeof(double);
-  MFM_HIP_CHECK(hipMemcpyAsync(c.out_lpd, d->dist_out.p, bytes, hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipMemcpyAsync(c.out_mean, d->dist_out.p + (size_t)N, bytes, hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipMemcpyAsync(c.out_var, d->dist_out.p + 2 * (size_t)N, bytes, hipMemcpyDeviceToHost, s));
-  if (c.task == LOGDENS_REGRESSION && c.out_pit) MFM_HIP_CHECK(hipMemcpyAsync(c.out_pit, d->dist_out.p + 3 * (size_t)N, bytes, hipMemcpyDeviceToHost, s));
-  MFM_HIP_CHECK(hipStreamSynchronize(s));
+  };
+  // out_ll: the tile's log weights, which KEEP_W leaves in the scratch; the call's out_mean / out_var are elpd_loo / k^ (loo_check)
+  dist_tiles_run(d, v, T, 0, c.chunk_samples, c.out_ll,
+                 {{c.out_lpd, 0, N}, {c.out_mean, N, N}, {c.out_var, 2 * N, N}, {c.out_pit, 3 * N, pit && c.out_pit ? N : 0}}, stage2);
 }
 
 }  // namespace mfm

@@ -15,7 +15,8 @@ Usage: python scripts/res_isa.py [--asm FILE] [--keep FILE] [--all]
 form's code alone): per k_mf_resident / k_res_score symbol whether the instruction streams and the .amdhsa_* resource lines are
 equal; every other kernel must be in both, and a changed instruction count of one is reported. A plain comparison of the text
 (comments, the __hip_cuid_* symbol and the function ordinal in local labels aside); exit status 1 on a difference or a missing
-kernel, with the differing symbol and its first differing line."""
+kernel, with the differing symbol and its first differing line. --full REGEX widens the symbols compared in full (default: the
+sweep and the scorer; --full . compares every kernel of the translation unit, as a change that claims to touch no device code needs)."""
 import argparse
 import os
 import re
@@ -98,7 +99,7 @@ def kernels(path):
     return {k: (text[k], meta[k]) for k in meta if k in text}
 
 
-def same(path_a, path_b):
+def same(path_a, path_b, full="k_mf_resident|k_res_score"):
     a, b = kernels(path_a), kernels(path_b)
     bad = 0
     for name in sorted(set(a) | set(b)):
@@ -107,8 +108,8 @@ def same(path_a, path_b):
             bad += 1
             continue
         n_a, n_b = (sum(1 for x in k[name][0] if not x.endswith(":") and not x.startswith(".")) for k in (a, b))
-        if not re.search(r"k_mf_resident|k_res_score", name):
-            if n_a != n_b:  # (reported, not counted: the exit status speaks of the sweep and the scorer)
+        if not re.search(full, name):
+            if n_a != n_b:  # (reported, not counted: the exit status speaks of the kernels that --full names)
                 print("other kernel, %d -> %d instructions: %s" % (n_a, n_b, name))
             continue
         for what, x, y in (("instruction stream", a[name][0], b[name][0]), ("resources", a[name][1], b[name][1])):
@@ -206,9 +207,11 @@ def main():
     ap.add_argument("--keep", help="write the compiled listing here")
     ap.add_argument("--all", action="store_true", help="every instantiation (default: <512,4,1,...> in all its forms: OVF, XCH, S2B)")
     ap.add_argument("--same", nargs=2, metavar=("A.s", "B.s"), help="compare two listings kernel by kernel")
+    ap.add_argument("--full", default="k_mf_resident|k_res_score", metavar="REGEX",
+                    help="with --same: the kernels whose streams and resources are compared in full ('.': all)")
     args = ap.parse_args()
     if args.same:
-        return same(*args.same)
+        return same(*args.same, full=args.full)
     path = args.asm
     if not path:
         path = args.keep or os.path.join(tempfile.mkdtemp(prefix="res_isa_"), "mfm_hip.s")

@@ -143,20 +143,30 @@ def test_host_samples(K, N, S, kind, mode, quantiles):
 
 
 # ---- 2. tiling -----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode,noise", [(0, False), (1, False), (0, True)])
-def test_tiles_and_chunks_do_not_change_a_bit(mode, noise):
-    """257 rows in tiles of 64 (four full ones and a single row), 7 samples in chunks of 3, 3 and 1"""
+@pytest.mark.parametrize("mode,noise,block", [
+    pytest.param(0, False, False, id="0-False"), pytest.param(1, False, False, id="1-False"), pytest.param(0, True, False, id="0-True"),
+    pytest.param(0, False, True, id="0-False-block")])
+def test_tiles_and_chunks_do_not_change_a_bit(mode, noise, block):
+    """257 rows in tiles of 64 (four full ones and a single row), 7 samples in chunks of 3, 3 and 1; block: the relation-block
+    design of section 4 at 257 rows, whose tiles go through the per-sample pass"""
     rng = np.random.default_rng(21 + mode)
-    X = design("values", 257, rng)
-    est = make_predictor(task_of(mode), D, 3, normal_samples(rng, D, 3, 7))
+    if not block:
+        X, rels, n_features = design("values", 257, rng), [], D
+    else:
+        import myfm_amd
+        from myfm_amd.utils.synthetic import block_design
+
+        X, X_flat, blocks, _, _ = block_design(257)
+        rels, n_features = [myfm_amd.RelationBlock(idx, B) for idx, B in blocks], X_flat.shape[1]
+    est = make_predictor(task_of(mode), n_features, 3, normal_samples(rng, n_features, 3, 7))
     q = np.array([0.05, 0.5, 0.77, 0.95]) if noise else np.array(Q5)
     prec = np.geomspace(0.25, 400.0, 7) if noise else None
     p = est.predictor_
-    base = p.predict_dist(X, [], q, prec)
+    base = p.predict_dist(X, rels, q, prec)
     for kw in ({"tile_rows": 64}, {"chunk_samples": 3}, {"tile_rows": 64, "chunk_samples": 3}, {"tile_rows": 1000, "chunk_samples": 50}):
-        got = p.predict_dist(X, [], q, prec, **kw)
+        got = p.predict_dist(X, rels, q, prec, **kw)
         assert all(np.array_equal(a, b) for a, b in zip(base, got)), kw
-    assert np.array_equal(base[0], est.predict_proba(X) if mode else est.predict(X))
+    assert np.array_equal(base[0], est.predict_proba(X, rels) if mode else est.predict(X, rels))
 
 
 # ---- 3. ties -------------------------------------------------------------------------------------------------------------------
