@@ -545,6 +545,33 @@ int mfm_pairs_rank_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t cou
 int mfm_pairs_rank(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                    int32_t mode, int64_t *rank_out, double *value_out);
 
+/* ---- ranking under each kept sample (csrc/mfm_pairs_samples.hpp) ----------------------------------------------------
+ * The same sides, blocks, exclusions, sample views, order and memory rule, but the samples are not folded: with v_s(u, i) of the
+ * section above, sample s ranks the candidates of query u by (v_s(u, i) descending, i ascending).
+ *   topk_samples: row_sample == NULL: every sample's list, idx and value [count * U * k] row-major (sample, query, position).
+ *             Otherwise row_sample[U] with entries in [0, count): only the list of query u under sample row_sample[u] (Thompson
+ *             sampling when the entries are drawn uniformly), idx and value [U * k]; each query is contracted against one sample.
+ *             An entry outside the range is MFM_ERR_INVALID and the message names the row. Tail: idx -1, value -inf.
+ *             A list is bit for bit the topk of that one sample (the value of a pair under a sample is finished by shared code).
+ *   topk_prob: per query the n_top (1 <= n_top <= 256) candidates that the most samples hold among their k best, ordered by
+ *             (count descending, candidate index ascending), ties for the last place going to the smaller index;
+ *             idx [U * n_top], prob [U * n_top] = count / count-of-samples, an fp64 division. Missing entries: idx -1, prob 0.0.
+ *             The lists are counted on the device and never reach the host. count * k may not exceed MFM_PAIRS_VOTE_MAX (a
+ *             query's votes are sorted in the device's local memory).
+ * MFM_ERR_INVALID before any launch, with no output written: k outside [1, 256], n_top outside [1, 256], count * k over the vote's
+ * limit, a bad row_sample entry, mode 2 without cutpoints. The query chunks take half the scratch bound; each chunk's work -- one
+ * (sample, row tile) per workgroup -- is walked in slices whose per-stripe lists fit the rest (never less than one tile): results
+ * do not depend on the bound.                                                                                                   */
+#define MFM_PAIRS_VOTE_MAX 32768
+int mfm_pairs_topk_samples_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k,
+                                 const int32_t *row_sample, int64_t *idx, double *value);
+int mfm_pairs_topk_samples(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                           int32_t mode, int32_t k, const int32_t *row_sample, int64_t *idx, double *value);
+int mfm_pairs_topk_prob_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int32_t n_top,
+                              int64_t *idx, double *prob);
+int mfm_pairs_topk_prob(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                        int32_t mode, int32_t k, int32_t n_top, int64_t *idx, double *prob);
+
 /* ---- folding new one-hot features into the kept samples (csrc/mfm_foldin.hip) ----------------------------------
  * U new entities (users or items that were not in the training table), each a new one-hot column with value 1 in its own
  * observations. X (n, D) holds the CONTEXT of the n observations in the model's feature space (not the new column), y their

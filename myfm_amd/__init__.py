@@ -31,7 +31,10 @@ from .estimators import (  # noqa: E402
     PairSummary,
     PointwiseDensity,
     RankedSummary,
+    SampleRankings,
     TargetRanks,
+    ThompsonRanking,
+    TopKProbability,
     VariationalFMClassifier,
     VariationalFMRegressor,
 )
@@ -51,4 +54,7 @@ __all__ = [
     "TargetRanks",
     "PointwiseDensity",
     "LooDensity",
+    "SampleRankings",
+    "ThompsonRanking",
+    "TopKProbability",
 ]

@@ -42,12 +42,15 @@ SYMBOLS = [
     "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
     "mfm_pairs_set_cutpoints", "mfm_pairs_moments_store", "mfm_pairs_moments", "mfm_pairs_topk_ucb_store", "mfm_pairs_topk_ucb",
     "mfm_pairs_set_targets", "mfm_pairs_rank_store", "mfm_pairs_rank",
+    "mfm_pairs_topk_samples_store", "mfm_pairs_topk_samples", "mfm_pairs_topk_prob_store", "mfm_pairs_topk_prob",
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
     "mfm_design_logdens_store", "mfm_design_logdens", "mfm_logdens_value",
     "mfm_design_loo_store", "mfm_design_loo", "mfm_psis_row",
 ]
+
+PAIRS_VOTE_MAX = 32768  # (MFM_PAIRS_VOTE_MAX of myfm_hip.h: samples * k of a topk_prob call)
 
 _lib = None
 
@@ -198,6 +201,10 @@ def lib():
     L.mfm_pairs_set_targets.argtypes = [vp, P, P]
     L.mfm_pairs_rank_store.argtypes = [vp, vp, i32, i32, i32, P, P]
     L.mfm_pairs_rank.argtypes = [vp, i32, i32, P, P, P, i32, P, P]
+    L.mfm_pairs_topk_samples_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, P]
+    L.mfm_pairs_topk_samples.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, P]
+    L.mfm_pairs_topk_prob_store.argtypes = [vp, vp, i32, i32, i32, i32, i32, P, P]
+    L.mfm_pairs_topk_prob.argtypes = [vp, i32, i32, P, P, P, i32, i32, i32, P, P]
     L.mfm_foldin_create.argtypes = [C.c_int, i64, i64, P, P, P, P, i64, P, i32, C.POINTER(vp)]
     L.mfm_foldin_destroy.argtypes = [vp]
     L.mfm_foldin_destroy.restype = None
@@ -949,6 +956,43 @@ class Pairs:
 
     def rank_store(self, store, mode=0, first=0, count=None):
         return self._rank(_resident(store, first, count), mode)
+
+    # ---- the per-sample selecting form and the vote
+    def _topk_samples(self, src, k, mode, row_sample):
+        kk = max(int(k), 1)
+        if row_sample is None:
+            shape, rs = (src.S, self.U, kk), None
+        else:
+            rs = np.ascontiguousarray(row_sample, dtype=np.int32)
+            if rs.shape != (self.U,):
+                raise ValueError("row_sample must have one entry per query row")
+            shape = (self.U, kk)
+        idx, val = np.empty(shape, dtype=np.int64), np.empty(shape)
+        self._ck(src.call("mfm_pairs_topk_samples", self.h, mode, int(k), None if rs is None else _p(rs), _p(idx), _p(val)))
+        return idx, val
+
+    def _topk_prob(self, src, k, n_top, mode):
+        nn = max(int(n_top), 1)
+        idx, prob = np.empty((self.U, nn), dtype=np.int64), np.empty((self.U, nn))
+        self._ck(src.call("mfm_pairs_topk_prob", self.h, mode, int(k), int(n_top), _p(idx), _p(prob)))
+        return idx, prob
+
+    def topk_samples(self, samples, k, mode=0, row_sample=None):
+        """every sample's own top k under (value descending, index ascending): (indices int64 (S, U, k), values (S, U, k)); with
+        row_sample (U,) ints in [0, S) only the list of row u under sample row_sample[u]: (U, k) each. Tail -1 / -inf."""
+        return self._topk_samples(_host(samples), k, mode, row_sample)
+
+    def topk_samples_store(self, store, k, mode=0, row_sample=None, first=0, count=None):
+        return self._topk_samples(_resident(store, first, count), k, mode, row_sample)
+
+    def topk_prob(self, samples, k, n_top=None, mode=0):
+        """(indices int64 (U, n_top), probability (U, n_top)): the candidates that the most samples hold among their k best and
+        the share of the samples that do, ordered by (count descending, index ascending); missing entries -1 / 0.0. S * k may
+        not exceed PAIRS_VOTE_MAX."""
+        return self._topk_prob(_host(samples), k, k if n_top is None else n_top, mode)
+
+    def topk_prob_store(self, store, k, n_top=None, mode=0, first=0, count=None):
+        return self._topk_prob(_resident(store, first, count), k, k if n_top is None else n_top, mode)
 
 
 def group_by_entity(X, y, entity, n_entities):

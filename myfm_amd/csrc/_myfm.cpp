@@ -896,6 +896,52 @@ struct Predictor {
                      mean.mutable_data(), sd.mutable_data()));
     return py::make_tuple(idx, value, mean, sd);
   }
+  // ---- ranking under each kept sample
+  // (indices (S, U, k), value (S, U, k)): every sample's own list
+  py::tuple predict_topk_samples(const py::object &Xqo, const py::object &Xco, int64_t k, const py::object &excludeo, const py::object &rqo,
+                                 const py::object &rco) const {
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.ranked(k, excludeo);
+    py::array_t<int64_t> idx({(py::ssize_t)pc.S, pc.U(), (py::ssize_t)k});
+    py::array_t<double> value({(py::ssize_t)pc.S, pc.U(), (py::ssize_t)k});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_topk_samples_store, mfm_pairs_topk_samples, dp.p, pc.mode, (int)k, (const int32_t *)nullptr, idx.mutable_data(),
+                     value.mutable_data()));
+    return py::make_tuple(idx, value);
+  }
+  // (indices (U, k), value (U, k)): the list of query u under kept sample row_sample[u] alone
+  py::tuple predict_topk_thompson(const py::object &Xqo, const py::object &Xco, int64_t k,
+                                  const py::array_t<int32_t, py::array::c_style | py::array::forcecast> &row_sample, const py::object &excludeo,
+                                  const py::object &rqo, const py::object &rco) const {
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.ranked(k, excludeo);
+    if (row_sample.ndim() != 1 || row_sample.shape(0) != pc.U()) throw std::invalid_argument("row_sample must have one entry per query row");
+    for (py::ssize_t u = 0; u < pc.U(); u++)
+      if (pc.S > 0 && (row_sample.data()[u] < 0 || row_sample.data()[u] >= pc.S))
+        throw std::invalid_argument("row_sample: query row " + std::to_string(u) + " asks for sample " + std::to_string(row_sample.data()[u]) +
+                                    ", the model keeps " + std::to_string(pc.S));
+    py::array_t<int64_t> idx({pc.U(), (py::ssize_t)k});
+    py::array_t<double> value({pc.U(), (py::ssize_t)k});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_topk_samples_store, mfm_pairs_topk_samples, dp.p, pc.mode, (int)k, (const int32_t *)row_sample.data(),
+                     idx.mutable_data(), value.mutable_data()));
+    return py::make_tuple(idx, value);
+  }
+  // (indices (U, n_top), probability (U, n_top)): the share of the kept samples whose own top k holds the candidate
+  py::tuple predict_topk_prob(const py::object &Xqo, const py::object &Xco, int64_t k, int64_t n_top, const py::object &excludeo,
+                              const py::object &rqo, const py::object &rco) const {
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.ranked(k, excludeo);
+    if (n_top < 1 || n_top > 256) throw std::invalid_argument("n_top must be in [1, 256]");
+    if ((int64_t)pc.S * k > MFM_PAIRS_VOTE_MAX)
+      throw std::invalid_argument("predict_topk_prob counts at most " + std::to_string(MFM_PAIRS_VOTE_MAX) +
+                                  " list entries per query (kept samples * k), this call has " + std::to_string((int64_t)pc.S * k));
+    py::array_t<int64_t> idx({pc.U(), (py::ssize_t)n_top});
+    py::array_t<double> prob({pc.U(), (py::ssize_t)n_top});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_topk_prob_store, mfm_pairs_topk_prob, dp.p, pc.mode, (int)k, (int)n_top, idx.mutable_data(), prob.mutable_data()));
+    return py::make_tuple(idx, prob);
+  }
   // (rank int64 (nnz,), value (nnz,)) of the stored positions of `targets`, in CSR order
   py::tuple predict_rank(const py::object &Xqo, const py::object &Xco, const py::object &targetso, const py::object &excludeo,
                          const py::object &rqo, const py::object &rco) const {
@@ -3005,6 +3051,12 @@ PYBIND11_MODULE(_myfm, m) {
       .def("predict_pairs_dist", &Predictor::predict_pairs_dist, py::arg("X_query"), py::arg("X_cand"),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk_ucb", &Predictor::predict_topk_ucb, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("beta") = 1.0,
+           py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk_samples", &Predictor::predict_topk_samples, py::arg("X_query"), py::arg("X_cand"), py::arg("k"),
+           py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk_thompson", &Predictor::predict_topk_thompson, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("row_sample"),
+           py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk_prob", &Predictor::predict_topk_prob, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("n_top"),
            py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def_property_readonly("resident",
                              [](const Predictor &p) {

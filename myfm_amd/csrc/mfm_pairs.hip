@@ -5,7 +5,8 @@
 // for the whole call; they are refused, before anything is allocated, when they exceed MFM_STORE_MAX_FRACTION (default 0.5) of the
 // free device memory. The queries are walked in chunks of rows whose scratch -- P and the biases, the exclusion bitmask, the
 // per-stripe lists at the most stripes a launch can have, the outputs -- stays under `scratch_bound` bytes (256 MB unless
-// mfm_pairs_set_scratch_bound says otherwise; never less than one 64-row tile).
+// mfm_pairs_set_scratch_bound says otherwise; never less than one 64-row tile). The per-sample selecting form, whose lists scale
+// with samples x row tiles, splits the bound between a chunk's own scratch and slices of its plan (walk_samples).
 //
 // Relation blocks (mfm_pairs_add_block). A side's row is [main | B_0[o2b_0[r]] | ...]; every block of either side gets a table
 // (block rows x samples x (padded factors + 2) doubles, mfm_pairs.hpp) built once per call -- the query side's too, not once per
@@ -18,9 +19,12 @@
 // kept, ranking by mean + beta * std, and after each chunk's merge k_pairs_moments_at for mean and std of the selected pairs), or
 // the rank form (mfm_pairs_set_targets, mfm_pairs_rank*; k_pairs_tile_rank of mfm_pairs_rank.hpp, DESIGN 4.13.2: per query chunk
 // the values at the chunk's targets, then the count of the admissible candidates that beat each of them; a chunk without targets
-// launches nothing, a call without targets or candidates touches no device memory).
+// launches nothing, a call without targets or candidates touches no device memory), or the per-sample selecting form
+// (mfm_pairs_topk_samples*, mfm_pairs_topk_prob*; k_pairs_tile_samples and k_pairs_vote of mfm_pairs_samples.hpp, DESIGN 4.13.3:
+// walk_samples below builds each query chunk's plan and walks it in slices).
 #include "mfm_pairs.hpp"
 #include "mfm_pairs_rank.hpp"
+#include "mfm_pairs_samples.hpp"
 #include "mfm_pairs_ucb.hpp"
 #include "mfm_samples.hpp"
 
@@ -113,8 +117,8 @@ void launch_pairs(hipStream_t s, dim3 grid, size_t lds, const PairsArgs &a) {
 }
 
 // what becomes of a finished value: written (the scores entry points), selected (the top k), or looked up and counted at the
-// targets (the rank form's two launches)
-enum PairsOut { PAIRS_DENSE, PAIRS_SELECT, PAIRS_TARGETS };
+// targets (the rank form's two launches); PAIRS_SELECT_SAMPLE: selected under one sample per workgroup, by a plan
+enum PairsOut { PAIRS_DENSE, PAIRS_SELECT, PAIRS_TARGETS, PAIRS_SELECT_SAMPLE };
 
 template <int MT, int NT, int MODE, bool SPREAD, PairsOut OUT>
 void launch_form_mode(hipStream_t s, dim3 grid, const PairsArgs &a) {
@@ -122,6 +126,8 @@ void launch_form_mode(hipStream_t s, dim3 grid, const PairsArgs &a) {
     launch_pairs<k_pairs_tile_rank<MT, NT, MODE, false>>(s, grid, PairsRankLds<false>::BYTES, a);
     MFM_HIP_CHECK(hipGetLastError());
     launch_pairs<k_pairs_tile_rank<MT, NT, MODE, true>>(s, grid, PairsRankLds<true>::BYTES, a);
+  } else if constexpr (OUT == PAIRS_SELECT_SAMPLE) {
+    launch_pairs<k_pairs_tile_samples<MT, NT, MODE>>(s, grid, PairsSel<MT>::BYTES, a);
   } else {
     constexpr bool DENSE = OUT == PAIRS_DENSE;
     const size_t lds = DENSE ? 0 : PairsSel<MT>::BYTES;
@@ -159,9 +165,15 @@ PairsForm pairs_form_of() {
 
 // The one table of forms. A selecting form's tile shape follows from k: the per-row buffers of 16 MT rows x (256 / MT + 64)
 // candidates must fit the LDS. The moments forms hold MT NT = 4 tiles (their accumulators take twice the registers), the rank
-// form has the one shape its target lists are laid out for.
-PairsForm pairs_form(bool targets, bool spread, bool dense, int k) {
+// form has the one shape its target lists are laid out for. The per-sample selecting forms hold one sample's value next to the
+// accumulators, as the mean forms' modes 1 and 2 do, and take their shapes.
+PairsForm pairs_form(bool targets, bool spread, bool dense, int k, bool per_sample = false) {
   if (targets) return pairs_form_of<4, 2, false, PAIRS_TARGETS>();
+  if (per_sample) {
+    if (k <= 64) return pairs_form_of<4, 2, false, PAIRS_SELECT_SAMPLE>();
+    if (k <= 128) return pairs_form_of<2, 4, false, PAIRS_SELECT_SAMPLE>();
+    return pairs_form_of<1, 8, false, PAIRS_SELECT_SAMPLE>();
+  }
   if (!spread) {
     if (dense) return pairs_form_of<4, 2, false, PAIRS_DENSE>();
     if (k <= 64) return pairs_form_of<4, 2, false, PAIRS_SELECT>();
@@ -210,10 +222,188 @@ void check_targets_not_excluded(const mfm_pairs *p) {
   }
 }
 
+// ---- the per-sample selecting form (mfm_pairs_samples.hpp) --------------------------------------------------------
+// what a per-sample call asks for
+struct PairsPerSample {
+  const int32_t *row_sample = nullptr;  // [U]: only the list of row u's own sample, outputs [U][k]; null: every sample's, [S][U][k]
+  int n_top = 0;                        // > 0: the vote over every sample's list; idx / value are [U][n_top] indices / probabilities
+  int64_t *idx = nullptr;
+  double *value = nullptr;
+};
+
+static_assert(PAIRS_VOTE_MAX == MFM_PAIRS_VOTE_MAX && PAIRS_VOTE_MAX >= 95 * PAIRS_MAX_K, "the vote's limit as the header states it");
+
+// the checks that need the sample count (before any launch)
+void check_per_sample(const PairsPerSample &ps, int S, int k, int64_t U) {
+  if (ps.row_sample)
+    for (int64_t u = 0; u < U; u++)
+      if (ps.row_sample[u] < 0 || ps.row_sample[u] >= S)
+        throw Error(MFM_ERR_INVALID, "row_sample: query row " + std::to_string(u) + " asks for sample " + std::to_string(ps.row_sample[u]) +
+                                         ", the call has " + std::to_string(S));
+  if (ps.n_top > 0 && (int64_t)S * k > PAIRS_VOTE_MAX)
+    throw Error(MFM_ERR_INVALID, "the vote takes at most " + std::to_string(PAIRS_VOTE_MAX) + " list entries per query row (samples * k), the call has " +
+                                     std::to_string((int64_t)S * k));
+}
+
+// The queries in chunks, each chunk's plan in slices (the candidate side is resident: `call`).
+// Chunk: its per-row scratch -- P and the biases (all samples, or the row's own with the two maps), the exclusion bitmask, the
+// votes and the voted result -- stays under HALF the scratch bound (never less than one 64-row tile). Slice: consecutive plan
+// entries whose stripe lists and merged lists fit what the chunk's scratch leaves of the bound (never less than one entry). The
+// stripes are chosen per chunk from its entry count, as the other forms choose them from their row tiles. Every list is merged
+// under the selection's total order and lands at a place that its (sample, row) alone decides, so neither the bound nor the
+// stripes nor the slices change a bit of the results.
+template <class Embed>
+void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, int mode, const PairsPerSample &ps, Embed embed) {
+  hipStream_t s = p->stream;
+  const int S = call.S, k = call.k, KS = call.KS4 * 4, rows = form.rows();
+  const int64_t U = p->U, I = call.I, W = call.W;
+  const bool own = ps.row_sample != nullptr, vote = ps.n_top > 0, masked = p->has_exclude;
+  const double per_row = (own ? (double)KS * 8 + 16 : (double)S * KS * 8 + (double)S * 8) + (masked ? (double)W * 4 : 0.0) +
+                         (vote ? (double)S * k * 4 + (double)ps.n_top * 12 : 0.0);
+  int64_t chunk = (int64_t)std::min<double>((double)(p->scratch_bound / 2) / per_row, 1e12);
+  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
+  chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
+  const int64_t steps_total = (std::max<int64_t>(I, 1) + form.step() - 1) / form.step();
+  int n_sort = 2;  // the vote's sort length: the power of two at or above S * k
+  while (vote && n_sort < S * k) n_sort <<= 1;
+
+  DevBuf<double> Pf, Ab, list_v, out_v, res_p;
+  DevBuf<int32_t> list_i, out_i, votes, res_i, d_row_of, d_map_s;
+  DevBuf<uint32_t> mask;
+  DevBuf<PairsPlanEntry> d_plan;
+  std::vector<PairsPlanEntry> plan;
+  std::vector<int32_t> row_of, map_s, h_idx;
+  std::vector<double> h_val;
+  std::vector<int64_t> fill((size_t)S);
+  for (int64_t u0 = 0; u0 < U; u0 += chunk) {
+    const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
+    // ---- the chunk's plan (out: the entry's place in its slice, set below) and its rows of P
+    plan.clear();
+    int64_t Ppad = Upad;
+    if (own) {
+      // the rows grouped by their sample, a group's rows in row order, every non-empty group padded to whole tiles
+      std::fill(fill.begin(), fill.end(), 0);
+      for (int64_t u = 0; u < Uc; u++) fill[(size_t)ps.row_sample[u0 + u]]++;
+      Ppad = 0;
+      for (int g = 0; g < S; g++) {
+        const int64_t n_g = fill[(size_t)g];
+        fill[(size_t)g] = Ppad;  // (from here on: where the group's next row goes)
+        for (int64_t t = 0; t < n_g; t += rows) plan.push_back({Ppad + t, 0, g, (int32_t)std::min<int64_t>(rows, n_g - t)});
+        Ppad += round_up(n_g, rows);
+      }
+      row_of.assign((size_t)Ppad, -1);
+      map_s.assign((size_t)Ppad, 0);
+      for (int64_t u = 0; u < Uc; u++) row_of[(size_t)fill[(size_t)ps.row_sample[u0 + u]]++] = (int32_t)u;
+      for (const PairsPlanEntry &e : plan)
+        for (int r = 0; r < rows; r++) map_s[(size_t)e.row0 + r] = e.s;
+    } else {
+      for (int g = 0; g < S; g++)
+        for (int64_t t = 0; t < Uc; t += rows) plan.push_back({t, 0, g, (int32_t)std::min<int64_t>(rows, Uc - t)});
+    }
+    const int64_t n_e = (int64_t)plan.size();
+    if (n_e == 0) continue;
+    // stripes: enough workgroups to fill the device twice, at most PAIRS_MAX_STRIPES lists to merge
+    int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_e - 1) / n_e, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
+    const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
+    n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
+    // slices: what the chunk's own scratch leaves of the bound, in entries
+    const double fixed = (own ? (double)Ppad * (KS * 8 + 16) : (double)Upad * S * (KS + 1) * 8) + (masked ? (double)Uc * W * 4 : 0.0) +
+                         (vote ? (double)Uc * ((double)S * k * 4 + (double)ps.n_top * 12) : 0.0);
+    const double per_entry = (double)(n_stripes + 1) * rows * k * 12 + sizeof(PairsPlanEntry);
+    const int64_t slice = std::max<int64_t>(1, (int64_t)std::min<double>(((double)p->scratch_bound - fixed) / per_entry, (double)n_e));
+    for (int64_t e = 0; e < n_e; e++) plan[(size_t)e].out = (e % slice) * rows;
+    d_plan.upload(plan);
+    if (own) {
+      d_row_of.upload(row_of);
+      d_map_s.upload(map_s);
+    }
+    // ---- P, the mask
+    ensure(Pf, (size_t)(Ppad * (own ? (int64_t)KS : (int64_t)S * KS)));
+    ensure(Ab, (size_t)(own ? Ppad : Upad * S));
+    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Ppad, Pf.p, Ab.p, own ? d_row_of.p : nullptr, own ? d_map_s.p : nullptr);
+    MFM_HIP_CHECK(hipGetLastError());
+    const bool use_mask = masked && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
+    if (use_mask) {
+      ensure(mask, (size_t)(Uc * W));
+      MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), s));
+      hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
+    }
+    PairsArgs a = call;
+    a.Pf = Pf.p;
+    a.p_stride = own ? (int64_t)call.KS4 : call.NK;
+    a.Ab = Ab.p;
+    a.Upad = Upad;
+    a.Uc = Uc;
+    a.stripe_len = stripe_steps * form.step();
+    a.mask = use_mask ? mask.p : nullptr;
+    a.u0 = u0;
+    a.row_of = own ? d_row_of.p : nullptr;
+    a.list_rows = slice * rows;
+    ensure(list_v, (size_t)(n_stripes * slice * rows * k));
+    ensure(list_i, (size_t)(n_stripes * slice * rows * k));
+    ensure(out_v, (size_t)(slice * rows * k));
+    ensure(out_i, (size_t)(slice * rows * k));
+    a.list_v = list_v.p;
+    a.list_i = list_i.p;
+    if (vote) ensure(votes, (size_t)(Uc * S * k));
+    for (int64_t e0 = 0; e0 < n_e; e0 += slice) {
+      const int64_t E = std::min(slice, n_e - e0), L = E * rows;
+      a.plan = d_plan.p + e0;
+      if (I > 0) {
+        form.launch(s, dim3((unsigned)E, (unsigned)n_stripes), a, mode);
+        MFM_HIP_CHECK(hipGetLastError());
+      }
+      hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)L), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, a.list_rows, k,
+                         out_v.p, out_i.p);
+      MFM_HIP_CHECK(hipGetLastError());
+      if (vote) {  // the lists stay on the device
+        hipLaunchKernelGGL(k_pairs_votes_put, dim3((unsigned)E), dim3(PAIRS_WG), 0, s, a.plan, out_i.p, k, S, votes.p);
+        MFM_HIP_CHECK(hipGetLastError());
+        continue;
+      }
+      h_idx.resize((size_t)(L * k));
+      h_val.resize((size_t)(L * k));
+      MFM_HIP_CHECK(hipMemcpyAsync(h_val.data(), out_v.p, (size_t)(L * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), out_i.p, (size_t)(L * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipStreamSynchronize(s));
+      // a list goes where its (sample, row) says: [s][u][k], or -- the row's own sample -- [u][k]
+      for (int64_t e = e0; e < e0 + E; e++) {
+        const PairsPlanEntry &pe = plan[(size_t)e];
+        for (int r = 0; r < pe.rows; r++) {
+          const int64_t row = own ? (int64_t)row_of[(size_t)pe.row0 + r] : pe.row0 + r;
+          const size_t o = (size_t)((own ? (int64_t)0 : (int64_t)pe.s * U) + u0 + row) * k, l = (size_t)(pe.out + r) * k;
+          for (int j = 0; j < k; j++) {
+            ps.idx[o + j] = h_idx[l + j];
+            ps.value[o + j] = h_val[l + j];
+          }
+        }
+      }
+    }
+    if (vote) {
+      ensure(res_i, (size_t)(Uc * ps.n_top));
+      ensure(res_p, (size_t)(Uc * ps.n_top));
+      const size_t lds = (size_t)n_sort * sizeof(int);
+      static DeviceOnce raised;
+      if (lds > 48 * 1024 && raised.need()) {
+        MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_pairs_vote, hipFuncAttributeMaxDynamicSharedMemorySize, PAIRS_VOTE_MAX * (int)sizeof(int)));
+        raised.mark();
+      }
+      hipLaunchKernelGGL(k_pairs_vote, dim3((unsigned)Uc), dim3(PAIRS_WG), lds, s, votes.p, S * k, n_sort, S, ps.n_top, res_i.p, res_p.p);
+      MFM_HIP_CHECK(hipGetLastError());
+      h_idx.resize((size_t)(Uc * ps.n_top));
+      MFM_HIP_CHECK(hipMemcpyAsync(ps.value + (size_t)u0 * ps.n_top, res_p.p, (size_t)(Uc * ps.n_top) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), res_i.p, (size_t)(Uc * ps.n_top) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipStreamSynchronize(s));
+      for (int64_t e = 0; e < Uc * ps.n_top; e++) ps.idx[u0 * ps.n_top + e] = h_idx[(size_t)e];
+    }
+    MFM_HIP_CHECK(hipStreamSynchronize(s));
+  }
+}
+
 // The whole call over the samples of `v` (mfm_samples.hpp). dense != nullptr: (U, I) scores; else the top k. mo != nullptr: the
-// moments form. rk != nullptr: the rank form (neither dense nor k).
+// moments form. rk != nullptr: the rank form (neither dense nor k). ps != nullptr: the per-sample selecting form (k, its own outputs).
 void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx, double *score, double *dense,
-               const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr) {
+               const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr) {
   const int S = v.count(), rank = v.K;
   if (v.device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
   if (v.D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
@@ -230,8 +420,9 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   const bool is_dense = dense != nullptr;
   if (!is_dense && !rk && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
   // the form of the call, decided here once: the scratch per query row, the stripes, the grid and the launch all read it
-  const PairsForm form = pairs_form(rk != nullptr, mo != nullptr, is_dense, k);
+  const PairsForm form = pairs_form(rk != nullptr, mo != nullptr, is_dense, k, ps != nullptr);
   const int64_t U = p->U, I = p->I, D = p->D;
+  if (ps) check_per_sample(*ps, S, k, U);
   if (U == 0 || (is_dense && I == 0)) return;
   if (rk && (I == 0 || !p->has_targets)) return;
   hipStream_t s = p->stream;
@@ -313,15 +504,21 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     if (!refs.empty()) d_blk[side].upload(refs);
   }
   // a side with blocks gathers from its tables, one without takes the instantiation that reads no block argument
+  // (map_row / map_s: the row -> sample plan's flavour, one launch row per row of P under its own sample)
   const auto embed = [&](int side, const int64_t *ptr, const int32_t *idx, const double *val, int64_t r0, int64_t R, int64_t Rpad, double *Pf,
-                         double *bias) {
-    const dim3 grid((unsigned)((Rpad + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S);
-    if (p->blocks[side].empty())
-      hipLaunchKernelGGL(k_pairs_embed<false>, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K,
-                         KS, S, (const PairsBlockRef *)nullptr, 0, Pf, bias);
+                         double *bias, const int32_t *map_row, const int32_t *map_s) {
+    const dim3 grid((unsigned)((Rpad + PAIRS_WG - 1) / PAIRS_WG), map_row ? 1u : (unsigned)S);
+    const bool rel = !p->blocks[side].empty();
+    const PairsBlockRef *blk = rel ? (const PairsBlockRef *)d_blk[side].p : nullptr;
+    const int n_blk = (int)p->blocks[side].size();
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K, KS, S, blk,
+                         n_blk, Pf, bias, map_row, map_s);
+    };
+    if (map_row)
+      rel ? launch(k_pairs_embed<true, true>) : launch(k_pairs_embed<false, true>);
     else
-      hipLaunchKernelGGL(k_pairs_embed<true>, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K,
-                         KS, S, (const PairsBlockRef *)d_blk[side].p, (int)p->blocks[side].size(), Pf, bias);
+      rel ? launch(k_pairs_embed<true, false>) : launch(k_pairs_embed<false, false>);
   };
 
   // ---- candidate side, once
@@ -329,9 +526,53 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   Qf.alloc((size_t)std::max<int64_t>(Ipad * NK * 4, 1));
   Bb.alloc((size_t)Ipad * S);
   Bsum.alloc((size_t)Ipad);
-  embed(1, p->c_ptr.p, p->c_idx.p, p->c_val.p, (int64_t)0, I, Ipad, Qf.p, Bb.p);
+  embed(1, p->c_ptr.p, p->c_idx.p, p->c_val.p, (int64_t)0, I, Ipad, Qf.p, Bb.p, nullptr, nullptr);
   hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)(Ipad / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Bb.p, S, Ipad, Bsum.p);
   MFM_HIP_CHECK(hipGetLastError());
+
+  // ---- what every launch of the call reads; a chunk adds its own
+  PairsArgs call;
+  call.Pf = nullptr;
+  call.Qf = Qf.p;
+  call.NK = NK;
+  call.p_stride = NK;
+  call.q_stride = NK;
+  call.KS4 = KS4;
+  call.S = S;
+  call.Ab = nullptr;
+  call.Asum = nullptr;
+  call.Bb = Bb.p;
+  call.Bsum = Bsum.p;
+  call.w0s = d_w0.p;
+  call.w0sum = w0sum;
+  call.cut = mode == 2 ? d_cut.p : nullptr;
+  call.n_cut = mode == 2 ? p->n_cut : 0;
+  call.beta = mo ? mo->beta : 0.0;
+  call.Upad = 0;
+  call.Ipad = Ipad;
+  call.Uc = 0;
+  call.I = I;
+  call.stripe_len = 0;
+  call.dense = nullptr;
+  call.dense_std = nullptr;
+  call.mask = nullptr;
+  call.W = W;
+  call.k = k;
+  call.list_v = nullptr;
+  call.list_i = nullptr;
+  call.tptr = nullptr;
+  call.tidx = nullptr;
+  call.tval = nullptr;
+  call.trank = nullptr;
+  call.u0 = 0;
+  call.tbase = 0;
+  call.plan = nullptr;
+  call.row_of = nullptr;
+  call.list_rows = 0;
+  if (ps) {
+    walk_samples(p, form, call, mode, *ps, embed);
+    return;
+  }
 
   // ---- queries, chunk by chunk
   DevBuf<double> Pf, Ab, Asum, list_v, out_v, d_dense, d_dense_std, out_m, out_s;
@@ -347,7 +588,7 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     ensure(Pf, (size_t)(Upad * NK * 4));
     ensure(Ab, (size_t)(Upad * S));
     ensure(Asum, (size_t)Upad);
-    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p);
+    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p, nullptr, nullptr);
     hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Ab.p, S, Upad,
                        Asum.p);
     const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
@@ -362,37 +603,15 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
     n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
     const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
-    PairsArgs a;
+    PairsArgs a = call;
     a.Pf = Pf.p;
-    a.Qf = Qf.p;
-    a.NK = NK;
-    a.KS4 = KS4;
-    a.S = S;
     a.Ab = Ab.p;
     a.Asum = Asum.p;
-    a.Bb = Bb.p;
-    a.Bsum = Bsum.p;
-    a.w0s = d_w0.p;
-    a.w0sum = w0sum;
-    a.cut = mode == 2 ? d_cut.p : nullptr;
-    a.n_cut = mode == 2 ? p->n_cut : 0;
-    a.beta = mo ? mo->beta : 0.0;
     a.Upad = Upad;
-    a.Ipad = Ipad;
     a.Uc = Uc;
-    a.I = I;
     a.stripe_len = stripe_steps * form.step();
-    a.dense = nullptr;
-    a.dense_std = nullptr;
     a.mask = use_mask ? mask.p : nullptr;
-    a.W = W;
-    a.k = k;
-    a.list_v = nullptr;
-    a.list_i = nullptr;
-    a.tptr = nullptr;
-    a.tidx = nullptr;
-    a.tval = nullptr;
-    a.trank = nullptr;
+    a.list_rows = Upad;
     a.u0 = u0;
     a.tbase = tbase;
     if (rk) {
@@ -459,14 +678,28 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
 }
 
 void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense,
-                     const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr) {
+                     const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr) {
   if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo, rk);
+  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo, rk, ps);
 }
 
 void run_pairs_host(mfm_pairs *p, int rank, int n_samples, const double *w0s, const double *ws, const double *Vs, int mode, int k,
-                    int64_t *idx, double *score, double *dense, const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr) {
-  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo, rk);
+                    int64_t *idx, double *score, double *dense, const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr,
+                    const PairsPerSample *ps = nullptr) {
+  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo, rk, ps);
+}
+
+// the checks of the per-sample calls that need neither samples nor a device
+PairsPerSample checked_per_sample(int k, const int32_t *row_sample, int n_top, bool vote, int64_t *idx, double *value) {
+  if (!idx || !value) throw Error(MFM_ERR_INVALID, "no output array");
+  if (k < 1 || k > PAIRS_MAX_K) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  if (vote && (n_top < 1 || n_top > PAIRS_VOTE_MAX_TOP)) throw Error(MFM_ERR_INVALID, "n_top must be in [1, 256]");
+  PairsPerSample ps;
+  ps.row_sample = row_sample;
+  ps.n_top = vote ? n_top : 0;
+  ps.idx = idx;
+  ps.value = value;
+  return ps;
 }
 
 // the outputs of a rank call: none is needed while no target is stored
@@ -720,6 +953,38 @@ int mfm_pairs_topk_ucb(mfm_pairs *p, int32_t rank, int32_t n_samples, const doub
   PAIRS_TRY(p)
   const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
   run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, idx, value, nullptr, &mo);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_samples_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k,
+                                 const int32_t *row_sample, int64_t *idx, double *value) {
+  PAIRS_TRY(p)
+  const PairsPerSample ps = checked_per_sample(k, row_sample, 0, false, idx, value);
+  run_pairs_store(p, st, first, count, mode, k, nullptr, nullptr, nullptr, nullptr, nullptr, &ps);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_samples(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                           int32_t mode, int32_t k, const int32_t *row_sample, int64_t *idx, double *value) {
+  PAIRS_TRY(p)
+  const PairsPerSample ps = checked_per_sample(k, row_sample, 0, false, idx, value);
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, nullptr, nullptr, nullptr, nullptr, nullptr, &ps);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_prob_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int32_t n_top,
+                              int64_t *idx, double *prob) {
+  PAIRS_TRY(p)
+  const PairsPerSample ps = checked_per_sample(k, nullptr, n_top, true, idx, prob);
+  run_pairs_store(p, st, first, count, mode, k, nullptr, nullptr, nullptr, nullptr, nullptr, &ps);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_prob(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                        int32_t mode, int32_t k, int32_t n_top, int64_t *idx, double *prob) {
+  PAIRS_TRY(p)
+  const PairsPerSample ps = checked_per_sample(k, nullptr, n_top, true, idx, prob);
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, nullptr, nullptr, nullptr, nullptr, nullptr, &ps);
   PAIRS_CATCH(p)
 }
 

@@ -8,13 +8,14 @@
 // and gathered (k_pairs_embed_block / k_pairs_embed). Values: the mean over the samples of the score, of Phi(score), or -- ordered
 // probit -- of sum_j Phi(score - cut_s[j]), the expected class index.
 //
-// Every form of the tile kernel -- the mean forms here, the moments form (mfm_pairs_ucb.hpp), the rank form (mfm_pairs_rank.hpp) --
-// is put together from the pieces of this file, each of which exists once:
+// Every form of the tile kernel -- the mean forms here, the moments form (mfm_pairs_ucb.hpp), the rank form (mfm_pairs_rank.hpp),
+// the per-sample selecting form (mfm_pairs_samples.hpp) -- is put together from the pieces of this file, each of which exists once:
 //   pairs_contract        the MFMA contraction of one workgroup step, pass by pass
 //   pairs_finish_sample   a pass's tile -> the samples' scores ((w0 + A) + B) + acc;  pairs_sample_value: score -> value
 //   PairsMean             the accumulator of the mean forms (PairsWelford, the moments form's, is in mfm_pairs_ucb.hpp)
 //   pairs_step            contraction + accumulator + the guarded loop over the step's finished values
 //   PairsSel              the per-row selection (LDS state, push, compaction round, list write)
+//   pairs_select_stripe   the selecting workgroup: a row tile of P x a stripe of candidates into the stripe's lists
 //   pairs_tile_stripe     a dense or selecting workgroup over its stripe, for either accumulator
 // so a value finished by one form is bit for bit the value another form finishes for that pair (the build does not contract
 // a * b + c).
@@ -102,30 +103,35 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed_block(const int64_t *_
 // Summation order, fixed: the main CSR part, then -- REL, a side with relation blocks -- the blocks in list order (block b adds
 // T_b[s][o2b_b[r0 + r]][.] to P, lin_b to lin, vv_b to vv), then bias = lin + 1/2 (sum_k P_k^2 - vv). o2b is indexed with the
 // ABSOLUTE side row r0 + r: a query chunk does not re-base it. Without REL neither blk nor n_blk is read.
-template <bool REL>
+// MAPPED (the row -> sample plan of mfm_pairs_samples.hpp): output row r holds side row r0 + map_row[r] (-1: a padding row, zeros)
+// under sample map_s[r] alone -- one thread per output row, P with KS / 4 k-steps per row tile and one bias per row, the
+// arithmetic of a row under its sample unchanged. Without MAPPED neither map is read.
+template <bool REL, bool MAPPED = false>
 __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
                                                           const double *__restrict__ val, int64_t r0, int64_t R, int64_t Rpad,
                                                           const double *const *__restrict__ wv, int64_t D, int K, int KS, int S,
                                                           const PairsBlockRef *__restrict__ blk, int n_blk,
-                                                          double *__restrict__ Pf, double *__restrict__ bias) {
+                                                          double *__restrict__ Pf, double *__restrict__ bias,
+                                                          const int32_t *__restrict__ map_row, const int32_t *__restrict__ map_s) {
   const int64_t r = (int64_t)blockIdx.x * PAIRS_WG + threadIdx.x;
   if (r >= Rpad) return;
-  const int s = blockIdx.y;
+  const int s = MAPPED ? map_s[r] : (int)blockIdx.y;
   const double *__restrict__ w = wv[s];
   const int KS4 = KS >> 2;
-  const int64_t NK = (int64_t)S * KS4;
-  double *__restrict__ Prow = Pf + ((r >> 4) * NK + (int64_t)s * KS4) * 64 + (r & 15);
-  const bool live = r < R;
+  const int64_t NK = MAPPED ? (int64_t)KS4 : (int64_t)S * KS4;
+  double *__restrict__ Prow = Pf + ((r >> 4) * NK + (MAPPED ? (int64_t)0 : (int64_t)s * KS4)) * 64 + (r & 15);
+  const int64_t src = MAPPED ? (int64_t)map_row[r] : r;  // the side row, relative to r0
+  const bool live = MAPPED ? src >= 0 : r < R;
   int64_t pb = 0, pe = 0;
   if (live) {
-    pb = rowptr[r0 + r];
-    pe = rowptr[r0 + r + 1];
+    pb = rowptr[r0 + src];
+    pe = rowptr[r0 + src + 1];
   }
   double sq = 0.0, vv = 0.0;
   double lin = pairs_embed_row(colidx, val, pb, pe, w, w + D, D, K, KS, vv, [&](int f, double a) {
     if constexpr (REL) {
       if (live)
-        for (int b = 0; b < n_blk; b++) a += blk[b].T[((int64_t)s * blk[b].M + blk[b].o2b[r0 + r]) * KS + f];
+        for (int b = 0; b < n_blk; b++) a += blk[b].T[((int64_t)s * blk[b].M + blk[b].o2b[r0 + src]) * KS + f];
     }
     Prow[(int64_t)(f >> 2) * 64 + (f & 3) * 16] = a;
     sq += a * a;
@@ -133,12 +139,12 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed(const int64_t *__restr
   if constexpr (REL) {
     if (live)
       for (int b = 0; b < n_blk; b++) {
-        const int64_t e = (int64_t)s * blk[b].M + blk[b].o2b[r0 + r];
+        const int64_t e = (int64_t)s * blk[b].M + blk[b].o2b[r0 + src];
         lin += blk[b].lin[e];
         vv += blk[b].vv[e];
       }
   }
-  bias[(int64_t)s * Rpad + r] = lin + 0.5 * (sq - vv);
+  bias[(MAPPED ? (int64_t)0 : (int64_t)s * Rpad) + r] = lin + 0.5 * (sq - vv);
 }
 
 // sum over the samples, in sample order, of a side's biases (regression mode adds it once)
@@ -164,10 +170,13 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_mask(const int64_t *__restri
 }
 
 // ---- the tile kernels' argument ------------------------------------------------------------------------------------------
+struct PairsPlanEntry;  // (mfm_pairs_samples.hpp)
+
 struct PairsArgs {
   // the contraction
-  const double *Pf, *Qf;                    // fragment-ordered embeddings: [rows / 16][NK][64]
-  int64_t NK;                               // k-steps through all samples: S * KS4
+  const double *Pf, *Qf;                    // fragment-ordered embeddings: [rows / 16][p_stride or q_stride][64]
+  int64_t NK;                               // k-steps the contraction walks: S * KS4
+  int64_t p_stride, q_stride;               // k-steps between two row tiles of P and of Q (NK, but for a one-sample view of more)
   int KS4, S;
   // the finish of a value
   const double *Ab, *Asum, *Bb, *Bsum;      // biases: [S][Upad], [Upad], [S][Ipad], [Ipad]
@@ -194,6 +203,10 @@ struct PairsArgs {
   double *tval;                             // [the chunk's targets]: entry tptr[u0 + row] - tbase + t, the target's value
   int32_t *trank;                           // [the chunk's targets]: its rank, zeroed per chunk
   int64_t u0, tbase;                        // the chunk's first query row and tptr[u0]
+  // per-sample selecting form (mfm_pairs_samples.hpp)
+  const PairsPlanEntry *plan;               // the launch's entries, one per blockIdx.x
+  const int32_t *row_of;                    // [P rows] or null: the chunk's query row of a row of P (the row -> sample plan)
+  int64_t list_rows;                        // rows of one stripe's lists
 };
 
 // ---- the contraction -------------------------------------------------------------------------------------------------------
@@ -206,9 +219,9 @@ __device__ __forceinline__ void pairs_contract(const PairsArgs &a, int64_t q0, i
   const int64_t rt0 = q0 >> 4;
   const double *pa[MT], *pq[NT];
 #pragma unroll
-  for (int m = 0; m < MT; m++) pa[m] = a.Pf + (size_t)(rt0 + m) * a.NK * 64 + lane;
+  for (int m = 0; m < MT; m++) pa[m] = a.Pf + (size_t)(rt0 + m) * a.p_stride * 64 + lane;
 #pragma unroll
-  for (int n = 0; n < NT; n++) pq[n] = a.Qf + (size_t)(ct0 + n) * a.NK * 64 + lane;
+  for (int n = 0; n < NT; n++) pq[n] = a.Qf + (size_t)(ct0 + n) * a.q_stride * 64 + lane;
   double an[MT], bn[NT];
 #pragma unroll
   for (int m = 0; m < MT; m++) an[m] = a.NK > 0 ? pa[m][0] : 0.0;
@@ -474,14 +487,14 @@ struct PairsSel {
     }
   }
 
-  // the stripe's list of every row of the tile: its best k in order, padded (-inf, -1)
+  // the stripe's list of every row of the tile, from list row q0 on: its best k in order, padded (-inf, -1)
   __device__ __forceinline__ void finish(const PairsArgs &a, int64_t q0) {
     __syncthreads();
     compact(true);
     for (int e = threadIdx.x; e < ROWS * k; e += PAIRS_WG) {
       const int row = e / k, j = e - row * k;
       const bool have = j < cnt[row];
-      const size_t o = ((size_t)blockIdx.y * a.Upad + q0 + row) * k + j;
+      const size_t o = ((size_t)blockIdx.y * a.list_rows + q0 + row) * k + j;
       a.list_v[o] = have ? buf_v[row * CAP + j] : -INFINITY;
       a.list_i[o] = have ? buf_i[row * CAP + j] : -1;
     }
@@ -489,8 +502,22 @@ struct PairsSel {
 };
 
 // ---- the dense and the selecting forms -----------------------------------------------------------------------------------------
+// The selecting workgroup: the MT * 16 rows of P from q0 against the stripe [cb, ce), Acc::ranked of the values through the per-row
+// selection, the stripe's lists written at list row l0. mask_row(row): the row of the exclusion mask that belongs to a row of P.
+template <int MT, int NT, class Acc, class MaskRow>
+__device__ __forceinline__ void pairs_select_stripe(const PairsArgs &a, int64_t q0, int64_t l0, int64_t cb, int64_t ce, MaskRow mask_row) {
+  PairsSel<MT> sel;
+  sel.init(a.k);
+  for (int64_t c0 = cb; c0 < ce; c0 += 4 * NT * 16)
+    pairs_step<MT, NT, Acc>(
+        a, q0, c0, ce,
+        [&](int rloc, int64_t row, int64_t col, const typename Acc::Value &v) { sel.push(a, rloc, mask_row(row), col, Acc::ranked(v)); },
+        [&] { sel.round(); });
+  sel.finish(a, l0);
+}
+
 // A workgroup over its MT * 16 query rows x one stripe of candidates, for either accumulator. DENSE writes every value
-// (Acc::store_dense; it asks for no LDS and sets none up); otherwise Acc::ranked of the values goes through the per-row selection.
+// (Acc::store_dense; it asks for no LDS and sets none up); otherwise the selecting workgroup.
 template <int MT, int NT, class Acc, bool DENSE>
 __device__ __forceinline__ void pairs_tile_stripe(const PairsArgs &a) {
   const int64_t q0 = (int64_t)blockIdx.x * (MT * 16);
@@ -502,13 +529,7 @@ __device__ __forceinline__ void pairs_tile_stripe(const PairsArgs &a) {
           a, q0, c0, ce, [&](int, int64_t row, int64_t col, const typename Acc::Value &v) { Acc::store_dense(a, (size_t)row * a.I + col, v); },
           [] {});
   } else {
-    PairsSel<MT> sel;
-    sel.init(a.k);
-    for (int64_t c0 = cb; c0 < ce; c0 += 4 * NT * 16)
-      pairs_step<MT, NT, Acc>(
-          a, q0, c0, ce, [&](int rloc, int64_t row, int64_t col, const typename Acc::Value &v) { sel.push(a, rloc, row, col, Acc::ranked(v)); },
-          [&] { sel.round(); });
-    sel.finish(a, q0);
+    pairs_select_stripe<MT, NT, Acc>(a, q0, q0, cb, ce, [](int64_t row) { return row; });
   }
 }
 

@@ -88,8 +88,8 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_moments_at(PairsArgs a, cons
     }
     return;
   }
-  const double *__restrict__ P = a.Pf + (size_t)(u >> 4) * a.NK * 64 + (u & 15);
-  const double *__restrict__ Q = a.Qf + (size_t)(i >> 4) * a.NK * 64 + (i & 15);
+  const double *__restrict__ P = a.Pf + (size_t)(u >> 4) * a.p_stride * 64 + (u & 15);
+  const double *__restrict__ Q = a.Qf + (size_t)(i >> 4) * a.q_stride * 64 + (i & 15);
   const int KS = a.KS4 * 4;
   double mean = 0.0, m2 = 0.0;
   for (int s0 = 0; s0 < a.S; s0 += 64) {

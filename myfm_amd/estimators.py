@@ -622,6 +622,56 @@ class _PairUncertaintyMixin:
         k, beta, exclude = _ranked_args(Xq, Xc, k, exclude, beta)
         return RankedSummary(*predictor.predict_topk_ucb(Xq, Xc, k, beta, exclude, rq, rc))
 
+    # ---- ranking under each kept sample: the S kept samples are S complete models, and each ranks the candidates
+    # of a query by its own v_s(u, i) under predict_topk's order. Not row-sharded, k <= 256, no variational estimator.
+    def predict_topk_samples(self, X_query, X_cand, k: int, exclude=None, X_rel_query=[], X_rel_cand=[]):
+        """Every kept sample's own list: SampleRankings(indices int64 (S, U, k), value (S, U, k)), indices[s, u] the k candidates
+        of largest v_s(u, .) ordered by (value descending, candidate index ascending), bit for bit what predict_topk gives for
+        a model that keeps sample s alone. Tail: index -1, value -inf. `exclude` and 1 <= k <= 256 as in predict_topk."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        k, _, exclude = _ranked_args(Xq, Xc, k, exclude)
+        return SampleRankings(*predictor.predict_topk_samples(Xq, Xc, k, exclude, rq, rc))
+
+    def predict_topk_thompson(self, X_query, X_cand, k: int, random_seed: int = 0, exclude=None, X_rel_query=[], X_rel_cand=[]):
+        """Thompson sampling: for every query one kept sample is drawn and that sample's list is recommended.
+        ThompsonRanking(indices int64 (U, k), value (U, k), sample int64 (U,)) with
+        sample = np.random.default_rng(random_seed).integers(0, S, size=U), drawn on the host and returned, so a call is
+        reproducible and auditable: row u equals predict_topk_samples(...)[.][sample[u], u] bit for bit. A query is contracted
+        against its one sample, 1 / S of predict_topk's arithmetic. random_seed: a non-negative int, else ValueError."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        k, _, exclude = _ranked_args(Xq, Xc, k, exclude)
+        if isinstance(random_seed, (bool, np.bool_)) or not isinstance(random_seed, (int, np.integer)) or random_seed < 0:
+            raise ValueError("random_seed must be a non-negative integer")
+        n_samples = len(predictor.samples)
+        if n_samples == 0:
+            raise RuntimeError("Told to predict but no sample available.")
+        sample = np.random.default_rng(int(random_seed)).integers(0, n_samples, size=Xq.shape[0])
+        idx, value = predictor.predict_topk_thompson(Xq, Xc, k, sample.astype(np.int32), exclude, rq, rc)
+        return ThompsonRanking(idx, value, sample.astype(np.int64))
+
+    def predict_topk_prob(self, X_query, X_cand, k: int, n_top: Optional[int] = None, exclude=None, X_rel_query=[], X_rel_cand=[]):
+        """The top-k inclusion probability P(candidate i is among query u's k best): the share of the kept samples whose own
+        list (predict_topk_samples) holds i. TopKProbability(indices int64 (U, n_top), probability (U, n_top)): per query the
+        n_top (default k) candidates of largest probability ordered by (probability descending, candidate index ascending);
+        where fewer candidates got a vote the tail is index -1, probability 0.0. The lists are counted on the device and never
+        reach the host. n_top: an int in [1, 256]; kept samples * k may not exceed TOPK_PROB_MAX_VOTES; else ValueError."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        k, _, exclude = _ranked_args(Xq, Xc, k, exclude)
+        if n_top is not None and (isinstance(n_top, (bool, np.bool_)) or not isinstance(n_top, (int, np.integer)) or not 1 <= n_top <= 256):
+            raise ValueError("n_top must be an integer in [1, 256]")
+        n_top = k if n_top is None else n_top  # (a k out of range is refused as predict_topk refuses it)
+        n_samples = len(predictor.samples)
+        if 1 <= k <= 256 and n_samples * k > TOPK_PROB_MAX_VOTES:  # (a k out of range is refused as predict_topk refuses it)
+            raise ValueError("predict_topk_prob counts at most %d list entries per query (kept samples * k), this call has %d"
+                             % (TOPK_PROB_MAX_VOTES, n_samples * k))
+        return TopKProbability(*predictor.predict_topk_prob(Xq, Xc, k, int(n_top), exclude, rq, rc))
+
+
+TOPK_PROB_MAX_VOTES = 32768  # (MFM_PAIRS_VOTE_MAX of the device code: a query's votes are sorted in the device's local memory)
+SampleRankings = namedtuple("SampleRankings", ["indices", "value"])
+ThompsonRanking = namedtuple("ThompsonRanking", ["indices", "value", "sample"])
+TopKProbability = namedtuple("TopKProbability", ["indices", "probability"])
+
 
 def _fold_in_checked(est, name, X, y, entity, group, n_entities):
     """The host-side checks that fold_in and fold_in_gibbs share, in one order and with one set of messages (`name`: the calling
