@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include <dlfcn.h>
 
@@ -99,6 +100,21 @@ struct Comm {
       return;
     }
     if (fn(user, buf, count) != 0) throw Error(MFM_ERR_RUNTIME, "all-reduce callback failed");
+  }
+  // The ranks' agreement at setup: v summed over the ranks, the result on the host (s: the ctx stream the collective runs on).
+  // Every rank must come here with the same length at the same point, or all of them wait for ever.
+  void sum_ranks(std::vector<double> &v, hipStream_t s) const {
+    DevBuf<double> d;
+    d.upload(v);
+    allreduce(d.p, (int64_t)v.size());
+    MFM_HIP_CHECK(hipStreamSynchronize(s));
+    MFM_HIP_CHECK(hipMemcpy(v.data(), d.p, v.size() * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  // ... and a vote: did every rank say yes?
+  bool all_ranks(bool yes, hipStream_t s) const {
+    std::vector<double> no{yes ? 0.0 : 1.0};
+    sum_ranks(no, s);
+    return no[0] == 0.0;
   }
   ~Comm() {
     if (nccl) (void)Rccl::get().CommDestroy(nccl);

@@ -135,6 +135,10 @@ enum class EWhere : uint8_t { Rows, Slots, SlotsWithSums, Cell, Dropped };
 // The form update_V takes on the main table, decided by decide_main_paths. Deferred: the persistent sweep took the
 // table first and the generic plans are not built; ensure_main_plans resolves it when a call needs them.
 enum class VPath : uint8_t { Deferred, Generic, QFree, Split, SplitFused, TwoField, ShardedSplit, ShardedTwoField, Cell };
+// Whether the persistent sweep takes update_V's launch. Off: no layout, or given up (drop_resident). Refused: the
+// layout stood but ResidentBudget kept the CUs (plan_resident; mfm_finalize does not ask a second time). AwaitingPeers: row-sharded,
+// every rank has its layout and exchange buffers and the caller has yet to hand over the peers' (mfm_peer_set). Live: it runs.
+enum class ResState : uint8_t { Off, Refused, AwaitingPeers, Live };
 }
 using namespace mfm;
 
@@ -220,10 +224,11 @@ struct mfm_ctx {
   bool two_field() const { return v_path == VPath::TwoField || v_path == VPath::ShardedTwoField; }  // run_sweep_mf: no q-cache in HBM
   ResPlan res;                  // ... as one persistent launch with the residual resident on chip (mfm_res.hpp)
   // The persistent sweep is an overlay on the forms whose tables it can take: it is switched on at mfm_finalize or by mfm_peer_set
-  // and off by drop_resident, and update_V asks here whether it runs. A layout that is ready runs whatever form the generic plans of
+  // and off by drop_resident, and update_V asks here whether it runs. A live layout runs whatever form the generic plans of
   // the same table took (a one-row table's are VPath::Generic): mfm_sweep_V and mfm_sweep_wV take the same launch, with the plans
   // built (MFM_PLAN_CHECK, or after ensure_main_plans) and without. (No layout is ever built beside QFree or Cell.)
-  bool resident_V() const { return res.ready; }
+  ResState res_state = ResState::Off;
+  bool resident_V() const { return res_state == ResState::Live; }
   std::vector<DevBuf<int32_t>> pre_maps;  // the blocks' maps uploaded ahead of the blocks (mfm_finalize only)
   // regression: outside the sweeps the residual IS score - y (update_e recomputes it after every update_V, FMTrainer.hpp:494), so
   // the persistent launch need not write its copy back (mfm_set_residual_policy); whoever asks for it in between gets it recomputed
@@ -232,8 +237,6 @@ struct mfm_ctx {
   // caller has installed his own residual (mfm_set_e, mfm_shift_e, the latent draws of classification / ordered probit). Only
   // such a residual may be dropped by the sweep and recomputed on demand.
   bool e_is_residual = false;
-  bool res_sharded_pending = false;  // row-sharded: the persistent sweep's layout is built on every rank, waiting for mfm_peer_set
-  bool res_refused = false;  // the CUs of the persistent sweep were not ours to take
   int res_plan_cus = 0;      // workgroups the layout was asked for
   void ensure_main_plans();
   CellPlan cell;                // update_V of a design of index tuples (one-hot fields + relation blocks): no q-cache (mfm_cell.hpp)
@@ -338,11 +341,10 @@ struct mfm_ctx {
   void drop_resident() {
     for (void *m : res.peer_mapped) (void)hipIpcCloseMemHandle(m);
     res.peer_mapped.clear();
-    res_sharded_pending = false;
+    res_state = ResState::Off;
     res.peers_model = false;
     if (res_claim) ResidentBudget::get().release(device, res_claim);
     res_claim = 0;
-    res.ready = false;
     res_fills_device = false;
   }
   // Co-resident kernels (k_long_coop, k_cb_persist, k_mf_resident) raise ls.error when a partner did not show up within the spin
@@ -352,7 +354,7 @@ struct mfm_ctx {
     if (flag == 0) return;
     (void)hipMemsetAsync(ls.error.p, 0, sizeof(int), stream);
     (void)hipStreamSynchronize(stream);
-    const bool had = res.ready;
+    const bool had = resident_V();
     drop_resident();
     throw Error(MFM_ERR_RUNTIME,
                 std::string("co-resident workgroups timed out waiting for each other (long-column sweep / conflict-batched chain / "
@@ -627,7 +629,7 @@ static void score_train(mfm_ctx *c, bool subtract_y) {
   c->e_where = EWhere::Rows;  // (every residual is overwritten)
   hipStream_t s = c->stream;
   // regression on a table that takes the persistent sweep: e = score - y straight in the sweep's slot order, with its sums
-  const bool in_slots = subtract_y && c->res.ready && (c->v_path == VPath::Deferred || c->two_field()) && res_score_supported(c->res, c->K);
+  const bool in_slots = subtract_y && c->resident_V() && (c->v_path == VPath::Deferred || c->two_field()) && res_score_supported(c->res, c->K);
   if (!in_slots) c->ensure_main_plans();
   if (in_slots || c->two_field() || c->cell.ready) {
     TimedLaunch t(c->timing, s, KC_BUILD_VT, 16.0 * c->D * c->K);
@@ -1058,30 +1060,76 @@ int mfm_set_groups(mfm_ctx *ctx, const int32_t *group_index, int64_t D, int32_t 
   MFM_CATCH(ctx)
 }
 
-static int64_t res_min_rows(const mfm_ctx *) {
+static int64_t res_min_rows() {
   return env_i64("MFM_RES_MIN_ROWS", (int64_t)1 << 20);
 }
 
-// The persistent sweep's layout (build(plan, workgroups): the device builder of mfm_res_plan.hpp or the host builder) and the
-// claim on its CUs.
-static void plan_resident(mfm_ctx *c, const std::function<void(ResPlan &, int)> &build, bool tlog) {
+// f(b) for b in [0, n): all but the last on a host thread of their own, the last on the caller's, each on the context's device.
+// All are joined; the first error in index order is thrown again.
+static void for_each_block(int device, size_t n, const std::function<void(size_t)> &f) {
+  std::vector<std::thread> pool;
+  std::vector<std::exception_ptr> errs(n);
+  auto run = [&](size_t b) {
+    try {
+      MFM_HIP_CHECK(hipSetDevice(device));
+      f(b);
+    } catch (...) {
+      errs[b] = std::current_exception();
+    }
+  };
+  for (size_t b = 0; b + 1 < n; b++) pool.emplace_back(run, b);
+  if (n) run(n - 1);
+  for (auto &t : pool) t.join();
+  for (auto &e : errs)
+    if (e) std::rethrow_exception(e);
+}
+
+// Which layout of the persistent sweep is asked for. Xt: the host builder on X_t with these levels; null: the device builder of
+// mfm_res_plan.hpp on the CSR (levels: the caller's schedule, or null). draw_empty and no overflow slots: row-sharded
+// (ResPlan::build).
+struct ResLayoutAsk {
+  const HostCsr *Xt;
+  const std::vector<int32_t> *levels;
+  const std::vector<char> *draw_empty;
+  bool allow_overflow;
+};
+
+static void build_resident(ResPlan &rp, mfm_ctx *c, const ResLayoutAsk &ask, int n_cu) {
+  rp.allow_overflow = ask.allow_overflow;
+  if (ask.Xt)
+    rp.build(*ask.Xt, *ask.levels, &c->hgroup, n_cu, ask.draw_empty);
+  else
+    res_plan_build_device(rp, c->X, &c->hgroup, n_cu, c->stream, ask.levels, ask.draw_empty);
+}
+
+// tests (MFM_PLAN_CHECK): the host builder must give the layout that the device builder left in c->res, array for array
+static void check_resident_plan(mfm_ctx *c, const ResLayoutAsk &host_ask, const char *word) {
+  ResPlan chk;
+  build_resident(chk, c, host_ask, c->res_plan_cus);
+  const std::string diff = chk.ready ? res_plan_compare(c->res, chk, c->stream) : ("host builder: " + chk.why);
+  if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, std::string("plan check: device and host resident layouts differ (") + word + diff + ")");
+}
+
+// The persistent sweep's layout and the claim on its CUs. True: the layout stands and the CUs are ours (the caller says what
+// state that is); a refusal by ResidentBudget is recorded here.
+static bool plan_resident(mfm_ctx *c, const ResLayoutAsk &ask, bool tlog) {
   int n_cu = 0;
   MFM_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
   const int n_cu_dev = n_cu;
   if (env_flag("MFM_RES_CUS")) {
     n_cu = std::max(1, std::min(n_cu, env_int("MFM_RES_CUS", 0)));
-    build(c->res, n_cu);
+    build_resident(c->res, c, ask, n_cu);
   } else {
     // one CU per XCD stays free when the rows still fit the others (config 3: 40 323 of 40 959 slots per workgroup): the small
     // kernels between two launches, the side stream's single-workgroup draws and the slot-order scorer's last workgroup no
     // longer queue behind each other -- 308 -> 314-317 it/s at config 3 (MI355X, profiles/r04_q_res_cus.txt)
     bool done = false;
     if (n_cu >= 64 && c->N / (n_cu - 8) < 40500) {
-      build(c->res, n_cu - 8);
+      build_resident(c->res, c, ask, n_cu - 8);
       done = c->res.ready;
       if (done) n_cu -= 8;
     }
-    if (!done) build(c->res, n_cu);
+    if (!done) build_resident(c->res, c, ask, n_cu);
   }
   c->res_plan_cus = n_cu;
   if (c->res.ready) {
@@ -1093,7 +1141,7 @@ static void plan_resident(mfm_ctx *c, const std::function<void(ResPlan &, int)> 
       c->res.fail("the persistent kernel does not fit a CU (occupancy query)");
     } else if (!ResidentBudget::get().acquire(c->device, n_cu_dev, c->res.G, why)) {
       c->res.fail(why.c_str());
-      c->res_refused = true;
+      c->res_state = ResState::Refused;
     } else {
       c->res_claim = c->res.G;
     }
@@ -1103,131 +1151,112 @@ static void plan_resident(mfm_ctx *c, const std::function<void(ResPlan &, int)> 
     std::fprintf(stderr, "[mfm_finalize] resident plan: %s (G=%d RV=%d RL=%d umax=%d runs=%lld lds=%zu)\n",
                  c->res.ready ? "ready" : c->res.why.c_str(), c->res.G, c->res.RV, c->res.RL, c->res.umax, (long long)c->res.n_runs,
                  c->res.lds_bytes);
+  return c->res.ready;
 }
 
+using Lap = std::function<void(const char *)>;  // MFM_SETUP_TIMING: the time since the lap before, under this label
+
 // Before anything else is planned: does the table take the persistent sweep? (the layout from the device CSR, mfm_res_plan.hpp)
-static void try_resident_first(mfm_ctx *c, const std::function<void(const char *)> &lap) {
+static void try_resident_first(mfm_ctx *c, const Lap &lap) {
   for (const char *e : {"MFM_NO_RESIDENT", "MFM_RES_PROF", "MFM_NO_FUSED_NEXT", "MFM_NO_MF", "MFM_NO_SCATTER", "MFM_TILE_BITS"})
     if (env_flag(e)) return;
   if (env_int("MFM_QFREE", 0)) return;
   if (c->comm.active() || !c->hblocks.empty() || !c->hlevels.empty() || !c->X.unit || c->X.ell_width != 2 || c->K < 1 ||
-      c->N < res_min_rows(c))
+      c->N < res_min_rows())
     return;
-  const bool tlog = env_flag("MFM_SETUP_TIMING");
-  plan_resident(c, [&](ResPlan &rp, int n_cu) { res_plan_build_device(rp, c->X, &c->hgroup, n_cu, c->stream); }, tlog);
+  if (plan_resident(c, {nullptr, nullptr, nullptr, true}, env_flag("MFM_SETUP_TIMING"))) c->res_state = ResState::Live;
   lap("resident plan (device)");
   // (tests: with MFM_PLAN_CHECK everything else is built too and the host builder's layout compared)
-  if (c->res.ready && !env_flag("MFM_PLAN_CHECK")) c->v_path = VPath::Deferred;
+  if (c->resident_V() && !env_flag("MFM_PLAN_CHECK")) c->v_path = VPath::Deferred;
 }
 
 // The main table's generic structures: X_t (device transpose, copied back for the planner), the level plans of both sweeps, the
 // row tiles. Xt: filled here.
-static void plan_main_table(mfm_ctx *c, HostCsr &Xt, const std::function<void(const char *)> &lap) {
-    Xt = transpose_device(c->X, c->stream);
-    lap("transpose (device) + copy back");
-    c->plan_V.sharded = c->plan_W.sharded = c->comm.active();
-    c->plan_V.given_levels = c->plan_W.given_levels = c->hlevels;
-    // scattered levels: LDS row tiles of 2^tile_bits {e, q} records (64 KiB by default: two workgroups per CU)
-    // (short tables: 1024-row tiles -- a 4096-row tile leaves most of the 256 CUs without a workgroup and the pass is bound by
-    // the life time of one workgroup: ML-100k shape 3270 -> 4040 it/s)
-    int tile_bits = (c->N < ((int64_t)1 << 20) && !c->comm.active()) ? 10 : 12;
-    tile_bits = env_int("MFM_TILE_BITS", tile_bits);
-    if (tile_bits < 9 || tile_bits > 13) tile_bits = 0;  // 0: L2-window path (k_scat_*)
-    c->plan_V.tile_bits = c->plan_W.tile_bits = tile_bits;
-    // one plan serves the three latent policies of the main table: size the co-resident launch for all of them
-    const int coop_v = std::min({coop_capacity<PMainV>(), coop_capacity<PMainVe<false, false>>(), coop_capacity<PMainVe<true, false>>(),
-                                 coop_capacity<PMainVsq<false>>(), coop_capacity<PMainVsq<true>>(), coop_capacity<PMainVs>()});
-    // Row-sharded fused tile path: which first-level columns need an all-reduce of their statistics? Those
-    // with rows on more than one rank -- the same ("special") set on every rank, from two all-reduces of
-    // per-column indicators (columns empty on every rank are drawn from the prior by every rank itself).
-    bool try_fused = c->comm.active() && c->hblocks.empty() && !c->hlevels.empty() && tile_bits > 0 && c->N > 0;
-    if (c->comm.active()) {
-      // the predicate has rank-local inputs (an empty shard, the environment): every rank must enter the collectives
-      // below or none -- agree first
-      double no = try_fused ? 0.0 : 1.0;
-      DevBuf<double> d;
-      d.upload(&no, 1);
-      c->comm.allreduce(d.p, 1);
-      MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-      MFM_HIP_CHECK(hipMemcpy(&no, d.p, sizeof(double), hipMemcpyDeviceToHost));
-      try_fused = no == 0.0;
+static void plan_main_table(mfm_ctx *c, HostCsr &Xt, const Lap &lap) {
+  Xt = transpose_device(c->X, c->stream);
+  lap("transpose (device) + copy back");
+  c->plan_V.sharded = c->plan_W.sharded = c->comm.active();
+  c->plan_V.given_levels = c->plan_W.given_levels = c->hlevels;
+  // scattered levels: LDS row tiles of 2^tile_bits {e, q} records (64 KiB by default: two workgroups per CU)
+  // (short tables: 1024-row tiles -- a 4096-row tile leaves most of the 256 CUs without a workgroup and the pass is bound by
+  // the life time of one workgroup: ML-100k shape 3270 -> 4040 it/s)
+  int tile_bits = (c->N < ((int64_t)1 << 20) && !c->comm.active()) ? 10 : 12;
+  tile_bits = env_int("MFM_TILE_BITS", tile_bits);
+  if (tile_bits < 9 || tile_bits > 13) tile_bits = 0;  // 0: L2-window path (k_scat_*)
+  c->plan_V.tile_bits = c->plan_W.tile_bits = tile_bits;
+  // one plan serves the three latent policies of the main table: size the co-resident launch for all of them
+  const int coop_v = std::min({coop_capacity<PMainV>(), coop_capacity<PMainVe<false, false>>(), coop_capacity<PMainVe<true, false>>(),
+                               coop_capacity<PMainVsq<false>>(), coop_capacity<PMainVsq<true>>(), coop_capacity<PMainVs>()});
+  // Row-sharded fused tile path: which first-level columns need an all-reduce of their statistics? Those
+  // with rows on more than one rank -- the same ("special") set on every rank, from two all-reduces of
+  // per-column indicators (columns empty on every rank are drawn from the prior by every rank itself).
+  bool try_fused = c->comm.active() && c->hblocks.empty() && !c->hlevels.empty() && tile_bits > 0 && c->N > 0;
+  // the predicate has rank-local inputs (an empty shard, the environment): every rank must enter the collectives
+  // below or none -- agree first
+  if (c->comm.active()) try_fused = c->comm.all_ranks(try_fused, c->stream);
+  std::vector<double> col_cnt;
+  if (try_fused) {
+    const int64_t D0 = c->D0, RB = (int64_t)1 << tile_bits;
+    std::vector<double> h((size_t)2 * D0, 0.0);
+    col_cnt.resize((size_t)D0);
+    for (int64_t j = 0; j < D0; j++) {
+      col_cnt[j] = h[j] = (double)(Xt.ptr[j + 1] - Xt.ptr[j]);
+      h[D0 + j] = h[j] > (double)RB ? 1.0 : 0.0;
     }
-    std::vector<double> col_cnt;
-    if (try_fused) {
-      const int64_t D0 = c->D0, RB = (int64_t)1 << tile_bits;
-      std::vector<double> h((size_t)2 * D0, 0.0);
-      col_cnt.resize((size_t)D0);
-      for (int64_t j = 0; j < D0; j++) {
-        col_cnt[j] = h[j] = (double)(Xt.ptr[j + 1] - Xt.ptr[j]);
-        h[D0 + j] = h[j] > (double)RB ? 1.0 : 0.0;
-      }
-      DevBuf<double> d;
-      d.upload(h);
-      c->comm.allreduce(d.p, 2 * D0);
-      MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-      std::vector<double> g((size_t)2 * D0);
-      MFM_HIP_CHECK(hipMemcpy(g.data(), d.p, g.size() * sizeof(double), hipMemcpyDeviceToHost));
-      std::vector<double> sh((size_t)D0);
-      for (int64_t j = 0; j < D0; j++) sh[j] = (h[j] > 0 && h[j] < g[j]) ? 1.0 : 0.0;
-      d.upload(sh);
-      c->comm.allreduce(d.p, D0);
-      MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-      MFM_HIP_CHECK(hipMemcpy(sh.data(), d.p, sh.size() * sizeof(double), hipMemcpyDeviceToHost));
-      std::vector<char> special((size_t)D0, 0);
-      for (int64_t j = 0; j < D0; j++)
-        special[j] = c->hlevels[j] != 0 ? 0 : sh[j] > 0 ? 1 : g[j] == 0 ? 2 : 0;
-      c->plan_V.sharded_tiles = true;
-      c->plan_V.special = std::move(special);
+    std::vector<double> g = h;  // (h, this rank's own counts, is read again)
+    c->comm.sum_ranks(g, c->stream);
+    std::vector<double> sh((size_t)D0);
+    for (int64_t j = 0; j < D0; j++) sh[j] = (h[j] > 0 && h[j] < g[j]) ? 1.0 : 0.0;
+    c->comm.sum_ranks(sh, c->stream);
+    std::vector<char> special((size_t)D0, 0);
+    for (int64_t j = 0; j < D0; j++)
+      special[j] = c->hlevels[j] != 0 ? 0 : sh[j] > 0 ? 1 : g[j] == 0 ? 2 : 0;
+    c->plan_V.sharded_tiles = true;
+    c->plan_V.special = std::move(special);
+  }
+  c->plan_V.group_of = &c->hgroup;
+  // the row-tile layouts of scattered levels are packed on the device from the device-resident CSC
+  DevCscView dev_view = DevCscView{c->X.colptr.p, c->X.rowidx.p, c->X.cval.p, c->stream};
+  dev_view.rowptr = c->X.rowptr.p;
+  dev_view.colidx = c->X.colidx.p;
+  dev_view.n_rows = c->N;
+  dev_view.n_cols = c->D0;
+  dev_view.ell = (int)c->X.ell_width;
+  c->plan_V.dev_csc = c->X.colptr.p ? &dev_view : nullptr;
+  c->plan_W.dev_csc = c->plan_V.dev_csc;
+  c->plan_V.build(Xt, PMainV::R_W16, PMainV::R_WG, coop_v, true, c->X.unit);
+  lap("plan_V");
+  if (try_fused) {
+    // every rank must take the same path: agree
+    if (!c->comm.all_ranks(plan_supports_sharded_fused(c->plan_V), c->stream)) {
+      c->plan_V = StepPlan();
+      c->plan_V.sharded = true;
+      c->plan_V.given_levels = c->hlevels;
+      c->plan_V.tile_bits = tile_bits;
+      c->plan_V.group_of = &c->hgroup;
+      c->plan_V.dev_csc = c->plan_W.dev_csc;
+      c->plan_V.build(Xt, PMainV::R_W16, PMainV::R_WG, coop_v, true, c->X.unit);
+    } else {  // (plan_V.sharded_tiles stays set: decide_main_paths takes one of the Sharded forms)
+      // model synchronisation after the sweep: a non-special first-level column is contributed by the rank
+      // that holds its rows, every other column (identical on all ranks) by rank 0 of the communicator
+      // (a caller of the older sequence mfm_set_allreduce + mfm_set_row_offset never said which rank it is: the shard
+      // that starts at global row 0 is the root then)
+      const bool root = c->comm.shard_set ? c->comm.rank == 0 : c->row_offset == 0;
+      std::vector<double> mask((size_t)c->D, root ? 1.0 : 0.0);
+      for (int64_t j = 0; j < c->D0; j++)
+        if (c->hlevels[j] == 0 && c->plan_V.special[j] == 0) mask[j] = col_cnt[j] > 0 ? 1.0 : 0.0;
+      c->sync_mask.upload(mask);
     }
-    c->plan_V.group_of = &c->hgroup;
-    // the row-tile layouts of scattered levels are packed on the device from the device-resident CSC
-    DevCscView dev_view = DevCscView{c->X.colptr.p, c->X.rowidx.p, c->X.cval.p, c->stream};
-    dev_view.rowptr = c->X.rowptr.p;
-    dev_view.colidx = c->X.colidx.p;
-    dev_view.n_rows = c->N;
-    dev_view.n_cols = c->D0;
-    dev_view.ell = (int)c->X.ell_width;
-    c->plan_V.dev_csc = c->X.colptr.p ? &dev_view : nullptr;
-    c->plan_W.dev_csc = c->plan_V.dev_csc;
-    c->plan_V.build(Xt, PMainV::R_W16, PMainV::R_WG, coop_v, true, c->X.unit);
-    lap("plan_V");
-    if (try_fused) {
-      // every rank must take the same path: agree
-      double bad = plan_supports_sharded_fused(c->plan_V) ? 0.0 : 1.0;
-      DevBuf<double> d;
-      d.upload(&bad, 1);
-      c->comm.allreduce(d.p, 1);
-      MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-      MFM_HIP_CHECK(hipMemcpy(&bad, d.p, sizeof(double), hipMemcpyDeviceToHost));
-      if (bad > 0) {
-        c->plan_V = StepPlan();
-        c->plan_V.sharded = true;
-        c->plan_V.given_levels = c->hlevels;
-        c->plan_V.tile_bits = tile_bits;
-        c->plan_V.group_of = &c->hgroup;
-        c->plan_V.dev_csc = c->plan_W.dev_csc;
-        c->plan_V.build(Xt, PMainV::R_W16, PMainV::R_WG, coop_v, true, c->X.unit);
-      } else {  // (plan_V.sharded_tiles stays set: decide_main_paths takes one of the Sharded forms)
-        // model synchronisation after the sweep: a non-special first-level column is contributed by the rank
-        // that holds its rows, every other column (identical on all ranks) by rank 0 of the communicator
-        // (a caller of the older sequence mfm_set_allreduce + mfm_set_row_offset never said which rank it is: the shard
-        // that starts at global row 0 is the root then)
-        const bool root = c->comm.shard_set ? c->comm.rank == 0 : c->row_offset == 0;
-        std::vector<double> mask((size_t)c->D, root ? 1.0 : 0.0);
-        for (int64_t j = 0; j < c->D0; j++)
-          if (c->hlevels[j] == 0 && c->plan_V.special[j] == 0) mask[j] = col_cnt[j] > 0 ? 1.0 : 0.0;
-        c->sync_mask.upload(mask);
-      }
-    }
-    c->plan_W.build(Xt, PMainW::R_W16, PMainW::R_WG, coop_capacity<PMainW>(), true, c->X.unit,
-                    &c->plan_V);
-    lap("plan_W");
-    c->plan_V.dev_csc = c->plan_W.dev_csc = nullptr;  // (the view lives on this frame: build() is its only reader)
-    c->ls.reserve_cols(std::max(c->plan_V.max_cols_scat, c->plan_W.max_cols_scat));
-    if (c->comm.active()) {
-      c->ls.reserve_cols(c->D0);
-      c->ls.reserve_stats(c->D0);
-    }
+  }
+  c->plan_W.build(Xt, PMainW::R_W16, PMainW::R_WG, coop_capacity<PMainW>(), true, c->X.unit,
+                  &c->plan_V);
+  lap("plan_W");
+  c->plan_V.dev_csc = c->plan_W.dev_csc = nullptr;  // (the view lives on this frame: build() is its only reader)
+  c->ls.reserve_cols(std::max(c->plan_V.max_cols_scat, c->plan_W.max_cols_scat));
+  if (c->comm.active()) {
+    c->ls.reserve_cols(c->D0);
+    c->ls.reserve_stats(c->D0);
+  }
 }
 
 // which of update_V's forms the main table's plans support, and its buffers
@@ -1247,14 +1276,9 @@ static VPath decide_main_paths(mfm_ctx *c) {
   c->qc.alloc((size_t)c->N);
   if (sharded) {
     // no first-level column straddles a rank boundary (and none is longer than ... any length is fine): the two-field pass
-    double no = plan_supports_mf(c->plan_V) && c->plan_V.n_special == 0 && !env_flag("MFM_NO_MF") ? 0.0 : 1.0;
+    const bool mf = plan_supports_mf(c->plan_V) && c->plan_V.n_special == 0 && !env_flag("MFM_NO_MF");
     // every rank must take the same path
-    DevBuf<double> d;
-    d.upload(&no, 1);
-    c->comm.allreduce(d.p, 1);
-    MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    MFM_HIP_CHECK(hipMemcpy(&no, d.p, sizeof(double), hipMemcpyDeviceToHost));
-    return no == 0.0 ? VPath::ShardedTwoField : VPath::ShardedSplit;
+    return c->comm.all_ranks(mf, c->stream) ? VPath::ShardedTwoField : VPath::ShardedSplit;
   }
   if (!plan_supports_fused_next(c->plan_V) || env_flag("MFM_NO_FUSED_NEXT")) return VPath::Split;
   return plan_supports_mf(c->plan_V) && !env_flag("MFM_NO_MF") ? VPath::TwoField : VPath::SplitFused;
@@ -1293,11 +1317,10 @@ void mfm_ctx::ensure_main_plans() {
   v_path = decide_main_paths(this);
 }
 
-int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
-  MFM_TRY(ctx)
-  if (ctx->finalized) throw Error(MFM_ERR_RUNTIME, "design already finalized");
+// ---- mfm_finalize, stage by stage (in the order of the calls below) -----------------------------------------------------------
+static void check_design(mfm_ctx *c, int32_t rank) {
+  if (c->finalized) throw Error(MFM_ERR_RUNTIME, "design already finalized");
   if (rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
-  mfm_ctx *c = ctx;
   if (!c->main_set) {  // (no main table was given: an empty one)
     c->N = c->D0 = 0;
     c->X.upload(HostCsr(), nullptr);
@@ -1312,184 +1335,122 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
   if (c->N >= (int64_t)2147483647) throw Error(MFM_ERR_INVALID, "N must be < 2^31 per GPU");
   c->K = rank;
   c->KS = (rank + 1) & ~1;
-  // the parallel generator's jump polynomials (mfm_rng_set_program needs them right after this call): start computing
-  // them now on a helper thread (a caller that knows the problem's size earlier has already asked: mfm_rng_prepare)
-  c->rng.par_blocks = rng_prefetch_jumps(c->D, c->K, c->G, c->rng.par_blocks);
-  const bool tlog = env_flag("MFM_SETUP_TIMING");
-  auto tnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_prev = tnow();
-  CodeWarmup::get().join();
-  auto lap = [&](const char *what) {
-    if (!tlog) return;
-    const double t = tnow();
-    std::fprintf(stderr, "[mfm_finalize] %-28s %7.3f s\n", what, t - t_prev);
-    t_prev = t;
-  };
-  lap("(code object ready)");
-  // main table
-  HostCsr Xt_keep;  // (X_t outlives the planner's scope: the resident layout is built from it once the path is known)
-  {
-    HostCsr &Xt = Xt_keep;
-    // a row of unit-valued one-hot fields + relation blocks on one GPU: update_w / update_V / update_e on index tuples, no
-    // q-cache (mfm_cell.hpp). Decided first: when it takes the design, X_t, the main table's level plans and row tiles and
-    // the blocks' inverse maps are never used and are not built (config 5: 1.3 s of mfm_finalize and 3 GB of HBM).
-    {
-      const int64_t cell_min_rows = env_i64("MFM_CELL_MIN_ROWS", (int64_t)1 << 20);
-      // row-sharded: every rank plans its own rows; what must be the same everywhere (fields, streams, the verdict) is summed
-      // over the ranks inside the planner
-      const bool sh = c->comm.active();
-      auto sum_ranks = [&](std::vector<double> &v) {
-        DevBuf<double> d;
-        d.upload(v);
-        c->comm.allreduce(d.p, (int64_t)v.size());
-        MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        MFM_HIP_CHECK(hipMemcpy(v.data(), d.p, v.size() * sizeof(double), hipMemcpyDeviceToHost));
-      };
-      // (also tables of three or more one-hot fields WITHOUT relation blocks on one GPU: one pass per field instead of the
-      //  row-tile passes of run_sweep_soa_multi; two-field tables keep the persistent sweep / the two-field pass)
-      const bool flat = c->hblocks.empty() && !sh && c->X.ell_width >= 3;
-      bool try_cell = (!c->hblocks.empty() || flat) && c->K > 0 && !env_flag("MFM_NO_CELL");
-      if (!sh) {
-        try_cell = try_cell && c->X.unit && c->X.ell_width >= 1 && c->N >= cell_min_rows;
-      } else if (try_cell) {  // (the same decision on every rank: the rows of all of them count, an empty shard has no say)
-        std::vector<double> v{(double)c->N, (c->N > 0 && !(c->X.unit && c->X.ell_width >= 1)) ? 1.0 : 0.0, c->comm.shard_set ? 0.0 : 1.0};
-        sum_ranks(v);
-        try_cell = v[0] >= (double)cell_min_rows && v[1] == 0.0 && v[2] == 0.0;
-      }
-      if (try_cell) {
-        int n_cu = 0;
-        MFM_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
-        if (env_flag("MFM_CELL_GROUPS")) n_cu = std::max(1, env_int("MFM_CELL_GROUPS", 0));
-        std::vector<CellBlockIn> bin;
-        for (auto &hb : c->hblocks) bin.push_back(CellBlockIn{hb.map.get(), hb.X.rows});
-        const int sh_rank = c->comm.shard_set ? c->comm.rank : -1;
-        // one GPU: the plan is built on the device from the CSR and the blocks' maps (uploaded here, kept for the blocks)
-        const size_t nb = c->hblocks.size();
-        c->pre_maps.clear();
-        c->pre_maps.resize(nb);
-        {
-          std::vector<std::thread> pool;
-          std::vector<std::exception_ptr> errs(nb);
-          auto up = [&](size_t b) {
-            try {
-              MFM_HIP_CHECK(hipSetDevice(c->device));
-              c->pre_maps[b].upload(c->hblocks[b].map.get(), (size_t)c->N);
-            } catch (...) {
-              errs[b] = std::current_exception();
-            }
-          };
-          for (size_t b = 0; b + 1 < nb; b++) pool.emplace_back(up, b);
-          if (nb) up(nb - 1);
-          for (auto &t : pool) t.join();
-          for (auto &e : errs)
-            if (e) std::rethrow_exception(e);
-        }
-        lap("block maps to the device");
-        std::vector<CellBlockDev> bdev;
-        for (size_t b = 0; b < nb; b++) bdev.push_back(CellBlockDev{c->pre_maps[b].p, c->hblocks[b].X.rows});
-        // (row-sharded: every rank plans its own rows on its own device, the agreements are summed over the ranks inside)
-        auto host_plan = [&](CellPlan &cp) {
-          if (sh)
-            cell_plan_build(cp, c->host_main(), bin, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
-          else
-            cell_plan_build(cp, c->host_main(), bin, n_cu, c->stream);
-        };
-        if (sh)
-          cell_plan_build_device(c->cell, c->X, bdev, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
-        else
-          cell_plan_build_device(c->cell, c->X, bdev, n_cu, c->stream);
-        if (!c->cell.ready && c->cell.why.rfind("device planner:", 0) == 0) {
-          host_plan(c->cell);  // (a shape only the host planner handles: the same verdict on every rank)
-        } else if (env_flag("MFM_PLAN_CHECK")) {  // tests: the host planner must give the same plan, array for array
-          lap("cell plan (device)");
-          CellPlan chk;
-          host_plan(chk);
-          if (chk.ready != c->cell.ready) throw Error(MFM_ERR_RUNTIME, "plan check: device and host cell planners disagree: device '" + c->cell.why + "' host '" + chk.why + "'");
-          if (chk.ready) {
-            const std::string diff = cell_plan_compare(c->cell, chk, c->stream);
-            if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host cell plans differ (" + diff + ")");
-          }
-        }
-        c->cell_w = c->cell.ready && !env_flag("MFM_NO_CELL_W");
-        if (tlog)
-          std::fprintf(stderr, "[mfm_finalize] cell plan: %s (G=%d umax=%lld streams=%zu fields=%zu item32=%d)\n",
-                       c->cell.ready ? "ready" : c->cell.why.c_str(), c->cell.G, (long long)c->cell.umax, c->cell.streams.size(),
-                       c->cell.fields.size(), (int)c->cell.item32);
-        lap("cell plan");
-      }
-    }
-    // two-field unit-valued table on one GPU: the persistent sweep's layout is built FIRST, on the device, straight from the
-    // CSR (mfm_res_plan.hpp). When it takes the table, X_t, the level plans and the row tiles of the per-factor passes (its
-    // fall-back, and what a stand-alone mfm_sweep_w runs) are built only if a call ever needs them (ensure_main_plans):
-    // config 3 0.26 s of mfm_finalize -> 0.1 s.
-    if (!c->cell.ready) try_resident_first(c, lap);
-    const bool lean = c->cell_w || c->v_path == VPath::Deferred;
-    if (!lean) plan_main_table(c, Xt, lap);
+}
+
+// a row of unit-valued one-hot fields + relation blocks on one GPU: update_w / update_V / update_e on index tuples, no
+// q-cache (mfm_cell.hpp). Decided first: when it takes the design, X_t, the main table's level plans and row tiles and
+// the blocks' inverse maps are never used and are not built (config 5: 1.3 s of mfm_finalize and 3 GB of HBM).
+static void plan_cell(mfm_ctx *c, const Lap &lap) {
+  const int64_t cell_min_rows = env_i64("MFM_CELL_MIN_ROWS", (int64_t)1 << 20);
+  // row-sharded: every rank plans its own rows; what must be the same everywhere (fields, streams, the verdict) is summed
+  // over the ranks inside the planner
+  const bool sh = c->comm.active();
+  const std::function<void(std::vector<double> &)> sum_ranks = [c](std::vector<double> &v) { c->comm.sum_ranks(v, c->stream); };
+  // (also tables of three or more one-hot fields WITHOUT relation blocks on one GPU: one pass per field instead of the
+  //  row-tile passes of run_sweep_soa_multi; two-field tables keep the persistent sweep / the two-field pass)
+  const bool flat = c->hblocks.empty() && !sh && c->X.ell_width >= 3;
+  bool try_cell = (!c->hblocks.empty() || flat) && c->K > 0 && !env_flag("MFM_NO_CELL");
+  if (!sh) {
+    try_cell = try_cell && c->X.unit && c->X.ell_width >= 1 && c->N >= cell_min_rows;
+  } else if (try_cell) {  // (the same decision on every rank: the rows of all of them count, an empty shard has no say)
+    std::vector<double> v{(double)c->N, (c->N > 0 && !(c->X.unit && c->X.ell_width >= 1)) ? 1.0 : 0.0, c->comm.shard_set ? 0.0 : 1.0};
+    sum_ranks(v);
+    try_cell = v[0] >= (double)cell_min_rows && v[1] == 0.0 && v[2] == 0.0;
   }
+  if (!try_cell) return;
+  int n_cu = 0;
+  MFM_HIP_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device));
+  if (env_flag("MFM_CELL_GROUPS")) n_cu = std::max(1, env_int("MFM_CELL_GROUPS", 0));
+  std::vector<CellBlockIn> bin;
+  for (auto &hb : c->hblocks) bin.push_back(CellBlockIn{hb.map.get(), hb.X.rows});
+  const int sh_rank = c->comm.shard_set ? c->comm.rank : -1;
+  // one GPU: the plan is built on the device from the CSR and the blocks' maps (uploaded here, kept for the blocks)
+  const size_t nb = c->hblocks.size();
+  c->pre_maps.clear();
+  c->pre_maps.resize(nb);
+  for_each_block(c->device, nb, [&](size_t b) { c->pre_maps[b].upload(c->hblocks[b].map.get(), (size_t)c->N); });
+  lap("block maps to the device");
+  std::vector<CellBlockDev> bdev;
+  for (size_t b = 0; b < nb; b++) bdev.push_back(CellBlockDev{c->pre_maps[b].p, c->hblocks[b].X.rows});
+  // (row-sharded: every rank plans its own rows on its own device, the agreements are summed over the ranks inside)
+  auto host_plan = [&](CellPlan &cp) {
+    if (sh)
+      cell_plan_build(cp, c->host_main(), bin, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
+    else
+      cell_plan_build(cp, c->host_main(), bin, n_cu, c->stream);
+  };
+  if (sh)
+    cell_plan_build_device(c->cell, c->X, bdev, n_cu, c->stream, sh_rank, c->comm.world, sum_ranks);
+  else
+    cell_plan_build_device(c->cell, c->X, bdev, n_cu, c->stream);
+  if (!c->cell.ready && c->cell.why.rfind("device planner:", 0) == 0) {
+    host_plan(c->cell);  // (a shape only the host planner handles: the same verdict on every rank)
+  } else if (env_flag("MFM_PLAN_CHECK")) {  // tests: the host planner must give the same plan, array for array
+    lap("cell plan (device)");
+    CellPlan chk;
+    host_plan(chk);
+    if (chk.ready != c->cell.ready) throw Error(MFM_ERR_RUNTIME, "plan check: device and host cell planners disagree: device '" + c->cell.why + "' host '" + chk.why + "'");
+    if (chk.ready) {
+      const std::string diff = cell_plan_compare(c->cell, chk, c->stream);
+      if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host cell plans differ (" + diff + ")");
+    }
+  }
+  c->cell_w = c->cell.ready && !env_flag("MFM_NO_CELL_W");
+  if (env_flag("MFM_SETUP_TIMING"))
+    std::fprintf(stderr, "[mfm_finalize] cell plan: %s (G=%d umax=%lld streams=%zu fields=%zu item32=%d)\n",
+                 c->cell.ready ? "ready" : c->cell.why.c_str(), c->cell.G, (long long)c->cell.umax, c->cell.streams.size(),
+                 c->cell.fields.size(), (int)c->cell.item32);
+  lap("cell plan");
+}
+
+// the residual, the features' groups and the features sorted by group (FMLearningConfig.hpp:41-46 group_vs_feature_index)
+static void upload_feature_groups(mfm_ctx *c) {
   c->eq_.alloc_zero((size_t)c->N, c->stream);
   c->group.upload(c->hgroup);
-  // features sorted by group (FMLearningConfig.hpp:41-46 group_vs_feature_index)
-  {
-    std::vector<int64_t> gptr((size_t)c->G + 1, 0);
-    for (auto g : c->hgroup) gptr[g + 1]++;
-    for (int g = 0; g < c->G; g++) gptr[g + 1] += gptr[g];
-    std::vector<int32_t> fs((size_t)c->D);
-    std::vector<int64_t> cur(gptr.begin(), gptr.end() - 1);
-    for (int64_t j = 0; j < c->D; j++) fs[cur[c->hgroup[j]]++] = (int32_t)j;
-    c->group_ptr.upload(gptr);
-    c->feat_sorted.upload(fs);
-    int64_t big = 1;
-    for (int g = 0; g < c->G; g++) big = std::max(big, gptr[g + 1] - gptr[g]);
-    c->gs_chunks = (int)((big + GS_CHUNK - 1) / GS_CHUNK);
-  }
-  // relation blocks
+  std::vector<int64_t> gptr((size_t)c->G + 1, 0);
+  for (auto g : c->hgroup) gptr[g + 1]++;
+  for (int g = 0; g < c->G; g++) gptr[g + 1] += gptr[g];
+  std::vector<int32_t> fs((size_t)c->D);
+  std::vector<int64_t> cur(gptr.begin(), gptr.end() - 1);
+  for (int64_t j = 0; j < c->D; j++) fs[cur[c->hgroup[j]]++] = (int32_t)j;
+  c->group_ptr.upload(gptr);
+  c->feat_sorted.upload(fs);
+  int64_t big = 1;
+  for (int g = 0; g < c->G; g++) big = std::max(big, gptr[g + 1] - gptr[g]);
+  c->gs_chunks = (int)((big + GS_CHUNK - 1) / GS_CHUNK);
+}
+
+// the relation blocks' device structures (transpose, plans, inverse maps: O(N) host passes each) are independent: host threads.
+// With them the long-column scratch of every plan is known.
+static void build_blocks(mfm_ctx *c) {
+  const size_t nb = c->hblocks.size();
+  std::vector<std::unique_ptr<DevBlock>> built(nb);
+  std::vector<int64_t> offs(nb);
   int64_t off = c->D0;
+  for (size_t b = 0; b < nb; b++) {
+    offs[b] = off;
+    off += c->hblocks[b].X.cols;
+  }
+  (void)coop_capacity<PBlockV>();  // (function-local caches: filled before the threads start)
+  (void)coop_capacity<PBlockW>();
+  for_each_block(c->device, nb, [&](size_t b) {
+    built[b].reset(new DevBlock());
+    built[b]->col_off = offs[b];
+    built[b]->build(c->hblocks[b].X, c->hblocks[b].map.get(), c->N, c->KS, c->stream, c->cell_w,
+                    b < c->pre_maps.size() ? &c->pre_maps[b] : nullptr);
+  });
   int max_chunks = std::max(c->plan_V.max_hchunks, c->plan_W.max_hchunks);
   int max_long = std::max(c->plan_V.max_huge, c->plan_W.max_huge);
-  {
-    // the blocks' device structures (transpose, plans, inverse maps: O(N) host passes each) are independent: host threads
-    std::vector<std::unique_ptr<DevBlock>> built(c->hblocks.size());
-    std::vector<std::exception_ptr> errs(c->hblocks.size());
-    std::vector<int64_t> offs(c->hblocks.size());
-    for (size_t b = 0; b < c->hblocks.size(); b++) {
-      offs[b] = off;
-      off += c->hblocks[b].X.cols;
-    }
-    auto build_one = [&](size_t b) {
-      try {
-        MFM_HIP_CHECK(hipSetDevice(c->device));
-        built[b].reset(new DevBlock());
-        built[b]->col_off = offs[b];
-        built[b]->build(c->hblocks[b].X, c->hblocks[b].map.get(), c->N, c->KS, c->stream, c->cell_w,
-                        b < c->pre_maps.size() ? &c->pre_maps[b] : nullptr);
-      } catch (...) {
-        errs[b] = std::current_exception();
-      }
-    };
-    {
-      (void)coop_capacity<PBlockV>();  // (function-local caches: filled before the threads start)
-      (void)coop_capacity<PBlockW>();
-      std::vector<std::thread> pool;
-      const bool par = c->hblocks.size() > 1;
-      for (size_t b = 0; b < c->hblocks.size(); b++) {
-        if (par && b + 1 < c->hblocks.size())
-          pool.emplace_back(build_one, b);
-        else
-          build_one(b);
-      }
-      for (auto &t : pool) t.join();
-    }
-    for (size_t b = 0; b < built.size(); b++) {
-      if (errs[b]) std::rethrow_exception(errs[b]);
-      std::unique_ptr<DevBlock> &B = built[b];
-      max_chunks = std::max({max_chunks, B->plan_V.max_hchunks, B->plan_W.max_hchunks});
-      max_long = std::max({max_long, B->plan_V.max_huge, B->plan_W.max_huge});
-      B->allreduce_fields(c->stream, c->comm, 6, 1);  // cardinality counts the rows of ALL ranks (definitions.hpp:65-68)
-      c->blocks.push_back(std::move(B));
-    }
+  for (std::unique_ptr<DevBlock> &B : built) {
+    max_chunks = std::max({max_chunks, B->plan_V.max_hchunks, B->plan_W.max_hchunks});
+    max_long = std::max({max_long, B->plan_V.max_huge, B->plan_W.max_huge});
+    B->allreduce_fields(c->stream, c->comm, 6, 1);  // cardinality counts the rows of ALL ranks (definitions.hpp:65-68)
+    c->blocks.push_back(std::move(B));
   }
   c->ls.reserve(std::max(max_chunks, 1), std::max(max_long, 1));
-  // state + scratch
+}
+
+static void alloc_state(mfm_ctx *c) {  // state + scratch
   c->w.alloc_zero((size_t)c->D, c->stream);
   c->V.alloc_zero((size_t)c->D * c->K, c->stream);
   c->Vt.alloc_zero((size_t)c->D * c->KS, c->stream);
@@ -1499,81 +1460,105 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
   c->red_partial.alloc(REDUCE_BLOCKS);
   c->red_out.alloc((size_t)1 + (size_t)c->G * std::max(c->K, 1));
   c->scratch_n.alloc((size_t)std::max<int64_t>(c->N, 1));
-  if (c->v_path != VPath::Deferred) c->v_path = decide_main_paths(c);
-  // two-field unit-valued table on one GPU: the whole update_V as one persistent launch, residual resident on chip
-  // (small tables stay with the per-factor passes: the launch's fixed costs -- two grid barriers per sweep, census, slot-ordered
-  //  residual -- outweigh the bytes it saves; ML-100k shape: fit() 3060 it/s resident, 3950 per-factor. MFM_RES_MIN_ROWS)
-  if (c->res.ready) {
-    // (built first, on the device) tests: the host builder on X_t must give the same layout, array for array
+}
+
+// two-field unit-valued table on one GPU: the whole update_V as one persistent launch, residual resident on chip
+// (small tables stay with the per-factor passes: the launch's fixed costs -- two grid barriers per sweep, census, slot-ordered
+//  residual -- outweigh the bytes it saves; ML-100k shape: fit() 3060 it/s resident, 3950 per-factor. MFM_RES_MIN_ROWS)
+// Once the paths are known: a layout that try_resident_first built is checked (tests), a table it passed over gets the host builder's.
+static void resident_after_paths(mfm_ctx *c, const HostCsr &Xt, const Lap &lap) {
+  const ResLayoutAsk host{&Xt, &c->plan_V.h_level, nullptr, true};
+  if (c->resident_V()) {
     if (c->v_path != VPath::Deferred && env_flag("MFM_PLAN_CHECK")) {
-      ResPlan chk;
-      chk.build(Xt_keep, c->plan_V.h_level, &c->hgroup, c->res_plan_cus);
-      const std::string diff = chk.ready ? res_plan_compare(c->res, chk, c->stream) : ("host builder: " + chk.why);
-      if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host resident layouts differ (" + diff + ")");
+      check_resident_plan(c, host, "");
       lap("resident plan (host, check)");
     }
-  } else if (!c->res_refused && c->v_path == VPath::TwoField && c->X.unit && c->N >= res_min_rows(c) && !env_flag("MFM_NO_RESIDENT")) {
-    plan_resident(c, [&](ResPlan &rp, int n_cu) { rp.build(Xt_keep, c->plan_V.h_level, &c->hgroup, n_cu); }, tlog);
+  } else if (c->res_state != ResState::Refused && c->v_path == VPath::TwoField && c->X.unit && c->N >= res_min_rows() &&
+             !env_flag("MFM_NO_RESIDENT")) {
+    if (plan_resident(c, host, env_flag("MFM_SETUP_TIMING"))) c->res_state = ResState::Live;
     lap("resident plan (host)");
   }
-  // Row-sharded with the shards cut between users (VPath::ShardedTwoField): the persistent sweep runs on every rank
-  // over its own rows, the ranks' item sums meet inside the launch (mfm_res.hpp, XCH). The layout is built here -- items = the
-  // level-1 columns of the GLOBAL design, so every rank numbers them alike -- and goes live when the caller has handed over the
-  // peers' exchange buffers (mfm_peer_set); until then, and if any rank cannot take part, the per-factor passes run.
-  if (c->v_path == VPath::ShardedTwoField && c->comm.shard_set && c->comm.world <= RES_MAX_PEERS && c->comm.world > 1 &&
-      !env_flag("MFM_NO_RESIDENT") && !env_flag("MFM_NO_SHARDED_RESIDENT")) {
-    const int64_t min_rows = res_min_rows(c);
-    const bool want = c->X.unit && c->X.ell_width == 2 && c->N >= std::max<int64_t>(1, min_rows / c->comm.world) && c->K > 0;
-    bool mine = false;
-    if (want) {
-      std::vector<char> draw_empty((size_t)c->D0, 0);
-      for (int64_t j = 0; j < c->D0; j++) draw_empty[j] = (size_t)j < c->plan_V.special.size() && c->plan_V.special[j] == 2;
-      plan_resident(c, [&](ResPlan &rp, int n_cu) {
-        rp.allow_overflow = false;
-        res_plan_build_device(rp, c->X, &c->hgroup, n_cu, c->stream, &c->hlevels, &draw_empty);
-      }, tlog);
-      if (c->res.ready && env_flag("MFM_PLAN_CHECK")) {
-        ResPlan chk;
-        chk.allow_overflow = false;
-        chk.build(Xt_keep, c->hlevels, &c->hgroup, c->res_plan_cus, &draw_empty);
-        const std::string diff = chk.ready ? res_plan_compare(c->res, chk, c->stream) : ("host builder: " + chk.why);
-        if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host resident layouts differ (sharded; " + diff + ")");
-      }
-      mine = c->res.ready;
-      c->res.ready = false;
-    }
-    if (mine) {  // the exchange buffers BEFORE the ranks agree: a rank that gets no uncached memory votes against the layout
-      try {
-        c->res.alloc_exchange(c->comm.world, c->comm.rank, c->stream);
-      } catch (const Error &) {
-        mine = false;
-      }
-    }
-    double bad = mine ? 0.0 : 1.0;
-    {
-      DevBuf<double> d;
-      d.upload(&bad, 1);
-      c->comm.allreduce(d.p, 1);
-      MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-      MFM_HIP_CHECK(hipMemcpy(&bad, d.p, sizeof(double), hipMemcpyDeviceToHost));
-    }
-    if (bad == 0.0) {
-      c->res_sharded_pending = true;
-    } else {
-      c->drop_resident();
-    }
-    lap("resident plan (row-sharded)");
+}
+
+// Row-sharded with the shards cut between users (VPath::ShardedTwoField): the persistent sweep runs on every rank
+// over its own rows, the ranks' item sums meet inside the launch (mfm_res.hpp, XCH). The layout is built here -- items = the
+// level-1 columns of the GLOBAL design, so every rank numbers them alike -- and goes live when the caller has handed over the
+// peers' exchange buffers (mfm_peer_set); until then, and if any rank cannot take part, the per-factor passes run.
+static void resident_sharded(mfm_ctx *c, const HostCsr &Xt, const Lap &lap) {
+  if (!(c->v_path == VPath::ShardedTwoField && c->comm.shard_set && c->comm.world <= RES_MAX_PEERS && c->comm.world > 1 &&
+        !env_flag("MFM_NO_RESIDENT") && !env_flag("MFM_NO_SHARDED_RESIDENT")))
+    return;
+  bool mine = false;
+  if (c->X.unit && c->X.ell_width == 2 && c->N >= std::max<int64_t>(1, res_min_rows() / c->comm.world) && c->K > 0) {
+    std::vector<char> draw_empty((size_t)c->D0, 0);
+    for (int64_t j = 0; j < c->D0; j++) draw_empty[j] = (size_t)j < c->plan_V.special.size() && c->plan_V.special[j] == 2;
+    mine = plan_resident(c, {nullptr, &c->hlevels, &draw_empty, false}, env_flag("MFM_SETUP_TIMING"));
+    if (mine && env_flag("MFM_PLAN_CHECK")) check_resident_plan(c, {&Xt, &c->hlevels, &draw_empty, false}, "sharded; ");
   }
-  Xt_keep = HostCsr();
+  if (mine) {  // the exchange buffers BEFORE the ranks agree: a rank that gets no uncached memory votes against the layout
+    try {
+      c->res.alloc_exchange(c->comm.world, c->comm.rank, c->stream);
+    } catch (const Error &) {
+      mine = false;
+    }
+  }
+  if (c->comm.all_ranks(mine, c->stream))
+    c->res_state = ResState::AwaitingPeers;
+  else
+    c->drop_resident();
+  lap("resident plan (row-sharded)");
+}
+
+static void wait_for_setup(mfm_ctx *c, HostCsr &Xt) {
+  Xt = HostCsr();
   MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
-  lap("blocks, state, scratch");
-  // host copies are no longer needed
-  lap("(sync)");
+}
+
+static void release_host_copies(mfm_ctx *c) {  // host copies are no longer needed
   c->hX = HostCsr();
   c->hX_valid = false;
   c->hy = std::vector<double>();
   c->hblocks.clear();
   c->pre_maps.clear();
+}
+
+int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
+  MFM_TRY(ctx)
+  mfm_ctx *c = ctx;
+  check_design(c, rank);
+  // the parallel generator's jump polynomials (mfm_rng_set_program needs them right after this call): start computing
+  // them now on a helper thread (a caller that knows the problem's size earlier has already asked: mfm_rng_prepare)
+  c->rng.par_blocks = rng_prefetch_jumps(c->D, c->K, c->G, c->rng.par_blocks);
+  const bool tlog = env_flag("MFM_SETUP_TIMING");
+  auto tnow = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  double t_prev = tnow();
+  CodeWarmup::get().join();
+  const Lap lap = [&](const char *what) {
+    if (!tlog) return;
+    const double t = tnow();
+    std::fprintf(stderr, "[mfm_finalize] %-28s %7.3f s\n", what, t - t_prev);
+    t_prev = t;
+  };
+  lap("(code object ready)");
+  plan_cell(c, lap);
+  // two-field unit-valued table on one GPU: the persistent sweep's layout is built FIRST, on the device, straight from the
+  // CSR (mfm_res_plan.hpp). When it takes the table, X_t, the level plans and the row tiles of the per-factor passes (its
+  // fall-back, and what a stand-alone mfm_sweep_w runs) are built only if a call ever needs them (ensure_main_plans):
+  // config 3 0.26 s of mfm_finalize -> 0.1 s.
+  if (!c->cell.ready) try_resident_first(c, lap);
+  HostCsr Xt;  // (X_t outlives its planner: the resident layouts are built from it once the path is known)
+  const bool lean = c->cell_w || c->v_path == VPath::Deferred;
+  if (!lean) plan_main_table(c, Xt, lap);
+  upload_feature_groups(c);
+  build_blocks(c);
+  alloc_state(c);
+  if (c->v_path != VPath::Deferred) c->v_path = decide_main_paths(c);
+  resident_after_paths(c, Xt, lap);
+  resident_sharded(c, Xt, lap);
+  wait_for_setup(c, Xt);
+  lap("blocks, state, scratch");
+  lap("(sync)");
+  release_host_copies(c);
   lap("host copies released");
   c->finalized = true;
   MFM_CATCH(ctx)
@@ -1583,7 +1568,7 @@ int mfm_finalize(mfm_ctx *ctx, int32_t rank) {
 int mfm_peer_info(mfm_ctx *ctx, int32_t *pending, void **sum_buf, void **flag_buf, int64_t *sum_bytes, int64_t *flag_bytes) {
   MFM_TRY(ctx)
   ctx->need_final();
-  const bool p = ctx->res_sharded_pending;
+  const bool p = ctx->res_state == ResState::AwaitingPeers;
   if (pending) *pending = p ? 1 : 0;
   if (sum_buf) *sum_buf = p ? (void *)ctx->res.xsum.p : nullptr;
   if (flag_buf) *flag_buf = p ? (void *)ctx->res.xflag.p : nullptr;
@@ -1596,7 +1581,7 @@ int mfm_peer_set(mfm_ctx *ctx, int32_t world, int32_t rank, void *const *sum_buf
   MFM_TRY(ctx)
   ctx->need_final();
   mfm_ctx *c = ctx;
-  if (!c->res_sharded_pending) throw Error(MFM_ERR_RUNTIME, "mfm_peer_set: this context has no row-sharded persistent sweep waiting for its peers");
+  if (c->res_state != ResState::AwaitingPeers) throw Error(MFM_ERR_RUNTIME, "mfm_peer_set: this context has no row-sharded persistent sweep waiting for its peers");
   if (world != c->res.xworld || rank != c->res.xrank) throw Error(MFM_ERR_INVALID, "mfm_peer_set: world / rank differ from the communicator's");
   for (int r = 0; r < world; r++) {
     if (!sum_bufs[r] || !flag_bufs[r]) throw Error(MFM_ERR_INVALID, "mfm_peer_set: null buffer");
@@ -1607,8 +1592,7 @@ int mfm_peer_set(mfm_ctx *ctx, int32_t world, int32_t rank, void *const *sum_buf
     throw Error(MFM_ERR_INVALID, "mfm_peer_set: this rank's own entry must be the buffers of mfm_peer_info");
   MFM_HIP_CHECK(hipStreamSynchronize(c->stream));
   c->res.peers_set = true;
-  c->res.ready = true;
-  c->res_sharded_pending = false;
+  c->res_state = ResState::Live;
   MFM_CATCH(ctx)
 }
 
@@ -1618,7 +1602,7 @@ int mfm_peer_set_model(mfm_ctx *ctx, int32_t world, int32_t rank, void *const *w
   MFM_TRY(ctx)
   ctx->need_final();
   mfm_ctx *c = ctx;
-  if (!c->res.ready || !c->res.peers_set) throw Error(MFM_ERR_RUNTIME, "mfm_peer_set_model: mfm_peer_set comes first");
+  if (!c->resident_V() || !c->res.peers_set) throw Error(MFM_ERR_RUNTIME, "mfm_peer_set_model: mfm_peer_set comes first");
   if (world != c->res.xworld || rank != c->res.xrank) throw Error(MFM_ERR_INVALID, "mfm_peer_set_model: world / rank differ from the communicator's");
   for (int r = 0; r < world; r++) {
     if (!w_bufs[r] || (c->K > 0 && !V_bufs[r])) throw Error(MFM_ERR_INVALID, "mfm_peer_set_model: null buffer");
@@ -1644,7 +1628,7 @@ int mfm_peer_model_info(mfm_ctx *ctx, void **w_buf, void **V_buf) {
 int mfm_peer_export(mfm_ctx *ctx, void *handles256) {
   MFM_TRY(ctx)
   ctx->need_final();
-  if (!ctx->res_sharded_pending) throw Error(MFM_ERR_RUNTIME, "mfm_peer_export: no row-sharded persistent sweep waiting for its peers");
+  if (ctx->res_state != ResState::AwaitingPeers) throw Error(MFM_ERR_RUNTIME, "mfm_peer_export: no row-sharded persistent sweep waiting for its peers");
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
   hipIpcMemHandle_t h[4];
   std::memset(h, 0, sizeof h);
@@ -1661,7 +1645,7 @@ int mfm_peer_import(mfm_ctx *ctx, int32_t world, int32_t rank, const void *all_h
   MFM_TRY(ctx)
   ctx->need_final();
   mfm_ctx *c = ctx;
-  if (!c->res_sharded_pending) throw Error(MFM_ERR_RUNTIME, "mfm_peer_import: no row-sharded persistent sweep waiting for its peers");
+  if (c->res_state != ResState::AwaitingPeers) throw Error(MFM_ERR_RUNTIME, "mfm_peer_import: no row-sharded persistent sweep waiting for its peers");
   if (world != c->res.xworld || rank != c->res.xrank) throw Error(MFM_ERR_INVALID, "mfm_peer_import: world / rank differ from the communicator's");
   void *sums[RES_MAX_PEERS], *flags[RES_MAX_PEERS], *ws[RES_MAX_PEERS], *Vs[RES_MAX_PEERS];
   for (int r = 0; r < world; r++) {
@@ -1752,21 +1736,21 @@ int mfm_plan_flags(const mfm_ctx *ctx) {
     case VPath::Cell:
       break;
   }
-  return (streamed ? 1024 : 0) | (ctx->res.ready && ctx->res.RX > 0 ? 2048 : 0) | form | (ctx->X.unit ? 2 : 0) | (ctx->X.ell_width >= 0 ? 4 : 0) |
-         (ctx->comm.active() ? 8 : 0) | (ctx->res.ready ? 256 : 0) | (ctx->cell.ready ? 512 : 0);
+  return (streamed ? 1024 : 0) | (ctx->resident_V() && ctx->res.RX > 0 ? 2048 : 0) | form | (ctx->X.unit ? 2 : 0) | (ctx->X.ell_width >= 0 ? 4 : 0) |
+         (ctx->comm.active() ? 8 : 0) | (ctx->resident_V() ? 256 : 0) | (ctx->cell.ready ? 512 : 0);
 }
 
 // The persistent sweep's layout as the planner left it (host-side fields only: no launch, no synchronisation)
 int mfm_res_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why_len) {
   if (!ctx || n_out < 0 || (n_out > 0 && !out) || why_len < 0 || (why_len > 0 && !why)) return MFM_ERR_INVALID;
   const ResPlan &rp = ctx->res;
-  const int64_t v[MFM_RES_INFO_FIELDS] = {rp.ready ? 1 : 0, rp.G,       rp.RV,     rp.RL,           rp.RX,
+  const int64_t v[MFM_RES_INFO_FIELDS] = {ctx->resident_V() ? 1 : 0, rp.G,       rp.RV,     rp.RL,           rp.RX,
                                           rp.umax,          rp.n_items, rp.item_bits, rp.n_runs,    rp.max_wg_users,
                                           rp.max_slice_items, (int64_t)ctx->e_where, rp.n_rows, rp.s2b, (int64_t)rp.lds_bytes,
                                           rp.ent_bytes};
   for (int i = 0; i < n_out; i++) out[i] = i < MFM_RES_INFO_FIELDS ? v[i] : 0;
   if (why_len > 0) {
-    std::strncpy(why, rp.ready ? "" : rp.why.c_str(), (size_t)why_len - 1);
+    std::strncpy(why, ctx->resident_V() ? "" : rp.why.c_str(), (size_t)why_len - 1);
     why[why_len - 1] = 0;
   }
   return MFM_OK;
@@ -2108,7 +2092,7 @@ int mfm_sweep_wV(mfm_ctx *ctx, double alpha, double e_shift, const double *lambd
                  int32_t f_begin, int32_t f_end, const double *lambda_V, const double *mu_V, const double *zv) {
   {
     mfm_ctx *c = ctx;
-    const bool fused = c && c->finalized && c->res.ready && f_begin < f_end;
+    const bool fused = c && c->finalized && c->resident_V() && f_begin < f_end;
     if (!fused) {
       int rc = e_shift != 0.0 ? mfm_shift_e(ctx, e_shift) : MFM_OK;
       if (rc == MFM_OK) rc = mfm_sweep_w(ctx, alpha, lambda_w, mu_w, zw);
@@ -2153,7 +2137,7 @@ int mfm_sweep_wV(mfm_ctx *ctx, double alpha, double e_shift, const double *lambd
 
 // ---- a whole regression iteration without the host in its loop (include/myfm_hip.h) -------------------------------------------
 static bool regression_iteration_ready(mfm_ctx *c) {
-  if (!c || !c->finalized || !c->res.ready || c->comm.active() || c->K <= 0 || c->D <= 0) return false;
+  if (!c || !c->finalized || !c->resident_V() || c->comm.active() || c->K <= 0 || c->D <= 0) return false;
   if (!res_score_supported(c->res, c->K)) return false;
   if (!(c->e_where == EWhere::SlotsWithSums && c->e_is_residual)) return false;  // (update_e's slot-order sums)
   const auto &r = c->rng;
@@ -2340,7 +2324,7 @@ int mfm_sweep_V(mfm_ctx *ctx, int32_t f_begin, int32_t f_end, double alpha, cons
       throw Error(MFM_ERR_RUNTIME, "mfm_sweep_V(z = NULL) needs an acquired device random set with K*D z_V variates");
     zbase = c->rng.slot[c->rng.current].zv.p + (size_t)f_begin * c->D;
   }
-  if (c->v_path == VPath::Deferred && !c->res.ready) c->ensure_main_plans();
+  if (c->v_path == VPath::Deferred && !c->resident_V()) c->ensure_main_plans();
   if (c->resident_V()) {  // (row-sharded: the peers' buffers are set)
     launch_resident(c, f_begin, f_end, zbase, c->lam.p, c->mu.p, alpha);
     return MFM_OK;
@@ -2644,7 +2628,7 @@ int mfm_rng_prefetch(mfm_ctx *ctx) {
     throw Error(MFM_ERR_RUNTIME, "every random set is in use (one acquired, the others in flight): acquire the next one first");
   // (the gate only where the persistent sweep fills the device: a small table's launch leaves most CUs free, and there the
   //  generator should run beside it -- ML-100k shape: 2700 it/s gated, 3000 not)
-  const bool gated = ctx->res.ready && ctx->res_fills_device;
+  const bool gated = ctx->resident_V() && ctx->res_fills_device;
   rng_finish_pending(ctx, gated);
   auto &sl = r.slot[r.produced % mfm_ctx::RngEngine::N_SLOTS];
   hipStream_t s = r.stream;

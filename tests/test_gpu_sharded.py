@@ -571,10 +571,14 @@ def test_sharded_persistent_sweep_in_launch_exchange(oracle, world, model, monke
                 if model:
                     s.peer_set_model(world, rank, [peers[r][2] for r in range(world)], [peers[r][3] for r in range(world)])
                 flags = s.plan_flags()
+                assert not s.peer_info()[0]  # live: nothing waits for its peers any more
                 calls0 = ls.counts[rank]
                 for it in range(3):
                     s.step()
                 out[rank] = (s.fm.w0, np.asarray(s.fm.w), np.asarray(s.fm.V), s.residual(), lo, flags, ls.counts[rank] - calls0)
+                meet.wait()  # (no rank gives the sweep up while another is still inside its launch)
+                s.peer_drop()
+                assert not s.peer_info()[0] and not (s.plan_flags() & 256)  # given up: neither waiting nor live
             except BaseException as ex:  # noqa
                 errs.append(ex)
                 ls.bar.abort()
