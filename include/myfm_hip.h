@@ -469,6 +469,35 @@ int mfm_design_loo(mfm_design *d, int32_t rank, int32_t n_samples, const double 
  * tail_len in [0, S); out_lw[S] may be NULL                                                                                  */
 int mfm_psis_row(int32_t S, int32_t tail_len, const double *log_lik, double *out_elpd, double *out_k, double *out_lw);
 
+/* ---- chain diagnostics over the kept samples (csrc/mfm_ess.hpp) ------------------------------------------------
+ * Per design row t, the split R-hat, the effective sample sizes and the Monte Carlo error of a per-sample value over the S
+ * samples in their order, after Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021): the sequence is split into two halves
+ * of floor(S / 2) draws, E(x) is Geyer's estimate over the halves' biased autocovariances as Stan runs it, Z(x) the rank-normalised
+ * sequence (ties share the average rank).
+ *   kind 0: the prediction value v_s, mode_or_task 0 the score, 1 Phi(score), 2 the expected class index under cutpoints[S][n_cut];
+ *           y and precisions are NULL. out0 rhat = max(R of Z(v), R of Z(|v - median v|)), out1 ess_bulk = ess of Z(v), out2
+ *           ess_mean = ess of v, out3 mcse_mean = sd(v, ddof = 1) / sqrt(ess_mean).
+ *   kind 1: the likelihood u_s = exp(l_s - max_s l_s) with l_s, mode_or_task = task, y and the constants exactly as
+ *           mfm_design_logdens* takes and checks them. out0 rhat and out1 ess_bulk of u as above, out2 r_eff = ess of u / S, out3
+ *           mcse_lpd = sd(u, ddof = 1) / (mean(u) sqrt(ess of u)).
+ * All four are NaN for S < 8, for a row with a non-finite value (an l of -inf under every sample) and where the halves do not
+ * vary. Everything is fp64; the sums over samples run in sample order and those over lags in lag order: tile_rows /
+ * chunk_samples (0: automatic) do not change a bit of the results. MFM_ERR_INVALID, before the device is used: a bad kind or
+ * mode; for kind 1 what mfm_design_logdens* refuses; for kind 0 precisions given, cutpoints missing, non-finite or not ascending
+ * for mode 2 or given otherwise; a missing output; negative tiling overrides; more than 4096 samples. N = 0 returns at once.   */
+int mfm_design_ess_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t kind, int32_t mode_or_task,
+                         const double *y, const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
+                         int32_t chunk_samples, double *out0, double *out1, double *out2, double *out3);
+int mfm_design_ess(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                   int32_t kind, int32_t mode_or_task, const double *y, const double *precisions, int32_t n_cut,
+                   const double *cutpoints, int64_t tile_rows, int32_t chunk_samples, double *out0, double *out1, double *out2,
+                   double *out3);
+/* E(x) of one sequence on the host, by the scalar pieces the kernel runs and in its summation orders (no device): x[S],
+ * 1 <= S <= 4096; NaN for S < 8 and where the halves do not vary                                                              */
+int mfm_ess_row(int32_t S, const double *x, double *out_ess, double *out_rhat);
+/* out[j] = Phi^-1((1 + j / 2 - 3 / 8) / (S + 1 / 4)), j = 0 .. 2S - 2: the rank-normalised value of the average rank 1 + j / 2 */
+int mfm_rank_z_table(int32_t S, double *out);
+
 /* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
  * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), each optionally with relation blocks
  * (below); pair (u, i) is the design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column

@@ -22,6 +22,8 @@ _hip_runtime = _preload()
 from ._myfm import RelationBlock  # noqa: E402
 from .estimators import (  # noqa: E402
     FOLD_IN_MAX_RANK,
+    ChainDiagnostics,
+    LikelihoodDiagnostics,
     LooDensity,
     MyFMClassifier,
     MyFMGibbsClassifier,
@@ -54,6 +56,8 @@ __all__ = [
     "TargetRanks",
     "PointwiseDensity",
     "LooDensity",
+    "ChainDiagnostics",
+    "LikelihoodDiagnostics",
     "SampleRankings",
     "ThompsonRanking",
     "TopKProbability",

@@ -48,6 +48,7 @@ SYMBOLS = [
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
     "mfm_design_logdens_store", "mfm_design_logdens", "mfm_logdens_value",
     "mfm_design_loo_store", "mfm_design_loo", "mfm_psis_row",
+    "mfm_design_ess_store", "mfm_design_ess", "mfm_ess_row", "mfm_rank_z_table",
 ]
 
 PAIRS_VOTE_MAX = 32768  # (MFM_PAIRS_VOTE_MAX of myfm_hip.h: samples * k of a topk_prob call)
@@ -181,6 +182,10 @@ def lib():
     L.mfm_design_loo_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, i32, P, P, P, P, P]
     L.mfm_design_loo.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, i32, P, P, P, P, P]
     L.mfm_psis_row.argtypes = [i32, i32, P, P, P, P]
+    L.mfm_design_ess_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P, P]
+    L.mfm_design_ess.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, i32, P, i64, i32, P, P, P, P]
+    L.mfm_ess_row.argtypes = [i32, P, P, P]
+    L.mfm_rank_z_table.argtypes = [i32, P]
     L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
@@ -670,6 +675,24 @@ class Design:
         the tail of ceil(min(0.2 S, 3 sqrt(S / r_eff))) ratios smoothed (mfm_design_loo)."""
         return self._loo(_host(samples), task, y, precisions, cutpoints, log_weights, r_eff, tile_rows, chunk_samples)
 
+    def _ess(self, src, kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples):
+        if kind == 1:
+            y, prec, n_cut, cp = self._log_density_args(y, precisions, cutpoints)
+        else:  # (the value needs no targets; what it must not be given is the library's to refuse)
+            _, prec, n_cut, cp = self._log_density_args(np.zeros(self.N), precisions, cutpoints)
+            y = None
+        out = [np.empty(self.N) for _ in range(4)]
+        self._ck(src.call("mfm_design_ess", self.h, int(kind), int(mode_or_task), _p(y), _p(prec), n_cut, _p(cp), int(tile_rows),
+                          int(chunk_samples), *[_p(o) for o in out]))
+        return tuple(out)
+
+    def ess(self, samples, kind, mode_or_task, y=None, precisions=None, cutpoints=None, tile_rows=0, chunk_samples=0):
+        """samples as predict. Chain diagnostics per row over the samples in their order (mfm_design_ess). kind 0, the prediction
+        value of mode 0 score, 1 Phi(score), 2 the expected class index under cutpoints[S][n_cut]: (rhat[N], ess_bulk[N],
+        ess_mean[N], mcse_mean[N]). kind 1, the likelihood of y with task, precisions and cutpoints as log_density: (rhat[N],
+        ess_bulk[N], r_eff[N], mcse_lpd[N])."""
+        return self._ess(_host(samples), kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples)
+
     def predict(self, samples, mode=0, cutpoints=None):
         """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
         return self._predict(_host(samples), mode, cutpoints)
@@ -769,6 +792,29 @@ class Store:
             chunk_samples=0):
         """Design.loo over the resident samples [first, first + count) (mfm_design_loo_store)"""
         return design._loo(_resident(self, first, count), task, y, precisions, cutpoints, log_weights, r_eff, tile_rows, chunk_samples)
+
+    def ess(self, design, kind, mode_or_task, y=None, precisions=None, cutpoints=None, first=0, count=None, tile_rows=0, chunk_samples=0):
+        """Design.ess over the resident samples [first, first + count) (mfm_design_ess_store)"""
+        return design._ess(_resident(self, first, count), kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples)
+
+
+def ess_row(x):
+    """(ess, rhat) of one sequence of draws on the host, by the scalar pieces the device runs (mfm_ess_row)"""
+    x = _f64(x).reshape(-1)
+    ess, rhat = C.c_double(), C.c_double()
+    rc = lib().mfm_ess_row(x.shape[0], _p(x), C.byref(ess), C.byref(rhat))
+    if rc:
+        _raise(rc, lib().mfm_global_error())
+    return ess.value, rhat.value
+
+
+def rank_z_table(S):
+    """table[2S - 1] of the rank-normalised values by twice the average rank (mfm_rank_z_table)"""
+    out = np.empty(max(2 * int(S) - 1, 0))
+    rc = lib().mfm_rank_z_table(int(S), _p(out))
+    if rc:
+        _raise(rc, lib().mfm_global_error())
+    return out
 
 
 def psis_tail_len(S, r_eff=1.0):

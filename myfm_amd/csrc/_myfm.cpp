@@ -35,6 +35,7 @@
 #include "mfm_env.hpp"
 #include "mfm_hostnormals.hpp"
 #include "mfm_mtjump.hpp"
+#include "mfm_normal_quantile.hpp"
 #include "myfm_hip.h"
 
 namespace py = pybind11;
@@ -1058,20 +1059,6 @@ struct Predictor {
     return out;
   }
   // ---- posterior predictive summaries (not in the reference): mean, standard deviation and quantiles over the samples -------
-  // Phi^-1(p), 0 < p < 1, by bisection of 0.5 erfc(-z / sqrt 2) down to neighbouring doubles (it only places the root bracket
-  // of the device's mixture solve)
-  static double std_normal_quantile(double p) {
-    double lo = -40.0, hi = 40.0;
-    for (int it = 0; it < 200; it++) {
-      const double mid = 0.5 * (lo + hi);
-      if (!(mid > lo && mid < hi)) break;
-      if (0.5 * std::erfc(-mid * 0.70710678118654752440) < p)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    return 0.5 * (lo + hi);
-  }
   // The quantile arguments of predict_dist and predict_dist_oprobit: the probabilities, 1-D, at most 32, each in [0, 1] (`open`:
   // with noise, strictly inside, checked value by value together with the range) ...
   static vector<double> quantile_probs(const py::object &quantileso, bool open = false) {
@@ -1139,7 +1126,7 @@ struct Predictor {
     vector<double> prec, z;
     if (noise) {
       prec = noise_precisions(precisionso);
-      for (double p : probs) z.push_back(std_normal_quantile(p));
+      for (double p : probs) z.push_back(mfm_std_normal_quantile(p));  // (it only places the root bracket of the device's mixture solve)
     }
     const int n_q = (int)probs.size();
     check_summary_limits(probs.size(), tile_rows, chunk_samples);
@@ -1264,6 +1251,44 @@ struct Predictor {
     dd.ck(on_samples(mfm_design_loo_store, mfm_design_loo, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut, a.cutpoints(),
                      tile_rows, (int32_t)chunk_samples, tail_len, elpd.mutable_data(), khat.mutable_data(), lpd.mutable_data(), pit.p, lw.p));
     return py::make_tuple(elpd, khat, lpd, pit.array, lw.array);
+  }
+  // Chain diagnostics over the kept samples in their order (not in the reference). The limit both kinds share:
+  void check_ess_limits() const {
+    if (samples.size() > PSIS_MAX_SAMPLES)
+      throw std::invalid_argument("chain diagnostics are computed over at most " + std::to_string(PSIS_MAX_SAMPLES) +
+                                  " kept samples, this model keeps " + std::to_string(samples.size()));
+  }
+  // (rhat[N], ess_bulk[N], ess_mean[N], mcse_mean[N]) of the value predict_dist summarises: the score (regression), Phi(score)
+  // (classification), the expected class index under cutpoint group `cutpoint_idx` (ordered probit)
+  py::tuple predict_ess(const py::object &Xo, const py::object &relso, int64_t cutpoint_idx, int64_t tile_rows, int chunk_samples) const {
+    Csr X = csr_from_py(Xo);
+    Relations rels = relations_from_py(relso);
+    check_input(X, rels);
+    check_tiled_pass(tile_rows, chunk_samples);
+    check_ess_limits();
+    Cutpoints cp;
+    if (type == TaskType::ORDERED) cp = cutpoint_group(cutpoint_idx);
+    const py::ssize_t N = (py::ssize_t)X.rows;
+    py::array_t<double> rhat(N), bulk(N), mean(N), mcse(N);
+    DeviceDesign dd(X, rels);
+    dd.ck(on_samples(mfm_design_ess_store, mfm_design_ess, dd.d, 0, static_cast<int32_t>(type), nullptr, nullptr, (int32_t)cp.n_cut,
+                     cp.n_cut ? cp.cuts.data() : nullptr, tile_rows, (int32_t)chunk_samples, rhat.mutable_data(), bulk.mutable_data(),
+                     mean.mutable_data(), mcse.mutable_data()));
+    return py::make_tuple(rhat, bulk, mean, mcse);
+  }
+  // (rhat[N], ess_bulk[N], r_eff[N], mcse_lpd[N]) of the likelihood exp(l_s - max_s l_s) that predict_loo weights by; the
+  // arguments of density_args
+  py::tuple likelihood_ess(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
+                           const py::object &cutpointso, int64_t tile_rows, int chunk_samples) const {
+    const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
+    check_ess_limits();
+    const py::ssize_t N = (py::ssize_t)a.X.rows;
+    py::array_t<double> rhat(N), bulk(N), reff(N), mcse(N);
+    DeviceDesign dd(a.X, a.rels);
+    dd.ck(on_samples(mfm_design_ess_store, mfm_design_ess, dd.d, 1, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
+                     a.cutpoints(), tile_rows, (int32_t)chunk_samples, rhat.mutable_data(), bulk.mutable_data(), reff.mutable_data(),
+                     mcse.mutable_data()));
+    return py::make_tuple(rhat, bulk, reff, mcse);
   }
   // predictor.hpp:78-124
   py::array_t<double> predict_parallel_oprobit(const py::object &Xo, const py::object &relso, size_t n_workers,
@@ -3079,6 +3104,10 @@ PYBIND11_MODULE(_myfm, m) {
       .def("predict_loo", &Predictor::predict_loo, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
            py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("log_weights") = false, py::arg("r_eff") = 1.0,
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+      .def("predict_ess", &Predictor::predict_ess, py::arg("X"), py::arg("rels"), py::arg("cutpoint_index") = 0, py::arg("tile_rows") = 0,
+           py::arg("chunk_samples") = 0)
+      .def("likelihood_ess", &Predictor::likelihood_ess, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
+           py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def(py::pickle(
           [](const Predictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {
@@ -3340,6 +3369,29 @@ PYBIND11_MODULE(_myfm, m) {
         return py::make_tuple(elpd, k, lw);
       },
       py::arg("log_lik"), py::arg("r_eff") = 1.0);
+
+  // E of one sequence of draws on the host, by the scalar pieces k_row_ess runs on the device (csrc/mfm_ess.hpp): (ess, rhat)
+  m.def(
+      "ess_row",
+      [](const py::array_t<double, py::array::c_style | py::array::forcecast> &x) {
+        if (x.ndim() != 1 || x.shape(0) < 1) throw std::invalid_argument("x must be a non-empty 1-D array");
+        double ess = 0.0, rhat = 0.0;
+        const int code = mfm_ess_row((int32_t)std::min<py::ssize_t>(x.shape(0), PSIS_MAX_SAMPLES + 1), x.data(), &ess, &rhat);
+        if (code != MFM_OK) throw_code(code, mfm_global_error());
+        return py::make_tuple(ess, rhat);
+      },
+      py::arg("x"));
+  // the rank-normalised values of S draws by twice the average rank, table[2S - 1], as the device is handed them
+  m.def(
+      "rank_z_table",
+      [](int64_t S) {
+        if (S < 1 || S > PSIS_MAX_SAMPLES) throw std::invalid_argument("1 to " + std::to_string(PSIS_MAX_SAMPLES) + " draws are needed");
+        py::array_t<double> out((py::ssize_t)(2 * S - 1));
+        const int code = mfm_rank_z_table((int32_t)S, out.mutable_data());
+        if (code != MFM_OK) throw_code(code, mfm_global_error());
+        return out;
+      },
+      py::arg("S"));
 
   // extensions beyond the reference's surface (bench / tests)
   py::class_<GibbsSession>(m, "GibbsSession")

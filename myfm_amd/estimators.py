@@ -437,9 +437,10 @@ PREDICT_LOO_MAX_SAMPLES = PREDICT_DIST_MAX_SAMPLES  # a row's importance ratios 
 
 class _LooMixin(_LogDensityMixin):
     """Pareto-smoothed importance-sampling leave-one-out of a fitted Gibbs regressor, classifier or ordered probit (DESIGN
-    4.9.3), after Vehtari, Gelman and Gabry (2017) and Vehtari et al. (2024). Limits: one relative efficiency r_eff for all rows
-    (none per row, none estimated from the chain); no moment matching or refit for rows with a large k; at most 4096 kept samples;
-    no variational estimator; not row-sharded (the model is replicated: each rank may call it on its own rows)."""
+    4.9.3), after Vehtari, Gelman and Gabry (2017) and Vehtari et al. (2024). Limits: one tail length for all rows (r_eff is one
+    number, given or with "auto" the mean of the rows' estimates from the chain: no per-row tail length); no moment matching or
+    refit for rows with a large k; at most 4096 kept samples; no variational estimator; not row-sharded (the model is replicated:
+    each rank may call it on its own rows)."""
 
     def predict_loo(self, X, y, X_rel=[], log_weights=False, r_eff=1.0):
         """LooDensity(elpd_loo, pareto_k, lpd, loo_pit, log_weights) per row over the S kept samples, computed on the device in one
@@ -456,23 +457,91 @@ class _LooMixin(_LogDensityMixin):
         None): sum_s w_s Phi((y - score_s) sqrt(alpha_s)); pit_histogram(result.loo_pit) takes it. log_weights (S, N), only with
         log_weights=True (else None and nothing of that size exists on the host): log w_s.
 
-        r_eff: the relative efficiency of the draws, one finite positive number (1: independent draws), used for M alone. At most
-        4096 kept samples. X, y, X_rel (MyFMOrderedProbit: cutpoint_index) as predict_log_density takes and checks them; all
+        r_eff: the relative efficiency of the draws, one finite positive number (1: independent draws), used for M alone; or "auto":
+        the mean of the finite per-row r_eff of likelihood_diagnostics on the same rows (1 if none is finite), one more pass over
+        the rows. At most 4096 kept samples. X, y, X_rel (MyFMOrderedProbit: cutpoint_index) as predict_log_density takes and checks them; all
         arguments are checked on the host before the device is touched."""
         return self._predict_loo(X, y, X_rel, log_weights, r_eff, None)
 
     def _predict_loo(self, X, y, X_rel, log_weights, r_eff, cutpoint_index):
         if not isinstance(log_weights, (bool, np.bool_)):
             raise ValueError("log_weights must be a bool")
-        if isinstance(r_eff, (bool, np.bool_)) or not isinstance(r_eff, (int, float, np.integer, np.floating)) \
-                or not np.isfinite(r_eff) or not r_eff > 0:
-            raise ValueError("r_eff must be one finite positive number")
+        auto = isinstance(r_eff, str) and r_eff == "auto"
+        if not auto and (isinstance(r_eff, (bool, np.bool_)) or not isinstance(r_eff, (int, float, np.integer, np.floating))
+                         or not np.isfinite(r_eff) or not r_eff > 0):
+            raise ValueError("r_eff must be one finite positive number, or \"auto\"")
         predictor, args = self._log_density_args(X, y, X_rel, cutpoint_index, "predict_loo")
         n_samples = len(predictor.samples)
         if n_samples > PREDICT_LOO_MAX_SAMPLES:
             raise ValueError("leave-one-out weights are computed over at most %d kept samples, this model keeps %d"
                              % (PREDICT_LOO_MAX_SAMPLES, n_samples))
+        if auto:  # the chain's own estimate, one number for all rows (as arviz hands PSIS one)
+            per_row = np.asarray(predictor.likelihood_ess(*args)[2])
+            r_eff = float(np.nanmean(per_row)) if np.any(np.isfinite(per_row)) else 1.0  # (a row is finite or NaN)
         return LooDensity(*predictor.predict_loo(*args, bool(log_weights), float(r_eff)))
+
+
+ChainDiagnostics = namedtuple("ChainDiagnostics", ["rhat", "ess_bulk", "ess_mean", "mcse_mean"])
+LikelihoodDiagnostics = namedtuple("LikelihoodDiagnostics", ["r_eff", "rhat", "ess_bulk", "mcse_lpd"])
+
+
+class _DiagnosticsMixin(_LogDensityMixin):
+    """Have the kept samples mixed, and how many independent draws are they worth: per-row split R-hat, effective sample sizes and
+    Monte Carlo errors of a fitted Gibbs regressor, classifier or ordered probit over the S kept samples in their order (DESIGN
+    4.9.4), after Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021). The factors themselves are not identified (sign and
+    rotation), so what is diagnosed are the identified per-row quantities every other summary is a Monte Carlo estimate of. One fit
+    is one chain: the two halves of the kept samples stand in for two chains. Limits: no tail-ESS; at most 4096 kept samples; no
+    variational estimator (one sample); not row-sharded (the model is replicated: each rank may call it on its own rows)."""
+
+    def predict_diagnostics(self, X, X_rel=[]):
+        """ChainDiagnostics(rhat, ess_bulk, ess_mean, mcse_mean) per row, computed on the device in one pass over the rows, of the
+        per-sample value v_s that predict_dist summarises: the score for a regressor, Phi(score) for a classifier (for
+        MyFMOrderedProbit the expected class index under cutpoint group `cutpoint_index`).
+
+        rhat (N,): the larger of the split R-hat of the rank-normalised values and of the rank-normalised |v - median v|; above
+        1.01 the halves of the chain disagree. ess_bulk (N,): the effective sample size of the rank-normalised values, behind the
+        quantiles. ess_mean (N,): that of the values themselves, behind the mean; mcse_mean (N,) = sd(v, ddof = 1) / sqrt(ess_mean)
+        is the Monte Carlo standard error of predict_dist's mean. All are NaN with fewer than 8 kept samples and for a row whose
+        value does not vary; ess <= S log10(S). See myfm_amd.utils.evaluation.diagnostics_summary.
+
+        The arguments are checked on the host before the device is touched."""
+        return self._predict_diagnostics(X, X_rel, 0)
+
+    def _predict_diagnostics(self, X, X_rel, cutpoint_index):
+        predictor = self._fetch_predictor()
+        n = check_data_consistency(X, X_rel)
+        X = _as_csr(X, n)
+        if isinstance(cutpoint_index, bool) or not isinstance(cutpoint_index, (int, np.integer)):
+            raise ValueError("cutpoint_index must be an integer")
+        self._check_diagnostics_limit(predictor)
+        return ChainDiagnostics(*predictor.predict_ess(X, list(X_rel), int(cutpoint_index)))
+
+    def likelihood_diagnostics(self, X, y, X_rel=[]):
+        """LikelihoodDiagnostics(r_eff, rhat, ess_bulk, mcse_lpd) per row, computed on the device in one pass over the rows, of the
+        per-sample likelihood u_s = p(y | sample s) (scaled by its maximum: nothing underflows) that predict_log_density averages
+        and predict_loo weights by.
+
+        r_eff (N,): the relative efficiency ess(u) / S, the loo package's relative_eff(exp(log_lik)); predict_loo(r_eff="auto")
+        takes the mean of the finite ones. rhat, ess_bulk (N,): as predict_diagnostics, of u. mcse_lpd (N,) = sd(u, ddof = 1) /
+        (mean(u) sqrt(ess(u))): the delta-method Monte Carlo standard error of lpd. NaN with fewer than 8 kept samples, for a row
+        whose likelihood does not vary, and where y has density 0 under every sample.
+
+        X, y, X_rel (MyFMOrderedProbit: cutpoint_index) as predict_log_density takes and checks them, on the host before the
+        device is touched."""
+        return self._likelihood_diagnostics(X, y, X_rel, None)
+
+    def _likelihood_diagnostics(self, X, y, X_rel, cutpoint_index):
+        predictor, args = self._log_density_args(X, y, X_rel, cutpoint_index, "likelihood_diagnostics")
+        self._check_diagnostics_limit(predictor)
+        rhat, ess_bulk, r_eff, mcse = predictor.likelihood_ess(*args)
+        return LikelihoodDiagnostics(r_eff, rhat, ess_bulk, mcse)
+
+    @staticmethod
+    def _check_diagnostics_limit(predictor):
+        n_samples = len(predictor.samples)
+        if n_samples > PREDICT_LOO_MAX_SAMPLES:
+            raise ValueError("chain diagnostics are computed over at most %d kept samples, this model keeps %d"
+                             % (PREDICT_LOO_MAX_SAMPLES, n_samples))
 
 
 def _ranked_args(Xq, Xc, k, exclude, beta=0.0):
@@ -840,7 +909,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -908,7 +977,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDi
         return _folded_in(self, predictor.extended(w_new, V_new), D, U)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -984,7 +1053,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _DiagnosticsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""
@@ -1087,6 +1156,15 @@ class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _Fo
     def predict_loo(self, X, y, X_rel=[], log_weights=False, r_eff=1.0, cutpoint_index=0):
         """_LooMixin.predict_loo with the cutpoint group to use, as predict_log_density takes it."""
         return self._predict_loo(X, y, X_rel, log_weights, r_eff, cutpoint_index)
+
+    def predict_diagnostics(self, X, X_rel=[], cutpoint_index=0):
+        """_DiagnosticsMixin.predict_diagnostics of the expected class index sum_c c p_c under the cutpoints of group
+        `cutpoint_index`, the value predict_expected_dist summarises and predict_topk ranks by."""
+        return self._predict_diagnostics(X, X_rel, cutpoint_index)
+
+    def likelihood_diagnostics(self, X, y, X_rel=[], cutpoint_index=0):
+        """_DiagnosticsMixin.likelihood_diagnostics with the cutpoint group to use, as predict_log_density takes it."""
+        return self._likelihood_diagnostics(X, y, X_rel, cutpoint_index)
 
     @property
     def cutpoint_samples(self):

@@ -1,5 +1,5 @@
 """Model evaluation from the pointwise log predictive density (predict_log_density) and from Pareto-smoothed
-leave-one-out (predict_loo). Pure NumPy."""
+leave-one-out (predict_loo), and a digest of the chain diagnostics. Pure NumPy."""
 import numpy as np
 
 WAIC_HIGH_VARIANCE = 0.4  # a row whose log-likelihood variance exceeds this makes WAIC unreliable (Vehtari, Gelman, Gabry 2017)
@@ -94,3 +94,33 @@ def compare(a, b):
     d = ea - eb
     n = d.shape[0]
     return {"elpd_diff": float(d.sum()), "se_diff": float(np.sqrt(n * np.var(d))) if n else float("nan")}
+
+
+def diagnostics_summary(result, rhat_max=1.01, ess_min=100):
+    """What a ChainDiagnostics or LikelihoodDiagnostics `result` (predict_diagnostics, likelihood_diagnostics) says
+    about the rows as a whole, with the thresholds of Vehtari et al. (2021). Returns a dict:
+
+        rhat_max      the largest rhat over the rows (NaN rows left out; NaN where there is no other)
+        n_high_rhat   the number of rows with rhat > `rhat_max`
+        ess_min       the smallest ess_bulk over the rows
+        ess_median    the median ess_bulk over the rows
+        n_low_ess     the number of rows with ess_bulk < `ess_min`
+        n_nan         the number of rows without a diagnosis (fewer than 8 kept samples, a constant or non-finite value)
+
+    A LikelihoodDiagnostics adds r_eff_min and r_eff_median, the smallest and the median relative efficiency."""
+    rhat = np.asarray(result.rhat, dtype=np.float64)
+    ess = np.asarray(result.ess_bulk, dtype=np.float64)
+    if rhat.ndim != 1 or rhat.shape != ess.shape:
+        raise ValueError("rhat and ess_bulk must be 1-D arrays of one length")
+    nan = float("nan")
+    missing = np.isnan(rhat) | np.isnan(ess)
+    r, e = rhat[~missing], ess[~missing]
+    out = {"rhat_max": float(r.max()) if r.size else nan, "n_high_rhat": int(np.count_nonzero(r > rhat_max)),
+           "ess_min": float(e.min()) if e.size else nan, "ess_median": float(np.median(e)) if e.size else nan,
+           "n_low_ess": int(np.count_nonzero(e < ess_min)), "n_nan": int(np.count_nonzero(missing))}
+    if hasattr(result, "r_eff"):
+        f = np.asarray(result.r_eff, dtype=np.float64)
+        f = f[np.isfinite(f)]
+        out["r_eff_min"] = float(f.min()) if f.size else nan
+        out["r_eff_median"] = float(np.median(f)) if f.size else nan
+    return out
