@@ -498,6 +498,34 @@ int mfm_ess_row(int32_t S, const double *x, double *out_ess, double *out_rhat);
 /* out[j] = Phi^-1((1 + j / 2 - 3 / 8) / (S + 1 / 4)), j = 0 .. 2S - 2: the rank-normalised value of the average rank 1 + j / 2 */
 int mfm_rank_z_table(int32_t S, double *out);
 
+/* ---- continuous ranked probability score over the kept samples (csrc/mfm_crps.hpp) ----------------------------
+ * Per design row t with observed target y[t], over the samples of mfm_design_summary*, the energy form
+ * CRPS = E|Y - y| - E|Y - Y'| / 2 of the posterior predictive distribution of y (Y, Y' independent draws of it):
+ *   task 0 (regression)      Y ~ (1 / S) sum_s N(score_s, 1 / precisions[s]); with A(m, v) = m erf(m h) + g exp(-(m h)^2),
+ *                            h = 1 / sqrt(2 v), g = sqrt(2 v / pi):  accuracy = (1 / S) sum_s A(y - score_s, v_s),
+ *                            spread = (1 / S^2) sum_s [sum_{t < s} A(score_s - score_t, v_s + v_t) + g(2 v_s) / 2]
+ *   task 1 (probit), task 2 (ordered probit)   Y the class index 0 .. n_cut (task 1: one cutpoint 0, y in {0, 1}); per cut j
+ *                            d_j = mean_s Phi(cut_sj - score_s) if y > j, else mean_s Phi(score_s - cut_sj):
+ *                            accuracy = sum_j d_j, spread = sum_j d_j (1 - d_j), crps = sum_j d_j^2 (Brier / ranked probability score)
+ *   out_crps[N]      accuracy - spread (task 0), sum_j d_j^2 (tasks 1, 2); >= 0
+ *   out_accuracy[N]  E|Y - y|;   out_spread[N]  E|Y - Y'| / 2
+ * Everything is fp64; the sums over t < s run in sample order into one sum per s, those in s order, the sums over samples of
+ * tasks 1 and 2 in sample order and over cuts in cut order: tile_rows / chunk_samples (0: automatic) do not change a bit of the
+ * results. MFM_ERR_INVALID, before the device is used: what mfm_design_logdens* refuses (the three outputs in the place of its
+ * three), and for task 0 more than 1024 samples (S (S + 1) / 2 pair terms per row). Tasks 1 and 2 have no sample limit. N = 0
+ * returns at once. The upload rule of the host flavour is that of mfm_design_summary.                                        */
+int mfm_design_crps_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t task, const double *y,
+                          const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
+                          int32_t chunk_samples, double *out_crps, double *out_accuracy, double *out_spread);
+int mfm_design_crps(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                    int32_t task, const double *y, const double *precisions, int32_t n_cut, const double *cutpoints,
+                    int64_t tile_rows, int32_t chunk_samples, double *out_crps, double *out_accuracy, double *out_spread);
+/* one row on the host, by the functions the kernels run and in their summation orders (no device): scores[S], S >= 1 (task 0:
+ * S <= 1024), precisions[S] (task 0, else NULL), cutpoints[S * n_cut] (task 2, else NULL and n_cut 0);
+ * out[3] = (crps, accuracy, spread)                                                                                          */
+int mfm_crps_row(int32_t task, int32_t S, double y, const double *scores, const double *precisions, int32_t n_cut,
+                 const double *cutpoints, double *out);
+
 /* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
  * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), each optionally with relation blocks
  * (below); pair (u, i) is the design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column

@@ -23,6 +23,7 @@ from ._myfm import RelationBlock  # noqa: E402
 from .estimators import (  # noqa: E402
     FOLD_IN_MAX_RANK,
     ChainDiagnostics,
+    CrpsScore,
     LikelihoodDiagnostics,
     LooDensity,
     MyFMClassifier,
@@ -58,6 +59,7 @@ __all__ = [
     "LooDensity",
     "ChainDiagnostics",
     "LikelihoodDiagnostics",
+    "CrpsScore",
     "SampleRankings",
     "ThompsonRanking",
     "TopKProbability",

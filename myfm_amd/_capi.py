@@ -49,6 +49,7 @@ SYMBOLS = [
     "mfm_design_logdens_store", "mfm_design_logdens", "mfm_logdens_value",
     "mfm_design_loo_store", "mfm_design_loo", "mfm_psis_row",
     "mfm_design_ess_store", "mfm_design_ess", "mfm_ess_row", "mfm_rank_z_table",
+    "mfm_design_crps_store", "mfm_design_crps", "mfm_crps_row",
 ]
 
 PAIRS_VOTE_MAX = 32768  # (MFM_PAIRS_VOTE_MAX of myfm_hip.h: samples * k of a topk_prob call)
@@ -186,6 +187,9 @@ def lib():
     L.mfm_design_ess.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, i32, P, i64, i32, P, P, P, P]
     L.mfm_ess_row.argtypes = [i32, P, P, P]
     L.mfm_rank_z_table.argtypes = [i32, P]
+    L.mfm_design_crps_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P]
+    L.mfm_design_crps.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, P, P, P]
+    L.mfm_crps_row.argtypes = [i32, i32, dbl, P, P, i32, P, P]
     L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
@@ -693,6 +697,19 @@ class Design:
         ess_bulk[N], r_eff[N], mcse_lpd[N])."""
         return self._ess(_host(samples), kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples)
 
+    def _crps(self, src, task, y, precisions, cutpoints, tile_rows, chunk_samples):
+        y, prec, n_cut, cp = self._log_density_args(y, precisions, cutpoints)
+        crps, accuracy, spread = np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        self._ck(src.call("mfm_design_crps", self.h, int(task), _p(y), _p(prec), n_cut, _p(cp), int(tile_rows), int(chunk_samples),
+                          _p(crps), _p(accuracy), _p(spread)))
+        return crps, accuracy, spread
+
+    def crps(self, samples, task, y, precisions=None, cutpoints=None, tile_rows=0, chunk_samples=0):
+        """samples, task, y, precisions and cutpoints as log_density (task 0: at most 1024 samples). Returns (crps[N], accuracy[N],
+        spread[N]): the continuous ranked probability score E|Y - y| - E|Y - Y'| / 2 of the predictive distribution of y over the
+        samples and its two terms; the Brier score for task 1, the ranked probability score for task 2 (mfm_design_crps)."""
+        return self._crps(_host(samples), task, y, precisions, cutpoints, tile_rows, chunk_samples)
+
     def predict(self, samples, mode=0, cutpoints=None):
         """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
         return self._predict(_host(samples), mode, cutpoints)
@@ -796,6 +813,30 @@ class Store:
     def ess(self, design, kind, mode_or_task, y=None, precisions=None, cutpoints=None, first=0, count=None, tile_rows=0, chunk_samples=0):
         """Design.ess over the resident samples [first, first + count) (mfm_design_ess_store)"""
         return design._ess(_resident(self, first, count), kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples)
+
+    def crps(self, design, task, y, precisions=None, cutpoints=None, first=0, count=None, tile_rows=0, chunk_samples=0):
+        """Design.crps over the resident samples [first, first + count) (mfm_design_crps_store)"""
+        return design._crps(_resident(self, first, count), task, y, precisions, cutpoints, tile_rows, chunk_samples)
+
+
+def crps_row(task, y, scores, precisions=None, cutpoints=None):
+    """(crps, accuracy, spread) of one row on the host, by the functions the device runs and in its summation orders: scores[S],
+    precisions[S] (task 0), cutpoints[S, n_cut] (task 2) (mfm_crps_row)"""
+    scores = _f64(scores).reshape(-1)
+    prec = None if precisions is None else _f64(precisions).reshape(-1)
+    cp, n_cut = None, 0
+    if cutpoints is not None:
+        cp = _f64(cutpoints)
+        if cp.ndim != 2:
+            raise ValueError("cutpoints must be a 2-D array, one row of n_cut cutpoints per sample")
+        n_cut = cp.shape[1]
+    if (prec is not None and prec.shape[0] != scores.shape[0]) or (cp is not None and cp.shape[0] != scores.shape[0]):
+        raise ValueError("precisions and cutpoints hold one entry per score")
+    out = np.empty(3)
+    rc = lib().mfm_crps_row(int(task), scores.shape[0], float(y), _p(scores), _p(prec), n_cut, _p(cp), _p(out))
+    if rc:
+        _raise(rc, lib().mfm_global_error())
+    return tuple(out)
 
 
 def ess_row(x):

@@ -591,6 +591,7 @@ struct LearningHistory {
 // ---- Predictor (predictor.hpp:14-167) ---------------------------------------------------------------
 // the number of importance ratios PSIS smooths: ceil(min(0.2 S, 3 sqrt(S / r_eff))), r_eff one finite positive number
 constexpr int PSIS_MAX_SAMPLES = 4096;  // (DIST_MAX_S of the library: a row's ratios are sorted in the device's local memory)
+constexpr int CRPS_MAX_SAMPLES = 1024;  // (CRPS_MAX_S of the library: a regression row costs S (S + 1) / 2 pair terms)
 static int32_t psis_tail_len(size_t S, double r_eff) {
   if (!(r_eff > 0.0) || !std::isfinite(r_eff)) throw std::invalid_argument("r_eff must be one finite positive number");
   const int32_t M = (int32_t)std::ceil(std::min(0.2 * (double)S, 3.0 * std::sqrt((double)S / r_eff)));
@@ -1251,6 +1252,21 @@ struct Predictor {
     dd.ck(on_samples(mfm_design_loo_store, mfm_design_loo, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut, a.cutpoints(),
                      tile_rows, (int32_t)chunk_samples, tail_len, elpd.mutable_data(), khat.mutable_data(), lpd.mutable_data(), pit.p, lw.p));
     return py::make_tuple(elpd, khat, lpd, pit.array, lw.array);
+  }
+  // Continuous ranked probability score (not in the reference): (crps[N], accuracy[N], spread[N]) of the observed y
+  // under the predictive distribution of the kept samples; the arguments of density_args. Regression: at most CRPS_MAX_SAMPLES.
+  py::tuple predict_crps(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
+                         const py::object &cutpointso, int64_t tile_rows, int chunk_samples) const {
+    const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
+    const py::ssize_t N = (py::ssize_t)a.X.rows;
+    if (type == TaskType::REGRESSION && samples.size() > (size_t)CRPS_MAX_SAMPLES)
+      throw std::invalid_argument("a regression CRPS is computed over at most " + std::to_string(CRPS_MAX_SAMPLES) +
+                                  " kept samples, this model keeps " + std::to_string(samples.size()));
+    py::array_t<double> crps(N), accuracy(N), spread(N);
+    DeviceDesign dd(a.X, a.rels);
+    dd.ck(on_samples(mfm_design_crps_store, mfm_design_crps, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
+                     a.cutpoints(), tile_rows, (int32_t)chunk_samples, crps.mutable_data(), accuracy.mutable_data(), spread.mutable_data()));
+    return py::make_tuple(crps, accuracy, spread);
   }
   // Chain diagnostics over the kept samples in their order (not in the reference). The limit both kinds share:
   void check_ess_limits() const {
@@ -3104,6 +3120,8 @@ PYBIND11_MODULE(_myfm, m) {
       .def("predict_loo", &Predictor::predict_loo, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
            py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("log_weights") = false, py::arg("r_eff") = 1.0,
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+      .def("predict_crps", &Predictor::predict_crps, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
+           py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def("predict_ess", &Predictor::predict_ess, py::arg("X"), py::arg("rels"), py::arg("cutpoint_index") = 0, py::arg("tile_rows") = 0,
            py::arg("chunk_samples") = 0)
       .def("likelihood_ess", &Predictor::likelihood_ess, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
@@ -3381,6 +3399,30 @@ PYBIND11_MODULE(_myfm, m) {
         return py::make_tuple(ess, rhat);
       },
       py::arg("x"));
+  // the CRPS of one row on the host, by the functions k_row_crps_mix / k_row_crps_cdf run on the device and in their summation
+  // orders (csrc/mfm_crps.hpp): (crps, accuracy, spread)
+  m.def(
+      "crps_row",
+      [](int task, double y, const py::array_t<double, py::array::c_style | py::array::forcecast> &scores, const py::object &precisions,
+         const py::object &cutpoints) {
+        if (scores.ndim() != 1 || scores.shape(0) < 1) throw std::invalid_argument("scores must be a non-empty 1-D array");
+        const py::ssize_t S = scores.shape(0);
+        vector<double> prec;
+        if (!precisions.is_none()) prec = precisions.cast<vector<double>>();
+        py::array_t<double, py::array::c_style | py::array::forcecast> cut;
+        if (!cutpoints.is_none()) {
+          cut = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(cutpoints);
+          if (!cut || cut.ndim() != 2) throw std::invalid_argument("cutpoints must be a 2-D array, one row of n_cut cutpoints per sample");
+        }
+        if ((!precisions.is_none() && (py::ssize_t)prec.size() != S) || (!cutpoints.is_none() && cut.shape(0) != S))
+          throw std::invalid_argument("precisions and cutpoints hold one entry per score");
+        double out[3] = {0.0, 0.0, 0.0};
+        const int code = mfm_crps_row(task, (int32_t)S, y, scores.data(), precisions.is_none() ? nullptr : prec.data(),
+                                      cutpoints.is_none() ? 0 : (int32_t)cut.shape(1), cutpoints.is_none() ? nullptr : cut.data(), out);
+        if (code != MFM_OK) throw_code(code, mfm_global_error());
+        return py::make_tuple(out[0], out[1], out[2]);
+      },
+      py::arg("task"), py::arg("y"), py::arg("scores"), py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none());
   // the rank-normalised values of S draws by twice the average rank, table[2S - 1], as the device is handed them
   m.def(
       "rank_z_table",

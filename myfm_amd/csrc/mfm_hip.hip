@@ -2761,3 +2761,4 @@ int mfm_host_column_levels(int64_t n_rows, int64_t n_cols, const int64_t *indptr
 #include "mfm_logdens.hpp"  // ... and the pointwise log predictive density
 #include "mfm_psis.hpp"     // ... and Pareto-smoothed leave-one-out on top of it
 #include "mfm_ess.hpp"      // ... and the chain diagnostics of the values both are computed from
+#include "mfm_crps.hpp"     // ... and the continuous ranked probability score (after mfm_logdens.hpp: its checks and uploads)

@@ -481,6 +481,43 @@ class _LooMixin(_LogDensityMixin):
         return LooDensity(*predictor.predict_loo(*args, bool(log_weights), float(r_eff)))
 
 
+CrpsScore = namedtuple("CrpsScore", ["crps", "accuracy", "spread"])
+PREDICT_CRPS_MAX_SAMPLES = 1024  # regressor: a row costs S (S + 1) / 2 pair terms, the pair constants S (S + 1) doubles
+
+
+class _CrpsMixin(_LogDensityMixin):
+    """The continuous ranked probability score of a fitted Gibbs regressor, classifier or ordered probit: the
+    proper scoring rule in the units of y, which reduces to the absolute error for a point forecast and which no single row
+    dominates as it can the log score. Limits: a regressor with at most 1024 kept samples; no leave-one-out weighted CRPS; no
+    variational estimator; one cutpoint group per call; not row-sharded (the model is replicated: each rank may call it on its
+    own rows)."""
+
+    def predict_crps(self, X, y, X_rel=[]):
+        """CrpsScore(crps, accuracy, spread) per test row over the S kept samples, computed on the device in one pass over the
+        rows: CRPS = E|Y - y| - E|Y - Y'| / 2 with Y, Y' independent draws of the posterior predictive distribution of y.
+
+        Regressor: that distribution is the mixture mean_s N(score_s, 1 / alpha_s) of predict_dist(noise=True) (the noise
+        precisions are the last S entries of history_.hypers), and both expectations have a closed form in erf and exp (Grimit
+        et al. 2006) with S (S + 1) / 2 pair terms per row; at most 1024 kept samples. Classifier and ordered probit: Y is the
+        class index, crps = sum_j (P(Y <= j) - 1[y <= j])^2 with P the posterior mean class probabilities: the Brier score of
+        predict_proba for a classifier, the ranked probability score for ordered probit.
+
+        accuracy (N,): E|Y - y|. spread (N,): E|Y - Y'| / 2. crps (N,): their difference, >= 0, smaller is better; for the
+        discrete tasks summed directly and not as the difference. See myfm_amd.utils.evaluation.crps_summary.
+
+        X, y, X_rel (MyFMOrderedProbit: cutpoint_index) as predict_log_density takes and checks them; all arguments are checked
+        on the host before the device is touched."""
+        return self._predict_crps(X, y, X_rel, None)
+
+    def _predict_crps(self, X, y, X_rel, cutpoint_index):
+        predictor, args = self._log_density_args(X, y, X_rel, cutpoint_index, "predict_crps")
+        n_samples = len(predictor.samples)
+        if self._task_type == TaskType.REGRESSION and n_samples > PREDICT_CRPS_MAX_SAMPLES:
+            raise ValueError("a regression CRPS is computed over at most %d kept samples, this model keeps %d"
+                             % (PREDICT_CRPS_MAX_SAMPLES, n_samples))
+        return CrpsScore(*predictor.predict_crps(*args))
+
+
 ChainDiagnostics = namedtuple("ChainDiagnostics", ["rhat", "ess_bulk", "ess_mean", "mcse_mean"])
 LikelihoodDiagnostics = namedtuple("LikelihoodDiagnostics", ["r_eff", "rhat", "ess_bulk", "mcse_lpd"])
 
@@ -909,7 +946,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -977,7 +1014,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDi
         return _folded_in(self, predictor.extended(w_new, V_new), D, U)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -1053,7 +1090,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _DiagnosticsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""
@@ -1156,6 +1193,10 @@ class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _Di
     def predict_loo(self, X, y, X_rel=[], log_weights=False, r_eff=1.0, cutpoint_index=0):
         """_LooMixin.predict_loo with the cutpoint group to use, as predict_log_density takes it."""
         return self._predict_loo(X, y, X_rel, log_weights, r_eff, cutpoint_index)
+
+    def predict_crps(self, X, y, X_rel=[], cutpoint_index=0):
+        """_CrpsMixin.predict_crps with the cutpoint group to use, as predict_log_density takes it: the ranked probability score."""
+        return self._predict_crps(X, y, X_rel, cutpoint_index)
 
     def predict_diagnostics(self, X, X_rel=[], cutpoint_index=0):
         """_DiagnosticsMixin.predict_diagnostics of the expected class index sum_c c p_c under the cutpoints of group

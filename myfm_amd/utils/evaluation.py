@@ -1,5 +1,6 @@
 """Model evaluation from the pointwise log predictive density (predict_log_density) and from Pareto-smoothed
-leave-one-out (predict_loo), and a digest of the chain diagnostics. Pure NumPy."""
+leave-one-out (predict_loo), a digest of the chain diagnostics and of the continuous ranked
+probability score (predict_crps). Pure NumPy."""
 import numpy as np
 
 WAIC_HIGH_VARIANCE = 0.4  # a row whose log-likelihood variance exceeds this makes WAIC unreliable (Vehtari, Gelman, Gabry 2017)
@@ -123,4 +124,36 @@ def diagnostics_summary(result, rhat_max=1.01, ess_min=100):
         f = f[np.isfinite(f)]
         out["r_eff_min"] = float(f.min()) if f.size else nan
         out["r_eff_median"] = float(np.median(f)) if f.size else nan
+    return out
+
+
+def crps_summary(result, reference=None):
+    """What a CrpsScore `result` (predict_crps) says about the rows as a whole. Returns a dict:
+
+        crps       the mean crps over the rows, in the units of y (smaller is better)
+        se         its standard error sqrt(var_t(crps_t) / N) (population variance over the rows)
+        accuracy   the mean of E|Y - y|
+        spread     the mean of E|Y - Y'| / 2
+
+    With `reference`, a CrpsScore of another model on the same rows (or the pointwise crps array itself), it adds skill =
+    1 - crps / crps of the reference (positive where `result` predicts better), and se_diff, the paired standard error
+    sqrt(var_t(crps_t - ref_t) / N) of the mean difference."""
+    c = np.asarray(getattr(result, "crps", result), dtype=np.float64)
+    if c.ndim != 1:
+        raise ValueError("crps must hold one value per row")
+    n = c.shape[0]
+    nan = float("nan")
+
+    def mean_of(name):
+        v = getattr(result, name, None)
+        return float(np.mean(np.asarray(v, dtype=np.float64))) if v is not None and n else nan
+
+    out = {"crps": float(c.mean()) if n else nan, "se": float(np.sqrt(np.var(c) / n)) if n else nan,
+           "accuracy": mean_of("accuracy"), "spread": mean_of("spread")}
+    if reference is not None:
+        r = np.asarray(getattr(reference, "crps", reference), dtype=np.float64)
+        if r.ndim != 1 or r.shape != c.shape:
+            raise ValueError("the two results must hold one value per row of the same rows")
+        out["skill"] = 1.0 - float(c.mean()) / float(r.mean()) if n else nan
+        out["se_diff"] = float(np.sqrt(np.var(c - r) / n)) if n else nan
     return out
