@@ -1722,7 +1722,7 @@ int mfm_plan_info(const mfm_ctx *ctx, int64_t *n_levels_main, int64_t *n_launche
 int mfm_plan_flags(const mfm_ctx *ctx) {
   bool streamed = false;  // a relation block's feature chain runs as the streamed one-launch form (mfm_chain_stream.hpp)
   for (auto &B : ctx->blocks)
-    for (const Step &st : B->plan_V.steps) streamed = streamed || (st.is_chain && st.chain.stream);
+    for (const Step &st : B->plan_V.steps) streamed = streamed || (st.is_chain && st.chain.form == ChainForm::Stream);
   int form = 0;  // bits 0 and 4-7 (include/myfm_hip.h): what each form of update_V has always reported
   switch (ctx->v_path) {
     case VPath::QFree: form = 1; break;

@@ -1481,7 +1481,7 @@ struct ChainBatch {
 constexpr int CHAINB_NT = 512;
 constexpr int CHAINB_MAXCOLS = 64;
 
-// One column of a hot walk (k_chain_batched phase B, k_cb_hot), by ONE wavefront over records staged in LDS: statistics of
+// One column of a hot walk (k_chain_batched phase B, k_cb_persist's hot walker), by ONE wavefront over records staged in LDS: statistics of
 // the column's hot entries [hb, he), draw, update. Up to 4 x 64 entries are handled in a single round -- their slots and
 // records are loaded back to back (one LDS round trip instead of one per 64 entries), the four partial statistics
 // interleave, and the records stay in registers for the update. Lanes past the end read slot 0 and contribute nothing.
@@ -1679,363 +1679,20 @@ __global__ void k_gather_i32(const int32_t *__restrict__ src, const int32_t *__r
   if (i < n) out[i] = src[idx[i]];
 }
 
-// ---- the same batches, cold parts on the WHOLE GPU ------------------------------------------------------------------
-// When a batch's cold entries number in the tens of thousands (relation blocks with 10^5..10^6 rows: config 5) one
-// workgroup streaming them through a single CU is the bottleneck (~25 GB/s). Phases A and C touch every row at most once
-// per batch, so they run as grid launches; only the walk over the hot rows (B) stays on one workgroup:
-//   k_cb_stats  (grid)  per-column partial statistics of the cold entries, one partial row per workgroup
-//   k_cb_hot    (1 WG)  partials summed in workgroup order, hot rows in LDS, the columns in order: draw, (old, new) out
-//   k_cb_apply  (grid)  cold entries updated with their column's (old, new)
-template <class P>
-__global__ __launch_bounds__(CHAINB_NT) void k_cb_stats(SweepArgs a, ChainBatch B, const int32_t *__restrict__ cols,
-                                                        const int32_t *__restrict__ cold_ptr, const int32_t *__restrict__ cold_row,
-                                                        const int32_t *__restrict__ cold_lcol, const double *__restrict__ cold_x,
-                                                        double2 *__restrict__ part_g /* [gridDim.x][CHAINB_MAXCOLS] */,
-                                                        const int32_t *__restrict__ hot_rows, double2 *__restrict__ hot_pack) {
-  constexpr int NT = CHAINB_NT, NW = NT / WAVE, MC = CHAINB_MAXCOLS, U = 4;
-  __shared__ double c_old[MC];
-  __shared__ double2 part[MC * NW];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  {
-    // the batch's hot records, gathered by the whole grid into a packed buffer: k_cb_hot then stages them with ONE coalesced
-    // round trip instead of a dependent pair (row list -> records) on a single workgroup
-    constexpr int rec2_g = P::REC_DOUBLES / 2;
-    const int rec2_global = P::REC_DOUBLES > 2 ? a.rec2 : 1;
-    for (int i = (int)blockIdx.x * NT + tid; i < B.n_hot * rec2_g; i += (int)gridDim.x * NT) {
-      const int slot = i / rec2_g, w = i - slot * rec2_g;
-      hot_pack[i] = ((const double2 *)a.state)[(int64_t)hot_rows[B.hot_row0 + slot] * rec2_global + w];
-    }
-  }
-  if (tid < B.ncols) c_old[tid] = a.theta[cols[B.col0 + tid]];
-  for (int i = tid; i < MC * NW; i += NT) part[i] = make_double2(0.0, 0.0);
-  __syncthreads();
-  const int cb = B.cold_b, ce = B.cold_e;
-  for (int base = cb + ((int)blockIdx.x * NW + wv) * WAVE * U; base < ce; base += (int)gridDim.x * NW * WAVE * U) {
-    int lc[U], row[U];
-    double xv[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int p = base + u * WAVE + lane;
-      lc[u] = -1 - lane;
-      row[u] = -1;
-      xv[u] = 0.0;
-      if (p < ce) {
-        lc[u] = cold_lcol[p];
-        row[u] = cold_row[p];
-        xv[u] = cold_x[p];
-      }
-    }
-    typename P::St st[U];
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      if (row[u] >= 0) st[u] = P::load(a, row[u]);
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      if (base + u * WAVE >= ce) break;  // wave-uniform
-      double s1 = 0.0, s2 = 0.0;
-      if (row[u] >= 0) P::stats(xv[u], st[u], c_old[lc[u]], s1, s2);
-      const int lp = dpp_i32<0x138, 0xf>(lc[u], 0), ln = dpp_i32<0x130, 0xf>(lc[u], 0);
-      const bool head = lane == 0 || lp != lc[u], tail = lane == 63 || ln != lc[u];
-      int f = head ? 1 : 0;
-      wave_segscan2(s1, s2, f);
-      if (row[u] >= 0 && tail) {  // one lane per column of this tile; a wave adds its tiles in program order
-        double2 &q = part[lc[u] * NW + wv];
-        q.x += s1;
-        q.y += s2;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < MC) {
-    double S1 = 0.0, S2 = 0.0;
-    if (tid < B.ncols)
-      for (int w = 0; w < NW; w++) {  // wave order: deterministic
-        S1 += part[tid * NW + w].x;
-        S2 += part[tid * NW + w].y;
-      }
-    part_g[(size_t)blockIdx.x * MC + tid] = make_double2(S1, S2);
-  }
-}
-
-template <class P>
-__global__ __launch_bounds__(CHAINB_NT) void k_cb_hot(SweepArgs a, ChainBatch B, const int32_t *__restrict__ cols,
-                                                      const int32_t *__restrict__ hot_ptr, const int32_t *__restrict__ hot_slot,
-                                                      const double *__restrict__ hot_x, double2 *__restrict__ hot_pack,
-                                                      const int32_t *__restrict__ col_group, int max_hot, int max_hot_ent,
-                                                      const double2 *__restrict__ part_g, int n_part,
-                                                      double2 *__restrict__ oldnew_g /* [CHAINB_MAXCOLS] */,
-                                                      const double *__restrict__ colpack = nullptr) {
-  extern __shared__ double2 lds_hot[];
-  constexpr int NT = CHAINB_NT, MC = CHAINB_MAXCOLS;
-  constexpr int rec2_g = P::REC_DOUBLES / 2;
-  constexpr int rec2_l = P::REC_DOUBLES > 2 ? rec2_g + 1 : rec2_g;
-  double *c_old = (double *)(lds_hot + (size_t)max_hot * rec2_l);
-  double *c_z = c_old + MC, *c_lam = c_z + MC, *c_mu = c_lam + MC, *c_new = c_mu + MC;
-  double2 *csum = (double2 *)(c_new + MC);    // [MC]
-  double *h_x = (double *)(csum + MC);        // [max_hot_ent]
-  int *h_slot = (int *)(h_x + max_hot_ent);
-  int *h_ptr = h_slot + max_hot_ent;          // [MC + 1]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  SweepArgs al = a;
-  al.state = lds_hot;
-  al.rec2 = rec2_l;
-  if (tid < B.ncols) {  // (first: the longest dependent chain of the prologue, column -> coefficient / variate, group -> lambda / mu)
-    if (colpack) {      //  ... or one load each when k_cb_step packed them)
-      c_old[tid] = colpack[tid];
-      c_z[tid] = colpack[MC + tid];
-      c_lam[tid] = colpack[2 * MC + tid];
-      c_mu[tid] = colpack[3 * MC + tid];
-    } else {
-      const int j = cols[B.col0 + tid];
-      const int g = col_group[B.col0 + tid];
-      c_old[tid] = a.theta[j];
-      c_z[tid] = a.z[j];
-      c_lam[tid] = a.lambda[g];
-      c_mu[tid] = a.mu[g];
-    }
-  }
-  for (int i = tid; i < B.n_hot * rec2_g; i += NT) {
-    const int slot = i / rec2_g, w = i - slot * rec2_g;
-    lds_hot[(size_t)slot * rec2_l + w] = hot_pack[i];  // (packed by k_cb_stats)
-  }
-  const int hb0 = B.hot_b, hb1 = B.hot_e;
-  for (int i = tid; i < hb1 - hb0; i += NT) {
-    h_x[i] = hot_x[hb0 + i];
-    h_slot[i] = hot_slot[hb0 + i];
-  }
-  if (tid <= B.ncols) h_ptr[tid] = hot_ptr[B.col0 + tid] - hb0;
-  if (tid < B.ncols) {
-    double S1 = 0.0, S2 = 0.0;
-    for (int w0 = 0; w0 < n_part; w0 += 8) {  // workgroup order: deterministic (eight loads in flight)
-      double2 q[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) q[u] = w0 + u < n_part ? part_g[(size_t)(w0 + u) * MC + tid] : make_double2(0.0, 0.0);
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-        S1 += q[u].x;
-        S2 += q[u].y;
-      }
-    }
-    csum[tid] = make_double2(S1, S2);
-  }
-  __syncthreads();
-  if (wv == 0) {
-    for (int c = 0; c < B.ncols; c++) {
-      const double S1 = csum[c].x, S2 = csum[c].y;
-      const double old = c_old[c];
-      const int hb = h_ptr[c], he = h_ptr[c + 1];
-      const double fresh = hot_column<P>(a, al, h_x, h_slot, hb, he, lane, S1, S2, old, c_lam[c], c_mu[c], c_z[c]);
-      if (lane == 0) c_new[c] = fresh;
-      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < B.n_hot * rec2_g; i += NT) {
-    const int slot = i / rec2_g, w = i - slot * rec2_g;
-    hot_pack[i] = lds_hot[(size_t)slot * rec2_l + w];  // (k_cb_apply scatters them to their rows)
-  }
-  if (tid < B.ncols) {
-    a.theta[cols[B.col0 + tid]] = c_new[tid];
-    oldnew_g[tid] = make_double2(c_old[tid], c_new[tid]);
-  }
-}
-
-template <class P>
-__global__ __launch_bounds__(CHAINB_NT) void k_cb_apply(SweepArgs a, ChainBatch B, const int32_t *__restrict__ cold_ptr,
-                                                        const int32_t *__restrict__ cold_row, const int32_t *__restrict__ cold_lcol,
-                                                        const double *__restrict__ cold_x, const double2 *__restrict__ oldnew_g,
-                                                        const int32_t *__restrict__ hot_rows, const double2 *__restrict__ hot_pack) {
-  constexpr int NT = CHAINB_NT, MC = CHAINB_MAXCOLS, U = 4;
-  __shared__ double2 on[MC];
-  const int tid = threadIdx.x;
-  {
-    constexpr int rec2_g = P::REC_DOUBLES / 2;
-    const int rec2_global = P::REC_DOUBLES > 2 ? a.rec2 : 1;
-    for (int i = (int)blockIdx.x * NT + tid; i < B.n_hot * rec2_g; i += (int)gridDim.x * NT) {
-      const int slot = i / rec2_g, w = i - slot * rec2_g;
-      ((double2 *)a.state)[(int64_t)hot_rows[B.hot_row0 + slot] * rec2_global + w] = hot_pack[i];
-    }
-  }
-  if (tid < B.ncols) on[tid] = oldnew_g[tid];
-  __syncthreads();
-  const int cb = B.cold_b, ce = B.cold_e;
-  for (int base = cb + (int)blockIdx.x * NT * U + tid; base < ce; base += (int)gridDim.x * NT * U) {
-    int lc[U], row[U];
-    double xv[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-      const int p = base + u * NT;
-      row[u] = -1;
-      lc[u] = 0;
-      xv[u] = 0.0;
-      if (p < ce) {
-        lc[u] = cold_lcol[p];
-        row[u] = cold_row[p];
-        xv[u] = cold_x[p];
-      }
-    }
-    typename P::St st[U];
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      if (row[u] >= 0) st[u] = P::load(a, row[u]);
-#pragma unroll
-    for (int u = 0; u < U; u++)
-      if (row[u] >= 0) P::apply(a, row[u], xv[u], st[u], on[lc[u]].x, on[lc[u]].y);
-  }
-}
-
-// ---- cold update of batch b and cold statistics of batch b + 1 in ONE launch ----------------------------------------------
-// Both touch block-row records only, so the rows are split into CB_BUCKETS contiguous ranges and workgroup w owns range w in
-// both halves (the batches' cold entries and hot rows are bucketed by row range on the host): the statistics of batch b + 1
-// depend on the update of batch b only through rows of the same range, i.e. through this workgroup -- a workgroup barrier
-// replaces the kernel boundary (two launches per batch instead of three). Bp.ncols == 0: nothing to update (first batch);
-// Bn.ncols == 0: no statistics to take (after the last batch).
+// ---- the same batches, cold parts on the WHOLE GPU: the batch sequence of a chain run as ONE launch (k_cb_persist) ------------
+// When a batch's cold entries number in the tens of thousands (relation blocks with 10^5..10^6 rows: config 5) one workgroup
+// streaming them through a single CU is the bottleneck (~25 GB/s). The cold statistics and the cold update touch every row at
+// most once per batch and block-row records only, so the rows are split into CB_BUCKETS contiguous ranges (the batches' cold
+// entries and hot rows are bucketed by row range by the planner); only the walk over the hot rows stays on one workgroup.
+// Workgroup 0 is the hot walker and workgroups 1 .. CB_BUCKETS own the row ranges for the whole run: the statistics of batch
+// b + 1 depend on the update of batch b only through rows of the same range, i.e. through the same workgroup, and the hand-over
+// between the ranges and the walker is a counter in device memory, not a kernel boundary. Everything the two sides exchange
+// (the batch's packed hot records, the per-range partial statistics, the packed column scalars, the (old, new) pairs) is written
+// with agent-scope stores and read with agent-scope loads (write-through / L2-bypassing on gfx950: visible across XCDs without a
+// fence), so no L2 is written back or invalidated between batches and a range's block-row records stay in its workgroup's L2.
+// The block-row records themselves are only ever touched by their range's workgroup. A column's cold statistics are summed in
+// range order, the hot walk is k_chain_batched's.
 constexpr int CB_BUCKETS = 16;
-template <class P>
-__global__ __launch_bounds__(CHAINB_NT) void k_cb_step(SweepArgs a, ChainBatch Bp, int ip, ChainBatch Bn, int in_, const int32_t *__restrict__ cols,
-                                                       const int32_t *__restrict__ bk_ptr, const int32_t *__restrict__ bk_row,
-                                                       const int32_t *__restrict__ bk_lcol, const double *__restrict__ bk_x,
-                                                       const int32_t *__restrict__ hbk_ptr, const int32_t *__restrict__ hot_rows,
-                                                       const double2 *__restrict__ oldnew_g, double2 *__restrict__ part_g,
-                                                       const double2 *__restrict__ hot_pack_p, double2 *__restrict__ hot_pack_n,
-                                                       const int32_t *__restrict__ col_group, double *__restrict__ colpack) {
-  constexpr int NT = CHAINB_NT, NW = NT / WAVE, MC = CHAINB_MAXCOLS, U = 4, NB = CB_BUCKETS;
-  constexpr int rec2_g = P::REC_DOUBLES / 2;
-  __shared__ double2 on[MC];
-  __shared__ double c_old[MC];
-  __shared__ double2 part[MC * NW];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, w = blockIdx.x;
-  const int rec2_global = P::REC_DOUBLES > 2 ? a.rec2 : 1;
-  if (tid < Bp.ncols) on[tid] = oldnew_g[tid];
-  if (tid < Bn.ncols) {
-    const int j = cols[Bn.col0 + tid];
-    const double th = a.theta[j];
-    c_old[tid] = th;
-    if (w == 0) {  // the hot walk's per-column scalars, packed: k_cb_hot reads them with one round trip
-      const int g = col_group[Bn.col0 + tid];
-      colpack[tid] = th;
-      colpack[MC + tid] = a.z[j];
-      colpack[2 * MC + tid] = a.lambda[g];
-      colpack[3 * MC + tid] = a.mu[g];
-    }
-  }
-  for (int i = tid; i < MC * NW; i += NT) part[i] = make_double2(0.0, 0.0);
-  // the first round of the statistics half's entries is requested now: it does not depend on the update half, and after the
-  // barrier only the record gather is left of that half's dependent loads
-  const int cbn = Bn.ncols > 0 ? bk_ptr[in_ * (NB + 1) + w] : 0, cen = Bn.ncols > 0 ? bk_ptr[in_ * (NB + 1) + w + 1] : 0;
-  int lc0[U], row0[U];
-  double xv0[U];
-#pragma unroll
-  for (int u = 0; u < U; u++) {
-    const int p = cbn + wv * WAVE * U + u * WAVE + lane;
-    lc0[u] = -1 - lane;
-    row0[u] = -1;
-    xv0[u] = 0.0;
-    if (p < cen) {
-      lc0[u] = bk_lcol[p];
-      row0[u] = bk_row[p];
-      xv0[u] = bk_x[p];
-    }
-  }
-  __syncthreads();
-  if (Bp.ncols > 0) {
-    const int hb = hbk_ptr[ip * (NB + 1) + w], he = hbk_ptr[ip * (NB + 1) + w + 1];
-    for (int i = hb * rec2_g + tid; i < he * rec2_g; i += NT) {
-      const int slot = i / rec2_g, q = i - slot * rec2_g;
-      ((double2 *)a.state)[(int64_t)hot_rows[Bp.hot_row0 + slot] * rec2_global + q] = hot_pack_p[i];
-    }
-    const int cb = bk_ptr[ip * (NB + 1) + w], ce = bk_ptr[ip * (NB + 1) + w + 1];
-    for (int base = cb + tid; base < ce; base += NT * U) {
-      int lc[U], row[U];
-      double xv[U];
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const int p = base + u * NT;
-        row[u] = -1;
-        lc[u] = 0;
-        xv[u] = 0.0;
-        if (p < ce) {
-          lc[u] = bk_lcol[p];
-          row[u] = bk_row[p];
-          xv[u] = bk_x[p];
-        }
-      }
-      typename P::St st[U];
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (row[u] >= 0) st[u] = P::load(a, row[u]);
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (row[u] >= 0) P::apply(a, row[u], xv[u], st[u], on[lc[u]].x, on[lc[u]].y);
-    }
-  }
-  __threadfence_block();
-  __syncthreads();  // this range's records are up to date for everything below (the only reader of them is this workgroup)
-  if (Bn.ncols > 0) {
-    const int hb = hbk_ptr[in_ * (NB + 1) + w], he = hbk_ptr[in_ * (NB + 1) + w + 1];
-    for (int i = hb * rec2_g + tid; i < he * rec2_g; i += NT) {
-      const int slot = i / rec2_g, q = i - slot * rec2_g;
-      hot_pack_n[i] = ((const double2 *)a.state)[(int64_t)hot_rows[Bn.hot_row0 + slot] * rec2_global + q];
-    }
-    const int cb = cbn, ce = cen;
-    for (int base = cb + wv * WAVE * U; base < ce; base += NW * WAVE * U) {
-      int lc[U], row[U];
-      double xv[U];
-      const bool first = base == cb + wv * WAVE * U;
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const int p = base + u * WAVE + lane;
-        lc[u] = first ? lc0[u] : -1 - lane;
-        row[u] = first ? row0[u] : -1;
-        xv[u] = first ? xv0[u] : 0.0;
-        if (!first && p < ce) {
-          lc[u] = bk_lcol[p];
-          row[u] = bk_row[p];
-          xv[u] = bk_x[p];
-        }
-      }
-      typename P::St st[U];
-#pragma unroll
-      for (int u = 0; u < U; u++)
-        if (row[u] >= 0) st[u] = P::load(a, row[u]);
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        if (base + u * WAVE >= ce) break;  // wave-uniform
-        double s1 = 0.0, s2 = 0.0;
-        if (row[u] >= 0) P::stats(xv[u], st[u], c_old[lc[u]], s1, s2);
-        const int lp = dpp_i32<0x138, 0xf>(lc[u], 0), ln = dpp_i32<0x130, 0xf>(lc[u], 0);
-        const bool head = lane == 0 || lp != lc[u], tail = lane == 63 || ln != lc[u];
-        int f = head ? 1 : 0;
-        wave_segscan2(s1, s2, f);
-        if (row[u] >= 0 && tail) {  // one lane per column of this tile; a wave adds its tiles in program order
-          double2 &q = part[lc[u] * NW + wv];
-          q.x += s1;
-          q.y += s2;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid < MC) {
-      double S1 = 0.0, S2 = 0.0;
-      if (tid < Bn.ncols)
-        for (int k = 0; k < NW; k++) {  // wave order: deterministic
-          S1 += part[tid * NW + k].x;
-          S2 += part[tid * NW + k].y;
-        }
-      part_g[(size_t)w * MC + tid] = make_double2(S1, S2);
-    }
-  }
-}
-
-// ---- the whole batch sequence of a chain run as ONE launch (k_cb_persist) ------------------------------------------------------
-// k_cb_step and k_cb_hot alternate strictly (step b -> hot b -> step b + 1): 2 launches per batch, and at ~11 columns per batch a
-// kernel's start, its prologue round trips and the boundary's cache write-back / invalidate are most of its 16-20 us. Here
-// workgroup 0 is the hot walker and workgroups 1 .. CB_BUCKETS own the row ranges for the whole run; what used to be a kernel
-// boundary is a counter in device memory. Everything the two sides exchange (the batch's packed hot records, the per-range
-// partial statistics, the packed column scalars, the (old, new) pairs) is written with agent-scope stores and read with
-// agent-scope loads (write-through / L2-bypassing on gfx950: visible across XCDs without a fence), so no L2 is written back
-// or invalidated between batches and a range's block-row records stay in its workgroup's L2. The block-row records themselves
-// are only ever touched by their range's workgroup. Same arithmetic, same summation order as the two-launch form.
 struct CbSync {
   unsigned long long step_done;  // += 1 per range workgroup and batch step
   unsigned long long pad0[15];

@@ -19,6 +19,7 @@
 #include <mutex>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include <dlfcn.h>
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(1024) void k_cbb_batches(const int64_t *__restrict_
   }
 }
 
-// Row-bucketed copies for the grid form (k_cb_step / k_cb_persist): per batch the cold entries ordered by (row range, class,
+// Row-bucketed copies for the grid form (k_cb_persist): per batch the cold entries ordered by (row range, class,
 // column) -- class = (statistics near / far, update near / far): is the entry's row touched by the batch before / after? -- and the
 // hot slots' row ranges. ONE workgroup, batch by batch (the neighbours' rows are stamped as the host form stamps them).
 __global__ __launch_bounds__(1024) void k_cbb_buckets(const ChainBatch *__restrict__ bt, int nb, const int32_t *__restrict__ crow,
@@ -363,22 +364,51 @@ __global__ __launch_bounds__(1024) void k_cbb_buckets(const ChainBatch *__restri
   }
 }
 
+// What a chain run launches when its state does not fit the LDS chain (chain_fits_lds: k_chain_lds) or batching is forced
+enum class ChainForm {
+  Serial,   // k_chain: one workgroup, column after column, on global memory
+  Batched,  // k_chain_batched: conflict batches, one workgroup
+  Persist,  // k_cb_persist: conflict batches, their cold parts by row range on the grid
+  Stream,   // k_cs_stream (mfm_chain_stream.hpp): relation blocks only
+};
+
+// The chain switches, read once per StepPlan::build and handed to the builders: the launcher reads none of them
+struct ChainSwitches {
+  bool force_batched = false, no_grid = false, no_stream = false, check = false, timing = false;
+  int hot_cap = 1200;        // hot rows of a conflict batch (the LDS budget of the hot walk)
+  int64_t grid_min = 4096;   // cold entries per batch from which the cold parts go to the grid
+  static ChainSwitches read() {
+    ChainSwitches sw;
+    sw.force_batched = env_flag("MFM_CHAIN_FORCE_BATCHED");
+    sw.no_grid = env_flag("MFM_NO_CHAIN_GRID");
+    sw.no_stream = env_flag("MFM_NO_CB_STREAM");
+    sw.check = env_flag("MFM_PLAN_CHECK");
+    sw.timing = env_flag("MFM_SETUP_TIMING");
+    if (env_flag("MFM_CHAIN_HOT_CAP")) sw.hot_cap = std::max(64, env_int("MFM_CHAIN_HOT_CAP", 0));
+    sw.grid_min = env_i64("MFM_CHAIN_GRID_MIN", 4096);
+    return sw;
+  }
+  // batches with many cold entries (one CU cannot stream them): both builders add the row-bucketed copies, k_cb_persist runs
+  bool grid(int n_batches, int64_t n_cold) const { return n_batches > 0 && n_cold / n_batches >= grid_min && !no_grid; }
+};
+
 struct ChainRun {
   DevBuf<ChainDesc> desc;  // (first CSC entry, length, column) per chain column, for k_chain_lds
   DevBuf<int32_t> cols;
   int n_cols = 0;
   int64_t nnz = 0;
+  ChainForm form = ChainForm::Serial;  // set once, at the end of build_forms(), from what was built
+  bool skip_lds = false;               // batching is forced (MFM_CHAIN_FORCE_BATCHED at plan time): not the LDS chain either
   // conflict-batched form (k_chain_batched): per batch the rows touched by more than one of its columns ("hot")
   // are staged in LDS; entries are split into cold (sorted by column) and hot (slot into the batch's hot rows)
   bool batched = false;
   int n_batches = 0, max_hot = 0, max_hot_ent = 0;
   DevBuf<ChainBatch> batches;
-  std::vector<ChainBatch> h_batches;   // host copies: the grid form (k_cb_*) launches batch by batch
-  std::vector<int32_t> h_cold_cnt;     // cold entries per batch
   int64_t n_cold = 0;
   DevBuf<int32_t> cold_ptr, cold_row, cold_lcol, hot_ptr, hot_slot, hot_rows;
   DevBuf<double> cold_x, hot_x;
-  // row-bucketed copies for k_cb_step: per batch the cold entries ordered by (row range, column) and the hot slots' row ranges
+  // row-bucketed copies for k_cb_persist: per batch the cold entries ordered by (row range, class, column) and the hot slots' row
+  // ranges
   bool bucketed = false;
   DevBuf<int32_t> bk_ptr, bk_row, bk_lcol, hbk_ptr, bk_cls;
   DevBuf<double> bk_x;
@@ -395,13 +425,13 @@ struct ChainRun {
     cols.borrow(o.cols);
     n_cols = o.n_cols;
     nnz = o.nnz;
+    form = o.form;
+    skip_lds = o.skip_lds;
     batched = o.batched;
     n_batches = o.n_batches;
     max_hot = o.max_hot;
     max_hot_ent = o.max_hot_ent;
     batches.borrow(o.batches);
-    h_batches = o.h_batches;
-    h_cold_cnt = o.h_cold_cnt;
     n_cold = o.n_cold;
     cold_ptr.borrow(o.cold_ptr);
     cold_row.borrow(o.cold_row);
@@ -424,8 +454,9 @@ struct ChainRun {
 
   // the same structures built on the device from the device CSC (dv.colptr / rowidx / cval); false: not built (the caller takes
   // the host form)
-  bool build_batched_device(const DevCscView &dv, const std::vector<int32_t> &run, int hot_cap) {
+  bool build_batched_device(const DevCscView &dv, const std::vector<int32_t> &run, const ChainSwitches &sw) {
     const int64_t n_rows = dv.n_rows;
+    const int hot_cap = sw.hot_cap;
     const int n_run = (int)run.size();
     if (!dv.colptr || !dv.rowidx || !dv.cval || !cols.p || n_run < 1 || n_rows < 1 || hot_cap > CBB_MAX_HOT) return false;
     if (n_rows * 8 > ((int64_t)1 << 30)) return false;  // (scratch counters: 8 bytes per row and workgroup)
@@ -488,9 +519,6 @@ struct ChainRun {
       max_hot_ent = std::max(max_hot_ent, B.hot_e - B.hot_b);
     }
     n_batches = nb;
-    h_batches = bt;
-    h_cold_cnt.clear();
-    for (const ChainBatch &B : bt) h_cold_cnt.push_back(B.cold_e - B.cold_b);
     n_cold = cptr[n_run];
     const int64_t n_hot_ent = hptr[n_run];
     batches.upload(bt.data(), bt.size());
@@ -511,8 +539,7 @@ struct ChainRun {
     batched = true;
     bucketed = false;
     // 3. the grid form's row-bucketed copies
-    const int64_t grid_min = env_i64("MFM_CHAIN_GRID_MIN", 4096);
-    if (n_batches > 0 && n_cold / n_batches >= grid_min && !env_flag("MFM_NO_CHAIN_GRID")) {
+    if (sw.grid(n_batches, n_cold)) {
       constexpr int NB = CB_BUCKETS;
       DevBuf<int32_t> seen_prev, seen_next;
       seen_prev.alloc((size_t)n_rows);
@@ -537,7 +564,7 @@ struct ChainRun {
   // tests (MFM_PLAN_CHECK): every array of two builds of the same run
   std::string compare_batched(const ChainRun &o, hipStream_t s) const {
     if (batched != o.batched || n_batches != o.n_batches || max_hot != o.max_hot || max_hot_ent != o.max_hot_ent || n_cold != o.n_cold ||
-        bucketed != o.bucketed || h_cold_cnt != o.h_cold_cnt)
+        bucketed != o.bucketed)
       return "scalars";
     auto same = [&](const void *p, size_t np, const void *q, size_t nq, size_t elem) {
       if (np != nq) return false;
@@ -570,8 +597,9 @@ struct ChainRun {
     return "";
   }
 
-  void build_batched(const HostCsr &csc, const std::vector<int32_t> &run, int hot_cap) {
+  void build_batched(const HostCsr &csc, const std::vector<int32_t> &run, const ChainSwitches &sw) {
     const int64_t n_rows = csc.cols;
+    const int hot_cap = sw.hot_cap;
     std::vector<int32_t> cnt((size_t)n_rows, 0), slot_of((size_t)n_rows, -1);
     std::vector<ChainBatch> bt;
     std::vector<int32_t> cptr{0}, crow, clcol, hptr{0}, hslot, hrows;
@@ -603,7 +631,7 @@ struct ChainRun {
       B.ncols = (int32_t)(e - c);
       B.hot_row0 = (int32_t)hrows.size();
       int ns = 0;
-      {  // hot slots in ascending row order (k_cb_step splits them by row range)
+      {  // hot slots in ascending row order (k_cb_persist splits them by row range)
         std::vector<int32_t> hr;
         for (int32_t r : touched)
           if (cnt[r] > 1) hr.push_back(r);
@@ -644,9 +672,6 @@ struct ChainRun {
       c = e;
     }
     n_batches = (int)bt.size();
-    h_batches = bt;
-    h_cold_cnt.clear();
-    for (const ChainBatch &B : bt) h_cold_cnt.push_back(cptr[B.col0 + B.ncols] - cptr[B.col0]);
     n_cold = (int64_t)crow.size();
     batches.upload(bt.data(), bt.size());
     cold_ptr.upload(cptr);
@@ -658,9 +683,8 @@ struct ChainRun {
     hot_x.upload(hx);
     hot_rows.upload(hrows);
     batched = true;
-    // the grid form (k_cb_*) also gets the row-bucketed copies
-    const int64_t grid_min = env_i64("MFM_CHAIN_GRID_MIN", 4096);
-    if (n_batches > 0 && n_cold / n_batches >= grid_min && !env_flag("MFM_NO_CHAIN_GRID")) {
+    // the grid form (k_cb_persist) also gets the row-bucketed copies
+    if (sw.grid(n_batches, n_cold)) {
       constexpr int NB = CB_BUCKETS;
       auto bucket = [&](int32_t r) { return (int)(((int64_t)r * NB) / std::max<int64_t>(n_rows, 1)); };
       std::vector<int32_t> bptr((size_t)n_batches * (NB + 1), 0), hbptr((size_t)n_batches * (NB + 1), 0);
@@ -718,6 +742,57 @@ struct ChainRun {
       bk_x.upload(bx);
       bucketed = true;
     }
+  }
+
+  // the conflict batches of the run h_cols: on the device when the matrix's CSC is there (relation blocks, the main table); the
+  // host form is the fall-back and, under MFM_PLAN_CHECK, the checker
+  void build_batches(const HostCsr &csc, const DevCscView *dev, const ChainSwitches &sw) {
+    const bool on_dev = dev && build_batched_device(*dev, h_cols, sw);
+    if (sw.timing)
+      std::fprintf(stderr, "[plan] conflict batches of a %zu-column chain run: %s (%d batches, %lld cold entries)\n", h_cols.size(),
+                   on_dev ? "device" : "host", on_dev ? n_batches : -1, on_dev ? (long long)n_cold : -1ll);
+    if (!on_dev) {
+      build_batched(csc, h_cols, sw);
+    } else if (sw.check) {
+      ChainRun chk;
+      chk.build_batched(csc, h_cols, sw);
+      const std::string diff = compare_batched(chk, dev->stream);
+      if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host conflict batches differ (" + diff + ")");
+    }
+  }
+  void build_stream(const HostCsr &csc, const ChainSwitches &sw) {
+    CsStreamInfo ci;
+    stream = cs_stream_build(csc, h_cols, &ci);
+    if (!sw.timing) return;
+    if (stream)
+      std::fprintf(stderr, "[plan] streamed chain of %zu columns: steps of %d columns, window %d steps, %d ranges, %d LDS slots, %lld cold + %lld "
+                           "hot entries (<= %d hot per column), <= %d entering / %d leaving rows per step, planned in %.3f s\n",
+                   h_cols.size(), ci.Cg, ci.Lw, ci.NB, ci.n_slots, ci.n_cold, ci.n_hot, ci.max_hot_col, ci.max_enter, ci.max_exit, ci.plan_seconds);
+    else
+      std::fprintf(stderr, "[plan] streamed chain of %zu columns: no window fits the LDS, conflict batches kept\n", h_cols.size());
+  }
+  // The forms beyond the plain chain, for the run h_cols of csc. on_block: the plan of a relation block. A main-table plan never
+  // launches the stream: building it, and skipping the conflict batches for it, would leave a long main chain to the
+  // single-workgroup kernel.
+  void build_forms(const HostCsr &csc, const DevCscView *dev, bool on_block, const ChainSwitches &sw) {
+    // state too large for the LDS chain of any policy: also keep the conflict-batched form
+    const bool batches_wanted = (csc.cols > 1900 || sw.force_batched) && h_cols.size() >= 2;
+    const bool stream_allowed = on_block && !sw.no_stream && !sw.no_grid;
+    if (batches_wanted) {
+      // Long columns (the cold parts of a batch would run on the whole GPU: relation blocks with 10^5..10^6 rows): the streamed
+      // form is tried FIRST, and when it can be built the conflict batches -- then never launched -- are not built at all (0.06 s
+      // of device work and ~100 MB per big block at config 5). The checker mode builds both: the batches' device / host
+      // comparison stays tested.
+      const bool stream_first = stream_allowed && !sw.check && !sw.force_batched && nnz >= (int64_t)256 * (int64_t)h_cols.size();
+      if (stream_first) build_stream(csc, sw);
+      if (!stream) {
+        build_batches(csc, dev, sw);
+        // chains whose cold parts run on the whole GPU: the streamed form (unless it was tried above)
+        if (bucketed && stream_allowed && !stream_first) build_stream(csc, sw);
+      }
+    }
+    form = stream ? ChainForm::Stream : !batched ? ChainForm::Serial : bucketed ? ChainForm::Persist : ChainForm::Batched;
+    skip_lds = batched && sw.force_batched;
   }
 };
 
@@ -988,6 +1063,19 @@ struct StepPlan {
   // thread of the workgroup bin; coop_max: workgroups that are safely co-resident on the device
   int64_t max_cols_scat = 0;
 
+  // Entries of the level `cols` whose row an earlier entry of the level has already: 0 and as many entries as rows = the level
+  // touches every row exactly once (the device's count: k_dp_level_scan)
+  static int64_t rows_repeated(const HostCsr &csc, const std::vector<int32_t> &cols) {
+    std::vector<char> seen((size_t)csc.cols, 0);
+    int64_t twice = 0;
+    for (int32_t j : cols)
+      for (int64_t p = csc.ptr[j]; p < csc.ptr[j + 1]; p++) {
+        twice += seen[csc.idx[p]];
+        seen[csc.idx[p]] = 1;
+      }
+    return twice;
+  }
+
   // Row-blocked layout for a level whose columns jump between far-apart rows. Returns false (and leaves
   // L untouched) when the level is small or its columns are mostly contiguous.
   // tile_bits > 0: row-tile variant (tiles of 2^tile_bits rows staged in LDS, packed + padded entries)
@@ -1081,15 +1169,7 @@ struct StepPlan {
       std::vector<int32_t> cur(sptr.begin(), sptr.end() - 1);
       for (size_t r = 0; r < run_col.size(); r++) sidx[cur[local[run_col[r]]]++] = (int32_t)r;
     }
-    {
-      std::vector<char> seen((size_t)N, 0);
-      bool once = lnnz == N;
-      for (int64_t q = 0; once && q < lnnz; q++) {
-        once = !seen[ent[q].x];
-        seen[ent[q].x] = 1;
-      }
-      L.covers_rows_once = once;
-    }
+    L.covers_rows_once = lnnz == N && rows_repeated(csc, cols) == 0;
     L.scattered = true;
     L.n_ent = lnnz;
     L.n_cols = (int)cols.size();
@@ -1292,16 +1372,7 @@ struct StepPlan {
       std::vector<int32_t> cur(sptr.begin(), sptr.end() - 1);
       for (size_t r = 0; r < run_col.size(); r++) sidx[cur[run_col[r]]++] = (int32_t)r;
     }
-    {
-      std::vector<char> seen((size_t)N, 0);
-      bool once = lnnz == N;
-      for (int32_t j : cols)
-        for (int64_t p = csc.ptr[j]; once && p < csc.ptr[j + 1]; p++) {
-          once = !seen[csc.idx[p]];
-          seen[csc.idx[p]] = 1;
-        }
-      L.covers_rows_once = once;
-    }
+    L.covers_rows_once = lnnz == N && rows_repeated(csc, cols) == 0;
     L.scattered = true;
     L.tiled = true;
     L.tile_bits = tile_bits;
@@ -1598,20 +1669,24 @@ struct StepPlan {
     }
   }
 
-  void build(const HostCsr &csc, int r_w16, int r_wg, int coop_max, bool allow_scatter = false, bool unit = false,
-             const StepPlan *twin = nullptr) {
-    // twin: a plan already built for the SAME matrix with the same settings (the other sweep of the table): its level
-    // assignment and its row-tile levels are reused
-    const int coop_local = coop_max;  // (sharded_tiles: locally complete long columns still run co-resident)
-    if (sharded) coop_max = 0;
-    n_state_rows = csc.cols;
-    {
-      std::vector<int32_t> r0((size_t)csc.rows, 0);
-      for (int64_t j = 0; j < csc.rows; j++)
-        if (csc.ptr[j + 1] > csc.ptr[j]) r0[j] = csc.idx[csc.ptr[j]];
-      col_row0.upload(r0);
-    }
-    const int64_t cap_w1 = WAVE, cap_w4 = 4 * WAVE, cap_w16 = (int64_t)r_w16 * WAVE, cap_wg = (int64_t)r_wg * WG;
+  // ---- build, stage by stage (in the order of the calls in build() below) ----------------------------------------------------
+  struct BuildAsk {  // what every stage is handed
+    const HostCsr &csc;
+    const StepPlan *twin;  // a plan already built for the SAME matrix with the same settings (the other sweep of the table): its
+                           // level assignment, its chain runs and its row-tile levels are reused
+    ChainSwitches sw;
+    int64_t cap_w1, cap_w4, cap_w16, cap_wg;  // entries per column of the bins (see the file header)
+    int coop_max, coop_local;  // co-resident workgroups (sharded: none; sharded_tiles: locally complete long columns still have them)
+    bool allow_scatter, unit;
+  };
+  struct OpenRun {  // consecutive tiny levels, waiting to become one chain step
+    std::vector<int32_t> cols;
+    int64_t nnz = 0;
+  };
+
+  // level of every column: given (row-sharded mode), the twin's, computed on the device, or on the host
+  std::vector<int32_t> assign_levels(const BuildAsk &ask) {
+    const HostCsr &csc = ask.csc;
     std::vector<int32_t> level;
     if (!given_levels.empty() || (sharded && csc.rows > 0)) {
       if (given_levels.empty())
@@ -1620,11 +1695,11 @@ struct StepPlan {
       level = given_levels;
       n_levels = 0;
       for (auto l : level) n_levels = std::max(n_levels, l + 1);
-    } else if (twin && !twin->h_level.empty() && (int64_t)twin->h_level.size() == csc.rows) {
-      level = twin->h_level;
-      n_levels = twin->n_levels;
+    } else if (ask.twin && !ask.twin->h_level.empty() && (int64_t)ask.twin->h_level.size() == csc.rows) {
+      level = ask.twin->h_level;
+      n_levels = ask.twin->n_levels;
     } else if (dev_csc && column_levels_device(*dev_csc, level, n_levels)) {
-      if (env_flag("MFM_PLAN_CHECK")) {  // tests: the device schedule must be the host schedule
+      if (ask.sw.check) {  // tests: the device schedule must be the host schedule
         std::vector<int32_t> hl;
         const int32_t hn = column_levels(csc, hl);
         if (hn != n_levels || hl != level) throw Error(MFM_ERR_RUNTIME, "plan check: device and host level schedules differ");
@@ -1633,199 +1708,158 @@ struct StepPlan {
       n_levels = column_levels(csc, level);
     }
     h_level = level;
+    return level;
+  }
+
+  // a run of tiny levels as one CHAIN step (nothing when no run is open)
+  void add_chain_step(const BuildAsk &ask, OpenRun run) {
+    if (run.cols.empty()) return;
+    steps.emplace_back();
+    steps.back().is_chain = true;
+    launches += 1;
+    ChainRun &C = steps.back().chain;
+    {  // the twin has the same run at the same place: its arrays serve both sweeps
+      const size_t si = steps.size() - 1;
+      const StepPlan *twin = ask.twin;
+      const Step *tw = twin && si < twin->steps.size() && twin->steps[si].is_chain ? &twin->steps[si] : nullptr;
+      if (tw && !sharded && !twin->sharded && tw->chain.h_cols == run.cols) {
+        C.borrow(tw->chain);
+        return;
+      }
+    }
+    C.h_cols = run.cols;
+    C.n_cols = (int)run.cols.size();
+    C.nnz = run.nnz;
+    C.cols.upload(run.cols);
+    std::vector<ChainDesc> d;
+    for (int32_t j : run.cols) d.push_back(ChainDesc{ask.csc.ptr[j], (int32_t)(ask.csc.ptr[j + 1] - ask.csc.ptr[j]), j});
+    C.desc.upload(d.data(), d.size());
+    C.build_forms(ask.csc, dev_csc, block_plan, ask.sw);
+  }
+
+  // one level with enough work as a PAR step: borrowed from the twin, scattered (row tiles / row blocks), or binned by length
+  void add_par_step(const BuildAsk &ask, const std::vector<int32_t> &cols, int64_t lnnz) {
+    const HostCsr &csc = ask.csc;
+    steps.emplace_back();
+    ParLevel &L = steps.back().par;
+    const bool first = steps.size() == 1;
+    L.cols_all.upload(cols);
+    L.n_all = (int)cols.size();
+    L.jmin = *std::min_element(cols.begin(), cols.end());
+    L.jmax = *std::max_element(cols.begin(), cols.end());
+    {
+      // the twin built this level on row tiles with the same boundaries: borrow it
+      const size_t si = steps.size() - 1;
+      const StepPlan *twin = ask.twin;
+      const ParLevel *tw = twin && si < twin->steps.size() && !twin->steps[si].is_chain ? &twin->steps[si].par : nullptr;
+      if (ask.allow_scatter && tw && tw->tiled && tw->tile_bits == tile_bits && tw->n_cols == (int)cols.size() && tw->n_ent == lnnz &&
+          twin->aligned_tiles == aligned_tiles && twin->h_tile_start == h_tile_start && !sharded) {
+        L.borrow_tiled(*tw);
+        launches += 3;
+        max_cols_scat = std::max<int64_t>(max_cols_scat, csc.rows);
+        return;
+      }
+    }
+    // first look at the level -- contiguous columns? far-apart rows? every row exactly once? -- on the device when the CSC is there
+    const bool want_once = first && lnnz == csc.cols;
+    LevelScan scan;
+    if (dev_csc) {
+      scan = level_scan_device(*dev_csc, L.cols_all.p, L.n_all, want_once);
+      if (scan.valid && ask.sw.check) {  // tests: the host's counts
+        int64_t gaps = 0, far = 0;
+        for (int32_t j : cols)
+          for (int64_t p = csc.ptr[j] + 1; p < csc.ptr[j + 1]; p++) {
+            gaps += csc.idx[p] != csc.idx[p - 1] + 1;
+            far += (csc.idx[p] - csc.idx[p - 1]) >= 8;
+          }
+        if (gaps != scan.gaps || far != scan.far || (want_once ? rows_repeated(csc, cols) : 0) != scan.twice)
+          throw Error(MFM_ERR_RUNTIME, "plan check: device and host level scans differ");
+      }
+    }
+    if (ask.allow_scatter && build_scattered(csc, cols, lnnz, ask.unit, L, (sharded && !sharded_tiles) ? 0 : tile_bits,
+                                             aligned_tiles ? &h_tile_start : nullptr, dev_csc, &scan)) {
+      launches += 3;
+      max_cols_scat = std::max<int64_t>(max_cols_scat, csc.rows);
+      return;
+    }
+    if (want_once) L.first_and_once = (scan.valid ? scan.twice : rows_repeated(csc, cols)) == 0;
+    bin_columns(csc, cols, L, ask.cap_w1, ask.cap_w4, ask.cap_w16, ask.cap_wg, ask.coop_max);
+    {
+      bool contig = !scan.valid || scan.gaps == 0;
+      for (size_t c = 0; !scan.valid && contig && c < cols.size(); c++) {
+        const int32_t j = cols[c];
+        for (int64_t p = csc.ptr[j] + 1; contig && p < csc.ptr[j + 1]; p++) contig = csc.idx[p] == csc.idx[p - 1] + 1;
+      }
+      L.contig = contig;
+    }
+    if (first && L.contig && L.first_and_once && ask.allow_scatter && (!sharded || sharded_tiles) && tile_bits > 0)
+      build_aligned_tiles(csc, cols, (int64_t)1 << tile_bits);
+    if (first && sharded_tiles && aligned_tiles) split_first_level_sharded(ask, cols, L);
+    max_hchunks = std::max(max_hchunks, L.n_hchunks);
+    max_huge = std::max(max_huge, L.n_huge);
+    launches += ((L.n_w1 + L.n_w4) ? 1 : 0) + ((L.n_w16 + L.n_wg) ? 1 : 0) + (int64_t)L.rounds.size() + (L.n_huge ? 3 : 0);
+  }
+
+  // row-sharded mode on the fused tile path: the first level L split into special_level and local_level (see above)
+  void split_first_level_sharded(const BuildAsk &ask, const std::vector<int32_t> &cols, const ParLevel &L) {
+    const HostCsr &csc = ask.csc;
+    std::vector<int32_t> sp, loc;
+    for (int32_t j : cols) {
+      if (!special.empty() && special[j] == 1)
+        sp.push_back(j);
+      else if (csc.ptr[j + 1] > csc.ptr[j] || (!special.empty() && special[j] == 2))
+        loc.push_back(j);
+    }
+    local_level.cols_all.upload(loc);
+    local_level.n_all = (int)loc.size();
+    local_level.contig = L.contig;
+    bin_columns(csc, loc, local_level, ask.cap_w1, ask.cap_w4, ask.cap_w16, ask.cap_wg, ask.coop_local);
+    max_hchunks = std::max(max_hchunks, local_level.n_hchunks);
+    max_huge = std::max(max_huge, local_level.n_huge);
+    n_special = (int)sp.size();
+    special_cols.upload(sp);
+    special_level.cols_all.upload(sp);
+    special_level.n_all = n_special;
+    special_level.contig = L.contig;
+    if (n_special) {
+      special_level.jmin = sp.front();
+      special_level.jmax = sp.back();
+      bin_columns(csc, sp, special_level, ask.cap_w1, ask.cap_w4, ask.cap_w16, ask.cap_wg, 0);
+      max_hchunks = std::max(max_hchunks, special_level.n_hchunks);
+      max_huge = std::max(max_huge, special_level.n_huge);
+    }
+  }
+
+  void build(const HostCsr &csc, int r_w16, int r_wg, int coop_max, bool allow_scatter = false, bool unit = false,
+             const StepPlan *twin = nullptr) {
+    const BuildAsk ask{csc, twin, ChainSwitches::read(), WAVE, 4 * WAVE, (int64_t)r_w16 * WAVE, (int64_t)r_wg * WG,
+                       sharded ? 0 : coop_max, coop_max, allow_scatter, unit};
+    n_state_rows = csc.cols;
+    {
+      std::vector<int32_t> r0((size_t)csc.rows, 0);
+      for (int64_t j = 0; j < csc.rows; j++)
+        if (csc.ptr[j + 1] > csc.ptr[j]) r0[j] = csc.idx[csc.ptr[j]];
+      col_row0.upload(r0);
+    }
+    const std::vector<int32_t> level = assign_levels(ask);
     std::vector<std::vector<int32_t>> by_level((size_t)n_levels);
     for (int64_t j = 0; j < csc.rows; j++) by_level[level[j]].push_back((int32_t)j);
     steps.clear();
     launches = 0;
-    std::vector<int32_t> run;
-    int64_t run_nnz = 0;
-    auto flush_run = [&]() {
-      if (run.empty()) return;
-      steps.emplace_back();
-      Step &s = steps.back();
-      s.is_chain = true;
-      {  // the twin has the same run at the same place: its arrays serve both sweeps
-        const size_t si = steps.size() - 1;
-        const Step *tw = twin && si < twin->steps.size() && twin->steps[si].is_chain ? &twin->steps[si] : nullptr;
-        if (tw && !sharded && !twin->sharded && tw->chain.h_cols == run) {
-          s.chain.borrow(tw->chain);
-          launches += 1;
-          run.clear();
-          run_nnz = 0;
-          return;
-        }
-      }
-      s.chain.h_cols = run;
-      s.chain.n_cols = (int)run.size();
-      s.chain.nnz = run_nnz;
-      s.chain.cols.upload(run);
-      {
-        std::vector<ChainDesc> d;
-        for (int32_t j : run) d.push_back(ChainDesc{csc.ptr[j], (int32_t)(csc.ptr[j + 1] - csc.ptr[j]), j});
-        s.chain.desc.upload(d.data(), d.size());
-      }
-      // state too large for the LDS chain of any policy: also keep the conflict-batched form
-      // (a main-table plan never launches the stream: building it, and skipping the conflict batches for it, would leave a long main
-      //  chain to the single-workgroup kernel)
-      const bool stream_allowed = block_plan && !env_flag("MFM_NO_CB_STREAM") && !env_flag("MFM_NO_CHAIN_GRID");
-      auto try_stream = [&]() {
-        CsStreamInfo ci;
-        s.chain.stream = cs_stream_build(csc, run, &ci);
-        if (env_flag("MFM_SETUP_TIMING")) {
-          if (s.chain.stream)
-            std::fprintf(stderr, "[plan] streamed chain of %zu columns: steps of %d columns, window %d steps, %d ranges, %d LDS slots, %lld cold + %lld "
-                                 "hot entries (<= %d hot per column), <= %d entering / %d leaving rows per step, planned in %.3f s\n",
-                         run.size(), ci.Cg, ci.Lw, ci.NB, ci.n_slots, ci.n_cold, ci.n_hot, ci.max_hot_col, ci.max_enter, ci.max_exit, ci.plan_seconds);
-          else
-            std::fprintf(stderr, "[plan] streamed chain of %zu columns: no window fits the LDS, conflict batches kept\n", run.size());
-        }
-      };
-      const bool chain_batched_wanted =
-          (csc.cols > 1900 || env_flag("MFM_CHAIN_FORCE_BATCHED")) && run.size() >= 2;
-      // Long columns (the cold parts of a batch would run on the whole GPU: relation blocks with 10^5..10^6 rows): the streamed form is
-      // tried FIRST, and when it can be built the conflict batches -- then never launched -- are not built at all (0.06 s of device
-      // work and ~100 MB per big block at config 5). The checker mode builds both: the batches' device / host comparison stays tested.
-      bool stream_tried = false;
-      if (chain_batched_wanted && stream_allowed && !env_flag("MFM_PLAN_CHECK") && !env_flag("MFM_CHAIN_FORCE_BATCHED") &&
-          run_nnz >= (int64_t)256 * (int64_t)run.size()) {
-        try_stream();
-        stream_tried = true;
-      }
-      if (chain_batched_wanted && !s.chain.stream) {
-        const int hot_cap = env_flag("MFM_CHAIN_HOT_CAP") ? std::max(64, env_int("MFM_CHAIN_HOT_CAP", 0)) : 1200;
-        // on the device when the matrix's CSC is there (relation blocks, the main table): the host form is the fall-back and,
-        // under MFM_PLAN_CHECK, the checker
-        const bool on_dev = dev_csc && s.chain.build_batched_device(*dev_csc, run, hot_cap);
-        if (env_flag("MFM_SETUP_TIMING"))
-          std::fprintf(stderr, "[plan] conflict batches of a %zu-column chain run: %s (%d batches, %lld cold entries)\n", run.size(),
-                       on_dev ? "device" : "host", on_dev ? s.chain.n_batches : -1, on_dev ? (long long)s.chain.n_cold : -1ll);
-        if (!on_dev) {
-          s.chain.build_batched(csc, run, hot_cap);
-        } else if (env_flag("MFM_PLAN_CHECK")) {
-          ChainRun chk;
-          chk.build_batched(csc, run, hot_cap);
-          const std::string diff = s.chain.compare_batched(chk, dev_csc->stream);
-          if (!diff.empty()) throw Error(MFM_ERR_RUNTIME, "plan check: device and host conflict batches differ (" + diff + ")");
-        }
-        // chains whose cold parts run on the whole GPU: the streamed form (unless it was tried above)
-        if (s.chain.bucketed && stream_allowed && !stream_tried) try_stream();
-      }
-      launches += 1;
-      run.clear();
-      run_nnz = 0;
-    };
-    for (int32_t l = 0; l < n_levels; l++) {
-      if (by_level[l].empty()) continue;
+    OpenRun open;
+    for (const std::vector<int32_t> &cols : by_level) {
+      if (cols.empty()) continue;
       int64_t lnnz = 0;
-      for (int32_t j : by_level[l]) lnnz += csc.ptr[j + 1] - csc.ptr[j];
-      if (!sharded && tiny(by_level[l].size(), lnnz)) {
-        for (int32_t j : by_level[l]) run.push_back(j);
-        run_nnz += lnnz;
+      for (int32_t j : cols) lnnz += csc.ptr[j + 1] - csc.ptr[j];
+      if (!sharded && tiny(cols.size(), lnnz)) {
+        open.cols.insert(open.cols.end(), cols.begin(), cols.end());
+        open.nnz += lnnz;
         continue;
       }
-      flush_run();
-      steps.emplace_back();
-      ParLevel &L = steps.back().par;
-      L.cols_all.upload(by_level[l]);
-      L.n_all = (int)by_level[l].size();
-      L.jmin = *std::min_element(by_level[l].begin(), by_level[l].end());
-      L.jmax = *std::max_element(by_level[l].begin(), by_level[l].end());
-      {
-        // the twin built this level on row tiles with the same boundaries: borrow it
-        const size_t si = steps.size() - 1;
-        const ParLevel *tw = twin && si < twin->steps.size() && !twin->steps[si].is_chain ? &twin->steps[si].par : nullptr;
-        if (allow_scatter && tw && tw->tiled && tw->tile_bits == tile_bits && tw->n_cols == (int)by_level[l].size() &&
-            tw->n_ent == lnnz && twin->aligned_tiles == aligned_tiles && twin->h_tile_start == h_tile_start && !sharded) {
-          L.borrow_tiled(*tw);
-          launches += 3;
-          max_cols_scat = std::max<int64_t>(max_cols_scat, csc.rows);
-          continue;
-        }
-      }
-      // first look at the level -- contiguous columns? far-apart rows? every row exactly once? -- on the device when the CSC is there
-      const bool want_once = steps.size() == 1 && lnnz == csc.cols;
-      LevelScan scan;
-      if (dev_csc) {
-        scan = level_scan_device(*dev_csc, L.cols_all.p, L.n_all, want_once);
-        if (scan.valid && env_flag("MFM_PLAN_CHECK")) {  // tests: the host's counts
-          int64_t gaps = 0, far = 0, twice = 0;
-          std::vector<char> seen(want_once ? (size_t)csc.cols : 0, 0);
-          for (int32_t j : by_level[l])
-            for (int64_t p = csc.ptr[j]; p < csc.ptr[j + 1]; p++) {
-              if (p > csc.ptr[j]) {
-                gaps += csc.idx[p] != csc.idx[p - 1] + 1;
-                far += (csc.idx[p] - csc.idx[p - 1]) >= 8;
-              }
-              if (want_once) {
-                twice += seen[csc.idx[p]];
-                seen[csc.idx[p]] = 1;
-              }
-            }
-          if (gaps != scan.gaps || far != scan.far || twice != scan.twice)
-            throw Error(MFM_ERR_RUNTIME, "plan check: device and host level scans differ");
-        }
-      }
-      if (allow_scatter && build_scattered(csc, by_level[l], lnnz, unit, L, (sharded && !sharded_tiles) ? 0 : tile_bits,
-                                           aligned_tiles ? &h_tile_start : nullptr, dev_csc, &scan)) {
-        launches += 3;
-        max_cols_scat = std::max<int64_t>(max_cols_scat, csc.rows);
-        continue;
-      }
-      if (want_once && scan.valid) {
-        L.first_and_once = scan.twice == 0;
-      } else if (want_once) {  // first step: does it touch every row exactly once?
-        std::vector<char> seen((size_t)csc.cols, 0);
-        bool once = true;
-        for (int32_t j : by_level[l])
-          for (int64_t p = csc.ptr[j]; once && p < csc.ptr[j + 1]; p++) {
-            once = !seen[csc.idx[p]];
-            seen[csc.idx[p]] = 1;
-          }
-        L.first_and_once = once;
-      }
-      bin_columns(csc, by_level[l], L, cap_w1, cap_w4, cap_w16, cap_wg, coop_max);
-      {
-        bool contig = !scan.valid || scan.gaps == 0;
-        for (size_t c = 0; !scan.valid && contig && c < by_level[l].size(); c++) {
-          const int32_t j = by_level[l][c];
-          for (int64_t p = csc.ptr[j] + 1; contig && p < csc.ptr[j + 1]; p++) contig = csc.idx[p] == csc.idx[p - 1] + 1;
-        }
-        L.contig = contig;
-      }
-      if (steps.size() == 1 && L.contig && L.first_and_once && allow_scatter && (!sharded || sharded_tiles) && tile_bits > 0)
-        build_aligned_tiles(csc, by_level[l], (int64_t)1 << tile_bits);
-      if (steps.size() == 1 && sharded_tiles && aligned_tiles) {
-        std::vector<int32_t> sp, loc;
-        for (int32_t j : by_level[l]) {
-          if (!special.empty() && special[j] == 1)
-            sp.push_back(j);
-          else if (csc.ptr[j + 1] > csc.ptr[j] || (!special.empty() && special[j] == 2))
-            loc.push_back(j);
-        }
-        local_level.cols_all.upload(loc);
-        local_level.n_all = (int)loc.size();
-        local_level.contig = L.contig;
-        bin_columns(csc, loc, local_level, cap_w1, cap_w4, cap_w16, cap_wg, coop_local);
-        max_hchunks = std::max(max_hchunks, local_level.n_hchunks);
-        max_huge = std::max(max_huge, local_level.n_huge);
-        n_special = (int)sp.size();
-        special_cols.upload(sp);
-        special_level.cols_all.upload(sp);
-        special_level.n_all = n_special;
-        special_level.contig = L.contig;
-        if (n_special) {
-          special_level.jmin = sp.front();
-          special_level.jmax = sp.back();
-          bin_columns(csc, sp, special_level, cap_w1, cap_w4, cap_w16, cap_wg, 0);
-          max_hchunks = std::max(max_hchunks, special_level.n_hchunks);
-          max_huge = std::max(max_huge, special_level.n_huge);
-        }
-      }
-      max_hchunks = std::max(max_hchunks, L.n_hchunks);
-      max_huge = std::max(max_huge, L.n_huge);
-      launches += ((L.n_w1 + L.n_w4) ? 1 : 0) + ((L.n_w16 + L.n_wg) ? 1 : 0) + (int64_t)L.rounds.size() + (L.n_huge ? 3 : 0);
+      add_chain_step(ask, std::exchange(open, OpenRun()));
+      add_par_step(ask, cols, lnnz);
     }
-    flush_run();
+    add_chain_step(ask, std::exchange(open, OpenRun()));
   }
 };
 
@@ -1841,8 +1875,8 @@ struct LongScratch {
   std::vector<DevBuf<double>> vnext_lvl;  // ... and per tile level: next factor's coefficient per column (MULTIQ)
   DevBuf<double2> cb_part, cb_oldnew;  // grid-batched chains: per-workgroup column partials, (old, new) per column of a batch
   DevBuf<double> cb_colpack;           // ... the batch's per-column scalars (old coefficient, variate, lambda, mu), packed
-  DevBuf<double2> cb_hot, cb_hot2;     // ... and the batch's hot records, packed (k_cb_stats -> k_cb_hot -> k_cb_apply; two: k_cb_step
-                                       //     reads the previous batch's while it packs the next one's)
+  DevBuf<double2> cb_hot, cb_hot2;     // ... and the batch's hot records, packed (two: the ranges scatter the previous batch's
+                                       //     while they pack the next one's)
   DevBuf<CbSync> cb_sync;              // ... the counters of the one-launch form (k_cb_persist), zeroed before every launch
   DevBuf<double2> dv_col;      // two-field pass: (delta of this factor, coefficient of the next) per second-level column
   void reserve_cols(int64_t n_cols) {
@@ -1921,6 +1955,152 @@ static inline bool plan_is_single_pass_par(const StepPlan &plan) {
   return !plan.steps.empty();
 }
 
+// ---- a CHAIN step: the LDS chain when the table's state fits, else the form the planner left in the run --------------------
+// The LDS test stays with the launch: the record size belongs to the policy.
+template <class P>
+static inline size_t chain_lds_bytes(int64_t n_state_rows) {
+  return (size_t)n_state_rows * (P::REC_DOUBLES > 2 ? P::REC_DOUBLES + 2 : P::REC_DOUBLES) * sizeof(double);
+}
+template <class P>
+static inline bool chain_fits_lds(int64_t n_state_rows) {
+  return n_state_rows > 0 && chain_lds_bytes<P>(n_state_rows) <= CHAIN_LDS_MAX;
+}
+
+// dynamic LDS of the batched forms' hot walk: hot records, five scalars per column, per-column sums ([n_sums] double2 each), the
+// batch's hot entries (value, slot), the columns' entry ranges
+template <class P>
+static inline size_t chain_hot_lds_bytes(const ChainRun &C, int n_sums) {
+  constexpr int rec2_l = P::REC_DOUBLES > 2 ? P::REC_DOUBLES / 2 + 1 : P::REC_DOUBLES / 2;
+  return (size_t)std::max(C.max_hot, 1) * rec2_l * sizeof(double2) + 5 * CHAINB_MAXCOLS * sizeof(double) +
+         (size_t)CHAINB_MAXCOLS * n_sums * sizeof(double2) + (size_t)std::max(C.max_hot_ent, 1) * 12 +
+         (CHAINB_MAXCOLS + 2) * sizeof(int);
+}
+template <class P>
+static void chain_batched_raise_lds() {  // beyond the default dynamic-LDS limit: opt in once per kernel
+  static DeviceOnce raised;
+  if (!raised.need()) return;
+  MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_batched<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHAIN_LDS_MAX));
+  MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_cb_persist<P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHAIN_LDS_MAX));
+  raised.mark();
+}
+
+// MFM_CB_PROF=n: phase sums of k_cb_persist's hot walker and of range 0 (s_memrealtime, thread 0), printed every n launches
+template <class P>
+struct CbProf {
+  static int every() {
+    static const int n = env_int("MFM_CB_PROF", 0);
+    return n;
+  }
+  static DevBuf<unsigned long long> &buf() {
+    static DevBuf<unsigned long long> b;
+    return b;
+  }
+  static unsigned long long *buffer() {  // null: not profiling
+    if (every() <= 0) return nullptr;
+    if (!buf().p) {
+      buf().alloc(16);
+      MFM_HIP_CHECK(hipMemset(buf().p, 0, 16 * sizeof(unsigned long long)));
+    }
+    return buf().p;
+  }
+  static void launched(hipStream_t s) {
+    static long launches = 0;
+    if (every() <= 0 || ++launches % every() != 0) return;
+    unsigned long long h[16];
+    MFM_HIP_CHECK(hipStreamSynchronize(s));
+    MFM_HIP_CHECK(hipMemcpy(h, buf().p, sizeof(h), hipMemcpyDeviceToHost));
+    MFM_HIP_CHECK(hipMemset(buf().p, 0, sizeof(h)));
+    const double nb = (double)std::max<unsigned long long>(h[4], 1), nr = (double)std::max<unsigned long long>(h[11], 1);
+    std::fprintf(stderr,
+                 "[k_cb_persist] %ld launches, us per batch -- hot walker (%llu batches): wait %.2f, stage in %.2f, walk %.2f, "
+                 "stage out + signal %.2f | range 0 (%llu): wait %.2f, near part %.2f, far part %.2f\n",
+                 launches, h[4], h[0] / nb / 100.0, h[1] / nb / 100.0, h[2] / nb / 100.0, h[3] / nb / 100.0, h[11], h[8] / nr / 100.0,
+                 h[9] / nr / 100.0, h[10] / nr / 100.0);
+  }
+};
+
+// k_cb_persist's arguments: the run's batches and row-bucketed copies, the scratch the walker and the ranges exchange through
+// (grown to this run's sizes), the group of every chain column (gathered once per group array)
+template <class P>
+static CbPersistArgs cb_persist_args(hipStream_t s, const ChainRun &C, const SweepArgs &a, LongScratch &ls) {
+  const size_t hot16 = (size_t)std::max(C.max_hot, 1) * (P::REC_DOUBLES / 2);
+  if (ls.cb_part.n < (size_t)CB_BUCKETS * CHAINB_MAXCOLS) ls.cb_part.alloc((size_t)CB_BUCKETS * CHAINB_MAXCOLS);
+  if (ls.cb_oldnew.n < (size_t)CHAINB_MAXCOLS) ls.cb_oldnew.alloc((size_t)CHAINB_MAXCOLS);
+  if (ls.cb_hot.n < hot16) ls.cb_hot.alloc(hot16);
+  if (ls.cb_hot2.n < hot16) ls.cb_hot2.alloc(hot16);
+  if (ls.cb_colpack.n < (size_t)8 * CHAINB_MAXCOLS) ls.cb_colpack.alloc((size_t)8 * CHAINB_MAXCOLS);
+  if (!ls.cb_sync.p) ls.cb_sync.alloc(1);
+  if (C.col_group.n < (size_t)C.n_cols || C.col_group_of != a.group) {
+    C.col_group.alloc((size_t)std::max(C.n_cols, 1));
+    hipLaunchKernelGGL(k_gather_i32, dim3((C.n_cols + 255) / 256), dim3(256), 0, s, a.group, C.cols.p, C.n_cols, C.col_group.p);
+    C.col_group_of = a.group;
+  }
+  CbPersistArgs g;
+  g.batches = C.batches.p;
+  g.n_batches = C.n_batches;
+  g.cols = C.cols.p;
+  g.col_group = C.col_group.p;
+  g.bk_ptr = C.bk_ptr.p;
+  g.bk_row = C.bk_row.p;
+  g.bk_lcol = C.bk_lcol.p;
+  g.hbk_ptr = C.hbk_ptr.p;
+  g.bk_cls = C.bk_cls.p;
+  g.hot_rows = C.hot_rows.p;
+  g.bk_x = C.bk_x.p;
+  g.hot_ptr = C.hot_ptr.p;
+  g.hot_slot = C.hot_slot.p;
+  g.hot_x = C.hot_x.p;
+  g.max_hot = std::max(C.max_hot, 1);
+  g.max_hot_ent = std::max(C.max_hot_ent, 1);
+  g.oldnew_g = ls.cb_oldnew.p;
+  g.part_g = ls.cb_part.p;
+  g.pack[0] = ls.cb_hot.p;
+  g.pack[1] = ls.cb_hot2.p;
+  g.colpack = ls.cb_colpack.p;
+  g.sync = ls.cb_sync.p;
+  g.error = ls.error.p;
+  g.prof = CbProf<P>::buffer();
+  return g;
+}
+
+template <class P>
+static void launch_chain(hipStream_t s, const ChainRun &C, int64_t n_state_rows, const SweepArgs &a, LongScratch &ls) {
+  if (chain_fits_lds<P>(n_state_rows) && !C.skip_lds) {
+    hipLaunchKernelGGL((k_chain_lds<P>), dim3(1), dim3(WAVE), chain_lds_bytes<P>(n_state_rows), s, a, C.desc.p, C.n_cols, n_state_rows,
+                       (int)P::REC_DOUBLES);
+    return;
+  }
+  switch (C.form) {
+    case ChainForm::Serial:
+      hipLaunchKernelGGL((k_chain<P>), dim3(1), dim3(CHAIN_WG), 0, s, a, C.desc.p, C.n_cols);
+      break;
+    case ChainForm::Batched:
+      chain_batched_raise_lds<P>();
+      hipLaunchKernelGGL((k_chain_batched<P>), dim3(1), dim3(CHAINB_NT), chain_hot_lds_bytes<P>(C, CHAINB_NT / WAVE), s, a, C.batches.p,
+                         C.n_batches, C.cols.p, C.cold_ptr.p, C.cold_row.p, C.cold_lcol.p, C.cold_x.p, C.hot_ptr.p, C.hot_slot.p, C.hot_x.p,
+                         C.hot_rows.p, std::max(C.max_hot, 1), std::max(C.max_hot_ent, 1));
+      break;
+    case ChainForm::Persist: {
+      // the whole batch sequence as one launch: the hot walker + CB_BUCKETS row-range workgroups, counters instead of kernel
+      // boundaries
+      chain_batched_raise_lds<P>();
+      const CbPersistArgs g = cb_persist_args<P>(s, C, a, ls);
+      MFM_HIP_CHECK(hipMemsetAsync(ls.cb_sync.p, 0, sizeof(CbSync), s));
+      const size_t lds_range = (size_t)CHAINB_MAXCOLS * (sizeof(double2) + 2 * sizeof(double)) +
+                               (size_t)CHAINB_MAXCOLS * (CHAINB_NT / WAVE) * sizeof(double2);
+      hipLaunchKernelGGL((k_cb_persist<P>), dim3(CB_BUCKETS + 1), dim3(CHAINB_NT), std::max(chain_hot_lds_bytes<P>(C, 1), lds_range), s, a, g);
+      CbProf<P>::launched(s);
+      break;
+    }
+    case ChainForm::Stream:  // one pipelined launch for the whole run (mfm_chain_stream.hpp); the planner builds it for relation blocks only
+      if constexpr (std::is_same<P, PBlockV>::value || std::is_same<P, PBlockW>::value)
+        cs_stream_launch(s, a, *C.stream, std::is_same<P, PBlockV>::value, ls.error.p);
+      else
+        throw Error(MFM_ERR_RUNTIME, "internal: streamed chain run outside a relation block");
+      break;
+  }
+}
+
 // PA: policy of the apply pass of scattered levels (differs from P only for the q-free policy)
 template <class P, bool UNIT, class PA = P>
 static void run_plan_t(hipStream_t s, Timing &tm, const StepPlan &plan, const SweepArgs &a, LongScratch &ls,
@@ -1928,145 +2108,7 @@ static void run_plan_t(hipStream_t s, Timing &tm, const StepPlan &plan, const Sw
   for (const Step &st : plan.steps) {
     if (st.is_chain) {
       TimedLaunch t(tm, s, kc.chain, P::BYTES * st.chain.nnz);
-      const size_t lds_bytes = (size_t)plan.n_state_rows * (P::REC_DOUBLES > 2 ? P::REC_DOUBLES + 2 : P::REC_DOUBLES) * sizeof(double);
-      const bool force_batched = st.chain.batched && env_flag("MFM_CHAIN_FORCE_BATCHED");
-      if (plan.n_state_rows > 0 && lds_bytes <= CHAIN_LDS_MAX && !force_batched) {
-        hipLaunchKernelGGL((k_chain_lds<P>), dim3(1), dim3(WAVE), lds_bytes, s, a, st.chain.desc.p, st.chain.n_cols,
-                           plan.n_state_rows, (int)P::REC_DOUBLES);
-      } else if (st.chain.stream && ls.error.p && (std::is_same<P, PBlockV>::value || std::is_same<P, PBlockW>::value)) {
-        // one pipelined launch for the whole run (mfm_chain_stream.hpp)
-        if constexpr (std::is_same<P, PBlockV>::value || std::is_same<P, PBlockW>::value)
-          cs_stream_launch(s, a, *st.chain.stream, std::is_same<P, PBlockV>::value, ls.error.p);
-      } else if (st.chain.batched) {
-        const ChainRun &C = st.chain;
-        constexpr int rec2_l = P::REC_DOUBLES > 2 ? P::REC_DOUBLES / 2 + 1 : P::REC_DOUBLES / 2;
-        const int mhe = std::max(C.max_hot_ent, 1);
-        const size_t lds_b = (size_t)std::max(C.max_hot, 1) * rec2_l * sizeof(double2) + 5 * CHAINB_MAXCOLS * sizeof(double) +
-                             (size_t)CHAINB_MAXCOLS * (CHAINB_NT / WAVE) * sizeof(double2) + (size_t)mhe * 12 +
-                             (CHAINB_MAXCOLS + 2) * sizeof(int);
-        static DeviceOnce raised;
-        if (raised.need()) {
-          MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_batched<P>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)CHAIN_LDS_MAX));
-          MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_cb_hot<P>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)CHAIN_LDS_MAX));
-          MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_cb_persist<P>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)CHAIN_LDS_MAX));
-          raised.mark();
-        }
-        // batches with many cold entries: cold statistics / updates as grid launches (one CU cannot stream them)
-        const int64_t grid_min = env_i64("MFM_CHAIN_GRID_MIN", 4096);
-        if (C.n_batches > 0 && C.n_cold / C.n_batches >= grid_min && !env_flag("MFM_NO_CHAIN_GRID")) {
-          constexpr int GMAX = 64;  // workgroups of a cold launch
-          if (ls.cb_part.n < (size_t)GMAX * CHAINB_MAXCOLS) ls.cb_part.alloc((size_t)GMAX * CHAINB_MAXCOLS);
-          if (ls.cb_oldnew.n < (size_t)CHAINB_MAXCOLS) ls.cb_oldnew.alloc((size_t)CHAINB_MAXCOLS);
-          const size_t hot16 = (size_t)std::max(C.max_hot, 1) * (P::REC_DOUBLES / 2);
-          if (ls.cb_hot.n < hot16) ls.cb_hot.alloc(hot16);
-          if (C.col_group.n < (size_t)C.n_cols || C.col_group_of != a.group) {  // group index per chain column (gathered once)
-            C.col_group.alloc((size_t)std::max(C.n_cols, 1));
-            hipLaunchKernelGGL(k_gather_i32, dim3((C.n_cols + 255) / 256), dim3(256), 0, s, a.group, C.cols.p, C.n_cols, C.col_group.p);
-            C.col_group_of = a.group;
-          }
-          const size_t lds_h = (size_t)std::max(C.max_hot, 1) * rec2_l * sizeof(double2) + 5 * CHAINB_MAXCOLS * sizeof(double) +
-                               (size_t)CHAINB_MAXCOLS * sizeof(double2) + (size_t)mhe * 12 + (CHAINB_MAXCOLS + 2) * sizeof(int);
-          if (C.bucketed) {
-            // two launches per batch: k_cb_step = cold update of the batch before + cold statistics of this one, by row range
-            if (ls.cb_hot2.n < hot16) ls.cb_hot2.alloc(hot16);
-            if (ls.cb_colpack.n < (size_t)8 * CHAINB_MAXCOLS) ls.cb_colpack.alloc((size_t)8 * CHAINB_MAXCOLS);
-            if (ls.cb_part.n < (size_t)CB_BUCKETS * CHAINB_MAXCOLS) ls.cb_part.alloc((size_t)CB_BUCKETS * CHAINB_MAXCOLS);
-            if (ls.error.p) {
-              // the whole batch sequence as one launch: the hot walker + CB_BUCKETS row-range workgroups, counters instead of
-              // kernel boundaries
-              if (!ls.cb_sync.p) ls.cb_sync.alloc(1);
-              MFM_HIP_CHECK(hipMemsetAsync(ls.cb_sync.p, 0, sizeof(CbSync), s));
-              CbPersistArgs g;
-              g.batches = C.batches.p;
-              g.n_batches = C.n_batches;
-              g.cols = C.cols.p;
-              g.col_group = C.col_group.p;
-              g.bk_ptr = C.bk_ptr.p;
-              g.bk_row = C.bk_row.p;
-              g.bk_lcol = C.bk_lcol.p;
-              g.hbk_ptr = C.hbk_ptr.p;
-              g.bk_cls = C.bk_cls.p;
-              g.hot_rows = C.hot_rows.p;
-              g.bk_x = C.bk_x.p;
-              g.hot_ptr = C.hot_ptr.p;
-              g.hot_slot = C.hot_slot.p;
-              g.hot_x = C.hot_x.p;
-              g.max_hot = std::max(C.max_hot, 1);
-              g.max_hot_ent = mhe;
-              g.oldnew_g = ls.cb_oldnew.p;
-              g.part_g = ls.cb_part.p;
-              g.pack[0] = ls.cb_hot.p;
-              g.pack[1] = ls.cb_hot2.p;
-              g.colpack = ls.cb_colpack.p;
-              g.sync = ls.cb_sync.p;
-              g.error = ls.error.p;
-              // MFM_CB_PROF=n: phase sums of the hot walker and of range 0 (s_memrealtime, thread 0), printed every n launches
-              static const int cb_prof = env_int("MFM_CB_PROF", 0);
-              static DevBuf<unsigned long long> prof_buf;
-              static long prof_launches = 0;
-              g.prof = nullptr;
-              if (cb_prof > 0) {
-                if (!prof_buf.p) {
-                  prof_buf.alloc(16);
-                  MFM_HIP_CHECK(hipMemset(prof_buf.p, 0, 16 * sizeof(unsigned long long)));
-                }
-                g.prof = prof_buf.p;
-              }
-              const size_t lds_range = (size_t)CHAINB_MAXCOLS * (sizeof(double2) + 2 * sizeof(double)) +
-                                       (size_t)CHAINB_MAXCOLS * (CHAINB_NT / WAVE) * sizeof(double2);
-              hipLaunchKernelGGL((k_cb_persist<P>), dim3(CB_BUCKETS + 1), dim3(CHAINB_NT), std::max(lds_h, lds_range), s, a, g);
-              if (cb_prof > 0 && ++prof_launches % cb_prof == 0) {
-                unsigned long long h[16];
-                MFM_HIP_CHECK(hipStreamSynchronize(s));
-                MFM_HIP_CHECK(hipMemcpy(h, prof_buf.p, sizeof(h), hipMemcpyDeviceToHost));
-                MFM_HIP_CHECK(hipMemset(prof_buf.p, 0, sizeof(h)));
-                const double nb = (double)std::max<unsigned long long>(h[4], 1), nr = (double)std::max<unsigned long long>(h[11], 1);
-                std::fprintf(stderr,
-                             "[k_cb_persist] %ld launches, us per batch -- hot walker (%llu batches): wait %.2f, stage in %.2f, walk %.2f, "
-                             "stage out + signal %.2f | range 0 (%llu): wait %.2f, near part %.2f, far part %.2f\n",
-                             prof_launches, h[4], h[0] / nb / 100.0, h[1] / nb / 100.0, h[2] / nb / 100.0, h[3] / nb / 100.0, h[11],
-                             h[8] / nr / 100.0, h[9] / nr / 100.0, h[10] / nr / 100.0);
-              }
-              continue;
-            }
-            const ChainBatch none{0, 0, 0, 0, 0, 0, 0, 0};
-            double2 *pack[2] = {ls.cb_hot.p, ls.cb_hot2.p};
-            for (int bi = 0; bi <= C.n_batches; bi++) {
-              const ChainBatch &Bp = bi > 0 ? C.h_batches[bi - 1] : none;
-              const ChainBatch &Bn = bi < C.n_batches ? C.h_batches[bi] : none;
-              hipLaunchKernelGGL((k_cb_step<P>), dim3(CB_BUCKETS), dim3(CHAINB_NT), 0, s, a, Bp, bi - 1, Bn, bi, C.cols.p, C.bk_ptr.p,
-                                 C.bk_row.p, C.bk_lcol.p, C.bk_x.p, C.hbk_ptr.p, C.hot_rows.p, ls.cb_oldnew.p, ls.cb_part.p,
-                                 pack[(bi + 1) & 1], pack[bi & 1], C.col_group.p, ls.cb_colpack.p);
-              if (bi < C.n_batches)
-                hipLaunchKernelGGL((k_cb_hot<P>), dim3(1), dim3(CHAINB_NT), lds_h, s, a, Bn, C.cols.p, C.hot_ptr.p, C.hot_slot.p,
-                                   C.hot_x.p, pack[bi & 1], C.col_group.p, std::max(C.max_hot, 1), mhe, ls.cb_part.p, CB_BUCKETS,
-                                   ls.cb_oldnew.p, ls.cb_colpack.p);
-            }
-            continue;
-          }
-          for (int bi = 0; bi < C.n_batches; bi++) {
-            const ChainBatch &B = C.h_batches[bi];
-            const int ncold = C.h_cold_cnt[bi];
-            const int g = std::max(1, std::min(GMAX, (ncold + CHAINB_NT * 4 - 1) / (CHAINB_NT * 4)));
-            hipLaunchKernelGGL((k_cb_stats<P>), dim3(g), dim3(CHAINB_NT), 0, s, a, B, C.cols.p, C.cold_ptr.p, C.cold_row.p,
-                               C.cold_lcol.p, C.cold_x.p, ls.cb_part.p, C.hot_rows.p, ls.cb_hot.p);
-            hipLaunchKernelGGL((k_cb_hot<P>), dim3(1), dim3(CHAINB_NT), lds_h, s, a, B, C.cols.p, C.hot_ptr.p, C.hot_slot.p,
-                               C.hot_x.p, ls.cb_hot.p, C.col_group.p, std::max(C.max_hot, 1), mhe, ls.cb_part.p, g, ls.cb_oldnew.p);
-            if (ncold || B.n_hot)
-              hipLaunchKernelGGL((k_cb_apply<P>), dim3(g), dim3(CHAINB_NT), 0, s, a, B, C.cold_ptr.p, C.cold_row.p,
-                                 C.cold_lcol.p, C.cold_x.p, ls.cb_oldnew.p, C.hot_rows.p, ls.cb_hot.p);
-          }
-          continue;
-        }
-        hipLaunchKernelGGL((k_chain_batched<P>), dim3(1), dim3(CHAINB_NT), lds_b, s, a, C.batches.p, C.n_batches, C.cols.p,
-                           C.cold_ptr.p, C.cold_row.p, C.cold_lcol.p, C.cold_x.p, C.hot_ptr.p, C.hot_slot.p, C.hot_x.p,
-                           C.hot_rows.p, std::max(C.max_hot, 1), mhe);
-      } else {
-        hipLaunchKernelGGL((k_chain<P>), dim3(1), dim3(CHAIN_WG), 0, s, a, st.chain.desc.p, st.chain.n_cols);
-      }
+      launch_chain<P>(s, st.chain, plan.n_state_rows, a, ls);
       continue;
     }
     const ParLevel &L = st.par;

@@ -557,6 +557,32 @@ def test_conflict_batched_chain(oracle, capi, monkeypatch, design, grid):
     np.testing.assert_allclose(c.get_e(), t.e(X.shape[0]), rtol=1e-7, atol=1e-7)
 
 
+def test_serial_chain_over_state_beyond_lds(oracle, capi):
+    # the plain chain (k_chain: one workgroup on global memory): 10 240 rows of 16-byte state are 163 840 B, above the LDS chain's
+    # 159 744 B, and the one column outside the one-hot field -- a tiny level of its own behind the field's -- is a chain run of a
+    # single column, which is never cut into conflict batches
+    rng = np.random.default_rng(29)
+    n, d, rank = 10240, 41, 3
+    field = rng.integers(0, 40, size=n)
+    extra = np.arange(0, n, 4)
+    rows = np.concatenate([np.arange(n), extra])
+    cols = np.concatenate([field, np.full(extra.size, 40)])
+    vals = np.concatenate([np.ones(n), np.round(rng.uniform(0.5, 1.5, size=extra.size), 2) + 0.25])
+    X = sps.csr_matrix((vals, (rows, cols)), shape=(n, d))
+    X.sort_indices()
+    y = ds.fm_score(X, 0.3, rng.normal(size=d) * 0.3, rng.normal(size=(d, rank)) * 0.3) + rng.normal(size=n) * 0.3
+    gi = np.concatenate([np.zeros(40, dtype=np.int32), np.ones(1, dtype=np.int32)])
+    t, c, _ = _pair(oracle, capi, X, y, gi, rank, ())
+    drv = CapiGibbs(c, t.clone(), n, gi)
+    for it in range(3):
+        t.step()
+        drv.step()
+        np.testing.assert_allclose(c.get_state()[2], t.fm()[2], rtol=1e-7, atol=1e-8)
+        np.testing.assert_allclose(c.get_state()[1], t.fm()[1], rtol=1e-7, atol=1e-8)
+    np.testing.assert_allclose(c.get_e(), t.e(n), rtol=1e-7, atol=1e-7)
+    assert "sweep_V_chain" in _timing_classes(c, drv)  # (the generic plan ran, with a chain step)
+
+
 @pytest.mark.parametrize("per_row", [3, 6])
 def test_conflict_batched_chain_many_batches(oracle, capi, monkeypatch, per_row):
     # the one-launch form of the grid-batched chains (k_cb_persist) classes a batch's cold entries by whether the batch before /
