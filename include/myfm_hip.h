@@ -495,6 +495,24 @@ int mfm_design_ess(mfm_design *d, int32_t rank, int32_t n_samples, const double 
 /* E(x) of one sequence on the host, by the scalar pieces the kernel runs and in its summation orders (no device): x[S],
  * 1 <= S <= 4096; NaN for S < 8 and where the halves do not vary                                                              */
 int mfm_ess_row(int32_t S, const double *x, double *out_ess, double *out_rhat);
+/* Several chains. The S samples are n_chains chains of L = S / n_chains draws each, chain after chain. Every chain is split as the
+ * one chain above is, n = L / 2: sequence 2m is the samples [mL, mL + n), sequence 2m + 1 the samples [mL + L - n, mL + L), and E
+ * compares the C = 2 n_chains sequences: A(t) is the mean of their autocovariances, V = A(0) + the variance (ddof = 1) of their
+ * means, ess = C n / tau. Ranks, the median, the mean and the standard deviation are taken over all S samples. n_chains = 1 is
+ * the entries above, bit for bit (they forward here). NaN where a chain has fewer than 8 draws. MFM_ERR_INVALID, before the
+ * device is used, beyond what the entries above refuse: n_chains < 1, n_chains > 32, S not a multiple of n_chains.             */
+int mfm_design_ess_chains_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t n_chains, int32_t kind,
+                                int32_t mode_or_task, const double *y, const double *precisions, int32_t n_cut,
+                                const double *cutpoints, int64_t tile_rows, int32_t chunk_samples, double *out0, double *out1,
+                                double *out2, double *out3);
+int mfm_design_ess_chains(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                          int32_t n_chains, int32_t kind, int32_t mode_or_task, const double *y, const double *precisions,
+                          int32_t n_cut, const double *cutpoints, int64_t tile_rows, int32_t chunk_samples, double *out0,
+                          double *out1, double *out2, double *out3);
+int mfm_ess_row_chains(int32_t S, int32_t n_chains, const double *x, double *out_ess, double *out_rhat);
+/* The three refusals of a chain count alone (no device; the message in mfm_global_error), and the largest count taken (32)    */
+int mfm_ess_check_chains(int32_t n_samples, int32_t n_chains);
+int32_t mfm_ess_max_chains(void);
 /* out[j] = Phi^-1((1 + j / 2 - 3 / 8) / (S + 1 / 4)), j = 0 .. 2S - 2: the rank-normalised value of the average rank 1 + j / 2 */
 int mfm_rank_z_table(int32_t S, double *out);
 

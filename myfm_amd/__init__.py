@@ -40,6 +40,8 @@ from .estimators import (  # noqa: E402
     TopKProbability,
     VariationalFMClassifier,
     VariationalFMRegressor,
+    combine_chains,
+    fit_chains,
 )
 
 __all__ = [
@@ -63,4 +65,6 @@ __all__ = [
     "SampleRankings",
     "ThompsonRanking",
     "TopKProbability",
+    "combine_chains",
+    "fit_chains",
 ]

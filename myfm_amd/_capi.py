@@ -49,6 +49,7 @@ SYMBOLS = [
     "mfm_design_logdens_store", "mfm_design_logdens", "mfm_logdens_value",
     "mfm_design_loo_store", "mfm_design_loo", "mfm_psis_row",
     "mfm_design_ess_store", "mfm_design_ess", "mfm_ess_row", "mfm_rank_z_table",
+    "mfm_design_ess_chains_store", "mfm_design_ess_chains", "mfm_ess_row_chains", "mfm_ess_check_chains", "mfm_ess_max_chains",
     "mfm_design_crps_store", "mfm_design_crps", "mfm_crps_row",
 ]
 
@@ -186,6 +187,11 @@ def lib():
     L.mfm_design_ess_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P, P]
     L.mfm_design_ess.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, i32, P, i64, i32, P, P, P, P]
     L.mfm_ess_row.argtypes = [i32, P, P, P]
+    L.mfm_design_ess_chains_store.argtypes = [vp, vp, i32, i32, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P, P]
+    L.mfm_design_ess_chains.argtypes = [vp, i32, i32, P, P, P, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P, P]
+    L.mfm_ess_row_chains.argtypes = [i32, i32, P, P, P]
+    L.mfm_ess_check_chains.argtypes = [i32, i32]
+    L.mfm_ess_max_chains.argtypes = []
     L.mfm_rank_z_table.argtypes = [i32, P]
     L.mfm_design_crps_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P]
     L.mfm_design_crps.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, P, P, P]
@@ -679,23 +685,24 @@ class Design:
         the tail of ceil(min(0.2 S, 3 sqrt(S / r_eff))) ratios smoothed (mfm_design_loo)."""
         return self._loo(_host(samples), task, y, precisions, cutpoints, log_weights, r_eff, tile_rows, chunk_samples)
 
-    def _ess(self, src, kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples):
+    def _ess(self, src, kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples, n_chains=1):
         if kind == 1:
             y, prec, n_cut, cp = self._log_density_args(y, precisions, cutpoints)
         else:  # (the value needs no targets; what it must not be given is the library's to refuse)
             _, prec, n_cut, cp = self._log_density_args(np.zeros(self.N), precisions, cutpoints)
             y = None
         out = [np.empty(self.N) for _ in range(4)]
-        self._ck(src.call("mfm_design_ess", self.h, int(kind), int(mode_or_task), _p(y), _p(prec), n_cut, _p(cp), int(tile_rows),
-                          int(chunk_samples), *[_p(o) for o in out]))
+        self._ck(src.call("mfm_design_ess_chains", self.h, int(n_chains), int(kind), int(mode_or_task), _p(y), _p(prec), n_cut, _p(cp),
+                          int(tile_rows), int(chunk_samples), *[_p(o) for o in out]))
         return tuple(out)
 
-    def ess(self, samples, kind, mode_or_task, y=None, precisions=None, cutpoints=None, tile_rows=0, chunk_samples=0):
-        """samples as predict. Chain diagnostics per row over the samples in their order (mfm_design_ess). kind 0, the prediction
+    def ess(self, samples, kind, mode_or_task, y=None, precisions=None, cutpoints=None, tile_rows=0, chunk_samples=0, n_chains=1):
+        """samples as predict. Chain diagnostics per row over the samples in their order, n_chains chains of equal length one after
+        another (mfm_design_ess_chains; one chain: what mfm_design_ess gives, bit for bit). kind 0, the prediction
         value of mode 0 score, 1 Phi(score), 2 the expected class index under cutpoints[S][n_cut]: (rhat[N], ess_bulk[N],
         ess_mean[N], mcse_mean[N]). kind 1, the likelihood of y with task, precisions and cutpoints as log_density: (rhat[N],
         ess_bulk[N], r_eff[N], mcse_lpd[N])."""
-        return self._ess(_host(samples), kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples)
+        return self._ess(_host(samples), kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples, n_chains)
 
     def _crps(self, src, task, y, precisions, cutpoints, tile_rows, chunk_samples):
         y, prec, n_cut, cp = self._log_density_args(y, precisions, cutpoints)
@@ -810,9 +817,10 @@ class Store:
         """Design.loo over the resident samples [first, first + count) (mfm_design_loo_store)"""
         return design._loo(_resident(self, first, count), task, y, precisions, cutpoints, log_weights, r_eff, tile_rows, chunk_samples)
 
-    def ess(self, design, kind, mode_or_task, y=None, precisions=None, cutpoints=None, first=0, count=None, tile_rows=0, chunk_samples=0):
-        """Design.ess over the resident samples [first, first + count) (mfm_design_ess_store)"""
-        return design._ess(_resident(self, first, count), kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples)
+    def ess(self, design, kind, mode_or_task, y=None, precisions=None, cutpoints=None, first=0, count=None, tile_rows=0, chunk_samples=0,
+            n_chains=1):
+        """Design.ess over the resident samples [first, first + count) (mfm_design_ess_chains_store)"""
+        return design._ess(_resident(self, first, count), kind, mode_or_task, y, precisions, cutpoints, tile_rows, chunk_samples, n_chains)
 
     def crps(self, design, task, y, precisions=None, cutpoints=None, first=0, count=None, tile_rows=0, chunk_samples=0):
         """Design.crps over the resident samples [first, first + count) (mfm_design_crps_store)"""
@@ -839,11 +847,12 @@ def crps_row(task, y, scores, precisions=None, cutpoints=None):
     return tuple(out)
 
 
-def ess_row(x):
-    """(ess, rhat) of one sequence of draws on the host, by the scalar pieces the device runs (mfm_ess_row)"""
+def ess_row(x, n_chains=1):
+    """(ess, rhat) of one sequence of draws on the host, n_chains chains of equal length one after another, by the scalar pieces the
+    device runs (mfm_ess_row_chains)"""
     x = _f64(x).reshape(-1)
     ess, rhat = C.c_double(), C.c_double()
-    rc = lib().mfm_ess_row(x.shape[0], _p(x), C.byref(ess), C.byref(rhat))
+    rc = lib().mfm_ess_row_chains(x.shape[0], int(n_chains), _p(x), C.byref(ess), C.byref(rhat))
     if rc:
         _raise(rc, lib().mfm_global_error())
     return ess.value, rhat.value

@@ -1059,6 +1059,31 @@ struct Predictor {
     }
     return out;
   }
+  // the predictor that keeps the samples of several, one predictor's after another's (host copies, as extended's): the chains of
+  // myfm_amd.combine_chains. Rank, feature size, task and the cutpoint counts must agree.
+  static Predictor concatenated(const vector<const Predictor *> &parts) {
+    if (parts.empty()) throw std::invalid_argument("concatenated: no predictor given");
+    const Predictor &p0 = *parts[0];
+    Predictor out(p0.rank, p0.feature_size, p0.type);
+    vector<size_t> cut_sizes;
+    bool have_cuts = false;
+    for (const Predictor *p : parts) {
+      if (p->rank != p0.rank || p->feature_size != p0.feature_size || p->type != p0.type)
+        throw std::invalid_argument("concatenated: the predictors differ in rank, feature size or task");
+      for (const FM &f0 : p->samples) {
+        const_cast<FM &>(f0).ensure();
+        const FM &f = f0;
+        if (f.w.size() != p0.feature_size || f.V.size() != p0.feature_size * p0.rank) throw std::invalid_argument("feature size mismatch!");
+        vector<size_t> sizes;
+        for (const auto &g : f.cutpoints) sizes.push_back(g.size());
+        if (have_cuts && sizes != cut_sizes) throw std::invalid_argument("concatenated: the samples differ in their cutpoint counts");
+        cut_sizes = sizes;
+        have_cuts = true;
+        out.samples.emplace_back(f.w0, f.w, f.V, (int)p0.rank, f.cutpoints);
+      }
+    }
+    return out;
+  }
   // ---- posterior predictive summaries (not in the reference): mean, standard deviation and quantiles over the samples -------
   // The quantile arguments of predict_dist and predict_dist_oprobit: the probabilities, 1-D, at most 32, each in [0, 1] (`open`:
   // with noise, strictly inside, checked value by value together with the range) ...
@@ -1269,25 +1294,30 @@ struct Predictor {
     return py::make_tuple(crps, accuracy, spread);
   }
   // Chain diagnostics over the kept samples in their order (not in the reference). The limit both kinds share:
-  void check_ess_limits() const {
+  void check_ess_limits(int n_chains) const {
     if (samples.size() > PSIS_MAX_SAMPLES)
       throw std::invalid_argument("chain diagnostics are computed over at most " + std::to_string(PSIS_MAX_SAMPLES) +
                                   " kept samples, this model keeps " + std::to_string(samples.size()));
+    // (the library's own refusals, asked for here because a design is made before the library sees the call, and that needs a device)
+    const int code = mfm_ess_check_chains((int32_t)samples.size(), (int32_t)n_chains);
+    if (code != MFM_OK) throw_code(code, mfm_global_error());
   }
   // (rhat[N], ess_bulk[N], ess_mean[N], mcse_mean[N]) of the value predict_dist summarises: the score (regression), Phi(score)
   // (classification), the expected class index under cutpoint group `cutpoint_idx` (ordered probit)
-  py::tuple predict_ess(const py::object &Xo, const py::object &relso, int64_t cutpoint_idx, int64_t tile_rows, int chunk_samples) const {
+  // the kept samples are n_chains chains of equal length, chain after chain
+  py::tuple predict_ess(const py::object &Xo, const py::object &relso, int64_t cutpoint_idx, int64_t tile_rows, int chunk_samples,
+                        int n_chains) const {
     Csr X = csr_from_py(Xo);
     Relations rels = relations_from_py(relso);
     check_input(X, rels);
     check_tiled_pass(tile_rows, chunk_samples);
-    check_ess_limits();
+    check_ess_limits(n_chains);
     Cutpoints cp;
     if (type == TaskType::ORDERED) cp = cutpoint_group(cutpoint_idx);
     const py::ssize_t N = (py::ssize_t)X.rows;
     py::array_t<double> rhat(N), bulk(N), mean(N), mcse(N);
     DeviceDesign dd(X, rels);
-    dd.ck(on_samples(mfm_design_ess_store, mfm_design_ess, dd.d, 0, static_cast<int32_t>(type), nullptr, nullptr, (int32_t)cp.n_cut,
+    dd.ck(on_samples(mfm_design_ess_chains_store, mfm_design_ess_chains, dd.d, (int32_t)n_chains, 0, static_cast<int32_t>(type), nullptr, nullptr, (int32_t)cp.n_cut,
                      cp.n_cut ? cp.cuts.data() : nullptr, tile_rows, (int32_t)chunk_samples, rhat.mutable_data(), bulk.mutable_data(),
                      mean.mutable_data(), mcse.mutable_data()));
     return py::make_tuple(rhat, bulk, mean, mcse);
@@ -1295,13 +1325,13 @@ struct Predictor {
   // (rhat[N], ess_bulk[N], r_eff[N], mcse_lpd[N]) of the likelihood exp(l_s - max_s l_s) that predict_loo weights by; the
   // arguments of density_args
   py::tuple likelihood_ess(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
-                           const py::object &cutpointso, int64_t tile_rows, int chunk_samples) const {
+                           const py::object &cutpointso, int64_t tile_rows, int chunk_samples, int n_chains) const {
     const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
-    check_ess_limits();
+    check_ess_limits(n_chains);
     const py::ssize_t N = (py::ssize_t)a.X.rows;
     py::array_t<double> rhat(N), bulk(N), reff(N), mcse(N);
     DeviceDesign dd(a.X, a.rels);
-    dd.ck(on_samples(mfm_design_ess_store, mfm_design_ess, dd.d, 1, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
+    dd.ck(on_samples(mfm_design_ess_chains_store, mfm_design_ess_chains, dd.d, (int32_t)n_chains, 1, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
                      a.cutpoints(), tile_rows, (int32_t)chunk_samples, rhat.mutable_data(), bulk.mutable_data(), reff.mutable_data(),
                      mcse.mutable_data()));
     return py::make_tuple(rhat, bulk, reff, mcse);
@@ -3122,10 +3152,12 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def("predict_crps", &Predictor::predict_crps, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
            py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+      .def_static("concatenated", &Predictor::concatenated, py::arg("predictors"))
       .def("predict_ess", &Predictor::predict_ess, py::arg("X"), py::arg("rels"), py::arg("cutpoint_index") = 0, py::arg("tile_rows") = 0,
-           py::arg("chunk_samples") = 0)
+           py::arg("chunk_samples") = 0, py::arg("n_chains") = 1)
       .def("likelihood_ess", &Predictor::likelihood_ess, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
-           py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+           py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0,
+           py::arg("n_chains") = 1)
       .def(py::pickle(
           [](const Predictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {
@@ -3141,6 +3173,15 @@ PYBIND11_MODULE(_myfm, m) {
       .def("create_Hyper", &FMTrainer::create_Hyper);
 
   py::class_<LearningHistory>(m, "LearningHistory")
+      // a history of given entries (myfm_amd.combine_chains: the kept samples' entries of several fits, one fit's after another's)
+      .def(py::init([](vector<Hyper> hypers, vector<Real> train_log_losses, vector<size_t> n_mh_accept) {
+             LearningHistory r;
+             r.hypers = std::move(hypers);
+             r.train_log_losses = std::move(train_log_losses);
+             r.n_mh_accept = std::move(n_mh_accept);
+             return r;
+           }),
+           py::arg("hypers"), py::arg("train_log_losses") = vector<Real>(), py::arg("n_mh_accept") = vector<size_t>())
       .def_readonly("hypers", &LearningHistory::hypers)
       .def_readonly("train_log_losses", &LearningHistory::train_log_losses)
       .def_readonly("n_mh_accept", &LearningHistory::n_mh_accept)
@@ -3388,17 +3429,20 @@ PYBIND11_MODULE(_myfm, m) {
       },
       py::arg("log_lik"), py::arg("r_eff") = 1.0);
 
-  // E of one sequence of draws on the host, by the scalar pieces k_row_ess runs on the device (csrc/mfm_ess.hpp): (ess, rhat)
+  m.attr("ESS_MAX_CHAINS") = (int)mfm_ess_max_chains();  // the most chains the diagnostics compare
+  // E of one sequence of draws on the host, n_chains chains of equal length one after another, by the scalar pieces k_row_ess runs
+  // on the device (csrc/mfm_ess.hpp): (ess, rhat)
   m.def(
       "ess_row",
-      [](const py::array_t<double, py::array::c_style | py::array::forcecast> &x) {
+      [](const py::array_t<double, py::array::c_style | py::array::forcecast> &x, int n_chains) {
         if (x.ndim() != 1 || x.shape(0) < 1) throw std::invalid_argument("x must be a non-empty 1-D array");
         double ess = 0.0, rhat = 0.0;
-        const int code = mfm_ess_row((int32_t)std::min<py::ssize_t>(x.shape(0), PSIS_MAX_SAMPLES + 1), x.data(), &ess, &rhat);
+        const int code =
+            mfm_ess_row_chains((int32_t)std::min<py::ssize_t>(x.shape(0), PSIS_MAX_SAMPLES + 1), (int32_t)n_chains, x.data(), &ess, &rhat);
         if (code != MFM_OK) throw_code(code, mfm_global_error());
         return py::make_tuple(ess, rhat);
       },
-      py::arg("x"));
+      py::arg("x"), py::arg("n_chains") = 1);
   // the CRPS of one row on the host, by the functions k_row_crps_mix / k_row_crps_cdf run on the device and in their summation
   // orders (csrc/mfm_crps.hpp): (crps, accuracy, spread)
   m.def(

@@ -9,6 +9,11 @@
 // runs in sample order and every sum over lags in lag order, so a row's result depends on its own samples alone: another row
 // tile, sample chunk, number of rows per workgroup or a rerun give the same bits. mfm_ess_row runs one sequence on the host
 // through the same scalar pieces in the same orders.
+//
+// Several chains: the S samples may be M chains of L = S / M draws each, chain after chain (n_chains of the *_chains entries). Each
+// chain is split as one chain is, n = L / 2: sequence 2m is x[mL .. mL + n), sequence 2m + 1 is x[mL + L - n .. mL + L), C = 2M
+// sequences in all; ranks, the median, the mean and the standard deviation are taken over all S draws. With M = 1 every operation
+// below is the one the single-chain form made, in its order: the same bits.
 #pragma once
 #include <algorithm>
 #include <numeric>
@@ -17,7 +22,8 @@
 
 namespace mfm {
 
-constexpr int ESS_MIN_HALF = 4;      // a half of fewer draws (S < 8) is not diagnosed: NaN
+constexpr int ESS_MIN_HALF = 4;      // a half of fewer draws (a chain of L < 8) is not diagnosed: NaN
+constexpr int ESS_MAX_CHAINS = 32;   // 2 x 32 sequences: a lane of the row's wavefront per sequence
 constexpr int ESS_MAX_ROWS = 32;     // rows per workgroup
 constexpr int ESS_LDS_BYTES = 64 * 1024;       // per workgroup, where more than one row fits
 constexpr int ESS_LDS_MAX_BYTES = 160 * 1024;  // what a workgroup of gfx950 can have: one row of DIST_MAX_S samples takes 114 784 B
@@ -29,24 +35,42 @@ constexpr int ESS_H_MAX = 0, ESS_H_MID_LO = 1, ESS_H_T = 2, ESS_H_R = 3, ESS_H_E
 // A half of equal values has d = 0 exactly, whatever the value (the sum of n copies of 0.1, divided by n, is not 0.1), and values
 // that lie close together keep their digits.
 __host__ __device__ __forceinline__ double ess_centered(double x, double x0, double m) { return (x - x0) - m; }
-// A(t) from the two halves' sums of d_i d_{i+t}: the mean of the biased autocovariances c_h(t) = sum / n
+// A(t) from the C sequences' sums of d_i d_{i+t}: the mean of the biased autocovariances c_h(t) = sum / n, added up in sequence
+// order, a chain's two halves at a time (acc starts at 0) ...
+__host__ __device__ __forceinline__ double ess_autocov_add(double acc, double sum_a, double sum_b, int n) {
+  return (acc + sum_a / (double)n) + sum_b / (double)n;
+}
+__host__ __device__ __forceinline__ double ess_autocov_mean(double acc, int C) { return acc / (double)C; }
+// ... of which one chain is the case C = 2, written out
 __host__ __device__ __forceinline__ double ess_autocov(double sum_a, double sum_b, int n) {
   return (sum_a / (double)n + sum_b / (double)n) / 2.0;
 }
-// W = A(0) n / (n - 1), V = A(0) + B with B the halves' means about their midpoint
+// W = A(0) n / (n - 1), V = A(0) + B with B the variance (ddof = 1) of the C sequences' means mean_of(c) about their mean, both sums
+// in sequence order
 __host__ __device__ __forceinline__ double ess_within(double A0, int n) { return A0 * (double)n / (double)(n - 1); }
-__host__ __device__ __forceinline__ double ess_total(double A0, double mu_a, double mu_b) {
+template <class MeanOf>
+__host__ __device__ __forceinline__ double ess_total(double A0, int C, const MeanOf &mean_of) {
+  double g = mean_of(0);
+  for (int c = 1; c < C; c++) g += mean_of(c);
+  g /= (double)C;
+  double B = (mean_of(0) - g) * (mean_of(0) - g);
+  for (int c = 1; c < C; c++) B += (mean_of(c) - g) * (mean_of(c) - g);
+  return A0 + B / (double)(C - 1);
+}
+__host__ __device__ __forceinline__ double ess_total(double A0, double mu_a, double mu_b) {  // (C = 2, written out)
   const double g = (mu_a + mu_b) / 2.0;
   return A0 + ((mu_a - g) * (mu_a - g) + (mu_b - g) * (mu_b - g));
 }
+// sequence c of a row of M chains of L draws, n = L / 2: where it starts
+__host__ __device__ __forceinline__ int ess_sequence_start(int c, int L, int n) { return (c >> 1) * L + ((c & 1) ? L - n : 0); }
 // no diagnosis: W is not > 0 (a constant half-pair) or not finite (a non-finite draw)
 __host__ __device__ __forceinline__ bool ess_within_ok(double W) { return W > 0.0 && W < __builtin_inf(); }
 __host__ __device__ __forceinline__ double ess_rho(double W, double A, double V) { return 1.0 - (W - A) / V; }
 // Geyer's initial positive sequence as Stan runs it: the loop goes on, and a pair is kept
 __host__ __device__ __forceinline__ bool ess_geyer_continue(int t, int n, double re, double ro) { return t < n - 5 && re + ro > 0.0; }
 __host__ __device__ __forceinline__ bool ess_geyer_keep(double re, double ro) { return re + ro >= 0.0; }
-// the floor of tau: ess <= 2n log10(2n)
-__host__ __device__ __forceinline__ double ess_tau_floor(int n) { return 1.0 / log10((double)(2 * n)); }
+// the floor of tau: ess <= draws log10(draws), draws = C n the draws that the sequences hold
+__host__ __device__ __forceinline__ double ess_tau_floor(int draws) { return 1.0 / log10((double)draws); }
 // the tie group at the sorted positions first .. last (0-based) has the average rank r = ((first + 1) + (last + 1)) / 2, a
 // multiple of 1/2: its z is table[2r - 2]
 __host__ __device__ __forceinline__ int ess_tie_table_index(int first, int last) { return first + last; }
@@ -84,8 +108,8 @@ __host__ __device__ __forceinline__ bool ess_geyer_advance(EssGeyer &g, int n, i
   }
   return true;
 }
-// ... and what follows it on rho[0 .. T]: the monotone sequence, tau in lag order and its floor. ess = 2n / tau.
-__host__ __device__ __forceinline__ double ess_from_rho(double *rho, int T, int n) {
+// ... and what follows it on rho[0 .. T]: the monotone sequence, tau in lag order and its floor. ess = draws / tau.
+__host__ __device__ __forceinline__ double ess_from_rho_of(double *rho, int T, int draws) {
   for (int t = 0; t <= T - 4;) {
     t += 2;
     const double prev = rho[t - 2] + rho[t - 1];
@@ -94,10 +118,12 @@ __host__ __device__ __forceinline__ double ess_from_rho(double *rho, int T, int 
   double sum = 0.0;
   for (int t = 0; t < T; t++) sum += rho[t];
   double tau = -1.0 + 2.0 * sum + rho[T];
-  const double floor_tau = ess_tau_floor(n);
+  const double floor_tau = ess_tau_floor(draws);
   if (tau < floor_tau) tau = floor_tau;
-  return (double)(2 * n) / tau;
+  return (double)draws / tau;
 }
+// one chain: its two halves of n draws
+__host__ __device__ __forceinline__ double ess_from_rho(double *rho, int T, int n) { return ess_from_rho_of(rho, T, 2 * n); }
 
 struct RowEssArgs {
   const double *scratch;  // [S][Tn] the tile's scores
@@ -110,6 +136,8 @@ struct RowEssArgs {
   int n_aux, aux_lds;     // the constants, in doubles, and whether they are staged in LDS behind the rows
   int P, R;               // S padded to a power of two, rows per workgroup
   int st, stv;            // doubles per row of v and z (S | 1) and of the sort buffer (P | 1): odd, the row-per-lane phases are conflict-free
+  int M;                  // the chains the S samples are, chain after chain (S % M == 0, M <= ESS_MAX_CHAINS); last: the single-chain
+                          // kernels, which do not read it, find every other argument where it was before chains were known
 };
 
 // LDS, in doubles: hdr[R][ESS_HDR], the values v[R][st], the work buffer z[R][st], the sort buffer sv[R][stv], the sample indices
@@ -185,6 +213,77 @@ __device__ __forceinline__ void ess_rows_truncate(const double *x, int xs, doubl
   }
 }
 
+// E for the rows of a workgroup up to Geyer's truncation, several chains: as ess_rows_truncate above with C = 2M sequences. Lanes
+// 0 .. C - 1 add up the sequences' means, a sequence per lane; lane j then owns lag t0 + j of a batch of 64 and walks the chains in
+// their order, and within a chain i in sample order for its two halves (x_i at one LDS address for all lanes: a broadcast; x_{i+t}
+// at consecutive addresses). A sequence's first draw is read from the row and its mean comes by shuffle from the lane that added it
+// up, outside the lanes' own loops: every lane of the wavefront takes part in a shuffle. At M = 1 every operation is the one
+// ess_rows_truncate makes, in its order (the same bits); the single-chain form is kept beside this one because this text ran the
+// single-chain calls 0.2 to 0.9 ms (up to 2.7 %) above the parent's range in four of six instantiations (Measured;
+// profiles/diagnostics_chains_bench.txt).
+__device__ __forceinline__ void ess_rows_truncate_chains(const double *x, int xs, double *rho, int rs, double *hdr, int R, int nr, int S,
+                                                  int M, bool want_ess) {
+  const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+  const int L = S / M, n = L / 2, C = 2 * M;
+  for (int rb = 0; rb < R; rb += WG / WAVE) {
+    const int r = rb + wave;
+    if (r >= nr) continue;  // (one value for the wavefront)
+    const double *xr = x + (size_t)r * xs;
+    double *rr = rho + (size_t)r * rs, *h = hdr + r * ESS_HDR;
+    double mu = 0.0, mean = 0.0;  // of lane c's sequence: shifted by its first draw, and itself
+    if (lane < C) {
+      const double *seq = xr + ess_sequence_start(lane, L, n);
+      const double x0 = seq[0];
+      double sum = 0.0;
+      for (int i = 0; i < n; i++) sum += seq[i] - x0;
+      mu = sum / (double)n;
+      mean = x0 + mu;
+    }
+    EssGeyer g{0, 1.0, 0.0};
+    double W = 0.0, V = 0.0;
+    bool done = false, ok = true;
+    for (int t0 = 0; t0 < n && !done; t0 += WAVE) {
+      const int t = t0 + lane;
+      const int m = t < n && (want_ess || t == 0) ? n - t : 0;  // (a lane without a lag adds up nothing: A = 0)
+      double acc = 0.0;
+      for (int ch = 0; ch < M; ch++) {
+        const double *xa = xr + ch * L, *xb = xa + (L - n);
+        const double x0_a = xa[0], x0_b = xb[0];
+        const double mu_a = __shfl(mu, 2 * ch), mu_b = __shfl(mu, 2 * ch + 1);
+        double sa = 0.0, sb = 0.0;
+        for (int i = 0; i < m; i++) {
+          sa += ess_centered(xa[i], x0_a, mu_a) * ess_centered(xa[i + t], x0_a, mu_a);
+          sb += ess_centered(xb[i], x0_b, mu_b) * ess_centered(xb[i + t], x0_b, mu_b);
+        }
+        acc = ess_autocov_add(acc, sa, sb, n);
+      }
+      const double A = ess_autocov_mean(acc, C);
+      if (t0 == 0) {
+        const double A0 = __shfl(A, 0);
+        W = ess_within(A0, n);
+        V = ess_total(A0, C, [&](int c) { return __shfl(mean, c); });
+        ok = ess_within_ok(W);
+        if (!ok || !want_ess) break;
+        g.ro = ess_rho(W, __shfl(A, 1), V);
+        if (lane == 0) {
+          rr[0] = g.re;
+          rr[1] = g.ro;
+        }
+      }
+      done = ess_geyer_advance(
+          g, n, t0 + WAVE < n ? t0 + WAVE : n, W, V, [&](int tt) { return __shfl(A, tt - t0); },
+          [&](int tt, double value) {
+            if (lane == 0) rr[tt] = value;
+          });
+    }
+    if (lane == 0) {
+      if (ok && want_ess && g.re > 0.0) rr[g.t] = g.re;
+      h[ESS_H_T] = ok ? (double)g.t : -1.0;
+      h[ESS_H_R] = ok ? sqrt(V / W) : __builtin_nan("");
+    }
+  }
+}
+
 // the bitonic network of k_row_psis over the (value, sample index) pairs of all R rows, P = S padded with +inf
 __device__ __forceinline__ void ess_rows_sort(double *sv, int stv, int *idx, int P, int R) {
   const int tid = threadIdx.x, half = P >> 1;
@@ -218,23 +317,24 @@ __device__ __forceinline__ void ess_rows_sort(double *sv, int stv, int *idx, int
 //       E on z, rho in the sort buffer, finished by a lane per row;
 //   (d) |v - med| (ess_folded) into the sort buffer, sorted and ranked in the same way, and E's lag 0 on its z, for R alone;
 //   (e) a lane per row takes the mean and the standard deviation (ddof = 1) of v in sample order and stores the four outputs.
-// S < 8: NaN and nothing else.
-template <int KIND, int SUB>
+// A chain of fewer than 8 draws (S / M < 8): NaN and nothing else.
+// CHAINS: the samples are a.M chains (ess_rows_truncate_chains); else one chain, the text as it was before chains were known.
+template <int KIND, int SUB, bool CHAINS>
 __global__ __launch_bounds__(WG) void k_row_ess(RowEssArgs a) {
   extern __shared__ double ess_lds[];
-  const int S = a.S, R = a.R, st = a.st, stv = a.stv, P = a.P, n_cut = a.n_cut;
+  const int S = a.S, M = CHAINS ? a.M : 1, R = a.R, st = a.st, stv = a.stv, P = a.P, n_cut = a.n_cut;
   const int64_t r0 = (int64_t)blockIdx.x * R;
   const int nr = (int)(a.Tn - r0 < R ? a.Tn - r0 : R);
   const int tid = threadIdx.x;
   const double nan = __builtin_nan("");
-  if (S < 2 * ESS_MIN_HALF) {
+  if (S / M < 2 * ESS_MIN_HALF) {
     if (tid < nr) a.out0[r0 + tid] = a.out1[r0 + tid] = a.out2[r0 + tid] = a.out3[r0 + tid] = nan;
     return;
   }
   double *hdr = ess_lds, *v = hdr + (size_t)R * ESS_HDR, *z = v + (size_t)R * st, *sv = z + (size_t)R * st;
   int *idx = reinterpret_cast<int *>(sv + (size_t)R * stv);
   double *staged = sv + (size_t)R * stv + (size_t)R * ((P + 1) / 2);
-  const int n = S / 2;
+  const int n = S / 2, draws = 2 * M * (S / M / 2);  // a half of one chain; the draws that the 2M sequences hold
   constexpr bool HAS_AUX = (KIND == 0 && SUB == 2) || (KIND == 1 && SUB != LOGDENS_CLASSIFICATION);
   const bool use_staged = HAS_AUX && a.aux_lds;
   if (use_staged) {
@@ -288,11 +388,19 @@ __global__ __launch_bounds__(WG) void k_row_ess(RowEssArgs a) {
     __syncthreads();
   }
   // (b)
-  ess_rows_truncate(v, st, z, st, hdr, R, nr, S, true);
+  if constexpr (CHAINS)
+    ess_rows_truncate_chains(v, st, z, st, hdr, R, nr, S, M, true);
+  else
+    ess_rows_truncate(v, st, z, st, hdr, R, nr, S, true);
   __syncthreads();
   if (tid < nr) {
     double *h = hdr + tid * ESS_HDR;
-    h[ESS_H_ESS_MEAN] = h[ESS_H_T] < 0.0 ? nan : ess_from_rho(z + tid * st, (int)h[ESS_H_T], n);
+    if (h[ESS_H_T] < 0.0)
+      h[ESS_H_ESS_MEAN] = nan;
+    else if constexpr (CHAINS)
+      h[ESS_H_ESS_MEAN] = ess_from_rho_of(z + tid * st, (int)h[ESS_H_T], draws);
+    else
+      h[ESS_H_ESS_MEAN] = ess_from_rho(z + tid * st, (int)h[ESS_H_T], n);
   }
   __syncthreads();
   // (c) and (d)
@@ -331,11 +439,19 @@ __global__ __launch_bounds__(WG) void k_row_ess(RowEssArgs a) {
       }
     }
     __syncthreads();
-    ess_rows_truncate(z, st, sv, stv, hdr, R, nr, S, pass == 0);
+    if constexpr (CHAINS)
+      ess_rows_truncate_chains(z, st, sv, stv, hdr, R, nr, S, M, pass == 0);
+    else
+      ess_rows_truncate(z, st, sv, stv, hdr, R, nr, S, pass == 0);
     __syncthreads();
     if (pass == 0 && tid < nr) {
       double *h = hdr + tid * ESS_HDR;
-      h[ESS_H_ESS_BULK] = h[ESS_H_T] < 0.0 ? nan : ess_from_rho(sv + tid * stv, (int)h[ESS_H_T], n);
+      if (h[ESS_H_T] < 0.0)
+        h[ESS_H_ESS_BULK] = nan;
+      else if constexpr (CHAINS)
+        h[ESS_H_ESS_BULK] = ess_from_rho_of(sv + tid * stv, (int)h[ESS_H_T], draws);
+      else
+        h[ESS_H_ESS_BULK] = ess_from_rho(sv + tid * stv, (int)h[ESS_H_T], n);
       h[ESS_H_R_BULK] = h[ESS_H_R];
     }
     __syncthreads();
@@ -364,15 +480,15 @@ __global__ __launch_bounds__(WG) void k_row_ess(RowEssArgs a) {
   }
 }
 
-template <int KIND, int SUB>
+template <int KIND, int SUB, bool CHAINS>
 static void launch_row_ess_form(hipStream_t s, const RowEssArgs &a, size_t lds) {
   static DeviceOnce raised;
   if (lds > 64 * 1024 && raised.need()) {  // above the default limit of dynamic LDS (opted into once per device)
-    void (*const kernel)(RowEssArgs) = k_row_ess<KIND, SUB>;
+    void (*const kernel)(RowEssArgs) = k_row_ess<KIND, SUB, CHAINS>;
     MFM_HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ESS_LDS_MAX_BYTES));
     raised.mark();
   }
-  hipLaunchKernelGGL((k_row_ess<KIND, SUB>), dim3((unsigned)cdiv(a.Tn, a.R)), dim3(WG), lds, s, a);
+  hipLaunchKernelGGL((k_row_ess<KIND, SUB, CHAINS>), dim3((unsigned)cdiv(a.Tn, a.R)), dim3(WG), lds, s, a);
 }
 // Sized next to launch_row_psis' arithmetic: R rows of 9 + 2 (S | 1) + (P | 1) + P / 2 doubles within ESS_LDS_BYTES, at most
 // ESS_MAX_ROWS and never less than one row (S = 95: 392 doubles, R = 20; S = 1024: 3 596, R = 2; S = 4096: 14 348 doubles =
@@ -392,9 +508,9 @@ static void launch_row_ess(hipStream_t s, int kind, int sub, RowEssArgs &a) {
   logdens_with_task(sub, [&](auto sub_c) {
     constexpr int SUB = decltype(sub_c)::value;
     if (kind == 0)
-      launch_row_ess_form<0, SUB>(s, a, lds);
+      a.M > 1 ? launch_row_ess_form<0, SUB, true>(s, a, lds) : launch_row_ess_form<0, SUB, false>(s, a, lds);
     else
-      launch_row_ess_form<1, SUB>(s, a, lds);
+      a.M > 1 ? launch_row_ess_form<1, SUB, true>(s, a, lds) : launch_row_ess_form<1, SUB, false>(s, a, lds);
   });
 }
 
@@ -403,27 +519,35 @@ static void ess_rank_z_table(int S, double *out) {
   for (int j = 0; j < 2 * S - 1; j++) out[j] = mfm_std_normal_quantile((1.0 + (double)j / 2.0 - 0.375) / ((double)S + 0.25));
 }
 
-// E of one sequence on the host, sequentially, through the scalar pieces and in the summation orders of k_row_ess
-static void ess_row_host(int S, const double *x, double *out_ess, double *out_rhat) {
+// E of one sequence of M chains on the host, sequentially, through the scalar pieces and in the summation orders of k_row_ess
+static void ess_row_host(int S, int M, const double *x, double *out_ess, double *out_rhat) {
   const double nan = std::numeric_limits<double>::quiet_NaN();
   *out_ess = *out_rhat = nan;
-  const int n = S / 2;
+  const int L = S / M, n = L / 2, C = 2 * M;
   if (n < ESS_MIN_HALF) return;
-  const double *xa = x, *xb = x + (S - n);
-  const double x0_a = xa[0], x0_b = xb[0];
-  double sum_a = 0.0, sum_b = 0.0;
-  for (int i = 0; i < n; i++) sum_a += xa[i] - x0_a;
-  for (int i = 0; i < n; i++) sum_b += xb[i] - x0_b;
-  const double mu_a = sum_a / (double)n, mu_b = sum_b / (double)n;  // (of the shifted halves)
+  std::vector<double> mu((size_t)C), mean((size_t)C);  // of the shifted sequences, and of the sequences
+  for (int c = 0; c < C; c++) {
+    const double *seq = x + ess_sequence_start(c, L, n);
+    double sum = 0.0;
+    for (int i = 0; i < n; i++) sum += seq[i] - seq[0];
+    mu[(size_t)c] = sum / (double)n;
+    mean[(size_t)c] = seq[0] + mu[(size_t)c];
+  }
   const auto A = [&](int t) {
-    double sa = 0.0, sb = 0.0;
-    for (int i = 0; i < n - t; i++) {
-      sa += ess_centered(xa[i], x0_a, mu_a) * ess_centered(xa[i + t], x0_a, mu_a);
-      sb += ess_centered(xb[i], x0_b, mu_b) * ess_centered(xb[i + t], x0_b, mu_b);
+    double acc = 0.0;
+    for (int ch = 0; ch < M; ch++) {
+      const double *xa = x + ch * L, *xb = xa + (L - n);
+      const double x0_a = xa[0], x0_b = xb[0], mu_a = mu[(size_t)(2 * ch)], mu_b = mu[(size_t)(2 * ch + 1)];
+      double sa = 0.0, sb = 0.0;
+      for (int i = 0; i < n - t; i++) {
+        sa += ess_centered(xa[i], x0_a, mu_a) * ess_centered(xa[i + t], x0_a, mu_a);
+        sb += ess_centered(xb[i], x0_b, mu_b) * ess_centered(xb[i + t], x0_b, mu_b);
+      }
+      acc = ess_autocov_add(acc, sa, sb, n);
     }
-    return ess_autocov(sa, sb, n);
+    return ess_autocov_mean(acc, C);
   };
-  const double A0 = A(0), W = ess_within(A0, n), V = ess_total(A0, x0_a + mu_a, x0_b + mu_b);
+  const double A0 = A(0), W = ess_within(A0, n), V = ess_total(A0, C, [&](int c) { return mean[(size_t)c]; });
   if (!ess_within_ok(W)) return;
   std::vector<double> rho((size_t)n + 2, 0.0);
   EssGeyer g{0, 1.0, ess_rho(W, A(1), V)};
@@ -431,13 +555,22 @@ static void ess_row_host(int S, const double *x, double *out_ess, double *out_rh
   rho[1] = g.ro;
   ess_geyer_advance(g, n, n, W, V, A, [&](int t, double value) { rho[(size_t)t] = value; });
   if (g.re > 0.0) rho[(size_t)g.t] = g.re;
-  *out_ess = ess_from_rho(rho.data(), g.t, n);
+  *out_ess = ess_from_rho_of(rho.data(), g.t, C * n);
   *out_rhat = std::sqrt(V / W);
 }
 
 // The checks of a diagnostics call; nothing here touches the device. The call is a LogdensCall whose task is the likelihood's task
 // (kind 1) or the value's mode (kind 0), and whose out_lpd / out_mean / out_var are the first three outputs.
-static void ess_check(int32_t kind, const LogdensCall &c, const double *out3, int64_t N, int count) {
+static void ess_check_chains(int32_t n_chains, int count) {
+  if (n_chains < 1) throw Error(MFM_ERR_INVALID, "n_chains must be at least 1, got " + std::to_string(n_chains));
+  if (n_chains > ESS_MAX_CHAINS)
+    throw Error(MFM_ERR_INVALID, "chain diagnostics combine at most " + std::to_string(ESS_MAX_CHAINS) + " chains, got " + std::to_string(n_chains));
+  if (count % n_chains != 0)
+    throw Error(MFM_ERR_INVALID, "the chains must be of equal length: " + std::to_string(count) + " samples are not a multiple of n_chains = " +
+                                     std::to_string(n_chains));
+}
+static void ess_check(int32_t kind, const LogdensCall &c, const double *out3, int64_t N, int count, int32_t n_chains) {
+  ess_check_chains(n_chains, count);
   if (kind < 0 || kind > 1) throw Error(MFM_ERR_INVALID, "bad kind (0: the prediction value, 1: the likelihood)");
   if (kind == 1) {
     logdens_check(c, N, count);
@@ -459,7 +592,7 @@ static void ess_check(int32_t kind, const LogdensCall &c, const double *out3, in
     throw Error(MFM_ERR_INVALID, "chain diagnostics are computed over at most " + std::to_string(DIST_MAX_S) + " samples, got " + std::to_string(count));
 }
 
-static void design_ess(mfm_design *d, const SampleView &v, int32_t kind, const LogdensCall &c, double *out3) {
+static void design_ess(mfm_design *d, const SampleView &v, int32_t kind, const LogdensCall &c, double *out3, int32_t n_chains) {
   const int count = v.count();
   check_sample_source(d, v);
   hipStream_t s = d->stream;
@@ -486,6 +619,7 @@ static void design_ess(mfm_design *d, const SampleView &v, int32_t kind, const L
   a.n_aux = (int)k.n_aux;
   a.table = d->dist_out.p + 4 * N;
   a.S = count;
+  a.M = n_chains;
   a.n_cut = c.task == 2 ? c.n_cut : 0;
   const auto stage2 = [&](int64_t r0, int64_t Tn) {
     a.Tn = Tn;
@@ -503,42 +637,74 @@ static void design_ess(mfm_design *d, const SampleView &v, int32_t kind, const L
 
 extern "C" {
 
-int mfm_design_ess_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t kind, int32_t mode_or_task, const double *y,
-                         const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows, int32_t chunk_samples,
-                         double *out0, double *out1, double *out2, double *out3) {
+int mfm_design_ess_chains_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t n_chains, int32_t kind, int32_t mode_or_task,
+                                const double *y, const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
+                                int32_t chunk_samples, double *out0, double *out1, double *out2, double *out3) {
   MFM_TRY(d)
   const LogdensCall c{mode_or_task, y, precisions, n_cut, cutpoints, tile_rows, chunk_samples, out0, out1, out2, nullptr, nullptr};
-  ess_check(kind, c, out3, d->N, std::max(count, 0));
-  design_ess(d, samples_of_store(st, first, count), kind, c, out3);
+  ess_check(kind, c, out3, d->N, std::max(count, 0), n_chains);
+  design_ess(d, samples_of_store(st, first, count), kind, c, out3, n_chains);
   MFM_CATCH(d)
 }
 
 // host samples: checked, then all S uploaded for this call under the rule of mfm_design_summary
-int mfm_design_ess(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t kind,
-                   int32_t mode_or_task, const double *y, const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
-                   int32_t chunk_samples, double *out0, double *out1, double *out2, double *out3) {
+int mfm_design_ess_chains(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t n_chains,
+                          int32_t kind, int32_t mode_or_task, const double *y, const double *precisions, int32_t n_cut, const double *cutpoints,
+                          int64_t tile_rows, int32_t chunk_samples, double *out0, double *out1, double *out2, double *out3) {
   MFM_TRY(d)
   const LogdensCall c{mode_or_task, y, precisions, n_cut, cutpoints, tile_rows, chunk_samples, out0, out1, out2, nullptr, nullptr};
-  ess_check(kind, c, out3, d->N, std::max(n_samples, 0));
+  ess_check(kind, c, out3, d->N, std::max(n_samples, 0), n_chains);
   store_check_fraction(d->D, rank, n_samples);
-  design_ess(d, samples_of_host(d->device, d->D, rank, n_samples, w0s, ws, Vs), kind, c, out3);
+  design_ess(d, samples_of_host(d->device, d->D, rank, n_samples, w0s, ws, Vs), kind, c, out3, n_chains);
   MFM_CATCH(d)
 }
 
-// E of one sequence on the host, by the scalar pieces the kernel runs (no device): x[S]; S < 8 gives NaN
-int mfm_ess_row(int32_t S, const double *x, double *out_ess, double *out_rhat) {
+// one chain
+int mfm_design_ess_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t kind, int32_t mode_or_task, const double *y,
+                         const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows, int32_t chunk_samples,
+                         double *out0, double *out1, double *out2, double *out3) {
+  return mfm_design_ess_chains_store(d, st, first, count, 1, kind, mode_or_task, y, precisions, n_cut, cutpoints, tile_rows, chunk_samples, out0,
+                                     out1, out2, out3);
+}
+int mfm_design_ess(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t kind,
+                   int32_t mode_or_task, const double *y, const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
+                   int32_t chunk_samples, double *out0, double *out1, double *out2, double *out3) {
+  return mfm_design_ess_chains(d, rank, n_samples, w0s, ws, Vs, 1, kind, mode_or_task, y, precisions, n_cut, cutpoints, tile_rows, chunk_samples,
+                               out0, out1, out2, out3);
+}
+
+// E of one sequence of n_chains chains on the host, by the scalar pieces the kernel runs (no device): x[S], chain after chain; chains
+// of fewer than 8 draws give NaN
+int mfm_ess_row_chains(int32_t S, int32_t n_chains, const double *x, double *out_ess, double *out_rhat) {
   if (S < 1 || S > mfm::DIST_MAX_S || !x || !out_ess || !out_rhat) {
     g_global_error = "a sequence of 1 to " + std::to_string(mfm::DIST_MAX_S) + " draws and the two outputs are needed";
     return MFM_ERR_INVALID;
   }
   try {
-    mfm::ess_row_host(S, x, out_ess, out_rhat);
+    mfm::ess_check_chains(n_chains, S);
+    mfm::ess_row_host(S, n_chains, x, out_ess, out_rhat);
+  } catch (const mfm::Error &e) {
+    g_global_error = e.what();
+    return e.code;
   } catch (const std::bad_alloc &) {
     g_global_error = "host out of memory";
     return MFM_ERR_RUNTIME;
   }
   return MFM_OK;
 }
+int mfm_ess_row(int32_t S, const double *x, double *out_ess, double *out_rhat) { return mfm_ess_row_chains(S, 1, x, out_ess, out_rhat); }
+
+// what ess_check refuses of a chain count over n_samples samples, for a caller that has to know before it makes a design
+int mfm_ess_check_chains(int32_t n_samples, int32_t n_chains) {
+  try {
+    mfm::ess_check_chains(n_chains, std::max(n_samples, 0));
+  } catch (const mfm::Error &e) {
+    g_global_error = e.what();
+    return e.code;
+  }
+  return MFM_OK;
+}
+int32_t mfm_ess_max_chains(void) { return mfm::ESS_MAX_CHAINS; }
 
 // the rank-normalised values of S draws by twice the average rank: out[2S - 1]
 int mfm_rank_z_table(int32_t S, double *out) {

@@ -476,7 +476,7 @@ class _LooMixin(_LogDensityMixin):
             raise ValueError("leave-one-out weights are computed over at most %d kept samples, this model keeps %d"
                              % (PREDICT_LOO_MAX_SAMPLES, n_samples))
         if auto:  # the chain's own estimate, one number for all rows (as arviz hands PSIS one)
-            per_row = np.asarray(predictor.likelihood_ess(*args)[2])
+            per_row = np.asarray(predictor.likelihood_ess(*args, n_chains=int(getattr(self, "n_chains_", 1)))[2])
             r_eff = float(np.nanmean(per_row)) if np.any(np.isfinite(per_row)) else 1.0  # (a row is finite or NaN)
         return LooDensity(*predictor.predict_loo(*args, bool(log_weights), float(r_eff)))
 
@@ -527,8 +527,13 @@ class _DiagnosticsMixin(_LogDensityMixin):
     Monte Carlo errors of a fitted Gibbs regressor, classifier or ordered probit over the S kept samples in their order (DESIGN
     4.9.4), after Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021). The factors themselves are not identified (sign and
     rotation), so what is diagnosed are the identified per-row quantities every other summary is a Monte Carlo estimate of. One fit
-    is one chain: the two halves of the kept samples stand in for two chains. Limits: no tail-ESS; at most 4096 kept samples; no
-    variational estimator (one sample); not row-sharded (the model is replicated: each rank may call it on its own rows)."""
+    is one chain: the two halves of the kept samples stand in for two chains. A model that combine_chains or fit_chains made of M
+    fits (n_chains_ = M) is M chains: every chain is split in two and the 2M halves are compared, which also sees chains that sit in
+    different modes. Limits: no tail-ESS; at most 4096 kept samples in all and at most 32 chains of equal length; no variational
+    estimator (one sample); not row-sharded (the model is replicated: each rank may call it on its own rows)."""
+
+    def _n_chains(self):
+        return int(getattr(self, "n_chains_", 1))
 
     def predict_diagnostics(self, X, X_rel=[]):
         """ChainDiagnostics(rhat, ess_bulk, ess_mean, mcse_mean) per row, computed on the device in one pass over the rows, of the
@@ -551,7 +556,7 @@ class _DiagnosticsMixin(_LogDensityMixin):
         if isinstance(cutpoint_index, bool) or not isinstance(cutpoint_index, (int, np.integer)):
             raise ValueError("cutpoint_index must be an integer")
         self._check_diagnostics_limit(predictor)
-        return ChainDiagnostics(*predictor.predict_ess(X, list(X_rel), int(cutpoint_index)))
+        return ChainDiagnostics(*predictor.predict_ess(X, list(X_rel), int(cutpoint_index), n_chains=self._n_chains()))
 
     def likelihood_diagnostics(self, X, y, X_rel=[]):
         """LikelihoodDiagnostics(r_eff, rhat, ess_bulk, mcse_lpd) per row, computed on the device in one pass over the rows, of the
@@ -570,7 +575,7 @@ class _DiagnosticsMixin(_LogDensityMixin):
     def _likelihood_diagnostics(self, X, y, X_rel, cutpoint_index):
         predictor, args = self._log_density_args(X, y, X_rel, cutpoint_index, "likelihood_diagnostics")
         self._check_diagnostics_limit(predictor)
-        rhat, ess_bulk, r_eff, mcse = predictor.likelihood_ess(*args)
+        rhat, ess_bulk, r_eff, mcse = predictor.likelihood_ess(*args, n_chains=self._n_chains())
         return LikelihoodDiagnostics(r_eff, rhat, ess_bulk, mcse)
 
     @staticmethod
@@ -845,15 +850,23 @@ def _fold_in_grouping(entity, U):
 
 
 def _folded_in(est, predictor, D, U):
-    """a new estimator of est's class around the extended predictor: constructor arguments, history_ and n_groups_ carried over"""
-    out = type(est)(est.rank, init_stdev=est.init_stdev, random_seed=est.random_seed, alpha_0=est.alpha_0, beta_0=est.beta_0,
-                    gamma_0=est.gamma_0, mu_0=est.mu_0, reg_0=est.reg_0, fit_w0=est.fit_w0, fit_linear=est.fit_linear,
-                    exact_latent_draws=est.exact_latent_draws)
+    """a new estimator of est's class around the extended predictor: constructor arguments, history_, n_groups_ and the chain count
+    of a combined model carried over"""
+    out = _unfitted_copy(est)
     out.predictor_ = predictor
     out.history_ = est.history_
     out.n_groups_ = est.n_groups_
     out.fold_in_columns_ = (D, D + U)
+    if hasattr(est, "n_chains_"):
+        out.n_chains_ = est.n_chains_
     return out
+
+
+def _unfitted_copy(est, random_seed=None):
+    """a new, unfitted Gibbs estimator of est's class with its constructor arguments (`random_seed`: another seed)"""
+    return type(est)(est.rank, init_stdev=est.init_stdev, random_seed=est.random_seed if random_seed is None else random_seed,
+                     alpha_0=est.alpha_0, beta_0=est.beta_0, gamma_0=est.gamma_0, mu_0=est.mu_0, reg_0=est.reg_0, fit_w0=est.fit_w0,
+                     fit_linear=est.fit_linear, exact_latent_draws=est.exact_latent_draws)
 
 
 FOLD_IN_GIBBS_MAX_SWEEPS = 65535  # n_burn + n_inner: the sweep number is part of the random streams' draw word
@@ -1302,3 +1315,102 @@ class VariationalFMClassifier(_PairScoringMixin, MyFMVariationalBase):
 
 MyFMRegressor = MyFMGibbsRegressor
 MyFMClassifier = MyFMGibbsClassifier
+
+
+# ---- several chains ----------------------------------------------------------------------------------------------
+COMBINE_MAX_CHAINS = int(_myfm.ESS_MAX_CHAINS)  # (of the device code: the 2 x 32 half-chains of a row are the lanes of one wavefront)
+
+
+def _kept_tail(entries, n):
+    """the last n entries (those of the kept samples) of a per-iteration list of a history; a shorter list whole"""
+    entries = list(entries)
+    return entries[len(entries) - n:] if len(entries) >= n else entries
+
+
+def combine_chains(estimators):
+    """One model of the kept samples of several fits of the same model from different seeds -- M chains -- as a new estimator of
+    their class; the inputs are left untouched. It holds the samples of chain 0, then chain 1, ... (host copies, the path of an
+    unpickled model), n_chains_ = M, the constructor arguments and n_groups_ of the first input, and a history_ whose hypers are
+    exactly the hyper-parameters of the kept samples in that order (train_log_losses and n_mh_accept likewise). Every predictor
+    works on the pooled samples: predict*, predict_dist, pairs, top-k, ranking, log density, LOO, CRPS, fold_in, pickling.
+    predict_diagnostics, likelihood_diagnostics and predict_loo(r_eff="auto") compare the chains: R-hat and the effective sample
+    sizes are those of the 2M half-chains, after Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021).
+
+    ValueError: an empty list; more than 32 estimators; estimators of different classes; a variational estimator; one that is not
+    fitted, is itself combined, or differs from the first in rank, feature size, n_groups_, fold_in_columns_, the number of kept
+    samples or the number of cutpoints."""
+    ests = list(estimators)
+    if not ests:
+        raise ValueError("combine_chains needs at least one fitted estimator")
+    first = ests[0]
+    if any(type(e) is not type(first) for e in ests):
+        raise ValueError("combine_chains needs estimators of one class, got %s" % sorted(set(type(e).__name__ for e in ests)))
+    if getattr(first, "_variational", False) or not isinstance(first, MyFMGibbsBase):
+        raise ValueError("combine_chains combines Gibbs chains: %s keeps no samples to pool" % type(first).__name__)
+    if len(ests) > COMBINE_MAX_CHAINS:
+        raise ValueError("at most %d chains are combined, got %d" % (COMBINE_MAX_CHAINS, len(ests)))
+    for c, e in enumerate(ests):
+        if e.predictor_ is None or e.history_ is None:
+            raise ValueError("combine_chains: estimator %d is not fitted" % c)
+        if getattr(e, "n_chains_", 1) != 1:
+            raise ValueError("combine_chains: estimator %d is itself a combination of chains" % c)
+    n_kept = len(first.predictor_.samples)
+
+    def cut_sizes(e):
+        samples = e.predictor_.samples
+        return tuple(len(g) for g in samples[0].cutpoints) if len(samples) else ()
+
+    for c, e in enumerate(ests):
+        for what, a, b in (("rank", first.rank, e.rank), ("feature size", first.predictor_.feature_size, e.predictor_.feature_size),
+                           ("n_groups_", first.n_groups_, e.n_groups_),
+                           ("fold_in_columns_", getattr(first, "fold_in_columns_", None), getattr(e, "fold_in_columns_", None)),
+                           ("number of kept samples", n_kept, len(e.predictor_.samples)),
+                           ("number of cutpoints", cut_sizes(first), cut_sizes(e))):
+            if a != b:
+                raise ValueError("combine_chains: estimator %d differs from the first in its %s (%s, the first has %s)" % (c, what, b, a))
+        if len(e.history_.hypers) < n_kept:
+            raise ValueError("combine_chains: estimator %d has no history_ entry for every kept sample" % c)
+    out = _unfitted_copy(first)
+    out.predictor_ = _myfm.Predictor.concatenated([e.predictor_ for e in ests])
+    out.history_ = _myfm.LearningHistory(
+        [h for e in ests for h in _kept_tail(e.history_.hypers, n_kept)],
+        [v for e in ests for v in _kept_tail(e.history_.train_log_losses, n_kept)],
+        [v for e in ests for v in _kept_tail(e.history_.n_mh_accept, n_kept)])
+    out.n_groups_ = first.n_groups_
+    out.n_chains_ = len(ests)
+    for name in ("fold_in_columns_", "n_cutpoint_groups"):
+        if hasattr(first, name):
+            setattr(out, name, getattr(first, name))
+    return out
+
+
+def fit_chains(estimator, X, y, n_chains=4, seeds=None, **fit_kwargs):
+    """Fit `n_chains` fresh copies of the Gibbs `estimator` on X, y one after another, each from its own seed, and return
+    combine_chains of them; `estimator` itself is left untouched. seeds: a list of n_chains distinct integers, by default
+    estimator.random_seed + c for chain c, so that chain 0 is draw for draw what estimator.fit(X, y, **fit_kwargs) gives.
+    fit_kwargs are fit's (X_rel, n_iter, n_kept_samples, grouping, ...). Each fit's samples leave the device as soon as they
+    are copied: at no time does more than one chain's store live there. 1 <= n_chains <= 32. Not row-sharded: RuntimeError while
+    myfm_amd.distributed is active."""
+    from . import distributed as _dist
+
+    if getattr(estimator, "_variational", False) or not isinstance(estimator, MyFMGibbsBase):
+        raise ValueError("fit_chains runs Gibbs chains: %s keeps no samples to pool" % type(estimator).__name__)
+    if isinstance(n_chains, (bool, np.bool_)) or not isinstance(n_chains, (int, np.integer)) or not 1 <= n_chains <= COMBINE_MAX_CHAINS:
+        raise ValueError("n_chains must be an integer in [1, %d]" % COMBINE_MAX_CHAINS)
+    if seeds is None:
+        seeds = [int(estimator.random_seed) + c for c in range(n_chains)]
+    else:
+        seeds = list(seeds)
+        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in seeds):
+            raise ValueError("seeds must hold integers")
+        seeds = [int(v) for v in seeds]
+        if len(seeds) != n_chains or len(set(seeds)) != n_chains:
+            raise ValueError("seeds must hold n_chains = %d distinct integers" % n_chains)
+    if _dist.active():
+        raise RuntimeError("fit_chains is not row-sharded: leave myfm_amd.distributed before running several chains")
+    chains = []
+    for seed in seeds:
+        chain = _unfitted_copy(estimator, seed).fit(X, y, **fit_kwargs)
+        chain.predictor_ = _myfm.Predictor.concatenated([chain.predictor_])  # (host copies: the fit's device store is released)
+        chains.append(chain)
+    return combine_chains(chains)

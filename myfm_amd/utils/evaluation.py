@@ -127,6 +127,62 @@ def diagnostics_summary(result, rhat_max=1.01, ess_min=100):
     return out
 
 
+def sequence_diagnostics(x, n_chains=1):
+    """(rhat, ess_bulk, ess_mean) of one scalar trace x (S,), `n_chains` chains of equal length one after another, as
+    predict_diagnostics computes them per row, on the host: the library's own sequence estimator and table of
+    rank-normalised values, ties sharing the average rank. rhat is the larger of the split R-hat of the rank-normalised draws and of
+    the rank-normalised |x - median x|, ess_bulk the effective sample size of the rank-normalised draws, ess_mean that of the draws
+    themselves. NaN for chains of fewer than 8 draws and for a trace that does not vary or is not finite."""
+    from scipy.stats import rankdata
+
+    from .. import _myfm
+
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.ndim != 1 or x.shape[0] < 1:
+        raise ValueError("x must be a non-empty 1-D array")
+    S = x.shape[0]
+    ess_mean, _ = _myfm.ess_row(x, n_chains=int(n_chains))  # (refuses a chain count that does not divide S)
+    nan = float("nan")
+    if not np.all(np.isfinite(x)):
+        return nan, nan, nan
+    table = np.asarray(_myfm.rank_z_table(S))
+
+    def z(v):
+        return np.ascontiguousarray(table[np.rint(2.0 * rankdata(v, method="average") - 2.0).astype(np.int64)])
+
+    ess_bulk, r_bulk = _myfm.ess_row(z(x), n_chains=int(n_chains))
+    xs = np.sort(x)
+    lo, hi = xs[(S - 1) // 2], xs[S // 2]
+    h = (hi - lo) * 0.5
+    _, r_folded = _myfm.ess_row(z(np.where(x >= hi, (x - hi) + h, (lo - x) + h)), n_chains=int(n_chains))
+    rhat = nan if np.isnan(r_bulk) or np.isnan(r_folded) else max(r_bulk, r_folded)
+    return float(rhat), float(ess_bulk), float(ess_mean)
+
+
+def hyper_diagnostics(est):
+    """sequence_diagnostics of the hyper-parameter trace of a fitted Gibbs estimator over its kept samples (the last S entries of
+    history_.hypers; for a model of combine_chains / fit_chains its n_chains_ chains): a dict from "alpha", "mu_w[g]" and
+    "lambda_w[g]" (g in range(n_groups_)) to (rhat, ess_bulk, ess_mean). These are the identified hyper-parameters; mu_V and
+    lambda_V belong to single factors, which are identified up to sign and order only, and are left out. A constant trace (the
+    alpha of the probit models) gives NaN."""
+    predictor, history = getattr(est, "predictor_", None), getattr(est, "history_", None)
+    if predictor is None or history is None:
+        raise RuntimeError("hyper_diagnostics needs a fitted Gibbs estimator")
+    S = len(predictor.samples)
+    hypers = history.hypers
+    if S < 1 or len(hypers) < S:
+        raise RuntimeError("hyper_diagnostics needs history_ with the hyper-parameters of every kept sample")
+    kept = hypers[len(hypers) - S:]
+    n_chains = int(getattr(est, "n_chains_", 1))
+    G = int(est.n_groups_ or 0)
+    traces = {"alpha": [h.alpha for h in kept]}
+    for g in range(G):
+        traces["mu_w[%d]" % g] = [np.asarray(h.mu_w)[g] for h in kept]
+    for g in range(G):
+        traces["lambda_w[%d]" % g] = [np.asarray(h.lambda_w)[g] for h in kept]
+    return {name: sequence_diagnostics(np.asarray(t, dtype=np.float64), n_chains) for name, t in traces.items()}
+
+
 def crps_summary(result, reference=None):
     """What a CrpsScore `result` (predict_crps) says about the rows as a whole. Returns a dict:
 

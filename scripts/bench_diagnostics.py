@@ -5,6 +5,8 @@
   (d) (D)         predict_log_density of the regressor, and with pointwise=True (the (S, N) matrix to the host);
   (l)             predict_loo(r_eff=1.0) of the regressor (mfm_design_loo_store), in this tree and, with --parent-root, in the
                   parent: the existing call is unchanged;
+  --chains M      the six diagnostics calls once more with the samples read as M chains of samples / M draws each (n_chains = M:
+                  the AR(1) sequence starts afresh at every chain), next to the single-chain calls of the same run;
   (h)             what a user had to do before for the likelihood's diagnostics: (D), then the vectorised NumPy reference of
                   tests/ess_ref.py on the host. The host part is timed on the first `--host-rows` rows and scaled to all rows (it
                   is linear in the rows); the report says so.
@@ -14,8 +16,9 @@ needs (at 95 samples: one, whatever phi is). Every device variant is timed end t
 copy back, synchronisation) in `--runs` runs of `--reps` calls each after one warm-up, the runs of the variants interleaved; a run
 reports its median call.
 
---parent-root DIR: a built checkout of the parent commit. Its predict_loo is timed in child processes alternating with this
-tree's, `--runs` runs each, and the report says whether this tree's lies within the spread of the parent's runs.
+--parent-root DIR: a built checkout of the parent commit. Its predict_loo and its six single-chain diagnostics calls are timed in
+child processes alternating with this tree's, `--runs` runs each (a child uploads once and times every variant), and the report
+says per variant whether this tree's median run lies within the spread of the parent's runs.
 Writes the report to stdout and, with --out FILE, to that file."""
 import argparse
 import json
@@ -40,8 +43,11 @@ ap.add_argument("--runs", type=int, default=3)
 ap.add_argument("--out", default=None)
 ap.add_argument("--parent-root", default=None)
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help=argparse.SUPPRESS)
-ap.add_argument("--child", choices=["l"], default=None, help=argparse.SUPPRESS)  # one variant: a JSON line of its run
+ap.add_argument("--chains", type=int, default=1)
+ap.add_argument("--child", default=None, help=argparse.SUPPRESS)  # variants, comma-separated: a JSON line of their runs
 args = ap.parse_args()
+if args.chains < 1 or args.samples % args.chains:
+    ap.error("--samples must be a multiple of --chains")
 sys.path.insert(0, os.path.abspath(args.root))
 from myfm_amd import _capi  # noqa: E402
 
@@ -62,7 +68,9 @@ def setup():
     w0, w, V = float(rng.normal()), rng.normal(size=D) * 0.3, rng.normal(size=(D, K)) * 0.2
     a0, aw, aV = 0.0, np.zeros(D), np.zeros((D, K))
     innov = np.sqrt(1.0 - args.phi ** 2)
-    for _ in range(S):  # an autocorrelated chain around one model
+    for k in range(S):  # an autocorrelated chain around one model (--chains: one per chain)
+        if k % (S // args.chains) == 0:
+            a0, aw, aV = 0.0, np.zeros(D), np.zeros((D, K))
         a0 = args.phi * a0 + innov * float(rng.normal())
         aw = args.phi * aw + innov * rng.normal(size=D)
         aV = args.phi * aV + innov * rng.normal(size=(D, K))
@@ -83,6 +91,10 @@ def setup():
         for name, task, kw in (("r", 0, dict(precisions=alphas)), ("c", 1, {}), ("o", 2, dict(cutpoints=cuts))):
             calls["p" + name] = lambda task=task, kw=kw: store.ess(design, 0, task, cutpoints=kw.get("cutpoints"))
             calls["l" + name] = lambda task=task, kw=kw: store.ess(design, 1, task, y[task], **kw)
+        if args.chains > 1 and not args.child:
+            for name, task, kw in (("r", 0, dict(precisions=alphas)), ("c", 1, {}), ("o", 2, dict(cutpoints=cuts))):
+                calls["p" + name + "M"] = lambda task=task, kw=kw: store.ess(design, 0, task, cutpoints=kw.get("cutpoints"), n_chains=args.chains)
+                calls["l" + name + "M"] = lambda task=task, kw=kw: store.ess(design, 1, task, y[task], n_chains=args.chains, **kw)
     return calls
 
 
@@ -96,23 +108,27 @@ def one_run(fn, reps):
 
 
 if args.child:
-    fn = setup()[args.child]
-    fn()  # warm-up
-    print(json.dumps({"variant": args.child, "median_s": one_run(fn, args.reps)}), flush=True)
+    calls = setup()
+    out = {}
+    for v in args.child.split(","):
+        calls[v]()  # warm-up
+        out[v] = one_run(calls[v], args.reps)
+    print(json.dumps({"median_s": out}), flush=True)
     sys.exit(0)
 
 
 def child_cmd(variant, root):
     return [sys.executable, os.path.abspath(__file__), "--child", variant, "--root", root, "--users", str(NU), "--items", str(NI), "--rank",
-            str(K), "--samples", str(S), "--rows", str(N), "--reps", str(args.reps), "--phi", str(args.phi)]
+            str(K), "--samples", str(S), "--rows", str(N), "--reps", str(args.reps), "--phi", str(args.phi), "--chains", str(args.chains)]
 
 
 def spread(ts):
     return "%s ms (min %.3f, max %.3f)" % (", ".join("%.3f" % (1e3 * t) for t in ts), 1e3 * min(ts), 1e3 * max(ts))
 
 
-say("chain diagnostics at the config-3 shape: %d + %d one-hot columns, rank %d, %d samples (AR(1) in the sample index, phi = %.2f), "
-    "%d rows; ordered probit with %d classes" % (NU, NI, K, S, args.phi, N, N_CUT + 1))
+say("chain diagnostics at the config-3 shape: %d + %d one-hot columns, rank %d, %d samples (%sAR(1) in the sample index, phi = %.2f), "
+    "%d rows; ordered probit with %d classes"
+    % (NU, NI, K, S, "%d chains of %d, each " % (args.chains, S // args.chains) if args.chains > 1 else "", args.phi, N, N_CUT + 1))
 calls = setup()
 for fn in calls.values():
     fn()  # warm-up
@@ -125,6 +141,9 @@ names = {"s": "(s)  predict_dist(quantiles=()), regression   ", "d": "(d)  log d
          "pr": "(pr) predict_diagnostics, regression         ", "pc": "(pc) predict_diagnostics, classification     ",
          "po": "(po) predict_diagnostics, ordered probit     ", "lr": "(lr) likelihood_diagnostics, regression      ",
          "lc": "(lc) likelihood_diagnostics, classification  ", "lo": "(lo) likelihood_diagnostics, ordered probit  "}
+for v in list(names):
+    if v[0] in "pl" and len(v) == 2:
+        names[v + "M"] = names[v].rstrip().replace(")", "M)", 1) + ", %d chains " % args.chains
 say("end to end, median call of each of %d runs of %d calls:" % (args.runs, args.reps))
 for v in calls:
     say("  %s %s" % (names[v], spread(runs[v])))
@@ -157,18 +176,22 @@ say("     over all %d rows: mean r_eff %.3f, %d rows with rhat above 1.01, media
 say("    the host path takes %.0f x the time of (lr)" % ((med["D"] + scaled) / med["lr"]))
 
 if args.parent_root:
-    here, parent = [], []
+    variants = ["l", "pr", "lr", "pc", "lc", "po", "lo"]
+    here, parent = {v: [] for v in variants}, {v: [] for v in variants}
     for _ in range(args.runs):  # alternating child processes, each with its own upload and warm-up
         for root, dst in ((args.parent_root, parent), (args.root, here)):
-            out = subprocess.run(child_cmd("l", root), check=True, capture_output=True, text=True, timeout=600).stdout
-            dst.append(json.loads(out.strip().splitlines()[-1])["median_s"])
-    say("%s against the parent commit, one process per run, alternating:" % names["l"].strip())
-    say("  parent   %s" % spread(parent))
-    say("  this one %s" % spread(here))
-    m = float(np.median(here))
-    say("  this tree's median run %.3f ms %s the parent's runs [%.3f, %.3f] ms"
-        % (1e3 * m, "lies within" if min(parent) <= m <= max(parent) else "lies BELOW" if m < min(parent) else "lies ABOVE",
-           1e3 * min(parent), 1e3 * max(parent)))
+            out = subprocess.run(child_cmd(",".join(variants), root), check=True, capture_output=True, text=True, timeout=600).stdout
+            for v, t in json.loads(out.strip().splitlines()[-1])["median_s"].items():
+                dst[v].append(t)
+    say("the single-chain calls against the parent commit, one process per run, alternating:")
+    for v in variants:
+        say("  %s" % names[v].strip())
+        say("    parent   %s" % spread(parent[v]))
+        say("    this one %s" % spread(here[v]))
+        m = float(np.median(here[v]))
+        say("    this tree's median run %.3f ms %s the parent's runs [%.3f, %.3f] ms"
+            % (1e3 * m, "lies within" if min(parent[v]) <= m <= max(parent[v]) else "lies BELOW" if m < min(parent[v]) else "lies ABOVE",
+               1e3 * min(parent[v]), 1e3 * max(parent[v])))
 if args.out:
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
