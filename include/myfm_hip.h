@@ -177,6 +177,18 @@ int mfm_res_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why
  * path was not tried), else empty. */
 #define MFM_CELL_INFO_FIELDS 74
 int mfm_cell_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int why_len);
+/* The streamed chain runs (csrc/mfm_chain_stream.hpp, k_cs_stream) of the relation blocks' plans as mfm_finalize left them, and how
+ * often each has been launched, for diagnostics and for tests that must prove which plan ran and which of the kernel's paths it
+ * reached. Reads host-side fields only: no launch, no synchronisation. One record of MFM_CHAIN_STREAM_INFO_FIELDS entries per
+ * streamed run, blocks in the order they were added, runs in sweep order; at most max_records are written to out, *n_records (may be
+ * NULL) is the number there are. A record:
+ *   0 block, 1 columns of the run, 2 steps, 3 Cg (columns per step), 4 Lw (window in steps), 5 NB (row ranges), 6 RD (slot reuse
+ *   delay), 7 LDS slots, 8 most hot entries of a column, 9 / 10 most rows entering / leaving the LDS in a step, 11 / 12 / 13 most
+ *   cold entries / entering rows / leaving rows of one (step, range), 14 columns without a hot entry, 15 + i, i < 10: columns whose
+ *   hot entries fill min(ceil(hot / 64), 9) = i wavefront rounds, 25 the walker workgroup's dynamic LDS in bytes, 26 cold entries,
+ *   27 hot entries, 28 / 29 launches enqueued so far by update_w / by update_V (one per factor), counted on the host.           */
+#define MFM_CHAIN_STREAM_INFO_FIELDS 30
+int mfm_chain_stream_info(const mfm_ctx *ctx, int64_t *out, int max_records, int *n_records);
 
 /* ---- model state (FM.hpp:164-168) ------------------------------------------------------ */
 int mfm_set_state(mfm_ctx *ctx, double w0, const double *w, const double *V);
@@ -731,6 +743,13 @@ int mfm_host_column_levels(int64_t n_rows, int64_t n_cols, const int64_t *indptr
  * most hot entries of a column, steps.                                                                                          */
 int mfm_cs_plan_selftest(int64_t n_rows, int32_t n_cols, const int64_t *colptr, const int32_t *rowidx, const double *val, int32_t cg,
                          int32_t lw, int32_t nb, int32_t rd, int32_t cap, double *max_rel_diff, int64_t *info);
+/* The same planner as the launch takes it, for tests that must prove which of the kernel's paths a design reaches: the plan with
+ * (cg, lw, nb, rd) as given and no slot cap. rec[MFM_CHAIN_STREAM_INFO_FIELDS]: one record of mfm_chain_stream_info (block and
+ * launches 0); hot_per_col[n_cols] (may be NULL): hot entries of every column; *built: 1 when the kernel could launch the plan (the
+ * walker's LDS and its staged entry lists hold it), else 0 -- the record then shows what it would have needed, and nothing is
+ * emulated; *max_rel_diff as above.                                                                                             */
+int mfm_cs_plan_probe(int64_t n_rows, int32_t n_cols, const int64_t *colptr, const int32_t *rowidx, const double *val, int32_t cg,
+                      int32_t lw, int32_t nb, int32_t rd, int64_t *rec, int32_t *hot_per_col, int32_t *built, double *max_rel_diff);
 
 /* ---- variational inference (csrc/mfm_vb.hip): the device steps of VariationalFMTrainer::update_all
  * (include/myfm/variational.hpp:192-217, BaseFMTrainer.hpp:135-152). An mfm_vb holds the table -- the main table with the

@@ -20,7 +20,7 @@ TASK_REGRESSION, TASK_CLASSIFICATION, TASK_ORDERED = 0, 1, 2
 SYMBOLS = [
     "mfm_version", "mfm_device_count", "mfm_global_error", "mfm_create", "mfm_destroy", "mfm_last_error",
     "mfm_set_stream", "mfm_synchronize", "mfm_set_main", "mfm_add_block", "mfm_set_groups", "mfm_finalize",
-    "mfm_peer_info", "mfm_peer_set", "mfm_peer_model_info", "mfm_peer_set_model", "mfm_peer_export", "mfm_peer_import", "mfm_peer_drop", "mfm_set_residual_policy", "mfm_dim_all", "mfm_plan_info", "mfm_plan_flags", "mfm_res_info", "mfm_cell_info", "mfm_set_state", "mfm_get_state", "mfm_set_w0", "mfm_zero_w", "mfm_get_e",
+    "mfm_peer_info", "mfm_peer_set", "mfm_peer_model_info", "mfm_peer_set_model", "mfm_peer_export", "mfm_peer_import", "mfm_peer_drop", "mfm_set_residual_policy", "mfm_dim_all", "mfm_plan_info", "mfm_plan_flags", "mfm_res_info", "mfm_cell_info", "mfm_chain_stream_info", "mfm_set_state", "mfm_get_state", "mfm_set_w0", "mfm_zero_w", "mfm_get_e",
     "mfm_get_q", "mfm_set_e", "mfm_reduce_e", "mfm_shift_e", "mfm_group_stats_w", "mfm_group_stats_V",
     "mfm_sweep_w", "mfm_sweep_V", "mfm_sweep_wV", "mfm_update_e_regression", "mfm_update_e_classification", "mfm_score_train",
     "mfm_oprobit_add_group", "mfm_oprobit_eval", "mfm_oprobit_sample_z", "mfm_hyper_stats", "mfm_timing_enable", "mfm_timing_select", "mfm_timing_reset",
@@ -30,7 +30,7 @@ SYMBOLS = [
     "mfm_rng_get_z", "mfm_design_score_ctx", "mfm_design_n_rows", "mfm_set_allreduce", "mfm_set_row_offset", "mfm_set_main_levels",
     "mfm_test_erfcx", "mfm_test_truncated_normal", "mfm_get_device", "mfm_set_shard", "mfm_comm_unique_id", "mfm_comm_init",
     "mfm_comm_stats", "mfm_comm_info", "mfm_store_create", "mfm_store_destroy", "mfm_store_last_error", "mfm_store_size", "mfm_store_push_ctx",
-    "mfm_store_push_host", "mfm_store_get", "mfm_design_predict_store", "mfm_store_reserve", "mfm_cs_plan_selftest",
+    "mfm_store_push_host", "mfm_store_get", "mfm_design_predict_store", "mfm_store_reserve", "mfm_cs_plan_selftest", "mfm_cs_plan_probe",
     "mfm_regression_iteration_ready", "mfm_regression_iteration",
     "mfm_update_e_classification_exact", "mfm_oprobit_sample_z_exact", "mfm_latent_stats", "mfm_rng_host_read", "mfm_rng_host_advance", "mfm_set_latent_order",
     "mfm_vb_create", "mfm_vb_add_block", "mfm_vb_finalize", "mfm_vb_destroy", "mfm_vb_last_error", "mfm_vb_plan_info", "mfm_vb_set_state", "mfm_vb_get_state",
@@ -54,6 +54,21 @@ SYMBOLS = [
 ]
 
 PAIRS_VOTE_MAX = 32768  # (MFM_PAIRS_VOTE_MAX of myfm_hip.h: samples * k of a topk_prob call)
+
+# a record of mfm_chain_stream_info / mfm_cs_plan_probe (MFM_CHAIN_STREAM_INFO_FIELDS of include/myfm_hip.h)
+CHAIN_STREAM_INFO = ("block", "n_cols", "n_steps", "Cg", "Lw", "NB", "RD", "n_slots", "max_hot_col", "max_enter", "max_exit", "max_cold_sr",
+                     "max_enter_sr", "max_exit_sr", "n_cols_no_hot")
+CHAIN_STREAM_INFO_TAIL = ("lds_bytes", "n_cold", "n_hot", "launches_w", "launches_V")
+CHAIN_STREAM_INFO_FIELDS = len(CHAIN_STREAM_INFO) + 10 + len(CHAIN_STREAM_INFO_TAIL)
+
+
+def chain_stream_record(rec):
+    n = len(CHAIN_STREAM_INFO)
+    d = dict(zip(CHAIN_STREAM_INFO, (int(v) for v in rec[:n])))
+    d["hot_rounds"] = [int(v) for v in rec[n:n + 10]]
+    d.update(zip(CHAIN_STREAM_INFO_TAIL, (int(v) for v in rec[n + 10:])))
+    return d
+
 
 _lib = None
 
@@ -102,6 +117,8 @@ def lib():
     L.mfm_plan_flags.argtypes = [vp]
     L.mfm_res_info.argtypes = [vp, P, C.c_int, C.c_char_p, C.c_int]
     L.mfm_cell_info.argtypes = [vp, P, C.c_int, C.c_char_p, C.c_int]
+    L.mfm_chain_stream_info.argtypes = [vp, P, C.c_int, C.POINTER(C.c_int)]
+    L.mfm_cs_plan_probe.argtypes = [i64, i32, P, P, P, i32, i32, i32, i32, P, P, C.POINTER(i32), C.POINTER(dbl)]
     L.mfm_set_state.argtypes = [vp, dbl, P, P]
     L.mfm_get_state.argtypes = [vp, C.POINTER(dbl), P, P]
     L.mfm_set_w0.argtypes = [vp, dbl]
@@ -548,6 +565,16 @@ class Context:
         d["fields"] = [tuple(int(x) for x in out[nf + 3 * k:nf + 3 * k + 3]) for k in range(d["n_fields"])]
         d["why"] = why.value.decode()
         return d
+
+    def chain_stream_info(self):
+        """the streamed chain runs of the relation blocks' plans (mfm_chain_stream_info): one dict per run with the
+        CHAIN_STREAM_INFO fields as ints and `hot_rounds`, a list of ten counts (columns whose hot entries fill i wavefront
+        rounds, the last entry: nine or more)"""
+        n = C.c_int(0)
+        self._ck(lib().mfm_chain_stream_info(self.h, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), CHAIN_STREAM_INFO_FIELDS), dtype=np.int64)
+        self._ck(lib().mfm_chain_stream_info(self.h, _p(out), n.value, C.byref(n)))
+        return [chain_stream_record(out[i]) for i in range(n.value)]
 
     def plan_info(self):
         a, b = C.c_int64(), C.c_int64()

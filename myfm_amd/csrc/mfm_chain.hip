@@ -17,9 +17,48 @@ struct CsStream {
   DevBuf<double> cold_x, hot_x;
   DevBuf<double2> in_ring, out_ring, part, oldnew;
   DevBuf<CsSync> sync;
+  mutable long long launches[2] = {0, 0};        // enqueued so far: [0] update_w's, [1] update_V's (host counters: mfm_chain_stream_info)
   mutable DevBuf<int32_t> col_group;             // group index of every chain column (gathered at the first launch)
   mutable const int32_t *col_group_of = nullptr;  // ... from this group array
 };
+
+// a built plan the kernel can take: the walker's LDS and the staged hot entry lists hold it
+static bool cs_plan_launchable(const CsPlanHost &P) {
+  return P.ok && (size_t)P.lds_bytes <= CS_LDS_MAX && cs_ecap(P.max_hot_col) <= CS_ECAP_MAX && P.prm.NB <= CS_MAX_NB && P.prm.RD < CS_SR &&
+         P.prm.RD <= CS_ER;
+}
+
+static CsStreamInfo cs_info_of(const CsPlanHost &P) {
+  CsStreamInfo I;
+  I.n_cols = P.n_cols;
+  I.n_steps = P.n_steps;
+  I.Cg = P.prm.Cg;
+  I.Lw = P.prm.Lw;
+  I.NB = P.prm.NB;
+  I.RD = P.prm.RD;
+  I.n_slots = P.n_slots;
+  I.max_hot_col = P.max_hot_col;
+  I.max_enter = P.max_enter;
+  I.max_exit = P.max_exit;
+  I.max_cold_sr = P.max_cold_sr;
+  I.max_enter_sr = P.max_enter_sr;
+  I.max_exit_sr = P.max_exit_sr;
+  I.n_cols_no_hot = P.n_cols_no_hot;
+  for (int i = 0; i < 10; i++) I.hot_rounds[i] = P.hot_rounds[i];
+  I.lds_bytes = P.lds_bytes;
+  I.n_cold = P.n_cold;
+  I.n_hot = P.n_hot;
+  return I;
+}
+
+void cs_info_record(const CsStreamInfo &I, int64_t *out) {
+  const int64_t v[CS_INFO_FIELDS] = {0,           I.n_cols,       I.n_steps,       I.Cg,           I.Lw,           I.NB,           I.RD,
+                                     I.n_slots,   I.max_hot_col,  I.max_enter,     I.max_exit,     I.max_cold_sr,  I.max_enter_sr, I.max_exit_sr,
+                                     I.n_cols_no_hot, I.hot_rounds[0], I.hot_rounds[1], I.hot_rounds[2], I.hot_rounds[3], I.hot_rounds[4],
+                                     I.hot_rounds[5], I.hot_rounds[6], I.hot_rounds[7], I.hot_rounds[8], I.hot_rounds[9], I.lds_bytes,
+                                     I.n_cold,    I.n_hot,        0,               0};
+  for (int i = 0; i < CS_INFO_FIELDS; i++) out[i] = v[i];
+}
 
 std::shared_ptr<CsStream> cs_stream_build(const HostCsr &csc, const std::vector<int32_t> &run, CsStreamInfo *info) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -46,7 +85,7 @@ std::shared_ptr<CsStream> cs_stream_build(const HostCsr &csc, const std::vector<
     std::vector<Cand> cands((size_t)CS_MAX_CG + 1);
     auto fits = [&](int cg, int lw, CsNeed &N) {
       N = cs_estimate(T, cg, lw, prm.RD);
-      return N.n_slots <= prm.cap && cs_lds_bytes(N.n_slots, cg, N.max_hot_col) <= CS_LDS_MAX && cs_ecap(N.max_hot_col) <= 1024;
+      return N.n_slots <= prm.cap && cs_lds_bytes(N.n_slots, cg, N.max_hot_col) <= CS_LDS_MAX && cs_ecap(N.max_hot_col) <= CS_ECAP_MAX;
     };
     auto search = [&](int cg) {  // the best window for this step width (the LDS need grows with the window: bisection)
       Cand &C = cands[(size_t)cg];
@@ -79,7 +118,7 @@ std::shared_ptr<CsStream> cs_stream_build(const HostCsr &csc, const std::vector<
     prm.Cg = best.cg;
     prm.Lw = best.lw;
     P = cs_build_plan(csc.ptr.data(), csc.idx.data(), csc.val.data(), csc.cols, run, prm);
-    if (P.ok && cs_lds_bytes(P.n_slots, prm.Cg, P.max_hot_col) > CS_LDS_MAX) P.ok = false;
+    if (P.ok && !cs_plan_launchable(P)) P.ok = false;
   }
   if (!P.ok) return nullptr;
   auto st = std::make_shared<CsStream>();
@@ -102,23 +141,14 @@ std::shared_ptr<CsStream> cs_stream_build(const HostCsr &csc, const std::vector<
   st->oldnew.alloc((size_t)CS_RING * CS_MAX_CG);
   st->sync.alloc(1);
   CsStreamInfo &I = st->info;
-  I.n_steps = P.n_steps;
-  I.Cg = P.prm.Cg;
-  I.Lw = P.prm.Lw;
-  I.NB = P.prm.NB;
-  I.RD = P.prm.RD;
-  I.n_slots = P.n_slots;
-  I.max_hot_col = P.max_hot_col;
-  I.max_enter = P.max_enter;
-  I.max_exit = P.max_exit;
-  I.n_cold = P.n_cold;
-  I.n_hot = P.n_hot;
+  I = cs_info_of(P);
   I.plan_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (info) *info = I;
   return st;
 }
 
 const CsStreamInfo &cs_stream_info(const CsStream &st) { return st.info; }
+long long cs_stream_launches(const CsStream &st, bool latent) { return st.launches[latent ? 1 : 0]; }
 
 static __global__ void k_cs_gather_i32(const int32_t *__restrict__ src, const int32_t *__restrict__ idx, int n, int32_t *__restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -133,7 +163,7 @@ void cs_stream_launch(hipStream_t s, const SweepArgs &a, const CsStream &st, boo
     hipLaunchKernelGGL(k_cs_gather_i32, dim3((n + 255) / 256), dim3(256), 0, s, a.group, st.cols.p, n, st.col_group.p);
     st.col_group_of = a.group;
   }
-  const size_t lds = cs_lds_bytes(I.n_slots, I.Cg, I.max_hot_col);
+  const size_t lds = (size_t)I.lds_bytes;
   static DeviceOnce raised;
   if (raised.need()) {
     MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_cs_stream<PBlockV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CS_LDS_MAX));
@@ -201,6 +231,7 @@ void cs_stream_launch(hipStream_t s, const SweepArgs &a, const CsStream &st, boo
   else
     hipLaunchKernelGGL((k_cs_stream<PBlockW>), dim3(1 + I.NB), dim3(CS_NT), lds, s, a, g);
   MFM_HIP_CHECK(hipGetLastError());
+  st.launches[latent ? 1 : 0]++;
   if (tracing) {
     std::vector<unsigned long long> h(trace_n);
     MFM_HIP_CHECK(hipStreamSynchronize(s));
@@ -266,6 +297,42 @@ extern "C" int mfm_cs_plan_selftest(int64_t n_rows, int32_t n_cols, const int64_
     std::string err;
     const double d = cs_emulate(P, colptr, rowidx, val, run, q0, &err);
     if (max_rel_diff) *max_rel_diff = d;
+    return err.empty() ? MFM_OK : MFM_ERR_INVALID;
+  } catch (...) {
+    return MFM_ERR_RUNTIME;
+  }
+}
+
+// Host-only probe of one plan (tests/test_chain_edges_cpu.py), beside mfm_cs_plan_selftest: the plan of the chain over ALL columns of
+// the given CSC with (cg, lw, nb, rd) as given and no slot cap, as the launch would take it. rec[MFM_CHAIN_STREAM_INFO_FIELDS]: the
+// record of mfm_chain_stream_info (block and launches 0); hot_per_col[n_cols] (may be NULL): hot entries of every column;
+// *built: 1 when the kernel could launch this plan (the walker's LDS and its staged lists hold it), else 0 -- the record then
+// shows what it would have needed, and the emulation is not run. *max_rel_diff: cs_emulate against the sequential sweep, from
+// q0[r] = sin(0.7 r) + 0.1. Returns MFM_OK, or MFM_ERR_INVALID when the emulation got stuck.
+extern "C" int mfm_cs_plan_probe(int64_t n_rows, int32_t n_cols, const int64_t *colptr, const int32_t *rowidx, const double *val, int32_t cg,
+                                 int32_t lw, int32_t nb, int32_t rd, int64_t *rec, int32_t *hot_per_col, int32_t *built, double *max_rel_diff) {
+  using namespace mfm;
+  if (!colptr || !rowidx || !val || !rec || !built || !max_rel_diff || n_cols < 0) return MFM_ERR_INVALID;
+  try {
+    std::vector<int32_t> run((size_t)n_cols);
+    for (int32_t j = 0; j < n_cols; j++) run[j] = j;
+    CsParams prm;
+    prm.Cg = cg;
+    prm.Lw = lw;
+    prm.NB = nb;
+    prm.RD = rd;
+    prm.cap = 1 << 20;
+    const CsPlanHost P = cs_build_plan(colptr, rowidx, val, n_rows, run, prm);
+    cs_info_record(cs_info_of(P), rec);
+    if (hot_per_col)
+      for (int32_t j = 0; j < n_cols; j++) hot_per_col[j] = P.ok ? P.hot_ptr[(size_t)j + 1] - P.hot_ptr[(size_t)j] : 0;
+    *built = cs_plan_launchable(P) ? 1 : 0;
+    *max_rel_diff = 0.0;
+    if (!*built) return MFM_OK;
+    std::vector<double> q0((size_t)n_rows);
+    for (int64_t r = 0; r < n_rows; r++) q0[r] = std::sin(0.7 * (double)r) + 0.1;
+    std::string err;
+    *max_rel_diff = cs_emulate(P, colptr, rowidx, val, run, q0, &err);
     return err.empty() ? MFM_OK : MFM_ERR_INVALID;
   } catch (...) {
     return MFM_ERR_RUNTIME;

@@ -29,6 +29,20 @@ constexpr int CS_MAX_CG = 4;       // columns per step
 constexpr int CS_RING = 8;         // ring slots of everything the two sides exchange (>= Lw + 1)
 constexpr int CS_MAX_LW = CS_RING - 1;
 constexpr int CS_LCOL_SHIFT = 27;  // cold entry word: row | (column inside the step) << 27
+// what the walker workgroup's LDS need is made of (the kernel's layout: mfm_chain_stream.hpp)
+constexpr int CS_WAVE = 64;        // lanes of a wavefront
+constexpr int CS_SR = 4;           // LDS ring of per-step scalars in the walker (>= RD + 1)
+constexpr int CS_NX = 2, CS_NY = 4;
+constexpr int CS_ER = 2;           // steps of hot entry lists in the walker's LDS (>= RD)
+constexpr size_t CS_LDS_MAX = 156 * 1024;  // of the CU's 160 KiB
+constexpr int CS_ECAP_MAX = 1024;  // hot entries of a column the staged lists hold at most
+
+// LDS of a launch (the walker's need; the ranges use a few hundred bytes of it)
+inline int cs_ecap(int max_hot_col) { return std::max(CS_WAVE, ((max_hot_col + CS_WAVE - 1) / CS_WAVE) * CS_WAVE); }
+inline size_t cs_lds_bytes(int n_slots, int Cg, int max_hot_col) {
+  return (size_t)(std::max(n_slots, 1) + 1) * 56 + (size_t)CS_SR * CS_MAX_CG * (2 * sizeof(double) + 5 * sizeof(double) + sizeof(int)) +
+         (size_t)CS_ER * Cg * cs_ecap(max_hot_col) * (sizeof(double) + sizeof(int)) + (CS_NY + 1 + 2 * CS_NX) * sizeof(int) + 64;
+}
 
 struct CsParams {
   int Cg = 4;         // columns per step
@@ -46,6 +60,12 @@ struct CsPlanHost {
   int max_enter = 0, max_exit = 0;    // per step (ring slot sizes)
   int max_hot_col = 0;                // hot entries of a column at most
   int64_t n_cold = 0, n_hot = 0;
+  // what decides the kernel's paths (diagnostics: mfm_chain_stream_info): most cold entries / entering rows / leaving rows of a
+  // (step, range); columns without a hot entry; columns by min(ceil(hot entries / 64), 9); the walker workgroup's LDS
+  int max_cold_sr = 0, max_enter_sr = 0, max_exit_sr = 0;
+  int n_cols_no_hot = 0;
+  int hot_rounds[10] = {0};
+  int64_t lds_bytes = 0;
   // cold entries by (step, range), by column inside
   std::vector<int32_t> cold_ptr;      // [n_steps * NB + 1]
   std::vector<int32_t> cold_rc;       // row | lcol << CS_LCOL_SHIFT
@@ -125,6 +145,13 @@ inline CsPlanHost cs_build_plan(const int64_t *csc_ptr, const int32_t *csc_idx, 
     }
     P.hot_ptr[k + 1] = P.hot_ptr[k] + hot;
     P.max_hot_col = std::max(P.max_hot_col, hot);
+    P.n_cols_no_hot += hot == 0 ? 1 : 0;
+    P.hot_rounds[std::min((hot + CS_WAVE - 1) / CS_WAVE, 9)]++;
+  }
+  for (size_t i = 1; i < ccnt.size(); i++) {
+    P.max_cold_sr = std::max(P.max_cold_sr, ccnt[i]);  // (still the counts of one (step, range))
+    P.max_enter_sr = std::max(P.max_enter_sr, encnt[i]);
+    P.max_exit_sr = std::max(P.max_exit_sr, excnt[i]);
   }
   for (size_t i = 1; i < ccnt.size(); i++) {
     ccnt[i] += ccnt[i - 1];
@@ -216,6 +243,7 @@ inline CsPlanHost cs_build_plan(const int64_t *csc_ptr, const int32_t *csc_idx, 
     }
   }
   P.n_slots = next_new;
+  P.lds_bytes = (int64_t)cs_lds_bytes(P.n_slots, Cg, P.max_hot_col);
   P.ok = true;
   return P;
 }
@@ -304,6 +332,10 @@ inline CsPlanHost cs_build_plan_fit(const int64_t *csc_ptr, const int32_t *csc_i
 // as soon as slot reuse allows) -- on separate copies of what each actor can see (records in global memory, LDS slots, ring
 // slots), so that a plan that lets an actor read something before it is final, or reuse a slot or a ring position too early,
 // gives other numbers than the plain sequential sweep. Returns the largest relative difference of the coefficients.
+// The toy map has slope up to 1.7 * 0.9 in S, and a column feeds its draw back into its rows' q with weight x: a column whose entries
+// have sum x^2 above about 0.65 EXPANDS a difference in S, so that over a run of such columns the two summation orders alone drift
+// apart to O(1) (a few hundred entries of 0.2-0.9 per column do that). A test of heavy columns must use small values (sum x^2 well
+// below 0.65 per column: a few hundred entries of about 0.02), or the difference it reads says nothing about the plan.
 inline double cs_emulate(const CsPlanHost &P, const int64_t *csc_ptr, const int32_t *csc_idx, const double *csc_val,
                          const std::vector<int32_t> &run, std::vector<double> q0, std::string *err = nullptr) {
   const int n = P.n_cols, ns = P.n_steps, Cg = P.prm.Cg, Lw = P.prm.Lw, NB = P.prm.NB, RD = P.prm.RD, R = CS_RING;

@@ -36,11 +36,8 @@ namespace mfm {
 constexpr int CS_NT = 512;       // threads of every workgroup
 constexpr int CS_NWS = 4;        // S wavefronts per range workgroup (the other four are U)
 constexpr int CS_MAX_NB = 32;    // row ranges at most
-constexpr int CS_SR = 4;         // LDS ring of per-step scalars in the walker (>= RD + 1)
 constexpr int CS_U = 8;          // 64-entry rounds of a column's hot entries kept in registers
-constexpr int CS_NX = 2, CS_NY = 4;
-constexpr int CS_ER = 2;         // steps of hot entry lists in the walker's LDS (>= RD)
-constexpr size_t CS_LDS_MAX = 156 * 1024;  // of the CU's 160 KiB
+static_assert(CS_WAVE == WAVE && sizeof(double2) == 2 * sizeof(double), "cs_lds_bytes (mfm_chain_plan.hpp) counts the layout below");
 
 struct CsSync {  // zeroed before every launch
   unsigned long long walk_done;  // steps whose exits and (old, new) pairs are published
@@ -884,13 +881,6 @@ __global__ __launch_bounds__(CS_NT) void k_cs_stream(SweepArgs a, CsArgs g) {
       g.prof[9] += t_work;
     }
   }
-}
-
-// LDS of a launch (the walker's need; the ranges use a few hundred bytes of it)
-inline int cs_ecap(int max_hot_col) { return std::max(WAVE, ((max_hot_col + WAVE - 1) / WAVE) * WAVE); }
-inline size_t cs_lds_bytes(int n_slots, int Cg, int max_hot_col) {
-  return (size_t)(std::max(n_slots, 1) + 1) * 56 + (size_t)CS_SR * CS_MAX_CG * (sizeof(double2) + 5 * sizeof(double) + sizeof(int)) +
-         (size_t)CS_ER * Cg * cs_ecap(max_hot_col) * (sizeof(double) + sizeof(int)) + (CS_NY + 1 + 2 * CS_NX) * sizeof(int) + 64;
 }
 
 }  // namespace mfm

@@ -1787,6 +1787,34 @@ int mfm_cell_info(const mfm_ctx *ctx, int64_t *out, int n_out, char *why, int wh
   return MFM_OK;
 }
 
+// The streamed chain runs of the relation blocks' plans and their launch counts (host-side fields only: no launch, no synchronisation)
+int mfm_chain_stream_info(const mfm_ctx *ctx, int64_t *out, int max_records, int *n_records) {
+  static_assert(MFM_CHAIN_STREAM_INFO_FIELDS == CS_INFO_FIELDS, "include/myfm_hip.h documents cs_info_record's fields");
+  if (!ctx || max_records < 0 || (max_records > 0 && !out)) return MFM_ERR_INVALID;
+  int n = 0;
+  for (size_t b = 0; b < ctx->blocks.size(); b++) {
+    // (update_w's plan of the block shares update_V's streams; one of its own is counted where it is, run by run)
+    std::vector<const CsStream *> of_w;
+    for (const Step &st : ctx->blocks[b]->plan_W.steps)
+      if (st.is_chain && st.chain.form == ChainForm::Stream) of_w.push_back(st.chain.stream.get());
+    size_t k = 0;
+    for (const Step &st : ctx->blocks[b]->plan_V.steps) {
+      if (!st.is_chain || st.chain.form != ChainForm::Stream) continue;
+      if (n < max_records) {
+        int64_t *rec = out + (size_t)n * MFM_CHAIN_STREAM_INFO_FIELDS;
+        cs_info_record(cs_stream_info(*st.chain.stream), rec);
+        rec[0] = (int64_t)b;
+        rec[28] = k < of_w.size() ? cs_stream_launches(*of_w[k], false) : 0;
+        rec[29] = cs_stream_launches(*st.chain.stream, true);
+      }
+      n++;
+      k++;
+    }
+  }
+  if (n_records) *n_records = n;
+  return MFM_OK;
+}
+
 // ---- state ------------------------------------------------------------------------------------
 int mfm_set_state(mfm_ctx *ctx, double w0, const double *w, const double *V) {
   MFM_TRY(ctx)

@@ -2,7 +2,8 @@
 not fit one CU's LDS (FMTrainer.hpp:276-302 for w, :419-470 for V) as ONE pipelined launch -- a walker wavefront over the hot rows'
 records in LDS, helper wavefronts moving rows in and out, row-range workgroups taking cold statistics / applying cold updates, all
 synchronised by monotonic counters. Regression chains against the CPU oracle (same seed, 1e-7), for several step widths, windows,
-range counts and LDS budgets; bit-reproducible; the conflict-batched form (MFM_NO_CB_STREAM) gives the same chain."""
+range counts and LDS budgets; bit-reproducible; the conflict-batched form (MFM_NO_CB_STREAM) gives the same chain. What was planned and
+that k_cs_stream ran is read from `chain_stream_info()`; the kernel's overflow paths and step edges: tests/test_gpu_chain_stream_edges.py."""
 import numpy as np
 import pytest
 import scipy.sparse as sps
@@ -55,19 +56,31 @@ def _chain(oracle, capi, design, rank=3, iters=2):
     return t, c
 
 
+_FITTING = {(4, 3, 16, 700): dict(per_a=3, per_b=3), (4, 5, 8, 0): dict(per_a=4)}
+
+
 @pytest.mark.parametrize("cg,lw,nb,cap", [(4, 3, 16, 0), (4, 4, 16, 0), (2, 5, 8, 0), (1, 6, 4, 0), (4, 2, 32, 0), (3, 2, 5, 0), (4, 3, 16, 700), (2, 5, 16, 0), (4, 5, 8, 0), (2, 3, 8, 0), (2, 6, 32, 0), (1, 7, 16, 0)])
 def test_streamed_chain_matches_oracle(oracle, capi, monkeypatch, cg, lw, nb, cap):
     monkeypatch.setenv("MFM_CHAIN_GRID_MIN", "0")  # (the test's blocks are small: their cold parts would not go to the grid otherwise)
     monkeypatch.setenv("MFM_NO_CELL", "1")         # the generic relation-block path (the cell path has its own tests)
     monkeypatch.setenv("MFM_CS_CG", str(cg))
-    monkeypatch.setenv("MFM_CS_LW", str(lw))
-    monkeypatch.setenv("MFM_CS_LW_MIN", "1")
+    monkeypatch.setenv("MFM_CS_LW", str(lw))       # the window is forced: MFM_CS_LW alone is an upper bound the cost model picks below
+    monkeypatch.setenv("MFM_CS_LW_MIN", str(lw))
     monkeypatch.setenv("MFM_CS_NB", str(nb))
     if cap:
         monkeypatch.setenv("MFM_CS_CAP", str(cap))
-    design = _design()
+    # two cases do not fit the default design with their window forced -- 700 slots hold neither block's hot rows at (4, 3), the
+    # walker's LDS not the first block's at (4, 5): theirs has fewer entries per row
+    design = _design(**_FITTING.get((cg, lw, nb, cap), {}))
     t, c = _chain(oracle, capi, design)
     assert c.plan_flags()["streamed_chain"]
+    info = c.chain_stream_info()
+    print(info)
+    # both blocks' chains are one streamed run each, planned as the case names, and k_cs_stream ran for update_w and update_V
+    assert [(r["block"], r["n_cols"]) for r in info] == [(0, 90), (1, 50)], info
+    for r in info:
+        assert (r["Cg"], r["Lw"], r["NB"]) == (cg, lw, nb) and (not cap or r["n_slots"] <= cap), r
+        assert r["launches_w"] > 0 and r["launches_V"] > 0, r
     w0, w, V = t.fm()
     _, gw, gV = c.get_state()
     np.testing.assert_allclose(gV, V, rtol=1e-7, atol=1e-8)
@@ -82,10 +95,14 @@ def test_streamed_chain_is_reproducible_and_equals_the_batched_form(oracle, capi
     _, c1 = _chain(oracle, capi, design)
     _, c2 = _chain(oracle, capi, design)
     assert c1.plan_flags()["streamed_chain"]
+    i1, i2 = c1.chain_stream_info(), c2.chain_stream_info()
+    print(i1)
+    assert [r["block"] for r in i1] == [0, 1] and i1 == i2  # the planner's own choice, both times the same, and it ran
+    assert all(r["launches_w"] > 0 and r["launches_V"] > 0 for r in i1), i1
     assert np.array_equal(c1.get_state()[2], c2.get_state()[2]) and np.array_equal(c1.get_e(), c2.get_e())
     monkeypatch.setenv("MFM_NO_CB_STREAM", "1")
     _, c3 = _chain(oracle, capi, design)
-    assert not c3.plan_flags()["streamed_chain"]
+    assert not c3.plan_flags()["streamed_chain"] and c3.chain_stream_info() == []
     np.testing.assert_allclose(c3.get_state()[2], c1.get_state()[2], rtol=1e-8, atol=1e-9)
 
 
@@ -99,6 +116,9 @@ def test_streamed_chain_on_the_cell_path_and_with_identity_columns(oracle, capi,
     t, c = _chain(oracle, capi, (main, y, blocks, gi), rank=3, iters=2)
     flags = c.plan_flags()
     assert flags["streamed_chain"] and flags["cell"], flags
+    info = c.chain_stream_info()
+    print(info)
+    assert info and all(r["launches_w"] > 0 and r["launches_V"] > 0 for r in info), info
     w0, w, V = t.fm()
     _, gw, gV = c.get_state()
     np.testing.assert_allclose(gV, V, rtol=1e-7, atol=1e-8)
