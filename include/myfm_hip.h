@@ -830,6 +830,32 @@ int mfm_vb_synchronize(mfm_vb *v);
  * classification residual of mfm_vb_update_e runs on the device: out3 = mean, variance, log Z                              */
 int mfm_vb_truncated_normal(int32_t right, double mu, double *out3);
 
+/* ---- analytic score moments of a variational model (csrc/mfm_vbmoments.hpp, csrc/mfm_pairs_vb.hpp) -------------------
+ * The model is the mean-field Gaussian posterior w0 ~ N(w0, w0_var), w ~ N(w[D], w_var[D]), V ~ N(V, V_var), V and V_var column-major
+ * (D, K), all host arrays. Under it the FM score of a row has the closed-form mean (the mean model's score) and variance
+ *   w0_var + sum x^2 w_var + sum_k [ M^2 A - 2 M B + C + (A^2 - E) / 2 ]_k  + extra_var
+ * with M = sum x m, A = sum x^2 s, B = sum x^3 s m, C = sum x^4 s m^2, E = sum x^4 s^2 over the row's entries (relation blocks
+ * included, never expanded). extra_var >= 0 is added as it is (1 / alpha: the predictive variance of a regression target).
+ * mfm_design_moments_vb: out_mean[N] is bit for bit the score mfm_design_predict gives for the mean model on a design without
+ *   relation blocks; out_std[N] = sqrt(max(variance, 0)); want_prob != 0 also writes out_prob[N] = Phi(mean / sqrt(1 + variance)),
+ *   the probit link integrated over a Gaussian with these two moments (out_prob may be NULL otherwise). tile_rows forces the rows per
+ *   launch (0: automatic); the results do not depend on it. rank <= 512.
+ * mfm_pairs_moments_vb: mean[U * I] and std[U * I] of the score of every pair of an mfm_pairs handle (its sides, blocks, scratch
+ *   bound and query chunking); mean is bit for bit mfm_pairs_scores' (mode 0) for the mean model as its one sample.
+ * mfm_pairs_topk_bound_vb: per query row the k candidates of largest mean + beta * std that are not excluded, in mfm_pairs_topk's order
+ *   and with mfm_pairs_topk_ucb's outputs and tail (idx -1, value -inf, mean and std NaN); mean and std are recomputed for the selected
+ *   pairs in another association than the selecting kernel's, so value and mean + beta * std agree within rounding.
+ * NULL outputs, a negative rank, negative or non-finite variances, a non-finite beta and k outside [1, 256] are MFM_ERR_INVALID before
+ * any launch; a NULL handle is MFM_ERR_INVALID with the message under mfm_design_last_error(NULL) / mfm_pairs_last_error(NULL).   */
+int mfm_design_moments_vb(mfm_design *d, int32_t rank, double w0, double w0_var, const double *w, const double *w_var, const double *V,
+                          const double *V_var, double extra_var, int32_t want_prob, int64_t tile_rows, double *out_mean,
+                          double *out_std, double *out_prob);
+int mfm_pairs_moments_vb(mfm_pairs *p, int32_t rank, double w0, double w0_var, const double *w, const double *w_var, const double *V,
+                         const double *V_var, double extra_var, double *mean, double *std);
+int mfm_pairs_topk_bound_vb(mfm_pairs *p, int32_t rank, double w0, double w0_var, const double *w, const double *w_var, const double *V,
+                            const double *V_var, double extra_var, int32_t k, double beta, int64_t *idx, double *value, double *mean,
+                            double *std);
+
 #ifdef __cplusplus
 }
 #endif

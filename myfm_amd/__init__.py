@@ -35,6 +35,7 @@ from .estimators import (  # noqa: E402
     PointwiseDensity,
     RankedSummary,
     SampleRankings,
+    ScoreMoments,
     TargetRanks,
     ThompsonRanking,
     TopKProbability,
@@ -56,6 +57,7 @@ __all__ = [
     "FOLD_IN_MAX_RANK",
     "PairSummary",
     "RankedSummary",
+    "ScoreMoments",
     "TargetRanks",
     "PointwiseDensity",
     "LooDensity",

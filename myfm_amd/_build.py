@@ -18,12 +18,12 @@ PYMOD = os.path.join(HERE, "_myfm" + EXT_SUFFIX)
 HIP_UNITS = {
     "mfm_hip.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_policies.hpp", "mfm_kernels.hpp", "mfm_mf_kernels.hpp", "mfm_res.hpp", "mfm_res_entry.hpp", "mfm_res_plan.hpp",
                     "mfm_plan.hpp", "mfm_block_kernels.hpp", "mfm_erfcx.hpp", "mfm_tasks.hpp", "mfm_tn.hpp", "mfm_philox.hpp", "mfm_predict.hpp", "mfm_samples.hpp", "mfm_dist.hpp", "mfm_logdens.hpp", "mfm_psis.hpp", "mfm_ess.hpp", "mfm_crps.hpp", "mfm_normal_quantile.hpp", "mfm_rng.hpp", "mfm_mtjump.hpp", "mfm_cell.hpp",
-                    "mfm_chain_api.hpp", "mfm_rng_state.hpp", "mfm_latent_api.hpp", "mfm_latent_host.hpp", "mfm_comm.hpp"],
+                    "mfm_chain_api.hpp", "mfm_rng_state.hpp", "mfm_latent_api.hpp", "mfm_latent_host.hpp", "mfm_comm.hpp", "mfm_vbmoments.hpp", "mfm_vb_sums.hpp"],
     "mfm_latent.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_rng_state.hpp", "mfm_latent_api.hpp"],
     "mfm_cell.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_cell.hpp"],
     "mfm_chain.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_policies.hpp", "mfm_chain_api.hpp", "mfm_chain_plan.hpp", "mfm_chain_stream.hpp"],
     "mfm_vb.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_erfcx.hpp", "mfm_vb.hpp", "mfm_comm.hpp"],
-    "mfm_pairs.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_pairs.hpp", "mfm_pairs_rank.hpp", "mfm_pairs_samples.hpp", "mfm_pairs_ucb.hpp", "mfm_samples.hpp"],
+    "mfm_pairs.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_pairs.hpp", "mfm_pairs_rank.hpp", "mfm_pairs_samples.hpp", "mfm_pairs_ucb.hpp", "mfm_pairs_vb.hpp", "mfm_vb_sums.hpp", "mfm_samples.hpp"],
     "mfm_foldin.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_foldin.hpp", "mfm_foldin_handle.hpp", "mfm_philox.hpp", "mfm_samples.hpp"],
     "mfm_foldin_gibbs.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_foldin.hpp", "mfm_foldin_gibbs.hpp", "mfm_foldin_gibbs_plan.hpp",
                              "mfm_foldin_handle.hpp", "mfm_tn.hpp", "mfm_philox.hpp", "mfm_samples.hpp"],

@@ -51,6 +51,7 @@ SYMBOLS = [
     "mfm_design_ess_store", "mfm_design_ess", "mfm_ess_row", "mfm_rank_z_table",
     "mfm_design_ess_chains_store", "mfm_design_ess_chains", "mfm_ess_row_chains", "mfm_ess_check_chains", "mfm_ess_max_chains",
     "mfm_design_crps_store", "mfm_design_crps", "mfm_crps_row",
+    "mfm_design_moments_vb", "mfm_pairs_moments_vb", "mfm_pairs_topk_bound_vb",
 ]
 
 PAIRS_VOTE_MAX = 32768  # (MFM_PAIRS_VOTE_MAX of myfm_hip.h: samples * k of a topk_prob call)
@@ -231,6 +232,9 @@ def lib():
     L.mfm_pairs_topk_ucb_store.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, P, P, P, P]
     L.mfm_pairs_topk_ucb.argtypes = [vp, i32, i32, P, P, P, i32, i32, C.c_double, P, P, P, P]
     L.mfm_pairs_set_targets.argtypes = [vp, P, P]
+    L.mfm_design_moments_vb.argtypes = [vp, i32, dbl, dbl, P, P, P, P, dbl, i32, i64, P, P, P]
+    L.mfm_pairs_moments_vb.argtypes = [vp, i32, dbl, dbl, P, P, P, P, dbl, P, P]
+    L.mfm_pairs_topk_bound_vb.argtypes = [vp, i32, dbl, dbl, P, P, P, P, dbl, i32, dbl, P, P, P, P]
     L.mfm_pairs_rank_store.argtypes = [vp, vp, i32, i32, i32, P, P]
     L.mfm_pairs_rank.argtypes = [vp, i32, i32, P, P, P, i32, P, P]
     L.mfm_pairs_topk_samples_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, P]
@@ -646,6 +650,15 @@ class Design:
         if rc:
             _raise(rc, lib().mfm_design_last_error(self.h))
 
+    def moments_vb(self, model, extra_var=0.0, want_prob=False, tile_rows=0):
+        """(mean[N], std[N][, Phi(mean / sqrt(1 + var))[N]]) of the score under the mean-field posterior `model` = (w0, w0_var,
+        w[D], w_var[D], V[D, K], V_var[D, K]) (mfm_design_moments_vb)"""
+        K, head, keep = _pack_vb_model(model)
+        mean, std, prob = np.empty(self.N), np.empty(self.N), np.empty(self.N if want_prob else 0)
+        self._ck(lib().mfm_design_moments_vb(self.h, K, *head, float(extra_var), int(bool(want_prob)), int(tile_rows), _p(mean), _p(std),
+                                             _p(prob) if want_prob else None))
+        return (mean, std, prob) if want_prob else (mean, std)
+
     # each operation once, over a sample source (_host / _resident); Store's methods of the same names pass a resident range
     def _predict(self, src, mode, cutpoints):
         n_cut, cp = 0, None
@@ -902,6 +915,15 @@ def psis_tail_len(S, r_eff=1.0):
     return 0 if S <= 1 else int(np.ceil(min(0.2 * S, 3.0 * np.sqrt(S / r_eff))))  # (below 5 nothing is smoothed; the library wants M < S)
 
 
+def _pack_vb_model(model):
+    """(w0, w0_var, w[D], w_var[D], V[D, K], V_var[D, K]) -> K, the six arguments of the mfm_*_vb entry points (V, V_var
+    column-major), and the arrays they point into"""
+    w0, w0_var, w, w_var, V, V_var = model
+    V, V_var = np.asarray(V, dtype=np.float64), np.asarray(V_var, dtype=np.float64)
+    keep = (_f64(w), _f64(w_var), _f64(V.T), _f64(V_var.T))
+    return V.shape[1], (float(w0), float(w0_var)) + tuple(_p(a) for a in keep), keep
+
+
 def _pack_samples(samples):
     """list of (w0, w[D], V[D, K]) -> K, S, w0s, ws, Vs in the layout of the host-sample entry points"""
     S = len(samples)
@@ -1031,6 +1053,21 @@ class Pairs:
         kk = max(int(k), 1)
         idx, val, mean, std = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk)), np.empty((self.U, kk)), np.empty((self.U, kk))
         self._ck(src.call("mfm_pairs_topk_ucb", self.h, mode, int(k), float(beta), _p(idx), _p(val), _p(mean), _p(std)))
+        return idx, val, mean, std
+
+    def moments_vb(self, model, extra_var=0.0):
+        """(mean (U, I), std (U, I)) of the score of every pair under the mean-field posterior `model` (Design.moments_vb)"""
+        K, head, keep = _pack_vb_model(model)
+        mean, std = np.empty((self.U, self.I)), np.empty((self.U, self.I))
+        self._ck(lib().mfm_pairs_moments_vb(self.h, K, *head, float(extra_var), _p(mean), _p(std)))
+        return mean, std
+
+    def topk_bound_vb(self, model, k, beta, extra_var=0.0):
+        """(indices, value, mean, std), each (U, k): the top k by value = mean + beta * std of the score under `model`"""
+        K, head, keep = _pack_vb_model(model)
+        kk = max(int(k), 1)
+        idx, val, mean, std = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk)), np.empty((self.U, kk)), np.empty((self.U, kk))
+        self._ck(lib().mfm_pairs_topk_bound_vb(self.h, K, *head, float(extra_var), int(k), float(beta), _p(idx), _p(val), _p(mean), _p(std)))
         return idx, val, mean, std
 
     def _rank(self, src, mode):

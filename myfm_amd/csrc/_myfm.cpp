@@ -2622,6 +2622,63 @@ struct VPredictor {
                          const py::object &rq, const py::object &rc) const {
     return mean_predictor().predict_rank(Xq, Xc, targets, exclude, rq, rc);
   }
+  // ---- analytic moments of the score under the mean-field posterior: the six arrays of the one VFM, after ensure()
+  const VFM &posterior() const {
+    if (samples.empty()) throw std::runtime_error("Told to predict but no sample available.");
+    VFM &m = const_cast<VFM &>(samples[0]);
+    m.ensure();
+    const size_t D = feature_size;
+    if (m.w.size() != D || m.w_var.size() != D || m.V.size() != D * rank || m.V_var.size() != D * rank)
+      throw std::invalid_argument("feature size mismatch!");
+    return m;
+  }
+  static void check_extra_var(double extra_var) {
+    if (!(extra_var >= 0.0) || !std::isfinite(extra_var)) throw std::invalid_argument("extra_var must be finite and non-negative");
+  }
+  // (mean (N), std (N)[, Phi(mean / sqrt(1 + var)) (N)]) of the score of every design row
+  py::tuple predict_moments(const py::object &Xo, const py::object &relso, double extra_var, bool want_prob) const {
+    Csr X = csr_from_py(Xo);
+    Relations rels = relations_from_py(relso);
+    Predictor(rank, feature_size, type).check_input(X, rels);
+    check_extra_var(extra_var);
+    const VFM &m = posterior();
+    py::array_t<double> mean((py::ssize_t)X.rows), sd((py::ssize_t)X.rows), prob((py::ssize_t)(want_prob ? X.rows : 0));
+    DeviceDesign dd(X, rels);
+    dd.ck(mfm_design_moments_vb(dd.d, (int32_t)rank, m.w0, m.w0_var, m.w.data(), m.w_var.data(), m.V.data(), m.V_var.data(), extra_var,
+                                want_prob ? 1 : 0, 0, mean.mutable_data(), sd.mutable_data(), want_prob ? prob.mutable_data() : nullptr));
+    if (want_prob) return py::make_tuple(mean, sd, prob);
+    return py::make_tuple(mean, sd);
+  }
+  // the sides of a pair call as the Gibbs predictor checks them; the score is what is summarised, whatever the task
+  Predictor::PairCall vb_pair_call(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
+    Predictor::PairCall pc = Predictor(rank, feature_size, TaskType::REGRESSION).pair_call(Xqo, Xco, rqo, rco);
+    pc.S = (int)samples.size();
+    return pc;
+  }
+  // (mean (U, I), std (U, I)) of the score of every pair
+  py::tuple predict_pairs_moments(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
+    const Predictor::PairCall pc = vb_pair_call(Xqo, Xco, rqo, rco);
+    pc.refuse_every_pair("predict_pairs_moments", "predict_topk_bound");
+    const VFM &m = posterior();
+    py::array_t<double> mean({pc.U(), pc.I()}), sd({pc.U(), pc.I()});
+    const DevicePairs dp = pc.open();
+    dp.ck(mfm_pairs_moments_vb(dp.p, (int32_t)rank, m.w0, m.w0_var, m.w.data(), m.w_var.data(), m.V.data(), m.V_var.data(), 0.0,
+                               mean.mutable_data(), sd.mutable_data()));
+    return py::make_tuple(mean, sd);
+  }
+  // (indices, value, mean, std), each (U, k): the top k by value = mean + beta * std of the score
+  py::tuple predict_topk_bound(const py::object &Xqo, const py::object &Xco, int64_t k, double beta, const py::object &excludeo,
+                               const py::object &rqo, const py::object &rco) const {
+    Predictor::PairCall pc = vb_pair_call(Xqo, Xco, rqo, rco);
+    pc.ranked(k, excludeo, beta);
+    const VFM &m = posterior();
+    py::array_t<int64_t> idx({pc.U(), (py::ssize_t)k});
+    py::array_t<double> value({pc.U(), (py::ssize_t)k}), mean({pc.U(), (py::ssize_t)k}), sd({pc.U(), (py::ssize_t)k});
+    const DevicePairs dp = pc.open();
+    dp.ck(mfm_pairs_topk_bound_vb(dp.p, (int32_t)rank, m.w0, m.w0_var, m.w.data(), m.w_var.data(), m.V.data(), m.V_var.data(), 0.0, (int32_t)k,
+                                  beta, idx.mutable_data(), value.mutable_data(), mean.mutable_data(), sd.mutable_data()));
+    return py::make_tuple(idx, value, mean, sd);
+  }
 };
 
 struct VFMTrainer {
@@ -3349,6 +3406,12 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_rank", &VPredictor::predict_rank, py::arg("X_query"), py::arg("X_cand"), py::arg("targets"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_moments", &VPredictor::predict_moments, py::arg("X"), py::arg("relations") = py::tuple(), py::arg("extra_var") = 0.0,
+           py::arg("want_prob") = false)
+      .def("predict_pairs_moments", &VPredictor::predict_pairs_moments, py::arg("X_query"), py::arg("X_cand"),
+           py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk_bound", &VPredictor::predict_topk_bound, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("beta") = 1.0,
+           py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def(py::pickle(
           [](const VPredictor &p) { return py::make_tuple(p.rank, p.feature_size, static_cast<int>(p.type), p.samples); },
           [](py::tuple t) {

@@ -22,10 +22,13 @@
 // launches nothing, a call without targets or candidates touches no device memory), or the per-sample selecting form
 // (mfm_pairs_topk_samples*, mfm_pairs_topk_prob*; k_pairs_tile_samples and k_pairs_vote of mfm_pairs_samples.hpp, DESIGN 4.13.3:
 // walk_samples below builds each query chunk's plan and walks it in slices).
+// The variational forms (mfm_pairs_moments_vb, mfm_pairs_topk_bound_vb; mfm_pairs_vb.hpp) score a mean-field Gaussian
+// posterior instead of samples: run_pairs_vb at the end of this file, with the memory rule, the chunks and the stripes above.
 #include "mfm_pairs.hpp"
 #include "mfm_pairs_rank.hpp"
 #include "mfm_pairs_samples.hpp"
 #include "mfm_pairs_ucb.hpp"
+#include "mfm_pairs_vb.hpp"
 #include "mfm_samples.hpp"
 
 #include <algorithm>
@@ -1000,6 +1003,273 @@ int mfm_pairs_rank(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *
   PAIRS_TRY(p)
   const PairsRank rk = checked_rank(p, rank_out, value_out);
   run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, 0, nullptr, nullptr, nullptr, nullptr, &rk);
+  PAIRS_CATCH(p)
+}
+
+}  // extern "C"
+
+// ---- the variational forms (mfm_pairs_vb.hpp) ----------------------------------------------------------------------
+// Analytic mean and standard deviation of the score of every pair under the posterior N(w0, w0_var), N(w, w_var), N(V, V_var): five
+// pseudo-samples of width KS through the per-sample contraction. The handle's sides, blocks, exclusions, scratch bound and query
+// chunking are run_pairs', with S = 5 in every formula; the tile shapes are the moments forms' (MT NT = 4).
+namespace {
+
+struct PairsVbForm {
+  int MT, NT;
+  void (*launch)(hipStream_t, dim3, const PairsArgs &);
+  int rows() const { return 16 * MT; }
+  int step() const { return 64 * NT; }
+};
+
+template <int MT, int NT, bool DENSE>
+void launch_vb_form(hipStream_t s, dim3 grid, const PairsArgs &a) {
+  launch_pairs<k_pairs_tile_vb<MT, NT, DENSE>>(s, grid, DENSE ? 0 : PairsSel<MT>::BYTES, a);
+}
+
+PairsVbForm pairs_vb_form(bool dense, int k) {
+  if (dense) return {2, 2, &launch_vb_form<2, 2, true>};
+  if (k <= 64) return {4, 1, &launch_vb_form<4, 1, false>};
+  if (k <= 128) return {2, 2, &launch_vb_form<2, 2, false>};
+  return {1, 4, &launch_vb_form<1, 4, false>};
+}
+
+// the six arrays of a variational model as a C-ABI call hands them over (host memory; V, V_var column-major (D, K))
+struct PairsVbHost {
+  int rank;
+  double w0, w0_var, extra_var;
+  const double *w, *w_var, *V, *V_var;
+};
+
+// the checks of the variational calls that need no device
+void check_vb_model(const mfm_pairs *p, const PairsVbHost &h) {
+  if (h.rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
+  if (!(h.w0_var >= 0.0)) throw Error(MFM_ERR_INVALID, "w0_var must be non-negative");
+  if (!(h.extra_var >= 0.0) || !std::isfinite(h.extra_var)) throw Error(MFM_ERR_INVALID, "extra_var must be finite and non-negative");
+  if (p->D > 0 && (!h.w || !h.w_var || (h.rank > 0 && (!h.V || !h.V_var)))) throw Error(MFM_ERR_INVALID, "no posterior arrays");
+}
+
+// dense != nullptr: (U, I) mean into dense and std into mo.sd; else the top k by mean + mo.beta * std (idx, score, mo.mean, mo.sd)
+void run_pairs_vb(mfm_pairs *p, const PairsVbHost &h, int k, int64_t *idx, double *score, double *dense, const PairsMoments &mo) {
+  check_vb_model(p, h);
+  const bool is_dense = dense != nullptr;
+  if (!is_dense && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  const PairsVbForm form = pairs_vb_form(is_dense, k);
+  const int64_t U = p->U, I = p->I, D = p->D;
+  if (U == 0 || (is_dense && I == 0)) return;
+  hipStream_t s = p->stream;
+  const int S = PAIRS_VB_S, K = h.rank, KS = (K + 3) & ~3, KS4 = KS / 4;
+  const int64_t NK = (int64_t)S * KS4;
+  const int64_t Ipad = round_up(std::max<int64_t>(I, 1), PAIRS_COL_ALIGN);
+
+  // ---- the memory rule of run_pairs: Q and every block table resident, the query scratch bounded
+  const double q_bytes = ((double)Ipad * S * KS + (double)Ipad * S) * sizeof(double);
+  double t_bytes = 0.0;
+  for (int side = 0; side < 2; side++)
+    for (auto &b : p->blocks[side]) t_bytes += (double)b->M * (5 * KS + 3) * sizeof(double);
+  {
+    size_t free_b = 0, total_b = 0;
+    const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && q_bytes + t_bytes > frac * (double)free_b)
+      throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + std::to_string((int64_t)(q_bytes / 1048576.0)) +
+                                       " MB) and the block tables (" + std::to_string((int64_t)(t_bytes / 1048576.0)) +
+                                       " MB) exceed MFM_STORE_MAX_FRACTION of the free device memory; score fewer candidates or smaller blocks per call");
+  }
+  const int64_t W = (I + 31) / 32;
+  const int64_t steps_total = (std::max<int64_t>(I, 1) + form.step() - 1) / form.step();
+  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && !is_dense ? (double)W * 4 : 0.0) +
+                         (is_dense ? (double)I * 16 : (double)(PAIRS_MAX_STRIPES + 1) * k * 12 + (double)k * 16);
+  int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
+  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
+  chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
+
+  // ---- the posterior on the device
+  const size_t DK = (size_t)D * (size_t)K;
+  DevBuf<double> model, d_w0;
+  model.alloc(std::max<size_t>(2 * (size_t)D + 2 * DK, 1));
+  if (D) {
+    MFM_HIP_CHECK(hipMemcpy(model.p, h.w, (size_t)D * sizeof(double), hipMemcpyHostToDevice));
+    MFM_HIP_CHECK(hipMemcpy(model.p + D, h.w_var, (size_t)D * sizeof(double), hipMemcpyHostToDevice));
+    if (K) {
+      MFM_HIP_CHECK(hipMemcpy(model.p + 2 * D, h.V, DK * sizeof(double), hipMemcpyHostToDevice));
+      MFM_HIP_CHECK(hipMemcpy(model.p + 2 * D + DK, h.V_var, DK * sizeof(double), hipMemcpyHostToDevice));
+    }
+  }
+  PairsVbModel pm;
+  pm.w = model.p;
+  pm.wv = model.p + D;
+  pm.V = model.p + 2 * D;
+  pm.Vv = model.p + 2 * D + DK;
+  pm.D = D;
+  pm.K = K;
+  pm.KS = KS;
+  pm.var0 = h.w0_var + h.extra_var;
+  d_w0.upload(std::vector<double>{h.w0, 0.0, 0.0, 0.0, 0.0});
+
+  // ---- the block tables of both sides, once per call
+  std::vector<DevBuf<double>> tables[2];
+  DevBuf<PairsVbBlockRef> d_blk[2];
+  for (int side = 0; side < 2; side++) {
+    std::vector<PairsVbBlockRef> refs;
+    for (auto &b : p->blocks[side]) {
+      const size_t M = (size_t)b->M;
+      tables[side].emplace_back();
+      DevBuf<double> &t = tables[side].back();
+      t.alloc(std::max<size_t>(M * (size_t)(5 * KS + 3), 1));
+      PairsVbBlockRef ref;
+      ref.o2b = b->o2b.p;
+      ref.T = t.p;
+      ref.lin = t.p + M * (size_t)(5 * KS);
+      ref.vv = ref.lin + M;
+      ref.lv = ref.vv + M;
+      ref.M = b->M;
+      refs.push_back(ref);
+      if (b->M > 0) {
+        hipLaunchKernelGGL(k_pairs_vb_embed_block, dim3((unsigned)((b->M + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, b->ptr.p, b->idx.p,
+                           b->val.p, b->M, b->off, pm, t.p, t.p + M * (size_t)(5 * KS), t.p + M * (size_t)(5 * KS + 1),
+                           t.p + M * (size_t)(5 * KS + 2));
+        MFM_HIP_CHECK(hipGetLastError());
+      }
+    }
+    if (!refs.empty()) d_blk[side].upload(refs);
+  }
+  const auto embed = [&](int side, const int64_t *ptr, const int32_t *ci, const double *val, int64_t r0, int64_t R, int64_t Rpad, double *Pf,
+                         double *bias) {
+    const dim3 grid((unsigned)((Rpad + PAIRS_WG - 1) / PAIRS_WG));
+    const bool rel = !p->blocks[side].empty();
+    const PairsVbBlockRef *blk = rel ? (const PairsVbBlockRef *)d_blk[side].p : nullptr;
+    const int n_blk = (int)p->blocks[side].size();
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(PAIRS_WG), 0, s, ptr, ci, val, r0, R, Rpad, pm, blk, n_blk, Pf, bias);
+    };
+    if (side == 1)
+      rel ? launch(k_pairs_vb_embed<true, true>) : launch(k_pairs_vb_embed<false, true>);
+    else
+      rel ? launch(k_pairs_vb_embed<true, false>) : launch(k_pairs_vb_embed<false, false>);
+  };
+
+  // ---- candidate side, once
+  DevBuf<double> Qf, Bb;
+  Qf.alloc((size_t)std::max<int64_t>(Ipad * NK * 4, 1));
+  Bb.alloc((size_t)Ipad * S);
+  embed(1, p->c_ptr.p, p->c_idx.p, p->c_val.p, (int64_t)0, I, Ipad, Qf.p, Bb.p);
+  MFM_HIP_CHECK(hipGetLastError());
+
+  PairsArgs call;
+  std::memset(&call, 0, sizeof(call));
+  call.Qf = Qf.p;
+  call.NK = NK;
+  call.p_stride = NK;
+  call.q_stride = NK;
+  call.KS4 = KS4;
+  call.S = S;
+  call.Bb = Bb.p;
+  call.w0s = d_w0.p;
+  call.beta = mo.beta;
+  call.Ipad = Ipad;
+  call.I = I;
+  call.W = W;
+  call.k = k;
+
+  // ---- queries, chunk by chunk
+  DevBuf<double> Pf, Ab, list_v, out_v, d_dense, d_dense_std, out_m, out_s;
+  DevBuf<int32_t> list_i, out_i;
+  DevBuf<uint32_t> mask;
+  std::vector<int32_t> h_idx;
+  for (int64_t u0 = 0; u0 < U; u0 += chunk) {
+    const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
+    ensure(Pf, (size_t)(Upad * NK * 4));
+    ensure(Ab, (size_t)(Upad * S));
+    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
+    if (use_mask) {
+      ensure(mask, (size_t)(Uc * W));
+      MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), s));
+      hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
+    }
+    const int64_t n_qt = Upad / form.rows();
+    int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_qt - 1) / n_qt, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
+    const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
+    n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
+    const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
+    PairsArgs a = call;
+    a.Pf = Pf.p;
+    a.Ab = Ab.p;
+    a.Upad = Upad;
+    a.Uc = Uc;
+    a.stripe_len = stripe_steps * form.step();
+    a.mask = use_mask ? mask.p : nullptr;
+    a.list_rows = Upad;
+    a.u0 = u0;
+    if (is_dense) {
+      ensure(d_dense, (size_t)(Uc * I));
+      ensure(d_dense_std, (size_t)(Uc * I));
+      a.dense = d_dense.p;
+      a.dense_std = d_dense_std.p;
+      form.launch(s, grid, a);
+      MFM_HIP_CHECK(hipGetLastError());
+      MFM_HIP_CHECK(hipMemcpyAsync(mo.sd + (size_t)u0 * I, d_dense_std.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipStreamSynchronize(s));
+      continue;
+    }
+    ensure(list_v, (size_t)(n_stripes * Upad * k));
+    ensure(list_i, (size_t)(n_stripes * Upad * k));
+    ensure(out_v, (size_t)(Uc * k));
+    ensure(out_i, (size_t)(Uc * k));
+    ensure(out_m, (size_t)(Uc * k));
+    ensure(out_s, (size_t)(Uc * k));
+    a.list_v = list_v.p;
+    a.list_i = list_i.p;
+    if (I > 0) {
+      form.launch(s, grid, a);
+      MFM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, k,
+                       out_v.p, out_i.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_pairs_vb_at, dim3((unsigned)((Uc * k + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, a, out_i.p, Uc * k, out_m.p,
+                       out_s.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    h_idx.resize((size_t)(Uc * k));
+    MFM_HIP_CHECK(hipMemcpyAsync(mo.mean + (size_t)u0 * k, out_m.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipMemcpyAsync(mo.sd + (size_t)u0 * k, out_s.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipMemcpyAsync(score + (size_t)u0 * k, out_v.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), out_i.p, (size_t)(Uc * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipStreamSynchronize(s));
+    for (int64_t e = 0; e < Uc * k; e++) idx[u0 * k + e] = h_idx[(size_t)e];
+  }
+  MFM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfm_pairs_moments_vb(mfm_pairs *p, int32_t rank, double w0, double w0_var, const double *w, const double *w_var, const double *V,
+                         const double *V_var, double extra_var, double *mean, double *sd) {
+  if (!p) {
+    g_pairs_error = "mfm_pairs_moments_vb: no pair design";
+    return MFM_ERR_INVALID;
+  }
+  PAIRS_TRY(p)
+  if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
+  PairsMoments mo;
+  mo.sd = sd;
+  run_pairs_vb(p, PairsVbHost{rank, w0, w0_var, extra_var, w, w_var, V, V_var}, 0, nullptr, nullptr, mean, mo);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_bound_vb(mfm_pairs *p, int32_t rank, double w0, double w0_var, const double *w, const double *w_var, const double *V,
+                            const double *V_var, double extra_var, int32_t k, double beta, int64_t *idx, double *value, double *mean,
+                            double *sd) {
+  if (!p) {
+    g_pairs_error = "mfm_pairs_topk_bound_vb: no pair design";
+    return MFM_ERR_INVALID;
+  }
+  PAIRS_TRY(p)
+  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
+  run_pairs_vb(p, PairsVbHost{rank, w0, w0_var, extra_var, w, w_var, V, V_var}, k, idx, value, nullptr, mo);
   PAIRS_CATCH(p)
 }
 

@@ -343,7 +343,8 @@ def _kept_precisions(est, n_samples, what):
 
 class _PredictiveDistMixin:
     """Posterior predictive summaries of a fitted Gibbs regressor / classifier. MyFMOrderedProbit and the
-    variational estimators have no predict_dist (for ordered probit see predict_proba_dist / predict_expected_dist). Row-sharded
+    variational estimators have no predict_dist (for ordered probit see predict_proba_dist / predict_expected_dist; the variational
+    estimators give the analytic moments of their posterior instead, predict_moments). Row-sharded
     operation is not covered: the model is replicated, so each rank may call predict_dist on its own rows."""
 
     def predict_dist(self, X, X_rel=[], quantiles=(0.05, 0.5, 0.95), noise=False):
@@ -381,8 +382,8 @@ PointwiseDensity = namedtuple("PointwiseDensity", ["lpd", "log_lik_mean", "log_l
 
 class _LogDensityMixin:
     """How probable were the observed targets under the posterior: the pointwise log predictive density of a fitted Gibbs
-    regressor, classifier or ordered probit. The variational estimators keep one point estimate and have no such
-    method. Row-sharded operation is not covered: the model is replicated, so each rank may call it on its own rows."""
+    regressor, classifier or ordered probit. The variational estimators keep no samples (their posterior is one Gaussian,
+    summarised analytically by predict_moments) and have no such method. Row-sharded operation is not covered: the model is replicated, so each rank may call it on its own rows."""
 
     def predict_log_density(self, X, y, X_rel=[], pointwise=False):
         """PointwiseDensity(lpd, log_lik_mean, log_lik_var, pit, log_lik) per test row over the S kept samples, computed on the
@@ -707,8 +708,9 @@ RankedSummary = namedtuple("RankedSummary", ["indices", "value", "mean", "std"])
 
 class _PairUncertaintyMixin:
     """Ranking that counts what the model does not know yet, for the estimators that keep S posterior samples:
-    the Gibbs regressor and classifier and MyFMOrderedProbit. The variational estimators keep one sample, the mean model, and have
-    no spread to rank by. With v_s(u, i) the per-sample value of the pair -- the score for a regressor, Phi(score) for a
+    the Gibbs regressor and classifier and MyFMOrderedProbit. The variational estimators keep one sample, the mean model, and so
+    have no spread over samples; their spread is the analytic one of their Gaussian posterior, and they rank by it with
+    predict_topk_bound (_VariationalMomentsMixin). With v_s(u, i) the per-sample value of the pair -- the score for a regressor, Phi(score) for a
     classifier, the expected class index for ordered probit, i.e. what predict_dist / predict_expected_dist summarise per row --
 
         mean = sum_s v_s / S,    std = the population standard deviation (ddof = 0) of the v_s,    value = mean + beta * std.
@@ -1227,6 +1229,65 @@ class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _Di
         return np.asarray([fm.cutpoints[0] for fm in self.predictor_.samples], dtype=REAL)
 
 
+ScoreMoments = namedtuple("ScoreMoments", ["mean", "std"])
+
+
+class _VariationalMomentsMixin:
+    """What the variational posterior knows about a score. The variational estimators keep one model, but that model
+    is a full mean-field Gaussian posterior -- w0 ~ N(w0_mean, w0_var), w ~ N(w_mean, w_var), V ~ N(V_mean, V_var), independent --
+    under which the FM score of a row has a closed-form mean (the mean model's score, what predict returns) and variance
+
+        Var[score] = w0_var + sum x^2 w_var + sum_k [ M^2 A - 2 M B + C + (A^2 - E) / 2 ]_k,
+        M = sum x m,  A = sum x^2 s,  B = sum x^3 s m,  C = sum x^4 s m^2,  E = sum x^4 s^2     (m = V_mean, s = V_var, per factor).
+
+    The score is not Gaussian; these are its two exact moments, computed on the device for design rows (relation blocks are never
+    expanded) and for every (query, candidate) pair, with the top k by mean + beta * std fused into the pair kernel. Sides,
+    relation-block arguments, the disjoint-columns rule, the exclusions and the memory rule are _PairScoringMixin's; the arguments
+    are validated on the host before the device is touched. Not row-sharded: the model is replicated, so each rank calls on its own
+    rows. Everything here reads the six posterior arrays alone, so it works on an unpickled estimator."""
+
+    def _noise_variance(self, noise):
+        if not noise:
+            return 0.0
+        if self._task_type != TaskType.REGRESSION:
+            raise ValueError("noise=True describes a regression target: it is not available on a classifier")
+        hyper = None if self.history_ is None else self.history_.hypers
+        if hyper is None or not np.isfinite(hyper.alpha) or not hyper.alpha > 0.0:
+            raise RuntimeError("noise=True needs history_ with the fitted noise precision alpha")
+        return 1.0 / float(hyper.alpha)
+
+    def predict_moments(self, X, X_rel=[], noise=False):
+        """ScoreMoments(mean (N,), std (N,)) of the score of every row. mean is predict() of the regressor (the mean model's score
+        for the classifier) bit for bit on a design without relation blocks; std = sqrt(max(Var[score], 0)). noise=True (regressor
+        only, ValueError on the classifier) describes y itself: 1 / alpha, alpha the fitted noise precision (history_.hypers.alpha),
+        is added to the variance."""
+        predictor = self._fetch_predictor()
+        extra_var = self._noise_variance(noise)
+        n = check_data_consistency(X, X_rel)
+        X = _as_csr(X, n)
+        return ScoreMoments(*predictor.predict_moments(X, list(X_rel), extra_var, False))
+
+    def predict_pairs_moments(self, X_query, X_cand, X_rel_query=[], X_rel_cand=[]):
+        """PairSummary(mean (U, I), std (U, I)) of the SCORE of every pair, for both estimators; mean is the regressor's
+        predict_pairs bit for bit. U * I > 2^24 is refused (ValueError): use predict_topk_bound."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        return PairSummary(*predictor.predict_pairs_moments(Xq, Xc, rq, rc))
+
+    def predict_topk_bound(self, X_query, X_cand, k: int, beta: float = 1.0, exclude=None, X_rel_query=[], X_rel_cand=[]):
+        """Per query row the k candidates of largest value = mean + beta * std of the score: RankedSummary(indices int64 (U, k),
+        value, mean, std), each row ordered by (value descending, candidate index ascending). beta may be any finite float:
+        positive ranks by an optimistic bound, negative by a conservative one, 0 by the mean. For the classifier this ranks by a
+        quantile of the probability: Phi is monotone, so the order of mean + beta * std of the score is the order of Phi of it.
+        `exclude` as in predict_topk.
+
+        value is what the selection compared; mean and std are recomputed for the selected pairs with the factors summed in another
+        order, so value equals mean + beta * std within rounding. Where fewer than k candidates remain the tail is index -1, value
+        -inf, mean and std NaN. 1 <= k <= 256 and a finite real beta, else ValueError."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        k, beta, exclude = _ranked_args(Xq, Xc, k, exclude, beta)
+        return RankedSummary(*predictor.predict_topk_bound(Xq, Xc, k, beta, exclude, rq, rc))
+
+
 class MyFMVariationalBase(_FMEstimatorBase):
     """Common part of the variational estimators (src/myfm/variational.py:40-167): the same arguments as the Gibbs
     estimators (exact_latent_draws does not apply), and the posterior means and variances of the final model."""
@@ -1274,7 +1335,7 @@ class MyFMVariationalBase(_FMEstimatorBase):
         return self
 
 
-class VariationalFMRegressor(_PairScoringMixin, MyFMVariationalBase):
+class VariationalFMRegressor(_PairScoringMixin, _VariationalMomentsMixin, MyFMVariationalBase):
     """Bayesian FM regression by mean-field variational inference (variational.py:170-265)."""
 
     # the task hooks of the regression estimators (the two families are siblings, as in the reference)
@@ -1292,7 +1353,7 @@ class VariationalFMRegressor(_PairScoringMixin, MyFMVariationalBase):
         return self._predict_core(X, X_rel)
 
 
-class VariationalFMClassifier(_PairScoringMixin, MyFMVariationalBase):
+class VariationalFMClassifier(_PairScoringMixin, _VariationalMomentsMixin, MyFMVariationalBase):
     """Bayesian FM probit classification by mean-field variational inference (variational.py:268-383)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -1308,6 +1369,15 @@ class VariationalFMClassifier(_PairScoringMixin, MyFMVariationalBase):
     def predict_proba(self, X, X_rel=[]):
         """Phi of the mean model's score (variational.py:366-383)."""
         return self._predict_core(X, X_rel)
+
+    def predict_proba_marginal(self, X, X_rel=[]):
+        """(N,) Phi(mean / sqrt(1 + Var[score])): the probit link integrated over the score's posterior, the score taken as Gaussian
+        with its two exact moments (predict_moments). predict_proba stays the mean model's Phi(mean); this one is pulled towards
+        1/2 where the posterior is wide."""
+        predictor = self._fetch_predictor()
+        n = check_data_consistency(X, X_rel)
+        X = _as_csr(X, n)
+        return predictor.predict_moments(X, list(X_rel), 0.0, True)[2]
 
     def predict(self, X, X_rel=[]):
         return self.predict_proba(X, X_rel) > 0.5
