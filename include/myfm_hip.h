@@ -556,6 +556,48 @@ int mfm_design_crps(mfm_design *d, int32_t rank, int32_t n_samples, const double
 int mfm_crps_row(int32_t task, int32_t S, double y, const double *scores, const double *precisions, int32_t n_cut,
                  const double *cutpoints, double *out);
 
+/* ---- leave-one-out predictions over the kept samples (csrc/mfm_loo_pred.hpp) -------------------------------------
+ * The weights w_s = exp(lw_s) of mfm_design_loo* applied to what the samples predict. The arguments up to tail_len are those of
+ * mfm_design_loo*, out_k[N] is its k^ bit for bit. A row with an l_s of -inf has NaN everywhere and k^ = +inf.
+ * mfm_design_loo_summary*: of the value v_s that mfm_design_summary* summarises (task 0 the score, task 1 Phi(score), task 2 the
+ * expected class index under the sample's cutpoints)
+ *   out_mean[N]   sum_s w_s v_s;   out_std[N]  sqrt(sum_s w_s (v_s - mean)^2)
+ *   out_q[n_q * N]  row-major (n_q, N), n_q <= 32, probs[n_q] in [0, 1] in any order: with the samples ordered by (v_s, s) and c_i the
+ *                 running sum of the weights in that order, v_(0) if c_0 >= p, else for the first i with c_i >= p
+ *                 v_(i-1) + (v_(i) - v_(i-1)) clamp((p - c_(i-1)) / (c_i - c_(i-1)), 0, 1), else v_(S-1)  (the loo package's E_loo)
+ *   out_std_y[N]  task 0 only, may be NULL: sqrt(std^2 + sum_s w_s / precisions[s])
+ *   out_ess[N]    1 / sum_s w_s^2
+ * mfm_design_loo_crps*: mfm_design_crps* with the predictive distribution reweighted (A, g as there)
+ *   task 0        accuracy = sum_s w_s A(y - score_s, v_s), spread = sum_s w_s [sum_{u < s} w_u A(score_s - score_u, v_s + v_u)
+ *                 + w_s g(2 v_s) / 2], crps = accuracy - spread; at most 1024 samples
+ *   tasks 1, 2    d_j = sum_s w_s Phi(+-(cut_sj - score_s)), accuracy = sum_j d_j, spread = sum_j d_j (1 - d_j), crps = sum_j d_j^2
+ * Everything is fp64 and summed in sample order (pair sums in u order, then in s order; cuts in cut order): tile_rows /
+ * chunk_samples do not change a bit. MFM_ERR_INVALID, before the device is used: what mfm_design_loo* refuses, the quantile
+ * refusals of mfm_design_summary*, for the task-0 CRPS more than 1024 samples. N = 0 returns at once.                          */
+int mfm_design_loo_summary_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t task, const double *y,
+                                 const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
+                                 int32_t chunk_samples, int32_t tail_len, int32_t n_q, const double *probs, double *out_mean,
+                                 double *out_std, double *out_q, double *out_std_y, double *out_ess, double *out_k);
+int mfm_design_loo_summary(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                           int32_t task, const double *y, const double *precisions, int32_t n_cut, const double *cutpoints,
+                           int64_t tile_rows, int32_t chunk_samples, int32_t tail_len, int32_t n_q, const double *probs,
+                           double *out_mean, double *out_std, double *out_q, double *out_std_y, double *out_ess, double *out_k);
+int mfm_design_loo_crps_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t task, const double *y,
+                              const double *precisions, int32_t n_cut, const double *cutpoints, int64_t tile_rows,
+                              int32_t chunk_samples, int32_t tail_len, double *out_crps, double *out_accuracy, double *out_spread,
+                              double *out_k);
+int mfm_design_loo_crps(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                        int32_t task, const double *y, const double *precisions, int32_t n_cut, const double *cutpoints,
+                        int64_t tile_rows, int32_t chunk_samples, int32_t tail_len, double *out_crps, double *out_accuracy,
+                        double *out_spread, double *out_k);
+/* one row on the host, by the scalar pieces the kernels run and in their summation orders (no device). Summary: values[S] (v_s) and
+ * log_weights[S], 1 <= S <= 4096; inv_alpha[S] and out_std_y together or both NULL; out_q[n_q] in the order of probs. CRPS:
+ * scores[S], log_weights[S], the constants of mfm_crps_row; out[3] = (crps, accuracy, spread)                                   */
+int mfm_loo_summary_row(int32_t S, const double *values, const double *log_weights, const double *inv_alpha, int32_t n_q,
+                        const double *probs, double *out_mean, double *out_std, double *out_q, double *out_std_y, double *out_ess);
+int mfm_loo_crps_row(int32_t task, int32_t S, double y, const double *scores, const double *log_weights, const double *precisions,
+                     int32_t n_cut, const double *cutpoints, double *out);
+
 /* ---- query x candidate scoring with fused top-k (csrc/mfm_pairs.hip) -----------------------------------------
  * Two sparse sides in the model's full feature space, X_query (U, D) and X_cand (I, D), each optionally with relation blocks
  * (below); pair (u, i) is the design row X_query[u] + X_cand[i]. No column may be stored in both sides (MFM_ERR_INVALID "X_query and X_cand share column

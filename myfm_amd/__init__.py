@@ -25,7 +25,9 @@ from .estimators import (  # noqa: E402
     ChainDiagnostics,
     CrpsScore,
     LikelihoodDiagnostics,
+    LooCrps,
     LooDensity,
+    LooPredictive,
     MyFMClassifier,
     MyFMGibbsClassifier,
     MyFMGibbsRegressor,
@@ -61,6 +63,8 @@ __all__ = [
     "TargetRanks",
     "PointwiseDensity",
     "LooDensity",
+    "LooPredictive",
+    "LooCrps",
     "ChainDiagnostics",
     "LikelihoodDiagnostics",
     "CrpsScore",

@@ -51,6 +51,8 @@ SYMBOLS = [
     "mfm_design_ess_store", "mfm_design_ess", "mfm_ess_row", "mfm_rank_z_table",
     "mfm_design_ess_chains_store", "mfm_design_ess_chains", "mfm_ess_row_chains", "mfm_ess_check_chains", "mfm_ess_max_chains",
     "mfm_design_crps_store", "mfm_design_crps", "mfm_crps_row",
+    "mfm_design_loo_summary_store", "mfm_design_loo_summary", "mfm_design_loo_crps_store", "mfm_design_loo_crps",
+    "mfm_loo_summary_row", "mfm_loo_crps_row",
     "mfm_design_moments_vb", "mfm_pairs_moments_vb", "mfm_pairs_topk_bound_vb",
 ]
 
@@ -214,6 +216,12 @@ def lib():
     L.mfm_design_crps_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, P, P, P]
     L.mfm_design_crps.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, P, P, P]
     L.mfm_crps_row.argtypes = [i32, i32, dbl, P, P, i32, P, P]
+    L.mfm_design_loo_summary_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, i32, i32, P, P, P, P, P, P, P]
+    L.mfm_design_loo_summary.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, i32, i32, P, P, P, P, P, P, P]
+    L.mfm_design_loo_crps_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, i32, P, P, P, P]
+    L.mfm_design_loo_crps.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, i32, P, P, P, P]
+    L.mfm_loo_summary_row.argtypes = [i32, P, P, P, i32, P, P, P, P, P, P]
+    L.mfm_loo_crps_row.argtypes = [i32, i32, dbl, P, P, P, i32, P, P]
     L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
@@ -757,6 +765,34 @@ class Design:
         samples and its two terms; the Brier score for task 1, the ranked probability score for task 2 (mfm_design_crps)."""
         return self._crps(_host(samples), task, y, precisions, cutpoints, tile_rows, chunk_samples)
 
+    def _loo_summary(self, src, task, y, precisions, cutpoints, quantiles, r_eff, tile_rows, chunk_samples):
+        y, prec, n_cut, cp = self._log_density_args(y, precisions, cutpoints)
+        probs = _f64(quantiles).reshape(-1)
+        mean, std, ess, k = np.empty(self.N), np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        q = np.empty((len(probs), self.N))
+        std_y = np.empty(self.N) if task == TASK_REGRESSION else None
+        self._ck(src.call("mfm_design_loo_summary", self.h, int(task), _p(y), _p(prec), n_cut, _p(cp), int(tile_rows), int(chunk_samples),
+                          psis_tail_len(src.S, r_eff), len(probs), _p(probs), _p(mean), _p(std), _p(q), _p(std_y), _p(ess), _p(k)))
+        return mean, std, q, std_y, ess, k
+
+    def loo_summary(self, samples, task, y, precisions=None, cutpoints=None, quantiles=(), r_eff=1.0, tile_rows=0, chunk_samples=0):
+        """samples, task, y, precisions, cutpoints and r_eff as loo. Returns (mean[N], std[N], quantiles[Q, N], std_y[N] or None,
+        ess[N], pareto_k[N]): the leave-one-out weighted summary of the value summary / summary_oprobit(expected) summarise
+        (mfm_design_loo_summary)."""
+        return self._loo_summary(_host(samples), task, y, precisions, cutpoints, quantiles, r_eff, tile_rows, chunk_samples)
+
+    def _loo_crps(self, src, task, y, precisions, cutpoints, r_eff, tile_rows, chunk_samples):
+        y, prec, n_cut, cp = self._log_density_args(y, precisions, cutpoints)
+        crps, accuracy, spread, k = np.empty(self.N), np.empty(self.N), np.empty(self.N), np.empty(self.N)
+        self._ck(src.call("mfm_design_loo_crps", self.h, int(task), _p(y), _p(prec), n_cut, _p(cp), int(tile_rows), int(chunk_samples),
+                          psis_tail_len(src.S, r_eff), _p(crps), _p(accuracy), _p(spread), _p(k)))
+        return crps, accuracy, spread, k
+
+    def loo_crps(self, samples, task, y, precisions=None, cutpoints=None, r_eff=1.0, tile_rows=0, chunk_samples=0):
+        """samples, task, y, precisions, cutpoints and r_eff as loo (task 0: at most 1024 samples). Returns (crps[N], accuracy[N],
+        spread[N], pareto_k[N]): crps with the predictive distribution reweighted by the leave-one-out weights (mfm_design_loo_crps)."""
+        return self._loo_crps(_host(samples), task, y, precisions, cutpoints, r_eff, tile_rows, chunk_samples)
+
     def predict(self, samples, mode=0, cutpoints=None):
         """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
         return self._predict(_host(samples), mode, cutpoints)
@@ -865,6 +901,15 @@ class Store:
     def crps(self, design, task, y, precisions=None, cutpoints=None, first=0, count=None, tile_rows=0, chunk_samples=0):
         """Design.crps over the resident samples [first, first + count) (mfm_design_crps_store)"""
         return design._crps(_resident(self, first, count), task, y, precisions, cutpoints, tile_rows, chunk_samples)
+
+    def loo_summary(self, design, task, y, precisions=None, cutpoints=None, quantiles=(), r_eff=1.0, first=0, count=None, tile_rows=0,
+                    chunk_samples=0):
+        """Design.loo_summary over the resident samples [first, first + count) (mfm_design_loo_summary_store)"""
+        return design._loo_summary(_resident(self, first, count), task, y, precisions, cutpoints, quantiles, r_eff, tile_rows, chunk_samples)
+
+    def loo_crps(self, design, task, y, precisions=None, cutpoints=None, r_eff=1.0, first=0, count=None, tile_rows=0, chunk_samples=0):
+        """Design.loo_crps over the resident samples [first, first + count) (mfm_design_loo_crps_store)"""
+        return design._loo_crps(_resident(self, first, count), task, y, precisions, cutpoints, r_eff, tile_rows, chunk_samples)
 
 
 def crps_row(task, y, scores, precisions=None, cutpoints=None):

@@ -1260,6 +1260,16 @@ struct Predictor {
                      a.cutpoints(), tile_rows, (int32_t)chunk_samples, lpd.mutable_data(), mean.mutable_data(), var.mutable_data(), pit.p, ll.p));
     return py::make_tuple(lpd, mean, var, pit.array, ll.array);
   }
+  // The length of the smoothed tail for r_eff (refused unless one finite positive number), then the sample limit: what
+  // predict_loo, predict_loo_dist and predict_loo_crps check after density_args, in this order
+  int32_t loo_tail_len(double r_eff) const {
+    const size_t S = samples.size();
+    const int32_t tail_len = psis_tail_len(S, r_eff);
+    if (S > (size_t)PSIS_MAX_SAMPLES)
+      throw std::invalid_argument("leave-one-out weights are computed over at most " + std::to_string(PSIS_MAX_SAMPLES) +
+                                  " kept samples, this model keeps " + std::to_string(S));
+    return tail_len;
+  }
   // Pareto-smoothed leave-one-out (not in the reference): (elpd_loo[N], pareto_k[N], lpd[N], loo_pit[N] or None,
   // log_weights[S, N] or None) of the observed y under the kept samples; the arguments of density_args, and the relative efficiency
   // of the draws that sets the length of the smoothed tail.
@@ -1267,10 +1277,7 @@ struct Predictor {
                         const py::object &cutpointso, bool log_weights, double r_eff, int64_t tile_rows, int chunk_samples) const {
     const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
     const py::ssize_t N = (py::ssize_t)a.X.rows, S = (py::ssize_t)samples.size();
-    const int32_t tail_len = psis_tail_len((size_t)S, r_eff);
-    if (S > PSIS_MAX_SAMPLES)
-      throw std::invalid_argument("leave-one-out weights are computed over at most " + std::to_string(PSIS_MAX_SAMPLES) +
-                                  " kept samples, this model keeps " + std::to_string(S));
+    const int32_t tail_len = loo_tail_len(r_eff);
     py::array_t<double> elpd(N), khat(N), lpd(N);
     const OptionalOut pit(type == TaskType::REGRESSION, {N}), lw(log_weights, {S, N});
     DeviceDesign dd(a.X, a.rels);
@@ -1292,6 +1299,41 @@ struct Predictor {
     dd.ck(on_samples(mfm_design_crps_store, mfm_design_crps, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
                      a.cutpoints(), tile_rows, (int32_t)chunk_samples, crps.mutable_data(), accuracy.mutable_data(), spread.mutable_data()));
     return py::make_tuple(crps, accuracy, spread);
+  }
+  // Leave-one-out predictions (not in the reference): the weights of predict_loo applied to what the samples predict.
+  // Both take the arguments of density_args and predict_loo's r_eff (loo_tail_len).
+  // (mean[N], std[N], quantiles[Q, N], std_y[N] or None, ess[N], pareto_k[N]) of the value predict_dist / predict_dist_oprobit(expected)
+  // summarise
+  py::tuple predict_loo_dist(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
+                             const py::object &cutpointso, const py::object &quantileso, double r_eff, int64_t tile_rows,
+                             int chunk_samples) const {
+    const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
+    const vector<double> probs = quantile_probs(quantileso);
+    const int32_t tail_len = loo_tail_len(r_eff);
+    const py::ssize_t N = (py::ssize_t)a.X.rows, n_q = (py::ssize_t)probs.size();
+    py::array_t<double> mean(N), sd(N), ess(N), khat(N), q({n_q, N});
+    const OptionalOut sd_y(type == TaskType::REGRESSION, {N});
+    DeviceDesign dd(a.X, a.rels);
+    dd.ck(on_samples(mfm_design_loo_summary_store, mfm_design_loo_summary, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
+                     a.cutpoints(), tile_rows, (int32_t)chunk_samples, tail_len, (int32_t)n_q, probs.data(), mean.mutable_data(),
+                     sd.mutable_data(), q.mutable_data(), sd_y.p, ess.mutable_data(), khat.mutable_data()));
+    return py::make_tuple(mean, sd, q, sd_y.array, ess, khat);
+  }
+  // (crps[N], accuracy[N], spread[N], pareto_k[N]); regression: at most CRPS_MAX_SAMPLES
+  py::tuple predict_loo_crps(const py::object &Xo, const py::object &relso, const py::object &yo, int task, const py::object &precisionso,
+                             const py::object &cutpointso, double r_eff, int64_t tile_rows, int chunk_samples) const {
+    const DensityArgs a = density_args(Xo, relso, yo, task, precisionso, cutpointso, tile_rows, chunk_samples);
+    const int32_t tail_len = loo_tail_len(r_eff);
+    if (type == TaskType::REGRESSION && samples.size() > (size_t)CRPS_MAX_SAMPLES)
+      throw std::invalid_argument("a regression CRPS is computed over at most " + std::to_string(CRPS_MAX_SAMPLES) +
+                                  " kept samples, this model keeps " + std::to_string(samples.size()));
+    const py::ssize_t N = (py::ssize_t)a.X.rows;
+    py::array_t<double> crps(N), accuracy(N), spread(N), khat(N);
+    DeviceDesign dd(a.X, a.rels);
+    dd.ck(on_samples(mfm_design_loo_crps_store, mfm_design_loo_crps, dd.d, (int32_t)task, a.y.data(), a.precisions(), (int32_t)a.cp.n_cut,
+                     a.cutpoints(), tile_rows, (int32_t)chunk_samples, tail_len, crps.mutable_data(), accuracy.mutable_data(),
+                     spread.mutable_data(), khat.mutable_data()));
+    return py::make_tuple(crps, accuracy, spread, khat);
   }
   // Chain diagnostics over the kept samples in their order (not in the reference). The limit both kinds share:
   void check_ess_limits(int n_chains) const {
@@ -3209,6 +3251,12 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def("predict_crps", &Predictor::predict_crps, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
            py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+      .def("predict_loo_dist", &Predictor::predict_loo_dist, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
+           py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("quantiles") = py::tuple(), py::arg("r_eff") = 1.0,
+           py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+      .def("predict_loo_crps", &Predictor::predict_loo_crps, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
+           py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("r_eff") = 1.0, py::arg("tile_rows") = 0,
+           py::arg("chunk_samples") = 0)
       .def_static("concatenated", &Predictor::concatenated, py::arg("predictors"))
       .def("predict_ess", &Predictor::predict_ess, py::arg("X"), py::arg("rels"), py::arg("cutpoint_index") = 0, py::arg("tile_rows") = 0,
            py::arg("chunk_samples") = 0, py::arg("n_chains") = 1)
@@ -3530,6 +3578,56 @@ PYBIND11_MODULE(_myfm, m) {
         return py::make_tuple(out[0], out[1], out[2]);
       },
       py::arg("task"), py::arg("y"), py::arg("scores"), py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none());
+  // one row of the leave-one-out summary on the host, by the scalar pieces k_row_loo_summary runs on the device and in its orders
+  // (csrc/mfm_loo_pred.hpp): values[S] (what the kernel forms from the score), log_weights[S]; (mean, std, quantiles[Q], std_y or None, ess)
+  using RowArray = py::array_t<double, py::array::c_style | py::array::forcecast>;
+  m.def(
+      "loo_summary_row",
+      [](const RowArray &values, const RowArray &log_weights, const RowArray &quantiles, const py::object &inv_alpha) {
+        if (values.ndim() != 1 || values.shape(0) < 1) throw std::invalid_argument("values must be a non-empty 1-D array");
+        const py::ssize_t S = values.shape(0);
+        if (log_weights.ndim() != 1 || log_weights.shape(0) != S) throw std::invalid_argument("log_weights hold one entry per value");
+        if (quantiles.ndim() != 1) throw std::invalid_argument("quantiles must be a 1-D sequence of probabilities");
+        RowArray ia;
+        if (!inv_alpha.is_none()) {
+          ia = RowArray::ensure(inv_alpha);
+          if (!ia || ia.ndim() != 1 || ia.shape(0) != S) throw std::invalid_argument("inv_alpha holds one entry per value");
+        }
+        py::array_t<double> q(quantiles.shape(0));
+        double mean = 0.0, sd = 0.0, sd_y = 0.0, ess = 0.0;
+        const bool noise = !inv_alpha.is_none();
+        const int code = mfm_loo_summary_row((int32_t)std::min<py::ssize_t>(S, PSIS_MAX_SAMPLES + 1), values.data(), log_weights.data(),
+                                             noise ? ia.data() : nullptr, (int32_t)std::min<py::ssize_t>(quantiles.shape(0), 33),
+                                             quantiles.data(), &mean, &sd, q.mutable_data(), noise ? &sd_y : nullptr, &ess);
+        if (code != MFM_OK) throw_code(code, mfm_global_error());
+        return py::make_tuple(mean, sd, q, noise ? py::object(py::float_(sd_y)) : py::object(py::none()), ess);
+      },
+      py::arg("values"), py::arg("log_weights"), py::arg("quantiles") = RowArray(0), py::arg("inv_alpha") = py::none());
+  // the leave-one-out CRPS of one row on the host, by the functions k_row_loo_crps_mix / k_row_loo_crps_cdf run on the device and in
+  // their summation orders: (crps, accuracy, spread)
+  m.def(
+      "loo_crps_row",
+      [](int task, double y, const RowArray &scores, const RowArray &log_weights, const py::object &precisions, const py::object &cutpoints) {
+        if (scores.ndim() != 1 || scores.shape(0) < 1) throw std::invalid_argument("scores must be a non-empty 1-D array");
+        const py::ssize_t S = scores.shape(0);
+        if (log_weights.ndim() != 1 || log_weights.shape(0) != S) throw std::invalid_argument("log_weights hold one entry per score");
+        vector<double> prec;
+        if (!precisions.is_none()) prec = precisions.cast<vector<double>>();
+        RowArray cut;
+        if (!cutpoints.is_none()) {
+          cut = RowArray::ensure(cutpoints);
+          if (!cut || cut.ndim() != 2) throw std::invalid_argument("cutpoints must be a 2-D array, one row of n_cut cutpoints per sample");
+        }
+        if ((!precisions.is_none() && (py::ssize_t)prec.size() != S) || (!cutpoints.is_none() && cut.shape(0) != S))
+          throw std::invalid_argument("precisions and cutpoints hold one entry per score");
+        double out[3] = {0.0, 0.0, 0.0};
+        const int code = mfm_loo_crps_row(task, (int32_t)S, y, scores.data(), log_weights.data(), precisions.is_none() ? nullptr : prec.data(),
+                                          cutpoints.is_none() ? 0 : (int32_t)cut.shape(1), cutpoints.is_none() ? nullptr : cut.data(), out);
+        if (code != MFM_OK) throw_code(code, mfm_global_error());
+        return py::make_tuple(out[0], out[1], out[2]);
+      },
+      py::arg("task"), py::arg("y"), py::arg("scores"), py::arg("log_weights"), py::arg("precisions") = py::none(),
+      py::arg("cutpoints") = py::none());
   // the rank-normalised values of S draws by twice the average rank, table[2S - 1], as the device is handed them
   m.def(
       "rank_z_table",

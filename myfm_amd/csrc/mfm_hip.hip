@@ -2790,4 +2790,5 @@ int mfm_host_column_levels(int64_t n_rows, int64_t n_cols, const int64_t *indptr
 #include "mfm_psis.hpp"     // ... and Pareto-smoothed leave-one-out on top of it
 #include "mfm_ess.hpp"      // ... and the chain diagnostics of the values both are computed from
 #include "mfm_crps.hpp"     // ... and the continuous ranked probability score (after mfm_logdens.hpp: its checks and uploads)
+#include "mfm_loo_pred.hpp"  // ... and the leave-one-out weighted summaries and CRPS (after mfm_psis.hpp and mfm_crps.hpp)
 #include "mfm_vbmoments.hpp"  // ... and the analytic score moments of the variational posterior (mfm_design_moments_vb)

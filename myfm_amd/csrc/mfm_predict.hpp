@@ -269,6 +269,7 @@ struct mfm_design {
   DevBuf<const double *> wvp;      // ... and the samples' buffers
   DevBuf<double> dist_scratch, dist_out, dist_aux;  // posterior summaries (mfm_dist.hpp): [S][T] values of a row tile, outputs, sqrt(alpha)
   DevBuf<double> dist_y;                            // log densities (mfm_logdens.hpp): the observed targets
+  DevBuf<double> loo_scores, loo_aux;               // leave-one-out predictions (mfm_loo_pred.hpp): a tile's scores beside its weights, that file's constants
   PinnedRing ring;
   Timing timing;
   ~mfm_design() {

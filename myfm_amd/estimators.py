@@ -433,6 +433,8 @@ class _LogDensityMixin:
 
 
 LooDensity = namedtuple("LooDensity", ["elpd_loo", "pareto_k", "lpd", "loo_pit", "log_weights"])
+LooPredictive = namedtuple("LooPredictive", ["mean", "std", "quantiles", "std_y", "ess", "pareto_k"])
+LooCrps = namedtuple("LooCrps", ["crps", "accuracy", "spread", "pareto_k"])
 PREDICT_LOO_MAX_SAMPLES = PREDICT_DIST_MAX_SAMPLES  # a row's importance ratios are sorted in the device's local memory
 
 
@@ -441,7 +443,9 @@ class _LooMixin(_LogDensityMixin):
     4.9.3), after Vehtari, Gelman and Gabry (2017) and Vehtari et al. (2024). Limits: one tail length for all rows (r_eff is one
     number, given or with "auto" the mean of the rows' estimates from the chain: no per-row tail length); no moment matching or
     refit for rows with a large k; at most 4096 kept samples; no variational estimator; not row-sharded (the model is replicated:
-    each rank may call it on its own rows)."""
+    each rank may call it on its own rows). predict_loo_dist and predict_loo_crps apply the same weights to what
+    the samples predict; their further limits: at most 32 quantiles, a regressor CRPS over at most 1024 kept samples, and one k
+    per row -- no separate Pareto fit per summarised function."""
 
     def predict_loo(self, X, y, X_rel=[], log_weights=False, r_eff=1.0):
         """LooDensity(elpd_loo, pareto_k, lpd, loo_pit, log_weights) per row over the S kept samples, computed on the device in one
@@ -467,19 +471,74 @@ class _LooMixin(_LogDensityMixin):
     def _predict_loo(self, X, y, X_rel, log_weights, r_eff, cutpoint_index):
         if not isinstance(log_weights, (bool, np.bool_)):
             raise ValueError("log_weights must be a bool")
+        predictor, args, r_eff = self._loo_args(X, y, X_rel, r_eff, cutpoint_index, "predict_loo")
+        return LooDensity(*predictor.predict_loo(*args, bool(log_weights), r_eff))
+
+    def _loo_args(self, X, y, X_rel, r_eff, cutpoint_index, what, max_samples=None):
+        """(predictor, the arguments of _log_density_args, r_eff as one number): what every leave-one-out method checks, in
+        predict_loo's order, and "auto" resolved. max_samples: (limit, message) of a method with a limit of its own."""
         auto = isinstance(r_eff, str) and r_eff == "auto"
         if not auto and (isinstance(r_eff, (bool, np.bool_)) or not isinstance(r_eff, (int, float, np.integer, np.floating))
                          or not np.isfinite(r_eff) or not r_eff > 0):
             raise ValueError("r_eff must be one finite positive number, or \"auto\"")
-        predictor, args = self._log_density_args(X, y, X_rel, cutpoint_index, "predict_loo")
+        predictor, args = self._log_density_args(X, y, X_rel, cutpoint_index, what)
         n_samples = len(predictor.samples)
         if n_samples > PREDICT_LOO_MAX_SAMPLES:
             raise ValueError("leave-one-out weights are computed over at most %d kept samples, this model keeps %d"
                              % (PREDICT_LOO_MAX_SAMPLES, n_samples))
+        if max_samples is not None and n_samples > max_samples[0]:
+            raise ValueError(max_samples[1] % (max_samples[0], n_samples))
         if auto:  # the chain's own estimate, one number for all rows (as arviz hands PSIS one)
             per_row = np.asarray(predictor.likelihood_ess(*args, n_chains=int(getattr(self, "n_chains_", 1)))[2])
             r_eff = float(np.nanmean(per_row)) if np.any(np.isfinite(per_row)) else 1.0  # (a row is finite or NaN)
-        return LooDensity(*predictor.predict_loo(*args, bool(log_weights), float(r_eff)))
+        return predictor, args, float(r_eff)
+
+    def predict_loo_dist(self, X, y, X_rel=[], quantiles=(0.05, 0.5, 0.95), r_eff=1.0):
+        """LooPredictive(mean, std, quantiles, std_y, ess, pareto_k) per row: what the model predicts for a row it was fitted on
+        when that row is left out, computed on the device in one pass over the rows. The per-sample value v_s is
+        that of predict_dist / predict_expected_dist -- the score for a regressor, Phi(score) for a classifier, the expected class
+        index for ordered probit -- and the weights are w_s = exp(log_weights) of predict_loo, which never leave the device.
+
+        mean (N,): sum_s w_s v_s. std (N,): sqrt(sum_s w_s (v_s - mean)^2), the mean taken first. quantiles (Q, N): the
+        inverse-CDF rule of the loo package's E_loo -- with the samples ordered by (v_s, s) and c_i the running sum of the weights
+        in that order, the quantile at p is v_(0) if c_0 >= p; else, for the first i with c_i >= p, v_(i-1) + (v_(i) - v_(i-1))
+        (p - c_(i-1)) / (c_i - c_(i-1)); v_(S-1) if rounding leaves no such i. With equal weights this is not np.quantile's
+        "linear" rule (which predict_dist follows): it inverts the step function of the weights and interpolates inside a step.
+        std_y (N,), regressor only (else None): sqrt(std^2 + sum_s w_s / alpha_s), the leave-one-out predictive standard deviation
+        of y itself, what a standardised leave-one-out residual divides by. ess (N,): 1 / sum_s w_s^2, Kish's effective number of
+        weights. pareto_k (N,): predict_loo's, bit for bit. A row whose y has density 0 under some sample has NaN everywhere and
+        pareto_k = +inf. See myfm_amd.utils.evaluation.loo_residuals.
+
+        Limits: at most 32 quantiles (`quantiles` may be empty); at most 4096 kept samples; one k per row, that of the weights --
+        no separate Pareto fit per summarised function, which E_loo makes for h r. r_eff as predict_loo takes it. X, y, X_rel
+        (MyFMOrderedProbit: cutpoint_index) as predict_log_density takes and checks them; all arguments are checked on the host
+        before the device is touched."""
+        return self._predict_loo_dist(X, y, X_rel, quantiles, r_eff, None)
+
+    def _predict_loo_dist(self, X, y, X_rel, quantiles, r_eff, cutpoint_index):
+        probs = _checked_quantiles(quantiles)
+        predictor, args, r_eff = self._loo_args(X, y, X_rel, r_eff, cutpoint_index, "predict_loo_dist")
+        return LooPredictive(*predictor.predict_loo_dist(*args, probs, r_eff))
+
+    def predict_loo_crps(self, X, y, X_rel=[], r_eff=1.0):
+        """LooCrps(crps, accuracy, spread, pareto_k) per row: predict_crps with the predictive distribution reweighted by the
+        leave-one-out weights w_s of predict_loo, on the device in one pass over the rows. Regressor: the mixture
+        sum_s w_s N(score_s, 1 / alpha_s), accuracy = sum_s w_s A(y - score_s, v_s), spread = sum_s w_s [sum_{u < s} w_u
+        A(score_s - score_u, v_s + v_u) + w_s g(2 v_s) / 2], crps = accuracy - spread; at most 1024 kept samples. Classifier and
+        ordered probit: d_j = sum_s w_s Phi(+-(cut_sj - score_s)) in the place of predict_crps' mean, crps = sum_j d_j^2. With
+        equal weights it is predict_crps. pareto_k (N,): predict_loo's, bit for bit; a row whose y has density 0 under some sample
+        has NaN scores. myfm_amd.utils.evaluation.crps_summary takes the result as it takes predict_crps'.
+
+        r_eff as predict_loo takes it; X, y, X_rel (MyFMOrderedProbit: cutpoint_index) as predict_log_density takes and checks
+        them; all arguments are checked on the host before the device is touched."""
+        return self._predict_loo_crps(X, y, X_rel, r_eff, None)
+
+    def _predict_loo_crps(self, X, y, X_rel, r_eff, cutpoint_index):
+        limit = None
+        if self._task_type == TaskType.REGRESSION:
+            limit = (PREDICT_CRPS_MAX_SAMPLES, "a regression CRPS is computed over at most %d kept samples, this model keeps %d")
+        predictor, args, r_eff = self._loo_args(X, y, X_rel, r_eff, cutpoint_index, "predict_loo_crps", limit)
+        return LooCrps(*predictor.predict_loo_crps(*args, r_eff))
 
 
 CrpsScore = namedtuple("CrpsScore", ["crps", "accuracy", "spread"])
@@ -489,8 +548,8 @@ PREDICT_CRPS_MAX_SAMPLES = 1024  # regressor: a row costs S (S + 1) / 2 pair ter
 class _CrpsMixin(_LogDensityMixin):
     """The continuous ranked probability score of a fitted Gibbs regressor, classifier or ordered probit: the
     proper scoring rule in the units of y, which reduces to the absolute error for a point forecast and which no single row
-    dominates as it can the log score. Limits: a regressor with at most 1024 kept samples; no leave-one-out weighted CRPS; no
-    variational estimator; one cutpoint group per call; not row-sharded (the model is replicated: each rank may call it on its
+    dominates as it can the log score. Limits: a regressor with at most 1024 kept samples (the leave-one-out weighted
+    form is predict_loo_crps); no variational estimator; one cutpoint group per call; not row-sharded (the model is replicated: each rank may call it on its
     own rows)."""
 
     def predict_crps(self, X, y, X_rel=[]):
@@ -1208,6 +1267,15 @@ class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _Di
     def predict_loo(self, X, y, X_rel=[], log_weights=False, r_eff=1.0, cutpoint_index=0):
         """_LooMixin.predict_loo with the cutpoint group to use, as predict_log_density takes it."""
         return self._predict_loo(X, y, X_rel, log_weights, r_eff, cutpoint_index)
+
+    def predict_loo_dist(self, X, y, X_rel=[], quantiles=(0.05, 0.5, 0.95), r_eff=1.0, cutpoint_index=0):
+        """_LooMixin.predict_loo_dist of the expected class index sum_c c p_c under the cutpoints of group `cutpoint_index`, the
+        value predict_expected_dist summarises."""
+        return self._predict_loo_dist(X, y, X_rel, quantiles, r_eff, cutpoint_index)
+
+    def predict_loo_crps(self, X, y, X_rel=[], r_eff=1.0, cutpoint_index=0):
+        """_LooMixin.predict_loo_crps with the cutpoint group to use: the leave-one-out ranked probability score."""
+        return self._predict_loo_crps(X, y, X_rel, r_eff, cutpoint_index)
 
     def predict_crps(self, X, y, X_rel=[], cutpoint_index=0):
         """_CrpsMixin.predict_crps with the cutpoint group to use, as predict_log_density takes it: the ranked probability score."""

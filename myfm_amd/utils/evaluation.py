@@ -1,6 +1,7 @@
 """Model evaluation from the pointwise log predictive density (predict_log_density) and from Pareto-smoothed
 leave-one-out (predict_loo), a digest of the chain diagnostics and of the continuous ranked
-probability score (predict_crps). Pure NumPy."""
+probability score (predict_crps), and the residuals of the leave-one-out predictions (predict_loo_dist).
+Pure NumPy."""
 import numpy as np
 
 WAIC_HIGH_VARIANCE = 0.4  # a row whose log-likelihood variance exceeds this makes WAIC unreliable (Vehtari, Gelman, Gabry 2017)
@@ -212,4 +213,38 @@ def crps_summary(result, reference=None):
             raise ValueError("the two results must hold one value per row of the same rows")
         out["skill"] = 1.0 - float(c.mean()) / float(r.mean()) if n else nan
         out["se_diff"] = float(np.sqrt(np.var(c - r) / n)) if n else nan
+    return out
+
+
+def loo_residuals(result, y, interval=None):
+    """What a LooPredictive `result` (predict_loo_dist) says about the targets y (N,) of the rows it was computed on,
+    each predicted without itself. Returns a dict:
+
+        residuals      y - mean (N,)
+        rmse, mae      sqrt(mean_t residual_t^2), mean_t |residual_t|
+        r2             1 - var_t(residual_t) / var_t(y_t), the leave-one-out R^2 (population variances over the rows)
+        standardized   (y - mean) / std_y (N,), for a regressor (std_y is None otherwise: None)
+        coverage       with interval = (lo_index, hi_index) into the quantile axis of `result`, the share of rows with
+                       quantiles[lo_index] <= y <= quantiles[hi_index] (else None)
+
+    Rows whose prediction is NaN (a target of density 0 under some sample) make the means NaN: drop them first."""
+    y = np.asarray(y, dtype=np.float64)
+    mean = np.asarray(result.mean, dtype=np.float64)
+    if y.ndim != 1 or mean.ndim != 1 or y.shape != mean.shape:
+        raise ValueError("y must hold one value per row of the result")
+    res = y - mean
+    n = y.shape[0]
+    nan = float("nan")
+    var_y = float(np.var(y)) if n else nan
+    out = {"residuals": res, "rmse": float(np.sqrt(np.mean(res * res))) if n else nan, "mae": float(np.mean(np.abs(res))) if n else nan,
+           "r2": 1.0 - float(np.var(res)) / var_y if n and var_y > 0.0 else nan,
+           "standardized": None if result.std_y is None else res / np.asarray(result.std_y, dtype=np.float64), "coverage": None}
+    if interval is not None:
+        q = np.asarray(result.quantiles, dtype=np.float64)
+        lo, hi = interval
+        if isinstance(lo, bool) or isinstance(hi, bool) or not all(isinstance(i, (int, np.integer)) for i in (lo, hi)):
+            raise ValueError("interval must be two indices into the quantile axis")
+        if q.ndim != 2 or q.shape[1] != n or not (0 <= lo < q.shape[0] and 0 <= hi < q.shape[0]):
+            raise ValueError("interval must be two indices into the quantile axis")
+        out["coverage"] = float(np.mean((q[lo] <= y) & (y <= q[hi]))) if n else nan
     return out
