@@ -556,6 +556,33 @@ int mfm_design_crps(mfm_design *d, int32_t rank, int32_t n_samples, const double
 int mfm_crps_row(int32_t task, int32_t S, double y, const double *scores, const double *precisions, int32_t n_cut,
                  const double *cutpoints, double *out);
 
+/* ---- the score taken apart by field, over the kept samples (csrc/mfm_contrib.hpp) -------------------------------
+ * field_of[n_field_of] gives every column of the flat design (main columns, then the relation blocks') a field in [0, n_fields).
+ * For a design row x and a sample s:  p_g[k] = sum_{j in g} x_j V_s[k, j],  q_g = sum_{j in g} x_j^2 sum_k V_s[k, j]^2,
+ *   lin_g = sum_{j in g} x_j w_s[j],   I_gg = (sum_k p_g[k]^2 - q_g) / 2,   I_gh = sum_k p_g[k] p_h[k]  (g < h),
+ *   score_s = w0_s + sum_g lin_g + sum_{g <= h} I_gh.
+ * Per row and component the mean and the population standard deviation over the samples (a streaming mean and M2 in sample
+ * order), components along the first axis:
+ *   out_bias[2]                          mean and standard deviation of w0
+ *   out_linear, out_linear_std           (F, N)
+ *   out_interaction, out_interaction_std (P, N), P = F (F + 1) / 2, pair (g, h), g <= h, at row g F - g (g - 1) / 2 + (h - g)
+ * Everything is fp64 without atomics; tile_rows / chunk_samples (0: automatic) do not change a bit of the results. Relation blocks
+ * are read in place. MFM_ERR_INVALID, before the device is used: n_fields outside [1, 16], n_field_of different from the design's
+ * number of columns, a field outside [0, n_fields), a negative tiling override, a missing output; then the checks of the sample
+ * source. N = 0 returns after out_bias is written. The upload rule of the host flavour is that of mfm_design_summary.       */
+int mfm_design_contrib_store(mfm_design *d, mfm_store *st, int32_t first, int32_t count, int32_t n_fields, const int32_t *field_of,
+                             int64_t n_field_of, int64_t tile_rows, int32_t chunk_samples, double *out_bias, double *out_linear,
+                             double *out_linear_std, double *out_interaction, double *out_interaction_std);
+int mfm_design_contrib(mfm_design *d, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t n_fields, const int32_t *field_of, int64_t n_field_of, int64_t tile_rows, int32_t chunk_samples,
+                       double *out_bias, double *out_linear, double *out_linear_std, double *out_interaction,
+                       double *out_interaction_std);
+/* one row on the host, by the functions the kernel runs and in its orders (no device): the row's n entries (idx, val) in the flat
+ * design of D columns, in the order main matrix, then block by block; ws[S * D], Vs[S * rank * D] (factor-major per sample);
+ * out_mean[F + P], out_std[F + P]: the linear terms, then the interactions                                                    */
+int mfm_contrib_row(int32_t n, const int32_t *idx, const double *val, int64_t D, int32_t rank, int32_t S, const double *ws,
+                    const double *Vs, int32_t n_fields, const int32_t *field_of, int64_t n_field_of, double *out_mean, double *out_std);
+
 /* ---- leave-one-out predictions over the kept samples (csrc/mfm_loo_pred.hpp) -------------------------------------
  * The weights w_s = exp(lw_s) of mfm_design_loo* applied to what the samples predict. The arguments up to tail_len are those of
  * mfm_design_loo*, out_k[N] is its k^ bit for bit. A row with an l_s of -inf has NaN everywhere and k^ = +inf.

@@ -37,6 +37,7 @@ from .estimators import (  # noqa: E402
     PointwiseDensity,
     RankedSummary,
     SampleRankings,
+    ScoreContributions,
     ScoreMoments,
     TargetRanks,
     ThompsonRanking,
@@ -68,6 +69,7 @@ __all__ = [
     "ChainDiagnostics",
     "LikelihoodDiagnostics",
     "CrpsScore",
+    "ScoreContributions",
     "SampleRankings",
     "ThompsonRanking",
     "TopKProbability",

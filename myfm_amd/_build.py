@@ -17,7 +17,7 @@ PYMOD = os.path.join(HERE, "_myfm" + EXT_SUFFIX)
 # its object file; the objects live in csrc/_obj/, git-ignored)
 HIP_UNITS = {
     "mfm_hip.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_policies.hpp", "mfm_kernels.hpp", "mfm_mf_kernels.hpp", "mfm_res.hpp", "mfm_res_entry.hpp", "mfm_res_plan.hpp",
-                    "mfm_plan.hpp", "mfm_block_kernels.hpp", "mfm_erfcx.hpp", "mfm_tasks.hpp", "mfm_tn.hpp", "mfm_philox.hpp", "mfm_predict.hpp", "mfm_samples.hpp", "mfm_dist.hpp", "mfm_logdens.hpp", "mfm_psis.hpp", "mfm_ess.hpp", "mfm_crps.hpp", "mfm_loo_pred.hpp", "mfm_normal_quantile.hpp", "mfm_rng.hpp", "mfm_mtjump.hpp", "mfm_cell.hpp",
+                    "mfm_plan.hpp", "mfm_block_kernels.hpp", "mfm_erfcx.hpp", "mfm_tasks.hpp", "mfm_tn.hpp", "mfm_philox.hpp", "mfm_predict.hpp", "mfm_samples.hpp", "mfm_dist.hpp", "mfm_contrib.hpp", "mfm_logdens.hpp", "mfm_psis.hpp", "mfm_ess.hpp", "mfm_crps.hpp", "mfm_loo_pred.hpp", "mfm_normal_quantile.hpp", "mfm_rng.hpp", "mfm_mtjump.hpp", "mfm_cell.hpp",
                     "mfm_chain_api.hpp", "mfm_rng_state.hpp", "mfm_latent_api.hpp", "mfm_latent_host.hpp", "mfm_comm.hpp", "mfm_vbmoments.hpp", "mfm_vb_sums.hpp"],
     "mfm_latent.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_rng_state.hpp", "mfm_latent_api.hpp"],
     "mfm_cell.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_cell.hpp"],

@@ -53,6 +53,7 @@ SYMBOLS = [
     "mfm_design_crps_store", "mfm_design_crps", "mfm_crps_row",
     "mfm_design_loo_summary_store", "mfm_design_loo_summary", "mfm_design_loo_crps_store", "mfm_design_loo_crps",
     "mfm_loo_summary_row", "mfm_loo_crps_row",
+    "mfm_design_contrib_store", "mfm_design_contrib", "mfm_contrib_row",
     "mfm_design_moments_vb", "mfm_pairs_moments_vb", "mfm_pairs_topk_bound_vb",
 ]
 
@@ -218,6 +219,9 @@ def lib():
     L.mfm_crps_row.argtypes = [i32, i32, dbl, P, P, i32, P, P]
     L.mfm_design_loo_summary_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, i32, i32, P, P, P, P, P, P, P]
     L.mfm_design_loo_summary.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, i32, i32, P, P, P, P, P, P, P]
+    L.mfm_design_contrib_store.argtypes = [vp, vp, i32, i32, i32, P, i64, i64, i32, P, P, P, P, P]
+    L.mfm_design_contrib.argtypes = [vp, i32, i32, P, P, P, i32, P, i64, i64, i32, P, P, P, P, P]
+    L.mfm_contrib_row.argtypes = [i32, P, P, i64, i32, i32, P, P, i32, P, i64, P, P]
     L.mfm_design_loo_crps_store.argtypes = [vp, vp, i32, i32, i32, P, P, i32, P, i64, i32, i32, P, P, P, P]
     L.mfm_design_loo_crps.argtypes = [vp, i32, i32, P, P, P, i32, P, P, i32, P, i64, i32, i32, P, P, P, P]
     L.mfm_loo_summary_row.argtypes = [i32, P, P, P, i32, P, P, P, P, P, P]
@@ -793,6 +797,22 @@ class Design:
         spread[N], pareto_k[N]): crps with the predictive distribution reweighted by the leave-one-out weights (mfm_design_loo_crps)."""
         return self._loo_crps(_host(samples), task, y, precisions, cutpoints, r_eff, tile_rows, chunk_samples)
 
+    def _contributions(self, src, n_fields, field_of, tile_rows, chunk_samples):
+        F = int(n_fields)
+        fo = np.ascontiguousarray(np.asarray(field_of).reshape(-1), dtype=np.int32)
+        Pn = max(F, 0) * (max(F, 0) + 1) // 2
+        bias, lin, lin_std = np.empty(2), np.empty((max(F, 0), self.N)), np.empty((max(F, 0), self.N))
+        inter, inter_std = np.empty((Pn, self.N)), np.empty((Pn, self.N))
+        self._ck(src.call("mfm_design_contrib", self.h, F, _p(fo), fo.shape[0], int(tile_rows), int(chunk_samples), _p(bias), _p(lin),
+                          _p(lin_std), _p(inter), _p(inter_std)))
+        return bias[0], bias[1], lin, lin_std, inter, inter_std
+
+    def contributions(self, samples, n_fields, field_of, tile_rows=0, chunk_samples=0):
+        """samples as predict; field_of[D] in [0, n_fields), n_fields <= 16. Returns (bias, bias_std, linear[F, N], linear_std[F, N],
+        interaction[P, N], interaction_std[P, N]): mean and population standard deviation over the samples of every field's linear
+        term and every field pair's interaction, pair (g, h), g <= h, at g F - g (g - 1) / 2 + (h - g) (mfm_design_contrib)."""
+        return self._contributions(_host(samples), n_fields, field_of, tile_rows, chunk_samples)
+
     def predict(self, samples, mode=0, cutpoints=None):
         """samples: list of (w0, w[D], V[D, K]); mode 0 mean score, 1 mean Phi(score), 2 ordered probit."""
         return self._predict(_host(samples), mode, cutpoints)
@@ -910,6 +930,30 @@ class Store:
     def loo_crps(self, design, task, y, precisions=None, cutpoints=None, r_eff=1.0, first=0, count=None, tile_rows=0, chunk_samples=0):
         """Design.loo_crps over the resident samples [first, first + count) (mfm_design_loo_crps_store)"""
         return design._loo_crps(_resident(self, first, count), task, y, precisions, cutpoints, r_eff, tile_rows, chunk_samples)
+
+
+    def contributions(self, design, n_fields, field_of, first=0, count=None, tile_rows=0, chunk_samples=0):
+        """Design.contributions over the resident samples [first, first + count) (mfm_design_contrib_store)"""
+        return design._contributions(_resident(self, first, count), n_fields, field_of, tile_rows, chunk_samples)
+
+
+def contrib_row(idx, val, samples, n_fields, field_of):
+    """(mean[F + P], std[F + P]) of one row's components on the host, by the functions the device runs and in its orders: the
+    row's entries (idx, val) in the flat design, samples a list of (w0, w[D], V[D, K]) (mfm_contrib_row)"""
+    K, S, _, ws, Vs = _pack_samples(samples)
+    D = np.asarray(samples[0][1]).shape[0] if S else 0
+    idx = np.ascontiguousarray(np.asarray(idx).reshape(-1), dtype=np.int32)
+    val = _f64(val).reshape(-1)
+    if idx.shape[0] != val.shape[0]:
+        raise ValueError("idx and val hold one entry each per stored element of the row")
+    fo = np.ascontiguousarray(np.asarray(field_of).reshape(-1), dtype=np.int32)
+    F = int(n_fields)
+    n_out = max(F, 0) + max(F, 0) * (max(F, 0) + 1) // 2
+    mean, std = np.empty(n_out), np.empty(n_out)
+    rc = lib().mfm_contrib_row(idx.shape[0], _p(idx), _p(val), D, K, S, _p(ws), _p(Vs), F, _p(fo), fo.shape[0], _p(mean), _p(std))
+    if rc:
+        _raise(rc, lib().mfm_global_error())
+    return mean, std
 
 
 def crps_row(task, y, scores, precisions=None, cutpoints=None):

@@ -591,6 +591,7 @@ struct LearningHistory {
 // ---- Predictor (predictor.hpp:14-167) ---------------------------------------------------------------
 // the number of importance ratios PSIS smooths: ceil(min(0.2 S, 3 sqrt(S / r_eff))), r_eff one finite positive number
 constexpr int PSIS_MAX_SAMPLES = 4096;  // (DIST_MAX_S of the library: a row's ratios are sorted in the device's local memory)
+constexpr int CONTRIB_MAX_FIELDS = 16;   // (CONTRIB_MAX_FIELDS of the library: a lane group keeps every field pair's moments in registers)
 constexpr int CRPS_MAX_SAMPLES = 1024;  // (CRPS_MAX_S of the library: a regression row costs S (S + 1) / 2 pair terms)
 static int32_t psis_tail_len(size_t S, double r_eff) {
   if (!(r_eff > 0.0) || !std::isfinite(r_eff)) throw std::invalid_argument("r_eff must be one finite positive number");
@@ -1334,6 +1335,34 @@ struct Predictor {
                      a.cutpoints(), tile_rows, (int32_t)chunk_samples, tail_len, crps.mutable_data(), accuracy.mutable_data(),
                      spread.mutable_data(), khat.mutable_data()));
     return py::make_tuple(crps, accuracy, spread, khat);
+  }
+  // The score of every kept sample taken apart by field (not in the reference): (bias, bias_std, linear[F, N],
+  // linear_std[F, N], interaction[P, N], interaction_std[P, N]); field_of: one field in [0, n_fields) per column of the flat design.
+  // Every argument is checked here, before the device is looked for.
+  py::tuple predict_contributions(const py::object &Xo, const py::object &relso, int n_fields,
+                                  const py::array_t<int32_t, py::array::c_style | py::array::forcecast> &field_of, int64_t tile_rows,
+                                  int chunk_samples) const {
+    Csr X = csr_from_py(Xo);
+    Relations rels = relations_from_py(relso);
+    check_input(X, rels);
+    if (n_fields < 1 || n_fields > CONTRIB_MAX_FIELDS)
+      throw std::invalid_argument("the number of fields must lie in [1, " + std::to_string(CONTRIB_MAX_FIELDS) + "], got " + std::to_string(n_fields));
+    if (field_of.ndim() != 1 || (size_t)field_of.shape(0) != feature_size)
+      throw std::invalid_argument("the grouping holds one field per column of the design: " + std::to_string(feature_size) + " expected, got " +
+                                  std::to_string(field_of.ndim() == 1 ? (long long)field_of.shape(0) : -1LL));
+    for (py::ssize_t j = 0; j < field_of.shape(0); j++)
+      if (field_of.at(j) < 0 || field_of.at(j) >= n_fields)
+        throw std::invalid_argument("field " + std::to_string(field_of.at(j)) + " of column " + std::to_string(j) + " lies outside [0, " +
+                                    std::to_string(n_fields) + ")");
+    check_tiled_pass(tile_rows, chunk_samples);
+    const py::ssize_t N = (py::ssize_t)X.rows, F = n_fields, P = F * (F + 1) / 2;
+    double bias[2] = {0.0, 0.0};
+    py::array_t<double> lin({F, N}), lin_std({F, N}), inter({P, N}), inter_std({P, N});
+    DeviceDesign dd(X, rels);
+    dd.ck(on_samples(mfm_design_contrib_store, mfm_design_contrib, dd.d, (int32_t)n_fields, field_of.data(), (int64_t)field_of.shape(0),
+                     tile_rows, (int32_t)chunk_samples, (double *)bias, lin.mutable_data(), lin_std.mutable_data(), inter.mutable_data(),
+                     inter_std.mutable_data()));
+    return py::make_tuple(bias[0], bias[1], lin, lin_std, inter, inter_std);
   }
   // Chain diagnostics over the kept samples in their order (not in the reference). The limit both kinds share:
   void check_ess_limits(int n_chains) const {
@@ -3251,6 +3280,8 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def("predict_crps", &Predictor::predict_crps, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
            py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
+      .def("predict_contributions", &Predictor::predict_contributions, py::arg("X"), py::arg("rels"), py::arg("n_fields"), py::arg("field_of"),
+           py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
       .def("predict_loo_dist", &Predictor::predict_loo_dist, py::arg("X"), py::arg("rels"), py::arg("y"), py::arg("task"),
            py::arg("precisions") = py::none(), py::arg("cutpoints") = py::none(), py::arg("quantiles") = py::tuple(), py::arg("r_eff") = 1.0,
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)
@@ -3628,6 +3659,28 @@ PYBIND11_MODULE(_myfm, m) {
       },
       py::arg("task"), py::arg("y"), py::arg("scores"), py::arg("log_weights"), py::arg("precisions") = py::none(),
       py::arg("cutpoints") = py::none());
+  // the field components of one row on the host, by the functions k_contrib runs on the device and in its orders
+  // (csrc/mfm_contrib.hpp): (mean[F + P], std[F + P]); ws[S, D], Vs[S, K, D]
+  m.def(
+      "contrib_row",
+      [](const py::array_t<int32_t, py::array::c_style | py::array::forcecast> &idx,
+         const py::array_t<double, py::array::c_style | py::array::forcecast> &val,
+         const py::array_t<double, py::array::c_style | py::array::forcecast> &ws,
+         const py::array_t<double, py::array::c_style | py::array::forcecast> &Vs, int n_fields,
+         const py::array_t<int32_t, py::array::c_style | py::array::forcecast> &field_of) {
+        if (idx.ndim() != 1 || val.ndim() != 1 || idx.shape(0) != val.shape(0)) throw std::invalid_argument("idx and val are 1-D arrays of one length");
+        if (ws.ndim() != 2 || Vs.ndim() != 3 || Vs.shape(0) != ws.shape(0) || Vs.shape(2) != ws.shape(1) || ws.shape(0) < 1)
+          throw std::invalid_argument("ws is (S, D) and Vs (S, K, D) with S >= 1");
+        if (field_of.ndim() != 1) throw std::invalid_argument("field_of is a 1-D array");
+        const py::ssize_t F = std::max(n_fields, 0), C = F + F * (F + 1) / 2;
+        py::array_t<double> mean(C), sd(C);
+        const int code = mfm_contrib_row((int32_t)idx.shape(0), idx.data(), val.data(), (int64_t)ws.shape(1), (int32_t)Vs.shape(1),
+                                         (int32_t)ws.shape(0), ws.data(), Vs.data(), (int32_t)n_fields, field_of.data(),
+                                         (int64_t)field_of.shape(0), mean.mutable_data(), sd.mutable_data());
+        if (code != MFM_OK) throw_code(code, mfm_global_error());
+        return py::make_tuple(mean, sd);
+      },
+      py::arg("idx"), py::arg("val"), py::arg("ws"), py::arg("Vs"), py::arg("n_fields"), py::arg("field_of"));
   // the rank-normalised values of S draws by twice the average rank, table[2S - 1], as the device is handed them
   m.def(
       "rank_z_table",

@@ -2786,6 +2786,7 @@ int mfm_host_column_levels(int64_t n_rows, int64_t n_cols, const int64_t *indptr
 #include "mfm_latent_host.hpp"  // ... their exact latent draws on the device stream
 #include "mfm_predict.hpp"  // mfm_design_* entry points
 #include "mfm_dist.hpp"     // ... and the posterior summaries over the kept samples
+#include "mfm_contrib.hpp"  // ... and the score taken apart by field (after mfm_dist.hpp: its checks, the staged samples)
 #include "mfm_logdens.hpp"  // ... and the pointwise log predictive density
 #include "mfm_psis.hpp"     // ... and Pareto-smoothed leave-one-out on top of it
 #include "mfm_ess.hpp"      // ... and the chain diagnostics of the values both are computed from

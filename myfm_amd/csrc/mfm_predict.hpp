@@ -270,6 +270,8 @@ struct mfm_design {
   DevBuf<double> dist_scratch, dist_out, dist_aux;  // posterior summaries (mfm_dist.hpp): [S][T] values of a row tile, outputs, sqrt(alpha)
   DevBuf<double> dist_y;                            // log densities (mfm_logdens.hpp): the observed targets
   DevBuf<double> loo_scores, loo_aux;               // leave-one-out predictions (mfm_loo_pred.hpp): a tile's scores beside its weights, that file's constants
+  DevBuf<int32_t> contrib_field;                    // score contributions (mfm_contrib.hpp): the field of every column ...
+  DevBuf<int64_t> contrib_segs;                     // ... and the sources of a row's entries (main matrix, relation blocks), as words
   PinnedRing ring;
   Timing timing;
   ~mfm_design() {

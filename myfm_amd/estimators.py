@@ -187,10 +187,12 @@ class _FMEstimatorBase:
             grouping = [g for g, size in enumerate(group_shapes) for _ in range(size)]
         if grouping is None:
             self.n_groups_ = 1
+            self.grouping_ = None  # (one field)
             config_builder.set_identical_groups(dim_all)
         else:
             assert dim_all == len(grouping)
             self.n_groups_ = len(set(grouping))
+            self.grouping_ = np.asarray([int(g) for g in grouping], dtype=np.int32)
             config_builder.set_group_index([int(g) for g in grouping])
 
         if X_test is not None or X_rel_test:
@@ -578,6 +580,73 @@ class _CrpsMixin(_LogDensityMixin):
         return CrpsScore(*predictor.predict_crps(*args))
 
 
+ScoreContributions = namedtuple("ScoreContributions", ["bias", "bias_std", "linear", "linear_std", "interaction", "interaction_std", "pairs"])
+CONTRIB_MAX_FIELDS = 16  # a lane group of the device pass keeps the moments of all F + F (F + 1) / 2 components in registers
+
+
+def _contribution_fields(est, D, grouping, group_shapes):
+    """(F, field_of int32 (D,)) of a predict_contributions call: the arguments as fit takes them, or the fit's own grouping_"""
+    if grouping is not None and group_shapes is not None:
+        raise ValueError("give grouping or group_shapes, not both")
+    F = None
+    if group_shapes is not None:
+        shapes = [int(v) for v in group_shapes]
+        if any(v < 0 for v in shapes):
+            raise ValueError("group_shapes must hold non-negative sizes")
+        F = len(shapes)
+        if not 1 <= F <= CONTRIB_MAX_FIELDS:
+            raise ValueError("predict_contributions serves 1 to %d fields, got %d" % (CONTRIB_MAX_FIELDS, F))
+        grouping = np.repeat(np.arange(F, dtype=np.int64), shapes)
+    elif grouping is None:
+        if not hasattr(est, "grouping_"):
+            raise ValueError("this model does not record the grouping of its fit (it has no grouping_, as a model pickled by an "
+                             "earlier version): pass grouping or group_shapes")
+        grouping = np.zeros(D, dtype=np.int64) if est.grouping_ is None else est.grouping_
+    g = np.asarray(grouping)
+    if g.ndim != 1 or g.shape[0] != D:
+        raise ValueError("the grouping must hold one field per column: %d expected, got shape %s" % (D, g.shape))
+    if D and not np.issubdtype(g.dtype, np.integer):
+        raise ValueError("the grouping must hold integers")
+    if D and g.min() < 0:
+        raise ValueError("the grouping holds a negative field")
+    if F is None:
+        F = int(g.max()) + 1 if D else 1
+    if not 1 <= F <= CONTRIB_MAX_FIELDS:
+        raise ValueError("predict_contributions serves 1 to %d fields, got %d" % (CONTRIB_MAX_FIELDS, F))
+    return F, np.ascontiguousarray(g, dtype=np.int32)
+
+
+class _ContributionsMixin:
+    """The score of a fitted Gibbs regressor, classifier or ordered probit taken apart by field: which fields, and
+    which pairs of fields, carry the prediction for a row. The inner products of the fields' embeddings are formed under every kept
+    sample and summarised afterwards -- they are invariant to the signs, permutations and rotations that differ between the
+    samples' factors, which an average of V is not. Limits: at most 16 fields; no variational estimator; not row-sharded."""
+
+    def predict_contributions(self, X, X_rel=[], grouping=None, group_shapes=None):
+        """ScoreContributions(bias, bias_std, linear, linear_std, interaction, interaction_std, pairs) of the rows of X over the S
+        kept samples, computed on the device in one pass over the rows.
+
+        With the columns of the flat design (X's, then the relation blocks') assigned to F fields, the score of a row under one
+        sample is w0 + sum_g lin_g + sum_{g <= h} I_gh: lin_g the field's linear term, I_gh (g < h) the inner product of the two
+        fields' embeddings p_g = sum_{j in g} x_j V[j], and I_gg the interactions inside field g (zero for a one-hot field).
+        linear, linear_std (F, N) and interaction, interaction_std (P, N), P = F (F + 1) / 2: per row the mean and the population
+        standard deviation of every component over the kept samples; row p of the interactions is the pair pairs[p] = (g, h);
+        bias, bias_std: those of w0. All values are on the SCORE scale for every task: for a classifier and an ordered probit
+        that is the probit's latent scale, not a probability. bias + linear.sum(0) + interaction.sum(0) is the posterior mean
+        score (myfm_amd.utils.evaluation.contribution_total; see also contribution_matrix and contribution_summary).
+
+        grouping (one field id in [0, F) per column) or group_shapes as fit takes them, not both; with neither the grouping of
+        the fit (grouping_; None there: one field) is used -- a model without grouping_, as one pickled by an earlier version,
+        must be given one. All arguments are checked on the host before the device is touched."""
+        predictor = self._fetch_predictor()
+        F, field_of = _contribution_fields(self, int(predictor.feature_size), grouping, group_shapes)
+        n = check_data_consistency(X, X_rel)
+        X = _as_csr(X, n)
+        res = predictor.predict_contributions(X, list(X_rel), F, field_of)
+        pairs = np.asarray([(g, h) for g in range(F) for h in range(g, F)], dtype=np.int64).reshape(-1, 2)
+        return ScoreContributions(*res, pairs)
+
+
 ChainDiagnostics = namedtuple("ChainDiagnostics", ["rhat", "ess_bulk", "ess_mean", "mcse_mean"])
 LikelihoodDiagnostics = namedtuple("LikelihoodDiagnostics", ["r_eff", "rhat", "ess_bulk", "mcse_lpd"])
 
@@ -910,13 +979,16 @@ def _fold_in_grouping(entity, U):
     return order, offsets
 
 
-def _folded_in(est, predictor, D, U):
+def _folded_in(est, predictor, D, U, group):
     """a new estimator of est's class around the extended predictor: constructor arguments, history_, n_groups_ and the chain count
-    of a combined model carried over"""
+    of a combined model carried over, grouping_ (where est has one) with `group` for the U new columns"""
     out = _unfitted_copy(est)
     out.predictor_ = predictor
     out.history_ = est.history_
     out.n_groups_ = est.n_groups_
+    if hasattr(est, "grouping_"):
+        g = est.grouping_
+        out.grouping_ = None if g is None else np.concatenate([np.asarray(g, dtype=np.int32), np.full(U, group, dtype=np.int32)])
     out.fold_in_columns_ = (D, D + U)
     if hasattr(est, "n_chains_"):
         out.n_chains_ = est.n_chains_
@@ -971,7 +1043,7 @@ class _FoldInGibbsMixin:
         w_new, V_new = predictor.fold_in_gibbs_solve(X[order], np.ascontiguousarray(y[order]), offsets, bool(self.fit_linear), mu, lam,
                                                      int(cutpoint_index), int(n_burn), int(n_inner), bool(draw),
                                                      int(random_seed) & 0xFFFFFFFFFFFFFFFF)
-        return _folded_in(self, predictor.extended(w_new, V_new), D, U)
+        return _folded_in(self, predictor.extended(w_new, V_new), D, U, g)
 
 
 class MyFMGibbsBase(_FMEstimatorBase):
@@ -1020,7 +1092,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -1085,10 +1157,10 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDi
         order, offsets = _fold_in_grouping(entity, U)
         w_new, V_new = predictor.fold_in_solve(X[order], np.ascontiguousarray(y[order]), offsets, bool(self.fit_linear), alpha, mu,
                                                lam, bool(draw), int(random_seed) & 0xFFFFFFFFFFFFFFFF)
-        return _folded_in(self, predictor.extended(w_new, V_new), D, U)
+        return _folded_in(self, predictor.extended(w_new, V_new), D, U, g)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -1164,7 +1236,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""
@@ -1516,7 +1588,7 @@ def combine_chains(estimators):
         [v for e in ests for v in _kept_tail(e.history_.n_mh_accept, n_kept)])
     out.n_groups_ = first.n_groups_
     out.n_chains_ = len(ests)
-    for name in ("fold_in_columns_", "n_cutpoint_groups"):
+    for name in ("fold_in_columns_", "n_cutpoint_groups", "grouping_"):
         if hasattr(first, name):
             setattr(out, name, getattr(first, name))
     return out

@@ -248,3 +248,56 @@ def loo_residuals(result, y, interval=None):
             raise ValueError("interval must be two indices into the quantile axis")
         out["coverage"] = float(np.mean((q[lo] <= y) & (y <= q[hi]))) if n else nan
     return out
+
+
+def _contribution_arrays(result):
+    lin, lin_std = np.asarray(result.linear, dtype=np.float64), np.asarray(result.linear_std, dtype=np.float64)
+    inter, inter_std = np.asarray(result.interaction, dtype=np.float64), np.asarray(result.interaction_std, dtype=np.float64)
+    F = lin.shape[0]
+    if lin.ndim != 2 or inter.ndim != 2 or inter.shape != (F * (F + 1) // 2, lin.shape[1]) or lin_std.shape != lin.shape or inter_std.shape != inter.shape:
+        raise ValueError("linear must be (F, N) and interaction (F (F + 1) / 2, N), each with a standard deviation of its shape")
+    return F, lin, lin_std, inter, inter_std
+
+
+def contribution_total(result):
+    """bias + sum_g linear[g] + sum_p interaction[p] of a ScoreContributions `result` (predict_contributions), shape
+    (N,): the posterior mean score of every row, the fields' terms added in their order."""
+    _, lin, _, inter, _ = _contribution_arrays(result)
+    return float(result.bias) + lin.sum(axis=0) + inter.sum(axis=0)
+
+
+def contribution_matrix(result, row):
+    """(mean, std), each a symmetric (F, F) matrix, of the interactions of row `row` of a ScoreContributions `result`: entry
+    (g, h) = (h, g) is the pair's interaction, the diagonal the interactions inside a field."""
+    F, _, _, inter, inter_std = _contribution_arrays(result)
+    mean, std = np.zeros((F, F)), np.zeros((F, F))
+    for p, (g, h) in enumerate(np.asarray(result.pairs).reshape(-1, 2)):
+        mean[g, h] = mean[h, g] = inter[p, row]
+        std[g, h] = std[h, g] = inter_std[p, row]
+    return mean, std
+
+
+def contribution_summary(result):
+    """What a ScoreContributions `result` says about the rows as a whole. Returns a dict of two dicts, "linear" and "interaction",
+    each with one array entry per component (F and P long):
+
+        magnitude     the mean over the rows of |mean contribution|
+        share         magnitude / the sum of the magnitudes of ALL components, linear and interaction (0 where that sum is 0)
+        significant   the share of rows whose |mean| exceeds 2 std over the kept samples
+
+    and "pairs", the (P, 2) field pairs of the interaction entries."""
+    _, lin, lin_std, inter, inter_std = _contribution_arrays(result)
+    n = lin.shape[1]
+
+    def part(m, s):
+        if n == 0:
+            return np.zeros(m.shape[0]), np.zeros(m.shape[0])
+        return np.abs(m).mean(axis=1), (np.abs(m) > 2.0 * s).mean(axis=1)
+
+    lm, ls = part(lin, lin_std)
+    im, is_ = part(inter, inter_std)
+    total = float(lm.sum() + im.sum())
+    scale = 1.0 / total if total > 0.0 else 0.0
+    return {"linear": {"magnitude": lm, "share": lm * scale, "significant": ls},
+            "interaction": {"magnitude": im, "share": im * scale, "significant": is_},
+            "pairs": np.asarray(result.pairs).reshape(-1, 2)}
