@@ -728,6 +728,40 @@ int mfm_pairs_topk_prob_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_
 int mfm_pairs_topk_prob(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                         int32_t mode, int32_t k, int32_t n_top, int64_t *idx, double *prob);
 
+/* ---- similar rows under each kept sample (csrc/mfm_pairs_sim.hpp) ----------------------------------------------------
+ * "Which items are like this item": the geometry of the rows of V. For side rows a (query side) and b (candidate side), with
+ * P_s[a, k] = sum_j V_s[k, j] a_j the embedding of a under kept sample s (relation blocks as above),
+ *   metric MFM_PAIRS_SIM_COSINE: c_s(a, b) = (<P_s[a], P_s[b]> * r_s[a]) * r_s[b],  r = 1 / sqrt(sum_k P_k^2) with the squares summed
+ *          in factor order, r = 0 where that sum is 0 (an empty row, rank 0, an all-zero embedding: the value is 0, not NaN). This holds for
+ *          finite embeddings: where a row's sum of squares overflows, r is 0 too and the value may be NaN;
+ *          the value is not clamped to [-1, 1].
+ *   metric MFM_PAIRS_SIM_DOT:    r = 1, the inner product (for sides with disjoint columns the interaction part of the pair score).
+ * The samples' factors differ by signs and rotations, so the cosine is formed under each sample and then summarised:
+ *   mean = (sum_s c_s) / S,   std = the population standard deviation of the c_s (Welford's recurrence in sample order, as the
+ *   moments above),   value = mean + beta * std.   w0, w, the cutpoints and the task play no part; w0s and ws are not read.
+ *   create_sim: mfm_pairs_create without the check that the sides store disjoint columns (items against items share every column);
+ *          add_block on such a handle still refuses a column its own side already stores. A similarity handle serves the four entry
+ *          points below only: scores, topk, moments, topk_ucb, rank, topk_samples, topk_prob and the _vb entry points return
+ *          MFM_ERR_INVALID on it, with a message that says so (their decomposition is wrong when columns are shared).
+ *   sim:      mean[U * I], std[U * I] row-major, every pair; U * I > 2^24 is MFM_ERR_INVALID.
+ *   topk_sim: per query row the k (1 <= k <= 256) candidates of largest value under the order of topk, the exclusion pattern left
+ *          out; idx, value, mean, std [U * k] as topk_ucb returns them (mean and std recomputed for the selected pairs in another
+ *          association: equal to the selecting kernel's within rounding, bit for bit on exact data). Tail: idx -1, value -inf, mean
+ *          and std NaN.
+ * Both work on either kind of handle, with the sample views, chunks, stripes and memory rule of the moments entry points.
+ * MFM_ERR_INVALID before any launch: a metric outside {0, 1}, k outside [1, 256], a non-finite beta, the dense call's pair limit.  */
+#define MFM_PAIRS_SIM_COSINE 0
+#define MFM_PAIRS_SIM_DOT 1
+int mfm_pairs_create_sim(int device, int64_t D, int64_t U, const int64_t *q_indptr, const int32_t *q_indices, const double *q_data,
+                         int64_t I, const int64_t *c_indptr, const int32_t *c_indices, const double *c_data, mfm_pairs **out);
+int mfm_pairs_sim_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t metric, double *mean, double *std);
+int mfm_pairs_sim(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t metric,
+                  double *mean, double *std);
+int mfm_pairs_topk_sim_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t metric, int32_t k, double beta,
+                             int64_t *idx, double *value, double *mean, double *std);
+int mfm_pairs_topk_sim(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t metric, int32_t k, double beta, int64_t *idx, double *value, double *mean, double *std);
+
 /* ---- folding new one-hot features into the kept samples (csrc/mfm_foldin.hip) ----------------------------------
  * U new entities (users or items that were not in the training table), each a new one-hot column with value 1 in its own
  * observations. X (n, D) holds the CONTEXT of the n observations in the model's feature space (not the new column), y their

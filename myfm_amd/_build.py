@@ -23,7 +23,7 @@ HIP_UNITS = {
     "mfm_cell.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_cell.hpp"],
     "mfm_chain.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_wave.hpp", "mfm_policies.hpp", "mfm_chain_api.hpp", "mfm_chain_plan.hpp", "mfm_chain_stream.hpp"],
     "mfm_vb.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_erfcx.hpp", "mfm_vb.hpp", "mfm_comm.hpp"],
-    "mfm_pairs.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_pairs.hpp", "mfm_pairs_rank.hpp", "mfm_pairs_samples.hpp", "mfm_pairs_ucb.hpp", "mfm_pairs_vb.hpp", "mfm_vb_sums.hpp", "mfm_samples.hpp"],
+    "mfm_pairs.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_pairs.hpp", "mfm_pairs_rank.hpp", "mfm_pairs_samples.hpp", "mfm_pairs_sim.hpp", "mfm_pairs_ucb.hpp", "mfm_pairs_vb.hpp", "mfm_vb_sums.hpp", "mfm_samples.hpp"],
     "mfm_foldin.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_foldin.hpp", "mfm_foldin_handle.hpp", "mfm_philox.hpp", "mfm_samples.hpp"],
     "mfm_foldin_gibbs.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_foldin.hpp", "mfm_foldin_gibbs.hpp", "mfm_foldin_gibbs_plan.hpp",
                              "mfm_foldin_handle.hpp", "mfm_tn.hpp", "mfm_philox.hpp", "mfm_samples.hpp"],

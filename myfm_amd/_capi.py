@@ -43,6 +43,7 @@ SYMBOLS = [
     "mfm_pairs_set_cutpoints", "mfm_pairs_moments_store", "mfm_pairs_moments", "mfm_pairs_topk_ucb_store", "mfm_pairs_topk_ucb",
     "mfm_pairs_set_targets", "mfm_pairs_rank_store", "mfm_pairs_rank",
     "mfm_pairs_topk_samples_store", "mfm_pairs_topk_samples", "mfm_pairs_topk_prob_store", "mfm_pairs_topk_prob",
+    "mfm_pairs_create_sim", "mfm_pairs_sim_store", "mfm_pairs_sim", "mfm_pairs_topk_sim_store", "mfm_pairs_topk_sim",
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
@@ -57,6 +58,7 @@ SYMBOLS = [
     "mfm_design_moments_vb", "mfm_pairs_moments_vb", "mfm_pairs_topk_bound_vb",
 ]
 
+SIM_METRICS = {"cosine": 0, "dot": 1}  # (MFM_PAIRS_SIM_* of myfm_hip.h)
 PAIRS_VOTE_MAX = 32768  # (MFM_PAIRS_VOTE_MAX of myfm_hip.h: samples * k of a topk_prob call)
 
 # a record of mfm_chain_stream_info / mfm_cs_plan_probe (MFM_CHAIN_STREAM_INFO_FIELDS of include/myfm_hip.h)
@@ -227,6 +229,11 @@ def lib():
     L.mfm_loo_summary_row.argtypes = [i32, P, P, P, i32, P, P, P, P, P, P]
     L.mfm_loo_crps_row.argtypes = [i32, i32, dbl, P, P, P, i32, P, P]
     L.mfm_pairs_create.argtypes = [C.c_int, i64, i64, P, P, P, i64, P, P, P, C.POINTER(vp)]
+    L.mfm_pairs_create_sim.argtypes = L.mfm_pairs_create.argtypes
+    L.mfm_pairs_sim_store.argtypes = [vp, vp, i32, i32, i32, P, P]
+    L.mfm_pairs_sim.argtypes = [vp, i32, i32, P, P, P, i32, P, P]
+    L.mfm_pairs_topk_sim_store.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, P, P, P, P]
+    L.mfm_pairs_topk_sim.argtypes = [vp, i32, i32, P, P, P, i32, i32, C.c_double, P, P, P, P]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
     L.mfm_pairs_last_error.restype = C.c_char_p
@@ -1047,6 +1054,15 @@ def _resident(store, first, count):
     return _Samples(count, store.K, "_store", (store.h, first, count), store)
 
 
+def _sim_metric(metric):
+    """"cosine" / "dot" -> the number the C ABI takes; an integer is passed on for the library to judge"""
+    if isinstance(metric, str) and metric in SIM_METRICS:
+        return SIM_METRICS[metric]
+    if isinstance(metric, (bool, np.bool_)) or not isinstance(metric, (int, np.integer)):
+        raise ValueError('metric must be "cosine" or "dot" (or the C ABI\'s number, 0 or 1), got %r' % (metric,))
+    return int(metric)
+
+
 class Pairs:
     """Query x candidate scoring (mfm_pairs_*): both sides (U, D) / (I, D) sparse in the model's feature space, no column in
     both. `exclude`: optional (U, I) sparse pattern of pairs the top-k leaves out. `scratch_bound`: bytes of query-side
@@ -1055,18 +1071,19 @@ class Pairs:
     `csr` at columns [col_offset, col_offset + csr.shape[1]) of the same D columns (the main matrices keep the model's width
     and leave the blocks' columns empty); applied in list order. `cutpoints`: (S, n_cut) array, the samples' cutpoints for
     mode 2 (the mean over the samples of the expected class index of the ordered probit). `targets`: optional (U, I) sparse
-    pattern of the pairs `rank` ranks, at most 64 per row and none of them excluded."""
+    pattern of the pairs `rank` ranks, at most 64 per row and none of them excluded. `similarity`: a similarity handle
+    (mfm_pairs_create_sim): the sides may share columns, and only sim / topk_sim run on it."""
 
     def __init__(self, X_query, X_cand, exclude=None, scratch_bound=None, device=0, rel_query=(), rel_cand=(), cutpoints=None,
-                 targets=None):
+                 targets=None, similarity=False):
         L = lib()
         h = C.c_void_p()
         Xq, qp, qx, qv = csr_parts(X_query)
         Xc, cp, cx, cv = csr_parts(X_cand)
         if Xq.shape[1] != Xc.shape[1]:
             raise ValueError("X_query and X_cand differ in width")
-        rc = L.mfm_pairs_create(device, Xq.shape[1], Xq.shape[0], _p(qp), _p(qx), _p(qv), Xc.shape[0], _p(cp), _p(cx), _p(cv),
-                                C.byref(h))
+        create = L.mfm_pairs_create_sim if similarity else L.mfm_pairs_create
+        rc = create(device, Xq.shape[1], Xq.shape[0], _p(qp), _p(qx), _p(qv), Xc.shape[0], _p(cp), _p(cx), _p(cv), C.byref(h))
         if rc:
             _raise(rc, L.mfm_pairs_last_error(None))
         self.h, self.U, self.I, self.D = h, Xq.shape[0], Xc.shape[0], Xq.shape[1]
@@ -1195,6 +1212,34 @@ class Pairs:
 
     def topk_ucb_store(self, store, k, beta=1.0, mode=0, first=0, count=None):
         return self._topk_ucb(_resident(store, first, count), k, beta, mode)
+
+    # ---- the similarity forms: mean and population std over the samples of the per-sample cosine / inner product
+    def _sim(self, src, metric):
+        mean, std = np.empty((self.U, self.I)), np.empty((self.U, self.I))
+        self._ck(src.call("mfm_pairs_sim", self.h, _sim_metric(metric), _p(mean), _p(std)))
+        return mean, std
+
+    def _topk_sim(self, src, k, metric, beta):
+        kk = max(int(k), 1)
+        idx, val, mean, std = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk)), np.empty((self.U, kk)), np.empty((self.U, kk))
+        self._ck(src.call("mfm_pairs_topk_sim", self.h, _sim_metric(metric), int(k), float(beta), _p(idx), _p(val), _p(mean), _p(std)))
+        return idx, val, mean, std
+
+    def sim(self, samples, metric="cosine"):
+        """(mean (U, I), std (U, I)) of the per-sample cosine ("cosine") or inner product ("dot") of the two rows' embeddings;
+        metric: one of the two names or the C ABI's number. An empty row or an all-zero embedding gives 0 under both."""
+        return self._sim(_host(samples), metric)
+
+    def sim_store(self, store, metric="cosine", first=0, count=None):
+        return self._sim(_resident(store, first, count), metric)
+
+    def topk_sim(self, samples, k, metric="cosine", beta=0.0):
+        """(indices int64 (U, k), value, mean, std (U, k)) ranked by value = mean + beta * std of the similarity, as topk_ucb ranks
+        the score; the handle's exclusions are left out. Tail: -1 / -inf / NaN / NaN."""
+        return self._topk_sim(_host(samples), k, metric, beta)
+
+    def topk_sim_store(self, store, k, metric="cosine", beta=0.0, first=0, count=None):
+        return self._topk_sim(_resident(store, first, count), k, metric, beta)
 
     # ---- the rank form (DESIGN 4.13.2)
     def rank(self, samples, mode=0):

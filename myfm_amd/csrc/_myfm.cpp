@@ -391,9 +391,11 @@ struct DeviceStore {
 // Two sparse sides resident on the GPU for the duration of one pair-scoring call (include/myfm_hip.h "query x candidate scoring").
 struct DevicePairs {
   mfm_pairs *p = nullptr;
-  DevicePairs(int64_t D, const Csr &Xq, const Csr &Xc) {
-    int code = mfm_pairs_create(selected_device(), D, Xq.rows, Xq.indptr.data(), Xq.indices.data(), Xq.data.data(), Xc.rows,
-                                Xc.indptr.data(), Xc.indices.data(), Xc.data.data(), &p);
+  // similarity: a similarity handle (mfm_pairs_create_sim), whose sides may share columns
+  DevicePairs(int64_t D, const Csr &Xq, const Csr &Xc, bool similarity = false) {
+    const auto create = similarity ? mfm_pairs_create_sim : mfm_pairs_create;
+    int code = create(selected_device(), D, Xq.rows, Xq.indptr.data(), Xq.indices.data(), Xq.data.data(), Xc.rows, Xc.indptr.data(),
+                      Xc.indices.data(), Xc.data.data(), &p);
     if (code != MFM_OK) throw_code(code, mfm_pairs_last_error(nullptr));
   }
   ~DevicePairs() {
@@ -718,7 +720,8 @@ struct Predictor {
   // [X | B_0[idx_0] | B_1[idx_1] ...]: each list is empty (no blocks on that side; made a list of nulls here) or has one entry per
   // block position, a null entry meaning that the side holds nothing there; the matrices then have the main width. Returns the
   // column offset of every block position in the model's feature space.
-  vector<size_t> check_pairs(const Csr &Xq, const Csr &Xc, Relations &rq, Relations &rc) const {
+  // shared_ok (the similarity methods): the two sides may store the same columns.
+  vector<size_t> check_pairs(const Csr &Xq, const Csr &Xc, Relations &rq, Relations &rc, bool shared_ok = false) const {
     vector<size_t> offsets;
     if (rq.empty() && rc.empty()) {
       check_width((size_t)Xq.cols);
@@ -766,6 +769,7 @@ struct Predictor {
         if (r)
           for (int32_t j : r->X.indices)
             if (j < 0 || j >= r->X.cols) throw std::invalid_argument("relation block: column index out of range");
+    if (shared_ok) return offsets;
     // disjointness over the whole feature space; a block counts every column it stores, referenced or not
     vector<uint8_t> seen(feature_size, 0);
     for (int32_t j : Xq.indices) seen[(size_t)j] = 1;
@@ -793,6 +797,7 @@ struct Predictor {
     bool excluded = false;
     Csr tg;  // the targets of a rank call
     bool targeted = false;
+    bool similarity = false;  // a similarity call: the sides may share columns, the task plays no part
     py::ssize_t U() const { return (py::ssize_t)Xq.rows; }
     py::ssize_t I() const { return (py::ssize_t)Xc.rows; }
     void refuse_every_pair(const char *method, const char *instead) const {
@@ -838,22 +843,24 @@ struct Predictor {
     // the first device contact: both sides with their blocks, the exclusion and the mode-2 cutpoints
     DevicePairs open() const {
       if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
-      DevicePairs dp(D, Xq, Xc);
+      DevicePairs dp(D, Xq, Xc, similarity);
       dp.add_blocks(0, rq, offsets);
       dp.add_blocks(1, rc, offsets);
       if (excluded) dp.ck(mfm_pairs_set_exclude(dp.p, ex.indptr.data(), ex.indices.data()));
-      if (mode == 2) dp.ck(mfm_pairs_set_cutpoints(dp.p, S, (int)cp.n_cut, cp.cuts.data()));
+      if (mode == 2 && !similarity) dp.ck(mfm_pairs_set_cutpoints(dp.p, S, (int)cp.n_cut, cp.cuts.data()));
       if (targeted) dp.ck(mfm_pairs_set_targets(dp.p, tg.indptr.data(), tg.indices.data()));
       return dp;
     }
   };
-  PairCall pair_call(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
+  PairCall pair_call(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco,
+                     bool similarity = false) const {
     PairCall pc{csr_from_py(Xqo), csr_from_py(Xco), Csr(), pair_relations_from_py(rqo), pair_relations_from_py(rco)};
-    pc.offsets = check_pairs(pc.Xq, pc.Xc, pc.rq, pc.rc);
+    pc.offsets = check_pairs(pc.Xq, pc.Xc, pc.rq, pc.rc, similarity);
     pc.D = (int64_t)feature_size;
     pc.S = (int)samples.size();
+    pc.similarity = similarity;
     pc.mode = type == TaskType::CLASSIFICATION ? 1 : type == TaskType::ORDERED ? 2 : 0;
-    if (pc.mode == 2 && pc.S > 0) {
+    if (pc.mode == 2 && pc.S > 0 && !similarity) {
       pc.cp = gather_cutpoints(0);
       if (pc.cp.bad)
         throw std::runtime_error(pc.cp.at == 0 ? "No cutpoint available for this FM." : "inconsistent cutpoint sizes among samples.");
@@ -896,6 +903,36 @@ struct Predictor {
     py::array_t<double> value({pc.U(), (py::ssize_t)k}), mean({pc.U(), (py::ssize_t)k}), sd({pc.U(), (py::ssize_t)k});
     const DevicePairs dp = pc.open();
     dp.ck(on_samples(mfm_pairs_topk_ucb_store, mfm_pairs_topk_ucb, dp.p, pc.mode, (int)k, beta, idx.mutable_data(), value.mutable_data(),
+                     mean.mutable_data(), sd.mutable_data()));
+    return py::make_tuple(idx, value, mean, sd);
+  }
+  // ---- similar rows under each kept sample: the per-sample cosine / inner product of two rows' embeddings
+  static int sim_metric(const std::string &metric) {
+    if (metric == "cosine") return MFM_PAIRS_SIM_COSINE;
+    if (metric == "dot") return MFM_PAIRS_SIM_DOT;
+    throw std::invalid_argument("metric must be \"cosine\" or \"dot\", got \"" + metric + "\"");
+  }
+  // (mean (U, I), std (U, I)) over the kept samples of the similarity of every (row of X_a, row of X_b)
+  py::tuple predict_similarity(const py::object &Xao, const py::object &Xbo, const std::string &metric, const py::object &rao,
+                               const py::object &rbo) const {
+    const int m = sim_metric(metric);
+    const PairCall pc = pair_call(Xao, Xbo, rao, rbo, true);
+    pc.refuse_every_pair("predict_similarity", "predict_similar");
+    py::array_t<double> mean({pc.U(), pc.I()}), sd({pc.U(), pc.I()});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_sim_store, mfm_pairs_sim, dp.p, m, mean.mutable_data(), sd.mutable_data()));
+    return py::make_tuple(mean, sd);
+  }
+  // (indices, value, mean, std), each (U, k): the k most similar candidates by value = mean + beta * std
+  py::tuple predict_similar(const py::object &Xqo, const py::object &Xco, int64_t k, const std::string &metric, double beta,
+                            const py::object &excludeo, const py::object &rqo, const py::object &rco) const {
+    const int m = sim_metric(metric);
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco, true);
+    pc.ranked(k, excludeo, beta);
+    py::array_t<int64_t> idx({pc.U(), (py::ssize_t)k});
+    py::array_t<double> value({pc.U(), (py::ssize_t)k}), mean({pc.U(), (py::ssize_t)k}), sd({pc.U(), (py::ssize_t)k});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_topk_sim_store, mfm_pairs_topk_sim, dp.p, m, (int)k, beta, idx.mutable_data(), value.mutable_data(),
                      mean.mutable_data(), sd.mutable_data()));
     return py::make_tuple(idx, value, mean, sd);
   }
@@ -3251,6 +3288,10 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk_ucb", &Predictor::predict_topk_ucb, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("beta") = 1.0,
            py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_similarity", &Predictor::predict_similarity, py::arg("X_a"), py::arg("X_b"), py::arg("metric") = "cosine",
+           py::arg("X_rel_a") = py::tuple(), py::arg("X_rel_b") = py::tuple())
+      .def("predict_similar", &Predictor::predict_similar, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("metric") = "cosine",
+           py::arg("beta") = 0.0, py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk_samples", &Predictor::predict_topk_samples, py::arg("X_query"), py::arg("X_cand"), py::arg("k"),
            py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk_thompson", &Predictor::predict_topk_thompson, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("row_sample"),

@@ -21,12 +21,15 @@
 // the values at the chunk's targets, then the count of the admissible candidates that beat each of them; a chunk without targets
 // launches nothing, a call without targets or candidates touches no device memory), or the per-sample selecting form
 // (mfm_pairs_topk_samples*, mfm_pairs_topk_prob*; k_pairs_tile_samples and k_pairs_vote of mfm_pairs_samples.hpp, DESIGN 4.13.3:
-// walk_samples below builds each query chunk's plan and walks it in slices).
+// walk_samples below builds each query chunk's plan and walks it in slices), or the similarity forms (mfm_pairs_sim*,
+// mfm_pairs_topk_sim*; k_pairs_tile_sim of mfm_pairs_sim.hpp, DESIGN 4.13.4: the moments forms' walk over embeddings whose bias slot
+// holds the rows' normalisation; the one family that a similarity handle, mfm_pairs_create_sim, serves).
 // The variational forms (mfm_pairs_moments_vb, mfm_pairs_topk_bound_vb; mfm_pairs_vb.hpp) score a mean-field Gaussian
 // posterior instead of samples: run_pairs_vb at the end of this file, with the memory rule, the chunks and the stripes above.
 #include "mfm_pairs.hpp"
 #include "mfm_pairs_rank.hpp"
 #include "mfm_pairs_samples.hpp"
+#include "mfm_pairs_sim.hpp"
 #include "mfm_pairs_ucb.hpp"
 #include "mfm_pairs_vb.hpp"
 #include "mfm_samples.hpp"
@@ -66,6 +69,7 @@ struct mfm_pairs {
   std::vector<int32_t> t_idx_host;
   bool has_targets = false;
   int64_t scratch_bound = (int64_t)256 << 20;
+  bool similarity = false;  // made by mfm_pairs_create_sim: the sides may share columns, only the similarity forms run on it
   ~mfm_pairs() {
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -141,6 +145,13 @@ void launch_form_mode(hipStream_t s, dim3 grid, const PairsArgs &a) {
   }
 }
 
+// the similarity forms (mfm_pairs_sim.hpp): one per tile shape, whatever the metric and the task
+template <int MT, int NT, PairsOut OUT>
+void launch_form_sim(hipStream_t s, dim3 grid, const PairsArgs &a, int) {
+  constexpr bool DENSE = OUT == PAIRS_DENSE;
+  launch_pairs<k_pairs_tile_sim<MT, NT, DENSE>>(s, grid, DENSE ? 0 : PairsSel<MT>::BYTES, a);
+}
+
 template <int MT, int NT, bool SPREAD, PairsOut OUT>
 void launch_form(hipStream_t s, dim3 grid, const PairsArgs &a, int mode) {
   if (mode == 0)
@@ -157,6 +168,7 @@ struct PairsForm {
   bool spread;  // the moments over the samples (mfm_pairs_ucb.hpp) instead of the mean
   PairsOut out;
   void (*launch)(hipStream_t, dim3, const PairsArgs &, int mode);
+  bool sim = false;  // the similarity finish (mfm_pairs_sim.hpp) instead of the score's
   int rows() const { return 16 * MT; }
   int step() const { return 64 * NT; }
 };
@@ -166,11 +178,23 @@ PairsForm pairs_form_of() {
   return {MT, NT, SPREAD, OUT, &launch_form<MT, NT, SPREAD, OUT>};
 }
 
+template <int MT, int NT, PairsOut OUT>
+PairsForm pairs_sim_form_of() {
+  return {MT, NT, true, OUT, &launch_form_sim<MT, NT, OUT>, true};
+}
+
 // The one table of forms. A selecting form's tile shape follows from k: the per-row buffers of 16 MT rows x (256 / MT + 64)
 // candidates must fit the LDS. The moments forms hold MT NT = 4 tiles (their accumulators take twice the registers), the rank
 // form has the one shape its target lists are laid out for. The per-sample selecting forms hold one sample's value next to the
-// accumulators, as the mean forms' modes 1 and 2 do, and take their shapes.
-PairsForm pairs_form(bool targets, bool spread, bool dense, int k, bool per_sample = false) {
+// accumulators, as the mean forms' modes 1 and 2 do, and take their shapes. The similarity forms are moments forms with another
+// finish and take the moments forms' shapes.
+PairsForm pairs_form(bool targets, bool spread, bool dense, int k, bool per_sample = false, bool sim = false) {
+  if (sim) {
+    if (dense) return pairs_sim_form_of<2, 2, PAIRS_DENSE>();
+    if (k <= 64) return pairs_sim_form_of<4, 1, PAIRS_SELECT>();
+    if (k <= 128) return pairs_sim_form_of<2, 2, PAIRS_SELECT>();
+    return pairs_sim_form_of<1, 4, PAIRS_SELECT>();
+  }
   if (targets) return pairs_form_of<4, 2, false, PAIRS_TARGETS>();
   if (per_sample) {
     if (k <= 64) return pairs_form_of<4, 2, false, PAIRS_SELECT_SAMPLE>();
@@ -189,9 +213,11 @@ PairsForm pairs_form(bool targets, bool spread, bool dense, int k, bool per_samp
   return pairs_form_of<1, 4, true, PAIRS_SELECT>();
 }
 
-void launch_moments_at(hipStream_t s, const PairsArgs &a, int mode, const int32_t *out_i, int64_t n, double *mean, double *sd) {
+void launch_moments_at(hipStream_t s, const PairsArgs &a, int mode, bool sim, const int32_t *out_i, int64_t n, double *mean, double *sd) {
   const dim3 grid((unsigned)((n + PAIRS_WG / 64 - 1) / (PAIRS_WG / 64)));
-  if (mode == 0)
+  if (sim)
+    hipLaunchKernelGGL((k_pairs_moments_at<0, PairsFinishSim>), grid, dim3(PAIRS_WG), 0, s, a, out_i, n, mean, sd);
+  else if (mode == 0)
     hipLaunchKernelGGL(k_pairs_moments_at<0>, grid, dim3(PAIRS_WG), 0, s, a, out_i, n, mean, sd);
   else if (mode == 1)
     hipLaunchKernelGGL(k_pairs_moments_at<1>, grid, dim3(PAIRS_WG), 0, s, a, out_i, n, mean, sd);
@@ -405,8 +431,10 @@ void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, in
 
 // The whole call over the samples of `v` (mfm_samples.hpp). dense != nullptr: (U, I) scores; else the top k. mo != nullptr: the
 // moments form. rk != nullptr: the rank form (neither dense nor k). ps != nullptr: the per-sample selecting form (k, its own outputs).
+// sim >= 0: the similarity forms under that metric (PAIRS_SIM_*; with mo, mode 0): the embeddings carry the normalisation in the
+// bias slot and no bias is summed; everything else -- the memory rule, the chunks, the stripes, the merge -- is the moments call's.
 void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx, double *score, double *dense,
-               const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr) {
+               const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr, int sim = -1) {
   const int S = v.count(), rank = v.K;
   if (v.device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
   if (v.D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
@@ -423,7 +451,7 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   const bool is_dense = dense != nullptr;
   if (!is_dense && !rk && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
   // the form of the call, decided here once: the scratch per query row, the stripes, the grid and the launch all read it
-  const PairsForm form = pairs_form(rk != nullptr, mo != nullptr, is_dense, k, ps != nullptr);
+  const PairsForm form = pairs_form(rk != nullptr, mo != nullptr, is_dense, k, ps != nullptr, sim >= 0);
   const int64_t U = p->U, I = p->I, D = p->D;
   if (ps) check_per_sample(*ps, S, k, U);
   if (U == 0 || (is_dense && I == 0)) return;
@@ -498,9 +526,12 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
       ref.M = b->M;
       refs.push_back(ref);
       if (b->M > 0) {
-        hipLaunchKernelGGL(k_pairs_embed_block, dim3((unsigned)((b->M + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S), dim3(PAIRS_WG), 0, s,
-                           b->ptr.p, b->idx.p, b->val.p, b->M, b->off, (const double *const *)d_wv.p, D, K, KS, t.p,
-                           t.p + SM * (size_t)KS, t.p + SM * (size_t)(KS + 1));
+        const auto launch = [&](auto kernel) {
+          hipLaunchKernelGGL(kernel, dim3((unsigned)((b->M + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S), dim3(PAIRS_WG), 0, s, b->ptr.p,
+                             b->idx.p, b->val.p, b->M, b->off, (const double *const *)d_wv.p, D, K, KS, t.p, t.p + SM * (size_t)KS,
+                             t.p + SM * (size_t)(KS + 1));
+        };
+        sim >= 0 ? launch(k_pairs_embed_block<true>) : launch(k_pairs_embed_block<false>);
         MFM_HIP_CHECK(hipGetLastError());
       }
     }
@@ -518,7 +549,11 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
       hipLaunchKernelGGL(kernel, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K, KS, S, blk,
                          n_blk, Pf, bias, map_row, map_s);
     };
-    if (map_row)
+    if (sim == PAIRS_SIM_COSINE)  // (the bias slot gets the rows' 1 / norm, or 1.0: mfm_pairs_sim.hpp)
+      rel ? launch(k_pairs_embed<true, false, 1>) : launch(k_pairs_embed<false, false, 1>);
+    else if (sim == PAIRS_SIM_DOT)
+      rel ? launch(k_pairs_embed<true, false, 2>) : launch(k_pairs_embed<false, false, 2>);
+    else if (map_row)
       rel ? launch(k_pairs_embed<true, true>) : launch(k_pairs_embed<false, true>);
     else
       rel ? launch(k_pairs_embed<true, false>) : launch(k_pairs_embed<false, false>);
@@ -528,9 +563,9 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   DevBuf<double> Qf, Bb, Bsum;
   Qf.alloc((size_t)std::max<int64_t>(Ipad * NK * 4, 1));
   Bb.alloc((size_t)Ipad * S);
-  Bsum.alloc((size_t)Ipad);
+  if (sim < 0) Bsum.alloc((size_t)Ipad);  // (the similarity finish reads the per-sample slots alone: no sums, Asum / Bsum stay null)
   embed(1, p->c_ptr.p, p->c_idx.p, p->c_val.p, (int64_t)0, I, Ipad, Qf.p, Bb.p, nullptr, nullptr);
-  hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)(Ipad / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Bb.p, S, Ipad, Bsum.p);
+  if (sim < 0) hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)(Ipad / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Bb.p, S, Ipad, Bsum.p);
   MFM_HIP_CHECK(hipGetLastError());
 
   // ---- what every launch of the call reads; a chunk adds its own
@@ -590,10 +625,11 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     if (rk && n_t == 0) continue;
     ensure(Pf, (size_t)(Upad * NK * 4));
     ensure(Ab, (size_t)(Upad * S));
-    ensure(Asum, (size_t)Upad);
+    if (sim < 0) ensure(Asum, (size_t)Upad);
     embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p, nullptr, nullptr);
-    hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Ab.p, S, Upad,
-                       Asum.p);
+    if (sim < 0)
+      hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Ab.p, S, Upad,
+                         Asum.p);
     const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
     if (use_mask) {
       ensure(mask, (size_t)(Uc * W));
@@ -666,7 +702,7 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     if (mo) {
       ensure(out_m, (size_t)(Uc * k));
       ensure(out_s, (size_t)(Uc * k));
-      launch_moments_at(s, a, mode, out_i.p, Uc * k, out_m.p, out_s.p);
+      launch_moments_at(s, a, mode, form.sim, out_i.p, Uc * k, out_m.p, out_s.p);
       MFM_HIP_CHECK(hipGetLastError());
       MFM_HIP_CHECK(hipMemcpyAsync(mo->mean + (size_t)u0 * k, out_m.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
       MFM_HIP_CHECK(hipMemcpyAsync(mo->sd + (size_t)u0 * k, out_s.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -680,16 +716,44 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   MFM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// A similarity handle's sides may share columns: the score's split into per-side terms and one contraction is wrong there, so every
+// scoring form is refused on it, before the samples are looked at.
+void refuse_similarity_handle(const mfm_pairs *p) {
+  if (p->similarity)
+    throw Error(MFM_ERR_INVALID, "this is a similarity handle (mfm_pairs_create_sim): its sides may share columns, which the pair score's "
+                                 "decomposition does not allow; it serves mfm_pairs_sim* and mfm_pairs_topk_sim* only");
+}
+
 void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense,
-                     const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr) {
+                     const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr, int sim = -1) {
+  if (sim < 0) refuse_similarity_handle(p);
   if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo, rk, ps);
+  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo, rk, ps, sim);
 }
 
 void run_pairs_host(mfm_pairs *p, int rank, int n_samples, const double *w0s, const double *ws, const double *Vs, int mode, int k,
                     int64_t *idx, double *score, double *dense, const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr,
-                    const PairsPerSample *ps = nullptr) {
-  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo, rk, ps);
+                    const PairsPerSample *ps = nullptr, int sim = -1) {
+  if (sim < 0) refuse_similarity_handle(p);
+  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo, rk, ps, sim);
+}
+
+static_assert(PAIRS_SIM_COSINE == MFM_PAIRS_SIM_COSINE && PAIRS_SIM_DOT == MFM_PAIRS_SIM_DOT, "the metrics as the header numbers them");
+
+// the checks of the similarity calls that need neither samples nor a device
+void check_sim_metric(int metric) {
+  if (metric != PAIRS_SIM_COSINE && metric != PAIRS_SIM_DOT)
+    throw Error(MFM_ERR_INVALID, "bad similarity metric " + std::to_string(metric) + " (0: cosine, 1: dot)");
+}
+
+PairsMoments checked_sim_dense(const mfm_pairs *p, int metric, double *mean, double *sd) {
+  if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
+  check_sim_metric(metric);
+  if ((double)p->U * (double)p->I > 16777216.0)
+    throw Error(MFM_ERR_INVALID, "the dense similarity call returns every pair: more than 2^24 pairs are refused, use mfm_pairs_topk_sim");
+  PairsMoments mo;
+  mo.sd = sd;
+  return mo;
 }
 
 // the checks of the per-sample calls that need neither samples nor a device
@@ -730,8 +794,10 @@ PairsMoments checked_ucb(int k, double beta, const int64_t *idx, const double *v
 
 extern "C" {
 
-int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, const int32_t *q_indices, const double *q_data,
-                     int64_t I, const int64_t *c_indptr, const int32_t *c_indices, const double *c_data, mfm_pairs **out) {
+// both kinds of handle; `similarity`: no cross-side disjointness check (mfm_pairs_create_sim)
+static int pairs_create(bool similarity, int device, int64_t D, int64_t U, const int64_t *q_indptr, const int32_t *q_indices,
+                        const double *q_data, int64_t I, const int64_t *c_indptr, const int32_t *c_indices, const double *c_data,
+                        mfm_pairs **out) {
   *out = nullptr;
   try {
     // (the arguments first: a machine without a GPU still learns that they are wrong)
@@ -741,7 +807,7 @@ int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, 
     std::vector<uint8_t> seen((size_t)D, 0), seen_c((size_t)D, 0);
     for (int64_t q = 0; q < q_indptr[U]; q++) seen[(size_t)q_indices[q]] = 1;
     for (int64_t q = 0; q < c_indptr[I]; q++) {
-      if (seen[(size_t)c_indices[q]]) throw Error(MFM_ERR_INVALID, "X_query and X_cand share column " + std::to_string(c_indices[q]));
+      if (!similarity && seen[(size_t)c_indices[q]]) throw Error(MFM_ERR_INVALID, "X_query and X_cand share column " + std::to_string(c_indices[q]));
       seen_c[(size_t)c_indices[q]] = 1;
     }
     const int n = mfm_device_count();
@@ -750,6 +816,7 @@ int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, 
     if (device < 0 || device >= n) throw Error(MFM_ERR_INVALID, "device index out of range");
     std::unique_ptr<mfm_pairs> p(new mfm_pairs());
     p->device = device;
+    p->similarity = similarity;
     p->use_device();
     MFM_HIP_CHECK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     p->D = D;
@@ -772,6 +839,16 @@ int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, 
     g_pairs_error = ex.what();
     return MFM_ERR_RUNTIME;
   }
+}
+
+int mfm_pairs_create(int device, int64_t D, int64_t U, const int64_t *q_indptr, const int32_t *q_indices, const double *q_data,
+                     int64_t I, const int64_t *c_indptr, const int32_t *c_indices, const double *c_data, mfm_pairs **out) {
+  return pairs_create(false, device, D, U, q_indptr, q_indices, q_data, I, c_indptr, c_indices, c_data, out);
+}
+
+int mfm_pairs_create_sim(int device, int64_t D, int64_t U, const int64_t *q_indptr, const int32_t *q_indices, const double *q_data,
+                         int64_t I, const int64_t *c_indptr, const int32_t *c_indices, const double *c_data, mfm_pairs **out) {
+  return pairs_create(true, device, D, U, q_indptr, q_indices, q_data, I, c_indptr, c_indices, c_data, out);
 }
 
 void mfm_pairs_destroy(mfm_pairs *p) {
@@ -855,7 +932,7 @@ int mfm_pairs_add_block(mfm_pairs *p, int32_t side, int64_t col_offset, int64_t 
   // every stored column counts, referenced or not; nothing is marked before the whole block has passed
   for (int64_t q = 0; q < nnz; q++) {
     const size_t j = (size_t)(col_offset + indices[q]);
-    if (p->stored[1 - side][j]) throw Error(MFM_ERR_INVALID, "X_query and X_cand share column " + std::to_string(j));
+    if (!p->similarity && p->stored[1 - side][j]) throw Error(MFM_ERR_INVALID, "X_query and X_cand share column " + std::to_string(j));
   }
   {
     std::vector<uint8_t> own((size_t)width, 0);
@@ -959,6 +1036,39 @@ int mfm_pairs_topk_ucb(mfm_pairs *p, int32_t rank, int32_t n_samples, const doub
   PAIRS_CATCH(p)
 }
 
+int mfm_pairs_sim_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t metric, double *mean, double *sd) {
+  PAIRS_TRY(p)
+  const PairsMoments mo = checked_sim_dense(p, metric, mean, sd);
+  run_pairs_store(p, st, first, count, 0, 0, nullptr, nullptr, mean, &mo, nullptr, nullptr, metric);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_sim(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t metric,
+                  double *mean, double *sd) {
+  PAIRS_TRY(p)
+  const PairsMoments mo = checked_sim_dense(p, metric, mean, sd);
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, 0, 0, nullptr, nullptr, mean, &mo, nullptr, nullptr, metric);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_sim_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t metric, int32_t k, double beta,
+                             int64_t *idx, double *value, double *mean, double *sd) {
+  PAIRS_TRY(p)
+  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
+  check_sim_metric(metric);
+  run_pairs_store(p, st, first, count, 0, k, idx, value, nullptr, &mo, nullptr, nullptr, metric);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_sim(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                       int32_t metric, int32_t k, double beta, int64_t *idx, double *value, double *mean, double *sd) {
+  PAIRS_TRY(p)
+  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
+  check_sim_metric(metric);
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, 0, k, idx, value, nullptr, &mo, nullptr, nullptr, metric);
+  PAIRS_CATCH(p)
+}
+
 int mfm_pairs_topk_samples_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k,
                                  const int32_t *row_sample, int64_t *idx, double *value) {
   PAIRS_TRY(p)
@@ -1050,6 +1160,7 @@ void check_vb_model(const mfm_pairs *p, const PairsVbHost &h) {
 
 // dense != nullptr: (U, I) mean into dense and std into mo.sd; else the top k by mean + mo.beta * std (idx, score, mo.mean, mo.sd)
 void run_pairs_vb(mfm_pairs *p, const PairsVbHost &h, int k, int64_t *idx, double *score, double *dense, const PairsMoments &mo) {
+  refuse_similarity_handle(p);
   check_vb_model(p, h);
   const bool is_dense = dense != nullptr;
   if (!is_dense && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");

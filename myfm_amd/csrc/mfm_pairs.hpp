@@ -39,13 +39,15 @@ __device__ __forceinline__ bool pairs_beats(double va, int ia, double vb, int ib
 // The CSR row [pb, pe) times w and V, the one loop of the three embedding kernels: returns the linear term, hands put(f, a_f) the
 // row's factor f for every f in [0, KS) (zero for f >= K) and adds sum_j V[f, j]^2 x_j^2 over the factors to vv, all in CSR
 // order. V is read where it lies (factor-major (K, D), the store's layout): a side's rows hold a few entries each, and
-// neighbouring one-hot rows gather neighbouring columns.
-template <class Put>
+// neighbouring one-hot rows gather neighbouring columns. Without SIDE_TERMS (the similarity embedding, mfm_pairs_sim.hpp) only the
+// factors are formed: w is not read, neither the linear term nor vv is summed, the returned value is 0.
+template <bool SIDE_TERMS = true, class Put>
 __device__ __forceinline__ double pairs_embed_row(const int32_t *__restrict__ colidx, const double *__restrict__ val, int64_t pb,
                                                   int64_t pe, const double *__restrict__ w, const double *__restrict__ V, int64_t D,
                                                   int K, int KS, double &vv, Put put) {
   double lin = 0.0;
-  for (int64_t p = pb; p < pe; p++) lin += val[p] * w[colidx[p]];
+  if constexpr (SIDE_TERMS)
+    for (int64_t p = pb; p < pe; p++) lin += val[p] * w[colidx[p]];
   for (int f = 0; f < KS; f++) {
     double a = 0.0;
     if (f < K) {
@@ -53,7 +55,7 @@ __device__ __forceinline__ double pairs_embed_row(const int32_t *__restrict__ co
       for (int64_t p = pb; p < pe; p++) {
         const double x = val[p], v = Vf[colidx[p]];
         a += x * v;
-        vv += (x * x) * (v * v);
+        if constexpr (SIDE_TERMS) vv += (x * x) * (v * v);
       }
     }
     put(f, a);
@@ -79,6 +81,8 @@ struct PairsBlockRef {
 };
 
 // One thread per (block row m, sample s). CSR with block-local columns; `off`: the block's first column in the model's feature space.
+// SIM (the similarity embedding): the factors alone, lin and vv are neither computed nor written.
+template <bool SIM = false>
 __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed_block(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
                                                                 const double *__restrict__ val, int64_t M, int64_t off,
                                                                 const double *const *__restrict__ wv, int64_t D, int K, int KS,
@@ -89,10 +93,12 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed_block(const int64_t *_
   const int s = blockIdx.y;
   double *__restrict__ Trow = T + ((int64_t)s * M + m) * KS;
   double vv = 0.0;
-  const double lin =
-      pairs_embed_row(colidx, val, rowptr[m], rowptr[m + 1], wv[s] + off, wv[s] + D + off, D, K, KS, vv, [&](int f, double a) { Trow[f] = a; });
-  lin_out[(int64_t)s * M + m] = lin;
-  vv_out[(int64_t)s * M + m] = vv;
+  const double lin = pairs_embed_row<!SIM>(colidx, val, rowptr[m], rowptr[m + 1], wv[s] + off, wv[s] + D + off, D, K, KS, vv,
+                                           [&](int f, double a) { Trow[f] = a; });
+  if constexpr (!SIM) {
+    lin_out[(int64_t)s * M + m] = lin;
+    vv_out[(int64_t)s * M + m] = vv;
+  }
 }
 
 // One thread per (side row, sample): P_s[r, 0..KS) in the order the MFMA reads it and the bias A_s[r]. Fragment order: the 64
@@ -106,7 +112,12 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed_block(const int64_t *_
 // MAPPED (the row -> sample plan of mfm_pairs_samples.hpp): output row r holds side row r0 + map_row[r] (-1: a padding row, zeros)
 // under sample map_s[r] alone -- one thread per output row, P with KS / 4 k-steps per row tile and one bias per row, the
 // arithmetic of a row under its sample unchanged. Without MAPPED neither map is read.
-template <bool REL, bool MAPPED = false>
+// SIM (the similarity forms, mfm_pairs_sim.hpp): the bias slot holds the row's normalisation r instead -- SIM 1
+// (cosine) r = 1 / sqrt(sq) with sq = sum_k P_k^2 summed in factor order as above, r = 0 where sq is 0 (an empty row, rank 0, an
+// all-zero embedding; an sq that overflowed gives 0 as well, and the value of such a row may be NaN: finite embeddings are
+// assumed); SIM 2 (dot) r = 1 -- and 0 for a padding row; neither w nor a block's lin / vv is read. SIM 0 is the scorer's
+// embedding, unchanged.
+template <bool REL, bool MAPPED = false, int SIM = 0>
 __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
                                                           const double *__restrict__ val, int64_t r0, int64_t R, int64_t Rpad,
                                                           const double *const *__restrict__ wv, int64_t D, int K, int KS, int S,
@@ -128,7 +139,7 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed(const int64_t *__restr
     pe = rowptr[r0 + src + 1];
   }
   double sq = 0.0, vv = 0.0;
-  double lin = pairs_embed_row(colidx, val, pb, pe, w, w + D, D, K, KS, vv, [&](int f, double a) {
+  double lin = pairs_embed_row<SIM == 0>(colidx, val, pb, pe, w, w + D, D, K, KS, vv, [&](int f, double a) {
     if constexpr (REL) {
       if (live)
         for (int b = 0; b < n_blk; b++) a += blk[b].T[((int64_t)s * blk[b].M + blk[b].o2b[r0 + src]) * KS + f];
@@ -136,7 +147,7 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed(const int64_t *__restr
     Prow[(int64_t)(f >> 2) * 64 + (f & 3) * 16] = a;
     sq += a * a;
   });
-  if constexpr (REL) {
+  if constexpr (REL && SIM == 0) {
     if (live)
       for (int b = 0; b < n_blk; b++) {
         const int64_t e = (int64_t)s * blk[b].M + blk[b].o2b[r0 + src];
@@ -144,7 +155,10 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed(const int64_t *__restr
         vv += blk[b].vv[e];
       }
   }
-  bias[(MAPPED ? (int64_t)0 : (int64_t)s * Rpad) + r] = lin + 0.5 * (sq - vv);
+  if constexpr (SIM == 0)
+    bias[(MAPPED ? (int64_t)0 : (int64_t)s * Rpad) + r] = lin + 0.5 * (sq - vv);
+  else
+    bias[(MAPPED ? (int64_t)0 : (int64_t)s * Rpad) + r] = !live ? 0.0 : SIM == 2 ? 1.0 : sq > 0.0 ? 1.0 / sqrt(sq) : 0.0;
 }
 
 // sum over the samples, in sample order, of a side's biases (regression mode adds it once)

@@ -20,6 +20,24 @@ __device__ __forceinline__ void pairs_welford(double v, double rn, double &mean,
   m2 += d * (v - mean);
 }
 
+// The finish of the scorer's moments forms, a policy of PairsWelford and k_pairs_moments_at: the per-sample value of the pair from
+// the contraction. tile: a pass's MT x NT tiles through pairs_finish_sample and pairs_sample_value; at: one pair from its inner
+// product `dot`. (The similarity forms bring their own, PairsFinishSim of mfm_pairs_sim.hpp.)
+template <int MODE>
+struct PairsFinishScore {
+  template <int MT, int NT, class Take>
+  static __device__ __forceinline__ void tile(const PairsArgs &a, int s, int64_t q0, int64_t ct0, int lane, const pairs_d4 (&acc)[MT][NT],
+                                              Take take) {
+    const double *__restrict__ cs = MODE == 2 ? a.cut + (size_t)s * a.n_cut : nullptr;
+    pairs_finish_sample<MT, NT>(a, s, q0, ct0, lane, acc,
+                                [&](int m, int n, int g, double t) { take(m, n, g, pairs_sample_value<MODE>(t, cs, a.n_cut)); });
+  }
+  static __device__ __forceinline__ double at(const PairsArgs &a, int s, int64_t u, int i, double dot) {
+    const double t = ((a.w0s[s] + a.Ab[(size_t)s * a.Upad + u]) + a.Bb[(size_t)s * a.Ipad + i]) + dot;
+    return pairs_sample_value<MODE>(t, MODE == 2 ? a.cut + (size_t)s * a.n_cut : nullptr, a.n_cut);
+  }
+};
+
 // what the moments form finishes for a pair
 struct PairsSpread {
   double mean, sd, v;  // v = mean + beta * sd, the ranking value
@@ -27,7 +45,8 @@ struct PairsSpread {
 
 // The accumulator of the moments form (the interface: PairsMean). Every MODE finishes its 16 x 16 tiles per sample, and the tile
 // counts are MT * NT = 4: 32 accumulator registers and 2 x 32 of moments, against 64 + 64 of the mean forms' modes 1 and 2.
-template <int MT, int NT, int MODE>
+// Finish: what a sample's value is (PairsFinishScore; PairsFinishSim); the recurrence, value(), store_dense and ranked are shared.
+template <int MT, int NT, int MODE, class Finish = PairsFinishScore<MODE>>
 struct PairsWelford {
   static constexpr bool PER_SAMPLE = true;
   typedef PairsSpread Value;
@@ -43,10 +62,8 @@ struct PairsWelford {
   }
   __device__ __forceinline__ void add(const PairsArgs &a, int s, int64_t q0, int64_t ct0, int lane, const pairs_d4 (&acc)[MT][NT]) {
     const double rn = 1.0 / (double)(s + 1);
-    const double *__restrict__ cs = MODE == 2 ? a.cut + (size_t)s * a.n_cut : nullptr;
-    pairs_finish_sample<MT, NT>(a, s, q0, ct0, lane, acc, [&](int m, int n, int g, double t) {
-      pairs_welford(pairs_sample_value<MODE>(t, cs, a.n_cut), rn, mean[m][n][g], m2[m][n][g]);
-    });
+    Finish::template tile<MT, NT>(a, s, q0, ct0, lane, acc,
+                                  [&](int m, int n, int g, double v) { pairs_welford(v, rn, mean[m][n][g], m2[m][n][g]); });
   }
   __device__ __forceinline__ void rows(const PairsArgs &, int64_t, int) {}
   __device__ __forceinline__ void column(const PairsArgs &, int64_t) {}
@@ -72,8 +89,8 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_tile_moments(PairsArgs a) {
 // one after the other in factor order, which is NOT the MFMA's association, so mean + beta * std of this kernel agrees with the
 // selected value within rounding, not bit for bit -- then the 64 values pass through the same Welford recurrence in sample
 // order, every lane doing the same arithmetic on broadcast values. No atomics, nothing depends on the grid. An entry without a
-// candidate (index -1) gets NaN for both.
-template <int MODE>
+// candidate (index -1) gets NaN for both. Finish::at gives the sample's value from the inner product, as Finish::tile does for a tile.
+template <int MODE, class Finish = PairsFinishScore<MODE>>
 __global__ __launch_bounds__(PAIRS_WG) void k_pairs_moments_at(PairsArgs a, const int32_t *__restrict__ out_i, int64_t n_entries,
                                                                double *__restrict__ out_mean, double *__restrict__ out_std) {
   const int lane = threadIdx.x & 63;
@@ -102,8 +119,7 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_moments_at(PairsArgs a, cons
         const size_t of = o + (size_t)(f >> 2) * 64 + (f & 3) * 16;
         dot += P[of] * Q[of];
       }
-      const double t = ((a.w0s[s] + a.Ab[(size_t)s * a.Upad + u]) + a.Bb[(size_t)s * a.Ipad + i]) + dot;
-      v = pairs_sample_value<MODE>(t, MODE == 2 ? a.cut + (size_t)s * a.n_cut : nullptr, a.n_cut);
+      v = Finish::at(a, s, u, i, dot);
     }
     const int n_here = a.S - s0 < 64 ? a.S - s0 : 64;
     for (int j = 0; j < n_here; j++) pairs_welford(__shfl(v, j), 1.0 / (double)(s0 + j + 1), mean, m2);

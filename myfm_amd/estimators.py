@@ -914,6 +914,64 @@ ThompsonRanking = namedtuple("ThompsonRanking", ["indices", "value", "sample"])
 TopKProbability = namedtuple("TopKProbability", ["indices", "probability"])
 
 
+SIMILARITY_METRICS = ("cosine", "dot")
+
+
+class _SimilarityMixin:
+    """"Which items are like this item" (or user like this user) with a fitted model, for the estimators that keep S
+    posterior samples. A side row a -- sparse in the model's feature space, with relation-block arguments as _PairScoringMixin takes
+    them -- has the embedding P_s[a] = V_s^T a under kept sample s, and per sample
+
+        cosine: c_s(a, b) = <P_s[a], P_s[b]> / (|P_s[a]| |P_s[b]|), 0 where a norm is 0 (an empty row, rank 0), not clamped;
+        dot:    c_s(a, b) = <P_s[a], P_s[b]>;
+
+        mean = sum_s c_s / S,    std = the population standard deviation of the c_s,    value = mean + beta * std.
+
+    The kept samples' factors differ by signs and rotations, so the cosine of the averaged V means nothing; c_s is invariant under
+    each sample's own rotation, which is also why a combine_chains result pools chains whose factors are rotated against each other.
+    The task plays no part: w0, w and the cutpoints are not read. The two sides may store the same columns (items against items).
+    Not covered: the variational estimators, row-sharded operation, other metrics. The arguments are validated on the host before the
+    device is touched."""
+
+    @staticmethod
+    def _similarity_metric(metric):
+        if not isinstance(metric, str) or metric not in SIMILARITY_METRICS:
+            raise ValueError('metric must be "cosine" or "dot"')
+        return metric
+
+    def predict_similarity(self, X_a, X_b=None, metric="cosine", X_rel_a=[], X_rel_b=[]):
+        """PairSummary(mean (U, I), std (U, I)) of the similarity of every row of X_a with every row of X_b (None: X_a itself, with
+        X_rel_a). U * I > 2^24 is refused (ValueError): use predict_similar."""
+        metric = self._similarity_metric(metric)
+        if X_b is None:
+            X_b, X_rel_b = X_a, X_rel_a
+        predictor, Xa, Xb, ra, rb = self._pair_sides(X_a, X_b, X_rel_a, X_rel_b)
+        return PairSummary(*predictor.predict_similarity(Xa, Xb, metric, ra, rb))
+
+    def predict_similar(self, X_query, X_cand=None, k: int = 10, metric="cosine", beta: float = 0.0, exclude=None, exclude_self=None,
+                        X_rel_query=[], X_rel_cand=[]):
+        """Per query row the k candidates of largest value = mean + beta * std of the similarity: RankedSummary(indices int64 (U, k),
+        value, mean, std), each row ordered by (value descending, candidate index ascending); tail index -1, value -inf, mean and
+        std NaN. X_cand None: the candidates are the query rows themselves (with X_rel_query), and exclude_self, which then defaults
+        to True, leaves every row out of its own list (the diagonal joins the exclusion pattern). exclude_self=True with an X_cand
+        is a ValueError. `exclude`, k and beta as in predict_topk_ucb; mean and std are recomputed for the selected pairs with the
+        factors summed in another order, so value equals mean + beta * std within rounding."""
+        metric = self._similarity_metric(metric)
+        same = X_cand is None
+        if same:
+            X_cand, X_rel_cand = X_query, X_rel_query
+        elif exclude_self:
+            raise ValueError("exclude_self needs the candidates to be the query rows (X_cand=None)")
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        k, beta, exclude = _ranked_args(Xq, Xc, k, exclude, beta)
+        if same and (exclude_self is None or exclude_self):
+            diag = sps.identity(Xq.shape[0], dtype=np.float64, format="csr")
+            if exclude is not None:  # (the stored positions count, whatever their values)
+                diag = sps.csr_matrix(sps.csr_matrix((np.ones(exclude.nnz), exclude.indices, exclude.indptr), shape=exclude.shape) + diag)
+            exclude = diag
+        return RankedSummary(*predictor.predict_similar(Xq, Xc, k, metric, beta, exclude, rq, rc))
+
+
 def _fold_in_checked(est, name, X, y, entity, group, n_entities):
     """The host-side checks that fold_in and fold_in_gibbs share, in one order and with one set of messages (`name`: the calling
     method). Returns (predictor, D, K, X csr, y float64 (n,), entity int64 (n,), U, the hyper-parameters of the kept samples, group)."""
@@ -1092,7 +1150,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -1160,7 +1218,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDi
         return _folded_in(self, predictor.extended(w_new, V_new), D, U, g)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -1236,7 +1294,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""

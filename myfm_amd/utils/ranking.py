@@ -1,4 +1,5 @@
-"""Ranking metrics from the ranks of held-out pairs (predict_rank). Pure NumPy."""
+"""Ranking metrics from the ranks of held-out pairs (predict_rank) and neighbour lists from predict_similar (DESIGN
+4.13.4). Pure NumPy."""
 import numpy as np
 from scipy import sparse as sps
 
@@ -59,3 +60,26 @@ def ranking_metrics(result, targets, k=10):
     if ok.any():
         out["auc"] = float(np.mean(1.0 - sum_only[ok] / (Tq[ok] * others[ok])))
     return out
+
+
+def neighbour_table(result, names=None, min_mean=None, max_std=None):
+    """Per-query neighbour lists from a RankedSummary `result` of predict_similar (or any (indices, value, mean, std) quadruple of
+    (U, k) arrays): a list of U lists of (name or index, mean, std) in the order of the ranking, the padding entries (index -1)
+    left out. names: a sequence indexed by candidate index; without it the int index itself. min_mean / max_std: keep only the
+    entries with mean >= min_mean and std <= max_std -- neighbours that are similar, and on which the kept samples agree."""
+    indices, _, mean, std = result
+    indices, mean, std = np.asarray(indices), np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    if indices.ndim != 2 or mean.shape != indices.shape or std.shape != indices.shape:
+        raise ValueError("result must hold (U, k) arrays of indices, value, mean and std")
+    if names is not None and indices.size and int(indices.max()) >= len(names):
+        raise ValueError("names has %d entries but the result holds candidate index %d" % (len(names), int(indices.max())))
+    keep = indices >= 0
+    if min_mean is not None:
+        keep &= mean >= float(min_mean)
+    if max_std is not None:
+        keep &= std <= float(max_std)
+    table = []
+    for u in range(indices.shape[0]):
+        at = np.flatnonzero(keep[u])
+        table.append([(int(indices[u, j]) if names is None else names[int(indices[u, j])], float(mean[u, j]), float(std[u, j])) for j in at])
+    return table
