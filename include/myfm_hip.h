@@ -668,6 +668,26 @@ int mfm_pairs_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double
 int mfm_pairs_topk(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                    int32_t mode, int32_t k, int64_t *idx, double *score);
 
+/* ---- the screened top-k (csrc/mfm_pairs_screen.hpp) -----------------------------------------------------------------
+ * mfm_pairs_topk's mode-0 list by another route: a bf16 MFMA contraction leaves min(256, max(64, 2 k)) candidates per query row, all
+ * but the last are rescored with the fp64 MFMA in mfm_pairs_topk's accumulation order, and a per-row certificate -- a derived bound on
+ * the bf16 path's error, one constant of it measured -- says whether a candidate left out could belong to the list.
+ *   topk_screened: idx[U * k], value[U * k], certified[U] (one byte per row). Where certified[u] != 0, row u of idx and value is bit for
+ *          bit mfm_pairs_topk's (mode 0), tail included; the other rows hold no result and are the caller's to pass to mfm_pairs_topk.
+ *          1 <= k <= 128. A row or candidate with an operand that is not finite or of magnitude outside [2^-50, 2^50] (zero apart) is
+ *          never certified (such a candidate: no row is).
+ *   screen_scores: the dense diagnostic, U * I <= 2^24: r[U * I] = Bsum[i] + the bf16 contraction, the approximation of
+ *          r(u, i) = S value(u, i) - (sum_s w0_s + A_s[u]), and bound[U], E_u with |r~ - r| <= S E_u by the error model.
+ * The bf16 copy of the candidate embedding (+ 25 %) is resident next to it and counts in the memory rule. MFM_ERR_INVALID before any
+ * launch: NULL outputs, k outside [1, 128], the dense call's pair limit, a similarity handle.                                      */
+int mfm_pairs_topk_screened_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t k, int64_t *idx, double *value,
+                                  uint8_t *certified);
+int mfm_pairs_topk_screened(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t k,
+                            int64_t *idx, double *value, uint8_t *certified);
+int mfm_pairs_screen_scores_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, double *r, double *bound);
+int mfm_pairs_screen_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, double *r,
+                            double *bound);
+
 /* ---- ranking by an upper confidence bound (csrc/mfm_pairs_ucb.hpp) ---------------------------------------------
  * The same pairs, sides, blocks, exclusions, sample views and memory rule, but the spread over the samples is kept. With v_s(u, i)
  * the per-sample value of the mode (0: score_s, 1: Phi(score_s), 2: sum_j Phi(score_s - cut_s[j])):

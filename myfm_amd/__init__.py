@@ -36,6 +36,7 @@ from .estimators import (  # noqa: E402
     PairSummary,
     PointwiseDensity,
     RankedSummary,
+    ScreenedRanking,
     SampleRankings,
     ScoreContributions,
     ScoreMoments,
@@ -60,6 +61,7 @@ __all__ = [
     "FOLD_IN_MAX_RANK",
     "PairSummary",
     "RankedSummary",
+    "ScreenedRanking",
     "ScoreMoments",
     "TargetRanks",
     "PointwiseDensity",

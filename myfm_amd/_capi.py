@@ -40,6 +40,7 @@ SYMBOLS = [
     "mfm_vb_design_levels",
     "mfm_pairs_create", "mfm_pairs_destroy", "mfm_pairs_last_error", "mfm_pairs_set_exclude", "mfm_pairs_set_scratch_bound",
     "mfm_pairs_scores_store", "mfm_pairs_topk_store", "mfm_pairs_scores", "mfm_pairs_topk", "mfm_pairs_add_block",
+    "mfm_pairs_topk_screened_store", "mfm_pairs_topk_screened", "mfm_pairs_screen_scores_store", "mfm_pairs_screen_scores",
     "mfm_pairs_set_cutpoints", "mfm_pairs_moments_store", "mfm_pairs_moments", "mfm_pairs_topk_ucb_store", "mfm_pairs_topk_ucb",
     "mfm_pairs_set_targets", "mfm_pairs_rank_store", "mfm_pairs_rank",
     "mfm_pairs_topk_samples_store", "mfm_pairs_topk_samples", "mfm_pairs_topk_prob_store", "mfm_pairs_topk_prob",
@@ -246,6 +247,10 @@ def lib():
     L.mfm_pairs_topk_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P]
     L.mfm_pairs_scores.argtypes = [vp, i32, i32, P, P, P, i32, P]
     L.mfm_pairs_topk.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P]
+    L.mfm_pairs_topk_screened_store.argtypes = [vp, vp, i32, i32, i32, P, P, P]
+    L.mfm_pairs_topk_screened.argtypes = [vp, i32, i32, P, P, P, i32, P, P, P]
+    L.mfm_pairs_screen_scores_store.argtypes = [vp, vp, i32, i32, P, P]
+    L.mfm_pairs_screen_scores.argtypes = [vp, i32, i32, P, P, P, P, P]
     L.mfm_pairs_moments_store.argtypes = [vp, vp, i32, i32, i32, P, P]
     L.mfm_pairs_moments.argtypes = [vp, i32, i32, P, P, P, i32, P, P]
     L.mfm_pairs_topk_ucb_store.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, P, P, P, P]
@@ -1195,6 +1200,34 @@ class Pairs:
 
     def topk_store(self, store, k, mode=0, first=0, count=None):
         return self._topk(_resident(store, first, count), k, mode)
+
+    # ---- the screened top-k: mode 0's list through a bf16 shortlist, exact rescoring and a per-row certificate
+    def _topk_screened(self, src, k):
+        kk = max(int(k), 1)
+        idx, val, cert = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk)), np.zeros(self.U, dtype=np.uint8)
+        self._ck(src.call("mfm_pairs_topk_screened", self.h, int(k), _p(idx), _p(val), _p(cert)))
+        return idx, val, cert.astype(bool)
+
+    def _screen_scores(self, src):
+        r, bound = np.empty((self.U, self.I)), np.empty(self.U)
+        self._ck(src.call("mfm_pairs_screen_scores", self.h, _p(r), _p(bound)))
+        return r, bound
+
+    def topk_screened(self, samples, k):
+        """(indices int64 (U, k), values (U, k), certified bool (U,)): where certified, the row equals topk(samples, k, mode=0)
+        bit for bit; the other rows hold no result (send them through topk). 1 <= k <= 128."""
+        return self._topk_screened(_host(samples), k)
+
+    def topk_screened_store(self, store, k, first=0, count=None):
+        return self._topk_screened(_resident(store, first, count), k)
+
+    def screen_scores(self, samples):
+        """(r (U, I), E (U,)): the bf16 path's approximation of S * value - (sum of w0 + the query bias) and the per-row bound with
+        |r - exact| <= S * E by the error model"""
+        return self._screen_scores(_host(samples))
+
+    def screen_scores_store(self, store, first=0, count=None):
+        return self._screen_scores(_resident(store, first, count))
 
     # ---- the moments form (DESIGN 4.13.1): mean and population std over the samples of the per-sample value
     def moments(self, samples, mode=0):

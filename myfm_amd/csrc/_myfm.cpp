@@ -885,6 +885,22 @@ struct Predictor {
     dp.ck(on_samples(mfm_pairs_topk_store, mfm_pairs_topk, dp.p, pc.mode, (int)k, idx.mutable_data(), score.mutable_data()));
     return py::make_tuple(idx, score);
   }
+  // (indices (U, k), value (U, k), certified bool (U,)): predict_topk's rows where certified; regression only
+  py::tuple predict_topk_screened(const py::object &Xqo, const py::object &Xco, int64_t k, const py::object &excludeo, const py::object &rqo,
+                                  const py::object &rco) const {
+    if (k < 1 || k > 128) throw std::invalid_argument("k must be in [1, 128]");
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    if (pc.mode != 0) throw std::invalid_argument("predict_topk_screened serves regression models (a value linear in the score)");
+    pc.ranked(k, excludeo);
+    py::array_t<int64_t> idx({pc.U(), (py::ssize_t)k});
+    py::array_t<double> value({pc.U(), (py::ssize_t)k});
+    py::array_t<bool> cert((py::ssize_t)pc.U());
+    static_assert(sizeof(bool) == 1, "one byte per row");
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_topk_screened_store, mfm_pairs_topk_screened, dp.p, (int)k, idx.mutable_data(), value.mutable_data(),
+                     (uint8_t *)cert.mutable_data()));
+    return py::make_tuple(idx, value, cert);
+  }
   // (mean (U, I), std (U, I)) over the kept samples of the per-sample value of every pair
   py::tuple predict_pairs_dist(const py::object &Xqo, const py::object &Xco, const py::object &rqo, const py::object &rco) const {
     const PairCall pc = pair_call(Xqo, Xco, rqo, rco);
@@ -2726,6 +2742,10 @@ struct VPredictor {
                          const py::object &rc) const {
     return mean_predictor().predict_topk(Xq, Xc, k, exclude, rq, rc);
   }
+  py::tuple predict_topk_screened(const py::object &Xq, const py::object &Xc, int64_t k, const py::object &exclude, const py::object &rq,
+                                  const py::object &rc) const {
+    return mean_predictor().predict_topk_screened(Xq, Xc, k, exclude, rq, rc);
+  }
   py::tuple predict_rank(const py::object &Xq, const py::object &Xc, const py::object &targets, const py::object &exclude,
                          const py::object &rq, const py::object &rc) const {
     return mean_predictor().predict_rank(Xq, Xc, targets, exclude, rq, rc);
@@ -3282,6 +3302,8 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk", &Predictor::predict_topk, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk_screened", &Predictor::predict_topk_screened, py::arg("X_query"), py::arg("X_cand"), py::arg("k"),
+           py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_rank", &Predictor::predict_rank, py::arg("X_query"), py::arg("X_cand"), py::arg("targets"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_pairs_dist", &Predictor::predict_pairs_dist, py::arg("X_query"), py::arg("X_cand"),
@@ -3524,6 +3546,8 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk", &VPredictor::predict_topk, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk_screened", &VPredictor::predict_topk_screened, py::arg("X_query"), py::arg("X_cand"), py::arg("k"),
+           py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_rank", &VPredictor::predict_rank, py::arg("X_query"), py::arg("X_cand"), py::arg("targets"), py::arg("exclude") = py::none(),
            py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_moments", &VPredictor::predict_moments, py::arg("X"), py::arg("relations") = py::tuple(), py::arg("extra_var") = 0.0,

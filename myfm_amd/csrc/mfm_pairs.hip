@@ -26,9 +26,13 @@
 // holds the rows' normalisation; the one family that a similarity handle, mfm_pairs_create_sim, serves).
 // The variational forms (mfm_pairs_moments_vb, mfm_pairs_topk_bound_vb; mfm_pairs_vb.hpp) score a mean-field Gaussian
 // posterior instead of samples: run_pairs_vb at the end of this file, with the memory rule, the chunks and the stripes above.
+// The screened top-k (mfm_pairs_topk_screened*, mfm_pairs_screen_scores*; mfm_pairs_screen.hpp): mode 0's list through a
+// bf16 contraction, an exact rescoring of its shortlist and a per-row certificate (run_screened below); a bf16 copy of Q is resident
+// next to Q and counts in the memory rule.
 #include "mfm_pairs.hpp"
 #include "mfm_pairs_rank.hpp"
 #include "mfm_pairs_samples.hpp"
+#include "mfm_pairs_screen.hpp"
 #include "mfm_pairs_sim.hpp"
 #include "mfm_pairs_ucb.hpp"
 #include "mfm_pairs_vb.hpp"
@@ -429,12 +433,191 @@ void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, in
   }
 }
 
+// ---- the screened top-k (mfm_pairs_screen.hpp) -------------------------------------------------------------------
+// what a screened call adds: the per-row certificate, or -- the dense diagnostic -- the per-row bound next to r~
+struct PairsScreen {
+  uint8_t *certified = nullptr;  // [U]
+  double *bound = nullptr;       // [U]: E_u (dense)
+};
+
+// the bf16 copy of Q, its norms and flags: what a screened call keeps resident beyond a plain one
+double screen_q_bytes(int64_t Ipad, int64_t NK) {
+  const int64_t Ipb = round_up(Ipad, SCREEN_COL_ALIGN), NC = round_up(NK * 4, SCREEN_INNER) / SCREEN_INNER;
+  return (double)Ipb * NC * SCREEN_INNER * 2 + (double)Ipb * 12;
+}
+
+template <auto KERNEL>
+void launch_screen(hipStream_t s, dim3 grid, size_t lds, const ScreenArgs &sa) {
+  static DeviceOnce raised;
+  if (lds > 48 * 1024 && raised.need()) {
+    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised.mark();
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(PAIRS_WG), lds, s, sa);
+}
+
+// The form of a screened call: the shortlist length k_s picks the rows per tile by PairsSel's table, the dense diagnostic takes 64.
+struct ScreenForm {
+  int MT;
+  void (*launch)(hipStream_t, dim3, const ScreenArgs &);
+  int rows() const { return 16 * MT; }
+  int step() const { return 64 * (16 / MT); }
+};
+
+template <int MT, bool DENSE>
+ScreenForm screen_form_of() {
+  return {MT, [](hipStream_t s, dim3 grid, const ScreenArgs &sa) {
+            launch_screen<k_screen_tile<MT, DENSE>>(s, grid, (DENSE ? 0 : PairsSel<MT>::BYTES) + screen_stage_bytes<MT>(), sa);
+          }};
+}
+
+ScreenForm screen_form(bool dense, int ks) {
+  if (dense) return screen_form_of<4, true>();
+  if (ks <= 64) return screen_form_of<4, false>();
+  if (ks <= 128) return screen_form_of<2, false>();
+  return screen_form_of<1, false>();
+}
+
+// The queries in chunks against the resident candidate side of `call` (mode 0). Per chunk: embed and pack P, screen into the
+// stripes' lists of k_s = min(256, max(64, 2 k)) entries, merge, rescore the merged list's first k_s - 1 entries exactly, finish.
+// Scratch per query row: run_pairs' mean-form terms with k_s for k, plus the bf16 P, the norm and flag, the exact values and the
+// outputs. The rows that come back uncertified are the caller's to send through mfm_pairs_topk.
+template <class Embed>
+void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsScreen &sc, int k, int64_t *idx, double *score, double *dense, Embed embed) {
+  hipStream_t s = p->stream;
+  const bool is_dense = dense != nullptr;
+  const int S = call.S, KS = call.KS4 * 4, ks = is_dense ? 0 : std::min(256, std::max(64, 2 * k));
+  const int64_t U = p->U, I = call.I, W = call.W, NK = call.NK, Ipad = call.Ipad, L = NK * 4;
+  const int64_t Lp = round_up(L, SCREEN_INNER), Ipb = round_up(Ipad, SCREEN_COL_ALIGN);
+  const int NC = (int)(Lp / SCREEN_INNER);
+  const ScreenForm form = screen_form(is_dense, ks);
+  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (double)Lp * 2 + 12 +
+                         (is_dense ? (double)I * 8 + 8
+                                   : (p->has_exclude ? (double)W * 4 : 0.0) + (double)(PAIRS_MAX_STRIPES + 2) * ks * 12 + (double)k * 12 + 1);
+  int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
+  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
+  chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
+  const int64_t steps_total = (std::max<int64_t>(I, 1) + form.step() - 1) / form.step();
+
+  // ---- candidate side, once: the bf16 copy, the norms, the flags and the two maxima
+  DevBuf<screen_u4> Qb, Pb;
+  DevBuf<double> qn, cmax, pn;
+  DevBuf<int32_t> qflag, cand_flag, pflag;
+  Qb.alloc((size_t)std::max<int64_t>(Ipb / 16 * NC * 64, 1));
+  qn.alloc((size_t)Ipb);
+  qflag.alloc((size_t)Ipb);
+  cmax.alloc(2);
+  cand_flag.alloc_zero(1, s);
+  hipLaunchKernelGGL(k_screen_pack, dim3((unsigned)(Ipb / 16)), dim3(PAIRS_WG), 0, s, call.Qf, NK, Ipad / 16, NC, call.Bsum, Qb.p, qn.p, qflag.p,
+                     cand_flag.p);
+  hipLaunchKernelGGL(k_screen_cand_max, dim3(1), dim3(PAIRS_WG), 0, s, (const double *)qn.p, call.Bsum, I, cmax.p);
+  MFM_HIP_CHECK(hipGetLastError());
+
+  DevBuf<double> Pf, Ab, Asum, list_v, sl_v, ex_v, out_v, d_dense, d_E;
+  DevBuf<int32_t> list_i, sl_i, out_i;
+  DevBuf<uint32_t> mask;
+  DevBuf<uint8_t> d_cert;
+  std::vector<int32_t> h_idx;
+  for (int64_t u0 = 0; u0 < U; u0 += chunk) {
+    const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
+    ensure(Pf, (size_t)(Upad * NK * 4));
+    ensure(Ab, (size_t)(Upad * S));
+    ensure(Asum, (size_t)Upad);
+    ensure(Pb, (size_t)(Upad / 16 * NC * 64));
+    ensure(pn, (size_t)Upad);
+    ensure(pflag, (size_t)Upad);
+    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p, nullptr, nullptr);
+    hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Ab.p, S, Upad, Asum.p);
+    hipLaunchKernelGGL(k_screen_pack, dim3((unsigned)(Upad / 16)), dim3(PAIRS_WG), 0, s, (const double *)Pf.p, NK, Upad / 16, NC,
+                       (const double *)Asum.p, Pb.p, pn.p, pflag.p, (int32_t *)nullptr);
+    MFM_HIP_CHECK(hipGetLastError());
+    const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
+    if (use_mask) {
+      ensure(mask, (size_t)(Uc * W));
+      MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), s));
+      hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
+    }
+    // stripes as run_pairs chooses them, from this form's rows and step
+    const int64_t n_qt = Upad / form.rows();
+    int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_qt - 1) / n_qt, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
+    const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
+    n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
+    const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
+    ScreenArgs sa;
+    sa.a = call;
+    sa.a.Pf = Pf.p;
+    sa.a.Ab = Ab.p;
+    sa.a.Asum = Asum.p;
+    sa.a.Upad = Upad;
+    sa.a.Uc = Uc;
+    sa.a.stripe_len = stripe_steps * form.step();
+    sa.a.mask = use_mask ? mask.p : nullptr;
+    sa.a.list_rows = Upad;
+    sa.a.u0 = u0;
+    sa.a.k = ks;
+    sa.Pb = Pb.p;
+    sa.Qb = Qb.p;
+    sa.NC = NC;
+    ScreenBound sb;
+    sb.pnorm = pn.p;
+    sb.pflag = pflag.p;
+    sb.cand_flag = cand_flag.p;
+    sb.cmax = cmax.p;
+    sb.Asum = Asum.p;
+    sb.w0sum = call.w0sum;
+    sb.eps = screen_eps(Lp);
+    sb.L = (double)L;
+    sb.S = S;
+    if (is_dense) {
+      ensure(d_dense, (size_t)(Uc * I));
+      ensure(d_E, (size_t)Uc);
+      sa.a.dense = d_dense.p;
+      form.launch(s, grid, sa);
+      hipLaunchKernelGGL(k_screen_bound, dim3((unsigned)((Uc + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, sb, Uc, d_E.p);
+      MFM_HIP_CHECK(hipGetLastError());
+      MFM_HIP_CHECK(hipMemcpyAsync(dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(sc.bound + u0, d_E.p, (size_t)Uc * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipStreamSynchronize(s));
+      continue;
+    }
+    ensure(list_v, (size_t)(n_stripes * Upad * ks));
+    ensure(list_i, (size_t)(n_stripes * Upad * ks));
+    ensure(sl_v, (size_t)(Uc * ks));
+    ensure(sl_i, (size_t)(Uc * ks));
+    ensure(ex_v, (size_t)(Uc * ks));
+    ensure(out_v, (size_t)(Uc * k));
+    ensure(out_i, (size_t)(Uc * k));
+    ensure(d_cert, (size_t)Uc);
+    sa.a.list_v = list_v.p;
+    sa.a.list_i = list_i.p;
+    if (I > 0) {
+      form.launch(s, grid, sa);
+      MFM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, ks, sl_v.p,
+                       sl_i.p);
+    const int64_t waves = Uc * ((ks + 15) / 16);
+    hipLaunchKernelGGL(k_screen_rescore, dim3((unsigned)((waves + 3) / 4)), dim3(PAIRS_WG), 0, s, sa.a, (const int32_t *)sl_i.p, ks, ks - 1, ex_v.p);
+    hipLaunchKernelGGL(k_screen_finish, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, (const double *)sl_v.p, (const int32_t *)sl_i.p,
+                       (const double *)ex_v.p, ks, k, Uc, sb, out_v.p, out_i.p, d_cert.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    h_idx.resize((size_t)(Uc * k));
+    MFM_HIP_CHECK(hipMemcpyAsync(score + (size_t)u0 * k, out_v.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), out_i.p, (size_t)(Uc * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipMemcpyAsync(sc.certified + u0, d_cert.p, (size_t)Uc, hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipStreamSynchronize(s));
+    for (int64_t e = 0; e < Uc * k; e++) idx[u0 * k + e] = h_idx[(size_t)e];
+  }
+  MFM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
 // The whole call over the samples of `v` (mfm_samples.hpp). dense != nullptr: (U, I) scores; else the top k. mo != nullptr: the
 // moments form. rk != nullptr: the rank form (neither dense nor k). ps != nullptr: the per-sample selecting form (k, its own outputs).
 // sim >= 0: the similarity forms under that metric (PAIRS_SIM_*; with mo, mode 0): the embeddings carry the normalisation in the
 // bias slot and no bias is summed; everything else -- the memory rule, the chunks, the stripes, the merge -- is the moments call's.
 void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx, double *score, double *dense,
-               const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr, int sim = -1) {
+               const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr, int sim = -1,
+               const PairsScreen *sc = nullptr) {
   const int S = v.count(), rank = v.K;
   if (v.device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
   if (v.D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
@@ -462,7 +645,7 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
   const int64_t Ipad = round_up(std::max<int64_t>(I, 1), PAIRS_COL_ALIGN);
 
   // ---- the memory rule: Q and every block table resident, the query scratch bounded
-  const double q_bytes = ((double)Ipad * S * KS + (double)Ipad * (S + 1)) * sizeof(double);
+  const double q_bytes = ((double)Ipad * S * KS + (double)Ipad * (S + 1)) * sizeof(double) + (sc ? screen_q_bytes(Ipad, NK) : 0.0);
   double t_bytes[2] = {0.0, 0.0};
   for (int side = 0; side < 2; side++)
     for (auto &b : p->blocks[side]) t_bytes[side] += (double)b->M * S * (KS + 2) * sizeof(double);
@@ -611,6 +794,10 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     walk_samples(p, form, call, mode, *ps, embed);
     return;
   }
+  if (sc) {
+    run_screened(p, call, *sc, k, idx, score, dense, embed);
+    return;
+  }
 
   // ---- queries, chunk by chunk
   DevBuf<double> Pf, Ab, Asum, list_v, out_v, d_dense, d_dense_std, out_m, out_s;
@@ -725,17 +912,18 @@ void refuse_similarity_handle(const mfm_pairs *p) {
 }
 
 void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense,
-                     const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr, int sim = -1) {
+                     const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr, int sim = -1,
+                     const PairsScreen *sc = nullptr) {
   if (sim < 0) refuse_similarity_handle(p);
   if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo, rk, ps, sim);
+  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo, rk, ps, sim, sc);
 }
 
 void run_pairs_host(mfm_pairs *p, int rank, int n_samples, const double *w0s, const double *ws, const double *Vs, int mode, int k,
                     int64_t *idx, double *score, double *dense, const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr,
-                    const PairsPerSample *ps = nullptr, int sim = -1) {
+                    const PairsPerSample *ps = nullptr, int sim = -1, const PairsScreen *sc = nullptr) {
   if (sim < 0) refuse_similarity_handle(p);
-  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo, rk, ps, sim);
+  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo, rk, ps, sim, sc);
 }
 
 static_assert(PAIRS_SIM_COSINE == MFM_PAIRS_SIM_COSINE && PAIRS_SIM_DOT == MFM_PAIRS_SIM_DOT, "the metrics as the header numbers them");
@@ -776,6 +964,24 @@ PairsRank checked_rank(const mfm_pairs *p, int64_t *rank_out, double *value_out)
   rk.rank = rank_out;
   rk.value = value_out;
   return rk;
+}
+
+// the checks of the screened calls that need neither samples nor a device
+PairsScreen checked_screened(int k, const int64_t *idx, const double *value, uint8_t *certified) {
+  if (!idx || !value || !certified) throw Error(MFM_ERR_INVALID, "no output array");
+  if (k < 1 || k > SCREEN_MAX_K) throw Error(MFM_ERR_INVALID, "k must be in [1, 128]");
+  PairsScreen sc;
+  sc.certified = certified;
+  return sc;
+}
+
+PairsScreen checked_screen_dense(const mfm_pairs *p, const double *r, double *bound) {
+  if (!r || !bound) throw Error(MFM_ERR_INVALID, "no output array");
+  if ((double)p->U * (double)p->I > 16777216.0)
+    throw Error(MFM_ERR_INVALID, "the dense screening call returns every pair: more than 2^24 pairs are refused, use mfm_pairs_topk_screened");
+  PairsScreen sc;
+  sc.bound = bound;
+  return sc;
 }
 
 // the checks of the ranked moments calls that need neither samples nor a device
@@ -998,6 +1204,37 @@ int mfm_pairs_topk(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *
   PAIRS_TRY(p)
   if (!idx || !score) throw Error(MFM_ERR_INVALID, "no output array");
   run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, idx, score, nullptr);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_screened_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t k, int64_t *idx, double *value,
+                                  uint8_t *certified) {
+  PAIRS_TRY(p)
+  const PairsScreen sc = checked_screened(k, idx, value, certified);
+  run_pairs_store(p, st, first, count, 0, k, idx, value, nullptr, nullptr, nullptr, nullptr, -1, &sc);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_topk_screened(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t k,
+                            int64_t *idx, double *value, uint8_t *certified) {
+  PAIRS_TRY(p)
+  const PairsScreen sc = checked_screened(k, idx, value, certified);
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, 0, k, idx, value, nullptr, nullptr, nullptr, nullptr, -1, &sc);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_screen_scores_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, double *r, double *bound) {
+  PAIRS_TRY(p)
+  const PairsScreen sc = checked_screen_dense(p, r, bound);
+  run_pairs_store(p, st, first, count, 0, 0, nullptr, nullptr, r, nullptr, nullptr, nullptr, -1, &sc);
+  PAIRS_CATCH(p)
+}
+
+int mfm_pairs_screen_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, double *r,
+                            double *bound) {
+  PAIRS_TRY(p)
+  const PairsScreen sc = checked_screen_dense(p, r, bound);
+  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, 0, 0, nullptr, nullptr, r, nullptr, nullptr, nullptr, -1, &sc);
   PAIRS_CATCH(p)
 }
 

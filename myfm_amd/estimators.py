@@ -828,6 +828,30 @@ class _PairScoringMixin:
         return TargetRanks(rank, value, n_candidates)
 
 
+class _ScreenedRankingMixin:
+    """predict_topk by a cheaper route, for the estimators whose ranked value is linear in the score -- the regressors:
+    a bf16 matrix contraction leaves a shortlist per query, the shortlist is rescored in fp64 exactly as predict_topk scores it, and
+    a per-row certificate (a bound on the bf16 path's error) says whether a candidate left out could belong to the list. Rows
+    without a certificate go through predict_topk itself, so the result is predict_topk's bit for bit, whatever the data."""
+
+    def predict_topk_screened(self, X_query, X_cand, k: int, exclude=None, X_rel_query=[], X_rel_cand=[]):
+        """ScreenedRanking(indices int64 (U, k), value float64 (U, k), certified bool (U,)): indices and value equal predict_topk's,
+        tails included; certified[u] says that row u was answered by the screened path and not by the fallback. Arguments as
+        predict_topk, but 1 <= k <= 128, else ValueError."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        k, _, exclude = _ranked_args(Xq, Xc, k, exclude)
+        if not 1 <= k <= 128:
+            raise ValueError("k must be an integer in [1, 128]")
+        idx, value, certified = predictor.predict_topk_screened(Xq, Xc, k, exclude, rq, rc)
+        rows = np.flatnonzero(~certified)
+        if rows.size:
+            sub = lambda r: None if r is None else RelationBlock(np.asarray(r.original_to_block_array)[rows], r.data)
+            idx[rows], value[rows] = predictor.predict_topk(Xq[rows], Xc, k, None if exclude is None else exclude[rows],
+                                                            [sub(r) for r in rq], rc)
+        return ScreenedRanking(idx, value, certified)
+
+
+ScreenedRanking = namedtuple("ScreenedRanking", ["indices", "value", "certified"])
 _RANK_TARGETS_PER_CALL = 64  # (PAIRS_RANK_MAX_T of the device code)
 TargetRanks = namedtuple("TargetRanks", ["rank", "value", "n_candidates"])
 PairSummary = namedtuple("PairSummary", ["mean", "std"])
@@ -1150,7 +1174,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _ScreenedRankingMixin, _PairUncertaintyMixin, _SimilarityMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -1533,7 +1557,7 @@ class MyFMVariationalBase(_FMEstimatorBase):
         return self
 
 
-class VariationalFMRegressor(_PairScoringMixin, _VariationalMomentsMixin, MyFMVariationalBase):
+class VariationalFMRegressor(_PairScoringMixin, _ScreenedRankingMixin, _VariationalMomentsMixin, MyFMVariationalBase):
     """Bayesian FM regression by mean-field variational inference (variational.py:170-265)."""
 
     # the task hooks of the regression estimators (the two families are siblings, as in the reference)
