@@ -25,7 +25,7 @@
 // mfm_pairs_topk_sim*; k_pairs_tile_sim of mfm_pairs_sim.hpp, DESIGN 4.13.4: the moments forms' walk over embeddings whose bias slot
 // holds the rows' normalisation; the one family that a similarity handle, mfm_pairs_create_sim, serves).
 // The variational forms (mfm_pairs_moments_vb, mfm_pairs_topk_bound_vb; mfm_pairs_vb.hpp) score a mean-field Gaussian
-// posterior instead of samples: run_pairs_vb at the end of this file, with the memory rule, the chunks and the stripes above.
+// posterior instead of samples: score_vb below, which hands its embedding to the query walk of the sample forms (walk_queries).
 // The screened top-k (mfm_pairs_topk_screened*, mfm_pairs_screen_scores*; mfm_pairs_screen.hpp): mode 0's list through a
 // bf16 contraction, an exact rescoring of its shortlist and a per-row certificate (run_screened below); a bf16 copy of Q is resident
 // next to Q and counts in the memory rule.
@@ -115,6 +115,132 @@ void ensure(DevBuf<T> &b, size_t n) {
   if (b.n < std::max<size_t>(n, 1)) b.alloc(std::max<size_t>(n, 1));
 }
 
+// ---- what a call asks for ---------------------------------------------------------------------------------------------------------
+// The forms of the C ABI, the variational calls included (the moments and the ranked moments of mfm_pairs_vb.hpp).
+enum PairsAsk {
+  ASK_SCORES,        // (U, I) values
+  ASK_TOPK,          // the k best per query row
+  ASK_MOMENTS,       // (U, I) mean and std over the samples
+  ASK_UCB,           // the k best by mean + beta * std, with mean and std
+  ASK_RANK,          // value and rank of every stored target
+  ASK_SAMPLES,       // the k best under each sample, or under each row's own
+  ASK_VOTE,          // the n_top candidates most often in the samples' lists
+  ASK_SCREENED,      // mode 0's k best through the bf16 screen, certified per row
+  ASK_SCREEN_DENSE,  // (U, I) screened values and the per-row bound
+  ASK_SIM,           // (U, I) mean and std of the similarity
+  ASK_TOPK_SIM       // the k most similar by mean + beta * std
+};
+
+// One request: the form, its parameters and its outputs by name. The checked_* functions below build it, with the checks that need
+// neither samples nor a device; a field that the form does not use keeps its default.
+struct PairsRequest {
+  PairsAsk ask;
+  int mode = 0;     // the prediction mode; the similarity and the screened forms score under 0
+  int metric = -1;  // PAIRS_SIM_*, the similarity forms alone
+  int k = 0;
+  double beta = 0.0;                    // the ranked moments forms rank by mean + beta * std
+  const int32_t *row_sample = nullptr;  // ASK_SAMPLES, [U]: only the list of row u's own sample, outputs [U][k]; null: every sample's, [S][U][k]
+  int n_top = 0;                        // ASK_VOTE: idx / value are [U][n_top] indices / probabilities
+  // the outputs
+  double *dense = nullptr;                      // (U, I): the value, the moments forms' mean, the screen's r~
+  int64_t *idx = nullptr;                       // the lists: (U, k), or as the per-sample forms lay them out
+  double *value = nullptr;
+  double *mean = nullptr;                       // (U, k): the moments of the listed pairs
+  double *sd = nullptr;                         // (U, k), or (U, I) next to `dense`
+  int64_t *target_rank = nullptr;               // ASK_RANK: one entry per stored target in CSR order
+  double *target_value = nullptr;
+  uint8_t *certified = nullptr;                 // ASK_SCREENED, [U]
+  double *bound = nullptr;                      // ASK_SCREEN_DENSE, [U]: E_u
+
+  bool dense_form() const { return ask == ASK_SCORES || ask == ASK_MOMENTS || ask == ASK_SCREEN_DENSE || ask == ASK_SIM; }
+  bool spread() const { return ask == ASK_MOMENTS || ask == ASK_UCB || sim(); }
+  bool sim() const { return ask == ASK_SIM || ask == ASK_TOPK_SIM; }
+  bool per_sample() const { return ask == ASK_SAMPLES || ask == ASK_VOTE; }
+  bool screened() const { return ask == ASK_SCREENED || ask == ASK_SCREEN_DENSE; }
+};
+
+// ---- the steps every driver shares ------------------------------------------------------------------------------------------------
+// the sizes every formula of a call reads: S samples (or pseudo-samples) of K factors, padded to KS = 4 KS4
+struct PairsDims {
+  int S, K, KS, KS4;
+  int64_t NK, Ipad, W;
+};
+
+PairsDims pairs_dims(const mfm_pairs *p, int S, int K) {
+  const int KS = (K + 3) & ~3;
+  return {S, K, KS, KS / 4, (int64_t)S * (KS / 4), round_up(std::max<int64_t>(p->I, 1), PAIRS_COL_ALIGN), (p->I + 31) / 32};
+}
+
+// the resident part of a call against MFM_STORE_MAX_FRACTION (default 0.5) of the free device memory
+bool exceeds_store_fraction(double bytes) {
+  size_t free_b = 0, total_b = 0;
+  const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
+  return hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > frac * (double)free_b;
+}
+
+// query rows per chunk: what `bound` bytes hold at `per_row` bytes a row, in whole 64-row tiles and never less than one
+int64_t chunk_rows(int64_t bound, double per_row, int64_t U) {
+  int64_t chunk = (int64_t)std::min<double>((double)bound / per_row, 1e12);
+  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
+  return std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
+}
+
+// steps of `step` candidates that a workgroup takes over the whole candidate side
+int64_t candidate_steps(int64_t I, int step) { return (std::max<int64_t>(I, 1) + step - 1) / step; }
+
+// stripes of the candidate walk for a launch of n_tiles row tiles (or plan entries): enough workgroups to fill the device twice, at
+// most PAIRS_MAX_STRIPES lists to merge, no empty stripe
+struct Stripes {
+  int64_t n, steps;
+};
+
+Stripes split_stripes(int64_t n_tiles, int64_t steps_total) {
+  const int64_t n = std::max<int64_t>(1, std::min<int64_t>({(512 + n_tiles - 1) / n_tiles, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
+  const int64_t steps = (steps_total + n - 1) / n;
+  return {(steps_total + steps - 1) / steps, steps};
+}
+
+// the exclusion bitmask [Uc][W] of the chunk's rows, built in `mask`; null when the chunk excludes nothing
+const uint32_t *chunk_mask(mfm_pairs *p, DevBuf<uint32_t> &mask, int64_t u0, int64_t Uc, int64_t W) {
+  if (!p->has_exclude || !(p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0])) return nullptr;
+  ensure(mask, (size_t)(Uc * W));
+  MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), p->stream));
+  hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, p->stream, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
+  return mask.p;
+}
+
+// a chunk's rows of P and their biases (Asum stays empty where the form sums none)
+struct QueryRows {
+  DevBuf<double> Pf, Ab, Asum;
+};
+
+// a chunk's PairsArgs from the call's: its rows, its share of the grid, its mask; the form's own outputs are the driver's to add
+PairsArgs chunk_args(const PairsArgs &call, const QueryRows &q, int64_t u0, int64_t Uc, int64_t Upad, int64_t stripe_len, const uint32_t *mask) {
+  PairsArgs a = call;
+  a.Pf = q.Pf.p;
+  a.Ab = q.Ab.p;
+  a.Asum = q.Asum.p;
+  a.Upad = Upad;
+  a.Uc = Uc;
+  a.stripe_len = stripe_len;
+  a.mask = mask;
+  a.list_rows = Upad;
+  a.u0 = u0;
+  return a;
+}
+
+// A finished (rows, k) list off the device to row `row0` of the caller's arrays: the values straight, the indices through h_idx and
+// widened from int32 to int64. Synchronises the stream: whatever else the chunk has queued has arrived too, and the chunk's device and
+// host buffers may be reused.
+void download_list(hipStream_t s, std::vector<int32_t> &h_idx, const double *d_value, const int32_t *d_idx, int64_t rows, int64_t k, int64_t row0,
+                   double *value, int64_t *idx) {
+  h_idx.resize((size_t)(rows * k));
+  MFM_HIP_CHECK(hipMemcpyAsync(value + (size_t)(row0 * k), d_value, (size_t)(rows * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+  MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), d_idx, (size_t)(rows * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  MFM_HIP_CHECK(hipStreamSynchronize(s));
+  for (int64_t e = 0; e < rows * k; e++) idx[row0 * k + e] = h_idx[(size_t)e];
+}
+
 // ---- the forms of the tile kernel ---------------------------------------------------------------------------------------------
 // launches a tile kernel with its dynamic LDS, the limit raised once per device where the form needs more than the default
 template <auto KERNEL>
@@ -192,20 +318,22 @@ PairsForm pairs_sim_form_of() {
 // form has the one shape its target lists are laid out for. The per-sample selecting forms hold one sample's value next to the
 // accumulators, as the mean forms' modes 1 and 2 do, and take their shapes. The similarity forms are moments forms with another
 // finish and take the moments forms' shapes.
-PairsForm pairs_form(bool targets, bool spread, bool dense, int k, bool per_sample = false, bool sim = false) {
-  if (sim) {
+PairsForm pairs_form(const PairsRequest &rq) {
+  const bool dense = rq.dense_form();
+  const int k = rq.k;
+  if (rq.sim()) {
     if (dense) return pairs_sim_form_of<2, 2, PAIRS_DENSE>();
     if (k <= 64) return pairs_sim_form_of<4, 1, PAIRS_SELECT>();
     if (k <= 128) return pairs_sim_form_of<2, 2, PAIRS_SELECT>();
     return pairs_sim_form_of<1, 4, PAIRS_SELECT>();
   }
-  if (targets) return pairs_form_of<4, 2, false, PAIRS_TARGETS>();
-  if (per_sample) {
+  if (rq.ask == ASK_RANK) return pairs_form_of<4, 2, false, PAIRS_TARGETS>();
+  if (rq.per_sample()) {
     if (k <= 64) return pairs_form_of<4, 2, false, PAIRS_SELECT_SAMPLE>();
     if (k <= 128) return pairs_form_of<2, 4, false, PAIRS_SELECT_SAMPLE>();
     return pairs_form_of<1, 8, false, PAIRS_SELECT_SAMPLE>();
   }
-  if (!spread) {
+  if (!rq.spread()) {
     if (dense) return pairs_form_of<4, 2, false, PAIRS_DENSE>();
     if (k <= 64) return pairs_form_of<4, 2, false, PAIRS_SELECT>();
     if (k <= 128) return pairs_form_of<2, 4, false, PAIRS_SELECT>();
@@ -229,19 +357,6 @@ void launch_moments_at(hipStream_t s, const PairsArgs &a, int mode, bool sim, co
     hipLaunchKernelGGL(k_pairs_moments_at<2>, grid, dim3(PAIRS_WG), 0, s, a, out_i, n, mean, sd);
 }
 
-// what a moments call adds to a mean call: rank by mean + beta * std, and return mean and std ((U, I) each with `dense`, which
-// then holds the mean; (U, k) each with the top k)
-struct PairsMoments {
-  double beta = 0.0;
-  double *mean = nullptr, *sd = nullptr;
-};
-
-// the outputs of a rank call, one entry per stored target in CSR order
-struct PairsRank {
-  int64_t *rank = nullptr;
-  double *value = nullptr;
-};
-
 // a target that is also excluded has no rank: refused when the second of the two patterns arrives
 void check_targets_not_excluded(const mfm_pairs *p) {
   if (!p->has_targets || !p->has_exclude) return;
@@ -256,26 +371,18 @@ void check_targets_not_excluded(const mfm_pairs *p) {
 }
 
 // ---- the per-sample selecting form (mfm_pairs_samples.hpp) --------------------------------------------------------
-// what a per-sample call asks for
-struct PairsPerSample {
-  const int32_t *row_sample = nullptr;  // [U]: only the list of row u's own sample, outputs [U][k]; null: every sample's, [S][U][k]
-  int n_top = 0;                        // > 0: the vote over every sample's list; idx / value are [U][n_top] indices / probabilities
-  int64_t *idx = nullptr;
-  double *value = nullptr;
-};
-
 static_assert(PAIRS_VOTE_MAX == MFM_PAIRS_VOTE_MAX && PAIRS_VOTE_MAX >= 95 * PAIRS_MAX_K, "the vote's limit as the header states it");
 
 // the checks that need the sample count (before any launch)
-void check_per_sample(const PairsPerSample &ps, int S, int k, int64_t U) {
-  if (ps.row_sample)
+void check_per_sample(const PairsRequest &rq, int S, int64_t U) {
+  if (rq.row_sample)
     for (int64_t u = 0; u < U; u++)
-      if (ps.row_sample[u] < 0 || ps.row_sample[u] >= S)
-        throw Error(MFM_ERR_INVALID, "row_sample: query row " + std::to_string(u) + " asks for sample " + std::to_string(ps.row_sample[u]) +
+      if (rq.row_sample[u] < 0 || rq.row_sample[u] >= S)
+        throw Error(MFM_ERR_INVALID, "row_sample: query row " + std::to_string(u) + " asks for sample " + std::to_string(rq.row_sample[u]) +
                                          ", the call has " + std::to_string(S));
-  if (ps.n_top > 0 && (int64_t)S * k > PAIRS_VOTE_MAX)
+  if (rq.ask == ASK_VOTE && (int64_t)S * rq.k > PAIRS_VOTE_MAX)
     throw Error(MFM_ERR_INVALID, "the vote takes at most " + std::to_string(PAIRS_VOTE_MAX) + " list entries per query row (samples * k), the call has " +
-                                     std::to_string((int64_t)S * k));
+                                     std::to_string((int64_t)S * rq.k));
 }
 
 // The queries in chunks, each chunk's plan in slices (the candidate side is resident: `call`).
@@ -286,21 +393,20 @@ void check_per_sample(const PairsPerSample &ps, int S, int k, int64_t U) {
 // under the selection's total order and lands at a place that its (sample, row) alone decides, so neither the bound nor the
 // stripes nor the slices change a bit of the results.
 template <class Embed>
-void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, int mode, const PairsPerSample &ps, Embed embed) {
+void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, const PairsRequest &rq, Embed embed) {
   hipStream_t s = p->stream;
-  const int S = call.S, k = call.k, KS = call.KS4 * 4, rows = form.rows();
+  const int S = call.S, k = call.k, KS = call.KS4 * 4, rows = form.rows(), n_top = rq.n_top;
   const int64_t U = p->U, I = call.I, W = call.W;
-  const bool own = ps.row_sample != nullptr, vote = ps.n_top > 0, masked = p->has_exclude;
+  const bool own = rq.row_sample != nullptr, vote = rq.ask == ASK_VOTE, masked = p->has_exclude;
   const double per_row = (own ? (double)KS * 8 + 16 : (double)S * KS * 8 + (double)S * 8) + (masked ? (double)W * 4 : 0.0) +
-                         (vote ? (double)S * k * 4 + (double)ps.n_top * 12 : 0.0);
-  int64_t chunk = (int64_t)std::min<double>((double)(p->scratch_bound / 2) / per_row, 1e12);
-  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
-  chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
-  const int64_t steps_total = (std::max<int64_t>(I, 1) + form.step() - 1) / form.step();
+                         (vote ? (double)S * k * 4 + (double)n_top * 12 : 0.0);
+  const int64_t chunk = chunk_rows(p->scratch_bound / 2, per_row, U);
+  const int64_t steps_total = candidate_steps(I, form.step());
   int n_sort = 2;  // the vote's sort length: the power of two at or above S * k
   while (vote && n_sort < S * k) n_sort <<= 1;
 
-  DevBuf<double> Pf, Ab, list_v, out_v, res_p;
+  QueryRows q;
+  DevBuf<double> list_v, out_v, res_p;
   DevBuf<int32_t> list_i, out_i, votes, res_i, d_row_of, d_map_s;
   DevBuf<uint32_t> mask;
   DevBuf<PairsPlanEntry> d_plan;
@@ -316,7 +422,7 @@ void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, in
     if (own) {
       // the rows grouped by their sample, a group's rows in row order, every non-empty group padded to whole tiles
       std::fill(fill.begin(), fill.end(), 0);
-      for (int64_t u = 0; u < Uc; u++) fill[(size_t)ps.row_sample[u0 + u]]++;
+      for (int64_t u = 0; u < Uc; u++) fill[(size_t)rq.row_sample[u0 + u]]++;
       Ppad = 0;
       for (int g = 0; g < S; g++) {
         const int64_t n_g = fill[(size_t)g];
@@ -326,7 +432,7 @@ void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, in
       }
       row_of.assign((size_t)Ppad, -1);
       map_s.assign((size_t)Ppad, 0);
-      for (int64_t u = 0; u < Uc; u++) row_of[(size_t)fill[(size_t)ps.row_sample[u0 + u]]++] = (int32_t)u;
+      for (int64_t u = 0; u < Uc; u++) row_of[(size_t)fill[(size_t)rq.row_sample[u0 + u]]++] = (int32_t)u;
       for (const PairsPlanEntry &e : plan)
         for (int r = 0; r < rows; r++) map_s[(size_t)e.row0 + r] = e.s;
     } else {
@@ -335,13 +441,11 @@ void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, in
     }
     const int64_t n_e = (int64_t)plan.size();
     if (n_e == 0) continue;
-    // stripes: enough workgroups to fill the device twice, at most PAIRS_MAX_STRIPES lists to merge
-    int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_e - 1) / n_e, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
-    const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
-    n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
+    const Stripes stripes = split_stripes(n_e, steps_total);
+    const int64_t n_stripes = stripes.n;
     // slices: what the chunk's own scratch leaves of the bound, in entries
     const double fixed = (own ? (double)Ppad * (KS * 8 + 16) : (double)Upad * S * (KS + 1) * 8) + (masked ? (double)Uc * W * 4 : 0.0) +
-                         (vote ? (double)Uc * ((double)S * k * 4 + (double)ps.n_top * 12) : 0.0);
+                         (vote ? (double)Uc * ((double)S * k * 4 + (double)n_top * 12) : 0.0);
     const double per_entry = (double)(n_stripes + 1) * rows * k * 12 + sizeof(PairsPlanEntry);
     const int64_t slice = std::max<int64_t>(1, (int64_t)std::min<double>(((double)p->scratch_bound - fixed) / per_entry, (double)n_e));
     for (int64_t e = 0; e < n_e; e++) plan[(size_t)e].out = (e % slice) * rows;
@@ -351,25 +455,12 @@ void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, in
       d_map_s.upload(map_s);
     }
     // ---- P, the mask
-    ensure(Pf, (size_t)(Ppad * (own ? (int64_t)KS : (int64_t)S * KS)));
-    ensure(Ab, (size_t)(own ? Ppad : Upad * S));
-    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Ppad, Pf.p, Ab.p, own ? d_row_of.p : nullptr, own ? d_map_s.p : nullptr);
+    ensure(q.Pf, (size_t)(Ppad * (own ? (int64_t)KS : (int64_t)S * KS)));
+    ensure(q.Ab, (size_t)(own ? Ppad : Upad * S));
+    embed(0, u0, Uc, Ppad, q.Pf.p, q.Ab.p, own ? d_row_of.p : nullptr, own ? d_map_s.p : nullptr);
     MFM_HIP_CHECK(hipGetLastError());
-    const bool use_mask = masked && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
-    if (use_mask) {
-      ensure(mask, (size_t)(Uc * W));
-      MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
-    }
-    PairsArgs a = call;
-    a.Pf = Pf.p;
+    PairsArgs a = chunk_args(call, q, u0, Uc, Upad, stripes.steps * form.step(), chunk_mask(p, mask, u0, Uc, W));
     a.p_stride = own ? (int64_t)call.KS4 : call.NK;
-    a.Ab = Ab.p;
-    a.Upad = Upad;
-    a.Uc = Uc;
-    a.stripe_len = stripe_steps * form.step();
-    a.mask = use_mask ? mask.p : nullptr;
-    a.u0 = u0;
     a.row_of = own ? d_row_of.p : nullptr;
     a.list_rows = slice * rows;
     ensure(list_v, (size_t)(n_stripes * slice * rows * k));
@@ -383,7 +474,7 @@ void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, in
       const int64_t E = std::min(slice, n_e - e0), L = E * rows;
       a.plan = d_plan.p + e0;
       if (I > 0) {
-        form.launch(s, dim3((unsigned)E, (unsigned)n_stripes), a, mode);
+        form.launch(s, dim3((unsigned)E, (unsigned)n_stripes), a, rq.mode);
         MFM_HIP_CHECK(hipGetLastError());
       }
       hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)L), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, a.list_rows, k,
@@ -406,40 +497,30 @@ void walk_samples(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, in
           const int64_t row = own ? (int64_t)row_of[(size_t)pe.row0 + r] : pe.row0 + r;
           const size_t o = (size_t)((own ? (int64_t)0 : (int64_t)pe.s * U) + u0 + row) * k, l = (size_t)(pe.out + r) * k;
           for (int j = 0; j < k; j++) {
-            ps.idx[o + j] = h_idx[l + j];
-            ps.value[o + j] = h_val[l + j];
+            rq.idx[o + j] = h_idx[l + j];
+            rq.value[o + j] = h_val[l + j];
           }
         }
       }
     }
     if (vote) {
-      ensure(res_i, (size_t)(Uc * ps.n_top));
-      ensure(res_p, (size_t)(Uc * ps.n_top));
+      ensure(res_i, (size_t)(Uc * n_top));
+      ensure(res_p, (size_t)(Uc * n_top));
       const size_t lds = (size_t)n_sort * sizeof(int);
       static DeviceOnce raised;
       if (lds > 48 * 1024 && raised.need()) {
         MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_pairs_vote, hipFuncAttributeMaxDynamicSharedMemorySize, PAIRS_VOTE_MAX * (int)sizeof(int)));
         raised.mark();
       }
-      hipLaunchKernelGGL(k_pairs_vote, dim3((unsigned)Uc), dim3(PAIRS_WG), lds, s, votes.p, S * k, n_sort, S, ps.n_top, res_i.p, res_p.p);
+      hipLaunchKernelGGL(k_pairs_vote, dim3((unsigned)Uc), dim3(PAIRS_WG), lds, s, votes.p, S * k, n_sort, S, n_top, res_i.p, res_p.p);
       MFM_HIP_CHECK(hipGetLastError());
-      h_idx.resize((size_t)(Uc * ps.n_top));
-      MFM_HIP_CHECK(hipMemcpyAsync(ps.value + (size_t)u0 * ps.n_top, res_p.p, (size_t)(Uc * ps.n_top) * sizeof(double), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), res_i.p, (size_t)(Uc * ps.n_top) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipStreamSynchronize(s));
-      for (int64_t e = 0; e < Uc * ps.n_top; e++) ps.idx[u0 * ps.n_top + e] = h_idx[(size_t)e];
+      download_list(s, h_idx, res_p.p, res_i.p, Uc, n_top, u0, rq.value, rq.idx);
     }
     MFM_HIP_CHECK(hipStreamSynchronize(s));
   }
 }
 
 // ---- the screened top-k (mfm_pairs_screen.hpp) -------------------------------------------------------------------
-// what a screened call adds: the per-row certificate, or -- the dense diagnostic -- the per-row bound next to r~
-struct PairsScreen {
-  uint8_t *certified = nullptr;  // [U]
-  double *bound = nullptr;       // [U]: E_u (dense)
-};
-
 // the bf16 copy of Q, its norms and flags: what a screened call keeps resident beyond a plain one
 double screen_q_bytes(int64_t Ipad, int64_t NK) {
   const int64_t Ipb = round_up(Ipad, SCREEN_COL_ALIGN), NC = round_up(NK * 4, SCREEN_INNER) / SCREEN_INNER;
@@ -483,10 +564,10 @@ ScreenForm screen_form(bool dense, int ks) {
 // Scratch per query row: run_pairs' mean-form terms with k_s for k, plus the bf16 P, the norm and flag, the exact values and the
 // outputs. The rows that come back uncertified are the caller's to send through mfm_pairs_topk.
 template <class Embed>
-void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsScreen &sc, int k, int64_t *idx, double *score, double *dense, Embed embed) {
+void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsRequest &rq, Embed embed) {
   hipStream_t s = p->stream;
-  const bool is_dense = dense != nullptr;
-  const int S = call.S, KS = call.KS4 * 4, ks = is_dense ? 0 : std::min(256, std::max(64, 2 * k));
+  const bool is_dense = rq.dense_form();
+  const int k = rq.k, S = call.S, KS = call.KS4 * 4, ks = is_dense ? 0 : std::min(256, std::max(64, 2 * k));
   const int64_t U = p->U, I = call.I, W = call.W, NK = call.NK, Ipad = call.Ipad, L = NK * 4;
   const int64_t Lp = round_up(L, SCREEN_INNER), Ipb = round_up(Ipad, SCREEN_COL_ALIGN);
   const int NC = (int)(Lp / SCREEN_INNER);
@@ -494,10 +575,8 @@ void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsScreen &sc, in
   const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (double)Lp * 2 + 12 +
                          (is_dense ? (double)I * 8 + 8
                                    : (p->has_exclude ? (double)W * 4 : 0.0) + (double)(PAIRS_MAX_STRIPES + 2) * ks * 12 + (double)k * 12 + 1);
-  int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
-  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
-  chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
-  const int64_t steps_total = (std::max<int64_t>(I, 1) + form.step() - 1) / form.step();
+  const int64_t chunk = chunk_rows(p->scratch_bound, per_row, U);
+  const int64_t steps_total = candidate_steps(I, form.step());
 
   // ---- candidate side, once: the bf16 copy, the norms, the flags and the two maxima
   DevBuf<screen_u4> Qb, Pb;
@@ -513,47 +592,31 @@ void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsScreen &sc, in
   hipLaunchKernelGGL(k_screen_cand_max, dim3(1), dim3(PAIRS_WG), 0, s, (const double *)qn.p, call.Bsum, I, cmax.p);
   MFM_HIP_CHECK(hipGetLastError());
 
-  DevBuf<double> Pf, Ab, Asum, list_v, sl_v, ex_v, out_v, d_dense, d_E;
+  QueryRows q;
+  DevBuf<double> list_v, sl_v, ex_v, out_v, d_dense, d_E;
   DevBuf<int32_t> list_i, sl_i, out_i;
   DevBuf<uint32_t> mask;
   DevBuf<uint8_t> d_cert;
   std::vector<int32_t> h_idx;
   for (int64_t u0 = 0; u0 < U; u0 += chunk) {
     const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
-    ensure(Pf, (size_t)(Upad * NK * 4));
-    ensure(Ab, (size_t)(Upad * S));
-    ensure(Asum, (size_t)Upad);
+    ensure(q.Pf, (size_t)(Upad * NK * 4));
+    ensure(q.Ab, (size_t)(Upad * S));
+    ensure(q.Asum, (size_t)Upad);
     ensure(Pb, (size_t)(Upad / 16 * NC * 64));
     ensure(pn, (size_t)Upad);
     ensure(pflag, (size_t)Upad);
-    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p, nullptr, nullptr);
-    hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Ab.p, S, Upad, Asum.p);
-    hipLaunchKernelGGL(k_screen_pack, dim3((unsigned)(Upad / 16)), dim3(PAIRS_WG), 0, s, (const double *)Pf.p, NK, Upad / 16, NC,
-                       (const double *)Asum.p, Pb.p, pn.p, pflag.p, (int32_t *)nullptr);
+    embed(0, u0, Uc, Upad, q.Pf.p, q.Ab.p);
+    hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, q.Ab.p, S, Upad, q.Asum.p);
+    hipLaunchKernelGGL(k_screen_pack, dim3((unsigned)(Upad / 16)), dim3(PAIRS_WG), 0, s, (const double *)q.Pf.p, NK, Upad / 16, NC,
+                       (const double *)q.Asum.p, Pb.p, pn.p, pflag.p, (int32_t *)nullptr);
     MFM_HIP_CHECK(hipGetLastError());
-    const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
-    if (use_mask) {
-      ensure(mask, (size_t)(Uc * W));
-      MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
-    }
-    // stripes as run_pairs chooses them, from this form's rows and step
     const int64_t n_qt = Upad / form.rows();
-    int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_qt - 1) / n_qt, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
-    const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
-    n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
+    const Stripes stripes = split_stripes(n_qt, steps_total);
+    const int64_t n_stripes = stripes.n;
     const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
     ScreenArgs sa;
-    sa.a = call;
-    sa.a.Pf = Pf.p;
-    sa.a.Ab = Ab.p;
-    sa.a.Asum = Asum.p;
-    sa.a.Upad = Upad;
-    sa.a.Uc = Uc;
-    sa.a.stripe_len = stripe_steps * form.step();
-    sa.a.mask = use_mask ? mask.p : nullptr;
-    sa.a.list_rows = Upad;
-    sa.a.u0 = u0;
+    sa.a = chunk_args(call, q, u0, Uc, Upad, stripes.steps * form.step(), is_dense ? nullptr : chunk_mask(p, mask, u0, Uc, W));
     sa.a.k = ks;
     sa.Pb = Pb.p;
     sa.Qb = Qb.p;
@@ -563,7 +626,7 @@ void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsScreen &sc, in
     sb.pflag = pflag.p;
     sb.cand_flag = cand_flag.p;
     sb.cmax = cmax.p;
-    sb.Asum = Asum.p;
+    sb.Asum = q.Asum.p;
     sb.w0sum = call.w0sum;
     sb.eps = screen_eps(Lp);
     sb.L = (double)L;
@@ -575,8 +638,8 @@ void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsScreen &sc, in
       form.launch(s, grid, sa);
       hipLaunchKernelGGL(k_screen_bound, dim3((unsigned)((Uc + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, sb, Uc, d_E.p);
       MFM_HIP_CHECK(hipGetLastError());
-      MFM_HIP_CHECK(hipMemcpyAsync(dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipMemcpyAsync(sc.bound + u0, d_E.p, (size_t)Uc * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(rq.dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(rq.bound + u0, d_E.p, (size_t)Uc * sizeof(double), hipMemcpyDeviceToHost, s));
       MFM_HIP_CHECK(hipStreamSynchronize(s));
       continue;
     }
@@ -601,24 +664,158 @@ void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsScreen &sc, in
     hipLaunchKernelGGL(k_screen_finish, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, (const double *)sl_v.p, (const int32_t *)sl_i.p,
                        (const double *)ex_v.p, ks, k, Uc, sb, out_v.p, out_i.p, d_cert.p);
     MFM_HIP_CHECK(hipGetLastError());
-    h_idx.resize((size_t)(Uc * k));
-    MFM_HIP_CHECK(hipMemcpyAsync(score + (size_t)u0 * k, out_v.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), out_i.p, (size_t)(Uc * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipMemcpyAsync(sc.certified + u0, d_cert.p, (size_t)Uc, hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipStreamSynchronize(s));
-    for (int64_t e = 0; e < Uc * k; e++) idx[u0 * k + e] = h_idx[(size_t)e];
+    MFM_HIP_CHECK(hipMemcpyAsync(rq.certified + u0, d_cert.p, (size_t)Uc, hipMemcpyDeviceToHost, s));
+    download_list(s, h_idx, out_v.p, out_i.p, Uc, k, u0, rq.value, rq.idx);
   }
   MFM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// The whole call over the samples of `v` (mfm_samples.hpp). dense != nullptr: (U, I) scores; else the top k. mo != nullptr: the
-// moments form. rk != nullptr: the rank form (neither dense nor k). ps != nullptr: the per-sample selecting form (k, its own outputs).
-// sim >= 0: the similarity forms under that metric (PAIRS_SIM_*; with mo, mode 0): the embeddings carry the normalisation in the
-// bias slot and no bias is summed; everything else -- the memory rule, the chunks, the stripes, the merge -- is the moments call's.
-void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx, double *score, double *dense,
-               const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr, int sim = -1,
-               const PairsScreen *sc = nullptr) {
-  const int S = v.count(), rank = v.K;
+// ---- the query walk that the sample forms and the variational forms share --------------------------------------------------------
+// The queries in chunks against the resident candidate side of `call`. Per chunk: embed P (and sum its biases where the candidate
+// side has sums), then what the form does with a value -- the targets' values and ranks (a chunk without targets launches nothing);
+// or the dense values; or the stripes' lists, their merge, mean and std of the merged pairs where the form has a spread, and the
+// download. What depends on where the model comes from is passed in: `embed` puts a side's rows into P and the biases, `moments_at`
+// computes mean and std of listed pairs; the form carries its launch. Scratch per query row: P and the biases, the exclusion bitmask,
+// the outputs, and for a selecting form the per-stripe lists at the most stripes a launch can have.
+template <class Embed, class MomentsAt>
+void walk_queries(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, const PairsRequest &rq, Embed embed, MomentsAt moments_at) {
+  hipStream_t s = p->stream;
+  const int S = call.S, KS = call.KS4 * 4, k = call.k;
+  const int64_t U = p->U, I = call.I, W = call.W;
+  const bool is_dense = form.out == PAIRS_DENSE, targets = form.out == PAIRS_TARGETS, bias_sums = call.Bsum != nullptr;
+  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && !is_dense ? (double)W * 4 : 0.0) +
+                         (is_dense  ? (double)I * 8
+                          : targets ? (double)PAIRS_RANK_MAX_T * 12  // (the targets' values and ranks)
+                                    : (double)(PAIRS_MAX_STRIPES + 1) * k * 12) +
+                         // (the second dense output / mean and std of the lists)
+                         (!form.spread ? 0.0 : is_dense ? (double)I * 8 : (double)k * 16);
+  const int64_t chunk = chunk_rows(p->scratch_bound, per_row, U);
+  const int64_t steps_total = candidate_steps(I, form.step());
+
+  QueryRows q;
+  DevBuf<double> list_v, out_v, d_dense, d_dense_std, out_m, out_s, t_val;
+  DevBuf<int32_t> list_i, out_i, t_rank;
+  DevBuf<uint32_t> mask;
+  std::vector<int32_t> h_idx;
+  for (int64_t u0 = 0; u0 < U; u0 += chunk) {
+    const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
+    const int64_t tbase = targets ? p->t_ptr_host[u0] : 0, n_t = targets ? p->t_ptr_host[u0 + Uc] - tbase : 0;
+    if (targets && n_t == 0) continue;
+    ensure(q.Pf, (size_t)(Upad * call.NK * 4));
+    ensure(q.Ab, (size_t)(Upad * S));
+    embed(0, u0, Uc, Upad, q.Pf.p, q.Ab.p);
+    if (bias_sums) {
+      ensure(q.Asum, (size_t)Upad);
+      hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, q.Ab.p, S, Upad, q.Asum.p);
+    }
+    MFM_HIP_CHECK(hipGetLastError());
+    const int64_t n_qt = Upad / form.rows();
+    const Stripes stripes = split_stripes(n_qt, steps_total);
+    const int64_t n_stripes = stripes.n;
+    const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
+    PairsArgs a = chunk_args(call, q, u0, Uc, Upad, stripes.steps * form.step(), is_dense ? nullptr : chunk_mask(p, mask, u0, Uc, W));
+    if (targets) {
+      ensure(t_val, (size_t)n_t);
+      ensure(t_rank, (size_t)n_t);
+      a.tptr = p->t_ptr.p;
+      a.tidx = p->t_idx.p;
+      a.tval = t_val.p;
+      a.trank = t_rank.p;
+      a.tbase = tbase;
+      MFM_HIP_CHECK(hipMemsetAsync(t_rank.p, 0, (size_t)n_t * sizeof(int32_t), s));
+      form.launch(s, grid, a, rq.mode);
+      MFM_HIP_CHECK(hipGetLastError());
+      download_list(s, h_idx, t_val.p, t_rank.p, n_t, 1, tbase, rq.target_value, rq.target_rank);
+      continue;
+    }
+    if (is_dense) {
+      ensure(d_dense, (size_t)(Uc * I));
+      a.dense = d_dense.p;
+      if (form.spread) {
+        ensure(d_dense_std, (size_t)(Uc * I));
+        a.dense_std = d_dense_std.p;
+      }
+      form.launch(s, grid, a, rq.mode);
+      MFM_HIP_CHECK(hipGetLastError());
+      if (form.spread)
+        MFM_HIP_CHECK(hipMemcpyAsync(rq.sd + (size_t)u0 * I, d_dense_std.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(rq.dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipStreamSynchronize(s));
+      continue;
+    }
+    ensure(list_v, (size_t)(n_stripes * Upad * k));
+    ensure(list_i, (size_t)(n_stripes * Upad * k));
+    ensure(out_v, (size_t)(Uc * k));
+    ensure(out_i, (size_t)(Uc * k));
+    a.list_v = list_v.p;
+    a.list_i = list_i.p;
+    if (I > 0) {
+      form.launch(s, grid, a, rq.mode);
+      MFM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, k,
+                       out_v.p, out_i.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    if (form.spread) {
+      ensure(out_m, (size_t)(Uc * k));
+      ensure(out_s, (size_t)(Uc * k));
+      moments_at(a, out_i.p, Uc * k, out_m.p, out_s.p);
+      MFM_HIP_CHECK(hipGetLastError());
+      MFM_HIP_CHECK(hipMemcpyAsync(rq.mean + (size_t)u0 * k, out_m.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+      MFM_HIP_CHECK(hipMemcpyAsync(rq.sd + (size_t)u0 * k, out_s.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    download_list(s, h_idx, out_v.p, out_i.p, Uc, k, u0, rq.value, rq.idx);
+  }
+  MFM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// The candidate side, embedded once and resident for the call (Bsum only where the form sums the biases: the similarity finish and
+// the variational forms read the per-sample slots alone, Asum / Bsum stay null), and what every launch of the call reads of it and
+// of the request; the model's own fields are its driver's to add, a chunk adds its own.
+struct Candidates {
+  DevBuf<double> Qf, Bb, Bsum;
+};
+
+template <class Embed>
+PairsArgs embed_candidates(mfm_pairs *p, const PairsDims &d, const PairsRequest &rq, bool bias_sums, Embed embed, Candidates &c) {
+  c.Qf.alloc((size_t)std::max<int64_t>(d.Ipad * d.NK * 4, 1));
+  c.Bb.alloc((size_t)d.Ipad * d.S);
+  if (bias_sums) c.Bsum.alloc((size_t)d.Ipad);
+  embed(1, (int64_t)0, p->I, d.Ipad, c.Qf.p, c.Bb.p);
+  if (bias_sums)
+    hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)(d.Ipad / PAIRS_WG)), dim3(PAIRS_WG), 0, p->stream, c.Bb.p, d.S, d.Ipad, c.Bsum.p);
+  MFM_HIP_CHECK(hipGetLastError());
+  PairsArgs call;
+  call.Qf = c.Qf.p;
+  call.NK = d.NK;
+  call.p_stride = d.NK;
+  call.q_stride = d.NK;
+  call.KS4 = d.KS4;
+  call.S = d.S;
+  call.Bb = c.Bb.p;
+  call.Bsum = c.Bsum.p;
+  call.beta = rq.beta;
+  call.Ipad = d.Ipad;
+  call.I = p->I;
+  call.W = d.W;
+  call.k = rq.k;
+  return call;
+}
+
+// A similarity handle's sides may share columns: the score's split into per-side terms and one contraction is wrong there, so every
+// scoring form is refused on it, before the samples are looked at.
+void refuse_similarity_handle(const mfm_pairs *p) {
+  if (p->similarity)
+    throw Error(MFM_ERR_INVALID, "this is a similarity handle (mfm_pairs_create_sim): its sides may share columns, which the pair score's "
+                                 "decomposition does not allow; it serves mfm_pairs_sim* and mfm_pairs_topk_sim* only");
+}
+
+// ---- the sample forms ------------------------------------------------------------------------------------------------------------
+// The whole call over the samples of `v` (mfm_samples.hpp): the checks that need the samples, the memory rule, the block tables and
+// the candidate side, then the walk the request names. The similarity forms (rq.metric, mode 0) are moments forms whose embeddings
+// carry the normalisation in the bias slot and sum no bias; everything else is the moments call's.
+void run_pairs(mfm_pairs *p, const SampleView &v, const PairsRequest &rq) {
+  const int S = v.count(), mode = rq.mode, k = rq.k, sim = rq.metric;
   if (v.device != p->device) throw Error(MFM_ERR_INVALID, "pair design and sample store live on different devices");
   if (v.D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
   // a store's device-to-device copies (training stream) must be complete: this stream waits for the latest one's event
@@ -631,54 +828,38 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     if (p->cut_S != S)
       throw Error(MFM_ERR_INVALID, "mode 2: cutpoints were set for " + std::to_string(p->cut_S) + " samples, the call has " + std::to_string(S));
   }
-  const bool is_dense = dense != nullptr;
-  if (!is_dense && !rk && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  const bool is_dense = rq.dense_form(), targets = rq.ask == ASK_RANK;
+  if (!is_dense && !targets && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
   // the form of the call, decided here once: the scratch per query row, the stripes, the grid and the launch all read it
-  const PairsForm form = pairs_form(rk != nullptr, mo != nullptr, is_dense, k, ps != nullptr, sim >= 0);
+  const PairsForm form = pairs_form(rq);
   const int64_t U = p->U, I = p->I, D = p->D;
-  if (ps) check_per_sample(*ps, S, k, U);
+  if (rq.per_sample()) check_per_sample(rq, S, U);
   if (U == 0 || (is_dense && I == 0)) return;
-  if (rk && (I == 0 || !p->has_targets)) return;
+  if (targets && (I == 0 || !p->has_targets)) return;
   hipStream_t s = p->stream;
-  const int K = rank, KS = (K + 3) & ~3, KS4 = KS / 4;
-  const int64_t NK = (int64_t)S * KS4;
-  const int64_t Ipad = round_up(std::max<int64_t>(I, 1), PAIRS_COL_ALIGN);
+  const PairsDims d = pairs_dims(p, S, v.K);
+  const int K = d.K, KS = d.KS;
 
   // ---- the memory rule: Q and every block table resident, the query scratch bounded
-  const double q_bytes = ((double)Ipad * S * KS + (double)Ipad * (S + 1)) * sizeof(double) + (sc ? screen_q_bytes(Ipad, NK) : 0.0);
+  const double q_bytes =
+      ((double)d.Ipad * S * KS + (double)d.Ipad * (S + 1)) * sizeof(double) + (rq.screened() ? screen_q_bytes(d.Ipad, d.NK) : 0.0);
   double t_bytes[2] = {0.0, 0.0};
   for (int side = 0; side < 2; side++)
     for (auto &b : p->blocks[side]) t_bytes[side] += (double)b->M * S * (KS + 2) * sizeof(double);
-  {
-    size_t free_b = 0, total_b = 0;
-    const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
-    const double all_bytes = q_bytes + t_bytes[0] + t_bytes[1];
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && all_bytes > frac * (double)free_b) {
-      if (t_bytes[0] + t_bytes[1] == 0.0)
-        throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + std::to_string((int64_t)(q_bytes / 1048576.0)) +
-                                         " MB for all samples) exceeds MFM_STORE_MAX_FRACTION of the free device memory; "
-                                         "score fewer samples or fewer candidates per call");
-      const auto mb = [](double b) { return std::to_string((int64_t)(b / 1048576.0)) + " MB"; };
-      const char *large = q_bytes >= t_bytes[0] && q_bytes >= t_bytes[1] ? "the candidate side's embedding"
-                          : t_bytes[0] >= t_bytes[1]                     ? "the query side's block tables"
-                                                                         : "the candidate side's block tables";
-      throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + mb(q_bytes) + "), the query side's block tables (" +
-                                       mb(t_bytes[0]) + ") and the candidate side's block tables (" + mb(t_bytes[1]) +
-                                       ") for all samples together exceed MFM_STORE_MAX_FRACTION of the free device memory; the largest part is " +
-                                       large + ": score fewer samples, fewer candidates or smaller blocks per call");
-    }
+  if (exceeds_store_fraction(q_bytes + t_bytes[0] + t_bytes[1])) {
+    if (t_bytes[0] + t_bytes[1] == 0.0)
+      throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + std::to_string((int64_t)(q_bytes / 1048576.0)) +
+                                       " MB for all samples) exceeds MFM_STORE_MAX_FRACTION of the free device memory; "
+                                       "score fewer samples or fewer candidates per call");
+    const auto mb = [](double b) { return std::to_string((int64_t)(b / 1048576.0)) + " MB"; };
+    const char *large = q_bytes >= t_bytes[0] && q_bytes >= t_bytes[1] ? "the candidate side's embedding"
+                        : t_bytes[0] >= t_bytes[1]                     ? "the query side's block tables"
+                                                                       : "the candidate side's block tables";
+    throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + mb(q_bytes) + "), the query side's block tables (" +
+                                     mb(t_bytes[0]) + ") and the candidate side's block tables (" + mb(t_bytes[1]) +
+                                     ") for all samples together exceed MFM_STORE_MAX_FRACTION of the free device memory; the largest part is " +
+                                     large + ": score fewer samples, fewer candidates or smaller blocks per call");
   }
-  const int64_t W = (I + 31) / 32;
-  const int64_t steps_total = (std::max<int64_t>(I, 1) + form.step() - 1) / form.step();
-  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && form.out != PAIRS_DENSE ? (double)W * 4 : 0.0) +
-                         (form.out == PAIRS_DENSE     ? (double)I * 8
-                          : form.out == PAIRS_TARGETS ? (double)PAIRS_RANK_MAX_T * 12  // (the targets' values and ranks)
-                                                      : (double)(PAIRS_MAX_STRIPES + 1) * k * 12) +
-                         // (the second dense output / mean and std of the lists)
-                         (!form.spread ? 0.0 : form.out == PAIRS_DENSE ? (double)I * 8 : (double)k * 16);
-  int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
-  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
-  chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
 
   // ---- the samples' pointers and w0
   DevBuf<const double *> d_wv;
@@ -720,17 +901,19 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
     }
     if (!refs.empty()) d_blk[side].upload(refs);
   }
-  // a side with blocks gathers from its tables, one without takes the instantiation that reads no block argument
+  // rows [r0, r0 + R) of a side (0 query, 1 candidates) into Pf and the biases: a side with blocks gathers from its tables, one
+  // without takes the instantiation that reads no block argument
   // (map_row / map_s: the row -> sample plan's flavour, one launch row per row of P under its own sample)
-  const auto embed = [&](int side, const int64_t *ptr, const int32_t *idx, const double *val, int64_t r0, int64_t R, int64_t Rpad, double *Pf,
-                         double *bias, const int32_t *map_row, const int32_t *map_s) {
+  const auto embed = [&](int side, int64_t r0, int64_t R, int64_t Rpad, double *Pf, double *bias, const int32_t *map_row = nullptr,
+                         const int32_t *map_s = nullptr) {
     const dim3 grid((unsigned)((Rpad + PAIRS_WG - 1) / PAIRS_WG), map_row ? 1u : (unsigned)S);
     const bool rel = !p->blocks[side].empty();
     const PairsBlockRef *blk = rel ? (const PairsBlockRef *)d_blk[side].p : nullptr;
     const int n_blk = (int)p->blocks[side].size();
     const auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, grid, dim3(PAIRS_WG), 0, s, ptr, idx, val, r0, R, Rpad, (const double *const *)d_wv.p, D, K, KS, S, blk,
-                         n_blk, Pf, bias, map_row, map_s);
+      hipLaunchKernelGGL(kernel, grid, dim3(PAIRS_WG), 0, s, side ? p->c_ptr.p : p->q_ptr.p, side ? p->c_idx.p : p->q_idx.p,
+                         side ? p->c_val.p : p->q_val.p, r0, R, Rpad, (const double *const *)d_wv.p, D, K, KS, S, blk, n_blk, Pf, bias, map_row,
+                         map_s);
     };
     if (sim == PAIRS_SIM_COSINE)  // (the bias slot gets the rows' 1 / norm, or 1.0: mfm_pairs_sim.hpp)
       rel ? launch(k_pairs_embed<true, false, 1>) : launch(k_pairs_embed<false, false, 1>);
@@ -742,258 +925,291 @@ void run_pairs(mfm_pairs *p, const SampleView &v, int mode, int k, int64_t *idx,
       rel ? launch(k_pairs_embed<true, false>) : launch(k_pairs_embed<false, false>);
   };
 
-  // ---- candidate side, once
-  DevBuf<double> Qf, Bb, Bsum;
-  Qf.alloc((size_t)std::max<int64_t>(Ipad * NK * 4, 1));
-  Bb.alloc((size_t)Ipad * S);
-  if (sim < 0) Bsum.alloc((size_t)Ipad);  // (the similarity finish reads the per-sample slots alone: no sums, Asum / Bsum stay null)
-  embed(1, p->c_ptr.p, p->c_idx.p, p->c_val.p, (int64_t)0, I, Ipad, Qf.p, Bb.p, nullptr, nullptr);
-  if (sim < 0) hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)(Ipad / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Bb.p, S, Ipad, Bsum.p);
-  MFM_HIP_CHECK(hipGetLastError());
-
-  // ---- what every launch of the call reads; a chunk adds its own
-  PairsArgs call;
-  call.Pf = nullptr;
-  call.Qf = Qf.p;
-  call.NK = NK;
-  call.p_stride = NK;
-  call.q_stride = NK;
-  call.KS4 = KS4;
-  call.S = S;
-  call.Ab = nullptr;
-  call.Asum = nullptr;
-  call.Bb = Bb.p;
-  call.Bsum = Bsum.p;
+  Candidates cand;
+  PairsArgs call = embed_candidates(p, d, rq, sim < 0, embed, cand);
   call.w0s = d_w0.p;
   call.w0sum = w0sum;
   call.cut = mode == 2 ? d_cut.p : nullptr;
   call.n_cut = mode == 2 ? p->n_cut : 0;
-  call.beta = mo ? mo->beta : 0.0;
-  call.Upad = 0;
-  call.Ipad = Ipad;
-  call.Uc = 0;
-  call.I = I;
-  call.stripe_len = 0;
-  call.dense = nullptr;
-  call.dense_std = nullptr;
-  call.mask = nullptr;
-  call.W = W;
-  call.k = k;
-  call.list_v = nullptr;
-  call.list_i = nullptr;
-  call.tptr = nullptr;
-  call.tidx = nullptr;
-  call.tval = nullptr;
-  call.trank = nullptr;
-  call.u0 = 0;
-  call.tbase = 0;
-  call.plan = nullptr;
-  call.row_of = nullptr;
-  call.list_rows = 0;
-  if (ps) {
-    walk_samples(p, form, call, mode, *ps, embed);
-    return;
-  }
-  if (sc) {
-    run_screened(p, call, *sc, k, idx, score, dense, embed);
-    return;
-  }
+  if (rq.per_sample())
+    walk_samples(p, form, call, rq, embed);
+  else if (rq.screened())
+    run_screened(p, call, rq, embed);
+  else
+    walk_queries(p, form, call, rq, embed, [&](const PairsArgs &a, const int32_t *out_i, int64_t n, double *mean, double *sd) {
+      launch_moments_at(s, a, mode, form.sim, out_i, n, mean, sd);
+    });
+}
 
-  // ---- queries, chunk by chunk
-  DevBuf<double> Pf, Ab, Asum, list_v, out_v, d_dense, d_dense_std, out_m, out_s;
-  DevBuf<int32_t> list_i, out_i;
-  DevBuf<uint32_t> mask;
-  DevBuf<int32_t> t_rank;
-  DevBuf<double> t_val;
-  std::vector<int32_t> h_idx;
-  for (int64_t u0 = 0; u0 < U; u0 += chunk) {
-    const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
-    const int64_t tbase = rk ? p->t_ptr_host[u0] : 0, n_t = rk ? p->t_ptr_host[u0 + Uc] - tbase : 0;
-    if (rk && n_t == 0) continue;
-    ensure(Pf, (size_t)(Upad * NK * 4));
-    ensure(Ab, (size_t)(Upad * S));
-    if (sim < 0) ensure(Asum, (size_t)Upad);
-    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p, nullptr, nullptr);
-    if (sim < 0)
-      hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, Ab.p, S, Upad,
-                         Asum.p);
-    const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
-    if (use_mask) {
-      ensure(mask, (size_t)(Uc * W));
-      MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
+// ---- the variational forms (mfm_pairs_vb.hpp, DESIGN 10.1) ----------------------------------------------------------------------
+// Analytic mean and standard deviation of the score of every pair under the posterior N(w0, w0_var), N(w, w_var), N(V, V_var): five
+// pseudo-samples of width KS through the per-sample contraction, ASK_MOMENTS or ASK_UCB. The memory rule, the chunks, the stripes and
+// the merge are walk_queries', with S = 5 in every formula; the tile shapes are the moments forms' (MT NT = 4).
+template <int MT, int NT, PairsOut OUT>
+PairsForm pairs_vb_form_of() {
+  return {MT, NT, true, OUT, [](hipStream_t s, dim3 grid, const PairsArgs &a, int) {
+            constexpr bool DENSE = OUT == PAIRS_DENSE;
+            launch_pairs<k_pairs_tile_vb<MT, NT, DENSE>>(s, grid, DENSE ? 0 : PairsSel<MT>::BYTES, a);
+          }};
+}
+
+PairsForm pairs_vb_form(const PairsRequest &rq) {
+  if (rq.dense_form()) return pairs_vb_form_of<2, 2, PAIRS_DENSE>();
+  if (rq.k <= 64) return pairs_vb_form_of<4, 1, PAIRS_SELECT>();
+  if (rq.k <= 128) return pairs_vb_form_of<2, 2, PAIRS_SELECT>();
+  return pairs_vb_form_of<1, 4, PAIRS_SELECT>();
+}
+
+// the six arrays of a variational model as a C-ABI call hands them over (host memory; V, V_var column-major (D, K))
+struct PairsVbHost {
+  int rank;
+  double w0, w0_var, extra_var;
+  const double *w, *w_var, *V, *V_var;
+};
+
+// the checks of the variational calls that need no device
+void check_vb_model(const mfm_pairs *p, const PairsVbHost &h) {
+  if (h.rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
+  if (!(h.w0_var >= 0.0)) throw Error(MFM_ERR_INVALID, "w0_var must be non-negative");
+  if (!(h.extra_var >= 0.0) || !std::isfinite(h.extra_var)) throw Error(MFM_ERR_INVALID, "extra_var must be finite and non-negative");
+  if (p->D > 0 && (!h.w || !h.w_var || (h.rank > 0 && (!h.V || !h.V_var)))) throw Error(MFM_ERR_INVALID, "no posterior arrays");
+}
+
+void score_vb(mfm_pairs *p, const PairsVbHost &h, const PairsRequest &rq) {
+  refuse_similarity_handle(p);
+  check_vb_model(p, h);
+  const bool is_dense = rq.dense_form();
+  if (!is_dense && (rq.k < 1 || rq.k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  const PairsForm form = pairs_vb_form(rq);
+  const int64_t U = p->U, I = p->I, D = p->D;
+  if (U == 0 || (is_dense && I == 0)) return;
+  hipStream_t s = p->stream;
+  const PairsDims d = pairs_dims(p, PAIRS_VB_S, h.rank);
+  const int K = d.K, KS = d.KS;
+
+  // ---- the memory rule: Q and every block table resident, the query scratch bounded
+  const double q_bytes = ((double)d.Ipad * d.S * KS + (double)d.Ipad * d.S) * sizeof(double);
+  double t_bytes = 0.0;
+  for (int side = 0; side < 2; side++)
+    for (auto &b : p->blocks[side]) t_bytes += (double)b->M * (5 * KS + 3) * sizeof(double);
+  if (exceeds_store_fraction(q_bytes + t_bytes))
+    throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + std::to_string((int64_t)(q_bytes / 1048576.0)) +
+                                     " MB) and the block tables (" + std::to_string((int64_t)(t_bytes / 1048576.0)) +
+                                     " MB) exceed MFM_STORE_MAX_FRACTION of the free device memory; score fewer candidates or smaller blocks per call");
+
+  // ---- the posterior on the device
+  const size_t DK = (size_t)D * (size_t)K;
+  DevBuf<double> model, d_w0;
+  model.alloc(std::max<size_t>(2 * (size_t)D + 2 * DK, 1));
+  if (D) {
+    MFM_HIP_CHECK(hipMemcpy(model.p, h.w, (size_t)D * sizeof(double), hipMemcpyHostToDevice));
+    MFM_HIP_CHECK(hipMemcpy(model.p + D, h.w_var, (size_t)D * sizeof(double), hipMemcpyHostToDevice));
+    if (K) {
+      MFM_HIP_CHECK(hipMemcpy(model.p + 2 * D, h.V, DK * sizeof(double), hipMemcpyHostToDevice));
+      MFM_HIP_CHECK(hipMemcpy(model.p + 2 * D + DK, h.V_var, DK * sizeof(double), hipMemcpyHostToDevice));
     }
-    // stripes: enough workgroups to fill the device twice, at most PAIRS_MAX_STRIPES lists to merge
-    const int64_t n_qt = Upad / form.rows();
-    int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_qt - 1) / n_qt, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
-    const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
-    n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
-    const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
-    PairsArgs a = call;
-    a.Pf = Pf.p;
-    a.Ab = Ab.p;
-    a.Asum = Asum.p;
-    a.Upad = Upad;
-    a.Uc = Uc;
-    a.stripe_len = stripe_steps * form.step();
-    a.mask = use_mask ? mask.p : nullptr;
-    a.list_rows = Upad;
-    a.u0 = u0;
-    a.tbase = tbase;
-    if (rk) {
-      ensure(t_val, (size_t)n_t);
-      ensure(t_rank, (size_t)n_t);
-      a.tptr = p->t_ptr.p;
-      a.tidx = p->t_idx.p;
-      a.tval = t_val.p;
-      a.trank = t_rank.p;
-      MFM_HIP_CHECK(hipMemsetAsync(t_rank.p, 0, (size_t)n_t * sizeof(int32_t), s));
-      form.launch(s, grid, a, mode);
-      MFM_HIP_CHECK(hipGetLastError());
-      h_idx.resize((size_t)n_t);
-      MFM_HIP_CHECK(hipMemcpyAsync(rk->value + tbase, t_val.p, (size_t)n_t * sizeof(double), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), t_rank.p, (size_t)n_t * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipStreamSynchronize(s));
-      for (int64_t e = 0; e < n_t; e++) rk->rank[tbase + e] = h_idx[(size_t)e];
-      continue;
-    }
-    if (is_dense) {
-      ensure(d_dense, (size_t)(Uc * I));
-      a.dense = d_dense.p;
-      if (mo) {
-        ensure(d_dense_std, (size_t)(Uc * I));
-        a.dense_std = d_dense_std.p;
+  }
+  PairsVbModel pm;
+  pm.w = model.p;
+  pm.wv = model.p + D;
+  pm.V = model.p + 2 * D;
+  pm.Vv = model.p + 2 * D + DK;
+  pm.D = D;
+  pm.K = K;
+  pm.KS = KS;
+  pm.var0 = h.w0_var + h.extra_var;
+  d_w0.upload(std::vector<double>{h.w0, 0.0, 0.0, 0.0, 0.0});
+
+  // ---- the block tables of both sides, once per call
+  std::vector<DevBuf<double>> tables[2];
+  DevBuf<PairsVbBlockRef> d_blk[2];
+  for (int side = 0; side < 2; side++) {
+    std::vector<PairsVbBlockRef> refs;
+    for (auto &b : p->blocks[side]) {
+      const size_t M = (size_t)b->M;
+      tables[side].emplace_back();
+      DevBuf<double> &t = tables[side].back();
+      t.alloc(std::max<size_t>(M * (size_t)(5 * KS + 3), 1));
+      PairsVbBlockRef ref;
+      ref.o2b = b->o2b.p;
+      ref.T = t.p;
+      ref.lin = t.p + M * (size_t)(5 * KS);
+      ref.vv = ref.lin + M;
+      ref.lv = ref.vv + M;
+      ref.M = b->M;
+      refs.push_back(ref);
+      if (b->M > 0) {
+        hipLaunchKernelGGL(k_pairs_vb_embed_block, dim3((unsigned)((b->M + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, b->ptr.p, b->idx.p,
+                           b->val.p, b->M, b->off, pm, t.p, t.p + M * (size_t)(5 * KS), t.p + M * (size_t)(5 * KS + 1),
+                           t.p + M * (size_t)(5 * KS + 2));
+        MFM_HIP_CHECK(hipGetLastError());
       }
-      form.launch(s, grid, a, mode);
-      MFM_HIP_CHECK(hipGetLastError());
-      if (mo)
-        MFM_HIP_CHECK(
-            hipMemcpyAsync(mo->sd + (size_t)u0 * I, d_dense_std.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipMemcpyAsync(dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipStreamSynchronize(s));
-      continue;
     }
-    ensure(list_v, (size_t)(n_stripes * Upad * k));
-    ensure(list_i, (size_t)(n_stripes * Upad * k));
-    ensure(out_v, (size_t)(Uc * k));
-    ensure(out_i, (size_t)(Uc * k));
-    a.list_v = list_v.p;
-    a.list_i = list_i.p;
-    if (I > 0) {
-      form.launch(s, grid, a, mode);
-      MFM_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, k,
-                       out_v.p, out_i.p);
-    MFM_HIP_CHECK(hipGetLastError());
-    if (mo) {
-      ensure(out_m, (size_t)(Uc * k));
-      ensure(out_s, (size_t)(Uc * k));
-      launch_moments_at(s, a, mode, form.sim, out_i.p, Uc * k, out_m.p, out_s.p);
-      MFM_HIP_CHECK(hipGetLastError());
-      MFM_HIP_CHECK(hipMemcpyAsync(mo->mean + (size_t)u0 * k, out_m.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipMemcpyAsync(mo->sd + (size_t)u0 * k, out_s.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    h_idx.resize((size_t)(Uc * k));
-    MFM_HIP_CHECK(hipMemcpyAsync(score + (size_t)u0 * k, out_v.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), out_i.p, (size_t)(Uc * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipStreamSynchronize(s));
-    for (int64_t e = 0; e < Uc * k; e++) idx[u0 * k + e] = h_idx[(size_t)e];
+    if (!refs.empty()) d_blk[side].upload(refs);
   }
-  MFM_HIP_CHECK(hipStreamSynchronize(s));
-}
+  const auto embed = [&](int side, int64_t r0, int64_t R, int64_t Rpad, double *Pf, double *bias) {
+    const dim3 grid((unsigned)((Rpad + PAIRS_WG - 1) / PAIRS_WG));
+    const bool rel = !p->blocks[side].empty();
+    const PairsVbBlockRef *blk = rel ? (const PairsVbBlockRef *)d_blk[side].p : nullptr;
+    const int n_blk = (int)p->blocks[side].size();
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(PAIRS_WG), 0, s, side ? p->c_ptr.p : p->q_ptr.p, side ? p->c_idx.p : p->q_idx.p,
+                         side ? p->c_val.p : p->q_val.p, r0, R, Rpad, pm, blk, n_blk, Pf, bias);
+    };
+    if (side == 1)
+      rel ? launch(k_pairs_vb_embed<true, true>) : launch(k_pairs_vb_embed<false, true>);
+    else
+      rel ? launch(k_pairs_vb_embed<true, false>) : launch(k_pairs_vb_embed<false, false>);
+  };
 
-// A similarity handle's sides may share columns: the score's split into per-side terms and one contraction is wrong there, so every
-// scoring form is refused on it, before the samples are looked at.
-void refuse_similarity_handle(const mfm_pairs *p) {
-  if (p->similarity)
-    throw Error(MFM_ERR_INVALID, "this is a similarity handle (mfm_pairs_create_sim): its sides may share columns, which the pair score's "
-                                 "decomposition does not allow; it serves mfm_pairs_sim* and mfm_pairs_topk_sim* only");
-}
-
-void run_pairs_store(mfm_pairs *p, mfm_store *st, int first, int count, int mode, int k, int64_t *idx, double *score, double *dense,
-                     const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr, const PairsPerSample *ps = nullptr, int sim = -1,
-                     const PairsScreen *sc = nullptr) {
-  if (sim < 0) refuse_similarity_handle(p);
-  if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  run_pairs(p, samples_of_store(st, first, count), mode, k, idx, score, dense, mo, rk, ps, sim, sc);
-}
-
-void run_pairs_host(mfm_pairs *p, int rank, int n_samples, const double *w0s, const double *ws, const double *Vs, int mode, int k,
-                    int64_t *idx, double *score, double *dense, const PairsMoments *mo = nullptr, const PairsRank *rk = nullptr,
-                    const PairsPerSample *ps = nullptr, int sim = -1, const PairsScreen *sc = nullptr) {
-  if (sim < 0) refuse_similarity_handle(p);
-  run_pairs(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), mode, k, idx, score, dense, mo, rk, ps, sim, sc);
+  Candidates cand;
+  PairsArgs call = embed_candidates(p, d, rq, false, embed, cand);
+  call.w0s = d_w0.p;
+  walk_queries(p, form, call, rq, embed, [&](const PairsArgs &a, const int32_t *out_i, int64_t n, double *mean, double *sd) {
+    hipLaunchKernelGGL(k_pairs_vb_at, dim3((unsigned)((n + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, a, out_i, n, mean, sd);
+  });
 }
 
 static_assert(PAIRS_SIM_COSINE == MFM_PAIRS_SIM_COSINE && PAIRS_SIM_DOT == MFM_PAIRS_SIM_DOT, "the metrics as the header numbers them");
 
-// the checks of the similarity calls that need neither samples nor a device
+// ---- the requests of the entry points: each form's checks that need neither samples nor a device, once for its twins ------------
+PairsRequest checked_scores(int mode, double *out) {
+  if (!out) throw Error(MFM_ERR_INVALID, "no output array");
+  PairsRequest rq{ASK_SCORES};
+  rq.mode = mode;
+  rq.dense = out;
+  return rq;
+}
+
+PairsRequest checked_topk(int mode, int k, int64_t *idx, double *score) {
+  if (!idx || !score) throw Error(MFM_ERR_INVALID, "no output array");
+  PairsRequest rq{ASK_TOPK};
+  rq.mode = mode;
+  rq.k = k;
+  rq.idx = idx;
+  rq.value = score;
+  return rq;
+}
+
+PairsRequest checked_moments(int mode, double *mean, double *sd) {
+  if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
+  PairsRequest rq{ASK_MOMENTS};
+  rq.mode = mode;
+  rq.dense = mean;
+  rq.sd = sd;
+  return rq;
+}
+
+PairsRequest checked_ucb(int mode, int k, double beta, int64_t *idx, double *value, double *mean, double *sd) {
+  if (!idx || !value || !mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
+  if (k < 1 || k > PAIRS_MAX_K) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
+  if (!std::isfinite(beta)) throw Error(MFM_ERR_INVALID, "beta must be a finite number");
+  PairsRequest rq{ASK_UCB};
+  rq.mode = mode;
+  rq.k = k;
+  rq.beta = beta;
+  rq.idx = idx;
+  rq.value = value;
+  rq.mean = mean;
+  rq.sd = sd;
+  return rq;
+}
+
 void check_sim_metric(int metric) {
   if (metric != PAIRS_SIM_COSINE && metric != PAIRS_SIM_DOT)
     throw Error(MFM_ERR_INVALID, "bad similarity metric " + std::to_string(metric) + " (0: cosine, 1: dot)");
 }
 
-PairsMoments checked_sim_dense(const mfm_pairs *p, int metric, double *mean, double *sd) {
+PairsRequest checked_sim_dense(const mfm_pairs *p, int metric, double *mean, double *sd) {
   if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
   check_sim_metric(metric);
   if ((double)p->U * (double)p->I > 16777216.0)
     throw Error(MFM_ERR_INVALID, "the dense similarity call returns every pair: more than 2^24 pairs are refused, use mfm_pairs_topk_sim");
-  PairsMoments mo;
-  mo.sd = sd;
-  return mo;
+  PairsRequest rq{ASK_SIM};
+  rq.metric = metric;
+  rq.dense = mean;
+  rq.sd = sd;
+  return rq;
 }
 
-// the checks of the per-sample calls that need neither samples nor a device
-PairsPerSample checked_per_sample(int k, const int32_t *row_sample, int n_top, bool vote, int64_t *idx, double *value) {
+PairsRequest checked_topk_sim(int metric, int k, double beta, int64_t *idx, double *value, double *mean, double *sd) {
+  PairsRequest rq = checked_ucb(0, k, beta, idx, value, mean, sd);
+  check_sim_metric(metric);
+  rq.ask = ASK_TOPK_SIM;
+  rq.metric = metric;
+  return rq;
+}
+
+PairsRequest checked_per_sample(PairsAsk ask, int mode, int k, const int32_t *row_sample, int n_top, int64_t *idx, double *value) {
   if (!idx || !value) throw Error(MFM_ERR_INVALID, "no output array");
   if (k < 1 || k > PAIRS_MAX_K) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
-  if (vote && (n_top < 1 || n_top > PAIRS_VOTE_MAX_TOP)) throw Error(MFM_ERR_INVALID, "n_top must be in [1, 256]");
-  PairsPerSample ps;
-  ps.row_sample = row_sample;
-  ps.n_top = vote ? n_top : 0;
-  ps.idx = idx;
-  ps.value = value;
-  return ps;
+  if (ask == ASK_VOTE && (n_top < 1 || n_top > PAIRS_VOTE_MAX_TOP)) throw Error(MFM_ERR_INVALID, "n_top must be in [1, 256]");
+  PairsRequest rq{ask};
+  rq.mode = mode;
+  rq.k = k;
+  rq.row_sample = row_sample;
+  rq.n_top = n_top;
+  rq.idx = idx;
+  rq.value = value;
+  return rq;
 }
 
-// the outputs of a rank call: none is needed while no target is stored
-PairsRank checked_rank(const mfm_pairs *p, int64_t *rank_out, double *value_out) {
+// (no output is needed while no target is stored)
+PairsRequest checked_rank(const mfm_pairs *p, int mode, int64_t *rank_out, double *value_out) {
   if (p->has_targets && (!rank_out || !value_out)) throw Error(MFM_ERR_INVALID, "no output array");
-  PairsRank rk;
-  rk.rank = rank_out;
-  rk.value = value_out;
-  return rk;
+  PairsRequest rq{ASK_RANK};
+  rq.mode = mode;
+  rq.target_rank = rank_out;
+  rq.target_value = value_out;
+  return rq;
 }
 
-// the checks of the screened calls that need neither samples nor a device
-PairsScreen checked_screened(int k, const int64_t *idx, const double *value, uint8_t *certified) {
+PairsRequest checked_screened(int k, int64_t *idx, double *value, uint8_t *certified) {
   if (!idx || !value || !certified) throw Error(MFM_ERR_INVALID, "no output array");
   if (k < 1 || k > SCREEN_MAX_K) throw Error(MFM_ERR_INVALID, "k must be in [1, 128]");
-  PairsScreen sc;
-  sc.certified = certified;
-  return sc;
+  PairsRequest rq{ASK_SCREENED};
+  rq.k = k;
+  rq.idx = idx;
+  rq.value = value;
+  rq.certified = certified;
+  return rq;
 }
 
-PairsScreen checked_screen_dense(const mfm_pairs *p, const double *r, double *bound) {
+PairsRequest checked_screen_dense(const mfm_pairs *p, double *r, double *bound) {
   if (!r || !bound) throw Error(MFM_ERR_INVALID, "no output array");
   if ((double)p->U * (double)p->I > 16777216.0)
     throw Error(MFM_ERR_INVALID, "the dense screening call returns every pair: more than 2^24 pairs are refused, use mfm_pairs_topk_screened");
-  PairsScreen sc;
-  sc.bound = bound;
-  return sc;
+  PairsRequest rq{ASK_SCREEN_DENSE};
+  rq.dense = r;
+  rq.bound = bound;
+  return rq;
 }
 
-// the checks of the ranked moments calls that need neither samples nor a device
-PairsMoments checked_ucb(int k, double beta, const int64_t *idx, const double *value, double *mean, double *sd) {
-  if (!idx || !value || !mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
-  if (k < 1 || k > PAIRS_MAX_K) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
-  if (!std::isfinite(beta)) throw Error(MFM_ERR_INVALID, "beta must be a finite number");
-  PairsMoments mo;
-  mo.beta = beta;
-  mo.mean = mean;
-  mo.sd = sd;
-  return mo;
+// ---- where a call's samples come from: all that the _store and the host twin of a form differ in ---------------------------------
+struct FromStore {
+  mfm_store *st;
+  int first, count;
+  SampleView samples(const mfm_pairs *) const {
+    if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
+    return samples_of_store(st, first, count);
+  }
+};
+
+struct FromHost {
+  int rank, n_samples;
+  const double *w0s, *ws, *Vs;
+  SampleView samples(const mfm_pairs *p) const { return samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs); }
+};
+
+// An entry point over samples: the form's checks (`checked`, one of the functions above), the refusal of a similarity handle for every
+// form but its own, the samples, the call.
+template <class From, class Checked>
+int pairs_call(mfm_pairs *p, const From &from, Checked checked) {
+  PAIRS_TRY(p)
+  const PairsRequest rq = checked();
+  if (!rq.sim()) refuse_similarity_handle(p);
+  run_pairs(p, from.samples(p), rq);
+  PAIRS_CATCH(p)
 }
 
 }  // namespace
@@ -1177,422 +1393,109 @@ int mfm_pairs_set_scratch_bound(mfm_pairs *p, int64_t bytes) {
 }
 
 int mfm_pairs_scores_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, double *out) {
-  PAIRS_TRY(p)
-  if (!out) throw Error(MFM_ERR_INVALID, "no output array");
-  run_pairs_store(p, st, first, count, mode, 0, nullptr, nullptr, out);
-  PAIRS_CATCH(p)
-}
-
-int mfm_pairs_topk_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int64_t *idx,
-                         double *score) {
-  PAIRS_TRY(p)
-  if (!idx || !score) throw Error(MFM_ERR_INVALID, "no output array");
-  run_pairs_store(p, st, first, count, mode, k, idx, score, nullptr);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_scores(mode, out); });
 }
 
 int mfm_pairs_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                      int32_t mode, double *out) {
-  PAIRS_TRY(p)
-  if (!out) throw Error(MFM_ERR_INVALID, "no output array");
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, 0, nullptr, nullptr, out);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_scores(mode, out); });
+}
+
+int mfm_pairs_topk_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int64_t *idx,
+                         double *score) {
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_topk(mode, k, idx, score); });
 }
 
 int mfm_pairs_topk(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                    int32_t mode, int32_t k, int64_t *idx, double *score) {
-  PAIRS_TRY(p)
-  if (!idx || !score) throw Error(MFM_ERR_INVALID, "no output array");
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, idx, score, nullptr);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_topk(mode, k, idx, score); });
 }
 
 int mfm_pairs_topk_screened_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t k, int64_t *idx, double *value,
                                   uint8_t *certified) {
-  PAIRS_TRY(p)
-  const PairsScreen sc = checked_screened(k, idx, value, certified);
-  run_pairs_store(p, st, first, count, 0, k, idx, value, nullptr, nullptr, nullptr, nullptr, -1, &sc);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_screened(k, idx, value, certified); });
 }
 
 int mfm_pairs_topk_screened(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t k,
                             int64_t *idx, double *value, uint8_t *certified) {
-  PAIRS_TRY(p)
-  const PairsScreen sc = checked_screened(k, idx, value, certified);
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, 0, k, idx, value, nullptr, nullptr, nullptr, nullptr, -1, &sc);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_screened(k, idx, value, certified); });
 }
 
 int mfm_pairs_screen_scores_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, double *r, double *bound) {
-  PAIRS_TRY(p)
-  const PairsScreen sc = checked_screen_dense(p, r, bound);
-  run_pairs_store(p, st, first, count, 0, 0, nullptr, nullptr, r, nullptr, nullptr, nullptr, -1, &sc);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_screen_dense(p, r, bound); });
 }
 
 int mfm_pairs_screen_scores(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, double *r,
                             double *bound) {
-  PAIRS_TRY(p)
-  const PairsScreen sc = checked_screen_dense(p, r, bound);
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, 0, 0, nullptr, nullptr, r, nullptr, nullptr, nullptr, -1, &sc);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_screen_dense(p, r, bound); });
 }
 
 int mfm_pairs_moments_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, double *mean, double *sd) {
-  PAIRS_TRY(p)
-  if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
-  PairsMoments mo;
-  mo.sd = sd;
-  run_pairs_store(p, st, first, count, mode, 0, nullptr, nullptr, mean, &mo);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_moments(mode, mean, sd); });
 }
 
 int mfm_pairs_moments(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                       int32_t mode, double *mean, double *sd) {
-  PAIRS_TRY(p)
-  if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
-  PairsMoments mo;
-  mo.sd = sd;
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, 0, nullptr, nullptr, mean, &mo);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_moments(mode, mean, sd); });
 }
 
 int mfm_pairs_topk_ucb_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, double beta,
                              int64_t *idx, double *value, double *mean, double *sd) {
-  PAIRS_TRY(p)
-  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
-  run_pairs_store(p, st, first, count, mode, k, idx, value, nullptr, &mo);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_ucb(mode, k, beta, idx, value, mean, sd); });
 }
 
 int mfm_pairs_topk_ucb(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                        int32_t mode, int32_t k, double beta, int64_t *idx, double *value, double *mean, double *sd) {
-  PAIRS_TRY(p)
-  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, idx, value, nullptr, &mo);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_ucb(mode, k, beta, idx, value, mean, sd); });
 }
 
 int mfm_pairs_sim_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t metric, double *mean, double *sd) {
-  PAIRS_TRY(p)
-  const PairsMoments mo = checked_sim_dense(p, metric, mean, sd);
-  run_pairs_store(p, st, first, count, 0, 0, nullptr, nullptr, mean, &mo, nullptr, nullptr, metric);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_sim_dense(p, metric, mean, sd); });
 }
 
 int mfm_pairs_sim(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t metric,
                   double *mean, double *sd) {
-  PAIRS_TRY(p)
-  const PairsMoments mo = checked_sim_dense(p, metric, mean, sd);
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, 0, 0, nullptr, nullptr, mean, &mo, nullptr, nullptr, metric);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_sim_dense(p, metric, mean, sd); });
 }
 
 int mfm_pairs_topk_sim_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t metric, int32_t k, double beta,
                              int64_t *idx, double *value, double *mean, double *sd) {
-  PAIRS_TRY(p)
-  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
-  check_sim_metric(metric);
-  run_pairs_store(p, st, first, count, 0, k, idx, value, nullptr, &mo, nullptr, nullptr, metric);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_topk_sim(metric, k, beta, idx, value, mean, sd); });
 }
 
 int mfm_pairs_topk_sim(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                        int32_t metric, int32_t k, double beta, int64_t *idx, double *value, double *mean, double *sd) {
-  PAIRS_TRY(p)
-  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
-  check_sim_metric(metric);
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, 0, k, idx, value, nullptr, &mo, nullptr, nullptr, metric);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_topk_sim(metric, k, beta, idx, value, mean, sd); });
 }
 
 int mfm_pairs_topk_samples_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k,
                                  const int32_t *row_sample, int64_t *idx, double *value) {
-  PAIRS_TRY(p)
-  const PairsPerSample ps = checked_per_sample(k, row_sample, 0, false, idx, value);
-  run_pairs_store(p, st, first, count, mode, k, nullptr, nullptr, nullptr, nullptr, nullptr, &ps);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_per_sample(ASK_SAMPLES, mode, k, row_sample, 0, idx, value); });
 }
 
 int mfm_pairs_topk_samples(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                            int32_t mode, int32_t k, const int32_t *row_sample, int64_t *idx, double *value) {
-  PAIRS_TRY(p)
-  const PairsPerSample ps = checked_per_sample(k, row_sample, 0, false, idx, value);
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, nullptr, nullptr, nullptr, nullptr, nullptr, &ps);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_per_sample(ASK_SAMPLES, mode, k, row_sample, 0, idx, value); });
 }
 
 int mfm_pairs_topk_prob_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int32_t n_top,
                               int64_t *idx, double *prob) {
-  PAIRS_TRY(p)
-  const PairsPerSample ps = checked_per_sample(k, nullptr, n_top, true, idx, prob);
-  run_pairs_store(p, st, first, count, mode, k, nullptr, nullptr, nullptr, nullptr, nullptr, &ps);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_per_sample(ASK_VOTE, mode, k, nullptr, n_top, idx, prob); });
 }
 
 int mfm_pairs_topk_prob(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                         int32_t mode, int32_t k, int32_t n_top, int64_t *idx, double *prob) {
-  PAIRS_TRY(p)
-  const PairsPerSample ps = checked_per_sample(k, nullptr, n_top, true, idx, prob);
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, k, nullptr, nullptr, nullptr, nullptr, nullptr, &ps);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_per_sample(ASK_VOTE, mode, k, nullptr, n_top, idx, prob); });
 }
 
 int mfm_pairs_rank_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int64_t *rank_out, double *value_out) {
-  PAIRS_TRY(p)
-  const PairsRank rk = checked_rank(p, rank_out, value_out);
-  run_pairs_store(p, st, first, count, mode, 0, nullptr, nullptr, nullptr, nullptr, &rk);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_rank(p, mode, rank_out, value_out); });
 }
 
 int mfm_pairs_rank(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t mode,
                    int64_t *rank_out, double *value_out) {
-  PAIRS_TRY(p)
-  const PairsRank rk = checked_rank(p, rank_out, value_out);
-  run_pairs_host(p, rank, n_samples, w0s, ws, Vs, mode, 0, nullptr, nullptr, nullptr, nullptr, &rk);
-  PAIRS_CATCH(p)
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_rank(p, mode, rank_out, value_out); });
 }
-
-}  // extern "C"
-
-// ---- the variational forms (mfm_pairs_vb.hpp, DESIGN 10.1) ----------------------------------------------------------------------
-// Analytic mean and standard deviation of the score of every pair under the posterior N(w0, w0_var), N(w, w_var), N(V, V_var): five
-// pseudo-samples of width KS through the per-sample contraction. The handle's sides, blocks, exclusions, scratch bound and query
-// chunking are run_pairs', with S = 5 in every formula; the tile shapes are the moments forms' (MT NT = 4).
-namespace {
-
-struct PairsVbForm {
-  int MT, NT;
-  void (*launch)(hipStream_t, dim3, const PairsArgs &);
-  int rows() const { return 16 * MT; }
-  int step() const { return 64 * NT; }
-};
-
-template <int MT, int NT, bool DENSE>
-void launch_vb_form(hipStream_t s, dim3 grid, const PairsArgs &a) {
-  launch_pairs<k_pairs_tile_vb<MT, NT, DENSE>>(s, grid, DENSE ? 0 : PairsSel<MT>::BYTES, a);
-}
-
-PairsVbForm pairs_vb_form(bool dense, int k) {
-  if (dense) return {2, 2, &launch_vb_form<2, 2, true>};
-  if (k <= 64) return {4, 1, &launch_vb_form<4, 1, false>};
-  if (k <= 128) return {2, 2, &launch_vb_form<2, 2, false>};
-  return {1, 4, &launch_vb_form<1, 4, false>};
-}
-
-// the six arrays of a variational model as a C-ABI call hands them over (host memory; V, V_var column-major (D, K))
-struct PairsVbHost {
-  int rank;
-  double w0, w0_var, extra_var;
-  const double *w, *w_var, *V, *V_var;
-};
-
-// the checks of the variational calls that need no device
-void check_vb_model(const mfm_pairs *p, const PairsVbHost &h) {
-  if (h.rank < 0) throw Error(MFM_ERR_INVALID, "rank must be non-negative");
-  if (!(h.w0_var >= 0.0)) throw Error(MFM_ERR_INVALID, "w0_var must be non-negative");
-  if (!(h.extra_var >= 0.0) || !std::isfinite(h.extra_var)) throw Error(MFM_ERR_INVALID, "extra_var must be finite and non-negative");
-  if (p->D > 0 && (!h.w || !h.w_var || (h.rank > 0 && (!h.V || !h.V_var)))) throw Error(MFM_ERR_INVALID, "no posterior arrays");
-}
-
-// dense != nullptr: (U, I) mean into dense and std into mo.sd; else the top k by mean + mo.beta * std (idx, score, mo.mean, mo.sd)
-void run_pairs_vb(mfm_pairs *p, const PairsVbHost &h, int k, int64_t *idx, double *score, double *dense, const PairsMoments &mo) {
-  refuse_similarity_handle(p);
-  check_vb_model(p, h);
-  const bool is_dense = dense != nullptr;
-  if (!is_dense && (k < 1 || k > PAIRS_MAX_K)) throw Error(MFM_ERR_INVALID, "k must be in [1, 256]");
-  const PairsVbForm form = pairs_vb_form(is_dense, k);
-  const int64_t U = p->U, I = p->I, D = p->D;
-  if (U == 0 || (is_dense && I == 0)) return;
-  hipStream_t s = p->stream;
-  const int S = PAIRS_VB_S, K = h.rank, KS = (K + 3) & ~3, KS4 = KS / 4;
-  const int64_t NK = (int64_t)S * KS4;
-  const int64_t Ipad = round_up(std::max<int64_t>(I, 1), PAIRS_COL_ALIGN);
-
-  // ---- the memory rule of run_pairs: Q and every block table resident, the query scratch bounded
-  const double q_bytes = ((double)Ipad * S * KS + (double)Ipad * S) * sizeof(double);
-  double t_bytes = 0.0;
-  for (int side = 0; side < 2; side++)
-    for (auto &b : p->blocks[side]) t_bytes += (double)b->M * (5 * KS + 3) * sizeof(double);
-  {
-    size_t free_b = 0, total_b = 0;
-    const double frac = env_double("MFM_STORE_MAX_FRACTION", 0.5);
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && q_bytes + t_bytes > frac * (double)free_b)
-      throw Error(MFM_ERR_RUNTIME, "pair scoring: the candidate side's embedding (" + std::to_string((int64_t)(q_bytes / 1048576.0)) +
-                                       " MB) and the block tables (" + std::to_string((int64_t)(t_bytes / 1048576.0)) +
-                                       " MB) exceed MFM_STORE_MAX_FRACTION of the free device memory; score fewer candidates or smaller blocks per call");
-  }
-  const int64_t W = (I + 31) / 32;
-  const int64_t steps_total = (std::max<int64_t>(I, 1) + form.step() - 1) / form.step();
-  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude && !is_dense ? (double)W * 4 : 0.0) +
-                         (is_dense ? (double)I * 16 : (double)(PAIRS_MAX_STRIPES + 1) * k * 12 + (double)k * 16);
-  int64_t chunk = (int64_t)std::min<double>((double)p->scratch_bound / per_row, 1e12);
-  chunk = std::max<int64_t>(chunk / PAIRS_ROW_ALIGN * PAIRS_ROW_ALIGN, PAIRS_ROW_ALIGN);
-  chunk = std::min<int64_t>(chunk, round_up(U, PAIRS_ROW_ALIGN));
-
-  // ---- the posterior on the device
-  const size_t DK = (size_t)D * (size_t)K;
-  DevBuf<double> model, d_w0;
-  model.alloc(std::max<size_t>(2 * (size_t)D + 2 * DK, 1));
-  if (D) {
-    MFM_HIP_CHECK(hipMemcpy(model.p, h.w, (size_t)D * sizeof(double), hipMemcpyHostToDevice));
-    MFM_HIP_CHECK(hipMemcpy(model.p + D, h.w_var, (size_t)D * sizeof(double), hipMemcpyHostToDevice));
-    if (K) {
-      MFM_HIP_CHECK(hipMemcpy(model.p + 2 * D, h.V, DK * sizeof(double), hipMemcpyHostToDevice));
-      MFM_HIP_CHECK(hipMemcpy(model.p + 2 * D + DK, h.V_var, DK * sizeof(double), hipMemcpyHostToDevice));
-    }
-  }
-  PairsVbModel pm;
-  pm.w = model.p;
-  pm.wv = model.p + D;
-  pm.V = model.p + 2 * D;
-  pm.Vv = model.p + 2 * D + DK;
-  pm.D = D;
-  pm.K = K;
-  pm.KS = KS;
-  pm.var0 = h.w0_var + h.extra_var;
-  d_w0.upload(std::vector<double>{h.w0, 0.0, 0.0, 0.0, 0.0});
-
-  // ---- the block tables of both sides, once per call
-  std::vector<DevBuf<double>> tables[2];
-  DevBuf<PairsVbBlockRef> d_blk[2];
-  for (int side = 0; side < 2; side++) {
-    std::vector<PairsVbBlockRef> refs;
-    for (auto &b : p->blocks[side]) {
-      const size_t M = (size_t)b->M;
-      tables[side].emplace_back();
-      DevBuf<double> &t = tables[side].back();
-      t.alloc(std::max<size_t>(M * (size_t)(5 * KS + 3), 1));
-      PairsVbBlockRef ref;
-      ref.o2b = b->o2b.p;
-      ref.T = t.p;
-      ref.lin = t.p + M * (size_t)(5 * KS);
-      ref.vv = ref.lin + M;
-      ref.lv = ref.vv + M;
-      ref.M = b->M;
-      refs.push_back(ref);
-      if (b->M > 0) {
-        hipLaunchKernelGGL(k_pairs_vb_embed_block, dim3((unsigned)((b->M + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, b->ptr.p, b->idx.p,
-                           b->val.p, b->M, b->off, pm, t.p, t.p + M * (size_t)(5 * KS), t.p + M * (size_t)(5 * KS + 1),
-                           t.p + M * (size_t)(5 * KS + 2));
-        MFM_HIP_CHECK(hipGetLastError());
-      }
-    }
-    if (!refs.empty()) d_blk[side].upload(refs);
-  }
-  const auto embed = [&](int side, const int64_t *ptr, const int32_t *ci, const double *val, int64_t r0, int64_t R, int64_t Rpad, double *Pf,
-                         double *bias) {
-    const dim3 grid((unsigned)((Rpad + PAIRS_WG - 1) / PAIRS_WG));
-    const bool rel = !p->blocks[side].empty();
-    const PairsVbBlockRef *blk = rel ? (const PairsVbBlockRef *)d_blk[side].p : nullptr;
-    const int n_blk = (int)p->blocks[side].size();
-    const auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, grid, dim3(PAIRS_WG), 0, s, ptr, ci, val, r0, R, Rpad, pm, blk, n_blk, Pf, bias);
-    };
-    if (side == 1)
-      rel ? launch(k_pairs_vb_embed<true, true>) : launch(k_pairs_vb_embed<false, true>);
-    else
-      rel ? launch(k_pairs_vb_embed<true, false>) : launch(k_pairs_vb_embed<false, false>);
-  };
-
-  // ---- candidate side, once
-  DevBuf<double> Qf, Bb;
-  Qf.alloc((size_t)std::max<int64_t>(Ipad * NK * 4, 1));
-  Bb.alloc((size_t)Ipad * S);
-  embed(1, p->c_ptr.p, p->c_idx.p, p->c_val.p, (int64_t)0, I, Ipad, Qf.p, Bb.p);
-  MFM_HIP_CHECK(hipGetLastError());
-
-  PairsArgs call;
-  std::memset(&call, 0, sizeof(call));
-  call.Qf = Qf.p;
-  call.NK = NK;
-  call.p_stride = NK;
-  call.q_stride = NK;
-  call.KS4 = KS4;
-  call.S = S;
-  call.Bb = Bb.p;
-  call.w0s = d_w0.p;
-  call.beta = mo.beta;
-  call.Ipad = Ipad;
-  call.I = I;
-  call.W = W;
-  call.k = k;
-
-  // ---- queries, chunk by chunk
-  DevBuf<double> Pf, Ab, list_v, out_v, d_dense, d_dense_std, out_m, out_s;
-  DevBuf<int32_t> list_i, out_i;
-  DevBuf<uint32_t> mask;
-  std::vector<int32_t> h_idx;
-  for (int64_t u0 = 0; u0 < U; u0 += chunk) {
-    const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
-    ensure(Pf, (size_t)(Upad * NK * 4));
-    ensure(Ab, (size_t)(Upad * S));
-    embed(0, p->q_ptr.p, p->q_idx.p, p->q_val.p, u0, Uc, Upad, Pf.p, Ab.p);
-    MFM_HIP_CHECK(hipGetLastError());
-    const bool use_mask = !is_dense && p->has_exclude && p->e_ptr_host[u0 + Uc] > p->e_ptr_host[u0];
-    if (use_mask) {
-      ensure(mask, (size_t)(Uc * W));
-      MFM_HIP_CHECK(hipMemsetAsync(mask.p, 0, (size_t)(Uc * W) * sizeof(uint32_t), s));
-      hipLaunchKernelGGL(k_pairs_mask, dim3((unsigned)((Uc + 3) / 4)), dim3(PAIRS_WG), 0, s, p->e_ptr.p, p->e_idx.p, u0, Uc, W, mask.p);
-    }
-    const int64_t n_qt = Upad / form.rows();
-    int64_t n_stripes = std::max<int64_t>(1, std::min<int64_t>({(512 + n_qt - 1) / n_qt, steps_total, (int64_t)PAIRS_MAX_STRIPES}));
-    const int64_t stripe_steps = (steps_total + n_stripes - 1) / n_stripes;
-    n_stripes = (steps_total + stripe_steps - 1) / stripe_steps;
-    const dim3 grid((unsigned)n_qt, (unsigned)n_stripes);
-    PairsArgs a = call;
-    a.Pf = Pf.p;
-    a.Ab = Ab.p;
-    a.Upad = Upad;
-    a.Uc = Uc;
-    a.stripe_len = stripe_steps * form.step();
-    a.mask = use_mask ? mask.p : nullptr;
-    a.list_rows = Upad;
-    a.u0 = u0;
-    if (is_dense) {
-      ensure(d_dense, (size_t)(Uc * I));
-      ensure(d_dense_std, (size_t)(Uc * I));
-      a.dense = d_dense.p;
-      a.dense_std = d_dense_std.p;
-      form.launch(s, grid, a);
-      MFM_HIP_CHECK(hipGetLastError());
-      MFM_HIP_CHECK(hipMemcpyAsync(mo.sd + (size_t)u0 * I, d_dense_std.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipMemcpyAsync(dense + (size_t)u0 * I, d_dense.p, (size_t)(Uc * I) * sizeof(double), hipMemcpyDeviceToHost, s));
-      MFM_HIP_CHECK(hipStreamSynchronize(s));
-      continue;
-    }
-    ensure(list_v, (size_t)(n_stripes * Upad * k));
-    ensure(list_i, (size_t)(n_stripes * Upad * k));
-    ensure(out_v, (size_t)(Uc * k));
-    ensure(out_i, (size_t)(Uc * k));
-    ensure(out_m, (size_t)(Uc * k));
-    ensure(out_s, (size_t)(Uc * k));
-    a.list_v = list_v.p;
-    a.list_i = list_i.p;
-    if (I > 0) {
-      form.launch(s, grid, a);
-      MFM_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, k,
-                       out_v.p, out_i.p);
-    MFM_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_pairs_vb_at, dim3((unsigned)((Uc * k + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, a, out_i.p, Uc * k, out_m.p,
-                       out_s.p);
-    MFM_HIP_CHECK(hipGetLastError());
-    h_idx.resize((size_t)(Uc * k));
-    MFM_HIP_CHECK(hipMemcpyAsync(mo.mean + (size_t)u0 * k, out_m.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipMemcpyAsync(mo.sd + (size_t)u0 * k, out_s.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipMemcpyAsync(score + (size_t)u0 * k, out_v.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipMemcpyAsync(h_idx.data(), out_i.p, (size_t)(Uc * k) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    MFM_HIP_CHECK(hipStreamSynchronize(s));
-    for (int64_t e = 0; e < Uc * k; e++) idx[u0 * k + e] = h_idx[(size_t)e];
-  }
-  MFM_HIP_CHECK(hipStreamSynchronize(s));
-}
-
-}  // namespace
-
-extern "C" {
 
 int mfm_pairs_moments_vb(mfm_pairs *p, int32_t rank, double w0, double w0_var, const double *w, const double *w_var, const double *V,
                          const double *V_var, double extra_var, double *mean, double *sd) {
@@ -1601,10 +1504,8 @@ int mfm_pairs_moments_vb(mfm_pairs *p, int32_t rank, double w0, double w0_var, c
     return MFM_ERR_INVALID;
   }
   PAIRS_TRY(p)
-  if (!mean || !sd) throw Error(MFM_ERR_INVALID, "no output array");
-  PairsMoments mo;
-  mo.sd = sd;
-  run_pairs_vb(p, PairsVbHost{rank, w0, w0_var, extra_var, w, w_var, V, V_var}, 0, nullptr, nullptr, mean, mo);
+  const PairsRequest rq = checked_moments(0, mean, sd);
+  score_vb(p, PairsVbHost{rank, w0, w0_var, extra_var, w, w_var, V, V_var}, rq);
   PAIRS_CATCH(p)
 }
 
@@ -1616,8 +1517,8 @@ int mfm_pairs_topk_bound_vb(mfm_pairs *p, int32_t rank, double w0, double w0_var
     return MFM_ERR_INVALID;
   }
   PAIRS_TRY(p)
-  const PairsMoments mo = checked_ucb(k, beta, idx, value, mean, sd);
-  run_pairs_vb(p, PairsVbHost{rank, w0, w0_var, extra_var, w, w_var, V, V_var}, k, idx, value, nullptr, mo);
+  const PairsRequest rq = checked_ucb(0, k, beta, idx, value, mean, sd);
+  score_vb(p, PairsVbHost{rank, w0, w0_var, extra_var, w, w_var, V, V_var}, rq);
   PAIRS_CATCH(p)
 }
 

@@ -22,6 +22,8 @@
 #pragma once
 #include "mfm_common.hpp"
 
+#include <type_traits>
+
 namespace mfm {
 
 constexpr int PAIRS_WG = 256;        // 4 waves: the same query rows, side-by-side candidate columns
@@ -188,40 +190,41 @@ struct PairsPlanEntry;  // (mfm_pairs_samples.hpp)
 
 struct PairsArgs {
   // the contraction
-  const double *Pf, *Qf;                    // fragment-ordered embeddings: [rows / 16][p_stride or q_stride][64]
-  int64_t NK;                               // k-steps the contraction walks: S * KS4
-  int64_t p_stride, q_stride;               // k-steps between two row tiles of P and of Q (NK, but for a one-sample view of more)
-  int KS4, S;
+  const double *Pf = nullptr, *Qf = nullptr;      // fragment-ordered embeddings: [rows / 16][p_stride or q_stride][64]
+  int64_t NK = 0;                                 // k-steps the contraction walks: S * KS4
+  int64_t p_stride = 0, q_stride = 0;             // k-steps between two row tiles of P and of Q (NK, but for a one-sample view of more)
+  int KS4 = 0, S = 0;
   // the finish of a value
-  const double *Ab, *Asum, *Bb, *Bsum;      // biases: [S][Upad], [Upad], [S][Ipad], [Ipad]
-  const double *w0s;                        // [S]
-  double w0sum;
-  const double *cut;                        // [S][n_cut]: the samples' cutpoints (MODE 2)
-  int n_cut;
-  double beta;                              // the moments form ranks by mean + beta * std
+  const double *Ab = nullptr, *Asum = nullptr, *Bb = nullptr, *Bsum = nullptr;  // biases: [S][Upad], [Upad], [S][Ipad], [Ipad]
+  const double *w0s = nullptr;                    // [S]
+  double w0sum = 0.0;
+  const double *cut = nullptr;                    // [S][n_cut]: the samples' cutpoints (MODE 2)
+  int n_cut = 0;
+  double beta = 0.0;                              // the moments form ranks by mean + beta * std
   // the grid's share of the pairs
-  int64_t Upad, Ipad, Uc, I;                // the chunk's padded / valid query rows, the padded / valid candidates
-  int64_t stripe_len;                       // candidates per stripe, a multiple of the workgroup step
+  int64_t Upad = 0, Ipad = 0, Uc = 0, I = 0;      // the chunk's padded / valid query rows, the padded / valid candidates
+  int64_t stripe_len = 0;                         // candidates per stripe, a multiple of the workgroup step
   // dense forms
-  double *dense;                            // [Uc][I]: the value (the moments form: the mean)
-  double *dense_std;                        // [Uc][I]: the moments form's second output
+  double *dense = nullptr;                        // [Uc][I]: the value (the moments form: the mean)
+  double *dense_std = nullptr;                    // [Uc][I]: the moments form's second output
   // selecting forms
-  const uint32_t *mask;                     // [Uc][W] or null: the exclusions (the counting rank form reads it too)
-  int64_t W;
-  int k;
-  double *list_v;                           // [stripes][Upad][k]: each stripe's best k per row, in order, padded (-inf, -1)
-  int32_t *list_i;
+  const uint32_t *mask = nullptr;                 // [Uc][W] or null: the exclusions (the counting rank form reads it too)
+  int64_t W = 0;
+  int k = 0;
+  double *list_v = nullptr;                       // [stripes][Upad][k]: each stripe's best k per row, in order, padded (-inf, -1)
+  int32_t *list_i = nullptr;
   // rank form (mfm_pairs_rank.hpp)
-  const int64_t *tptr;                      // the targets: CSR over ALL query rows, indexed u0 + row
-  const int32_t *tidx;
-  double *tval;                             // [the chunk's targets]: entry tptr[u0 + row] - tbase + t, the target's value
-  int32_t *trank;                           // [the chunk's targets]: its rank, zeroed per chunk
-  int64_t u0, tbase;                        // the chunk's first query row and tptr[u0]
+  const int64_t *tptr = nullptr;                  // the targets: CSR over ALL query rows, indexed u0 + row
+  const int32_t *tidx = nullptr;
+  double *tval = nullptr;                         // [the chunk's targets]: entry tptr[u0 + row] - tbase + t, the target's value
+  int32_t *trank = nullptr;                       // [the chunk's targets]: its rank, zeroed per chunk
+  int64_t u0 = 0, tbase = 0;                      // the chunk's first query row and tptr[u0]
   // per-sample selecting form (mfm_pairs_samples.hpp)
-  const PairsPlanEntry *plan;               // the launch's entries, one per blockIdx.x
-  const int32_t *row_of;                    // [P rows] or null: the chunk's query row of a row of P (the row -> sample plan)
-  int64_t list_rows;                        // rows of one stripe's lists
+  const PairsPlanEntry *plan = nullptr;           // the launch's entries, one per blockIdx.x
+  const int32_t *row_of = nullptr;                // [P rows] or null: the chunk's query row of a row of P (the row -> sample plan)
+  int64_t list_rows = 0;                          // rows of one stripe's lists
 };
+static_assert(std::is_trivially_copyable<PairsArgs>::value, "PairsArgs is a kernel argument");
 
 // ---- the contraction -------------------------------------------------------------------------------------------------------
 // A workgroup owns MT * 16 query rows (from q0) and walks candidates in steps of 4 * NT * 16; wave w accumulates the MT x NT tiles
