@@ -782,6 +782,26 @@ int mfm_pairs_topk_sim_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t
 int mfm_pairs_topk_sim(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                        int32_t metric, int32_t k, double beta, int64_t *idx, double *value, double *mean, double *std);
 
+/* ---- the diversified top-k (csrc/mfm_pairs_diverse.hpp) -------------------------------------------------------------
+ * Greedy maximal marginal relevance over the head of mfm_pairs_topk's list. Per query row, with the pool = mfm_pairs_topk's list of
+ * length `pool` for the same mode and exclusions (bit for bit; n_live its entries with index >= 0, v_0 >= ... their values),
+ *   rel_j     = (v_j - v_min) / (v_0 - v_min), v_min the last live value; every rel_j = 1 where v_0 == v_min,
+ *   sim(i, j) = (1 / S) sum_s c_s(i, j), c_s the per-sample cosine of the section above between the CANDIDATE rows i and j (a zero
+ *               embedding gives 0); w0, w and the task play no part in it,
+ *   step 0 takes pool position 0; step t >= 1 the unchosen live position j of largest
+ *   g_t(j) = lam rel_j - (1 - lam) max over the chosen c of sim(j, c), ties to the lower pool position.
+ *   topk_diverse: idx, value, objective, redundancy [U * k] row-major; per step the chosen candidate, its value (the pool's, bit for bit),
+ *          g_t of the pick (step 0: lam rel_0) and the max-sim term (step 0: 0). Steps t >= n_live: idx -1, value -inf, objective and
+ *          redundancy NaN. lam = 1 returns mfm_pairs_topk's list of length k.
+ * A pre-normalised row-major copy of the candidate embedding (as large as the embedding) is resident for the call and counts in the
+ * memory rule. MFM_ERR_INVALID before any launch: NULL outputs, pool outside [1, MFM_PAIRS_DIVERSE_MAX_POOL], k outside [1, pool],
+ * lam outside [0, 1] or not finite, a similarity handle.                                                                           */
+#define MFM_PAIRS_DIVERSE_MAX_POOL 128
+int mfm_pairs_topk_diverse_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int32_t pool, double lam,
+                                 int64_t *idx, double *value, double *objective, double *redundancy);
+int mfm_pairs_topk_diverse(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t mode,
+                           int32_t k, int32_t pool, double lam, int64_t *idx, double *value, double *objective, double *redundancy);
+
 /* ---- folding new one-hot features into the kept samples (csrc/mfm_foldin.hip) ----------------------------------
  * U new entities (users or items that were not in the training table), each a new one-hot column with value 1 in its own
  * observations. X (n, D) holds the CONTEXT of the n observations in the model's feature space (not the new column), y their

@@ -24,6 +24,7 @@ from .estimators import (  # noqa: E402
     FOLD_IN_MAX_RANK,
     ChainDiagnostics,
     CrpsScore,
+    DiverseRanking,
     LikelihoodDiagnostics,
     LooCrps,
     LooDensity,
@@ -62,6 +63,7 @@ __all__ = [
     "PairSummary",
     "RankedSummary",
     "ScreenedRanking",
+    "DiverseRanking",
     "ScoreMoments",
     "TargetRanks",
     "PointwiseDensity",

@@ -45,6 +45,7 @@ SYMBOLS = [
     "mfm_pairs_set_targets", "mfm_pairs_rank_store", "mfm_pairs_rank",
     "mfm_pairs_topk_samples_store", "mfm_pairs_topk_samples", "mfm_pairs_topk_prob_store", "mfm_pairs_topk_prob",
     "mfm_pairs_create_sim", "mfm_pairs_sim_store", "mfm_pairs_sim", "mfm_pairs_topk_sim_store", "mfm_pairs_topk_sim",
+    "mfm_pairs_topk_diverse_store", "mfm_pairs_topk_diverse",
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
@@ -61,6 +62,12 @@ SYMBOLS = [
 
 SIM_METRICS = {"cosine": 0, "dot": 1}  # (MFM_PAIRS_SIM_* of myfm_hip.h)
 PAIRS_VOTE_MAX = 32768  # (MFM_PAIRS_VOTE_MAX of myfm_hip.h: samples * k of a topk_prob call)
+DIVERSE_MAX_POOL = 128  # (MFM_PAIRS_DIVERSE_MAX_POOL of myfm_hip.h)
+
+
+def diverse_pool(k):
+    """the default pool of a diversified top-k of k picks"""
+    return min(DIVERSE_MAX_POOL, max(4 * int(k), 32))
 
 # a record of mfm_chain_stream_info / mfm_cs_plan_probe (MFM_CHAIN_STREAM_INFO_FIELDS of include/myfm_hip.h)
 CHAIN_STREAM_INFO = ("block", "n_cols", "n_steps", "Cg", "Lw", "NB", "RD", "n_slots", "max_hot_col", "max_enter", "max_exit", "max_cold_sr",
@@ -235,6 +242,8 @@ def lib():
     L.mfm_pairs_sim.argtypes = [vp, i32, i32, P, P, P, i32, P, P]
     L.mfm_pairs_topk_sim_store.argtypes = [vp, vp, i32, i32, i32, i32, C.c_double, P, P, P, P]
     L.mfm_pairs_topk_sim.argtypes = [vp, i32, i32, P, P, P, i32, i32, C.c_double, P, P, P, P]
+    L.mfm_pairs_topk_diverse_store.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.c_double, P, P, P, P]
+    L.mfm_pairs_topk_diverse.argtypes = [vp, i32, i32, P, P, P, i32, i32, i32, C.c_double, P, P, P, P]
     L.mfm_pairs_destroy.argtypes = [vp]
     L.mfm_pairs_destroy.restype = None
     L.mfm_pairs_last_error.restype = C.c_char_p
@@ -1273,6 +1282,23 @@ class Pairs:
 
     def topk_sim_store(self, store, k, metric="cosine", beta=0.0, first=0, count=None):
         return self._topk_sim(_resident(store, first, count), k, metric, beta)
+
+    # ---- the diversified top-k: greedy relevance minus redundancy over the top `pool` of topk
+    def _topk_diverse(self, src, k, lam, pool, mode):
+        pool = diverse_pool(k) if pool is None else int(pool)
+        kk = max(int(k), 1)
+        idx, val, obj, red = np.empty((self.U, kk), dtype=np.int64), np.empty((self.U, kk)), np.empty((self.U, kk)), np.empty((self.U, kk))
+        self._ck(src.call("mfm_pairs_topk_diverse", self.h, mode, int(k), pool, float(lam), _p(idx), _p(val), _p(obj), _p(red)))
+        return idx, val, obj, red
+
+    def topk_diverse(self, samples, k, lam=0.7, pool=None, mode=0):
+        """(indices int64 (U, k), value, objective, redundancy (U, k)): k greedy picks out of topk(samples, pool, mode) by
+        lam * relevance - (1 - lam) * (largest mean cosine with the picks so far). pool None: min(128, max(4 k, 32)).
+        Steps past the live pool entries: -1 / -inf / NaN / NaN."""
+        return self._topk_diverse(_host(samples), k, lam, pool, mode)
+
+    def topk_diverse_store(self, store, k, lam=0.7, pool=None, mode=0, first=0, count=None):
+        return self._topk_diverse(_resident(store, first, count), k, lam, pool, mode)
 
     # ---- the rank form (DESIGN 4.13.2)
     def rank(self, samples, mode=0):

@@ -952,6 +952,22 @@ struct Predictor {
                      mean.mutable_data(), sd.mutable_data()));
     return py::make_tuple(idx, value, mean, sd);
   }
+  // ---- the diversified top-k: (indices, value, objective, redundancy), each (U, k): k greedy picks out of
+  // predict_topk's first `pool` by lam * relevance - (1 - lam) * the largest mean cosine with the picks so far
+  py::tuple predict_topk_diverse(const py::object &Xqo, const py::object &Xco, int64_t k, double lam, int64_t pool, const py::object &excludeo,
+                                 const py::object &rqo, const py::object &rco) const {
+    if (pool < 1 || pool > MFM_PAIRS_DIVERSE_MAX_POOL) throw std::invalid_argument("pool must be in [1, 128]");
+    if (k < 1 || k > pool) throw std::invalid_argument("k must be in [1, pool]");
+    if (!(lam >= 0.0 && lam <= 1.0)) throw std::invalid_argument("lam must be a finite number in [0, 1]");
+    PairCall pc = pair_call(Xqo, Xco, rqo, rco);
+    pc.ranked(k, excludeo);
+    py::array_t<int64_t> idx({pc.U(), (py::ssize_t)k});
+    py::array_t<double> value({pc.U(), (py::ssize_t)k}), objective({pc.U(), (py::ssize_t)k}), redundancy({pc.U(), (py::ssize_t)k});
+    const DevicePairs dp = pc.open();
+    dp.ck(on_samples(mfm_pairs_topk_diverse_store, mfm_pairs_topk_diverse, dp.p, pc.mode, (int)k, (int)pool, lam, idx.mutable_data(),
+                     value.mutable_data(), objective.mutable_data(), redundancy.mutable_data()));
+    return py::make_tuple(idx, value, objective, redundancy);
+  }
   // ---- ranking under each kept sample
   // (indices (S, U, k), value (S, U, k)): every sample's own list
   py::tuple predict_topk_samples(const py::object &Xqo, const py::object &Xco, int64_t k, const py::object &excludeo, const py::object &rqo,
@@ -3314,6 +3330,8 @@ PYBIND11_MODULE(_myfm, m) {
            py::arg("X_rel_a") = py::tuple(), py::arg("X_rel_b") = py::tuple())
       .def("predict_similar", &Predictor::predict_similar, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("metric") = "cosine",
            py::arg("beta") = 0.0, py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
+      .def("predict_topk_diverse", &Predictor::predict_topk_diverse, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("lam"),
+           py::arg("pool"), py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk_samples", &Predictor::predict_topk_samples, py::arg("X_query"), py::arg("X_cand"), py::arg("k"),
            py::arg("exclude") = py::none(), py::arg("X_rel_query") = py::tuple(), py::arg("X_rel_cand") = py::tuple())
       .def("predict_topk_thompson", &Predictor::predict_topk_thompson, py::arg("X_query"), py::arg("X_cand"), py::arg("k"), py::arg("row_sample"),

@@ -29,7 +29,11 @@
 // The screened top-k (mfm_pairs_topk_screened*, mfm_pairs_screen_scores*; mfm_pairs_screen.hpp): mode 0's list through a
 // bf16 contraction, an exact rescoring of its shortlist and a per-row certificate (run_screened below); a bf16 copy of Q is resident
 // next to Q and counts in the memory rule.
+// The diversified top-k (mfm_pairs_topk_diverse*; mfm_pairs_diverse.hpp): the mean forms' top-k of length `pool` per
+// query chunk, left on the device, and greedy maximal marginal relevance over it (run_diverse below); a row-major, pre-normalised
+// copy of Q is resident next to Q for the call and counts in the memory rule.
 #include "mfm_pairs.hpp"
+#include "mfm_pairs_diverse.hpp"
 #include "mfm_pairs_rank.hpp"
 #include "mfm_pairs_samples.hpp"
 #include "mfm_pairs_screen.hpp"
@@ -128,7 +132,8 @@ enum PairsAsk {
   ASK_SCREENED,      // mode 0's k best through the bf16 screen, certified per row
   ASK_SCREEN_DENSE,  // (U, I) screened values and the per-row bound
   ASK_SIM,           // (U, I) mean and std of the similarity
-  ASK_TOPK_SIM       // the k most similar by mean + beta * std
+  ASK_TOPK_SIM,      // the k most similar by mean + beta * std
+  ASK_DIVERSE        // k greedy picks by relevance minus redundancy out of the `pool` best
 };
 
 // One request: the form, its parameters and its outputs by name. The checked_* functions below build it, with the checks that need
@@ -141,6 +146,8 @@ struct PairsRequest {
   double beta = 0.0;                    // the ranked moments forms rank by mean + beta * std
   const int32_t *row_sample = nullptr;  // ASK_SAMPLES, [U]: only the list of row u's own sample, outputs [U][k]; null: every sample's, [S][U][k]
   int n_top = 0;                        // ASK_VOTE: idx / value are [U][n_top] indices / probabilities
+  int pool = 0;                         // ASK_DIVERSE: the picks come out of the top `pool` of the mean form
+  double lam = 0.0;                     // ASK_DIVERSE: g = lam * relevance - (1 - lam) * redundancy
   // the outputs
   double *dense = nullptr;                      // (U, I): the value, the moments forms' mean, the screen's r~
   int64_t *idx = nullptr;                       // the lists: (U, k), or as the per-sample forms lay them out
@@ -151,6 +158,10 @@ struct PairsRequest {
   double *target_value = nullptr;
   uint8_t *certified = nullptr;                 // ASK_SCREENED, [U]
   double *bound = nullptr;                      // ASK_SCREEN_DENSE, [U]: E_u
+  double *objective = nullptr;                  // ASK_DIVERSE, (U, k): g of each pick
+  double *redundancy = nullptr;                 // ASK_DIVERSE, (U, k): the pick's largest similarity with the picks before it
+
+  int list_k() const { return ask == ASK_DIVERSE ? pool : k; }  // the length of the lists the tile kernel selects
 
   bool dense_form() const { return ask == ASK_SCORES || ask == ASK_MOMENTS || ask == ASK_SCREEN_DENSE || ask == ASK_SIM; }
   bool spread() const { return ask == ASK_MOMENTS || ask == ASK_UCB || sim(); }
@@ -320,7 +331,7 @@ PairsForm pairs_sim_form_of() {
 // finish and take the moments forms' shapes.
 PairsForm pairs_form(const PairsRequest &rq) {
   const bool dense = rq.dense_form();
-  const int k = rq.k;
+  const int k = rq.list_k();
   if (rq.sim()) {
     if (dense) return pairs_sim_form_of<2, 2, PAIRS_DENSE>();
     if (k <= 64) return pairs_sim_form_of<4, 1, PAIRS_SELECT>();
@@ -670,6 +681,95 @@ void run_screened(mfm_pairs *p, const PairsArgs &call, const PairsRequest &rq, E
   MFM_HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// ---- the diversified top-k (mfm_pairs_diverse.hpp) ---------------------------------------------------------------
+// the row-major pre-normalised copy of Q: what a diversified call keeps resident beyond a plain one (valid candidates only)
+double diverse_q_bytes(int64_t I, int64_t NK) { return (double)I * (double)div_padded_length(NK * 4) * sizeof(double); }
+
+// The queries in chunks against the resident candidate side of `call` (call.k = the pool length M; `form`: the mean form that
+// mfm_pairs_topk takes for k = M). Once, before the first chunk: k_div_pack. Per chunk: embed P, the form's launch and the merge exactly
+// as walk_queries queues them for a top-k of M -- the pool, which stays on the device --, then k_div_select, one workgroup per query
+// row, and the download of the k picks. Scratch per query row: walk_queries' selecting terms with M for k, plus the four outputs.
+// Qh lives for this call alone and is freed when it returns.
+template <class Embed>
+void run_diverse(mfm_pairs *p, const PairsForm &form, const PairsArgs &call, const PairsRequest &rq, Embed embed) {
+  hipStream_t s = p->stream;
+  const int S = call.S, KS = call.KS4 * 4, M = rq.pool, k = rq.k;
+  const int64_t U = p->U, I = call.I, W = call.W, L = call.NK * 4, Lpad = div_padded_length(L);
+  const double per_row = (double)S * KS * 8 + (double)(S + 1) * 8 + (p->has_exclude ? (double)W * 4 : 0.0) +
+                         (double)(PAIRS_MAX_STRIPES + 1) * M * 12 + (double)k * 28;
+  const int64_t chunk = chunk_rows(p->scratch_bound, per_row, U);
+  const int64_t steps_total = candidate_steps(I, form.step());
+
+  DevBuf<double> Qh;
+  Qh.alloc((size_t)std::max<int64_t>(I * Lpad, 1));
+  if (I > 0 && L > 0) {
+    hipLaunchKernelGGL(k_div_pack, dim3((unsigned)((I + PAIRS_WG - 1) / PAIRS_WG), (unsigned)S), dim3(PAIRS_WG), 0, s, call.Qf, call.NK, call.KS4,
+                       S, I, Lpad, Qh.p);
+    MFM_HIP_CHECK(hipGetLastError());
+  }
+  const size_t lds = div_lds_bytes((int)round_up(M, 16));
+  static DeviceOnce raised;
+  if (lds > 48 * 1024 && raised.need()) {
+    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)k_div_select, hipFuncAttributeMaxDynamicSharedMemorySize, (int)div_lds_bytes(DIV_MAX_POOL)));
+    raised.mark();
+  }
+
+  QueryRows q;
+  DevBuf<double> list_v, pool_v, out_v, out_g, out_r;
+  DevBuf<int32_t> list_i, pool_i, out_i;
+  DevBuf<uint32_t> mask;
+  std::vector<int32_t> h_idx;
+  for (int64_t u0 = 0; u0 < U; u0 += chunk) {
+    const int64_t Uc = std::min(chunk, U - u0), Upad = round_up(Uc, PAIRS_ROW_ALIGN);
+    ensure(q.Pf, (size_t)(Upad * call.NK * 4));
+    ensure(q.Ab, (size_t)(Upad * S));
+    ensure(q.Asum, (size_t)Upad);
+    embed(0, u0, Uc, Upad, q.Pf.p, q.Ab.p);
+    hipLaunchKernelGGL(k_pairs_bias_sum, dim3((unsigned)((Upad + PAIRS_WG - 1) / PAIRS_WG)), dim3(PAIRS_WG), 0, s, q.Ab.p, S, Upad, q.Asum.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    const int64_t n_qt = Upad / form.rows();
+    const Stripes stripes = split_stripes(n_qt, steps_total);
+    const int64_t n_stripes = stripes.n;
+    PairsArgs a = chunk_args(call, q, u0, Uc, Upad, stripes.steps * form.step(), chunk_mask(p, mask, u0, Uc, W));
+    ensure(list_v, (size_t)(n_stripes * Upad * M));
+    ensure(list_i, (size_t)(n_stripes * Upad * M));
+    ensure(pool_v, (size_t)(Uc * M));
+    ensure(pool_i, (size_t)(Uc * M));
+    a.list_v = list_v.p;
+    a.list_i = list_i.p;
+    if (I > 0) {
+      form.launch(s, dim3((unsigned)n_qt, (unsigned)n_stripes), a, rq.mode);
+      MFM_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pairs_merge, dim3((unsigned)Uc), dim3(PAIRS_WG), 0, s, list_v.p, list_i.p, I > 0 ? (int)n_stripes : 0, Upad, M, pool_v.p,
+                       pool_i.p);
+    MFM_HIP_CHECK(hipGetLastError());
+    ensure(out_i, (size_t)(Uc * k));
+    ensure(out_v, (size_t)(Uc * k));
+    ensure(out_g, (size_t)(Uc * k));
+    ensure(out_r, (size_t)(Uc * k));
+    DivArgs da;
+    da.Qh = Qh.p;
+    da.Lpad = Lpad;
+    da.pool_v = pool_v.p;
+    da.pool_i = pool_i.p;
+    da.M = M;
+    da.k = k;
+    da.S = S;
+    da.lam = rq.lam;
+    da.out_i = out_i.p;
+    da.out_v = out_v.p;
+    da.out_g = out_g.p;
+    da.out_r = out_r.p;
+    hipLaunchKernelGGL(k_div_select, dim3((unsigned)Uc), dim3(PAIRS_WG), lds, s, da);
+    MFM_HIP_CHECK(hipGetLastError());
+    MFM_HIP_CHECK(hipMemcpyAsync(rq.objective + (size_t)u0 * k, out_g.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    MFM_HIP_CHECK(hipMemcpyAsync(rq.redundancy + (size_t)u0 * k, out_r.p, (size_t)(Uc * k) * sizeof(double), hipMemcpyDeviceToHost, s));
+    download_list(s, h_idx, out_v.p, out_i.p, Uc, k, u0, rq.value, rq.idx);
+  }
+  MFM_HIP_CHECK(hipStreamSynchronize(s));
+}
+
 // ---- the query walk that the sample forms and the variational forms share --------------------------------------------------------
 // The queries in chunks against the resident candidate side of `call`. Per chunk: embed P (and sum its biases where the candidate
 // side has sums), then what the form does with a value -- the targets' values and ranks (a chunk without targets launches nothing);
@@ -798,7 +898,7 @@ PairsArgs embed_candidates(mfm_pairs *p, const PairsDims &d, const PairsRequest 
   call.Ipad = d.Ipad;
   call.I = p->I;
   call.W = d.W;
-  call.k = rq.k;
+  call.k = rq.list_k();
   return call;
 }
 
@@ -842,7 +942,8 @@ void run_pairs(mfm_pairs *p, const SampleView &v, const PairsRequest &rq) {
 
   // ---- the memory rule: Q and every block table resident, the query scratch bounded
   const double q_bytes =
-      ((double)d.Ipad * S * KS + (double)d.Ipad * (S + 1)) * sizeof(double) + (rq.screened() ? screen_q_bytes(d.Ipad, d.NK) : 0.0);
+      ((double)d.Ipad * S * KS + (double)d.Ipad * (S + 1)) * sizeof(double) + (rq.screened() ? screen_q_bytes(d.Ipad, d.NK) : 0.0) +
+      (rq.ask == ASK_DIVERSE ? diverse_q_bytes(I, d.NK) : 0.0);
   double t_bytes[2] = {0.0, 0.0};
   for (int side = 0; side < 2; side++)
     for (auto &b : p->blocks[side]) t_bytes[side] += (double)b->M * S * (KS + 2) * sizeof(double);
@@ -935,6 +1036,8 @@ void run_pairs(mfm_pairs *p, const SampleView &v, const PairsRequest &rq) {
     walk_samples(p, form, call, rq, embed);
   else if (rq.screened())
     run_screened(p, call, rq, embed);
+  else if (rq.ask == ASK_DIVERSE)
+    run_diverse(p, form, call, rq, embed);
   else
     walk_queries(p, form, call, rq, embed, [&](const PairsArgs &a, const int32_t *out_i, int64_t n, double *mean, double *sd) {
       launch_moments_at(s, a, mode, form.sim, out_i, n, mean, sd);
@@ -1185,6 +1288,25 @@ PairsRequest checked_screen_dense(const mfm_pairs *p, double *r, double *bound) 
   return rq;
 }
 
+static_assert(DIV_MAX_POOL == MFM_PAIRS_DIVERSE_MAX_POOL, "the pool's limit as the header states it");
+
+PairsRequest checked_diverse(int mode, int k, int pool, double lam, int64_t *idx, double *value, double *objective, double *redundancy) {
+  if (!idx || !value || !objective || !redundancy) throw Error(MFM_ERR_INVALID, "no output array");
+  if (pool < 1 || pool > DIV_MAX_POOL) throw Error(MFM_ERR_INVALID, "pool must be in [1, 128]");
+  if (k < 1 || k > pool) throw Error(MFM_ERR_INVALID, "k must be in [1, pool]");
+  if (!(lam >= 0.0 && lam <= 1.0)) throw Error(MFM_ERR_INVALID, "lam must be a finite number in [0, 1]");
+  PairsRequest rq{ASK_DIVERSE};
+  rq.mode = mode;
+  rq.k = k;
+  rq.pool = pool;
+  rq.lam = lam;
+  rq.idx = idx;
+  rq.value = value;
+  rq.objective = objective;
+  rq.redundancy = redundancy;
+  return rq;
+}
+
 // ---- where a call's samples come from: all that the _store and the host twin of a form differ in ---------------------------------
 struct FromStore {
   mfm_store *st;
@@ -1419,6 +1541,17 @@ int mfm_pairs_topk_screened_store(mfm_pairs *p, mfm_store *st, int32_t first, in
 int mfm_pairs_topk_screened(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t k,
                             int64_t *idx, double *value, uint8_t *certified) {
   return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs}, [&] { return checked_screened(k, idx, value, certified); });
+}
+
+int mfm_pairs_topk_diverse_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, int32_t mode, int32_t k, int32_t pool, double lam,
+                                 int64_t *idx, double *value, double *objective, double *redundancy) {
+  return pairs_call(p, FromStore{st, first, count}, [&] { return checked_diverse(mode, k, pool, lam, idx, value, objective, redundancy); });
+}
+
+int mfm_pairs_topk_diverse(mfm_pairs *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t mode,
+                           int32_t k, int32_t pool, double lam, int64_t *idx, double *value, double *objective, double *redundancy) {
+  return pairs_call(p, FromHost{rank, n_samples, w0s, ws, Vs},
+                    [&] { return checked_diverse(mode, k, pool, lam, idx, value, objective, redundancy); });
 }
 
 int mfm_pairs_screen_scores_store(mfm_pairs *p, mfm_store *st, int32_t first, int32_t count, double *r, double *bound) {

@@ -996,6 +996,43 @@ class _SimilarityMixin:
         return RankedSummary(*predictor.predict_similar(Xq, Xc, k, metric, beta, exclude, rq, rc))
 
 
+DIVERSE_MAX_POOL = 128  # (MFM_PAIRS_DIVERSE_MAX_POOL of the device code: a query's Gram matrix lives in the device's local memory)
+DiverseRanking = namedtuple("DiverseRanking", ["indices", "value", "objective", "redundancy"])
+
+
+class _DiverseRankingMixin:
+    """A slate instead of k near-copies: greedy maximal marginal relevance (Carbonell & Goldstein 1998) over the
+    head of predict_topk's list, for the estimators that keep S posterior samples. Per query, with the pool = predict_topk(X_query,
+    X_cand, pool, exclude) bit for bit, v_0 >= ... its live values and v_min the last of them,
+
+        rel_j = (v_j - v_min) / (v_0 - v_min) (1 where v_0 == v_min),   sim(i, j) = the mean over the kept samples of the
+        per-sample cosine of _SimilarityMixin between the candidate rows i and j (0 for a zero embedding);
+
+    step 0 takes the pool's head, step t >= 1 the unchosen pool entry j of largest g_t(j) = lam * rel_j - (1 - lam) * max over the
+    chosen c of sim(j, c), ties to the earlier pool position. The pool, the pool's Gram matrix and the greedy steps stay on the
+    device: neither the (U, I) nor the (I, I) matrix is built. Not covered: the variational estimators, row-sharded operation,
+    the dot metric, pools above 128. The arguments are validated on the host before the device is touched."""
+
+    def predict_topk_diverse(self, X_query, X_cand, k: int, lam: float = 0.7, pool: Optional[int] = None, exclude=None, X_rel_query=[],
+                             X_rel_cand=[]):
+        """DiverseRanking(indices int64 (U, k), value, objective, redundancy (U, k)): per step the chosen candidate, its
+        predict_topk value (bit for bit), g_t of the pick (step 0: lam * rel_0) and its largest similarity with the picks before it
+        (step 0: 0). Steps past the pool's live entries: index -1, value -inf, objective and redundancy NaN. lam = 1 returns
+        predict_topk(k). pool defaults to min(128, max(4 k, 32)); 1 <= k <= pool <= 128 and a finite lam in [0, 1], else
+        ValueError. `exclude` as in predict_topk."""
+        predictor, Xq, Xc, rq, rc = self._pair_sides(X_query, X_cand, X_rel_query, X_rel_cand)
+        k, _, exclude = _ranked_args(Xq, Xc, k, exclude)
+        if isinstance(lam, (bool, np.bool_)) or not isinstance(lam, (int, float, np.integer, np.floating)) or not 0.0 <= lam <= 1.0:
+            raise ValueError("lam must be a finite number in [0, 1]")
+        if pool is None:
+            pool = min(DIVERSE_MAX_POOL, max(4 * k, 32))
+        if isinstance(pool, (bool, np.bool_)) or not isinstance(pool, (int, np.integer)) or not 1 <= pool <= DIVERSE_MAX_POOL:
+            raise ValueError("pool must be an integer in [1, %d]" % DIVERSE_MAX_POOL)
+        if not 1 <= k <= pool:
+            raise ValueError("k must be an integer in [1, pool]")
+        return DiverseRanking(*predictor.predict_topk_diverse(Xq, Xc, k, float(lam), int(pool), exclude, rq, rc))
+
+
 def _fold_in_checked(est, name, X, y, entity, group, n_entities):
     """The host-side checks that fold_in and fold_in_gibbs share, in one order and with one set of messages (`name`: the calling
     method). Returns (predictor, D, K, X csr, y float64 (n,), entity int64 (n,), U, the hyper-parameters of the kept samples, group)."""
@@ -1174,7 +1211,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _ScreenedRankingMixin, _PairUncertaintyMixin, _SimilarityMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_PairScoringMixin, _ScreenedRankingMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -1242,7 +1279,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, _ScreenedRankingMixin, _PairUncertai
         return _folded_in(self, predictor.extended(w_new, V_new), D, U, g)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -1318,7 +1355,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""

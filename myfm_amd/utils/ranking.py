@@ -83,3 +83,16 @@ def neighbour_table(result, names=None, min_mean=None, max_std=None):
         at = np.flatnonzero(keep[u])
         table.append([(int(indices[u, j]) if names is None else names[int(indices[u, j])], float(mean[u, j]), float(std[u, j])) for j in at])
     return table
+
+
+def intra_list_similarity(result_or_indices, sim):
+    """Per query the mean of sim[i, j] over the unordered pairs of its list: (U,) floats, NaN where a list holds fewer than two
+    candidates. result_or_indices: a DiverseRanking (or any tuple whose first entry is the (U, k) index array) or that array itself,
+    padding entries (index -1) left out; sim: an (I, I) array of candidate similarities, e.g. predict_similarity(X_cand).mean."""
+    idx = np.asarray(result_or_indices[0] if isinstance(result_or_indices, tuple) else result_or_indices)
+    sim, out = np.asarray(sim, dtype=np.float64), np.full(idx.shape[0], np.nan)
+    for u in range(idx.shape[0]):
+        c = idx[u][idx[u] >= 0]
+        if c.size >= 2:
+            out[u] = sim[np.ix_(c, c)][np.triu_indices(c.size, 1)].mean()
+    return out
