@@ -855,6 +855,35 @@ int mfm_foldin_gibbs_solve(mfm_foldin *p, int32_t rank, int32_t n_samples, const
                            int32_t task, int32_t n_class, const double *cutpoints, const double *mu, const double *lambda,
                            int32_t n_burn, int32_t n_inner, int32_t draw, uint64_t seed, double *w_new, double *V_new);
 
+/* ---- aligned factor embeddings: orthogonal Procrustes over the kept samples (csrc/mfm_align.hip) -----------------------
+ * The FM score is invariant under V -> R^T V for any orthogonal R, so the kept samples' factors differ by rotations and reflections
+ * and their plain mean means nothing. With V_s the (K, D) factor-major matrix of sample s, c the column weights (NULL: all ones)
+ * and ref = V_reference in round 0, the mean of the round before in each of the n_refine further rounds, a round computes
+ *   M_s[a][b] = sum_d c_d V_s[a][d] ref[b][d],    R_s = U W^T with M_s = U Sigma W^T (the maximiser of tr(R^T M_s) over the full
+ *   orthogonal group, reflections included),      Y_s[b][d] = sum_a R_s[a][b] V_s[a][d],
+ *   mean, std = the mean and the population standard deviation over s of Y_s (Welford in sample order).
+ * The outputs are those of the last round: mean, std [K][D] FACTOR-MAJOR (all D columns, whatever the weights), rotations [S][K][K]
+ * row-major, alignment[s] = sum_i sigma_i(M_s) / sqrt(|V_s|_c^2 |ref|_c^2) clamped to [0, 1] and 0 where a norm is 0 (|.|_c the
+ * c-weighted Frobenius norm): 1 for a rotated, scaled copy of the reference. A singular M_s (a zero factor, D < K) still gives an
+ * orthogonal R_s: columns of U with sigma <= 2^-36 sigma_max are completed from unit vectors in index order. Every sum has one
+ * order that depends on D and K alone (no atomics): two calls, a store and its host copy, and any scratch bound give the same bits.
+ * `reference` in [-S, S) (negative: from the end), n_refine in [0, 8], weights finite and >= 0, rank <= the value of
+ * mfm_align_max_rank() (64), S >= 1: else MFM_ERR_INVALID before any launch. Rank 0 writes alignment = 0 and launches nothing.
+ * The handle holds the device, the feature size and a stream. *_store reads samples [first, first + count) of a device store in
+ * place; the other takes host samples laid out as for the host-sample prediction entry point (w0s and ws are not read by the
+ * kernels). Scratch: the partial M_s of a group of samples (S_g ceil(D / 2048) K^2 doubles) stay under the scratch bound, 256 MB
+ * by default. The handle's last error: NULL for the last failed create of this thread.                                          */
+typedef struct mfm_aligner mfm_aligner;
+int mfm_align_create(int device, int64_t D, mfm_aligner **out);
+void mfm_align_destroy(mfm_aligner *p);
+const char *mfm_align_last_error(const mfm_aligner *p);
+int mfm_align_set_scratch_bound(mfm_aligner *p, int64_t bytes);
+int mfm_align_max_rank(void);
+int mfm_align_store(mfm_aligner *p, mfm_store *st, int32_t first, int32_t count, int32_t reference, int32_t n_refine,
+                    const double *weights, double *mean, double *std, double *rotations, double *alignment);
+int mfm_align(mfm_aligner *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs, int32_t reference,
+              int32_t n_refine, const double *weights, double *mean, double *std, double *rotations, double *alignment);
+
 /* FM::predict_score of the LIVE sample (the FM* handed to the per-iteration callback,
  * FMTrainer.hpp:78; utils/callbacks/libfm.py:85): scores design `d` with the (w0, w, V) currently
  * resident in training context `ctx` -- no download / upload of the model state. Same device only.  */

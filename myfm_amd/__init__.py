@@ -25,6 +25,8 @@ from .estimators import (  # noqa: E402
     ChainDiagnostics,
     CrpsScore,
     DiverseRanking,
+    ALIGN_MAX_RANK,
+    AlignedFactors,
     LikelihoodDiagnostics,
     LooCrps,
     LooDensity,
@@ -64,6 +66,8 @@ __all__ = [
     "RankedSummary",
     "ScreenedRanking",
     "DiverseRanking",
+    "ALIGN_MAX_RANK",
+    "AlignedFactors",
     "ScoreMoments",
     "TargetRanks",
     "PointwiseDensity",

@@ -27,6 +27,7 @@ HIP_UNITS = {
     "mfm_foldin.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_foldin.hpp", "mfm_foldin_handle.hpp", "mfm_philox.hpp", "mfm_samples.hpp"],
     "mfm_foldin_gibbs.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_foldin.hpp", "mfm_foldin_gibbs.hpp", "mfm_foldin_gibbs_plan.hpp",
                              "mfm_foldin_handle.hpp", "mfm_tn.hpp", "mfm_philox.hpp", "mfm_samples.hpp"],
+    "mfm_align.hip": ["mfm_env.hpp", "mfm_common.hpp", "mfm_align.hpp", "mfm_samples.hpp"],
 }
 OBJ_DIR = os.path.join(CSRC, "_obj")
 PYMOD_HEADERS = ["mfm_env.hpp", "mfm_hostnormals.hpp", "mfm_mtjump.hpp", "mfm_normal_quantile.hpp"]

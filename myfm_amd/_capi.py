@@ -48,6 +48,8 @@ SYMBOLS = [
     "mfm_pairs_topk_diverse_store", "mfm_pairs_topk_diverse",
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
+    "mfm_align_create", "mfm_align_destroy", "mfm_align_last_error", "mfm_align_set_scratch_bound", "mfm_align_max_rank",
+    "mfm_align_store", "mfm_align",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
     "mfm_design_logdens_store", "mfm_design_logdens", "mfm_logdens_value",
     "mfm_design_loo_store", "mfm_design_loo", "mfm_psis_row",
@@ -63,6 +65,8 @@ SYMBOLS = [
 SIM_METRICS = {"cosine": 0, "dot": 1}  # (MFM_PAIRS_SIM_* of myfm_hip.h)
 PAIRS_VOTE_MAX = 32768  # (MFM_PAIRS_VOTE_MAX of myfm_hip.h: samples * k of a topk_prob call)
 DIVERSE_MAX_POOL = 128  # (MFM_PAIRS_DIVERSE_MAX_POOL of myfm_hip.h)
+ALIGN_MAX_RANK = 64  # (mfm_align_max_rank(): a sample's K x K matrices live in the device's local memory)
+ALIGN_MAX_REFINE = 8
 
 
 def diverse_pool(k):
@@ -283,6 +287,15 @@ def lib():
     L.mfm_foldin_max_rank.argtypes = []
     L.mfm_foldin_solve_store.argtypes = [vp, vp, i32, i32, P, P, P, i32, u64, P, P]
     L.mfm_foldin_solve.argtypes = [vp, i32, i32, P, P, P, P, P, P, i32, u64, P, P]
+    L.mfm_align_create.argtypes = [C.c_int, i64, C.POINTER(vp)]
+    L.mfm_align_destroy.argtypes = [vp]
+    L.mfm_align_destroy.restype = None
+    L.mfm_align_last_error.restype = C.c_char_p
+    L.mfm_align_last_error.argtypes = [vp]
+    L.mfm_align_set_scratch_bound.argtypes = [vp, i64]
+    L.mfm_align_max_rank.argtypes = []
+    L.mfm_align_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, P, P, P]
+    L.mfm_align.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, P, P, P]
     L.mfm_foldin_gibbs_solve_store.argtypes = [vp, vp, i32, i32, i32, i32, P, P, P, i32, i32, i32, u64, P, P]
     L.mfm_foldin_gibbs_solve.argtypes = [vp, i32, i32, P, P, P, i32, i32, P, P, P, i32, i32, i32, u64, P, P]
     L.mfm_test_erfcx.argtypes = [C.c_int, P, i64, P]
@@ -1435,3 +1448,65 @@ class FoldIn:
 
     def solve_gibbs_store(self, store, mu, lam, task, cutpoints=None, n_burn=10, n_inner=40, draw=False, seed=0, first=0, count=None):
         return self._solve_gibbs(_resident(store, first, count), mu, lam, task, cutpoints, n_burn, n_inner, draw, seed)
+
+
+def align_args(S, K, D, reference, n_refine, weights):
+    """The host-side checks of an alignment call (ValueError), shared with the estimators: -> (reference in [0, S), n_refine,
+    weights float64 (D,) or None)."""
+    if S < 1:
+        raise ValueError("alignment needs at least one kept sample")
+    if K > ALIGN_MAX_RANK:
+        raise ValueError("aligned_factors serves ranks up to %d, this model has rank %d" % (ALIGN_MAX_RANK, K))
+    for name, v in (("reference", reference), ("n_refine", n_refine)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer" % name)
+    if not -S <= reference < S:
+        raise ValueError("reference %d is out of range for %d kept samples" % (reference, S))
+    if not 0 <= n_refine <= ALIGN_MAX_REFINE:
+        raise ValueError("n_refine must lie in [0, %d]" % ALIGN_MAX_REFINE)
+    if weights is not None:
+        weights = _f64(weights)
+        if weights.shape != (D,):
+            raise ValueError("weights must have shape (%d,)" % D)
+        if not np.all(np.isfinite(weights)) or np.any(weights < 0):
+            raise ValueError("weights must be finite and non-negative")
+    return int(reference) % S, int(n_refine), weights
+
+
+def align_result(mean_t, std_t, K, D):
+    """the library's factor-major (K, D) mean and std -> contiguous (D, K)"""
+    return np.ascontiguousarray(mean_t.reshape(K, D).T), np.ascontiguousarray(std_t.reshape(K, D).T)
+
+
+def _align(src, D, reference, n_refine, weights, device, scratch_bound):
+    S, K = src.S, src.K
+    reference, n_refine, weights = align_args(S, K, D, reference, n_refine, weights)
+    mean, std, rot, al = np.zeros((K, D)), np.zeros((K, D)), np.zeros((S, K, K)), np.zeros(S)
+    if K > 0:
+        L, h = lib(), C.c_void_p()
+        rc = L.mfm_align_create(device, D, C.byref(h))
+        if rc:
+            _raise(rc, L.mfm_align_last_error(None))
+        try:
+            if scratch_bound is not None:
+                rc = L.mfm_align_set_scratch_bound(h, int(scratch_bound))
+            rc = rc or src.call("mfm_align", h, reference, n_refine, _p(weights), _p(mean), _p(std), _p(rot), _p(al))
+            if rc:
+                _raise(rc, L.mfm_align_last_error(h))
+        finally:
+            L.mfm_align_destroy(h)
+    return align_result(mean, std, K, D) + (rot, al)
+
+
+def align(samples, reference=-1, n_refine=1, weights=None, device=0, scratch_bound=None):
+    """Orthogonal Procrustes alignment of host samples, a list of (w0, w[D], V[D, K]) (mfm_align): (mean (D, K),
+    std (D, K), rotations (S, K, K), alignment (S,)) of the last round. `scratch_bound`: bytes of partial cross products per group
+    of samples (default 256 MB; a small value makes a small problem cross the grouping)."""
+    if not len(samples):
+        raise ValueError("alignment needs at least one kept sample")
+    return _align(_host(samples), np.asarray(samples[0][2]).shape[0], reference, n_refine, weights, device, scratch_bound)
+
+
+def align_store(store, reference=-1, n_refine=1, weights=None, first=0, count=None, device=0, scratch_bound=None):
+    """align over the resident samples [first, first + count) of a Store, read in place (mfm_align_store)"""
+    return _align(_resident(store, first, count), store.D, reference, n_refine, weights, device, scratch_bound)

@@ -1104,6 +1104,50 @@ struct Predictor {
                                ordered ? cp.cuts.data() : nullptr, mu.data(), lam.data(), n_burn, n_inner, draw ? 1 : 0, seed,
                                c.w_new.mutable_data(), c.V_new.mutable_data()));
   }
+  // ---- one embedding per feature out of the kept samples (not in the reference; include/myfm_hip.h "aligned factor embeddings"):
+  // (mean (D, K), std (D, K), rotations (S, K, K), alignment (S,)). weights: None or (D,). Everything is checked here, on the host,
+  // before the device is looked for; rank 0 launches nothing.
+  py::tuple aligned_factors(int64_t reference, int64_t n_refine, const py::object &weightso) const {
+    const py::ssize_t S = (py::ssize_t)samples.size(), K = (py::ssize_t)rank, D = (py::ssize_t)feature_size;
+    if (S == 0) throw std::runtime_error("Told to predict but no sample available.");
+    if ((int)K > mfm_align_max_rank()) {
+      std::ostringstream ss;
+      ss << "aligned_factors serves ranks up to " << mfm_align_max_rank() << ", this model has rank " << K;
+      throw std::invalid_argument(ss.str());
+    }
+    if (reference < -S || reference >= S) throw std::invalid_argument("reference is out of range for the kept samples");
+    if (n_refine < 0 || n_refine > 8) throw std::invalid_argument("n_refine must lie in [0, 8]");
+    NpF64 weights;
+    const double *wp = nullptr;
+    if (!weightso.is_none()) {
+      weights = NpF64::ensure(weightso);
+      if (!weights || weights.ndim() != 1 || weights.shape(0) != D) throw std::invalid_argument("weights must be a float array of shape (D,)");
+      wp = weights.data();
+      for (py::ssize_t d = 0; d < D; d++)
+        if (!(wp[d] >= 0.0) || !std::isfinite(wp[d])) throw std::invalid_argument("weights must be finite and non-negative");
+    }
+    py::array_t<double> mean_t({K, D}), std_t({K, D}), rot({S, K, K}), al({S});
+    std::fill(al.mutable_data(), al.mutable_data() + S, 0.0);
+    if (K > 0) {
+      mfm_aligner *h = nullptr;
+      int code = mfm_align_create(selected_device(), (int64_t)D, &h);
+      if (code != MFM_OK) throw_code(code, mfm_align_last_error(nullptr));
+      std::unique_ptr<mfm_aligner, void (*)(mfm_aligner *)> guard(h, mfm_align_destroy);
+      code = on_samples(mfm_align_store, mfm_align, h, (int32_t)reference, (int32_t)n_refine, wp, mean_t.mutable_data(), std_t.mutable_data(),
+                        rot.mutable_data(), al.mutable_data());
+      if (code != MFM_OK) throw_code(code, mfm_align_last_error(h));
+    }
+    // the library's factor-major (K, D) -> (D, K)
+    py::array_t<double> mean({D, K}), std({D, K});
+    double *m = mean.mutable_data(), *sd = std.mutable_data();
+    const double *mt = mean_t.data(), *st = std_t.data();
+    for (py::ssize_t d = 0; d < D; d++)
+      for (py::ssize_t k = 0; k < K; k++) {
+        m[d * K + k] = mt[k * D + d];
+        sd[d * K + k] = st[k * D + d];
+      }
+    return py::make_tuple(mean, std, rot, al);
+  }
   // the predictor of feature size D + U whose sample s is this one's sample s with w and V extended by w_new[s], V_new[s] (host
   // samples: the restored-model path of every device predictor)
   Predictor extended(const NpF64 &w_new, const NpF64 &V_new) const {
@@ -3348,6 +3392,7 @@ PYBIND11_MODULE(_myfm, m) {
       .def("fold_in_gibbs_solve", &Predictor::fold_in_gibbs_solve, py::arg("X"), py::arg("y"), py::arg("offsets"), py::arg("fit_linear"),
            py::arg("mu"), py::arg("lam"), py::arg("cutpoint_index") = 0, py::arg("n_burn") = 10, py::arg("n_inner") = 40,
            py::arg("draw") = false, py::arg("seed") = 0)
+      .def("aligned_factors", &Predictor::aligned_factors, py::arg("reference") = -1, py::arg("n_refine") = 1, py::arg("weights") = py::none())
       .def("extended", &Predictor::extended, py::arg("w_new"), py::arg("V_new"))
       .def("predict_dist", &Predictor::predict_dist, py::arg("X"), py::arg("rels"), py::arg("quantiles"), py::arg("precisions") = py::none(),
            py::arg("tile_rows") = 0, py::arg("chunk_samples") = 0)

@@ -1033,6 +1033,52 @@ class _DiverseRankingMixin:
         return DiverseRanking(*predictor.predict_topk_diverse(Xq, Xc, k, float(lam), int(pool), exclude, rq, rc))
 
 
+ALIGN_MAX_RANK = 64  # (mfm_align_max_rank() of the device code: a sample's K x K matrices live in the device's local memory)
+
+
+class AlignedFactors(namedtuple("AlignedFactors", ["mean", "std", "rotations", "alignment"])):
+    """aligned_factors' result: mean, std (D, K), rotations (S, K, K), alignment (S,)"""
+
+    __slots__ = ()
+
+    def embed(self, X):
+        """X @ mean, an (N, K) array: the embedding of expanded rows X (scipy sparse, D columns) under the aligned mean factors"""
+        if not sps.issparse(X) or X.shape[1] != self.mean.shape[0]:
+            raise ValueError("X must be a scipy sparse matrix with %d columns" % self.mean.shape[0])
+        return np.asarray(sps.csr_matrix(X, dtype=REAL) @ self.mean)
+
+
+class _AlignedFactorsMixin:
+    """One embedding per feature with an error bar, for the estimators that keep S posterior samples. The FM score is
+    invariant under V -> V R for any orthogonal R, so the kept samples' factors differ by rotations and reflections and the mean of
+    V_samples is noise. Orthogonal Procrustes alignment: with V_s the (K, D) factors of sample s, c the column weights and
+    ref = V_reference in round 0, each round computes per sample
+
+        M_s = V_s diag(c) ref^T,   R_s = U W^T with M_s = U Sigma W^T (the orthogonal polar factor; reflections allowed),
+        Y_s = R_s^T V_s,           mean / std = the mean and the population standard deviation over s of Y_s,
+
+    and each of the n_refine further rounds takes ref = the mean of the round before (generalised Procrustes; n_refine = 0 is plain
+    alignment to one sample). The samples are read in place from the device store of a fresh fit, or uploaded (an unpickled model,
+    fold_in and combine_chains results). Not covered: the variational estimators, ranks above ALIGN_MAX_RANK, alignment across
+    differently fitted models. The linear weights w are rotation-invariant and not part of this. The arguments are validated on the
+    host before the device is touched."""
+
+    def aligned_factors(self, reference: int = -1, n_refine: int = 1, weights=None):
+        """AlignedFactors(mean (D, K), std (D, K), rotations (S, K, K), alignment (S,)) of the last round. reference: an index into
+        the kept samples, negative from the end. n_refine in [0, 8]. weights: None, or (D,) finite and non-negative: the rotation
+        is fitted on the weighted columns only (items only, say), mean and std still cover all D columns. alignment[s] =
+        sum_i sigma_i(M_s) / (|V_s|_c |ref|_c) in [0, 1]: 1 for a rotated, scaled copy of the reference, 0 where a norm is 0; a low
+        value flags a sample, or a chain, that sits elsewhere. Rank 0 returns empty arrays and alignment 0 without a launch."""
+        from ._capi import align_args
+
+        predictor = self._fetch_predictor()
+        S, K, D = len(predictor.samples), int(self.rank), int(predictor.feature_size)
+        if S == 0:
+            raise RuntimeError("Told to predict but no sample available.")
+        reference, n_refine, weights = align_args(S, K, D, reference, n_refine, weights)
+        return AlignedFactors(*predictor.aligned_factors(reference, n_refine, weights))
+
+
 def _fold_in_checked(est, name, X, y, entity, group, n_entities):
     """The host-side checks that fold_in and fold_in_gibbs share, in one order and with one set of messages (`name`: the calling
     method). Returns (predictor, D, K, X csr, y float64 (n,), entity int64 (n,), U, the hyper-parameters of the kept samples, group)."""
@@ -1211,7 +1257,7 @@ class MyFMGibbsBase(_FMEstimatorBase):
         return df
 
 
-class MyFMGibbsRegressor(_PairScoringMixin, _ScreenedRankingMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
+class MyFMGibbsRegressor(_AlignedFactorsMixin, _PairScoringMixin, _ScreenedRankingMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, MyFMGibbsBase):
     """Bayesian FM regression by Gibbs sampling (gibbs.py:145-240)."""
 
     _task_type = TaskType.REGRESSION
@@ -1279,7 +1325,7 @@ class MyFMGibbsRegressor(_PairScoringMixin, _ScreenedRankingMixin, _PairUncertai
         return _folded_in(self, predictor.extended(w_new, V_new), D, U, g)
 
 
-class MyFMGibbsClassifier(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMGibbsClassifier(_AlignedFactorsMixin, _PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM probit classification (gibbs.py:243-371)."""
 
     _task_type = TaskType.CLASSIFICATION
@@ -1355,7 +1401,7 @@ def _device_row_order(X):
     return _myfm.row_order_by_first_column(X.indptr, X.indices, X.shape[1])  # (stable counting sort)
 
 
-class MyFMOrderedProbit(_PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
+class MyFMOrderedProbit(_AlignedFactorsMixin, _PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
     """Bayesian FM ordinal regression (gibbs.py:374-543). predict_pairs / predict_topk rank by the posterior mean of the expected
     class index (see _PairScoringMixin). predict_proba_dist / predict_expected_dist give the posterior mean, standard deviation and
     quantiles of every class probability and of the expected class index over the kept samples."""
