@@ -833,6 +833,32 @@ int mfm_foldin_solve(mfm_foldin *p, int32_t rank, int32_t n_samples, const doubl
                      const double *alpha, const double *mu, const double *lambda, int32_t draw, uint64_t seed, double *w_new,
                      double *V_new);
 
+/* ---- ranking candidates under the new entities' own posterior (csrc/mfm_foldin_rank.hip) --------------------------
+ * On a handle of the create call above (regression's closed form only). The candidates are I context rows (I, D) in the model's
+ * feature space; pair (u, c) is the row X_cand[c] + e_u. With f_sc = score_s(X_cand[c]), z_sc = (1, q_s(X_cand[c])) (no leading 1
+ * with fit_linear = 0) and theta_us, Lambda_us the posterior mean and precision above,
+ *   m = f_sc + z_sc^T theta_us,  v = z_sc^T Lambda_us^-1 z_sc,  mean = 1/S sum_s m,  sd_within^2 = 1/S sum_s v,
+ *   sd^2 = sd_within^2 + 1/S sum_s (m - mean)^2,  gain = 1/S sum_s 1/2 log1p(alpha_s v)   (nats).
+ * _dist writes the four (U, I) arrays (U * I <= 2^24). _topk writes, per entity, the k best candidates (1 <= k <= 256) by
+ * value = mean + beta sd (by = 0) or gain (by = 1), value descending and index ascending, without the entity's row of the (U, I)
+ * exclusion pattern: idx, value, mean, sd, gain, each [U][k]; missing entries are -1, -inf and NaN. mean, sd and gain of a listed
+ * entry are recomputed and agree with value within rounding. set_candidates drops an exclusion pattern set before. The arguments
+ * are checked before the device is looked for; hyper-parameters, limits and errors as the solve entry points above; a result does
+ * not depend on U, I, the chunking or the scratch bound.                                                                        */
+int mfm_foldin_rank_set_candidates(mfm_foldin *p, int64_t I, const int64_t *indptr, const int32_t *indices, const double *data);
+int mfm_foldin_rank_set_exclude(mfm_foldin *p, const int64_t *indptr /*[U + 1]*/, const int32_t *indices);
+int mfm_foldin_rank_dist_store(mfm_foldin *p, mfm_store *st, int32_t first, int32_t count, const double *alpha, const double *mu,
+                               const double *lambda, double *mean, double *sd, double *sd_within, double *gain);
+int mfm_foldin_rank_dist(mfm_foldin *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                         const double *alpha, const double *mu, const double *lambda, double *mean, double *sd, double *sd_within,
+                         double *gain);
+int mfm_foldin_rank_topk_store(mfm_foldin *p, mfm_store *st, int32_t first, int32_t count, const double *alpha, const double *mu,
+                               const double *lambda, int32_t by, int32_t k, double beta, int64_t *idx, double *value, double *mean,
+                               double *sd, double *gain);
+int mfm_foldin_rank_topk(mfm_foldin *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
+                         const double *alpha, const double *mu, const double *lambda, int32_t by, int32_t k, double beta, int64_t *idx,
+                         double *value, double *mean, double *sd, double *gain);
+
 /* ---- the same for the probit tasks: a short Albert-Chib chain per (entity, sample) (csrc/mfm_foldin_gibbs.hip) ----
  * The handle is mfm_foldin_create's; its y holds the labels: +-1 for the classifier (task 0), class indices in [0, n_class) for
  * ordered probit (task 1; cutpoints[S][n_class - 1], the group's cutpoints of every sample; NULL and n_class ignored for task 0).

@@ -23,6 +23,8 @@ from ._myfm import RelationBlock  # noqa: E402
 from .estimators import (  # noqa: E402
     FOLD_IN_MAX_RANK,
     ChainDiagnostics,
+    ColdStartRanking,
+    ColdStartSummary,
     CrpsScore,
     DiverseRanking,
     ALIGN_MAX_RANK,
@@ -62,6 +64,8 @@ __all__ = [
     "VariationalFMRegressor",
     "VariationalFMClassifier",
     "FOLD_IN_MAX_RANK",
+    "ColdStartRanking",
+    "ColdStartSummary",
     "PairSummary",
     "RankedSummary",
     "ScreenedRanking",

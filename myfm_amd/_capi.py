@@ -48,6 +48,8 @@ SYMBOLS = [
     "mfm_pairs_topk_diverse_store", "mfm_pairs_topk_diverse",
     "mfm_foldin_create", "mfm_foldin_destroy", "mfm_foldin_last_error", "mfm_foldin_set_scratch_bound", "mfm_foldin_max_rank",
     "mfm_foldin_solve_store", "mfm_foldin_solve", "mfm_foldin_gibbs_solve_store", "mfm_foldin_gibbs_solve",
+    "mfm_foldin_rank_set_candidates", "mfm_foldin_rank_set_exclude", "mfm_foldin_rank_dist_store", "mfm_foldin_rank_dist",
+    "mfm_foldin_rank_topk_store", "mfm_foldin_rank_topk",
     "mfm_align_create", "mfm_align_destroy", "mfm_align_last_error", "mfm_align_set_scratch_bound", "mfm_align_max_rank",
     "mfm_align_store", "mfm_align",
     "mfm_design_summary_store", "mfm_design_summary", "mfm_design_summary_oprobit_store", "mfm_design_summary_oprobit",
@@ -287,6 +289,12 @@ def lib():
     L.mfm_foldin_max_rank.argtypes = []
     L.mfm_foldin_solve_store.argtypes = [vp, vp, i32, i32, P, P, P, i32, u64, P, P]
     L.mfm_foldin_solve.argtypes = [vp, i32, i32, P, P, P, P, P, P, i32, u64, P, P]
+    L.mfm_foldin_rank_set_candidates.argtypes = [vp, i64, P, P, P]
+    L.mfm_foldin_rank_set_exclude.argtypes = [vp, P, P]
+    L.mfm_foldin_rank_dist_store.argtypes = [vp, vp, i32, i32, P, P, P, P, P, P, P]
+    L.mfm_foldin_rank_dist.argtypes = [vp, i32, i32, P, P, P, P, P, P, P, P, P, P]
+    L.mfm_foldin_rank_topk_store.argtypes = [vp, vp, i32, i32, P, P, P, i32, i32, C.c_double, P, P, P, P, P]
+    L.mfm_foldin_rank_topk.argtypes = [vp, i32, i32, P, P, P, P, P, P, i32, i32, C.c_double, P, P, P, P, P]
     L.mfm_align_create.argtypes = [C.c_int, i64, C.POINTER(vp)]
     L.mfm_align_destroy.argtypes = [vp]
     L.mfm_align_destroy.restype = None
@@ -1423,6 +1431,54 @@ class FoldIn:
 
     def solve_store(self, store, alpha, mu, lam, draw=False, seed=0, first=0, count=None):
         return self._solve(_resident(store, first, count), alpha, mu, lam, draw, seed)
+
+    # ---- ranking candidates under the entities' own posterior (mfm_foldin_rank_*)
+    def set_candidates(self, X_cand):
+        """the candidate contexts (I, D); drops an exclusion pattern set before"""
+        Xc, ip, ix, dv = csr_parts(X_cand)
+        if Xc.shape[1] != self.D:
+            raise ValueError("X_cand must have %d columns" % self.D)
+        self._ck(lib().mfm_foldin_rank_set_candidates(self.h, Xc.shape[0], _p(ip), _p(ix), _p(dv)))
+        self.I = Xc.shape[0]
+
+    def set_exclude(self, exclude):
+        """the (U, I) sparse pattern of the pairs the lists leave out"""
+        E, ip, ix, _ = csr_parts(exclude)
+        if E.shape != (self.U, getattr(self, "I", -1)):
+            raise ValueError("exclude must have shape (n_entities, n_candidates)")
+        self._ck(lib().mfm_foldin_rank_set_exclude(self.h, _p(ip), _p(ix)))
+
+    def _rank_dist(self, src, alpha, mu, lam):
+        alpha, mu, lam = self._hypers(src.S, src.K, alpha, mu, lam)
+        out = [np.empty((self.U, self.I)) for _ in range(4)]
+        self._ck(src.call("mfm_foldin_rank_dist", self.h, _p(alpha), _p(mu), _p(lam), *[_p(o) for o in out]))
+        return tuple(out)
+
+    def rank_dist(self, samples, alpha, mu, lam):
+        """(mean, std, std_within, gain), each (U, I), under host samples; hyper-parameters as solve"""
+        return self._rank_dist(_host(samples), alpha, mu, lam)
+
+    def rank_dist_store(self, store, alpha, mu, lam, first=0, count=None):
+        return self._rank_dist(_resident(store, first, count), alpha, mu, lam)
+
+    RANK_BY = {"ucb": 0, "gain": 1}
+
+    def _rank_topk(self, src, alpha, mu, lam, k, by, beta):
+        alpha, mu, lam = self._hypers(src.S, src.K, alpha, mu, lam)
+        kk = max(int(k), 1)
+        idx = np.empty((self.U, kk), dtype=np.int64)
+        out = [np.empty((self.U, kk)) for _ in range(4)]
+        self._ck(src.call("mfm_foldin_rank_topk", self.h, _p(alpha), _p(mu), _p(lam), self.RANK_BY.get(by, by), int(k), float(beta), _p(idx),
+                          *[_p(o) for o in out]))
+        return (idx,) + tuple(out)
+
+    def rank_topk(self, samples, alpha, mu, lam, k, by="ucb", beta=1.0):
+        """(indices int64, value, mean, std, gain), each (U, k): the k best candidates per entity by mean + beta std ('ucb') or by
+        the information gain ('gain'), value descending and index ascending; tail -1 / -inf / NaN"""
+        return self._rank_topk(_host(samples), alpha, mu, lam, k, by, beta)
+
+    def rank_topk_store(self, store, alpha, mu, lam, k, by="ucb", beta=1.0, first=0, count=None):
+        return self._rank_topk(_resident(store, first, count), alpha, mu, lam, k, by, beta)
 
     FOLDIN_TASKS = {"classifier": 0, "ordered": 1}
 

@@ -1059,11 +1059,12 @@ struct Predictor {
         throw std::invalid_argument(ss.str());
       }
     }
-    void open(bool fit_linear) {
+    void open(bool fit_linear, bool columns = true) {  // columns: the call returns the new columns (w_new, V_new)
       const int64_t U = (int64_t)offsets.size() - 1;
       const int code = mfm_foldin_create(selected_device(), X.cols, X.rows, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), U,
                                          offsets.data(), fit_linear ? 1 : 0, &h);
       if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(nullptr));
+      if (!columns) return;
       w_new = py::array_t<double>({(py::ssize_t)S, (py::ssize_t)U});
       V_new = py::array_t<double>({(py::ssize_t)S, (py::ssize_t)U, (py::ssize_t)K});
     }
@@ -1082,6 +1083,62 @@ struct Predictor {
     c.open(fit_linear);
     return c.result(on_samples(mfm_foldin_solve_store, mfm_foldin_solve, c.h, alpha.data(), mu.data(), lam.data(), draw ? 1 : 0, seed,
                                c.w_new.mutable_data(), c.V_new.mutable_data()));
+  }
+  // ---- ranking candidates under the new entities' own posterior (mfm_foldin_rank_*). Xc (I, D): the candidate contexts.
+  // What the two calls share: every host check, then the handle with the candidates and the exclusion pattern (None or (U, I)) set.
+  void fold_in_rank_open(FoldInCall &c, const Csr &Xc, const py::object &excludeo, bool fit_linear, const NpF64 &alpha, const NpF64 &mu,
+                         const NpF64 &lam) const {
+    if ((size_t)Xc.cols != feature_size) {
+      std::ostringstream ss;
+      ss << "X_cand has " << Xc.cols << " columns but this->feature_size is " << feature_size;
+      throw std::invalid_argument(ss.str());
+    }
+    if ((size_t)alpha.size() != c.S || (size_t)mu.size() != c.S * (c.K + 1) || (size_t)lam.size() != c.S * (c.K + 1))
+      throw std::invalid_argument("fold-in: alpha must hold one entry per kept sample, mu and lambda (K + 1) per kept sample");
+    const int64_t U = (int64_t)c.offsets.size() - 1;
+    Csr ex;
+    if (!excludeo.is_none()) {
+      ex = csr_from_py(excludeo);
+      if (ex.rows != U || ex.cols != Xc.rows) throw std::invalid_argument("exclude must have shape (n_entities, n_candidates)");
+      for (int32_t j : ex.indices)
+        if (j < 0 || j >= ex.cols) throw std::invalid_argument("exclude: column index out of range");
+    }
+    c.check_rank();
+    c.open(fit_linear, false);
+    int code = mfm_foldin_rank_set_candidates(c.h, Xc.rows, Xc.indptr.data(), Xc.indices.data(), Xc.data.data());
+    if (code == MFM_OK && !excludeo.is_none()) code = mfm_foldin_rank_set_exclude(c.h, ex.indptr.data(), ex.indices.data());
+    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(c.h));
+  }
+  // (mean, std, std_within, gain), each (U, I)
+  py::tuple fold_in_pairs_dist(const py::object &Xo, const NpF64 &y, const NpI64 &offsets, bool fit_linear, const NpF64 &alpha, const NpF64 &mu,
+                               const NpF64 &lam, const py::object &Xco) const {
+    FoldInCall c(*this, "fold_in_pairs_dist", csr_from_py(Xo), y, offsets);
+    const Csr Xc = csr_from_py(Xco);
+    const py::ssize_t U = (py::ssize_t)offsets.size() - 1, I = (py::ssize_t)Xc.rows;
+    if ((double)U * (double)I > 16777216.0) throw std::invalid_argument("fold_in_pairs_dist writes at most 2^24 pairs per call (entities * candidates)");
+    fold_in_rank_open(c, Xc, py::none(), fit_linear, alpha, mu, lam);
+    py::array_t<double> mean({U, I}), sd({U, I}), within({U, I}), gain({U, I});
+    const int code = on_samples(mfm_foldin_rank_dist_store, mfm_foldin_rank_dist, c.h, alpha.data(), mu.data(), lam.data(), mean.mutable_data(),
+                                sd.mutable_data(), within.mutable_data(), gain.mutable_data());
+    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(c.h));
+    return py::make_tuple(mean, sd, within, gain);
+  }
+  // (indices, value, mean, std, gain), each (U, k): by 0 ranks by mean + beta std, 1 by the information gain
+  py::tuple fold_in_topk(const py::object &Xo, const NpF64 &y, const NpI64 &offsets, bool fit_linear, const NpF64 &alpha, const NpF64 &mu,
+                         const NpF64 &lam, const py::object &Xco, int64_t k, int by, double beta, const py::object &excludeo) const {
+    FoldInCall c(*this, "fold_in_topk", csr_from_py(Xo), y, offsets);
+    if (k < 1 || k > 256) throw std::invalid_argument("k must be in [1, 256]");
+    if (by != 0 && by != 1) throw std::invalid_argument("by must be 'ucb' or 'gain'");
+    if (!std::isfinite(beta)) throw std::invalid_argument("beta must be finite");
+    const Csr Xc = csr_from_py(Xco);
+    fold_in_rank_open(c, Xc, excludeo, fit_linear, alpha, mu, lam);
+    const py::ssize_t U = (py::ssize_t)offsets.size() - 1;
+    py::array_t<int64_t> idx({U, (py::ssize_t)k});
+    py::array_t<double> value({U, (py::ssize_t)k}), mean({U, (py::ssize_t)k}), sd({U, (py::ssize_t)k}), gain({U, (py::ssize_t)k});
+    const int code = on_samples(mfm_foldin_rank_topk_store, mfm_foldin_rank_topk, c.h, alpha.data(), mu.data(), lam.data(), (int32_t)by, (int32_t)k,
+                                beta, idx.mutable_data(), value.mutable_data(), mean.mutable_data(), sd.mutable_data(), gain.mutable_data());
+    if (code != MFM_OK) throw_code(code, mfm_foldin_last_error(c.h));
+    return py::make_tuple(idx, value, mean, sd, gain);
   }
   // the same for the probit tasks (mfm_foldin_gibbs_*): y the labels (+-1, or class indices), the task this predictor's type, the
   // cutpoints those of group `cutpoint_index` of every kept sample; mu / lam (S, K + 1)
@@ -3389,6 +3446,11 @@ PYBIND11_MODULE(_myfm, m) {
                              })  // the samples are read in place from the device store (else: uploaded from the host)
       .def("fold_in_solve", &Predictor::fold_in_solve, py::arg("X"), py::arg("y"), py::arg("offsets"), py::arg("fit_linear"), py::arg("alpha"),
            py::arg("mu"), py::arg("lam"), py::arg("draw") = false, py::arg("seed") = 0)
+      .def("fold_in_pairs_dist", &Predictor::fold_in_pairs_dist, py::arg("X"), py::arg("y"), py::arg("offsets"), py::arg("fit_linear"),
+           py::arg("alpha"), py::arg("mu"), py::arg("lam"), py::arg("X_cand"))
+      .def("fold_in_topk", &Predictor::fold_in_topk, py::arg("X"), py::arg("y"), py::arg("offsets"), py::arg("fit_linear"), py::arg("alpha"),
+           py::arg("mu"), py::arg("lam"), py::arg("X_cand"), py::arg("k"), py::arg("by") = 0, py::arg("beta") = 1.0,
+           py::arg("exclude") = py::none())
       .def("fold_in_gibbs_solve", &Predictor::fold_in_gibbs_solve, py::arg("X"), py::arg("y"), py::arg("offsets"), py::arg("fit_linear"),
            py::arg("mu"), py::arg("lam"), py::arg("cutpoint_index") = 0, py::arg("n_burn") = 10, py::arg("n_inner") = 40,
            py::arg("draw") = false, py::arg("seed") = 0)

@@ -35,24 +35,10 @@ void launch_foldin(hipStream_t s, dim3 grid, size_t lds, const FoldinArgs &a) {
 void run_foldin(mfm_foldin *p, const SampleView &v, const double *alpha, const double *mu, const double *lam, int draw, uint64_t seed,
                 double *w_new, double *V_new) {
   const int S = v.count(), K = v.K;
-  if (v.device != p->device) throw Error(MFM_ERR_INVALID, "fold-in observations and sample store live on different devices");
-  if (v.D != p->D) throw Error(MFM_ERR_INVALID, "feature size mismatch!");
-  if (K > FOLDIN_MAX_RANK)
-    throw Error(MFM_ERR_INVALID, "fold-in serves ranks up to " + std::to_string(FOLDIN_MAX_RANK) + ", the samples have rank " + std::to_string(K));
-  if (S > 65535) throw Error(MFM_ERR_INVALID, "at most 65535 samples per call");
-  if (!alpha || !mu || !lam) throw Error(MFM_ERR_INVALID, "no hyper-parameter arrays");
+  foldin_check_samples(p, v.device, v.D, K, S, FOLDIN_MAX_RANK, alpha, mu, lam);
   if (!w_new || (K > 0 && !V_new)) throw Error(MFM_ERR_INVALID, "no output array");
   const int off = p->lin ? 1 : 0, M = K + off;
-  for (int s = 0; s < S; s++) {
-    if (!(alpha[s] > 0.0) || !std::isfinite(alpha[s]))
-      throw Error(MFM_ERR_INVALID, "fold-in: the noise precision of sample " + std::to_string(s) + " is not positive and finite");
-    for (int j = 1 - off; j < K + 1; j++) {
-      const double l = lam[(size_t)s * (K + 1) + j], m = mu[(size_t)s * (K + 1) + j];
-      if (!(l > 0.0) || !std::isfinite(l) || !std::isfinite(m))
-        throw Error(MFM_ERR_INVALID, "fold-in: sample " + std::to_string(s) + " has a prior precision that is not positive and finite, or a "
-                                         "prior mean that is not finite (component " + std::to_string(j) + ")");
-    }
-  }
+  foldin_check_hypers(S, K, off, alpha, mu, lam);
   const int64_t U = p->U;
   if (U == 0) return;
   if (M == 0) {  // rank 0 without a linear term: nothing to estimate

@@ -38,7 +38,17 @@ struct FoldinArgs {
   uint64_t seed;
   double *out_w, *out_V;   // [gridDim.y][gridDim.x], [gridDim.y][gridDim.x][K]
   int *err;                // set when a pivot is not positive
+  double *Wf = nullptr;    // KEEP: [gridDim.x][S_all][foldin_keep_doubles(M)], the left operands of mfm_foldin_rank.hpp
+  int S_all = 0;           // KEEP: samples of the call (an entity's operands lie sample after sample)
 };
+
+// The kept factor of one (entity, sample), KEEP: W = U^-T (lower triangular, M x M; z^T Lambda^-1 z = |W z|^2) and below it
+// theta_mean^T as row M, an (M + 1) x M left operand in the fragment order of v_mfma_f64_16x16x4_f64 (the layout k_pairs_embed
+// writes, mfm_pairs.hpp): 16-row tiles x 4-wide k-steps, the 64 values of (tile t, k-step q) contiguous, (row r, component k) at
+// (k & 3) * 16 + (r & 15); rows above M and components from M on are zeros.
+__host__ __device__ inline int foldin_keep_tiles(int M) { return (M + 16) >> 4; }  // row tiles of the M + 1 rows
+__host__ __device__ inline int foldin_keep_ksteps(int M) { return (M + 3) >> 2; }
+__host__ __device__ inline size_t foldin_keep_doubles(int M) { return (size_t)foldin_keep_tiles(M) * foldin_keep_ksteps(M) * 64; }
 
 // doubles of dynamic LDS before the (i, j) table of the upper triangle
 __host__ __device__ inline size_t foldin_lds_doubles(int M) {
@@ -110,8 +120,29 @@ __device__ __forceinline__ FoldinDD foldin_rows_zf(const FoldinArgs &a, const do
   return f;
 }
 
-template <bool DRAW>
+// value (row r, component k) of the kept operand from the workgroup's LDS: W below the diagonal where the inversion left it (the
+// lower triangle of A), its diagonal in dinv, theta_mean in bv
+__device__ __forceinline__ void foldin_keep_write(double *__restrict__ Wf, int M, const double *A, const double *dinv, const double *bv) {
+  const int KS4 = foldin_keep_ksteps(M), n = (int)foldin_keep_doubles(M);
+  for (int e = threadIdx.x; e < n; e += FOLDIN_WG) {
+    const int tq = e >> 6, t = tq / KS4, q = tq - t * KS4;
+    const int r = t * 16 + (e & 15), k = q * 4 + ((e >> 4) & 3);
+    double v = 0.0;
+    if (k < M) {
+      if (r < M)
+        v = k < r ? A[r * M + k] : k == r ? dinv[r] : 0.0;
+      else if (r == M)
+        v = bv[k];
+    }
+    Wf[e] = v;
+  }
+}
+
+// KEEP (mfm_foldin_rank.hpp): after the solves the triangular factor is inverted in LDS and written with the mean
+// as the left operand of the ranking contraction (a.Wf); the means themselves are still written. KEEP excludes DRAW.
+template <bool DRAW, bool KEEP = false>
 __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
+  static_assert(!(DRAW && KEEP), "the kept operand holds the posterior mean");
   extern __shared__ double foldin_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, off = a.lin, M = K + off, ldz = M | 1;
@@ -157,6 +188,15 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
         oV[tid - off] = t;
     }
     if (!off && tid == 0) *ow = 0.0;
+    if constexpr (KEEP) {  // the prior: W = diag(1 / sqrt(lambda)), theta_mean = mu
+      for (int t = tid; t < M * M; t += FOLDIN_WG) A[t] = 0.0;
+      if (tid < M) {
+        Z[tid] = 1.0 / sqrt(lam[tid]);
+        bv[tid] = mu[tid];
+      }
+      __syncthreads();
+      foldin_keep_write(a.Wf + ((size_t)blockIdx.x * a.S_all + s) * foldin_keep_doubles(M), M, A, Z, bv);
+    }
     return;
   }
 
@@ -243,6 +283,10 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
         oV[tid - off] = 0.0;
     }
     if (!off && tid == 0) *ow = 0.0;
+    if constexpr (KEEP) {
+      double *__restrict__ Wf = a.Wf + ((size_t)blockIdx.x * a.S_all + s) * foldin_keep_doubles(M);
+      for (int e = tid; e < (int)foldin_keep_doubles(M); e += FOLDIN_WG) Wf[e] = 0.0;
+    }
     return;
   }
 
@@ -272,6 +316,25 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
       oV[tid - off] = bv[tid];
   }
   if (!off && tid == 0) *ow = 0.0;
+
+  if constexpr (KEEP) {
+    // ---- X = U^-1 column by column, thread r column r by back substitution: X[i][r] = -(sum_{i < j <= r} U[i][j] X[j][r]) / U[i][i]
+    // from X[r][r] = 1 / U[r][r]. W = X^T: W[r][i] goes to A[r][i] below the diagonal, which the factorisation never touched, the
+    // diagonal to Z (the passes are over); a thread reads the upper triangle and its own row only.
+    __syncthreads();
+    if (tid < M) {
+      const int r = tid;
+      const double xr = 1.0 / A[r * M + r];
+      Z[r] = xr;
+      for (int i = r - 1; i >= 0; i--) {
+        double acc = A[i * M + r] * xr;
+        for (int j = i + 1; j < r; j++) acc = fma(A[i * M + j], A[r * M + j], acc);
+        A[r * M + i] = -acc / A[i * M + i];
+      }
+    }
+    __syncthreads();
+    foldin_keep_write(a.Wf + ((size_t)blockIdx.x * a.S_all + s) * foldin_keep_doubles(M), M, A, Z, bv);
+  }
 }
 
 }  // namespace mfm

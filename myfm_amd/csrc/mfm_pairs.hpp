@@ -164,7 +164,8 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_embed(const int64_t *__restr
 }
 
 // sum over the samples, in sample order, of a side's biases (regression mode adds it once)
-__global__ __launch_bounds__(PAIRS_WG) void k_pairs_bias_sum(const double *__restrict__ bias, int S, int64_t Rpad,
+// (the kernels of this file that are no templates are static: mfm_foldin_rank.hip includes it as well as mfm_pairs.hip)
+static __global__ __launch_bounds__(PAIRS_WG) void k_pairs_bias_sum(const double *__restrict__ bias, int S, int64_t Rpad,
                                                              double *__restrict__ out) {
   const int64_t r = (int64_t)blockIdx.x * PAIRS_WG + threadIdx.x;
   if (r >= Rpad) return;
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_bias_sum(const double *__res
 }
 
 // exclusion bitmask of a query chunk: bit (u - u0, i) set for every stored (u, i); one wave per query row
-__global__ __launch_bounds__(PAIRS_WG) void k_pairs_mask(const int64_t *__restrict__ eptr, const int32_t *__restrict__ eidx,
+static __global__ __launch_bounds__(PAIRS_WG) void k_pairs_mask(const int64_t *__restrict__ eptr, const int32_t *__restrict__ eidx,
                                                          int64_t u0, int64_t Uc, int64_t W, uint32_t *__restrict__ mask) {
   const int64_t u = (int64_t)blockIdx.x * (PAIRS_WG / 64) + (threadIdx.x >> 6);
   if (u >= Uc) return;
@@ -557,7 +558,7 @@ __global__ __launch_bounds__(PAIRS_WG) void k_pairs_tile(PairsArgs a) {
 }
 
 // ---- merge: the stripes' lists of one query row into its final k under the same order (one workgroup per row) -------------
-__global__ __launch_bounds__(PAIRS_WG) void k_pairs_merge(const double *__restrict__ list_v, const int32_t *__restrict__ list_i,
+static __global__ __launch_bounds__(PAIRS_WG) void k_pairs_merge(const double *__restrict__ list_v, const int32_t *__restrict__ list_i,
                                                           int n_stripes, int64_t Upad, int k, double *__restrict__ out_v,
                                                           int32_t *__restrict__ out_i) {
   const int64_t u = blockIdx.x;

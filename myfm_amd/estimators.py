@@ -1079,6 +1079,10 @@ class _AlignedFactorsMixin:
         return AlignedFactors(*predictor.aligned_factors(reference, n_refine, weights))
 
 
+ColdStartSummary = namedtuple("ColdStartSummary", ["mean", "std", "std_within", "gain"])
+ColdStartRanking = namedtuple("ColdStartRanking", ["indices", "value", "mean", "std", "gain"])
+
+
 def _fold_in_checked(est, name, X, y, entity, group, n_entities):
     """The host-side checks that fold_in and fold_in_gibbs share, in one order and with one set of messages (`name`: the calling
     method). Returns (predictor, D, K, X csr, y float64 (n,), entity int64 (n,), U, the hyper-parameters of the kept samples, group)."""
@@ -1323,6 +1327,53 @@ class MyFMGibbsRegressor(_AlignedFactorsMixin, _PairScoringMixin, _ScreenedRanki
         w_new, V_new = predictor.fold_in_solve(X[order], np.ascontiguousarray(y[order]), offsets, bool(self.fit_linear), alpha, mu,
                                                lam, bool(draw), int(random_seed) & 0xFFFFFFFFFFFFFFFF)
         return _folded_in(self, predictor.extended(w_new, V_new), D, U, g)
+
+    # ---- ranking for new entities under their OWN posterior. fold_in stores the posterior mean of the new column
+    # and every predictor then treats it as known; for an entity with a few ratings almost all of a score's uncertainty is the
+    # within-sample term z^T Lambda^-1 z, which these two calls keep.
+    def _fold_in_rank_args(self, name, X, y, entity, group, X_cand, n_entities):
+        predictor, D, K, X, y, entity, U, kept, g = _fold_in_checked(self, name, X, y, entity, group, n_entities)
+        if X_cand is None or not sps.issparse(X_cand):
+            raise ValueError("X_cand must be a scipy sparse matrix of shape (n_candidates, %d)" % D)
+        X_cand = _as_csr(X_cand, 0)
+        if X_cand.shape[1] != D:
+            raise ValueError("X_cand has %d columns but the fitted feature size is %d" % (X_cand.shape[1], D))
+        if X_cand.nnz and not np.all(np.isfinite(X_cand.data)):
+            raise ValueError("X_cand holds a value that is not finite")
+        alpha = np.asarray([h.alpha for h in kept], dtype=REAL)
+        mu, lam = _fold_in_prior(kept, g, K)
+        order, offsets = _fold_in_grouping(entity, U)
+        return predictor, (X[order], np.ascontiguousarray(y[order]), offsets, bool(self.fit_linear), alpha, mu, lam, X_cand), U
+
+    def fold_in_pairs_dist(self, X, y, entity, group, X_cand, n_entities=None):
+        """ColdStartSummary(mean, std, std_within, gain), each (U, I): the score of every (new entity u, candidate context c) pair
+        -- the design row X_cand[c] + e_{D+u} -- under the entity's own posterior. X, y, entity, group and n_entities are
+        fold_in's and are checked the same way; X_cand (I, D) sparse holds the contexts in the fitted feature space. With
+        f_sc = score_s(X_cand[c]), z_sc = (1, q_s(X_cand[c])) and theta_us, Lambda_us the posterior mean and precision of fold_in,
+            m = f_sc + z_sc^T theta_us,  v = z_sc^T Lambda_us^-1 z_sc,  mean = mean_s m,  std_within^2 = mean_s v,
+            std^2 = std_within^2 + mean_s (m - mean)^2  (the mixture of the S normals, ddof 0),  gain = mean_s 1/2 log1p(alpha_s v),
+        gain being the expected information (nats) about theta_u from observing the pair. mean is what
+        fold_in(...).predict_pairs(one-hot queries, X_cand) returns; std is never below that model's predict_pairs_dist std. An
+        entity without observations gets the prior. U * I > 2^24 is refused (ValueError): use fold_in_topk. Limits as fold_in."""
+        predictor, args, U = self._fold_in_rank_args("fold_in_pairs_dist", X, y, entity, group, X_cand, n_entities)
+        if U * args[-1].shape[0] > 1 << 24:
+            raise ValueError("fold_in_pairs_dist writes at most 2^24 pairs per call (entities * candidates): use fold_in_topk")
+        return ColdStartSummary(*predictor.fold_in_pairs_dist(*args))
+
+    def fold_in_topk(self, X, y, entity, group, X_cand, k, by="ucb", beta=1.0, exclude=None, n_entities=None):
+        """Per new entity the k candidate contexts of largest value: ColdStartRanking(indices int64 (U, k), value, mean, std,
+        gain), ordered by (value descending, candidate index ascending). by="ucb": value = mean + beta * std with the std of
+        fold_in_pairs_dist, which holds the entity's own uncertainty (what to recommend while exploring); by="gain": value = gain
+        (which item to ask the entity to rate next; beta is not used). exclude: None or a (U, I) sparse pattern of the pairs to
+        leave out, as predict_topk's. 1 <= k <= 256; where fewer candidates remain the tail is index -1, value -inf, the rest
+        NaN. mean, std and gain of the listed pairs are recomputed in another summation order: value agrees within rounding."""
+        if by not in ("ucb", "gain"):
+            raise ValueError("by must be 'ucb' or 'gain'")
+        predictor, args, U = self._fold_in_rank_args("fold_in_topk", X, y, entity, group, X_cand, n_entities)
+        k, beta, exclude = _ranked_args(sps.csr_matrix((U, 0)), args[-1], k, exclude, beta)
+        if not 1 <= k <= 256:
+            raise ValueError("k must be an integer in [1, 256]")
+        return ColdStartRanking(*predictor.fold_in_topk(*args, k, 1 if by == "gain" else 0, beta, exclude))
 
 
 class MyFMGibbsClassifier(_AlignedFactorsMixin, _PairScoringMixin, _PairUncertaintyMixin, _SimilarityMixin, _DiverseRankingMixin, _PredictiveDistMixin, _LooMixin, _DiagnosticsMixin, _CrpsMixin, _ContributionsMixin, _FoldInGibbsMixin, MyFMGibbsBase):
