@@ -1059,6 +1059,10 @@ struct Predictor {
         throw std::invalid_argument(ss.str());
       }
     }
+    void check_hyper_sizes(const NpF64 &alpha, const NpF64 &mu, const NpF64 &lam) const {
+      if ((size_t)alpha.size() != S || (size_t)mu.size() != S * (K + 1) || (size_t)lam.size() != S * (K + 1))
+        throw std::invalid_argument("fold-in: alpha must hold one entry per kept sample, mu and lambda (K + 1) per kept sample");
+    }
     void open(bool fit_linear, bool columns = true) {  // columns: the call returns the new columns (w_new, V_new)
       const int64_t U = (int64_t)offsets.size() - 1;
       const int code = mfm_foldin_create(selected_device(), X.cols, X.rows, X.indptr.data(), X.indices.data(), X.data.data(), y.data(), U,
@@ -1077,8 +1081,7 @@ struct Predictor {
   py::tuple fold_in_solve(const py::object &Xo, const NpF64 &y, const NpI64 &offsets, bool fit_linear, const NpF64 &alpha, const NpF64 &mu,
                           const NpF64 &lam, bool draw, uint64_t seed) const {
     FoldInCall c(*this, "fold_in", csr_from_py(Xo), y, offsets);
-    if ((size_t)alpha.size() != c.S || (size_t)mu.size() != c.S * (c.K + 1) || (size_t)lam.size() != c.S * (c.K + 1))
-      throw std::invalid_argument("fold-in: alpha must hold one entry per kept sample, mu and lambda (K + 1) per kept sample");
+    c.check_hyper_sizes(alpha, mu, lam);
     c.check_rank();
     c.open(fit_linear);
     return c.result(on_samples(mfm_foldin_solve_store, mfm_foldin_solve, c.h, alpha.data(), mu.data(), lam.data(), draw ? 1 : 0, seed,
@@ -1093,8 +1096,7 @@ struct Predictor {
       ss << "X_cand has " << Xc.cols << " columns but this->feature_size is " << feature_size;
       throw std::invalid_argument(ss.str());
     }
-    if ((size_t)alpha.size() != c.S || (size_t)mu.size() != c.S * (c.K + 1) || (size_t)lam.size() != c.S * (c.K + 1))
-      throw std::invalid_argument("fold-in: alpha must hold one entry per kept sample, mu and lambda (K + 1) per kept sample");
+    c.check_hyper_sizes(alpha, mu, lam);
     const int64_t U = (int64_t)c.offsets.size() - 1;
     Csr ex;
     if (!excludeo.is_none()) {

@@ -10,6 +10,9 @@
 // the residual (f in double-double, see there) into LDS; then every thread adds the pass to its entries of the upper triangle of the Gram matrix and of b, in row
 // order. Nothing is summed between workgroups and no order depends on the grid: a result depends on the entity's own rows only, not on
 // the number of entities, the chunking or the scratch bound. The factorisation and the two triangular solves run in LDS.
+// The steps that the probit chain (k_foldin_gibbs, mfm_foldin_gibbs.hpp) takes in the same way are said once here: the LDS layout
+// (foldin_lds), the cell and the write of theta (FoldinCell), the Gram sums (foldin_gram_*), the factorisation (foldin_factor) and
+// the draw's normals (foldin_normal).
 #pragma once
 #include "mfm_common.hpp"
 #include "mfm_philox.hpp"
@@ -50,13 +53,34 @@ __host__ __device__ inline int foldin_keep_tiles(int M) { return (M + 16) >> 4; 
 __host__ __device__ inline int foldin_keep_ksteps(int M) { return (M + 3) >> 2; }
 __host__ __device__ inline size_t foldin_keep_doubles(int M) { return (size_t)foldin_keep_tiles(M) * foldin_keep_ksteps(M) * 64; }
 
-// doubles of dynamic LDS before the (i, j) table of the upper triangle
-__host__ __device__ inline size_t foldin_lds_doubles(int M) {
-  const size_t ldz = (size_t)M | 1;
-  return (size_t)M * M + M + FOLDIN_ROWS * ldz + FOLDIN_ROWS + 2 * (FOLDIN_WG / 64) * FOLDIN_ROWS;
+// ---- the dynamic LDS of a workgroup: layout and size side by side ------------------------------------------------------------------
+// What foldin_rows_zf fills, which is all that k_foldin_rank_cand (mfm_foldin_rank.hpp) asks for
+struct FoldinRowsLds {
+  double *Z;     // [FOLDIN_ROWS][ldz]: the pass's z (ldz = M | 1 is odd: a column walk touches every bank)
+  double *part;  // [2][4][FOLDIN_ROWS]: per wave the high and low parts of its factors' pair terms
+};
+__host__ __device__ inline size_t foldin_rows_lds_doubles(int M) {
+  return FOLDIN_ROWS * ((size_t)M | 1) + 2 * (FOLDIN_WG / 64) * FOLDIN_ROWS;
 }
+__device__ __forceinline__ FoldinRowsLds foldin_rows_lds(double *smem, int M) { return {smem, smem + FOLDIN_ROWS * (M | 1)}; }
+
+// A cell's (k_foldin, k_foldin_gibbs): the matrix, the right-hand side and the residuals before the rows' part, the table behind it
+struct FoldinLds {
+  double *A;      // [M][M], the upper triangle: the Gram sums, then Lambda, then U = L^T
+  double *bv;     // [M]: sum z r, then b, then the solves' right-hand side
+  double *res;    // [FOLDIN_ROWS]: the pass's residuals
+  double *Z, *part;
+  uint16_t *tab;  // [T]: i | j << 8 of entry e of the upper triangle, T = M (M + 1) / 2
+};
+// doubles before tab
+__host__ __device__ inline size_t foldin_lds_doubles(int M) { return (size_t)M * M + M + FOLDIN_ROWS + foldin_rows_lds_doubles(M); }
 __host__ __device__ inline size_t foldin_lds_bytes(int M) {
   return foldin_lds_doubles(M) * sizeof(double) + ((size_t)M * (M + 1) / 2) * sizeof(uint16_t) + 16;
+}
+__device__ __forceinline__ FoldinLds foldin_lds(double *smem, int M) {
+  double *bv = smem + M * M, *res = bv + M;
+  const FoldinRowsLds r = foldin_rows_lds(res + FOLDIN_ROWS, M);
+  return {smem, bv, res, r.Z, r.part, (uint16_t *)(smem + foldin_lds_doubles(M))};
 }
 
 // an unevaluated sum hi + lo, |lo| <= ulp(hi) / 2: add() takes a term given the same way (Knuth's two-sum; the unit is compiled
@@ -120,6 +144,100 @@ __device__ __forceinline__ FoldinDD foldin_rows_zf(const FoldinArgs &a, const do
   return f;
 }
 
+// ---- the steps of a cell that the closed form and the probit chain share ------------------------------------------------------------
+// The cell of workgroup (blockIdx.x, blockIdx.y): entity u under sample s of the call, the sample's model and prior (component 0 of
+// mu / lam is passed over without a linear term), the entity's rows [e0, e1), the cell's outputs and its row of the draws' streams.
+struct FoldinCell {
+  int64_t u, e0, e1, srow;
+  int sl, s, off, M;
+  const double *w, *V, *mu, *lam;
+  double w0;
+  double *ow, *oV;
+  // v: component threadIdx.x of theta (read below M only). Component 0 is w where the model has a linear term, which is 0 otherwise.
+  __device__ __forceinline__ void put(double v) const {
+    const int tid = threadIdx.x;
+    if (tid < M) {
+      if (off && tid == 0)
+        *ow = v;
+      else
+        oV[tid - off] = v;
+    }
+    if (!off && tid == 0) *ow = 0.0;
+  }
+  // a cell without a result: reported through the handle, never a NaN in the output
+  __device__ __forceinline__ void fail(int *err) const {
+    if (threadIdx.x == 0) atomicOr(err, 1);
+    put(0.0);
+  }
+};
+__device__ __forceinline__ FoldinCell foldin_cell(const FoldinArgs &a) {
+  FoldinCell c;
+  c.u = a.u0 + blockIdx.x;
+  c.sl = blockIdx.y;
+  c.s = a.s0 + c.sl;
+  c.off = a.lin;
+  c.M = a.K + c.off;
+  c.w = a.wv[c.s];
+  c.V = c.w + a.D;
+  c.mu = a.mu + (size_t)c.s * (a.K + 1) + (1 - c.off);
+  c.lam = a.lam + (size_t)c.s * (a.K + 1) + (1 - c.off);
+  c.w0 = a.w0[c.s];
+  c.e0 = a.eoff[c.u];
+  c.e1 = a.eoff[c.u + 1];
+  c.ow = a.out_w + (size_t)c.sl * gridDim.x + blockIdx.x;
+  c.oV = a.out_V + ((size_t)c.sl * gridDim.x + blockIdx.x) * a.K;
+  c.srow = (int64_t)c.s * a.U + c.u;
+  return c;
+}
+
+// component j of the normals of (draw word, stream row): the Box-Muller value of counter word j >> 1, r cos for even j, r sin for odd j
+__device__ __forceinline__ double foldin_normal(uint64_t seed, uint64_t word, int64_t srow, int j) {
+  RowRng g(seed ^ ((uint64_t)(srow >> 32) * 0x9E3779B97F4A7C15ull), word, (uint32_t)srow);
+  g.n = (uint32_t)(j >> 1);
+  const double2 un = g.next2();
+  const double r = sqrt(-2.0 * log(un.x));
+  double sn, cs;
+  sincospi(2.0 * un.y, &sn, &cs);
+  return (j & 1) ? r * sn : r * cs;
+}
+
+// A = 0 and the (i, j) table of its upper triangle; the caller's barrier follows
+__device__ __forceinline__ void foldin_gram_zero(double *A, uint16_t *tab, int M) {
+  for (int t = threadIdx.x; t < M * M; t += FOLDIN_WG) {
+    const int i = t / M, j = t - i * M;
+    A[t] = 0.0;
+    if (i <= j) tab[i * M - (i * (i - 1)) / 2 + (j - i)] = (uint16_t)(i | (j << 8));
+  }
+}
+// entry e < T of the upper triangle takes the pass's share of sum z z^T, row after row (thread e of every FOLDIN_WG owns it)
+__device__ __forceinline__ void foldin_gram_add(double *A, const uint16_t *tab, const double *Z, int M, int e, int nr) {
+  const int ldz = M | 1, ij = tab[e], i = ij & 255, j = ij >> 8;
+  double acc = A[i * M + j];
+  for (int r = 0; r < nr; r++) acc = fma(Z[r * ldz + i], Z[r * ldz + j], acc);
+  A[i * M + j] = acc;
+}
+
+// Lambda = U^T U in place (right-looking; every entry takes its updates in column order). True when a pivot is not positive and
+// finite: every thread reads the same value, so the exit is uniform.
+__device__ __forceinline__ bool foldin_factor(double *A, int M) {
+  const int tid = threadIdx.x;
+  for (int j = 0; j < M; j++) {
+    const double d = A[j * M + j];
+    if (!(d > 0.0) || !(d < INFINITY)) return true;
+    const double piv = sqrt(d);
+    __syncthreads();
+    for (int i = j + tid; i < M; i += FOLDIN_WG) A[j * M + i] = i == j ? piv : A[j * M + i] / piv;
+    __syncthreads();
+    const int m = M - j - 1;
+    for (int t = tid; t < m * m; t += FOLDIN_WG) {
+      const int i = j + 1 + t / m, k = j + 1 + t % m;
+      if (i <= k) A[i * M + k] = fma(-A[j * M + i], A[j * M + k], A[i * M + k]);
+    }
+    __syncthreads();
+  }
+  return false;
+}
+
 // value (row r, component k) of the kept operand from the workgroup's LDS: W below the diagonal where the inversion left it (the
 // lower triangle of A), its diagonal in dinv, theta_mean in bv
 __device__ __forceinline__ void foldin_keep_write(double *__restrict__ Wf, int M, const double *A, const double *dinv, const double *bv) {
@@ -145,49 +263,22 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
   static_assert(!(DRAW && KEEP), "the kept operand holds the posterior mean");
   extern __shared__ double foldin_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = a.K, off = a.lin, M = K + off, ldz = M | 1;
+  const FoldinCell c = foldin_cell(a);
+  const int off = c.off, M = c.M, ldz = M | 1;
   const int T = M * (M + 1) / 2;
-  double *A = foldin_smem;                    // [M][M], the upper triangle: the Gram sums, then Lambda, then U = L^T
-  double *bv = A + M * M;                     // [M]: sum z r, then b, then the solves' right-hand side
-  double *Z = bv + M;                         // [FOLDIN_ROWS][ldz]: the pass's z (ldz odd: a column walk touches every bank)
-  double *res = Z + FOLDIN_ROWS * ldz;        // [FOLDIN_ROWS]: the pass's residuals
-  double *part = res + FOLDIN_ROWS;           // [2][4][FOLDIN_ROWS]: per wave the high and low parts of its factors' pair terms
-  uint16_t *tab = (uint16_t *)(part + 2 * (FOLDIN_WG / 64) * FOLDIN_ROWS);  // [T]: i | j << 8 of triangle entry e
+  const auto [A, bv, res, Z, part, tab] = foldin_lds(foldin_smem, M);
+  const double *mu = c.mu, *lam = c.lam;
+  const double alpha = a.alpha[c.s];
+  double *Wf = KEEP ? a.Wf + ((size_t)blockIdx.x * a.S_all + c.s) * foldin_keep_doubles(M) : nullptr;
+  const double eps = DRAW && tid < M ? foldin_normal(a.seed, FOLDIN_DRAW_TAG, c.srow, tid) : 0.0;
 
-  const int64_t u = a.u0 + blockIdx.x;
-  const int sl = blockIdx.y, s = a.s0 + sl;
-  const double *__restrict__ w = a.wv[s];
-  const double *__restrict__ V = w + a.D;
-  const double *__restrict__ mu = a.mu + (size_t)s * (K + 1) + (1 - off);
-  const double *__restrict__ lam = a.lam + (size_t)s * (K + 1) + (1 - off);
-  const double alpha = a.alpha[s], w0 = a.w0[s];
-  const int64_t e0 = a.eoff[u], e1 = a.eoff[u + 1];
-  double *__restrict__ ow = a.out_w + (size_t)sl * gridDim.x + blockIdx.x;
-  double *__restrict__ oV = a.out_V + ((size_t)sl * gridDim.x + blockIdx.x) * K;
-
-  // the draw's normals: component j is the Box-Muller value of counter word j >> 1, r cos for even j, r sin for odd j
-  double eps = 0.0;
-  if (DRAW && tid < M) {
-    const int64_t srow = (int64_t)s * a.U + u;
-    RowRng g(a.seed ^ ((uint64_t)(srow >> 32) * 0x9E3779B97F4A7C15ull), FOLDIN_DRAW_TAG, (uint32_t)srow);
-    g.n = (uint32_t)(tid >> 1);
-    const double2 un = g.next2();
-    const double r = sqrt(-2.0 * log(un.x));
-    double sn, cs;
-    sincospi(2.0 * un.y, &sn, &cs);
-    eps = (tid & 1) ? r * sn : r * cs;
-  }
-
-  if (e1 == e0) {  // no rows: the prior itself, mu bit for bit (the factorisation would round lambda mu / sqrt(lambda) / sqrt(lambda))
+  if (c.e1 == c.e0) {  // no rows: the prior itself, mu bit for bit (the factorisation would round lambda mu / sqrt(lambda) / sqrt(lambda))
+    double t = 0.0;
     if (tid < M) {
-      double t = mu[tid];
+      t = mu[tid];
       if (DRAW) t = t + eps / sqrt(lam[tid]);
-      if (off && tid == 0)
-        *ow = t;
-      else
-        oV[tid - off] = t;
     }
-    if (!off && tid == 0) *ow = 0.0;
+    c.put(t);
     if constexpr (KEEP) {  // the prior: W = diag(1 / sqrt(lambda)), theta_mean = mu
       for (int t = tid; t < M * M; t += FOLDIN_WG) A[t] = 0.0;
       if (tid < M) {
@@ -195,24 +286,20 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
         bv[tid] = mu[tid];
       }
       __syncthreads();
-      foldin_keep_write(a.Wf + ((size_t)blockIdx.x * a.S_all + s) * foldin_keep_doubles(M), M, A, Z, bv);
+      foldin_keep_write(Wf, M, A, Z, bv);
     }
     return;
   }
 
-  for (int t = tid; t < M * M; t += FOLDIN_WG) {
-    const int i = t / M, j = t - i * M;
-    A[t] = 0.0;
-    if (i <= j) tab[i * M - (i * (i - 1)) / 2 + (j - i)] = (uint16_t)(i | (j << 8));
-  }
+  foldin_gram_zero(A, tab, M);
   for (int t = tid; t < M; t += FOLDIN_WG) bv[t] = 0.0;
   __syncthreads();
 
-  for (int64_t rb = e0; rb < e1; rb += FOLDIN_ROWS) {
-    const int nr = (int)(e1 - rb < FOLDIN_ROWS ? e1 - rb : FOLDIN_ROWS);
+  for (int64_t rb = c.e0; rb < c.e1; rb += FOLDIN_ROWS) {
+    const int nr = (int)(c.e1 - rb < FOLDIN_ROWS ? c.e1 - rb : FOLDIN_ROWS);
     // ---- z, f and the residual of rows [rb, rb + nr)
     {
-      const FoldinDD f = foldin_rows_zf(a, w, V, w0, rb, nr, Z, part);
+      const FoldinDD f = foldin_rows_zf(a, c.w, c.V, c.w0, rb, nr, Z, part);
       if (wave == 0) {
         double rr = 0.0;
         if (lane < nr) {
@@ -228,10 +315,7 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
     // ---- the pass's share of sum z z^T (upper triangle) and of sum z r, row after row
     for (int e = tid; e < T + M; e += FOLDIN_WG) {
       if (e < T) {
-        const int ij = tab[e], i = ij & 255, j = ij >> 8;
-        double acc = A[i * M + j];
-        for (int r = 0; r < nr; r++) acc = fma(Z[r * ldz + i], Z[r * ldz + j], acc);
-        A[i * M + j] = acc;
+        foldin_gram_add(A, tab, Z, M, e, nr);
       } else {
         const int i = e - T;
         double acc = bv[i];
@@ -255,38 +339,10 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
   }
   __syncthreads();
 
-  // ---- Lambda = U^T U in place (right-looking; every entry takes its updates in column order)
-  bool bad = false;
-  for (int j = 0; j < M; j++) {
-    const double d = A[j * M + j];  // (the same value in every thread: the exit is uniform)
-    if (!(d > 0.0) || !(d < INFINITY)) {
-      bad = true;
-      break;
-    }
-    const double piv = sqrt(d);
-    __syncthreads();
-    for (int i = j + tid; i < M; i += FOLDIN_WG) A[j * M + i] = i == j ? piv : A[j * M + i] / piv;
-    __syncthreads();
-    const int m = M - j - 1;
-    for (int t = tid; t < m * m; t += FOLDIN_WG) {
-      const int i = j + 1 + t / m, k = j + 1 + t % m;
-      if (i <= k) A[i * M + k] = fma(-A[j * M + i], A[j * M + k], A[i * M + k]);
-    }
-    __syncthreads();
-  }
-  if (bad) {  // a non-finite or non-positive lambda: reported through the handle, never a NaN in the result
-    if (tid == 0) atomicOr(a.err, 1);
-    if (tid < M) {
-      if (off && tid == 0)
-        *ow = 0.0;
-      else
-        oV[tid - off] = 0.0;
-    }
-    if (!off && tid == 0) *ow = 0.0;
-    if constexpr (KEEP) {
-      double *__restrict__ Wf = a.Wf + ((size_t)blockIdx.x * a.S_all + s) * foldin_keep_doubles(M);
+  if (foldin_factor(A, M)) {  // a non-finite or non-positive lambda
+    c.fail(a.err);
+    if constexpr (KEEP)
       for (int e = tid; e < (int)foldin_keep_doubles(M); e += FOLDIN_WG) Wf[e] = 0.0;
-    }
     return;
   }
 
@@ -309,13 +365,7 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
     for (int i = tid; i < j; i += FOLDIN_WG) bv[i] = fma(-A[i * M + j], tj, bv[i]);
     __syncthreads();
   }
-  if (tid < M) {
-    if (off && tid == 0)
-      *ow = bv[0];
-    else
-      oV[tid - off] = bv[tid];
-  }
-  if (!off && tid == 0) *ow = 0.0;
+  c.put(tid < M ? bv[tid] : 0.0);
 
   if constexpr (KEEP) {
     // ---- X = U^-1 column by column, thread r column r by back substitution: X[i][r] = -(sum_{i < j <= r} U[i][j] X[j][r]) / U[i][i]
@@ -333,7 +383,7 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin(FoldinArgs a) {
       }
     }
     __syncthreads();
-    foldin_keep_write(a.Wf + ((size_t)blockIdx.x * a.S_all + s) * foldin_keep_doubles(M), M, A, Z, bv);
+    foldin_keep_write(Wf, M, A, Z, bv);
   }
 }
 

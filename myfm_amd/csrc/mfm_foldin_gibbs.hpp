@@ -34,72 +34,44 @@ struct FoldinGibbsArgs {
   int64_t rows;       // rows of the launch's entities, eoff[u0 + gridDim.x] - eoff[u0]
 };
 
-// component j of the normals of (draw word, stream row)
-__device__ __forceinline__ double foldin_normal(uint64_t seed, uint64_t word, int64_t srow, int j) {
-  RowRng g(seed ^ ((uint64_t)(srow >> 32) * 0x9E3779B97F4A7C15ull), word, (uint32_t)srow);
-  g.n = (uint32_t)(j >> 1);
-  const double2 un = g.next2();
-  const double r = sqrt(-2.0 * log(un.x));
-  double sn, cs;
-  sincospi(2.0 * un.y, &sn, &cs);
-  return (j & 1) ? r * sn : r * cs;
-}
-
 template <int TASK, bool DRAW>
 __global__ __launch_bounds__(FOLDIN_WG) void k_foldin_gibbs(FoldinGibbsArgs ga) {
   extern __shared__ double foldin_smem[];
   const FoldinArgs &a = ga.a;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = a.K, off = a.lin, M = K + off, ldz = M | 1;
+  const FoldinCell c = foldin_cell(a);
+  const int off = c.off, M = c.M, ldz = M | 1;
   const int T = M * (M + 1) / 2;
   const int sweeps = ga.n_burn + ga.n_inner;
-  double *A = foldin_smem;                    // [M][M]: the Gram sums, Lambda, U, then W = U^-1 (upper) and W^T (lower)
-  double *bv = A + M * M;                     // [M]: b of the sweep
-  double *Z = bv + M;                         // [FOLDIN_ROWS][ldz]: the setup pass's z
-  double *res = Z + FOLDIN_ROWS * ldz;        // [FOLDIN_ROWS]: (the setup pass's flag of a non-finite f sits in its first word)
-  double *part = res + FOLDIN_ROWS;           // [2][4][FOLDIN_ROWS]
-  uint16_t *tab = (uint16_t *)(part + 2 * (FOLDIN_WG / 64) * FOLDIN_ROWS);  // [T]
-  // the sweeps' arrays lie over Z, res and part (5 M + 2 FOLDIN_WG <= 64 ldz + 64 + 512 doubles), which the setup pass is done with
-  double *theta = Z;                          // [M]
+  // A: the Gram sums, Lambda, U, then W = U^-1 (upper) and W^T (lower); bv: b of the sweep; res: in the setup pass only the flag
+  // of a non-finite f, in its first word
+  const auto [A, bv, res, Z, part, tab] = foldin_lds(foldin_smem, M);
+  // the sweeps' arrays lie over res, Z and part (5 M + 2 FOLDIN_WG <= 64 + 64 ldz + 512 doubles), which the setup pass is done with
+  double *theta = res;                        // [M]
   double *yv = theta + M;                     // [M]: W^T b
   double *ye = yv + M;                        // [M]: W^T b + eps
   double *lmu = ye + M;                       // [M]: lambda mu
   double *rl = lmu + M;                       // [FOLDIN_WG]: the pass's r
   double *pb = rl + FOLDIN_WG;                // [FOLDIN_WG]: the owners' partial sums of z r
 
-  const int64_t u = a.u0 + blockIdx.x;
-  const int sl = blockIdx.y, s = a.s0 + sl;
-  const double *__restrict__ w = a.wv[s];
-  const double *__restrict__ V = w + a.D;
-  const double *__restrict__ mu = a.mu + (size_t)s * (K + 1) + (1 - off);
-  const double *__restrict__ lam = a.lam + (size_t)s * (K + 1) + (1 - off);
-  const double w0 = a.w0[s];
-  const int64_t e0 = a.eoff[u], e1 = a.eoff[u + 1], nu = e1 - e0;
-  double *__restrict__ ow = a.out_w + (size_t)sl * gridDim.x + blockIdx.x;
-  double *__restrict__ oV = a.out_V + ((size_t)sl * gridDim.x + blockIdx.x) * K;
-  const int64_t srow = (int64_t)s * a.U + u;
+  const int s = c.s;
+  const double *mu = c.mu, *lam = c.lam;
+  const int64_t e0 = c.e0, e1 = c.e1, nu = e1 - e0, srow = c.srow;
 
   if (nu == 0) {  // no rows: the prior itself, mu bit for bit; a draw: the chain's last step from it
+    double t = 0.0;
     if (tid < M) {
-      double t = mu[tid];
+      t = mu[tid];
       if (DRAW) t = t + foldin_normal(a.seed, FOLDIN_DRAW_TAG + (uint64_t)sweeps, srow, tid) / sqrt(lam[tid]);
-      if (off && tid == 0)
-        *ow = t;
-      else
-        oV[tid - off] = t;
     }
-    if (!off && tid == 0) *ow = 0.0;
+    c.put(t);
     return;
   }
   // the cell's scratch: z^T [M][nu], then f [nu]
-  double *__restrict__ zT = ga.zf + ((size_t)sl * ga.rows + (size_t)(e0 - a.eoff[a.u0])) * (size_t)(M + 1);
+  double *__restrict__ zT = ga.zf + ((size_t)c.sl * ga.rows + (size_t)(e0 - a.eoff[a.u0])) * (size_t)(M + 1);
   double *__restrict__ fS = zT + (size_t)M * nu;
 
-  for (int t = tid; t < M * M; t += FOLDIN_WG) {
-    const int i = t / M, j = t - i * M;
-    A[t] = 0.0;
-    if (i <= j) tab[i * M - (i * (i - 1)) / 2 + (j - i)] = (uint16_t)(i | (j << 8));
-  }
+  foldin_gram_zero(A, tab, M);
   int *badf = (int *)res;
   if (tid == 0) *badf = 0;
   __syncthreads();
@@ -107,7 +79,7 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin_gibbs(FoldinGibbsArgs ga) 
   // ---- the setup pass: z and f of every row into the scratch, sum z z^T (upper triangle) row after row
   for (int64_t rb = e0; rb < e1; rb += FOLDIN_ROWS) {
     const int nr = (int)(e1 - rb < FOLDIN_ROWS ? e1 - rb : FOLDIN_ROWS);
-    const FoldinDD f = foldin_rows_zf(a, w, V, w0, rb, nr, Z, part);
+    const FoldinDD f = foldin_rows_zf(a, c.w, c.V, c.w0, rb, nr, Z, part);
     if (wave == 0) {
       if (lane < nr) {
         const double fv = f.hi + f.lo;
@@ -121,12 +93,7 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin_gibbs(FoldinGibbsArgs ga) 
       const int j = e / nr, r = e - j * nr;
       zT[(size_t)j * nu + (size_t)(rb - e0) + r] = Z[r * ldz + j];
     }
-    for (int e = tid; e < T; e += FOLDIN_WG) {
-      const int ij = tab[e], i = ij & 255, j = ij >> 8;
-      double acc = A[i * M + j];
-      for (int r = 0; r < nr; r++) acc = fma(Z[r * ldz + i], Z[r * ldz + j], acc);
-      A[i * M + j] = acc;
-    }
+    for (int e = tid; e < T; e += FOLDIN_WG) foldin_gram_add(A, tab, Z, M, e, nr);
     __syncthreads();
   }
 
@@ -135,36 +102,10 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin_gibbs(FoldinGibbsArgs ga) 
     const int ij = tab[e], i = ij & 255, j = ij >> 8;
     if (i == j) A[i * M + j] = lam[i] + A[i * M + j];
   }
-  bool bad = *badf != 0;
+  const bool badf_seen = *badf != 0;
   __syncthreads();
-
-  // ---- Lambda = U^T U in place (right-looking; every entry takes its updates in column order)
-  for (int j = 0; j < M && !bad; j++) {
-    const double d = A[j * M + j];  // (the same value in every thread: the exit is uniform)
-    if (!(d > 0.0) || !(d < INFINITY)) {
-      bad = true;
-      break;
-    }
-    const double piv = sqrt(d);
-    __syncthreads();
-    for (int i = j + tid; i < M; i += FOLDIN_WG) A[j * M + i] = i == j ? piv : A[j * M + i] / piv;
-    __syncthreads();
-    const int m = M - j - 1;
-    for (int t = tid; t < m * m; t += FOLDIN_WG) {
-      const int i = j + 1 + t / m, k = j + 1 + t % m;
-      if (i <= k) A[i * M + k] = fma(-A[j * M + i], A[j * M + k], A[i * M + k]);
-    }
-    __syncthreads();
-  }
-  if (bad) {  // a non-finite model value or a non-positive pivot: reported through the handle, never a NaN in the result
-    if (tid == 0) atomicOr(a.err, 1);
-    if (tid < M) {
-      if (off && tid == 0)
-        *ow = 0.0;
-      else
-        oV[tid - off] = 0.0;
-    }
-    if (!off && tid == 0) *ow = 0.0;
+  if (badf_seen || foldin_factor(A, M)) {  // a non-finite model value or a non-positive pivot
+    c.fail(a.err);
     return;
   }
 
@@ -258,14 +199,7 @@ __global__ __launch_bounds__(FOLDIN_WG) void k_foldin_gibbs(FoldinGibbsArgs ga) 
     }
     __syncthreads();
   }
-  if (tid < M) {
-    const double v = DRAW ? theta[tid] : mean / (double)ga.n_inner;
-    if (off && tid == 0)
-      *ow = v;
-    else
-      oV[tid - off] = v;
-  }
-  if (!off && tid == 0) *ow = 0.0;
+  c.put(!DRAW ? mean / (double)ga.n_inner : tid < M ? theta[tid] : 0.0);
 }
 
 }  // namespace mfm

@@ -1,5 +1,6 @@
 // mfm_foldin_gibbs_plan.hpp -- the host side of mfm_foldin_gibbs_* that needs no device (mfm_foldin_gibbs.hip): the
-// refusals made before any launch and the walk over (entity, sample) cells in chunks whose scratch stays under the handle's bound.
+// refusals made before any launch and the walk over (entity, sample) cells in chunks whose scratch stays under the handle's bound,
+// for the chain (foldin_gibbs_plan) and for the closed form of mfm_foldin.hip (foldin_chunks).
 // Plain C++ with no HIP header, so that a stand-alone program can run it under a host sanitizer.
 #pragma once
 #include <algorithm>
@@ -82,6 +83,19 @@ inline std::vector<FoldinChunk> foldin_gibbs_plan(const int64_t *eoff, int64_t U
     for (int s0 = 0; s0 < S; s0 += Sc) out.push_back(FoldinChunk{u0, 1, s0, std::min(Sc, S - s0)});
     u0++;
   }
+  return out;
+}
+
+// The chunks of a closed-form call (mfm_foldin.hip), in launch order. Its only scratch is the result, (K + 1) doubles per cell
+// whatever the entity's rows, so the chunks are blocks of one shape: whole sample ranges of as many entities as `bound` bytes hold;
+// below one entity's worth, ranges of samples; never less than one cell.
+inline std::vector<FoldinChunk> foldin_chunks(int64_t U, int S, int K, int64_t bound) {
+  std::vector<FoldinChunk> out;
+  const int64_t cells = std::max<int64_t>(bound / ((int64_t)(K + 1) * (int64_t)sizeof(double)), 1);
+  const int Sc = (int)std::min<int64_t>(S, cells);
+  const int64_t Uc = std::min<int64_t>({U, std::max<int64_t>(cells / Sc, 1), (int64_t)2147483647});
+  for (int64_t u0 = 0; u0 < U; u0 += Uc)
+    for (int s0 = 0; s0 < S; s0 += Sc) out.push_back(FoldinChunk{u0, std::min(Uc, U - u0), s0, std::min(Sc, S - s0)});
   return out;
 }
 

@@ -38,14 +38,6 @@ void split_stripes(int64_t n_tiles, int64_t steps_total, int64_t &n_stripes, int
   n_stripes = (steps_total + steps - 1) / steps;
 }
 
-template <class K>
-void raise_lds(K kernel, DeviceOnce &raised, int bytes) {
-  if (raised.need()) {
-    MFM_HIP_CHECK(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    raised.mark();
-  }
-}
-
 // the checks of a call that need neither samples nor a device
 void check_request(const mfm_foldin *p, const RankRequest &rq) {
   if (p->I < 0) throw Error(MFM_ERR_INVALID, "fold-in ranking: no candidates set (mfm_foldin_rank_set_candidates)");
@@ -63,7 +55,8 @@ void check_request(const mfm_foldin *p, const RankRequest &rq) {
 
 void run_rank(mfm_foldin *p, const SampleView &v, const double *alpha, const double *mu, const double *lam, const RankRequest &rq) {
   const int S = v.count(), K = v.K;
-  foldin_check_samples(p, v.device, v.D, K, S, FOLDIN_MAX_RANK, alpha, mu, lam);
+  foldin_check_samples(p, v);
+  foldin_check_hyper_arrays(alpha, mu, lam);
   const int off = p->lin ? 1 : 0, M = K + off;
   foldin_check_hypers(S, K, off, alpha, mu, lam);
   const int64_t U = p->U, I = p->I;
@@ -79,8 +72,6 @@ void run_rank(mfm_foldin *p, const SampleView &v, const double *alpha, const dou
     return;
   }
   hipStream_t st = p->stream;
-  if (v.pushed) MFM_HIP_CHECK(hipStreamWaitEvent(st, v.pushed, 0));
-
   const int KS4 = foldin_keep_ksteps(M), RT = foldin_keep_tiles(M);
   const int64_t Ipad = round_up(I, FRANK_STEP), W = (I + 31) / 32;
   const size_t opnd = foldin_keep_doubles(M), stage = frank_stage_doubles(KS4);
@@ -99,41 +90,14 @@ void run_rank(mfm_foldin *p, const SampleView &v, const double *alpha, const dou
                                        "candidates or fewer samples per call");
   }
 
-  DevBuf<const double *> d_wv;
-  DevBuf<double> d_w0, d_alpha, d_mu, d_lam, Zf, F;
-  DevBuf<int> d_err;
-  d_wv.upload(v.wv);
-  d_w0.upload(v.w0);
-  d_alpha.upload(alpha, (size_t)S);
-  d_mu.upload(mu, (size_t)S * (K + 1));
-  d_lam.upload(lam, (size_t)S * (K + 1));
-  d_err.alloc_zero(1, st);
+  const FoldinStaged staged(p, v, alpha, mu, lam);
 
   // ---- the candidate table
-  FoldinArgs fa;
-  fa.rowptr = p->c_ptr.p;
-  fa.colidx = p->c_idx.p;
-  fa.val = p->c_val.p;
-  fa.y = nullptr;
-  fa.eoff = nullptr;
-  fa.wv = (const double *const *)d_wv.p;
-  fa.w0 = d_w0.p;
-  fa.alpha = d_alpha.p;
-  fa.mu = d_mu.p;
-  fa.lam = d_lam.p;
-  fa.D = p->D;
-  fa.U = U;
-  fa.u0 = 0;
-  fa.s0 = 0;
-  fa.K = K;
-  fa.lin = off;
-  fa.seed = 0;
-  fa.out_w = fa.out_V = nullptr;
-  fa.err = d_err.p;
+  DevBuf<double> Zf, F;
   Zf.alloc(std::max<size_t>((size_t)S * (Ipad >> 4) * KS4 * 64, 1));
   F.alloc((size_t)S * Ipad);
   hipLaunchKernelGGL(k_foldin_rank_cand, dim3((unsigned)(Ipad / FOLDIN_ROWS), (unsigned)S), dim3(FOLDIN_WG),
-                     (size_t)(FOLDIN_ROWS * (M | 1) + 2 * (FOLDIN_WG / 64) * FOLDIN_ROWS) * sizeof(double), st, fa, I, Ipad, Zf.p, F.p);
+                     foldin_rows_lds_doubles(M) * sizeof(double), st, staged.args(0, true), I, Ipad, Zf.p, F.p);
   MFM_HIP_CHECK(hipGetLastError());
 
   // ---- the entity chunks
@@ -153,11 +117,7 @@ void run_rank(mfm_foldin *p, const SampleView &v, const double *alpha, const dou
   oV.alloc(std::max<size_t>((size_t)Uc * S * K, 1));
   for (int j = 0; j < (rq.dense ? 4 : 1); j++) d_out[j].alloc((size_t)Uc * I);
 
-  fa.rowptr = p->ptr.p;
-  fa.colidx = p->idx.p;
-  fa.val = p->val.p;
-  fa.y = p->y.p;
-  fa.eoff = p->eoff.p;
+  FoldinArgs fa = staged.args(0);
   fa.out_w = ow.p;
   fa.out_V = oV.p;
   fa.Wf = Wf.p;
@@ -167,7 +127,7 @@ void run_rank(mfm_foldin *p, const SampleView &v, const double *alpha, const dou
   ra.Wf = Wf.p;
   ra.Zf = Zf.p;
   ra.F = F.p;
-  ra.alpha = d_alpha.p;
+  ra.alpha = staged.alpha.p;
   ra.M = M;
   ra.KS4 = KS4;
   ra.RT = RT;
@@ -184,12 +144,12 @@ void run_rank(mfm_foldin *p, const SampleView &v, const double *alpha, const dou
   ra.value = d_out[0].p;
   const size_t tile_lds = (size_t)nbuf * stage * sizeof(double);
   static DeviceOnce raised_keep, raised_dense, raised_value, raised_select;
-  raise_lds(k_foldin<false, true>, raised_keep, (int)foldin_lds_bytes(FOLDIN_MAX_RANK + 1));
+  foldin_raise_lds(k_foldin<false, true>, raised_keep, (int)foldin_lds_bytes(FOLDIN_MAX_RANK + 1));
   if (rq.dense)
-    raise_lds(k_foldin_rank_tile<true>, raised_dense, lds_max);
+    foldin_raise_lds(k_foldin_rank_tile<true>, raised_dense, lds_max);
   else {
-    raise_lds(k_foldin_rank_tile<false>, raised_value, lds_max);
-    raise_lds(k_foldin_rank_select, raised_select, (int)PairsSel<1>::BYTES);
+    foldin_raise_lds(k_foldin_rank_tile<false>, raised_value, lds_max);
+    foldin_raise_lds(k_foldin_rank_select, raised_select, (int)PairsSel<1>::BYTES);
   }
 
   for (int64_t u0 = 0; u0 < U; u0 += Uc) {
@@ -262,12 +222,17 @@ void run_rank(mfm_foldin *p, const SampleView &v, const double *alpha, const dou
     MFM_HIP_CHECK(hipStreamSynchronize(st));
     for (size_t e = 0; e < n_e; e++) rq.idx[o + e] = h_idx[e];
   }
-  int h_err = 0;
-  MFM_HIP_CHECK(hipMemcpyAsync(&h_err, d_err.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  MFM_HIP_CHECK(hipStreamSynchronize(st));
-  if (h_err)
-    throw Error(MFM_ERR_INVALID, "fold-in ranking: a posterior precision matrix is not positive definite (a non-finite or non-positive "
-                                 "prior precision, noise precision or model value); no result is returned");
+  staged.finish("fold-in ranking: a posterior precision matrix is not positive definite (a non-finite or non-positive prior precision, "
+                "noise precision or model value); no result is returned");
+}
+
+// An entry point: the request's checks, which need neither samples nor a device, then the samples, then the call
+template <class From>
+int rank_call(mfm_foldin *p, const From &from, const double *alpha, const double *mu, const double *lam, const RankRequest &rq) {
+  return foldin_call(p, from, [&](auto samples) {
+    check_request(p, rq);
+    run_rank(p, samples(), alpha, mu, lam, rq);
+  });
 }
 
 RankRequest dense_request(double *mean, double *sd, double *sd_within, double *gain) {
@@ -291,15 +256,6 @@ RankRequest topk_request(int by, int k, double beta, int64_t *idx, double *value
   rq.sd = sd;
   rq.gain = gain;
   return rq;
-}
-
-void check_pattern(int64_t rows, int64_t cols, const int64_t *indptr, const int32_t *indices, const char *what) {
-  if (!indptr || (rows > 0 && indptr[rows] > 0 && !indices)) throw Error(MFM_ERR_INVALID, std::string(what) + ": no index arrays");
-  if (indptr[0] != 0) throw Error(MFM_ERR_INVALID, std::string(what) + ": indptr[0] must be 0");
-  for (int64_t i = 0; i < rows; i++)
-    if (indptr[i + 1] < indptr[i]) throw Error(MFM_ERR_INVALID, std::string(what) + ": indptr must be non-decreasing");
-  for (int64_t q = 0; q < indptr[rows]; q++)
-    if (indices[q] < 0 || indices[q] >= cols) throw Error(MFM_ERR_INVALID, std::string(what) + ": column index out of range");
 }
 
 }  // namespace
@@ -333,47 +289,25 @@ int mfm_foldin_rank_set_exclude(mfm_foldin *p, const int64_t *indptr, const int3
 
 int mfm_foldin_rank_dist_store(mfm_foldin *p, mfm_store *st, int32_t first, int32_t count, const double *alpha, const double *mu,
                                const double *lambda, double *mean, double *sd, double *sd_within, double *gain) {
-  FOLDIN_TRY(p)
-  const RankRequest rq = dense_request(mean, sd, sd_within, gain);
-  check_request(p, rq);
-  if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  run_rank(p, samples_of_store(st, first, count), alpha, mu, lambda, rq);
-  FOLDIN_CATCH(p)
+  return rank_call(p, FoldinFromStore{st, first, count}, alpha, mu, lambda, dense_request(mean, sd, sd_within, gain));
 }
 
 int mfm_foldin_rank_dist(mfm_foldin *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                          const double *alpha, const double *mu, const double *lambda, double *mean, double *sd, double *sd_within,
                          double *gain) {
-  FOLDIN_TRY(p)
-  const RankRequest rq = dense_request(mean, sd, sd_within, gain);
-  check_request(p, rq);
-  if (rank > FOLDIN_MAX_RANK)
-    throw Error(MFM_ERR_INVALID, "fold-in serves ranks up to " + std::to_string(FOLDIN_MAX_RANK) + ", the samples have rank " + std::to_string(rank));
-  run_rank(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), alpha, mu, lambda, rq);
-  FOLDIN_CATCH(p)
+  return rank_call(p, FoldinFromHost{rank, n_samples, w0s, ws, Vs}, alpha, mu, lambda, dense_request(mean, sd, sd_within, gain));
 }
 
 int mfm_foldin_rank_topk_store(mfm_foldin *p, mfm_store *st, int32_t first, int32_t count, const double *alpha, const double *mu,
                                const double *lambda, int32_t by, int32_t k, double beta, int64_t *idx, double *value, double *mean,
                                double *sd, double *gain) {
-  FOLDIN_TRY(p)
-  const RankRequest rq = topk_request(by, k, beta, idx, value, mean, sd, gain);
-  check_request(p, rq);
-  if (!st) throw Error(MFM_ERR_INVALID, "no sample store");
-  run_rank(p, samples_of_store(st, first, count), alpha, mu, lambda, rq);
-  FOLDIN_CATCH(p)
+  return rank_call(p, FoldinFromStore{st, first, count}, alpha, mu, lambda, topk_request(by, k, beta, idx, value, mean, sd, gain));
 }
 
 int mfm_foldin_rank_topk(mfm_foldin *p, int32_t rank, int32_t n_samples, const double *w0s, const double *ws, const double *Vs,
                          const double *alpha, const double *mu, const double *lambda, int32_t by, int32_t k, double beta, int64_t *idx,
                          double *value, double *mean, double *sd, double *gain) {
-  FOLDIN_TRY(p)
-  const RankRequest rq = topk_request(by, k, beta, idx, value, mean, sd, gain);
-  check_request(p, rq);
-  if (rank > FOLDIN_MAX_RANK)
-    throw Error(MFM_ERR_INVALID, "fold-in serves ranks up to " + std::to_string(FOLDIN_MAX_RANK) + ", the samples have rank " + std::to_string(rank));
-  run_rank(p, samples_of_host(p->device, p->D, rank, n_samples, w0s, ws, Vs), alpha, mu, lambda, rq);
-  FOLDIN_CATCH(p)
+  return rank_call(p, FoldinFromHost{rank, n_samples, w0s, ws, Vs}, alpha, mu, lambda, topk_request(by, k, beta, idx, value, mean, sd, gain));
 }
 
 }  // extern "C"

@@ -24,13 +24,13 @@ constexpr int FRANK_STEP = 256;  // candidates per workgroup step: 64 per wave, 
 // One workgroup per (64 candidates, sample): foldin_rows_zf forms z and the double-double f of the rows, exactly as for an entity's
 // observations; then z goes out in fragment order, Zf[s][c >> 4][k >> 2][(k & 3) * 16 + (c & 15)] (k = component, column =
 // candidate: lane l of the MFMA holds B[k l >> 4][col l & 15]), zeros for k >= M and c >= I, and f to F[s][c].
-// a: the candidates' CSR in rowptr / colidx / val, and wv, w0, D, K, lin. LDS: (64 (M | 1) + 512) doubles.
+// a: the candidates' CSR in rowptr / colidx / val, and wv, w0, D, K, lin. LDS: foldin_rows_lds_doubles(M).
 __global__ __launch_bounds__(FOLDIN_WG) void k_foldin_rank_cand(FoldinArgs a, int64_t I, int64_t Ipad, double *__restrict__ Zf,
                                                                 double *__restrict__ F) {
   extern __shared__ double frank_cand_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int off = a.lin, M = a.K + off, ldz = M | 1, KS4 = foldin_keep_ksteps(M);
-  double *Z = frank_cand_smem, *part = Z + FOLDIN_ROWS * ldz;
+  const auto [Z, part] = foldin_rows_lds(frank_cand_smem, M);
   const int s = blockIdx.y;
   const int64_t rb = (int64_t)blockIdx.x * FOLDIN_ROWS;
   const int nr = (int)(I - rb < 0 ? 0 : I - rb < FOLDIN_ROWS ? I - rb : FOLDIN_ROWS);

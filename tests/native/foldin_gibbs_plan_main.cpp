@@ -1,4 +1,4 @@
-// A stand-alone program around csrc/mfm_foldin_gibbs_plan.hpp, the host code of mfm_foldin_gibbs_* that needs no device: built with
+// A stand-alone program around csrc/mfm_foldin_gibbs_plan.hpp, the host code of the two fold-in solvers that needs no device: built with
 // -fsanitize=address,undefined by tests/test_fold_in_gibbs_cpu.py. Exit status 0 and "plan: ok", "check: ok" on success.
 #include "mfm_foldin_gibbs_plan.hpp"
 
@@ -16,6 +16,38 @@ using namespace mfm;
       return 1;                                                     \
     }                                                               \
   } while (0)
+
+// foldin_chunks, the closed form's walk (its scratch is the result alone, (K + 1) doubles per cell, whatever the entity's rows),
+// on the entity and sample counts of one case: bounds from one cell to more than the whole call
+static int closed_form_chunks(int64_t U, int S) {
+  for (int K : {0, 1, 64}) {
+    const int64_t cell = (int64_t)(K + 1) * 8;
+    const int64_t bounds[] = {1, cell, cell + 1, 2 * cell, S * cell - 1, S * cell, 3 * S * cell + 5, U * S * cell, U * S * cell + 1, (int64_t)256 << 20};
+    for (int64_t bound : bounds) {
+      const std::vector<FoldinChunk> chunks = foldin_chunks(U, S, K, bound);
+      // the sequence of the two nested loops that mfm_foldin.hip held before the chunks became a function
+      std::vector<FoldinChunk> want;
+      const int64_t cells = std::max<int64_t>(bound / ((int64_t)(K + 1) * (int64_t)sizeof(double)), 1);
+      const int Sc = (int)std::min<int64_t>(S, cells);
+      const int64_t Uc = std::min<int64_t>({U, std::max<int64_t>(cells / Sc, 1), (int64_t)2147483647});
+      for (int64_t u0 = 0; u0 < U; u0 += Uc)
+        for (int s0 = 0; s0 < S; s0 += Sc) want.push_back(FoldinChunk{u0, std::min(Uc, U - u0), s0, std::min(Sc, S - s0)});
+      REQUIRE(chunks.size() == want.size());
+      std::vector<int> seen((size_t)U * S, 0);
+      for (size_t i = 0; i < chunks.size(); i++) {
+        const FoldinChunk &c = chunks[i];
+        REQUIRE(c.u0 == want[i].u0 && c.nu == want[i].nu && c.s0 == want[i].s0 && c.ns == want[i].ns);
+        REQUIRE(c.nu >= 1 && c.ns >= 1 && c.u0 >= 0 && c.u0 + c.nu <= U && c.s0 >= 0 && c.s0 + c.ns <= S);
+        for (int64_t u = c.u0; u < c.u0 + c.nu; u++)
+          for (int s = c.s0; s < c.s0 + c.ns; s++) seen[(size_t)u * S + s]++;
+        if (c.nu * (int64_t)c.ns > 1) REQUIRE(c.ns * c.nu * cell <= bound);
+      }
+      for (int v : seen) REQUIRE(v == 1);
+      if (bound >= U * S * cell) REQUIRE(chunks.size() == 1);
+    }
+  }
+  return 0;
+}
 
 static int plan_cases() {
   std::mt19937_64 rng(7);
@@ -44,6 +76,7 @@ static int plan_cases() {
       for (int v : seen) REQUIRE(v == 1);
       if (bound == ((int64_t)256 << 20)) REQUIRE(chunks.size() == 1);
     }
+    if (closed_form_chunks(U, S) != 0) return 1;
   }
   std::printf("plan: ok\n");
   return 0;
